@@ -19,7 +19,9 @@ two headline workloads every row of the CPU baseline's sample.  A failed check a
 
 Rank 0 prints ONE JSON line (contract in the task statement) with two extra objects: "roofline" (algorithmic bytes /
 HIP-event kernel time vs 8 TB/s) and "cpu_baseline" (the reference's own spmvRowsBasicCSR from oracle/_ref, or the
-oracle port, timed on this box's host cores).
+oracle port, timed on this box's host cores).  The line stays under 8000 bytes: of the secondary workloads it holds a
+summary of c3 ("headline_c3"); the whole blocks (c3, c3b, c2, c4, structured) are logged on stderr as one JSON object
+after "[bench] secondary blocks:".  --dump-outputs DIR writes the timed path's y (dump_outputs).
 """
 import argparse
 import ctypes as C
@@ -76,7 +78,15 @@ def parse():
                         "box; the RCCL all-gather candidates are skipped and the timings mean nothing")
     p.add_argument("--force-dist", action="store_true",
                    help="run the multi-rank code path (process group, all-gather) even with --gpus 1; for rehearsal")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR", default="",
+                   help="after the timed steps, write the y = A.x of the timed path's last step (rank 0's full copy at N > 1) as "
+                        "DIR/y.npy, float64: the whole vector up to 4 Mi rows, else the rows of dump_rows(), a fixed seeded sample")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    if args.dump_outputs and args.only_structured:
+        p.error("--dump-outputs dumps the headline workload, which --only-structured does not run")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------- timing
@@ -159,6 +169,28 @@ def pick_launcher(api, torch, dm, x_ptr, y_ptr, requested, n_cols, eligible=None
         times[name] = (time.perf_counter() - t0) / 3 * 1e3
     best = min((n for n in times if not eligible or n in eligible), key=times.get)
     return best, times
+
+
+DUMP_ROWS_MAX = 4 << 20      # 32 MiB of float64: --dump-outputs stays under its 64 MB cap
+
+
+def dump_rows(n):
+    """the rows of an n-row y that --dump-outputs writes: None (all of them) up to DUMP_ROWS_MAX rows, else a sample
+    drawn with a fixed seed (sorted, distinct) -- the same rows in every run with the same arguments"""
+    import numpy as np
+    if n <= DUMP_ROWS_MAX:
+        return None
+    return np.unique(np.random.default_rng(20261015).integers(0, n, size=DUMP_ROWS_MAX))
+
+
+def dump_outputs(out_dir, y):
+    """y, the float64 device vector the timed path left, -> out_dir/y.npy (the rows of dump_rows)"""
+    import numpy as np
+    import torch
+    rows = dump_rows(y.numel())
+    part = y if rows is None else y[torch.from_numpy(rows).to(y.device)]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "y.npy"), part.cpu().numpy().astype(np.float64, copy=False))
 
 
 def lib_sha256(api):
@@ -601,11 +633,13 @@ def set_rows_variant(api, v):
     _ROWS_VARIANT[0] = v
 
 
-def measure_block(api, synth, torch, w, launcher, steps, warmup, candidates=None, cpu_rows=0):
+def measure_block(api, synth, torch, w, launcher, steps, warmup, candidates=None, cpu_rows=0, dump=""):
     """measure + check one workload; returns the block for the JSON line (with "parity", and "cpu_baseline" when
-    cpu_rows > 0).  A failed check aborts the bench."""
+    cpu_rows > 0).  A failed check aborts the bench.  `dump`: directory for the timed launcher's y (dump_outputs)."""
     res, ctx = measure_single(api, synth, torch, w, launcher, steps, warmup, candidates)
     y_t = ctx["y"]
+    if dump:                                         # before the selection checks below write into y_t
+        dump_outputs(dump, y_t)
     win = OracleWindows(synth, w, ctx["irp"], ctx["x_host"], ctx["lens"])
     parity = win.check(lambda a, b: y_t[a:b].cpu().numpy())
     if _Y_HASH[0]:
@@ -953,6 +987,15 @@ def measure_structured(api, synth, torch, args, steps, warmup, only=""):
     return out
 
 
+def brief(res):
+    """the figures of a measure_block() result that go into the result line"""
+    b = {k: res[k] for k in ("launcher", "ms_per_step", "gflops", "kernel_ms_avg", "hbm_gbps", "hbm_frac")}
+    b["parity_ok"] = res["parity"]["ok"]
+    if "cpu_baseline" in res:
+        b["cpu_baseline"] = {k: res["cpu_baseline"][k] for k in ("value", "unit", "cores", "kind")}
+    return b
+
+
 def emit(line):
     """The ONE JSON line goes to the real stdout (saved before RCCL could write its banner there)."""
     data = (json.dumps(line) + "\n").encode()
@@ -973,7 +1016,7 @@ def run_single(args, api, synth, torch, w):
               "extra_structured": measure_structured(api, synth, torch, args, min(steps, 10), min(warmup, 2), only=args.only_structured)})
         return
     res = measure_block(api, synth, torch, w, args.launcher, steps, warmup,
-                        cpu_rows=0 if args.no_cpu_baseline else args.cpu_sample_nnz)
+                        cpu_rows=0 if args.no_cpu_baseline else args.cpu_sample_nnz, dump=args.dump_outputs)
     extra = {}
     if not args.no_extra:
         for key in ("c3", "c3b", "c2"):
@@ -1021,10 +1064,11 @@ def run_single(args, api, synth, torch, w):
     if "cpu_baseline" in res:
         line["cpu_baseline"] = res["cpu_baseline"]
     if "c3" in extra:
-        line["headline_c3"] = extra["c3"]
-    for k in ("c3b", "c2", "c4", "structured"):
-        if k in extra:
-            line["extra_" + k] = extra[k]
+        line["headline_c3"] = brief(extra["c3"])
+    if extra:
+        # whole, the secondary blocks are ~50 kB: a reader that keeps only the last 8000 bytes of stdout could not parse
+        # the line any more, so they go to the log, as one JSON object after this tag
+        log("secondary blocks:", json.dumps({("headline_c3" if k == "c3" else "extra_" + k): v for k, v in extra.items()}))
     emit(line)
 
 
@@ -1246,6 +1290,8 @@ def run_multi(args, api, synth, torch, dist, w, world, rank, local):
     for per_step in evs:
         free_events(api, per_step)
     y = setup.y
+    if rank == 0 and args.dump_outputs:              # before the serial-order step below, which may reuse y's window
+        dump_outputs(args.dump_outputs, y)
     t = torch.tensor([wall, sum(kms) / len(kms)], dtype=torch.float64, device="cuda")
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     wall_max, kernel_ms_max = float(t[0]), float(t[1])

@@ -5,6 +5,7 @@
     restated): every HIP and OpenMP implementation must pass the 7e-4 gate;
   * spmvHipShardCSR/spmvHipSpMVSharded with nDev = 1, with and without RCCL."""
 import ctypes as C
+import hashlib
 import os
 import subprocess
 
@@ -206,7 +207,7 @@ def test_bench_spawns_its_own_ranks():
     assert line["parity"]["ok"] is True
 
 
-def test_serial_order_y_is_the_same_bits_on_one_rank_and_on_three():
+def test_serial_order_y_is_the_same_bits_on_one_rank_and_on_three(tmp_path):
     """The whole y of `hipSpMVRowsCSR` in its default (serial-order) variant, hashed: the 1-rank bench and a 3-rank
     shared-GPU rehearsal (three processes, each computing a third of the rows with whatever serial-order kernel its own
     selection picked, y assembled through the exchange) must produce byte-identical vectors ("gathered y
@@ -218,11 +219,35 @@ def test_serial_order_y_is_the_same_bits_on_one_rank_and_on_three():
     common = ["--workload", "c3", "--scale", "0.05", "--steps", "2", "--warmup", "1", "--launcher", "hipSpMVRowsCSR", "--variant", "2",
               "--y-hash", "--no-cpu-baseline", "--no-extra"]
     hashes = []
-    for extra in (["--gpus", "1"], ["--gpus", "3", "--rehearse-shared-gpu", "--exchange-budget", "20"]):
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra + common, capture_output=True, text=True, timeout=900,
-                           env=env, cwd=ROOT)
+    for i, extra in enumerate((["--gpus", "1"], ["--gpus", "3", "--rehearse-shared-gpu", "--exchange-budget", "20"])):
+        dump = tmp_path / f"dump{i}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra + common + ["--dump-outputs", str(dump)],
+                           capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
         assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
         line = json.loads([l for l in r.stdout.splitlines() if l.strip()][-1])
         assert line["parity"]["ok"] is True and len(line["y_sha256"]) == 64
         hashes.append(line["y_sha256"])
+        # --dump-outputs: the whole y of the timed path (500 k rows fit under the cap), the very bytes that were hashed
+        y = np.load(dump / "y.npy")
+        assert y.dtype == np.float64 and y.size == line["config"]["N"]
+        assert hashlib.sha256(y.tobytes()).hexdigest() == line["y_sha256"]
     assert hashes[0] == hashes[1]
+
+
+def test_bench_default_line_fits_and_dumps(tmp_path):
+    """The default bench (all secondary blocks) at 2 %: ONE JSON line on stdout short enough for a reader that keeps only
+    the last 8000 bytes, `steps` / `ms_per_step` as asked, and --dump-outputs writing the timed launcher's y."""
+    import json
+    import sys
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT",
+                                                              "TORCHELASTIC_RUN_ID", "GROUP_RANK", "LOCAL_WORLD_SIZE")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--scale", "0.02", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1 and len(lines[0]) < 8000, len(lines[0])
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["parity"]["ok"] is True
+    assert line["headline_c3"]["parity_ok"] is True and "secondary blocks:" in r.stderr
+    y = np.load(tmp_path / "y.npy")
+    assert y.dtype == np.float64 and y.size == line["config"]["N"] and not np.isnan(y).any()
