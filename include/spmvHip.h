@@ -105,10 +105,61 @@ int hipFreeSpmat(spmat* dMat);
  * callers that assemble matrices on the GPU.  The handle takes ownership of
  * nothing: the caller frees the arrays after hipFreeSpmat(). `irpBytes` is 4 or 8.
  * `hIRP` is the same row-pointer array on the host (needed for the row-block
- * analysis); it may be NULL, in which case it is downloaded. */
+ * analysis); it may be NULL, in which case it is downloaded.
+ * VALUES ARE A SNAPSHOT.  `dAS` is read at adopt (unit detection: spmvHipSetUnitValues) and copied into every private
+ * format built later (two-phase, stripes, SELL), which keep their copy.  `dAS` must therefore be complete on the device
+ * before this call (it runs on the null stream).  Rewriting `dAS` afterwards is NOT seen -- y then mixes old and new
+ * values -- until the caller says so with spmvHipValuesChanged(), or writes new values through spmvHipUpdateValues(). */
 int spmvHipAdoptCSR(spmat* dMat, ulong M, ulong N, ulong NZ,
                     const void* dIRP, int irpBytes, const uint32_t* dJA,
                     const double* dAS, const void* hIRP);
+
+/* ------------------------------------------------------ new values, same pattern */
+/* For iterative callers (Newton steps, time steps, parameter sweeps) whose values change while the sparsity pattern stays:
+ * what a handle costs to make -- upload, row-block analysis, the measured kernel selection of hipSpMVRowsCSR /
+ * hipSpMVWarpPerRowCSR, the private formats -- depends on the pattern only, and is kept.
+ *
+ * spmvHipUpdateValues: new values for `dMat`.  `AS` has the handle's value layout and is read from the host
+ * (asOnDevice = 0) or the device (asOnDevice = 1):
+ *   spMatCpyCSR / spmvHipAdoptCSR handle   NZ values in CSR order; copied into the handle's AS -- for an adopted handle
+ *                                          that is the caller's own dAS, which it handed over at adopt
+ *   spMatCpyELL / spMatCpyELLTransposed    the host ELL value array in the layout of the upload (row-major rows x slots,
+ *                                          or the transposed slots x rows); copied into the pitched device array
+ *   spmvHipCsrToEll handle                 REFUSED: it keeps no link to its source (update the source, convert again)
+ * spmvHipValuesChanged: the handle's own value array was rewritten on the device by the caller (an adopted dAS, or the
+ *   array published in dMat->AS); the formats and the unit detection re-read it.  Same refusals.
+ *
+ * KEPT across an update: IRP, JA, RL, the row blocks; every built format's index arrays in both of its forms; the form
+ * preferences (spmvHipBuild*Opt); the kernel selections (spmvHipAutoChoice[Rows]) -- a launch after the update runs the
+ * same kernel as before, so the reduction-order name gives the same bits for the same values; every device address.
+ * REFRESHED: AS, the unit detection (spmvHipUnitValue; off with spmvHipSetUnitValues(0)), and the value array of every
+ * format that has been built, in every form.  Formats not built stay unbuilt.  The two-phase and the stripes format keep
+ * a map from their storage order to CSR order for this (4 B per entry and form, reported in spmvHip*Bytes, freed with the
+ * format); it is built at the format's FIRST update, never before -- a handle that is never updated costs nothing more.
+ * NaN and Inf are values like any other.
+ * Unit transitions ("all stored values equal", spmvHipSetUnitValues): unit -> unit with another value changes only the
+ * value the kernels take from a register; non-unit -> unit switches to the unit kernels (y unchanged: c * x rounds as
+ * AS[j] * x does); unit -> non-unit rebuilds, with its recorded options, a stripes format that was built without a value
+ * array, and forgets both kernel selections (their measurements counted the bytes of the unit kernels): the next call of
+ * each name measures again.
+ * spmvUpdateInfo (spmvHipLastUpdateInfo, the handle's last update): inPlace = 1 when every launch captured before the
+ * update (a HIP graph) computes with the new values as it stands: same kernels, same arguments, refreshed arrays at their
+ * old addresses -- 0 after a unit transition other than non-unit -> unit, or when a format was rebuilt (rebuilt = 1: its
+ * addresses changed).  mapsBuilt = value maps built by this call, mapMs their build time, ms the whole call (host wall
+ * time), unitBefore / unitAfter the unit detection around it.
+ * Streams: everything is enqueued on the library stream (spmvHipSetStream) and the call returns with the values in place,
+ * like the other synchronous calls.  The unit detection reads one word back (and a first build of a map, or a rebuild,
+ * synchronises the device).  A device `AS` -- and for ValuesChanged the handle's own array -- must be complete on that
+ * stream before the call.  Launches already enqueued on other streams that read this handle must be finished by the caller.
+ * Refused with a message and EXIT_FAILURE, the handle left as it was: NULL handle or AS, something that is not a live
+ * handle (never made, or freed), a derived ELL handle. */
+typedef struct {
+    int    inPlace, rebuilt, mapsBuilt, unitBefore, unitAfter;
+    double ms, mapMs;
+} spmvUpdateInfo;
+int spmvHipUpdateValues(spmat* dMat, const double* AS, int asOnDevice);
+int spmvHipValuesChanged(spmat* dMat);
+int spmvHipLastUpdateInfo(spmat* dMat, spmvUpdateInfo* info);
 
 /* --------------------------------------------------------------- SpMV on GPU */
 /* y = A x with A, x, y resident on the device.  (mat, x, CONFIG by value, y):
@@ -319,6 +370,10 @@ int spmvHipShardCSRGroups(spmat* host, int nDev, int groups, void** shardHandle)
 int spmvHipSpMVSharded(void* shardHandle, const double* hX, int mode, double* hY,
                        double* kernelSec, double* gatherSec);
 int spmvHipShardFree(void* shardHandle);
+/* New values for a sharded matrix of the same pattern: `hAS` (host) holds the WHOLE matrix's NZ values in CSR order; every
+ * row block gets its slice and is updated on its own device (spmvHipUpdateValues, on that device's compute stream), the
+ * per-block kernel selections stay.  Refused: NULL, a handle that is not a live shard (freed with spmvHipShardFree). */
+int spmvHipShardUpdateValues(void* shardHandle, const double* hAS);
 
 /* ------------------------------------ peer windows: one process per GPU, xGMI */
 /* bench.py's layout (one process per GPU) exchanges y with RCCL by default.  xGMI

@@ -95,6 +95,8 @@ _sigs = {
     "spmvHipTilesPushJoin": ([], _i),
     "spmvHipBuildTilesOpt": ([C.POINTER(spmat), _vp], _i), "spmvHipTilesInfo": ([C.POINTER(spmat), _vp], _i),
     "spmvHipTilesBinRow": ([C.POINTER(spmat), C.c_uint, C.POINTER(C.c_ulong)], _i),
+    "spmvHipUpdateValues": ([C.POINTER(spmat), _vp, _i], _i), "spmvHipValuesChanged": ([C.POINTER(spmat)], _i),
+    "spmvHipLastUpdateInfo": ([C.POINTER(spmat), _vp], _i), "spmvHipShardUpdateValues": ([_vp, _vp], _i),
 }
 
 
@@ -123,6 +125,12 @@ class spmvStripesOpts(C.Structure):
 class spmvStripesInfo(C.Structure):
     _fields_ = [("nBins", C.c_uint), ("rowsPerBin", C.c_uint), ("grid", C.c_uint), ("spread", C.c_uint), ("wide", _i),
                 ("deterministic", _i), ("buildMs", C.c_double), ("bytes", _sz)]
+
+
+class spmvUpdateInfo(C.Structure):
+    """include/spmvHip.h `spmvUpdateInfo`: what the last value update of a handle did."""
+    _fields_ = [("inPlace", _i), ("rebuilt", _i), ("mapsBuilt", _i), ("unitBefore", _i), ("unitAfter", _i),
+                ("ms", C.c_double), ("mapMs", C.c_double)]
 
 
 IPC_HANDLE_BYTES = 64
@@ -341,6 +349,36 @@ class DeviceMatrix:
         self.handle = spmat()
         self.keep = []
         self.rows = 0
+
+    def update_values(self, AS, on_device=False):
+        """spmvHipUpdateValues: new values for the same pattern, in the handle's value layout (CSR: NZ values in CSR order;
+        uploaded ELL: the host ELL value array of the upload).  AS: a numpy array (host), a float64 torch tensor (read
+        where it lives) or a raw device pointer (int / c_void_p, with on_device=True)."""
+        try:
+            import torch
+        except ImportError:                              # (numpy arrays and raw pointers need no torch)
+            torch = None
+        keep = None
+        if torch is not None and isinstance(AS, torch.Tensor):
+            if AS.dtype != torch.float64 or not AS.is_contiguous():
+                raise SpmvHipError("update_values: the tensor must be contiguous float64")
+            ptr, on_device = C.c_void_p(AS.data_ptr()), AS.is_cuda
+        elif isinstance(AS, np.ndarray):
+            keep = np.ascontiguousarray(AS, dtype=np.float64)
+            ptr, on_device = _ptr(keep), False
+        else:
+            ptr = AS if isinstance(AS, C.c_void_p) else C.c_void_p(int(AS))
+        _check(lib.spmvHipUpdateValues(C.byref(self.handle), ptr, 1 if on_device else 0), "spmvHipUpdateValues")
+
+    def values_changed(self):
+        """spmvHipValuesChanged: the handle's own value array (an adopted dAS) was rewritten on the device."""
+        _check(lib.spmvHipValuesChanged(C.byref(self.handle)), "spmvHipValuesChanged")
+
+    def update_info(self) -> "spmvUpdateInfo":
+        """spmvHipLastUpdateInfo: what the last update_values / values_changed did."""
+        info = spmvUpdateInfo()
+        _check(lib.spmvHipLastUpdateInfo(C.byref(self.handle), C.byref(info)), "spmvHipLastUpdateInfo")
+        return info
 
     def free(self):
         if self.handle.dev:

@@ -4,6 +4,7 @@
 // src/main.cu:221-238 and test/SpMV_test.cu:103-146.
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <chrono>
 #include <cstring>
 #include <map>
 #include <vector>
@@ -277,16 +278,17 @@ __global__ __launch_bounds__(256) void ell_values_differ_kernel(uint64_t rows, s
 }
 
 // ... for an ELL upload that has row lengths; `first` = the bits of any real cell (found on the host side of the upload)
-static int detectUnitValuesEll(DevMat* d, bool anyCell, uint64_t first) {
+static int detectUnitValuesEll(DevMat* d, bool anyCell, uint64_t first, hipStream_t st = nullptr) {
     d->unit = false;
     if (!S.unitValues || !anyCell || !d->RL || !d->AS || d->M == 0) return EXIT_SUCCESS;
     uint32_t differ = 1, *dFlag = nullptr;
     HIP_TRY(hipMalloc(&dFlag, 4));
     int rc = EXIT_FAILURE;
-    if (hipOk(hipMemset(dFlag, 0, 4), "hipMemset")) {
-        hipLaunchKernelGGL(ell_values_differ_kernel, grid2d((d->M + 255) / 256, 256), dim3(256), 0, nullptr, d->M, d->pitch,
+    if (hipOk(hipMemsetAsync(dFlag, 0, 4, st), "hipMemset")) {
+        hipLaunchKernelGGL(ell_values_differ_kernel, grid2d((d->M + 255) / 256, 256), dim3(256), 0, st, d->M, d->pitch,
                            d->kind == Kind::ELL_COLMAJOR ? 1 : 0, reinterpret_cast<const uint64_t*>(d->AS), d->RL, first, dFlag);
-        if (hipOk(hipGetLastError(), "ell_values_differ_kernel") && hipOk(hipMemcpy(&differ, dFlag, 4, hipMemcpyDeviceToHost), "hipMemcpy")) rc = EXIT_SUCCESS;
+        if (hipOk(hipGetLastError(), "ell_values_differ_kernel") && hipOk(hipMemcpyAsync(&differ, dFlag, 4, hipMemcpyDeviceToHost, st), "hipMemcpy") &&
+            hipOk(hipStreamSynchronize(st), "hipStreamSynchronize")) rc = EXIT_SUCCESS;
     }
     (void)hipFree(dFlag);
     if (rc == EXIT_SUCCESS && !differ) { d->unit = true; memcpy(&d->unitValue, &first, 8); }
@@ -294,18 +296,20 @@ static int detectUnitValuesEll(DevMat* d, bool anyCell, uint64_t first) {
 }
 
 // sets d->unit / d->unitValue from the uploaded values (one pass over AS at upload; off with spmvHipSetUnitValues(0))
-static int detectUnitValues(DevMat* d) {
+static int detectUnitValues(DevMat* d, hipStream_t st = nullptr) {
     d->unit = false;
     if (!S.unitValues || d->NZ == 0 || !d->AS) return EXIT_SUCCESS;
     uint64_t first = 0;
     uint32_t differ = 1, *dFlag = nullptr;
-    HIP_TRY(hipMemcpy(&first, d->AS, 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpyAsync(&first, d->AS, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     HIP_TRY(hipMalloc(&dFlag, 4));
     int rc = EXIT_FAILURE;
-    if (hipOk(hipMemset(dFlag, 0, 4), "hipMemset")) {
+    if (hipOk(hipMemsetAsync(dFlag, 0, 4, st), "hipMemset")) {
         const uint64_t blocks = std::min<uint64_t>((d->NZ + 255) / 256, 256 * 64);
-        hipLaunchKernelGGL(values_differ_kernel, grid2d(blocks, 256), dim3(256), 0, nullptr, reinterpret_cast<const uint64_t*>(d->AS), d->NZ, first, dFlag);
-        if (hipOk(hipGetLastError(), "values_differ_kernel") && hipOk(hipMemcpy(&differ, dFlag, 4, hipMemcpyDeviceToHost), "hipMemcpy")) rc = EXIT_SUCCESS;
+        hipLaunchKernelGGL(values_differ_kernel, grid2d(blocks, 256), dim3(256), 0, st, reinterpret_cast<const uint64_t*>(d->AS), d->NZ, first, dFlag);
+        if (hipOk(hipGetLastError(), "values_differ_kernel") && hipOk(hipMemcpyAsync(&differ, dFlag, 4, hipMemcpyDeviceToHost, st), "hipMemcpy") &&
+            hipOk(hipStreamSynchronize(st), "hipStreamSynchronize")) rc = EXIT_SUCCESS;
     }
     (void)hipFree(dFlag);
     if (rc == EXIT_SUCCESS && !differ) { d->unit = true; memcpy(&d->unitValue, &first, 8); }
@@ -387,6 +391,11 @@ static int ellUpload(spmat* m, spmat* dst, bool transposed) {
     if (transposed) rc = uploadPitched(d, m->JA, m->AS, slots, rows, (rows + 63) / 64 * 64, colLimit);
     else            rc = uploadPitched(d, m->JA, m->AS, rows, slots, (slots + 1) / 2 * 2, colLimit);   // (rows stay 16-B aligned; a wider pitch is only padding to stream)
     if (!rc && m->RL) rc = narrowUpload<uint32_t>(&d->RL, m->RL, rows, slots, "RL");
+    if (!rc && m->RL) {                                // (kept for the unit detection of a value update)
+        ulong r = 0;
+        while (r < rows && m->RL[r] == 0) ++r;
+        if (r < rows) d->ellFirstRow = r;
+    }
     if (!rc && m->RL && S.unitValues) {                // first real cell on the host: slot 0 of the first non-empty row
         ulong r = 0;
         while (r < rows && m->RL[r] == 0) ++r;
@@ -456,7 +465,75 @@ int hostCall(spmat* mat, double* x, CONFIG* cfg, double* y, int kind, SPMV_HIP_I
 }  // namespace
 
 
-namespace spmvhip { hipStream_t libraryStream() { return S.stream; } }
+namespace spmvhip {
+hipStream_t libraryStream() { return S.stream; }
+
+// spmvHipUpdateValues / spmvHipValuesChanged (reread: the handle's own AS was rewritten) / spmvHipShardUpdateValues (its
+// per-device stream): the contract is in spmvHip.h, the design in DESIGN.md section 14
+int updateValues(spmat* h, const double* AS, bool onDevice, bool reread, hipStream_t st, const char* who) {
+    if (!ready(who)) return EXIT_FAILURE;
+    DevMat* d = descOf(h, who);
+    if (!d) return EXIT_FAILURE;
+    if (!reread && !AS) { ERR("%s: AS is NULL", who); return EXIT_FAILURE; }
+    if (d->derived) {
+        ERR("%s: this ELL handle was made on the device from a CSR handle (spmvHipCsrToEll) and keeps no link to it: "
+            "update the CSR handle and convert again", who);
+        return EXIT_FAILURE;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    spmvUpdateInfo info{};
+    info.unitBefore = d->unit;
+    const double valueBefore = d->unitValue;
+    const hipMemcpyKind kind = onDevice ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    if (d->kind == Kind::CSR) {
+        if (!reread && d->NZ) HIP_TRY(hipMemcpyAsync(d->AS, AS, d->NZ * sizeof(double), kind, st));
+        if (detectUnitValues(d, st)) return EXIT_FAILURE;
+        // every built format, both forms.  When the values were unit before and are unit now no kernel reads a value array
+        // (SELL has no unit kernel): only the value in the registers changes.  A stripes format built for a unit matrix has
+        // no value array: it is rebuilt, with its recorded options, when the values stop being unit.
+        const bool arrays = !(info.unitBefore && d->unit);
+        for (TileFormat* t : {d->tiles, d->tilesAlt})
+            if (t && arrays && tilesRefreshValues(d, t, st, &info.mapMs, &info.mapsBuilt)) return EXIT_FAILURE;
+        std::vector<spmvStripesOpts> rebuild;
+        for (StripeFormat* f : {d->stripes, d->stripesAlt}) {
+            if (!f) continue;
+            if (!stripesHasValues(f) && !d->unit) { rebuild.push_back(stripesOptions(f)); continue; }
+            if (stripesHasValues(f) && arrays && stripesRefreshValues(d, f, st, &info.mapMs, &info.mapsBuilt)) return EXIT_FAILURE;
+            stripesSetUnit(f, d->unit, d->unitValue);
+        }
+        if (sellRefreshValues(d, st)) return EXIT_FAILURE;
+        if (!rebuild.empty()) {
+            HIP_TRY(hipStreamSynchronize(st));           // the builds run on the null stream from AS
+            for (const spmvStripesOpts& o : rebuild)
+                if (buildStripes(d, &o)) { ERR("%s: rebuilding the stripes format failed", who); return EXIT_FAILURE; }
+            info.rebuilt = 1;
+        }
+        if (info.unitBefore && !d->unit) {               // the selections measured the byte counts of the unit kernels
+            d->autoPick[0] = d->autoPick[1] = -1;
+            memset(d->autoMs, 0, sizeof d->autoMs);
+        }
+    } else {
+        const bool colMajor = d->kind == Kind::ELL_COLMAJOR;
+        const size_t nRows = colMajor ? d->K : d->M, nCols = colMajor ? d->M : d->K;      // the host layout of the upload
+        if (!reread && nRows && nCols)
+            HIP_TRY(hipMemcpy2DAsync(d->AS, d->pitch * sizeof(double), AS, nCols * sizeof(double), nCols * sizeof(double), nRows, kind, st));
+        const bool anyCell = d->RL && d->ellFirstRow != ~0ull;
+        uint64_t first = 0;
+        if (anyCell && S.unitValues) {
+            HIP_TRY(hipMemcpyAsync(&first, d->AS + (colMajor ? d->ellFirstRow : d->ellFirstRow * d->pitch), 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+        }
+        if (detectUnitValuesEll(d, anyCell, first, st)) return EXIT_FAILURE;
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    info.unitAfter = d->unit;
+    const bool sameUnit = info.unitBefore && d->unit && memcmp(&valueBefore, &d->unitValue, 8) == 0;
+    info.inPlace = !info.rebuilt && (!info.unitBefore || sameUnit);
+    info.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    d->lastUpdate = info;
+    return EXIT_SUCCESS;
+}
+}  // namespace spmvhip
 
 extern "C" {
 
@@ -670,6 +747,7 @@ int spmvHipCsrToEll(spmat* dCsr, int transposed, spmat* dEll) {
     const uint64_t K = c->maxRowNnz, rows = c->M;
     DevMat* d = new DevMat;
     d->kind = transposed ? Kind::ELL_COLMAJOR : Kind::ELL_ROWMAJOR;
+    d->derived = true;
     d->M = rows; d->N = c->N; d->NZ = c->NZ; d->K = K;
     d->pitch = transposed ? (rows + 63) / 64 * 64 : (K + 1) / 2 * 2;
     const size_t cells = std::max<size_t>((transposed ? K : rows) * d->pitch, 1);
@@ -707,6 +785,17 @@ int spmvHipCsrToEll(spmat* dCsr, int transposed, spmat* dEll) {
     // handle fields follow the reference's conventions (transposed: M = slots, MAX_ROW_NZ = rows)
     if (transposed) publish(dEll, d, K, rows, c->NZ, rows);
     else            publish(dEll, d, rows, c->N, c->NZ, K);
+    return EXIT_SUCCESS;
+}
+
+int spmvHipUpdateValues(spmat* dMat, const double* AS, int asOnDevice) {
+    return updateValues(dMat, AS, asOnDevice != 0, false, S.stream, "spmvHipUpdateValues");
+}
+int spmvHipValuesChanged(spmat* dMat) { return updateValues(dMat, nullptr, true, true, S.stream, "spmvHipValuesChanged"); }
+int spmvHipLastUpdateInfo(spmat* dMat, spmvUpdateInfo* info) {
+    DevMat* d = descOf(dMat, "spmvHipLastUpdateInfo");
+    if (!d || !info) return EXIT_FAILURE;
+    *info = d->lastUpdate;
     return EXIT_SUCCESS;
 }
 

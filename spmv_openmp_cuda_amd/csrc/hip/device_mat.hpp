@@ -42,6 +42,8 @@ struct DevMat {
     uint32_t* RL  = nullptr;
     size_t    pitch = 0;            // ELL pitch in elements (same for JA and AS)
     bool      owns = true;          // false for adopted arrays
+    bool      derived = false;      // ELL made on the device from a CSR handle (spmvHipCsrToEll): its values cannot be updated
+    uint64_t  ellFirstRow = ~0ull;  // ELL with row lengths: first row that holds an entry (unit detection after a value update)
     // every stored value is the same double (MatrixMarket `pattern` files are loaded as all 1.0 -- the graphs of the
     // reference's report, asia_osm and channel-500x100x100, are such files): found at upload; the CSR kernels then take
     // the value from a register instead of streaming 8 B per entry.  c * x[j] rounds exactly as AS[j] * x[j] does.
@@ -66,6 +68,7 @@ struct DevMat {
     // serial-order kernels (hipSpMVRowsCSR): index of the launcher chosen for this matrix (-1: not chosen yet) ...
     int       autoPick[2] = {-1, -1};
     float     autoMs[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};    // ... and what each candidate took (0 = not tried)
+    spmvUpdateInfo lastUpdate{};    // what the last spmvHipUpdateValues / spmvHipValuesChanged did
 };
 
 int  buildSell(DevMat* d);                                      // sell.hip
@@ -97,6 +100,22 @@ uint32_t tilesPhase2Threads(const DevMat* d);                   // workgroup siz
 uint64_t tilesBinRow(const DevMat* d, uint32_t bin);
 hipStream_t libraryStream();                                    // abi.hip: the stream set with spmvHipSetStream
 size_t tilesBytes(const DevMat* d);
+
+// Value refresh (values.hip and the format files).  Each format rewrites its value array from the handle's CSR `AS`
+// (already updated) on `stream`; the map from storage to CSR order is built at a format's first refresh (*mapMs grows by
+// its build time).  Index arrays, tables and addresses stay as they are.
+int  tilesRefreshValues(DevMat* d, TileFormat* t, hipStream_t stream, double* mapMs, int* mapsBuilt);       // tiles.hip
+int  stripesRefreshValues(DevMat* d, StripeFormat* f, hipStream_t stream, double* mapMs, int* mapsBuilt);   // stripes.hip
+bool stripesHasValues(const StripeFormat* f);                  // false: built for a unit matrix, no value array to refresh
+spmvStripesOpts stripesOptions(const StripeFormat* f);          // what the format was built with
+void stripesSetUnit(StripeFormat* f, bool unit, double value);
+int  sellRefreshValues(DevMat* d, hipStream_t stream);          // sell.hip
+int  enqueueGatherValues(double* val, const uint32_t* map, uint64_t n, const double* AS, hipStream_t stream);   // values.hip
+int  enqueueScatterValues(double* val, const uint32_t* map, uint64_t n, const double* AS, hipStream_t stream);
+int  enqueueSellValues(uint32_t nSlices, const uint64_t* sliceOff, const uint32_t* perm, const uint32_t* slen, const void* IRP,
+                       int irpBytes, const double* AS, double* val, hipStream_t stream);
+int  updateValues(spmat* h, const double* AS, bool onDevice, bool reread, hipStream_t stream, const char* who);   // abi.hip
+constexpr uint32_t VMAP_NONE = 0xFFFFFFFFu;                    // map entry of a padding cell (value 0.0); nnz < 2^32 - 65536
 
 // Fold `blocks` workgroups into an (x, y) grid whose x extent keeps
 // x * threads < 2^32 (AQL grid_size is 32-bit work-items per dimension).

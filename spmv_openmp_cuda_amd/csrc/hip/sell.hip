@@ -272,6 +272,13 @@ int buildSell(DevMat* d) {
 
 size_t sellBytes(const DevMat* d) { return d->sell ? d->sell->bytes : 0; }
 
+// new values (same pattern): the slices' values rewritten from the handle's AS; the long rows read AS themselves
+int sellRefreshValues(DevMat* d, hipStream_t stream) {
+    const SellFormat* f = d->sell;
+    if (!f) return EXIT_SUCCESS;
+    return enqueueSellValues(f->nSlices, f->sliceOff, f->perm, f->slen, d->IRP, d->irpBytes, d->AS, f->val, stream);
+}
+
 int enqueueSell(DevMat* d, const double* x, double* y, hipStream_t stream) {
     SellFormat* f = d->sell;
     if (!f) return EXIT_FAILURE;

@@ -20,6 +20,7 @@
 #include <dlfcn.h>
 #include <algorithm>
 #include <cstring>
+#include <set>
 #include <vector>
 
 #include "spmvHip.h"
@@ -79,6 +80,9 @@ struct Shard {
     ulong hi(int d, int g) const { return bounds[(size_t)d * G + g + 1]; }
 };
 
+// the shard objects alive in this process: a freed (or never made) handle is refused instead of dereferenced
+std::set<const Shard*> g_liveShards;
+
 #define NCCL_TRY(expr) do { ncclResult_t r_ = (expr); if (r_ != 0) { fprintf(stderr, "libspmvhip: %s: %s\n", #expr, rccl.GetErrorString(r_)); return EXIT_FAILURE; } } while (0)
 
 int shardStep(Shard* sh, const double* hX, int mode, bool timed) {
@@ -128,6 +132,7 @@ int spmvHipShardFree(void* handle) {
     Shard* sh = static_cast<Shard*>(handle);
     if (!sh) return EXIT_SUCCESS;
     DeviceGuard guard;
+    g_liveShards.erase(sh);
     for (int d = 0; d < sh->nDev; ++d) {
         (void)hipSetDevice(d);
         for (int g = 0; g < sh->G; ++g) {
@@ -198,11 +203,31 @@ int spmvHipShardCSRGroups(spmat* host, int nDev, int groups, void** shardHandle)
         }
     }
     if (rc) { spmvHipShardFree(sh); return EXIT_FAILURE; }
+    g_liveShards.insert(sh);
     *shardHandle = sh;
     return EXIT_SUCCESS;
 }
 
 int spmvHipShardCSR(spmat* host, int nDev, void** shardHandle) { return spmvHipShardCSRGroups(host, nDev, 0, shardHandle); }
+
+// the whole matrix's values in CSR order: block k (device k / G, group k % G) holds rows bounds[k]..bounds[k+1], i.e. the
+// values after those of the blocks before it; each block is updated on its device's compute stream, the selections stay
+int spmvHipShardUpdateValues(void* handle, const double* hAS) {
+    Shard* sh = static_cast<Shard*>(handle);
+    if (!sh || !hAS) { fprintf(stderr, "libspmvhip: spmvHipShardUpdateValues: %s is NULL\n", sh ? "AS" : "the shard handle"); return EXIT_FAILURE; }
+    if (!g_liveShards.count(sh)) { fprintf(stderr, "libspmvhip: spmvHipShardUpdateValues: not a live shard handle (freed?)\n"); return EXIT_FAILURE; }
+    DeviceGuard guard;
+    size_t off = 0;
+    for (int d = 0; d < sh->nDev; ++d) {
+        HIP_TRY(hipSetDevice(d));
+        for (int g = 0; g < sh->G; ++g) {
+            spmat& m = sh->mats[(size_t)d * sh->G + g];
+            if (spmvhip::updateValues(&m, hAS + off, false, false, sh->compute[d], "spmvHipShardUpdateValues")) return EXIT_FAILURE;
+            off += m.NZ;
+        }
+    }
+    return EXIT_SUCCESS;
+}
 
 // mode: 0 = hipSpMVRowsCSR (serial order, bit-identical to the 1-GPU y), != 0 = hipSpMVWarpPerRowCSR (the fastest
 // reduction-order kernel per block; chosen by an untimed pass at the first call)

@@ -55,6 +55,7 @@
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <algorithm>
+#include <chrono>
 #include <vector>
 
 #include "spmvHip.h"
@@ -90,6 +91,7 @@ struct StripeFormat {
     size_t    bytes = 0;
     double    buildMs = 0;
     spmvStripesOpts opts{0, 0, -1, -1, 0};          // what the format was built with (0 / -1 = automatic)
+    uint32_t* vmap = nullptr;                       // value map: cell -> CSR position, VMAP_NONE for padding (built at the first value update)
 };
 
 namespace {
@@ -138,6 +140,16 @@ __global__ __launch_bounds__(256) void sb_bounds_kernel(uint64_t nnz, unsigned c
         for (uint64_t u = g + 1; u <= nGroups; ++u) start[u] = nnz;
 }
 
+// cell of the entry at position `pos` of a sub-stream whose first step is `firstStep`: inside a step the 128 column-ordered
+// entries are dealt to the lanes as (e, 64 + e) -- lane l reads the pair at positions 2l, 2l + 1 with one 16-byte load, and
+// each of the step's two gather instructions covers 64 NEIGHBOURING entries (lanes share lines inside an instruction; the two
+// instructions touch different lines -- with (2l, 2l + 1) pairs the second gather hit lines still pending from the first and
+// stalled the L1: TCP_PENDING_STALL_CYCLES)
+__device__ __forceinline__ uint64_t sb_cell(uint64_t pos, uint32_t firstStep) {
+    const uint64_t e = pos % SB_STEP;
+    return (uint64_t)firstStep * SB_STEP + (pos - e) + (e < SB_STEP / 2 ? 2 * e : 2 * (e - SB_STEP / 2) + 1);
+}
+
 // sorted position p -> padded position q of its sub-stream; values, encoded columns / rows, step bases
 template <bool WIDE>
 __global__ __launch_bounds__(256) void sb_scatter_kernel(
@@ -153,12 +165,8 @@ __global__ __launch_bounds__(256) void sb_scatter_kernel(
     const uint32_t bin = (uint32_t)(group / subs);
     const uint32_t col = (uint32_t)(key & ((1ull << colBits) - 1));
     const uint64_t pos = p - start[group];
-    // inside a step the 128 column-ordered entries are dealt to the lanes as (e, 64 + e): lane l reads the pair at
-    // positions 2l, 2l + 1 with one 16-byte load, and each of the step's two gather instructions covers 64 NEIGHBOURING
-    // entries (lanes share lines inside an instruction; the two instructions touch different lines -- with (2l, 2l + 1)
-    // pairs the second gather hit lines still pending from the first and stalled the L1: TCP_PENDING_STALL_CYCLES)
     const uint64_t e = pos % SB_STEP;
-    const uint64_t q = (uint64_t)subStep[group] * SB_STEP + (pos - e) + (e < SB_STEP / 2 ? 2 * e : 2 * (e - SB_STEP / 2) + 1);
+    const uint64_t q = sb_cell(pos, subStep[group]);
     const uint32_t j = perm[p];
     const uint32_t lrow = rowOf[j] - binRow[bin];
     if (val) val[q] = AS[j];                      // (no value array for a matrix whose values are all the same)
@@ -172,6 +180,16 @@ __global__ __launch_bounds__(256) void sb_scatter_kernel(
         cr[q] = d << SB_ROWBITS | lrow;
         if (e == 0) stepBase[q / SB_STEP] = base;
     }
+}
+
+// value map (spmvHipUpdateValues): the cell of every sorted position, as sb_scatter_kernel places it, gets its CSR position
+__global__ __launch_bounds__(256) void sb_map_kernel(uint64_t nnz, unsigned colBits, const uint64_t* __restrict__ skeys,
+                                                     const uint32_t* __restrict__ perm, const uint64_t* __restrict__ start,
+                                                     const uint32_t* __restrict__ subStep, uint32_t* __restrict__ map) {
+    const uint64_t p = lin_block() * 256 + threadIdx.x;
+    if (p >= nnz) return;
+    const uint64_t group = skeys[p] >> colBits;
+    map[sb_cell(p - start[group], subStep[group])] = perm[p];
 }
 
 __global__ __launch_bounds__(256) void sb_fill32_kernel(uint32_t* __restrict__ p, uint64_t n, uint32_t v) {
@@ -423,7 +441,7 @@ void launchSpmv(const StripeFormat* f, const double* x, double* y, hipStream_t s
 void freeStripes(StripeFormat* f) {
     if (!f) return;
     (void)hipFree(f->val); (void)hipFree(f->cr); (void)hipFree(f->lrowW); (void)hipFree(f->stepBase);
-    (void)hipFree(f->binRow); (void)hipFree(f->subStep);
+    (void)hipFree(f->binRow); (void)hipFree(f->subStep); (void)hipFree(f->vmap);
     delete f;
 }
 
@@ -575,6 +593,65 @@ int buildStripes(DevMat* d, const spmvStripesOpts* opts) {
     f->buildMs = ms;
     d->stripes = f;
     return EXIT_SUCCESS;
+}
+
+bool stripesHasValues(const StripeFormat* f) { return f->val != nullptr; }
+spmvStripesOpts stripesOptions(const StripeFormat* f) { return f->opts; }
+void stripesSetUnit(StripeFormat* f, bool unit, double value) { f->unit = unit; f->unitValue = value; }
+
+// New values (same pattern) into the format's value array (it must have one: a format built for a unit matrix has none and
+// is rebuilt by the caller).  The value map is built here at the format's first refresh: the build's key sort again (the
+// same keys and bits; a stable sort's permutation depends on the keys alone), its sub-stream starts, and every sorted
+// position's cell -- the padding cells keep VMAP_NONE.
+int stripesRefreshValues(DevMat* d, StripeFormat* f, hipStream_t stream, double* mapMs, int* mapsBuilt) {
+    if (!f->val) return EXIT_FAILURE;
+    const uint64_t cells = f->nSteps * SB_STEP, nnz = f->nnz, M = d->M;
+    if (!f->vmap) {
+        const auto t0 = std::chrono::steady_clock::now();
+        auto fail = [&](const char* what) {
+            (void)hipGetLastError();
+            fprintf(stderr, "libspmvhip: stripes: value map: %s failed\n", what);
+            (void)hipStreamSynchronize(stream);
+            (void)hipFree(f->vmap);
+            f->vmap = nullptr;
+            return EXIT_FAILURE;
+        };
+        if (hipMalloc(&f->vmap, std::max<uint64_t>(cells, 1) * 4) != hipSuccess) { f->vmap = nullptr; return fail("allocation"); }
+        const uint64_t nGroups = (uint64_t)f->B * f->subs;
+        TempBuf keys, keysOut, idx, perm, rowOf, sortTmp, dStart;
+        if (keys.alloc(nnz * 8) || keysOut.alloc(nnz * 8) || idx.alloc(nnz * 4) || perm.alloc(nnz * 4) || rowOf.alloc(nnz * 4) ||
+            dStart.alloc((nGroups + 1) * 8))
+            return fail("temporary allocation (28 B per entry)");
+        if (cells) hipLaunchKernelGGL(sb_fill32_kernel, grid2d((cells + 255) / 256, 256), dim3(256), 0, stream, f->vmap, cells, VMAP_NONE);
+        unsigned colBits = 1, groupBits = 1;         // (as buildStripes chose them)
+        while (colBits < 32 && (1ull << colBits) < d->N) ++colBits;
+        while ((1ull << groupBits) < nGroups) ++groupBits;
+        if (d->irpBytes == 4)
+            hipLaunchKernelGGL((sb_keys_kernel<uint32_t>), grid2d((M + 3) / 4, 256), dim3(256), 0, stream, M, static_cast<const uint32_t*>(d->IRP), d->JA,
+                               f->binRow, f->B, f->subs, colBits, keys.as<uint64_t>(), idx.as<uint32_t>(), rowOf.as<uint32_t>());
+        else
+            hipLaunchKernelGGL((sb_keys_kernel<uint64_t>), grid2d((M + 3) / 4, 256), dim3(256), 0, stream, M, static_cast<const uint64_t*>(d->IRP), d->JA,
+                               f->binRow, f->B, f->subs, colBits, keys.as<uint64_t>(), idx.as<uint32_t>(), rowOf.as<uint32_t>());
+        if (hipGetLastError() != hipSuccess) return fail("key kernel");
+        rocprim::double_buffer<uint64_t> dKeys(keys.as<uint64_t>(), keysOut.as<uint64_t>());
+        rocprim::double_buffer<uint32_t> dIdx(idx.as<uint32_t>(), perm.as<uint32_t>());
+        size_t tmpBytes = 0;
+        if (rocprim::radix_sort_pairs(nullptr, tmpBytes, dKeys, dIdx, (size_t)nnz, 0, colBits + groupBits, stream) != hipSuccess ||
+            sortTmp.alloc(tmpBytes))
+            return fail("sort workspace");
+        if (rocprim::radix_sort_pairs(sortTmp.p, tmpBytes, dKeys, dIdx, (size_t)nnz, 0, colBits + groupBits, stream) != hipSuccess)
+            return fail("sort");
+        hipLaunchKernelGGL(sb_bounds_kernel, grid2d((nnz + 255) / 256, 256), dim3(256), 0, stream, nnz, colBits, dKeys.current(), nGroups,
+                           dStart.as<uint64_t>());
+        hipLaunchKernelGGL(sb_map_kernel, grid2d((nnz + 255) / 256, 256), dim3(256), 0, stream, nnz, colBits, dKeys.current(), dIdx.current(),
+                           dStart.as<uint64_t>(), f->subStep, f->vmap);
+        if (hipGetLastError() != hipSuccess) return fail("map kernels");
+        if (hipStreamSynchronize(stream) != hipSuccess) return fail("synchronise");      // (the temporaries go)
+        f->bytes += cells * 4;
+        *mapMs += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        ++*mapsBuilt;
+    }
+    return enqueueGatherValues(f->val, f->vmap, cells, d->AS, stream);
 }
 
 // One persistent workgroup per CU (its bin of y fills the LDS).  Start of the sweeps: the workgroups of one XCD begin

@@ -110,6 +110,7 @@ struct TileFormat {
     uint32_t  chunk = 0;                            // phase-1 work item size in entries actually used
     double    buildMs = 0;                          // wall time of the one-time build (events on the null stream around it)
     double    allocMs = 0;                          // ... of which the host spent in hipMalloc (format, product workspace, 36 B/entry of temporaries)
+    uint32_t* vmap = nullptr;                       // value map: CSR position -> slice-major position (built at the first value update)
 };
 
 struct TileDst { double* p[SPMV_MAX_PEERS]; uint32_t n; };
@@ -223,6 +224,18 @@ __global__ __launch_bounds__(256) void pb_place_kernel(
 __global__ __launch_bounds__(256) void pb_fill_kernel(uint32_t* p, uint64_t n, uint32_t v) {
     const uint64_t i = lin_block() * 256 + threadIdx.x;
     if (i < n) p[i] = v;
+}
+
+// value map (spmvHipUpdateValues): the build's sort again, on the same keys and bits, with the CSR position as payload.  A
+// stable sort's permutation depends on the keys alone, so sorted position p holds the same entry as val[p] of the build.
+__global__ __launch_bounds__(256) void pb_iota_kernel(uint64_t n, uint32_t* __restrict__ p) {
+    const uint64_t i = lin_block() * 256 + threadIdx.x;
+    if (i < n) p[i] = (uint32_t)i;
+}
+// ... and inverted: the refresh walks CSR order (values.hip)
+__global__ __launch_bounds__(256) void pb_invert_kernel(uint64_t n, const uint32_t* __restrict__ perm, uint32_t* __restrict__ inv) {
+    const uint64_t p = lin_block() * 256 + threadIdx.x;
+    if (p < n) inv[perm[p]] = (uint32_t)p;
 }
 
 // ---- phase 1 -----------------------------------------------------------------------------------
@@ -791,7 +804,7 @@ uint64_t tilesBinRow(const DevMat* d, uint32_t bin) {
 
 void freeTiles(TileFormat* t) {
     if (!t) return;
-    (void)hipFree(t->slab); (void)hipFree(t->tl); (void)hipFree(t->pidx);
+    (void)hipFree(t->slab); (void)hipFree(t->tl); (void)hipFree(t->pidx); (void)hipFree(t->vmap);
     (void)hipFree(t->binPos); (void)hipFree(t->waveTile); (void)hipFree(t->work); (void)hipFree(t->ready);
     delete t;
 }
@@ -1085,6 +1098,48 @@ int buildTiles(DevMat* d, const spmvTilesOpts* opts) {
     d->tiles = t;
     t = nullptr;                                    // the guard lets go
     return EXIT_SUCCESS;
+}
+
+// New values (same pattern) into the slice-major value array; the value map is built here at the format's first refresh.
+// The slab keeps `val` also for a unit matrix (it is the build's sort buffer), so this form never needs a rebuild.
+int tilesRefreshValues(DevMat* d, TileFormat* t, hipStream_t stream, double* mapMs, int* mapsBuilt) {
+    const uint64_t nnz = t->nnz;
+    if (!t->vmap) {
+        const auto t0 = std::chrono::steady_clock::now();
+        auto fail = [&](const char* what) {
+            (void)hipGetLastError();
+            fprintf(stderr, "libspmvhip: tiles: value map: %s failed\n", what);
+            (void)hipStreamSynchronize(stream);
+            (void)hipFree(t->vmap);
+            t->vmap = nullptr;
+            return EXIT_FAILURE;
+        };
+        if (hipMalloc(&t->vmap, std::max<uint64_t>(nnz, 1) * 4) != hipSuccess) { t->vmap = nullptr; return fail("allocation"); }
+        const TileFormat* other = d->tiles == t ? d->tilesAlt : d->tiles;
+        if (other && other->vmap) {                  // both forms share the slice-major order (the same sort): the same map
+            if (hipMemcpyAsync(t->vmap, other->vmap, nnz * 4, hipMemcpyDeviceToDevice, stream) != hipSuccess) return fail("copy");
+        } else {
+            TempBuf idx, keysOut, perm, sortTmp;
+            if (idx.alloc(nnz * 4) || keysOut.alloc(nnz * 4) || perm.alloc(nnz * 4)) return fail("temporary allocation (12 B per entry)");
+            hipLaunchKernelGGL(pb_iota_kernel, grid2d((nnz + 255) / 256, 256), dim3(256), 0, stream, nnz, idx.as<uint32_t>());
+            unsigned bits = 1;
+            while ((1u << bits) < t->S) ++bits;
+            size_t tmpBytes = 0;
+            if (rocprim::radix_sort_pairs(nullptr, tmpBytes, d->JA, keysOut.as<uint32_t>(), idx.as<uint32_t>(), perm.as<uint32_t>(), (size_t)nnz,
+                                          PB_CBITS, PB_CBITS + bits, stream) != hipSuccess || sortTmp.alloc(tmpBytes))
+                return fail("sort workspace");
+            if (rocprim::radix_sort_pairs(sortTmp.p, tmpBytes, d->JA, keysOut.as<uint32_t>(), idx.as<uint32_t>(), perm.as<uint32_t>(), (size_t)nnz,
+                                          PB_CBITS, PB_CBITS + bits, stream) != hipSuccess)
+                return fail("sort");
+            hipLaunchKernelGGL(pb_invert_kernel, grid2d((nnz + 255) / 256, 256), dim3(256), 0, stream, nnz, perm.as<uint32_t>(), t->vmap);
+            if (hipGetLastError() != hipSuccess) return fail("map kernels");
+        }
+        if (hipStreamSynchronize(stream) != hipSuccess) return fail("synchronise");      // (the temporaries go)
+        t->bytes += nnz * 4;
+        *mapMs += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        ++*mapsBuilt;
+    }
+    return enqueueScatterValues(t->val, t->vmap, nnz, d->AS, stream);
 }
 
 size_t tilesBytes(const DevMat* d) { return (d->tiles ? d->tiles->bytes : 0) + (d->tilesAlt ? d->tilesAlt->bytes : 0); }
