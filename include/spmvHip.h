@@ -173,6 +173,32 @@ SPMV_HIP hipSpMVRowsELL;                  /* <- cudaSpMVRowsELL (transposed)    
 SPMV_HIP hipSpMVRowsELLNNTransposed;      /* <- cudaSpMVRowsELLNNTransposed      SpMV_CUDA.cu:99-115  */
 SPMV_HIP hipSpMVWarpsPerRowELLNTrasposed; /* <- cudaSpMVWarpsPerRowELLNTrasposed SpMV_CUDA.cu:116-135 */
 
+/* --------------------------------------------------------- blocks of vectors */
+#define SPMV_DENSE_ROW_MAJOR 0   /* element (i, c) at P[i*ld + c], ld >= k          */
+#define SPMV_DENSE_COL_MAJOR 1   /* element (i, c) at P[c*ld + i], ld >= rows of P  */
+/* Y = A X for k >= 1 columns.  X is N x k and Y is M x k, both on the device; each has its own layout and leading
+ * dimension.  Column c of Y has the bits of sgemvSerial(A, X[:, c]): every row's products are rounded and added in the
+ * handle's stored entry order, exactly as the oracle walks it.  For block solvers (block CG / GMRES, LOBPCG), several
+ * right-hand sides, probing: one call instead of k calls of hipSpMVRowsCSR, which stream the matrix k times (DESIGN.md
+ * section 15).
+ * Handles: CSR handles from spMatCpyCSR and spmvHipAdoptCSR, 4- or 8-byte row pointers.  ELL handles (spmvHipCsrToEll's
+ *   included) are refused.
+ * Order: the stored order, not the sorted one -- the bits hold for unsorted rows and for repeated columns too, and do not
+ *   rest on the LDS atomic order (spmvHipProbeLdsAtomicOrder).  An empty row gives +0.0 in every column; NaN and Inf
+ *   propagate as in the oracle.  Elements of Y outside the M x k block (the ld padding) are never written.
+ * Width: any k >= 1.  The columns are taken in panels of at most 16 and the matrix is streamed once per panel (k = 17 is
+ *   two panels: twice the matrix).  k = 1 with unit strides runs the LDS-stream kernel of hipSpMVRowsCSR (variant 1): the
+ *   bits of hipSpMVRowsCSR.  Row-major X and Y are the fast layout; column-major X gathers one line per element.
+ * Values are read at every call: AS and the unit detection (spmvHipUnitValue: the value then comes from a register, Y
+ *   unchanged), so the next call after spmvHipUpdateValues / spmvHipValuesChanged uses the new values.
+ * Launch: as the SpMV launchers -- spmvHipSetSync(1) waits, then sets spmvHipLastKernelSeconds (all panels) and
+ *   spmvHipLastLaunch (one panel's shape); spmvHipSetSync(0) only enqueues on the library stream.  No device allocation,
+ *   no format: the call can be captured into a HIP graph.
+ * Refused with a message and EXIT_FAILURE, Y untouched: NULL pointers or a handle that is not live, an ELL handle,
+ *   k = 0, an unknown layout, ld too small for its layout, X and Y address ranges that overlap (checked on the host). */
+int hipSpMMRowsCSR(spmat* dMat, unsigned k, const double* dX, size_t ldx, int xLayout,
+                   double* dY, size_t ldy, int yLayout);
+
 /* Column-sliced two-phase SpMV for matrices whose x gather misses the caches
  * (DESIGN.md section 7): the GPU counterpart of the reference's 2-D decomposed
  * CPU variants spmvTilesCSR / spmvTilesAllocdCSR (src/SpMV_CSR_OMP.c:101-226:

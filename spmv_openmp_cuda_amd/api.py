@@ -97,7 +97,9 @@ _sigs = {
     "spmvHipTilesBinRow": ([C.POINTER(spmat), C.c_uint, C.POINTER(C.c_ulong)], _i),
     "spmvHipUpdateValues": ([C.POINTER(spmat), _vp, _i], _i), "spmvHipValuesChanged": ([C.POINTER(spmat)], _i),
     "spmvHipLastUpdateInfo": ([C.POINTER(spmat), _vp], _i), "spmvHipShardUpdateValues": ([_vp, _vp], _i),
+    "hipSpMMRowsCSR": ([C.POINTER(spmat), C.c_uint, _vp, _sz, _i, _vp, _sz, _i], _i),
 }
+SPMV_DENSE_ROW_MAJOR, SPMV_DENSE_COL_MAJOR = 0, 1          # include/spmvHip.h: layouts of hipSpMMRowsCSR's X and Y
 
 
 class spmvTilesOpts(C.Structure):
@@ -380,6 +382,42 @@ class DeviceMatrix:
         _check(lib.spmvHipLastUpdateInfo(C.byref(self.handle), C.byref(info)), "spmvHipLastUpdateInfo")
         return info
 
+    def matmul(self, X, out=None):
+        """hipSpMMRowsCSR: Y = A X, column c of Y bit-identical to sgemvSerial on column c of X.  X is (N, k) float64:
+        a device torch tensor with unit stride in one dimension (a contiguous tensor is row-major, a `.t()` view of a
+        contiguous (k, N) tensor column-major; the leading dimension is the other stride) -> a torch tensor, `out` if
+        given (same rules); or a numpy array -> uploaded, multiplied, returned as numpy.  Runs on the library stream."""
+        M, N = int(self.handle.M), int(self.handle.N)
+        if isinstance(X, np.ndarray):
+            if out is not None:
+                raise SpmvHipError("matmul: `out` is for torch tensors")
+            if X.ndim != 2 or X.shape[0] != N or X.shape[1] < 1:
+                raise SpmvHipError(f"matmul: X must be ({N}, k) with k >= 1, not {X.shape}")
+            k = X.shape[1]
+            hx = np.ascontiguousarray(X, dtype=np.float64)
+            dx, dy = DeviceBuffer(hx.nbytes).up(hx), DeviceBuffer(M * k * 8)
+            try:
+                _check(lib.hipSpMMRowsCSR(C.byref(self.handle), k, dx.ptr, k, SPMV_DENSE_ROW_MAJOR, dy.ptr, k,
+                                          SPMV_DENSE_ROW_MAJOR), "hipSpMMRowsCSR")
+                return dy.down(np.float64).reshape(M, k)
+            finally:
+                dx.free()
+                dy.free()
+        import torch
+        if not isinstance(X, torch.Tensor):
+            raise SpmvHipError("matmul: X must be a numpy array or a torch tensor")
+        if X.dim() != 2 or X.shape[0] != N or X.shape[1] < 1:
+            raise SpmvHipError(f"matmul: X must be ({N}, k) with k >= 1, not {tuple(X.shape)}")
+        k = X.shape[1]
+        if out is None:
+            out = torch.empty((M, k), dtype=torch.float64, device=X.device)
+        elif out.dim() != 2 or tuple(out.shape) != (M, k):
+            raise SpmvHipError(f"matmul: out must be ({M}, {k}), not {tuple(out.shape)}")
+        xl, ldx = _dense_layout(X, "X")
+        yl, ldy = _dense_layout(out, "out")
+        _check(lib.hipSpMMRowsCSR(C.byref(self.handle), k, X.data_ptr(), ldx, xl, out.data_ptr(), ldy, yl), "hipSpMMRowsCSR")
+        return out
+
     def free(self):
         if self.handle.dev:
             lib.hipFreeSpmat(C.byref(self.handle))
@@ -393,6 +431,19 @@ class DeviceMatrix:
             self.free()
         except Exception:
             pass
+
+
+def _dense_layout(t, what):
+    """(layout, leading dimension) of a 2-D float64 device tensor of shape (rows, k) with unit stride in one dimension"""
+    import torch
+    if t.dtype != torch.float64 or not t.is_cuda:
+        raise SpmvHipError(f"matmul: {what} must be a float64 tensor on the device")
+    (rows, k), (s0, s1) = t.shape, t.stride()
+    if (s1 == 1 or k == 1) and s0 >= k:
+        return SPMV_DENSE_ROW_MAJOR, s0
+    if (s0 == 1 or rows == 1) and s1 >= rows:
+        return SPMV_DENSE_COL_MAJOR, s1
+    raise SpmvHipError(f"matmul: {what} needs unit stride in one dimension (strides {t.stride()})")
 
 
 def spMatCpyCSR(host: HostCSR) -> DeviceMatrix:

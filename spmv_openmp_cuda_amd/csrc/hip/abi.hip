@@ -914,6 +914,42 @@ int hipSpMVWarpPerRowCSR(spmat* dMat, double* dX, CONFIG cfg, double* dY) {
     return L.finish("hipSpMVWarpPerRowCSR");
 }
 
+// ---- blocks of vectors: Y = A X (contract in spmvHip.h, design in DESIGN.md section 15)
+// bytes spanned by a dense rows x k block in `layout` with leading dimension ld (0 for an empty block)
+static unsigned __int128 denseSpan(uint64_t rows, unsigned k, size_t ld, int layout) {
+    if (rows == 0) return 0;
+    const unsigned __int128 last = layout == SPMV_DENSE_ROW_MAJOR ? (unsigned __int128)(rows - 1) * ld + (k - 1)
+                                                                   : (unsigned __int128)(k - 1) * ld + (rows - 1);
+    return (last + 1) * sizeof(double);
+}
+
+int hipSpMMRowsCSR(spmat* dMat, unsigned k, const double* dX, size_t ldx, int xLayout, double* dY, size_t ldy, int yLayout) {
+    const char* who = "hipSpMMRowsCSR";
+    DevMat* d = descOf(dMat, dX, dY, who);
+    if (!d) return EXIT_FAILURE;
+    if (d->kind != Kind::CSR) { ERR("%s: handle is not CSR (ELL handles are not supported)", who); return EXIT_FAILURE; }
+    if (k == 0) { ERR("%s: k = 0 columns", who); return EXIT_FAILURE; }
+    for (int layout : {xLayout, yLayout})
+        if (layout != SPMV_DENSE_ROW_MAJOR && layout != SPMV_DENSE_COL_MAJOR) { ERR("%s: unknown layout %d", who, layout); return EXIT_FAILURE; }
+    // ld >= k (row-major) or >= the block's rows (column-major)
+    const uint64_t needX = xLayout == SPMV_DENSE_ROW_MAJOR ? k : d->N, needY = yLayout == SPMV_DENSE_ROW_MAJOR ? k : d->M;
+    if (ldx < needX || ldy < needY) {
+        ERR("%s: leading dimension %s = %zu is below %lu", who, ldx < needX ? "ldx" : "ldy", ldx < needX ? ldx : ldy,
+            (unsigned long)(ldx < needX ? needX : needY));
+        return EXIT_FAILURE;
+    }
+    const unsigned __int128 spanX = denseSpan(d->N, k, ldx, xLayout), spanY = denseSpan(d->M, k, ldy, yLayout);
+    const unsigned __int128 x0 = (uintptr_t)dX, y0 = (uintptr_t)dY;
+    if (spanX && spanY && x0 < y0 + spanY && y0 < x0 + spanX) { ERR("%s: X and Y overlap", who); return EXIT_FAILURE; }
+    if (d->M == 0) return nothingToLaunch(d, nullptr);
+    const uint64_t sxr = xLayout == SPMV_DENSE_ROW_MAJOR ? ldx : 1, sxc = xLayout == SPMV_DENSE_ROW_MAJOR ? 1 : ldx;
+    const uint64_t syr = yLayout == SPMV_DENSE_ROW_MAJOR ? ldy : 1, syc = yLayout == SPMV_DENSE_ROW_MAJOR ? 1 : ldy;
+    Launch L(grid2d(d->nBlk2, WG_THREADS), dim3(WG_THREADS));
+    if (k == 1 && sxr == 1 && syr == 1) launchStream2<true>(d, const_cast<double*>(dX), dY);     // one plain vector: the SpMV kernel
+    else if (enqueueSpmm(d, k, dX, sxr, sxc, dY, syr, syc, S.stream)) { ERR("%s: launch failed", who); return EXIT_FAILURE; }
+    return L.finish(who);
+}
+
 // explicit launchers and queries work on the form last asked for with spmvHipBuild*Opt (default: arrival order)
 int hipSpMVTilesCSR(spmat* dMat, double* dX, CONFIG cfg, double* dY) {
     (void)cfg;

@@ -115,6 +115,10 @@ int  enqueueScatterValues(double* val, const uint32_t* map, uint64_t n, const do
 int  enqueueSellValues(uint32_t nSlices, const uint64_t* sliceOff, const uint32_t* perm, const uint32_t* slen, const void* IRP,
                        int irpBytes, const double* AS, double* val, hipStream_t stream);
 int  updateValues(spmat* h, const double* AS, bool onDevice, bool reread, hipStream_t stream, const char* who);   // abi.hip
+// Y = A X for k columns, X(j, c) at X[j*sxr + c*sxc], Y(i, c) at Y[i*syr + c*syc] (spmm.hip): one launch per panel of at
+// most 16 columns on `stream`, no allocation; the caller has checked handle, pointers and extents
+int  enqueueSpmm(const DevMat* d, uint32_t k, const double* X, uint64_t sxr, uint64_t sxc, double* Y, uint64_t syr,
+                 uint64_t syc, hipStream_t stream);
 constexpr uint32_t VMAP_NONE = 0xFFFFFFFFu;                    // map entry of a padding cell (value 0.0); nnz < 2^32 - 65536
 
 // Fold `blocks` workgroups into an (x, y) grid whose x extent keeps

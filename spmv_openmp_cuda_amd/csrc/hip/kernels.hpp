@@ -120,6 +120,15 @@ constexpr int STREAM_UNROLL = STREAM_NNZ / WG_THREADS;
 //  replaces already runs at ~1 lane/clk/CU.  Not kept)
 constexpr uint32_t STREAM2_MAX_ROWS = 2 * WG_THREADS;     // two row pointers per lane
 
+// Row block of workgroup `blk` (< nBlk): the long-row blocks in table order, then the XCD-contiguous deal of the
+// row-ordered blocks (bijection of [0,n): stripe x = q % 8 gets the a or a+1 consecutive blocks starting at x*a + min(x, rem))
+__device__ __forceinline__ uint64_t stream2_block(uint64_t blk, uint32_t nBlk, uint32_t nLong) {
+    if (blk < nLong) return blk;
+    const uint64_t q = blk - nLong, n = nBlk - nLong;
+    const uint64_t a = n / 8, rem = n % 8, xcd = q % 8;
+    return nLong + xcd * a + (xcd < rem ? xcd : rem) + q / 8;
+}
+
 template <typename I, bool SEQ, bool UNIT>
 __global__ __launch_bounds__(WG_THREADS) void csr_stream2_kernel(
     uint32_t nBlk, uint32_t nLong, const uint4* __restrict__ blkInfo, const uint64_t* __restrict__ blkBase,
@@ -130,15 +139,8 @@ __global__ __launch_bounds__(WG_THREADS) void csr_stream2_kernel(
     __shared__ double   wpart[WG_THREADS / WAVE];
 
     const uint32_t tid = threadIdx.x;
-    uint64_t blk = linear_block();
-    if (blk >= nBlk) return;
-    if (blk >= nLong) {
-        // XCD-contiguous deal of the row-ordered blocks
-        // (bijection of [0,n): stripe x = q % 8 gets the a or a+1 consecutive blocks starting at x*a + min(x, rem))
-        const uint64_t q = blk - nLong, n = nBlk - nLong;
-        const uint64_t a = n / 8, rem = n % 8, xcd = q % 8;
-        blk = nLong + xcd * a + (xcd < rem ? xcd : rem) + q / 8;
-    }
+    if (linear_block() >= nBlk) return;
+    const uint64_t blk = stream2_block(linear_block(), nBlk, nLong);
     const uint4 info = blkInfo[blk];
     const uint32_t r0 = info.x, R = info.y, n = info.z;
     const uint64_t base = blkBase[blk];
