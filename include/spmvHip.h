@@ -242,7 +242,9 @@ int    spmvHipStripesShape(spmat* dMat, unsigned* nBins, unsigned* rowsPerBin, i
  *   deterministic  1 or 2: a row's products are added in ascending column order, so the result is the same bits in every run,
  *                  on any number of row shards, and -- the products being rounded before they are added -- the bits of the
  *                  serial oracle (sgemvSerial, src/SpMV_CSR_OMP.c:229-250) when the columns of every row ascend, as the
- *                  reference's loader guarantees (src/lib/parser.c:195-202).  1 = "owner wavefronts": every row is added by
+ *                  reference's loader guarantees (src/lib/parser.c:195-202).  The build does not check that: on a row whose
+ *                  columns do not ascend both forms add the row's products stably sorted by column (equal columns in stored
+ *                  order), which is not the oracle's order there.  1 = "owner wavefronts": every row is added by
  *                  ONE wavefront (local row mod 4 owns it) walking its own column-ordered sub-stream -- a layout of its own;
  *                  nearly free on matrices with column locality, 1.5-2x on uniformly spread columns (a gather covers
  *                  neighbours of a quarter of the bin's entries).  2 = "ordered tickets": the layout and the shared stream
@@ -448,6 +450,9 @@ int spmvHipTilesShape(spmat* dMat, unsigned* nBins, unsigned* rowsPerBin);
  *   deterministic  1: every row is added by ONE wavefront in ascending column order (a bin is four sub-bins, each walked by
  *               one wavefront), so y is the same bits in every run and on any number of row shards, and -- products being
  *               rounded before they are added -- the bits of the serial oracle when the columns of every row ascend.
+ *               The build does not check that.  Precisely, a row is added in its stored order stably sorted by SLICE
+ *               (column >> 14, 16 Ki columns): the same as ascending columns on sorted rows, but on a row whose columns
+ *               do not ascend the entries of one slice keep their stored order (the stripes forms sort them by column).
  *               Costs time: four wavefronts per CU instead of sixteen, tiles a quarter as long.  No
  *               tapered bins in this form. */
 typedef struct { unsigned rowsPerBin; int taper; int ntStore; unsigned chunk; int deterministic; } spmvTilesOpts;

@@ -11,6 +11,7 @@ poisoned before every launch.  On top of it:
 import numpy as np
 import pytest
 
+from bits import assert_same_bits
 from conftest import random_csr, tight_error
 
 pytestmark = pytest.mark.gpu
@@ -124,7 +125,7 @@ def test_csr(api, oracle, name, launcher, variant, exact):
     y = _run(api, launcher, dmat, x, M)
     if launcher == "hipSpMVRowsSELL":                   # one lane per row, ascending j: exact for rows <= 256 entries
         short = np.diff(IRP.astype(np.int64)) <= 256
-        assert np.array_equal(y[short], y_ref[short])
+        assert_same_bits(y[short], y_ref[short])
     if launcher in ("hipSpMVTilesCSR", "hipSpMVStripesCSR") and JA.size:       # second call re-uses the built format
         assert np.max(np.abs(_run(api, launcher, dmat, x, M) - y)) <= 1e-15    # arrival-order sums differ in the last bits
     if launcher == "hipSpMVStripesCSR" and JA.size:
@@ -139,7 +140,7 @@ def test_csr(api, oracle, name, launcher, variant, exact):
     assert not np.isnan(y).any(), "rows left unwritten (poison survived)"
     assert np.max(np.abs(y - y_ref), initial=0.0) <= GATE
     if exact:
-        assert np.array_equal(y, y_ref)
+        assert_same_bits(y, y_ref)
     else:
         assert tight_error(IRP, JA, AS, x, y_ref, y) <= TIGHT
 
@@ -168,7 +169,7 @@ def test_ell(api, oracle, name, rowlens, launcher, transposed, exact):
     assert np.max(np.abs(y - y_ref), initial=0.0) <= GATE
     if exact:
         # padding adds +0.0*x[0] terms: exact unless the row sum is -0.0
-        assert np.array_equal(y, y_ref + 0.0)
+        assert_same_bits(y, y_ref + 0.0)
     else:
         assert tight_error(IRP, JA, AS, x, y_ref, y) <= TIGHT
 
@@ -210,7 +211,7 @@ def test_synth_device_matches_twin_and_oracle(api, oracle):
                 y = _run(api, launcher, dm, x, w.N)
                 assert np.max(np.abs(y - y_ref)) <= GATE
                 if exact:
-                    assert np.array_equal(y, y_ref)
+                    assert_same_bits(y, y_ref)
             # a shard generated with a row offset equals the same rows of the whole matrix
             r0, r1 = w.N // 3, w.N // 3 + 1000
             sh = synth.device_csr(w, irp, r0, r1)
@@ -264,7 +265,7 @@ def test_full_size_spot_checks(api, oracle, key):
         for (r0, r1), yr in zip(ranges, refs):
             assert np.max(np.abs(y[r0:r1] - yr)) <= GATE
             if exact:
-                assert np.array_equal(y[r0:r1], yr)
+                assert_same_bits(y[r0:r1], yr)
         arrival_order = launcher in ("hipSpMVTilesCSR", "hipSpMVStripesCSR", "hipSpMVAutoCSR") or (launcher, variant) == ("hipSpMVWarpPerRowCSR", 2)
         if launcher == "hipSpMVAutoCSR" or (launcher, variant) == ("hipSpMVWarpPerRowCSR", 2):
             assert api.lib.spmvHipAutoChoice(C.byref(dm.handle), None) == expect
@@ -283,7 +284,7 @@ def test_full_size_spot_checks(api, oracle, key):
         if arrival_order:                                   # arrival-order sums: linear up to rounding only
             assert np.max(np.abs(dy.down() - 2.0 * y)) <= 1e-15
         else:
-            assert np.array_equal(dy.down(), 2.0 * y)
+            assert_same_bits(dy.down(), 2.0 * y)
         dx2.free()
     dm.free()
 
@@ -303,7 +304,7 @@ def test_device_csr_to_ell(api, oracle, name):
             y = _run(api, launcher, dell, x, M)
             assert not np.isnan(y).any() and np.max(np.abs(y - y_ref), initial=0.0) <= GATE
             if launcher != "hipSpMVWarpsPerRowELLNTrasposed":
-                assert np.array_equal(y, y_ref + 0.0)
+                assert_same_bits(y, y_ref + 0.0)
         dell.free()
     api.lib.spmvHipSetEllRowLens(1)
     dcsr.free()
@@ -331,7 +332,7 @@ def test_64bit_row_pointers_small(api, oracle):
             y = _run(api, launcher, dm, x, M)
             assert not np.isnan(y).any() and np.max(np.abs(y - y_ref)) <= GATE
             if exact:
-                assert np.array_equal(y, y_ref)
+                assert_same_bits(y, y_ref)
     api.set_variant("hipSpMVRowsCSR", 1)
     api.set_variant("hipSpMVWarpPerRowCSR", 2)
     dm.free()
@@ -364,7 +365,7 @@ def test_more_than_4g_nnz(api, oracle):
             yr = oracle.csr_serial_dev((irp[r0:r1 + 1] - irp[r0]).astype(np.uint32), ja, as_, x)
             assert np.max(np.abs(y[r0:r1] - yr)) <= GATE
             if exact:
-                assert np.array_equal(y[r0:r1], yr)
+                assert_same_bits(y[r0:r1], yr)
     for launcher in ("hipSpMVTilesCSR", "hipSpMVStripesCSR"):
         with pytest.raises(api.SpmvHipError):
             api.spmv(launcher, dm, dx, dy)
@@ -491,7 +492,7 @@ def test_config4_full_size_ell_vs_csr(api, oracle):
     api.spmv("hipSpMVRowsCSR", dm, dx, dy)
     y_csr = dy.down()
     for (r0, r1), yr in zip(ranges, refs):
-        assert np.array_equal(y_csr[r0:r1], yr)
+        assert_same_bits(y_csr[r0:r1], yr)
     for transposed, launcher, exact in ((True, "hipSpMVRowsELL", True), (False, "hipSpMVWarpsPerRowELLNTrasposed", False)):
         dell = api.csr_to_ell_device(dm, transposed)
         for rl in (1, 0):
@@ -501,7 +502,7 @@ def test_config4_full_size_ell_vs_csr(api, oracle):
             y = dy.down()
             assert not np.isnan(y).any(), (launcher, rl)
             if exact:
-                assert np.array_equal(y, y_csr + 0.0), (launcher, rl)         # padding adds +0.0 * x[0] terms
+                assert_same_bits(y, y_csr + 0.0, (launcher, rl))         # padding adds +0.0 * x[0] terms
             for (r0, r1), yr, sc in zip(ranges, refs, scales):
                 assert np.max(np.abs(y[r0:r1] - yr)) <= GATE
                 assert np.all(np.abs(y[r0:r1] - yr) <= TIGHT * sc), (launcher, rl)
@@ -540,7 +541,7 @@ def test_host_pointer_wrappers_and_cache(api, oracle):
             assert fn(C.byref(mat.struct), x.ctypes.data_as(vp), None, y.ctypes.data_as(vp)) == 0
             assert not np.isnan(y).any() and np.max(np.abs(y - y_ref)) <= GATE
             if exact:
-                assert np.array_equal(y, y_ref + 0.0)
+                assert_same_bits(y, y_ref + 0.0)
     # same struct address, other matrix (as after free + malloc): shape and pointers differ -> re-upload
     M2, N2, IRP2, JA2, AS2 = CASES["uniform32"]
     host2 = api.HostCSR(M2, N2, IRP2, JA2, AS2)
@@ -549,11 +550,11 @@ def test_host_pointer_wrappers_and_cache(api, oracle):
     C.memmove(C.byref(host.struct), C.byref(host2.struct), C.sizeof(host.struct))
     y2 = np.full(M2, np.nan)
     assert lib.spmvHipRowsCSR(C.byref(host.struct), x2.ctypes.data_as(vp), None, y2.ctypes.data_as(vp)) == 0
-    assert np.array_equal(y2, y2_ref)
+    assert_same_bits(y2, y2_ref)
     assert lib.spmvHipDropCache() == 0
     y2[:] = np.nan
     assert lib.spmvHipRowsCSR(C.byref(host.struct), x2.ctypes.data_as(vp), None, y2.ctypes.data_as(vp)) == 0
-    assert np.array_equal(y2, y2_ref)
+    assert_same_bits(y2, y2_ref)
     assert lib.spmvHipDropCache() == 0
 
 
@@ -628,7 +629,7 @@ def test_auto_launcher_picks_and_remembers(api, oracle):
     assert api.lib.spmvHipAutoChoiceRows(C.byref(d2.handle), None) is None
     for call in range(3):
         yr = _run(api, "hipSpMVRowsCSR", d2, x2, M2)
-        assert np.array_equal(yr, y2_ref), call
+        assert_same_bits(yr, y2_ref, call)
         rname = api.lib.spmvHipAutoChoiceRows(C.byref(d2.handle), ms)
         assert rname in (b"hipSpMVRowsCSR", b"hipSpMVTilesCSR(deterministic)", b"hipSpMVStripesCSR(owner wavefronts)",
                          b"hipSpMVStripesCSR(ordered tickets)") and all(t > 0 for t in ms)
@@ -670,7 +671,7 @@ def test_serial_order_contract_on_rows_with_unsorted_columns(api, oracle):
     y_ref = oracle.csr_serial(IRP, JA, AS, x)                         # ascending j, whatever the columns
     dm = api.spMatCpyCSR(api.HostCSR(M, N, IRP, JA, AS))
     for _ in range(2):
-        assert np.array_equal(_run(api, "hipSpMVRowsCSR", dm, x, M), y_ref)
+        assert_same_bits(_run(api, "hipSpMVRowsCSR", dm, x, M), y_ref)
     assert api.lib.spmvHipAutoChoiceRows(C.byref(dm.handle), None) == b"hipSpMVRowsCSR"
     assert api.lib.spmvHipTilesBytes(C.byref(dm.handle)) == 0 and api.lib.spmvHipStripesBytes(C.byref(dm.handle)) == 0
     y = _run(api, "hipSpMVWarpPerRowCSR", dm, x, M)
@@ -716,7 +717,7 @@ def test_launchers_capture_into_a_hip_graph(api, oracle):
                 yh = y.cpu().numpy()
                 assert not np.isnan(yh).any(), n
                 assert tight_error(IRP, JA, AS, x_host, y_ref, yh) <= TIGHT, n
-            assert np.array_equal(ys[0].cpu().numpy(), y_ref)
+            assert_same_bits(ys[0].cpu().numpy(), y_ref)
     finally:
         api.lib.spmvHipSetStream(None)
         api.lib.spmvHipSetSync(1)
@@ -759,7 +760,7 @@ def test_fuzz_random_shapes(api, oracle, seed):
         assert not np.isnan(y).any(), (seed, launcher)
         assert np.max(np.abs(y - y_ref), initial=0.0) <= GATE, (seed, launcher)
         if launcher == "hipSpMVRowsCSR":
-            assert np.array_equal(y, y_ref), (seed, launcher)
+            assert_same_bits(y, y_ref, (seed, launcher))
         else:
             assert tight_error(IRP, JA, AS, x, y_ref, y) <= TIGHT, (seed, launcher)
     if JA.size:
@@ -768,7 +769,7 @@ def test_fuzz_random_shapes(api, oracle, seed):
             for form in forms:
                 build(dmat, deterministic=form)
                 y = _run(api, launcher, dmat, x, M)
-                assert np.array_equal(y, y_ref), (seed, launcher, form)
+                assert_same_bits(y, y_ref, (seed, launcher, form))
     dmat.free()
     if JA.size and int(np.diff(IRP.astype(np.int64)).max()) * M <= 4_000_000:
         for rowlens in (True, False):
@@ -840,8 +841,8 @@ def test_stripes_deterministic_form_is_the_serial_order(api, oracle, name):
                 ys.append(_run(api, "hipSpMVStripesCSR", dmat, x, M))
     dmat.free()
     for y in ys:
-        assert np.array_equal(y, ys[0])
-    assert np.array_equal(ys[0], y_ref)
+        assert_same_bits(y, ys[0])
+    assert_same_bits(ys[0], y_ref)
     # three row blocks, as three ranks would hold them
     cuts = [0, M // 3, 2 * M // 3, M]
     parts = []
@@ -856,7 +857,7 @@ def test_stripes_deterministic_form_is_the_serial_order(api, oracle, name):
         api.build_stripes(blk, deterministic=1 + len(parts) % 2)
         parts.append(_run(api, "hipSpMVStripesCSR", blk, x, r1 - r0))
         blk.free()
-    assert np.array_equal(np.concatenate(parts), ys[0])
+    assert_same_bits(np.concatenate(parts), ys[0])
 
 
 @pytest.mark.parametrize("name", list(CASES))
@@ -891,8 +892,8 @@ def test_tiles_deterministic_form_is_the_serial_order(api, oracle, name):
         api.build_tiles(dmat, taper=True, deterministic=True)
     dmat.free()
     for y in ys:
-        assert np.array_equal(y, ys[0])
-    assert np.array_equal(ys[0], y_ref)
+        assert_same_bits(y, ys[0])
+    assert_same_bits(ys[0], y_ref)
     cuts = [0, M // 3, 2 * M // 3, M]
     parts = []
     for r0, r1 in zip(cuts[:-1], cuts[1:]):
@@ -906,7 +907,7 @@ def test_tiles_deterministic_form_is_the_serial_order(api, oracle, name):
         api.build_tiles(blk, deterministic=True)
         parts.append(_run(api, "hipSpMVTilesCSR", blk, x, r1 - r0))
         blk.free()
-    assert np.array_equal(np.concatenate(parts), ys[0])
+    assert_same_bits(np.concatenate(parts), ys[0])
 
 
 @pytest.mark.parametrize("key", ["c3", "c5"])
@@ -941,14 +942,14 @@ def test_deterministic_forms_at_full_size(api, oracle, key):
                 first = y
                 assert not np.isnan(y).any()
                 for (r0, r1), yr in zip(ranges, refs):
-                    assert np.array_equal(y[r0:r1], yr), (launcher, r0)
+                    assert_same_bits(y[r0:r1], yr, (launcher, r0))
             else:
-                assert np.array_equal(y, first), launcher
+                assert_same_bits(y, first, launcher)
         if launcher in results:
-            assert np.array_equal(results[launcher], first)
+            assert_same_bits(results[launcher], first)
         results[launcher] = first
     if len(results) == 2:
-        assert np.array_equal(results["hipSpMVTilesCSR"], results["hipSpMVStripesCSR"])
+        assert_same_bits(results["hipSpMVTilesCSR"], results["hipSpMVStripesCSR"])
     dm.free()
 
 
@@ -1007,7 +1008,7 @@ def test_device_memory_comes_back(api, oracle):
     for round_ in range(7):
         host = api.HostCSR(M, N, IRP, JA, AS)
         d = api.spMatCpyCSR(host)
-        assert np.array_equal(_run(api, "hipSpMVRowsCSR", d, x, M), y_ref)
+        assert_same_bits(_run(api, "hipSpMVRowsCSR", d, x, M), y_ref)
         assert tight_error(IRP, JA, AS, x, y_ref, _run(api, "hipSpMVWarpPerRowCSR", d, x, M)) <= TIGHT
         for det in (False, True):
             api.build_tiles(d, deterministic=det)
@@ -1018,11 +1019,11 @@ def test_device_memory_comes_back(api, oracle):
         assert np.max(np.abs(_run(api, "hipSpMVRowsSELL", d, x, M) - y_ref)) <= GATE
         for transposed in (False, True):
             e = api.csr_to_ell_device(d, transposed)
-            assert np.array_equal(_run(api, "hipSpMVRowsELL" if transposed else "hipSpMVRowsELLNNTransposed", e, x, M), y_ref + 0.0)
+            assert_same_bits(_run(api, "hipSpMVRowsELL" if transposed else "hipSpMVRowsELLNNTransposed", e, x, M), y_ref + 0.0)
             e.free()
         y = np.empty(M)
         assert api.lib.spmvHipRowsCSR(C.byref(host.struct), x.ctypes.data_as(vp), None, y.ctypes.data_as(vp)) == 0
-        assert np.array_equal(y, y_ref)
+        assert_same_bits(y, y_ref)
         d.free()
         api.spmvHipFinalize()                                                # cache, workspace, events
         api.spmvHipInit(0)
@@ -1099,7 +1100,7 @@ def test_subnormal_products_and_sums(api, oracle, name):
 
     def check(y, exact, who):
         if exact:
-            assert np.array_equal(y, y_ref), who
+            assert_same_bits(y, y_ref, who)
         else:                                                            # every product exact in its last bit or rounded by <= 1 ulp
             assert np.all(np.abs(y - y_ref) <= ulp * (rowlen + 1)), who
     for launcher, variant, exact in (("hipSpMVRowsCSR", 0, True), ("hipSpMVRowsCSR", 1, True), ("hipSpMVWarpPerRowCSR", 0, False),
@@ -1116,7 +1117,7 @@ def test_subnormal_products_and_sums(api, oracle, name):
     ell = host.to_ell(with_row_lens=True)
     for launcher, mat in (("hipSpMVRowsELL", ell.transpose()), ("hipSpMVRowsELLNNTransposed", ell)):
         de = api.spMatCpyELL(mat)
-        assert np.array_equal(_run(api, launcher, de, x, M), y_ref + 0.0), launcher
+        assert_same_bits(_run(api, launcher, de, x, M), y_ref + 0.0, launcher)
         de.free()
 
 
@@ -1146,7 +1147,7 @@ def test_under_device_memory_pressure(api, oracle, capfd):
                 api.spmv(launcher, d, dx, dy)
                 y = dy.down()
                 if exact:
-                    assert np.array_equal(y, y_ref)
+                    assert_same_bits(y, y_ref)
                 else:
                     assert tight_error(IRP, JA, AS, x, y_ref, y) <= TIGHT
         assert api.lib.spmvHipAutoChoice(C.byref(d.handle), None) == b"hipSpMVWarpPerRowCSR"
@@ -1326,11 +1327,11 @@ def test_matrices_whose_values_are_all_the_same(api, oracle, name, value):
     for k, y in fast.items():
         assert not np.isnan(y).any(), k
         if k in exact:
-            assert np.array_equal(y, y_ref), k
+            assert_same_bits(y, y_ref, k)
         else:
             assert tight_error(IRP, JA, AS, x, y_ref, y) <= TIGHT, k
         if k not in arrival:
-            assert np.array_equal(y, plain[k]), k
+            assert_same_bits(y, plain[k], k)
     small = M * int(np.diff(IRP.astype(np.int64)).max(initial=0)) <= 20_000_000     # "wide": one 30 000-entry row would make 1.2 G ELL cells
     if small:
         # ELL with row lengths: the real cells are all `value`, the padding cells {0.0, column 0} are never touched
@@ -1345,7 +1346,7 @@ def test_matrices_whose_values_are_all_the_same(api, oracle, name, value):
             assert api.lib.spmvHipUnitValue(C.byref(de.handle), C.byref(c)) == (1 if JA.size else 0), launcher
             y = _run(api, launcher, de, x, M)
             if bitwise:
-                assert np.array_equal(y, y_ref + 0.0), launcher
+                assert_same_bits(y, y_ref + 0.0, launcher)
             else:
                 assert tight_error(IRP, JA, AS, x, y_ref, y) <= TIGHT, launcher
             api.lib.spmvHipSetEllRowLens(0)                                         # all slots: padding is part of the sum, values are read
@@ -1362,10 +1363,10 @@ def test_matrices_whose_values_are_all_the_same(api, oracle, name, value):
     d = api.spMatCpyCSR(api.HostCSR(M, N, IRP, JA, AS2))
     assert api.lib.spmvHipUnitValue(C.byref(d.handle), None) == 0
     y2_ref = oracle.csr_serial(IRP, JA, AS2, x)
-    assert np.array_equal(_run(api, "hipSpMVRowsCSR", d, x, M), y2_ref)
+    assert_same_bits(_run(api, "hipSpMVRowsCSR", d, x, M), y2_ref)
     d.free()
     if small:
         de = api.spMatCpyELL(api.HostCSR(M, N, IRP, JA, AS2).to_ell(with_row_lens=True).transpose())
         assert api.lib.spmvHipUnitValue(C.byref(de.handle), None) == 0
-        assert np.array_equal(_run(api, "hipSpMVRowsELL", de, x, M), y2_ref + 0.0)
+        assert_same_bits(_run(api, "hipSpMVRowsELL", de, x, M), y2_ref + 0.0)
         de.free()

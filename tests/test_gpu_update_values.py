@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from bits import assert_same_bits
 from conftest import random_csr, tight_error
 
 pytestmark = pytest.mark.gpu
@@ -98,7 +99,7 @@ def _check(oracle, path, IRP, JA, AS, x, y, step):
     y_ref = oracle.csr_serial(IRP, JA, AS, x)
     assert not np.isnan(y).any(), (path[0], step)
     if path[4]:
-        assert np.array_equal(y, y_ref), (path[0], step, np.max(np.abs(y - y_ref)))
+        assert_same_bits(y, y_ref, (path[0], step, np.max(np.abs(y - y_ref))))
     else:
         assert tight_error(IRP, JA, AS, x, y_ref, y) <= TIGHT, (path[0], step)
     return y_ref
@@ -149,7 +150,7 @@ def test_both_forms_held_are_refreshed(api, oracle, pattern):
         _run(api, "hipSpMVWarpPerRowCSR", dm, x, M)          # (the reduction-order selection leaves the other form active)
         dm.update_values(B)
         assert dm.update_info().mapsBuilt == 2
-        assert np.array_equal(_run(api, "hipSpMVTilesCSR", dm, x, M), oracle.csr_serial(IRP, JA, B, x))
+        assert_same_bits(_run(api, "hipSpMVTilesCSR", dm, x, M), oracle.csr_serial(IRP, JA, B, x))
     finally:
         dm.free()
 
@@ -251,7 +252,7 @@ def test_unit_detection_off_is_honoured(api, oracle, pattern):
         api.lib.spmvHipSetUnitValues(0)
         dm.update_values(np.full(JA.size, 3.0))
         assert api.lib.spmvHipUnitValue(C.byref(dm.handle), None) == 0
-        assert np.array_equal(_run(api, "hipSpMVRowsCSR", dm, x, M), oracle.csr_serial(IRP, JA, np.full(JA.size, 3.0), x))
+        assert_same_bits(_run(api, "hipSpMVRowsCSR", dm, x, M), oracle.csr_serial(IRP, JA, np.full(JA.size, 3.0), x))
     finally:
         dm.free()
 
@@ -281,7 +282,7 @@ def test_ell_handles(api, oracle, capfd):
                         y = _run(api, name, dm, x, M)
                         assert not np.isnan(y).any() and np.max(np.abs(y - y_ref)) <= GATE, (name, rl, step)
                         if exact:
-                            assert np.array_equal(y, y_ref + 0.0), (name, rl, step)
+                            assert_same_bits(y, y_ref + 0.0, (name, rl, step))
             finally:
                 dm.free()
     dcsr = api.spMatCpyCSR(api.HostCSR(M, N, IRP, JA, A))
@@ -294,7 +295,7 @@ def test_ell_handles(api, oracle, capfd):
             de.update_values(B)
         assert "spmvHipCsrToEll" in capfd.readouterr().err
         assert api.lib.spmvHipValuesChanged(C.byref(de.handle)) != 0
-        assert np.array_equal(_run(api, name, de, x, M), before)
+        assert_same_bits(_run(api, name, de, x, M), before)
         de.free()
     dcsr.free()
 
@@ -317,7 +318,7 @@ def test_sharded_handle_on_one_device(api, oracle, pattern, capfd):
                 y = np.full(M, np.nan)
                 assert api.lib.spmvHipSpMVSharded(h, x.ctypes.data_as(vp), mode, y.ctypes.data_as(vp), None, None) == 0
                 if mode == 0:
-                    assert np.array_equal(y, y_ref), step
+                    assert_same_bits(y, y_ref, step)
                 else:
                     assert tight_error(IRP, JA, vals, x, y_ref, y) <= TIGHT, step
     finally:
@@ -388,7 +389,7 @@ def test_device_memory_comes_back_after_updates(api, oracle):
         for v in vals:
             d.update_values(v)
         assert d.update_info().inPlace == 1
-        assert np.array_equal(_run(api, "hipSpMVRowsCSR", d, x, M), oracle.csr_serial(IRP, JA, vals[-1], x))
+        assert_same_bits(_run(api, "hipSpMVRowsCSR", d, x, M), oracle.csr_serial(IRP, JA, vals[-1], x))
         d.free()
         api.spmvHipFinalize()
         api.spmvHipInit(0)
@@ -407,7 +408,7 @@ def test_refusals_leave_the_handle_as_it_was(api, oracle, pattern, capfd):
     try:
         api.build_stripes(dm, deterministic=1)
         before = _run(api, "hipSpMVStripesCSR", dm, x, M)
-        assert np.array_equal(before, oracle.csr_serial(IRP, JA, A, x))
+        assert_same_bits(before, oracle.csr_serial(IRP, JA, A, x))
         for call in (lambda: api.lib.spmvHipUpdateValues(None, Bc.ctypes.data_as(vp), 0),
                      lambda: api.lib.spmvHipUpdateValues(C.byref(dm.handle), None, 0),
                      lambda: api.lib.spmvHipValuesChanged(None),
@@ -424,8 +425,8 @@ def test_refusals_leave_the_handle_as_it_was(api, oracle, pattern, capfd):
         assert api.lib.spmvHipUpdateValues(C.byref(e.handle), Bc.ctypes.data_as(vp), 0) != 0
         assert "spmvHipCsrToEll" in capfd.readouterr().err
         e.free()
-        assert np.array_equal(_run(api, "hipSpMVStripesCSR", dm, x, M), before)
-        assert np.array_equal(_run(api, "hipSpMVRowsCSR", dm, x, M), before)
+        assert_same_bits(_run(api, "hipSpMVStripesCSR", dm, x, M), before)
+        assert_same_bits(_run(api, "hipSpMVRowsCSR", dm, x, M), before)
     finally:
         dm.free()
 
@@ -445,12 +446,12 @@ def test_unsorted_and_repeated_columns(api, oracle):
     x = _x(rng, N)
     dm = api.spMatCpyCSR(api.HostCSR(M, N, IRP, JA, A))
     try:
-        assert np.array_equal(_run(api, "hipSpMVRowsCSR", dm, x, M), oracle.csr_serial(IRP, JA, A, x))
+        assert_same_bits(_run(api, "hipSpMVRowsCSR", dm, x, M), oracle.csr_serial(IRP, JA, A, x))
         for name in ("hipSpMVTilesCSR", "hipSpMVStripesCSR", "hipSpMVRowsSELL"):
             _run(api, name, dm, x, M)
         dm.update_values(B)
         y_ref = oracle.csr_serial(IRP, JA, B, x)
-        assert np.array_equal(_run(api, "hipSpMVRowsCSR", dm, x, M), y_ref)
+        assert_same_bits(_run(api, "hipSpMVRowsCSR", dm, x, M), y_ref)
         for name in ("hipSpMVWarpPerRowCSR", "hipSpMVTilesCSR", "hipSpMVStripesCSR", "hipSpMVRowsSELL"):
             assert tight_error(IRP, JA, B, x, y_ref, _run(api, name, dm, x, M)) <= TIGHT, name
     finally:
