@@ -97,6 +97,40 @@ int spMatCpyELLTransposed(spmat* hostT, spmat* dMat);
  * padded cells (parser.c:223-232); here the copy is refused (EXIT_FAILURE, no
  * allocation attempted) when it does not fit the device memory that is free. */
 int spmvHipCsrToEll(spmat* dCsr, int transposed, spmat* dEll);
+/* ------------------------------------------------------------- transposed products */
+/* The transpose of a device CSR handle, built on the device as a new, independent CSR handle: for y = A^T x (BiCG, QMR,
+ * LSQR / CGNR, adjoints and gradients such as A^T (A x - b), PageRank pulls along in-edges).  DESIGN.md section 16.
+ * spmvHipCsrTranspose writes into dAT a CSR handle of A^T: dAT->M = A.N, dAT->N = A.M, the same NZ.  The caller owns it
+ *   and frees it with hipFreeSpmat.
+ *   Order: STABLE.  Row j of A^T holds the entries of column j of A in their CSR position order -- ascending source row,
+ *   and within a row the stored order -- unsorted rows and repeated (i, j) pairs included.  JA of dAT holds the source
+ *   row ids (u32), AS the values; the row pointers are 4 bytes.
+ *   Every CSR entry point works on dAT unchanged (both selections, variants 0-2, the explicit two-phase / stripes / SELL
+ *   launchers, hipSpMMRowsCSR, graph capture, spmvHipUpdateValues).  hipSpMVRowsCSR(dAT, x, y) gives the bits of the
+ *   serial scatter loop, on every candidate of its selection:
+ *       y = +0.0;  for i in 0..M-1: for p in IRP[i]..IRP[i+1]-1: y[JA[p]] += AS[p] * x[i]
+ *   i.e. sgemvSerial on the stable transpose: its rows have non-decreasing column ids, which the serial-order selection
+ *   counts as sorted, and the deterministic two-phase and stripes forms keep the stored order of equal columns.
+ *   Sources: spMatCpyCSR / spmvHipAdoptCSR handles with 4- or 8-byte row pointers, unit-value handles included.  dAT runs
+ *   its own unit detection (spmvHipSetUnitValues).
+ *   Ordering: the build runs on the library stream, after what is already enqueued there (an AS just written there), and
+ *   returns with dAT complete.  It allocates: not capturable.
+ *   Device memory of dAT: 4 (A.N + 1) B of row pointers; 16 B/nnz (JA 4, AS 8, and the source-position map 4, kept for
+ *   spmvHipTransposeRefresh); the row blocks.  Build temporaries (4 B/nnz of source rows, the sort's workspace) are freed
+ *   before the call returns.
+ * spmvHipTransposeRefresh gathers dAT's values from dA's value array as it is on the device (for an adopted source the
+ *   caller's array), then does exactly what spmvHipValuesChanged(dAT) does: the unit detection, every built format in both
+ *   forms, the unit transition rules of spmvHipUpdateValues.  Selections and device addresses stay, so a graph captured on
+ *   dAT replays with the new values; spmvHipLastUpdateInfo(dAT) reports the call.  Ordering as spmvHipValuesChanged.
+ * Source identity: every device handle has a process-unique id, and dAT records its source's.  A refresh from any other
+ *   handle is refused, even one of the same shape or one that reuses a freed source's memory.  dAT keeps no pointer to
+ *   dA: freeing either first is safe.
+ * Refused with a message and EXIT_FAILURE, dAT untouched: NULL pointers, or a handle that is not live; dAT == dA; ELL
+ *   handles, spmvHipCsrToEll's included; A.NZ >= IRP32_LIMIT (2^32 - 65536: the map and the positions are 32-bit, the
+ *   limit of the two-phase and stripes formats); A.N >= 2^32 - 1 (the rows of A^T must fit the device format); a refresh
+ *   of a handle that is not a transpose, or from a handle that is not its source. */
+int spmvHipCsrTranspose(spmat* dA, spmat* dAT);
+int spmvHipTransposeRefresh(spmat* dAT, spmat* dA);
 /* Release the device arrays behind a handle (cudaUtils.h:70-78). */
 int hipFreeSpmat(spmat* dMat);
 

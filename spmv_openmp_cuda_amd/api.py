@@ -98,6 +98,8 @@ _sigs = {
     "spmvHipUpdateValues": ([C.POINTER(spmat), _vp, _i], _i), "spmvHipValuesChanged": ([C.POINTER(spmat)], _i),
     "spmvHipLastUpdateInfo": ([C.POINTER(spmat), _vp], _i), "spmvHipShardUpdateValues": ([_vp, _vp], _i),
     "hipSpMMRowsCSR": ([C.POINTER(spmat), C.c_uint, _vp, _sz, _i, _vp, _sz, _i], _i),
+    "spmvHipCsrTranspose": ([C.POINTER(spmat), C.POINTER(spmat)], _i),
+    "spmvHipTransposeRefresh": ([C.POINTER(spmat), C.POINTER(spmat)], _i),
 }
 SPMV_DENSE_ROW_MAJOR, SPMV_DENSE_COL_MAJOR = 0, 1          # include/spmvHip.h: layouts of hipSpMMRowsCSR's X and Y
 
@@ -381,6 +383,20 @@ class DeviceMatrix:
         info = spmvUpdateInfo()
         _check(lib.spmvHipLastUpdateInfo(C.byref(self.handle), C.byref(info)), "spmvHipLastUpdateInfo")
         return info
+
+    def transpose(self) -> "DeviceMatrix":
+        """spmvHipCsrTranspose: A^T built on the device as a new DeviceMatrix that owns its handle.  Row j holds the entries
+        of column j in CSR position order, so hipSpMVRowsCSR on it gives the bits of the serial scatter loop y[JA[p]] +=
+        AS[p] * x[i].  Refresh its values after this matrix's change with `refresh_from(self)`."""
+        t = DeviceMatrix()
+        _check(lib.spmvHipCsrTranspose(C.byref(self.handle), C.byref(t.handle)), "spmvHipCsrTranspose")
+        t.rows = int(t.handle.M)
+        return t
+
+    def refresh_from(self, source: "DeviceMatrix"):
+        """spmvHipTransposeRefresh: this transpose takes `source`'s current device values (source must be the matrix it
+        was transposed from), then refreshes its formats as values_changed() does."""
+        _check(lib.spmvHipTransposeRefresh(C.byref(self.handle), C.byref(source.handle)), "spmvHipTransposeRefresh")
 
     def matmul(self, X, out=None):
         """hipSpMMRowsCSR: Y = A X, column c of Y bit-identical to sgemvSerial on column c of X.  X is (N, k) float64:

@@ -109,7 +109,7 @@ void freeDesc(DevMat* d) {
     if (d->owns) {
         (void)hipFree(d->IRP); (void)hipFree(d->JA); (void)hipFree(d->AS); (void)hipFree(d->RL);
     }
-    (void)hipFree(d->blkInfo); (void)hipFree(d->blkBase);
+    (void)hipFree(d->blkInfo); (void)hipFree(d->blkBase); (void)hipFree(d->tmap);
     freeTiles(d->tiles); freeTiles(d->tilesAlt);
     freeSell(d->sell);
     freeStripes(d->stripes); freeStripes(d->stripesAlt);
@@ -786,6 +786,53 @@ int spmvHipCsrToEll(spmat* dCsr, int transposed, spmat* dEll) {
     if (transposed) publish(dEll, d, K, rows, c->NZ, rows);
     else            publish(dEll, d, rows, c->N, c->NZ, K);
     return EXIT_SUCCESS;
+}
+
+// A^T as a handle of its own (transpose.hip builds the arrays; the contract is in spmvHip.h, the design in DESIGN.md
+// section 16).  Refusals come before anything is allocated; a failure after that frees what was made, and dAT is written
+// only on success.
+int spmvHipCsrTranspose(spmat* dA, spmat* dAT) {
+    const char* who = "spmvHipCsrTranspose";
+    if (!ready(who)) return EXIT_FAILURE;
+    if (!dAT) { ERR("%s: dAT is NULL", who); return EXIT_FAILURE; }
+    DevMat* a = descOf(dA, who);
+    if (!a) return EXIT_FAILURE;
+    if (dAT == dA) { ERR("%s: dAT is the source handle itself", who); return EXIT_FAILURE; }
+    if (a->kind != Kind::CSR) { ERR("%s: the source is an ELL handle (only CSR handles can be transposed)", who); return EXIT_FAILURE; }
+    if (a->NZ >= IRP32_LIMIT) {
+        ERR("%s: NZ=%lu: the map and the row pointers of the transpose are 32-bit (limit %lu)", who, (unsigned long)a->NZ,
+            (unsigned long)IRP32_LIMIT);
+        return EXIT_FAILURE;
+    }
+    if (a->N >= (1ull << 32) - 1) { ERR("%s: N=%lu columns do not fit the row ids of the transpose", who, (unsigned long)a->N); return EXIT_FAILURE; }
+    if (a->NZ && (!a->JA || !a->AS)) { ERR("%s: the source has no column or value array", who); return EXIT_FAILURE; }
+    DevMat* t = new DevMat;
+    t->kind = Kind::CSR;
+    t->M = a->N; t->N = a->M; t->NZ = a->NZ; t->irpBytes = 4;
+    t->srcId = a->id;
+    const size_t nz1 = std::max<size_t>(a->NZ, 1);
+    std::vector<uint32_t> hIRP(t->M + 1);
+    const bool ok = hipOk(hipMalloc(&t->IRP, (t->M + 1) * 4), "hipMalloc IRP") && hipOk(hipMalloc(&t->JA, nz1 * 4), "hipMalloc JA") &&
+                    hipOk(hipMalloc(&t->AS, nz1 * 8), "hipMalloc AS") && hipOk(hipMalloc(&t->tmap, nz1 * 4), "hipMalloc map") &&
+                    !transposeCsr(a, t, S.stream) &&
+                    hipOk(hipMemcpy(hIRP.data(), t->IRP, hIRP.size() * 4, hipMemcpyDeviceToHost), "hipMemcpy IRP") &&
+                    !buildRowBlocks2(t, hIRP.data(), t->M) && !detectUnitValues(t, S.stream);
+    if (!ok) { ERR("%s: building the transpose failed", who); freeDesc(t); return EXIT_FAILURE; }
+    publish(dAT, t, t->M, t->N, t->NZ, 0);
+    return EXIT_SUCCESS;
+}
+
+int spmvHipTransposeRefresh(spmat* dAT, spmat* dA) {
+    const char* who = "spmvHipTransposeRefresh";
+    if (!ready(who)) return EXIT_FAILURE;
+    DevMat* t = descOf(dAT, who);
+    if (!t) return EXIT_FAILURE;
+    DevMat* a = descOf(dA, who);
+    if (!a) return EXIT_FAILURE;
+    if (!t->srcId) { ERR("%s: dAT was not made by spmvHipCsrTranspose", who); return EXIT_FAILURE; }
+    if (a->id != t->srcId) { ERR("%s: dA is not the handle dAT was transposed from", who); return EXIT_FAILURE; }
+    if (enqueueGatherValues(t->AS, t->tmap, t->NZ, a->AS, S.stream)) return EXIT_FAILURE;
+    return updateValues(dAT, nullptr, true, true, S.stream, who);
 }
 
 int spmvHipUpdateValues(spmat* dMat, const double* AS, int asOnDevice) {

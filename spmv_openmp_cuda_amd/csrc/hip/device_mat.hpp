@@ -10,6 +10,7 @@
 //   blkInfo / blkBase  row blocks of the LDS-stream kernel (CSR only)
 #pragma once
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <cstdint>
 #include <cstdio>
 
@@ -30,8 +31,15 @@ struct TileFormat;          // column-sliced two-phase format, tiles.hip
 struct SellFormat;          // SELL-C-sigma, sell.hip
 struct StripeFormat;        // bin-wise CSC (y bins in LDS, x from the XCD's L2), stripes.hip
 
+// process-unique identity of a descriptor (never 0, never reused: a new handle at a freed one's address gets another id)
+inline uint64_t newDevMatId() {
+    static std::atomic<uint64_t> last{0};
+    return ++last;
+}
+
 struct DevMat {
     uint32_t magic = 0x53504D56;    // 'SPMV'
+    uint64_t id = newDevMatId();
     Kind     kind  = Kind::CSR;
     uint64_t M = 0, N = 0, NZ = 0;  // logical rows, cols, true nnz
     uint64_t K = 0;                 // ELL slots per row (max row nnz)
@@ -69,6 +77,10 @@ struct DevMat {
     int       autoPick[2] = {-1, -1};
     float     autoMs[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};    // ... and what each candidate took (0 = not tried)
     spmvUpdateInfo lastUpdate{};    // what the last spmvHipUpdateValues / spmvHipValuesChanged did
+    // a transpose built by spmvHipCsrTranspose (transpose.hip): the id of its source and, for every entry p of this
+    // handle, the CSR position of the same entry in the source (ASt[p] = AS[tmap[p]]); no pointer to the source is kept
+    uint64_t  srcId = 0;            // 0: not a transpose
+    uint32_t* tmap = nullptr;
 };
 
 int  buildSell(DevMat* d);                                      // sell.hip
@@ -110,6 +122,10 @@ bool stripesHasValues(const StripeFormat* f);                  // false: built f
 spmvStripesOpts stripesOptions(const StripeFormat* f);          // what the format was built with
 void stripesSetUnit(StripeFormat* f, bool unit, double value);
 int  sellRefreshValues(DevMat* d, hipStream_t stream);          // sell.hip
+// A^T of a CSR handle on `stream` (transpose.hip): t->IRP (4 B), t->JA, t->AS and t->tmap are allocated by the caller
+// for a->N + 1 rows / a->NZ entries; the temporaries are freed before the call returns, and it returns with the stream
+// synchronised
+int  transposeCsr(const DevMat* a, DevMat* t, hipStream_t stream);
 int  enqueueGatherValues(double* val, const uint32_t* map, uint64_t n, const double* AS, hipStream_t stream);   // values.hip
 int  enqueueScatterValues(double* val, const uint32_t* map, uint64_t n, const double* AS, hipStream_t stream);
 int  enqueueSellValues(uint32_t nSlices, const uint64_t* sliceOff, const uint32_t* perm, const uint32_t* slen, const void* IRP,
