@@ -131,6 +131,57 @@ int spmvHipCsrToEll(spmat* dCsr, int transposed, spmat* dEll);
  *   of a handle that is not a transpose, or from a handle that is not its source. */
 int spmvHipCsrTranspose(spmat* dA, spmat* dAT);
 int spmvHipTransposeRefresh(spmat* dAT, spmat* dA);
+/* ------------------------------------------------------------- triangular solves */
+/* x = T^-1 b for the lower or upper triangle T of a square device CSR handle (M == N): Gauss-Seidel / SGS sweeps, SOR,
+ * ILU(0) / IC(0) preconditioners, back-substitution.  DESIGN.md section 17.  The solve writes the bits of this loop, in
+ * IEEE double with no FMA contraction (the library is built with -ffp-contract=off):
+ *     lower: for i = 0, 1, ..., M-1            upper: for i = M-1, M-2, ..., 0
+ *         acc = +0.0
+ *         for p in IRP[i] .. IRP[i+1]-1   (stored order)
+ *             j = JA[p]
+ *             if (lower ? j < i : j > i):  acc += AS[p] * x[j]      -- one rounding for the product, one for the add
+ *         x[i] = STORED ? (b[i] - acc) / AS[diagPos[i]] : (b[i] - acc)
+ *   Entries on the other side of the diagonal are IGNORED: the whole matrix A may be passed, for a forward or backward
+ *   Gauss-Seidel sweep on its triangle.  Unsorted rows and repeated (i, j) pairs are allowed; every stored strict-triangle
+ *   entry is added, in stored order.  One handle may hold an ILU(0) pair (strictly lower L with unit diagonal, U with the
+ *   diagonal): hipSpTRSVCSR(LOWER, UNIT) then hipSpTRSVCSR(UPPER, STORED) applies the preconditioner.
+ *   STORED: every row holds exactly one entry with j == i, diagPos[i].  UNIT: diagonal entries are ignored, stored or not.
+ *   A stored diagonal value of 0.0 is not an error: x[i] is then +-Inf or NaN as the loop gives, and propagates as the
+ *   loop propagates it.  Unit-value handles (spmvHipUnitValue) take the value from a register: c * x rounds as AS[p] * x.
+ *   dB == dX (in place) is allowed: a row reads b only at its own index, writes x only at its own index, and reads x only
+ *   at rows that are already final.
+ * Analysis: level sets of the triangle's pattern, one schedule per triangle kept on the handle; spmvHipTriAnalyse builds it
+ *   (a no-op when it exists), and the first solve of an unanalysed triangle does.  Synchronous, allocates (not capturable).
+ *   spmvHipUpdateValues, spmvHipValuesChanged and spmvHipTransposeRefresh keep it (the solve reads AS live); hipFreeSpmat
+ *   frees it.  Device memory kept: 8 B per row and 4 B per level.  Build temporaries (16 B/nnz, 16 B/row, the sorts'
+ *   workspace) are freed before the call returns.  The runs' row threshold T is 256 (spmvHipSetVariant("hipSpTRSVCSR",
+ *   T), 0 <= T <= 65536, sets it for later analyses; 0: no runs).
+ * Solve: kernels only, on the library stream, one launch per wide level and one per run of thin levels; no allocation and
+ *   no host sync once the triangle is analysed, so it can be captured into a graph after spmvHipTriAnalyse.  With
+ *   spmvHipSetSync(1) it waits and sets spmvHipLastKernelSeconds (the whole solve) and spmvHipLastLaunch (the last launch);
+ *   with spmvHipSetSync(0) it only enqueues.  M = 0 succeeds and writes nothing.
+ * Refused with a message and EXIT_FAILURE, x untouched: NULL pointers, or a handle that is not live; ELL handles,
+ *   spmvHipCsrToEll's included; M != N; an unknown uplo or diag; NZ >= IRP32_LIMIT or M >= 2^31 (positions and rows are
+ *   32-bit); STORED when firstBadDiag >= 0 (the message names the row); dB and dX overlapping without being equal.
+ * spmvHipTriInfo: the schedule of one triangle, all zeros (and firstBadDiag 0) when it has not been analysed. */
+#define SPMV_TRI_LOWER   0
+#define SPMV_TRI_UPPER   1
+#define SPMV_DIAG_STORED 0
+#define SPMV_DIAG_UNIT   1
+typedef struct {
+    ulong  levels;          /* 0: this triangle has not been analysed                               */
+    ulong  maxLevelRows;    /* rows of the widest level                                              */
+    ulong  launches;        /* kernel launches one solve enqueues                                    */
+    ulong  fusedLevels;     /* levels solved inside single-workgroup runs                            */
+    ulong  longRows;        /* rows on the wavefront-per-row path                                    */
+    long   firstBadDiag;    /* -1, or the first row without exactly one stored diagonal entry        */
+    int    analyses;        /* analyses run on this handle for this triangle (stays 1 across updates) */
+    double analysisMs;      /* host wall time of the last analysis                                   */
+    size_t bytes;           /* device memory the schedule keeps                                      */
+} spmvTriInfo;
+int spmvHipTriAnalyse(spmat* dA, int uplo);
+int hipSpTRSVCSR(spmat* dA, int uplo, int diag, const double* dB, double* dX);
+int spmvHipTriInfo(spmat* dA, int uplo, spmvTriInfo* info);
 /* Release the device arrays behind a handle (cudaUtils.h:70-78). */
 int hipFreeSpmat(spmat* dMat);
 
@@ -373,6 +424,8 @@ int spmvHipProbeLdsAtomicOrder(void);
  *                             construction, the reference's slowest kernel); also what runs when CONFIG.blockSize is given
  *                         1 = (default) the same sums -- one thread adds its row's cells in ascending slot order, bit for
  *                             bit -- fed from a coalesced span parked in LDS (rows of up to 2048 slots; longer: variant 0)
+ *   hipSpTRSVCSR              T, 0..65536: the row threshold of the single-workgroup runs for triangles analysed after
+ *                             the call (default 256; 0 = a launch per level).  x does not change by a bit.
  * Returns EXIT_FAILURE for an unknown (launcher, variant). */
 int spmvHipSetVariant(const char* launcher, int variant);
 /* Use the RL array for ELL early exit (1, default when RL was uploaded) or walk

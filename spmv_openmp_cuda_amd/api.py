@@ -100,8 +100,13 @@ _sigs = {
     "hipSpMMRowsCSR": ([C.POINTER(spmat), C.c_uint, _vp, _sz, _i, _vp, _sz, _i], _i),
     "spmvHipCsrTranspose": ([C.POINTER(spmat), C.POINTER(spmat)], _i),
     "spmvHipTransposeRefresh": ([C.POINTER(spmat), C.POINTER(spmat)], _i),
+    "spmvHipTriAnalyse": ([C.POINTER(spmat), _i], _i),
+    "hipSpTRSVCSR": ([C.POINTER(spmat), _i, _i, _vp, _vp], _i),
+    "spmvHipTriInfo": ([C.POINTER(spmat), _i, _vp], _i),
 }
 SPMV_DENSE_ROW_MAJOR, SPMV_DENSE_COL_MAJOR = 0, 1          # include/spmvHip.h: layouts of hipSpMMRowsCSR's X and Y
+SPMV_TRI_LOWER, SPMV_TRI_UPPER = 0, 1                      # include/spmvHip.h: hipSpTRSVCSR's uplo ...
+SPMV_DIAG_STORED, SPMV_DIAG_UNIT = 0, 1                    # ... and diag
 
 
 class spmvTilesOpts(C.Structure):
@@ -135,6 +140,13 @@ class spmvUpdateInfo(C.Structure):
     """include/spmvHip.h `spmvUpdateInfo`: what the last value update of a handle did."""
     _fields_ = [("inPlace", _i), ("rebuilt", _i), ("mapsBuilt", _i), ("unitBefore", _i), ("unitAfter", _i),
                 ("ms", C.c_double), ("mapMs", C.c_double)]
+
+
+class spmvTriInfo(C.Structure):
+    """include/spmvHip.h `spmvTriInfo`: the level-set schedule of one triangle (all zeros: not analysed)."""
+    _fields_ = [("levels", C.c_ulong), ("maxLevelRows", C.c_ulong), ("launches", C.c_ulong), ("fusedLevels", C.c_ulong),
+                ("longRows", C.c_ulong), ("firstBadDiag", C.c_long), ("analyses", _i), ("analysisMs", C.c_double),
+                ("bytes", _sz)]
 
 
 IPC_HANDLE_BYTES = 64
@@ -432,6 +444,52 @@ class DeviceMatrix:
         xl, ldx = _dense_layout(X, "X")
         yl, ldy = _dense_layout(out, "out")
         _check(lib.hipSpMMRowsCSR(C.byref(self.handle), k, X.data_ptr(), ldx, xl, out.data_ptr(), ldy, yl), "hipSpMMRowsCSR")
+        return out
+
+    def triangular_analyse(self, lower=True):
+        """spmvHipTriAnalyse: build the level-set schedule of the lower (or upper) triangle now (the first solve does it
+        otherwise); a no-op when it exists."""
+        _check(lib.spmvHipTriAnalyse(C.byref(self.handle), SPMV_TRI_LOWER if lower else SPMV_TRI_UPPER), "spmvHipTriAnalyse")
+
+    def triangular_info(self, lower=True) -> "spmvTriInfo":
+        """spmvHipTriInfo: the schedule of that triangle (all zeros when it has not been analysed)."""
+        info = spmvTriInfo()
+        _check(lib.spmvHipTriInfo(C.byref(self.handle), SPMV_TRI_LOWER if lower else SPMV_TRI_UPPER, C.byref(info)),
+               "spmvHipTriInfo")
+        return info
+
+    def solve_triangular(self, b, lower=True, unit_diagonal=False, out=None):
+        """hipSpTRSVCSR: x = T^-1 b for the lower (upper) triangle T of this square matrix, the other triangle ignored, with
+        the bits of the serial loop (include/spmvHip.h).  b: a contiguous float64 device torch tensor of length N -> a torch
+        tensor, `out` if given (same rules; `out` may be `b`: an in-place solve); or a numpy array -> uploaded, solved,
+        returned as numpy.  Runs on the library stream."""
+        N = int(self.handle.N)
+        uplo = SPMV_TRI_LOWER if lower else SPMV_TRI_UPPER
+        diag = SPMV_DIAG_UNIT if unit_diagonal else SPMV_DIAG_STORED
+        if isinstance(b, np.ndarray):
+            if out is not None:
+                raise SpmvHipError("solve_triangular: `out` is for torch tensors")
+            if b.ndim != 1 or b.shape[0] != N:
+                raise SpmvHipError(f"solve_triangular: b must have shape ({N},), not {b.shape}")
+            hb = np.ascontiguousarray(b, dtype=np.float64)
+            db, dx = DeviceBuffer(hb.nbytes).up(hb), DeviceBuffer(hb.nbytes)
+            try:
+                _check(lib.hipSpTRSVCSR(C.byref(self.handle), uplo, diag, db.ptr, dx.ptr), "hipSpTRSVCSR")
+                return dx.down(np.float64)
+            finally:
+                db.free()
+                dx.free()
+        import torch
+        for t, what in ((b, "b"), (out, "out")):
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous():
+                raise SpmvHipError(f"solve_triangular: {what} must be a contiguous float64 torch tensor on the device")
+            if t.dim() != 1 or t.shape[0] != N:
+                raise SpmvHipError(f"solve_triangular: {what} must have shape ({N},), not {tuple(t.shape)}")
+        if out is None:
+            out = torch.empty_like(b)
+        _check(lib.hipSpTRSVCSR(C.byref(self.handle), uplo, diag, b.data_ptr(), out.data_ptr()), "hipSpTRSVCSR")
         return out
 
     def free(self):

@@ -26,6 +26,7 @@ struct State {
     int         variantWarpCSR = 2;     // 0 wavefront-per-row restatement, 1 LDS-stream kernel (LDS segmented reduction), 2 the fastest
                                         // reduction-order kernel for the matrix (LDS-stream / two-phase / stripes), measured at first use
     int         variantEllRowMajor = 1; // hipSpMVRowsELLNNTransposed: 0 a thread walks its row in global memory, 1 LDS-stream kernel, same sums
+    uint32_t    triRunRows = 256;       // hipSpTRSVCSR: T, the row threshold of the single-workgroup runs
     int         ldsOrder = -1;          // lds_order_probe_kernel: -1 not run yet, 1 lane-ascending + in issue order, 0 anything else
     bool        ellRowLens = true;
     bool        unitValues = true;      // look for "every stored value is the same double" at upload (spmvHipSetUnitValues)
@@ -110,6 +111,7 @@ void freeDesc(DevMat* d) {
         (void)hipFree(d->IRP); (void)hipFree(d->JA); (void)hipFree(d->AS); (void)hipFree(d->RL);
     }
     (void)hipFree(d->blkInfo); (void)hipFree(d->blkBase); (void)hipFree(d->tmap);
+    freeTri(d->tri[0]); freeTri(d->tri[1]);
     freeTiles(d->tiles); freeTiles(d->tilesAlt);
     freeSell(d->sell);
     freeStripes(d->stripes); freeStripes(d->stripesAlt);
@@ -631,6 +633,7 @@ int spmvHipSetVariant(const char* launcher, int variant) {
     if (!strcmp(launcher, "hipSpMVRowsCSR") && variant >= 0 && variant <= 2) { S.variantRowsCSR = variant; return EXIT_SUCCESS; }
     if (!strcmp(launcher, "hipSpMVWarpPerRowCSR") && variant >= 0 && variant <= 2) { S.variantWarpCSR = variant; return EXIT_SUCCESS; }
     if (!strcmp(launcher, "hipSpMVRowsELLNNTransposed") && variant >= 0 && variant <= 1) { S.variantEllRowMajor = variant; return EXIT_SUCCESS; }
+    if (!strcmp(launcher, "hipSpTRSVCSR") && variant >= 0 && variant <= 65536) { S.triRunRows = (uint32_t)variant; return EXIT_SUCCESS; }
     ERR("spmvHipSetVariant: unknown (%s, %d)", launcher, variant);
     return EXIT_FAILURE;
 }
@@ -833,6 +836,68 @@ int spmvHipTransposeRefresh(spmat* dAT, spmat* dA) {
     if (a->id != t->srcId) { ERR("%s: dA is not the handle dAT was transposed from", who); return EXIT_FAILURE; }
     if (enqueueGatherValues(t->AS, t->tmap, t->NZ, a->AS, S.stream)) return EXIT_FAILURE;
     return updateValues(dAT, nullptr, true, true, S.stream, who);
+}
+
+// ---- triangular solves (trsv.hip builds and launches; the contract is in spmvHip.h, the design in DESIGN.md section 17)
+// the checks every entry point shares
+static DevMat* triHandle(spmat* dA, int uplo, const char* who) {
+    if (!ready(who)) return nullptr;
+    DevMat* d = descOf(dA, who);
+    if (!d) return nullptr;
+    if (d->kind != Kind::CSR) { ERR("%s: the handle is an ELL handle (only CSR handles are solved)", who); return nullptr; }
+    if (d->M != d->N) { ERR("%s: M=%lu != N=%lu: the matrix is not square", who, (unsigned long)d->M, (unsigned long)d->N); return nullptr; }
+    if (uplo != SPMV_TRI_LOWER && uplo != SPMV_TRI_UPPER) { ERR("%s: unknown uplo %d", who, uplo); return nullptr; }
+    if (d->NZ >= IRP32_LIMIT || d->M >= (1ull << 31)) {
+        ERR("%s: NZ=%lu, M=%lu: positions and rows of the schedule are 32-bit (limits %lu, 2^31)", who, (unsigned long)d->NZ,
+            (unsigned long)d->M, (unsigned long)IRP32_LIMIT);
+        return nullptr;
+    }
+    if (d->NZ && !d->JA) { ERR("%s: the handle has no column array", who); return nullptr; }
+    return d;
+}
+
+int spmvHipTriAnalyse(spmat* dA, int uplo) {
+    const char* who = "spmvHipTriAnalyse";
+    DevMat* d = triHandle(dA, uplo, who);
+    if (!d) return EXIT_FAILURE;
+    if (d->tri[uplo] || d->M == 0) return EXIT_SUCCESS;
+    if (triAnalyse(d, uplo, S.triRunRows, S.stream)) { ERR("%s: the analysis failed", who); return EXIT_FAILURE; }
+    return EXIT_SUCCESS;
+}
+
+int hipSpTRSVCSR(spmat* dA, int uplo, int diag, const double* dB, double* dX) {
+    const char* who = "hipSpTRSVCSR";
+    DevMat* d = triHandle(dA, uplo, who);
+    if (!d) return EXIT_FAILURE;
+    if (!dB || !dX) { ERR("%s: %s is NULL", who, !dB ? "dB" : "dX"); return EXIT_FAILURE; }
+    if (diag != SPMV_DIAG_STORED && diag != SPMV_DIAG_UNIT) { ERR("%s: unknown diag %d", who, diag); return EXIT_FAILURE; }
+    const uintptr_t b0 = (uintptr_t)dB, x0 = (uintptr_t)dX, bytes = d->M * sizeof(double);
+    if (b0 != x0 && b0 < x0 + bytes && x0 < b0 + bytes) { ERR("%s: dB and dX overlap without being equal", who); return EXIT_FAILURE; }
+    if (d->M == 0) return nothingToLaunch(d, nullptr);
+    if (d->NZ && !d->AS && !d->unit) { ERR("%s: the handle has no value array", who); return EXIT_FAILURE; }
+    if (!d->tri[uplo] && triAnalyse(d, uplo, S.triRunRows, S.stream)) { ERR("%s: the analysis failed", who); return EXIT_FAILURE; }
+    spmvTriInfo info;
+    triInfo(d, uplo, &info);
+    if (diag == SPMV_DIAG_STORED && info.firstBadDiag >= 0) {
+        ERR("%s: row %ld does not hold exactly one stored diagonal entry (SPMV_DIAG_STORED needs one in every row)", who,
+            info.firstBadDiag);
+        return EXIT_FAILURE;
+    }
+    Launch L(dim3(1), dim3(1));
+    dim3 grid(1), block(1);
+    if (enqueueTrsv(d, uplo, diag, dB, dX, S.stream, &grid, &block)) { ERR("%s: launch failed", who); return EXIT_FAILURE; }
+    L.shape(grid, block);
+    return L.finish(who);
+}
+
+int spmvHipTriInfo(spmat* dA, int uplo, spmvTriInfo* info) {
+    const char* who = "spmvHipTriInfo";
+    DevMat* d = descOf(dA, who);
+    if (!d) return EXIT_FAILURE;
+    if (!info) { ERR("%s: info is NULL", who); return EXIT_FAILURE; }
+    if (uplo != SPMV_TRI_LOWER && uplo != SPMV_TRI_UPPER) { ERR("%s: unknown uplo %d", who, uplo); return EXIT_FAILURE; }
+    triInfo(d, uplo, info);
+    return EXIT_SUCCESS;
 }
 
 int spmvHipUpdateValues(spmat* dMat, const double* AS, int asOnDevice) {

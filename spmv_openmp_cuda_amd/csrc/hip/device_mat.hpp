@@ -30,6 +30,7 @@ enum class Kind : int { CSR = 0, ELL_ROWMAJOR = 1, ELL_COLMAJOR = 2 };
 struct TileFormat;          // column-sliced two-phase format, tiles.hip
 struct SellFormat;          // SELL-C-sigma, sell.hip
 struct StripeFormat;        // bin-wise CSC (y bins in LDS, x from the XCD's L2), stripes.hip
+struct TriSchedule;         // level sets of one triangle, trsv.hip
 
 // process-unique identity of a descriptor (never 0, never reused: a new handle at a freed one's address gets another id)
 inline uint64_t newDevMatId() {
@@ -81,6 +82,9 @@ struct DevMat {
     // handle, the CSR position of the same entry in the source (ASt[p] = AS[tmap[p]]); no pointer to the source is kept
     uint64_t  srcId = 0;            // 0: not a transpose
     uint32_t* tmap = nullptr;
+    // the level-set schedules of the triangular solve (trsv.hip), [SPMV_TRI_LOWER] and [SPMV_TRI_UPPER]: built from the
+    // pattern at the first solve or by spmvHipTriAnalyse, kept across value updates (the solve reads AS live)
+    TriSchedule* tri[2] = {nullptr, nullptr};
 };
 
 int  buildSell(DevMat* d);                                      // sell.hip
@@ -126,6 +130,17 @@ int  sellRefreshValues(DevMat* d, hipStream_t stream);          // sell.hip
 // for a->N + 1 rows / a->NZ entries; the temporaries are freed before the call returns, and it returns with the stream
 // synchronised
 int  transposeCsr(const DevMat* a, DevMat* t, hipStream_t stream);
+// the pieces of the transpose that the triangular analysis shares (transpose.hip): ptr[c] = the first of the nnz sorted
+// keys that is >= c, for c in [0, N] (keys >= N clamp to N); rowOf[p] = the row of CSR position p
+void enqueueSortedBounds(uint64_t nnz, uint64_t N, const uint32_t* keys, uint32_t* ptr, hipStream_t stream);
+void enqueueRowOf(uint64_t M, const void* IRP, int irpBytes, uint32_t* rowOf, hipStream_t stream);
+// Triangular solves (trsv.hip; contract in spmvHip.h, design in DESIGN.md section 17).  triAnalyse builds d->tri[uplo]
+// (synchronous, allocates, temporaries freed before it returns; runThreshold = the T of the single-workgroup runs, 0: none);
+// enqueueTrsv enqueues one solve of an analysed triangle on `stream` (no allocation, no sync) and reports the last launch.
+int  triAnalyse(DevMat* d, int uplo, uint32_t runThreshold, hipStream_t stream);
+int  enqueueTrsv(const DevMat* d, int uplo, int diag, const double* b, double* x, hipStream_t stream, dim3* grid, dim3* block);
+void triInfo(const DevMat* d, int uplo, spmvTriInfo* out);
+void freeTri(TriSchedule* s);
 int  enqueueGatherValues(double* val, const uint32_t* map, uint64_t n, const double* AS, hipStream_t stream);   // values.hip
 int  enqueueScatterValues(double* val, const uint32_t* map, uint64_t n, const double* AS, hipStream_t stream);
 int  enqueueSellValues(uint32_t nSlices, const uint64_t* sliceOff, const uint32_t* perm, const uint32_t* slen, const void* IRP,

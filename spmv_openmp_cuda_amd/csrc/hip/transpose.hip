@@ -106,6 +106,21 @@ __global__ __launch_bounds__(TR_THREADS) void tr_place_kernel(uint64_t n, const 
 
 }  // namespace
 
+// also the dependents list of a triangular solve's analysis (trsv.hip)
+void enqueueSortedBounds(uint64_t nnz, uint64_t N, const uint32_t* keys, uint32_t* ptr, hipStream_t st) {
+    hipLaunchKernelGGL(tr_bounds_kernel, grid2d((nnz + 1 + TR_THREADS - 1) / TR_THREADS, TR_THREADS), dim3(TR_THREADS), 0, st,
+                       nnz, N, keys, ptr);
+}
+
+void enqueueRowOf(uint64_t M, const void* IRP, int irpBytes, uint32_t* rowOf, hipStream_t st) {
+    if (!M) return;
+    const dim3 rows = grid2d((M + TR_THREADS / TR_ROW_LANES - 1) / (TR_THREADS / TR_ROW_LANES), TR_THREADS);
+    if (irpBytes == 4)
+        hipLaunchKernelGGL((tr_row_of_kernel<uint32_t>), rows, dim3(TR_THREADS), 0, st, M, static_cast<const uint32_t*>(IRP), rowOf);
+    else
+        hipLaunchKernelGGL((tr_row_of_kernel<uint64_t>), rows, dim3(TR_THREADS), 0, st, M, static_cast<const uint64_t*>(IRP), rowOf);
+}
+
 int transposeCsr(const DevMat* a, DevMat* t, hipStream_t st) {
     const uint64_t nnz = a->NZ, M = a->M, N = a->N;
     uint32_t* const IRPt = static_cast<uint32_t*>(t->IRP);
@@ -129,14 +144,9 @@ int transposeCsr(const DevMat* a, DevMat* t, hipStream_t st) {
         if (rocprim::radix_sort_pairs(sortTmp.p, tmpBytes, a->JA, t->JA, iota, t->tmap, (size_t)nnz, 0u, bits, st) != hipSuccess)
             return fail("sort");
     }
-    hipLaunchKernelGGL(tr_bounds_kernel, grid2d((nnz + 1 + TR_THREADS - 1) / TR_THREADS, TR_THREADS), dim3(TR_THREADS), 0, st,
-                       nnz, N, t->JA, IRPt);
+    enqueueSortedBounds(nnz, N, t->JA, IRPt, st);
     if (nnz) {
-        const dim3 rows = grid2d((M + TR_THREADS / TR_ROW_LANES - 1) / (TR_THREADS / TR_ROW_LANES), TR_THREADS);
-        if (a->irpBytes == 4)
-            hipLaunchKernelGGL((tr_row_of_kernel<uint32_t>), rows, dim3(TR_THREADS), 0, st, M, static_cast<const uint32_t*>(a->IRP), rowOf.as<uint32_t>());
-        else
-            hipLaunchKernelGGL((tr_row_of_kernel<uint64_t>), rows, dim3(TR_THREADS), 0, st, M, static_cast<const uint64_t*>(a->IRP), rowOf.as<uint32_t>());
+        enqueueRowOf(M, a->IRP, a->irpBytes, rowOf.as<uint32_t>(), st);
         hipLaunchKernelGGL(tr_place_kernel, grid2d((nnz + TR_CHUNK - 1) / TR_CHUNK, TR_THREADS), dim3(TR_THREADS), 0, st,
                            nnz, t->tmap, rowOf.as<uint32_t>(), a->AS, t->JA, t->AS);
     }
