@@ -469,7 +469,8 @@ int spmvHipPartitionRows(const ulong* IRP, ulong M, int nParts, ulong* bounds);
 spmat* spmvHipRowBlockCSR(const spmat* host, ulong r0, ulong r1);
 /* After an all-gather of equally padded row blocks (dYPad = nParts blocks of
  * maxRows doubles, block p holding rows bounds[p]..bounds[p+1]) copy the rows
- * back to back into dY -- nParts device-to-device copies on the library stream. */
+ * back to back into dY -- nParts device-to-device copies on the library stream.  A block longer than maxRows is
+ * refused before anything is copied: dY is left as it was. */
 int spmvHipCompactRows(double* dY, const double* dYPad, const ulong* bounds, int nParts, ulong maxRows);
 /* Single-process multi-device path (C drivers): shard, upload one block per
  * device, replicate x, run `mode` on every device concurrently, gather y with

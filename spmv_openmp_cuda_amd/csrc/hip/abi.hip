@@ -1507,9 +1507,12 @@ int spmvHipPartitionRows(const ulong* IRP, ulong M, int nParts, ulong* bounds) {
 
 int spmvHipCompactRows(double* dY, const double* dYPad, const ulong* bounds, int nParts, ulong maxRows) {
     if (!dY || !dYPad || !bounds || nParts <= 0) return EXIT_FAILURE;
-    for (int p = 0; p < nParts; ++p) {
+    for (int p = 0; p < nParts; ++p) {                   // every block checked before the first copy: a refusal leaves dY as it was
         const ulong rows = bounds[p + 1] - bounds[p];
         if (rows > maxRows) { ERR("spmvHipCompactRows: block %d has %lu rows > pad %lu", p, rows, maxRows); return EXIT_FAILURE; }
+    }
+    for (int p = 0; p < nParts; ++p) {
+        const ulong rows = bounds[p + 1] - bounds[p];
         if (rows)
             HIP_TRY(hipMemcpyAsync(dY + bounds[p], dYPad + (size_t)p * maxRows, rows * sizeof(double),
                                    hipMemcpyDeviceToDevice, S.stream));

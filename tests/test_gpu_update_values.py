@@ -8,6 +8,7 @@ import pytest
 
 from bits import assert_same_bits
 from conftest import random_csr, tight_error
+from exact_ref import check_any_order
 
 pytestmark = pytest.mark.gpu
 
@@ -101,6 +102,7 @@ def _check(oracle, path, IRP, JA, AS, x, y, step):
     if path[4]:
         assert_same_bits(y, y_ref, (path[0], step, np.max(np.abs(y - y_ref))))
     else:
+        check_any_order(IRP, JA, AS, x, y, f"{path[0]}, {step}")
         assert tight_error(IRP, JA, AS, x, y_ref, y) <= TIGHT, (path[0], step)
     return y_ref
 
