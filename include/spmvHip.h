@@ -182,6 +182,47 @@ typedef struct {
 int spmvHipTriAnalyse(spmat* dA, int uplo);
 int hipSpTRSVCSR(spmat* dA, int uplo, int diag, const double* dB, double* dX);
 int spmvHipTriInfo(spmat* dA, int uplo, spmvTriInfo* info);
+/* ------------------------------------------------------------- incomplete factorisation */
+/* hipSpILU0CSR overwrites the values of a square device CSR handle with its ILU(0) factors, in place: the strictly lower
+ * part becomes L (unit diagonal, not stored), the diagonal and the upper part U, so that hipSpTRSVCSR(LOWER, UNIT) then
+ * hipSpTRSVCSR(UPPER, STORED) on the same handle applies the preconditioner.  DESIGN.md section 18.  AS ends with the bits
+ * of this loop, in IEEE double with no FMA contraction (the library is built with -ffp-contract=off):
+ *     for i = 0, 1, ..., M-1
+ *         for p = IRP[i] .. diagPos[i]-1                 -- k = JA[p] < i, ascending
+ *             k = JA[p]
+ *             AS[p] = AS[p] / AS[diagPos[k]]             -- row k is final
+ *             for q = p+1 .. IRP[i+1]-1                   -- j = JA[q] > k, ascending
+ *                 if row k stores column JA[q] at position r:
+ *                     AS[q] = AS[q] - AS[p] * AS[r]      -- one rounding for the product, one for the subtraction
+ *   Preconditions (of the pattern; checked once per handle, the answer kept across value updates): every row's columns are
+ *   strictly ascending (sorted, no repeated column) and every row holds exactly one diagonal entry.
+ *   Zero pivot: a factored diagonal of +-0.0 is not an error (as in hipSpTRSVCSR); later rows get +-Inf or NaN exactly as
+ *   the loop gives them, and spmvIluInfo.zeroPivot names the smallest such row (cuSPARSE's csrilu02_zeroPivot).
+ *   Afterwards the handle is refreshed as by spmvHipValuesChanged: unit detection runs again (a pattern handle stops being
+ *   unit), built formats take the new values, the selections stay; hipSpMVRowsCSR on it gives sgemvSerial of the L\U
+ *   values.  For a spmvHipAdoptCSR handle the caller's dAS is overwritten.
+ *   Schedule: the lower triangle's level sets (spmvHipTriAnalyse(dA, SPMV_TRI_LOWER)), built by this call when missing and
+ *   never a second time: spmvTriInfo.analyses stays 1 across refactorisations.  Rows of one level are factored in parallel,
+ *   each by a group of lanes (16; spmvHipSetVariant("hipSpILU0CSR", 8 | 16 | 64)), in one launch per wide level and one
+ *   single-workgroup launch per run of thin levels, on the library stream.
+ *   Synchronous (it reads the zero-pivot word back and refreshes the handle), allocates a few words: not capturable.
+ *   M = 0 succeeds.
+ * Refused with a message and EXIT_FAILURE, AS untouched bit for bit: NULL, or a handle that is not live, or one with no
+ *   value array; ELL handles, spmvHipCsrToEll's included (sharded matrices are no spmat handles); M != N; NZ >= IRP32_LIMIT
+ *   or M >= 2^31 (the solve's limits); a row whose columns are not strictly ascending, or a row without exactly one
+ *   diagonal entry (the message names the row; spmvIluInfo.firstBadRow is the smaller of the two).
+ * spmvHipIlu0Info: what the last factorisation of the handle did (all zeros, zeroPivot and firstBadRow -1, before one). */
+typedef struct {
+    long   zeroPivot;       /* -1, or the smallest row whose factored diagonal is +-0.0      */
+    long   firstBadRow;     /* -1, or the first row refused (unsorted / repeated / diagonal) */
+    ulong  levels;          /* levels of the lower schedule the factorisation ran by         */
+    ulong  launches;        /* kernel launches of one factorisation                          */
+    ulong  longRows;        /* rows that took the long-row path                              */
+    int    factorisations;  /* on this handle                                                */
+    double ms;              /* host wall time of the last call                               */
+} spmvIluInfo;
+int hipSpILU0CSR(spmat* dA);
+int spmvHipIlu0Info(spmat* dA, spmvIluInfo* info);
 /* Release the device arrays behind a handle (cudaUtils.h:70-78). */
 int hipFreeSpmat(spmat* dMat);
 
@@ -194,7 +235,8 @@ int hipFreeSpmat(spmat* dMat);
  * VALUES ARE A SNAPSHOT.  `dAS` is read at adopt (unit detection: spmvHipSetUnitValues) and copied into every private
  * format built later (two-phase, stripes, SELL), which keep their copy.  `dAS` must therefore be complete on the device
  * before this call (it runs on the null stream).  Rewriting `dAS` afterwards is NOT seen -- y then mixes old and new
- * values -- until the caller says so with spmvHipValuesChanged(), or writes new values through spmvHipUpdateValues(). */
+ * values -- until the caller says so with spmvHipValuesChanged(), or writes new values through spmvHipUpdateValues().
+ * hipSpILU0CSR on an adopted handle overwrites `dAS` in place with the factors. */
 int spmvHipAdoptCSR(spmat* dMat, ulong M, ulong N, ulong NZ,
                     const void* dIRP, int irpBytes, const uint32_t* dJA,
                     const double* dAS, const void* hIRP);
@@ -426,6 +468,7 @@ int spmvHipProbeLdsAtomicOrder(void);
  *                             bit -- fed from a coalesced span parked in LDS (rows of up to 2048 slots; longer: variant 0)
  *   hipSpTRSVCSR              T, 0..65536: the row threshold of the single-workgroup runs for triangles analysed after
  *                             the call (default 256; 0 = a launch per level).  x does not change by a bit.
+ *   hipSpILU0CSR              8, 16 or 64: the lanes that factor one row (default 16).  AS does not change by a bit.
  * Returns EXIT_FAILURE for an unknown (launcher, variant). */
 int spmvHipSetVariant(const char* launcher, int variant);
 /* Use the RL array for ELL early exit (1, default when RL was uploaded) or walk

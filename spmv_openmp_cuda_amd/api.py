@@ -103,6 +103,8 @@ _sigs = {
     "spmvHipTriAnalyse": ([C.POINTER(spmat), _i], _i),
     "hipSpTRSVCSR": ([C.POINTER(spmat), _i, _i, _vp, _vp], _i),
     "spmvHipTriInfo": ([C.POINTER(spmat), _i, _vp], _i),
+    "hipSpILU0CSR": ([C.POINTER(spmat)], _i),
+    "spmvHipIlu0Info": ([C.POINTER(spmat), _vp], _i),
 }
 SPMV_DENSE_ROW_MAJOR, SPMV_DENSE_COL_MAJOR = 0, 1          # include/spmvHip.h: layouts of hipSpMMRowsCSR's X and Y
 SPMV_TRI_LOWER, SPMV_TRI_UPPER = 0, 1                      # include/spmvHip.h: hipSpTRSVCSR's uplo ...
@@ -147,6 +149,12 @@ class spmvTriInfo(C.Structure):
     _fields_ = [("levels", C.c_ulong), ("maxLevelRows", C.c_ulong), ("launches", C.c_ulong), ("fusedLevels", C.c_ulong),
                 ("longRows", C.c_ulong), ("firstBadDiag", C.c_long), ("analyses", _i), ("analysisMs", C.c_double),
                 ("bytes", _sz)]
+
+
+class spmvIluInfo(C.Structure):
+    """include/spmvHip.h `spmvIluInfo`: what the last ILU(0) factorisation of a handle did."""
+    _fields_ = [("zeroPivot", C.c_long), ("firstBadRow", C.c_long), ("levels", C.c_ulong), ("launches", C.c_ulong),
+                ("longRows", C.c_ulong), ("factorisations", _i), ("ms", C.c_double)]
 
 
 IPC_HANDLE_BYTES = 64
@@ -491,6 +499,18 @@ class DeviceMatrix:
             out = torch.empty_like(b)
         _check(lib.hipSpTRSVCSR(C.byref(self.handle), uplo, diag, b.data_ptr(), out.data_ptr()), "hipSpTRSVCSR")
         return out
+
+    def ilu0(self) -> "spmvIluInfo":
+        """hipSpILU0CSR: overwrite this square matrix's values with its ILU(0) factors in place (L strictly lower with a unit
+        diagonal, U the diagonal and above), with the bits of the serial loop (include/spmvHip.h); returns ilu0_info()."""
+        _check(lib.hipSpILU0CSR(C.byref(self.handle)), "hipSpILU0CSR")
+        return self.ilu0_info()
+
+    def ilu0_info(self) -> "spmvIluInfo":
+        """spmvHipIlu0Info: what the last factorisation of this matrix did (zeroPivot, firstBadRow, levels, ...)."""
+        info = spmvIluInfo()
+        _check(lib.spmvHipIlu0Info(C.byref(self.handle), C.byref(info)), "spmvHipIlu0Info")
+        return info
 
     def free(self):
         if self.handle.dev:

@@ -27,6 +27,7 @@ struct State {
                                         // reduction-order kernel for the matrix (LDS-stream / two-phase / stripes), measured at first use
     int         variantEllRowMajor = 1; // hipSpMVRowsELLNNTransposed: 0 a thread walks its row in global memory, 1 LDS-stream kernel, same sums
     uint32_t    triRunRows = 256;       // hipSpTRSVCSR: T, the row threshold of the single-workgroup runs
+    uint32_t    iluGroup = 16;          // hipSpILU0CSR: lanes per row
     int         ldsOrder = -1;          // lds_order_probe_kernel: -1 not run yet, 1 lane-ascending + in issue order, 0 anything else
     bool        ellRowLens = true;
     bool        unitValues = true;      // look for "every stored value is the same double" at upload (spmvHipSetUnitValues)
@@ -634,6 +635,7 @@ int spmvHipSetVariant(const char* launcher, int variant) {
     if (!strcmp(launcher, "hipSpMVWarpPerRowCSR") && variant >= 0 && variant <= 2) { S.variantWarpCSR = variant; return EXIT_SUCCESS; }
     if (!strcmp(launcher, "hipSpMVRowsELLNNTransposed") && variant >= 0 && variant <= 1) { S.variantEllRowMajor = variant; return EXIT_SUCCESS; }
     if (!strcmp(launcher, "hipSpTRSVCSR") && variant >= 0 && variant <= 65536) { S.triRunRows = (uint32_t)variant; return EXIT_SUCCESS; }
+    if (!strcmp(launcher, "hipSpILU0CSR") && (variant == 8 || variant == 16 || variant == 64)) { S.iluGroup = (uint32_t)variant; return EXIT_SUCCESS; }
     ERR("spmvHipSetVariant: unknown (%s, %d)", launcher, variant);
     return EXIT_FAILURE;
 }
@@ -897,6 +899,53 @@ int spmvHipTriInfo(spmat* dA, int uplo, spmvTriInfo* info) {
     if (!info) { ERR("%s: info is NULL", who); return EXIT_FAILURE; }
     if (uplo != SPMV_TRI_LOWER && uplo != SPMV_TRI_UPPER) { ERR("%s: unknown uplo %d", who, uplo); return EXIT_FAILURE; }
     triInfo(d, uplo, info);
+    return EXIT_SUCCESS;
+}
+
+// ---- ILU(0) (ilu0.hip factors; the contract is in spmvHip.h, the design in DESIGN.md section 18)
+int hipSpILU0CSR(spmat* dA) {
+    const char* who = "hipSpILU0CSR";
+    const auto t0 = std::chrono::steady_clock::now();
+    DevMat* d = triHandle(dA, SPMV_TRI_LOWER, who);
+    if (!d) return EXIT_FAILURE;
+    if (d->NZ && !d->AS) { ERR("%s: the handle has no value array", who); return EXIT_FAILURE; }
+    if (d->M) {
+        if (!d->iluChecked) {
+            long row = -1;
+            if (iluUnsortedRow(d, S.stream, &row)) { ERR("%s: the pattern check failed", who); return EXIT_FAILURE; }
+            d->iluUnsortedRow = row;
+            d->iluChecked = true;
+        }
+        if (!d->tri[SPMV_TRI_LOWER] && triAnalyse(d, SPMV_TRI_LOWER, S.triRunRows, S.stream)) {
+            ERR("%s: the analysis failed", who);
+            return EXIT_FAILURE;
+        }
+        const long unsorted = d->iluUnsortedRow, badDiag = d->tri[SPMV_TRI_LOWER]->info.firstBadDiag;
+        if (unsorted >= 0 || badDiag >= 0) {
+            const bool first = unsorted >= 0 && (badDiag < 0 || unsorted <= badDiag);
+            d->ilu.firstBadRow = first ? unsorted : badDiag;
+            if (first) ERR("%s: row %ld: its columns are not strictly ascending (unsorted, or a repeated column)", who, unsorted);
+            else       ERR("%s: row %ld does not hold exactly one stored diagonal entry", who, badDiag);
+            return EXIT_FAILURE;
+        }
+        d->ilu.firstBadRow = -1;
+        if (iluFactor(d, S.iluGroup, S.stream)) { ERR("%s: the factorisation failed", who); return EXIT_FAILURE; }
+        if (updateValues(dA, nullptr, true, true, S.stream, who)) return EXIT_FAILURE;
+    } else {
+        d->ilu.zeroPivot = d->ilu.firstBadRow = -1;
+        d->ilu.levels = d->ilu.launches = d->ilu.longRows = 0;
+    }
+    ++d->ilu.factorisations;
+    d->ilu.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return EXIT_SUCCESS;
+}
+
+int spmvHipIlu0Info(spmat* dA, spmvIluInfo* info) {
+    const char* who = "spmvHipIlu0Info";
+    DevMat* d = descOf(dA, who);
+    if (!d) return EXIT_FAILURE;
+    if (!info) { ERR("%s: info is NULL", who); return EXIT_FAILURE; }
+    *info = d->ilu;
     return EXIT_SUCCESS;
 }
 

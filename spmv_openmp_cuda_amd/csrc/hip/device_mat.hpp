@@ -13,6 +13,7 @@
 #include <atomic>
 #include <cstdint>
 #include <cstdio>
+#include <vector>
 
 #include "spmvHip.h"
 
@@ -30,7 +31,17 @@ enum class Kind : int { CSR = 0, ELL_ROWMAJOR = 1, ELL_COLMAJOR = 2 };
 struct TileFormat;          // column-sliced two-phase format, tiles.hip
 struct SellFormat;          // SELL-C-sigma, sell.hip
 struct StripeFormat;        // bin-wise CSC (y bins in LDS, x from the XCD's L2), stripes.hip
-struct TriSchedule;         // level sets of one triangle, trsv.hip
+
+// the level sets of one triangle (built by triAnalyse in trsv.hip; the ILU(0) factorisation of ilu0.hip runs on the lower one)
+struct TriSchedule {
+    spmvTriInfo info{};
+    uint32_t* perm = nullptr;        // rows by (level, class, id)
+    uint32_t* diagPos = nullptr;     // CSR position of row i's diagonal (meaningful where the row has exactly one)
+    uint32_t* levelPtr = nullptr;    // device copy of the level table (the run kernels read it)
+    struct Step { uint32_t l0, l1; };           // l1 - l0 > 1: a run (one workgroup), else one level
+    std::vector<uint32_t> levelPtr_h, split_h;  // level l: short rows perm[levelPtr[l], split[l]), long [split[l], levelPtr[l+1])
+    std::vector<Step> steps;
+};
 
 // process-unique identity of a descriptor (never 0, never reused: a new handle at a freed one's address gets another id)
 inline uint64_t newDevMatId() {
@@ -85,6 +96,11 @@ struct DevMat {
     // the level-set schedules of the triangular solve (trsv.hip), [SPMV_TRI_LOWER] and [SPMV_TRI_UPPER]: built from the
     // pattern at the first solve or by spmvHipTriAnalyse, kept across value updates (the solve reads AS live)
     TriSchedule* tri[2] = {nullptr, nullptr};
+    // the ILU(0) factorisation (ilu0.hip): what its pattern check found (checked once, kept across value updates) and
+    // what the last call did
+    bool      iluChecked = false;
+    long      iluUnsortedRow = -1;  // the first row whose columns are not strictly ascending
+    spmvIluInfo ilu{-1, -1, 0, 0, 0, 0, 0.0};
 };
 
 int  buildSell(DevMat* d);                                      // sell.hip
@@ -141,6 +157,12 @@ int  triAnalyse(DevMat* d, int uplo, uint32_t runThreshold, hipStream_t stream);
 int  enqueueTrsv(const DevMat* d, int uplo, int diag, const double* b, double* x, hipStream_t stream, dim3* grid, dim3* block);
 void triInfo(const DevMat* d, int uplo, spmvTriInfo* out);
 void freeTri(TriSchedule* s);
+// ILU(0) in place on the lower schedule d->tri[SPMV_TRI_LOWER] (ilu0.hip; contract in spmvHip.h, design in DESIGN.md section
+// 18).  iluUnsortedRow: the first row that is not strictly ascending, or -1 (synchronous).  iluFactor: the factorisation's
+// launches on `stream` for the checked handle, then the zero-pivot read-back (synchronous); groupWidth 8, 16 or 64 lanes
+// per row; fills d->ilu's zeroPivot, levels, launches and longRows.
+int  iluUnsortedRow(const DevMat* d, hipStream_t stream, long* row);
+int  iluFactor(DevMat* d, uint32_t groupWidth, hipStream_t stream);
 int  enqueueGatherValues(double* val, const uint32_t* map, uint64_t n, const double* AS, hipStream_t stream);   // values.hip
 int  enqueueScatterValues(double* val, const uint32_t* map, uint64_t n, const double* AS, hipStream_t stream);
 int  enqueueSellValues(uint32_t nSlices, const uint64_t* sliceOff, const uint32_t* perm, const uint32_t* slen, const void* IRP,

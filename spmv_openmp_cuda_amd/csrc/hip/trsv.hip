@@ -30,16 +30,6 @@
 
 namespace spmvhip {
 
-struct TriSchedule {
-    spmvTriInfo info{};
-    uint32_t* perm = nullptr;        // rows by (level, class, id)
-    uint32_t* diagPos = nullptr;     // CSR position of row i's diagonal (meaningful where the row has exactly one)
-    uint32_t* levelPtr = nullptr;    // device copy of the level table (the run kernel reads it)
-    struct Step { uint32_t l0, l1; };           // l1 - l0 > 1: a run (one workgroup), else one level
-    std::vector<uint32_t> levelPtr_h, split_h;  // level l: short rows perm[levelPtr[l], split[l]), long [split[l], levelPtr[l+1])
-    std::vector<Step> steps;
-};
-
 void freeTri(TriSchedule* s) {
     if (!s) return;
     (void)hipFree(s->perm); (void)hipFree(s->diagPos); (void)hipFree(s->levelPtr);
