@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- SpMV GFLOP/s + achieved HBM GB/s on synthetic CSR/ELL matrices, 1..8 MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c5|c3|c2|...]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c5|c3|c2|...] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one y = A.x over the whole matrix: every rank runs the hot kernel (a C-ABI launcher, picked among
@@ -9,19 +9,23 @@ hipSpMVWarpPerRowCSR / hipSpMVTilesCSR / hipSpMVStripesCSR / hipSpMVRowsSELL by 
 nnz-balanced contiguous row block and, for N > 1, the ranks exchange y over xGMI so that each ends with the full
 vector (ready to be the next x).  The default workload is BASELINE.json configs[4] (power-law CSR, 80 M rows /
 1.6 G nnz, max row 50 k), the configuration the metric's 1/2/4/8-GPU curve is quoted on; it is kept whole at every N
-(strong scaling).  At N = 1 the same run also measures configs[2] (10 M / 200 M: "headline_c3", the configuration the
-roofline target is quoted on), its banded twin, configs[1] (c2) and configs[3] (c4: the clipped matrix in ELL against
-CSR, with and without the row-length early exit).
+(strong scaling).
 
-EVERY number in the line has a parity block from the same run: head / middle / tail / heaviest-row windows against
-the serial oracle (the reference's 7e-4 gate, NaN = failure, plus the tight figure max|dy| / sum|a x|), and for the
-two headline workloads every row of the CPU baseline's sample.  A failed check aborts the bench.
+A plain run at N = 1 does what the headline needs and nothing else: generate the workload, pick the launcher, warm up,
+time the K steps, write --dump-outputs, print the line.  --full adds everything else the bench measures or checks:
+head / middle / tail / heaviest-row windows against the serial oracle (the reference's 7e-4 gate, NaN = failure, plus
+the tight figure max|dy| / sum|a x|), the CPU baseline ("cpu_baseline": the reference's own spmvRowsBasicCSR from
+oracle/_ref, or the oracle port, on the host cores; its y checks the GPU's on its rows), what the library's own
+selections resolve to, the two kernels of the two-phase launcher timed apart, and the secondary workloads: configs[2]
+(10 M / 200 M: "headline_c3", the configuration the roofline target is quoted on), its banded twin, configs[1] (c2),
+configs[3] (c4: the clipped matrix in ELL against CSR, with and without the row-length early exit) and the structured
+stand-ins.  Every block measured under --full has its parity block; a failed check aborts the bench.  At N > 1 every
+run validates the exchange it picks, so --full changes nothing there.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra objects: "roofline" (algorithmic bytes /
-HIP-event kernel time vs 8 TB/s) and "cpu_baseline" (the reference's own spmvRowsBasicCSR from oracle/_ref, or the
-oracle port, timed on this box's host cores).  The line stays under 8000 bytes: of the secondary workloads it holds a
-summary of c3 ("headline_c3"); the whole blocks (c3, c3b, c2, c4, structured) are logged on stderr as one JSON object
-after "[bench] secondary blocks:".  --dump-outputs DIR writes the timed path's y (dump_outputs).
+Rank 0 prints ONE JSON line (contract in the task statement) with "roofline" (algorithmic bytes / HIP-event kernel time
+vs 8 TB/s).  The line stays under 8000 bytes: of the secondary workloads it holds a summary of c3 ("headline_c3"); the
+whole blocks (c3, c3b, c2, c4, structured) are logged on stderr as one JSON object after "[bench] secondary blocks:".
+--dump-outputs DIR writes the timed path's y (dump_outputs).
 """
 import argparse
 import ctypes as C
@@ -54,8 +58,11 @@ def parse():
     p.add_argument("--launcher", default="auto",
                    help="a C-ABI launcher name, or 'auto': time the candidates during warm-up and keep the fastest")
     p.add_argument("--variant", type=int, default=-1)
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-extra", action="store_true", help="skip the secondary workloads measured at N=1")
+    p.add_argument("--full", action="store_true",
+                   help="at N=1, besides the headline: the oracle checks, the CPU baseline, the library's own selections, the "
+                        "two-phase kernels timed apart and the secondary workloads (off: only what the headline needs)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    p.add_argument("--no-extra", action="store_true", help="with --full: skip the secondary workloads measured at N=1")
     p.add_argument("--cpu-sample-nnz", type=int, default=100_000_000)
     p.add_argument("--y-hash", action="store_true",
                    help="add `y_sha256`, the hash of the bytes of the timed kernel's full y (rank 0's copy), to the line: two runs with a "
@@ -255,8 +262,9 @@ def tiles_phase_ms(api, torch, dm, x_ptr, y_ptr, reps=5):
     return {"pb_expand_kernel": sum(p1) / reps, "pb_reduce_kernel": sum(p2) / reps}
 
 
-def measure_single(api, synth, torch, w, launcher, steps, warmup, candidates=None):
-    """1-GPU measurement of workload `w`; returns (dict, context for checks)."""
+def measure_single(api, synth, torch, w, launcher, steps, warmup, candidates=None, full=True):
+    """1-GPU measurement of workload `w`; returns (dict, context for checks).  `full`: also time the two kernels of the
+    two-phase launcher apart (runs of their own)."""
     lens = synth.row_lengths(w)
     irp = synth.prefix(lens)
     info = synth.describe(w, lens)
@@ -285,7 +293,7 @@ def measure_single(api, synth, torch, w, launcher, steps, warmup, candidates=Non
     if launcher == "hipSpMVRowsCSR" and _ROWS_VARIANT[0] == 2:
         nm = api.lib.spmvHipAutoChoiceRows(C.byref(dm.handle), None)
         res["launcher_resolved_to"] = nm.decode() if nm else None
-    if launcher == "hipSpMVTilesCSR":
+    if full and launcher == "hipSpMVTilesCSR":
         res["kernel_ms_phases"] = tiles_phase_ms(api, torch, dm, x.data_ptr(), y.data_ptr())
     return res, dict(dm=dm, irp=irp, x_host=x_host, y=y, x=x, lens=lens)
 
@@ -633,17 +641,23 @@ def set_rows_variant(api, v):
     _ROWS_VARIANT[0] = v
 
 
-def measure_block(api, synth, torch, w, launcher, steps, warmup, candidates=None, cpu_rows=0, dump=""):
-    """measure + check one workload; returns the block for the JSON line (with "parity", and "cpu_baseline" when
-    cpu_rows > 0).  A failed check aborts the bench.  `dump`: directory for the timed launcher's y (dump_outputs)."""
-    res, ctx = measure_single(api, synth, torch, w, launcher, steps, warmup, candidates)
+def measure_block(api, synth, torch, w, launcher, steps, warmup, candidates=None, cpu_rows=0, dump="", full=True):
+    """measure one workload; returns the block for the JSON line.  `full`: also check it (with "parity", and
+    "cpu_baseline" when cpu_rows > 0) and report the library's own selections; a failed check aborts the bench.
+    `dump`: directory for the timed launcher's y (dump_outputs)."""
+    res, ctx = measure_single(api, synth, torch, w, launcher, steps, warmup, candidates, full)
     y_t = ctx["y"]
     if dump:                                         # before the selection checks below write into y_t
         dump_outputs(dump, y_t)
-    win = OracleWindows(synth, w, ctx["irp"], ctx["x_host"], ctx["lens"])
-    parity = win.check(lambda a, b: y_t[a:b].cpu().numpy())
     if _Y_HASH[0]:
         res["y_sha256"] = hashlib.sha256(y_t.cpu().numpy().tobytes()).hexdigest()
+    if not full:
+        log(f"{w.name} [{res['launcher']}]: {res['gflops']:.1f} GFLOP/s  kernel {res['kernel_ms_avg']:.3f} ms  "
+            f"{res['hbm_gbps']:.0f} GB/s = {100 * res['hbm_frac']:.1f}% of 8 TB/s   (not checked: --full checks)")
+        ctx["dm"].free()
+        return res
+    win = OracleWindows(synth, w, ctx["irp"], ctx["x_host"], ctx["lens"])
+    parity = win.check(lambda a, b: y_t[a:b].cpu().numpy())
     if cpu_rows:
         import numpy as np
         rows = w.N if cpu_rows >= int(ctx["irp"][-1]) else int(np.searchsorted(ctx["irp"], cpu_rows, side="right") - 1)
@@ -1016,9 +1030,10 @@ def run_single(args, api, synth, torch, w):
               "extra_structured": measure_structured(api, synth, torch, args, min(steps, 10), min(warmup, 2), only=args.only_structured)})
         return
     res = measure_block(api, synth, torch, w, args.launcher, steps, warmup,
-                        cpu_rows=0 if args.no_cpu_baseline else args.cpu_sample_nnz, dump=args.dump_outputs)
+                        cpu_rows=args.cpu_sample_nnz if args.full and not args.no_cpu_baseline else 0, dump=args.dump_outputs,
+                        full=args.full)
     extra = {}
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         for key in ("c3", "c3b", "c2"):
             if key == args.workload:
                 continue
@@ -1057,8 +1072,10 @@ def run_single(args, api, synth, torch, w):
                      "format_build_peak_temporary_bytes_per_nnz": res.get("format_build_peak_temporary_bytes_per_nnz"),
                      "spmvs_to_amortise_format_build": res.get("spmvs_to_amortise_format_build"),
                      "extra_device_bytes": res.get("extra_device_bytes")},
-        "parity": res["parity"],
+        "full": bool(args.full),
     }
+    if "parity" in res:
+        line["parity"] = res["parity"]
     if "y_sha256" in res:
         line["y_sha256"] = res["y_sha256"]
     if "cpu_baseline" in res:

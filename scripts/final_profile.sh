@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp
 RND=${1:-r03}
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/${RND}c; rm -rf $O; mkdir -p $O; cd $R
 sha256sum spmv_openmp_cuda_amd/lib/libspmvhip.so | cut -d' ' -f1 > $O/libspmvhip.sha256
-( time timeout -k 10 900 python3 bench.py ) > $O/bench_default.json 2> $O/bench_default.err
+( time timeout -k 10 900 python3 bench.py --full ) > $O/bench_default.json 2> $O/bench_default.err
 grep "^\[bench\]" $O/bench_default.err | cut -c1-200
 prof() {  # tag, passes ("t f w s" subset), bench args...
   tag=$1; passes=$2; shift 2

@@ -6,7 +6,7 @@ mkdir -p $O
 timeout -k 10 1000 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1
 echo "pytest rc=$?" | tee -a $O/pytest.log
 tail -15 $O/pytest.log
-timeout -k 10 900 python bench.py > $O/bench.json 2> $O/bench.err
+timeout -k 10 900 python bench.py --full > $O/bench.json 2> $O/bench.err
 echo "bench rc=$?"
 tail -30 $O/bench.err
 python - <<'PY'

@@ -217,7 +217,7 @@ def test_serial_order_y_is_the_same_bits_on_one_rank_and_on_three(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT",
                                                               "TORCHELASTIC_RUN_ID", "GROUP_RANK", "LOCAL_WORLD_SIZE")}
     common = ["--workload", "c3", "--scale", "0.05", "--steps", "2", "--warmup", "1", "--launcher", "hipSpMVRowsCSR", "--variant", "2",
-              "--y-hash", "--no-cpu-baseline", "--no-extra"]
+              "--y-hash", "--full", "--no-cpu-baseline", "--no-extra"]
     hashes = []
     for i, extra in enumerate((["--gpus", "1"], ["--gpus", "3", "--rehearse-shared-gpu", "--exchange-budget", "20"])):
         dump = tmp_path / f"dump{i}"
@@ -235,19 +235,52 @@ def test_serial_order_y_is_the_same_bits_on_one_rank_and_on_three(tmp_path):
 
 
 def test_bench_default_line_fits_and_dumps(tmp_path):
-    """The default bench (all secondary blocks) at 2 %: ONE JSON line on stdout short enough for a reader that keeps only
-    the last 8000 bytes, `steps` / `ms_per_step` as asked, and --dump-outputs writing the timed launcher's y."""
+    """The full bench (--full: all checks and secondary blocks) at 2 %: ONE JSON line on stdout short enough for a reader
+    that keeps only the last 8000 bytes, `steps` / `ms_per_step` as asked, and --dump-outputs writing the timed launcher's y."""
     import json
     import sys
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT",
+                                                              "TORCHELASTIC_RUN_ID", "GROUP_RANK", "LOCAL_WORLD_SIZE")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--scale", "0.02", "--steps", "3", "--warmup", "1",
+                        "--full", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1 and len(lines[0]) < 8000, len(lines[0])
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["parity"]["ok"] is True and line["full"] is True
+    assert line["headline_c3"]["parity_ok"] is True and "secondary blocks:" in r.stderr
+    y = np.load(tmp_path / "y.npy")
+    assert y.dtype == np.float64 and y.size == line["config"]["N"] and not np.isnan(y).any()
+
+
+def test_bench_plain_run_measures_only_the_headline(tmp_path):
+    """A plain run (no --full) at 2 %: the ONE JSON line with the headline fields, none of the blocks that --full adds
+    (oracle checks, CPU baseline, secondary workloads), and a dumped y that this test checks against the serial oracle
+    itself on the windows --full would check."""
+    import json
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    from spmv_openmp_cuda_amd import synth
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT",
                                                               "TORCHELASTIC_RUN_ID", "GROUP_RANK", "LOCAL_WORLD_SIZE")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--scale", "0.02", "--steps", "3", "--warmup", "1",
                         "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
-    assert len(lines) == 1 and len(lines[0]) < 8000, len(lines[0])
+    assert len(lines) == 1, r.stdout[-2000:]
     line = json.loads(lines[0])
-    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["parity"]["ok"] is True
-    assert line["headline_c3"]["parity_ok"] is True and "secondary blocks:" in r.stderr
+    assert (line["metric"], line["unit"], line["higher_is_better"], line["dtype"]) == ("spmv_gflops", "GFLOP/s", True, "f64")
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["full"] is False
+    for key in ("parity", "cpu_baseline", "headline_c3"):
+        assert key not in line, key
+    assert line["roofline"]["kernel_ms_phases"] is None and line["config"]["library_auto_choice"] is None
+    assert "secondary blocks:" not in r.stderr
+    w = synth.scaled(synth.WORKLOADS["c5"], 0.02)
     y = np.load(tmp_path / "y.npy")
-    assert y.dtype == np.float64 and y.size == line["config"]["N"] and not np.isnan(y).any()
+    assert y.dtype == np.float64 and y.size == line["config"]["N"] == w.N
+    lens = synth.row_lengths(w)
+    win = bench.OracleWindows(synth, w, synth.prefix(lens), synth.make_x(w.N, w.cfg), lens)
+    parity = win.check(lambda a, b: y[a:b])
+    assert parity["ok"], parity
