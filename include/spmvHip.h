@@ -223,6 +223,89 @@ typedef struct {
 } spmvIluInfo;
 int hipSpILU0CSR(spmat* dA);
 int spmvHipIlu0Info(spmat* dA, spmvIluInfo* info);
+/* ------------------------------------------------------------- Krylov solves */
+/* spmvHipDot: *dResult (one double on the device) = u . v over n elements, in an order that is a function of n alone --
+ * not of the grid, the device, the stream, the alignment of the pointers or the run.  DESIGN.md section 19.  Every
+ * product u[i] * v[i] is rounded on its own (no FMA), then:
+ *     blocks of 4096 consecutive indices, block c = [4096 c, 4096 c + 4096), the last one padded with +0.0 products;
+ *     in block c, 256 lane partials from +0.0: lane t adds the products of indices 4096 c + 512 s + 2 t and
+ *         4096 c + 512 s + 2 t + 1 for s = 0, 1, ..., 7, in that (ascending) order;
+ *     the 256 lane partials a[0..255] meet in the tree: for h = 128, 64, 32, ..., 1: a[t] = a[t] + a[t + h], t < h;
+ *         the block partial is a[0];
+ *     the block partials P[0..nb-1] by the same rule: lane t adds P[t], P[t + 256], ... in order from +0.0, then the
+ *         same tree; the result is a[0].
+ *   n = 0 gives +0.0.  Pointers that are only 8-byte aligned give the same bits.  Kernels only, on the library stream: the
+ *   block partials go to a library workspace that grows (allocation, device synchronisation) at the first call with more
+ *   than any earlier n; calls up to that n only enqueue and can be captured into a graph.  Calls on different streams
+ *   share the workspace: keep them ordered.  spmvHipSetSync(1) waits and sets spmvHipLastKernelSeconds; spmvHipSetSync(0)
+ *   only enqueues.  spmvHipFinalize frees the workspace.  Refused (EXIT_FAILURE): a NULL dResult, a NULL dU or dV
+ *   when n > 0.
+ *
+ * hipSpCGCSR (A symmetric positive definite) and hipSpBiCGStabCSR (A square, right-preconditioned) solve A x = b on the
+ * device.  dX holds x0 on entry and x on return; dM NULL means no preconditioner, otherwise M^-1 v is
+ * hipSpTRSVCSR(dM, UPPER, STORED, hipSpTRSVCSR(dM, LOWER, UNIT, v)) -- the ILU(0) pair of hipSpILU0CSR; dM == dA is
+ * allowed.  x, info.status, info.iterations, info.rr and history are the bits of these loops, in IEEE double with no FMA:
+ * dot() is spmvHipDot, A v is serial-order SpMV (sgemvSerial's bits, spmvHipEnqueueAutoRows: its first call for a handle
+ * chooses the kernel), every a + s*v is two roundings in the order written, tol2 = tol*tol is computed on the host.
+ *     q = A x; r = b - q; rr = dot(r,r); bb = dot(b,b); thresh = tol2 * bb; hist[0] = rr
+ *     if rr <= thresh: CONVERGED, 0;  if rr is not finite: NONFINITE, 0;  if maxIter == 0: MAXITER, 0
+ *   CG                                            BiCGStab
+ *     z = M^-1 r (z = r without M)                  rhat = r; rho = rr; rho_old = alpha = omega = 1
+ *     rz = dot(r,z) (rz = rr without M); p = z      if rho == 0: BREAKDOWN, 0
+ *     for k = 1 .. maxIter:                         for k = 1 .. maxIter:
+ *       q = A p; pq = dot(p,q)                        p = k == 1 ? r : r + beta*(p - omega*v)
+ *       if pq == 0: BREAKDOWN, k-1                    phat = M^-1 p (phat = p without M); v = A phat; rv = dot(rhat,v)
+ *       alpha = rz / pq                               if rv == 0: BREAKDOWN, k-1
+ *       x = x + alpha*p; r = r - alpha*q              alpha = rho / rv; s = r - alpha*v; rr = dot(s,s); hist[k] = rr
+ *       rr = dot(r,r); hist[k] = rr                   if rr <= thresh: x = x + alpha*phat; CONVERGED, k
+ *       if rr <= thresh: CONVERGED, k                 shat = M^-1 s (shat = s without M); t = A shat
+ *       if rr is not finite: NONFINITE, k             tt = dot(t,t); ts = dot(t,s)
+ *       if k == maxIter: MAXITER, k                   if tt == 0: x = x + alpha*phat; BREAKDOWN, k
+ *       z = M^-1 r; rzn = dot(r,z)                    omega = ts / tt
+ *         (without M: z = r, rzn = rr)                x = (x + alpha*phat) + omega*shat; r = s - omega*t
+ *       beta = rzn / rz; rz = rzn                     rr = dot(r,r); hist[k] = rr; rhon = dot(rhat,r)
+ *       p = z + beta*p                                if rr <= thresh: CONVERGED, k
+ *                                                     if rr is not finite: NONFINITE, k
+ *                                                     if omega == 0: BREAKDOWN, k
+ *                                                     if k == maxIter: MAXITER, k
+ *                                                     rho_old = rho; rho = rhon; if rho == 0: BREAKDOWN, k
+ *                                                     beta = (rho / rho_old) * (alpha / omega)
+ *   "STATUS, j" ends the loop with info.status = STATUS and info.iterations = j.  info.rr is the last rr the loop set
+ *   (BiCGStab: dot(s,s) at a half-step exit), info.bb = bb; opts.history (NULL, or room for maxIter + 1 host doubles)
+ *   receives hist[0 .. iterations]; later entries are not written.
+ * Execution: the scalars and the status live in a device state block that the dot finish kernels write; every kernel
+ *   that writes x, r, p or the state, and every triangular solve of M, returns at once once the loop has stopped.  The host
+ *   enqueues K iterations, then reads the state back once (info.hostChecks); iterations past the stop write nothing.
+ *   K = 16 (spmvHipSetVariant("hipSpCGCSR" / "hipSpBiCGStabCSR", K), 1 <= K <= 4096); x does not change by a bit.
+ *   info.launches counts the kernels enqueued (an SpMV counted as one), info.ms the host wall time of the call.
+ *   Workspace (CG 3 vectors, 4 with M; BiCGStab 6, 8 with M; 16 B per 4096 rows; history) is allocated by the call and
+ *   freed before it returns; the triangles of dM are analysed by the call when they are not yet.  Synchronous, on the
+ *   library stream; not capturable.  M = 0 succeeds: CONVERGED, 0.
+ * Returns EXIT_SUCCESS whatever the status (info may be NULL).  Refused with a message and EXIT_FAILURE, x untouched:
+ *   NULL dA, dB, dX or opts, or a handle that is not live; ELL handles; M != N; dM of another size; dB and dX overlapping; tol negative or
+ *   NaN; a history with maxIter + 1 overflowing; for dM the limits of hipSpTRSVCSR and a row without exactly one diagonal
+ *   entry (STORED). */
+#define SPMV_KRYLOV_CONVERGED 0
+#define SPMV_KRYLOV_MAXITER   1
+#define SPMV_KRYLOV_BREAKDOWN 2
+#define SPMV_KRYLOV_NONFINITE 3
+typedef struct {
+    double  tol;            /* stop when dot(r,r) <= (tol*tol) * dot(b,b)                  */
+    ulong   maxIter;        /* iterations at most                                           */
+    double* history;        /* NULL, or maxIter + 1 host doubles: hist[0 .. iterations]      */
+} spmvKrylovOpts;
+typedef struct {
+    int    status;          /* SPMV_KRYLOV_*                                                 */
+    ulong  iterations;
+    double rr;              /* the last squared residual the loop computed                   */
+    double bb;              /* dot(b,b)                                                      */
+    ulong  launches;        /* kernels enqueued (an SpMV counted as one)                     */
+    ulong  hostChecks;      /* read-backs of the device state                                */
+    double ms;              /* host wall time of the call                                    */
+} spmvKrylovInfo;
+int spmvHipDot(size_t n, const double* dU, const double* dV, double* dResult);
+int hipSpCGCSR(spmat* dA, spmat* dM, const double* dB, double* dX, const spmvKrylovOpts* opts, spmvKrylovInfo* info);
+int hipSpBiCGStabCSR(spmat* dA, spmat* dM, const double* dB, double* dX, const spmvKrylovOpts* opts, spmvKrylovInfo* info);
 /* Release the device arrays behind a handle (cudaUtils.h:70-78). */
 int hipFreeSpmat(spmat* dMat);
 
@@ -469,6 +552,8 @@ int spmvHipProbeLdsAtomicOrder(void);
  *   hipSpTRSVCSR              T, 0..65536: the row threshold of the single-workgroup runs for triangles analysed after
  *                             the call (default 256; 0 = a launch per level).  x does not change by a bit.
  *   hipSpILU0CSR              8, 16 or 64: the lanes that factor one row (default 16).  AS does not change by a bit.
+ *   hipSpCGCSR, hipSpBiCGStabCSR  K, 1..4096: iterations enqueued per read-back of the solver's device state
+ *                             (default 16).  x does not change by a bit.
  * Returns EXIT_FAILURE for an unknown (launcher, variant). */
 int spmvHipSetVariant(const char* launcher, int variant);
 /* Use the RL array for ELL early exit (1, default when RL was uploaded) or walk

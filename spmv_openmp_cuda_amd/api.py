@@ -105,6 +105,9 @@ _sigs = {
     "spmvHipTriInfo": ([C.POINTER(spmat), _i, _vp], _i),
     "hipSpILU0CSR": ([C.POINTER(spmat)], _i),
     "spmvHipIlu0Info": ([C.POINTER(spmat), _vp], _i),
+    "spmvHipDot": ([_sz, _vp, _vp, _vp], _i),
+    "hipSpCGCSR": ([C.POINTER(spmat), C.POINTER(spmat), _vp, _vp, _vp, _vp], _i),
+    "hipSpBiCGStabCSR": ([C.POINTER(spmat), C.POINTER(spmat), _vp, _vp, _vp, _vp], _i),
 }
 SPMV_DENSE_ROW_MAJOR, SPMV_DENSE_COL_MAJOR = 0, 1          # include/spmvHip.h: layouts of hipSpMMRowsCSR's X and Y
 SPMV_TRI_LOWER, SPMV_TRI_UPPER = 0, 1                      # include/spmvHip.h: hipSpTRSVCSR's uplo ...
@@ -156,6 +159,20 @@ class spmvIluInfo(C.Structure):
     _fields_ = [("zeroPivot", C.c_long), ("firstBadRow", C.c_long), ("levels", C.c_ulong), ("launches", C.c_ulong),
                 ("longRows", C.c_ulong), ("factorisations", _i), ("ms", C.c_double)]
 
+
+class spmvKrylovOpts(C.Structure):
+    """include/spmvHip.h `spmvKrylovOpts`: tolerance, iteration cap, optional host history (maxIter + 1 doubles)."""
+    _fields_ = [("tol", C.c_double), ("maxIter", C.c_ulong), ("history", C.POINTER(C.c_double))]
+
+
+class spmvKrylovInfo(C.Structure):
+    """include/spmvHip.h `spmvKrylovInfo`: what a hipSpCGCSR / hipSpBiCGStabCSR call did."""
+    _fields_ = [("status", _i), ("iterations", C.c_ulong), ("rr", C.c_double), ("bb", C.c_double), ("launches", C.c_ulong),
+                ("hostChecks", C.c_ulong), ("ms", C.c_double)]
+
+
+SPMV_KRYLOV_CONVERGED, SPMV_KRYLOV_MAXITER, SPMV_KRYLOV_BREAKDOWN, SPMV_KRYLOV_NONFINITE = 0, 1, 2, 3
+KRYLOV_STATUS = {0: "converged", 1: "maxiter", 2: "breakdown", 3: "nonfinite"}
 
 IPC_HANDLE_BYTES = 64
 MAX_PEERS = 15
@@ -512,6 +529,51 @@ class DeviceMatrix:
         _check(lib.spmvHipIlu0Info(C.byref(self.handle), C.byref(info)), "spmvHipIlu0Info")
         return info
 
+    def cg(self, b, x0=None, precond=None, tol=1e-8, maxiter=1000, history=False):
+        """hipSpCGCSR: solve A x = b (A symmetric positive definite) on the device with the bits of the loop in
+        include/spmvHip.h; precond: None or a DeviceMatrix holding ILU(0) factors (`ilu0()`).  b (and x0): numpy arrays ->
+        x as numpy; or contiguous float64 device torch tensors -> x as a new torch tensor.  Returns (x, info) with
+        info.history a numpy array of the squared residuals hist[0 .. iterations] when history=True."""
+        return self._krylov(lib.hipSpCGCSR, "hipSpCGCSR", b, x0, precond, tol, maxiter, history)
+
+    def bicgstab(self, b, x0=None, precond=None, tol=1e-8, maxiter=1000, history=False):
+        """hipSpBiCGStabCSR: solve A x = b (A square) by right-preconditioned BiCGStab; arguments and result as cg()."""
+        return self._krylov(lib.hipSpBiCGStabCSR, "hipSpBiCGStabCSR", b, x0, precond, tol, maxiter, history)
+
+    def _krylov(self, fn, name, b, x0, precond, tol, maxiter, history):
+        N = int(self.handle.N)
+        hist = np.zeros(int(maxiter) + 1, np.float64) if history else None
+        opts = spmvKrylovOpts(float(tol), int(maxiter), hist.ctypes.data_as(C.POINTER(C.c_double)) if history else None)
+        info = spmvKrylovInfo()
+        mh = C.byref(precond.handle) if precond is not None else None
+        if isinstance(b, np.ndarray):
+            for t, what in ((b, "b"), (x0, "x0")):
+                if t is not None and (not isinstance(t, np.ndarray) or t.shape != (N,)):
+                    raise SpmvHipError(f"{name}: {what} must be a numpy array of shape ({N},)")
+            hb = np.ascontiguousarray(b, dtype=np.float64)
+            hx = np.zeros(N) if x0 is None else np.ascontiguousarray(x0, dtype=np.float64)
+            db, dx = DeviceBuffer(hb.nbytes).up(hb), DeviceBuffer(hx.nbytes).up(hx)
+            try:
+                _check(fn(C.byref(self.handle), mh, db.ptr, dx.ptr, C.byref(opts), C.byref(info)), name)
+                x = dx.down(np.float64)
+            finally:
+                db.free()
+                dx.free()
+        else:
+            import torch
+            for t, what in ((b, "b"), (x0, "x0")):
+                if t is None:
+                    continue
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous():
+                    raise SpmvHipError(f"{name}: {what} must be a contiguous float64 torch tensor on the device")
+                if t.dim() != 1 or t.shape[0] != N:
+                    raise SpmvHipError(f"{name}: {what} must have shape ({N},), not {tuple(t.shape)}")
+            x = torch.zeros_like(b) if x0 is None else x0.clone()
+            _check(fn(C.byref(self.handle), mh, b.data_ptr(), x.data_ptr(), C.byref(opts), C.byref(info)), name)
+        if history:
+            info.history = hist[:info.iterations + 1].copy()
+        return x, info
+
     def free(self):
         if self.handle.dev:
             lib.hipFreeSpmat(C.byref(self.handle))
@@ -589,6 +651,21 @@ def stripes_info(dmat: DeviceMatrix) -> spmvStripesInfo:
     info = spmvStripesInfo()
     _check(lib.spmvHipStripesInfo(C.byref(dmat.handle), C.byref(info)), "spmvHipStripesInfo")
     return info
+
+
+def dot(u, v):
+    """spmvHipDot: u . v of two float64 device torch tensors of one length (1-D, unit stride; any element offset) in the
+    fixed order of include/spmvHip.h, as a 0-d float64 tensor on the same device.  Runs on the library stream."""
+    import torch
+    for t, what in ((u, "u"), (v, "v")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or not t.is_cuda or t.dim() != 1 or \
+                (t.numel() > 1 and t.stride(0) != 1):
+            raise SpmvHipError(f"dot: {what} must be a 1-D float64 torch tensor on the device with unit stride")
+    if u.numel() != v.numel():
+        raise SpmvHipError(f"dot: lengths {u.numel()} and {v.numel()} differ")
+    out = torch.empty((), dtype=torch.float64, device=u.device)
+    _check(lib.spmvHipDot(u.numel(), u.data_ptr(), v.data_ptr(), out.data_ptr()), "spmvHipDot")
+    return out
 
 
 def set_variant(launcher: str, variant: int):

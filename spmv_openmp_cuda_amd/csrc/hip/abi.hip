@@ -28,6 +28,7 @@ struct State {
     int         variantEllRowMajor = 1; // hipSpMVRowsELLNNTransposed: 0 a thread walks its row in global memory, 1 LDS-stream kernel, same sums
     uint32_t    triRunRows = 256;       // hipSpTRSVCSR: T, the row threshold of the single-workgroup runs
     uint32_t    iluGroup = 16;          // hipSpILU0CSR: lanes per row
+    uint32_t    krylovK[2] = {16, 16};  // hipSpCGCSR, hipSpBiCGStabCSR: iterations per host check
     int         ldsOrder = -1;          // lds_order_probe_kernel: -1 not run yet, 1 lane-ascending + in issue order, 0 anything else
     bool        ellRowLens = true;
     bool        unitValues = true;      // look for "every stored value is the same double" at upload (spmvHipSetUnitValues)
@@ -573,6 +574,7 @@ int spmvHipFinalize(void) {
     if (!S.inited) return EXIT_SUCCESS;
     spmvHipDropCache();
     freeTilesWorkspace();
+    freeDotWorkspace();
     peerFinalize();
     if (g_pushSide) {
         (void)hipStreamSynchronize(g_pushSide);
@@ -636,6 +638,8 @@ int spmvHipSetVariant(const char* launcher, int variant) {
     if (!strcmp(launcher, "hipSpMVRowsELLNNTransposed") && variant >= 0 && variant <= 1) { S.variantEllRowMajor = variant; return EXIT_SUCCESS; }
     if (!strcmp(launcher, "hipSpTRSVCSR") && variant >= 0 && variant <= 65536) { S.triRunRows = (uint32_t)variant; return EXIT_SUCCESS; }
     if (!strcmp(launcher, "hipSpILU0CSR") && (variant == 8 || variant == 16 || variant == 64)) { S.iluGroup = (uint32_t)variant; return EXIT_SUCCESS; }
+    if (!strcmp(launcher, "hipSpCGCSR") && variant >= 1 && variant <= 4096) { S.krylovK[0] = (uint32_t)variant; return EXIT_SUCCESS; }
+    if (!strcmp(launcher, "hipSpBiCGStabCSR") && variant >= 1 && variant <= 4096) { S.krylovK[1] = (uint32_t)variant; return EXIT_SUCCESS; }
     ERR("spmvHipSetVariant: unknown (%s, %d)", launcher, variant);
     return EXIT_FAILURE;
 }
@@ -947,6 +951,60 @@ int spmvHipIlu0Info(spmat* dA, spmvIluInfo* info) {
     if (!info) { ERR("%s: info is NULL", who); return EXIT_FAILURE; }
     *info = d->ilu;
     return EXIT_SUCCESS;
+}
+
+// ---- Krylov solves (krylov.hip runs them; the contract is in spmvHip.h, the design in DESIGN.md section 19)
+int spmvHipDot(size_t n, const double* dU, const double* dV, double* dResult) {
+    const char* who = "spmvHipDot";
+    if (!ready(who)) return EXIT_FAILURE;
+    if (!dResult || (n && (!dU || !dV))) { ERR("%s: %s is NULL", who, !dResult ? "dResult" : !dU ? "dU" : "dV"); return EXIT_FAILURE; }
+    Launch L(dim3(1), dim3(256));
+    if (enqueueDot(n, dU, dV, dResult, S.stream)) { ERR("%s: launch failed", who); return EXIT_FAILURE; }
+    return L.finish(who);
+}
+
+static int krylov(int bicg, spmat* dA, spmat* dM, const double* dB, double* dX, const spmvKrylovOpts* opts, spmvKrylovInfo* info) {
+    const char* who = bicg ? "hipSpBiCGStabCSR" : "hipSpCGCSR";
+    if (!ready(who)) return EXIT_FAILURE;
+    if (!dB || !dX || !opts) { ERR("%s: %s is NULL", who, !dB ? "dB" : !dX ? "dX" : "opts"); return EXIT_FAILURE; }
+    DevMat* a = descOf(dA, who);
+    if (!a) return EXIT_FAILURE;
+    if (a->kind != Kind::CSR) { ERR("%s: dA is an ELL handle (only CSR handles are solved)", who); return EXIT_FAILURE; }
+    if (a->M != a->N) { ERR("%s: M=%lu != N=%lu: dA is not square", who, (unsigned long)a->M, (unsigned long)a->N); return EXIT_FAILURE; }
+    if (a->NZ && !a->AS && !a->unit) { ERR("%s: dA has no value array", who); return EXIT_FAILURE; }
+    const uintptr_t b0 = (uintptr_t)dB, x0 = (uintptr_t)dX, bytes = a->M * sizeof(double);
+    if (a->M && b0 < x0 + bytes && x0 < b0 + bytes) { ERR("%s: dB and dX overlap", who); return EXIT_FAILURE; }
+    if (!(opts->tol >= 0.0)) { ERR("%s: tol %g is negative or NaN", who, opts->tol); return EXIT_FAILURE; }
+    if (opts->history && opts->maxIter >= (SIZE_MAX / sizeof(double)) - 1) {
+        ERR("%s: a history of maxIter + 1 = %lu + 1 doubles does not fit", who, (unsigned long)opts->maxIter);
+        return EXIT_FAILURE;
+    }
+    DevMat* m = nullptr;
+    if (dM) {
+        if (!(m = triHandle(dM, SPMV_TRI_LOWER, who))) return EXIT_FAILURE;
+        if (m->M != a->M) { ERR("%s: dM has %lu rows, dA %lu", who, (unsigned long)m->M, (unsigned long)a->M); return EXIT_FAILURE; }
+        if (m->NZ && !m->AS && !m->unit) { ERR("%s: dM has no value array", who); return EXIT_FAILURE; }
+        for (int uplo : {SPMV_TRI_LOWER, SPMV_TRI_UPPER})
+            if (m->M && !m->tri[uplo] && triAnalyse(m, uplo, S.triRunRows, S.stream)) { ERR("%s: the analysis of dM failed", who); return EXIT_FAILURE; }
+        if (m->M && m->tri[SPMV_TRI_UPPER]->info.firstBadDiag >= 0) {
+            ERR("%s: row %ld of dM does not hold exactly one stored diagonal entry (M^-1 divides by it)", who,
+                m->tri[SPMV_TRI_UPPER]->info.firstBadDiag);
+            return EXIT_FAILURE;
+        }
+    }
+    if (a->M == 0) {
+        if (opts->history) opts->history[0] = 0.0;
+        if (info) *info = spmvKrylovInfo{SPMV_KRYLOV_CONVERGED, 0, 0.0, 0.0, 0, 0, 0.0};
+        return EXIT_SUCCESS;
+    }
+    if (krylovSolve(bicg, dA, a, m, dB, dX, opts, info, S.krylovK[bicg], S.stream)) { ERR("%s: the solve failed", who); return EXIT_FAILURE; }
+    return EXIT_SUCCESS;
+}
+int hipSpCGCSR(spmat* dA, spmat* dM, const double* dB, double* dX, const spmvKrylovOpts* opts, spmvKrylovInfo* info) {
+    return krylov(0, dA, dM, dB, dX, opts, info);
+}
+int hipSpBiCGStabCSR(spmat* dA, spmat* dM, const double* dB, double* dX, const spmvKrylovOpts* opts, spmvKrylovInfo* info) {
+    return krylov(1, dA, dM, dB, dX, opts, info);
 }
 
 int spmvHipUpdateValues(spmat* dMat, const double* AS, int asOnDevice) {

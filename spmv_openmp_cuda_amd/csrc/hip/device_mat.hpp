@@ -152,9 +152,11 @@ void enqueueSortedBounds(uint64_t nnz, uint64_t N, const uint32_t* keys, uint32_
 void enqueueRowOf(uint64_t M, const void* IRP, int irpBytes, uint32_t* rowOf, hipStream_t stream);
 // Triangular solves (trsv.hip; contract in spmvHip.h, design in DESIGN.md section 17).  triAnalyse builds d->tri[uplo]
 // (synchronous, allocates, temporaries freed before it returns; runThreshold = the T of the single-workgroup runs, 0: none);
-// enqueueTrsv enqueues one solve of an analysed triangle on `stream` (no allocation, no sync) and reports the last launch.
+// enqueueTrsv enqueues one solve of an analysed triangle on `stream` (no allocation, no sync) and reports the last launch;
+// every launch returns at once when `stop` is set and *stop != 0 when it starts (a stopped Krylov loop, krylov.hip).
 int  triAnalyse(DevMat* d, int uplo, uint32_t runThreshold, hipStream_t stream);
-int  enqueueTrsv(const DevMat* d, int uplo, int diag, const double* b, double* x, hipStream_t stream, dim3* grid, dim3* block);
+int  enqueueTrsv(const DevMat* d, int uplo, int diag, const double* b, double* x, hipStream_t stream, dim3* grid, dim3* block,
+                 const uint32_t* stop = nullptr);
 void triInfo(const DevMat* d, int uplo, spmvTriInfo* out);
 void freeTri(TriSchedule* s);
 // ILU(0) in place on the lower schedule d->tri[SPMV_TRI_LOWER] (ilu0.hip; contract in spmvHip.h, design in DESIGN.md section
@@ -163,6 +165,14 @@ void freeTri(TriSchedule* s);
 // per row; fills d->ilu's zeroPivot, levels, launches and longRows.
 int  iluUnsortedRow(const DevMat* d, hipStream_t stream, long* row);
 int  iluFactor(DevMat* d, uint32_t groupWidth, hipStream_t stream);
+// Krylov solves (krylov.hip; contract in spmvHip.h, design in DESIGN.md section 19).  enqueueDot: the fixed-order dot
+// product into one device double on `stream`, its block partials in a library workspace grown (synchronously) when a call
+// needs more; freeDotWorkspace gives it back.  krylovSolve: CG (bicg = 0) or BiCGStab on the checked handles a / hA, m the
+// analysed ILU(0) handle or null, K iterations per host check; allocates its workspace, synchronous.
+int  enqueueDot(uint64_t n, const double* u, const double* v, double* result, hipStream_t stream);
+void freeDotWorkspace();
+int  krylovSolve(int bicg, spmat* hA, const DevMat* a, const DevMat* m, const double* b, double* x, const spmvKrylovOpts* opts,
+                 spmvKrylovInfo* info, uint32_t K, hipStream_t stream);
 int  enqueueGatherValues(double* val, const uint32_t* map, uint64_t n, const double* AS, hipStream_t stream);   // values.hip
 int  enqueueScatterValues(double* val, const uint32_t* map, uint64_t n, const double* AS, hipStream_t stream);
 int  enqueueSellValues(uint32_t nSlices, const uint64_t* sliceOff, const uint32_t* perm, const uint32_t* slen, const void* IRP,

@@ -1,0 +1,520 @@
+// krylov.hip -- a fixed-order dot product (spmvHipDot) and the two Krylov solvers hipSpCGCSR / hipSpBiCGStabCSR on a
+// device CSR handle (contract in spmvHip.h, design in DESIGN.md section 19).  x, the iteration count and every residual
+// norm are the bits of the loops written out in spmvHip.h.
+//
+// The dot: blocks of KB = 4096 indices, 256 lanes a block; lane t adds the products of elements 2t, 2t+1 of each of the
+// block's eight 512-element slices in ascending index order from +0.0 (16-byte loads when every pointer allows, scalar
+// loads otherwise: the same order), then the lanes' partials meet in the fixed tree a[t] += a[t + h], h = 128, 64, ..., 1.
+// A second, single-workgroup kernel adds the block partials by the same rule (lane t: partials t, t + 256, ... in order,
+// then the tree).  Ordering across workgroups comes only from that kernel boundary: no flags, tickets or spins.
+//
+// The solvers: every vector update of the loop is fused with the partials of the dot that follows it (x += alpha p,
+// r -= alpha q and the partials of r.r in one pass), and every finish kernel also computes the loop's scalars and its
+// status into a small device state block.  Every kernel that writes x, r, p or the state reads that block first and
+// returns once the loop has stopped; so does every triangular solve of the preconditioner (a stop pointer).  The host
+// enqueues K iterations at a time and reads the block back once per batch: iterations enqueued past the stop write
+// nothing, and x is the loop's x however far the host overshoots.
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdio>
+#include <vector>
+
+#include "spmvHip.h"
+#include "kernels.hpp"
+
+namespace spmvhip {
+namespace {
+
+constexpr uint32_t KT = 256;                    // lanes of a block (partials) and of the finish workgroup
+constexpr uint32_t KB = 4096;                   // indices of a block
+constexpr uint32_t KSLICES = KB / (2 * KT);     // 8 slices of 512 indices, two per lane
+constexpr uint32_t KCHUNK = 4;                  // slices whose loads a lane issues together
+
+// the loop's scalars and its status (written only by the finish kernels, by one lane)
+struct KState {
+    uint32_t stop;          // 0 while the loop runs
+    int32_t  status;        // SPMV_KRYLOV_* once stopped
+    uint64_t iterations;
+    uint64_t halfK;         // BiCGStab: the iteration whose x = x + alpha*phat is still to be written (0: none)
+    uint64_t maxIter;
+    double   tol2, rr, bb, thresh, rz, alpha, beta, omega, rho, rhoOld;
+};
+
+enum Phase : int { F_DOT, F_CG_INIT, F_CG_RZ, F_CG_ALPHA, F_CG_RR, F_BI_INIT, F_BI_ALPHA, F_BI_SS, F_BI_OMEGA, F_BI_RR };
+
+template <bool VEC>
+__device__ __forceinline__ double2 ld2(const double* p, uint64_t i, bool two) {
+    if (VEC && two) return *reinterpret_cast<const double2*>(p + i);
+    return make_double2(p[i], two ? p[i + 1] : 0.0);
+}
+template <bool VEC>
+__device__ __forceinline__ void st2(double* p, uint64_t i, bool two, double2 v) {
+    if (VEC && two) { *reinterpret_cast<double2*>(p + i) = v; return; }
+    p[i] = v.x;
+    if (two) p[i + 1] = v.y;
+}
+// acc += a.x * b.x, then a.y * b.y when the pair is whole (a missing element adds nothing: acc is never -0.0)
+__device__ __forceinline__ void madd(double& acc, double2 a, double2 b, bool two) {
+    acc += a.x * b.x;
+    if (two) acc += a.y * b.y;
+}
+
+// ------------------------------------------------------------------------------------------------ the fused passes
+// Each op: NDOT dots whose partials it produces, mode(st) (0: write nothing; the stopped loop), load() the inputs of
+// one element pair, step() the update and the products in order.
+struct DotOp {                                  // u . v
+    static constexpr int NDOT = 1;
+    const double* u; const double* v;
+    struct R { double2 u, v; };
+    __device__ int mode(const KState*) const { return 1; }
+    template <bool VEC> __device__ void load(uint64_t i, bool two, R& r) const { r.u = ld2<VEC>(u, i, two); r.v = ld2<VEC>(v, i, two); }
+    template <bool VEC> __device__ void step(uint64_t, bool two, const R& r, double& a0, double&) const { madd(a0, r.u, r.v, two); }
+};
+
+struct GuardedDot : DotOp {                     // u . v inside a solve
+    __device__ int mode(const KState* st) const { return !st->stop; }
+};
+
+struct TtTsOp {                                 // t . t and t . s
+    static constexpr int NDOT = 2;
+    const double* t; const double* s;
+    struct R { double2 t, s; };
+    __device__ int mode(const KState* st) const { return !st->stop; }
+    template <bool VEC> __device__ void load(uint64_t i, bool two, R& r) const { r.t = ld2<VEC>(t, i, two); r.s = ld2<VEC>(s, i, two); }
+    template <bool VEC> __device__ void step(uint64_t, bool two, const R& r, double& a0, double& a1) const {
+        madd(a0, r.t, r.t, two);
+        madd(a1, r.t, r.s, two);
+    }
+};
+
+struct InitOp {                                 // r = b - q (rhat = r too when given); r . r and b . b
+    static constexpr int NDOT = 2;
+    const double* b; const double* q; double* r; double* rhat;
+    struct R { double2 b, q; };
+    __device__ int mode(const KState*) const { return 1; }
+    template <bool VEC> __device__ void load(uint64_t i, bool two, R& x) const { x.b = ld2<VEC>(b, i, two); x.q = ld2<VEC>(q, i, two); }
+    template <bool VEC> __device__ void step(uint64_t i, bool two, const R& x, double& a0, double& a1) const {
+        const double2 rv = make_double2(x.b.x - x.q.x, x.b.y - x.q.y);
+        st2<VEC>(r, i, two, rv);
+        if (rhat) st2<VEC>(rhat, i, two, rv);
+        madd(a0, rv, rv, two);
+        madd(a1, x.b, x.b, two);
+    }
+};
+
+struct CgUpdateOp {                             // x = x + alpha*p; r = r - alpha*q; r . r
+    static constexpr int NDOT = 1;
+    double* x; const double* p; double* r; const double* q;
+    mutable double alpha;
+    struct R { double2 x, p, r, q; };
+    __device__ int mode(const KState* st) const { if (st->stop) return 0; alpha = st->alpha; return 1; }
+    template <bool VEC> __device__ void load(uint64_t i, bool two, R& v) const {
+        v.x = ld2<VEC>(x, i, two); v.p = ld2<VEC>(p, i, two); v.r = ld2<VEC>(r, i, two); v.q = ld2<VEC>(q, i, two);
+    }
+    template <bool VEC> __device__ void step(uint64_t i, bool two, const R& v, double& a0, double&) const {
+        const double2 xn = make_double2(v.x.x + alpha * v.p.x, v.x.y + alpha * v.p.y);
+        const double2 rn = make_double2(v.r.x - alpha * v.q.x, v.r.y - alpha * v.q.y);
+        st2<VEC>(x, i, two, xn);
+        st2<VEC>(r, i, two, rn);
+        madd(a0, rn, rn, two);
+    }
+};
+
+struct CgPOp {                                  // p = z (first) or p = z + beta*p
+    static constexpr int NDOT = 0;
+    const double* z; double* p; int first;
+    mutable double beta;
+    struct R { double2 z, p; };
+    __device__ int mode(const KState* st) const { if (st->stop) return 0; beta = st->beta; return 1; }
+    template <bool VEC> __device__ void load(uint64_t i, bool two, R& v) const {
+        v.z = ld2<VEC>(z, i, two);
+        if (!first) v.p = ld2<VEC>(p, i, two);
+    }
+    template <bool VEC> __device__ void step(uint64_t i, bool two, const R& v, double&, double&) const {
+        st2<VEC>(p, i, two, first ? v.z : make_double2(v.z.x + beta * v.p.x, v.z.y + beta * v.p.y));
+    }
+};
+
+struct BiPOp {                                  // p = r (first) or p = r + beta*(p - omega*v)
+    static constexpr int NDOT = 0;
+    const double* r; double* p; const double* v; int first;
+    mutable double beta, omega;
+    struct R { double2 r, p, v; };
+    __device__ int mode(const KState* st) const { if (st->stop) return 0; beta = st->beta; omega = st->omega; return 1; }
+    template <bool VEC> __device__ void load(uint64_t i, bool two, R& x) const {
+        x.r = ld2<VEC>(r, i, two);
+        if (!first) { x.p = ld2<VEC>(p, i, two); x.v = ld2<VEC>(v, i, two); }
+    }
+    template <bool VEC> __device__ void step(uint64_t i, bool two, const R& x, double&, double&) const {
+        if (first) { st2<VEC>(p, i, two, x.r); return; }
+        const double d0 = x.p.x - omega * x.v.x, d1 = x.p.y - omega * x.v.y;
+        st2<VEC>(p, i, two, make_double2(x.r.x + beta * d0, x.r.y + beta * d1));
+    }
+};
+
+struct SOp {                                    // s = r - alpha*v; s . s
+    static constexpr int NDOT = 1;
+    const double* r; const double* v; double* s;
+    mutable double alpha;
+    struct R { double2 r, v; };
+    __device__ int mode(const KState* st) const { if (st->stop) return 0; alpha = st->alpha; return 1; }
+    template <bool VEC> __device__ void load(uint64_t i, bool two, R& x) const { x.r = ld2<VEC>(r, i, two); x.v = ld2<VEC>(v, i, two); }
+    template <bool VEC> __device__ void step(uint64_t i, bool two, const R& x, double& a0, double&) const {
+        const double2 sn = make_double2(x.r.x - alpha * x.v.x, x.r.y - alpha * x.v.y);
+        st2<VEC>(s, i, two, sn);
+        madd(a0, sn, sn, two);
+    }
+};
+
+// running: x = (x + alpha*phat) + omega*shat; r = s - omega*t; r . r and rhat . r.  Stopped at a half step of THIS
+// iteration (halfK == k): x = x + alpha*phat only.
+struct BiUpdateOp {
+    static constexpr int NDOT = 2;
+    double* x; const double* phat; const double* shat; double* r; const double* s; const double* t; const double* rhat;
+    uint64_t k;
+    mutable double alpha, omega;
+    mutable int full;
+    struct R { double2 x, ph, sh, s, t, rh; };
+    __device__ int mode(const KState* st) const {
+        full = !st->stop;
+        if (!full && st->halfK != k) return 0;
+        alpha = st->alpha; omega = st->omega;
+        return 1;
+    }
+    template <bool VEC> __device__ void load(uint64_t i, bool two, R& v) const {
+        v.x = ld2<VEC>(x, i, two); v.ph = ld2<VEC>(phat, i, two);
+        if (full) { v.sh = ld2<VEC>(shat, i, two); v.s = ld2<VEC>(s, i, two); v.t = ld2<VEC>(t, i, two); v.rh = ld2<VEC>(rhat, i, two); }
+    }
+    template <bool VEC> __device__ void step(uint64_t i, bool two, const R& v, double& a0, double& a1) const {
+        const double h0 = v.x.x + alpha * v.ph.x, h1 = v.x.y + alpha * v.ph.y;
+        if (!full) { st2<VEC>(x, i, two, make_double2(h0, h1)); return; }
+        st2<VEC>(x, i, two, make_double2(h0 + omega * v.sh.x, h1 + omega * v.sh.y));
+        const double2 rn = make_double2(v.s.x - omega * v.t.x, v.s.y - omega * v.t.y);
+        st2<VEC>(r, i, two, rn);
+        madd(a0, rn, rn, two);
+        madd(a1, v.rh, rn, two);
+    }
+};
+
+// the fixed tree over the 256 lanes of a workgroup: a[t] += a[t + h] for t < h, h = 128, 64, ..., 1; valid in lane 0
+__device__ __forceinline__ double2 tree256(double2 a, double2* sh) {
+    const uint32_t t = threadIdx.x;
+    sh[t] = a;
+    __syncthreads();
+#pragma unroll
+    for (uint32_t h = KT / 2; h >= 1; h >>= 1) {
+        if (t < h) {
+            const double2 o = sh[t + h], m = sh[t];
+            sh[t] = make_double2(m.x + o.x, m.y + o.y);
+        }
+        __syncthreads();
+    }
+    return sh[0];
+}
+
+// one block of KB indices: the op's update on them, and its dots' block partials into part0 / part1
+template <class Op, bool VEC>
+__global__ __launch_bounds__(KT) void krylov_vec_kernel(uint64_t n, const KState* __restrict__ st, Op op,
+                                                        double* __restrict__ part0, double* __restrict__ part1) {
+    __shared__ double2 sh[KT];
+    const uint64_t blk = linear_block();
+    if (blk * KB >= n || !op.mode(st)) return;                           // (a folded grid's tail); uniform: the state
+    const uint64_t base = blk * KB + 2 * threadIdx.x;
+    double a0 = 0.0, a1 = 0.0;
+#pragma unroll
+    for (uint32_t c = 0; c < KSLICES; c += KCHUNK) {
+        typename Op::R r[KCHUNK];
+#pragma unroll
+        for (uint32_t u = 0; u < KCHUNK; ++u) {
+            const uint64_t i = base + (uint64_t)(c + u) * (2 * KT);
+            if (i < n) op.template load<VEC>(i, i + 1 < n, r[u]);
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < KCHUNK; ++u) {
+            const uint64_t i = base + (uint64_t)(c + u) * (2 * KT);
+            if (i < n) op.template step<VEC>(i, i + 1 < n, r[u], a0, a1);
+        }
+    }
+    if (Op::NDOT == 0) return;
+    const double2 s = tree256(make_double2(a0, a1), sh);
+    if (threadIdx.x == 0) {
+        part0[blk] = s.x;
+        if (Op::NDOT > 1) part1[blk] = s.y;
+    }
+}
+
+// the block partials of one or two dots, by the same rule: lane t adds partials t, t + 256, ... in order, then the tree.
+// Lane 0 then runs the loop's scalar step `ph` for iteration k.
+__global__ __launch_bounds__(KT) void krylov_finish_kernel(uint64_t nb, const double* __restrict__ part0,
+                                                           const double* __restrict__ part1, int ph, uint64_t k, KState* st,
+                                                           double* hist, double* out, int precond) {
+    __shared__ double2 sh[KT];
+    if (ph != F_DOT && ph != F_CG_INIT && ph != F_BI_INIT && st->stop) return;
+    double a0 = 0.0, a1 = 0.0;
+    for (uint64_t j = threadIdx.x; j < nb; j += KT) {
+        a0 += part0[j];
+        if (part1) a1 += part1[j];
+    }
+    const double2 d = tree256(make_double2(a0, a1), sh);
+    if (threadIdx.x != 0) return;
+    auto stopAt = [&](int status, uint64_t it) { st->status = status; st->iterations = it; st->stop = 1; };
+    switch (ph) {
+    case F_DOT:
+        *out = d.x;
+        break;
+    case F_CG_INIT:
+    case F_BI_INIT: {
+        const double rr = d.x, bb = d.y, thresh = st->tol2 * bb;
+        st->rr = rr; st->bb = bb; st->thresh = thresh;
+        st->iterations = 0; st->halfK = 0; st->stop = 0; st->status = SPMV_KRYLOV_MAXITER;
+        if (hist) hist[0] = rr;
+        if (rr <= thresh) { stopAt(SPMV_KRYLOV_CONVERGED, 0); break; }
+        if (!isfinite(rr)) { stopAt(SPMV_KRYLOV_NONFINITE, 0); break; }
+        if (st->maxIter == 0) { stopAt(SPMV_KRYLOV_MAXITER, 0); break; }
+        if (ph == F_CG_INIT) {
+            if (!precond) st->rz = rr;
+        } else {
+            st->rho = rr; st->rhoOld = 1.0; st->alpha = 1.0; st->omega = 1.0;
+            if (rr == 0.0) stopAt(SPMV_KRYLOV_BREAKDOWN, 0);
+        }
+        break;
+    }
+    case F_CG_RZ:                                                        // rz = dot(r, z) (k = 0), else beta = rzn / rz
+        if (k == 0) st->rz = d.x;
+        else { st->beta = d.x / st->rz; st->rz = d.x; }
+        break;
+    case F_CG_ALPHA:
+        if (d.x == 0.0) stopAt(SPMV_KRYLOV_BREAKDOWN, k - 1);
+        else st->alpha = st->rz / d.x;
+        break;
+    case F_CG_RR: {
+        const double rr = d.x;
+        st->rr = rr;
+        if (hist) hist[k] = rr;
+        if (rr <= st->thresh) stopAt(SPMV_KRYLOV_CONVERGED, k);
+        else if (!isfinite(rr)) stopAt(SPMV_KRYLOV_NONFINITE, k);
+        else if (k == st->maxIter) stopAt(SPMV_KRYLOV_MAXITER, k);
+        else if (!precond) { st->beta = rr / st->rz; st->rz = rr; }
+        break;
+    }
+    case F_BI_ALPHA:
+        if (d.x == 0.0) stopAt(SPMV_KRYLOV_BREAKDOWN, k - 1);
+        else st->alpha = st->rho / d.x;
+        break;
+    case F_BI_SS:
+        st->rr = d.x;
+        if (hist) hist[k] = d.x;
+        if (d.x <= st->thresh) { st->halfK = k; stopAt(SPMV_KRYLOV_CONVERGED, k); }
+        break;
+    case F_BI_OMEGA:
+        if (d.x == 0.0) { st->halfK = k; stopAt(SPMV_KRYLOV_BREAKDOWN, k); }
+        else st->omega = d.y / d.x;
+        break;
+    case F_BI_RR: {
+        const double rr = d.x;
+        st->rr = rr;
+        if (hist) hist[k] = rr;
+        if (rr <= st->thresh) stopAt(SPMV_KRYLOV_CONVERGED, k);
+        else if (!isfinite(rr)) stopAt(SPMV_KRYLOV_NONFINITE, k);
+        else if (st->omega == 0.0) stopAt(SPMV_KRYLOV_BREAKDOWN, k);
+        else if (k == st->maxIter) stopAt(SPMV_KRYLOV_MAXITER, k);
+        else {
+            st->rhoOld = st->rho;
+            st->rho = d.y;
+            if (d.y == 0.0) stopAt(SPMV_KRYLOV_BREAKDOWN, k);
+            else st->beta = (st->rho / st->rhoOld) * (st->alpha / st->omega);
+        }
+        break;
+    }
+    default:
+        break;
+    }
+}
+
+uint64_t blocksOf(uint64_t n) { return (n + KB - 1) / KB; }
+bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+template <class Op>
+void launchVec(uint64_t n, const KState* st, const Op& op, bool vec, double* p0, double* p1, hipStream_t s) {
+    const uint64_t nb = blocksOf(n);
+    if (!nb) return;
+    const dim3 grid = grid2d(nb, KT);
+    if (vec) hipLaunchKernelGGL((krylov_vec_kernel<Op, true>), grid, dim3(KT), 0, s, n, st, op, p0, p1);
+    else     hipLaunchKernelGGL((krylov_vec_kernel<Op, false>), grid, dim3(KT), 0, s, n, st, op, p0, p1);
+}
+
+void launchFinish(uint64_t n, const double* p0, const double* p1, int ph, uint64_t k, KState* st, double* hist, double* out,
+                  int precond, hipStream_t s) {
+    hipLaunchKernelGGL(krylov_finish_kernel, dim3(1), dim3(KT), 0, s, blocksOf(n), p0, p1, ph, k, st, hist, out, precond);
+}
+
+// the public dot's block partials: a library workspace, grown (synchronously) by the first call that needs more
+struct DotWorkspace { double* p = nullptr; uint64_t blocks = 0; int dev = -1; } g_dot;
+
+struct DevBufs {
+    std::vector<void*> ptrs;
+    ~DevBufs() { for (void* p : ptrs) (void)hipFree(p); }
+    template <typename T> T* alloc(size_t count) {
+        void* p = nullptr;
+        if (hipMalloc(&p, std::max<size_t>(count * sizeof(T), 16)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+        ptrs.push_back(p);
+        return static_cast<T*>(p);
+    }
+};
+
+}  // namespace
+
+void freeDotWorkspace() {
+    if (g_dot.p) (void)hipFree(g_dot.p);
+    g_dot = DotWorkspace{};
+}
+
+int enqueueDot(uint64_t n, const double* u, const double* v, double* result, hipStream_t st) {
+    const uint64_t nb = blocksOf(n);
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    if (nb > g_dot.blocks || dev != g_dot.dev) {
+        HIP_TRY(hipDeviceSynchronize());                                 // the old workspace may still be read
+        freeDotWorkspace();
+        HIP_TRY(hipMalloc(&g_dot.p, std::max<uint64_t>(nb, 1) * sizeof(double)));
+        g_dot.blocks = std::max<uint64_t>(nb, 1);
+        g_dot.dev = dev;
+    }
+    launchVec(n, nullptr, DotOp{u, v}, aligned16(u) && aligned16(v), g_dot.p, nullptr, st);
+    launchFinish(n, g_dot.p, nullptr, F_DOT, 0, nullptr, nullptr, result, 0, st);
+    return hipGetLastError() == hipSuccess ? EXIT_SUCCESS : EXIT_FAILURE;
+}
+
+int krylovSolve(int bicg, spmat* hA, const DevMat* a, const DevMat* m, const double* b, double* x, const spmvKrylovOpts* o,
+                spmvKrylovInfo* info, uint32_t K, hipStream_t s) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint64_t n = a->M, nb = std::max<uint64_t>(blocksOf(n), 1);
+    const int pre = m != nullptr;
+    spmvKrylovInfo out{};
+    DevBufs w;
+    const int nvec = bicg ? (pre ? 8 : 6) : (pre ? 4 : 3);
+    double* v[8] = {};
+    for (int i = 0; i < nvec; ++i)
+        if (!(v[i] = w.alloc<double>(n))) { fprintf(stderr, "libspmvhip: Krylov solve: workspace allocation failed\n"); return EXIT_FAILURE; }
+    double* part = w.alloc<double>(2 * nb);
+    KState* st = w.alloc<KState>(1);
+    double* hist = o->history ? w.alloc<double>(o->maxIter + 1) : nullptr;
+    if (!part || !st || (o->history && !hist)) { fprintf(stderr, "libspmvhip: Krylov solve: workspace allocation failed\n"); return EXIT_FAILURE; }
+    double* p0 = part;
+    double* p1 = part + nb;
+    KState h{};
+    h.maxIter = o->maxIter;
+    h.tol2 = o->tol * o->tol;
+    HIP_TRY(hipMemcpyAsync(st, &h, sizeof h, hipMemcpyHostToDevice, s));
+    spmvTriInfo tl{}, tu{};
+    if (pre) { triInfo(m, SPMV_TRI_LOWER, &tl); triInfo(m, SPMV_TRI_UPPER, &tu); }
+    const uint32_t* stop = &st->stop;
+    dim3 g, bl;
+    auto precond = [&](const double* in, double* outv) {                 // outv = U^-1 (L^-1 in): the ILU(0) pair of dM
+        enqueueTrsv(m, SPMV_TRI_LOWER, SPMV_DIAG_UNIT, in, outv, s, &g, &bl, stop);
+        enqueueTrsv(m, SPMV_TRI_UPPER, SPMV_DIAG_STORED, outv, outv, s, &g, &bl, stop);
+        out.launches += tl.launches + tu.launches;
+    };
+    auto spmv = [&](double* in, double* outv) {
+        ++out.launches;
+        return spmvHipEnqueueAutoRows(hA, in, outv, s);
+    };
+    auto vec = [&](const auto& op, std::initializer_list<const void*> ptrs) {
+        bool al = true;
+        for (const void* p : ptrs) al = al && aligned16(p);
+        launchVec(n, st, op, al, p0, p1, s);
+        ++out.launches;
+    };
+    auto finish = [&](int ph, uint64_t k, int ndot) {
+        launchFinish(n, p0, ndot > 1 ? p1 : nullptr, ph, k, st, hist, nullptr, pre, s);
+        ++out.launches;
+    };
+    // r, p, q (, z) / r, rhat, p, v, s, t (, phat, shat)
+    double* r = v[0];
+    double* q = v[2];
+    if (spmv(x, q)) return EXIT_FAILURE;                                 // the first call for a handle chooses the kernel
+    if (!bicg) {
+        double* p = v[1];
+        double* z = pre ? v[3] : r;
+        vec(InitOp{b, q, r, nullptr}, {b, q, r});
+        finish(F_CG_INIT, 0, 2);
+        if (pre) {
+            precond(r, z);
+            vec(GuardedDot{{r, z}}, {r, z});
+            finish(F_CG_RZ, 0, 1);
+        }
+        vec(CgPOp{z, p, 1, 0.0}, {z, p});
+        for (uint64_t k = 1; k <= o->maxIter;) {
+            const uint64_t end = std::min<uint64_t>(o->maxIter, k + K - 1);
+            for (; k <= end; ++k) {
+                if (spmv(p, q)) return EXIT_FAILURE;
+                vec(GuardedDot{{p, q}}, {p, q});
+                finish(F_CG_ALPHA, k, 1);
+                vec(CgUpdateOp{x, p, r, q, 0.0}, {x, p, r, q});
+                finish(F_CG_RR, k, 1);
+                if (pre) {
+                    precond(r, z);
+                    vec(GuardedDot{{r, z}}, {r, z});
+                    finish(F_CG_RZ, k, 1);
+                }
+                vec(CgPOp{z, p, 0, 0.0}, {z, p});
+            }
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(&h, st, sizeof h, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            ++out.hostChecks;
+            if (h.stop) break;
+        }
+    } else {
+        double* rhat = v[1];
+        double* p = v[3];
+        double* vv = v[4];
+        double* sv = v[5];
+        double* t = q;
+        double* phat = pre ? v[6] : p;
+        double* shat = pre ? v[7] : sv;
+        vec(InitOp{b, q, r, rhat}, {b, q, r, rhat});
+        finish(F_BI_INIT, 0, 2);
+        for (uint64_t k = 1; k <= o->maxIter;) {
+            const uint64_t end = std::min<uint64_t>(o->maxIter, k + K - 1);
+            for (; k <= end; ++k) {
+                vec(BiPOp{r, p, vv, k == 1, 0.0, 0.0}, {r, p, vv});
+                if (pre) precond(p, phat);
+                if (spmv(phat, vv)) return EXIT_FAILURE;
+                vec(GuardedDot{{rhat, vv}}, {rhat, vv});
+                finish(F_BI_ALPHA, k, 1);
+                vec(SOp{r, vv, sv, 0.0}, {r, vv, sv});
+                finish(F_BI_SS, k, 1);
+                if (pre) precond(sv, shat);
+                if (spmv(shat, t)) return EXIT_FAILURE;
+                vec(TtTsOp{t, sv}, {t, sv});
+                finish(F_BI_OMEGA, k, 2);
+                vec(BiUpdateOp{x, phat, shat, r, sv, t, rhat, k, 0.0, 0.0, 0}, {x, phat, shat, r, sv, t, rhat});
+                finish(F_BI_RR, k, 2);
+            }
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(&h, st, sizeof h, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            ++out.hostChecks;
+            if (h.stop) break;
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&h, st, sizeof h, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (!h.stop) { fprintf(stderr, "libspmvhip: Krylov solve: the loop did not stop\n"); return EXIT_FAILURE; }
+    if (o->history) {
+        HIP_TRY(hipMemcpy(o->history, hist, (h.iterations + 1) * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    out.status = h.status;
+    out.iterations = h.iterations;
+    out.rr = h.rr;
+    out.bb = h.bb;
+    out.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (info) *info = out;
+    return EXIT_SUCCESS;
+}
+
+}  // namespace spmvhip

@@ -216,7 +216,8 @@ template <typename I, bool UVAL>
 __global__ __launch_bounds__(TRI_THREADS) void trsv_level_kernel(
     uint32_t begin, uint32_t nShort, uint32_t nLong, uint32_t shortBlocks, const uint32_t* __restrict__ perm,
     const I* __restrict__ IRP, const uint32_t* __restrict__ JA, const double* __restrict__ AS, double unitValue,
-    const uint32_t* __restrict__ diagPos, int upper, int dunit, uint64_t N, const double* b, double* x) {
+    const uint32_t* __restrict__ diagPos, int upper, int dunit, uint64_t N, const double* b, double* x, const uint32_t* stop) {
+    if (stop && *stop) return;                                           // a stopped Krylov loop (krylov.hip)
     const uint64_t blk = linear_block();
     if (blk < shortBlocks) {
         const uint64_t t = blk * TRI_THREADS + threadIdx.x;
@@ -255,7 +256,8 @@ template <typename I, bool UVAL>
 __global__ __launch_bounds__(TRI_RUN_THREADS) void trsv_run_kernel(
     uint32_t l0, uint32_t l1, const uint32_t* __restrict__ levelPtr, const uint32_t* __restrict__ perm,
     const I* __restrict__ IRP, const uint32_t* __restrict__ JA, const double* __restrict__ AS, double unitValue,
-    const uint32_t* __restrict__ diagPos, int upper, int dunit, uint64_t N, const double* b, double* x) {
+    const uint32_t* __restrict__ diagPos, int upper, int dunit, uint64_t N, const double* b, double* x, const uint32_t* stop) {
+    if (stop && *stop) return;
     for (uint32_t l = l0; l < l1; ++l) {
         const uint32_t s = levelPtr[l], e = levelPtr[l + 1];
         for (uint32_t t = s + threadIdx.x; t < e; t += TRI_RUN_THREADS) {
@@ -269,12 +271,12 @@ __global__ __launch_bounds__(TRI_RUN_THREADS) void trsv_run_kernel(
 
 template <typename I, bool UVAL>
 void launchSteps(const DevMat* d, const TriSchedule* s, int upper, int dunit, const double* b, double* x, hipStream_t st,
-                 dim3* lastGrid, dim3* lastBlock) {
+                 dim3* lastGrid, dim3* lastBlock, const uint32_t* stop) {
     const I* IRP = static_cast<const I*>(d->IRP);
     for (const TriSchedule::Step& step : s->steps) {
         if (step.l1 - step.l0 > 1) {
             hipLaunchKernelGGL((trsv_run_kernel<I, UVAL>), dim3(1), dim3(TRI_RUN_THREADS), 0, st, step.l0, step.l1, s->levelPtr,
-                               s->perm, IRP, d->JA, d->AS, d->unitValue, s->diagPos, upper, dunit, (uint64_t)d->N, b, x);
+                               s->perm, IRP, d->JA, d->AS, d->unitValue, s->diagPos, upper, dunit, (uint64_t)d->N, b, x, stop);
             *lastGrid = dim3(1); *lastBlock = dim3(TRI_RUN_THREADS);
             continue;
         }
@@ -284,7 +286,7 @@ void launchSteps(const DevMat* d, const TriSchedule* s, int upper, int dunit, co
         const uint32_t longBlocks = (nLong + TRI_THREADS / WAVE - 1) / (TRI_THREADS / WAVE);
         const dim3 grid = grid2d((uint64_t)shortBlocks + longBlocks, TRI_THREADS);
         hipLaunchKernelGGL((trsv_level_kernel<I, UVAL>), grid, dim3(TRI_THREADS), 0, st, begin, nShort, nLong, shortBlocks,
-                           s->perm, IRP, d->JA, d->AS, d->unitValue, s->diagPos, upper, dunit, (uint64_t)d->N, b, x);
+                           s->perm, IRP, d->JA, d->AS, d->unitValue, s->diagPos, upper, dunit, (uint64_t)d->N, b, x, stop);
         *lastGrid = grid; *lastBlock = dim3(TRI_THREADS);
     }
 }
@@ -418,15 +420,16 @@ int triAnalyse(DevMat* d, int uplo, uint32_t T, hipStream_t st) {
     return EXIT_SUCCESS;
 }
 
-int enqueueTrsv(const DevMat* d, int uplo, int diag, const double* b, double* x, hipStream_t st, dim3* grid, dim3* block) {
+int enqueueTrsv(const DevMat* d, int uplo, int diag, const double* b, double* x, hipStream_t st, dim3* grid, dim3* block,
+                const uint32_t* stop) {
     const TriSchedule* s = d->tri[uplo];
     const int upper = uplo == SPMV_TRI_UPPER, dunit = diag == SPMV_DIAG_UNIT;
     if (d->irpBytes == 4) {
-        if (d->unit) launchSteps<uint32_t, true>(d, s, upper, dunit, b, x, st, grid, block);
-        else         launchSteps<uint32_t, false>(d, s, upper, dunit, b, x, st, grid, block);
+        if (d->unit) launchSteps<uint32_t, true>(d, s, upper, dunit, b, x, st, grid, block, stop);
+        else         launchSteps<uint32_t, false>(d, s, upper, dunit, b, x, st, grid, block, stop);
     } else {
-        if (d->unit) launchSteps<uint64_t, true>(d, s, upper, dunit, b, x, st, grid, block);
-        else         launchSteps<uint64_t, false>(d, s, upper, dunit, b, x, st, grid, block);
+        if (d->unit) launchSteps<uint64_t, true>(d, s, upper, dunit, b, x, st, grid, block, stop);
+        else         launchSteps<uint64_t, false>(d, s, upper, dunit, b, x, st, grid, block, stop);
     }
     return hipGetLastError() == hipSuccess ? EXIT_SUCCESS : EXIT_FAILURE;
 }
