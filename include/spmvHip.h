@@ -280,7 +280,8 @@ int spmvHipIlu0Info(spmat* dA, spmvIluInfo* info);
  *   info.launches counts the kernels enqueued (an SpMV counted as one), info.ms the host wall time of the call.
  *   Workspace (CG 3 vectors, 4 with M; BiCGStab 6, 8 with M; 16 B per 4096 rows; history) is allocated by the call and
  *   freed before it returns; the triangles of dM are analysed by the call when they are not yet.  Synchronous, on the
- *   library stream; not capturable.  M = 0 succeeds: CONVERGED, 0.
+ *   library stream; not capturable.  M = 0 succeeds: CONVERGED, 0, no kernel and no read-back; history[0] = +0.0
+ *   (dot(r,r) over no elements) is all it writes.
  * Returns EXIT_SUCCESS whatever the status (info may be NULL).  Refused with a message and EXIT_FAILURE, x untouched:
  *   NULL dA, dB, dX or opts, or a handle that is not live; ELL handles; M != N; dM of another size; dB and dX overlapping; tol negative or
  *   NaN; a history with maxIter + 1 overflowing; for dM the limits of hipSpTRSVCSR and a row without exactly one diagonal

@@ -88,24 +88,42 @@ def _init(A, b, x, tol):
     return r, rr, bb, thresh
 
 
-def _first_exit(rr, thresh, maxiter):
+def _first_exit(rr, thresh, maxiter, trace):
     if rr <= thresh:
-        return CONVERGED
+        return _exit(trace, "init_converged", CONVERGED)
     if not np.isfinite(rr):
-        return NONFINITE
+        return _exit(trace, "init_nonfinite", NONFINITE)
     if maxiter == 0:
-        return MAXITER
+        return _exit(trace, "init_maxiter", MAXITER)
     return None
 
 
-def cg_ref(A, b, x0, tol, maxiter):
-    """hipSpCGCSR's loop.  Returns (x, status, iterations, history, rr)."""
+# one label per `return` of the two loops.  BiCGStab's `rho == 0` straight after the init needs rr == 0, which
+# `rr <= thresh` catches first (thresh >= 0 or NaN; with a NaN thresh rr = 0 is impossible, bb being a term of it): that
+# return is unreachable and has no label.
+CG_EXITS = ("init_converged", "init_nonfinite", "init_maxiter", "pq0", "converged", "nonfinite", "maxiter")
+BICGSTAB_EXITS = ("init_converged", "init_nonfinite", "init_maxiter", "rv0", "half_converged", "tt0", "converged",
+                  "nonfinite", "omega0", "maxiter", "rho0")
+
+
+def _exit(trace, label, status, half=None, **state):
+    """the loop ends here: `trace` (a list, or None) learns which line it was; at BiCGStab's two half-step exits `half`
+    (a dict, or None) also receives the x the iteration started from, alpha and phat"""
+    if trace is not None:
+        trace.append(label)
+    if half is not None:
+        half.update(state)
+    return status
+
+
+def cg_ref(A, b, x0, tol, maxiter, trace=None):
+    """hipSpCGCSR's loop.  Returns (x, status, iterations, history, rr); appends the exit's label (CG_EXITS) to `trace`."""
     with np.errstate(all="ignore"):
         x = np.array(x0, dtype=np.float64, copy=True)
         b = np.asarray(b, dtype=np.float64)
         r, rr, bb, thresh = _init(A, b, x, tol)
         hist = [rr]
-        st = _first_exit(rr, thresh, maxiter)
+        st = _first_exit(rr, thresh, maxiter, trace)
         if st is not None:
             return x, st, 0, np.array(hist), rr
         z = A.precond(r)
@@ -115,18 +133,18 @@ def cg_ref(A, b, x0, tol, maxiter):
             q = A.spmv(p)
             pq = dot_ref(p, q)
             if pq == 0:
-                return x, BREAKDOWN, k - 1, np.array(hist), rr
+                return x, _exit(trace, "pq0", BREAKDOWN), k - 1, np.array(hist), rr
             alpha = rz / pq
             x = x + alpha * p
             r = r - alpha * q
             rr = dot_ref(r, r)
             hist.append(rr)
             if rr <= thresh:
-                return x, CONVERGED, k, np.array(hist), rr
+                return x, _exit(trace, "converged", CONVERGED), k, np.array(hist), rr
             if not np.isfinite(rr):
-                return x, NONFINITE, k, np.array(hist), rr
+                return x, _exit(trace, "nonfinite", NONFINITE), k, np.array(hist), rr
             if k == maxiter:
-                return x, MAXITER, k, np.array(hist), rr
+                return x, _exit(trace, "maxiter", MAXITER), k, np.array(hist), rr
             if A.F is not None:
                 z = A.precond(r)
                 rzn = dot_ref(r, z)
@@ -138,14 +156,15 @@ def cg_ref(A, b, x0, tol, maxiter):
     raise AssertionError("unreachable")
 
 
-def bicgstab_ref(A, b, x0, tol, maxiter):
-    """hipSpBiCGStabCSR's loop (right-preconditioned).  Returns (x, status, iterations, history, rr)."""
+def bicgstab_ref(A, b, x0, tol, maxiter, trace=None, half=None):
+    """hipSpBiCGStabCSR's loop (right-preconditioned).  Returns (x, status, iterations, history, rr); appends the exit's
+    label (BICGSTAB_EXITS) to `trace`; `half` as in _exit."""
     with np.errstate(all="ignore"):
         x = np.array(x0, dtype=np.float64, copy=True)
         b = np.asarray(b, dtype=np.float64)
         r, rr, bb, thresh = _init(A, b, x, tol)
         hist = [rr]
-        st = _first_exit(rr, thresh, maxiter)
+        st = _first_exit(rr, thresh, maxiter, trace)
         if st is not None:
             return x, st, 0, np.array(hist), rr
         rhat = r.copy()
@@ -160,18 +179,20 @@ def bicgstab_ref(A, b, x0, tol, maxiter):
             v = A.spmv(phat)
             rv = dot_ref(rhat, v)
             if rv == 0:
-                return x, BREAKDOWN, k - 1, np.array(hist), rr
+                return x, _exit(trace, "rv0", BREAKDOWN), k - 1, np.array(hist), rr
             alpha = rho / rv
             s = r - alpha * v
             rr = dot_ref(s, s)
             hist.append(rr)
             if rr <= thresh:
-                return x + alpha * phat, CONVERGED, k, np.array(hist), rr
+                st = _exit(trace, "half_converged", CONVERGED, half, x=x, alpha=alpha, phat=phat)
+                return x + alpha * phat, st, k, np.array(hist), rr
             shat = A.precond(s)
             t = A.spmv(shat)
             tt, ts = dot_ref(t, t), dot_ref(t, s)
             if tt == 0:
-                return x + alpha * phat, BREAKDOWN, k, np.array(hist), rr
+                st = _exit(trace, "tt0", BREAKDOWN, half, x=x, alpha=alpha, phat=phat)
+                return x + alpha * phat, st, k, np.array(hist), rr
             omega = ts / tt
             x = (x + alpha * phat) + omega * shat
             r = s - omega * t
@@ -179,15 +200,15 @@ def bicgstab_ref(A, b, x0, tol, maxiter):
             hist[k] = rr
             rhon = dot_ref(rhat, r)
             if rr <= thresh:
-                return x, CONVERGED, k, np.array(hist), rr
+                return x, _exit(trace, "converged", CONVERGED), k, np.array(hist), rr
             if not np.isfinite(rr):
-                return x, NONFINITE, k, np.array(hist), rr
+                return x, _exit(trace, "nonfinite", NONFINITE), k, np.array(hist), rr
             if omega == 0:
-                return x, BREAKDOWN, k, np.array(hist), rr
+                return x, _exit(trace, "omega0", BREAKDOWN), k, np.array(hist), rr
             if k == maxiter:
-                return x, MAXITER, k, np.array(hist), rr
+                return x, _exit(trace, "maxiter", MAXITER), k, np.array(hist), rr
             rho_old, rho = rho, rhon
             if rho == 0:
-                return x, BREAKDOWN, k, np.array(hist), rr
+                return x, _exit(trace, "rho0", BREAKDOWN), k, np.array(hist), rr
             beta = (rho / rho_old) * (alpha / omega)
     raise AssertionError("unreachable")

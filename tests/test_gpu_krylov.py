@@ -1,16 +1,19 @@
 """spmvHipDot, hipSpCGCSR and hipSpBiCGStabCSR on the device against the numpy loops of tests/krylov_ref.py, bit for bit:
 the dot at block boundaries and with special values, CG and BiCGStab with and without ILU(0), every check interval,
-every exit status, the handle kinds, the refusals, a non-default stream and the device memory."""
+every exit status, the handle kinds, the refusals, a non-default stream and the device memory; then every exit of both
+loops (tests/krylov_exit_inputs.py) at K = 1, 16 and 64, b and x at odd element offsets (the scalar forms of the fused
+passes), and the clauses of the header on dM."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import krylov_exit_inputs as exits
 import serial_order_inputs as si
 from bits import assert_same_bits
 from ilu0_ref import ilu0_levels
 from krylov_ref import BREAKDOWN, CONVERGED, MAXITER, NONFINITE, Csr, bicgstab_ref, cg_ref, dot_ref
-from test_gpu_trsv import Source, same
+from test_gpu_trsv import POISON, Source, _carved, _outside_intact, same
 from test_krylov_abi import convdiff7
 from test_trsv_abi import laplacian7
 
@@ -355,3 +358,231 @@ def test_device_memory_comes_back(api):
         torch.cuda.synchronize()
         free.append(torch.cuda.mem_get_info()[0])
     assert np.median(free[2:]) >= free[1] - (8 << 20) and free[-1] >= free[1] - (8 << 20), free
+
+
+# ------------------------------------------------------------------------------------------------- every exit
+FN = {"cg": "hipSpCGCSR", "bicgstab": "hipSpBiCGStabCSR"}
+
+
+def _poisoned(n):
+    return np.full(n, POISON, dtype=np.uint64).view(np.float64)
+
+
+def _raw(api, kind, A, P, b_ptr, x_ptr, tol, maxiter):
+    """the solver through the C ABI with a history full of poison: (return code, info, history as handed back)"""
+    hist = _poisoned(maxiter + 1)
+    opts = api.spmvKrylovOpts(float(tol), int(maxiter), hist.ctypes.data_as(C.POINTER(C.c_double)))
+    info = api.spmvKrylovInfo()
+    rc = getattr(api.lib, FN[kind])(C.byref(A.handle), C.byref(P.handle) if P is not None else None, b_ptr, x_ptr,
+                                    C.byref(opts), C.byref(info))
+    return rc, info, hist
+
+
+def _check_raw(info, hist, x, ref, what):
+    rx, st, it, rhist, rr = ref
+    assert (info.status, info.iterations) == (st, it), (what, info.status, info.iterations, st, it)
+    same(x, rx, what + ": x")
+    same(hist[:it + 1], rhist, what + ": history")
+    assert (hist[it + 1:].view(np.uint64) == POISON).all(), what + ": history written past `iterations`"
+    same_scalar(info.rr, rr, what + ": rr")
+
+
+@pytest.mark.parametrize("name", exits.NAMES)
+def test_every_exit(api, name):
+    """each case of the exit table (tests/test_krylov_abi.py shows which `return` it takes) at three check intervals:
+    status, iterations, x, history and rr are the reference's bits, the history past `iterations` is not written, and at a
+    half-step exit x = x + alpha * phat was written after the stop"""
+    torch = _torch()
+    c = exits.case(name)
+    with np.errstate(all="ignore"):
+        F = ilu0_levels(c.M, c.IRP, c.JA, c.AS) if c.precond else None
+    half = {}
+    kw = {"half": half} if c.solver == "bicgstab" else {}
+    ref = (cg_ref if c.solver == "cg" else bicgstab_ref)(Csr(c.M, c.IRP, c.JA, c.AS, F), c.b, c.x0, c.tol, c.maxiter, **kw)
+    A = api.spMatCpyCSR(api.HostCSR(c.M, c.M, c.IRP, c.JA, c.AS))
+    P = _factors(api, c.M, c.IRP, c.JA, c.AS)[0] if c.precond else None
+    db = torch.from_numpy(c.b).cuda()
+    xs = {}
+    try:
+        if name.endswith(":2I"):                                         # the case is there for the unit kernels
+            v = C.c_double(0)
+            assert api.lib.spmvHipUnitValue(C.byref(A.handle), C.byref(v)) == 1 and v.value == 2.0
+        for K in (1, 16, 64):
+            assert api.lib.spmvHipSetVariant(FN[c.solver].encode(), K) == 0
+            got = _solve(c.solver, A, c.b, x0=c.x0, precond=P, tol=c.tol, maxiter=c.maxiter)
+            _check(c.solver, got, ref, f"{name} K={K}")
+            dx = torch.from_numpy(c.x0).cuda()
+            rc, info, hist = _raw(api, c.solver, A, P, db.data_ptr(), dx.data_ptr(), c.tol, c.maxiter)
+            assert rc == 0
+            xs[K] = dx.cpu().numpy()
+            _check_raw(info, hist, xs[K], ref, f"{name} K={K}, C ABI")
+            same(got[0], xs[K], f"{name} K={K}: the two calls")
+        for K in (16, 64):
+            same(xs[K], xs[1], f"{name}: x at K={K} against K=1")
+        if c.label in ("half_converged", "tt0"):
+            assert not np.array_equal(xs[1], c.x0), name
+            with np.errstate(all="ignore"):
+                same(xs[1], half["x"] + half["alpha"] * half["phat"], f"{name}: x + alpha * phat")
+    finally:
+        A.free()
+        if P is not None:
+            P.free()
+
+
+# ------------------------------------------------------------------------------------------------- alignment forms
+ODD_GRID = (21, 19, 17)                 # n = 6 783: odd (the last pair is half) and one block of 4 096 plus a short one
+
+
+@pytest.mark.parametrize("kind,precond", [("cg", False), ("cg", True), ("bicgstab", False), ("bicgstab", True)])
+def test_b_and_x_at_odd_offsets(api, kind, precond):
+    """dB / dX that are only 8-byte aligned send InitOp, CgUpdateOp / BiUpdateOp, the first SpMV and the triangular solves
+    of dM down their scalar forms, alternating with the 16-byte forms of the passes on the workspace: the same bits, and
+    nothing outside the views is touched"""
+    torch = _torch()
+    IRP, JA, AS = (laplacian7 if kind == "cg" else convdiff7)(*ODD_GRID)
+    M = int(np.prod(ODD_GRID))
+    assert M % 2 == 1 and M % 4096
+    rng = np.random.default_rng(3900)
+    b, x0 = rng.random(M), rng.uniform(-1, 1, M)
+    A = api.spMatCpyCSR(api.HostCSR(M, M, IRP, JA, AS))
+    P, F = _factors(api, M, IRP, JA, AS) if precond else (None, None)
+    ref = _ref(kind, M, IRP, JA, AS, F, b, x0, 1e-10, 40)
+    try:
+        for ob, ox in ((0, 0), (1, 0), (0, 1), (1, 1)):
+            what = f"{kind} precond={precond} b+{ob} x+{ox}"
+            bigb, vb = _carved(torch, b, ob)
+            bigx, vx = _carved(torch, x0, ox)
+            assert vb.data_ptr() % 16 == 8 * ob and vx.data_ptr() % 16 == 8 * ox
+            rc, info, hist = _raw(api, kind, A, P, vb.data_ptr(), vx.data_ptr(), 1e-10, 40)
+            assert rc == 0
+            _check_raw(info, hist, vx.cpu().numpy(), ref, what)
+            _outside_intact(bigb, ob, M, what + " (b)")
+            _outside_intact(bigx, ox, M, what + " (x)")
+            same(vb.cpu().numpy(), b, what + ": b is read only")
+    finally:
+        A.free()
+        if P is not None:
+            P.free()
+
+
+def test_serial_order_spmv_reads_x_at_an_odd_offset(api):
+    """the product inside a solve reads the caller's x0: the selected serial-order kernel on an 8-byte aligned x (and y)"""
+    torch = _torch()
+    n = 40
+    IRP, JA, AS = convdiff7(n, n, n)
+    M = n ** 3
+    assert JA.size >= exits.AUTO_MIN_NNZ
+    x = si.order_values(np.random.default_rng(3910), M, 8)
+    y_ref = Csr(M, IRP, JA, AS).spmv(x)
+    A = api.spMatCpyCSR(api.HostCSR(M, M, IRP, JA, AS))
+    try:
+        for ox, oy in ((1, 0), (1, 1), (0, 1), (0, 0)):
+            bigx, vx = _carved(torch, x, ox)
+            bigy, vy = _carved(torch, np.zeros(M), oy)
+            vy.fill_(float("nan"))
+            torch.cuda.synchronize()
+            assert api.lib.spmvHipEnqueueAutoRows(C.byref(A.handle), C.c_void_p(vx.data_ptr()), C.c_void_p(vy.data_ptr()), None) == 0
+            assert api.lib.spmvHipDeviceSynchronize() == 0
+            assert_same_bits(vy.cpu().numpy(), y_ref, f"x+{ox} y+{oy}")
+            _outside_intact(bigy, oy, M, f"x+{ox} y+{oy}")
+        assert api.lib.spmvHipAutoChoiceRows(C.byref(A.handle), None) is not None
+    finally:
+        A.free()
+
+
+# ------------------------------------------------------------------------------------------------- clauses on dM
+def _tame(IRP, JA, AS, lower):
+    """AS with the strictly lower (`lower`) or the strictly upper entries divided by 8: the other triangle dominates, and
+    the raw triangles of the result are a mild preconditioner"""
+    rows = si.row_of_entry(IRP)
+    j = JA.astype(np.int64)
+    return np.where((j < rows) if lower else (j > rows), AS / 8, AS)
+
+
+@pytest.mark.parametrize("kind", ["cg", "bicgstab"])
+def test_dM_is_dA(api, kind):
+    """"dM == dA is allowed": A used raw as its own preconditioner (M^-1 is its unit lower and its stored upper triangle,
+    for a lower- and an upper-dominant A), and A holding ILU(0) factors as matrix and preconditioner at once"""
+    n = 14
+    IRP, JA, AS0 = convdiff7(n, n, n)
+    M = n ** 3
+    b = np.random.default_rng(3920).random(M)
+    for what, AS, factor in (("upper-dominant, raw", _tame(IRP, JA, AS0, True), False),
+                             ("lower-dominant, raw", _tame(IRP, JA, AS0, False), False), ("ILU(0) factors", AS0, True)):
+        A = api.spMatCpyCSR(api.HostCSR(M, M, IRP, JA, AS))
+        try:
+            if factor:
+                A.ilu0()
+                AS = ilu0_levels(M, IRP, JA, AS)
+            got = _solve(kind, A, b, precond=A, tol=1e-10, maxiter=12)
+            _check(kind, got, _ref(kind, M, IRP, JA, AS, AS, b, np.zeros(M), 1e-10, 12), f"{kind} dM == dA, {what}")
+        finally:
+            A.free()
+
+
+@pytest.mark.parametrize("kind", ["cg", "bicgstab"])
+def test_M_zero(api, kind):
+    """"M = 0 succeeds: CONVERGED, 0": no read-back of a device state, x and its neighbours untouched, and of the history
+    only hist[0 .. iterations] = hist[0] is written: dot(r, r) over no elements, +0.0"""
+    torch = _torch()
+    empty = (np.zeros(1, np.uint64), np.zeros(0, np.uint64), np.zeros(0))
+    A, P = Source(api, 0, 0, *empty), Source(api, 0, 0, *empty)
+    big = torch.from_numpy(_poisoned(4)).cuda()
+    try:
+        for pre in (None, P.dm):
+            rc, info, hist = _raw(api, kind, A.dm, pre, big.data_ptr(), big.data_ptr() + 16, 1e-8, 5)
+            assert rc == 0
+            assert (info.status, info.iterations, info.hostChecks) == (CONVERGED, 0, 0)
+            assert_same_bits(hist[:1], np.array([0.0]), "hist[0]")
+            assert (hist[1:].view(np.uint64) == POISON).all()
+            same_scalar(info.rr, 0.0, "rr")
+            assert (big.cpu().numpy().view(np.uint64) == POISON).all()
+    finally:
+        A.free()
+        P.free()
+
+
+def test_dM_analysed_by_the_solve(api):
+    """a dM that holds factors but has never been analysed: the first solve builds both schedules, the second keeps them"""
+    n = 16
+    IRP, JA, AS = convdiff7(n, n, n)
+    M = n ** 3
+    b = np.random.default_rng(3930).random(M)
+    F = ilu0_levels(M, IRP, JA, AS)
+    A = api.spMatCpyCSR(api.HostCSR(M, M, IRP, JA, AS))
+    P = api.spMatCpyCSR(api.HostCSR(M, M, IRP, JA, F))                  # the factors uploaded: no hipSpILU0CSR, no analysis
+    try:
+        assert [P.triangular_info(lo).analyses for lo in (True, False)] == [0, 0]
+        assert [P.triangular_info(lo).levels for lo in (True, False)] == [0, 0]
+        for kind in ("bicgstab", "cg"):
+            got = _solve(kind, A, b, precond=P, tol=1e-10, maxiter=8)
+            _check(kind, got, _ref(kind, M, IRP, JA, AS, F, b, np.zeros(M), 1e-10, 8), f"{kind}, dM not analysed before")
+            infos = [P.triangular_info(lo) for lo in (True, False)]
+            assert [i.analyses for i in infos] == [1, 1] and all(i.levels == 3 * n - 2 for i in infos)
+    finally:
+        A.free()
+        P.free()
+
+
+@pytest.mark.parametrize("kind", ["cg", "bicgstab"])
+def test_dM_updated_to_a_constant_and_not_refactored(api, kind):
+    """dM factored, then every value set to 1.0 (a unit handle) and NOT factored again: M^-1 is the raw triangles of the
+    constant matrix, the schedules stay, the loop runs on whatever that gives"""
+    n = 10
+    IRP, JA, AS = (laplacian7 if kind == "cg" else convdiff7)(n, n, n)
+    M = n ** 3
+    b = np.random.default_rng(3940).random(M)
+    ones = np.ones_like(AS)
+    A = api.spMatCpyCSR(api.HostCSR(M, M, IRP, JA, AS))
+    P, _ = _factors(api, M, IRP, JA, AS)
+    try:
+        P.update_values(ones)
+        v = C.c_double(0)
+        assert api.lib.spmvHipUnitValue(C.byref(P.handle), C.byref(v)) == 1 and v.value == 1.0
+        got = _solve(kind, A, b, precond=P, tol=1e-10, maxiter=4)
+        _check(kind, got, _ref(kind, M, IRP, JA, AS, ones, b, np.zeros(M), 1e-10, 4), f"{kind}, dM a unit handle")
+        assert [P.triangular_info(lo).analyses for lo in (True, False)] == [1, 1]
+        assert P.ilu0_info().factorisations == 1
+    finally:
+        A.free()
+        P.free()

@@ -311,6 +311,51 @@ def test_zero_diagonals_and_in_place(api):
         src.free()
 
 
+def _carved(torch, v, off):
+    """v inside a larger device tensor of poison, at element offset `off`: (the larger tensor, the view)"""
+    host = np.full(v.size + 2, POISON, dtype=np.uint64).view(np.float64)
+    host[off:off + v.size] = v
+    big = torch.from_numpy(host).cuda()
+    return big, big[off:off + v.size]
+
+
+def _outside_intact(big, off, n, what):
+    host = big.cpu().numpy().view(np.uint64)
+    assert (host[:off] == POISON).all() and (host[off + n:] == POISON).all(), what + ": a neighbour of the view was written"
+
+
+def test_b_and_x_at_odd_offsets(api):
+    """b and x that are only 8-byte aligned (views at element offset 1 of larger tensors), apart and in place, M odd: the
+    same bits, and the elements next to the views keep their poison"""
+    torch = pytest.importorskip("torch")
+    rng = np.random.default_rng(1718)
+    M = 5001
+    IRP, JA, AS = random_square(rng, M, 9)
+    src = Source(api, M, M, IRP, JA, AS)
+    try:
+        b = si.order_values(rng, M)
+        for uplo, diag in ((LOWER, UNIT), (UPPER, STORED), (LOWER, STORED)):
+            ref = trsv_levels(M, IRP, JA, AS, b, uplo == LOWER, diag == UNIT)
+            for ob, ox in ((0, 0), (1, 0), (0, 1), (1, 1)):
+                what = f"uplo {uplo}, diag {diag}, b+{ob}, x+{ox}"
+                bigb, vb = _carved(torch, b, ob)
+                bigx, vx = _carved(torch, np.zeros(M), ox)
+                vx.fill_(float("nan"))
+                torch.cuda.synchronize()
+                assert vb.data_ptr() % 16 == 8 * ob and vx.data_ptr() % 16 == 8 * ox
+                assert _solve_raw(api, src.dm, uplo, diag, vb.data_ptr(), vx.data_ptr()) == 0
+                same(vx.cpu().numpy(), ref, what)
+                _outside_intact(bigx, ox, M, what)
+                assert_same_bits(vb.cpu().numpy(), b, what + ": b is read only")
+            for o in (0, 1):
+                big, v = _carved(torch, b, o)
+                assert _solve_raw(api, src.dm, uplo, diag, v.data_ptr(), v.data_ptr()) == 0
+                same(v.cpu().numpy(), ref, f"uplo {uplo}, diag {diag}, in place at +{o}")
+                _outside_intact(big, o, M, f"in place at +{o}")
+    finally:
+        src.free()
+
+
 # ------------------------------------------------------------------------------------------------- 3. values change
 def test_values_change_pattern_stays(api):
     torch = pytest.importorskip("torch")

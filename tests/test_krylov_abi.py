@@ -1,7 +1,8 @@
 """The Krylov entry points (spmvHipDot, hipSpCGCSR, hipSpBiCGStabCSR) are declared, exported and bound in Python with the
 C layouts of spmvKrylovOpts and spmvKrylovInfo, and the test side's references (tests/krylov_ref.py) are the loops of
 include/spmvHip.h: dot_ref is the documented order (which np.dot and math.fsum are not), cg_ref and bicgstab_ref equal
-the loops written in plain Python on tiny systems.  No GPU needed."""
+the loops written in plain Python on tiny systems, and every case of tests/krylov_exit_inputs.py takes the exit of the
+loop that the table claims for it (so the table reaches every `return` of both loops).  No GPU needed."""
 import ctypes as C
 import math
 import os
@@ -15,7 +16,8 @@ import serial_order_inputs as si
 from bits import assert_same_bits
 from conftest import ROOT
 from ilu0_ref import ilu0_levels, ilu0_loop
-from krylov_ref import BREAKDOWN, CONVERGED, MAXITER, NONFINITE, Csr, bicgstab_ref, cg_ref, dot_ref
+import krylov_exit_inputs as exits
+from krylov_ref import BICGSTAB_EXITS, BREAKDOWN, CG_EXITS, CONVERGED, MAXITER, NONFINITE, Csr, bicgstab_ref, cg_ref, dot_ref
 from test_trsv_abi import laplacian7
 from trsv_ref import trsv_loop
 
@@ -194,6 +196,12 @@ def _ops(M, IRP, JA, AS, F):
     return spmv, precond
 
 
+def _div(a, b):
+    """a / b as IEEE double gives it (Python raises on a zero divisor)"""
+    with np.errstate(all="ignore"):
+        return float(np.float64(a) / np.float64(b))
+
+
 def cg_loop(M, IRP, JA, AS, F, b, x, tol, maxiter):
     spmv, precond = _ops(M, IRP, JA, AS, F)
     x, b = [float(a) for a in x], [float(a) for a in b]
@@ -216,7 +224,7 @@ def cg_loop(M, IRP, JA, AS, F, b, x, tol, maxiter):
         pq = dot_loop(p, q)
         if pq == 0:
             return x, BREAKDOWN, k - 1, hist
-        alpha = rz / pq
+        alpha = _div(rz, pq)
         x = [xi + alpha * pi for xi, pi in zip(x, p)]
         r = [ri - alpha * qi for ri, qi in zip(r, q)]
         rr = dot_loop(r, r)
@@ -229,12 +237,14 @@ def cg_loop(M, IRP, JA, AS, F, b, x, tol, maxiter):
             return x, MAXITER, k, hist
         z = precond(r)
         rzn = dot_loop(r, z)
-        beta = rzn / rz
+        beta = _div(rzn, rz)
         rz = rzn
         p = [zi + beta * pi for zi, pi in zip(z, p)]
 
 
-def bicgstab_loop(M, IRP, JA, AS, F, b, x, tol, maxiter):
+def bicgstab_loop(M, IRP, JA, AS, F, b, x, tol, maxiter, fault=None):
+    """`fault` plants one of the mistakes the exit table must tell apart (test_exit_table_tells_planted_faults_apart):
+    "half x": a half-step exit returns x without alpha * phat; "omega rho": the omega == 0 and rho == 0 tests swapped"""
     spmv, precond = _ops(M, IRP, JA, AS, F)
     x, b = [float(a) for a in x], [float(a) for a in b]
     q = spmv(x)
@@ -261,18 +271,20 @@ def bicgstab_loop(M, IRP, JA, AS, F, b, x, tol, maxiter):
         rv = dot_loop(rhat, v)
         if rv == 0:
             return x, BREAKDOWN, k - 1, hist
-        alpha = rho / rv
+        alpha = _div(rho, rv)
         s = [ri - alpha * vi for ri, vi in zip(r, v)]
         ss = dot_loop(s, s)
         hist.append(ss)
         if ss <= thresh:
+            if fault == "half x":
+                return x, CONVERGED, k, hist
             return [xi + alpha * hi for xi, hi in zip(x, phat)], CONVERGED, k, hist
         shat = precond(s)
         t = spmv(shat)
         tt, ts = dot_loop(t, t), dot_loop(t, s)
         if tt == 0:
             return [xi + alpha * hi for xi, hi in zip(x, phat)], BREAKDOWN, k, hist
-        omega = ts / tt
+        omega = _div(ts, tt)
         x = [(xi + alpha * hi) + omega * si_ for xi, hi, si_ in zip(x, phat, shat)]
         r = [si_ - omega * ti for si_, ti in zip(s, t)]
         rr = dot_loop(r, r)
@@ -282,14 +294,14 @@ def bicgstab_loop(M, IRP, JA, AS, F, b, x, tol, maxiter):
             return x, CONVERGED, k, hist
         if not math.isfinite(rr):
             return x, NONFINITE, k, hist
-        if omega == 0:
+        if (rhon if fault == "omega rho" else omega) == 0:
             return x, BREAKDOWN, k, hist
         if k == maxiter:
             return x, MAXITER, k, hist
         rho_old, rho = rho, rhon
-        if rho == 0:
+        if (omega if fault == "omega rho" else rho) == 0:
             return x, BREAKDOWN, k, hist
-        beta = (rho / rho_old) * (alpha / omega)
+        beta = _div(rho, rho_old) * _div(alpha, omega)
 
 
 def convdiff7(nx, ny, nz, c=0.7):
@@ -369,3 +381,85 @@ def test_ilu0_pcg_needs_fewer_iterations():
     _, st1, it_ilu, _, _ = cg_ref(Csr(M, IRP, JA, AS, F), b, np.zeros(M), 1e-8, 1000)
     assert st0 == st1 == CONVERGED
     assert it_ilu <= 0.75 * it_plain, (it_ilu, it_plain)
+
+
+# ------------------------------------------------------------------------------------------------- every exit
+def _same(a, b, what):
+    """NaN where NaN is, and everything else (the infinities too) by its bits"""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    assert np.array_equal(np.isnan(a), np.isnan(b)), what + ": NaN in other places"
+    assert_same_bits(a[~np.isnan(a)], b[~np.isnan(b)], what)
+
+
+def _case_ref(c, trace=None):
+    with np.errstate(all="ignore"):
+        F = ilu0_levels(c.M, c.IRP, c.JA, c.AS) if c.precond else None
+    ref = cg_ref if c.solver == "cg" else bicgstab_ref
+    return F, ref(Csr(c.M, c.IRP, c.JA, c.AS, F), c.b, c.x0, c.tol, c.maxiter, trace)
+
+
+@pytest.mark.parametrize("name", exits.NAMES)
+def test_exit_case_takes_its_label_and_ref_is_the_loop(name):
+    """the labelled reference leaves by the line the table names, early (iteration <= 1) or late as it says, and on the
+    small cases the plain-Python loop gives the same bits"""
+    c = exits.case(name)
+    trace = []
+    F, (x, st, it, hist, rr) = _case_ref(c, trace)
+    assert trace == [c.label], (name, trace)
+    assert (it >= 2) == (c.when == "late"), (name, it)
+    assert c.label in (CG_EXITS if c.solver == "cg" else BICGSTAB_EXITS)
+    if name.endswith(":large"):
+        assert c.JA.size >= exits.AUTO_MIN_NNZ and c.M > 8 * 4096 and c.x0.any()
+        return                                                           # (the twin adds nothing to reference = loop)
+    loop = cg_loop if c.solver == "cg" else bicgstab_loop
+    xl, stl, itl, histl = loop(c.M, c.IRP, c.JA, c.AS, F, c.b, c.x0, c.tol, c.maxiter)
+    assert (st, it) == (stl, itl), name
+    _same(x, xl, name + ": x")
+    _same(hist, histl, name + ": history")
+    _same(np.array([rr]), [histl[-1]], name + ": rr")
+
+
+def test_exit_table_is_complete():
+    """every label of both loops, with and without ILU(0); `early` and `late` where both are asked for; a large twin for
+    the labels that must have one; no hole but the documented ones"""
+    have = {}
+    for name in exits.NAMES:
+        solver, label, when = name.split(":")[:3]
+        have.setdefault((solver.split("+")[0], "+ilu0" in solver, label), set()).add((when, name.endswith(":large")))
+    want = set()
+    for solver, labels in (("cg", CG_EXITS), ("bicgstab", BICGSTAB_EXITS)):
+        for pre in (False, True):
+            for label in labels:
+                whens = ("early", "late") if label in exits.BOTH_WHENS else (None,)
+                for when in whens:
+                    got = {w for w, _ in have.get((solver, pre, label), ())}
+                    hole = (solver, pre, label, when) in exits.HOLES
+                    assert hole != (bool(got) if when is None else when in got), (solver, pre, label, when)
+                    want.add((solver, pre, label))
+    assert set(have) | {k[:3] for k in exits.HOLES} == want
+    assert not any(pre is False for _, pre, _, _ in exits.HOLES), "the un-preconditioned table has no holes"
+    for label in exits.LARGE_REQUIRED:
+        assert any(large for _, large in have[("bicgstab", False, label)]), label
+    assert any(large for _, large in have[("cg", False, "converged")])
+
+
+@pytest.mark.parametrize("fault", ["half x", "omega rho"])
+def test_exit_table_tells_planted_faults_apart(fault):
+    """a loop that forgets x + alpha * phat at a half-step exit, or tests rho == 0 where omega == 0 belongs, differs from
+    the reference on a case of the table (status, iterations or the bits of x)"""
+    caught = []
+    for name in exits.NAMES:
+        if not name.startswith("bicgstab") or name.endswith(":large"):
+            continue
+        c = exits.case(name)
+        F, (x, st, it, _, _) = _case_ref(c)
+        xl, stl, itl, _ = bicgstab_loop(c.M, c.IRP, c.JA, c.AS, F, c.b, c.x0, c.tol, c.maxiter, fault=fault)
+        try:
+            assert (st, it) == (stl, itl)
+            _same(x, xl, name)
+        except AssertionError:
+            caught.append(name)
+    print(fault, "caught by", caught)
+    assert caught, fault
+    if fault == "half x":
+        assert all(":half_converged:" in n or ":tt0:" in n for n in caught)
