@@ -13,6 +13,7 @@
 #include <atomic>
 #include <cstdint>
 #include <cstdio>
+#include <type_traits>
 #include <vector>
 
 #include "spmvHip.h"
@@ -103,6 +104,15 @@ struct DevMat {
     spmvIluInfo ilu{-1, -1, 0, 0, 0, 0, 0.0};
 };
 
+// The one place that looks at the width of the row pointers: f (a generic lambda) is called with them as const uint32_t*
+// or const uint64_t*; IrpT<decltype(irp)> names the integer for a kernel's template argument.
+template <typename P> using IrpT = std::remove_const_t<std::remove_pointer_t<P>>;
+template <typename F>
+auto withIrp(const void* IRP, int irpBytes, F&& f) {
+    return irpBytes == 4 ? f(static_cast<const uint32_t*>(IRP)) : f(static_cast<const uint64_t*>(IRP));
+}
+template <typename F> auto withIrp(const DevMat* d, F&& f) { return withIrp(d->IRP, d->irpBytes, f); }
+
 int  buildSell(DevMat* d);                                      // sell.hip
 void freeSell(SellFormat* f);
 int  enqueueSell(DevMat* d, const double* x, double* y, hipStream_t stream);
@@ -177,7 +187,7 @@ int  enqueueGatherValues(double* val, const uint32_t* map, uint64_t n, const dou
 int  enqueueScatterValues(double* val, const uint32_t* map, uint64_t n, const double* AS, hipStream_t stream);
 int  enqueueSellValues(uint32_t nSlices, const uint64_t* sliceOff, const uint32_t* perm, const uint32_t* slen, const void* IRP,
                        int irpBytes, const double* AS, double* val, hipStream_t stream);
-int  updateValues(spmat* h, const double* AS, bool onDevice, bool reread, hipStream_t stream, const char* who);   // abi.hip
+int  updateValues(spmat* h, const double* AS, bool onDevice, bool reread, hipStream_t stream, const char* who);   // upload.hip
 // Y = A X for k columns, X(j, c) at X[j*sxr + c*sxc], Y(i, c) at Y[i*syr + c*syc] (spmm.hip): one launch per panel of at
 // most 16 columns on `stream`, no allocation; the caller has checked handle, pointers and extents
 int  enqueueSpmm(const DevMat* d, uint32_t k, const double* X, uint64_t sxr, uint64_t sxc, double* Y, uint64_t syr,
@@ -203,5 +213,20 @@ inline bool hipOk(hipError_t e, const char* what) {
     return false;
 }
 #define HIP_TRY(expr) do { if (!::spmvhip::hipOk((expr), #expr)) return EXIT_FAILURE; } while (0)
+
+// One 32-bit word on the device for a kernel to flag something in: allocated, every byte set to `init`, written by what
+// launch(word) enqueues on `stream`, read back into *out on that stream (synchronised) and freed.  A failure is reported
+// and leaves no sticky error behind; *out is then untouched.
+template <typename L>
+int deviceFlag(int init, hipStream_t stream, const char* kernel, uint32_t* out, L&& launch) {
+    uint32_t* dFlag = nullptr;
+    HIP_TRY(hipMalloc(&dFlag, 4));
+    bool ok = hipOk(hipMemsetAsync(dFlag, init, 4, stream), "hipMemset");
+    if (ok) launch(dFlag);
+    ok = ok && hipOk(hipGetLastError(), kernel) && hipOk(hipMemcpyAsync(out, dFlag, 4, hipMemcpyDeviceToHost, stream), "hipMemcpy") &&
+         hipOk(hipStreamSynchronize(stream), "hipStreamSynchronize");
+    (void)hipFree(dFlag);
+    return ok ? EXIT_SUCCESS : EXIT_FAILURE;
+}
 
 }  // namespace spmvhip

@@ -136,7 +136,7 @@ __global__ __launch_bounds__(ILU_THREADS) void ilu0_pivot_kernel(uint64_t M, con
 }
 
 // one wavefront per row: the first row whose columns are not STRICTLY ascending (a repeated column counts).  The
-// serial-order selection's csr_unsorted_kernel (abi.hip) asks the non-strict question.
+// serial-order selection's csr_unsorted_kernel (select.hip) asks the non-strict question.
 template <typename I>
 __global__ __launch_bounds__(256) void csr_not_strict_kernel(uint64_t M, const I* __restrict__ IRP, const uint32_t* __restrict__ JA,
                                                              uint32_t* __restrict__ first) {
@@ -179,20 +179,14 @@ struct Words {
 }  // namespace
 
 int iluUnsortedRow(const DevMat* d, hipStream_t st, long* row) {
-    Words w;
     uint32_t first = NO_ROW;
-    HIP_TRY(hipMalloc(&w.p, 4));
-    HIP_TRY(hipMemsetAsync(w.p, 0xFF, 4, st));
-    const dim3 grid = grid2d((d->M + 3) / 4, 256);
-    if (d->irpBytes == 4)
-        hipLaunchKernelGGL((csr_not_strict_kernel<uint32_t>), grid, dim3(256), 0, st, d->M, static_cast<const uint32_t*>(d->IRP), d->JA, w.p);
-    else
-        hipLaunchKernelGGL((csr_not_strict_kernel<uint64_t>), grid, dim3(256), 0, st, d->M, static_cast<const uint64_t*>(d->IRP), d->JA, w.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(&first, w.p, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    const int rc = deviceFlag(0xFF, st, "csr_not_strict_kernel", &first, [&](uint32_t* dFirst) {
+        withIrp(d, [&](auto irp) {
+            hipLaunchKernelGGL((csr_not_strict_kernel<IrpT<decltype(irp)>>), grid2d((d->M + 3) / 4, 256), dim3(256), 0, st, d->M, irp, d->JA, dFirst);
+        });
+    });
     *row = first == NO_ROW ? -1 : (long)first;
-    return EXIT_SUCCESS;
+    return rc;
 }
 
 int iluFactor(DevMat* d, uint32_t G, hipStream_t st) {
@@ -201,8 +195,7 @@ int iluFactor(DevMat* d, uint32_t G, hipStream_t st) {
     uint32_t h[2] = {NO_ROW, 0};                    // [0] the zero pivot, [1] rows on the long-row path
     HIP_TRY(hipMalloc(&w.p, 8));
     HIP_TRY(hipMemcpyAsync(w.p, h, 8, hipMemcpyHostToDevice, st));
-    if (d->irpBytes == 4) launchIluWidth<uint32_t>(d, s, G, w.p + 1, st);
-    else                  launchIluWidth<uint64_t>(d, s, G, w.p + 1, st);
+    withIrp(d, [&](auto irp) { launchIluWidth<IrpT<decltype(irp)>>(d, s, G, w.p + 1, st); });
     hipLaunchKernelGGL(ilu0_pivot_kernel, grid2d((d->M + ILU_THREADS - 1) / ILU_THREADS, ILU_THREADS), dim3(ILU_THREADS), 0, st,
                        d->M, s->diagPos, d->AS, w.p);
     HIP_TRY(hipGetLastError());

@@ -1,0 +1,122 @@
+// lib.hpp -- what the files behind the extern "C" boundary of libspmvhip.so (abi.hip, upload.hip, launch.hip, select.hip,
+// hostcall.hip; DESIGN.md has the table) share: the library state, the error line, the handle checks, the launch context
+// with its timing bracket, and the few functions one of those files calls in another.
+#pragma once
+#include <algorithm>
+
+#include "spmvHip.h"
+#include "kernels.hpp"
+
+#pragma GCC visibility push(hidden)                  // shared between the library's files, not part of its exported surface
+namespace spmvhip {
+
+struct State {
+    bool        inited = false;
+    int         dev = 0;
+    hipStream_t stream = nullptr;       // written by spmvHipSetStream only: a call on another stream passes a Ctx down
+    bool        sync = true;            // written by spmvHipSetSync only
+    int         variantRowsCSR = 2;     // 0 scalar restatement, 1 LDS-stream kernel (sequential row sums), 2 the fastest serial-order
+                                        // kernel for the matrix (LDS-stream / deterministic two-phase / deterministic stripes)
+    int         variantWarpCSR = 2;     // 0 wavefront-per-row restatement, 1 LDS-stream kernel (LDS segmented reduction), 2 the fastest
+                                        // reduction-order kernel for the matrix (LDS-stream / two-phase / stripes), measured at first use
+    int         variantEllRowMajor = 1; // hipSpMVRowsELLNNTransposed: 0 a thread walks its row in global memory, 1 LDS-stream kernel, same sums
+    uint32_t    triRunRows = 256;       // hipSpTRSVCSR: T, the row threshold of the single-workgroup runs
+    uint32_t    iluGroup = 16;          // hipSpILU0CSR: lanes per row
+    uint32_t    krylovK[2] = {16, 16};  // hipSpCGCSR, hipSpBiCGStabCSR: iterations per host check
+    int         ldsOrder = -1;          // lds_order_probe_kernel: -1 not run yet, 1 lane-ascending + in issue order, 0 anything else
+    bool        ellRowLens = true;
+    bool        unitValues = true;      // look for "every stored value is the same double" at upload (spmvHipSetUnitValues)
+    double      lastSeconds = 0;
+    spmvDim3    lastGrid{0, 0, 0}, lastBlock{0, 0, 0};
+    hipEvent_t  ev0 = nullptr, ev1 = nullptr;
+};
+extern State S;                         // abi.hip
+
+#define ERR(...) do { fprintf(stderr, "\33[31m\33[1m\33[44mlibspmvhip: "); fprintf(stderr, __VA_ARGS__); fprintf(stderr, "\33[0m\n"); } while (0)
+
+// Where a launch goes and whether the call waits for it (and is timed with the library's events, which belong to the device
+// of spmvHipInit).  The public launchers build it from the library state; a call on another device's stream (shard.hip), the
+// host-matrix wrappers (always synchronous) and the timed loops of the selections (always enqueue-only) build their own.
+struct Ctx { hipStream_t stream; bool sync; };
+inline Ctx libraryCtx() { return {S.stream, S.sync}; }
+
+inline bool ready(const char* who) {
+    if (S.inited) return true;
+    ERR("%s: spmvHipInit() has not been called", who);
+    return false;
+}
+
+inline DevMat* descOf(spmat* h, const char* who) {
+    if (!h || !h->dev || h->dev == SPMAT_TAG_ELL_TRANSPOSED) {
+        ERR("%s: not a device handle (upload with spMatCpyCSR/spMatCpyELL first)", who);
+        return nullptr;
+    }
+    DevMat* d = static_cast<DevMat*>(h->dev);
+    if (d->magic != 0x53504D56) { ERR("%s: corrupted device handle", who); return nullptr; }
+    return d;
+}
+// ... for a launcher: the vectors are raw device pointers whose extent the library cannot know, but a NULL one would be
+// dereferenced by every lane of the kernel -- a GPU page fault, which on a shared node is everybody's problem
+inline DevMat* descOf(spmat* h, const double* x, const double* y, const char* who) {
+    DevMat* d = descOf(h, who);
+    if (d && (!x || !y)) { ERR("%s: %s is NULL", who, !x ? "x" : "y"); return nullptr; }
+    return d;
+}
+// ... that must be CSR: `what` is this entry point's own wording of the refusal (null: refused without a line)
+inline DevMat* csrOnly(DevMat* d, const char* who, const char* what = "handle is not CSR") {
+    if (!d || d->kind == Kind::CSR) return d;
+    if (what) ERR("%s: %s", who, what);
+    return nullptr;
+}
+inline DevMat* csrOf(spmat* h, const char* who, const char* what = "handle is not CSR") { return csrOnly(descOf(h, who), who, what); }
+inline DevMat* csrOf(spmat* h, const double* x, const double* y, const char* who, const char* what = "handle is not CSR") {
+    return csrOnly(descOf(h, x, y, who), who, what);
+}
+
+// timing bracket used by every launcher
+struct Launch {
+    const Ctx cx;
+    Launch(Ctx c, dim3 grid, dim3 block) : cx(c) {
+        (void)hipGetLastError();                    // finish() judges THIS launch, not whatever failed before it
+        shape(grid, block);
+        if (cx.sync) (void)hipEventRecord(S.ev0, cx.stream);
+    }
+    void shape(dim3 grid, dim3 block) { S.lastGrid = {grid.x, grid.y, grid.z}; S.lastBlock = {block.x, block.y, block.z}; }
+    int finish(const char* who) {
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) { ERR("%s: launch failed: %s", who, hipGetErrorString(e)); return EXIT_FAILURE; }
+        if (!cx.sync) return EXIT_SUCCESS;
+        (void)hipEventRecord(S.ev1, cx.stream);
+        e = hipEventSynchronize(S.ev1);
+        if (e != hipSuccess) { ERR("%s: kernel failed: %s", who, hipGetErrorString(e)); return EXIT_FAILURE; }
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, S.ev0, S.ev1);
+        S.lastSeconds = ms * 1e-3;
+        return EXIT_SUCCESS;
+    }
+};
+
+// a launcher call that has nothing to launch (no rows, or no entries: y = 0): no stale time or shape is left behind
+inline int nothingToLaunch(Ctx cx, DevMat* d, double* dY) {
+    S.lastSeconds = 0;
+    S.lastGrid = {0, 0, 0}; S.lastBlock = {0, 0, 0};
+    if (d->M && dY) {
+        HIP_TRY(hipMemsetAsync(dY, 0, d->M * sizeof(double), cx.stream));
+        if (cx.sync) HIP_TRY(hipStreamSynchronize(cx.stream));
+    }
+    return EXIT_SUCCESS;
+}
+
+// the bodies of the public launchers that the host-matrix wrappers and the selections call with a context of their own
+typedef int LaunchFn(Ctx cx, spmat* dMat, double* dX, CONFIG cfg, double* dY);
+LaunchFn rowsCSR, warpPerRowCSR, rowsELL, warpsPerRowELL;     // launch.hip: hipSpMVRowsCSR, ...WarpPerRowCSR, ...RowsELL, ...WarpsPerRowELLNTrasposed
+int streamCSR(Ctx cx, spmat* dMat, double* dX, double* dY, bool seq);              // launch.hip: the LDS-stream kernel
+int tilesForm(Ctx cx, spmat* dMat, double* dX, double* dY, bool det, const char* who);     // ... the two-phase / stripes launchers on
+int stripesForm(Ctx cx, spmat* dMat, double* dX, double* dY, int mode, const char* who);   // the given form (built at the first call)
+int autoRun(Ctx cx, spmat* dMat, double* dX, double* dY, int serial, const char* who);     // select.hip
+int vecFill(Ctx cx, double* dVec, size_t n, uint64_t pattern);                     // abi.hip: spmvHipVecFill
+int probeLdsOrder(hipStream_t stream);                                             // abi.hip: spmvHipProbeLdsAtomicOrder
+void freePushStream();                                                             // launch.hip: the side stream of hipSpMVTilesReducePush
+
+}  // namespace spmvhip
+#pragma GCC visibility pop

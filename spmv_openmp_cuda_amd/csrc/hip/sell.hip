@@ -264,7 +264,7 @@ int buildSell(DevMat* d) {
     if (d->kind != Kind::CSR) return EXIT_FAILURE;
     if (d->M >= 0x7FFFFFFFull) { fprintf(stderr, "libspmvhip: sell: more than 2^31 rows unsupported\n"); return EXIT_FAILURE; }
     SellFormat* f = new SellFormat;
-    const int rc = d->irpBytes == 4 ? buildSellT<uint32_t>(d, f) : buildSellT<uint64_t>(d, f);
+    const int rc = withIrp(d, [&](auto irp) { return buildSellT<IrpT<decltype(irp)>>(d, f); });
     if (rc) { (void)hipGetLastError(); fprintf(stderr, "libspmvhip: sell: format build failed\n"); freeSell(f); return EXIT_FAILURE; }
     d->sell = f;
     return EXIT_SUCCESS;
@@ -285,14 +285,11 @@ int enqueueSell(DevMat* d, const double* x, double* y, hipStream_t stream) {
     if (f->nSlices)
         hipLaunchKernelGGL(sell_spmv_kernel, grid2d(((uint64_t)f->nSlices + 3) / 4, 256), dim3(256), 0, stream, f->nSlices,
                            f->sliceOff, f->perm, f->slen, f->val, f->col, x, y);
-    if (f->nLong) {
-        if (d->irpBytes == 4)
-            hipLaunchKernelGGL((sell_long_kernel<uint32_t>), grid2d(f->nLong, 256), dim3(256), 0, stream, f->nLong, f->longRows,
-                               static_cast<const uint32_t*>(d->IRP), d->JA, d->AS, x, y);
-        else
-            hipLaunchKernelGGL((sell_long_kernel<uint64_t>), grid2d(f->nLong, 256), dim3(256), 0, stream, f->nLong, f->longRows,
-                               static_cast<const uint64_t*>(d->IRP), d->JA, d->AS, x, y);
-    }
+    if (f->nLong)
+        withIrp(d, [&](auto irp) {
+            hipLaunchKernelGGL((sell_long_kernel<IrpT<decltype(irp)>>), grid2d(f->nLong, 256), dim3(256), 0, stream, f->nLong, f->longRows,
+                               irp, d->JA, d->AS, x, y);
+        });
     return hipGetLastError() == hipSuccess ? EXIT_SUCCESS : EXIT_FAILURE;
 }
 

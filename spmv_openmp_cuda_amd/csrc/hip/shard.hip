@@ -24,7 +24,7 @@
 #include <vector>
 
 #include "spmvHip.h"
-#include "device_mat.hpp"
+#include "lib.hpp"
 
 namespace {
 
@@ -268,6 +268,63 @@ int spmvHipSpMVSharded(void* handle, const double* hX, int mode, double* hY, dou
     if (kernelSec) *kernelSec = kmax;                       // kernels of all row groups, slowest device
     if (gatherSec) *gatherSec = std::max(0.0, tmax - kmax); // what the exchange adds to the step after overlap
     return EXIT_SUCCESS;
+}
+
+// ------------------------------------------------------------------------ sharding helpers (host side)
+int spmvHipPartitionRows(const ulong* IRP, ulong M, int nParts, ulong* bounds) {
+    if (!IRP || !bounds || nParts <= 0) return EXIT_FAILURE;
+    const ulong nnz = IRP[M] - IRP[0];
+    bounds[0] = 0;
+    for (int p = 1; p < nParts; ++p) {
+        // first row whose starting offset reaches p/nParts of the nnz
+        const ulong target = IRP[0] + (ulong)(((__uint128_t)nnz * (unsigned)p) / (unsigned)nParts);
+        const ulong* it = std::lower_bound(IRP, IRP + M + 1, target);
+        ulong r = (ulong)(it - IRP);
+        if (r > M) r = M;
+        // choose the closer of r-1 / r
+        if (r > 0 && target - IRP[r - 1] < IRP[r] - target) --r;
+        bounds[p] = std::max(r, bounds[p - 1]);
+    }
+    bounds[nParts] = M;
+    return EXIT_SUCCESS;
+}
+
+int spmvHipCompactRows(double* dY, const double* dYPad, const ulong* bounds, int nParts, ulong maxRows) {
+    if (!dY || !dYPad || !bounds || nParts <= 0) return EXIT_FAILURE;
+    const spmvhip::Ctx cx = spmvhip::libraryCtx();
+    for (int p = 0; p < nParts; ++p) {                   // every block checked before the first copy: a refusal leaves dY as it was
+        const ulong rows = bounds[p + 1] - bounds[p];
+        if (rows > maxRows) { ERR("spmvHipCompactRows: block %d has %lu rows > pad %lu", p, rows, maxRows); return EXIT_FAILURE; }
+    }
+    for (int p = 0; p < nParts; ++p) {
+        const ulong rows = bounds[p + 1] - bounds[p];
+        if (rows)
+            HIP_TRY(hipMemcpyAsync(dY + bounds[p], dYPad + (size_t)p * maxRows, rows * sizeof(double),
+                                   hipMemcpyDeviceToDevice, cx.stream));
+    }
+    if (cx.sync) HIP_TRY(hipStreamSynchronize(cx.stream));
+    return EXIT_SUCCESS;
+}
+
+spmat* spmvHipRowBlockCSR(const spmat* host, ulong r0, ulong r1) {
+    if (!host || !host->IRP || r0 > r1 || r1 > host->M) return nullptr;
+    spmat* out = static_cast<spmat*>(calloc(1, sizeof(spmat)));
+    if (!out) return nullptr;
+    const ulong base = host->IRP[r0], nz = host->IRP[r1] - base, rows = r1 - r0;
+    out->M = rows; out->N = host->N; out->NZ = nz;
+    out->IRP = static_cast<ulong*>(malloc((rows + 1) * sizeof(ulong)));
+    out->JA  = static_cast<ulong*>(malloc(std::max<ulong>(nz, 1) * sizeof(ulong)));
+    out->AS  = static_cast<double*>(malloc(std::max<ulong>(nz, 1) * sizeof(double)));
+    if (host->RL) out->RL = static_cast<ulong*>(malloc(std::max<ulong>(rows, 1) * sizeof(ulong)));
+    if (!out->IRP || !out->JA || !out->AS || (host->RL && !out->RL)) {
+        free(out->IRP); free(out->JA); free(out->AS); free(out->RL); free(out);
+        return nullptr;
+    }
+    for (ulong r = 0; r <= rows; ++r) out->IRP[r] = host->IRP[r0 + r] - base;
+    memcpy(out->JA, host->JA + base, nz * sizeof(ulong));
+    memcpy(out->AS, host->AS + base, nz * sizeof(double));
+    if (host->RL) memcpy(out->RL, host->RL + r0, rows * sizeof(ulong));
+    return out;
 }
 
 }  // extern "C"

@@ -134,12 +134,10 @@ template <int P, bool UNIT>
 void launchPanel(const DevMat* d, uint32_t w, const double* X, uint64_t sxr, uint64_t sxc, double* Y, uint64_t syr,
                  uint64_t syc, hipStream_t stream) {
     const dim3 grid = grid2d(d->nBlk2, WG_THREADS), block(WG_THREADS);
-    if (d->irpBytes == 4)
-        hipLaunchKernelGGL((csr_spmm_kernel<uint32_t, P, UNIT>), grid, block, 0, stream, d->nBlk2, d->nLong2, d->blkInfo,
-                           d->blkBase, static_cast<const uint32_t*>(d->IRP), d->JA, d->AS, d->unitValue, w, X, sxr, sxc, Y, syr, syc);
-    else
-        hipLaunchKernelGGL((csr_spmm_kernel<uint64_t, P, UNIT>), grid, block, 0, stream, d->nBlk2, d->nLong2, d->blkInfo,
-                           d->blkBase, static_cast<const uint64_t*>(d->IRP), d->JA, d->AS, d->unitValue, w, X, sxr, sxc, Y, syr, syc);
+    withIrp(d, [&](auto irp) {
+        hipLaunchKernelGGL((csr_spmm_kernel<IrpT<decltype(irp)>, P, UNIT>), grid, block, 0, stream, d->nBlk2, d->nLong2, d->blkInfo,
+                           d->blkBase, irp, d->JA, d->AS, d->unitValue, w, X, sxr, sxc, Y, syr, syc);
+    });
 }
 
 template <bool UNIT>

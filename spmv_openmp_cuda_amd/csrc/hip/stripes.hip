@@ -529,12 +529,10 @@ int buildStripes(DevMat* d, const spmvStripesOpts* opts) {
     unsigned colBits = 1, groupBits = 1;
     while (colBits < 32 && (1ull << colBits) < N) ++colBits;
     while ((1ull << groupBits) < nGroups) ++groupBits;
-    if (d->irpBytes == 4)
-        hipLaunchKernelGGL((sb_keys_kernel<uint32_t>), grid2d((M + 3) / 4, 256), dim3(256), 0, nullptr, M, static_cast<const uint32_t*>(d->IRP), d->JA,
+    withIrp(d, [&](auto irp) {
+        hipLaunchKernelGGL((sb_keys_kernel<IrpT<decltype(irp)>>), grid2d((M + 3) / 4, 256), dim3(256), 0, nullptr, M, irp, d->JA,
                            f->binRow, B, f->subs, colBits, keys.as<uint64_t>(), idx.as<uint32_t>(), rowOf.as<uint32_t>());
-    else
-        hipLaunchKernelGGL((sb_keys_kernel<uint64_t>), grid2d((M + 3) / 4, 256), dim3(256), 0, nullptr, M, static_cast<const uint64_t*>(d->IRP), d->JA,
-                           f->binRow, B, f->subs, colBits, keys.as<uint64_t>(), idx.as<uint32_t>(), rowOf.as<uint32_t>());
+    });
     if (hipGetLastError() != hipSuccess) return fail("key kernel");
     // (rocPRIM's double-buffer interface: the sort ping-pongs between the two pairs of buffers given here instead of
     // allocating a third full-size pair inside its temporary storage)
@@ -626,12 +624,10 @@ int stripesRefreshValues(DevMat* d, StripeFormat* f, hipStream_t stream, double*
         unsigned colBits = 1, groupBits = 1;         // (as buildStripes chose them)
         while (colBits < 32 && (1ull << colBits) < d->N) ++colBits;
         while ((1ull << groupBits) < nGroups) ++groupBits;
-        if (d->irpBytes == 4)
-            hipLaunchKernelGGL((sb_keys_kernel<uint32_t>), grid2d((M + 3) / 4, 256), dim3(256), 0, stream, M, static_cast<const uint32_t*>(d->IRP), d->JA,
+        withIrp(d, [&](auto irp) {
+            hipLaunchKernelGGL((sb_keys_kernel<IrpT<decltype(irp)>>), grid2d((M + 3) / 4, 256), dim3(256), 0, stream, M, irp, d->JA,
                                f->binRow, f->B, f->subs, colBits, keys.as<uint64_t>(), idx.as<uint32_t>(), rowOf.as<uint32_t>());
-        else
-            hipLaunchKernelGGL((sb_keys_kernel<uint64_t>), grid2d((M + 3) / 4, 256), dim3(256), 0, stream, M, static_cast<const uint64_t*>(d->IRP), d->JA,
-                               f->binRow, f->B, f->subs, colBits, keys.as<uint64_t>(), idx.as<uint32_t>(), rowOf.as<uint32_t>());
+        });
         if (hipGetLastError() != hipSuccess) return fail("key kernel");
         rocprim::double_buffer<uint64_t> dKeys(keys.as<uint64_t>(), keysOut.as<uint64_t>());
         rocprim::double_buffer<uint32_t> dIdx(idx.as<uint32_t>(), perm.as<uint32_t>());

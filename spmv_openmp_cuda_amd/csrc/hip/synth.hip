@@ -64,12 +64,10 @@ extern "C" int spmvHipSynthFillCSR(ulong M, ulong N, ulong rowOffset, const void
     }
     const uint64_t blocks = (M + 3) / 4;
     const dim3 grid = spmvhip::grid2d(blocks, 256);     // 2-D when blocks*256 would overflow the 32-bit work-item count
-    if (irpBytes == 4)
-        hipLaunchKernelGGL((synth_fill_kernel<uint32_t>), grid, dim3(256), 0, nullptr, M, N, rowOffset,
-                           static_cast<const uint32_t*>(dIRP), dJA, dAS, seedStruct, seedVal, band);
-    else
-        hipLaunchKernelGGL((synth_fill_kernel<uint64_t>), grid, dim3(256), 0, nullptr, M, N, rowOffset,
-                           static_cast<const uint64_t*>(dIRP), dJA, dAS, seedStruct, seedVal, band);
+    spmvhip::withIrp(dIRP, irpBytes, [&](auto irp) {
+        hipLaunchKernelGGL((synth_fill_kernel<spmvhip::IrpT<decltype(irp)>>), grid, dim3(256), 0, nullptr, M, N, rowOffset,
+                           irp, dJA, dAS, seedStruct, seedVal, band);
+    });
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     return EXIT_SUCCESS;

@@ -925,12 +925,7 @@ int buildTiles(DevMat* d, const spmvTilesOpts* opts) {
     uint32_t* const keysA = reinterpret_cast<uint32_t*>(prodBuf);
     PbPay* const payA = static_cast<PbPay*>(t->slab);
 
-    if (d->irpBytes == 4)
-        hipLaunchKernelGGL((pb_payload_kernel<uint32_t>), grid2d((M + 3) / 4, 256), dim3(256), 0, nullptr, M, static_cast<const uint32_t*>(d->IRP), d->JA, d->AS,
-                           keysA, payA);
-    else
-        hipLaunchKernelGGL((pb_payload_kernel<uint64_t>), grid2d((M + 3) / 4, 256), dim3(256), 0, nullptr, M, static_cast<const uint64_t*>(d->IRP), d->JA, d->AS,
-                           keysA, payA);
+    withIrp(d, [&](auto irp) { hipLaunchKernelGGL((pb_payload_kernel<IrpT<decltype(irp)>>), grid2d((M + 3) / 4, 256), dim3(256), 0, nullptr, M, irp, d->JA, d->AS, keysA, payA); });
     PB_TRY(hipGetLastError());
 
     unsigned bits = 1;

@@ -115,10 +115,7 @@ void enqueueSortedBounds(uint64_t nnz, uint64_t N, const uint32_t* keys, uint32_
 void enqueueRowOf(uint64_t M, const void* IRP, int irpBytes, uint32_t* rowOf, hipStream_t st) {
     if (!M) return;
     const dim3 rows = grid2d((M + TR_THREADS / TR_ROW_LANES - 1) / (TR_THREADS / TR_ROW_LANES), TR_THREADS);
-    if (irpBytes == 4)
-        hipLaunchKernelGGL((tr_row_of_kernel<uint32_t>), rows, dim3(TR_THREADS), 0, st, M, static_cast<const uint32_t*>(IRP), rowOf);
-    else
-        hipLaunchKernelGGL((tr_row_of_kernel<uint64_t>), rows, dim3(TR_THREADS), 0, st, M, static_cast<const uint64_t*>(IRP), rowOf);
+    withIrp(IRP, irpBytes, [&](auto irp) { hipLaunchKernelGGL((tr_row_of_kernel<IrpT<decltype(irp)>>), rows, dim3(TR_THREADS), 0, st, M, irp, rowOf); });
 }
 
 int transposeCsr(const DevMat* a, DevMat* t, hipStream_t st) {

@@ -322,12 +322,10 @@ int triAnalyse(DevMat* d, int uplo, uint32_t T, hipStream_t st) {
         hipMemsetAsync(bad.p, 0xFF, 4, st))
         return fail("memset");
     // 1. counts, keys, diagonal
-    if (d->irpBytes == 4)
-        hipLaunchKernelGGL((tri_count_kernel<uint32_t>), rowsGrid, blk, 0, st, M, N, static_cast<const uint32_t*>(d->IRP), d->JA,
+    withIrp(d, [&](auto irp) {
+        hipLaunchKernelGGL((tri_count_kernel<IrpT<decltype(irp)>>), rowsGrid, blk, 0, st, M, N, irp, d->JA,
                            upper, cnt.as<uint32_t>(), key.as<uint32_t>(), lvl.as<uint32_t>(), s->diagPos, bad.as<uint32_t>());
-    else
-        hipLaunchKernelGGL((tri_count_kernel<uint64_t>), rowsGrid, blk, 0, st, M, N, static_cast<const uint64_t*>(d->IRP), d->JA,
-                           upper, cnt.as<uint32_t>(), key.as<uint32_t>(), lvl.as<uint32_t>(), s->diagPos, bad.as<uint32_t>());
+    });
     // 2. dependents: rows of the strict triangle's entries, stably sorted by column
     if (nnz) {
         enqueueRowOf(M, d->IRP, d->irpBytes, rowOf.as<uint32_t>(), st);
@@ -424,13 +422,10 @@ int enqueueTrsv(const DevMat* d, int uplo, int diag, const double* b, double* x,
                 const uint32_t* stop) {
     const TriSchedule* s = d->tri[uplo];
     const int upper = uplo == SPMV_TRI_UPPER, dunit = diag == SPMV_DIAG_UNIT;
-    if (d->irpBytes == 4) {
-        if (d->unit) launchSteps<uint32_t, true>(d, s, upper, dunit, b, x, st, grid, block, stop);
-        else         launchSteps<uint32_t, false>(d, s, upper, dunit, b, x, st, grid, block, stop);
-    } else {
-        if (d->unit) launchSteps<uint64_t, true>(d, s, upper, dunit, b, x, st, grid, block, stop);
-        else         launchSteps<uint64_t, false>(d, s, upper, dunit, b, x, st, grid, block, stop);
-    }
+    withIrp(d, [&](auto irp) {
+        if (d->unit) launchSteps<IrpT<decltype(irp)>, true>(d, s, upper, dunit, b, x, st, grid, block, stop);
+        else         launchSteps<IrpT<decltype(irp)>, false>(d, s, upper, dunit, b, x, st, grid, block, stop);
+    });
     return hipGetLastError() == hipSuccess ? EXIT_SUCCESS : EXIT_FAILURE;
 }
 

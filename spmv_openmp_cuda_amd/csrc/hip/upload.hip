@@ -1,0 +1,443 @@
+// upload.hip -- device handles: upload, adoption of device arrays, CSR -> ELL, transpose handles, free, and what looks at
+// the values of a handle (unit-value detection, the value refresh).
+#include <hip/hip_runtime.h>
+#include <chrono>
+#include <cstring>
+#include <limits>
+#include <vector>
+
+#include "lib.hpp"
+
+using namespace spmvhip;
+
+namespace {
+
+// Block table of csr_stream2_kernel: rows packed while nnz <= STREAM_NNZ and rows <= STREAM2_MAX_ROWS;
+// a longer row is a block of its own, flagged, and all such blocks come first (longest first) so that
+// their serial tails overlap the rest of the grid.
+template <typename I>
+int buildRowBlocks2(DevMat* d, const I* IRP, uint64_t M) {
+    std::vector<uint4> info, longs;
+    std::vector<uint64_t> base, longBase;
+    info.reserve(M / 64 + 2); base.reserve(M / 64 + 2);
+    d->maxRowNnz = 0;
+    for (uint64_t i = 0; i < M; ++i) d->maxRowNnz = std::max<uint64_t>(d->maxRowNnz, (uint64_t)IRP[i + 1] - (uint64_t)IRP[i]);
+    uint64_t r = 0;
+    while (r < M) {
+        const uint64_t start = IRP[r];
+        uint64_t e = r;
+        while (e < M && (uint64_t)IRP[e + 1] - start <= (uint64_t)STREAM_NNZ && e - r < STREAM2_MAX_ROWS) ++e;
+        if (e == r) {
+            const uint64_t len = (uint64_t)IRP[r + 1] - start;
+            if (len >= (1ull << 32)) { ERR("a single row with %lu entries is not supported", (unsigned long)len); return EXIT_FAILURE; }
+            longs.push_back(make_uint4((uint32_t)r, 1u, (uint32_t)len, 1u));
+            longBase.push_back(start);
+            e = r + 1;
+        } else {
+            info.push_back(make_uint4((uint32_t)r, (uint32_t)(e - r), (uint32_t)((uint64_t)IRP[e] - start), 0u));
+            base.push_back(start);
+        }
+        r = e;
+    }
+    std::vector<size_t> order(longs.size());
+    for (size_t i = 0; i < order.size(); ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return longs[a].z > longs[b].z; });
+    std::vector<uint4> allInfo; std::vector<uint64_t> allBase;
+    allInfo.reserve(longs.size() + info.size()); allBase.reserve(longs.size() + info.size());
+    for (size_t i : order) { allInfo.push_back(longs[i]); allBase.push_back(longBase[i]); }
+    allInfo.insert(allInfo.end(), info.begin(), info.end());
+    allBase.insert(allBase.end(), base.begin(), base.end());
+    d->nBlk2 = (uint32_t)allInfo.size();
+    d->nLong2 = (uint32_t)longs.size();
+    HIP_TRY(hipMalloc(&d->blkInfo, std::max<size_t>(allInfo.size(), 1) * sizeof(uint4)));
+    HIP_TRY(hipMalloc(&d->blkBase, std::max<size_t>(allBase.size(), 1) * sizeof(uint64_t)));
+    HIP_TRY(hipMemcpy(d->blkInfo, allInfo.data(), allInfo.size() * sizeof(uint4), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d->blkBase, allBase.data(), allBase.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+    return EXIT_SUCCESS;
+}
+
+void freeDesc(DevMat* d) {
+    if (!d) return;
+    if (d->owns) {
+        (void)hipFree(d->IRP); (void)hipFree(d->JA); (void)hipFree(d->AS); (void)hipFree(d->RL);
+    }
+    (void)hipFree(d->blkInfo); (void)hipFree(d->blkBase); (void)hipFree(d->tmap);
+    freeTri(d->tri[0]); freeTri(d->tri[1]);
+    freeTiles(d->tiles); freeTiles(d->tilesAlt);
+    freeSell(d->sell);
+    freeStripes(d->stripes); freeStripes(d->stripesAlt);
+    d->magic = 0;
+    delete d;
+}
+
+void publish(spmat* h, DevMat* d, ulong M, ulong N, ulong NZ, ulong maxRowNz) {
+    memset(h, 0, sizeof *h);
+    h->M = M; h->N = N; h->NZ = NZ; h->MAX_ROW_NZ = maxRowNz;
+    h->JA = reinterpret_cast<ulong*>(d->JA);
+    h->AS = d->AS;
+    h->IRP = reinterpret_cast<ulong*>(d->IRP);
+    h->RL = reinterpret_cast<ulong*>(d->RL);
+    h->pitchJA = h->pitchAS = d->pitch;
+    h->dev = d;
+}
+
+template <typename T>
+int narrowUpload(T** dDst, const ulong* hSrc, size_t n, ulong limit, const char* what) {
+    std::vector<T> tmp(n);
+    for (size_t i = 0; i < n; ++i) {
+        if (hSrc[i] > limit) { ERR("%s[%zu] = %lu does not fit the device index width", what, i, hSrc[i]); return EXIT_FAILURE; }
+        tmp[i] = (T)hSrc[i];
+    }
+    HIP_TRY(hipMalloc(dDst, std::max<size_t>(n, 1) * sizeof(T)));
+    HIP_TRY(hipMemcpy(*dDst, tmp.data(), n * sizeof(T), hipMemcpyHostToDevice));
+    return EXIT_SUCCESS;
+}
+
+// device-side CSR -> ELL (row-major [rows][pitch] or column-major [slots][pitch]); one wavefront per row
+template <typename I>
+__global__ __launch_bounds__(256) void csr_to_ell_kernel(uint32_t M, uint32_t K, size_t pitch, int colMajor,
+                                                         const I* __restrict__ IRP, const uint32_t* __restrict__ JA,
+                                                         const double* __restrict__ AS, uint32_t* __restrict__ EJ,
+                                                         double* __restrict__ EA, uint32_t* __restrict__ RL) {
+    const uint64_t row = linear_block() * 4 + threadIdx.x / 64;
+    if (row >= M) return;
+    const uint32_t lane = threadIdx.x % 64;
+    const I b = IRP[row];
+    const uint32_t len = (uint32_t)(IRP[row + 1] - b);
+    if (lane == 0) RL[row] = len;
+    for (uint32_t c = lane; c < K; c += 64) {
+        const size_t at = colMajor ? (size_t)c * pitch + row : (size_t)row * pitch + c;
+        EJ[at] = c < len ? JA[b + c] : 0u;          // padding {0, 0.0} like the loader's calloc
+        EA[at] = c < len ? AS[b + c] : 0.0;
+    }
+}
+
+// 1 in *flag unless every value has the bit pattern `first` (bit patterns: -0.0 and 0.0, or two NaNs, are different values here)
+__global__ __launch_bounds__(256) void values_differ_kernel(const uint64_t* __restrict__ AS, uint64_t n, uint64_t first, uint32_t* __restrict__ flag) {
+    bool differ = false;
+    for (uint64_t j = linear_block() * 256 + threadIdx.x; j < n; j += (uint64_t)gridDim.x * gridDim.y * 256) differ |= AS[j] != first;
+    if (differ) atomicOr(flag, 1u);
+}
+
+// ELL: every REAL cell (slot < RL[row]) has the bit pattern `first`; padding cells are not looked at
+__global__ __launch_bounds__(256) void ell_values_differ_kernel(uint64_t rows, size_t pitch, int colMajor, const uint64_t* __restrict__ AS,
+                                                                const uint32_t* __restrict__ RL, uint64_t first, uint32_t* __restrict__ flag) {
+    const uint64_t r = linear_block() * 256 + threadIdx.x;
+    if (r >= rows) return;
+    bool differ = false;
+    for (uint32_t i = 0, n = RL[r]; i < n; ++i) differ |= AS[colMajor ? r + (uint64_t)i * pitch : r * pitch + i] != first;
+    if (differ) atomicOr(flag, 1u);
+}
+
+// sets d->unit / d->unitValue (one pass over the values at upload and after a value update; off with spmvHipSetUnitValues(0)):
+// does every stored value have the bit pattern `first` of one of them?  CSR: all of AS against AS[0]; ELL with row
+// lengths: every real cell against slot 0 of the first non-empty row
+int detectUnit(DevMat* d, hipStream_t st = nullptr) {
+    const bool csr = d->kind == Kind::CSR, colMajor = d->kind == Kind::ELL_COLMAJOR;
+    d->unit = false;
+    if (!S.unitValues || !d->AS || (csr ? d->NZ == 0 : !d->RL || d->M == 0 || d->ellFirstRow == ~0ull)) return EXIT_SUCCESS;
+    uint64_t first = 0;
+    uint32_t differ = 1;
+    HIP_TRY(hipMemcpyAsync(&first, d->AS + (csr ? 0 : colMajor ? d->ellFirstRow : d->ellFirstRow * d->pitch), 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const uint64_t* AS = reinterpret_cast<const uint64_t*>(d->AS);
+    const int rc = deviceFlag(0, st, csr ? "values_differ_kernel" : "ell_values_differ_kernel", &differ, [&](uint32_t* dFlag) {
+        if (csr) hipLaunchKernelGGL(values_differ_kernel, grid2d(std::min<uint64_t>((d->NZ + 255) / 256, 256 * 64), 256), dim3(256), 0, st, AS, d->NZ, first, dFlag);
+        else hipLaunchKernelGGL(ell_values_differ_kernel, grid2d((d->M + 255) / 256, 256), dim3(256), 0, st, d->M, d->pitch, colMajor ? 1 : 0, AS, d->RL, first, dFlag);
+    });
+    if (rc == EXIT_SUCCESS && !differ) { d->unit = true; memcpy(&d->unitValue, &first, 8); }
+    return rc;
+}
+// row pointers must start at 0, never decrease and end at NZ: the kernels trust them for every AS/JA access
+template <typename I>
+bool rowPointersOk(const I* IRP, uint64_t M, uint64_t NZ, const char* who) {
+    if ((uint64_t)IRP[0] != 0 || (uint64_t)IRP[M] != NZ) {
+        ERR("%s: inconsistent row pointers (IRP[0]=%lu IRP[M]=%lu NZ=%lu)", who, (unsigned long)IRP[0], (unsigned long)IRP[M], (unsigned long)NZ);
+        return false;
+    }
+    for (uint64_t r = 0; r < M; ++r)
+        if (IRP[r] > IRP[r + 1]) { ERR("%s: row pointers decrease at row %lu (%lu > %lu)", who, (unsigned long)r, (unsigned long)IRP[r], (unsigned long)IRP[r + 1]); return false; }
+    return true;
+}
+
+// Upload an (nRows x nCols) row-major host array pair with a padded pitch.
+int uploadPitched(DevMat* d, const ulong* hJA, const double* hAS, size_t nRows, size_t nCols,
+                         size_t pitch, ulong colLimit) {
+    const size_t total = std::max<size_t>(nRows * pitch, 1);
+    std::vector<uint32_t> ja(total, 0u);
+    std::vector<double>   as(total, 0.0);
+    for (size_t r = 0; r < nRows; ++r)
+        for (size_t c = 0; c < nCols; ++c) {
+            const ulong col = hJA[r * nCols + c];
+            if (col > colLimit) { ERR("spMatCpyELL: column id %lu out of range", col); return EXIT_FAILURE; }
+            ja[r * pitch + c] = (uint32_t)col;
+            as[r * pitch + c] = hAS[r * nCols + c];
+        }
+    HIP_TRY(hipMalloc(&d->JA, total * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc(&d->AS, total * sizeof(double)));
+    HIP_TRY(hipMemcpy(d->JA, ja.data(), total * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d->AS, as.data(), total * sizeof(double), hipMemcpyHostToDevice));
+    d->pitch = pitch;
+    return EXIT_SUCCESS;
+}
+
+int ellUpload(spmat* m, spmat* dst, bool transposed) {
+    if (!ready("spMatCpyELL") || !m || !dst) return EXIT_FAILURE;
+    if (!m->JA || !m->AS) { ERR("spMatCpyELL: host matrix has no ELL arrays"); return EXIT_FAILURE; }
+    // reference field convention: a transposed matrix keeps slots in M and rows in MAX_ROW_NZ / N
+    const ulong rows  = transposed ? m->MAX_ROW_NZ : m->M;
+    const ulong slots = transposed ? m->M : m->MAX_ROW_NZ;
+    // a transposed struct has lost the column count to the reference's field swap; this repo's ellTranspose (and
+    // api.HostELL.transpose) keep it in the unused host field pitchJA -- 0 = unknown, column ids then cannot be checked
+    const ulong cols  = transposed ? (ulong)m->pitchJA : m->N;
+    if (rows >= (1ull << 32) - 1 || slots >= (1ull << 32) - 1) { ERR("spMatCpyELL: dimensions exceed 32-bit ids"); return EXIT_FAILURE; }
+    DevMat* d = new DevMat;
+    d->kind = transposed ? Kind::ELL_COLMAJOR : Kind::ELL_ROWMAJOR;
+    d->M = rows; d->N = cols; d->NZ = m->NZ; d->K = slots;
+    int rc;
+    const ulong colLimit = transposed ? (cols ? cols - 1 : 0xFFFFFFFFul) : (m->N ? m->N - 1 : 0);
+    if (transposed) rc = uploadPitched(d, m->JA, m->AS, slots, rows, (rows + 63) / 64 * 64, colLimit);
+    else            rc = uploadPitched(d, m->JA, m->AS, rows, slots, (slots + 1) / 2 * 2, colLimit);   // (rows stay 16-B aligned; a wider pitch is only padding to stream)
+    if (!rc && m->RL) rc = narrowUpload<uint32_t>(&d->RL, m->RL, rows, slots, "RL");
+    if (!rc && m->RL) {                                // the first non-empty row: slot 0 of it is what the unit detection compares with
+        ulong r = 0;
+        while (r < rows && m->RL[r] == 0) ++r;
+        if (r < rows) d->ellFirstRow = r;
+        rc = detectUnit(d);
+    }
+    if (rc) { freeDesc(d); return EXIT_FAILURE; }
+    publish(dst, d, m->M, m->N, m->NZ, m->MAX_ROW_NZ);
+    return EXIT_SUCCESS;
+}
+
+}  // namespace
+
+namespace spmvhip {
+// spmvHipUpdateValues / spmvHipValuesChanged (reread: the handle's own AS was rewritten) / spmvHipShardUpdateValues (its
+// per-device stream): the contract is in spmvHip.h, the design in DESIGN.md section 14
+int updateValues(spmat* h, const double* AS, bool onDevice, bool reread, hipStream_t st, const char* who) {
+    if (!ready(who)) return EXIT_FAILURE;
+    DevMat* d = descOf(h, who);
+    if (!d) return EXIT_FAILURE;
+    if (!reread && !AS) { ERR("%s: AS is NULL", who); return EXIT_FAILURE; }
+    if (d->derived) {
+        ERR("%s: this ELL handle was made on the device from a CSR handle (spmvHipCsrToEll) and keeps no link to it: "
+            "update the CSR handle and convert again", who);
+        return EXIT_FAILURE;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    spmvUpdateInfo info{};
+    info.unitBefore = d->unit;
+    const double valueBefore = d->unitValue;
+    const hipMemcpyKind kind = onDevice ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    if (d->kind == Kind::CSR) {
+        if (!reread && d->NZ) HIP_TRY(hipMemcpyAsync(d->AS, AS, d->NZ * sizeof(double), kind, st));
+        if (detectUnit(d, st)) return EXIT_FAILURE;
+        // every built format, both forms.  When the values were unit before and are unit now no kernel reads a value array
+        // (SELL has no unit kernel): only the value in the registers changes.  A stripes format built for a unit matrix has
+        // no value array: it is rebuilt, with its recorded options, when the values stop being unit.
+        const bool arrays = !(info.unitBefore && d->unit);
+        for (TileFormat* t : {d->tiles, d->tilesAlt})
+            if (t && arrays && tilesRefreshValues(d, t, st, &info.mapMs, &info.mapsBuilt)) return EXIT_FAILURE;
+        std::vector<spmvStripesOpts> rebuild;
+        for (StripeFormat* f : {d->stripes, d->stripesAlt}) {
+            if (!f) continue;
+            if (!stripesHasValues(f) && !d->unit) { rebuild.push_back(stripesOptions(f)); continue; }
+            if (stripesHasValues(f) && arrays && stripesRefreshValues(d, f, st, &info.mapMs, &info.mapsBuilt)) return EXIT_FAILURE;
+            stripesSetUnit(f, d->unit, d->unitValue);
+        }
+        if (sellRefreshValues(d, st)) return EXIT_FAILURE;
+        if (!rebuild.empty()) {
+            HIP_TRY(hipStreamSynchronize(st));           // the builds run on the null stream from AS
+            for (const spmvStripesOpts& o : rebuild)
+                if (buildStripes(d, &o)) { ERR("%s: rebuilding the stripes format failed", who); return EXIT_FAILURE; }
+            info.rebuilt = 1;
+        }
+        if (info.unitBefore && !d->unit) {               // the selections measured the byte counts of the unit kernels
+            d->autoPick[0] = d->autoPick[1] = -1;
+            memset(d->autoMs, 0, sizeof d->autoMs);
+        }
+    } else {
+        const bool colMajor = d->kind == Kind::ELL_COLMAJOR;
+        const size_t nRows = colMajor ? d->K : d->M, nCols = colMajor ? d->M : d->K;      // the host layout of the upload
+        if (!reread && nRows && nCols)
+            HIP_TRY(hipMemcpy2DAsync(d->AS, d->pitch * sizeof(double), AS, nCols * sizeof(double), nCols * sizeof(double), nRows, kind, st));
+        if (detectUnit(d, st)) return EXIT_FAILURE;
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    info.unitAfter = d->unit;
+    const bool sameUnit = info.unitBefore && d->unit && memcmp(&valueBefore, &d->unitValue, 8) == 0;
+    info.inPlace = !info.rebuilt && (!info.unitBefore || sameUnit);
+    info.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    d->lastUpdate = info;
+    return EXIT_SUCCESS;
+}
+}  // namespace spmvhip
+
+extern "C" {
+
+int spMatCpyCSR(spmat* m, spmat* dst) {
+    if (!ready("spMatCpyCSR") || !m || !dst) return EXIT_FAILURE;
+    if (!m->IRP || (m->NZ && (!m->JA || !m->AS))) { ERR("spMatCpyCSR: host matrix has no CSR arrays"); return EXIT_FAILURE; }
+    if (m->M >= (1ull << 32) - 1 || m->N > (1ull << 32)) { ERR("spMatCpyCSR: %lu x %lu exceeds the 32-bit row/column ids of the device format", m->M, m->N); return EXIT_FAILURE; }
+    if (!rowPointersOk(m->IRP, m->M, m->NZ, "spMatCpyCSR")) return EXIT_FAILURE;
+    DevMat* d = new DevMat;
+    d->kind = Kind::CSR;
+    d->M = m->M; d->N = m->N; d->NZ = m->NZ;
+    d->irpBytes = m->NZ < IRP32_LIMIT ? 4 : 8;
+    int rc = withIrp(d, [&](auto irp) {
+        using I = IrpT<decltype(irp)>;
+        return narrowUpload<I>(reinterpret_cast<I**>(&d->IRP), m->IRP, m->M + 1, std::numeric_limits<I>::max(), "IRP");
+    });
+    if (!rc) rc = narrowUpload<uint32_t>(&d->JA, m->JA, m->NZ, m->N ? m->N - 1 : 0, "JA");
+    if (!rc) {
+        if (!hipOk(hipMalloc(&d->AS, std::max<size_t>(m->NZ, 1) * sizeof(double)), "hipMalloc AS") ||
+            !hipOk(hipMemcpy(d->AS, m->AS, m->NZ * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy AS")) rc = EXIT_FAILURE;
+    }
+    if (!rc && m->RL) rc = narrowUpload<uint32_t>(&d->RL, m->RL, m->M, 0xFFFFFFFFul, "RL");
+    if (!rc) rc = buildRowBlocks2(d, m->IRP, m->M);
+    if (!rc) rc = detectUnit(d);
+    if (rc) { freeDesc(d); return EXIT_FAILURE; }
+    publish(dst, d, m->M, m->N, m->NZ, 0);
+    return EXIT_SUCCESS;
+}
+
+int spmvHipAdoptCSR(spmat* dst, ulong M, ulong N, ulong NZ, const void* dIRP, int irpBytes,
+                    const uint32_t* dJA, const double* dAS, const void* hIRP) {
+    if (!ready("spmvHipAdoptCSR") || !dst || !dIRP) return EXIT_FAILURE;
+    if (irpBytes != 4 && irpBytes != 8) { ERR("spmvHipAdoptCSR: irpBytes must be 4 or 8"); return EXIT_FAILURE; }
+    if (irpBytes < 8 && NZ >= IRP32_LIMIT) { ERR("spmvHipAdoptCSR: NZ=%lu needs 64-bit row pointers", NZ); return EXIT_FAILURE; }
+    if (M >= (1ull << 32) - 1 || N > (1ull << 32)) { ERR("spmvHipAdoptCSR: dimensions exceed 32-bit ids"); return EXIT_FAILURE; }
+    std::vector<unsigned char> tmp;
+    if (!hIRP) {
+        tmp.resize((M + 1) * (size_t)irpBytes);
+        HIP_TRY(hipMemcpy(tmp.data(), dIRP, tmp.size(), hipMemcpyDeviceToHost));
+        hIRP = tmp.data();
+    }
+    if (!withIrp(hIRP, irpBytes, [&](auto irp) { return rowPointersOk(irp, M, NZ, "spmvHipAdoptCSR"); })) return EXIT_FAILURE;
+    DevMat* d = new DevMat;
+    d->kind = Kind::CSR; d->owns = false;
+    d->M = M; d->N = N; d->NZ = NZ; d->irpBytes = irpBytes;
+    d->IRP = const_cast<void*>(dIRP); d->JA = const_cast<uint32_t*>(dJA); d->AS = const_cast<double*>(dAS);
+    if (withIrp(hIRP, irpBytes, [&](auto irp) { return buildRowBlocks2(d, irp, M); }) || detectUnit(d)) { freeDesc(d); return EXIT_FAILURE; }
+    publish(dst, d, M, N, NZ, 0);
+    return EXIT_SUCCESS;
+}
+
+int spMatCpyELL(spmat* m, spmat* dst) { return ellUpload(m, dst, m && m->dev == SPMAT_TAG_ELL_TRANSPOSED); }
+int spMatCpyELLTransposed(spmat* m, spmat* dst) { return ellUpload(m, dst, true); }
+
+int spmvHipCsrToEll(spmat* dCsr, int transposed, spmat* dEll) {
+    DevMat* c = descOf(dCsr, "spmvHipCsrToEll");
+    if (!c || !dEll || !csrOnly(c, "spmvHipCsrToEll", "source handle is not CSR")) return EXIT_FAILURE;
+    const uint64_t K = c->maxRowNnz, rows = c->M;
+    DevMat* d = new DevMat;
+    d->kind = transposed ? Kind::ELL_COLMAJOR : Kind::ELL_ROWMAJOR;
+    d->derived = true;
+    d->M = rows; d->N = c->N; d->NZ = c->NZ; d->K = K;
+    d->pitch = transposed ? (rows + 63) / 64 * 64 : (K + 1) / 2 * 2;
+    const size_t cells = std::max<size_t>((transposed ? K : rows) * d->pitch, 1);
+    {   // ELL size guard.  The reference's loader refuses an ELL copy whose 2*M*maxRow padded cells exceed a fixed host
+        // budget (src/lib/parser.c:223-232, config.h:69-70: 6*2^27 cells); on the device the budget is what the GPU has
+        // free right now -- the unclipped power-law matrix (10 M rows x 50 k slots = 6 TB) is refused here, before any
+        // allocation, the same matrix clipped to 64 slots (7.7 GB) passes.
+        size_t freeB = 0, totalB = 0;
+        const unsigned __int128 need128 = (unsigned __int128)(transposed ? K : rows) * d->pitch * 12 + (unsigned __int128)rows * 4;
+        const size_t need = need128 > (unsigned __int128)~(size_t)0 ? ~(size_t)0 : (size_t)need128;
+        // best effort: what is free at this moment (other processes and cached pools count as used); when the query itself
+        // fails the guard is skipped and hipMalloc decides
+        const bool known = hipMemGetInfo(&freeB, &totalB) == hipSuccess;
+        if (!known) (void)hipGetLastError();
+        if (known && need > freeB) {
+            ERR("spmvHipCsrToEll: ELL copy of %lu rows x %lu slots needs %.1f GB, device has %.1f GB free: refused "
+                "(the reference refuses above 6*2^27 padded cells, parser.c:223-232)", (unsigned long)rows, (unsigned long)K,
+                (double)need * 1e-9, (double)freeB * 1e-9);
+            delete d;
+            return EXIT_FAILURE;
+        }
+    }
+    if (!hipOk(hipMalloc(&d->JA, cells * sizeof(uint32_t)), "hipMalloc ELL JA") ||
+        !hipOk(hipMalloc(&d->AS, cells * sizeof(double)), "hipMalloc ELL AS") ||
+        !hipOk(hipMalloc(&d->RL, std::max<size_t>(rows, 1) * sizeof(uint32_t)), "hipMalloc ELL RL") ||
+        !hipOk(hipMemsetAsync(d->JA, 0, cells * sizeof(uint32_t), S.stream), "memset") ||
+        !hipOk(hipMemsetAsync(d->AS, 0, cells * sizeof(double), S.stream), "memset")) { freeDesc(d); return EXIT_FAILURE; }
+    if (rows) {
+        const dim3 grid = grid2d((rows + 3) / 4, 256);
+        withIrp(c, [&](auto irp) { hipLaunchKernelGGL((csr_to_ell_kernel<IrpT<decltype(irp)>>), grid, dim3(256), 0, S.stream, (uint32_t)rows, (uint32_t)K, d->pitch, transposed, irp, c->JA, c->AS, d->JA, d->AS, d->RL); });
+    }
+    if (!hipOk(hipGetLastError(), "csr_to_ell launch") || !hipOk(hipStreamSynchronize(S.stream), "csr_to_ell")) { freeDesc(d); return EXIT_FAILURE; }
+    d->unit = c->unit; d->unitValue = c->unitValue;   // the same values, and row lengths always
+    // handle fields follow the reference's conventions (transposed: M = slots, MAX_ROW_NZ = rows)
+    if (transposed) publish(dEll, d, K, rows, c->NZ, rows);
+    else            publish(dEll, d, rows, c->N, c->NZ, K);
+    return EXIT_SUCCESS;
+}
+
+// A^T as a handle of its own (transpose.hip builds the arrays; the contract is in spmvHip.h, the design in DESIGN.md
+// section 16).  Refusals come before anything is allocated; a failure after that frees what was made, and dAT is written
+// only on success.
+int spmvHipCsrTranspose(spmat* dA, spmat* dAT) {
+    const char* who = "spmvHipCsrTranspose";
+    if (!ready(who)) return EXIT_FAILURE;
+    if (!dAT) { ERR("%s: dAT is NULL", who); return EXIT_FAILURE; }
+    DevMat* a = descOf(dA, who);
+    if (!a) return EXIT_FAILURE;
+    if (dAT == dA) { ERR("%s: dAT is the source handle itself", who); return EXIT_FAILURE; }
+    if (!csrOnly(a, who, "the source is an ELL handle (only CSR handles can be transposed)")) return EXIT_FAILURE;
+    if (a->NZ >= IRP32_LIMIT) {
+        ERR("%s: NZ=%lu: the map and the row pointers of the transpose are 32-bit (limit %lu)", who, (unsigned long)a->NZ,
+            (unsigned long)IRP32_LIMIT);
+        return EXIT_FAILURE;
+    }
+    if (a->N >= (1ull << 32) - 1) { ERR("%s: N=%lu columns do not fit the row ids of the transpose", who, (unsigned long)a->N); return EXIT_FAILURE; }
+    if (a->NZ && (!a->JA || !a->AS)) { ERR("%s: the source has no column or value array", who); return EXIT_FAILURE; }
+    DevMat* t = new DevMat;
+    t->kind = Kind::CSR;
+    t->M = a->N; t->N = a->M; t->NZ = a->NZ; t->irpBytes = 4;
+    t->srcId = a->id;
+    const size_t nz1 = std::max<size_t>(a->NZ, 1);
+    std::vector<uint32_t> hIRP(t->M + 1);
+    const bool ok = hipOk(hipMalloc(&t->IRP, (t->M + 1) * 4), "hipMalloc IRP") && hipOk(hipMalloc(&t->JA, nz1 * 4), "hipMalloc JA") &&
+                    hipOk(hipMalloc(&t->AS, nz1 * 8), "hipMalloc AS") && hipOk(hipMalloc(&t->tmap, nz1 * 4), "hipMalloc map") &&
+                    !transposeCsr(a, t, S.stream) &&
+                    hipOk(hipMemcpy(hIRP.data(), t->IRP, hIRP.size() * 4, hipMemcpyDeviceToHost), "hipMemcpy IRP") &&
+                    !buildRowBlocks2(t, hIRP.data(), t->M) && !detectUnit(t, S.stream);
+    if (!ok) { ERR("%s: building the transpose failed", who); freeDesc(t); return EXIT_FAILURE; }
+    publish(dAT, t, t->M, t->N, t->NZ, 0);
+    return EXIT_SUCCESS;
+}
+
+int spmvHipTransposeRefresh(spmat* dAT, spmat* dA) {
+    const char* who = "spmvHipTransposeRefresh";
+    if (!ready(who)) return EXIT_FAILURE;
+    DevMat* t = descOf(dAT, who);
+    if (!t) return EXIT_FAILURE;
+    DevMat* a = descOf(dA, who);
+    if (!a) return EXIT_FAILURE;
+    if (!t->srcId) { ERR("%s: dAT was not made by spmvHipCsrTranspose", who); return EXIT_FAILURE; }
+    if (a->id != t->srcId) { ERR("%s: dA is not the handle dAT was transposed from", who); return EXIT_FAILURE; }
+    if (enqueueGatherValues(t->AS, t->tmap, t->NZ, a->AS, S.stream)) return EXIT_FAILURE;
+    return updateValues(dAT, nullptr, true, true, S.stream, who);
+}
+
+int spmvHipUpdateValues(spmat* dMat, const double* AS, int asOnDevice) {
+    return updateValues(dMat, AS, asOnDevice != 0, false, S.stream, "spmvHipUpdateValues");
+}
+int spmvHipValuesChanged(spmat* dMat) { return updateValues(dMat, nullptr, true, true, S.stream, "spmvHipValuesChanged"); }
+int spmvHipLastUpdateInfo(spmat* dMat, spmvUpdateInfo* info) {
+    DevMat* d = descOf(dMat, "spmvHipLastUpdateInfo");
+    if (!d || !info) return EXIT_FAILURE;
+    *info = d->lastUpdate;
+    return EXIT_SUCCESS;
+}
+
+int hipFreeSpmat(spmat* h) {
+    if (!h || !h->dev) return EXIT_SUCCESS;
+    DevMat* d = descOf(h, "hipFreeSpmat");
+    if (!d) return EXIT_FAILURE;
+    freeDesc(d);
+    memset(h, 0, sizeof *h);
+    return EXIT_SUCCESS;
+}
+
+}  // extern "C"

@@ -115,12 +115,7 @@ int enqueueSellValues(uint32_t nSlices, const uint64_t* sliceOff, const uint32_t
                       int irpBytes, const double* AS, double* val, hipStream_t stream) {
     if (!nSlices) return EXIT_SUCCESS;
     const dim3 grid = grid2d(((uint64_t)nSlices + 3) / 4, 256);
-    if (irpBytes == 4)
-        hipLaunchKernelGGL((sell_values_kernel<uint32_t>), grid, dim3(256), 0, stream, nSlices, sliceOff, perm, slen,
-                           static_cast<const uint32_t*>(IRP), AS, val);
-    else
-        hipLaunchKernelGGL((sell_values_kernel<uint64_t>), grid, dim3(256), 0, stream, nSlices, sliceOff, perm, slen,
-                           static_cast<const uint64_t*>(IRP), AS, val);
+    withIrp(IRP, irpBytes, [&](auto irp) { hipLaunchKernelGGL((sell_values_kernel<IrpT<decltype(irp)>>), grid, dim3(256), 0, stream, nSlices, sliceOff, perm, slen, irp, AS, val); });
     return hipOk(hipGetLastError(), "sell_values_kernel") ? EXIT_SUCCESS : EXIT_FAILURE;
 }
 

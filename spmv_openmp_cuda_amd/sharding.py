@@ -50,7 +50,7 @@ class ShardPlan:
 
 
 def partition_by_nnz(irp, parts):
-    """Python twin of spmvHipPartitionRows (csrc/hip/abi.hip): boundary p is the row
+    """Python twin of spmvHipPartitionRows (csrc/hip/shard.hip): boundary p is the row
     whose starting offset is closest to p/parts of the nnz."""
     irp = np.asarray(irp)
     M = irp.size - 1
