@@ -68,6 +68,9 @@ def main():
         if name == "hipSpMVStripesCSR":
             i = api.stripes_info(dm)
             extra = f" bins={i.nBins} rows/bin<={i.rowsPerBin} wide={i.wide} det={i.deterministic} build={i.buildMs:.1f}ms"
+        if name == "hipSpMVTilesCSR":
+            i = api.tiles_info(dm)
+            extra = f" bins={i.nBins} rows/bin<={i.rowsPerBin} chunk={i.chunk} det={i.deterministic} build={i.buildMs:.1f}ms"
         if name in ("hipSpMVWarpPerRowCSR", "hipSpMVAutoCSR", "hipSpMVRowsCSR"):
             ms4 = (C.c_double * 4)()
             pick = (api.lib.spmvHipAutoChoiceRows if name == "hipSpMVRowsCSR" else api.lib.spmvHipAutoChoice)(C.byref(dm.handle), ms4)

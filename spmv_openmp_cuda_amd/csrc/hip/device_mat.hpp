@@ -76,12 +76,13 @@ struct DevMat {
     uint4*    blkInfo = nullptr;    // {first row, #rows, #nnz, long-row flag}
     uint64_t* blkBase = nullptr;    // nnz offset of the block
     uint32_t  nBlk2 = 0, nLong2 = 0;
-    // The two-phase and the stripes format exist in two FORMS each -- arrival-order and deterministic (serial-order) sums --
-    // and a handle may hold both: `tiles` / `stripes` is the ACTIVE one (what the functions of tiles.hip / stripes.hip work
-    // on), `*Alt` the other.  useTiles / useStripes make the requested form the active one (possibly a null slot still to
-    // be built).  `*Pref` is the form the explicit launchers and queries use: set by spmvHipBuildTilesOpt / ...StripesOpt.
-    TileFormat* tiles = nullptr, *tilesAlt = nullptr;         // built lazily by hipSpMVTilesCSR / spmvHipBuildTiles / the selections
-    StripeFormat* stripes = nullptr, *stripesAlt = nullptr;   // built lazily by hipSpMVStripesCSR / spmvHipBuildStripes / the selections
+    // The two-phase format exists in two FORMS -- arrival-order and deterministic (serial-order) sums -- and the stripes
+    // format in two LAYOUTS -- one stream per bin, and owner-wavefront sub-streams.  A handle may hold both of each, every
+    // one in a slot of its own: tiles[deterministic], stripes[stripesLayout(mode)].  The functions of tiles.hip / stripes.hip
+    // are handed the format they work on; nothing here is "the current one".  `*Pref` is the form the explicit launchers
+    // and queries use: set by spmvHipBuildTilesOpt / ...StripesOpt.
+    TileFormat*   tiles[2]   = {nullptr, nullptr};   // built lazily by hipSpMVTilesCSR / spmvHipBuildTiles / the selections
+    StripeFormat* stripes[2] = {nullptr, nullptr};   // built lazily by hipSpMVStripesCSR / spmvHipBuildStripes / the selections
     bool      tilesPref = false;
     int       stripesPref = 0;      // 0 arrival order, 1 owner wavefronts, 2 ordered tickets (spmvStripesOpts.deterministic)
     SellFormat* sell = nullptr;     // built lazily by hipSpMVRowsSELL / spmvHipBuildSell
@@ -118,30 +119,34 @@ void freeSell(SellFormat* f);
 int  enqueueSell(DevMat* d, const double* x, double* y, hipStream_t stream);
 size_t sellBytes(const DevMat* d);
 
-int  buildStripes(DevMat* d, const spmvStripesOpts* opts = nullptr);   // stripes.hip; explicit options replace an existing format
+// the stripes layout of a launch mode (spmvStripesOpts.deterministic, DevMat::stripesPref): 0 arrival order and 2 ordered tickets
+// share the one-stream-per-bin layout [0], 1 owner wavefronts has the sub-stream layout [1]
+inline int stripesLayout(int mode) { return mode == 1; }
+// Builds: nullptr = the automatic format of slot 0, kept if it exists; explicit options replace the format of the slot they name
+// and leave the other alone.  Every other function is handed the format it works on (null where noted: an empty answer).
+int  buildStripes(DevMat* d, const spmvStripesOpts* opts = nullptr);   // stripes.hip
 void freeStripes(StripeFormat* f);
-void useStripes(DevMat* d, bool subStreams);                    // make that LAYOUT the active one (d->stripes may then be null)
-int  enqueueStripes(DevMat* d, const double* x, double* y, hipStream_t stream, int mode, dim3* grid = nullptr, dim3* block = nullptr);
-size_t stripesBytes(const DevMat* d);
-void stripesInfo(const DevMat* d, spmvStripesInfo* out);
+int  enqueueStripes(const StripeFormat* f, const double* x, double* y, hipStream_t stream, int mode, dim3* grid = nullptr, dim3* block = nullptr);
+size_t stripesBytes(const DevMat* d);                           // both layouts
+void stripesInfo(const StripeFormat* f, spmvStripesInfo* out);  // f may be null
 
-int  buildTiles(DevMat* d, const spmvTilesOpts* opts = nullptr); // tiles.hip; explicit options replace an existing format
-void tilesInfo(const DevMat* d, spmvTilesInfo* out);
+int  buildTiles(DevMat* d, const spmvTilesOpts* opts = nullptr); // tiles.hip
+void tilesInfo(const TileFormat* t, spmvTilesInfo* out);        // t may be null
 void freeTiles(TileFormat* t);
-void useTiles(DevMat* d, bool deterministic);                   // make that form the active one (d->tiles may then be null)
 void peerFinalize();                                            // peer.hip: the copy streams of the push exchange
 void freeTilesWorkspace();                                      // the per-device product workspace (8 B/nnz of the largest matrix)
-int  enqueueTiles(DevMat* d, const double* x, double* y, hipStream_t stream);
-int  enqueueTilesExpand(DevMat* d, const double* x, hipStream_t stream);
-int  enqueueTilesReduce(DevMat* d, uint32_t binBegin, uint32_t binEnd, double* y, int nExtra, double* const* extra, hipStream_t stream);
-int  enqueueTilesReducePush(DevMat* d, double* y, int nExtra, double* const* extra, hipStream_t stream, hipStream_t side,
+int  enqueueTiles(const DevMat* d, const TileFormat* t, const double* x, double* y, hipStream_t stream);
+int  enqueueTilesExpand(const DevMat* d, const TileFormat* t, const double* x, hipStream_t stream);
+int  enqueueTilesReduce(const DevMat* d, const TileFormat* t, uint32_t binBegin, uint32_t binEnd, double* y, int nExtra, double* const* extra,
+                        hipStream_t stream);
+int  enqueueTilesReducePush(const DevMat* d, TileFormat* t, double* y, int nExtra, double* const* extra, hipStream_t stream, hipStream_t side,
                             hipEvent_t evFork, hipEvent_t evJoin);
-int  tilesPushFailed(DevMat* d);
-void tilesShape(const DevMat* d, uint32_t* bins, uint32_t* rowsPerBin);
-uint32_t tilesPhase2Threads(const DevMat* d);                   // workgroup size of phase 2 for the active form
-uint64_t tilesBinRow(const DevMat* d, uint32_t bin);
+int  tilesPushFailed(const TileFormat* t);                      // t may be null
+void tilesShape(const TileFormat* t, uint32_t* bins, uint32_t* rowsPerBin);   // t may be null
+uint32_t tilesPhase2Threads(const TileFormat* t);               // workgroup size of phase 2
+uint64_t tilesBinRow(const DevMat* d, const TileFormat* t, uint32_t bin);
 hipStream_t libraryStream();                                    // abi.hip: the stream set with spmvHipSetStream
-size_t tilesBytes(const DevMat* d);
+size_t tilesBytes(const DevMat* d);                             // both forms
 
 // Value refresh (values.hip and the format files).  Each format rewrites its value array from the handle's CSR `AS`
 // (already updated) on `stream`; the map from storage to CSR order is built at a format's first refresh (*mapMs grows by

@@ -57,14 +57,15 @@ void launchEllGroup(hipStream_t stream, DevMat* d, bool rl, dim3 grid, dim3 bloc
 // forms with the builders' own defaults, the deterministic forms (serial-order sums / owner wavefronts) with these
 const spmvTilesOpts   TILES_DETERMINISTIC{0, 0, -1, 0, 1};
 const spmvStripesOpts STRIPES_OWNER{0, 0, -1, -1, 1};
-// make that form the active one and build it if it is missing
-int ensureTiles(DevMat* d, bool deterministic) {
-    useTiles(d, deterministic);
-    return d->tiles ? EXIT_SUCCESS : buildTiles(d, deterministic ? &TILES_DETERMINISTIC : nullptr);
+// that form / the layout of that launch mode, built if it is missing; null: the build failed
+TileFormat* ensureTiles(DevMat* d, bool deterministic) {
+    if (!d->tiles[deterministic]) (void)buildTiles(d, deterministic ? &TILES_DETERMINISTIC : nullptr);
+    return d->tiles[deterministic];
 }
-int ensureStripes(DevMat* d, bool ownerLayout) {
-    useStripes(d, ownerLayout);
-    return d->stripes ? EXIT_SUCCESS : buildStripes(d, ownerLayout ? &STRIPES_OWNER : nullptr);
+StripeFormat* ensureStripes(DevMat* d, int mode) {
+    const int layout = stripesLayout(mode);
+    if (!d->stripes[layout]) (void)buildStripes(d, layout ? &STRIPES_OWNER : nullptr);
+    return d->stripes[layout];
 }
 bool nonEmptyCsr(const DevMat* d, const char* who) {
     if (d->kind == Kind::CSR && d->M && d->NZ) return true;
@@ -105,12 +106,13 @@ int tilesForm(Ctx cx, spmat* dMat, double* dX, double* dY, bool det, const char*
     DevMat* d = csrOf(dMat, dX, dY, who);
     if (!d) return EXIT_FAILURE;
     if (d->M == 0 || d->NZ == 0) return nothingToLaunch(cx, d, dY);         // nothing to slice: y = 0
-    if (ensureTiles(d, det)) return EXIT_FAILURE;
+    const TileFormat* t = ensureTiles(d, det);
+    if (!t) return EXIT_FAILURE;
     uint32_t bins = 0, rowsPerBin = 0;
-    tilesShape(d, &bins, &rowsPerBin);
-    const uint32_t p2t = tilesPhase2Threads(d);
+    tilesShape(t, &bins, &rowsPerBin);
+    const uint32_t p2t = tilesPhase2Threads(t);
     Launch L(cx, grid2d((uint64_t)((bins + 7) / 8) * 8, p2t), dim3(p2t));   // phase 2's shape (phase 1: one workgroup per slice piece)
-    if (enqueueTiles(d, dX, dY, cx.stream)) { ERR("%s: launch failed", who); return EXIT_FAILURE; }
+    if (enqueueTiles(d, t, dX, dY, cx.stream)) { ERR("%s: launch failed", who); return EXIT_FAILURE; }
     return L.finish(who);
 }
 // mode: 0 arrival order, 1 owner wavefronts (its own layout), 2 ordered tickets (the layout of mode 0)
@@ -118,10 +120,11 @@ int stripesForm(Ctx cx, spmat* dMat, double* dX, double* dY, int mode, const cha
     DevMat* d = csrOf(dMat, dX, dY, who);
     if (!d) return EXIT_FAILURE;
     if (d->M == 0 || d->NZ == 0) return nothingToLaunch(cx, d, dY);         // nothing to sweep: y = 0
-    if (ensureStripes(d, mode == 1)) return EXIT_FAILURE;
+    const StripeFormat* f = ensureStripes(d, mode);
+    if (!f) return EXIT_FAILURE;
     Launch L(cx, dim3(1), dim3(1));
     dim3 grid, block;
-    if (enqueueStripes(d, dX, dY, cx.stream, mode, &grid, &block)) { ERR("%s: launch failed", who); return EXIT_FAILURE; }
+    if (enqueueStripes(f, dX, dY, cx.stream, mode, &grid, &block)) { ERR("%s: launch failed", who); return EXIT_FAILURE; }
     L.shape(grid, block);                            // the persistent grid that ran: min(bins, CUs) workgroups of 256 threads
     return L.finish(who);
 }
@@ -260,7 +263,7 @@ int hipSpMVStripesCSR(spmat* dMat, double* dX, CONFIG, double* dY) {
 
 int spmvHipBuildTiles(spmat* dMat) {
     DevMat* d = csrOf(dMat, "spmvHipBuildTiles");
-    return d ? ensureTiles(d, d->tilesPref) : EXIT_FAILURE;
+    return d && ensureTiles(d, d->tilesPref) ? EXIT_SUCCESS : EXIT_FAILURE;
 }
 size_t spmvHipTilesBytes(spmat* dMat) { DevMat* d = descOf(dMat, "spmvHipTilesBytes"); return d ? tilesBytes(d) : 0; }
 
@@ -282,7 +285,7 @@ int hipSpMVRowsSELL(spmat* dMat, double* dX, CONFIG, double* dY) {
 
 int spmvHipBuildStripes(spmat* dMat) {
     DevMat* d = csrOf(dMat, "spmvHipBuildStripes");
-    return d ? ensureStripes(d, d->stripesPref == 1) : EXIT_FAILURE;
+    return d && ensureStripes(d, d->stripesPref) ? EXIT_SUCCESS : EXIT_FAILURE;
 }
 int spmvHipBuildStripesOpt(spmat* dMat, const spmvStripesOpts* opts) {
     DevMat* d = descOf(dMat, "spmvHipBuildStripesOpt");
@@ -294,8 +297,7 @@ size_t spmvHipStripesBytes(spmat* dMat) { DevMat* d = descOf(dMat, "spmvHipStrip
 int spmvHipStripesInfo(spmat* dMat, spmvStripesInfo* info) {
     DevMat* d = descOf(dMat, "spmvHipStripesInfo");
     if (!d || !info) return EXIT_FAILURE;
-    useStripes(d, d->stripesPref == 1);
-    stripesInfo(d, info);
+    stripesInfo(d->stripes[stripesLayout(d->stripesPref)], info);
     if (info->nBins && d->stripesPref == 2) info->deterministic = 2;     // the shared-stream layout, launched in ticket order
     return EXIT_SUCCESS;
 }
@@ -309,17 +311,18 @@ int spmvHipStripesShape(spmat* dMat, unsigned* nBins, unsigned* rowsPerBin, int*
     return EXIT_SUCCESS;
 }
 
-// the two-phase format the explicit entry points below work on: the preferred form, built if missing
-static DevMat* tilesReady(spmat* dMat, const char* who) {
+// the two-phase format the explicit entry points below work on: the preferred form, built if missing (null: refused or failed)
+struct TilesOf { DevMat* d; TileFormat* t; };
+static TilesOf tilesReady(spmat* dMat, const char* who) {
     DevMat* d = descOf(dMat, who);
-    return d && nonEmptyCsr(d, who) && !ensureTiles(d, d->tilesPref) ? d : nullptr;
+    return {d, d && nonEmptyCsr(d, who) ? ensureTiles(d, d->tilesPref) : nullptr};
 }
 
 int spmvHipTilesShape(spmat* dMat, unsigned* nBins, unsigned* rowsPerBin) {
-    DevMat* d = tilesReady(dMat, "spmvHipTilesShape");
-    if (!d || !nBins || !rowsPerBin) return EXIT_FAILURE;
+    const TileFormat* t = tilesReady(dMat, "spmvHipTilesShape").t;
+    if (!t || !nBins || !rowsPerBin) return EXIT_FAILURE;
     uint32_t b = 0, r = 0;
-    tilesShape(d, &b, &r);
+    tilesShape(t, &b, &r);
     *nBins = b; *rowsPerBin = r;
     return EXIT_SUCCESS;
 }
@@ -334,47 +337,46 @@ int spmvHipBuildTilesOpt(spmat* dMat, const spmvTilesOpts* opts) {
 int spmvHipTilesInfo(spmat* dMat, spmvTilesInfo* info) {
     DevMat* d = descOf(dMat, "spmvHipTilesInfo");
     if (!d || !info) return EXIT_FAILURE;
-    useTiles(d, d->tilesPref);
-    tilesInfo(d, info);
+    tilesInfo(d->tiles[d->tilesPref], info);
     return EXIT_SUCCESS;
 }
 
 int spmvHipTilesBinRow(spmat* dMat, unsigned bin, ulong* firstRow) {
-    DevMat* d = tilesReady(dMat, "spmvHipTilesBinRow");
-    if (!d || !firstRow) return EXIT_FAILURE;
-    *firstRow = tilesBinRow(d, bin);
+    const auto [d, t] = tilesReady(dMat, "spmvHipTilesBinRow");
+    if (!t || !firstRow) return EXIT_FAILURE;
+    *firstRow = tilesBinRow(d, t, bin);
     return EXIT_SUCCESS;
 }
 
 int hipSpMVTilesExpand(spmat* dMat, double* dX) {
     const Ctx cx = libraryCtx();
-    DevMat* d = tilesReady(dMat, "hipSpMVTilesExpand");
-    if (!d) return EXIT_FAILURE;
+    const auto [d, t] = tilesReady(dMat, "hipSpMVTilesExpand");
+    if (!t) return EXIT_FAILURE;
     if (!dX) { ERR("hipSpMVTilesExpand: x is NULL"); return EXIT_FAILURE; }
     Launch L(cx, dim3(1), dim3(1024));
-    if (enqueueTilesExpand(d, dX, cx.stream)) { ERR("hipSpMVTilesExpand: launch failed"); return EXIT_FAILURE; }
+    if (enqueueTilesExpand(d, t, dX, cx.stream)) { ERR("hipSpMVTilesExpand: launch failed"); return EXIT_FAILURE; }
     return L.finish("hipSpMVTilesExpand");
 }
 
 int hipSpMVTilesReduce(spmat* dMat, unsigned binBegin, unsigned binEnd, double* dY, int nExtra, double* const* dExtra) {
     const Ctx cx = libraryCtx();
-    DevMat* d = tilesReady(dMat, "hipSpMVTilesReduce");
-    if (!d) return EXIT_FAILURE;
+    const auto [d, t] = tilesReady(dMat, "hipSpMVTilesReduce");
+    if (!t) return EXIT_FAILURE;
     uint32_t b = 0, r = 0;
-    tilesShape(d, &b, &r);
+    tilesShape(t, &b, &r);
     if (binBegin > binEnd || binEnd > b || nExtra < 0 || nExtra > SPMV_MAX_PEERS || (nExtra && !dExtra) || !dY) {
         ERR("hipSpMVTilesReduce: bins [%u,%u) of %u, %d extra destinations: invalid", binBegin, binEnd, b, nExtra);
         return EXIT_FAILURE;
     }
     Launch L(cx, dim3(binEnd - binBegin ? binEnd - binBegin : 1), dim3(1024));
-    if (enqueueTilesReduce(d, binBegin, binEnd, dY, nExtra, dExtra, cx.stream)) { ERR("hipSpMVTilesReduce: launch failed"); return EXIT_FAILURE; }
+    if (enqueueTilesReduce(d, t, binBegin, binEnd, dY, nExtra, dExtra, cx.stream)) { ERR("hipSpMVTilesReduce: launch failed"); return EXIT_FAILURE; }
     return L.finish("hipSpMVTilesReduce");
 }
 
 int hipSpMVTilesReducePush(spmat* dMat, double* dY, int nExtra, double* const* dExtra) {
     const Ctx cx = libraryCtx();
-    DevMat* d = tilesReady(dMat, "hipSpMVTilesReducePush");
-    if (!d) return EXIT_FAILURE;
+    const auto [d, t] = tilesReady(dMat, "hipSpMVTilesReducePush");
+    if (!t) return EXIT_FAILURE;
     if (nExtra < 1 || nExtra > SPMV_MAX_PEERS || !dExtra || !dY) { ERR("hipSpMVTilesReducePush: %d destinations: invalid", nExtra); return EXIT_FAILURE; }
     if (!g_pushSide) {
         int lo = 0, hi = 0;
@@ -384,9 +386,9 @@ int hipSpMVTilesReducePush(spmat* dMat, double* dY, int nExtra, double* const* d
         HIP_TRY(hipEventCreateWithFlags(&g_pushJoin, hipEventDisableTiming));
     }
     uint32_t b = 0, r = 0;
-    tilesShape(d, &b, &r);
+    tilesShape(t, &b, &r);
     Launch L(cx, dim3(b), dim3(1024));
-    if (enqueueTilesReducePush(d, dY, nExtra, dExtra, cx.stream, g_pushSide, g_pushFork, g_pushJoin)) { ERR("hipSpMVTilesReducePush: launch failed"); return EXIT_FAILURE; }
+    if (enqueueTilesReducePush(d, t, dY, nExtra, dExtra, cx.stream, g_pushSide, g_pushFork, g_pushJoin)) { ERR("hipSpMVTilesReducePush: launch failed"); return EXIT_FAILURE; }
     g_pushPending = true;
     if (cx.sync && spmvHipTilesPushJoin()) return EXIT_FAILURE;         // synchronous mode: everything delivered on return
     return L.finish("hipSpMVTilesReducePush");
@@ -400,7 +402,7 @@ int spmvHipTilesPushJoin(void) {
     return EXIT_SUCCESS;
 }
 
-int spmvHipTilesPushFailed(spmat* dMat) { DevMat* d = descOf(dMat, "spmvHipTilesPushFailed"); return d ? tilesPushFailed(d) : 1; }
+int spmvHipTilesPushFailed(spmat* dMat) { DevMat* d = descOf(dMat, "spmvHipTilesPushFailed"); return d ? tilesPushFailed(d->tiles[d->tilesPref]) : 1; }
 
 int hipSpMVRowsELLNNTransposed(spmat* dMat, double* dX, CONFIG cfg, double* dY) {
     const Ctx cx = libraryCtx();

@@ -71,12 +71,9 @@ int autoSelect(Ctx cx, spmat* dMat, DevMat* d, int serial, double* dX, double* d
         if (unsorted || probeLdsOrder(cx.stream) != 1) { d->autoPick[serial] = 0; return EXIT_SUCCESS; }
     }
     // which formats exist already (the caller's, or the other selection's winner): those are never freed here
-    useTiles(d, serial != 0);
-    const bool hadTiles = d->tiles != nullptr;
-    useStripes(d, false);
-    const bool hadShared = d->stripes != nullptr;    // shared-stream layout: arrival order and ordered tickets
-    useStripes(d, true);
-    const bool hadOwner = d->stripes != nullptr;     // per-wavefront sub-streams
+    TileFormat*& tiles = d->tiles[serial != 0];
+    StripeFormat *&shared = d->stripes[0], *&owner = d->stripes[1];    // one stream per bin (arrival order, ordered tickets) / sub-streams
+    const bool hadTiles = tiles != nullptr, hadShared = shared != nullptr, hadOwner = owner != nullptr;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     HIP_TRY(hipEventCreate(&e0));
     if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); ERR("hipSpMVAutoCSR: event creation failed"); return EXIT_FAILURE; }
@@ -124,13 +121,10 @@ int autoSelect(Ctx cx, spmat* dMat, DevMat* d, int serial, double* dX, double* d
     if (best < 0) { ERR("hipSpMVAutoCSR: no candidate kernel ran"); return EXIT_FAILURE; }
     // the losers' private copies of the matrix (12 B/nnz each) go; formats that existed before stay.  The shared-stream
     // stripes layout serves candidate 2 of the reduction-order selection and candidate 3 of the serial-order one.
-    useTiles(d, serial != 0);
-    if (best != 1 && d->tiles && !hadTiles) { freeTiles(d->tiles); d->tiles = nullptr; }
     const bool keepShared = serial ? best == 3 : best == 2, keepOwner = serial && best == 2;
-    useStripes(d, false);
-    if (!keepShared && d->stripes && !hadShared) { freeStripes(d->stripes); d->stripes = nullptr; }
-    useStripes(d, true);
-    if (!keepOwner && d->stripes && !hadOwner) { freeStripes(d->stripes); d->stripes = nullptr; }
+    if (best != 1 && !hadTiles) { freeTiles(tiles); tiles = nullptr; }
+    if (!keepShared && !hadShared) { freeStripes(shared); shared = nullptr; }
+    if (!keepOwner && !hadOwner) { freeStripes(owner); owner = nullptr; }
     d->autoPick[serial] = best;
     return EXIT_SUCCESS;
 }

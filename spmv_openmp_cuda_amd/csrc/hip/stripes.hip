@@ -436,6 +436,42 @@ void launchSpmv(const StripeFormat* f, const double* x, double* y, hipStream_t s
                            f->unitValue, f->val, f->cr, f->lrowW, f->stepBase, x, y, f->R, f->spread);
 }
 
+// The key sort that the build and the value map share, on `stream`: every entry's key {sub-stream, column} with its CSR
+// position and row (sb_keys_kernel), the stable radix sort of (key, position) -- a stable sort's permutation depends on the
+// keys alone, so both callers see the same order --, and where every sub-stream starts in that order (sb_bounds_kernel).
+// The caller allocates the buffers: nnz entries each, dStart B * subs + 1.  Returns the step that failed, or null.
+struct StripeSort {
+    TempBuf keys, keysOut, idx, perm, rowOf, sortTmp;
+    unsigned colBits = 1;                            // width of the column part of a key
+    const uint64_t* skeys = nullptr;                 // the sorted keys ...
+    const uint32_t* sperm = nullptr;                 // ... and the CSR position of each
+};
+const char* sortStripeKeys(const DevMat* d, const StripeFormat* f, StripeSort& s, uint64_t* dStart, hipStream_t stream) {
+    const uint64_t nnz = d->NZ, M = d->M, nGroups = (uint64_t)f->B * f->subs;
+    unsigned groupBits = 1;
+    while (s.colBits < 32 && (1ull << s.colBits) < d->N) ++s.colBits;
+    while ((1ull << groupBits) < nGroups) ++groupBits;
+    withIrp(d, [&](auto irp) {
+        hipLaunchKernelGGL((sb_keys_kernel<IrpT<decltype(irp)>>), grid2d((M + 3) / 4, 256), dim3(256), 0, stream, M, irp, d->JA,
+                           f->binRow, f->B, f->subs, s.colBits, s.keys.as<uint64_t>(), s.idx.as<uint32_t>(), s.rowOf.as<uint32_t>());
+    });
+    if (hipGetLastError() != hipSuccess) return "key kernel";
+    // (rocPRIM's double-buffer interface: the sort ping-pongs between the two pairs of buffers given here instead of
+    // allocating a third full-size pair inside its temporary storage)
+    rocprim::double_buffer<uint64_t> dKeys(s.keys.as<uint64_t>(), s.keysOut.as<uint64_t>());
+    rocprim::double_buffer<uint32_t> dIdx(s.idx.as<uint32_t>(), s.perm.as<uint32_t>());
+    size_t tmpBytes = 0;
+    if (rocprim::radix_sort_pairs(nullptr, tmpBytes, dKeys, dIdx, (size_t)nnz, 0, s.colBits + groupBits, stream) != hipSuccess ||
+        s.sortTmp.alloc(tmpBytes))
+        return "sort workspace";
+    if (rocprim::radix_sort_pairs(s.sortTmp.p, tmpBytes, dKeys, dIdx, (size_t)nnz, 0, s.colBits + groupBits, stream) != hipSuccess)
+        return "sort";
+    s.skeys = dKeys.current();
+    s.sperm = dIdx.current();
+    hipLaunchKernelGGL(sb_bounds_kernel, grid2d((nnz + 255) / 256, 256), dim3(256), 0, stream, nnz, s.colBits, s.skeys, nGroups, dStart);
+    return hipGetLastError() != hipSuccess ? "bounds kernel" : nullptr;
+}
+
 }  // namespace
 
 void freeStripes(StripeFormat* f) {
@@ -445,18 +481,10 @@ void freeStripes(StripeFormat* f) {
     delete f;
 }
 
-size_t stripesBytes(const DevMat* d) { return (d->stripes ? d->stripes->bytes : 0) + (d->stripesAlt ? d->stripesAlt->bytes : 0); }
+size_t stripesBytes(const DevMat* d) { return (d->stripes[0] ? d->stripes[0]->bytes : 0) + (d->stripes[1] ? d->stripes[1]->bytes : 0); }
 
-// a handle holds at most one format of each form; the requested one becomes the active slot
-void useStripes(DevMat* d, bool deterministic) {
-    if (d->stripes && d->stripes->det == deterministic) return;
-    if (d->stripes || d->stripesAlt) std::swap(d->stripes, d->stripesAlt);
-    if (d->stripes && d->stripes->det != deterministic) std::swap(d->stripes, d->stripesAlt);
-}
-
-void stripesInfo(const DevMat* d, spmvStripesInfo* out) {
+void stripesInfo(const StripeFormat* f, spmvStripesInfo* out) {
     memset(out, 0, sizeof *out);
-    const StripeFormat* f = d->stripes;
     if (!f) return;
     out->nBins = f->B; out->rowsPerBin = f->R; out->grid = f->grid; out->spread = f->spread;
     out->wide = f->wide ? 1 : 0; out->deterministic = f->det ? 1 : 0; out->buildMs = f->buildMs; out->bytes = f->bytes;
@@ -464,14 +492,14 @@ void stripesInfo(const DevMat* d, spmvStripesInfo* out) {
 }
 
 // `opts` == nullptr: automatic format of the shared-stream layout, kept if one exists.  Explicit options: the existing format of
-// that LAYOUT is replaced (the other layout, if the handle holds it, is untouched).  Layouts: opts->deterministic == 1 -> per-
-// wavefront sub-streams; 0 and 2 -> one stream per bin (run in arrival order or in ticket order: a choice of the launch).
+// that LAYOUT, stripesLayout(opts->deterministic), is replaced (the other layout, if the handle holds it, is untouched): per-
+// wavefront sub-streams, or one stream per bin (run in arrival order or in ticket order: a choice of the launch).
 int buildStripes(DevMat* d, const spmvStripesOpts* opts) {
-    useStripes(d, opts && opts->deterministic == 1);
-    if (d->stripes && !opts) return EXIT_SUCCESS;
+    StripeFormat*& slot = d->stripes[opts ? stripesLayout(opts->deterministic) : 0];
+    if (slot && !opts) return EXIT_SUCCESS;
     if (d->kind != Kind::CSR) return EXIT_FAILURE;
     const spmvStripesOpts o = opts ? *opts : spmvStripesOpts{0, 0, -1, -1, 0};
-    const uint64_t nnz = d->NZ, M = d->M, N = d->N;
+    const uint64_t nnz = d->NZ, M = d->M;
     if (nnz >= IRP32_LIMIT || nnz == 0 || M == 0) {
         fprintf(stderr, "libspmvhip: stripes: nnz = %lu unsupported (needs 0 < nnz < 2^32)\n", (unsigned long)nnz);
         return EXIT_FAILURE;
@@ -484,7 +512,7 @@ int buildStripes(DevMat* d, const spmvStripesOpts* opts) {
         fprintf(stderr, "libspmvhip: stripes: options out of range (rowsPerBin 0..%u, grid 0..%d, spread -1..1024, deterministic 0..2)\n", SB_R_MAX, cusDev);
         return EXIT_FAILURE;
     }
-    if (d->stripes) { freeStripes(d->stripes); d->stripes = nullptr; }
+    if (slot) { freeStripes(slot); slot = nullptr; }
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     SB_TRY(hipEventCreate(&ev0));
     SB_TRY(hipEventCreate(&ev1));
@@ -510,7 +538,7 @@ int buildStripes(DevMat* d, const spmvStripesOpts* opts) {
 
     StripeFormat* f = new StripeFormat;
     f->opts = o;
-    f->det = o.deterministic == 1;
+    f->det = stripesLayout(o.deterministic) != 0;
     f->unit = d->unit; f->unitValue = d->unitValue;
     f->subs = f->det ? SB_WAVES : 1;
     f->B = B; f->R = R; f->nnz = nnz;
@@ -518,39 +546,17 @@ int buildStripes(DevMat* d, const spmvStripesOpts* opts) {
     f->spread = o.spread >= 0 ? (uint32_t)o.spread : SB_SPREAD;          // (used by the arrival-order launch only)
     const uint64_t nGroups = (uint64_t)B * f->subs;
     auto fail = [&](const char* what) { (void)hipGetLastError(); fprintf(stderr, "libspmvhip: stripes: %s failed\n", what); freeStripes(f); return EXIT_FAILURE; };
-    TempBuf keys, keysOut, idx, perm, rowOf, sortTmp, dStart, dOverflow;
+    StripeSort srt;
+    TempBuf dStart, dOverflow;
     if (hipMalloc(&f->binRow, ((size_t)B + 1) * 4) || hipMalloc(&f->subStep, ((size_t)nGroups + 1) * 4) || dStart.alloc(((size_t)nGroups + 1) * 8) ||
         dOverflow.alloc(4))
         return fail("table allocation");
     if (hipMemcpy(f->binRow, binRow.data(), ((size_t)B + 1) * 4, hipMemcpyHostToDevice)) return fail("table upload");
-    if (keys.alloc(nnz * 8) || keysOut.alloc(nnz * 8) || idx.alloc(nnz * 4) || perm.alloc(nnz * 4) || rowOf.alloc(nnz * 4))
+    if (srt.keys.alloc(nnz * 8) || srt.keysOut.alloc(nnz * 8) || srt.idx.alloc(nnz * 4) || srt.perm.alloc(nnz * 4) || srt.rowOf.alloc(nnz * 4))
         return fail("temporary allocation");
 
-    unsigned colBits = 1, groupBits = 1;
-    while (colBits < 32 && (1ull << colBits) < N) ++colBits;
-    while ((1ull << groupBits) < nGroups) ++groupBits;
-    withIrp(d, [&](auto irp) {
-        hipLaunchKernelGGL((sb_keys_kernel<IrpT<decltype(irp)>>), grid2d((M + 3) / 4, 256), dim3(256), 0, nullptr, M, irp, d->JA,
-                           f->binRow, B, f->subs, colBits, keys.as<uint64_t>(), idx.as<uint32_t>(), rowOf.as<uint32_t>());
-    });
-    if (hipGetLastError() != hipSuccess) return fail("key kernel");
-    // (rocPRIM's double-buffer interface: the sort ping-pongs between the two pairs of buffers given here instead of
-    // allocating a third full-size pair inside its temporary storage)
-    rocprim::double_buffer<uint64_t> dKeys(keys.as<uint64_t>(), keysOut.as<uint64_t>());
-    rocprim::double_buffer<uint32_t> dIdx(idx.as<uint32_t>(), perm.as<uint32_t>());
-    size_t tmpBytes = 0;
-    if (rocprim::radix_sort_pairs(nullptr, tmpBytes, dKeys, dIdx, (size_t)nnz, 0, colBits + groupBits, (hipStream_t) nullptr) != hipSuccess ||
-        sortTmp.alloc(tmpBytes))
-        return fail("sort workspace");
-    if (rocprim::radix_sort_pairs(sortTmp.p, tmpBytes, dKeys, dIdx, (size_t)nnz, 0, colBits + groupBits, (hipStream_t) nullptr) != hipSuccess)
-        return fail("sort");
-    const uint64_t* const skeys = dKeys.current();
-    const uint32_t* const sperm = dIdx.current();
-
     // where every sub-stream starts in the sorted order -> its first step (each sub-stream is padded to whole steps)
-    hipLaunchKernelGGL(sb_bounds_kernel, grid2d((nnz + 255) / 256, 256), dim3(256), 0, nullptr, nnz, colBits, skeys, nGroups,
-                       dStart.as<uint64_t>());
-    if (hipGetLastError() != hipSuccess) return fail("bounds kernel");
+    if (const char* step = sortStripeKeys(d, f, srt, dStart.as<uint64_t>(), nullptr)) return fail(step);
     std::vector<uint64_t> start(nGroups + 1);
     if (hipMemcpy(start.data(), dStart.p, (nGroups + 1) * 8, hipMemcpyDeviceToHost) != hipSuccess) return fail("bounds download");
     std::vector<uint32_t> subStep(nGroups + 1);
@@ -566,7 +572,7 @@ int buildStripes(DevMat* d, const spmvStripesOpts* opts) {
 
     bool wide = o.wide > 0;
     for (int attempt = 0; attempt < 2; ++attempt) {
-        if (fillFormat(f, wide, nnz, colBits, skeys, sperm, rowOf.as<uint32_t>(), d->AS,
+        if (fillFormat(f, wide, nnz, srt.colBits, srt.skeys, srt.sperm, srt.rowOf.as<uint32_t>(), d->AS,
                        dStart.as<uint64_t>(), dOverflow.as<uint32_t>()))
             return fail("scatter");
         uint32_t ovf = 0;
@@ -589,7 +595,7 @@ int buildStripes(DevMat* d, const spmvStripesOpts* opts) {
     float ms = 0;
     (void)hipEventElapsedTime(&ms, ev0, ev1);
     f->buildMs = ms;
-    d->stripes = f;
+    slot = f;
     return EXIT_SUCCESS;
 }
 
@@ -598,12 +604,11 @@ spmvStripesOpts stripesOptions(const StripeFormat* f) { return f->opts; }
 void stripesSetUnit(StripeFormat* f, bool unit, double value) { f->unit = unit; f->unitValue = value; }
 
 // New values (same pattern) into the format's value array (it must have one: a format built for a unit matrix has none and
-// is rebuilt by the caller).  The value map is built here at the format's first refresh: the build's key sort again (the
-// same keys and bits; a stable sort's permutation depends on the keys alone), its sub-stream starts, and every sorted
-// position's cell -- the padding cells keep VMAP_NONE.
+// is rebuilt by the caller).  The value map is built here at the format's first refresh: the build's key sort again, its
+// sub-stream starts, and every sorted position's cell -- the padding cells keep VMAP_NONE.
 int stripesRefreshValues(DevMat* d, StripeFormat* f, hipStream_t stream, double* mapMs, int* mapsBuilt) {
     if (!f->val) return EXIT_FAILURE;
-    const uint64_t cells = f->nSteps * SB_STEP, nnz = f->nnz, M = d->M;
+    const uint64_t cells = f->nSteps * SB_STEP, nnz = f->nnz;
     if (!f->vmap) {
         const auto t0 = std::chrono::steady_clock::now();
         auto fail = [&](const char* what) {
@@ -616,30 +621,14 @@ int stripesRefreshValues(DevMat* d, StripeFormat* f, hipStream_t stream, double*
         };
         if (hipMalloc(&f->vmap, std::max<uint64_t>(cells, 1) * 4) != hipSuccess) { f->vmap = nullptr; return fail("allocation"); }
         const uint64_t nGroups = (uint64_t)f->B * f->subs;
-        TempBuf keys, keysOut, idx, perm, rowOf, sortTmp, dStart;
-        if (keys.alloc(nnz * 8) || keysOut.alloc(nnz * 8) || idx.alloc(nnz * 4) || perm.alloc(nnz * 4) || rowOf.alloc(nnz * 4) ||
+        StripeSort srt;
+        TempBuf dStart;
+        if (srt.keys.alloc(nnz * 8) || srt.keysOut.alloc(nnz * 8) || srt.idx.alloc(nnz * 4) || srt.perm.alloc(nnz * 4) || srt.rowOf.alloc(nnz * 4) ||
             dStart.alloc((nGroups + 1) * 8))
             return fail("temporary allocation (28 B per entry)");
         if (cells) hipLaunchKernelGGL(sb_fill32_kernel, grid2d((cells + 255) / 256, 256), dim3(256), 0, stream, f->vmap, cells, VMAP_NONE);
-        unsigned colBits = 1, groupBits = 1;         // (as buildStripes chose them)
-        while (colBits < 32 && (1ull << colBits) < d->N) ++colBits;
-        while ((1ull << groupBits) < nGroups) ++groupBits;
-        withIrp(d, [&](auto irp) {
-            hipLaunchKernelGGL((sb_keys_kernel<IrpT<decltype(irp)>>), grid2d((M + 3) / 4, 256), dim3(256), 0, stream, M, irp, d->JA,
-                               f->binRow, f->B, f->subs, colBits, keys.as<uint64_t>(), idx.as<uint32_t>(), rowOf.as<uint32_t>());
-        });
-        if (hipGetLastError() != hipSuccess) return fail("key kernel");
-        rocprim::double_buffer<uint64_t> dKeys(keys.as<uint64_t>(), keysOut.as<uint64_t>());
-        rocprim::double_buffer<uint32_t> dIdx(idx.as<uint32_t>(), perm.as<uint32_t>());
-        size_t tmpBytes = 0;
-        if (rocprim::radix_sort_pairs(nullptr, tmpBytes, dKeys, dIdx, (size_t)nnz, 0, colBits + groupBits, stream) != hipSuccess ||
-            sortTmp.alloc(tmpBytes))
-            return fail("sort workspace");
-        if (rocprim::radix_sort_pairs(sortTmp.p, tmpBytes, dKeys, dIdx, (size_t)nnz, 0, colBits + groupBits, stream) != hipSuccess)
-            return fail("sort");
-        hipLaunchKernelGGL(sb_bounds_kernel, grid2d((nnz + 255) / 256, 256), dim3(256), 0, stream, nnz, colBits, dKeys.current(), nGroups,
-                           dStart.as<uint64_t>());
-        hipLaunchKernelGGL(sb_map_kernel, grid2d((nnz + 255) / 256, 256), dim3(256), 0, stream, nnz, colBits, dKeys.current(), dIdx.current(),
+        if (const char* step = sortStripeKeys(d, f, srt, dStart.as<uint64_t>(), stream)) return fail(step);
+        hipLaunchKernelGGL(sb_map_kernel, grid2d((nnz + 255) / 256, 256), dim3(256), 0, stream, nnz, srt.colBits, srt.skeys, srt.sperm,
                            dStart.as<uint64_t>(), f->subStep, f->vmap);
         if (hipGetLastError() != hipSuccess) return fail("map kernels");
         if (hipStreamSynchronize(stream) != hipSuccess) return fail("synchronise");      // (the temporaries go)
@@ -655,10 +644,9 @@ int stripesRefreshValues(DevMat* d, StripeFormat* f, hipStream_t stream, double*
 // the same microsecond and every one of them waits for the fabric; a few microseconds apart the first to arrive pays and
 // the rest hit: the first quarter of a bin 113 instead of 123 us and the bin 404 instead of 417 us on c3.  Past ~2 % the
 // tail of the pack outlives its lines in the 4 MiB L2 (c3: 6.4 % 1.05 ms, 100 % 2.96 ms; profiles/r02_stripes_spread.log).
-// mode 0: arrival order; 1: owner wavefronts (needs the sub-stream layout); 2: ordered tickets (needs the shared-stream layout)
-int enqueueStripes(DevMat* d, const double* x, double* y, hipStream_t stream, int mode, dim3* grid, dim3* block) {
-    const StripeFormat* f = d->stripes;
-    if (!f || mode < 0 || mode > 2 || (mode == 1) != f->det) return EXIT_FAILURE;
+// mode 0: arrival order; 1: owner wavefronts; 2: ordered tickets -- on the format of the layout stripesLayout(mode)
+int enqueueStripes(const StripeFormat* f, const double* x, double* y, hipStream_t stream, int mode, dim3* grid, dim3* block) {
+    if (!f || mode < 0 || mode > 2) return EXIT_FAILURE;
     if (grid) *grid = dim3(f->grid);
     if (block) *block = dim3(SB_THREADS);
     if (f->wide) { if (mode == 2) launchSpmv<true, 2>(f, x, y, stream); else if (mode == 1) launchSpmv<true, 1>(f, x, y, stream); else launchSpmv<true, 0>(f, x, y, stream); }

@@ -796,9 +796,8 @@ void freeTilesWorkspace() {
     (void)hipSetDevice(keep);
 }
 
-uint64_t tilesBinRow(const DevMat* d, uint32_t bin) {
-    if (!d->tiles) return 0;
-    const TileFormat* t = d->tiles;
+uint64_t tilesBinRow(const DevMat* d, const TileFormat* t, uint32_t bin) {
+    if (!t) return 0;
     return bin >= t->apiBins() ? d->M : std::min<uint64_t>(d->M, t->apiMap().row0(bin));
 }
 
@@ -809,20 +808,12 @@ void freeTiles(TileFormat* t) {
     delete t;
 }
 
-// a handle holds at most one format of each form; the requested one becomes the active slot
-void useTiles(DevMat* d, bool deterministic) {
-    if (d->tiles && d->tiles->det == deterministic) return;
-    if (d->tiles || d->tilesAlt) std::swap(d->tiles, d->tilesAlt);
-    if (d->tiles && d->tiles->det != deterministic) std::swap(d->tiles, d->tilesAlt);      // (only one slot was filled, with the other form)
-}
+// ---- the build, stage by stage (buildTiles below is their sequence)
+static int buildFailed(const char* what) { (void)hipGetLastError(); fprintf(stderr, "libspmvhip: tiles: %s failed\n", what); return EXIT_FAILURE; }
 
-// `opts` == nullptr: automatic arrival-order format, kept if one exists.  Explicit options: the existing format of that FORM
-// is replaced (the other form, if the handle holds it, is untouched).
-int buildTiles(DevMat* d, const spmvTilesOpts* opts) {
-    useTiles(d, opts && opts->deterministic);
-    if (d->tiles && !opts) return EXIT_SUCCESS;
+// what the options and the matrix must satisfy
+static int checkTilesBuild(const DevMat* d, const spmvTilesOpts& o) {
     if (d->kind != Kind::CSR) return EXIT_FAILURE;
-    const spmvTilesOpts o = opts ? *opts : spmvTilesOpts{0, 0, -1, 0, 0};
     if (o.deterministic && o.taper) { fprintf(stderr, "libspmvhip: tiles: the deterministic form has no tapered bins\n"); return EXIT_FAILURE; }
     if (o.rowsPerBin != 0 && (o.rowsPerBin < 64 || o.rowsPerBin > PB_R_MAX)) {
         fprintf(stderr, "libspmvhip: tiles: rowsPerBin = %u is not 0 (automatic) or 64..%u\n", o.rowsPerBin, PB_R_MAX);
@@ -832,26 +823,15 @@ int buildTiles(DevMat* d, const spmvTilesOpts* opts) {
         fprintf(stderr, "libspmvhip: tiles: chunk = %u is not 0 (automatic) or 4096..2^24\n", o.chunk);
         return EXIT_FAILURE;
     }
-    if (d->tiles) { freeTiles(d->tiles); d->tiles = nullptr; }
-    const uint64_t nnz = d->NZ, M = d->M, N = d->N;
+    const uint64_t nnz = d->NZ, N = d->N;
     if (nnz >= IRP32_LIMIT || nnz == 0) { fprintf(stderr, "libspmvhip: tiles: nnz = %lu unsupported (needs 0 < nnz < 2^32)\n", (unsigned long)nnz); return EXIT_FAILURE; }
-    const uint64_t S64 = (N + PB_C - 1) / PB_C;
-    if (S64 > 65535) { fprintf(stderr, "libspmvhip: tiles: %lu columns exceed 65535 slices\n", (unsigned long)N); return EXIT_FAILURE; }
-    TileFormat* t = new TileFormat;
-    struct Guard { TileFormat*& t; ~Guard() { if (t) freeTiles(t); } } guard{t};      // every early return frees the half-built format
-    {   // one workgroup per CU of the CURRENT device in phases 1 and 2: rounds are counted in units of its CU count
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
-            t->cus = (uint32_t)cus;
-    }
-    const uint32_t PB_CUS = t->cus;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    PB_TRY(hipEventCreate(&ev0));
-    PB_TRY(hipEventCreate(&ev1));
-    struct EvGuard { hipEvent_t a, b; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } evGuard{ev0, ev1};
-    PB_TRY(hipEventRecord(ev0, nullptr));
-    t->opts = o;
-    t->S = (uint32_t)S64;
+    if ((N + PB_C - 1) / PB_C > 65535) { fprintf(stderr, "libspmvhip: tiles: %lu columns exceed 65535 slices\n", (unsigned long)N); return EXIT_FAILURE; }
+    return EXIT_SUCCESS;
+}
+
+// Rows -> bins for M rows on a device of PB_CUS compute units (host arithmetic only): the map, its highest bin, the bin count
+struct TileGeometry { BinMap bins; uint32_t R = 0, B = 0; };
+static TileGeometry planTileBins(uint64_t M, uint32_t PB_CUS, const spmvTilesOpts& o) {
     // Rows per bin R (any value up to PB_R_MAX, not a power of two): phase 2 runs ONE workgroup per CU at a time (its
     // bin of y fills the LDS), so the bins are processed in rounds of PB_CUS and a partly filled last round leaves
     // most of the chip idle -- 610 bins of 16 Ki rows on 256 CUs are 2.4 rounds of work in the time of ~2.7.  For
@@ -859,68 +839,74 @@ int buildTiles(DevMat* d, const spmvTilesOpts* opts) {
     // (10 M rows: 512 bins of 19 532 rows = exactly two rounds, and 20 % longer tiles); beyond that the tail is
     // negligible and R is simply the largest that fits.  Measured (this box, ms): see DESIGN.md section 7.
     uint32_t R = PB_R_MAX;
-    {
-        const uint64_t bMin = (M + PB_R_MAX - 1) / PB_R_MAX;
-        if (bMin <= 8 * PB_CUS) {
-            const uint64_t b = (bMin + PB_CUS - 1) / PB_CUS * PB_CUS;
-            R = (uint32_t)std::max<uint64_t>(64, ((M + b - 1) / b + 63) / 64 * 64);
-            R = std::min(R, PB_R_MAX);
-        }
+    const uint64_t bMin = (M + PB_R_MAX - 1) / PB_R_MAX;
+    if (bMin <= 8 * PB_CUS) {
+        const uint64_t b = (bMin + PB_CUS - 1) / PB_CUS * PB_CUS;
+        R = (uint32_t)std::max<uint64_t>(64, ((M + b - 1) / b + 63) / 64 * 64);
+        R = std::min(R, PB_R_MAX);
     }
     if (o.rowsPerBin) R = o.rowsPerBin;
-    t->bins = BinMap{};
-    t->bins.c = R;
-    const bool taper = o.taper != 0;
-    if (taper && M >= (uint64_t)4 * PB_CUS * 1024) {
+    TileGeometry g;
+    g.bins.c = R;
+    if (o.taper != 0 && M >= (uint64_t)4 * PB_CUS * 1024) {
         // one round of quarter-height bins first and last, full-height bins (a multiple of PB_CUS of them) between
         const uint32_t low = std::max<uint32_t>(64, (R / 4 + 63) / 64 * 64);
         const uint64_t mid = M - (uint64_t)2 * PB_CUS * low;
         const uint64_t nb = ((mid + PB_R_MAX - 1) / PB_R_MAX + PB_CUS - 1) / PB_CUS * PB_CUS;
         const uint32_t high = std::min<uint32_t>(PB_R_MAX, (uint32_t)(((mid + nb - 1) / nb + 63) / 64 * 64));
         const uint64_t n2 = (mid + high - 1) / high;                       // the last full-height bin may reach into the low zone:
-        t->bins.n1 = PB_CUS; t->bins.a = low;                              // zone 3 simply starts where zone 2 ends
-        t->bins.n2 = (uint32_t)n2; t->bins.b = high;
-        t->bins.c = low;
-        t->bins.z1 = (uint64_t)PB_CUS * low;
-        t->bins.z2 = t->bins.z1 + n2 * high;
-        if (t->bins.z2 >= M) { t->bins.n2 = (uint32_t)((M - t->bins.z1 + high - 1) / high); t->bins.z2 = t->bins.z1 + (uint64_t)t->bins.n2 * high; }
+        g.bins.n1 = PB_CUS; g.bins.a = low;                                // zone 3 simply starts where zone 2 ends
+        g.bins.n2 = (uint32_t)n2; g.bins.b = high;
+        g.bins.c = low;
+        g.bins.z1 = (uint64_t)PB_CUS * low;
+        g.bins.z2 = g.bins.z1 + n2 * high;
+        if (g.bins.z2 >= M) { g.bins.n2 = (uint32_t)((M - g.bins.z1 + high - 1) / high); g.bins.z2 = g.bins.z1 + (uint64_t)g.bins.n2 * high; }
     }
-    t->det = o.deterministic != 0;
-    if (t->det) {                                    // sub-bins: a quarter of the bin each, PD_WAVES of them share a workgroup's LDS
+    if (o.deterministic) {                           // sub-bins: a quarter of the bin each, PD_WAVES of them share a workgroup's LDS
         const uint32_t Rs = o.rowsPerBin ? (o.rowsPerBin + PD_WAVES - 1) / PD_WAVES
                                          : std::min<uint32_t>(PB_R_MAX / PD_WAVES / 64 * 64, std::max<uint32_t>(64, ((R + PD_WAVES - 1) / PD_WAVES + 63) / 64 * 64));
-        t->bins = BinMap{};
-        t->bins.c = std::max<uint32_t>(1, std::min<uint32_t>(Rs, PB_R_MAX / PD_WAVES));
+        g.bins = BinMap{};
+        g.bins.c = std::max<uint32_t>(1, std::min<uint32_t>(Rs, PB_R_MAX / PD_WAVES));
     }
-    t->R = t->bins.maxHeight();
-    t->B = t->bins.z2 >= M ? t->bins.n1 + t->bins.n2 : t->bins.n1 + t->bins.n2 + (uint32_t)((M - t->bins.z2 + t->bins.c - 1) / t->bins.c);
-    t->nnz = nnz;
-    const uint64_t nTiles = (uint64_t)t->S * t->B;
-    if (nTiles >= (1ull << 32) - 2) { fprintf(stderr, "libspmvhip: tiles: too many tiles\n"); return EXIT_FAILURE; }
+    g.R = g.bins.maxHeight();
+    g.B = g.bins.z2 >= M ? g.bins.n1 + g.bins.n2 : g.bins.n1 + g.bins.n2 + (uint32_t)((M - g.bins.z2 + g.bins.c - 1) / g.bins.c);
+    return g;
+}
 
+// the temporaries that live until the build returns, and the sorted entries in them
+struct TileBuildTemps {
+    TempBuf payB, sortTmp, tileStart;
+    const uint32_t* skeys = nullptr;                 // slice ids in slice-major order (in the product workspace)
+    const PbPay* spay = nullptr;                     // ... and what travelled with them (in payB)
+};
+
+// Device stage 1: the format's arrays are allocated and the entries sorted into slice-major order; tileStart[] then holds
+// where every tile (slice, bin) starts.
+static int sortIntoSlices(const DevMat* d, TileFormat* t, TileBuildTemps& tmp) {
+    const uint64_t nnz = d->NZ, M = d->M, nTiles = (uint64_t)t->S * t->B;
+    TempBuf &payB = tmp.payB, &sortTmp = tmp.sortTmp, &tileStart = tmp.tileStart;
     // Memory.  The format's three arrays are ONE slab (val | lcol | lrow, each part 256-B aligned), and while the format is
     // built that slab and the device's product workspace (8 B/nnz, needed anyway) serve as sort buffers: the unsorted
     // payload lives in the slab, the two key buffers in the workspace, and the only temporary of size is the second payload
     // buffer, 12 B/nnz (round 2 allocated 36 B/nnz of its own plus, inside rocPRIM's pointer interface, 18 more: on c5
     // ~90 GB mapped for a 19 GB format, a second of hipMalloc).  rocPRIM's double-buffer interface sorts between the two
     // pairs of buffers without further full-size storage.
-    TempBuf payB, sortTmp, tileStart;
-    auto fail = [&](const char* what) { (void)hipGetLastError(); fprintf(stderr, "libspmvhip: tiles: %s failed\n", what); return EXIT_FAILURE; };
     PB_TRY(hipDeviceSynchronize());                  // nothing may still use the product workspace of this device
     prodIdle();
     const auto allocT0 = std::chrono::steady_clock::now();
     const size_t offLcol = (nnz * 8 + 255) / 256 * 256, offLrow = offLcol + (nnz * 2 + 255) / 256 * 256;
     const size_t slabBytes = std::max<size_t>(offLrow + nnz * 2, nnz * sizeof(PbPay));
     if (hipMalloc(&t->slab, slabBytes) || payB.alloc(nnz * sizeof(PbPay)) || tileStart.alloc((nTiles + 2) * 4))
-        return fail("format / temporary allocation (12 B per entry of temporaries while the format is built)");
+        return buildFailed("format / temporary allocation (12 B per entry of temporaries while the format is built)");
     double* const prodBuf = prodWorkspace(nnz, true);
     if (!prodBuf || hipMalloc(&t->binPos, ((size_t)t->B + 1) * 4) || hipMalloc(&t->waveTile, (size_t)t->B * (t->det ? 1 : P2_WAVES) * 4) ||
         (t->det && hipMalloc(&t->pidx, nnz * 4)))
-        return fail("format allocation");
+        return buildFailed("format allocation");
     t->allocMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - allocT0).count();
     t->val  = static_cast<double*>(t->slab);
     t->lcol = reinterpret_cast<uint16_t*>(static_cast<char*>(t->slab) + offLcol);
     t->lrow = reinterpret_cast<uint16_t*>(static_cast<char*>(t->slab) + offLrow);
+    t->bytes = slabBytes + (t->det ? nnz * 4 : 0) + ((size_t)t->B + 1) * 4 + (size_t)t->B * (t->det ? 1 : P2_WAVES) * 4;
     t->tempBytes = nnz * sizeof(PbPay) + (nTiles + 2) * 4;
     uint32_t* const keysA = reinterpret_cast<uint32_t*>(prodBuf);
     PbPay* const payA = static_cast<PbPay*>(t->slab);
@@ -934,93 +920,129 @@ int buildTiles(DevMat* d, const spmvTilesOpts* opts) {
     rocprim::double_buffer<PbPay>    dPay(payA, payB.as<PbPay>());
     size_t tmpBytes = 0;
     PB_TRY(rocprim::radix_sort_pairs(nullptr, tmpBytes, dKeys, dPay, (size_t)nnz, PB_CBITS, PB_CBITS + bits, (hipStream_t) nullptr));
-    if (sortTmp.alloc(tmpBytes)) return fail("sort workspace");
+    if (sortTmp.alloc(tmpBytes)) return buildFailed("sort workspace");
     t->tempBytes += tmpBytes;
     PB_TRY(rocprim::radix_sort_pairs(sortTmp.p, tmpBytes, dKeys, dPay, (size_t)nnz, PB_CBITS, PB_CBITS + bits, (hipStream_t) nullptr));
-    const uint32_t* const skeys = dKeys.current();
+    tmp.skeys = dKeys.current();
     if (dPay.current() == payA)                      // the sorted payload must not sit where val / lcol / lrow are about to be written
         PB_TRY(hipMemcpyAsync(payB.p, payA, nnz * sizeof(PbPay), hipMemcpyDeviceToDevice, nullptr));
-    const PbPay* const spay = payB.as<PbPay>();
+    tmp.spay = payB.as<PbPay>();
 
-    hipLaunchKernelGGL(pb_bounds_kernel, grid2d((nnz + 255) / 256, 256), dim3(256), 0, nullptr, nnz, spay, skeys, t->B, t->bins, nTiles,
+    hipLaunchKernelGGL(pb_bounds_kernel, grid2d((nnz + 255) / 256, 256), dim3(256), 0, nullptr, nnz, tmp.spay, tmp.skeys, t->B, t->bins, nTiles,
                        tileStart.as<uint32_t>());
     PB_TRY(hipGetLastError());
-    // bin-major view: tile lengths (bin-major) -> exclusive scans give every tile's bin-major start and its index
-    // in the list of non-empty tiles
-    {
-        TempBuf lens, flags, bmStart, listIdx, scanTmp, binTile;
-        if (lens.alloc(nTiles * 4) || flags.alloc(nTiles * 4) || bmStart.alloc(nTiles * 4) || listIdx.alloc(nTiles * 4) ||
-            binTile.alloc(((size_t)t->B + 1) * 4))
-            return fail("tile-list workspace");
-        t->tempBytes += nTiles * 16;
-        hipLaunchKernelGGL(pb_lens_kernel, grid2d((nTiles + 255) / 256, 256), dim3(256), 0, nullptr, t->S, t->B,
-                           tileStart.as<uint32_t>(), lens.as<uint32_t>(), flags.as<uint32_t>());
-        size_t scanBytes = 0;
-        PB_TRY(rocprim::exclusive_scan(nullptr, scanBytes, lens.as<uint32_t>(), bmStart.as<uint32_t>(), 0u, (size_t)nTiles,
-                                       rocprim::plus<uint32_t>(), (hipStream_t) nullptr));
-        if (scanTmp.alloc(scanBytes)) return fail("scan workspace");
-        PB_TRY(rocprim::exclusive_scan(scanTmp.p, scanBytes, lens.as<uint32_t>(), bmStart.as<uint32_t>(), 0u, (size_t)nTiles,
-                                       rocprim::plus<uint32_t>(), (hipStream_t) nullptr));
-        PB_TRY(rocprim::exclusive_scan(scanTmp.p, scanBytes, flags.as<uint32_t>(), listIdx.as<uint32_t>(), 0u, (size_t)nTiles,
-                                       rocprim::plus<uint32_t>(), (hipStream_t) nullptr));
-        uint32_t lastIdx = 0, lastFlag = 0;
-        PB_TRY(hipMemcpy(&lastIdx, listIdx.as<uint32_t>() + nTiles - 1, 4, hipMemcpyDeviceToHost));
-        PB_TRY(hipMemcpy(&lastFlag, flags.as<uint32_t>() + nTiles - 1, 4, hipMemcpyDeviceToHost));
-        t->nList = lastIdx + lastFlag;
-        if (t->nList >= P2_RUNS_FLAG) return fail("tile list (more than 2^31 non-empty tiles)");
-        if (hipMalloc(&t->tl, ((size_t)t->nList + TL_PAD) * sizeof(uint2))) return fail("tile-list allocation");
-        hipLaunchKernelGGL(pb_fill_kernel, dim3(1), dim3(256), 0, nullptr, reinterpret_cast<uint32_t*>(t->tl + t->nList), 2 * TL_PAD, 0xFFFFFFFFu);
-        hipLaunchKernelGGL(pb_list_kernel, grid2d((nTiles + 255) / 256, 256), dim3(256), 0, nullptr, t->S, t->B, nnz,
-                           tileStart.as<uint32_t>(), lens.as<uint32_t>(), bmStart.as<uint32_t>(), listIdx.as<uint32_t>(), t->nList,
-                           t->tl, t->binPos, binTile.as<uint32_t>());
-        hipLaunchKernelGGL(pb_place_kernel, grid2d((nnz + 255) / 256, 256), dim3(256), 0, nullptr, nnz, spay, skeys, t->S, t->B, t->bins,
-                           tileStart.as<uint32_t>(), bmStart.as<uint32_t>(), t->val, t->lcol, t->lrow, t->pidx);
-        if (t->det) {
-            // every wavefront walks a whole sub-bin: its cursor starts at the sub-bin's first tile
-            PB_TRY(hipMemcpyAsync(t->waveTile, binTile.p, (size_t)t->B * 4, hipMemcpyDeviceToDevice, nullptr));
-        } else {
-            TempBuf dupCount;
-            if (dupCount.alloc((size_t)t->B * P2_WAVES * 4)) return fail("run-count workspace");
-            PB_TRY(hipMemsetAsync(dupCount.p, 0, (size_t)t->B * P2_WAVES * 4, nullptr));
-            hipLaunchKernelGGL(pb_dupcount_kernel, grid2d((nnz + 255) / 256, 256), dim3(256), 0, nullptr, t->B, nnz, t->binPos, t->lrow,
-                               dupCount.as<uint32_t>());
-            hipLaunchKernelGGL(pb_wavetile_kernel, grid2d(((uint64_t)t->B * P2_WAVES + 255) / 256, 256), dim3(256), 0, nullptr, t->B,
-                               t->binPos, binTile.as<uint32_t>(), t->tl, dupCount.as<uint32_t>(), t->waveTile);
-            PB_TRY(hipGetLastError());
-            PB_TRY(hipDeviceSynchronize());          // dupCount goes out of scope
-        }
-        PB_TRY(hipGetLastError());
-        PB_TRY(hipDeviceSynchronize());
-    }
-    t->bytes = slabBytes + (t->det ? nnz * 4 : 0) + ((size_t)t->nList + TL_PAD) * 8 + ((size_t)t->B + 1) * 4 + (size_t)t->B * (t->det ? 1 : P2_WAVES) * 4;
+    return EXIT_SUCCESS;
+}
 
-    // phase-1 work list from the slice boundaries (tileStart[s*B])
-    std::vector<uint32_t> sliceStart(t->S + 1);
-    PB_TRY(hipMemcpy2D(sliceStart.data(), 4, tileStart.as<uint32_t>(), (size_t)t->B * 4, 4, t->S + 1, hipMemcpyDeviceToHost));
-    std::vector<uint3> work;
-    // Work item size.  One workgroup per CU at a time (the x slice fills the LDS), so the items are processed in rounds
-    // of PB_CUS and what counts is (a) items of 50-100 k entries (c5: 524 k 8.88 ms, 262 k 8.82, 131 k 8.76, 65-98 k
-    // 8.74) and (b) how full the LAST round is: on c3 (610 slices of 328 k entries) 3 pieces per slice = 7.15 rounds ran
-    // at 1.081 ms, 2 / 4 / 6 pieces (4.77 / 9.53 / 14.3 rounds) at 1.041-1.046 ms.  The extra x-slice fills of more pieces
-    // are nearly free (issued under the running stream, served by L2 / Infinity Cache).  Pieces per slice: within the
-    // 50-100 k window, minimise  0.35 * idle share of the last round + a tenth of the relative fill traffic.
-    uint32_t chunk = PB_CHUNK;
-    if (o.chunk) chunk = o.chunk;
-    else {
-        uint64_t nonEmpty = 0;
-        for (uint32_t s = 0; s < t->S; ++s) nonEmpty += sliceStart[s + 1] > sliceStart[s];
-        const double avgLen = nonEmpty ? (double)nnz / (double)nonEmpty : 1.0;
-        double bestCost = 1e300;
-        const uint32_t pLo = (uint32_t)std::max(1.0, std::ceil(avgLen / 100000.0));
-        const uint32_t pHi = (uint32_t)std::max((double)pLo, std::ceil(avgLen / 50000.0));
-        for (uint32_t p = pLo; p <= std::min<uint32_t>(pHi, 1024); ++p) {
-            const double rounds = (double)nonEmpty * p / PB_CUS;
-            const double waste = (std::ceil(rounds) - rounds) / rounds;
-            const double cost = 0.35 * waste + 0.1 * p * (PB_C * 8.0) / (avgLen * 18.0);
-            if (cost < bestCost) { bestCost = cost; chunk = (uint32_t)std::min(16777216.0, std::ceil(avgLen / p * 1.02) + 64); }
-        }
+// Device stage 2, the bin-major view: tile lengths (bin-major) -> exclusive scans give every tile's bin-major start and its
+// index in the list of non-empty tiles; then the tile list, the placement of every entry and where phase 2's wavefronts start
+static int placeTiles(TileFormat* t, TileBuildTemps& tmp) {
+    const uint64_t nnz = t->nnz, nTiles = (uint64_t)t->S * t->B;
+    TempBuf& tileStart = tmp.tileStart;
+    TempBuf lens, flags, bmStart, listIdx, scanTmp, binTile;
+    if (lens.alloc(nTiles * 4) || flags.alloc(nTiles * 4) || bmStart.alloc(nTiles * 4) || listIdx.alloc(nTiles * 4) ||
+        binTile.alloc(((size_t)t->B + 1) * 4))
+        return buildFailed("tile-list workspace");
+    t->tempBytes += nTiles * 16;
+    hipLaunchKernelGGL(pb_lens_kernel, grid2d((nTiles + 255) / 256, 256), dim3(256), 0, nullptr, t->S, t->B,
+                       tileStart.as<uint32_t>(), lens.as<uint32_t>(), flags.as<uint32_t>());
+    size_t scanBytes = 0;
+    PB_TRY(rocprim::exclusive_scan(nullptr, scanBytes, lens.as<uint32_t>(), bmStart.as<uint32_t>(), 0u, (size_t)nTiles,
+                                   rocprim::plus<uint32_t>(), (hipStream_t) nullptr));
+    if (scanTmp.alloc(scanBytes)) return buildFailed("scan workspace");
+    PB_TRY(rocprim::exclusive_scan(scanTmp.p, scanBytes, lens.as<uint32_t>(), bmStart.as<uint32_t>(), 0u, (size_t)nTiles,
+                                   rocprim::plus<uint32_t>(), (hipStream_t) nullptr));
+    PB_TRY(rocprim::exclusive_scan(scanTmp.p, scanBytes, flags.as<uint32_t>(), listIdx.as<uint32_t>(), 0u, (size_t)nTiles,
+                                   rocprim::plus<uint32_t>(), (hipStream_t) nullptr));
+    uint32_t lastIdx = 0, lastFlag = 0;
+    PB_TRY(hipMemcpy(&lastIdx, listIdx.as<uint32_t>() + nTiles - 1, 4, hipMemcpyDeviceToHost));
+    PB_TRY(hipMemcpy(&lastFlag, flags.as<uint32_t>() + nTiles - 1, 4, hipMemcpyDeviceToHost));
+    t->nList = lastIdx + lastFlag;
+    if (t->nList >= P2_RUNS_FLAG) return buildFailed("tile list (more than 2^31 non-empty tiles)");
+    if (hipMalloc(&t->tl, ((size_t)t->nList + TL_PAD) * sizeof(uint2))) return buildFailed("tile-list allocation");
+    t->bytes += ((size_t)t->nList + TL_PAD) * 8;
+    hipLaunchKernelGGL(pb_fill_kernel, dim3(1), dim3(256), 0, nullptr, reinterpret_cast<uint32_t*>(t->tl + t->nList), 2 * TL_PAD, 0xFFFFFFFFu);
+    hipLaunchKernelGGL(pb_list_kernel, grid2d((nTiles + 255) / 256, 256), dim3(256), 0, nullptr, t->S, t->B, nnz,
+                       tileStart.as<uint32_t>(), lens.as<uint32_t>(), bmStart.as<uint32_t>(), listIdx.as<uint32_t>(), t->nList,
+                       t->tl, t->binPos, binTile.as<uint32_t>());
+    hipLaunchKernelGGL(pb_place_kernel, grid2d((nnz + 255) / 256, 256), dim3(256), 0, nullptr, nnz, tmp.spay, tmp.skeys, t->S, t->B, t->bins,
+                       tileStart.as<uint32_t>(), bmStart.as<uint32_t>(), t->val, t->lcol, t->lrow, t->pidx);
+    if (t->det) {
+        // every wavefront walks a whole sub-bin: its cursor starts at the sub-bin's first tile
+        PB_TRY(hipMemcpyAsync(t->waveTile, binTile.p, (size_t)t->B * 4, hipMemcpyDeviceToDevice, nullptr));
+    } else {
+        TempBuf dupCount;
+        if (dupCount.alloc((size_t)t->B * P2_WAVES * 4)) return buildFailed("run-count workspace");
+        PB_TRY(hipMemsetAsync(dupCount.p, 0, (size_t)t->B * P2_WAVES * 4, nullptr));
+        hipLaunchKernelGGL(pb_dupcount_kernel, grid2d((nnz + 255) / 256, 256), dim3(256), 0, nullptr, t->B, nnz, t->binPos, t->lrow,
+                           dupCount.as<uint32_t>());
+        hipLaunchKernelGGL(pb_wavetile_kernel, grid2d(((uint64_t)t->B * P2_WAVES + 255) / 256, 256), dim3(256), 0, nullptr, t->B,
+                           t->binPos, binTile.as<uint32_t>(), t->tl, dupCount.as<uint32_t>(), t->waveTile);
+        PB_TRY(hipGetLastError());
+        PB_TRY(hipDeviceSynchronize());              // dupCount goes out of scope
     }
-    for (uint32_t s = 0; s < t->S; ++s) {
+    PB_TRY(hipGetLastError());
+    PB_TRY(hipDeviceSynchronize());
+    return EXIT_SUCCESS;
+}
+
+// Work item size of phase 1 when the caller names none.  One workgroup per CU at a time (the x slice fills the LDS), so the
+// items are processed in rounds of PB_CUS and what counts is (a) items of 50-100 k entries (c5: 524 k 8.88 ms, 262 k 8.82,
+// 131 k 8.76, 65-98 k 8.74) and (b) how full the LAST round is: on c3 (610 slices of 328 k entries) 3 pieces per slice =
+// 7.15 rounds ran at 1.081 ms, 2 / 4 / 6 pieces (4.77 / 9.53 / 14.3 rounds) at 1.041-1.046 ms.  The extra x-slice fills of
+// more pieces are nearly free (issued under the running stream, served by L2 / Infinity Cache).  Pieces per slice: within
+// the 50-100 k window, minimise  0.35 * idle share of the last round + a tenth of the relative fill traffic.
+static uint32_t phase1Chunk(const std::vector<uint32_t>& sliceStart, uint64_t nnz, uint32_t PB_CUS) {
+    uint32_t chunk = PB_CHUNK;
+    uint64_t nonEmpty = 0;
+    for (size_t s = 0; s + 1 < sliceStart.size(); ++s) nonEmpty += sliceStart[s + 1] > sliceStart[s];
+    const double avgLen = nonEmpty ? (double)nnz / (double)nonEmpty : 1.0;
+    double bestCost = 1e300;
+    const uint32_t pLo = (uint32_t)std::max(1.0, std::ceil(avgLen / 100000.0));
+    const uint32_t pHi = (uint32_t)std::max((double)pLo, std::ceil(avgLen / 50000.0));
+    for (uint32_t p = pLo; p <= std::min<uint32_t>(pHi, 1024); ++p) {
+        const double rounds = (double)nonEmpty * p / PB_CUS;
+        const double waste = (std::ceil(rounds) - rounds) / rounds;
+        const double cost = 0.35 * waste + 0.1 * p * (PB_C * 8.0) / (avgLen * 18.0);
+        if (cost < bestCost) { bestCost = cost; chunk = (uint32_t)std::min(16777216.0, std::ceil(avgLen / p * 1.02) + 64); }
+    }
+    return chunk;
+}
+
+// Order of the work items: workgroups are dealt round-robin to the 8 XCDs, each with its own L2, and the pieces of
+// one slice all stage the same 128 KiB of x.  Listed one after the other they land on different XCDs and every
+// piece fetches the slice from the fabric (c5, 4 pieces: 2.6 GB of fills per SpMV); listed 8 apart -- groups of 8
+// slices, piece k of each, then piece k+1 of each -- they land on ONE XCD at almost the same time and all but the
+// first fill hit its L2.
+static std::vector<uint3> interleaveSlices(const std::vector<uint3>& work) {
+    std::vector<uint3> ordered;
+    ordered.reserve(work.size());
+    size_t i = 0;
+    while (i < work.size()) {
+        // the next (up to) 8 slices and their pieces
+        size_t first[9];
+        int ns = 0;
+        size_t j = i;
+        while (j < work.size() && ns < 8) {
+            first[ns++] = j;
+            const uint32_t sl = work[j].x;
+            while (j < work.size() && work[j].x == sl) ++j;
+        }
+        first[ns] = j;
+        size_t maxPieces = 0;
+        for (int k = 0; k < ns; ++k) maxPieces = std::max(maxPieces, first[k + 1] - first[k]);
+        for (size_t pc = 0; pc < maxPieces; ++pc)
+            for (int k = 0; k < ns; ++k)
+                if (first[k] + pc < first[k + 1]) ordered.push_back(work[first[k] + pc]);
+        i = j;
+    }
+    return ordered;
+}
+
+// the phase-1 work list {slice, begin, end} from the slice boundaries, in launch order (host arithmetic only)
+static std::vector<uint3> planPhase1Work(const std::vector<uint32_t>& sliceStart, uint32_t chunk) {
+    std::vector<uint3> work;
+    for (uint32_t s = 0; s + 1 < sliceStart.size(); ++s) {
         // a slice is cut into equal pieces of at most PB_CHUNK entries (a fixed chunk size + remainder left one
         // short, fill-dominated work item per slice); inner boundaries fall on multiples of 64 entries so that
         // only a slice's first work item has a scalar head
@@ -1035,62 +1057,74 @@ int buildTiles(DevMat* d, const spmvTilesOpts* opts) {
             b = e;
         }
     }
-    // Order of the work items: workgroups are dealt round-robin to the 8 XCDs, each with its own L2, and the pieces of
-    // one slice all stage the same 128 KiB of x.  Listed one after the other they land on different XCDs and every
-    // piece fetches the slice from the fabric (c5, 4 pieces: 2.6 GB of fills per SpMV); listed 8 apart -- groups of 8
-    // slices, piece k of each, then piece k+1 of each -- they land on ONE XCD at almost the same time and all but the
-    // first fill hit its L2.
-    {
-        std::vector<uint3> ordered;
-        ordered.reserve(work.size());
-        size_t i = 0;
-        while (i < work.size()) {
-            // the next (up to) 8 slices and their pieces
-            size_t first[9];
-            int ns = 0;
-            size_t j = i;
-            while (j < work.size() && ns < 8) {
-                first[ns++] = j;
-                const uint32_t sl = work[j].x;
-                while (j < work.size() && work[j].x == sl) ++j;
-            }
-            first[ns] = j;
-            size_t maxPieces = 0;
-            for (int k = 0; k < ns; ++k) maxPieces = std::max(maxPieces, first[k + 1] - first[k]);
-            for (size_t pc = 0; pc < maxPieces; ++pc)
-                for (int k = 0; k < ns; ++k)
-                    if (first[k] + pc < first[k + 1]) ordered.push_back(work[first[k] + pc]);
-            i = j;
-        }
-        work.swap(ordered);
+    return interleaveSlices(work);
+}
+
+// the LDS of the launches (set at every build: the attribute belongs to the current device, and a process may drive several)
+static int setTilesKernelAttributes() {
+    const struct { const void* kernel; int ldsBytes; } attrs[] = {
+        {(const void*)pb_expand_kernel<true, false>, PB_C * 8}, {(const void*)pb_expand_kernel<false, false>, PB_C * 8},
+        {(const void*)pb_expand_kernel<true, true>, PB_C * 8},  {(const void*)pb_expand_kernel<false, true>, PB_C * 8},
+        {(const void*)pb_reduce_kernel<0>, PB_R_MAX * 8},       {(const void*)pb_reduce_kernel<1>, PB_R_MAX * 8},
+        {(const void*)pb_reduce_kernel<2>, PB_R_MAX * 8},       {(const void*)pb_reduce_det_kernel<0>, PB_R_MAX * 8},
+        {(const void*)pb_reduce_det_kernel<1>, PB_R_MAX * 8},   {(const void*)pb_reduce_det_kernel<2>, PB_R_MAX * 8}};
+    for (const auto& a : attrs) PB_TRY(hipFuncSetAttribute(a.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, a.ldsBytes));
+    return EXIT_SUCCESS;
+}
+
+// `opts` == nullptr: automatic arrival-order format, kept if one exists.  Explicit options: the existing format of the form they
+// name is replaced (the other form, if the handle holds it, is untouched).
+int buildTiles(DevMat* d, const spmvTilesOpts* opts) {
+    const spmvTilesOpts o = opts ? *opts : spmvTilesOpts{0, 0, -1, 0, 0};
+    TileFormat*& slot = d->tiles[o.deterministic != 0];
+    if (slot && !opts) return EXIT_SUCCESS;
+    if (checkTilesBuild(d, o)) return EXIT_FAILURE;
+    if (slot) { freeTiles(slot); slot = nullptr; }
+    const uint64_t nnz = d->NZ;
+    TileFormat* t = new TileFormat;
+    struct Guard { TileFormat*& t; ~Guard() { if (t) freeTiles(t); } } guard{t};      // every early return frees the half-built format
+    {   // one workgroup per CU of the CURRENT device in phases 1 and 2: rounds are counted in units of its CU count
+        int dev = 0, cus = 0;
+        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
+            t->cus = (uint32_t)cus;
     }
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    PB_TRY(hipEventCreate(&ev0));
+    PB_TRY(hipEventCreate(&ev1));
+    struct EvGuard { hipEvent_t a, b; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } evGuard{ev0, ev1};
+    PB_TRY(hipEventRecord(ev0, nullptr));
+    const TileGeometry g = planTileBins(d->M, t->cus, o);
+    t->opts = o;
+    t->S = (uint32_t)((d->N + PB_C - 1) / PB_C);
+    t->bins = g.bins; t->R = g.R; t->B = g.B;
+    t->det = o.deterministic != 0;
+    t->nnz = nnz;
+    if ((uint64_t)t->S * t->B >= (1ull << 32) - 2) { fprintf(stderr, "libspmvhip: tiles: too many tiles\n"); return EXIT_FAILURE; }
+
+    TileBuildTemps tmp;
+    if (sortIntoSlices(d, t, tmp) || placeTiles(t, tmp)) return EXIT_FAILURE;
+
+    // phase-1 work list from the slice boundaries (tileStart[s*B])
+    std::vector<uint32_t> sliceStart(t->S + 1);
+    PB_TRY(hipMemcpy2D(sliceStart.data(), 4, tmp.tileStart.as<uint32_t>(), (size_t)t->B * 4, 4, t->S + 1, hipMemcpyDeviceToHost));
+    t->chunk = o.chunk ? o.chunk : phase1Chunk(sliceStart, nnz, t->cus);
+    const std::vector<uint3> work = planPhase1Work(sliceStart, t->chunk);
     t->nWork = (uint32_t)work.size();
     PB_TRY(hipMalloc(&t->work, std::max<size_t>(work.size(), 1) * sizeof(uint3)));
     PB_TRY(hipMemcpy(t->work, work.data(), work.size() * sizeof(uint3), hipMemcpyHostToDevice));
     PB_TRY(hipDeviceSynchronize());
 
-    // (set at every build: the attribute belongs to the current device, and a process may drive several)
-    PB_TRY(hipFuncSetAttribute((const void*)pb_expand_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, PB_C * 8));
-    PB_TRY(hipFuncSetAttribute((const void*)pb_expand_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, PB_C * 8));
-    PB_TRY(hipFuncSetAttribute((const void*)pb_expand_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, PB_C * 8));
-    PB_TRY(hipFuncSetAttribute((const void*)pb_expand_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, PB_C * 8));
-    PB_TRY(hipFuncSetAttribute((const void*)pb_reduce_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, PB_R_MAX * 8));
-    PB_TRY(hipFuncSetAttribute((const void*)pb_reduce_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, PB_R_MAX * 8));
-    PB_TRY(hipFuncSetAttribute((const void*)pb_reduce_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, PB_R_MAX * 8));
-    PB_TRY(hipFuncSetAttribute((const void*)pb_reduce_det_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, PB_R_MAX * 8));
-    PB_TRY(hipFuncSetAttribute((const void*)pb_reduce_det_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, PB_R_MAX * 8));
-    PB_TRY(hipFuncSetAttribute((const void*)pb_reduce_det_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, PB_R_MAX * 8));
+    if (setTilesKernelAttributes()) return EXIT_FAILURE;
     // products that fit the Infinity Cache (with room for x and the streams) are stored with the default policy so
     // that phase 2 finds them there; larger streams bypass it (microbench_mall.hip: resident 7.0 vs 5.8 TB/s with
     // non-temporal stores; non-resident 4.9 vs 5.1-5.4)
     t->ntStore = o.ntStore >= 0 ? o.ntStore != 0 : nnz * 8 > PB_RESIDENT_BYTES;
-    t->chunk = chunk;
     PB_TRY(hipEventRecord(ev1, nullptr));
     PB_TRY(hipEventSynchronize(ev1));
     float ms = 0;
     (void)hipEventElapsedTime(&ms, ev0, ev1);
     t->buildMs = ms;
-    d->tiles = t;
+    slot = t;
     t = nullptr;                                    // the guard lets go
     return EXIT_SUCCESS;
 }
@@ -1110,7 +1144,7 @@ int tilesRefreshValues(DevMat* d, TileFormat* t, hipStream_t stream, double* map
             return EXIT_FAILURE;
         };
         if (hipMalloc(&t->vmap, std::max<uint64_t>(nnz, 1) * 4) != hipSuccess) { t->vmap = nullptr; return fail("allocation"); }
-        const TileFormat* other = d->tiles == t ? d->tilesAlt : d->tiles;
+        const TileFormat* other = d->tiles[!t->det];
         if (other && other->vmap) {                  // both forms share the slice-major order (the same sort): the same map
             if (hipMemcpyAsync(t->vmap, other->vmap, nnz * 4, hipMemcpyDeviceToDevice, stream) != hipSuccess) return fail("copy");
         } else {
@@ -1137,27 +1171,25 @@ int tilesRefreshValues(DevMat* d, TileFormat* t, hipStream_t stream, double* map
     return enqueueScatterValues(t->val, t->vmap, nnz, d->AS, stream);
 }
 
-size_t tilesBytes(const DevMat* d) { return (d->tiles ? d->tiles->bytes : 0) + (d->tilesAlt ? d->tilesAlt->bytes : 0); }
+size_t tilesBytes(const DevMat* d) { return (d->tiles[0] ? d->tiles[0]->bytes : 0) + (d->tiles[1] ? d->tiles[1]->bytes : 0); }
 
-void tilesInfo(const DevMat* d, spmvTilesInfo* out) {
+void tilesInfo(const TileFormat* t, spmvTilesInfo* out) {
     memset(out, 0, sizeof *out);
-    const TileFormat* t = d->tiles;
     if (!t) return;
     out->nBins = t->apiBins(); out->rowsPerBin = t->apiRows(); out->nSlices = t->S; out->taper = t->bins.n1 != 0; out->ntStore = t->ntStore;
     out->chunk = t->chunk; out->buildMs = t->buildMs; out->bytes = t->bytes; out->allocMs = t->allocMs;
     out->tempBytes = t->tempBytes; out->deterministic = t->det ? 1 : 0;
 }
 
-uint32_t tilesPhase2Threads(const DevMat* d) { return d->tiles && d->tiles->det ? (uint32_t)PD_THREADS : (uint32_t)PB_THREADS; }
+uint32_t tilesPhase2Threads(const TileFormat* t) { return t && t->det ? (uint32_t)PD_THREADS : (uint32_t)PB_THREADS; }
 
-void tilesShape(const DevMat* d, uint32_t* bins, uint32_t* rowsPerBin) {
-    *bins = d->tiles ? d->tiles->apiBins() : 0;
-    *rowsPerBin = d->tiles ? d->tiles->apiRows() : 0;
+void tilesShape(const TileFormat* t, uint32_t* bins, uint32_t* rowsPerBin) {
+    *bins = t ? t->apiBins() : 0;
+    *rowsPerBin = t ? t->apiRows() : 0;
 }
 
 // phase 1 on `stream`: products of the whole matrix into the format's workspace
-int enqueueTilesExpand(DevMat* d, const double* x, hipStream_t stream) {
-    TileFormat* t = d->tiles;
+int enqueueTilesExpand(const DevMat* d, const TileFormat* t, const double* x, hipStream_t stream) {
     if (!t) return EXIT_FAILURE;
     double* prod = prodWorkspace(t->nnz, true);      // grows (after a device synchronise) only if it was released meanwhile
     if (!prod || prodHandover(stream)) return EXIT_FAILURE;
@@ -1173,8 +1205,8 @@ int enqueueTilesExpand(DevMat* d, const double* x, hipStream_t stream) {
 
 // phase 2 on `stream` for the bins [binBegin, binEnd): rows [binBegin * R, min(binEnd * R, M)) of y, stored to y and
 // to the nExtra further destinations (same row indexing)
-int enqueueTilesReduce(DevMat* d, uint32_t binBegin, uint32_t binEnd, double* y, int nExtra, double* const* extra, hipStream_t stream) {
-    TileFormat* t = d->tiles;
+int enqueueTilesReduce(const DevMat* d, const TileFormat* t, uint32_t binBegin, uint32_t binEnd, double* y, int nExtra, double* const* extra,
+                       hipStream_t stream) {
     if (!t || binBegin > binEnd || binEnd > t->apiBins() || nExtra < 0 || nExtra > SPMV_MAX_PEERS) return EXIT_FAILURE;
     if (binBegin == binEnd) return EXIT_SUCCESS;
     const dim3 grid = grid2d((uint64_t)((binEnd - binBegin + 7) / 8) * 8, PB_THREADS);
@@ -1210,9 +1242,8 @@ int enqueueTilesReduce(DevMat* d, uint32_t binBegin, uint32_t binEnd, double* y,
 // phase 2 over all bins on `stream` with the push kernel beside it on `side`: `side` first waits for what is enqueued on
 // `stream` so far (phase 1); evJoin marks the end of the push kernel and `stream` does NOT wait for it here, so the
 // next row group's phase 1 can run while this group's rows are still travelling.  y and the destinations as above.
-int enqueueTilesReducePush(DevMat* d, double* y, int nExtra, double* const* extra, hipStream_t stream, hipStream_t side,
+int enqueueTilesReducePush(const DevMat* d, TileFormat* t, double* y, int nExtra, double* const* extra, hipStream_t stream, hipStream_t side,
                            hipEvent_t evFork, hipEvent_t evJoin) {
-    TileFormat* t = d->tiles;
     if (!t || nExtra < 1 || nExtra > SPMV_MAX_PEERS) return EXIT_FAILURE;
     const double* prod = prodWorkspace(t->nnz, true);
     if (!prod || prodHandover(stream)) return EXIT_FAILURE;
@@ -1243,8 +1274,7 @@ int enqueueTilesReducePush(DevMat* d, double* y, int nExtra, double* const* extr
 }
 
 // 1 when a push kernel of this matrix ever gave up waiting for a bin (synchronises the device)
-int tilesPushFailed(DevMat* d) {
-    TileFormat* t = d->tiles;
+int tilesPushFailed(const TileFormat* t) {
     if (!t || !t->pushFail) return 0;
     uint32_t f = 0;
     if (hipMemcpy(&f, t->pushFail, 4, hipMemcpyDeviceToHost) != hipSuccess) return 1;
@@ -1252,11 +1282,10 @@ int tilesPushFailed(DevMat* d) {
 }
 
 // enqueue both phases on `stream`
-int enqueueTiles(DevMat* d, const double* x, double* y, hipStream_t stream) {
-    TileFormat* t = d->tiles;
+int enqueueTiles(const DevMat* d, const TileFormat* t, const double* x, double* y, hipStream_t stream) {
     if (!t) return EXIT_FAILURE;
-    if (enqueueTilesExpand(d, x, stream)) return EXIT_FAILURE;
-    return enqueueTilesReduce(d, 0, t->apiBins(), y, 0, nullptr, stream);
+    if (enqueueTilesExpand(d, t, x, stream)) return EXIT_FAILURE;
+    return enqueueTilesReduce(d, t, 0, t->apiBins(), y, 0, nullptr, stream);
 }
 
 }  // namespace spmvhip

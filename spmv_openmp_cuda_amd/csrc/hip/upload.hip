@@ -63,9 +63,9 @@ void freeDesc(DevMat* d) {
     }
     (void)hipFree(d->blkInfo); (void)hipFree(d->blkBase); (void)hipFree(d->tmap);
     freeTri(d->tri[0]); freeTri(d->tri[1]);
-    freeTiles(d->tiles); freeTiles(d->tilesAlt);
+    freeTiles(d->tiles[0]); freeTiles(d->tiles[1]);
     freeSell(d->sell);
-    freeStripes(d->stripes); freeStripes(d->stripesAlt);
+    freeStripes(d->stripes[0]); freeStripes(d->stripes[1]);
     d->magic = 0;
     delete d;
 }
@@ -237,10 +237,10 @@ int updateValues(spmat* h, const double* AS, bool onDevice, bool reread, hipStre
         // (SELL has no unit kernel): only the value in the registers changes.  A stripes format built for a unit matrix has
         // no value array: it is rebuilt, with its recorded options, when the values stop being unit.
         const bool arrays = !(info.unitBefore && d->unit);
-        for (TileFormat* t : {d->tiles, d->tilesAlt})
+        for (TileFormat* t : d->tiles)
             if (t && arrays && tilesRefreshValues(d, t, st, &info.mapMs, &info.mapsBuilt)) return EXIT_FAILURE;
         std::vector<spmvStripesOpts> rebuild;
-        for (StripeFormat* f : {d->stripes, d->stripesAlt}) {
+        for (StripeFormat* f : d->stripes) {
             if (!f) continue;
             if (!stripesHasValues(f) && !d->unit) { rebuild.push_back(stripesOptions(f)); continue; }
             if (stripesHasValues(f) && arrays && stripesRefreshValues(d, f, st, &info.mapMs, &info.mapsBuilt)) return EXIT_FAILURE;

@@ -651,6 +651,80 @@ def test_auto_launcher_picks_and_remembers(api, oracle):
     de.free()
 
 
+def test_explicit_forms_are_rebuilt_alone_and_survive_the_selections(api, oracle):
+    """A handle holds each format in two forms side by side.  (1) An explicit build replaces the form its options name
+    and nothing else: the queries (which follow the preference the build sets) show the new shape, and the byte total of
+    the format moves by exactly that form's difference -- so the form not named kept its bytes.  (2) A selection times
+    every candidate and releases the losers' formats, but never a form the caller built: the totals do not shrink and
+    the explicit launchers still compute, the deterministic forms the bits of the serial oracle."""
+    import ctypes as C
+    rng = np.random.default_rng(32)
+    M = N = 40_000
+    IRP, JA, AS = random_csr(rng, M, N, np.full(M, 8))
+    assert JA.size >= 1 << 18                               # the formats are eligible in both selections
+    x = _x(rng, N)
+    y_ref = oracle.csr_serial(IRP, JA, AS, x)
+
+    def totals(dm):
+        return api.lib.spmvHipTilesBytes(C.byref(dm.handle)), api.lib.spmvHipStripesBytes(C.byref(dm.handle))
+
+    def shape(i):                                           # everything of an info but the times
+        return tuple(getattr(i, f) for f, _ in i._fields_ if not f.endswith("Ms"))
+
+    def explicit_launchers(dm, exact):
+        for launcher in ("hipSpMVTilesCSR", "hipSpMVStripesCSR"):
+            y = _run(api, launcher, dm, x, M)
+            assert not np.isnan(y).any(), launcher
+            if exact:
+                assert_same_bits(y, y_ref, launcher)
+            else:
+                assert tight_error(IRP, JA, AS, x, y_ref, y) <= TIGHT, launcher
+
+    for det_last in (0, 1):                                 # the forms built last are the ones the launchers and queries use
+        dm = api.spMatCpyCSR(api.HostCSR(M, N, IRP, JA, AS))
+        try:
+            ti, si = {}, {}
+            for det in (1 - det_last, det_last):
+                api.build_tiles(dm, deterministic=det)
+                ti[det] = api.tiles_info(dm)
+                api.build_stripes(dm, deterministic=det)
+                si[det] = api.stripes_info(dm)
+                assert ti[det].deterministic == det and si[det].deterministic == det and ti[det].bytes and si[det].bytes
+            assert totals(dm) == (ti[0].bytes + ti[1].bytes, si[0].bytes + si[1].bytes)
+            # (1) one form of each format again, with other options, first the preferred form, then the other one
+            for det in (det_last, 1 - det_last):
+                tb, sb = totals(dm)
+                api.build_tiles(dm, rowsPerBin=4096 if det else 2048, deterministic=det)
+                t = api.tiles_info(dm)
+                assert t.deterministic == det and t.rowsPerBin == (4096 if det else 2048) and shape(t) != shape(ti[det])
+                assert totals(dm) == (tb - ti[det].bytes + t.bytes, sb)
+                api.build_stripes(dm, rowsPerBin=1024 if det else 512, deterministic=det)
+                s = api.stripes_info(dm)
+                assert s.deterministic == det and s.rowsPerBin <= (1024 if det else 512) and shape(s) != shape(si[det])
+                assert totals(dm) == (tb - ti[det].bytes + t.bytes, sb - si[det].bytes + s.bytes)
+                ti[det], si[det] = t, s
+            assert totals(dm) == (ti[0].bytes + ti[1].bytes, si[0].bytes + si[1].bytes)
+            # the preference followed the last build: back to the forms of det_last, by a build with the options they have
+            api.build_tiles(dm, rowsPerBin=4096 if det_last else 2048, deterministic=det_last)
+            api.build_stripes(dm, rowsPerBin=1024 if det_last else 512, deterministic=det_last)
+            assert shape(api.tiles_info(dm)) == shape(ti[det_last]) and shape(api.stripes_info(dm)) == shape(si[det_last])
+            assert totals(dm) == (ti[0].bytes + ti[1].bytes, si[0].bytes + si[1].bytes)
+            explicit_launchers(dm, exact=bool(det_last))
+            # (2) both selections: each has a two-phase and a stripes candidate, so a form of the caller's loses in each
+            before = totals(dm)
+            y = _run(api, "hipSpMVAutoCSR", dm, x, M)
+            assert not np.isnan(y).any() and tight_error(IRP, JA, AS, x, y_ref, y) <= TIGHT
+            assert_same_bits(_run(api, "hipSpMVRowsCSR", dm, x, M), y_ref)
+            assert api.lib.spmvHipAutoChoice(C.byref(dm.handle), None) is not None
+            assert api.lib.spmvHipAutoChoiceRows(C.byref(dm.handle), None) is not None
+            after = totals(dm)
+            assert after[0] >= before[0] and after[1] >= before[1], (before, after)
+            assert shape(api.tiles_info(dm)) == shape(ti[det_last]) and shape(api.stripes_info(dm)) == shape(si[det_last])
+            explicit_launchers(dm, exact=bool(det_last))
+        finally:
+            dm.free()
+
+
 def test_lds_atomics_add_in_lane_order_on_this_device(api):
     """The property the deterministic kernels rest on, probed directly (and consulted by the serial-order selection)."""
     assert api.lib.spmvHipProbeLdsAtomicOrder() == 1
