@@ -94,8 +94,10 @@ struct TileFormat {
     uint32_t  nList = 0;
     uint32_t* binPos = nullptr;                     // [B+1] bin-major position where each bin starts
     uint32_t* waveTile = nullptr;                   // [B * waves] tile-list index where each wavefront of phase 2 starts
-    uint3*    work = nullptr;                       // phase-1 work items {slice, begin, end}
+    uint3*    work = nullptr;                       // phase-1 work items {slice, begin, end}, slice-major
     uint32_t  nWork = 0;
+    uint32_t* runs = nullptr;                       // [grid1+1] phase 1 is resident: workgroup g walks the items [runs[g], runs[g+1])
+    uint32_t  grid1 = 0;                            // workgroups of phase 1: min(work items, CUs)
     bool      ntStore = true;                       // phase 1 stores the products non-temporally (streams larger than the Infinity Cache)
     uint32_t* ready = nullptr;                      // [B] epoch of the last step whose bin was stored (push kernel hand-off)
     uint32_t* pushFail = nullptr;                   // set by the push kernel when a flag never arrived
@@ -255,14 +257,16 @@ constexpr int      P1_DEPTH = 8;                    // steps per batch
 constexpr uint32_t P1_STEP  = 2 * PB_THREADS;       // entries one workgroup step covers
 struct P1Regs { dbl2 a[P1_DEPTH]; ush2 c[P1_DEPTH]; };
 
-// requires ve - 2 >= first entry of the vector range
+// Positions past ve are clamped to the pair below it (nothing of them is stored); for a range without a whole pair that is a
+// pair at or below its start -- any address inside the arrays will do (their slab parts are padded to 256 B).
 // UNIT: every value of the matrix is `unitValue` (DevMat::unit) -- the 8 B/nnz value stream is not read
 template <bool UNIT>
 __device__ __forceinline__ void p1_load(P1Regs& r, uint32_t p, uint32_t ve, const double* __restrict__ val,
                                         const uint16_t* __restrict__ lcol, double unitValue) {
+    const uint32_t hi = max(ve, 2u) - 2u;
 #pragma unroll
     for (int u = 0; u < P1_DEPTH; ++u) {
-        const uint32_t q = min(p + u * P1_STEP, ve - 2u);
+        const uint32_t q = min(p + u * P1_STEP, hi);
         if (UNIT) r.a[u] = dbl2{unitValue, unitValue};
         else      r.a[u] = __builtin_nontemporal_load((const dbl2*)(val + q));
         r.c[u] = __builtin_nontemporal_load((const ush2*)(lcol + q));
@@ -282,49 +286,109 @@ __device__ __forceinline__ void p1_store(const P1Regs& r, uint32_t p, uint32_t v
     }
 }
 
+// the parts of a work item [begin, end): scalar head [begin, vb), whole line-aligned pairs [vb, ve), scalar tail [ve, end)
+struct P1Range { uint32_t begin, end, vb, ve; };
+__device__ __forceinline__ P1Range p1_range(const uint3 w) {
+    P1Range r;
+    r.begin = w.y; r.end = w.z;
+    r.vb = min(w.z, (w.y + 63u) & ~63u);            // first line-aligned entry inside the range
+    r.ve = r.vb + ((w.z - r.vb) & ~1u);             // end of the whole pairs
+    return r;
+}
+
+// A thread carries P1_XALL = 16 doubles of an x slice to LDS.  Only the first P1_XPRE of them are requested ahead, under the
+// previous item's last double batch: two live batches (80 VGPRs) and a whole share (32), or half of it, spilled to scratch
+// under the 128 VGPRs of a 1024-thread workgroup.  The rest is requested at the hand-over, where one batch is dead.
+constexpr uint32_t P1_XALL = PB_C / PB_THREADS;
+constexpr uint32_t P1_XPRE = 4;
+
+// doubles [I0, I1) of this thread's share of x slice `slice` into registers (clamped addresses, like the stream loads;
+// N >= 1) ...
+template <uint32_t I0, uint32_t I1>
+__device__ __forceinline__ void p1_load_x(double (&xv)[I1 - I0], uint32_t slice, const double* __restrict__ x, uint64_t N) {
+    const double* xb = x + (uint64_t)slice * PB_C;                              // uniform: the slice has 1 <= nIn <= PB_C columns
+    const uint32_t nIn = (uint32_t)min(N - (uint64_t)slice * PB_C, (uint64_t)PB_C);
+#pragma unroll
+    for (uint32_t i = I0; i < I1; ++i)
+        xv[i - I0] = xb[min(threadIdx.x + i * PB_THREADS, nIn - 1)];           // past the last column: any value, no entry refers to it
+}
+// ... and from there to LDS
+template <uint32_t I0, uint32_t I1>
+__device__ __forceinline__ void p1_fill_x(double* xs, const double (&xv)[I1 - I0]) {
+#pragma unroll
+    for (uint32_t i = I0; i < I1; ++i) xs[threadIdx.x + i * PB_THREADS] = xv[i - I0];
+}
+
+// RESIDENT: one workgroup per CU for the whole launch (the x slice fills the LDS, so no more than one fits anyway).
+// Workgroup g walks the work items [runs[g], runs[g+1]) -- a contiguous, slice-major run cut by the host so that every
+// workgroup streams the same number of entries.  Launched as one workgroup per item, a CU paid at every item a
+// workgroup exit (stores drained), a dispatch and an HBM round trip for a slice it mostly held already; here the
+// stream of the next item is requested before the current one's last stores, and the LDS is refilled only when the
+// slice changes: the first part of the next slice travels to registers (xv) under the last double batch of the current
+// item, and the hand-over is barrier / registers -> LDS / the rest of the slice / barrier with the next item's first
+// batch already in flight (vmcnt counts in issue order: the wait for xv leaves that batch outstanding).  All loop control is
+// workgroup-uniform.
 template <bool NT, bool UNIT>
 __global__ __launch_bounds__(PB_THREADS) void pb_expand_kernel(
-    const uint3* __restrict__ work, const double* __restrict__ val, const uint16_t* __restrict__ lcol,
-    const double* __restrict__ x, uint64_t N, double* __restrict__ prod, double unitValue) {
+    const uint32_t* __restrict__ runs, const uint3* __restrict__ work, const double* __restrict__ val,
+    const uint16_t* __restrict__ lcol, const double* __restrict__ x, uint64_t N, double* __restrict__ prod, double unitValue) {
     extern __shared__ double xs[];                  // PB_C doubles
-    const uint3 w = work[lin_block()];
-    const uint32_t begin = w.y, end = w.z;
-    const uint32_t vb = min(end, (begin + 63u) & ~63u);         // first line-aligned entry inside the range
-    const uint32_t ve = vb + ((end - vb) & ~1u);                // end of the whole pairs
-    const bool vec = ve > vb;                                   // uniform
+    constexpr uint32_t BATCH = P1_DEPTH * P1_STEP;
+    uint32_t item = runs[blockIdx.x];
+    const uint32_t itemEnd = runs[blockIdx.x + 1];
+    if (item >= itemEnd) return;
+    const uint32_t lane2 = 2 * threadIdx.x;
 
-    uint32_t p = vb + 2 * threadIdx.x;
+    uint3 w = work[item];
+    P1Range r = p1_range(w);
     P1Regs cur, nxt;
-    const uint64_t col0 = (uint64_t)w.x * PB_C;
+    double xv[P1_XPRE];
     // Order of the first requests: the x slice BEFORE the first stream batch.  vmcnt counts in issue order, so the LDS
     // fill below waits for the slice only while the batch behind it is still in flight; with the batch first (round 1)
     // the fill waited for both (c5: 8.13-8.20 against 8.26-8.46 ms over 5 fresh processes each,
     // profiles/r02_tiles_load_policy.log).
-    {
-        double xv[PB_C / PB_THREADS];
-#pragma unroll
-        for (uint32_t i = 0; i < PB_C / PB_THREADS; ++i) {
-            const uint32_t k = threadIdx.x + i * PB_THREADS;
-            xv[i] = (col0 + k < N) ? x[col0 + k] : 0.0;
-        }
-        if (vec) p1_load<UNIT>(cur, p, ve, val, lcol, unitValue);
-#pragma unroll
-        for (uint32_t i = 0; i < PB_C / PB_THREADS; ++i) xs[threadIdx.x + i * PB_THREADS] = xv[i];
-    }
-    __syncthreads();
+    p1_load_x<0, P1_XPRE>(xv, w.x, x, N);
+    p1_load<UNIT>(cur, r.vb + lane2, r.ve, val, lcol, unitValue);
+    bool restage = true;
 
-    // scalar head (at most 63 entries) and tail (at most 1)
-    if (threadIdx.x < vb - begin) { const uint32_t q = begin + threadIdx.x; prod[q] = (UNIT ? unitValue : val[q]) * xs[lcol[q]]; }
-    if (threadIdx.x < end - ve)   { const uint32_t q = ve + threadIdx.x;    prod[q] = (UNIT ? unitValue : val[q]) * xs[lcol[q]]; }
-
-    if (vec) {
-        constexpr uint32_t BATCH = P1_DEPTH * P1_STEP;
-        for (; p < ve; p += 2 * BATCH) {
-            p1_load<UNIT>(nxt, p + BATCH, ve, val, lcol, unitValue);
-            p1_store<NT>(cur, p, ve, xs, prod);
-            p1_load<UNIT>(cur, p + 2 * BATCH, ve, val, lcol, unitValue);
-            p1_store<NT>(nxt, p + BATCH, ve, xs, prod);
+    for (;;) {
+        // here: `cur` holds the first batch of item w (in flight), and xv the first part of its slice if that is not
+        // the one in LDS
+        if (restage) {
+            __syncthreads();                        // every wavefront has read what it needs of the old slice
+            double xr[P1_XALL - P1_XPRE];
+            p1_load_x<P1_XPRE, P1_XALL>(xr, w.x, x, N);
+            p1_fill_x<0, P1_XPRE>(xs, xv);
+            p1_fill_x<P1_XPRE, P1_XALL>(xs, xr);
+            __syncthreads();
         }
+        const bool more = item + 1 < itemEnd;
+        const uint3 wn = work[more ? item + 1 : item];
+        const P1Range rn = p1_range(wn);
+        restage = more && wn.x != w.x;
+
+        // scalar head (at most 63 entries) and tail (at most 1)
+        if (threadIdx.x < r.vb - r.begin) { const uint32_t q = r.begin + threadIdx.x; prod[q] = (UNIT ? unitValue : val[q]) * xs[lcol[q]]; }
+        if (threadIdx.x < r.end - r.ve)   { const uint32_t q = r.ve + threadIdx.x;    prod[q] = (UNIT ? unitValue : val[q]) * xs[lcol[q]]; }
+
+        // The vector range in double batches (one pass that stores nothing when the item has no whole pair).  Behind the
+        // loads of the LAST double batch go the next slice, if it differs, and the next item's first batch in the place
+        // of this item's next one: ONE copy of the stream code, the hand-over is a uniform choice of its addresses.
+        bool last;
+        uint32_t pb = r.vb;
+        do {
+            last = pb + 2 * BATCH >= r.ve;
+            const uint32_t p = pb + lane2;
+            p1_load<UNIT>(nxt, p + BATCH, r.ve, val, lcol, unitValue);
+            p1_store<NT>(cur, p, r.ve, xs, prod);
+            if (last && restage) p1_load_x<0, P1_XPRE>(xv, wn.x, x, N);
+            const bool hand = last && more;
+            p1_load<UNIT>(cur, hand ? rn.vb + lane2 : p + 2 * BATCH, hand ? rn.ve : r.ve, val, lcol, unitValue);
+            p1_store<NT>(nxt, p + BATCH, r.ve, xs, prod);
+            pb += 2 * BATCH;
+        } while (!last);
+        if (!more) break;
+        w = wn; r = rn; ++item;
     }
 }
 
@@ -804,7 +868,7 @@ uint64_t tilesBinRow(const DevMat* d, const TileFormat* t, uint32_t bin) {
 void freeTiles(TileFormat* t) {
     if (!t) return;
     (void)hipFree(t->slab); (void)hipFree(t->tl); (void)hipFree(t->pidx); (void)hipFree(t->vmap);
-    (void)hipFree(t->binPos); (void)hipFree(t->waveTile); (void)hipFree(t->work); (void)hipFree(t->ready);
+    (void)hipFree(t->binPos); (void)hipFree(t->waveTile); (void)hipFree(t->work); (void)hipFree(t->runs); (void)hipFree(t->ready);
     delete t;
 }
 
@@ -986,8 +1050,9 @@ static int placeTiles(TileFormat* t, TileBuildTemps& tmp) {
     return EXIT_SUCCESS;
 }
 
-// Work item size of phase 1 when the caller names none.  One workgroup per CU at a time (the x slice fills the LDS), so the
-// items are processed in rounds of PB_CUS and what counts is (a) items of 50-100 k entries (c5: 524 k 8.88 ms, 262 k 8.82,
+// Work item size of phase 1 when the caller names none.  (Chosen when every item was a workgroup of its own; the resident
+// kernel walks the same items, so the size -- what spmvHipTilesInfo reports -- is kept.)  One workgroup per CU at a time
+// (the x slice fills the LDS), so the items were processed in rounds of PB_CUS and what counted was (a) items of 50-100 k entries (c5: 524 k 8.88 ms, 262 k 8.82,
 // 131 k 8.76, 65-98 k 8.74) and (b) how full the LAST round is: on c3 (610 slices of 328 k entries) 3 pieces per slice =
 // 7.15 rounds ran at 1.081 ms, 2 / 4 / 6 pieces (4.77 / 9.53 / 14.3 rounds) at 1.041-1.046 ms.  The extra x-slice fills of
 // more pieces are nearly free (issued under the running stream, served by L2 / Infinity Cache).  Pieces per slice: within
@@ -1009,43 +1074,18 @@ static uint32_t phase1Chunk(const std::vector<uint32_t>& sliceStart, uint64_t nn
     return chunk;
 }
 
-// Order of the work items: workgroups are dealt round-robin to the 8 XCDs, each with its own L2, and the pieces of
-// one slice all stage the same 128 KiB of x.  Listed one after the other they land on different XCDs and every
-// piece fetches the slice from the fabric (c5, 4 pieces: 2.6 GB of fills per SpMV); listed 8 apart -- groups of 8
-// slices, piece k of each, then piece k+1 of each -- they land on ONE XCD at almost the same time and all but the
-// first fill hit its L2.
-static std::vector<uint3> interleaveSlices(const std::vector<uint3>& work) {
-    std::vector<uint3> ordered;
-    ordered.reserve(work.size());
-    size_t i = 0;
-    while (i < work.size()) {
-        // the next (up to) 8 slices and their pieces
-        size_t first[9];
-        int ns = 0;
-        size_t j = i;
-        while (j < work.size() && ns < 8) {
-            first[ns++] = j;
-            const uint32_t sl = work[j].x;
-            while (j < work.size() && work[j].x == sl) ++j;
-        }
-        first[ns] = j;
-        size_t maxPieces = 0;
-        for (int k = 0; k < ns; ++k) maxPieces = std::max(maxPieces, first[k + 1] - first[k]);
-        for (size_t pc = 0; pc < maxPieces; ++pc)
-            for (int k = 0; k < ns; ++k)
-                if (first[k] + pc < first[k + 1]) ordered.push_back(work[first[k] + pc]);
-        i = j;
-    }
-    return ordered;
-}
-
-// the phase-1 work list {slice, begin, end} from the slice boundaries, in launch order (host arithmetic only)
-static std::vector<uint3> planPhase1Work(const std::vector<uint32_t>& sliceStart, uint32_t chunk) {
-    std::vector<uint3> work;
+// The phase-1 work: items {slice, begin, end} in SLICE-MAJOR order (= ascending slice-major position: the items tile
+// [0, nnz) without gaps), and the runs of the resident launch -- workgroup g of `grid` walks the items
+// [runs[g], runs[g+1]).  Host arithmetic only.  (Launched as one workgroup per item, the pieces of a slice were listed 8
+// apart so that they met in one XCD's L2; a resident workgroup keeps the slice in its LDS from piece to piece instead,
+// and a slice is fetched by the one or two workgroups whose runs hold it.)
+struct Phase1Plan { std::vector<uint3> work; std::vector<uint32_t> runs; };
+static Phase1Plan planPhase1Work(const std::vector<uint32_t>& sliceStart, uint32_t chunk, uint32_t cus) {
+    std::vector<uint3> items;
     for (uint32_t s = 0; s + 1 < sliceStart.size(); ++s) {
-        // a slice is cut into equal pieces of at most PB_CHUNK entries (a fixed chunk size + remainder left one
-        // short, fill-dominated work item per slice); inner boundaries fall on multiples of 64 entries so that
-        // only a slice's first work item has a scalar head
+        // a slice is cut into equal pieces of at most `chunk` entries (a fixed chunk size + remainder left one
+        // short work item per slice); inner boundaries fall on multiples of 64 entries so that only a slice's
+        // first work item has a scalar head
         const uint32_t b0 = sliceStart[s], e0 = sliceStart[s + 1], len = e0 - b0;
         if (!len) continue;
         const uint32_t pieces = (len + chunk - 1) / chunk;
@@ -1053,11 +1093,32 @@ static std::vector<uint3> planPhase1Work(const std::vector<uint32_t>& sliceStart
         uint32_t b = b0;
         for (uint32_t k = 1; k <= pieces && b < e0; ++k) {
             const uint32_t e = (k == pieces) ? e0 : std::min<uint32_t>(e0, (b0 + k * piece + 63u) & ~63u);
-            if (e > b) work.push_back(make_uint3(s, b, e));
+            if (e > b) items.push_back(make_uint3(s, b, e));
             b = e;
         }
     }
-    return interleaveSlices(work);
+    Phase1Plan plan;
+    if (items.empty()) return plan;
+    // Runs balanced by ENTRIES: run g begins at the multiple of 64 below g * nnz / grid.  An item that straddles such a
+    // cut is split there (both halves keep their slice; the cut is line-aligned, so the second half has no scalar
+    // head), which leaves every run within 64 entries of its share instead of within one item of it -- an item is
+    // ~1 % of a workgroup's stream on c5, and the launch ends with its slowest workgroup.
+    const uint64_t nnz = items.back().z;
+    const uint32_t grid = (uint32_t)std::min<size_t>(items.size(), cus);
+    plan.runs.assign(grid + 1, 0);
+    uint32_t g = 1;
+    auto cutAt = [&](uint32_t k) { return (uint32_t)(nnz * k / grid) & ~63u; };
+    for (const uint3& it : items) {
+        uint32_t b = it.y;
+        for (; g < grid && cutAt(g) < it.z; ++g) {  // cuts inside (or at the start of) this item, in ascending order
+            const uint32_t c = cutAt(g);
+            if (c > b) { plan.work.push_back(make_uint3(it.x, b, c)); b = c; }
+            plan.runs[g] = (uint32_t)plan.work.size();       // (several cuts at one position: empty runs, the kernel returns)
+        }
+        plan.work.push_back(make_uint3(it.x, b, it.z));
+    }
+    for (; g <= grid; ++g) plan.runs[g] = (uint32_t)plan.work.size();
+    return plan;
 }
 
 // the LDS of the launches (set at every build: the attribute belongs to the current device, and a process may drive several)
@@ -1108,10 +1169,13 @@ int buildTiles(DevMat* d, const spmvTilesOpts* opts) {
     std::vector<uint32_t> sliceStart(t->S + 1);
     PB_TRY(hipMemcpy2D(sliceStart.data(), 4, tmp.tileStart.as<uint32_t>(), (size_t)t->B * 4, 4, t->S + 1, hipMemcpyDeviceToHost));
     t->chunk = o.chunk ? o.chunk : phase1Chunk(sliceStart, nnz, t->cus);
-    const std::vector<uint3> work = planPhase1Work(sliceStart, t->chunk);
-    t->nWork = (uint32_t)work.size();
-    PB_TRY(hipMalloc(&t->work, std::max<size_t>(work.size(), 1) * sizeof(uint3)));
-    PB_TRY(hipMemcpy(t->work, work.data(), work.size() * sizeof(uint3), hipMemcpyHostToDevice));
+    const Phase1Plan plan = planPhase1Work(sliceStart, t->chunk, t->cus);
+    t->nWork = (uint32_t)plan.work.size();
+    t->grid1 = plan.runs.empty() ? 0 : (uint32_t)plan.runs.size() - 1;
+    PB_TRY(hipMalloc(&t->work, std::max<size_t>(plan.work.size(), 1) * sizeof(uint3)));
+    PB_TRY(hipMemcpy(t->work, plan.work.data(), plan.work.size() * sizeof(uint3), hipMemcpyHostToDevice));
+    PB_TRY(hipMalloc(&t->runs, std::max<size_t>(plan.runs.size(), 1) * sizeof(uint32_t)));
+    PB_TRY(hipMemcpy(t->runs, plan.runs.data(), plan.runs.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     PB_TRY(hipDeviceSynchronize());
 
     if (setTilesKernelAttributes()) return EXIT_FAILURE;
@@ -1194,7 +1258,7 @@ int enqueueTilesExpand(const DevMat* d, const TileFormat* t, const double* x, hi
     double* prod = prodWorkspace(t->nnz, true);      // grows (after a device synchronise) only if it was released meanwhile
     if (!prod || prodHandover(stream)) return EXIT_FAILURE;
     if (t->nWork) {
-#define PB_EXPAND(NT, UNIT) hipLaunchKernelGGL((pb_expand_kernel<NT, UNIT>), grid2d(t->nWork, PB_THREADS), dim3(PB_THREADS), PB_C * 8, stream, t->work, \
+#define PB_EXPAND(NT, UNIT) hipLaunchKernelGGL((pb_expand_kernel<NT, UNIT>), dim3(t->grid1), dim3(PB_THREADS), PB_C * 8, stream, t->runs, t->work, \
                                               t->val, t->lcol, x, d->N, prod, d->unitValue)
         if (d->unit) { if (t->ntStore) PB_EXPAND(true, true); else PB_EXPAND(false, true); }      // (the format keeps its value array: the slab is
         else         { if (t->ntStore) PB_EXPAND(true, false); else PB_EXPAND(false, false); }    //  the build's sort buffer; it is just not read)
