@@ -307,6 +307,87 @@ typedef struct {
 int spmvHipDot(size_t n, const double* dU, const double* dV, double* dResult);
 int hipSpCGCSR(spmat* dA, spmat* dM, const double* dB, double* dX, const spmvKrylovOpts* opts, spmvKrylovInfo* info);
 int hipSpBiCGStabCSR(spmat* dA, spmat* dM, const double* dB, double* dX, const spmvKrylovOpts* opts, spmvKrylovInfo* info);
+/* spmvHipMultiDot: dH[i] (k doubles on the device) = V(:, i) . w for i = 0 .. k-1 in one pass over w, column i of V at
+ * dV + i*ldv (ldv >= n).  Every dH[i] is bit for bit spmvHipDot(n, dV + i*ldv, dW): the same blocks of 4096 indices, the
+ * same lane order, the same tree and the same second level -- whatever k, ldv and the alignment of the pointers are
+ * (one form is chosen per call on the host: 16-byte loads when dV and dW are 16-byte aligned and, for k > 1, ldv is even;
+ * scalar loads otherwise).  DESIGN.md section 20.  Two kernels on the library stream: the first keeps a block's 16 doubles
+ * of w per lane in registers and walks the columns (panels of 16 in the grid's z), block partials to part[i*nb + blk];
+ * the second adds them, one workgroup per pair of columns.  No flags, tickets or atomics: the kernel boundary orders them.
+ *   n = 0 writes k times +0.0.  dH[k ..] is not touched.
+ *   Workspace: the library's dot workspace, shared with spmvHipDot, here k * ceil(n / 4096) doubles: it grows (allocation,
+ *   device synchronisation) at the first call that needs more than any earlier call of either function; calls within
+ *   that size only enqueue and can be captured into a graph.  Calls on different streams share it: keep them ordered.
+ *   spmvHipSetSync, spmvHipLastKernelSeconds and spmvHipLastLaunch as for spmvHipDot (the last launch is the second
+ *   kernel: ceil(k/2) workgroups of 256).  spmvHipFinalize frees the workspace.
+ *   Refused (EXIT_FAILURE, dH untouched): a NULL dH; a NULL dV or dW when n > 0; k == 0; ldv < n.
+ *
+ * hipSpGMRESCSR: right-preconditioned restarted GMRES(restart) for a square A, with classical Gram-Schmidt applied twice
+ * (CGS2).  dA, dM, dB, dX, info as for the two solvers above; opts.restart in 1 .. 64; opts.maxIter counts inner
+ * iterations (Arnoldi steps) over all cycles.  x, info.status, info.iterations, info.rr, info.bb and history are the bits
+ * of this loop, in IEEE double with no FMA: dot() is spmvHipDot, A v is serial-order SpMV, M^-1 the two hipSpTRSVCSR
+ * solves, sqrt and / are correctly rounded, every a +- s*v is two roundings in the order written, tol2 = tol*tol on the
+ * host.  v[0 .. restart], w, z, u, r, q are vectors; h, c, cs, sn, g, y and the upper triangle R are scalars.
+ *     q = A x; r = b - q; rr = dot(r,r); bb = dot(b,b); thresh = tol2 * bb; hist[0] = rr
+ *     if rr <= thresh: CONVERGED, 0;  if rr is not finite: NONFINITE, 0;  if maxIter == 0: MAXITER, 0
+ *     k = 0
+ *     cycle:
+ *       beta = sqrt(rr); v[0] = r / beta (element by element); g[0] = beta
+ *       for j = 0 .. restart-1:
+ *         z = M^-1 v[j] (z = v[j] without M); w = A z
+ *         for i = 0..j: h[i] = dot(v[i], w)                            -- spmvHipMultiDot
+ *         for i = 0..j ascending: w = w - h[i]*v[i]
+ *         for i = 0..j: c[i] = dot(v[i], w)                            -- the second pass
+ *         for i = 0..j ascending: w = w - c[i]*v[i]
+ *         for i = 0..j: h[i] = h[i] + c[i]
+ *         ww = dot(w,w); hn = sqrt(ww)
+ *         for i = 0..j-1: t = cs[i]*h[i] + sn[i]*h[i+1]; h[i+1] = cs[i]*h[i+1] - sn[i]*h[i]; h[i] = t
+ *         d = sqrt(h[j]*h[j] + hn*hn)
+ *         if d == 0:                                                   -- the step is dropped: k and hist are as before it
+ *           if j == 0: BREAKDOWN, k                                    -- nothing to add to x; rr, hist[k] stay the last true ones
+ *           cols = j; go to endcycle
+ *         k = k + 1
+ *         cs[j] = h[j]/d; sn[j] = hn/d; h[j] = d; R[0..j][j] = h[0..j]
+ *         g[j+1] = -(sn[j]*g[j]); g[j] = cs[j]*g[j]; est = g[j+1]*g[j+1]; hist[k] = est
+ *         if est <= thresh or est is not finite or hn == 0 or j == restart-1 or k == maxIter: cols = j+1; go to endcycle
+ *         v[j+1] = w / hn
+ *       endcycle (cols >= 1):
+ *         for i = cols-1 .. 0: s = g[i]; for l = i+1 .. cols-1 ascending: s = s - R[i][l]*y[l]; y[i] = s / R[i][i]
+ *         u = y[0]*v[0]; for i = 1 .. cols-1: u = u + y[i]*v[i];  z = M^-1 u (z = u without M);  x = x + z
+ *         q = A x; r = b - q; rr = dot(r,r); hist[k] = rr              -- the TRUE residual replaces the estimate
+ *         if rr <= thresh: CONVERGED, k;  if rr is not finite: NONFINITE, k
+ *         if the cycle ended on hn == 0 or d == 0: BREAKDOWN, k
+ *         if k == maxIter: MAXITER, k;  else the next cycle
+ *   CONVERGED is only ever declared on the true dot(b - A x, b - A x), never on the estimate.  hist[k] is the estimate
+ *   inside a cycle and the true rr at index 0 and at every cycle's last index; info.rr is the last true rr.
+ *   The corners: a step with d == 0 does not count (k is the number of steps before it) and writes no hist entry; at
+ *   j == 0 the solve ends there with x, info.rr and hist[k] as the previous cycle end (or the init) left them; at j > 0 the
+ *   cycle ends with the j columns it has, hist[k] (the last kept step's estimate) becomes the true rr, and the status is
+ *   BREAKDOWN unless that rr converged or is not finite.
+ * Execution: the scalars live in a device state block that only single-lane finish steps write; the Givens step, the
+ *   tests and, at a cycle's end, the back-substitution run on one lane of the ww finish.  The block carries `stop` and,
+ *   next to it, `skip` (set when a cycle ends, cleared by the cycle-end step that starts the next one; stop implies
+ *   skip): the kernels of an inner step and its triangular solves return at once on skip, those of the cycle end on stop.
+ *   The host enqueues one whole cycle -- min(restart, maxIter - k) inner steps, then the cycle end -- and reads the block
+ *   back once per cycle: info.hostChecks is the number of cycles (the one read after the init step, which decides
+ *   whether a first cycle runs at all, is not counted); steps enqueued past an early cycle end write nothing.  Per inner
+ *   step: M^-1, the SpMV, and 8 launches whatever j is (two for each projection, the two updates -- w read and written
+ *   once, the v[i] streamed; the second carries the partials of dot(w,w) --, the ww finish, v[j+1] = w / hn);
+ *   spmvHipSetVariant("hipSpGMRESCSR", 1) folds the first update into the partials of the second projection (7; the bits
+ *   do not change), 0 is the default.
+ *   Workspace, allocated by the call and freed before it returns, with ldv = n rounded up to even and nb = ceil(n/4096):
+ *   8*ldv*(restart + 4) bytes (v[0 .. restart], w / u, r, q), 8*ldv more with M (z), 8*nb*(restart + 2) of partials,
+ *   about 36 KiB of state, 8*(maxIter + 1) with a history.  Synchronous, on the library stream; not capturable.
+ *   M = 0 succeeds as above: CONVERGED, 0, history[0] = +0.0, no kernel and no read-back.
+ * Refused with a message and EXIT_FAILURE, x untouched: everything hipSpBiCGStabCSR refuses; restart == 0 or > 64. */
+typedef struct {
+    double   tol;           /* stop when the true dot(r,r) <= (tol*tol) * dot(b,b)            */
+    ulong    maxIter;       /* inner iterations at most, over all cycles                     */
+    unsigned restart;       /* inner iterations of a cycle, 1 .. 64                          */
+    double*  history;       /* NULL, or maxIter + 1 host doubles: hist[0 .. iterations]      */
+} spmvGmresOpts;
+int spmvHipMultiDot(size_t n, unsigned k, const double* dV, size_t ldv, const double* dW, double* dH);
+int hipSpGMRESCSR(spmat* dA, spmat* dM, const double* dB, double* dX, const spmvGmresOpts* opts, spmvKrylovInfo* info);
 /* Release the device arrays behind a handle (cudaUtils.h:70-78). */
 int hipFreeSpmat(spmat* dMat);
 
@@ -555,6 +636,8 @@ int spmvHipProbeLdsAtomicOrder(void);
  *   hipSpILU0CSR              8, 16 or 64: the lanes that factor one row (default 16).  AS does not change by a bit.
  *   hipSpCGCSR, hipSpBiCGStabCSR  K, 1..4096: iterations enqueued per read-back of the solver's device state
  *                             (default 16).  x does not change by a bit.
+ *   hipSpGMRESCSR             0 or 1: 1 folds the first CGS2 update into the partials of the second projection
+ *                             (default 0).  x does not change by a bit.
  * Returns EXIT_FAILURE for an unknown (launcher, variant). */
 int spmvHipSetVariant(const char* launcher, int variant);
 /* Use the RL array for ELL early exit (1, default when RL was uploaded) or walk

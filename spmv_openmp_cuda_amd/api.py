@@ -108,6 +108,8 @@ _sigs = {
     "spmvHipDot": ([_sz, _vp, _vp, _vp], _i),
     "hipSpCGCSR": ([C.POINTER(spmat), C.POINTER(spmat), _vp, _vp, _vp, _vp], _i),
     "hipSpBiCGStabCSR": ([C.POINTER(spmat), C.POINTER(spmat), _vp, _vp, _vp, _vp], _i),
+    "spmvHipMultiDot": ([_sz, C.c_uint, _vp, _sz, _vp, _vp], _i),
+    "hipSpGMRESCSR": ([C.POINTER(spmat), C.POINTER(spmat), _vp, _vp, _vp, _vp], _i),
 }
 SPMV_DENSE_ROW_MAJOR, SPMV_DENSE_COL_MAJOR = 0, 1          # include/spmvHip.h: layouts of hipSpMMRowsCSR's X and Y
 SPMV_TRI_LOWER, SPMV_TRI_UPPER = 0, 1                      # include/spmvHip.h: hipSpTRSVCSR's uplo ...
@@ -163,6 +165,12 @@ class spmvIluInfo(C.Structure):
 class spmvKrylovOpts(C.Structure):
     """include/spmvHip.h `spmvKrylovOpts`: tolerance, iteration cap, optional host history (maxIter + 1 doubles)."""
     _fields_ = [("tol", C.c_double), ("maxIter", C.c_ulong), ("history", C.POINTER(C.c_double))]
+
+
+class spmvGmresOpts(C.Structure):
+    """include/spmvHip.h `spmvGmresOpts`: tolerance, cap on the inner iterations, restart length (1 .. 64), optional host
+    history (maxIter + 1 doubles)."""
+    _fields_ = [("tol", C.c_double), ("maxIter", C.c_ulong), ("restart", C.c_uint), ("history", C.POINTER(C.c_double))]
 
 
 class spmvKrylovInfo(C.Structure):
@@ -540,10 +548,20 @@ class DeviceMatrix:
         """hipSpBiCGStabCSR: solve A x = b (A square) by right-preconditioned BiCGStab; arguments and result as cg()."""
         return self._krylov(lib.hipSpBiCGStabCSR, "hipSpBiCGStabCSR", b, x0, precond, tol, maxiter, history)
 
-    def _krylov(self, fn, name, b, x0, precond, tol, maxiter, history):
+    def gmres(self, b, x0=None, precond=None, tol=1e-8, maxiter=1000, restart=30, history=False):
+        """hipSpGMRESCSR: solve A x = b (A square) by right-preconditioned restarted GMRES(restart) with CGS2; maxiter
+        counts inner iterations over all cycles, 1 <= restart <= 64; the other arguments and the result as cg().
+        info.history holds the estimates inside a cycle and the true squared residual at every cycle's last index."""
+        return self._krylov(lib.hipSpGMRESCSR, "hipSpGMRESCSR", b, x0, precond, tol, maxiter, history, restart=restart)
+
+    def _krylov(self, fn, name, b, x0, precond, tol, maxiter, history, restart=None):
         N = int(self.handle.N)
         hist = np.zeros(int(maxiter) + 1, np.float64) if history else None
-        opts = spmvKrylovOpts(float(tol), int(maxiter), hist.ctypes.data_as(C.POINTER(C.c_double)) if history else None)
+        hp = hist.ctypes.data_as(C.POINTER(C.c_double)) if history else None
+        if restart is None:
+            opts = spmvKrylovOpts(float(tol), int(maxiter), hp)
+        else:
+            opts = spmvGmresOpts(float(tol), int(maxiter), int(restart), hp)
         info = spmvKrylovInfo()
         mh = C.byref(precond.handle) if precond is not None else None
         if isinstance(b, np.ndarray):
@@ -665,6 +683,40 @@ def dot(u, v):
         raise SpmvHipError(f"dot: lengths {u.numel()} and {v.numel()} differ")
     out = torch.empty((), dtype=torch.float64, device=u.device)
     _check(lib.spmvHipDot(u.numel(), u.data_ptr(), v.data_ptr(), out.data_ptr()), "spmvHipDot")
+    return out
+
+
+def multi_dot(V, w):
+    """spmvHipMultiDot: h = V^T w, every h[i] the bits of dot(V[:, i], w).  V: a 2-D float64 device torch tensor (n, k) whose
+    columns are contiguous (V.stride(0) == 1, ldv = V.stride(1) >= n) and w a 1-D one of length n with unit stride -> a
+    length-k device tensor; or numpy arrays (V in Fortran order, else copied to it) -> a numpy array."""
+    if isinstance(V, np.ndarray):
+        if V.ndim != 2 or not isinstance(w, np.ndarray) or w.shape != (V.shape[0],):
+            raise SpmvHipError("multi_dot: V must be (n, k) and w (n,)")
+        n, k = V.shape
+        hV, hw = np.asfortranarray(V, dtype=np.float64), np.ascontiguousarray(w, dtype=np.float64)
+        dV, dw, dh = DeviceBuffer(max(hV.nbytes, 8)), DeviceBuffer(max(hw.nbytes, 8)), DeviceBuffer(8 * max(k, 1))
+        try:
+            if n:
+                dV.up(hV.ravel(order="F"))
+                dw.up(hw)
+            _check(lib.spmvHipMultiDot(n, k, dV.ptr, n, dw.ptr, dh.ptr), "spmvHipMultiDot")
+            return dh.down(np.float64)[:k]
+        finally:
+            for d in (dV, dw, dh):
+                d.free()
+    import torch
+    for t, dim, what in ((V, 2, "V"), (w, 1, "w")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or not t.is_cuda or t.dim() != dim:
+            raise SpmvHipError(f"multi_dot: {what} must be a {dim}-D float64 torch tensor on the device")
+    n, k = V.shape
+    if w.numel() != n or (n > 1 and w.stride(0) != 1):
+        raise SpmvHipError(f"multi_dot: w must have length {n} and unit stride")
+    if (n > 1 and V.stride(0) != 1) or (k > 1 and V.stride(1) < n):
+        raise SpmvHipError(f"multi_dot: V needs contiguous columns (strides {V.stride()})")
+    out = torch.empty(k, dtype=torch.float64, device=V.device)
+    _check(lib.spmvHipMultiDot(n, k, V.data_ptr(), V.stride(1) if k > 1 else max(n, 1), w.data_ptr(), out.data_ptr()),
+           "spmvHipMultiDot")
     return out
 
 

@@ -188,6 +188,14 @@ int  enqueueDot(uint64_t n, const double* u, const double* v, double* result, hi
 void freeDotWorkspace();
 int  krylovSolve(int bicg, spmat* hA, const DevMat* a, const DevMat* m, const double* b, double* x, const spmvKrylovOpts* opts,
                  spmvKrylovInfo* info, uint32_t K, hipStream_t stream);
+// h = V^T w and restarted GMRES (gmres.hip; contract in spmvHip.h, design in DESIGN.md section 20).  enqueueMultiDot: k
+// fixed-order dots in one pass into k device doubles, partials in the dot workspace (grown to k blocks-of-n).  gmresSolve:
+// GMRES(restart) with CGS2 on the checked handles; fused != 0 folds the first update into the second projection's
+// partials; allocates gmresWorkspaceBytes, synchronous.
+int  enqueueMultiDot(uint64_t n, uint32_t k, const double* V, uint64_t ldv, const double* w, double* out, hipStream_t stream);
+size_t gmresWorkspaceBytes(uint64_t n, uint32_t restart, uint64_t maxIter, int precond, int history);
+int  gmresSolve(spmat* hA, const DevMat* a, const DevMat* m, const double* b, double* x, const spmvGmresOpts* opts,
+                spmvKrylovInfo* info, int fused, hipStream_t stream);
 int  enqueueGatherValues(double* val, const uint32_t* map, uint64_t n, const double* AS, hipStream_t stream);   // values.hip
 int  enqueueScatterValues(double* val, const uint32_t* map, uint64_t n, const double* AS, hipStream_t stream);
 int  enqueueSellValues(uint32_t nSlices, const uint64_t* sliceOff, const uint32_t* perm, const uint32_t* slen, const void* IRP,

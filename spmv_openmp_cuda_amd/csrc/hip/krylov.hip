@@ -23,14 +23,10 @@
 
 #include "spmvHip.h"
 #include "kernels.hpp"
+#include "krylov.hpp"
 
 namespace spmvhip {
 namespace {
-
-constexpr uint32_t KT = 256;                    // lanes of a block (partials) and of the finish workgroup
-constexpr uint32_t KB = 4096;                   // indices of a block
-constexpr uint32_t KSLICES = KB / (2 * KT);     // 8 slices of 512 indices, two per lane
-constexpr uint32_t KCHUNK = 4;                  // slices whose loads a lane issues together
 
 // the loop's scalars and its status (written only by the finish kernels, by one lane)
 struct KState {
@@ -43,35 +39,6 @@ struct KState {
 };
 
 enum Phase : int { F_DOT, F_CG_INIT, F_CG_RZ, F_CG_ALPHA, F_CG_RR, F_BI_INIT, F_BI_ALPHA, F_BI_SS, F_BI_OMEGA, F_BI_RR };
-
-template <bool VEC>
-__device__ __forceinline__ double2 ld2(const double* p, uint64_t i, bool two) {
-    if (VEC && two) return *reinterpret_cast<const double2*>(p + i);
-    return make_double2(p[i], two ? p[i + 1] : 0.0);
-}
-template <bool VEC>
-__device__ __forceinline__ void st2(double* p, uint64_t i, bool two, double2 v) {
-    if (VEC && two) { *reinterpret_cast<double2*>(p + i) = v; return; }
-    p[i] = v.x;
-    if (two) p[i + 1] = v.y;
-}
-// acc += a.x * b.x, then a.y * b.y when the pair is whole (a missing element adds nothing: acc is never -0.0)
-__device__ __forceinline__ void madd(double& acc, double2 a, double2 b, bool two) {
-    acc += a.x * b.x;
-    if (two) acc += a.y * b.y;
-}
-
-// ------------------------------------------------------------------------------------------------ the fused passes
-// Each op: NDOT dots whose partials it produces, mode(st) (0: write nothing; the stopped loop), load() the inputs of
-// one element pair, step() the update and the products in order.
-struct DotOp {                                  // u . v
-    static constexpr int NDOT = 1;
-    const double* u; const double* v;
-    struct R { double2 u, v; };
-    __device__ int mode(const KState*) const { return 1; }
-    template <bool VEC> __device__ void load(uint64_t i, bool two, R& r) const { r.u = ld2<VEC>(u, i, two); r.v = ld2<VEC>(v, i, two); }
-    template <bool VEC> __device__ void step(uint64_t, bool two, const R& r, double& a0, double&) const { madd(a0, r.u, r.v, two); }
-};
 
 struct GuardedDot : DotOp {                     // u . v inside a solve
     __device__ int mode(const KState* st) const { return !st->stop; }
@@ -86,21 +53,6 @@ struct TtTsOp {                                 // t . t and t . s
     template <bool VEC> __device__ void step(uint64_t, bool two, const R& r, double& a0, double& a1) const {
         madd(a0, r.t, r.t, two);
         madd(a1, r.t, r.s, two);
-    }
-};
-
-struct InitOp {                                 // r = b - q (rhat = r too when given); r . r and b . b
-    static constexpr int NDOT = 2;
-    const double* b; const double* q; double* r; double* rhat;
-    struct R { double2 b, q; };
-    __device__ int mode(const KState*) const { return 1; }
-    template <bool VEC> __device__ void load(uint64_t i, bool two, R& x) const { x.b = ld2<VEC>(b, i, two); x.q = ld2<VEC>(q, i, two); }
-    template <bool VEC> __device__ void step(uint64_t i, bool two, const R& x, double& a0, double& a1) const {
-        const double2 rv = make_double2(x.b.x - x.q.x, x.b.y - x.q.y);
-        st2<VEC>(r, i, two, rv);
-        if (rhat) st2<VEC>(rhat, i, two, rv);
-        madd(a0, rv, rv, two);
-        madd(a1, x.b, x.b, two);
     }
 };
 
@@ -198,53 +150,6 @@ struct BiUpdateOp {
     }
 };
 
-// the fixed tree over the 256 lanes of a workgroup: a[t] += a[t + h] for t < h, h = 128, 64, ..., 1; valid in lane 0
-__device__ __forceinline__ double2 tree256(double2 a, double2* sh) {
-    const uint32_t t = threadIdx.x;
-    sh[t] = a;
-    __syncthreads();
-#pragma unroll
-    for (uint32_t h = KT / 2; h >= 1; h >>= 1) {
-        if (t < h) {
-            const double2 o = sh[t + h], m = sh[t];
-            sh[t] = make_double2(m.x + o.x, m.y + o.y);
-        }
-        __syncthreads();
-    }
-    return sh[0];
-}
-
-// one block of KB indices: the op's update on them, and its dots' block partials into part0 / part1
-template <class Op, bool VEC>
-__global__ __launch_bounds__(KT) void krylov_vec_kernel(uint64_t n, const KState* __restrict__ st, Op op,
-                                                        double* __restrict__ part0, double* __restrict__ part1) {
-    __shared__ double2 sh[KT];
-    const uint64_t blk = linear_block();
-    if (blk * KB >= n || !op.mode(st)) return;                           // (a folded grid's tail); uniform: the state
-    const uint64_t base = blk * KB + 2 * threadIdx.x;
-    double a0 = 0.0, a1 = 0.0;
-#pragma unroll
-    for (uint32_t c = 0; c < KSLICES; c += KCHUNK) {
-        typename Op::R r[KCHUNK];
-#pragma unroll
-        for (uint32_t u = 0; u < KCHUNK; ++u) {
-            const uint64_t i = base + (uint64_t)(c + u) * (2 * KT);
-            if (i < n) op.template load<VEC>(i, i + 1 < n, r[u]);
-        }
-#pragma unroll
-        for (uint32_t u = 0; u < KCHUNK; ++u) {
-            const uint64_t i = base + (uint64_t)(c + u) * (2 * KT);
-            if (i < n) op.template step<VEC>(i, i + 1 < n, r[u], a0, a1);
-        }
-    }
-    if (Op::NDOT == 0) return;
-    const double2 s = tree256(make_double2(a0, a1), sh);
-    if (threadIdx.x == 0) {
-        part0[blk] = s.x;
-        if (Op::NDOT > 1) part1[blk] = s.y;
-    }
-}
-
 // the block partials of one or two dots, by the same rule: lane t adds partials t, t + 256, ... in order, then the tree.
 // Lane 0 then runs the loop's scalar step `ph` for iteration k.
 __global__ __launch_bounds__(KT) void krylov_finish_kernel(uint64_t nb, const double* __restrict__ part0,
@@ -333,36 +238,13 @@ __global__ __launch_bounds__(KT) void krylov_finish_kernel(uint64_t nb, const do
     }
 }
 
-uint64_t blocksOf(uint64_t n) { return (n + KB - 1) / KB; }
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
-template <class Op>
-void launchVec(uint64_t n, const KState* st, const Op& op, bool vec, double* p0, double* p1, hipStream_t s) {
-    const uint64_t nb = blocksOf(n);
-    if (!nb) return;
-    const dim3 grid = grid2d(nb, KT);
-    if (vec) hipLaunchKernelGGL((krylov_vec_kernel<Op, true>), grid, dim3(KT), 0, s, n, st, op, p0, p1);
-    else     hipLaunchKernelGGL((krylov_vec_kernel<Op, false>), grid, dim3(KT), 0, s, n, st, op, p0, p1);
-}
-
 void launchFinish(uint64_t n, const double* p0, const double* p1, int ph, uint64_t k, KState* st, double* hist, double* out,
                   int precond, hipStream_t s) {
     hipLaunchKernelGGL(krylov_finish_kernel, dim3(1), dim3(KT), 0, s, blocksOf(n), p0, p1, ph, k, st, hist, out, precond);
 }
 
 // the public dot's block partials: a library workspace, grown (synchronously) by the first call that needs more
-struct DotWorkspace { double* p = nullptr; uint64_t blocks = 0; int dev = -1; } g_dot;
-
-struct DevBufs {
-    std::vector<void*> ptrs;
-    ~DevBufs() { for (void* p : ptrs) (void)hipFree(p); }
-    template <typename T> T* alloc(size_t count) {
-        void* p = nullptr;
-        if (hipMalloc(&p, std::max<size_t>(count * sizeof(T), 16)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-        ptrs.push_back(p);
-        return static_cast<T*>(p);
-    }
-};
+struct DotWorkspace { double* p = nullptr; uint64_t blocks = 0; int dev = -1; } g_dot;   // blocks: doubles held
 
 }  // namespace
 
@@ -371,19 +253,26 @@ void freeDotWorkspace() {
     g_dot = DotWorkspace{};
 }
 
-int enqueueDot(uint64_t n, const double* u, const double* v, double* result, hipStream_t st) {
-    const uint64_t nb = blocksOf(n);
+int dotWorkspace(uint64_t doubles, double** p) {
+    doubles = std::max<uint64_t>(doubles, 1);
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
-    if (nb > g_dot.blocks || dev != g_dot.dev) {
+    if (doubles > g_dot.blocks || dev != g_dot.dev) {
         HIP_TRY(hipDeviceSynchronize());                                 // the old workspace may still be read
         freeDotWorkspace();
-        HIP_TRY(hipMalloc(&g_dot.p, std::max<uint64_t>(nb, 1) * sizeof(double)));
-        g_dot.blocks = std::max<uint64_t>(nb, 1);
+        HIP_TRY(hipMalloc(&g_dot.p, doubles * sizeof(double)));
+        g_dot.blocks = doubles;
         g_dot.dev = dev;
     }
-    launchVec(n, nullptr, DotOp{u, v}, aligned16(u) && aligned16(v), g_dot.p, nullptr, st);
-    launchFinish(n, g_dot.p, nullptr, F_DOT, 0, nullptr, nullptr, result, 0, st);
+    *p = g_dot.p;
+    return EXIT_SUCCESS;
+}
+
+int enqueueDot(uint64_t n, const double* u, const double* v, double* result, hipStream_t st) {
+    double* part = nullptr;
+    if (dotWorkspace(blocksOf(n), &part)) return EXIT_FAILURE;
+    launchVec(n, nullptr, DotOp{u, v}, aligned16(u) && aligned16(v), part, nullptr, st);
+    launchFinish(n, part, nullptr, F_DOT, 0, nullptr, nullptr, result, 0, st);
     return hipGetLastError() == hipSuccess ? EXIT_SUCCESS : EXIT_FAILURE;
 }
 

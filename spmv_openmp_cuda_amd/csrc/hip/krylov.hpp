@@ -1,0 +1,139 @@
+// krylov.hpp -- what the Krylov files (krylov.hip, gmres.hip) share: the blocks and lanes of the fixed-order dot, the
+// element-pair loads and stores, the fixed tree, the fused-pass kernel and its launcher, the workspace holder.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cstdint>
+#include <vector>
+
+#include "kernels.hpp"
+
+namespace spmvhip {
+namespace {
+
+struct KState;                                  // krylov.hip: the state block of CG / BiCGStab (gmres.hip passes none)
+
+constexpr uint32_t KT = 256;                    // lanes of a block (partials) and of the finish workgroup
+constexpr uint32_t KB = 4096;                   // indices of a block
+constexpr uint32_t KSLICES = KB / (2 * KT);     // 8 slices of 512 indices, two per lane
+constexpr uint32_t KCHUNK = 4;                  // slices whose loads a lane issues together
+
+template <bool VEC>
+__device__ __forceinline__ double2 ld2(const double* p, uint64_t i, bool two) {
+    if (VEC && two) return *reinterpret_cast<const double2*>(p + i);
+    return make_double2(p[i], two ? p[i + 1] : 0.0);
+}
+template <bool VEC>
+__device__ __forceinline__ void st2(double* p, uint64_t i, bool two, double2 v) {
+    if (VEC && two) { *reinterpret_cast<double2*>(p + i) = v; return; }
+    p[i] = v.x;
+    if (two) p[i + 1] = v.y;
+}
+// acc += a.x * b.x, then a.y * b.y when the pair is whole (a missing element adds nothing: acc is never -0.0)
+__device__ __forceinline__ void madd(double& acc, double2 a, double2 b, bool two) {
+    acc += a.x * b.x;
+    if (two) acc += a.y * b.y;
+}
+
+// ------------------------------------------------------------------------------------------------ the fused passes
+// Each op: NDOT dots whose partials it produces, mode(st) (0: write nothing; the stopped loop), load() the inputs of
+// one element pair, step() the update and the products in order.
+struct DotOp {                                  // u . v
+    static constexpr int NDOT = 1;
+    const double* u; const double* v;
+    struct R { double2 u, v; };
+    __device__ int mode(const KState*) const { return 1; }
+    template <bool VEC> __device__ void load(uint64_t i, bool two, R& r) const { r.u = ld2<VEC>(u, i, two); r.v = ld2<VEC>(v, i, two); }
+    template <bool VEC> __device__ void step(uint64_t, bool two, const R& r, double& a0, double&) const { madd(a0, r.u, r.v, two); }
+};
+
+struct InitOp {                                 // r = b - q (rhat = r too when given); r . r and b . b
+    static constexpr int NDOT = 2;
+    const double* b; const double* q; double* r; double* rhat;
+    struct R { double2 b, q; };
+    __device__ int mode(const KState*) const { return 1; }
+    template <bool VEC> __device__ void load(uint64_t i, bool two, R& x) const { x.b = ld2<VEC>(b, i, two); x.q = ld2<VEC>(q, i, two); }
+    template <bool VEC> __device__ void step(uint64_t i, bool two, const R& x, double& a0, double& a1) const {
+        const double2 rv = make_double2(x.b.x - x.q.x, x.b.y - x.q.y);
+        st2<VEC>(r, i, two, rv);
+        if (rhat) st2<VEC>(rhat, i, two, rv);
+        madd(a0, rv, rv, two);
+        madd(a1, x.b, x.b, two);
+    }
+};
+
+// the fixed tree over the 256 lanes of a workgroup: a[t] += a[t + h] for t < h, h = 128, 64, ..., 1; valid in lane 0
+__device__ __forceinline__ double2 tree256(double2 a, double2* sh) {
+    const uint32_t t = threadIdx.x;
+    sh[t] = a;
+    __syncthreads();
+#pragma unroll
+    for (uint32_t h = KT / 2; h >= 1; h >>= 1) {
+        if (t < h) {
+            const double2 o = sh[t + h], m = sh[t];
+            sh[t] = make_double2(m.x + o.x, m.y + o.y);
+        }
+        __syncthreads();
+    }
+    return sh[0];
+}
+
+// one block of KB indices: the op's update on them, and its dots' block partials into part0 / part1
+template <class Op, bool VEC>
+__global__ __launch_bounds__(KT) void krylov_vec_kernel(uint64_t n, const KState* __restrict__ st, Op op,
+                                                        double* __restrict__ part0, double* __restrict__ part1) {
+    __shared__ double2 sh[KT];
+    const uint64_t blk = linear_block();
+    if (blk * KB >= n || !op.mode(st)) return;                           // (a folded grid's tail); uniform: the state
+    const uint64_t base = blk * KB + 2 * threadIdx.x;
+    double a0 = 0.0, a1 = 0.0;
+#pragma unroll
+    for (uint32_t c = 0; c < KSLICES; c += KCHUNK) {
+        typename Op::R r[KCHUNK];
+#pragma unroll
+        for (uint32_t u = 0; u < KCHUNK; ++u) {
+            const uint64_t i = base + (uint64_t)(c + u) * (2 * KT);
+            if (i < n) op.template load<VEC>(i, i + 1 < n, r[u]);
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < KCHUNK; ++u) {
+            const uint64_t i = base + (uint64_t)(c + u) * (2 * KT);
+            if (i < n) op.template step<VEC>(i, i + 1 < n, r[u], a0, a1);
+        }
+    }
+    if (Op::NDOT == 0) return;
+    const double2 s = tree256(make_double2(a0, a1), sh);
+    if (threadIdx.x == 0) {
+        part0[blk] = s.x;
+        if (Op::NDOT > 1) part1[blk] = s.y;
+    }
+}
+
+uint64_t blocksOf(uint64_t n) { return (n + KB - 1) / KB; }
+bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+template <class Op>
+void launchVec(uint64_t n, const KState* st, const Op& op, bool vec, double* p0, double* p1, hipStream_t s) {
+    const uint64_t nb = blocksOf(n);
+    if (!nb) return;
+    const dim3 grid = grid2d(nb, KT);
+    if (vec) hipLaunchKernelGGL((krylov_vec_kernel<Op, true>), grid, dim3(KT), 0, s, n, st, op, p0, p1);
+    else     hipLaunchKernelGGL((krylov_vec_kernel<Op, false>), grid, dim3(KT), 0, s, n, st, op, p0, p1);
+}
+
+struct DevBufs {
+    std::vector<void*> ptrs;
+    ~DevBufs() { for (void* p : ptrs) (void)hipFree(p); }
+    template <typename T> T* alloc(size_t count) {
+        void* p = nullptr;
+        if (hipMalloc(&p, std::max<size_t>(count * sizeof(T), 16)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+        ptrs.push_back(p);
+        return static_cast<T*>(p);
+    }
+};
+
+}  // namespace
+// the library's dot workspace (krylov.hip): at least `doubles` doubles on the current device, grown (device
+// synchronisation, allocation) when a call needs more than any earlier one
+int dotWorkspace(uint64_t doubles, double** p);
+}  // namespace spmvhip

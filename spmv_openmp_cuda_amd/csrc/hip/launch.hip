@@ -541,19 +541,32 @@ int spmvHipDot(size_t n, const double* dU, const double* dV, double* dResult) {
     return L.finish(who);
 }
 
-static int krylov(int bicg, spmat* dA, spmat* dM, const double* dB, double* dX, const spmvKrylovOpts* opts, spmvKrylovInfo* info) {
-    const char* who = bicg ? "hipSpBiCGStabCSR" : "hipSpCGCSR";
+int spmvHipMultiDot(size_t n, unsigned k, const double* dV, size_t ldv, const double* dW, double* dH) {
+    const char* who = "spmvHipMultiDot";
+    const Ctx cx = libraryCtx();
     if (!ready(who)) return EXIT_FAILURE;
-    if (!dB || !dX || !opts) { ERR("%s: %s is NULL", who, !dB ? "dB" : !dX ? "dX" : "opts"); return EXIT_FAILURE; }
+    if (!dH || (n && (!dV || !dW))) { ERR("%s: %s is NULL", who, !dH ? "dH" : !dV ? "dV" : "dW"); return EXIT_FAILURE; }
+    if (k == 0) { ERR("%s: k = 0 columns", who); return EXIT_FAILURE; }
+    if (ldv < n) { ERR("%s: ldv=%zu < n=%zu", who, ldv, n); return EXIT_FAILURE; }
+    Launch L(cx, dim3((k + 1) / 2), dim3(256));
+    if (enqueueMultiDot(n, k, dV, ldv, dW, dH, cx.stream)) { ERR("%s: launch failed", who); return EXIT_FAILURE; }
+    return L.finish(who);
+}
+
+// what the three solvers check alike: 0 go on (a, m set), 1 refused, 2 done (M = 0)
+static int krylovArgs(const char* who, spmat* dA, spmat* dM, const double* dB, double* dX, const void* optsPtr, double tol, ulong maxIter,
+                      double* history, spmvKrylovInfo* info, DevMat** pa, DevMat** pm) {
+    if (!ready(who)) return EXIT_FAILURE;
+    if (!dB || !dX || !optsPtr) { ERR("%s: %s is NULL", who, !dB ? "dB" : !dX ? "dX" : "opts"); return EXIT_FAILURE; }
     DevMat* a = csrOf(dA, who, "dA is an ELL handle (only CSR handles are solved)");
     if (!a) return EXIT_FAILURE;
     if (a->M != a->N) { ERR("%s: M=%lu != N=%lu: dA is not square", who, (unsigned long)a->M, (unsigned long)a->N); return EXIT_FAILURE; }
     if (a->NZ && !a->AS && !a->unit) { ERR("%s: dA has no value array", who); return EXIT_FAILURE; }
     const uintptr_t b0 = (uintptr_t)dB, x0 = (uintptr_t)dX, bytes = a->M * sizeof(double);
     if (a->M && b0 < x0 + bytes && x0 < b0 + bytes) { ERR("%s: dB and dX overlap", who); return EXIT_FAILURE; }
-    if (!(opts->tol >= 0.0)) { ERR("%s: tol %g is negative or NaN", who, opts->tol); return EXIT_FAILURE; }
-    if (opts->history && opts->maxIter >= (SIZE_MAX / sizeof(double)) - 1) {
-        ERR("%s: a history of maxIter + 1 = %lu + 1 doubles does not fit", who, (unsigned long)opts->maxIter);
+    if (!(tol >= 0.0)) { ERR("%s: tol %g is negative or NaN", who, tol); return EXIT_FAILURE; }
+    if (history && maxIter >= (SIZE_MAX / sizeof(double)) - 1) {
+        ERR("%s: a history of maxIter + 1 = %lu + 1 doubles does not fit", who, (unsigned long)maxIter);
         return EXIT_FAILURE;
     }
     DevMat* m = nullptr;
@@ -570,14 +583,38 @@ static int krylov(int bicg, spmat* dA, spmat* dM, const double* dB, double* dX, 
         }
     }
     if (a->M == 0) {
-        if (opts->history) opts->history[0] = 0.0;
+        if (history) history[0] = 0.0;
         if (info) *info = spmvKrylovInfo{SPMV_KRYLOV_CONVERGED, 0, 0.0, 0.0, 0, 0, 0.0};
-        return EXIT_SUCCESS;
+        return 2;
     }
+    *pa = a;
+    *pm = m;
+    return 0;
+}
+
+static int krylov(int bicg, spmat* dA, spmat* dM, const double* dB, double* dX, const spmvKrylovOpts* opts, spmvKrylovInfo* info) {
+    const char* who = bicg ? "hipSpBiCGStabCSR" : "hipSpCGCSR";
+    DevMat* a = nullptr;
+    DevMat* m = nullptr;
+    const int rc = krylovArgs(who, dA, dM, dB, dX, opts, opts ? opts->tol : 0.0, opts ? opts->maxIter : 0, opts ? opts->history : nullptr, info, &a, &m);
+    if (rc) return rc == 2 ? EXIT_SUCCESS : EXIT_FAILURE;
     if (krylovSolve(bicg, dA, a, m, dB, dX, opts, info, S.krylovK[bicg], S.stream)) { ERR("%s: the solve failed", who); return EXIT_FAILURE; }
     return EXIT_SUCCESS;
 }
 int hipSpCGCSR(spmat* dA, spmat* dM, const double* dB, double* dX, const spmvKrylovOpts* opts, spmvKrylovInfo* info) { return krylov(0, dA, dM, dB, dX, opts, info); }
 int hipSpBiCGStabCSR(spmat* dA, spmat* dM, const double* dB, double* dX, const spmvKrylovOpts* opts, spmvKrylovInfo* info) { return krylov(1, dA, dM, dB, dX, opts, info); }
+int hipSpGMRESCSR(spmat* dA, spmat* dM, const double* dB, double* dX, const spmvGmresOpts* opts, spmvKrylovInfo* info) {
+    const char* who = "hipSpGMRESCSR";
+    if (opts && (opts->restart == 0 || opts->restart > 64)) {
+        if (ready(who)) ERR("%s: restart %u is not in 1 .. 64", who, opts->restart);
+        return EXIT_FAILURE;
+    }
+    DevMat* a = nullptr;
+    DevMat* m = nullptr;
+    const int rc = krylovArgs(who, dA, dM, dB, dX, opts, opts ? opts->tol : 0.0, opts ? opts->maxIter : 0, opts ? opts->history : nullptr, info, &a, &m);
+    if (rc) return rc == 2 ? EXIT_SUCCESS : EXIT_FAILURE;
+    if (gmresSolve(dA, a, m, dB, dX, opts, info, S.gmresFused, S.stream)) { ERR("%s: the solve failed", who); return EXIT_FAILURE; }
+    return EXIT_SUCCESS;
+}
 
 }  // extern "C"
