@@ -388,6 +388,70 @@ typedef struct {
 } spmvGmresOpts;
 int spmvHipMultiDot(size_t n, unsigned k, const double* dV, size_t ldv, const double* dW, double* dH);
 int hipSpGMRESCSR(spmat* dA, spmat* dM, const double* dB, double* dX, const spmvGmresOpts* opts, spmvKrylovInfo* info);
+/* ------------------------------------------------------------- multi-colour ordering, symmetric permutation */
+/* Reordering for fewer level sets: if rows of one colour share no entry and the matrix is permuted so that colours are
+ * contiguous, both triangles of B = P A P^T have at most as many level sets as there are colours, and hipSpTRSVCSR /
+ * hipSpILU0CSR on B run that many launches.  The caller permutes (A, b), solves with B, and permutes x back; every other
+ * contract of this header applies to B's arrays unchanged.  DESIGN.md section 21.
+ *
+ * spmvHipColourCSR colours the vertices of a square CSR handle.  The result is a function of the PATTERN and the options
+ *   alone -- not of the run, the grid or the order in which lanes finish -- and is the output of this loop:
+ *       adj(i) = { j != i : row i stores column j, or row j stores column i }     (the pattern of A + A^T: repeats count
+ *                                                     once, the diagonal is ignored, rows need not be sorted)
+ *       key(i) = 0 for SPMV_COLOUR_NATURAL,  fmix32(i ^ seed) for SPMV_COLOUR_HASH, with the murmur3 finaliser
+ *                fmix32(h): h ^= h>>16; h *= 0x85ebca6b; h ^= h>>13; h *= 0xc2b2ae35; h ^= h>>16      (32-bit)
+ *       j wins against i:  NATURAL  j < i;   HASH  (key(j), j) > (key(i), i) as pairs
+ *       for i in the order in which every vertex comes after all that win against it
+ *                (NATURAL: 0, 1, .. M-1;  HASH: descending (key, id)):
+ *           colour[i] = the smallest c >= 0 that no j in adj(i) winning against i has as colour[j]
+ *   NATURAL is first-fit in row order: red-black on a bipartite stencil, but as many rounds as the longest ascending path.
+ *   HASH takes more colours and few rounds.  opts == NULL: NATURAL, seed 0.
+ *   dColour[i] = that colour (M words).  dPerm = the rows ordered by (colour, id): dPerm[new] = old (M words), the
+ *   argument of spmvHipCsrPermute / spmvHipVecPermute.  Either may be NULL.  Column ids >= M of an adopted array are no
+ *   vertices and are skipped.
+ *   info: colours (largest colour + 1), rounds (launch rounds until no row was left; the only figure that may differ from
+ *   run to run), hostChecks (read-backs of the device state: one per K rounds, K = 16 unless
+ *   spmvHipSetVariant("spmvHipColourCSR", K)), maxColourRows (rows of the largest colour), longRows (rows with more than 64
+ *   adjacency entries: one wavefront each), symmetric (1: the stored pattern was found symmetric and the transposed
+ *   pattern was not built; tried when no row stores more than 64 entries), ms (wall time of the call).
+ *   Synchronous on the library stream; allocates, so not capturable; temporaries (the transposed pattern 8 B/nnz + 4 B/row,
+ *   row lists 16 B/row, the sorts' workspaces) are freed before it returns.  M = 0 succeeds with colours = 0, nothing written.
+ * spmvHipCsrPermute writes into dB a new, independent CSR handle of B = P A P^T for ANY permutation dPerm (dPerm[new] =
+ *   old; a caller's RCM as well): with inv[dPerm[r]] = r, row r of B holds the entries of row dPerm[r] of A, each column j
+ *   as inv[j].  Order inside a row: ascending new column, STABLE for repeated columns, which keep A's stored order -- so a
+ *   sorted, repeat-free A gives a B that hipSpILU0CSR accepts.  Values move as bits (NaN payloads, -0.0).  dB is like a
+ *   transpose handle: u32 columns, 4-byte row pointers, its own unit detection, every CSR entry point works on it, freed
+ *   with hipFreeSpmat; it keeps a 4 B/nnz source-position map.  The library checks on the device that dPerm is a
+ *   permutation of 0..M-1 before anything of dB is made.  Build temporaries (20 B/nnz + 4 B/row + the sort's workspace) are
+ *   freed before it returns; synchronous, not capturable.
+ * spmvHipPermuteRefresh gathers B's values from dA's current value array through that map, then does what
+ *   spmvHipValuesChanged(dB) does.  dB records its source's id and refuses any other source, as spmvHipTransposeRefresh.
+ * spmvHipVecPermute: inverse == 0: dOut[r] = dIn[dPerm[r]] (b' = P b); inverse != 0: dOut[dPerm[r]] = dIn[r] (x = P^T x').
+ *   Bits are copied.  One kernel on the library stream, no allocation: capturable; honours spmvHipSetSync; any 8-byte
+ *   alignment.  An entry of dPerm >= n is skipped (nothing is read or written for it).
+ * Refused with a message and EXIT_FAILURE, outputs untouched: NULL pointers (dColour, dPerm of spmvHipColourCSR, opts and
+ *   info excepted); a handle that is not live; ELL handles; M != N; M >= 2^31 or NZ >= IRP32_LIMIT; dB == dA; a dPerm
+ *   with a value >= M or a repeated value; a source column id >= M; an unknown order; a refresh of a handle that is not a
+ *   permutation, or from a handle that is not its source; dIn == dOut or overlapping. */
+#define SPMV_COLOUR_NATURAL 0
+#define SPMV_COLOUR_HASH    1
+typedef struct {
+    int      order;         /* SPMV_COLOUR_NATURAL or SPMV_COLOUR_HASH                        */
+    uint32_t seed;          /* of the HASH keys                                              */
+} spmvColourOpts;
+typedef struct {
+    ulong  colours;         /* largest colour + 1                                            */
+    ulong  rounds;          /* rounds until every row had its colour                         */
+    ulong  hostChecks;      /* read-backs of the device state                                */
+    ulong  maxColourRows;   /* rows of the largest colour class                              */
+    ulong  longRows;        /* rows coloured by a wavefront each                             */
+    int    symmetric;       /* 1: stored pattern symmetric, transposed pattern not built     */
+    double ms;              /* wall time of the call                                         */
+} spmvColourInfo;
+int spmvHipColourCSR(spmat* dA, const spmvColourOpts* opts, uint32_t* dColour, uint32_t* dPerm, spmvColourInfo* info);
+int spmvHipCsrPermute(spmat* dA, const uint32_t* dPerm, spmat* dB);
+int spmvHipPermuteRefresh(spmat* dB, spmat* dA);
+int spmvHipVecPermute(size_t n, const uint32_t* dPerm, const double* dIn, double* dOut, int inverse);
 /* Release the device arrays behind a handle (cudaUtils.h:70-78). */
 int hipFreeSpmat(spmat* dMat);
 
@@ -638,6 +702,8 @@ int spmvHipProbeLdsAtomicOrder(void);
  *                             (default 16).  x does not change by a bit.
  *   hipSpGMRESCSR             0 or 1: 1 folds the first CGS2 update into the partials of the second projection
  *                             (default 0).  x does not change by a bit.
+ *   spmvHipColourCSR          K, 1..4096: rounds enqueued per read-back of the colouring's device state (default 16,
+ *                             unmeasured).  No colour changes.
  * Returns EXIT_FAILURE for an unknown (launcher, variant). */
 int spmvHipSetVariant(const char* launcher, int variant);
 /* Use the RL array for ELL early exit (1, default when RL was uploaded) or walk

@@ -110,6 +110,10 @@ _sigs = {
     "hipSpBiCGStabCSR": ([C.POINTER(spmat), C.POINTER(spmat), _vp, _vp, _vp, _vp], _i),
     "spmvHipMultiDot": ([_sz, C.c_uint, _vp, _sz, _vp, _vp], _i),
     "hipSpGMRESCSR": ([C.POINTER(spmat), C.POINTER(spmat), _vp, _vp, _vp, _vp], _i),
+    "spmvHipColourCSR": ([C.POINTER(spmat), _vp, _vp, _vp, _vp], _i),
+    "spmvHipCsrPermute": ([C.POINTER(spmat), _vp, C.POINTER(spmat)], _i),
+    "spmvHipPermuteRefresh": ([C.POINTER(spmat), C.POINTER(spmat)], _i),
+    "spmvHipVecPermute": ([_sz, _vp, _vp, _vp, _i], _i),
 }
 SPMV_DENSE_ROW_MAJOR, SPMV_DENSE_COL_MAJOR = 0, 1          # include/spmvHip.h: layouts of hipSpMMRowsCSR's X and Y
 SPMV_TRI_LOWER, SPMV_TRI_UPPER = 0, 1                      # include/spmvHip.h: hipSpTRSVCSR's uplo ...
@@ -179,6 +183,19 @@ class spmvKrylovInfo(C.Structure):
                 ("hostChecks", C.c_ulong), ("ms", C.c_double)]
 
 
+class spmvColourOpts(C.Structure):
+    """include/spmvHip.h `spmvColourOpts`: the order of the colouring and the seed of the HASH keys."""
+    _fields_ = [("order", _i), ("seed", C.c_uint32)]
+
+
+class spmvColourInfo(C.Structure):
+    """include/spmvHip.h `spmvColourInfo`: what a spmvHipColourCSR call did."""
+    _fields_ = [("colours", C.c_ulong), ("rounds", C.c_ulong), ("hostChecks", C.c_ulong), ("maxColourRows", C.c_ulong),
+                ("longRows", C.c_ulong), ("symmetric", _i), ("ms", C.c_double)]
+
+
+SPMV_COLOUR_NATURAL, SPMV_COLOUR_HASH = 0, 1
+COLOUR_ORDERS = {"natural": SPMV_COLOUR_NATURAL, "hash": SPMV_COLOUR_HASH}
 SPMV_KRYLOV_CONVERGED, SPMV_KRYLOV_MAXITER, SPMV_KRYLOV_BREAKDOWN, SPMV_KRYLOV_NONFINITE = 0, 1, 2, 3
 KRYLOV_STATUS = {0: "converged", 1: "maxiter", 2: "breakdown", 3: "nonfinite"}
 
@@ -443,6 +460,59 @@ class DeviceMatrix:
         was transposed from), then refreshes its formats as values_changed() does."""
         _check(lib.spmvHipTransposeRefresh(C.byref(self.handle), C.byref(source.handle)), "spmvHipTransposeRefresh")
 
+    def colour(self, order="natural", seed=0, want_colours=False, as_torch=False) -> "Colouring":
+        """spmvHipColourCSR: a multi-colour ordering of this square matrix, a function of its pattern and (order, seed) alone
+        (include/spmvHip.h states the loop).  Returns a Colouring: `perm` (rows by (colour, id), perm[new] = old: the
+        argument of permute() and permute_vector()), `colours` (per row, when want_colours), `info` (spmvColourInfo) and
+        free().  perm / colours are DeviceBuffers of uint32, or int32 device torch tensors with as_torch=True."""
+        if order not in COLOUR_ORDERS:
+            raise SpmvHipError(f"colour: order must be one of {sorted(COLOUR_ORDERS)}, not {order!r}")
+        M = int(self.handle.M)
+        opts, info = spmvColourOpts(COLOUR_ORDERS[order], int(seed) & 0xFFFFFFFF), spmvColourInfo()
+        if as_torch:
+            import torch
+            perm = torch.empty(M, dtype=torch.int32, device="cuda")
+            colours = torch.empty(M, dtype=torch.int32, device="cuda") if want_colours else None
+        else:
+            perm = DeviceBuffer(4 * M)
+            colours = DeviceBuffer(4 * M) if want_colours else None
+        try:
+            _check(lib.spmvHipColourCSR(C.byref(self.handle), C.byref(opts), _dev_ptr(colours), _dev_ptr(perm), C.byref(info)),
+                   "spmvHipColourCSR")
+        except SpmvHipError:
+            for b in (perm, colours):
+                if isinstance(b, DeviceBuffer):
+                    b.free()
+            raise
+        return Colouring(perm, colours, info)
+
+    def permute(self, perm) -> "DeviceMatrix":
+        """spmvHipCsrPermute: B = P A P^T as a new DeviceMatrix that owns its handle; row r of B is row perm[r] of this
+        matrix, columns renumbered alike and sorted ascending (stable for repeats).  perm: a Colouring, a DeviceBuffer of
+        M uint32, an int32 device torch tensor, or a numpy array (uploaded for the call)."""
+        M = int(self.handle.M)
+        perm = perm.perm if isinstance(perm, Colouring) else perm
+        tmp = None
+        if isinstance(perm, np.ndarray):
+            if perm.shape != (M,):
+                raise SpmvHipError(f"permute: perm must have shape ({M},), not {perm.shape}")
+            perm = tmp = DeviceBuffer(4 * M).up(np.ascontiguousarray(perm, dtype=np.uint32))
+        elif _perm_len(perm, "permute") != M:
+            raise SpmvHipError(f"permute: perm must hold {M} entries")
+        b = DeviceMatrix()
+        try:
+            _check(lib.spmvHipCsrPermute(C.byref(self.handle), _dev_ptr(perm), C.byref(b.handle)), "spmvHipCsrPermute")
+        finally:
+            if tmp is not None:
+                tmp.free()
+        b.rows = int(b.handle.M)
+        return b
+
+    def permute_refresh(self, source: "DeviceMatrix"):
+        """spmvHipPermuteRefresh: this permuted matrix takes `source`'s current device values (source must be the matrix it
+        was permuted from), then refreshes its formats as values_changed() does."""
+        _check(lib.spmvHipPermuteRefresh(C.byref(self.handle), C.byref(source.handle)), "spmvHipPermuteRefresh")
+
     def matmul(self, X, out=None):
         """hipSpMMRowsCSR: Y = A X, column c of Y bit-identical to sgemvSerial on column c of X.  X is (N, k) float64:
         a device torch tensor with unit stride in one dimension (a contiguous tensor is row-major, a `.t()` view of a
@@ -605,6 +675,75 @@ class DeviceMatrix:
             self.free()
         except Exception:
             pass
+
+
+class Colouring:
+    """What DeviceMatrix.colour() returns: the device arrays `perm` and `colours` (None unless asked for) and `info`."""
+
+    def __init__(self, perm, colours, info):
+        self.perm, self.colours, self.info = perm, colours, info
+
+    def free(self):
+        for b in (self.perm, self.colours):
+            if isinstance(b, DeviceBuffer):
+                b.free()
+        self.perm = self.colours = None
+
+
+def _dev_ptr(b):
+    """the device address of a DeviceBuffer or a torch tensor (None stays None)"""
+    if b is None:
+        return None
+    return b.ptr if isinstance(b, DeviceBuffer) else C.c_void_p(b.data_ptr())
+
+
+def _perm_len(perm, who):
+    """entries of a device permutation: a DeviceBuffer of uint32 or a contiguous int32 torch tensor on the device"""
+    if isinstance(perm, DeviceBuffer):
+        return perm.nbytes // 4
+    try:
+        import torch
+    except ImportError:
+        torch = None
+    if torch is None or not isinstance(perm, torch.Tensor) or perm.dtype != torch.int32 or not perm.is_cuda or perm.dim() != 1 \
+            or not perm.is_contiguous():
+        raise SpmvHipError(f"{who}: perm must be a DeviceBuffer of uint32 or a contiguous 1-D int32 torch tensor on the device")
+    return perm.numel()
+
+
+def permute_vector(perm, v, inverse=False, out=None):
+    """spmvHipVecPermute: forward out[r] = v[perm[r]] (b' = P b), inverse out[perm[r]] = v[r] (x = P^T x'); bits are copied.
+    perm: a Colouring, a DeviceBuffer of uint32 or an int32 device torch tensor.  v: a 1-D float64 device torch tensor with
+    unit stride (any element offset) -> a torch tensor, `out` if given (same rules, not v itself); or a numpy array ->
+    uploaded, permuted, returned as numpy.  Runs on the library stream."""
+    perm = perm.perm if isinstance(perm, Colouring) else perm
+    n = _perm_len(perm, "permute_vector")
+    if isinstance(v, np.ndarray):
+        if out is not None:
+            raise SpmvHipError("permute_vector: `out` is for torch tensors")
+        if v.shape != (n,):
+            raise SpmvHipError(f"permute_vector: v must have shape ({n},), not {v.shape}")
+        hv = np.ascontiguousarray(v, dtype=np.float64)
+        dv, do = DeviceBuffer(hv.nbytes).up(hv), DeviceBuffer(hv.nbytes)
+        try:
+            _check(lib.spmvHipVecPermute(n, _dev_ptr(perm), dv.ptr, do.ptr, 1 if inverse else 0), "spmvHipVecPermute")
+            return do.down(np.float64)
+        finally:
+            dv.free()
+            do.free()
+    import torch
+    for t, what in ((v, "v"), (out, "out")):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or not t.is_cuda or t.dim() != 1 or \
+                (t.numel() > 1 and t.stride(0) != 1):
+            raise SpmvHipError(f"permute_vector: {what} must be a 1-D float64 torch tensor on the device with unit stride")
+        if t.numel() != n:
+            raise SpmvHipError(f"permute_vector: {what} must have length {n}, not {t.numel()}")
+    if out is None:
+        out = torch.empty(n, dtype=torch.float64, device=v.device)
+    _check(lib.spmvHipVecPermute(n, _dev_ptr(perm), v.data_ptr(), out.data_ptr(), 1 if inverse else 0), "spmvHipVecPermute")
+    return out
 
 
 def _dense_layout(t, what):

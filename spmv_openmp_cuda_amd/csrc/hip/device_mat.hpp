@@ -93,8 +93,10 @@ struct DevMat {
     spmvUpdateInfo lastUpdate{};    // what the last spmvHipUpdateValues / spmvHipValuesChanged did
     // a transpose built by spmvHipCsrTranspose (transpose.hip): the id of its source and, for every entry p of this
     // handle, the CSR position of the same entry in the source (ASt[p] = AS[tmap[p]]); no pointer to the source is kept
-    uint64_t  srcId = 0;            // 0: not a transpose
+    uint64_t  srcId = 0;            // 0: neither a transpose nor a permutation
     uint32_t* tmap = nullptr;
+    // ... and so has a permutation built by spmvHipCsrPermute (colour.hip): the same id and map, refreshed by its own call
+    bool      permuted = false;
     // the level-set schedules of the triangular solve (trsv.hip), [SPMV_TRI_LOWER] and [SPMV_TRI_UPPER]: built from the
     // pattern at the first solve or by spmvHipTriAnalyse, kept across value updates (the solve reads AS live)
     TriSchedule* tri[2] = {nullptr, nullptr};
@@ -165,6 +167,16 @@ int  transposeCsr(const DevMat* a, DevMat* t, hipStream_t stream);
 // keys that is >= c, for c in [0, N] (keys >= N clamp to N); rowOf[p] = the row of CSR position p
 void enqueueSortedBounds(uint64_t nnz, uint64_t N, const uint32_t* keys, uint32_t* ptr, hipStream_t stream);
 void enqueueRowOf(uint64_t M, const void* IRP, int irpBytes, uint32_t* rowOf, hipStream_t stream);
+// Multi-colour ordering and symmetric permutation (colour.hip; contracts in spmvHip.h, design in DESIGN.md section 21).
+// colourCsr: the colours and the (colour, id) order of the checked square handle, K rounds per host check; dColour / dPerm
+// may be null; synchronous, allocates, temporaries freed before it returns.  invertPerm: inv = perm^-1 into the caller's M
+// words, *bad != 0 when perm is no permutation of 0..M-1 (synchronous).  permuteCsr: B = P A P^T into t, whose IRP (4 B), JA,
+// AS and tmap the caller has allocated for M + 1 rows / NZ entries, as transposeCsr.  enqueueVecPermute: kernels only.
+int  colourCsr(const DevMat* a, int order, uint32_t seed, uint32_t K, uint32_t* dColour, uint32_t* dPerm, spmvColourInfo* info,
+               hipStream_t stream);
+int  invertPerm(uint64_t M, const uint32_t* perm, uint32_t* inv, uint32_t* bad, hipStream_t stream);
+int  permuteCsr(const DevMat* a, const uint32_t* inv, DevMat* t, hipStream_t stream);
+int  enqueueVecPermute(uint64_t n, const uint32_t* perm, const double* in, double* out, int inverse, hipStream_t stream);
 // Triangular solves (trsv.hip; contract in spmvHip.h, design in DESIGN.md section 17).  triAnalyse builds d->tri[uplo]
 // (synchronous, allocates, temporaries freed before it returns; runThreshold = the T of the single-workgroup runs, 0: none);
 // enqueueTrsv enqueues one solve of an analysed triangle on `stream` (no allocation, no sync) and reports the last launch;

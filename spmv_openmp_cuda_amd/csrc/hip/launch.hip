@@ -530,6 +530,30 @@ int spmvHipIlu0Info(spmat* dA, spmvIluInfo* info) {
     return EXIT_SUCCESS;
 }
 
+// ---- multi-colour ordering and vector permutation (colour.hip; the contract is in spmvHip.h, the design in DESIGN.md section 21)
+int spmvHipColourCSR(spmat* dA, const spmvColourOpts* opts, uint32_t* dColour, uint32_t* dPerm, spmvColourInfo* info) {
+    const char* who = "spmvHipColourCSR";
+    DevMat* d = triHandle(dA, SPMV_TRI_LOWER, who);          // ready, live, CSR, square, 32-bit rows and positions
+    if (!d) return EXIT_FAILURE;
+    const int order = opts ? opts->order : SPMV_COLOUR_NATURAL;
+    if (order != SPMV_COLOUR_NATURAL && order != SPMV_COLOUR_HASH) { ERR("%s: unknown order %d", who, order); return EXIT_FAILURE; }
+    if (colourCsr(d, order, opts ? opts->seed : 0u, S.colourK, dColour, dPerm, info, S.stream)) { ERR("%s: the colouring failed", who); return EXIT_FAILURE; }
+    return EXIT_SUCCESS;
+}
+
+int spmvHipVecPermute(size_t n, const uint32_t* dPerm, const double* dIn, double* dOut, int inverse) {
+    const char* who = "spmvHipVecPermute";
+    const Ctx cx = libraryCtx();
+    if (!ready(who)) return EXIT_FAILURE;
+    if (n && (!dPerm || !dIn || !dOut)) { ERR("%s: %s is NULL", who, !dPerm ? "dPerm" : !dIn ? "dIn" : "dOut"); return EXIT_FAILURE; }
+    if (n >= (1ull << 32)) { ERR("%s: n=%zu does not fit the 32-bit ids of a permutation", who, n); return EXIT_FAILURE; }
+    const uintptr_t i0 = (uintptr_t)dIn, o0 = (uintptr_t)dOut, bytes = n * sizeof(double);
+    if (n && i0 < o0 + bytes && o0 < i0 + bytes) { ERR("%s: dIn and dOut are the same vector or overlap", who); return EXIT_FAILURE; }
+    Launch L(cx, grid2d((n + 255) / 256, 256), dim3(256));
+    if (enqueueVecPermute(n, dPerm, dIn, dOut, inverse != 0, cx.stream)) { ERR("%s: launch failed", who); return EXIT_FAILURE; }
+    return L.finish(who);
+}
+
 // ---- Krylov solves (krylov.hip runs them; the contract is in spmvHip.h, the design in DESIGN.md section 19)
 int spmvHipDot(size_t n, const double* dU, const double* dV, double* dResult) {
     const char* who = "spmvHipDot";

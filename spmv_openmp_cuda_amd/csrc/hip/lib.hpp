@@ -23,6 +23,7 @@ struct State {
     uint32_t    triRunRows = 256;       // hipSpTRSVCSR: T, the row threshold of the single-workgroup runs
     uint32_t    iluGroup = 16;          // hipSpILU0CSR: lanes per row
     int         gmresFused = 0;         // hipSpGMRESCSR: fold the first CGS2 update into the second projection
+    uint32_t    colourK = 16;           // spmvHipColourCSR: rounds per host check
     uint32_t    krylovK[2] = {16, 16};  // hipSpCGCSR, hipSpBiCGStabCSR: iterations per host check
     int         ldsOrder = -1;          // lds_order_probe_kernel: -1 not run yet, 1 lane-ascending + in issue order, 0 anything else
     bool        ellRowLens = true;

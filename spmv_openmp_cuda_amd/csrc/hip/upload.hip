@@ -414,10 +414,67 @@ int spmvHipTransposeRefresh(spmat* dAT, spmat* dA) {
     if (!t) return EXIT_FAILURE;
     DevMat* a = descOf(dA, who);
     if (!a) return EXIT_FAILURE;
-    if (!t->srcId) { ERR("%s: dAT was not made by spmvHipCsrTranspose", who); return EXIT_FAILURE; }
+    if (!t->srcId || t->permuted) { ERR("%s: dAT was not made by spmvHipCsrTranspose", who); return EXIT_FAILURE; }
     if (a->id != t->srcId) { ERR("%s: dA is not the handle dAT was transposed from", who); return EXIT_FAILURE; }
     if (enqueueGatherValues(t->AS, t->tmap, t->NZ, a->AS, S.stream)) return EXIT_FAILURE;
     return updateValues(dAT, nullptr, true, true, S.stream, who);
+}
+
+// B = P A P^T as a handle of its own (colour.hip builds the arrays; the contract is in spmvHip.h, the design in DESIGN.md
+// section 21).  As the transpose: refusals come before anything is allocated for dB, and dB is written only on success.
+int spmvHipCsrPermute(spmat* dA, const uint32_t* dPerm, spmat* dB) {
+    const char* who = "spmvHipCsrPermute";
+    if (!ready(who)) return EXIT_FAILURE;
+    if (!dB || !dPerm) { ERR("%s: %s is NULL", who, !dB ? "dB" : "dPerm"); return EXIT_FAILURE; }
+    DevMat* a = descOf(dA, who);
+    if (!a) return EXIT_FAILURE;
+    if (dB == dA) { ERR("%s: dB is the source handle itself", who); return EXIT_FAILURE; }
+    if (!csrOnly(a, who, "the source is an ELL handle (only CSR handles can be permuted)")) return EXIT_FAILURE;
+    if (a->M != a->N) { ERR("%s: M=%lu != N=%lu: the matrix is not square", who, (unsigned long)a->M, (unsigned long)a->N); return EXIT_FAILURE; }
+    if (a->NZ >= IRP32_LIMIT || a->M >= (1ull << 31)) {
+        ERR("%s: NZ=%lu, M=%lu: the map, the positions and the sort keys are 32-bit (limits %lu, 2^31)", who, (unsigned long)a->NZ,
+            (unsigned long)a->M, (unsigned long)IRP32_LIMIT);
+        return EXIT_FAILURE;
+    }
+    if (a->NZ && (!a->JA || !a->AS)) { ERR("%s: the source has no column or value array", who); return EXIT_FAILURE; }
+    uint32_t* inv = nullptr;
+    uint32_t bad = 0;
+    HIP_TRY(hipMalloc(&inv, std::max<size_t>(a->M, 1) * 4));
+    if (invertPerm(a->M, dPerm, inv, &bad, S.stream)) { (void)hipFree(inv); ERR("%s: checking dPerm failed", who); return EXIT_FAILURE; }
+    if (bad) {
+        (void)hipFree(inv);
+        ERR("%s: dPerm is not a permutation of 0..M-1 (%s)", who, bad & 1 ? "a value >= M" : "a repeated value");
+        return EXIT_FAILURE;
+    }
+    DevMat* t = new DevMat;
+    t->kind = Kind::CSR;
+    t->M = t->N = a->M; t->NZ = a->NZ; t->irpBytes = 4;
+    t->srcId = a->id;
+    t->permuted = true;
+    const size_t nz1 = std::max<size_t>(a->NZ, 1);
+    std::vector<uint32_t> hIRP(t->M + 1);
+    const bool ok = hipOk(hipMalloc(&t->IRP, (t->M + 1) * 4), "hipMalloc IRP") && hipOk(hipMalloc(&t->JA, nz1 * 4), "hipMalloc JA") &&
+                    hipOk(hipMalloc(&t->AS, nz1 * 8), "hipMalloc AS") && hipOk(hipMalloc(&t->tmap, nz1 * 4), "hipMalloc map") &&
+                    !permuteCsr(a, inv, t, S.stream) &&
+                    hipOk(hipMemcpy(hIRP.data(), t->IRP, hIRP.size() * 4, hipMemcpyDeviceToHost), "hipMemcpy IRP") &&
+                    !buildRowBlocks2(t, hIRP.data(), t->M) && !detectUnit(t, S.stream);
+    (void)hipFree(inv);
+    if (!ok) { ERR("%s: building the permuted matrix failed", who); freeDesc(t); return EXIT_FAILURE; }
+    publish(dB, t, t->M, t->N, t->NZ, 0);
+    return EXIT_SUCCESS;
+}
+
+int spmvHipPermuteRefresh(spmat* dB, spmat* dA) {
+    const char* who = "spmvHipPermuteRefresh";
+    if (!ready(who)) return EXIT_FAILURE;
+    DevMat* t = descOf(dB, who);
+    if (!t) return EXIT_FAILURE;
+    DevMat* a = descOf(dA, who);
+    if (!a) return EXIT_FAILURE;
+    if (!t->srcId || !t->permuted) { ERR("%s: dB was not made by spmvHipCsrPermute", who); return EXIT_FAILURE; }
+    if (a->id != t->srcId) { ERR("%s: dA is not the handle dB was permuted from", who); return EXIT_FAILURE; }
+    if (enqueueGatherValues(t->AS, t->tmap, t->NZ, a->AS, S.stream)) return EXIT_FAILURE;
+    return updateValues(dB, nullptr, true, true, S.stream, who);
 }
 
 int spmvHipUpdateValues(spmat* dMat, const double* AS, int asOnDevice) {
