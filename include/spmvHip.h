@@ -452,6 +452,59 @@ int spmvHipColourCSR(spmat* dA, const spmvColourOpts* opts, uint32_t* dColour, u
 int spmvHipCsrPermute(spmat* dA, const uint32_t* dPerm, spmat* dB);
 int spmvHipPermuteRefresh(spmat* dB, spmat* dA);
 int spmvHipVecPermute(size_t n, const uint32_t* dPerm, const double* dIn, double* dOut, int inverse);
+/* ------------------------------------------------------------- sparse matrix product C = A B */
+/* spmvHipSpGEMM writes into dC a new, independent CSR handle of C = A B.  A name is a contract, and the contract is the
+ * bits of this serial loop on the two handles' arrays (IRP, JA, AS as stored):
+ *       for i in 0 .. A.M-1:
+ *           for p in A.IRP[i] .. A.IRP[i+1]-1:                 (A's stored order)
+ *               k = A.JA[p]
+ *               for q in B.IRP[k] .. B.IRP[k+1]-1:             (B's stored order)
+ *                   j = B.JA[q]
+ *                   if (i, j) is new: acc[i,j] = +0.0
+ *                   acc[i,j] = acc[i,j] + (A.AS[p] * B.AS[q])  (product rounded, then the add: contraction is off)
+ *           row i of C = the (j, acc[i,j]) in ascending j
+ *   Structural: every (i, j) that some product reaches is stored, even when the sum is 0.0; nothing is dropped or added.
+ *   A and B may have unsorted rows and repeated (row, col) pairs: each repeat is one more term, in stored order.  Rows of
+ *   C ascend strictly and have no repeats, so hipSpILU0CSR, hipSpTRSVCSR and the serial-order SpMV selection accept C as it
+ *   is.  The result is a function of the two handles' arrays alone -- not of the run, the grid, the class a row fell into
+ *   or the options -- and two calls give the same bits.  Where a term is NaN, C has a NaN at that place; its payload is not
+ *   pinned (hardware and host differ in which operand's payload an add keeps).  Every other value is pinned as bits:
+ *   +-Inf, -0.0 inputs and sums that cancel to +0.0 included.
+ *   dC is like a transpose or permuted handle: u32 columns, 4-byte row pointers, its own unit detection, row blocks; every
+ *   CSR entry point works on it; freed with hipFreeSpmat.  dA == dB is allowed (A^2).  Sources: spMatCpyCSR /
+ *   spmvHipAdoptCSR / transpose / permuted / product handles, row pointers of 4 or 8 bytes, unit-value handles included.
+ *   opts (NULL, or a field 0: the built-in default; a value above the built-in limit is clamped to it) only LOWER the class
+ *   limits: a row's class comes from m = min(products of the row, B.N): m <= waveMaxProducts (512) one wavefront with a
+ *   1 024-slot hash table in LDS, m <= groupMaxProducts (6 144) one workgroup with 8 192 slots, above that the sorted path
+ *   (one stable radix sort per batch of rows whose products fit sortBudgetBytes: 32 B per product, default 256 MiB, limit
+ *   4 GiB; a row above the budget is a batch of its own).
+ *   Memory: C itself 12 B per entry + 4 B per row, its row blocks, and 4 B per row for the refresh (the rows by class).
+ *   Temporaries, freed before the call returns: 20 B per row for the bound and the lists, then 12 B per row for the counts
+ *   and their scan, 16 B per sorted row, and 32 B per product of the largest sorted batch + the sort's workspace.
+ *   info: products (sum of the bounds), nnzC, maxRowProducts, maxRowNnz, rowsWave / rowsGroup / rowsSorted (they sum to the
+ *   rows with a product), sortBatches, tempBytes (peak of the temporaries), symbolicMs / numericMs / ms (wall times).
+ *   Synchronous on the library stream; allocates, so not capturable.  opts and info may be NULL.
+ *   A.M = 0, A.N = 0, B.N = 0 and "no products" succeed with an empty C: valid row pointers, NZ = 0, SpMV on it gives +0.0.
+ * spmvHipSpGEMMRefresh recomputes C's values from the sources' CURRENT value arrays, C's pattern and addresses kept: the
+ *   numeric phase only, on the classes of the build, then what spmvHipValuesChanged(dC) does.  dC records both sources'
+ *   ids and refuses any other pair, and the same pair in the other order.  The sources' patterns must be unchanged.
+ * Refused with a message and EXIT_FAILURE, dC and info untouched: NULL dA, dB or dC; a handle that is not live; an ELL
+ *   handle; A.N != B.M; dC == dA or dC == dB; A.M or B.N >= 2^32 - 1; nnz(C) >= IRP32_LIMIT (2^32 - 65536; found after the
+ *   symbolic phase, before anything of dC exists); a column id of A that is >= B.M (an adopted array; checked on the
+ *   device); a refresh of a handle that is not a product, or from other sources. */
+typedef struct {            /* 0 = the built-in default; a value above the built-in limit is clamped to it */
+    ulong waveMaxProducts;  /* rows with at most this many products: one wavefront each            */
+    ulong groupMaxProducts; /* ... at most this many: one workgroup each; above: the sorted path   */
+    ulong sortBudgetBytes;  /* temporaries of one batch of the sorted path                         */
+} spmvSpgemmOpts;
+typedef struct {
+    ulong products, nnzC, maxRowProducts, maxRowNnz;
+    ulong rowsWave, rowsGroup, rowsSorted, sortBatches;
+    ulong tempBytes;        /* peak of the build's temporaries */
+    double symbolicMs, numericMs, ms;
+} spmvSpgemmInfo;
+int spmvHipSpGEMM(spmat* dA, spmat* dB, const spmvSpgemmOpts* opts, spmat* dC, spmvSpgemmInfo* info);
+int spmvHipSpGEMMRefresh(spmat* dC, spmat* dA, spmat* dB, spmvSpgemmInfo* info);
 /* Release the device arrays behind a handle (cudaUtils.h:70-78). */
 int hipFreeSpmat(spmat* dMat);
 

@@ -114,6 +114,8 @@ _sigs = {
     "spmvHipCsrPermute": ([C.POINTER(spmat), _vp, C.POINTER(spmat)], _i),
     "spmvHipPermuteRefresh": ([C.POINTER(spmat), C.POINTER(spmat)], _i),
     "spmvHipVecPermute": ([_sz, _vp, _vp, _vp, _i], _i),
+    "spmvHipSpGEMM": ([C.POINTER(spmat), C.POINTER(spmat), _vp, C.POINTER(spmat), _vp], _i),
+    "spmvHipSpGEMMRefresh": ([C.POINTER(spmat), C.POINTER(spmat), C.POINTER(spmat), _vp], _i),
 }
 SPMV_DENSE_ROW_MAJOR, SPMV_DENSE_COL_MAJOR = 0, 1          # include/spmvHip.h: layouts of hipSpMMRowsCSR's X and Y
 SPMV_TRI_LOWER, SPMV_TRI_UPPER = 0, 1                      # include/spmvHip.h: hipSpTRSVCSR's uplo ...
@@ -192,6 +194,18 @@ class spmvColourInfo(C.Structure):
     """include/spmvHip.h `spmvColourInfo`: what a spmvHipColourCSR call did."""
     _fields_ = [("colours", C.c_ulong), ("rounds", C.c_ulong), ("hostChecks", C.c_ulong), ("maxColourRows", C.c_ulong),
                 ("longRows", C.c_ulong), ("symmetric", _i), ("ms", C.c_double)]
+
+
+class spmvSpgemmOpts(C.Structure):
+    """include/spmvHip.h `spmvSpgemmOpts`: the class limits of spmvHipSpGEMM (0 = the built-in default; they only lower)."""
+    _fields_ = [("waveMaxProducts", C.c_ulong), ("groupMaxProducts", C.c_ulong), ("sortBudgetBytes", C.c_ulong)]
+
+
+class spmvSpgemmInfo(C.Structure):
+    """include/spmvHip.h `spmvSpgemmInfo`: what a spmvHipSpGEMM / spmvHipSpGEMMRefresh call did."""
+    _fields_ = [("products", C.c_ulong), ("nnzC", C.c_ulong), ("maxRowProducts", C.c_ulong), ("maxRowNnz", C.c_ulong),
+                ("rowsWave", C.c_ulong), ("rowsGroup", C.c_ulong), ("rowsSorted", C.c_ulong), ("sortBatches", C.c_ulong),
+                ("tempBytes", C.c_ulong), ("symbolicMs", C.c_double), ("numericMs", C.c_double), ("ms", C.c_double)]
 
 
 SPMV_COLOUR_NATURAL, SPMV_COLOUR_HASH = 0, 1
@@ -512,6 +526,33 @@ class DeviceMatrix:
         """spmvHipPermuteRefresh: this permuted matrix takes `source`'s current device values (source must be the matrix it
         was permuted from), then refreshes its formats as values_changed() does."""
         _check(lib.spmvHipPermuteRefresh(C.byref(self.handle), C.byref(source.handle)), "spmvHipPermuteRefresh")
+
+    def multiply(self, other: "DeviceMatrix", waveMaxProducts=0, groupMaxProducts=0, sortBudgetBytes=0) -> "DeviceMatrix":
+        """spmvHipSpGEMM: C = self * other as a new DeviceMatrix that owns its handle, bit for bit the serial loop of
+        include/spmvHip.h (terms in stored (p, q) order, rows of C ascending, structural zeros kept).  The options only
+        lower the class limits (0: the defaults).  `other` may be this matrix.  spgemm_info() tells what the call did."""
+        c = DeviceMatrix()
+        opts, info = spmvSpgemmOpts(int(waveMaxProducts), int(groupMaxProducts), int(sortBudgetBytes)), spmvSpgemmInfo()
+        _check(lib.spmvHipSpGEMM(C.byref(self.handle), C.byref(other.handle), C.byref(opts), C.byref(c.handle), C.byref(info)),
+               "spmvHipSpGEMM")
+        c.rows = int(c.handle.M)
+        c._spgemm = info
+        return c
+
+    def multiply_refresh(self, a: "DeviceMatrix", b: "DeviceMatrix"):
+        """spmvHipSpGEMMRefresh: this product takes its values again from the current values of `a` and `b` (the pair it
+        was built from, in that order), pattern and addresses kept, then refreshes its formats as values_changed() does."""
+        info = spmvSpgemmInfo()
+        _check(lib.spmvHipSpGEMMRefresh(C.byref(self.handle), C.byref(a.handle), C.byref(b.handle), C.byref(info)),
+               "spmvHipSpGEMMRefresh")
+        self._spgemm = info
+
+    def spgemm_info(self) -> "spmvSpgemmInfo":
+        """the spmvSpgemmInfo of the multiply() that made this matrix, or of its last multiply_refresh()"""
+        info = getattr(self, "_spgemm", None)
+        if info is None:
+            raise SpmvHipError("spgemm_info: this matrix was not made by multiply()")
+        return info
 
     def matmul(self, X, out=None):
         """hipSpMMRowsCSR: Y = A X, column c of Y bit-identical to sgemvSerial on column c of X.  X is (N, k) float64:

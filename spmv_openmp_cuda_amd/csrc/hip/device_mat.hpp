@@ -32,6 +32,7 @@ enum class Kind : int { CSR = 0, ELL_ROWMAJOR = 1, ELL_COLMAJOR = 2 };
 struct TileFormat;          // column-sliced two-phase format, tiles.hip
 struct SellFormat;          // SELL-C-sigma, sell.hip
 struct StripeFormat;        // bin-wise CSC (y bins in LDS, x from the XCD's L2), stripes.hip
+struct SpgemmPlan;          // what a product C = A B keeps for its refresh, spgemm.hip
 
 // the level sets of one triangle (built by triAnalyse in trsv.hip; the ILU(0) factorisation of ilu0.hip runs on the lower one)
 struct TriSchedule {
@@ -97,6 +98,9 @@ struct DevMat {
     uint32_t* tmap = nullptr;
     // ... and so has a permutation built by spmvHipCsrPermute (colour.hip): the same id and map, refreshed by its own call
     bool      permuted = false;
+    // a product built by spmvHipSpGEMM (spgemm.hip): the ids of its two sources and its rows by class (4 B per row); no
+    // pointer to a source is kept
+    SpgemmPlan* prod = nullptr;
     // the level-set schedules of the triangular solve (trsv.hip), [SPMV_TRI_LOWER] and [SPMV_TRI_UPPER]: built from the
     // pattern at the first solve or by spmvHipTriAnalyse, kept across value updates (the solve reads AS live)
     TriSchedule* tri[2] = {nullptr, nullptr};
@@ -177,6 +181,13 @@ int  colourCsr(const DevMat* a, int order, uint32_t seed, uint32_t K, uint32_t* 
 int  invertPerm(uint64_t M, const uint32_t* perm, uint32_t* inv, uint32_t* bad, hipStream_t stream);
 int  permuteCsr(const DevMat* a, const uint32_t* inv, DevMat* t, hipStream_t stream);
 int  enqueueVecPermute(uint64_t n, const uint32_t* perm, const double* in, double* out, int inverse, hipStream_t stream);
+// C = A B (spgemm.hip; contract in spmvHip.h, design in DESIGN.md section 22).  spgemmBuild: c has kind, M and N set and owns
+// nothing; on success it owns IRP (4 B), JA, AS and the plan, with NZ set; on failure the caller frees c with whatever it
+// holds.  spgemmRefresh: the numeric phase again into c's arrays.  Both synchronous, temporaries freed before they return.
+int  spgemmBuild(const DevMat* a, const DevMat* b, const spmvSpgemmOpts* opts, DevMat* c, spmvSpgemmInfo* info, hipStream_t stream);
+int  spgemmRefresh(DevMat* c, const DevMat* a, const DevMat* b, spmvSpgemmInfo* info, hipStream_t stream);
+bool spgemmSources(const DevMat* c, uint64_t* idA, uint64_t* idB);   // false: c is no product
+void freeSpgemmPlan(SpgemmPlan* p);
 // Triangular solves (trsv.hip; contract in spmvHip.h, design in DESIGN.md section 17).  triAnalyse builds d->tri[uplo]
 // (synchronous, allocates, temporaries freed before it returns; runThreshold = the T of the single-workgroup runs, 0: none);
 // enqueueTrsv enqueues one solve of an analysed triangle on `stream` (no allocation, no sync) and reports the last launch;

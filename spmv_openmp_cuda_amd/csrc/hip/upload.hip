@@ -63,6 +63,7 @@ void freeDesc(DevMat* d) {
     }
     (void)hipFree(d->blkInfo); (void)hipFree(d->blkBase); (void)hipFree(d->tmap);
     freeTri(d->tri[0]); freeTri(d->tri[1]);
+    freeSpgemmPlan(d->prod);
     freeTiles(d->tiles[0]); freeTiles(d->tiles[1]);
     freeSell(d->sell);
     freeStripes(d->stripes[0]); freeStripes(d->stripes[1]);
@@ -475,6 +476,57 @@ int spmvHipPermuteRefresh(spmat* dB, spmat* dA) {
     if (a->id != t->srcId) { ERR("%s: dA is not the handle dB was permuted from", who); return EXIT_FAILURE; }
     if (enqueueGatherValues(t->AS, t->tmap, t->NZ, a->AS, S.stream)) return EXIT_FAILURE;
     return updateValues(dB, nullptr, true, true, S.stream, who);
+}
+
+// C = A B as a handle of its own (spgemm.hip builds the arrays; the contract is in spmvHip.h, the design in DESIGN.md
+// section 22).  Refusals come first; dC and info are written only on success.
+int spmvHipSpGEMM(spmat* dA, spmat* dB, const spmvSpgemmOpts* opts, spmat* dC, spmvSpgemmInfo* info) {
+    const char* who = "spmvHipSpGEMM";
+    if (!ready(who)) return EXIT_FAILURE;
+    if (!dA || !dB || !dC) { ERR("%s: %s is NULL", who, !dA ? "dA" : !dB ? "dB" : "dC"); return EXIT_FAILURE; }
+    if (dC == dA || dC == dB) { ERR("%s: dC is a source handle itself", who); return EXIT_FAILURE; }
+    DevMat* a = descOf(dA, who);
+    DevMat* b = a ? descOf(dB, who) : nullptr;
+    if (!a || !b) return EXIT_FAILURE;
+    if (!csrOnly(a, who, "dA is an ELL handle (only CSR handles can be multiplied)") ||
+        !csrOnly(b, who, "dB is an ELL handle (only CSR handles can be multiplied)"))
+        return EXIT_FAILURE;
+    if (a->N != b->M) { ERR("%s: A.N=%lu != B.M=%lu", who, (unsigned long)a->N, (unsigned long)b->M); return EXIT_FAILURE; }
+    if (a->M >= (1ull << 32) - 1 || b->N >= (1ull << 32) - 1) {
+        ERR("%s: A.M=%lu, B.N=%lu: the product has 32-bit row and column ids", who, (unsigned long)a->M, (unsigned long)b->N);
+        return EXIT_FAILURE;
+    }
+    if ((a->NZ && (!a->JA || !a->AS)) || (b->NZ && (!b->JA || !b->AS))) { ERR("%s: a source has no column or value array", who); return EXIT_FAILURE; }
+    DevMat* c = new DevMat;
+    c->kind = Kind::CSR;
+    c->M = a->M; c->N = b->N;
+    spmvSpgemmInfo out{};
+    std::vector<uint32_t> hIRP(c->M + 1);
+    const bool ok = !spgemmBuild(a, b, opts, c, &out, S.stream) &&
+                    hipOk(hipMemcpy(hIRP.data(), c->IRP, hIRP.size() * 4, hipMemcpyDeviceToHost), "hipMemcpy IRP") &&
+                    !buildRowBlocks2(c, hIRP.data(), c->M) && !detectUnit(c, S.stream);
+    if (!ok) { ERR("%s: building the product failed", who); freeDesc(c); return EXIT_FAILURE; }
+    publish(dC, c, c->M, c->N, c->NZ, 0);
+    if (info) *info = out;
+    return EXIT_SUCCESS;
+}
+
+int spmvHipSpGEMMRefresh(spmat* dC, spmat* dA, spmat* dB, spmvSpgemmInfo* info) {
+    const char* who = "spmvHipSpGEMMRefresh";
+    if (!ready(who)) return EXIT_FAILURE;
+    if (!dA || !dB || !dC) { ERR("%s: %s is NULL", who, !dC ? "dC" : !dA ? "dA" : "dB"); return EXIT_FAILURE; }
+    DevMat* c = descOf(dC, who);
+    DevMat* a = c ? descOf(dA, who) : nullptr;
+    DevMat* b = a ? descOf(dB, who) : nullptr;
+    if (!c || !a || !b) return EXIT_FAILURE;
+    uint64_t idA = 0, idB = 0;
+    if (!spgemmSources(c, &idA, &idB)) { ERR("%s: dC was not made by spmvHipSpGEMM", who); return EXIT_FAILURE; }
+    if (a->id != idA || b->id != idB) { ERR("%s: (dA, dB) is not the pair, in its order, that dC is the product of", who); return EXIT_FAILURE; }
+    spmvSpgemmInfo out{};
+    if (spgemmRefresh(c, a, b, &out, S.stream)) { ERR("%s: recomputing the values failed", who); return EXIT_FAILURE; }
+    if (updateValues(dC, nullptr, true, true, S.stream, who)) return EXIT_FAILURE;
+    if (info) *info = out;
+    return EXIT_SUCCESS;
 }
 
 int spmvHipUpdateValues(spmat* dMat, const double* AS, int asOnDevice) {
