@@ -16,36 +16,28 @@
 //      the short list, one lane each.
 //   3. K rounds are enqueued, then the K + 1 list counts of the batch are read back (one small state, as the Krylov loops
 //      do).  Every round compacts: it reads its list and writes the rows that wait into the other one.
-//   4. dPerm: a stable rocprim::radix_sort_pairs of the colours over an iota = the rows by (colour, id).
+//   4. dPerm: a stable radix sort of the colours over an iota = the rows by (colour, id).
 //
 // Permutation.  One stable sort of the keys (new row << bits | new column) with the source CSR position as payload gives the
 // entries of B in their order -- rows ascending, within a row ascending new column, repeated columns in A's stored order --
 // and the payload is the source-position map.  Then the row pointers from the sorted keys and a gather of the values.
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_radix_sort.hpp>
 #include <algorithm>
 #include <chrono>
-#include <cstdio>
 #include <vector>
 
 #include "spmvHip.h"
 #include "kernels.hpp"
+#include "device_prims.hpp"
 
 namespace spmvhip {
 
 namespace {
 
-constexpr uint32_t CL_THREADS = 256;
+constexpr uint32_t CL_THREADS = WG_THREADS;                    // (what gridFor deals to by default)
 constexpr uint32_t CL_WAVES = CL_THREADS / 64;
 constexpr uint32_t UNCOLOURED = 0xFFFFFFFFu;
 constexpr uint32_t CL_LONG = 64;                               // adjacency entries above which a row takes a wavefront
-
-struct TempBuf {
-    void* p = nullptr;
-    ~TempBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, std::max<size_t>(bytes, 1)); }
-    template <typename T> T* as() { return static_cast<T*>(p); }
-};
 
 __device__ __forceinline__ uint32_t fmix32(uint32_t h) {      // the murmur3 32-bit finaliser
     h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
@@ -57,11 +49,6 @@ __device__ __forceinline__ bool wins(uint32_t j, uint32_t i, int order, uint32_t
     if (order == SPMV_COLOUR_NATURAL) return j < i;
     const uint32_t kj = fmix32(j ^ seed), ki = fmix32(i ^ seed);
     return kj != ki ? kj > ki : j > i;
-}
-
-__global__ __launch_bounds__(CL_THREADS) void cl_iota_kernel(uint64_t n, uint32_t* __restrict__ p) {
-    const uint64_t i = linear_block() * CL_THREADS + threadIdx.x;
-    if (i < n) p[i] = (uint32_t)i;
 }
 
 // 1 in *flag unless every stored (i, j), j != i, has a stored (j, i): one lane per entry scans row j (rows of at most 64
@@ -235,13 +222,6 @@ __global__ __launch_bounds__(CL_THREADS) void vec_permute_kernel(uint64_t n, con
     else         out[r] = in[v];
 }
 
-inline dim3 gridFor(uint64_t items, uint32_t perBlock = CL_THREADS) { return grid2d((items + perBlock - 1) / perBlock, CL_THREADS); }
-inline unsigned bitsFor(uint64_t n) {                          // the bits that hold every id below n (at least 1)
-    unsigned bits = 1;
-    while (bits < 32 && (1ull << bits) < n) ++bits;
-    return bits;
-}
-
 }  // namespace
 
 int enqueueVecPermute(uint64_t n, const uint32_t* perm, const double* in, double* out, int inverse, hipStream_t st) {
@@ -265,17 +245,12 @@ int permuteCsr(const DevMat* a, const uint32_t* inv, DevMat* t, hipStream_t st) 
     const uint64_t nnz = a->NZ, M = a->M;
     uint32_t* const IRPt = static_cast<uint32_t*>(t->IRP);
     TempBuf rowOf, keyIn, keyOut, sortTmp;
-    auto fail = [&](const char* what) {
-        (void)hipGetLastError();
-        fprintf(stderr, "libspmvhip: permute: %s failed\n", what);
-        (void)hipStreamSynchronize(st);                   // nothing may still use the temporaries when they go
-        return EXIT_FAILURE;
-    };
+    auto fail = [&](const char* what) { return buildFail(st, "permute", what); };
     const unsigned bits = bitsFor(M);
     if (nnz) {
         if (rowOf.alloc(nnz * 4) || keyIn.alloc(nnz * 8) || keyOut.alloc(nnz * 8)) return fail("temporary allocation (20 B per entry)");
         uint32_t* const iota = reinterpret_cast<uint32_t*>(t->AS);                  // (the room of the values, written last)
-        hipLaunchKernelGGL(cl_iota_kernel, gridFor(nnz), dim3(CL_THREADS), 0, st, nnz, iota);
+        enqueueIota(nnz, iota, st);
         enqueueRowOf(M, a->IRP, a->irpBytes, rowOf.as<uint32_t>(), st);
         uint32_t outOfRange = 0;
         if (deviceFlag(0, st, "pm_keys_kernel", &outOfRange, [&](uint32_t* dFlag) {
@@ -284,12 +259,7 @@ int permuteCsr(const DevMat* a, const uint32_t* inv, DevMat* t, hipStream_t st) 
             }))
             return fail("keys");
         if (outOfRange) { fprintf(stderr, "libspmvhip: permute: a column id of the source is >= M\n"); return EXIT_FAILURE; }
-        size_t tmpBytes = 0;
-        if (rocprim::radix_sort_pairs(nullptr, tmpBytes, keyIn.as<uint64_t>(), keyOut.as<uint64_t>(), iota, t->tmap, (size_t)nnz, 0u, 2 * bits,
-                                      st) != hipSuccess || sortTmp.alloc(tmpBytes))
-            return fail("sort workspace");
-        if (rocprim::radix_sort_pairs(sortTmp.p, tmpBytes, keyIn.as<uint64_t>(), keyOut.as<uint64_t>(), iota, t->tmap, (size_t)nnz, 0u, 2 * bits,
-                                      st) != hipSuccess)
+        if (sortPairs(sortTmp, keyIn.as<uint64_t>(), keyOut.as<uint64_t>(), iota, t->tmap, (size_t)nnz, 0u, 2 * bits, st) != hipSuccess)
             return fail("sort");
         hipLaunchKernelGGL(pm_split_kernel, gridFor(nnz), dim3(CL_THREADS), 0, st, nnz, bits, keyOut.as<uint64_t>(), rowOf.as<uint32_t>(), t->JA);
     }
@@ -306,12 +276,7 @@ int colourCsr(const DevMat* a, int order, uint32_t seed, uint32_t K, uint32_t* d
     const uint64_t nnz = a->NZ, M = a->M;
     spmvColourInfo out{};
     out.symmetric = 1;                                         // (no entry: nothing comes in from the transposed side)
-    auto fail = [&](const char* what) {
-        (void)hipGetLastError();
-        fprintf(stderr, "libspmvhip: colour: %s failed\n", what);
-        (void)hipStreamSynchronize(st);
-        return EXIT_FAILURE;
-    };
+    auto fail = [&](const char* what) { return buildFail(st, "colour", what); };
     if (M == 0) { if (info) *info = out; return EXIT_SUCCESS; }
     TempBuf rowOf, tkeys, tcolBuf, tptrBuf, sortTmp, colourBuf, lists, state, iotaBuf, sortedBuf, permBuf;
     // 1. the incoming side
@@ -331,17 +296,11 @@ int colourCsr(const DevMat* a, int order, uint32_t seed, uint32_t K, uint32_t* d
         out.symmetric = asym ? 0 : 1;
         if (asym) {
             if (tkeys.alloc(nnz * 4) || tcolBuf.alloc(nnz * 4) || tptrBuf.alloc((M + 1) * 4)) return fail("temporary allocation (transposed pattern)");
-            size_t tmpBytes = 0;
-            const unsigned bits = bitsFor(a->N);
-            if (rocprim::radix_sort_pairs(nullptr, tmpBytes, a->JA, tkeys.as<uint32_t>(), rowOf.as<uint32_t>(), tcolBuf.as<uint32_t>(), (size_t)nnz,
-                                          0u, bits, st) != hipSuccess || sortTmp.alloc(tmpBytes))
-                return fail("sort workspace");
-            if (rocprim::radix_sort_pairs(sortTmp.p, tmpBytes, a->JA, tkeys.as<uint32_t>(), rowOf.as<uint32_t>(), tcolBuf.as<uint32_t>(), (size_t)nnz,
-                                          0u, bits, st) != hipSuccess)
-                return fail("sort");
             // (preset: with column ids >= N the sort leaves keys out of order and the bounds kernel words unwritten)
             if (hipMemsetAsync(tptrBuf.p, 0, (M + 1) * 4, st) != hipSuccess) return fail("transposed pattern");
-            enqueueSortedBounds(nnz, M, tkeys.as<uint32_t>(), tptrBuf.as<uint32_t>(), st);
+            if (enqueueSortedByColumn(nnz, M, bitsFor(a->N), a->JA, rowOf.as<uint32_t>(), tkeys.as<uint32_t>(), tcolBuf.as<uint32_t>(),
+                                      tptrBuf.as<uint32_t>(), sortTmp, st) != hipSuccess)
+                return fail("sort");
             tptr = tptrBuf.as<uint32_t>();
             tcol = tcolBuf.as<uint32_t>();
         }
@@ -410,16 +369,10 @@ int colourCsr(const DevMat* a, int order, uint32_t seed, uint32_t K, uint32_t* d
         if (permBuf.alloc(M * 4)) return fail("temporary allocation (order)");
         dPerm = permBuf.as<uint32_t>();
     }
-    hipLaunchKernelGGL(cl_iota_kernel, gridFor(M), dim3(CL_THREADS), 0, st, M, iotaBuf.as<uint32_t>());
+    enqueueIota(M, iotaBuf.as<uint32_t>(), st);
     {
-        size_t tmpBytes = 0;
         TempBuf tmp;
-        const unsigned bits = bitsFor(out.colours);
-        if (rocprim::radix_sort_pairs(nullptr, tmpBytes, dColour, sortedBuf.as<uint32_t>(), iotaBuf.as<uint32_t>(), dPerm, (size_t)M, 0u, bits, st) !=
-                hipSuccess || tmp.alloc(tmpBytes))
-            return fail("sort workspace");
-        if (rocprim::radix_sort_pairs(tmp.p, tmpBytes, dColour, sortedBuf.as<uint32_t>(), iotaBuf.as<uint32_t>(), dPerm, (size_t)M, 0u, bits, st) !=
-            hipSuccess)
+        if (sortPairs(tmp, dColour, sortedBuf.as<uint32_t>(), iotaBuf.as<uint32_t>(), dPerm, (size_t)M, 0u, bitsFor(out.colours), st) != hipSuccess)
             return fail("sort");
         TempBuf cptr;
         std::vector<uint32_t> hc(out.colours + 1);

@@ -33,6 +33,7 @@ struct TileFormat;          // column-sliced two-phase format, tiles.hip
 struct SellFormat;          // SELL-C-sigma, sell.hip
 struct StripeFormat;        // bin-wise CSC (y bins in LDS, x from the XCD's L2), stripes.hip
 struct SpgemmPlan;          // what a product C = A B keeps for its refresh, spgemm.hip
+struct TempBuf;             // a scoped device buffer, device_prims.hpp
 
 // the level sets of one triangle (built by triAnalyse in trsv.hip; the ILU(0) factorisation of ilu0.hip runs on the lower one)
 struct TriSchedule {
@@ -167,10 +168,14 @@ int  sellRefreshValues(DevMat* d, hipStream_t stream);          // sell.hip
 // for a->N + 1 rows / a->NZ entries; the temporaries are freed before the call returns, and it returns with the stream
 // synchronised
 int  transposeCsr(const DevMat* a, DevMat* t, hipStream_t stream);
-// the pieces of the transpose that the triangular analysis shares (transpose.hip): ptr[c] = the first of the nnz sorted
-// keys that is >= c, for c in [0, N] (keys >= N clamp to N); rowOf[p] = the row of CSR position p
+// the pieces of the transpose that the triangular analysis and the colouring share (transpose.hip): ptr[c] = the first of
+// the nnz sorted keys that is >= c, for c in [0, N] (keys >= N clamp to N); rowOf[p] = the row of CSR position p; and the
+// pattern sorted by column: the stable sort of (keys, payload) over `bits` key bits into (keysOut, payloadOut), its
+// workspace in ws (which must outlive what is enqueued), then ptr from keysOut -- the bounds also when nnz is 0
 void enqueueSortedBounds(uint64_t nnz, uint64_t N, const uint32_t* keys, uint32_t* ptr, hipStream_t stream);
 void enqueueRowOf(uint64_t M, const void* IRP, int irpBytes, uint32_t* rowOf, hipStream_t stream);
+hipError_t enqueueSortedByColumn(uint64_t nnz, uint64_t N, unsigned bits, uint32_t* keys, uint32_t* payload, uint32_t* keysOut,
+                                 uint32_t* payloadOut, uint32_t* ptr, TempBuf& ws, hipStream_t stream);
 // Multi-colour ordering and symmetric permutation (colour.hip; contracts in spmvHip.h, design in DESIGN.md section 21).
 // colourCsr: the colours and the (colour, id) order of the checked square handle, K rounds per host check; dColour / dPerm
 // may be null; synchronous, allocates, temporaries freed before it returns.  invertPerm: inv = perm^-1 into the caller's M

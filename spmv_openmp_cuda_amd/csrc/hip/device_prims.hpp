@@ -1,0 +1,123 @@
+// device_prims.hpp -- what a build step on the device gets its temporaries, sorts and scans from (library-private; the
+// format files tiles / stripes / sell and transpose, trsv, ilu0, colour, spgemm include it after kernels.hpp).
+//
+//   TempBuf                     one scoped device buffer; with a TempTally it keeps the bytes held and their peak
+//   sortPairs / sortKeys /      rocPRIM's "two-call" algorithms in one call: the size query, the workspace (grown only
+//   exclusiveScan               when the call needs more than it holds), the run.  The argument list is written once.
+//   enqueueIota / enqueueFill32 the two trivial kernels, defined ONCE in transpose.hip (a definition here would put a
+//                               copy of each into every translation unit that includes this header)
+//   bitsFor / gridFor           key bits of a radix sort, the grid of a one-item-per-lane launch
+//   buildFail                   how a synchronous build step reports a failure and leaves
+// rocPRIM is included here and nowhere else; its kernels are still instantiated by, and compiled into, each caller.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+#include <algorithm>
+#include <cstdio>
+
+#include "kernels.hpp"
+
+namespace spmvhip {
+
+struct TempTally { size_t cur = 0, peak = 0; };     // bytes held now by the buffers that share it, and the most they held
+
+// freed when it leaves scope: the caller sees to it that no kernel still uses it then (a synchronised stream)
+struct TempBuf {
+    void* p = nullptr;
+    size_t n = 0;                                   // bytes asked for (the allocation itself has a floor of one byte)
+    TempTally* tally;
+    explicit TempBuf(TempTally* t = nullptr) : tally(t) {}
+    TempBuf(const TempBuf&) = delete;
+    TempBuf& operator=(const TempBuf&) = delete;
+    ~TempBuf() { release(); }
+    void release() {
+        if (!p) return;
+        (void)hipFree(p);
+        if (tally) tally->cur -= n;
+        p = nullptr; n = 0;
+    }
+    hipError_t alloc(size_t bytes) {                // a buffer that holds memory gives it back first
+        release();
+        const hipError_t e = hipMalloc(&p, std::max<size_t>(bytes, 1));
+        if (e != hipSuccess) { p = nullptr; return e; }
+        n = bytes;
+        if (tally) { tally->cur += n; tally->peak = std::max(tally->peak, tally->cur); }
+        return e;
+    }
+    template <typename T> T* as() const { return static_cast<T*>(p); }
+};
+
+// call(nullptr, bytes) asks a rocPRIM algorithm for its workspace size, call(ws.p, bytes) runs it on `stream`.  ws grows
+// only when it holds less (the size is no monotonic function of the item count); a workspace that already holds memory
+// may still be in use by what the stream has queued, so the stream is synchronised before it is replaced.  Returns the
+// error of the step that failed; ws.n is the size of the workspace afterwards.
+template <typename F>
+hipError_t withWorkspace(TempBuf& ws, hipStream_t stream, F&& call) {
+    size_t bytes = 0;
+    hipError_t e = call(nullptr, bytes);
+    if (e != hipSuccess) return e;
+    if (!ws.p || bytes > ws.n) {
+        if (ws.p && (e = hipStreamSynchronize(stream)) != hipSuccess) return e;
+        if ((e = ws.alloc(bytes)) != hipSuccess) return e;
+    }
+    return call(ws.p, bytes);
+}
+
+// The iterator types are the callers' (a rocPRIM kernel is instantiated on them): pass the pointers as they are held.
+// Stable sorts of key bits [beginBit, endBit).
+template <typename KI, typename KO, typename VI, typename VO>
+hipError_t sortPairs(TempBuf& ws, KI keysIn, KO keysOut, VI valsIn, VO valsOut, size_t n, unsigned beginBit, unsigned endBit,
+                     hipStream_t stream) {
+    return withWorkspace(ws, stream, [&](void* tmp, size_t& bytes) {
+        return rocprim::radix_sort_pairs(tmp, bytes, keysIn, keysOut, valsIn, valsOut, n, beginBit, endBit, stream);
+    });
+}
+// ... ping-pong between the two halves of each double buffer (no third full-size pair inside the workspace); the sorted
+// data is where current() points afterwards
+template <typename K, typename V>
+hipError_t sortPairs(TempBuf& ws, rocprim::double_buffer<K>& keys, rocprim::double_buffer<V>& vals, size_t n, unsigned beginBit,
+                     unsigned endBit, hipStream_t stream) {
+    return withWorkspace(ws, stream, [&](void* tmp, size_t& bytes) {
+        return rocprim::radix_sort_pairs(tmp, bytes, keys, vals, n, beginBit, endBit, stream);
+    });
+}
+template <typename KI, typename KO>
+hipError_t sortKeys(TempBuf& ws, KI keysIn, KO keysOut, size_t n, unsigned beginBit, unsigned endBit, hipStream_t stream) {
+    return withWorkspace(ws, stream, [&](void* tmp, size_t& bytes) {
+        return rocprim::radix_sort_keys(tmp, bytes, keysIn, keysOut, n, beginBit, endBit, stream);
+    });
+}
+// out[i] = init + in[0] + ... + in[i - 1], summed in the output's type
+template <typename In, typename T>
+hipError_t exclusiveScan(TempBuf& ws, In in, T* out, T init, size_t n, hipStream_t stream) {
+    return withWorkspace(ws, stream, [&](void* tmp, size_t& bytes) {
+        return rocprim::exclusive_scan(tmp, bytes, in, out, init, n, rocprim::plus<T>(), stream);
+    });
+}
+
+void enqueueIota(uint64_t n, uint32_t* p, hipStream_t stream);                  // p[i] = i          (transpose.hip)
+void enqueueFill32(uint32_t* p, uint64_t n, uint32_t v, hipStream_t stream);    // p[i] = v
+
+// the bits that hold every key below n (at least 1, at most 32); every key in [0, maxKey] needs bitsFor(maxKey + 1)
+inline unsigned bitsFor(uint64_t n) {
+    unsigned bits = 1;
+    while (bits < 32 && (1ull << bits) < n) ++bits;
+    return bits;
+}
+
+// the grid of `items` dealt perBlock to a workgroup of `threads` lanes
+inline dim3 gridFor(uint64_t items, uint32_t perBlock = WG_THREADS, unsigned threads = WG_THREADS) {
+    return grid2d((items + perBlock - 1) / perBlock, threads);
+}
+
+// a failed step of a synchronous build: the sticky error cleared, one line, and the stream synchronised -- nothing may
+// still use the caller's temporaries when they go
+inline int buildFail(hipStream_t stream, const char* module, const char* what) {
+    (void)hipGetLastError();
+    fprintf(stderr, "libspmvhip: %s: %s failed\n", module, what);
+    (void)hipStreamSynchronize(stream);
+    return EXIT_FAILURE;
+}
+
+}  // namespace spmvhip

@@ -25,6 +25,7 @@
 
 #include "spmvHip.h"
 #include "kernels.hpp"
+#include "device_prims.hpp"
 
 namespace spmvhip {
 namespace {
@@ -171,11 +172,6 @@ void launchIluWidth(const DevMat* d, const TriSchedule* s, uint32_t G, uint32_t*
     else              launchIlu<8, I>(d, s, longRows, st);
 }
 
-struct Words {
-    uint32_t* p = nullptr;
-    ~Words() { if (p) (void)hipFree(p); }
-};
-
 }  // namespace
 
 int iluUnsortedRow(const DevMat* d, hipStream_t st, long* row) {
@@ -191,15 +187,16 @@ int iluUnsortedRow(const DevMat* d, hipStream_t st, long* row) {
 
 int iluFactor(DevMat* d, uint32_t G, hipStream_t st) {
     const TriSchedule* s = d->tri[SPMV_TRI_LOWER];
-    Words w;
+    TempBuf words;
     uint32_t h[2] = {NO_ROW, 0};                    // [0] the zero pivot, [1] rows on the long-row path
-    HIP_TRY(hipMalloc(&w.p, 8));
-    HIP_TRY(hipMemcpyAsync(w.p, h, 8, hipMemcpyHostToDevice, st));
-    withIrp(d, [&](auto irp) { launchIluWidth<IrpT<decltype(irp)>>(d, s, G, w.p + 1, st); });
+    HIP_TRY(words.alloc(8));
+    uint32_t* const w = words.as<uint32_t>();
+    HIP_TRY(hipMemcpyAsync(w, h, 8, hipMemcpyHostToDevice, st));
+    withIrp(d, [&](auto irp) { launchIluWidth<IrpT<decltype(irp)>>(d, s, G, w + 1, st); });
     hipLaunchKernelGGL(ilu0_pivot_kernel, grid2d((d->M + ILU_THREADS - 1) / ILU_THREADS, ILU_THREADS), dim3(ILU_THREADS), 0, st,
-                       d->M, s->diagPos, d->AS, w.p);
+                       d->M, s->diagPos, d->AS, w);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(h, w.p, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h, w, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     d->ilu.zeroPivot = h[0] == NO_ROW ? -1 : (long)h[0];
     d->ilu.levels = s->info.levels;

@@ -31,13 +31,12 @@
 //     a whole slice): they are processed workgroup-per-row from the CSR arrays (shuffle tree).
 #include <hip/hip_runtime.h>
 #include <cstring>
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 #include <algorithm>
 #include <vector>
 
 #include "spmvHip.h"
-#include "device_mat.hpp"
+#include "kernels.hpp"
+#include "device_prims.hpp"
 
 namespace spmvhip {
 
@@ -190,62 +189,43 @@ __global__ __launch_bounds__(256) void sell_flag_long_kernel(uint64_t n, const I
     if ((uint64_t)IRP[row + 1] - (uint64_t)IRP[row] > SELL_MAX_ROW) perm[p] = row | 0x80000000u;
 }
 
-#define SELL_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { (void)hipGetLastError(); fprintf(stderr, "libspmvhip: sell: %s: %s\n", #expr, hipGetErrorString(e_)); return EXIT_FAILURE; } } while (0)
-
-struct Tmp {
-    void* p = nullptr;
-    ~Tmp() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, std::max<size_t>(bytes, 1)); }
-    template <typename T> T* as() { return static_cast<T*>(p); }
-};
-
 template <typename I>
 int buildSellT(DevMat* d, SellFormat* f) {
     const uint64_t M = d->M;
     const I* IRP = static_cast<const I*>(d->IRP);
     const uint64_t padded = (M + SELL_C - 1) / SELL_C * SELL_C;
     f->nSlices = (uint32_t)(padded / SELL_C);
-    Tmp keys, keysOut, rows, sortTmp, cells, scanTmp;
+    TempBuf keys, keysOut, rows, sortTmp, cells, scanTmp;
     if (keys.alloc(padded * 8) || keysOut.alloc(padded * 8) || rows.alloc(padded * 4) || cells.alloc(((size_t)f->nSlices + 1) * 8)) return EXIT_FAILURE;
-    SELL_TRY(hipMalloc(&f->perm, std::max<size_t>(padded, 1) * 4));
-    SELL_TRY(hipMalloc(&f->slen, std::max<size_t>(padded, 1) * 4));
-    SELL_TRY(hipMalloc(&f->sliceOff, ((size_t)f->nSlices + 1) * 8));
+    HIP_TRY(hipMalloc(&f->perm, std::max<size_t>(padded, 1) * 4));
+    HIP_TRY(hipMalloc(&f->slen, std::max<size_t>(padded, 1) * 4));
+    HIP_TRY(hipMalloc(&f->sliceOff, ((size_t)f->nSlices + 1) * 8));
     const dim3 gRows = grid2d((padded + 255) / 256, 256);
     const uint32_t sigma = SELL_SIGMA;              // whole slices: a window that ends inside a slice would break "first row of a slice is its longest"
     hipLaunchKernelGGL((sell_keys_kernel<I>), gRows, dim3(256), 0, nullptr, M, padded, sigma, IRP, keys.as<uint64_t>(), rows.as<uint32_t>());
-    size_t tmpBytes = 0;
-    SELL_TRY(rocprim::radix_sort_pairs(nullptr, tmpBytes, keys.as<uint64_t>(), keysOut.as<uint64_t>(), rows.as<uint32_t>(), f->perm,
-                                       (size_t)padded, 0, 64, (hipStream_t) nullptr));
-    if (sortTmp.alloc(tmpBytes)) return EXIT_FAILURE;
-    SELL_TRY(rocprim::radix_sort_pairs(sortTmp.p, tmpBytes, keys.as<uint64_t>(), keysOut.as<uint64_t>(), rows.as<uint32_t>(), f->perm,
-                                       (size_t)padded, 0, 64, (hipStream_t) nullptr));
+    HIP_TRY(sortPairs(sortTmp, keys.as<uint64_t>(), keysOut.as<uint64_t>(), rows.as<uint32_t>(), f->perm, (size_t)padded, 0, 64, nullptr));
     hipLaunchKernelGGL((sell_widths_kernel<I>), gRows, dim3(256), 0, nullptr, M, f->nSlices, IRP, f->perm, f->slen, cells.as<uint64_t>());
-    SELL_TRY(hipMemsetAsync(cells.as<uint64_t>() + f->nSlices, 0, 8, nullptr));
-    size_t scanBytes = 0;
-    SELL_TRY(rocprim::exclusive_scan(nullptr, scanBytes, cells.as<uint64_t>(), f->sliceOff, (uint64_t)0, (size_t)f->nSlices + 1,
-                                     rocprim::plus<uint64_t>(), (hipStream_t) nullptr));
-    if (scanTmp.alloc(scanBytes)) return EXIT_FAILURE;
-    SELL_TRY(rocprim::exclusive_scan(scanTmp.p, scanBytes, cells.as<uint64_t>(), f->sliceOff, (uint64_t)0, (size_t)f->nSlices + 1,
-                                     rocprim::plus<uint64_t>(), (hipStream_t) nullptr));
+    HIP_TRY(hipMemsetAsync(cells.as<uint64_t>() + f->nSlices, 0, 8, nullptr));
+    HIP_TRY(exclusiveScan(scanTmp, cells.as<uint64_t>(), f->sliceOff, (uint64_t)0, (size_t)f->nSlices + 1, nullptr));
     uint64_t total = 0;
-    SELL_TRY(hipMemcpy(&total, f->sliceOff + f->nSlices, 8, hipMemcpyDeviceToHost));
-    SELL_TRY(hipMalloc(&f->val, std::max<uint64_t>(total, 1) * 8));
-    SELL_TRY(hipMalloc(&f->col, std::max<uint64_t>(total, 1) * 4));
+    HIP_TRY(hipMemcpy(&total, f->sliceOff + f->nSlices, 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMalloc(&f->val, std::max<uint64_t>(total, 1) * 8));
+    HIP_TRY(hipMalloc(&f->col, std::max<uint64_t>(total, 1) * 4));
     if (f->nSlices)
         hipLaunchKernelGGL((sell_fill_kernel<I>), grid2d(((uint64_t)f->nSlices + 3) / 4, 256), dim3(256), 0, nullptr, f->nSlices,
                            f->sliceOff, f->perm, f->slen, IRP, d->JA, d->AS, f->val, f->col);
     // long rows
-    Tmp counter;
+    TempBuf counter;
     if (counter.alloc(4)) return EXIT_FAILURE;
-    SELL_TRY(hipMemsetAsync(counter.p, 0, 4, nullptr));
-    SELL_TRY(hipMalloc(&f->longRows, std::max<uint64_t>(std::min<uint64_t>(M, d->NZ / SELL_MAX_ROW + 1), 1) * 4));
+    HIP_TRY(hipMemsetAsync(counter.p, 0, 4, nullptr));
+    HIP_TRY(hipMalloc(&f->longRows, std::max<uint64_t>(std::min<uint64_t>(M, d->NZ / SELL_MAX_ROW + 1), 1) * 4));
     if (M) {
         hipLaunchKernelGGL((sell_longlist_kernel<I>), grid2d((M + 255) / 256, 256), dim3(256), 0, nullptr, M, IRP, f->longRows, counter.as<uint32_t>());
         hipLaunchKernelGGL((sell_flag_long_kernel<I>), gRows, dim3(256), 0, nullptr, padded, IRP, f->perm);
     }
-    SELL_TRY(hipGetLastError());
-    SELL_TRY(hipMemcpy(&f->nLong, counter.p, 4, hipMemcpyDeviceToHost));
-    SELL_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(&f->nLong, counter.p, 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipDeviceSynchronize());
     f->bytes = total * 12 + padded * 8 + ((size_t)f->nSlices + 1) * 8 + (size_t)f->nLong * 4;
     return EXIT_SUCCESS;
 }

@@ -16,19 +16,17 @@
 //      compacted and sorted by column (rank by counting for short rows, bitonic over the table otherwise).
 //   3. sorted path (rows above the group class, and whatever the options send there): batches of rows whose products fit
 //      the budget are expanded to (row in batch << 32 | j, product) in (p, q) order and sorted by ONE stable
-//      rocprim::radix_sort; a wavefront per row counts the run heads (symbolic) or lets one lane per head add its run
+//      radix sort; a wavefront per row counts the run heads (symbolic) or lets one lane per head add its run
 //      serially from +0.0 (numeric).  The symbolic phase keeps nothing but the counts; the numeric phase expands again.
 // Every kernel of a row-list launch covers the count the host read; no kernel spins or waits on a flag.
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 #include <algorithm>
 #include <chrono>
-#include <cstdio>
 #include <vector>
 
 #include "spmvHip.h"
 #include "kernels.hpp"
+#include "device_prims.hpp"
 
 namespace spmvhip {
 
@@ -43,7 +41,7 @@ struct SpgemmPlan {
 
 namespace {
 
-constexpr uint32_t SG_THREADS = 256;
+constexpr uint32_t SG_THREADS = WG_THREADS;                    // (what gridFor deals to by default)
 constexpr uint32_t SG_EMPTY = 0xFFFFFFFFu;
 constexpr uint32_t SG_LONG = 64;                               // entries of A's row above which the bound takes a wavefront
 constexpr uint32_t SG_WAVE_SLOTS = 1024, SG_WAVE_MAX = 512;    // min(ub, B.N) <= MAX: the table can never fill
@@ -51,31 +49,6 @@ constexpr uint32_t SG_GROUP_SLOTS = 8192, SG_GROUP_MAX = 6144;
 constexpr uint32_t SG_WAVE_RANK = 128, SG_GROUP_RANK = 512;    // rows of at most this many entries are ranked by counting
 constexpr uint64_t SG_BUDGET = 256ull << 20, SG_BUDGET_MAX = 4ull << 30;
 constexpr uint64_t SG_PRODUCT_BYTES = 32;                      // keys in / out and values in / out of the sort
-
-struct Temps { size_t cur = 0, peak = 0; };
-struct TempBuf {
-    void* p = nullptr;
-    size_t n = 0;
-    Temps* tm;
-    explicit TempBuf(Temps& t) : tm(&t) {}
-    TempBuf(const TempBuf&) = delete;
-    ~TempBuf() { release(); }
-    void release() { if (p) { (void)hipFree(p); tm->cur -= n; p = nullptr; n = 0; } }
-    hipError_t alloc(size_t bytes) {
-        release();
-        const hipError_t e = hipMalloc(&p, std::max<size_t>(bytes, 1));
-        if (e == hipSuccess) { n = bytes; tm->cur += n; tm->peak = std::max(tm->peak, tm->cur); } else p = nullptr;
-        return e;
-    }
-    template <typename T> T* as() { return static_cast<T*>(p); }
-};
-
-inline dim3 gridFor(uint64_t items, uint32_t perBlock = SG_THREADS) { return grid2d((items + perBlock - 1) / perBlock, SG_THREADS); }
-inline unsigned bitsFor(uint64_t n) {
-    unsigned bits = 1;
-    while (bits < 32 && (1ull << bits) < n) ++bits;
-    return bits;
-}
 
 // ---------------------------------------------------------------------------------------------------- 1. upper bound
 template <typename IB>
@@ -406,19 +379,14 @@ struct Run {
     const DevMat *a, *b;
     SpgemmPlan* plan;
     hipStream_t st;
-    Temps tm;
+    TempTally tm;                                              // every temporary of the call counts into it: tempBytes = its peak
     // the sorted path: products before each of its rows, and the batches [batch[i], batch[i + 1]) of its list
-    TempBuf off{tm};
+    TempBuf off{&tm};
     std::vector<uint64_t> hOff;
     std::vector<uint32_t> batch;
 };
 
-int fail(hipStream_t st, const char* what) {
-    (void)hipGetLastError();
-    fprintf(stderr, "libspmvhip: spgemm: %s failed\n", what);
-    (void)hipStreamSynchronize(st);                            // nothing may still use the temporaries when they go
-    return EXIT_FAILURE;
-}
+int fail(hipStream_t st, const char* what) { return buildFail(st, "spgemm", what); }
 
 template <typename F> auto withBoth(const DevMat* a, const DevMat* b, F&& f) {
     return withIrp(a, [&](auto ia) { return withIrp(b, [&](auto ib) { return f(ia, ib); }); });
@@ -453,7 +421,7 @@ int sortedPrepare(Run& r) {
     const uint32_t n = pl->nSorted;
     if (!n) return EXIT_SUCCESS;
     const uint32_t* list = pl->list + pl->nWave + pl->nGroup;
-    TempBuf ubS(r.tm), scanTmp(r.tm), flag(r.tm);
+    TempBuf ubS(&r.tm), scanTmp(&r.tm), flag(&r.tm);
     if (ubS.alloc(((size_t)n + 1) * 8) || r.off.alloc(((size_t)n + 1) * 8) || flag.alloc(4)) return fail(r.st, "temporary allocation (sorted rows)");
     if (hipMemsetAsync(ubS.p, 0, ((size_t)n + 1) * 8, r.st) != hipSuccess || hipMemsetAsync(flag.p, 0, 4, r.st) != hipSuccess) return fail(r.st, "memset");
     withBoth(r.a, r.b, [&](auto ia, auto ib) {
@@ -461,13 +429,7 @@ int sortedPrepare(Run& r) {
                            list, ia, r.a->JA, ib, r.b->M, ubS.as<uint64_t>(), false, flag.as<uint32_t>());
         return 0;
     });
-    size_t bytes = 0;
-    if (rocprim::exclusive_scan(nullptr, bytes, ubS.as<uint64_t>(), r.off.as<uint64_t>(), (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), r.st) !=
-            hipSuccess || scanTmp.alloc(bytes))
-        return fail(r.st, "scan workspace");
-    if (rocprim::exclusive_scan(scanTmp.p, bytes, ubS.as<uint64_t>(), r.off.as<uint64_t>(), (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), r.st) !=
-        hipSuccess)
-        return fail(r.st, "scan");
+    if (exclusiveScan(scanTmp, ubS.as<uint64_t>(), r.off.as<uint64_t>(), (uint64_t)0, (size_t)n + 1, r.st) != hipSuccess) return fail(r.st, "scan");
     r.hOff.resize((size_t)n + 1);
     if (hipMemcpyAsync(r.hOff.data(), r.off.p, r.hOff.size() * 8, hipMemcpyDeviceToHost, r.st) != hipSuccess ||
         hipStreamSynchronize(r.st) != hipSuccess)
@@ -494,15 +456,10 @@ int sortedPass(Run& r, uint32_t* counts, DevMat* c) {
         mostRows = std::max(mostRows, r.batch[i + 1] - r.batch[i]);
     }
     if (most >= (1ull << 40)) { fprintf(stderr, "libspmvhip: spgemm: a batch of %lu products is not supported\n", (unsigned long)most); return EXIT_FAILURE; }
-    TempBuf keyIn(r.tm), keyOut(r.tm), valIn(r.tm), valOut(r.tm), sortTmp(r.tm);
+    TempBuf keyIn(&r.tm), keyOut(&r.tm), valIn(&r.tm), valOut(&r.tm), sortTmp(&r.tm);
     if (keyIn.alloc(most * 8) || keyOut.alloc(most * 8) || (NUMERIC && (valIn.alloc(most * 8) || valOut.alloc(most * 8))))
         return fail(r.st, "temporary allocation (products of a batch)");
     const unsigned endBit = 32 + bitsFor(mostRows);
-    auto sort = [&](void* tmp, size_t& bytes, uint64_t n) {
-        return NUMERIC ? rocprim::radix_sort_pairs(tmp, bytes, keyIn.as<uint64_t>(), keyOut.as<uint64_t>(), valIn.as<double>(), valOut.as<double>(),
-                                                   (size_t)n, 0u, endBit, r.st)
-                       : rocprim::radix_sort_keys(tmp, bytes, keyIn.as<uint64_t>(), keyOut.as<uint64_t>(), (size_t)n, 0u, endBit, r.st);
-    };
     for (size_t i = 0; i + 1 < r.batch.size(); ++i) {
         const uint32_t k0 = r.batch[i], nRows = r.batch[i + 1] - k0;
         const uint64_t nProd = r.hOff[k0 + nRows] - r.hOff[k0];
@@ -512,10 +469,10 @@ int sortedPass(Run& r, uint32_t* counts, DevMat* c) {
                                nRows, list + k0, off, ia, r.a->JA, r.a->AS, ib, r.b->JA, r.b->AS, r.b->M, keyIn.as<uint64_t>(), valIn.as<double>());
             return 0;
         });
-        size_t bytes = 0;                                      // (the workspace is no monotonic function of the size)
-        if (sort(nullptr, bytes, nProd) != hipSuccess) return fail(r.st, "sort workspace");
-        if (bytes > sortTmp.n && (hipStreamSynchronize(r.st) != hipSuccess || sortTmp.alloc(bytes))) return fail(r.st, "sort workspace");
-        const hipError_t e = sort(sortTmp.p, bytes, nProd);
+        // (sortTmp is shared by the batches: it grows, after a wait for the batch before, only when one needs more)
+        const hipError_t e = NUMERIC ? sortPairs(sortTmp, keyIn.as<uint64_t>(), keyOut.as<uint64_t>(), valIn.as<double>(), valOut.as<double>(),
+                                                 (size_t)nProd, 0u, endBit, r.st)
+                                     : sortKeys(sortTmp, keyIn.as<uint64_t>(), keyOut.as<uint64_t>(), (size_t)nProd, 0u, endBit, r.st);
         if (e != hipSuccess) return fail(r.st, "sort");
         hipLaunchKernelGGL((sg_runs_kernel<NUMERIC>), gridFor(nRows, SG_THREADS / 64), dim3(SG_THREADS), 0, r.st, nRows, list + k0, off,
                            keyOut.as<uint64_t>(), valOut.as<double>(), counts, c ? static_cast<const uint32_t*>(c->IRP) : nullptr,
@@ -569,7 +526,7 @@ int spgemmBuild(const DevMat* a, const DevMat* b, const spmvSpgemmOpts* opts, De
     uint64_t nnzC = 0;
     if (M && a->NZ && b->NZ && BN) {
         // 1. the upper bound, the classes, the lists
-        TempBuf ub(r.tm), lists(r.tm), longList(r.tm), cnt(r.tm), tot(r.tm);
+        TempBuf ub(&r.tm), lists(&r.tm), longList(&r.tm), cnt(&r.tm), tot(&r.tm);
         const bool longRows = a->maxRowNnz > SG_LONG;
         if (ub.alloc(M * 8) || lists.alloc(M * 12) || cnt.alloc(5 * 4) || tot.alloc(16) || (longRows && longList.alloc(M * 4)))
             return fail(st, "temporary allocation (20 B per row)");
@@ -609,18 +566,12 @@ int spgemmBuild(const DevMat* a, const DevMat* b, const spmvSpgemmOpts* opts, De
         if (hipStreamSynchronize(st) != hipSuccess) return fail(st, "class lists");
         ub.release(); lists.release(); longList.release();
         // 2. symbolic: the counts, their scan, the row pointers
-        TempBuf counts(r.tm), irp64(r.tm), scanTmp(r.tm);
+        TempBuf counts(&r.tm), irp64(&r.tm), scanTmp(&r.tm);
         if (counts.alloc((M + 1) * 4) || irp64.alloc((M + 1) * 8)) return fail(st, "temporary allocation (12 B per row)");
         if (hipMemsetAsync(counts.p, 0, (M + 1) * 4, st) != hipSuccess || hipMemsetAsync(dCnt, 0, 4, st) != hipSuccess) return fail(st, "memset");
         if (sortedPrepare(r) || hashPass<false>(r, counts.as<uint32_t>(), nullptr) || sortedPass<false>(r, counts.as<uint32_t>(), nullptr))
             return EXIT_FAILURE;
-        size_t bytes = 0;
-        if (rocprim::exclusive_scan(nullptr, bytes, counts.as<uint32_t>(), irp64.as<uint64_t>(), (uint64_t)0, (size_t)M + 1, rocprim::plus<uint64_t>(), st) !=
-                hipSuccess || scanTmp.alloc(bytes))
-            return fail(st, "scan workspace");
-        if (rocprim::exclusive_scan(scanTmp.p, bytes, counts.as<uint32_t>(), irp64.as<uint64_t>(), (uint64_t)0, (size_t)M + 1, rocprim::plus<uint64_t>(), st) !=
-            hipSuccess)
-            return fail(st, "scan");
+        if (exclusiveScan(scanTmp, counts.as<uint32_t>(), irp64.as<uint64_t>(), (uint64_t)0, (size_t)M + 1, st) != hipSuccess) return fail(st, "scan");
         if (hipMemcpyAsync(&nnzC, irp64.as<uint64_t>() + M, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
             return fail(st, "row pointers");
         if (nnzC >= IRP32_LIMIT) {

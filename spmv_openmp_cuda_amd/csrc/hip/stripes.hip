@@ -53,13 +53,13 @@
 //     meet in a row (banded matrices: long add phases) the serial chain shows: +-16 Ki band 0.64 ms.
 #include <hip/hip_runtime.h>
 #include <cstring>
-#include <rocprim/device/device_radix_sort.hpp>
 #include <algorithm>
 #include <chrono>
 #include <vector>
 
 #include "spmvHip.h"
-#include "device_mat.hpp"
+#include "kernels.hpp"
+#include "device_prims.hpp"
 
 namespace spmvhip {
 
@@ -192,10 +192,6 @@ __global__ __launch_bounds__(256) void sb_map_kernel(uint64_t nnz, unsigned colB
     map[sb_cell(p - start[group], subStep[group])] = perm[p];
 }
 
-__global__ __launch_bounds__(256) void sb_fill32_kernel(uint32_t* __restrict__ p, uint64_t n, uint32_t v) {
-    const uint64_t i = lin_block() * 256 + threadIdx.x;
-    if (i < n) p[i] = v;
-}
 __global__ __launch_bounds__(256) void sb_fill16_kernel(uint16_t* __restrict__ p, uint64_t n, uint16_t v) {
     const uint64_t i = lin_block() * 256 + threadIdx.x;
     if (i < n) p[i] = v;
@@ -353,15 +349,6 @@ __global__ __launch_bounds__(SB_THREADS) void sb_spmv_kernel(
     }
 }
 
-#define SB_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { (void)hipGetLastError(); fprintf(stderr, "libspmvhip: stripes: %s: %s\n", #expr, hipGetErrorString(e_)); return EXIT_FAILURE; } } while (0)
-
-struct TempBuf {
-    void* p = nullptr;
-    ~TempBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, std::max<size_t>(bytes, 1)); }
-    template <typename T> T* as() { return static_cast<T*>(p); }
-};
-
 // Bins: consecutive rows, (nearly) equal entry counts, at most rMax rows.  Equal counts are what keeps the
 // workgroups of one XCD at the same place of their column sweeps; the bin count is a multiple of the workgroup count
 // (one workgroup per CU at a time: bins run in rounds) once the matrix is large enough for a full round.
@@ -400,29 +387,29 @@ int fillFormat(StripeFormat* f, bool wide, uint64_t nnz, unsigned colBits, const
     f->wide = wide;
     (void)hipFree(f->cr); (void)hipFree(f->lrowW); (void)hipFree(f->stepBase);
     f->cr = nullptr; f->lrowW = nullptr; f->stepBase = nullptr;
-    if (!f->val && !f->unit) SB_TRY(hipMalloc(&f->val, std::max<uint64_t>(cells, 1) * 8));
-    SB_TRY(hipMalloc(&f->cr, std::max<uint64_t>(cells, 1) * 4));
-    if (wide) SB_TRY(hipMalloc(&f->lrowW, std::max<uint64_t>(cells, 1) * 2));
-    else      SB_TRY(hipMalloc(&f->stepBase, std::max<uint64_t>(f->nSteps, 1) * 4));
+    if (!f->val && !f->unit) HIP_TRY(hipMalloc(&f->val, std::max<uint64_t>(cells, 1) * 8));
+    HIP_TRY(hipMalloc(&f->cr, std::max<uint64_t>(cells, 1) * 4));
+    if (wide) HIP_TRY(hipMalloc(&f->lrowW, std::max<uint64_t>(cells, 1) * 2));
+    else      HIP_TRY(hipMalloc(&f->stepBase, std::max<uint64_t>(f->nSteps, 1) * 4));
     // padding entries: value 0, local row SB_NONE (skipped by the kernel: 0 * x must not turn an Inf/NaN of x into a NaN of y)
-    if (f->val) SB_TRY(hipMemsetAsync(f->val, 0, cells * 8, nullptr));
+    if (f->val) HIP_TRY(hipMemsetAsync(f->val, 0, cells * 8, nullptr));
     if (cells) {
         if (wide) {
-            SB_TRY(hipMemsetAsync(f->cr, 0, cells * 4, nullptr));
+            HIP_TRY(hipMemsetAsync(f->cr, 0, cells * 4, nullptr));
             hipLaunchKernelGGL(sb_fill16_kernel, grid2d((cells + 255) / 256, 256), dim3(256), 0, nullptr, f->lrowW, cells, (uint16_t)SB_NONE);
         } else {
-            hipLaunchKernelGGL(sb_fill32_kernel, grid2d((cells + 255) / 256, 256), dim3(256), 0, nullptr, f->cr, cells, SB_NONE);
-            SB_TRY(hipMemsetAsync(f->stepBase, 0, f->nSteps * 4, nullptr));
+            enqueueFill32(f->cr, cells, SB_NONE, nullptr);
+            HIP_TRY(hipMemsetAsync(f->stepBase, 0, f->nSteps * 4, nullptr));
         }
     }
-    SB_TRY(hipMemsetAsync(dOverflow, 0, 4, nullptr));
+    HIP_TRY(hipMemsetAsync(dOverflow, 0, 4, nullptr));
     if (wide)
         hipLaunchKernelGGL(sb_scatter_kernel<true>, grid2d((nnz + 255) / 256, 256), dim3(256), 0, nullptr, nnz, colBits, f->subs, skeys, perm, rowOf, AS,
                            f->binRow, dStart, f->subStep, f->val, f->cr, f->lrowW, f->stepBase, dOverflow);
     else
         hipLaunchKernelGGL(sb_scatter_kernel<false>, grid2d((nnz + 255) / 256, 256), dim3(256), 0, nullptr, nnz, colBits, f->subs, skeys, perm, rowOf, AS,
                            f->binRow, dStart, f->subStep, f->val, f->cr, f->lrowW, f->stepBase, dOverflow);
-    SB_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return EXIT_SUCCESS;
 }
 
@@ -448,9 +435,8 @@ struct StripeSort {
 };
 const char* sortStripeKeys(const DevMat* d, const StripeFormat* f, StripeSort& s, uint64_t* dStart, hipStream_t stream) {
     const uint64_t nnz = d->NZ, M = d->M, nGroups = (uint64_t)f->B * f->subs;
-    unsigned groupBits = 1;
-    while (s.colBits < 32 && (1ull << s.colBits) < d->N) ++s.colBits;
-    while ((1ull << groupBits) < nGroups) ++groupBits;
+    const unsigned groupBits = bitsFor(nGroups);     // (fewer than 2^31 groups: planBins)
+    s.colBits = bitsFor(d->N);
     withIrp(d, [&](auto irp) {
         hipLaunchKernelGGL((sb_keys_kernel<IrpT<decltype(irp)>>), grid2d((M + 3) / 4, 256), dim3(256), 0, stream, M, irp, d->JA,
                            f->binRow, f->B, f->subs, s.colBits, s.keys.as<uint64_t>(), s.idx.as<uint32_t>(), s.rowOf.as<uint32_t>());
@@ -460,12 +446,7 @@ const char* sortStripeKeys(const DevMat* d, const StripeFormat* f, StripeSort& s
     // allocating a third full-size pair inside its temporary storage)
     rocprim::double_buffer<uint64_t> dKeys(s.keys.as<uint64_t>(), s.keysOut.as<uint64_t>());
     rocprim::double_buffer<uint32_t> dIdx(s.idx.as<uint32_t>(), s.perm.as<uint32_t>());
-    size_t tmpBytes = 0;
-    if (rocprim::radix_sort_pairs(nullptr, tmpBytes, dKeys, dIdx, (size_t)nnz, 0, s.colBits + groupBits, stream) != hipSuccess ||
-        s.sortTmp.alloc(tmpBytes))
-        return "sort workspace";
-    if (rocprim::radix_sort_pairs(s.sortTmp.p, tmpBytes, dKeys, dIdx, (size_t)nnz, 0, s.colBits + groupBits, stream) != hipSuccess)
-        return "sort";
+    if (sortPairs(s.sortTmp, dKeys, dIdx, (size_t)nnz, 0, s.colBits + groupBits, stream) != hipSuccess) return "sort";
     s.skeys = dKeys.current();
     s.sperm = dIdx.current();
     hipLaunchKernelGGL(sb_bounds_kernel, grid2d((nnz + 255) / 256, 256), dim3(256), 0, stream, nnz, s.colBits, s.skeys, nGroups, dStart);
@@ -505,8 +486,8 @@ int buildStripes(DevMat* d, const spmvStripesOpts* opts) {
         return EXIT_FAILURE;
     }
     int dev = 0, cusDev = 0;                         // one workgroup per CU of the CURRENT device (a process may drive several)
-    SB_TRY(hipGetDevice(&dev));
-    SB_TRY(hipDeviceGetAttribute(&cusDev, hipDeviceAttributeMultiprocessorCount, dev));
+    HIP_TRY(hipGetDevice(&dev));
+    HIP_TRY(hipDeviceGetAttribute(&cusDev, hipDeviceAttributeMultiprocessorCount, dev));
     cusDev = std::max(1, cusDev);
     if (o.rowsPerBin > SB_R_MAX || o.grid > (unsigned)cusDev || o.spread < -1 || o.spread > 1024 || o.deterministic < 0 || o.deterministic > 2) {
         fprintf(stderr, "libspmvhip: stripes: options out of range (rowsPerBin 0..%u, grid 0..%d, spread -1..1024, deterministic 0..2)\n", SB_R_MAX, cusDev);
@@ -514,17 +495,17 @@ int buildStripes(DevMat* d, const spmvStripesOpts* opts) {
     }
     if (slot) { freeStripes(slot); slot = nullptr; }
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    SB_TRY(hipEventCreate(&ev0));
-    SB_TRY(hipEventCreate(&ev1));
+    HIP_TRY(hipEventCreate(&ev0));
+    HIP_TRY(hipEventCreate(&ev1));
     struct EvGuard { hipEvent_t a, b; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } evGuard{ev0, ev1};
-    SB_TRY(hipEventRecord(ev0, nullptr));
+    HIP_TRY(hipEventRecord(ev0, nullptr));
 
     // row pointers on the host (bins are cut there)
     std::vector<uint64_t> irp(M + 1);
-    if (d->irpBytes == 8) SB_TRY(hipMemcpy(irp.data(), d->IRP, (M + 1) * 8, hipMemcpyDeviceToHost));
+    if (d->irpBytes == 8) HIP_TRY(hipMemcpy(irp.data(), d->IRP, (M + 1) * 8, hipMemcpyDeviceToHost));
     else {
         std::vector<uint32_t> tmp(M + 1);
-        SB_TRY(hipMemcpy(tmp.data(), d->IRP, (M + 1) * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(tmp.data(), d->IRP, (M + 1) * 4, hipMemcpyDeviceToHost));
         for (uint64_t i = 0; i <= M; ++i) irp[i] = tmp[i];
     }
     const uint32_t rMax = o.rowsPerBin ? o.rowsPerBin : SB_R_MAX;
@@ -626,7 +607,7 @@ int stripesRefreshValues(DevMat* d, StripeFormat* f, hipStream_t stream, double*
         if (srt.keys.alloc(nnz * 8) || srt.keysOut.alloc(nnz * 8) || srt.idx.alloc(nnz * 4) || srt.perm.alloc(nnz * 4) || srt.rowOf.alloc(nnz * 4) ||
             dStart.alloc((nGroups + 1) * 8))
             return fail("temporary allocation (28 B per entry)");
-        if (cells) hipLaunchKernelGGL(sb_fill32_kernel, grid2d((cells + 255) / 256, 256), dim3(256), 0, stream, f->vmap, cells, VMAP_NONE);
+        if (cells) enqueueFill32(f->vmap, cells, VMAP_NONE, stream);
         if (const char* step = sortStripeKeys(d, f, srt, dStart.as<uint64_t>(), stream)) return fail(step);
         hipLaunchKernelGGL(sb_map_kernel, grid2d((nnz + 255) / 256, 256), dim3(256), 0, stream, nnz, srt.colBits, srt.skeys, srt.sperm,
                            dStart.as<uint64_t>(), f->subStep, f->vmap);

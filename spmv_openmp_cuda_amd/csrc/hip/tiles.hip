@@ -38,13 +38,12 @@
 #include <cstring>
 #include <cmath>
 #include <chrono>
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 #include <algorithm>
 #include <vector>
 
 #include "spmvHip.h"
-#include "device_mat.hpp"
+#include "kernels.hpp"
+#include "device_prims.hpp"
 
 namespace spmvhip {
 
@@ -228,13 +227,9 @@ __global__ __launch_bounds__(256) void pb_fill_kernel(uint32_t* p, uint64_t n, u
     if (i < n) p[i] = v;
 }
 
-// value map (spmvHipUpdateValues): the build's sort again, on the same keys and bits, with the CSR position as payload.  A
-// stable sort's permutation depends on the keys alone, so sorted position p holds the same entry as val[p] of the build.
-__global__ __launch_bounds__(256) void pb_iota_kernel(uint64_t n, uint32_t* __restrict__ p) {
-    const uint64_t i = lin_block() * 256 + threadIdx.x;
-    if (i < n) p[i] = (uint32_t)i;
-}
-// ... and inverted: the refresh walks CSR order (values.hip)
+// value map (spmvHipUpdateValues): the build's sort again, on the same keys and bits, with the CSR position (an iota) as
+// payload.  A stable sort's permutation depends on the keys alone, so sorted position p holds the same entry as val[p] of
+// the build.  Inverted here: the refresh walks CSR order (values.hip)
 __global__ __launch_bounds__(256) void pb_invert_kernel(uint64_t n, const uint32_t* __restrict__ perm, uint32_t* __restrict__ inv) {
     const uint64_t p = lin_block() * 256 + threadIdx.x;
     if (p < n) inv[perm[p]] = (uint32_t)p;
@@ -767,15 +762,6 @@ __global__ __launch_bounds__(256) void pb_dupcount_kernel(uint32_t B, uint64_t n
     }
 }
 
-#define PB_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { (void)hipGetLastError(); fprintf(stderr, "libspmvhip: tiles: %s: %s\n", #expr, hipGetErrorString(e_)); return EXIT_FAILURE; } } while (0)
-
-struct TempBuf {
-    void* p = nullptr;
-    ~TempBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, std::max<size_t>(bytes, 1)); }
-    template <typename T> T* as() { return static_cast<T*>(p); }
-};
-
 }  // namespace
 
 // The products live in ONE workspace per device, shared by every matrix of the process: phase 1 of a matrix fills
@@ -955,7 +941,7 @@ static int sortIntoSlices(const DevMat* d, TileFormat* t, TileBuildTemps& tmp) {
     // buffer, 12 B/nnz (round 2 allocated 36 B/nnz of its own plus, inside rocPRIM's pointer interface, 18 more: on c5
     // ~90 GB mapped for a 19 GB format, a second of hipMalloc).  rocPRIM's double-buffer interface sorts between the two
     // pairs of buffers without further full-size storage.
-    PB_TRY(hipDeviceSynchronize());                  // nothing may still use the product workspace of this device
+    HIP_TRY(hipDeviceSynchronize());                  // nothing may still use the product workspace of this device
     prodIdle();
     const auto allocT0 = std::chrono::steady_clock::now();
     const size_t offLcol = (nnz * 8 + 255) / 256 * 256, offLrow = offLcol + (nnz * 2 + 255) / 256 * 256;
@@ -976,25 +962,20 @@ static int sortIntoSlices(const DevMat* d, TileFormat* t, TileBuildTemps& tmp) {
     PbPay* const payA = static_cast<PbPay*>(t->slab);
 
     withIrp(d, [&](auto irp) { hipLaunchKernelGGL((pb_payload_kernel<IrpT<decltype(irp)>>), grid2d((M + 3) / 4, 256), dim3(256), 0, nullptr, M, irp, d->JA, d->AS, keysA, payA); });
-    PB_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
 
-    unsigned bits = 1;
-    while ((1u << bits) < t->S) ++bits;
     rocprim::double_buffer<uint32_t> dKeys(keysA, keysA + nnz);
     rocprim::double_buffer<PbPay>    dPay(payA, payB.as<PbPay>());
-    size_t tmpBytes = 0;
-    PB_TRY(rocprim::radix_sort_pairs(nullptr, tmpBytes, dKeys, dPay, (size_t)nnz, PB_CBITS, PB_CBITS + bits, (hipStream_t) nullptr));
-    if (sortTmp.alloc(tmpBytes)) return buildFailed("sort workspace");
-    t->tempBytes += tmpBytes;
-    PB_TRY(rocprim::radix_sort_pairs(sortTmp.p, tmpBytes, dKeys, dPay, (size_t)nnz, PB_CBITS, PB_CBITS + bits, (hipStream_t) nullptr));
+    HIP_TRY(sortPairs(sortTmp, dKeys, dPay, (size_t)nnz, PB_CBITS, PB_CBITS + bitsFor(t->S), nullptr));
+    t->tempBytes += sortTmp.n;
     tmp.skeys = dKeys.current();
     if (dPay.current() == payA)                      // the sorted payload must not sit where val / lcol / lrow are about to be written
-        PB_TRY(hipMemcpyAsync(payB.p, payA, nnz * sizeof(PbPay), hipMemcpyDeviceToDevice, nullptr));
+        HIP_TRY(hipMemcpyAsync(payB.p, payA, nnz * sizeof(PbPay), hipMemcpyDeviceToDevice, nullptr));
     tmp.spay = payB.as<PbPay>();
 
     hipLaunchKernelGGL(pb_bounds_kernel, grid2d((nnz + 255) / 256, 256), dim3(256), 0, nullptr, nnz, tmp.spay, tmp.skeys, t->B, t->bins, nTiles,
                        tileStart.as<uint32_t>());
-    PB_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return EXIT_SUCCESS;
 }
 
@@ -1010,17 +991,11 @@ static int placeTiles(TileFormat* t, TileBuildTemps& tmp) {
     t->tempBytes += nTiles * 16;
     hipLaunchKernelGGL(pb_lens_kernel, grid2d((nTiles + 255) / 256, 256), dim3(256), 0, nullptr, t->S, t->B,
                        tileStart.as<uint32_t>(), lens.as<uint32_t>(), flags.as<uint32_t>());
-    size_t scanBytes = 0;
-    PB_TRY(rocprim::exclusive_scan(nullptr, scanBytes, lens.as<uint32_t>(), bmStart.as<uint32_t>(), 0u, (size_t)nTiles,
-                                   rocprim::plus<uint32_t>(), (hipStream_t) nullptr));
-    if (scanTmp.alloc(scanBytes)) return buildFailed("scan workspace");
-    PB_TRY(rocprim::exclusive_scan(scanTmp.p, scanBytes, lens.as<uint32_t>(), bmStart.as<uint32_t>(), 0u, (size_t)nTiles,
-                                   rocprim::plus<uint32_t>(), (hipStream_t) nullptr));
-    PB_TRY(rocprim::exclusive_scan(scanTmp.p, scanBytes, flags.as<uint32_t>(), listIdx.as<uint32_t>(), 0u, (size_t)nTiles,
-                                   rocprim::plus<uint32_t>(), (hipStream_t) nullptr));
+    HIP_TRY(exclusiveScan(scanTmp, lens.as<uint32_t>(), bmStart.as<uint32_t>(), 0u, (size_t)nTiles, nullptr));
+    HIP_TRY(exclusiveScan(scanTmp, flags.as<uint32_t>(), listIdx.as<uint32_t>(), 0u, (size_t)nTiles, nullptr));   // (the same size: scanTmp stays)
     uint32_t lastIdx = 0, lastFlag = 0;
-    PB_TRY(hipMemcpy(&lastIdx, listIdx.as<uint32_t>() + nTiles - 1, 4, hipMemcpyDeviceToHost));
-    PB_TRY(hipMemcpy(&lastFlag, flags.as<uint32_t>() + nTiles - 1, 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&lastIdx, listIdx.as<uint32_t>() + nTiles - 1, 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&lastFlag, flags.as<uint32_t>() + nTiles - 1, 4, hipMemcpyDeviceToHost));
     t->nList = lastIdx + lastFlag;
     if (t->nList >= P2_RUNS_FLAG) return buildFailed("tile list (more than 2^31 non-empty tiles)");
     if (hipMalloc(&t->tl, ((size_t)t->nList + TL_PAD) * sizeof(uint2))) return buildFailed("tile-list allocation");
@@ -1033,20 +1008,20 @@ static int placeTiles(TileFormat* t, TileBuildTemps& tmp) {
                        tileStart.as<uint32_t>(), bmStart.as<uint32_t>(), t->val, t->lcol, t->lrow, t->pidx);
     if (t->det) {
         // every wavefront walks a whole sub-bin: its cursor starts at the sub-bin's first tile
-        PB_TRY(hipMemcpyAsync(t->waveTile, binTile.p, (size_t)t->B * 4, hipMemcpyDeviceToDevice, nullptr));
+        HIP_TRY(hipMemcpyAsync(t->waveTile, binTile.p, (size_t)t->B * 4, hipMemcpyDeviceToDevice, nullptr));
     } else {
         TempBuf dupCount;
         if (dupCount.alloc((size_t)t->B * P2_WAVES * 4)) return buildFailed("run-count workspace");
-        PB_TRY(hipMemsetAsync(dupCount.p, 0, (size_t)t->B * P2_WAVES * 4, nullptr));
+        HIP_TRY(hipMemsetAsync(dupCount.p, 0, (size_t)t->B * P2_WAVES * 4, nullptr));
         hipLaunchKernelGGL(pb_dupcount_kernel, grid2d((nnz + 255) / 256, 256), dim3(256), 0, nullptr, t->B, nnz, t->binPos, t->lrow,
                            dupCount.as<uint32_t>());
         hipLaunchKernelGGL(pb_wavetile_kernel, grid2d(((uint64_t)t->B * P2_WAVES + 255) / 256, 256), dim3(256), 0, nullptr, t->B,
                            t->binPos, binTile.as<uint32_t>(), t->tl, dupCount.as<uint32_t>(), t->waveTile);
-        PB_TRY(hipGetLastError());
-        PB_TRY(hipDeviceSynchronize());              // dupCount goes out of scope
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipDeviceSynchronize());              // dupCount goes out of scope
     }
-    PB_TRY(hipGetLastError());
-    PB_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
     return EXIT_SUCCESS;
 }
 
@@ -1129,7 +1104,7 @@ static int setTilesKernelAttributes() {
         {(const void*)pb_reduce_kernel<0>, PB_R_MAX * 8},       {(const void*)pb_reduce_kernel<1>, PB_R_MAX * 8},
         {(const void*)pb_reduce_kernel<2>, PB_R_MAX * 8},       {(const void*)pb_reduce_det_kernel<0>, PB_R_MAX * 8},
         {(const void*)pb_reduce_det_kernel<1>, PB_R_MAX * 8},   {(const void*)pb_reduce_det_kernel<2>, PB_R_MAX * 8}};
-    for (const auto& a : attrs) PB_TRY(hipFuncSetAttribute(a.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, a.ldsBytes));
+    for (const auto& a : attrs) HIP_TRY(hipFuncSetAttribute(a.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, a.ldsBytes));
     return EXIT_SUCCESS;
 }
 
@@ -1150,10 +1125,10 @@ int buildTiles(DevMat* d, const spmvTilesOpts* opts) {
             t->cus = (uint32_t)cus;
     }
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    PB_TRY(hipEventCreate(&ev0));
-    PB_TRY(hipEventCreate(&ev1));
+    HIP_TRY(hipEventCreate(&ev0));
+    HIP_TRY(hipEventCreate(&ev1));
     struct EvGuard { hipEvent_t a, b; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } evGuard{ev0, ev1};
-    PB_TRY(hipEventRecord(ev0, nullptr));
+    HIP_TRY(hipEventRecord(ev0, nullptr));
     const TileGeometry g = planTileBins(d->M, t->cus, o);
     t->opts = o;
     t->S = (uint32_t)((d->N + PB_C - 1) / PB_C);
@@ -1167,24 +1142,24 @@ int buildTiles(DevMat* d, const spmvTilesOpts* opts) {
 
     // phase-1 work list from the slice boundaries (tileStart[s*B])
     std::vector<uint32_t> sliceStart(t->S + 1);
-    PB_TRY(hipMemcpy2D(sliceStart.data(), 4, tmp.tileStart.as<uint32_t>(), (size_t)t->B * 4, 4, t->S + 1, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy2D(sliceStart.data(), 4, tmp.tileStart.as<uint32_t>(), (size_t)t->B * 4, 4, t->S + 1, hipMemcpyDeviceToHost));
     t->chunk = o.chunk ? o.chunk : phase1Chunk(sliceStart, nnz, t->cus);
     const Phase1Plan plan = planPhase1Work(sliceStart, t->chunk, t->cus);
     t->nWork = (uint32_t)plan.work.size();
     t->grid1 = plan.runs.empty() ? 0 : (uint32_t)plan.runs.size() - 1;
-    PB_TRY(hipMalloc(&t->work, std::max<size_t>(plan.work.size(), 1) * sizeof(uint3)));
-    PB_TRY(hipMemcpy(t->work, plan.work.data(), plan.work.size() * sizeof(uint3), hipMemcpyHostToDevice));
-    PB_TRY(hipMalloc(&t->runs, std::max<size_t>(plan.runs.size(), 1) * sizeof(uint32_t)));
-    PB_TRY(hipMemcpy(t->runs, plan.runs.data(), plan.runs.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    PB_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMalloc(&t->work, std::max<size_t>(plan.work.size(), 1) * sizeof(uint3)));
+    HIP_TRY(hipMemcpy(t->work, plan.work.data(), plan.work.size() * sizeof(uint3), hipMemcpyHostToDevice));
+    HIP_TRY(hipMalloc(&t->runs, std::max<size_t>(plan.runs.size(), 1) * sizeof(uint32_t)));
+    HIP_TRY(hipMemcpy(t->runs, plan.runs.data(), plan.runs.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipDeviceSynchronize());
 
     if (setTilesKernelAttributes()) return EXIT_FAILURE;
     // products that fit the Infinity Cache (with room for x and the streams) are stored with the default policy so
     // that phase 2 finds them there; larger streams bypass it (microbench_mall.hip: resident 7.0 vs 5.8 TB/s with
     // non-temporal stores; non-resident 4.9 vs 5.1-5.4)
     t->ntStore = o.ntStore >= 0 ? o.ntStore != 0 : nnz * 8 > PB_RESIDENT_BYTES;
-    PB_TRY(hipEventRecord(ev1, nullptr));
-    PB_TRY(hipEventSynchronize(ev1));
+    HIP_TRY(hipEventRecord(ev1, nullptr));
+    HIP_TRY(hipEventSynchronize(ev1));
     float ms = 0;
     (void)hipEventElapsedTime(&ms, ev0, ev1);
     t->buildMs = ms;
@@ -1214,15 +1189,9 @@ int tilesRefreshValues(DevMat* d, TileFormat* t, hipStream_t stream, double* map
         } else {
             TempBuf idx, keysOut, perm, sortTmp;
             if (idx.alloc(nnz * 4) || keysOut.alloc(nnz * 4) || perm.alloc(nnz * 4)) return fail("temporary allocation (12 B per entry)");
-            hipLaunchKernelGGL(pb_iota_kernel, grid2d((nnz + 255) / 256, 256), dim3(256), 0, stream, nnz, idx.as<uint32_t>());
-            unsigned bits = 1;
-            while ((1u << bits) < t->S) ++bits;
-            size_t tmpBytes = 0;
-            if (rocprim::radix_sort_pairs(nullptr, tmpBytes, d->JA, keysOut.as<uint32_t>(), idx.as<uint32_t>(), perm.as<uint32_t>(), (size_t)nnz,
-                                          PB_CBITS, PB_CBITS + bits, stream) != hipSuccess || sortTmp.alloc(tmpBytes))
-                return fail("sort workspace");
-            if (rocprim::radix_sort_pairs(sortTmp.p, tmpBytes, d->JA, keysOut.as<uint32_t>(), idx.as<uint32_t>(), perm.as<uint32_t>(), (size_t)nnz,
-                                          PB_CBITS, PB_CBITS + bits, stream) != hipSuccess)
+            enqueueIota(nnz, idx.as<uint32_t>(), stream);
+            if (sortPairs(sortTmp, d->JA, keysOut.as<uint32_t>(), idx.as<uint32_t>(), perm.as<uint32_t>(), (size_t)nnz, PB_CBITS,
+                          PB_CBITS + bitsFor(t->S), stream) != hipSuccess)
                 return fail("sort");
             hipLaunchKernelGGL(pb_invert_kernel, grid2d((nnz + 255) / 256, 256), dim3(256), 0, stream, nnz, perm.as<uint32_t>(), t->vmap);
             if (hipGetLastError() != hipSuccess) return fail("map kernels");

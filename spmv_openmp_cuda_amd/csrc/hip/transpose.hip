@@ -10,7 +10,7 @@
 //
 // Steps, all on the library stream, none with atomics (the arrays are the same on every run):
 //   1. iota payload (in the room of ASt, which is written last)
-//   2. rocprim::radix_sort_pairs of JA over bits [0, ceil(log2 N)): keys into JAt (the room is free until step 5),
+//   2. the stable radix sort of JA over bits [0, ceil(log2 N)): keys into JAt (the room is free until step 5),
 //      payload into the map
 //   3. tr_bounds_kernel: IRPt from the sorted keys -- empty columns included, and the final NZ
 //   4. tr_row_of_kernel: the source row of every CSR position (a 4 B/nnz temporary)
@@ -19,12 +19,10 @@
 // its addresses, and a binary search over M rows is ~log2(M) dependent gathers per entry (24 on
 // c3); the expansion is one streamed write of 4 B/nnz and ONE more gather per entry, at the index AS is gathered at.
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_radix_sort.hpp>
-#include <algorithm>
-#include <cstdio>
 
 #include "spmvHip.h"
 #include "kernels.hpp"
+#include "device_prims.hpp"
 
 namespace spmvhip {
 
@@ -35,16 +33,14 @@ constexpr uint32_t TR_PER_THREAD = 8;                          // positions per 
 constexpr uint32_t TR_CHUNK = TR_THREADS * TR_PER_THREAD;
 constexpr uint32_t TR_ROW_LANES = 16;                          // lanes per source row in tr_row_of_kernel
 
-struct TempBuf {
-    void* p = nullptr;
-    ~TempBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, std::max<size_t>(bytes, 1)); }
-    template <typename T> T* as() { return static_cast<T*>(p); }
-};
-
-__global__ __launch_bounds__(TR_THREADS) void tr_iota_kernel(uint64_t n, uint32_t* __restrict__ p) {
+// the two kernels of device_prims.hpp
+__global__ __launch_bounds__(TR_THREADS) void iota_kernel(uint64_t n, uint32_t* __restrict__ p) {
     const uint64_t i = linear_block() * TR_THREADS + threadIdx.x;
     if (i < n) p[i] = (uint32_t)i;
+}
+__global__ __launch_bounds__(TR_THREADS) void fill32_kernel(uint32_t* __restrict__ p, uint64_t n, uint32_t v) {
+    const uint64_t i = linear_block() * TR_THREADS + threadIdx.x;
+    if (i < n) p[i] = v;
 }
 
 // IRPt[c] = the first sorted position whose key is >= c.  Lane p (0 <= p <= nnz) writes the columns in
@@ -106,10 +102,31 @@ __global__ __launch_bounds__(TR_THREADS) void tr_place_kernel(uint64_t n, const 
 
 }  // namespace
 
-// also the dependents list of a triangular solve's analysis (trsv.hip)
+void enqueueIota(uint64_t n, uint32_t* p, hipStream_t st) {
+    hipLaunchKernelGGL(iota_kernel, gridFor(n, TR_THREADS, TR_THREADS), dim3(TR_THREADS), 0, st, n, p);
+}
+
+void enqueueFill32(uint32_t* p, uint64_t n, uint32_t v, hipStream_t st) {
+    hipLaunchKernelGGL(fill32_kernel, gridFor(n, TR_THREADS, TR_THREADS), dim3(TR_THREADS), 0, st, p, n, v);
+}
+
 void enqueueSortedBounds(uint64_t nnz, uint64_t N, const uint32_t* keys, uint32_t* ptr, hipStream_t st) {
     hipLaunchKernelGGL(tr_bounds_kernel, grid2d((nnz + 1 + TR_THREADS - 1) / TR_THREADS, TR_THREADS), dim3(TR_THREADS), 0, st,
                        nnz, N, keys, ptr);
+}
+
+// The pattern sorted by column: the stable sort of (keys, payload) over the low `bits` key bits into (keysOut,
+// payloadOut), then ptr[0 .. N] from the sorted keys.  Payload = the row of every position: the transposed pattern (the
+// dependents of a triangular analysis, the incoming side of a colouring); = an iota: the transpose's value map.  The
+// pointers are not const: rocPRIM's kernels are instantiated on the iterator types, and every caller holds plain ones.
+hipError_t enqueueSortedByColumn(uint64_t nnz, uint64_t N, unsigned bits, uint32_t* keys, uint32_t* payload, uint32_t* keysOut,
+                                 uint32_t* payloadOut, uint32_t* ptr, TempBuf& ws, hipStream_t st) {
+    if (nnz) {
+        const hipError_t e = sortPairs(ws, keys, keysOut, payload, payloadOut, (size_t)nnz, 0u, bits, st);
+        if (e != hipSuccess) return e;
+    }
+    enqueueSortedBounds(nnz, N, keysOut, ptr, st);
+    return hipSuccess;
 }
 
 void enqueueRowOf(uint64_t M, const void* IRP, int irpBytes, uint32_t* rowOf, hipStream_t st) {
@@ -122,26 +139,13 @@ int transposeCsr(const DevMat* a, DevMat* t, hipStream_t st) {
     const uint64_t nnz = a->NZ, M = a->M, N = a->N;
     uint32_t* const IRPt = static_cast<uint32_t*>(t->IRP);
     TempBuf rowOf, sortTmp;
-    auto fail = [&](const char* what) {
-        (void)hipGetLastError();
-        fprintf(stderr, "libspmvhip: transpose: %s failed\n", what);
-        (void)hipStreamSynchronize(st);                   // nothing may still use the temporaries when they go
-        return EXIT_FAILURE;
-    };
+    auto fail = [&](const char* what) { return buildFail(st, "transpose", what); };
+    uint32_t* const iota = reinterpret_cast<uint32_t*>(t->AS);
     if (nnz) {
         if (rowOf.alloc(nnz * 4)) return fail("temporary allocation (4 B per entry)");
-        uint32_t* const iota = reinterpret_cast<uint32_t*>(t->AS);
-        hipLaunchKernelGGL(tr_iota_kernel, grid2d((nnz + TR_THREADS - 1) / TR_THREADS, TR_THREADS), dim3(TR_THREADS), 0, st, nnz, iota);
-        unsigned bits = 1;
-        while (bits < 32 && (1ull << bits) < N) ++bits;
-        size_t tmpBytes = 0;
-        if (rocprim::radix_sort_pairs(nullptr, tmpBytes, a->JA, t->JA, iota, t->tmap, (size_t)nnz, 0u, bits, st) != hipSuccess ||
-            sortTmp.alloc(tmpBytes))
-            return fail("sort workspace");
-        if (rocprim::radix_sort_pairs(sortTmp.p, tmpBytes, a->JA, t->JA, iota, t->tmap, (size_t)nnz, 0u, bits, st) != hipSuccess)
-            return fail("sort");
+        enqueueIota(nnz, iota, st);
     }
-    enqueueSortedBounds(nnz, N, t->JA, IRPt, st);
+    if (enqueueSortedByColumn(nnz, N, bitsFor(N), a->JA, iota, t->JA, t->tmap, IRPt, sortTmp, st) != hipSuccess) return fail("sort");
     if (nnz) {
         enqueueRowOf(M, a->IRP, a->irpBytes, rowOf.as<uint32_t>(), st);
         hipLaunchKernelGGL(tr_place_kernel, grid2d((nnz + TR_CHUNK - 1) / TR_CHUNK, TR_THREADS), dim3(TR_THREADS), 0, st,

@@ -19,14 +19,13 @@
 // wavefront per long row), trsv_run_kernel for a run of consecutive thin levels in ONE workgroup with a barrier between
 // levels.  No flags, tickets or spins: ordering across workgroups comes only from kernel boundaries on one stream.
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_radix_sort.hpp>
 #include <algorithm>
 #include <chrono>
-#include <cstdio>
 #include <vector>
 
 #include "spmvHip.h"
 #include "kernels.hpp"
+#include "device_prims.hpp"
 
 namespace spmvhip {
 
@@ -45,13 +44,6 @@ constexpr uint32_t TRI_AHEAD = 8;               // gathers in flight per lane on
 constexpr uint32_t TRI_BATCH = 64;              // analysis steps enqueued per host read-back
 constexpr uint32_t TRI_WIDE_BLOCKS = 1024;      // grid of the wide peeling kernel (grid-stride)
 constexpr uint32_t NO_ROW = 0xFFFFFFFFu;
-
-struct TempBuf {
-    void* p = nullptr;
-    ~TempBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, std::max<size_t>(bytes, 1)); }
-    template <typename T> T* as() { return static_cast<T*>(p); }
-};
 
 // the strict triangle: lower j < i, upper i < j < N (a column id >= N of an adopted handle is never read)
 __device__ __forceinline__ bool in_tri(uint64_t j, uint64_t i, int upper, uint64_t N) {
@@ -172,11 +164,6 @@ __global__ __launch_bounds__(TRI_THREADS) void tri_split_kernel(uint64_t M, cons
     if ((k & 1u) && (p == 0 || keys[p - 1] != k)) split[k >> 1] = (uint32_t)p;
 }
 
-__global__ __launch_bounds__(TRI_THREADS) void tri_iota_kernel(uint64_t n, uint32_t* __restrict__ p) {
-    const uint64_t i = linear_block() * TRI_THREADS + threadIdx.x;
-    if (i < n) p[i] = (uint32_t)i;
-}
-
 // ------------------------------------------------------------------------------------------------ solve
 // row i on one lane: its strict-triangle products in stored order, TRI_AHEAD gathers of x in flight, adds in order
 // (an entry outside the triangle is skipped, never added as 0.0: -0.0 + 0.0 is +0.0)
@@ -291,12 +278,6 @@ void launchSteps(const DevMat* d, const TriSchedule* s, int upper, int dunit, co
     }
 }
 
-unsigned keyBits(uint64_t maxKey) {        // bits that hold every key in [0, maxKey]
-    unsigned bits = 1;
-    while (bits < 32 && (1ull << bits) <= maxKey) ++bits;
-    return bits;
-}
-
 }  // namespace
 
 int triAnalyse(DevMat* d, int uplo, uint32_t T, hipStream_t st) {
@@ -305,11 +286,9 @@ int triAnalyse(DevMat* d, int uplo, uint32_t T, hipStream_t st) {
     TriSchedule* s = new TriSchedule;
     TempBuf cnt, key, rowOf, keysOut, depRow, depPtr, lvl, order, tab, state, sortTmp, split, bad;
     auto fail = [&](const char* what) {
-        (void)hipGetLastError();
-        fprintf(stderr, "libspmvhip: triangular analysis: %s failed\n", what);
-        (void)hipStreamSynchronize(st);                   // nothing may still use the temporaries when they go
-        freeTri(s);
-        return EXIT_FAILURE;
+        const int rc = buildFail(st, "triangular analysis", what);
+        freeTri(s);                                       // (after the synchronisation)
+        return rc;
     };
     const size_t m1 = std::max<uint64_t>(M, 1);
     if (hipMalloc(&s->perm, m1 * 4) || hipMalloc(&s->diagPos, m1 * 4) || cnt.alloc(m1 * 4) || lvl.alloc(m1 * 4) ||
@@ -327,18 +306,10 @@ int triAnalyse(DevMat* d, int uplo, uint32_t T, hipStream_t st) {
                            upper, cnt.as<uint32_t>(), key.as<uint32_t>(), lvl.as<uint32_t>(), s->diagPos, bad.as<uint32_t>());
     });
     // 2. dependents: rows of the strict triangle's entries, stably sorted by column
-    if (nnz) {
-        enqueueRowOf(M, d->IRP, d->irpBytes, rowOf.as<uint32_t>(), st);
-        size_t tmpBytes = 0;
-        const unsigned bits = keyBits(N);
-        if (rocprim::radix_sort_pairs(nullptr, tmpBytes, key.as<uint32_t>(), keysOut.as<uint32_t>(), rowOf.as<uint32_t>(),
-                                      depRow.as<uint32_t>(), (size_t)nnz, 0u, bits, st) != hipSuccess || sortTmp.alloc(tmpBytes))
-            return fail("sort workspace");
-        if (rocprim::radix_sort_pairs(sortTmp.p, tmpBytes, key.as<uint32_t>(), keysOut.as<uint32_t>(), rowOf.as<uint32_t>(),
-                                      depRow.as<uint32_t>(), (size_t)nnz, 0u, bits, st) != hipSuccess)
-            return fail("sort");
-    }
-    enqueueSortedBounds(nnz, N, keysOut.as<uint32_t>(), depPtr.as<uint32_t>(), st);
+    if (nnz) enqueueRowOf(M, d->IRP, d->irpBytes, rowOf.as<uint32_t>(), st);
+    if (enqueueSortedByColumn(nnz, N, bitsFor(N + 1) /* a key may be N */, key.as<uint32_t>(), rowOf.as<uint32_t>(), keysOut.as<uint32_t>(),
+                              depRow.as<uint32_t>(), depPtr.as<uint32_t>(), sortTmp, st) != hipSuccess)
+        return fail("sort");
     // 3. levels
     hipLaunchKernelGGL(tri_level0_kernel, rowsGrid, blk, 0, st, M, cnt.as<uint32_t>(), order.as<uint32_t>(), tab.as<uint2>());
     uint32_t hState[4] = {0, 0, 0, 0};
@@ -368,16 +339,11 @@ int triAnalyse(DevMat* d, int uplo, uint32_t T, hipStream_t st) {
     for (uint32_t l = 0; l <= L; ++l) s->levelPtr_h[l] = hTab[l].x;
     for (uint32_t l = 0; l < L; ++l) s->split_h[l] = hTab[l + 1].x;
     if (M) {
-        hipLaunchKernelGGL(tri_iota_kernel, rowsGrid, blk, 0, st, M, order.as<uint32_t>());
-        size_t tmpBytes = 0;
-        const unsigned bits = keyBits(2ull * L);
-        if (rocprim::radix_sort_pairs(nullptr, tmpBytes, lvl.as<uint32_t>(), cnt.as<uint32_t>(), order.as<uint32_t>(), s->perm,
-                                      (size_t)M, 0u, bits, st) != hipSuccess)
-            return fail("level sort workspace");
-        TempBuf sortTmp2;
-        if (sortTmp2.alloc(tmpBytes) || split.alloc(L * 4ull) ||
-            rocprim::radix_sort_pairs(sortTmp2.p, tmpBytes, lvl.as<uint32_t>(), cnt.as<uint32_t>(), order.as<uint32_t>(), s->perm,
-                                      (size_t)M, 0u, bits, st) != hipSuccess)
+        enqueueIota(M, order.as<uint32_t>(), st);
+        TempBuf sortTmp2;                                 // (not sortTmp: replacing a held workspace waits for the stream)
+        if (split.alloc(L * 4ull) ||
+            sortPairs(sortTmp2, lvl.as<uint32_t>(), cnt.as<uint32_t>(), order.as<uint32_t>(), s->perm, (size_t)M, 0u, bitsFor(2ull * L + 1), st) !=
+                hipSuccess)
             return fail("level sort");
         if (hipMemcpyAsync(split.p, s->split_h.data(), L * 4ull, hipMemcpyHostToDevice, st)) return fail("split upload");
         hipLaunchKernelGGL(tri_split_kernel, rowsGrid, blk, 0, st, M, cnt.as<uint32_t>(), split.as<uint32_t>());
