@@ -244,7 +244,9 @@ int spmvHipIlu0Info(spmat* dA, spmvIluInfo* info);
  * hipSpCGCSR (A symmetric positive definite) and hipSpBiCGStabCSR (A square, right-preconditioned) solve A x = b on the
  * device.  dX holds x0 on entry and x on return; dM NULL means no preconditioner, otherwise M^-1 v is
  * hipSpTRSVCSR(dM, UPPER, STORED, hipSpTRSVCSR(dM, LOWER, UNIT, v)) -- the ILU(0) pair of hipSpILU0CSR; dM == dA is
- * allowed.  x, info.status, info.iterations, info.rr and history are the bits of these loops, in IEEE double with no FMA:
+ * allowed.  A dM made by spmvHipAmgSetup(dA) (hipSpGMRESCSR too) makes M^-1 v = V(0, v), the cycle of spmvHipAmgApply: its
+ * kernels stop with the loop as the triangular solves do, its SpMVs run regardless, info.launches counts them all; a
+ * hierarchy of another source is refused.  x, info.status, info.iterations, info.rr and history are the bits of these loops, in IEEE double with no FMA:
  * dot() is spmvHipDot, A v is serial-order SpMV (sgemvSerial's bits, spmvHipEnqueueAutoRows: its first call for a handle
  * chooses the kernel), every a + s*v is two roundings in the order written, tol2 = tol*tol is computed on the host.
  *     q = A x; r = b - q; rr = dot(r,r); bb = dot(b,b); thresh = tol2 * bb; hist[0] = rr
@@ -505,6 +507,116 @@ typedef struct {
 } spmvSpgemmInfo;
 int spmvHipSpGEMM(spmat* dA, spmat* dB, const spmvSpgemmOpts* opts, spmat* dC, spmvSpgemmInfo* info);
 int spmvHipSpGEMMRefresh(spmat* dC, spmat* dA, spmat* dB, spmvSpgemmInfo* info);
+/* ------------------------------------------------------------- aggregation multigrid preconditioner */
+/* Plain (unsmoothed) aggregation AMG built from the pieces above: an aggregation of the pattern, the Galerkin products by
+ * spmvHipCsrTranspose / spmvHipSpGEMM, a damped-Jacobi V-cycle on serial-order SpMVs.  DESIGN.md section 24.  As everywhere
+ * in this header the result is a function of the handle's arrays and the options alone, and every number is the bits of a
+ * loop written here.
+ *
+ * spmvHipAggregateCSR: dAgg[i] (M words) = the aggregate of vertex i of a square CSR handle.  A function of the PATTERN and
+ *   the seed alone.  adj(i) is the one of spmvHipColourCSR (the pattern of A + A^T, the diagonal ignored, repeats counted
+ *   once, unsorted rows allowed, column ids >= M skipped); key(i) = fmix32(i ^ seed); j beats i iff (key(j), j) > (key(i), i)
+ *   (the HASH order of spmvHipColourCSR).  dist(i, j) is the path length in adj.
+ *       roots:     for i in descending (key, id):  i is a root iff no root chosen so far has dist(i, root) <= 2
+ *                  (the lexicographically first distance-2 maximal independent set; a vertex with empty adj is a root)
+ *       numbering: id(root r) = the number of roots with a smaller row id
+ *       ring 1:    a non-root i with a root r in adj(i):  agg[i] = id(r)            (there is at most one such root)
+ *       ring 2:    every other i:  agg[i] = agg[k], k the ring-1 vertex of adj(i) that beats all other ring-1 vertices of
+ *                  adj(i)                                                            (one exists: the set is maximal)
+ *   The device runs rounds: every undecided vertex that beats all undecided vertices within distance 2 becomes a root, then
+ *   everything within distance 2 of a new root retires; a distance-2 path counts whatever its middle vertex is (undecided,
+ *   retired).  Only info.rounds may differ between runs.  Rows with more than 64 adjacency entries take a wavefront each,
+ *   the others a lane.  info: aggregates, rounds, hostChecks (one read-back per K rounds, K = 16 unless
+ *   spmvHipSetVariant("spmvHipAggregateCSR", K), 1 <= K <= 4096), longRows, symmetric (as spmvColourInfo), maxAggRows /
+ *   minAggRows (the largest and smallest aggregate; 0 when M = 0), ms.  opts == NULL: seed 0.  Synchronous on the library
+ *   stream; allocates, so not capturable; temporaries freed before it returns.  M = 0 succeeds, nothing written.
+ *   Refusals: those of spmvHipColourCSR (a handle that is not live, ELL, M != N, M >= 2^31 or NZ >= IRP32_LIMIT), and a NULL
+ *   dAgg when M > 0.
+ *
+ * spmvHipAmgSetup writes into dM a handle of its own kind: a hierarchy.  It is no matrix -- every SpMV, format, build and
+ *   solve entry point refuses it with a message -- and is freed by hipFreeSpmat.  It records dA's id and keeps no pointer to
+ *   it.  With A_0 = A, for l = 0, 1, ...:
+ *       dinv_l[i] = 1.0 / (the one stored entry (i, i) of A_l)       (a row without exactly one: refused, the STORED rule)
+ *       stop (l is the last level) when M_l <= coarseRows, or l + 1 == maxLevels
+ *       agg_l = spmvHipAggregateCSR(A_l, seed);  stop when nAgg_l == M_l
+ *       P_l = the M_l x nAgg_l CSR handle with the one entry (i, agg_l[i]) = 1.0 per row        (a unit-value handle)
+ *       R_l = spmvHipCsrTranspose(P_l);  A_{l+1} = spmvHipSpGEMM(R_l, spmvHipSpGEMM(A_l, P_l))
+ *   so A_{l+1}'s arrays are what those calls give (rows ascend strictly).  A_l P_l is kept: the refresh of A_{l+1} reads it.
+ *   P_l and R_l keep their value arrays of 1.0 (8 B per row of A_l each, counted in info.bytes): their SpMVs stream no
+ *   values, but the products and their refreshes read the value arrays of their operands.
+ *   opts (NULL, or a field 0: the built-in default): seed; coarseRows 512; maxLevels 16 (at most SPMV_AMG_MAX_LEVELS);
+ *   omega 2/3; nu1 1, nu2 1, nuCoarse 8 sweeps -- SPMV_AMG_NO_SWEEPS asks for none, 0 being the default.  The defaults are
+ *   conventions.  The workspace of the cycle (t, d per level, r, z below level 0) is allocated here, and every level's
+ *   serial-order SpMV selection is made here, dA's included.  info (also spmvHipAmgInfo): levels, rows / nnz / aggregates per
+ *   level (aggregates 0 on the last), opComplexity = sum nnz_l / nnz_0, bytes kept, tempBytes (the largest of the products'
+ *   temporaries), ms.  Synchronous; allocates.
+ * spmvHipAmgLevel: a view of level l for inspection: *dAl = a copy of A_l's spmat with dev = NULL (its arrays stay dM's;
+ *   level 0: only M, N, NZ are set), *dAgg = agg_l (NULL on the last level), *dDinv = dinv_l.  Any of the three may be NULL.
+ * spmvHipAmgRefresh: dA has new values on the same pattern: spmvHipSpGEMMRefresh down the chain and every dinv again;
+ *   aggregates, P and R stay.  Bit-identical to a fresh setup.
+ * spmvHipAmgApply: dZ = V(0, dR), in IEEE double, no FMA, every operation rounded in the order written; A v is level l's
+ *   serial-order SpMV (spmvHipEnqueueAutoRows), L the number of levels:
+ *       V(l, r) -> z:
+ *         sweeps = (l == L-1) ? nuCoarse : nu1
+ *         if sweeps == 0: z_i = +0.0
+ *         else first sweep (no SpMV):  z_i = omega * (dinv_i * r_i)
+ *              each further sweep:     t = A_l z;  z_i = z_i + omega * (dinv_i * (r_i - t_i))        (Jacobi: t from the old z)
+ *         if l == L-1: return z
+ *         t = A_l z;  d_i = r_i - t_i;  rc = R_l d (serial-order SpMV on the transpose handle);  e = V(l+1, rc)
+ *         z_i = z_i + e[agg_l[i]]                              (a gather, NOT an SpMV with P_l: the two differ at -0.0)
+ *         nu2 times:  t = A_l z;  z_i = z_i + omega * (dinv_i * (r_i - t_i))
+ *   Kernels only, on the library stream, no allocation: capturable; honours spmvHipSetSync.  dR and dZ need 8-byte
+ *   alignment only.  dA must be the handle of the setup, with the values of the setup or of the last refresh.
+ *   One cycle enqueues, with s(n) = 1 + 2 * (max(n, 1) - 1) kernels for n sweeps from nothing (an SpMV counted as one),
+ *       (L - 1) * (s(nu1) + 3 + 1 + 2 * nu2) + s(nuCoarse)
+ *   kernels: the residual's SpMV and pass and the restriction, the gather, two per further sweep.
+ *   A hierarchy has ONE workspace: every Apply and every solve with it as dM uses the same vectors.  Two of them running at
+ *   once -- on two streams, or a replayed capture beside a call -- race; keep them in stream order or synchronised.
+ * As dM of hipSpCGCSR / hipSpBiCGStabCSR / hipSpGMRESCSR: see there.
+ * Refused with a message and EXIT_FAILURE, outputs untouched: NULL dA, dM, dR or dZ; handles that are not live; for the
+ *   setup the refusals of spmvHipAggregateCSR, dM == dA, a source without column or value array, a row without exactly one
+ *   stored diagonal entry, omega negative or not finite, maxLevels > SPMV_AMG_MAX_LEVELS; a dM that is not a hierarchy; a
+ *   dA that is not the source; dR and dZ overlapping; a level beyond the last. */
+#define SPMV_AMG_MAX_LEVELS 16
+#define SPMV_AMG_NO_SWEEPS  0xFFFFFFFFu
+typedef struct {
+    uint32_t seed;          /* of the keys                                                   */
+} spmvAggOpts;
+typedef struct {
+    ulong  aggregates;
+    ulong  rounds;          /* rounds until every vertex was a root or retired               */
+    ulong  hostChecks;      /* read-backs of the device state                                */
+    ulong  longRows;        /* rows handled by a wavefront each                              */
+    int    symmetric;       /* 1: stored pattern symmetric, transposed pattern not built     */
+    ulong  maxAggRows;
+    ulong  minAggRows;
+    double ms;
+} spmvAggInfo;
+typedef struct {            /* 0 = the built-in default */
+    uint32_t seed;
+    ulong    coarseRows;    /* a level with at most this many rows is the last (512)         */
+    unsigned maxLevels;     /* levels at most (16)                                           */
+    double   omega;         /* Jacobi damping (2/3)                                          */
+    unsigned nu1;           /* sweeps before the coarse correction (1)                       */
+    unsigned nu2;           /* ... after it (1)                                              */
+    unsigned nuCoarse;      /* sweeps on the last level (8); SPMV_AMG_NO_SWEEPS: none        */
+} spmvAmgOpts;
+typedef struct {
+    unsigned levels;
+    ulong  rows[SPMV_AMG_MAX_LEVELS];
+    ulong  nnz[SPMV_AMG_MAX_LEVELS];
+    ulong  aggregates[SPMV_AMG_MAX_LEVELS];
+    double opComplexity;    /* sum of nnz over the levels / nnz of level 0                   */
+    ulong  bytes;           /* device memory the hierarchy keeps                             */
+    ulong  tempBytes;       /* the largest temporaries of one product of the build           */
+    double ms;
+} spmvAmgInfo;
+int spmvHipAggregateCSR(spmat* dA, const spmvAggOpts* opts, uint32_t* dAgg, spmvAggInfo* info);
+int spmvHipAmgSetup(spmat* dA, const spmvAmgOpts* opts, spmat* dM, spmvAmgInfo* info);
+int spmvHipAmgRefresh(spmat* dM, spmat* dA);
+int spmvHipAmgApply(spmat* dM, spmat* dA, const double* dR, double* dZ);
+int spmvHipAmgInfo(spmat* dM, spmvAmgInfo* info);
+int spmvHipAmgLevel(spmat* dM, unsigned level, spmat* dAl, const uint32_t** dAgg, const double** dDinv);
 /* Release the device arrays behind a handle (cudaUtils.h:70-78). */
 int hipFreeSpmat(spmat* dMat);
 

@@ -116,6 +116,12 @@ _sigs = {
     "spmvHipVecPermute": ([_sz, _vp, _vp, _vp, _i], _i),
     "spmvHipSpGEMM": ([C.POINTER(spmat), C.POINTER(spmat), _vp, C.POINTER(spmat), _vp], _i),
     "spmvHipSpGEMMRefresh": ([C.POINTER(spmat), C.POINTER(spmat), C.POINTER(spmat), _vp], _i),
+    "spmvHipAggregateCSR": ([C.POINTER(spmat), _vp, _vp, _vp], _i),
+    "spmvHipAmgSetup": ([C.POINTER(spmat), _vp, C.POINTER(spmat), _vp], _i),
+    "spmvHipAmgRefresh": ([C.POINTER(spmat), C.POINTER(spmat)], _i),
+    "spmvHipAmgApply": ([C.POINTER(spmat), C.POINTER(spmat), _vp, _vp], _i),
+    "spmvHipAmgInfo": ([C.POINTER(spmat), _vp], _i),
+    "spmvHipAmgLevel": ([C.POINTER(spmat), C.c_uint, C.POINTER(spmat), C.POINTER(_vp), C.POINTER(_vp)], _i),
 }
 SPMV_DENSE_ROW_MAJOR, SPMV_DENSE_COL_MAJOR = 0, 1          # include/spmvHip.h: layouts of hipSpMMRowsCSR's X and Y
 SPMV_TRI_LOWER, SPMV_TRI_UPPER = 0, 1                      # include/spmvHip.h: hipSpTRSVCSR's uplo ...
@@ -206,6 +212,33 @@ class spmvSpgemmInfo(C.Structure):
     _fields_ = [("products", C.c_ulong), ("nnzC", C.c_ulong), ("maxRowProducts", C.c_ulong), ("maxRowNnz", C.c_ulong),
                 ("rowsWave", C.c_ulong), ("rowsGroup", C.c_ulong), ("rowsSorted", C.c_ulong), ("sortBatches", C.c_ulong),
                 ("tempBytes", C.c_ulong), ("symbolicMs", C.c_double), ("numericMs", C.c_double), ("ms", C.c_double)]
+
+
+SPMV_AMG_MAX_LEVELS, SPMV_AMG_NO_SWEEPS = 16, 0xFFFFFFFF
+
+
+class spmvAggOpts(C.Structure):
+    """include/spmvHip.h `spmvAggOpts`: the seed of the keys."""
+    _fields_ = [("seed", C.c_uint32)]
+
+
+class spmvAggInfo(C.Structure):
+    """include/spmvHip.h `spmvAggInfo`: what a spmvHipAggregateCSR call did."""
+    _fields_ = [("aggregates", C.c_ulong), ("rounds", C.c_ulong), ("hostChecks", C.c_ulong), ("longRows", C.c_ulong),
+                ("symmetric", _i), ("maxAggRows", C.c_ulong), ("minAggRows", C.c_ulong), ("ms", C.c_double)]
+
+
+class spmvAmgOpts(C.Structure):
+    """include/spmvHip.h `spmvAmgOpts` (a field 0: the built-in default; SPMV_AMG_NO_SWEEPS: no sweeps)."""
+    _fields_ = [("seed", C.c_uint32), ("coarseRows", C.c_ulong), ("maxLevels", C.c_uint), ("omega", C.c_double),
+                ("nu1", C.c_uint), ("nu2", C.c_uint), ("nuCoarse", C.c_uint)]
+
+
+class spmvAmgInfo(C.Structure):
+    """include/spmvHip.h `spmvAmgInfo`: the levels of a hierarchy."""
+    _fields_ = [("levels", C.c_uint), ("rows", C.c_ulong * SPMV_AMG_MAX_LEVELS), ("nnz", C.c_ulong * SPMV_AMG_MAX_LEVELS),
+                ("aggregates", C.c_ulong * SPMV_AMG_MAX_LEVELS), ("opComplexity", C.c_double), ("bytes", C.c_ulong),
+                ("tempBytes", C.c_ulong), ("ms", C.c_double)]
 
 
 SPMV_COLOUR_NATURAL, SPMV_COLOUR_HASH = 0, 1
@@ -554,6 +587,32 @@ class DeviceMatrix:
             raise SpmvHipError("spgemm_info: this matrix was not made by multiply()")
         return info
 
+    def aggregate(self, seed=0):
+        """spmvHipAggregateCSR: the aggregate id of every vertex of this square matrix, a function of its pattern and the
+        seed alone (include/spmvHip.h states the loop).  Returns (ids, info): a numpy uint32 array and a spmvAggInfo."""
+        M = int(self.handle.M)
+        opts, info = spmvAggOpts(int(seed) & 0xFFFFFFFF), spmvAggInfo()
+        buf = DeviceBuffer(4 * M)
+        try:
+            _check(lib.spmvHipAggregateCSR(C.byref(self.handle), C.byref(opts), buf.ptr, C.byref(info)), "spmvHipAggregateCSR")
+            ids = buf.down(np.uint32) if M else np.zeros(0, np.uint32)
+        finally:
+            buf.free()
+        return ids, info
+
+    def amg(self, seed=0, coarseRows=None, maxLevels=None, omega=None, nu1=None, nu2=None, nuCoarse=None) -> "AmgHierarchy":
+        """spmvHipAmgSetup: an aggregation multigrid hierarchy of this square matrix (include/spmvHip.h states the loops).
+        None: the built-in default (512, 16, 2/3, 1, 1, 8); nu1 / nu2 / nuCoarse = 0 asks for no sweeps.  The result is
+        accepted as `precond=` by cg / bicgstab / gmres of this matrix."""
+        def sweeps(v):
+            return 0 if v is None else SPMV_AMG_NO_SWEEPS if int(v) == 0 else int(v)
+        opts = spmvAmgOpts(int(seed) & 0xFFFFFFFF, int(coarseRows or 0), int(maxLevels or 0), float(omega or 0.0), sweeps(nu1),
+                           sweeps(nu2), sweeps(nuCoarse))
+        h = AmgHierarchy(self)
+        _check(lib.spmvHipAmgSetup(C.byref(self.handle), C.byref(opts), C.byref(h.handle), C.byref(h.info)), "spmvHipAmgSetup")
+        h.rows = int(h.handle.M)
+        return h
+
     def matmul(self, X, out=None):
         """hipSpMMRowsCSR: Y = A X, column c of Y bit-identical to sgemvSerial on column c of X.  X is (N, k) float64:
         a device torch tensor with unit stride in one dimension (a contiguous tensor is row-major, a `.t()` view of a
@@ -650,7 +709,8 @@ class DeviceMatrix:
 
     def cg(self, b, x0=None, precond=None, tol=1e-8, maxiter=1000, history=False):
         """hipSpCGCSR: solve A x = b (A symmetric positive definite) on the device with the bits of the loop in
-        include/spmvHip.h; precond: None or a DeviceMatrix holding ILU(0) factors (`ilu0()`).  b (and x0): numpy arrays ->
+        include/spmvHip.h; precond: None, a DeviceMatrix holding ILU(0) factors (`ilu0()`) or this
+        matrix's multigrid hierarchy (`amg()`).  b (and x0): numpy arrays ->
         x as numpy; or contiguous float64 device torch tensors -> x as a new torch tensor.  Returns (x, info) with
         info.history a numpy array of the squared residuals hist[0 .. iterations] when history=True."""
         return self._krylov(lib.hipSpCGCSR, "hipSpCGCSR", b, x0, precond, tol, maxiter, history)
@@ -716,6 +776,60 @@ class DeviceMatrix:
             self.free()
         except Exception:
             pass
+
+
+class AmgHierarchy(DeviceMatrix):
+    """What DeviceMatrix.amg() returns: a hierarchy handle (no matrix: SpMV, formats and solves refuse it) with `info`
+    (spmvAmgInfo), apply(), refresh_from(), level() and free().  It keeps a reference to its source matrix."""
+
+    def __init__(self, source):
+        super().__init__()
+        self.source = source
+        self.info = spmvAmgInfo()
+
+    def apply(self, r, out=None):
+        """spmvHipAmgApply: z = V(0, r), one cycle.  r: a numpy array -> z as numpy; or a float64 device torch tensor
+        (any 8-byte alignment) -> z as a torch tensor (`out` when given)."""
+        N = int(self.handle.M)
+        if isinstance(r, np.ndarray):
+            if out is not None:
+                raise SpmvHipError("spmvHipAmgApply: `out` is for torch tensors")
+            if r.shape != (N,):
+                raise SpmvHipError(f"spmvHipAmgApply: r must have shape ({N},), not {r.shape}")
+            hr = np.ascontiguousarray(r, dtype=np.float64)
+            dr, dz = DeviceBuffer(hr.nbytes).up(hr), DeviceBuffer(hr.nbytes)
+            try:
+                _check(lib.spmvHipAmgApply(C.byref(self.handle), C.byref(self.source.handle), dr.ptr, dz.ptr), "spmvHipAmgApply")
+                return dz.down(np.float64) if N else np.zeros(0)
+            finally:
+                dr.free()
+                dz.free()
+        import torch
+        for t, what in ((r, "r"), (out, "out")):
+            if t is None and what == "out":
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous() or t.shape != (N,):
+                raise SpmvHipError(f"spmvHipAmgApply: {what} must be a contiguous float64 device tensor of shape ({N},)")
+        if out is None:
+            out = torch.empty(N, dtype=torch.float64, device=r.device)
+        _check(lib.spmvHipAmgApply(C.byref(self.handle), C.byref(self.source.handle), r.data_ptr(), out.data_ptr()), "spmvHipAmgApply")
+        return out
+
+    def refresh_from(self, source: "DeviceMatrix"):
+        """spmvHipAmgRefresh: `source` (the matrix of the setup) has new values on the same pattern."""
+        _check(lib.spmvHipAmgRefresh(C.byref(self.handle), C.byref(source.handle)), "spmvHipAmgRefresh")
+        _check(lib.spmvHipAmgInfo(C.byref(self.handle), C.byref(self.info)), "spmvHipAmgInfo")
+
+    def level(self, l):
+        """spmvHipAmgLevel: (view, agg, dinv) of level l: an spmat copy whose arrays stay the hierarchy's (dev = NULL), and
+        the device addresses of agg_l (None on the last level) and dinv_l"""
+        view, agg, dinv = spmat(), C.c_void_p(), C.c_void_p()
+        _check(lib.spmvHipAmgLevel(C.byref(self.handle), int(l), C.byref(view), C.byref(agg), C.byref(dinv)), "spmvHipAmgLevel")
+        return view, agg.value, dinv.value
+
+    def free(self):
+        super().free()
+        self.source = None
 
 
 class Colouring:

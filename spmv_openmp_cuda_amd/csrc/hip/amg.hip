@@ -1,0 +1,666 @@
+// amg.hip -- aggregation multigrid on the device: the aggregation of a square CSR handle (spmvHipAggregateCSR), the
+// hierarchy of Galerkin products (spmvHipAmgSetup, spmvHipAmgRefresh) and its damped-Jacobi V-cycle (spmvHipAmgApply, and
+// the dM of the Krylov solvers).  DESIGN.md section 24; the contracts -- the bits of the loops -- are in spmvHip.h.
+//
+// Aggregation.  The roots are the lexicographically first distance-2 maximal independent set under the HASH order of the
+// colouring.  Rounds of two launches over the rows still undecided:
+//   select   an undecided row that no vertex within distance 2, retired ones excepted, beats becomes a ROOT.  A state word
+//            read inside the launch is UNDECIDED or, for a row that became a root in this very launch, ROOT: both count,
+//            and a root of this round within distance 2 beats the row anyway, so the race changes nothing.
+//   retire   an undecided row with a ROOT within distance 2 retires; the others are counted into the round's word.  Roots
+//            do not change in this launch, and a row writes its own word only.
+// The middle vertex of a distance-2 path is never looked at: undecided or retired, the path counts.  No row list is
+// compacted between rounds (a decided row returns at its first load); K rounds are enqueued, then their K counts are read.
+// Then the roots are numbered by a scan, ring 1 takes its root's id, ring 2 the id of its best ring-1 neighbour.
+// Rows with more than 64 adjacency entries take a wavefront each (the lanes share the first hop), the others a lane.
+//
+// Hierarchy.  Every level's matrix, prolongator, restriction and A P are handles made by the library's own entry points
+// (spmvHipCsrTranspose, spmvHipSpGEMM), so their bits are pinned there.  The cycle's vector kernels are ops of the Krylov
+// files' fused-pass kernel (krylov.hpp: 16-byte accesses when every pointer allows, the same bits otherwise), each with the
+// stop pointer of a Krylov loop.
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "lib.hpp"
+#include "device_prims.hpp"
+#include "krylov.hpp"
+
+namespace spmvhip {
+
+struct AmgLevel {
+    spmat A{}, P{}, R{}, AP{};          // A: levels below 0 only (level 0 is the caller's); P, R, AP: all but the last level
+    uint64_t M = 0, nnz = 0, nAgg = 0;
+    const uint32_t* agg = nullptr;      // P's column array
+    double* dinv = nullptr;
+    double *r = nullptr, *z = nullptr;  // below level 0: the restricted residual and the correction
+    double *t = nullptr, *d = nullptr;
+};
+
+struct AmgHierarchy {
+    uint64_t srcId = 0;
+    uint32_t seed = 0, nu1 = 1, nu2 = 1, nuCoarse = 8;
+    double omega = 2.0 / 3.0;
+    std::vector<AmgLevel> lv;
+    spmvAmgInfo info{};
+};
+
+namespace {
+
+constexpr uint32_t AG_THREADS = WG_THREADS;
+constexpr uint32_t AG_WAVES = AG_THREADS / 64;
+constexpr uint32_t AG_LONG = 64;                               // adjacency entries above which a row takes a wavefront
+constexpr uint32_t UNDECIDED = 0xFFFFFFFFu, RETIRED = 0, ROOT = 1, RING1 = 2;
+
+__device__ __forceinline__ uint32_t fmix32(uint32_t h) {      // the murmur3 32-bit finaliser
+    h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
+    return h;
+}
+// (key, id) as one word: j beats i iff pri(j) > pri(i)
+__device__ __forceinline__ uint64_t pri(uint32_t i, uint32_t seed) { return (uint64_t)fmix32(i ^ seed) << 32 | i; }
+__device__ __forceinline__ uint32_t stateOf(const uint32_t* state, uint32_t i) { return __atomic_load_n(state + i, __ATOMIC_RELAXED); }
+
+// the pattern of A + A^T as two CSR sides: the stored rows and the incoming ones (null when the pattern is symmetric)
+template <typename I> struct Adj {
+    uint64_t M;
+    const I* IRP; const uint32_t* JA;
+    const uint32_t* tptr; const uint32_t* tcol;
+    // f(j) for every adjacency entry j != i, j < M of row i (repeats included) taken `width` apart from `lane`, until f
+    // returns true; returns whether it did
+    template <typename F> __device__ __forceinline__ bool any(uint32_t i, uint32_t lane, uint32_t width, F&& f) const {
+        for (int side = 0; side < 2; ++side) {
+            if (side && !tptr) break;
+            const uint32_t* col = side ? tcol : JA;
+            const uint64_t b = side ? tptr[i] : (uint64_t)IRP[i], e = side ? tptr[i + 1] : (uint64_t)IRP[i + 1];
+            for (uint64_t p = b + lane; p < e; p += width) {
+                const uint32_t j = col[p];
+                if (j != i && j < M && f(j)) return true;
+            }
+        }
+        return false;
+    }
+};
+
+// every row gets UNDECIDED and joins the short or the long list (one atomic per wavefront and list: the ORDER of a list
+// depends on the run, no output does)
+template <typename I>
+__global__ __launch_bounds__(AG_THREADS) void ag_classify_kernel(Adj<I> g, uint32_t* __restrict__ state, uint32_t* __restrict__ shortList,
+                                                                 uint32_t* __restrict__ longList, uint32_t* __restrict__ cnt) {
+    const uint64_t r = linear_block() * AG_THREADS + threadIdx.x;
+    const bool live = r < g.M;
+    uint64_t deg = 0;
+    if (live) {
+        state[r] = UNDECIDED;
+        deg = (uint64_t)g.IRP[r + 1] - (uint64_t)g.IRP[r] + (g.tptr ? g.tptr[r + 1] - g.tptr[r] : 0u);
+    }
+    const bool isLong = live && deg > AG_LONG, isShort = live && !isLong;
+    const uint32_t lane = threadIdx.x % 64;
+    const uint64_t below = (1ull << lane) - 1;
+    const uint64_t bs = __ballot(isShort), bl = __ballot(isLong);
+    uint32_t baseS = 0, baseL = 0;
+    if (lane == 0) {
+        if (bs) baseS = atomicAdd(&cnt[0], (uint32_t)__popcll(bs));
+        if (bl) baseL = atomicAdd(&cnt[1], (uint32_t)__popcll(bl));
+    }
+    baseS = __shfl(baseS, 0);
+    baseL = __shfl(baseL, 0);
+    if (isShort) shortList[baseS + __popcll(bs & below)] = (uint32_t)r;
+    if (isLong) longList[baseL + __popcll(bl & below)] = (uint32_t)r;
+}
+
+// the row of list place k for this lane: a lane per row, or a wavefront per row (uniform in the wavefront)
+template <bool WAVE_ROW>
+__device__ __forceinline__ bool ag_row(uint32_t n, const uint32_t* __restrict__ list, uint32_t& i, uint32_t& lane) {
+    const uint64_t k = WAVE_ROW ? linear_block() * AG_WAVES + threadIdx.x / 64 : linear_block() * AG_THREADS + threadIdx.x;
+    lane = WAVE_ROW ? threadIdx.x % 64 : 0;
+    if (k >= n) return false;
+    i = list[k];
+    return true;
+}
+
+template <typename I, bool WAVE_ROW>
+__global__ __launch_bounds__(AG_THREADS) void ag_select_kernel(Adj<I> g, uint32_t seed, uint32_t n, const uint32_t* __restrict__ list,
+                                                               uint32_t* state) {
+    uint32_t i = 0, lane = 0;
+    const bool live = ag_row<WAVE_ROW>(n, list, i, lane) && stateOf(state, i) == UNDECIDED;
+    bool blocked = false;
+    if (live) {
+        const uint64_t pi = pri(i, seed);
+        auto beats = [&](uint32_t j) { return j != i && stateOf(state, j) != RETIRED && pri(j, seed) > pi; };
+        blocked = g.any(i, lane, WAVE_ROW ? 64 : 1, [&](uint32_t k) { return beats(k) || g.any(k, 0, 1, beats); });
+    }
+    if (WAVE_ROW) blocked = __ballot(blocked) != 0;
+    if (live && !blocked && lane == 0) __atomic_store_n(state + i, ROOT, __ATOMIC_RELAXED);
+}
+
+template <typename I, bool WAVE_ROW>
+__global__ __launch_bounds__(AG_THREADS) void ag_retire_kernel(Adj<I> g, uint32_t n, const uint32_t* __restrict__ list, uint32_t* state,
+                                                               uint32_t* __restrict__ left) {
+    uint32_t i = 0, lane = 0;
+    const bool live = ag_row<WAVE_ROW>(n, list, i, lane) && stateOf(state, i) == UNDECIDED;
+    bool near = false;
+    if (live) {
+        auto isRoot = [&](uint32_t j) { return stateOf(state, j) == ROOT; };
+        near = g.any(i, lane, WAVE_ROW ? 64 : 1, [&](uint32_t k) { return isRoot(k) || g.any(k, 0, 1, isRoot); });
+    }
+    if (WAVE_ROW) near = __ballot(near) != 0;
+    if (live && near && lane == 0) __atomic_store_n(state + i, RETIRED, __ATOMIC_RELAXED);
+    const uint64_t waits = __ballot(live && !near && lane == 0);
+    if (waits && threadIdx.x % 64 == 0) atomicAdd(left, (uint32_t)__popcll(waits));
+}
+
+__global__ __launch_bounds__(AG_THREADS) void ag_flag_kernel(uint64_t M, const uint32_t* __restrict__ state, uint32_t* __restrict__ flag) {
+    const uint64_t r = linear_block() * AG_THREADS + threadIdx.x;
+    if (r <= M) flag[r] = r < M && state[r] == ROOT;
+}
+
+// roots take their number, ring 1 the number of its root (and the state RING1: a row writes its own word only, and only
+// ROOT is looked for)
+template <typename I, bool WAVE_ROW>
+__global__ __launch_bounds__(AG_THREADS) void ag_ring1_kernel(Adj<I> g, uint32_t n, const uint32_t* __restrict__ list, uint32_t* state,
+                                                              const uint32_t* __restrict__ number, uint32_t* __restrict__ agg) {
+    uint32_t i = 0, lane = 0;
+    if (!ag_row<WAVE_ROW>(n, list, i, lane)) return;
+    if (stateOf(state, i) == ROOT) { if (lane == 0) agg[i] = number[i]; return; }
+    uint32_t root = UNDECIDED;
+    g.any(i, lane, WAVE_ROW ? 64 : 1, [&](uint32_t k) { if (stateOf(state, k) == ROOT) root = k; return root != UNDECIDED; });
+    if (WAVE_ROW)
+        for (int off = 32; off; off >>= 1) root = min(root, (uint32_t)__shfl_xor(root, off));   // (one root at most: min picks it)
+    if (root == UNDECIDED || lane) return;
+    agg[i] = number[root];
+    __atomic_store_n(state + i, RING1, __ATOMIC_RELAXED);
+}
+
+template <typename I, bool WAVE_ROW>
+__global__ __launch_bounds__(AG_THREADS) void ag_ring2_kernel(Adj<I> g, uint32_t seed, uint32_t n, const uint32_t* __restrict__ list,
+                                                              const uint32_t* __restrict__ state, uint32_t* agg) {
+    uint32_t i = 0, lane = 0;
+    if (!ag_row<WAVE_ROW>(n, list, i, lane) || state[i] != RETIRED) return;
+    uint64_t best = 0;
+    bool found = false;
+    g.any(i, lane, WAVE_ROW ? 64 : 1, [&](uint32_t k) {
+        if (state[k] == RING1) {
+            const uint64_t pk = pri(k, seed);
+            if (!found || pk > best) best = pk;
+            found = true;
+        }
+        return false;
+    });
+    if (WAVE_ROW)
+        for (int off = 32; off; off >>= 1) {
+            const uint64_t ob = __shfl_xor(best, off);
+            const bool of = __shfl_xor((int)found, off) != 0;
+            if (of && (!found || ob > best)) best = ob;
+            found = found || of;
+        }
+    if (found && lane == 0) agg[i] = __atomic_load_n(agg + (uint32_t)best, __ATOMIC_RELAXED);   // (a ring-1 word: final before this launch)
+}
+
+// (bad: an id that is no aggregate -- never, by maximality; it must not index the sizes)
+__global__ __launch_bounds__(AG_THREADS) void ag_hist_kernel(uint64_t M, uint32_t nAgg, const uint32_t* __restrict__ agg, uint32_t* __restrict__ size,
+                                                             uint32_t* __restrict__ bad) {
+    const uint64_t r = linear_block() * AG_THREADS + threadIdx.x;
+    if (r >= M) return;
+    const uint32_t a = agg[r];
+    if (a < nAgg) atomicAdd(size + a, 1u);
+    else atomicOr(bad, 1u);
+}
+__global__ __launch_bounds__(AG_THREADS) void ag_minmax_kernel(uint64_t n, const uint32_t* __restrict__ size, uint32_t* __restrict__ mm) {
+    const uint64_t r = linear_block() * AG_THREADS + threadIdx.x;
+    if (r < n) { atomicMin(mm, size[r]); atomicMax(mm + 1, size[r]); }
+}
+
+// P's row pointers and values; dinv from the one stored diagonal entry of every row (*bad = the first row without exactly one)
+__global__ __launch_bounds__(AG_THREADS) void amg_ones_kernel(uint64_t n, double* __restrict__ v) {
+    const uint64_t r = linear_block() * AG_THREADS + threadIdx.x;
+    if (r < n) v[r] = 1.0;
+}
+template <typename I>
+__global__ __launch_bounds__(AG_THREADS) void amg_dinv_kernel(uint64_t M, const I* __restrict__ IRP, const uint32_t* __restrict__ JA,
+                                                              const double* __restrict__ AS, double* __restrict__ dinv, uint32_t* __restrict__ bad) {
+    const uint64_t r = linear_block() * AG_THREADS + threadIdx.x;
+    if (r >= M) return;
+    uint32_t count = 0;
+    double dv = 0.0;
+    for (uint64_t p = IRP[r], e = IRP[r + 1]; p < e; ++p)
+        if (JA[p] == r) { ++count; dv = AS[p]; }
+    if (count != 1) { atomicMin(bad, (uint32_t)r); return; }
+    dinv[r] = 1.0 / dv;
+}
+
+// ------------------------------------------------------------------------------------------------ the cycle's passes
+struct StopMode {
+    const uint32_t* stop;
+    __device__ int mode(const KState*) const { return !(stop && *stop); }
+};
+struct AmgZeroOp : StopMode {                   // z = +0.0
+    static constexpr int NDOT = 0;
+    double* z;
+    struct R {};
+    template <bool VEC> __device__ void load(uint64_t, bool, R&) const {}
+    template <bool VEC> __device__ void step(uint64_t i, bool two, const R&, double&, double&) const { st2<VEC>(z, i, two, make_double2(0.0, 0.0)); }
+};
+struct AmgFirstOp : StopMode {                  // z = omega * (dinv * r)
+    static constexpr int NDOT = 0;
+    const double* r; const double* dinv; double* z; double omega;
+    struct R { double2 r, d; };
+    template <bool VEC> __device__ void load(uint64_t i, bool two, R& v) const { v.r = ld2<VEC>(r, i, two); v.d = ld2<VEC>(dinv, i, two); }
+    template <bool VEC> __device__ void step(uint64_t i, bool two, const R& v, double&, double&) const {
+        st2<VEC>(z, i, two, make_double2(omega * (v.d.x * v.r.x), omega * (v.d.y * v.r.y)));
+    }
+};
+struct AmgSweepOp : StopMode {                  // z = z + omega * (dinv * (r - t))
+    static constexpr int NDOT = 0;
+    const double* r; const double* t; const double* dinv; double* z; double omega;
+    struct R { double2 r, t, d, z; };
+    template <bool VEC> __device__ void load(uint64_t i, bool two, R& v) const {
+        v.r = ld2<VEC>(r, i, two); v.t = ld2<VEC>(t, i, two); v.d = ld2<VEC>(dinv, i, two); v.z = ld2<VEC>(z, i, two);
+    }
+    template <bool VEC> __device__ void step(uint64_t i, bool two, const R& v, double&, double&) const {
+        st2<VEC>(z, i, two, make_double2(v.z.x + omega * (v.d.x * (v.r.x - v.t.x)), v.z.y + omega * (v.d.y * (v.r.y - v.t.y))));
+    }
+};
+struct AmgResidOp : StopMode {                  // d = r - t
+    static constexpr int NDOT = 0;
+    const double* r; const double* t; double* d;
+    struct R { double2 r, t; };
+    template <bool VEC> __device__ void load(uint64_t i, bool two, R& v) const { v.r = ld2<VEC>(r, i, two); v.t = ld2<VEC>(t, i, two); }
+    template <bool VEC> __device__ void step(uint64_t i, bool two, const R& v, double&, double&) const {
+        st2<VEC>(d, i, two, make_double2(v.r.x - v.t.x, v.r.y - v.t.y));
+    }
+};
+struct AmgCorrectOp : StopMode {                // z = z + e[agg]
+    static constexpr int NDOT = 0;
+    const double* e; const uint32_t* agg; double* z;
+    struct R { double2 z, e; };
+    template <bool VEC> __device__ void load(uint64_t i, bool two, R& v) const {
+        v.z = ld2<VEC>(z, i, two);
+        uint2 a;
+        if (VEC && two) a = *reinterpret_cast<const uint2*>(agg + i);      // (i is even, agg a whole allocation: 8-byte aligned)
+        else a = make_uint2(agg[i], two ? agg[i + 1] : 0u);
+        v.e = make_double2(e[a.x], two ? e[a.y] : 0.0);
+    }
+    template <bool VEC> __device__ void step(uint64_t i, bool two, const R& v, double&, double&) const {
+        st2<VEC>(z, i, two, make_double2(v.z.x + v.e.x, v.z.y + v.e.y));
+    }
+};
+
+double msSince(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+DevMat* matOf(spmat* h) { return static_cast<DevMat*>(h->dev); }
+
+// dinv of one level; *badRow < 0 when every row has exactly one stored diagonal entry
+int levelDinv(const DevMat* a, double* dinv, long* badRow, hipStream_t st) {
+    uint32_t bad = UNDECIDED;
+    *badRow = -1;
+    if (!a->M) return EXIT_SUCCESS;
+    if (deviceFlag(0xFF, st, "amg_dinv_kernel", &bad, [&](uint32_t* dFlag) {
+            withIrp(a, [&](auto irp) {
+                hipLaunchKernelGGL((amg_dinv_kernel<IrpT<decltype(irp)>>), gridFor(a->M), dim3(AG_THREADS), 0, st, a->M, irp, a->JA, a->AS, dinv, dFlag);
+            });
+        }))
+        return EXIT_FAILURE;
+    if (bad != UNDECIDED) *badRow = (long)bad;
+    return EXIT_SUCCESS;
+}
+
+// the serial-order selection of a handle, made now on workspace vectors so that the cycle only enqueues
+int warmSpmv(spmat* h, double* x, double* y, hipStream_t st) {
+    const DevMat* d = matOf(h);
+    if (!d->M || !d->N) return EXIT_SUCCESS;
+    if (hipMemsetAsync(x, 0, d->N * sizeof(double), st) != hipSuccess) return EXIT_FAILURE;
+    if (spmvHipEnqueueAutoRows(h, x, y, st)) return EXIT_FAILURE;
+    return hipStreamSynchronize(st) == hipSuccess ? EXIT_SUCCESS : EXIT_FAILURE;
+}
+
+size_t handleBytes(const spmat* h) {
+    const DevMat* d = static_cast<const DevMat*>(h->dev);
+    return d ? (size_t)(d->NZ * 12 + (d->M + 1) * 4 + (d->tmap ? d->NZ * 4 : 0)) : 0;
+}
+
+}  // namespace
+
+void freeAmg(AmgHierarchy* h) {
+    if (!h) return;
+    for (AmgLevel& l : h->lv) {
+        for (spmat* m : {&l.A, &l.P, &l.R, &l.AP})
+            if (m->dev) (void)hipFreeSpmat(m);
+        for (double* p : {l.dinv, l.r, l.z, l.t, l.d}) (void)hipFree(p);
+    }
+    delete h;
+}
+
+int aggregateCsr(const DevMat* a, uint32_t seed, uint32_t K, uint32_t* dAgg, spmvAggInfo* info, hipStream_t st) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint64_t M = a->M;
+    spmvAggInfo out{};
+    out.symmetric = 1;
+    auto fail = [&](const char* what) { return buildFail(st, "aggregate", what); };
+    if (M == 0) { if (info) *info = out; return EXIT_SUCCESS; }
+    IncomingPattern in;
+    if (buildIncoming(a, in, st, "aggregate")) return EXIT_FAILURE;
+    out.symmetric = in.symmetric;
+    TempBuf state, lists, cnt, number, scanTmp, size;
+    if (state.alloc(M * 4) || lists.alloc(M * 8) || cnt.alloc((K + 2) * 4) || number.alloc((M + 1) * 8)) return fail("temporary allocation (20 B per row)");
+    uint32_t* const dState = state.as<uint32_t>();
+    uint32_t* const list[2] = {lists.as<uint32_t>(), lists.as<uint32_t>() + M};
+    uint32_t* const dCnt = cnt.as<uint32_t>();                 // [0], [1] the list lengths; [2 .. K + 1] undecided rows after a round
+    uint32_t* const dFlag = number.as<uint32_t>();             // root flags, M + 1 words, then their scan, M + 1 words
+    uint32_t* const dNumber = dFlag + M + 1;
+    std::vector<uint32_t> h(K + 2, 0);
+    if (hipMemsetAsync(dCnt, 0, (K + 2) * 4, st) != hipSuccess) return fail("state");
+    int rc = EXIT_SUCCESS;
+    withIrp(a, [&](auto irp) {
+        using I = IrpT<decltype(irp)>;
+        const Adj<I> g{M, irp, a->JA, in.ptr, in.col};
+        hipLaunchKernelGGL((ag_classify_kernel<I>), gridFor(M), dim3(AG_THREADS), 0, st, g, dState, list[0], list[1], dCnt);
+        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(h.data(), dCnt, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess) { rc = fail("classification"); return; }
+        const uint32_t nS = h[0], nL = h[1];
+        out.longRows = nL;
+        const dim3 gS = gridFor(nS), gL = gridFor(nL, AG_WAVES), blk(AG_THREADS);
+        // the rounds
+        for (bool done = false; !done;) {
+            if (hipMemsetAsync(dCnt + 2, 0, K * 4, st) != hipSuccess) { rc = fail("state"); return; }
+            for (uint32_t t = 0; t < K; ++t) {
+                if (nS) hipLaunchKernelGGL((ag_select_kernel<I, false>), gS, blk, 0, st, g, seed, nS, list[0], dState);
+                if (nL) hipLaunchKernelGGL((ag_select_kernel<I, true>), gL, blk, 0, st, g, seed, nL, list[1], dState);
+                if (nS) hipLaunchKernelGGL((ag_retire_kernel<I, false>), gS, blk, 0, st, g, nS, list[0], dState, dCnt + 2 + t);
+                if (nL) hipLaunchKernelGGL((ag_retire_kernel<I, true>), gL, blk, 0, st, g, nL, list[1], dState, dCnt + 2 + t);
+            }
+            if (hipGetLastError() != hipSuccess || hipMemcpyAsync(h.data() + 2, dCnt + 2, K * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                hipStreamSynchronize(st) != hipSuccess) { rc = fail("rounds"); return; }
+            ++out.hostChecks;
+            uint32_t used = K;
+            for (uint32_t t = 0; t < K; ++t)
+                if (h[2 + t] == 0) { used = t + 1; done = true; break; }
+            out.rounds += used;
+        }
+        // numbering and the rings
+        hipLaunchKernelGGL(ag_flag_kernel, gridFor(M + 1), blk, 0, st, M, dState, dFlag);
+        if (exclusiveScan(scanTmp, dFlag, dNumber, 0u, (size_t)M + 1, st) != hipSuccess) { rc = fail("scan"); return; }
+        if (nS) hipLaunchKernelGGL((ag_ring1_kernel<I, false>), gS, blk, 0, st, g, nS, list[0], dState, dNumber, dAgg);
+        if (nL) hipLaunchKernelGGL((ag_ring1_kernel<I, true>), gL, blk, 0, st, g, nL, list[1], dState, dNumber, dAgg);
+        if (nS) hipLaunchKernelGGL((ag_ring2_kernel<I, false>), gS, blk, 0, st, g, seed, nS, list[0], dState, dAgg);
+        if (nL) hipLaunchKernelGGL((ag_ring2_kernel<I, true>), gL, blk, 0, st, g, seed, nL, list[1], dState, dAgg);
+        uint32_t nAgg = 0;
+        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&nAgg, dNumber + M, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess) { rc = fail("rings"); return; }
+        out.aggregates = nAgg;
+    });
+    if (rc) return rc;
+    // the largest and the smallest aggregate
+    uint32_t mm[3] = {UNDECIDED, 0, 0};                        // smallest, largest, "an id out of range"
+    if (size.alloc((out.aggregates + 3) * 4)) return fail("temporary allocation (aggregate sizes)");
+    uint32_t* const dSize = size.as<uint32_t>();
+    if (hipMemsetAsync(dSize, 0, out.aggregates * 4, st) != hipSuccess ||
+        hipMemcpyAsync(dSize + out.aggregates, mm, 12, hipMemcpyHostToDevice, st) != hipSuccess)
+        return fail("aggregate sizes");
+    hipLaunchKernelGGL(ag_hist_kernel, gridFor(M), dim3(AG_THREADS), 0, st, M, (uint32_t)out.aggregates, dAgg, dSize, dSize + out.aggregates + 2);
+    hipLaunchKernelGGL(ag_minmax_kernel, gridFor(out.aggregates), dim3(AG_THREADS), 0, st, out.aggregates, dSize, dSize + out.aggregates);
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(mm, dSize + out.aggregates, 12, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+        return fail("aggregate sizes");
+    if (mm[2]) { fprintf(stderr, "libspmvhip: aggregate: a vertex was left without an aggregate\n"); return EXIT_FAILURE; }
+    out.minAggRows = mm[0]; out.maxAggRows = mm[1];
+    out.ms = msSince(t0);
+    if (info) *info = out;
+    return EXIT_SUCCESS;
+}
+
+int amgBuild(spmat* hA, const DevMat* a0, const spmvAmgOpts* o, DevMat* m, hipStream_t st) {
+    const auto t0 = std::chrono::steady_clock::now();
+    AmgHierarchy* H = m->amg = new AmgHierarchy;
+    H->srcId = a0->id;
+    const uint64_t coarseRows = o && o->coarseRows ? o->coarseRows : 512;
+    const uint32_t maxLevels = o && o->maxLevels ? o->maxLevels : SPMV_AMG_MAX_LEVELS;
+    auto sweeps = [](unsigned v, uint32_t dflt) { return v == 0 ? dflt : v == SPMV_AMG_NO_SWEEPS ? 0u : v; };
+    H->seed = o ? o->seed : 0u;
+    H->omega = o && o->omega != 0.0 ? o->omega : 2.0 / 3.0;
+    H->nu1 = sweeps(o ? o->nu1 : 0, 1); H->nu2 = sweeps(o ? o->nu2 : 0, 1); H->nuCoarse = sweeps(o ? o->nuCoarse : 0, 8);
+    spmvAmgInfo& info = H->info;
+    auto fail = [&](const char* what) { return buildFail(st, "multigrid setup", what); };
+    auto vec = [&](double** p, uint64_t n) { return hipMalloc(p, std::max<uint64_t>(n, 2) * sizeof(double)) != hipSuccess; };
+    H->lv.reserve(SPMV_AMG_MAX_LEVELS);                        // (a level is referred to while the next one is appended)
+    H->lv.emplace_back();
+    for (uint32_t l = 0;; ++l) {
+        AmgLevel& L = H->lv[l];
+        spmat* cur = l ? &L.A : hA;
+        const DevMat* a = matOf(cur);
+        L.M = a->M; L.nnz = a->NZ;
+        info.rows[l] = L.M; info.nnz[l] = L.nnz;
+        info.levels = l + 1;
+        if (vec(&L.dinv, L.M) || vec(&L.t, L.M) || vec(&L.d, L.M) || (l && vec(&L.z, L.M))) return fail("allocation of a level's vectors");
+        info.bytes += (l ? 5 : 3) * L.M * 8 + (l ? handleBytes(cur) : 0);
+        long bad = -1;
+        if (levelDinv(a, L.dinv, &bad, st)) return fail("the diagonal");
+        if (bad >= 0) {
+            fprintf(stderr, "libspmvhip: multigrid setup: row %ld of level %u does not hold exactly one stored diagonal entry\n", bad, l);
+            return EXIT_FAILURE;
+        }
+        if (warmSpmv(cur, L.d, L.t, st)) return fail("the SpMV selection of a level");
+        if (L.M <= coarseRows || l + 1 == maxLevels) break;
+        // aggregates -> P (its column array IS agg), R, A P, R (A P)
+        uint32_t *irp = nullptr, *agg = nullptr;
+        double* ones = nullptr;
+        spmvAggInfo ai{};
+        bool ok = hipMalloc(&irp, (L.M + 1) * 4) == hipSuccess && hipMalloc(&agg, L.M * 4) == hipSuccess && hipMalloc(&ones, L.M * 8) == hipSuccess &&
+                  !aggregateCsr(a, H->seed, S.aggK, agg, &ai, st);
+        const bool alone = ok && ai.aggregates == L.M;         // every vertex its own aggregate: nothing to coarsen
+        if (ok && !alone) {
+            enqueueIota(L.M + 1, irp, st);
+            hipLaunchKernelGGL(amg_ones_kernel, gridFor(L.M), dim3(AG_THREADS), 0, st, L.M, ones);
+            ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
+        }
+        if (!ok || alone) {
+            (void)hipFree(irp); (void)hipFree(agg); (void)hipFree(ones);
+            if (alone) break;
+            return fail("the aggregation");
+        }
+        L.nAgg = ai.aggregates;
+        info.aggregates[l] = L.nAgg;
+        if (ownCsr(&L.P, L.M, L.nAgg, L.M, irp, agg, ones)) return fail("the prolongator");
+        L.agg = matOf(&L.P)->JA;
+        spmvSpgemmInfo s1{}, s2{};
+        if (spmvHipCsrTranspose(&L.P, &L.R) || spmvHipSpGEMM(cur, &L.P, nullptr, &L.AP, &s1)) return fail("a level's products");
+        H->lv.emplace_back();
+        if (spmvHipSpGEMM(&L.R, &L.AP, nullptr, &H->lv[l + 1].A, &s2)) { H->lv.pop_back(); return fail("a level's products"); }
+        info.tempBytes = std::max<ulong>(info.tempBytes, std::max(s1.tempBytes, s2.tempBytes));
+        info.bytes += handleBytes(&L.P) + handleBytes(&L.R) + handleBytes(&L.AP);
+        if (vec(&H->lv[l + 1].r, L.nAgg)) return fail("allocation of a level's vectors");
+        if (warmSpmv(&L.R, L.d, H->lv[l + 1].r, st)) return fail("the SpMV selection of a restriction");
+    }
+    double sum = 0;
+    for (uint32_t l = 0; l < info.levels; ++l) sum += (double)info.nnz[l];
+    info.opComplexity = info.nnz[0] ? sum / (double)info.nnz[0] : 1.0;
+    info.ms = msSince(t0);
+    return EXIT_SUCCESS;
+}
+
+int amgRefresh(DevMat* m, spmat* hA, hipStream_t st) {
+    const auto t0 = std::chrono::steady_clock::now();
+    AmgHierarchy* H = m->amg;
+    auto fail = [&](const char* what) { return buildFail(st, "multigrid refresh", what); };
+    for (size_t l = 0; l < H->lv.size(); ++l) {
+        AmgLevel& L = H->lv[l];
+        spmat* cur = l ? &L.A : hA;
+        long bad = -1;
+        if (levelDinv(matOf(cur), L.dinv, &bad, st)) return fail("the diagonal");
+        if (bad >= 0) { fprintf(stderr, "libspmvhip: multigrid refresh: row %ld of level %zu lost its one diagonal entry\n", bad, l); return EXIT_FAILURE; }
+        if (warmSpmv(cur, L.d, L.t, st)) return fail("the SpMV selection of a level");
+        if (l + 1 == H->lv.size()) break;
+        if (spmvHipSpGEMMRefresh(&L.AP, cur, &L.P, nullptr) || spmvHipSpGEMMRefresh(&H->lv[l + 1].A, &L.R, &L.AP, nullptr)) return fail("a level's products");
+    }
+    H->info.ms = msSince(t0);
+    return EXIT_SUCCESS;
+}
+
+int enqueueAmgCycle(const DevMat* m, spmat* hA, const double* r0, double* z0, hipStream_t st, const uint32_t* stop, unsigned long* launches) {
+    AmgHierarchy* H = m->amg;
+    const size_t nl = H->lv.size();
+    const double om = H->omega;
+    unsigned long n = 0;
+    auto pass = [&](uint64_t rows, const auto& op, std::initializer_list<const void*> ptrs) {
+        bool al = true;
+        for (const void* p : ptrs) al = al && aligned16(p);
+        launchVec(rows, nullptr, op, al, nullptr, nullptr, st);
+        ++n;
+    };
+    auto spmv = [&](spmat* h, const double* x, double* y) { ++n; return spmvHipEnqueueAutoRows(h, const_cast<double*>(x), y, st); };
+    auto matAt = [&](size_t l) { return l ? &H->lv[l].A : hA; };
+    auto sweep = [&](size_t l, const double* r, double* z) {
+        AmgLevel& L = H->lv[l];
+        if (spmv(matAt(l), z, L.t)) return EXIT_FAILURE;
+        pass(L.M, AmgSweepOp{{stop}, r, L.t, L.dinv, z, om}, {r, L.t, L.dinv, z});
+        return EXIT_SUCCESS;
+    };
+    for (size_t l = 0; l < nl; ++l) {                          // down
+        AmgLevel& L = H->lv[l];
+        const double* r = l ? L.r : r0;
+        double* z = l ? L.z : z0;
+        const bool last = l + 1 == nl;
+        const uint32_t sweeps = last ? H->nuCoarse : H->nu1;
+        if (sweeps == 0) pass(L.M, AmgZeroOp{{stop}, z}, {z});
+        else pass(L.M, AmgFirstOp{{stop}, r, L.dinv, z, om}, {r, L.dinv, z});
+        for (uint32_t s = 1; s < sweeps; ++s)
+            if (sweep(l, r, z)) return EXIT_FAILURE;
+        if (last) break;
+        if (spmv(matAt(l), z, L.t)) return EXIT_FAILURE;
+        pass(L.M, AmgResidOp{{stop}, r, L.t, L.d}, {r, L.t, L.d});
+        if (spmv(&L.R, L.d, H->lv[l + 1].r)) return EXIT_FAILURE;
+    }
+    for (size_t l = nl - 1; l-- > 0;) {                        // up
+        AmgLevel& L = H->lv[l];
+        const double* r = l ? L.r : r0;
+        double* z = l ? L.z : z0;
+        pass(L.M, AmgCorrectOp{{stop}, H->lv[l + 1].z, L.agg, z}, {z});
+        for (uint32_t s = 0; s < H->nu2; ++s)
+            if (sweep(l, r, z)) return EXIT_FAILURE;
+    }
+    if (launches) *launches += n;
+    return hipGetLastError() == hipSuccess ? EXIT_SUCCESS : EXIT_FAILURE;
+}
+
+}  // namespace spmvhip
+
+using namespace spmvhip;
+
+// the checks the aggregation and the setup share with spmvHipColourCSR: ready, live, CSR, square, 32-bit rows and positions
+static DevMat* squareCsr(spmat* dA, const char* who) {
+    if (!ready(who)) return nullptr;
+    DevMat* d = csrOf(dA, who, "the handle is an ELL handle (only CSR handles are aggregated)");
+    if (!d) return nullptr;
+    if (d->M != d->N) { ERR("%s: M=%lu != N=%lu: the matrix is not square", who, (unsigned long)d->M, (unsigned long)d->N); return nullptr; }
+    if (d->NZ >= IRP32_LIMIT || d->M >= (1ull << 31)) {
+        ERR("%s: NZ=%lu, M=%lu: positions and rows are 32-bit (limits %lu, 2^31)", who, (unsigned long)d->NZ, (unsigned long)d->M,
+            (unsigned long)IRP32_LIMIT);
+        return nullptr;
+    }
+    if (d->NZ && !d->JA) { ERR("%s: the handle has no column array", who); return nullptr; }
+    return d;
+}
+
+// dM as a hierarchy of dA
+static DevMat* hierarchyOf(spmat* dM, spmat* dA, const char* who, DevMat** pa) {
+    if (!ready(who)) return nullptr;
+    if (!dM || !dA) { ERR("%s: %s is NULL", who, !dM ? "dM" : "dA"); return nullptr; }
+    DevMat* m = anyDescOf(dM, who);
+    if (!m) return nullptr;
+    if (!m->amg) { ERR("%s: dM was not made by spmvHipAmgSetup", who); return nullptr; }
+    DevMat* a = csrOf(dA, who, "dA is an ELL handle");
+    if (!a) return nullptr;
+    if (a->id != m->amg->srcId) { ERR("%s: dA is not the handle dM was set up from", who); return nullptr; }
+    *pa = a;
+    return m;
+}
+
+extern "C" {
+
+int spmvHipAggregateCSR(spmat* dA, const spmvAggOpts* opts, uint32_t* dAgg, spmvAggInfo* info) {
+    const char* who = "spmvHipAggregateCSR";
+    DevMat* d = squareCsr(dA, who);
+    if (!d) return EXIT_FAILURE;
+    if (d->M && !dAgg) { ERR("%s: dAgg is NULL", who); return EXIT_FAILURE; }
+    spmvAggInfo out{};
+    if (aggregateCsr(d, opts ? opts->seed : 0u, S.aggK, dAgg, &out, S.stream)) { ERR("%s: the aggregation failed", who); return EXIT_FAILURE; }
+    if (info) *info = out;
+    return EXIT_SUCCESS;
+}
+
+int spmvHipAmgSetup(spmat* dA, const spmvAmgOpts* opts, spmat* dM, spmvAmgInfo* info) {
+    const char* who = "spmvHipAmgSetup";
+    if (!ready(who)) return EXIT_FAILURE;
+    if (!dA || !dM) { ERR("%s: %s is NULL", who, !dA ? "dA" : "dM"); return EXIT_FAILURE; }
+    if (dM == dA) { ERR("%s: dM is the source handle itself", who); return EXIT_FAILURE; }
+    DevMat* a = squareCsr(dA, who);
+    if (!a) return EXIT_FAILURE;
+    if (a->NZ && (!a->JA || !a->AS)) { ERR("%s: the source has no column or value array", who); return EXIT_FAILURE; }
+    if (opts && opts->maxLevels > SPMV_AMG_MAX_LEVELS) { ERR("%s: maxLevels %u is above %d", who, opts->maxLevels, SPMV_AMG_MAX_LEVELS); return EXIT_FAILURE; }
+    if (opts && !(opts->omega >= 0.0 && std::isfinite(opts->omega))) { ERR("%s: omega %g is negative or not finite", who, opts->omega); return EXIT_FAILURE; }
+    DevMat* m = new DevMat;
+    m->kind = Kind::CSR;
+    m->M = m->N = a->M;
+    m->srcId = a->id;
+    if (amgBuild(dA, a, opts, m, S.stream)) { ERR("%s: building the hierarchy failed", who); freeDesc(m); return EXIT_FAILURE; }
+    publish(dM, m, m->M, m->N, 0, 0);
+    if (info) *info = m->amg->info;
+    return EXIT_SUCCESS;
+}
+
+int spmvHipAmgRefresh(spmat* dM, spmat* dA) {
+    const char* who = "spmvHipAmgRefresh";
+    DevMat* a = nullptr;
+    DevMat* m = hierarchyOf(dM, dA, who, &a);
+    if (!m) return EXIT_FAILURE;
+    if (amgRefresh(m, dA, S.stream)) { ERR("%s: recomputing the hierarchy failed", who); return EXIT_FAILURE; }
+    return EXIT_SUCCESS;
+}
+
+int spmvHipAmgApply(spmat* dM, spmat* dA, const double* dR, double* dZ) {
+    const char* who = "spmvHipAmgApply";
+    const Ctx cx = libraryCtx();
+    DevMat* a = nullptr;
+    DevMat* m = hierarchyOf(dM, dA, who, &a);
+    if (!m) return EXIT_FAILURE;
+    if (!dR || !dZ) { ERR("%s: %s is NULL", who, !dR ? "dR" : "dZ"); return EXIT_FAILURE; }
+    if (a->M != m->M) { ERR("%s: dA has %lu rows, dM %lu", who, (unsigned long)a->M, (unsigned long)m->M); return EXIT_FAILURE; }
+    const uintptr_t r0 = (uintptr_t)dR, z0 = (uintptr_t)dZ, bytes = m->M * sizeof(double);
+    if (m->M && r0 < z0 + bytes && z0 < r0 + bytes) { ERR("%s: dR and dZ are the same vector or overlap", who); return EXIT_FAILURE; }
+    if (m->M == 0) return nothingToLaunch(cx, m, nullptr);
+    Launch L(cx, grid2d((m->M + KB - 1) / KB, KT), dim3(KT));
+    if (enqueueAmgCycle(m, dA, dR, dZ, cx.stream, nullptr, nullptr)) { ERR("%s: launch failed", who); return EXIT_FAILURE; }
+    return L.finish(who);
+}
+
+int spmvHipAmgInfo(spmat* dM, spmvAmgInfo* info) {
+    const char* who = "spmvHipAmgInfo";
+    DevMat* m = anyDescOf(dM, who);
+    if (!m) return EXIT_FAILURE;
+    if (!m->amg || !info) { ERR("%s: %s", who, !info ? "info is NULL" : "dM was not made by spmvHipAmgSetup"); return EXIT_FAILURE; }
+    *info = m->amg->info;
+    return EXIT_SUCCESS;
+}
+
+int spmvHipAmgLevel(spmat* dM, unsigned level, spmat* dAl, const uint32_t** dAgg, const double** dDinv) {
+    const char* who = "spmvHipAmgLevel";
+    DevMat* m = anyDescOf(dM, who);
+    if (!m) return EXIT_FAILURE;
+    if (!m->amg) { ERR("%s: dM was not made by spmvHipAmgSetup", who); return EXIT_FAILURE; }
+    if (level >= m->amg->lv.size()) { ERR("%s: level %u of %zu", who, level, m->amg->lv.size()); return EXIT_FAILURE; }
+    const AmgLevel& L = m->amg->lv[level];
+    if (dAl) {
+        if (level) *dAl = L.A; else memset(dAl, 0, sizeof *dAl);
+        dAl->M = dAl->N = L.M; dAl->NZ = L.nnz;
+        dAl->dev = nullptr;
+    }
+    if (dAgg) *dAgg = L.agg;
+    if (dDinv) *dDinv = L.dinv;
+    return EXIT_SUCCESS;
+}
+
+}  // extern "C"

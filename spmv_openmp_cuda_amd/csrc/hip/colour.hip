@@ -270,41 +270,48 @@ int permuteCsr(const DevMat* a, const uint32_t* inv, DevMat* t, hipStream_t st) 
     return EXIT_SUCCESS;
 }
 
+int buildIncoming(const DevMat* a, IncomingPattern& in, hipStream_t st, const char* module) {
+    const uint64_t nnz = a->NZ, M = a->M;
+    auto fail = [&](const char* what) { return buildFail(st, module, what); };
+    if (!nnz) return EXIT_SUCCESS;
+    if (in.rowOf.alloc(nnz * 4)) return fail("temporary allocation (4 B per entry)");
+    enqueueRowOf(M, a->IRP, a->irpBytes, in.rowOf.as<uint32_t>(), st);
+    uint32_t asym = 1;
+    if (a->maxRowNnz <= CL_LONG &&
+        deviceFlag(0, st, "cl_symmetric_kernel", &asym, [&](uint32_t* dFlag) {
+            withIrp(a, [&](auto irp) {
+                hipLaunchKernelGGL((cl_symmetric_kernel<IrpT<decltype(irp)>>), gridFor(nnz), dim3(CL_THREADS), 0, st, nnz, M, irp, a->JA,
+                                   in.rowOf.as<uint32_t>(), dFlag);
+            });
+        }))
+        return fail("symmetry check");
+    in.symmetric = asym ? 0 : 1;
+    if (!asym) return EXIT_SUCCESS;
+    if (in.keys.alloc(nnz * 4) || in.colBuf.alloc(nnz * 4) || in.ptrBuf.alloc((M + 1) * 4)) return fail("temporary allocation (transposed pattern)");
+    // (preset: with column ids >= N the sort leaves keys out of order and the bounds kernel words unwritten)
+    if (hipMemsetAsync(in.ptrBuf.p, 0, (M + 1) * 4, st) != hipSuccess) return fail("transposed pattern");
+    if (enqueueSortedByColumn(nnz, M, bitsFor(a->N), a->JA, in.rowOf.as<uint32_t>(), in.keys.as<uint32_t>(), in.colBuf.as<uint32_t>(),
+                              in.ptrBuf.as<uint32_t>(), in.sortTmp, st) != hipSuccess)
+        return fail("sort");
+    in.ptr = in.ptrBuf.as<uint32_t>();
+    in.col = in.colBuf.as<uint32_t>();
+    return EXIT_SUCCESS;
+}
+
 int colourCsr(const DevMat* a, int order, uint32_t seed, uint32_t K, uint32_t* dColour, uint32_t* dPerm, spmvColourInfo* info,
               hipStream_t st) {
     const auto t0 = std::chrono::steady_clock::now();
-    const uint64_t nnz = a->NZ, M = a->M;
+    const uint64_t M = a->M;
     spmvColourInfo out{};
     out.symmetric = 1;                                         // (no entry: nothing comes in from the transposed side)
     auto fail = [&](const char* what) { return buildFail(st, "colour", what); };
     if (M == 0) { if (info) *info = out; return EXIT_SUCCESS; }
-    TempBuf rowOf, tkeys, tcolBuf, tptrBuf, sortTmp, colourBuf, lists, state, iotaBuf, sortedBuf, permBuf;
+    TempBuf colourBuf, lists, state, iotaBuf, sortedBuf, permBuf;
     // 1. the incoming side
-    const uint32_t *tptr = nullptr, *tcol = nullptr;
-    if (nnz) {
-        if (rowOf.alloc(nnz * 4)) return fail("temporary allocation (4 B per entry)");
-        enqueueRowOf(M, a->IRP, a->irpBytes, rowOf.as<uint32_t>(), st);
-        uint32_t asym = 1;
-        if (a->maxRowNnz <= CL_LONG &&
-            deviceFlag(0, st, "cl_symmetric_kernel", &asym, [&](uint32_t* dFlag) {
-                withIrp(a, [&](auto irp) {
-                    hipLaunchKernelGGL((cl_symmetric_kernel<IrpT<decltype(irp)>>), gridFor(nnz), dim3(CL_THREADS), 0, st, nnz, M, irp, a->JA,
-                                       rowOf.as<uint32_t>(), dFlag);
-                });
-            }))
-            return fail("symmetry check");
-        out.symmetric = asym ? 0 : 1;
-        if (asym) {
-            if (tkeys.alloc(nnz * 4) || tcolBuf.alloc(nnz * 4) || tptrBuf.alloc((M + 1) * 4)) return fail("temporary allocation (transposed pattern)");
-            // (preset: with column ids >= N the sort leaves keys out of order and the bounds kernel words unwritten)
-            if (hipMemsetAsync(tptrBuf.p, 0, (M + 1) * 4, st) != hipSuccess) return fail("transposed pattern");
-            if (enqueueSortedByColumn(nnz, M, bitsFor(a->N), a->JA, rowOf.as<uint32_t>(), tkeys.as<uint32_t>(), tcolBuf.as<uint32_t>(),
-                                      tptrBuf.as<uint32_t>(), sortTmp, st) != hipSuccess)
-                return fail("sort");
-            tptr = tptrBuf.as<uint32_t>();
-            tcol = tcolBuf.as<uint32_t>();
-        }
-    }
+    IncomingPattern in;
+    if (buildIncoming(a, in, st, "colour")) return EXIT_FAILURE;
+    out.symmetric = in.symmetric;
+    const uint32_t *tptr = in.ptr, *tcol = in.col;
     // 2. colours, lists and the state: cnt[0 .. K] short counts, cnt[K+1 .. 2K+1] long counts, then the largest colour
     if (!dColour) {
         if (colourBuf.alloc(M * 4)) return fail("temporary allocation (colours)");

@@ -33,6 +33,7 @@ struct TileFormat;          // column-sliced two-phase format, tiles.hip
 struct SellFormat;          // SELL-C-sigma, sell.hip
 struct StripeFormat;        // bin-wise CSC (y bins in LDS, x from the XCD's L2), stripes.hip
 struct SpgemmPlan;          // what a product C = A B keeps for its refresh, spgemm.hip
+struct AmgHierarchy;        // the levels of an aggregation multigrid preconditioner, amg.hip
 struct TempBuf;             // a scoped device buffer, device_prims.hpp
 
 // the level sets of one triangle (built by triAnalyse in trsv.hip; the ILU(0) factorisation of ilu0.hip runs on the lower one)
@@ -102,6 +103,9 @@ struct DevMat {
     // a product built by spmvHipSpGEMM (spgemm.hip): the ids of its two sources and its rows by class (4 B per row); no
     // pointer to a source is kept
     SpgemmPlan* prod = nullptr;
+    // a multigrid hierarchy built by spmvHipAmgSetup (amg.hip): the handle is then no matrix (no arrays, NZ = 0) and only
+    // the spmvHipAmg* calls, a Krylov solve's dM and hipFreeSpmat take it; srcId is the id of its level-0 matrix
+    AmgHierarchy* amg = nullptr;
     // the level-set schedules of the triangular solve (trsv.hip), [SPMV_TRI_LOWER] and [SPMV_TRI_UPPER]: built from the
     // pattern at the first solve or by spmvHipTriAnalyse, kept across value updates (the solve reads AS live)
     TriSchedule* tri[2] = {nullptr, nullptr};
@@ -193,6 +197,19 @@ int  spgemmBuild(const DevMat* a, const DevMat* b, const spmvSpgemmOpts* opts, D
 int  spgemmRefresh(DevMat* c, const DevMat* a, const DevMat* b, spmvSpgemmInfo* info, hipStream_t stream);
 bool spgemmSources(const DevMat* c, uint64_t* idA, uint64_t* idB);   // false: c is no product
 void freeSpgemmPlan(SpgemmPlan* p);
+// Aggregation multigrid (amg.hip; contracts in spmvHip.h, design in DESIGN.md section 24).  aggregateCsr: the aggregate ids
+// of the checked square handle into dAgg (M words), K rounds per host check; synchronous, allocates, temporaries freed
+// before it returns.  amgBuild: the hierarchy of hA / a into m->amg (on failure the caller frees m with whatever it holds);
+// amgRefresh: the products and the inverse diagonals again.  enqueueAmgCycle: z = V(0, r), kernels only on `stream`; every
+// kernel of the cycle but its SpMVs returns at once when `stop` is set and *stop != 0; *launches grows by the kernels
+// enqueued (an SpMV counted as one).  ownCsr (upload.hip): a CSR handle that takes ownership of three device arrays.
+int  aggregateCsr(const DevMat* a, uint32_t seed, uint32_t K, uint32_t* dAgg, spmvAggInfo* info, hipStream_t stream);
+int  amgBuild(spmat* hA, const DevMat* a, const spmvAmgOpts* opts, DevMat* m, hipStream_t stream);
+int  amgRefresh(DevMat* m, spmat* hA, hipStream_t stream);
+int  enqueueAmgCycle(const DevMat* m, spmat* hA, const double* r, double* z, hipStream_t stream, const uint32_t* stop,
+                     unsigned long* launches);
+void freeAmg(AmgHierarchy* h);
+int  ownCsr(spmat* dst, uint64_t M, uint64_t N, uint64_t NZ, uint32_t* dIRP, uint32_t* dJA, double* dAS);
 // Triangular solves (trsv.hip; contract in spmvHip.h, design in DESIGN.md section 17).  triAnalyse builds d->tri[uplo]
 // (synchronous, allocates, temporaries freed before it returns; runThreshold = the T of the single-workgroup runs, 0: none);
 // enqueueTrsv enqueues one solve of an analysed triangle on `stream` (no allocation, no sync) and reports the last launch;

@@ -99,6 +99,19 @@ hipError_t exclusiveScan(TempBuf& ws, In in, T* out, T init, size_t n, hipStream
 void enqueueIota(uint64_t n, uint32_t* p, hipStream_t stream);                  // p[i] = i          (transpose.hip)
 void enqueueFill32(uint32_t* p, uint64_t n, uint32_t v, hipStream_t stream);    // p[i] = v
 
+// The incoming side of a square handle's adjacency (colour.hip; the colouring and the aggregation share it): the pattern
+// transposed -- ptr / col, M + 1 and nnz words -- or nothing (ptr == col == null, symmetric = 1) when the stored pattern
+// was found structurally symmetric, which is tried when no row stores more than 64 entries.  The sort is enqueued on
+// `stream`; the buffers live as long as the object, which must outlive what reads them.
+struct IncomingPattern {
+    TempBuf rowOf, keys, colBuf, ptrBuf, sortTmp;
+    const uint32_t* ptr = nullptr;
+    const uint32_t* col = nullptr;
+    int symmetric = 1;                              // (no entry: nothing comes in from the transposed side)
+};
+struct DevMat;
+int buildIncoming(const DevMat* a, IncomingPattern& in, hipStream_t stream, const char* module);
+
 // the bits that hold every key below n (at least 1, at most 32); every key in [0, maxKey] needs bitsFor(maxKey + 1)
 inline unsigned bitsFor(uint64_t n) {
     unsigned bits = 1;

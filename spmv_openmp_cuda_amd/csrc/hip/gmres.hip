@@ -416,13 +416,15 @@ int gmresSolve(spmat* hA, const DevMat* a, const DevMat* m, const double* b, dou
     h.tol2 = o->tol * o->tol;
     HIP_TRY(hipMemcpyAsync(st, &h, GSTATE_HEAD, hipMemcpyHostToDevice, s));
     spmvTriInfo tl{}, tu{};
-    if (pre) { triInfo(m, SPMV_TRI_LOWER, &tl); triInfo(m, SPMV_TRI_UPPER, &tu); }
+    if (pre && !m->amg) { triInfo(m, SPMV_TRI_LOWER, &tl); triInfo(m, SPMV_TRI_UPPER, &tu); }
     const uint32_t* flags = &st->stop;                                   // {stop, skip}
     dim3 g, bl;
     auto precond = [&](const double* in, double* outv, const uint32_t* flag) {
+        if (m->amg) return enqueueAmgCycle(m, hA, in, outv, s, flag, &out.launches);   // the cycle of a hierarchy
         enqueueTrsv(m, SPMV_TRI_LOWER, SPMV_DIAG_UNIT, in, outv, s, &g, &bl, flag);
         enqueueTrsv(m, SPMV_TRI_UPPER, SPMV_DIAG_STORED, outv, outv, s, &g, &bl, flag);
         out.launches += tl.launches + tu.launches;
+        return EXIT_SUCCESS;
     };
     auto spmv = [&](const double* in, double* outv) {
         ++out.launches;
@@ -454,7 +456,7 @@ int gmresSolve(spmat* hA, const DevMat* a, const DevMat* m, const double* b, dou
         vec(GScaleOp{r, V, &st->beta, &st->skip, 0.0}, {r, V});          // v[0] = r / beta
         for (uint32_t j = 0; j < steps; ++j) {
             const double* vj = V + (uint64_t)j * ldv;
-            if (pre) precond(vj, z, &st->skip);
+            if (pre && precond(vj, z, &st->skip)) return EXIT_FAILURE;
             if (spmv(pre ? z : vj, w)) return EXIT_FAILURE;
             project(j + 1, st->h);
             if (fused) {
@@ -475,7 +477,7 @@ int gmresSolve(spmat* hA, const DevMat* a, const DevMat* m, const double* b, dou
         if (pre) {
             hipLaunchKernelGGL(gmres_comb_kernel, ugrid, dim3(KT), 0, s, n, V, ldv, st, w, (double*)nullptr, 0, nb);
             ++out.launches;
-            precond(w, z, &st->stop);
+            if (precond(w, z, &st->stop)) return EXIT_FAILURE;
             vec(GAddOp{x, z, &st->stop}, {x, z});
         } else {
             hipLaunchKernelGGL(gmres_comb_kernel, ugrid, dim3(KT), 0, s, n, V, ldv, st, w, x, (int)aligned16(x), nb);

@@ -298,13 +298,15 @@ int krylovSolve(int bicg, spmat* hA, const DevMat* a, const DevMat* m, const dou
     h.tol2 = o->tol * o->tol;
     HIP_TRY(hipMemcpyAsync(st, &h, sizeof h, hipMemcpyHostToDevice, s));
     spmvTriInfo tl{}, tu{};
-    if (pre) { triInfo(m, SPMV_TRI_LOWER, &tl); triInfo(m, SPMV_TRI_UPPER, &tu); }
+    if (pre && !m->amg) { triInfo(m, SPMV_TRI_LOWER, &tl); triInfo(m, SPMV_TRI_UPPER, &tu); }
     const uint32_t* stop = &st->stop;
     dim3 g, bl;
     auto precond = [&](const double* in, double* outv) {                 // outv = U^-1 (L^-1 in): the ILU(0) pair of dM
+        if (m->amg) return enqueueAmgCycle(m, hA, in, outv, s, stop, &out.launches);   // ... or the cycle of a hierarchy
         enqueueTrsv(m, SPMV_TRI_LOWER, SPMV_DIAG_UNIT, in, outv, s, &g, &bl, stop);
         enqueueTrsv(m, SPMV_TRI_UPPER, SPMV_DIAG_STORED, outv, outv, s, &g, &bl, stop);
         out.launches += tl.launches + tu.launches;
+        return EXIT_SUCCESS;
     };
     auto spmv = [&](double* in, double* outv) {
         ++out.launches;
@@ -330,7 +332,7 @@ int krylovSolve(int bicg, spmat* hA, const DevMat* a, const DevMat* m, const dou
         vec(InitOp{b, q, r, nullptr}, {b, q, r});
         finish(F_CG_INIT, 0, 2);
         if (pre) {
-            precond(r, z);
+            if (precond(r, z)) return EXIT_FAILURE;
             vec(GuardedDot{{r, z}}, {r, z});
             finish(F_CG_RZ, 0, 1);
         }
@@ -344,7 +346,7 @@ int krylovSolve(int bicg, spmat* hA, const DevMat* a, const DevMat* m, const dou
                 vec(CgUpdateOp{x, p, r, q, 0.0}, {x, p, r, q});
                 finish(F_CG_RR, k, 1);
                 if (pre) {
-                    precond(r, z);
+                    if (precond(r, z)) return EXIT_FAILURE;
                     vec(GuardedDot{{r, z}}, {r, z});
                     finish(F_CG_RZ, k, 1);
                 }
@@ -370,13 +372,13 @@ int krylovSolve(int bicg, spmat* hA, const DevMat* a, const DevMat* m, const dou
             const uint64_t end = std::min<uint64_t>(o->maxIter, k + K - 1);
             for (; k <= end; ++k) {
                 vec(BiPOp{r, p, vv, k == 1, 0.0, 0.0}, {r, p, vv});
-                if (pre) precond(p, phat);
+                if (pre && precond(p, phat)) return EXIT_FAILURE;
                 if (spmv(phat, vv)) return EXIT_FAILURE;
                 vec(GuardedDot{{rhat, vv}}, {rhat, vv});
                 finish(F_BI_ALPHA, k, 1);
                 vec(SOp{r, vv, sv, 0.0}, {r, vv, sv});
                 finish(F_BI_SS, k, 1);
-                if (pre) precond(sv, shat);
+                if (pre && precond(sv, shat)) return EXIT_FAILURE;
                 if (spmv(shat, t)) return EXIT_FAILURE;
                 vec(TtTsOp{t, sv}, {t, sv});
                 finish(F_BI_OMEGA, k, 2);

@@ -594,7 +594,12 @@ static int krylovArgs(const char* who, spmat* dA, spmat* dM, const double* dB, d
         return EXIT_FAILURE;
     }
     DevMat* m = nullptr;
-    if (dM) {
+    DevMat* hier = dM ? anyDescOf(dM, who) : nullptr;
+    if (dM && !hier) return EXIT_FAILURE;
+    if (hier && hier->amg) {                                 // a multigrid hierarchy: M^-1 v is its cycle
+        if (hier->srcId != a->id) { ERR("%s: dM is a multigrid hierarchy of another handle than dA", who); return EXIT_FAILURE; }
+        m = hier;
+    } else if (dM) {
         if (!(m = triHandle(dM, SPMV_TRI_LOWER, who))) return EXIT_FAILURE;
         if (m->M != a->M) { ERR("%s: dM has %lu rows, dA %lu", who, (unsigned long)m->M, (unsigned long)a->M); return EXIT_FAILURE; }
         if (m->NZ && !m->AS && !m->unit) { ERR("%s: dM has no value array", who); return EXIT_FAILURE; }

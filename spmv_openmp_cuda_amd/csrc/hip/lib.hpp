@@ -24,6 +24,7 @@ struct State {
     uint32_t    iluGroup = 16;          // hipSpILU0CSR: lanes per row
     int         gmresFused = 0;         // hipSpGMRESCSR: fold the first CGS2 update into the second projection
     uint32_t    colourK = 16;           // spmvHipColourCSR: rounds per host check
+    uint32_t    aggK = 16;              // spmvHipAggregateCSR: rounds per host check
     uint32_t    krylovK[2] = {16, 16};  // hipSpCGCSR, hipSpBiCGStabCSR: iterations per host check
     int         ldsOrder = -1;          // lds_order_probe_kernel: -1 not run yet, 1 lane-ascending + in issue order, 0 anything else
     bool        ellRowLens = true;
@@ -48,13 +49,24 @@ inline bool ready(const char* who) {
     return false;
 }
 
-inline DevMat* descOf(spmat* h, const char* who) {
+// any live device handle, a multigrid hierarchy included: hipFreeSpmat, the spmvHipAmg* calls and the solvers' dM
+inline DevMat* anyDescOf(spmat* h, const char* who) {
     if (!h || !h->dev || h->dev == SPMAT_TAG_ELL_TRANSPOSED) {
         ERR("%s: not a device handle (upload with spMatCpyCSR/spMatCpyELL first)", who);
         return nullptr;
     }
     DevMat* d = static_cast<DevMat*>(h->dev);
     if (d->magic != 0x53504D56) { ERR("%s: corrupted device handle", who); return nullptr; }
+    return d;
+}
+// ... that is a matrix: what every SpMV, format, build and solve entry point takes
+inline DevMat* descOf(spmat* h, const char* who) {
+    DevMat* d = anyDescOf(h, who);
+    if (d && d->amg) {
+        ERR("%s: the handle is a multigrid hierarchy (spmvHipAmgSetup), not a matrix: spmvHipAmgApply, spmvHipAmgRefresh, the dM of a "
+            "Krylov solve and hipFreeSpmat take it", who);
+        return nullptr;
+    }
     return d;
 }
 // ... for a launcher: the vectors are raw device pointers whose extent the library cannot know, but a NULL one would be
@@ -116,6 +128,8 @@ int streamCSR(Ctx cx, spmat* dMat, double* dX, double* dY, bool seq);           
 int tilesForm(Ctx cx, spmat* dMat, double* dX, double* dY, bool det, const char* who);     // ... the two-phase / stripes launchers on
 int stripesForm(Ctx cx, spmat* dMat, double* dX, double* dY, int mode, const char* who);   // the given form (built at the first call)
 int autoRun(Ctx cx, spmat* dMat, double* dX, double* dY, int serial, const char* who);     // select.hip
+void freeDesc(DevMat* d);                                                          // upload.hip: a descriptor and all it holds
+void publish(spmat* h, DevMat* d, ulong M, ulong N, ulong NZ, ulong maxRowNz);     // ... into the caller's handle
 int vecFill(Ctx cx, double* dVec, size_t n, uint64_t pattern);                     // abi.hip: spmvHipVecFill
 int probeLdsOrder(hipStream_t stream);                                             // abi.hip: spmvHipProbeLdsAtomicOrder
 void freePushStream();                                                             // launch.hip: the side stream of hipSpMVTilesReducePush

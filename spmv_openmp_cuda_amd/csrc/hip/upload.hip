@@ -56,6 +56,9 @@ int buildRowBlocks2(DevMat* d, const I* IRP, uint64_t M) {
     return EXIT_SUCCESS;
 }
 
+}  // namespace
+
+namespace spmvhip {
 void freeDesc(DevMat* d) {
     if (!d) return;
     if (d->owns) {
@@ -64,6 +67,7 @@ void freeDesc(DevMat* d) {
     (void)hipFree(d->blkInfo); (void)hipFree(d->blkBase); (void)hipFree(d->tmap);
     freeTri(d->tri[0]); freeTri(d->tri[1]);
     freeSpgemmPlan(d->prod);
+    freeAmg(d->amg);
     freeTiles(d->tiles[0]); freeTiles(d->tiles[1]);
     freeSell(d->sell);
     freeStripes(d->stripes[0]); freeStripes(d->stripes[1]);
@@ -81,6 +85,9 @@ void publish(spmat* h, DevMat* d, ulong M, ulong N, ulong NZ, ulong maxRowNz) {
     h->pitchJA = h->pitchAS = d->pitch;
     h->dev = d;
 }
+}  // namespace spmvhip
+
+namespace {
 
 template <typename T>
 int narrowUpload(T** dDst, const ulong* hSrc, size_t n, ulong limit, const char* what) {
@@ -271,6 +278,21 @@ int updateValues(spmat* h, const double* AS, bool onDevice, bool reread, hipStre
     info.inPlace = !info.rebuilt && (!info.unitBefore || sameUnit);
     info.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     d->lastUpdate = info;
+    return EXIT_SUCCESS;
+}
+
+// a CSR handle over three device arrays the library itself has made (4-byte row pointers): the handle owns them from the
+// call on -- on failure they are freed with the descriptor
+int ownCsr(spmat* dst, uint64_t M, uint64_t N, uint64_t NZ, uint32_t* dIRP, uint32_t* dJA, double* dAS) {
+    DevMat* d = new DevMat;
+    d->kind = Kind::CSR;
+    d->M = M; d->N = N; d->NZ = NZ; d->irpBytes = 4;
+    d->IRP = dIRP; d->JA = dJA; d->AS = dAS;
+    std::vector<uint32_t> hIRP(M + 1);
+    const bool ok = hipOk(hipMemcpy(hIRP.data(), dIRP, hIRP.size() * 4, hipMemcpyDeviceToHost), "hipMemcpy IRP") &&
+                    !buildRowBlocks2(d, hIRP.data(), M) && !detectUnit(d, S.stream);
+    if (!ok) { freeDesc(d); return EXIT_FAILURE; }
+    publish(dst, d, M, N, NZ, 0);
     return EXIT_SUCCESS;
 }
 }  // namespace spmvhip
@@ -542,7 +564,7 @@ int spmvHipLastUpdateInfo(spmat* dMat, spmvUpdateInfo* info) {
 
 int hipFreeSpmat(spmat* h) {
     if (!h || !h->dev) return EXIT_SUCCESS;
-    DevMat* d = descOf(h, "hipFreeSpmat");
+    DevMat* d = anyDescOf(h, "hipFreeSpmat");
     if (!d) return EXIT_FAILURE;
     freeDesc(d);
     memset(h, 0, sizeof *h);
