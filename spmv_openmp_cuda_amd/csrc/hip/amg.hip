@@ -21,11 +21,9 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <chrono>
-#include <cmath>
 #include <cstring>
 #include <vector>
 
-#include "lib.hpp"
 #include "device_prims.hpp"
 #include "krylov.hpp"
 
@@ -41,7 +39,6 @@ struct AmgLevel {
 };
 
 struct AmgHierarchy {
-    uint64_t srcId = 0;
     uint32_t seed = 0, nu1 = 1, nu2 = 1, nuCoarse = 8;
     double omega = 2.0 / 3.0;
     std::vector<AmgLevel> lv;
@@ -413,10 +410,9 @@ int aggregateCsr(const DevMat* a, uint32_t seed, uint32_t K, uint32_t* dAgg, spm
     return EXIT_SUCCESS;
 }
 
-int amgBuild(spmat* hA, const DevMat* a0, const spmvAmgOpts* o, DevMat* m, hipStream_t st) {
+int amgBuild(spmat* hA, const spmvAmgOpts* o, uint32_t K, DevMat* m, hipStream_t st) {
     const auto t0 = std::chrono::steady_clock::now();
     AmgHierarchy* H = m->amg = new AmgHierarchy;
-    H->srcId = a0->id;
     const uint64_t coarseRows = o && o->coarseRows ? o->coarseRows : 512;
     const uint32_t maxLevels = o && o->maxLevels ? o->maxLevels : SPMV_AMG_MAX_LEVELS;
     auto sweeps = [](unsigned v, uint32_t dflt) { return v == 0 ? dflt : v == SPMV_AMG_NO_SWEEPS ? 0u : v; };
@@ -450,7 +446,7 @@ int amgBuild(spmat* hA, const DevMat* a0, const spmvAmgOpts* o, DevMat* m, hipSt
         double* ones = nullptr;
         spmvAggInfo ai{};
         bool ok = hipMalloc(&irp, (L.M + 1) * 4) == hipSuccess && hipMalloc(&agg, L.M * 4) == hipSuccess && hipMalloc(&ones, L.M * 8) == hipSuccess &&
-                  !aggregateCsr(a, H->seed, S.aggK, agg, &ai, st);
+                  !aggregateCsr(a, H->seed, K, agg, &ai, st);
         const bool alone = ok && ai.aggregates == L.M;         // every vertex its own aggregate: nothing to coarsen
         if (ok && !alone) {
             enqueueIota(L.M + 1, irp, st);
@@ -546,112 +542,9 @@ int enqueueAmgCycle(const DevMat* m, spmat* hA, const double* r0, double* z0, hi
     return hipGetLastError() == hipSuccess ? EXIT_SUCCESS : EXIT_FAILURE;
 }
 
-}  // namespace spmvhip
+const spmvAmgInfo* amgInfo(const DevMat* m) { return &m->amg->info; }
 
-using namespace spmvhip;
-
-// the checks the aggregation and the setup share with spmvHipColourCSR: ready, live, CSR, square, 32-bit rows and positions
-static DevMat* squareCsr(spmat* dA, const char* who) {
-    if (!ready(who)) return nullptr;
-    DevMat* d = csrOf(dA, who, "the handle is an ELL handle (only CSR handles are aggregated)");
-    if (!d) return nullptr;
-    if (d->M != d->N) { ERR("%s: M=%lu != N=%lu: the matrix is not square", who, (unsigned long)d->M, (unsigned long)d->N); return nullptr; }
-    if (d->NZ >= IRP32_LIMIT || d->M >= (1ull << 31)) {
-        ERR("%s: NZ=%lu, M=%lu: positions and rows are 32-bit (limits %lu, 2^31)", who, (unsigned long)d->NZ, (unsigned long)d->M,
-            (unsigned long)IRP32_LIMIT);
-        return nullptr;
-    }
-    if (d->NZ && !d->JA) { ERR("%s: the handle has no column array", who); return nullptr; }
-    return d;
-}
-
-// dM as a hierarchy of dA
-static DevMat* hierarchyOf(spmat* dM, spmat* dA, const char* who, DevMat** pa) {
-    if (!ready(who)) return nullptr;
-    if (!dM || !dA) { ERR("%s: %s is NULL", who, !dM ? "dM" : "dA"); return nullptr; }
-    DevMat* m = anyDescOf(dM, who);
-    if (!m) return nullptr;
-    if (!m->amg) { ERR("%s: dM was not made by spmvHipAmgSetup", who); return nullptr; }
-    DevMat* a = csrOf(dA, who, "dA is an ELL handle");
-    if (!a) return nullptr;
-    if (a->id != m->amg->srcId) { ERR("%s: dA is not the handle dM was set up from", who); return nullptr; }
-    *pa = a;
-    return m;
-}
-
-extern "C" {
-
-int spmvHipAggregateCSR(spmat* dA, const spmvAggOpts* opts, uint32_t* dAgg, spmvAggInfo* info) {
-    const char* who = "spmvHipAggregateCSR";
-    DevMat* d = squareCsr(dA, who);
-    if (!d) return EXIT_FAILURE;
-    if (d->M && !dAgg) { ERR("%s: dAgg is NULL", who); return EXIT_FAILURE; }
-    spmvAggInfo out{};
-    if (aggregateCsr(d, opts ? opts->seed : 0u, S.aggK, dAgg, &out, S.stream)) { ERR("%s: the aggregation failed", who); return EXIT_FAILURE; }
-    if (info) *info = out;
-    return EXIT_SUCCESS;
-}
-
-int spmvHipAmgSetup(spmat* dA, const spmvAmgOpts* opts, spmat* dM, spmvAmgInfo* info) {
-    const char* who = "spmvHipAmgSetup";
-    if (!ready(who)) return EXIT_FAILURE;
-    if (!dA || !dM) { ERR("%s: %s is NULL", who, !dA ? "dA" : "dM"); return EXIT_FAILURE; }
-    if (dM == dA) { ERR("%s: dM is the source handle itself", who); return EXIT_FAILURE; }
-    DevMat* a = squareCsr(dA, who);
-    if (!a) return EXIT_FAILURE;
-    if (a->NZ && (!a->JA || !a->AS)) { ERR("%s: the source has no column or value array", who); return EXIT_FAILURE; }
-    if (opts && opts->maxLevels > SPMV_AMG_MAX_LEVELS) { ERR("%s: maxLevels %u is above %d", who, opts->maxLevels, SPMV_AMG_MAX_LEVELS); return EXIT_FAILURE; }
-    if (opts && !(opts->omega >= 0.0 && std::isfinite(opts->omega))) { ERR("%s: omega %g is negative or not finite", who, opts->omega); return EXIT_FAILURE; }
-    DevMat* m = new DevMat;
-    m->kind = Kind::CSR;
-    m->M = m->N = a->M;
-    m->srcId = a->id;
-    if (amgBuild(dA, a, opts, m, S.stream)) { ERR("%s: building the hierarchy failed", who); freeDesc(m); return EXIT_FAILURE; }
-    publish(dM, m, m->M, m->N, 0, 0);
-    if (info) *info = m->amg->info;
-    return EXIT_SUCCESS;
-}
-
-int spmvHipAmgRefresh(spmat* dM, spmat* dA) {
-    const char* who = "spmvHipAmgRefresh";
-    DevMat* a = nullptr;
-    DevMat* m = hierarchyOf(dM, dA, who, &a);
-    if (!m) return EXIT_FAILURE;
-    if (amgRefresh(m, dA, S.stream)) { ERR("%s: recomputing the hierarchy failed", who); return EXIT_FAILURE; }
-    return EXIT_SUCCESS;
-}
-
-int spmvHipAmgApply(spmat* dM, spmat* dA, const double* dR, double* dZ) {
-    const char* who = "spmvHipAmgApply";
-    const Ctx cx = libraryCtx();
-    DevMat* a = nullptr;
-    DevMat* m = hierarchyOf(dM, dA, who, &a);
-    if (!m) return EXIT_FAILURE;
-    if (!dR || !dZ) { ERR("%s: %s is NULL", who, !dR ? "dR" : "dZ"); return EXIT_FAILURE; }
-    if (a->M != m->M) { ERR("%s: dA has %lu rows, dM %lu", who, (unsigned long)a->M, (unsigned long)m->M); return EXIT_FAILURE; }
-    const uintptr_t r0 = (uintptr_t)dR, z0 = (uintptr_t)dZ, bytes = m->M * sizeof(double);
-    if (m->M && r0 < z0 + bytes && z0 < r0 + bytes) { ERR("%s: dR and dZ are the same vector or overlap", who); return EXIT_FAILURE; }
-    if (m->M == 0) return nothingToLaunch(cx, m, nullptr);
-    Launch L(cx, grid2d((m->M + KB - 1) / KB, KT), dim3(KT));
-    if (enqueueAmgCycle(m, dA, dR, dZ, cx.stream, nullptr, nullptr)) { ERR("%s: launch failed", who); return EXIT_FAILURE; }
-    return L.finish(who);
-}
-
-int spmvHipAmgInfo(spmat* dM, spmvAmgInfo* info) {
-    const char* who = "spmvHipAmgInfo";
-    DevMat* m = anyDescOf(dM, who);
-    if (!m) return EXIT_FAILURE;
-    if (!m->amg || !info) { ERR("%s: %s", who, !info ? "info is NULL" : "dM was not made by spmvHipAmgSetup"); return EXIT_FAILURE; }
-    *info = m->amg->info;
-    return EXIT_SUCCESS;
-}
-
-int spmvHipAmgLevel(spmat* dM, unsigned level, spmat* dAl, const uint32_t** dAgg, const double** dDinv) {
-    const char* who = "spmvHipAmgLevel";
-    DevMat* m = anyDescOf(dM, who);
-    if (!m) return EXIT_FAILURE;
-    if (!m->amg) { ERR("%s: dM was not made by spmvHipAmgSetup", who); return EXIT_FAILURE; }
-    if (level >= m->amg->lv.size()) { ERR("%s: level %u of %zu", who, level, m->amg->lv.size()); return EXIT_FAILURE; }
+void amgLevel(const DevMat* m, unsigned level, spmat* dAl, const uint32_t** dAgg, const double** dDinv) {
     const AmgLevel& L = m->amg->lv[level];
     if (dAl) {
         if (level) *dAl = L.A; else memset(dAl, 0, sizeof *dAl);
@@ -660,7 +553,6 @@ int spmvHipAmgLevel(spmat* dM, unsigned level, spmat* dAl, const uint32_t** dAgg
     }
     if (dAgg) *dAgg = L.agg;
     if (dDinv) *dDinv = L.dinv;
-    return EXIT_SUCCESS;
 }
 
-}  // extern "C"
+}  // namespace spmvhip

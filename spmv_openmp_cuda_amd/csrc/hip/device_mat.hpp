@@ -28,6 +28,11 @@ constexpr int      STREAM_NNZ      = 2048;              // nnz staged in LDS per
 constexpr uint64_t IRP32_LIMIT     = (1ull << 32) - 65536;
 
 enum class Kind : int { CSR = 0, ELL_ROWMAJOR = 1, ELL_COLMAJOR = 2 };
+// How a handle came to be (DevMat::origin; UPLOADED is also what ownCsr makes).  The last four are made from other handles,
+// whose ids -- never pointers: a source may be freed first -- DevMat::src records: TRANSPOSE, PERMUTATION, HIERARCHY the
+// source (the level-0 matrix) in src[0], PRODUCT A and B in that order.  What made a handle refreshes it, from those handles
+// only (madeBy in lib.hpp).  ELL_OF_CSR (spmvHipCsrToEll) keeps no link to its source, and its values cannot be updated.
+enum class Origin : int { UPLOADED, ADOPTED, ELL_OF_CSR, TRANSPOSE, PERMUTATION, PRODUCT, HIERARCHY };
 
 struct TileFormat;          // column-sliced two-phase format, tiles.hip
 struct SellFormat;          // SELL-C-sigma, sell.hip
@@ -66,7 +71,8 @@ struct DevMat {
     uint32_t* RL  = nullptr;
     size_t    pitch = 0;            // ELL pitch in elements (same for JA and AS)
     bool      owns = true;          // false for adopted arrays
-    bool      derived = false;      // ELL made on the device from a CSR handle (spmvHipCsrToEll): its values cannot be updated
+    Origin    origin = Origin::UPLOADED;
+    uint64_t  src[2] = {0, 0};      // ids of the handles this one was made from (0: none)
     uint64_t  ellFirstRow = ~0ull;  // ELL with row lengths: first row that holds an entry (unit detection after a value update)
     // every stored value is the same double (MatrixMarket `pattern` files are loaded as all 1.0 -- the graphs of the
     // reference's report, asia_osm and channel-500x100x100, are such files): found at upload; the CSR kernels then take
@@ -94,17 +100,13 @@ struct DevMat {
     int       autoPick[2] = {-1, -1};
     float     autoMs[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};    // ... and what each candidate took (0 = not tried)
     spmvUpdateInfo lastUpdate{};    // what the last spmvHipUpdateValues / spmvHipValuesChanged did
-    // a transpose built by spmvHipCsrTranspose (transpose.hip): the id of its source and, for every entry p of this
-    // handle, the CSR position of the same entry in the source (ASt[p] = AS[tmap[p]]); no pointer to the source is kept
-    uint64_t  srcId = 0;            // 0: neither a transpose nor a permutation
+    // a transpose (spmvHipCsrTranspose, transpose.hip) or a permutation (spmvHipCsrPermute, colour.hip): for every entry p
+    // of this handle, the CSR position of the same entry in the source (ASt[p] = AS[tmap[p]])
     uint32_t* tmap = nullptr;
-    // ... and so has a permutation built by spmvHipCsrPermute (colour.hip): the same id and map, refreshed by its own call
-    bool      permuted = false;
-    // a product built by spmvHipSpGEMM (spgemm.hip): the ids of its two sources and its rows by class (4 B per row); no
-    // pointer to a source is kept
+    // a product (spmvHipSpGEMM, spgemm.hip): its rows by class (4 B per row)
     SpgemmPlan* prod = nullptr;
-    // a multigrid hierarchy built by spmvHipAmgSetup (amg.hip): the handle is then no matrix (no arrays, NZ = 0) and only
-    // the spmvHipAmg* calls, a Krylov solve's dM and hipFreeSpmat take it; srcId is the id of its level-0 matrix
+    // a multigrid hierarchy (spmvHipAmgSetup, amg.hip): the handle is then no matrix (no arrays, NZ = 0) and only the
+    // spmvHipAmg* calls, a Krylov solve's dM and hipFreeSpmat take it
     AmgHierarchy* amg = nullptr;
     // the level-set schedules of the triangular solve (trsv.hip), [SPMV_TRI_LOWER] and [SPMV_TRI_UPPER]: built from the
     // pattern at the first solve or by spmvHipTriAnalyse, kept across value updates (the solve reads AS live)
@@ -195,19 +197,22 @@ int  enqueueVecPermute(uint64_t n, const uint32_t* perm, const double* in, doubl
 // holds.  spgemmRefresh: the numeric phase again into c's arrays.  Both synchronous, temporaries freed before they return.
 int  spgemmBuild(const DevMat* a, const DevMat* b, const spmvSpgemmOpts* opts, DevMat* c, spmvSpgemmInfo* info, hipStream_t stream);
 int  spgemmRefresh(DevMat* c, const DevMat* a, const DevMat* b, spmvSpgemmInfo* info, hipStream_t stream);
-bool spgemmSources(const DevMat* c, uint64_t* idA, uint64_t* idB);   // false: c is no product
 void freeSpgemmPlan(SpgemmPlan* p);
 // Aggregation multigrid (amg.hip; contracts in spmvHip.h, design in DESIGN.md section 24).  aggregateCsr: the aggregate ids
 // of the checked square handle into dAgg (M words), K rounds per host check; synchronous, allocates, temporaries freed
-// before it returns.  amgBuild: the hierarchy of hA / a into m->amg (on failure the caller frees m with whatever it holds);
-// amgRefresh: the products and the inverse diagonals again.  enqueueAmgCycle: z = V(0, r), kernels only on `stream`; every
-// kernel of the cycle but its SpMVs returns at once when `stop` is set and *stop != 0; *launches grows by the kernels
-// enqueued (an SpMV counted as one).  ownCsr (upload.hip): a CSR handle that takes ownership of three device arrays.
+// before it returns.  amgBuild: the hierarchy of the checked handle hA into m->amg, K aggregation rounds per host check (on
+// failure the caller frees m with whatever it holds); amgRefresh: the products and the inverse diagonals again.
+// enqueueAmgCycle: z = V(0, r), kernels only on `stream`; every kernel of the cycle but its SpMVs returns at once when `stop`
+// is set and *stop != 0; *launches grows by the kernels enqueued (an SpMV counted as one).  amgInfo: what the setup or the
+// last refresh did.  amgLevel: spmvHipAmgLevel's outputs for a level below amgInfo()->levels.  ownCsr (upload.hip): a CSR
+// handle that takes ownership of three device arrays.
 int  aggregateCsr(const DevMat* a, uint32_t seed, uint32_t K, uint32_t* dAgg, spmvAggInfo* info, hipStream_t stream);
-int  amgBuild(spmat* hA, const DevMat* a, const spmvAmgOpts* opts, DevMat* m, hipStream_t stream);
+int  amgBuild(spmat* hA, const spmvAmgOpts* opts, uint32_t K, DevMat* m, hipStream_t stream);
 int  amgRefresh(DevMat* m, spmat* hA, hipStream_t stream);
 int  enqueueAmgCycle(const DevMat* m, spmat* hA, const double* r, double* z, hipStream_t stream, const uint32_t* stop,
                      unsigned long* launches);
+const spmvAmgInfo* amgInfo(const DevMat* m);
+void amgLevel(const DevMat* m, unsigned level, spmat* dAl, const uint32_t** dAgg, const double** dDinv);
 void freeAmg(AmgHierarchy* h);
 int  ownCsr(spmat* dst, uint64_t M, uint64_t N, uint64_t NZ, uint32_t* dIRP, uint32_t* dJA, double* dAS);
 // Triangular solves (trsv.hip; contract in spmvHip.h, design in DESIGN.md section 17).  triAnalyse builds d->tri[uplo]

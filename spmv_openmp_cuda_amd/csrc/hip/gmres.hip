@@ -415,17 +415,9 @@ int gmresSolve(spmat* hA, const DevMat* a, const DevMat* m, const double* b, dou
     h.restart = m_;
     h.tol2 = o->tol * o->tol;
     HIP_TRY(hipMemcpyAsync(st, &h, GSTATE_HEAD, hipMemcpyHostToDevice, s));
-    spmvTriInfo tl{}, tu{};
-    if (pre && !m->amg) { triInfo(m, SPMV_TRI_LOWER, &tl); triInfo(m, SPMV_TRI_UPPER, &tu); }
     const uint32_t* flags = &st->stop;                                   // {stop, skip}
-    dim3 g, bl;
-    auto precond = [&](const double* in, double* outv, const uint32_t* flag) {
-        if (m->amg) return enqueueAmgCycle(m, hA, in, outv, s, flag, &out.launches);   // the cycle of a hierarchy
-        enqueueTrsv(m, SPMV_TRI_LOWER, SPMV_DIAG_UNIT, in, outv, s, &g, &bl, flag);
-        enqueueTrsv(m, SPMV_TRI_UPPER, SPMV_DIAG_STORED, outv, outv, s, &g, &bl, flag);
-        out.launches += tl.launches + tu.launches;
-        return EXIT_SUCCESS;
-    };
+    const Precond pc(m, hA, s);
+    auto precond = [&](const double* in, double* outv, const uint32_t* flag) { return pc.apply(in, outv, flag, &out.launches); };
     auto spmv = [&](const double* in, double* outv) {
         ++out.launches;
         return spmvHipEnqueueAutoRows(hA, const_cast<double*>(in), outv, s);

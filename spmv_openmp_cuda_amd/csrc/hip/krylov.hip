@@ -297,17 +297,8 @@ int krylovSolve(int bicg, spmat* hA, const DevMat* a, const DevMat* m, const dou
     h.maxIter = o->maxIter;
     h.tol2 = o->tol * o->tol;
     HIP_TRY(hipMemcpyAsync(st, &h, sizeof h, hipMemcpyHostToDevice, s));
-    spmvTriInfo tl{}, tu{};
-    if (pre && !m->amg) { triInfo(m, SPMV_TRI_LOWER, &tl); triInfo(m, SPMV_TRI_UPPER, &tu); }
-    const uint32_t* stop = &st->stop;
-    dim3 g, bl;
-    auto precond = [&](const double* in, double* outv) {                 // outv = U^-1 (L^-1 in): the ILU(0) pair of dM
-        if (m->amg) return enqueueAmgCycle(m, hA, in, outv, s, stop, &out.launches);   // ... or the cycle of a hierarchy
-        enqueueTrsv(m, SPMV_TRI_LOWER, SPMV_DIAG_UNIT, in, outv, s, &g, &bl, stop);
-        enqueueTrsv(m, SPMV_TRI_UPPER, SPMV_DIAG_STORED, outv, outv, s, &g, &bl, stop);
-        out.launches += tl.launches + tu.launches;
-        return EXIT_SUCCESS;
-    };
+    const Precond pc(m, hA, s);
+    auto precond = [&](const double* in, double* outv) { return pc.apply(in, outv, &st->stop, &out.launches); };
     auto spmv = [&](double* in, double* outv) {
         ++out.launches;
         return spmvHipEnqueueAutoRows(hA, in, outv, s);

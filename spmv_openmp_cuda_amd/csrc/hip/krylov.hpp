@@ -1,5 +1,6 @@
 // krylov.hpp -- what the Krylov files (krylov.hip, gmres.hip) share: the blocks and lanes of the fixed-order dot, the
-// element-pair loads and stores, the fixed tree, the fused-pass kernel and its launcher, the workspace holder.
+// element-pair loads and stores, the fixed tree, the fused-pass kernel and its launcher, the workspace holder, and the
+// preconditioner of a solve.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -129,6 +130,27 @@ struct DevBufs {
         if (hipMalloc(&p, std::max<size_t>(count * sizeof(T), 16)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
         ptrs.push_back(p);
         return static_cast<T*>(p);
+    }
+};
+
+// M^-1 of one solve, from its checked dM (null: none, and apply is not called): the ILU(0) pair U^-1 (L^-1 in) of an
+// analysed matrix handle, or the cycle of a hierarchy of hA.  apply enqueues kernels only on the solve's stream; every one
+// returns at once when *flag != 0; *launches grows by the kernels enqueued.
+struct Precond {
+    const DevMat* m; spmat* hA; hipStream_t s;
+    unsigned long triLaunches = 0;              // of the two triangular solves
+    Precond(const DevMat* m_, spmat* hA_, hipStream_t s_) : m(m_), hA(hA_), s(s_) {
+        spmvTriInfo t{};
+        if (m && m->origin != Origin::HIERARCHY)
+            for (int uplo : {SPMV_TRI_LOWER, SPMV_TRI_UPPER}) { triInfo(m, uplo, &t); triLaunches += t.launches; }
+    }
+    int apply(const double* in, double* out, const uint32_t* flag, unsigned long* launches) const {
+        if (m->origin == Origin::HIERARCHY) return enqueueAmgCycle(m, hA, in, out, s, flag, launches);
+        dim3 g, bl;
+        enqueueTrsv(m, SPMV_TRI_LOWER, SPMV_DIAG_UNIT, in, out, s, &g, &bl, flag);
+        enqueueTrsv(m, SPMV_TRI_UPPER, SPMV_DIAG_STORED, out, out, s, &g, &bl, flag);
+        *launches += triLaunches;
+        return EXIT_SUCCESS;
     }
 };
 

@@ -1,9 +1,7 @@
 // launch.hip -- the launchers of the extern "C" boundary: CSR (restatements, LDS-stream kernel, blocks of vectors), SELL, the
-// two-phase and the stripes format with their build entry points and queries, ELL, and the entry points of the solves.
+// two-phase and the stripes format with their build entry points and queries, and ELL.  (The solver side is solve.hip.)
 // Every launcher takes its stream and its synchronisation from a Ctx (lib.hpp); the public ones build it from the library state.
 #include <hip/hip_runtime.h>
-#include <chrono>
-#include <cstring>
 
 #include "lib.hpp"
 
@@ -419,231 +417,6 @@ int hipSpMVRowsELLNNTransposed(spmat* dMat, double* dX, CONFIG cfg, double* dY) 
     if (rl) hipLaunchKernelGGL((ell_rowmajor_thread<true>), grid, block, 0, cx.stream, (uint32_t)d->M, (uint32_t)d->K, d->pitch, d->JA, d->AS, d->RL, dX, dY);
     else    hipLaunchKernelGGL((ell_rowmajor_thread<false>), grid, block, 0, cx.stream, (uint32_t)d->M, (uint32_t)d->K, d->pitch, d->JA, d->AS, d->RL, dX, dY);
     return L.finish("hipSpMVRowsELLNNTransposed");
-}
-
-// ---- triangular solves (trsv.hip builds and launches; the contract is in spmvHip.h, the design in DESIGN.md section 17)
-// the checks every entry point shares
-static DevMat* triHandle(spmat* dA, int uplo, const char* who) {
-    if (!ready(who)) return nullptr;
-    DevMat* d = csrOf(dA, who, "the handle is an ELL handle (only CSR handles are solved)");
-    if (!d) return nullptr;
-    if (d->M != d->N) { ERR("%s: M=%lu != N=%lu: the matrix is not square", who, (unsigned long)d->M, (unsigned long)d->N); return nullptr; }
-    if (uplo != SPMV_TRI_LOWER && uplo != SPMV_TRI_UPPER) { ERR("%s: unknown uplo %d", who, uplo); return nullptr; }
-    if (d->NZ >= IRP32_LIMIT || d->M >= (1ull << 31)) {
-        ERR("%s: NZ=%lu, M=%lu: positions and rows of the schedule are 32-bit (limits %lu, 2^31)", who, (unsigned long)d->NZ,
-            (unsigned long)d->M, (unsigned long)IRP32_LIMIT);
-        return nullptr;
-    }
-    if (d->NZ && !d->JA) { ERR("%s: the handle has no column array", who); return nullptr; }
-    return d;
-}
-
-int spmvHipTriAnalyse(spmat* dA, int uplo) {
-    const char* who = "spmvHipTriAnalyse";
-    DevMat* d = triHandle(dA, uplo, who);
-    if (!d) return EXIT_FAILURE;
-    if (d->tri[uplo] || d->M == 0) return EXIT_SUCCESS;
-    if (triAnalyse(d, uplo, S.triRunRows, S.stream)) { ERR("%s: the analysis failed", who); return EXIT_FAILURE; }
-    return EXIT_SUCCESS;
-}
-
-int hipSpTRSVCSR(spmat* dA, int uplo, int diag, const double* dB, double* dX) {
-    const char* who = "hipSpTRSVCSR";
-    const Ctx cx = libraryCtx();
-    DevMat* d = triHandle(dA, uplo, who);
-    if (!d) return EXIT_FAILURE;
-    if (!dB || !dX) { ERR("%s: %s is NULL", who, !dB ? "dB" : "dX"); return EXIT_FAILURE; }
-    if (diag != SPMV_DIAG_STORED && diag != SPMV_DIAG_UNIT) { ERR("%s: unknown diag %d", who, diag); return EXIT_FAILURE; }
-    const uintptr_t b0 = (uintptr_t)dB, x0 = (uintptr_t)dX, bytes = d->M * sizeof(double);
-    if (b0 != x0 && b0 < x0 + bytes && x0 < b0 + bytes) { ERR("%s: dB and dX overlap without being equal", who); return EXIT_FAILURE; }
-    if (d->M == 0) return nothingToLaunch(cx, d, nullptr);
-    if (d->NZ && !d->AS && !d->unit) { ERR("%s: the handle has no value array", who); return EXIT_FAILURE; }
-    if (!d->tri[uplo] && triAnalyse(d, uplo, S.triRunRows, cx.stream)) { ERR("%s: the analysis failed", who); return EXIT_FAILURE; }
-    spmvTriInfo info;
-    triInfo(d, uplo, &info);
-    if (diag == SPMV_DIAG_STORED && info.firstBadDiag >= 0) {
-        ERR("%s: row %ld does not hold exactly one stored diagonal entry (SPMV_DIAG_STORED needs one in every row)", who,
-            info.firstBadDiag);
-        return EXIT_FAILURE;
-    }
-    Launch L(cx, dim3(1), dim3(1));
-    dim3 grid(1), block(1);
-    if (enqueueTrsv(d, uplo, diag, dB, dX, cx.stream, &grid, &block)) { ERR("%s: launch failed", who); return EXIT_FAILURE; }
-    L.shape(grid, block);
-    return L.finish(who);
-}
-
-int spmvHipTriInfo(spmat* dA, int uplo, spmvTriInfo* info) {
-    const char* who = "spmvHipTriInfo";
-    DevMat* d = descOf(dA, who);
-    if (!d) return EXIT_FAILURE;
-    if (!info) { ERR("%s: info is NULL", who); return EXIT_FAILURE; }
-    if (uplo != SPMV_TRI_LOWER && uplo != SPMV_TRI_UPPER) { ERR("%s: unknown uplo %d", who, uplo); return EXIT_FAILURE; }
-    triInfo(d, uplo, info);
-    return EXIT_SUCCESS;
-}
-
-// ---- ILU(0) (ilu0.hip factors; the contract is in spmvHip.h, the design in DESIGN.md section 18)
-int hipSpILU0CSR(spmat* dA) {
-    const char* who = "hipSpILU0CSR";
-    const auto t0 = std::chrono::steady_clock::now();
-    DevMat* d = triHandle(dA, SPMV_TRI_LOWER, who);
-    if (!d) return EXIT_FAILURE;
-    if (d->NZ && !d->AS) { ERR("%s: the handle has no value array", who); return EXIT_FAILURE; }
-    if (d->M) {
-        if (!d->iluChecked) {
-            long row = -1;
-            if (iluUnsortedRow(d, S.stream, &row)) { ERR("%s: the pattern check failed", who); return EXIT_FAILURE; }
-            d->iluUnsortedRow = row;
-            d->iluChecked = true;
-        }
-        if (!d->tri[SPMV_TRI_LOWER] && triAnalyse(d, SPMV_TRI_LOWER, S.triRunRows, S.stream)) {
-            ERR("%s: the analysis failed", who);
-            return EXIT_FAILURE;
-        }
-        const long unsorted = d->iluUnsortedRow, badDiag = d->tri[SPMV_TRI_LOWER]->info.firstBadDiag;
-        if (unsorted >= 0 || badDiag >= 0) {
-            const bool first = unsorted >= 0 && (badDiag < 0 || unsorted <= badDiag);
-            d->ilu.firstBadRow = first ? unsorted : badDiag;
-            if (first) ERR("%s: row %ld: its columns are not strictly ascending (unsorted, or a repeated column)", who, unsorted);
-            else       ERR("%s: row %ld does not hold exactly one stored diagonal entry", who, badDiag);
-            return EXIT_FAILURE;
-        }
-        d->ilu.firstBadRow = -1;
-        if (iluFactor(d, S.iluGroup, S.stream)) { ERR("%s: the factorisation failed", who); return EXIT_FAILURE; }
-        if (updateValues(dA, nullptr, true, true, S.stream, who)) return EXIT_FAILURE;
-    } else {
-        d->ilu.zeroPivot = d->ilu.firstBadRow = -1;
-        d->ilu.levels = d->ilu.launches = d->ilu.longRows = 0;
-    }
-    ++d->ilu.factorisations;
-    d->ilu.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return EXIT_SUCCESS;
-}
-
-int spmvHipIlu0Info(spmat* dA, spmvIluInfo* info) {
-    const char* who = "spmvHipIlu0Info";
-    DevMat* d = descOf(dA, who);
-    if (!d) return EXIT_FAILURE;
-    if (!info) { ERR("%s: info is NULL", who); return EXIT_FAILURE; }
-    *info = d->ilu;
-    return EXIT_SUCCESS;
-}
-
-// ---- multi-colour ordering and vector permutation (colour.hip; the contract is in spmvHip.h, the design in DESIGN.md section 21)
-int spmvHipColourCSR(spmat* dA, const spmvColourOpts* opts, uint32_t* dColour, uint32_t* dPerm, spmvColourInfo* info) {
-    const char* who = "spmvHipColourCSR";
-    DevMat* d = triHandle(dA, SPMV_TRI_LOWER, who);          // ready, live, CSR, square, 32-bit rows and positions
-    if (!d) return EXIT_FAILURE;
-    const int order = opts ? opts->order : SPMV_COLOUR_NATURAL;
-    if (order != SPMV_COLOUR_NATURAL && order != SPMV_COLOUR_HASH) { ERR("%s: unknown order %d", who, order); return EXIT_FAILURE; }
-    if (colourCsr(d, order, opts ? opts->seed : 0u, S.colourK, dColour, dPerm, info, S.stream)) { ERR("%s: the colouring failed", who); return EXIT_FAILURE; }
-    return EXIT_SUCCESS;
-}
-
-int spmvHipVecPermute(size_t n, const uint32_t* dPerm, const double* dIn, double* dOut, int inverse) {
-    const char* who = "spmvHipVecPermute";
-    const Ctx cx = libraryCtx();
-    if (!ready(who)) return EXIT_FAILURE;
-    if (n && (!dPerm || !dIn || !dOut)) { ERR("%s: %s is NULL", who, !dPerm ? "dPerm" : !dIn ? "dIn" : "dOut"); return EXIT_FAILURE; }
-    if (n >= (1ull << 32)) { ERR("%s: n=%zu does not fit the 32-bit ids of a permutation", who, n); return EXIT_FAILURE; }
-    const uintptr_t i0 = (uintptr_t)dIn, o0 = (uintptr_t)dOut, bytes = n * sizeof(double);
-    if (n && i0 < o0 + bytes && o0 < i0 + bytes) { ERR("%s: dIn and dOut are the same vector or overlap", who); return EXIT_FAILURE; }
-    Launch L(cx, grid2d((n + 255) / 256, 256), dim3(256));
-    if (enqueueVecPermute(n, dPerm, dIn, dOut, inverse != 0, cx.stream)) { ERR("%s: launch failed", who); return EXIT_FAILURE; }
-    return L.finish(who);
-}
-
-// ---- Krylov solves (krylov.hip runs them; the contract is in spmvHip.h, the design in DESIGN.md section 19)
-int spmvHipDot(size_t n, const double* dU, const double* dV, double* dResult) {
-    const char* who = "spmvHipDot";
-    const Ctx cx = libraryCtx();
-    if (!ready(who)) return EXIT_FAILURE;
-    if (!dResult || (n && (!dU || !dV))) { ERR("%s: %s is NULL", who, !dResult ? "dResult" : !dU ? "dU" : "dV"); return EXIT_FAILURE; }
-    Launch L(cx, dim3(1), dim3(256));
-    if (enqueueDot(n, dU, dV, dResult, cx.stream)) { ERR("%s: launch failed", who); return EXIT_FAILURE; }
-    return L.finish(who);
-}
-
-int spmvHipMultiDot(size_t n, unsigned k, const double* dV, size_t ldv, const double* dW, double* dH) {
-    const char* who = "spmvHipMultiDot";
-    const Ctx cx = libraryCtx();
-    if (!ready(who)) return EXIT_FAILURE;
-    if (!dH || (n && (!dV || !dW))) { ERR("%s: %s is NULL", who, !dH ? "dH" : !dV ? "dV" : "dW"); return EXIT_FAILURE; }
-    if (k == 0) { ERR("%s: k = 0 columns", who); return EXIT_FAILURE; }
-    if (ldv < n) { ERR("%s: ldv=%zu < n=%zu", who, ldv, n); return EXIT_FAILURE; }
-    Launch L(cx, dim3((k + 1) / 2), dim3(256));
-    if (enqueueMultiDot(n, k, dV, ldv, dW, dH, cx.stream)) { ERR("%s: launch failed", who); return EXIT_FAILURE; }
-    return L.finish(who);
-}
-
-// what the three solvers check alike: 0 go on (a, m set), 1 refused, 2 done (M = 0)
-static int krylovArgs(const char* who, spmat* dA, spmat* dM, const double* dB, double* dX, const void* optsPtr, double tol, ulong maxIter,
-                      double* history, spmvKrylovInfo* info, DevMat** pa, DevMat** pm) {
-    if (!ready(who)) return EXIT_FAILURE;
-    if (!dB || !dX || !optsPtr) { ERR("%s: %s is NULL", who, !dB ? "dB" : !dX ? "dX" : "opts"); return EXIT_FAILURE; }
-    DevMat* a = csrOf(dA, who, "dA is an ELL handle (only CSR handles are solved)");
-    if (!a) return EXIT_FAILURE;
-    if (a->M != a->N) { ERR("%s: M=%lu != N=%lu: dA is not square", who, (unsigned long)a->M, (unsigned long)a->N); return EXIT_FAILURE; }
-    if (a->NZ && !a->AS && !a->unit) { ERR("%s: dA has no value array", who); return EXIT_FAILURE; }
-    const uintptr_t b0 = (uintptr_t)dB, x0 = (uintptr_t)dX, bytes = a->M * sizeof(double);
-    if (a->M && b0 < x0 + bytes && x0 < b0 + bytes) { ERR("%s: dB and dX overlap", who); return EXIT_FAILURE; }
-    if (!(tol >= 0.0)) { ERR("%s: tol %g is negative or NaN", who, tol); return EXIT_FAILURE; }
-    if (history && maxIter >= (SIZE_MAX / sizeof(double)) - 1) {
-        ERR("%s: a history of maxIter + 1 = %lu + 1 doubles does not fit", who, (unsigned long)maxIter);
-        return EXIT_FAILURE;
-    }
-    DevMat* m = nullptr;
-    DevMat* hier = dM ? anyDescOf(dM, who) : nullptr;
-    if (dM && !hier) return EXIT_FAILURE;
-    if (hier && hier->amg) {                                 // a multigrid hierarchy: M^-1 v is its cycle
-        if (hier->srcId != a->id) { ERR("%s: dM is a multigrid hierarchy of another handle than dA", who); return EXIT_FAILURE; }
-        m = hier;
-    } else if (dM) {
-        if (!(m = triHandle(dM, SPMV_TRI_LOWER, who))) return EXIT_FAILURE;
-        if (m->M != a->M) { ERR("%s: dM has %lu rows, dA %lu", who, (unsigned long)m->M, (unsigned long)a->M); return EXIT_FAILURE; }
-        if (m->NZ && !m->AS && !m->unit) { ERR("%s: dM has no value array", who); return EXIT_FAILURE; }
-        for (int uplo : {SPMV_TRI_LOWER, SPMV_TRI_UPPER})
-            if (m->M && !m->tri[uplo] && triAnalyse(m, uplo, S.triRunRows, S.stream)) { ERR("%s: the analysis of dM failed", who); return EXIT_FAILURE; }
-        if (m->M && m->tri[SPMV_TRI_UPPER]->info.firstBadDiag >= 0) {
-            ERR("%s: row %ld of dM does not hold exactly one stored diagonal entry (M^-1 divides by it)", who,
-                m->tri[SPMV_TRI_UPPER]->info.firstBadDiag);
-            return EXIT_FAILURE;
-        }
-    }
-    if (a->M == 0) {
-        if (history) history[0] = 0.0;
-        if (info) *info = spmvKrylovInfo{SPMV_KRYLOV_CONVERGED, 0, 0.0, 0.0, 0, 0, 0.0};
-        return 2;
-    }
-    *pa = a;
-    *pm = m;
-    return 0;
-}
-
-static int krylov(int bicg, spmat* dA, spmat* dM, const double* dB, double* dX, const spmvKrylovOpts* opts, spmvKrylovInfo* info) {
-    const char* who = bicg ? "hipSpBiCGStabCSR" : "hipSpCGCSR";
-    DevMat* a = nullptr;
-    DevMat* m = nullptr;
-    const int rc = krylovArgs(who, dA, dM, dB, dX, opts, opts ? opts->tol : 0.0, opts ? opts->maxIter : 0, opts ? opts->history : nullptr, info, &a, &m);
-    if (rc) return rc == 2 ? EXIT_SUCCESS : EXIT_FAILURE;
-    if (krylovSolve(bicg, dA, a, m, dB, dX, opts, info, S.krylovK[bicg], S.stream)) { ERR("%s: the solve failed", who); return EXIT_FAILURE; }
-    return EXIT_SUCCESS;
-}
-int hipSpCGCSR(spmat* dA, spmat* dM, const double* dB, double* dX, const spmvKrylovOpts* opts, spmvKrylovInfo* info) { return krylov(0, dA, dM, dB, dX, opts, info); }
-int hipSpBiCGStabCSR(spmat* dA, spmat* dM, const double* dB, double* dX, const spmvKrylovOpts* opts, spmvKrylovInfo* info) { return krylov(1, dA, dM, dB, dX, opts, info); }
-int hipSpGMRESCSR(spmat* dA, spmat* dM, const double* dB, double* dX, const spmvGmresOpts* opts, spmvKrylovInfo* info) {
-    const char* who = "hipSpGMRESCSR";
-    if (opts && (opts->restart == 0 || opts->restart > 64)) {
-        if (ready(who)) ERR("%s: restart %u is not in 1 .. 64", who, opts->restart);
-        return EXIT_FAILURE;
-    }
-    DevMat* a = nullptr;
-    DevMat* m = nullptr;
-    const int rc = krylovArgs(who, dA, dM, dB, dX, opts, opts ? opts->tol : 0.0, opts ? opts->maxIter : 0, opts ? opts->history : nullptr, info, &a, &m);
-    if (rc) return rc == 2 ? EXIT_SUCCESS : EXIT_FAILURE;
-    if (gmresSolve(dA, a, m, dB, dX, opts, info, S.gmresFused, S.stream)) { ERR("%s: the solve failed", who); return EXIT_FAILURE; }
-    return EXIT_SUCCESS;
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
-// lib.hpp -- what the files behind the extern "C" boundary of libspmvhip.so (abi.hip, upload.hip, launch.hip, select.hip,
-// hostcall.hip; DESIGN.md has the table) share: the library state, the error line, the handle checks, the launch context
-// with its timing bracket, and the few functions one of those files calls in another.
+// lib.hpp -- what the files behind the extern "C" boundary of libspmvhip.so (abi.hip, upload.hip, launch.hip, solve.hip,
+// select.hip, hostcall.hip; DESIGN.md has the table) share: the library state, the error line, the handle checks (live,
+// matrix, CSR, square, made by whom from what), the launch context with its timing bracket, and the few functions one of
+// those files calls in another.
 #pragma once
 #include <algorithm>
 
@@ -62,7 +63,7 @@ inline DevMat* anyDescOf(spmat* h, const char* who) {
 // ... that is a matrix: what every SpMV, format, build and solve entry point takes
 inline DevMat* descOf(spmat* h, const char* who) {
     DevMat* d = anyDescOf(h, who);
-    if (d && d->amg) {
+    if (d && d->origin == Origin::HIERARCHY) {
         ERR("%s: the handle is a multigrid hierarchy (spmvHipAmgSetup), not a matrix: spmvHipAmgApply, spmvHipAmgRefresh, the dM of a "
             "Krylov solve and hipFreeSpmat take it", who);
         return nullptr;
@@ -85,6 +86,45 @@ inline DevMat* csrOnly(DevMat* d, const char* who, const char* what = "handle is
 inline DevMat* csrOf(spmat* h, const char* who, const char* what = "handle is not CSR") { return csrOnly(descOf(h, who), who, what); }
 inline DevMat* csrOf(spmat* h, const double* x, const double* y, const char* who, const char* what = "handle is not CSR") {
     return csrOnly(descOf(h, x, y, who), who, what);
+}
+// ... square, with rows and positions that fit 32-bit words, and a column array: what the triangular solves, ILU(0), the
+// colouring, the permutation, the aggregation and the multigrid setup take (`ell`: the entry point's wording for an ELL handle)
+inline DevMat* squareCsrOf(spmat* h, const char* who, const char* ell) {
+    if (!ready(who)) return nullptr;
+    DevMat* d = csrOf(h, who, ell);
+    if (!d) return nullptr;
+    if (d->M != d->N) { ERR("%s: M=%lu != N=%lu: the matrix is not square", who, (unsigned long)d->M, (unsigned long)d->N); return nullptr; }
+    if (d->NZ >= IRP32_LIMIT || d->M >= (1ull << 31)) {
+        ERR("%s: NZ=%lu, M=%lu: positions and rows are 32-bit (limits %lu, 2^31)", who, (unsigned long)d->NZ, (unsigned long)d->M,
+            (unsigned long)IRP32_LIMIT);
+        return nullptr;
+    }
+    if (d->NZ && !d->JA) { ERR("%s: the handle has no column array", who); return nullptr; }
+    return d;
+}
+
+// Provenance.  The makers record it with setOrigin; everything that takes a derived handle asks madeBy: was x (argument
+// xName) made as `want`, TRANSPOSE or later, from a (and, a product, from b, in that order)?  The refusal names the maker,
+// or the argument that is not the source.  a == null asks for the origin alone.
+inline void setOrigin(DevMat* d, Origin o, const DevMat* a = nullptr, const DevMat* b = nullptr) {
+    d->origin = o; d->src[0] = a ? a->id : 0; d->src[1] = b ? b->id : 0;
+}
+inline bool madeBy(const DevMat* x, Origin want, const DevMat* a, const DevMat* b, const char* who, const char* xName,
+                   const char* aName = nullptr, const char* bName = nullptr) {
+    static const struct { const char* maker; const char* made; } texts[] = {     // TRANSPOSE .. HIERARCHY
+        {"spmvHipCsrTranspose", "transposed"}, {"spmvHipCsrPermute", "permuted"}, {"spmvHipSpGEMM", ""}, {"spmvHipAmgSetup", "set up"}};
+    const auto& text = texts[(int)want - (int)Origin::TRANSPOSE];
+    if (x->origin != want) { ERR("%s: %s was not made by %s", who, xName, text.maker); return false; }
+    if (!a || (a->id == x->src[0] && (!b || b->id == x->src[1]))) return true;
+    if (b) ERR("%s: (%s, %s) is not the pair, in its order, that %s is the product of", who, aName, bName, xName);
+    else ERR("%s: %s is not the handle %s was %s from", who, aName, xName, text.made);
+    return false;
+}
+
+// two vectors of `bytes` bytes each share memory (the same vector included)
+inline bool overlaps(const void* p, const void* q, uint64_t bytes) {
+    const uintptr_t p0 = (uintptr_t)p, q0 = (uintptr_t)q;
+    return bytes && p0 < q0 + bytes && q0 < p0 + bytes;
 }
 
 // timing bracket used by every launcher

@@ -1,0 +1,314 @@
+// solve.hip -- the solver side of the extern "C" boundary: triangular solves, ILU(0), the multi-colour ordering and the
+// vector permutation, the dots, aggregation multigrid, and the three Krylov solvers.  The algorithm files (trsv.hip,
+// ilu0.hip, colour.hip, krylov.hip, gmres.hip, amg.hip) build and launch; here are the checks, the library's settings
+// handed down as arguments, and the timing bracket.  Contracts in spmvHip.h, designs in DESIGN.md sections 17 to 21 and 24.
+#include <hip/hip_runtime.h>
+#include <chrono>
+#include <cmath>
+
+#include "lib.hpp"
+#include "krylov.hpp"
+
+using namespace spmvhip;
+
+// a square CSR handle and a triangle of it
+static DevMat* triHandle(spmat* dA, int uplo, const char* who) {
+    DevMat* d = squareCsrOf(dA, who, "the handle is an ELL handle (only CSR handles are solved)");
+    if (d && uplo != SPMV_TRI_LOWER && uplo != SPMV_TRI_UPPER) { ERR("%s: unknown uplo %d", who, uplo); return nullptr; }
+    return d;
+}
+
+// dM as a hierarchy of dA (*pa)
+static DevMat* hierarchyOf(spmat* dM, spmat* dA, const char* who, DevMat** pa) {
+    if (!ready(who)) return nullptr;
+    if (!dM || !dA) { ERR("%s: %s is NULL", who, !dM ? "dM" : "dA"); return nullptr; }
+    DevMat* m = anyDescOf(dM, who);
+    DevMat* a = m ? csrOf(dA, who, "dA is an ELL handle") : nullptr;
+    if (!a || !madeBy(m, Origin::HIERARCHY, a, nullptr, who, "dM", "dA")) return nullptr;
+    *pa = a;
+    return m;
+}
+
+extern "C" {
+
+// ---- triangular solves
+int spmvHipTriAnalyse(spmat* dA, int uplo) {
+    const char* who = "spmvHipTriAnalyse";
+    DevMat* d = triHandle(dA, uplo, who);
+    if (!d) return EXIT_FAILURE;
+    if (d->tri[uplo] || d->M == 0) return EXIT_SUCCESS;
+    if (triAnalyse(d, uplo, S.triRunRows, S.stream)) { ERR("%s: the analysis failed", who); return EXIT_FAILURE; }
+    return EXIT_SUCCESS;
+}
+
+int hipSpTRSVCSR(spmat* dA, int uplo, int diag, const double* dB, double* dX) {
+    const char* who = "hipSpTRSVCSR";
+    const Ctx cx = libraryCtx();
+    DevMat* d = triHandle(dA, uplo, who);
+    if (!d) return EXIT_FAILURE;
+    if (!dB || !dX) { ERR("%s: %s is NULL", who, !dB ? "dB" : "dX"); return EXIT_FAILURE; }
+    if (diag != SPMV_DIAG_STORED && diag != SPMV_DIAG_UNIT) { ERR("%s: unknown diag %d", who, diag); return EXIT_FAILURE; }
+    if (dB != dX && overlaps(dB, dX, d->M * sizeof(double))) { ERR("%s: dB and dX overlap without being equal", who); return EXIT_FAILURE; }
+    if (d->M == 0) return nothingToLaunch(cx, d, nullptr);
+    if (d->NZ && !d->AS && !d->unit) { ERR("%s: the handle has no value array", who); return EXIT_FAILURE; }
+    if (!d->tri[uplo] && triAnalyse(d, uplo, S.triRunRows, cx.stream)) { ERR("%s: the analysis failed", who); return EXIT_FAILURE; }
+    spmvTriInfo info;
+    triInfo(d, uplo, &info);
+    if (diag == SPMV_DIAG_STORED && info.firstBadDiag >= 0) {
+        ERR("%s: row %ld does not hold exactly one stored diagonal entry (SPMV_DIAG_STORED needs one in every row)", who,
+            info.firstBadDiag);
+        return EXIT_FAILURE;
+    }
+    Launch L(cx, dim3(1), dim3(1));
+    dim3 grid(1), block(1);
+    if (enqueueTrsv(d, uplo, diag, dB, dX, cx.stream, &grid, &block)) { ERR("%s: launch failed", who); return EXIT_FAILURE; }
+    L.shape(grid, block);
+    return L.finish(who);
+}
+
+int spmvHipTriInfo(spmat* dA, int uplo, spmvTriInfo* info) {
+    const char* who = "spmvHipTriInfo";
+    DevMat* d = descOf(dA, who);
+    if (!d) return EXIT_FAILURE;
+    if (!info) { ERR("%s: info is NULL", who); return EXIT_FAILURE; }
+    if (uplo != SPMV_TRI_LOWER && uplo != SPMV_TRI_UPPER) { ERR("%s: unknown uplo %d", who, uplo); return EXIT_FAILURE; }
+    triInfo(d, uplo, info);
+    return EXIT_SUCCESS;
+}
+
+// ---- ILU(0)
+int hipSpILU0CSR(spmat* dA) {
+    const char* who = "hipSpILU0CSR";
+    const auto t0 = std::chrono::steady_clock::now();
+    DevMat* d = triHandle(dA, SPMV_TRI_LOWER, who);
+    if (!d) return EXIT_FAILURE;
+    if (d->NZ && !d->AS) { ERR("%s: the handle has no value array", who); return EXIT_FAILURE; }
+    if (d->M) {
+        if (!d->iluChecked) {
+            long row = -1;
+            if (iluUnsortedRow(d, S.stream, &row)) { ERR("%s: the pattern check failed", who); return EXIT_FAILURE; }
+            d->iluUnsortedRow = row;
+            d->iluChecked = true;
+        }
+        if (!d->tri[SPMV_TRI_LOWER] && triAnalyse(d, SPMV_TRI_LOWER, S.triRunRows, S.stream)) {
+            ERR("%s: the analysis failed", who);
+            return EXIT_FAILURE;
+        }
+        const long unsorted = d->iluUnsortedRow, badDiag = d->tri[SPMV_TRI_LOWER]->info.firstBadDiag;
+        if (unsorted >= 0 || badDiag >= 0) {
+            const bool first = unsorted >= 0 && (badDiag < 0 || unsorted <= badDiag);
+            d->ilu.firstBadRow = first ? unsorted : badDiag;
+            if (first) ERR("%s: row %ld: its columns are not strictly ascending (unsorted, or a repeated column)", who, unsorted);
+            else       ERR("%s: row %ld does not hold exactly one stored diagonal entry", who, badDiag);
+            return EXIT_FAILURE;
+        }
+        d->ilu.firstBadRow = -1;
+        if (iluFactor(d, S.iluGroup, S.stream)) { ERR("%s: the factorisation failed", who); return EXIT_FAILURE; }
+        if (updateValues(dA, nullptr, true, true, S.stream, who)) return EXIT_FAILURE;
+    } else {
+        d->ilu.zeroPivot = d->ilu.firstBadRow = -1;
+        d->ilu.levels = d->ilu.launches = d->ilu.longRows = 0;
+    }
+    ++d->ilu.factorisations;
+    d->ilu.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return EXIT_SUCCESS;
+}
+
+int spmvHipIlu0Info(spmat* dA, spmvIluInfo* info) {
+    const char* who = "spmvHipIlu0Info";
+    DevMat* d = descOf(dA, who);
+    if (!d) return EXIT_FAILURE;
+    if (!info) { ERR("%s: info is NULL", who); return EXIT_FAILURE; }
+    *info = d->ilu;
+    return EXIT_SUCCESS;
+}
+
+// ---- multi-colour ordering and vector permutation
+int spmvHipColourCSR(spmat* dA, const spmvColourOpts* opts, uint32_t* dColour, uint32_t* dPerm, spmvColourInfo* info) {
+    const char* who = "spmvHipColourCSR";
+    DevMat* d = squareCsrOf(dA, who, "the handle is an ELL handle (only CSR handles are coloured)");
+    if (!d) return EXIT_FAILURE;
+    const int order = opts ? opts->order : SPMV_COLOUR_NATURAL;
+    if (order != SPMV_COLOUR_NATURAL && order != SPMV_COLOUR_HASH) { ERR("%s: unknown order %d", who, order); return EXIT_FAILURE; }
+    if (colourCsr(d, order, opts ? opts->seed : 0u, S.colourK, dColour, dPerm, info, S.stream)) { ERR("%s: the colouring failed", who); return EXIT_FAILURE; }
+    return EXIT_SUCCESS;
+}
+
+int spmvHipVecPermute(size_t n, const uint32_t* dPerm, const double* dIn, double* dOut, int inverse) {
+    const char* who = "spmvHipVecPermute";
+    const Ctx cx = libraryCtx();
+    if (!ready(who)) return EXIT_FAILURE;
+    if (n && (!dPerm || !dIn || !dOut)) { ERR("%s: %s is NULL", who, !dPerm ? "dPerm" : !dIn ? "dIn" : "dOut"); return EXIT_FAILURE; }
+    if (n >= (1ull << 32)) { ERR("%s: n=%zu does not fit the 32-bit ids of a permutation", who, n); return EXIT_FAILURE; }
+    if (overlaps(dIn, dOut, n * sizeof(double))) { ERR("%s: dIn and dOut are the same vector or overlap", who); return EXIT_FAILURE; }
+    Launch L(cx, grid2d((n + 255) / 256, 256), dim3(256));
+    if (enqueueVecPermute(n, dPerm, dIn, dOut, inverse != 0, cx.stream)) { ERR("%s: launch failed", who); return EXIT_FAILURE; }
+    return L.finish(who);
+}
+
+// ---- the dots
+int spmvHipDot(size_t n, const double* dU, const double* dV, double* dResult) {
+    const char* who = "spmvHipDot";
+    const Ctx cx = libraryCtx();
+    if (!ready(who)) return EXIT_FAILURE;
+    if (!dResult || (n && (!dU || !dV))) { ERR("%s: %s is NULL", who, !dResult ? "dResult" : !dU ? "dU" : "dV"); return EXIT_FAILURE; }
+    Launch L(cx, dim3(1), dim3(256));
+    if (enqueueDot(n, dU, dV, dResult, cx.stream)) { ERR("%s: launch failed", who); return EXIT_FAILURE; }
+    return L.finish(who);
+}
+
+int spmvHipMultiDot(size_t n, unsigned k, const double* dV, size_t ldv, const double* dW, double* dH) {
+    const char* who = "spmvHipMultiDot";
+    const Ctx cx = libraryCtx();
+    if (!ready(who)) return EXIT_FAILURE;
+    if (!dH || (n && (!dV || !dW))) { ERR("%s: %s is NULL", who, !dH ? "dH" : !dV ? "dV" : "dW"); return EXIT_FAILURE; }
+    if (k == 0) { ERR("%s: k = 0 columns", who); return EXIT_FAILURE; }
+    if (ldv < n) { ERR("%s: ldv=%zu < n=%zu", who, ldv, n); return EXIT_FAILURE; }
+    Launch L(cx, dim3((k + 1) / 2), dim3(256));
+    if (enqueueMultiDot(n, k, dV, ldv, dW, dH, cx.stream)) { ERR("%s: launch failed", who); return EXIT_FAILURE; }
+    return L.finish(who);
+}
+
+// ---- aggregation multigrid
+int spmvHipAggregateCSR(spmat* dA, const spmvAggOpts* opts, uint32_t* dAgg, spmvAggInfo* info) {
+    const char* who = "spmvHipAggregateCSR";
+    DevMat* d = squareCsrOf(dA, who, "the handle is an ELL handle (only CSR handles are aggregated)");
+    if (!d) return EXIT_FAILURE;
+    if (d->M && !dAgg) { ERR("%s: dAgg is NULL", who); return EXIT_FAILURE; }
+    spmvAggInfo out{};
+    if (aggregateCsr(d, opts ? opts->seed : 0u, S.aggK, dAgg, &out, S.stream)) { ERR("%s: the aggregation failed", who); return EXIT_FAILURE; }
+    if (info) *info = out;
+    return EXIT_SUCCESS;
+}
+
+int spmvHipAmgSetup(spmat* dA, const spmvAmgOpts* opts, spmat* dM, spmvAmgInfo* info) {
+    const char* who = "spmvHipAmgSetup";
+    if (!ready(who)) return EXIT_FAILURE;
+    if (!dA || !dM) { ERR("%s: %s is NULL", who, !dA ? "dA" : "dM"); return EXIT_FAILURE; }
+    if (dM == dA) { ERR("%s: dM is the source handle itself", who); return EXIT_FAILURE; }
+    DevMat* a = squareCsrOf(dA, who, "the handle is an ELL handle (only CSR handles are aggregated)");
+    if (!a) return EXIT_FAILURE;
+    if (a->NZ && (!a->JA || !a->AS)) { ERR("%s: the source has no column or value array", who); return EXIT_FAILURE; }
+    if (opts && opts->maxLevels > SPMV_AMG_MAX_LEVELS) { ERR("%s: maxLevels %u is above %d", who, opts->maxLevels, SPMV_AMG_MAX_LEVELS); return EXIT_FAILURE; }
+    if (opts && !(opts->omega >= 0.0 && std::isfinite(opts->omega))) { ERR("%s: omega %g is negative or not finite", who, opts->omega); return EXIT_FAILURE; }
+    DevMat* m = new DevMat;
+    m->M = m->N = a->M;
+    setOrigin(m, Origin::HIERARCHY, a);
+    if (amgBuild(dA, opts, S.aggK, m, S.stream)) { ERR("%s: building the hierarchy failed", who); freeDesc(m); return EXIT_FAILURE; }
+    publish(dM, m, m->M, m->N, 0, 0);
+    if (info) *info = *amgInfo(m);
+    return EXIT_SUCCESS;
+}
+
+int spmvHipAmgRefresh(spmat* dM, spmat* dA) {
+    const char* who = "spmvHipAmgRefresh";
+    DevMat* a = nullptr;
+    DevMat* m = hierarchyOf(dM, dA, who, &a);
+    if (!m) return EXIT_FAILURE;
+    if (amgRefresh(m, dA, S.stream)) { ERR("%s: recomputing the hierarchy failed", who); return EXIT_FAILURE; }
+    return EXIT_SUCCESS;
+}
+
+int spmvHipAmgApply(spmat* dM, spmat* dA, const double* dR, double* dZ) {
+    const char* who = "spmvHipAmgApply";
+    const Ctx cx = libraryCtx();
+    DevMat* a = nullptr;
+    DevMat* m = hierarchyOf(dM, dA, who, &a);
+    if (!m) return EXIT_FAILURE;
+    if (!dR || !dZ) { ERR("%s: %s is NULL", who, !dR ? "dR" : "dZ"); return EXIT_FAILURE; }
+    if (a->M != m->M) { ERR("%s: dA has %lu rows, dM %lu", who, (unsigned long)a->M, (unsigned long)m->M); return EXIT_FAILURE; }
+    if (overlaps(dR, dZ, m->M * sizeof(double))) { ERR("%s: dR and dZ are the same vector or overlap", who); return EXIT_FAILURE; }
+    if (m->M == 0) return nothingToLaunch(cx, m, nullptr);
+    Launch L(cx, grid2d((m->M + KB - 1) / KB, KT), dim3(KT));
+    if (enqueueAmgCycle(m, dA, dR, dZ, cx.stream, nullptr, nullptr)) { ERR("%s: launch failed", who); return EXIT_FAILURE; }
+    return L.finish(who);
+}
+
+int spmvHipAmgInfo(spmat* dM, spmvAmgInfo* info) {
+    const char* who = "spmvHipAmgInfo";
+    DevMat* m = anyDescOf(dM, who);
+    if (!m) return EXIT_FAILURE;
+    if (!info) { ERR("%s: info is NULL", who); return EXIT_FAILURE; }
+    if (!madeBy(m, Origin::HIERARCHY, nullptr, nullptr, who, "dM")) return EXIT_FAILURE;
+    *info = *amgInfo(m);
+    return EXIT_SUCCESS;
+}
+
+int spmvHipAmgLevel(spmat* dM, unsigned level, spmat* dAl, const uint32_t** dAgg, const double** dDinv) {
+    const char* who = "spmvHipAmgLevel";
+    DevMat* m = anyDescOf(dM, who);
+    if (!m) return EXIT_FAILURE;
+    if (!madeBy(m, Origin::HIERARCHY, nullptr, nullptr, who, "dM")) return EXIT_FAILURE;
+    if (level >= amgInfo(m)->levels) { ERR("%s: level %u of %zu", who, level, (size_t)amgInfo(m)->levels); return EXIT_FAILURE; }
+    amgLevel(m, level, dAl, dAgg, dDinv);
+    return EXIT_SUCCESS;
+}
+
+// ---- Krylov solves
+// what the three solvers check alike: 0 go on (a, m set), 1 refused, 2 done (M = 0)
+static int krylovArgs(const char* who, spmat* dA, spmat* dM, const double* dB, double* dX, const void* optsPtr, double tol, ulong maxIter,
+                      double* history, spmvKrylovInfo* info, DevMat** pa, DevMat** pm) {
+    if (!ready(who)) return EXIT_FAILURE;
+    if (!dB || !dX || !optsPtr) { ERR("%s: %s is NULL", who, !dB ? "dB" : !dX ? "dX" : "opts"); return EXIT_FAILURE; }
+    DevMat* a = csrOf(dA, who, "dA is an ELL handle (only CSR handles are solved)");
+    if (!a) return EXIT_FAILURE;
+    if (a->M != a->N) { ERR("%s: M=%lu != N=%lu: dA is not square", who, (unsigned long)a->M, (unsigned long)a->N); return EXIT_FAILURE; }
+    if (a->NZ && !a->AS && !a->unit) { ERR("%s: dA has no value array", who); return EXIT_FAILURE; }
+    if (overlaps(dB, dX, a->M * sizeof(double))) { ERR("%s: dB and dX overlap", who); return EXIT_FAILURE; }
+    if (!(tol >= 0.0)) { ERR("%s: tol %g is negative or NaN", who, tol); return EXIT_FAILURE; }
+    if (history && maxIter >= (SIZE_MAX / sizeof(double)) - 1) {
+        ERR("%s: a history of maxIter + 1 = %lu + 1 doubles does not fit", who, (unsigned long)maxIter);
+        return EXIT_FAILURE;
+    }
+    DevMat* m = dM ? anyDescOf(dM, who) : nullptr;
+    if (dM && !m) return EXIT_FAILURE;
+    if (m && m->origin == Origin::HIERARCHY) {               // a multigrid hierarchy: M^-1 v is its cycle
+        if (!madeBy(m, Origin::HIERARCHY, a, nullptr, who, "dM", "dA")) return EXIT_FAILURE;
+    } else if (dM) {
+        if (!(m = triHandle(dM, SPMV_TRI_LOWER, who))) return EXIT_FAILURE;
+        if (m->M != a->M) { ERR("%s: dM has %lu rows, dA %lu", who, (unsigned long)m->M, (unsigned long)a->M); return EXIT_FAILURE; }
+        if (m->NZ && !m->AS && !m->unit) { ERR("%s: dM has no value array", who); return EXIT_FAILURE; }
+        for (int uplo : {SPMV_TRI_LOWER, SPMV_TRI_UPPER})
+            if (m->M && !m->tri[uplo] && triAnalyse(m, uplo, S.triRunRows, S.stream)) { ERR("%s: the analysis of dM failed", who); return EXIT_FAILURE; }
+        if (m->M && m->tri[SPMV_TRI_UPPER]->info.firstBadDiag >= 0) {
+            ERR("%s: row %ld of dM does not hold exactly one stored diagonal entry (M^-1 divides by it)", who,
+                m->tri[SPMV_TRI_UPPER]->info.firstBadDiag);
+            return EXIT_FAILURE;
+        }
+    }
+    if (a->M == 0) {
+        if (history) history[0] = 0.0;
+        if (info) *info = spmvKrylovInfo{SPMV_KRYLOV_CONVERGED, 0, 0.0, 0.0, 0, 0, 0.0};
+        return 2;
+    }
+    *pa = a;
+    *pm = m;
+    return 0;
+}
+
+static int krylov(int bicg, spmat* dA, spmat* dM, const double* dB, double* dX, const spmvKrylovOpts* opts, spmvKrylovInfo* info) {
+    const char* who = bicg ? "hipSpBiCGStabCSR" : "hipSpCGCSR";
+    DevMat* a = nullptr;
+    DevMat* m = nullptr;
+    const int rc = krylovArgs(who, dA, dM, dB, dX, opts, opts ? opts->tol : 0.0, opts ? opts->maxIter : 0, opts ? opts->history : nullptr, info, &a, &m);
+    if (rc) return rc == 2 ? EXIT_SUCCESS : EXIT_FAILURE;
+    if (krylovSolve(bicg, dA, a, m, dB, dX, opts, info, S.krylovK[bicg], S.stream)) { ERR("%s: the solve failed", who); return EXIT_FAILURE; }
+    return EXIT_SUCCESS;
+}
+int hipSpCGCSR(spmat* dA, spmat* dM, const double* dB, double* dX, const spmvKrylovOpts* opts, spmvKrylovInfo* info) { return krylov(0, dA, dM, dB, dX, opts, info); }
+int hipSpBiCGStabCSR(spmat* dA, spmat* dM, const double* dB, double* dX, const spmvKrylovOpts* opts, spmvKrylovInfo* info) { return krylov(1, dA, dM, dB, dX, opts, info); }
+int hipSpGMRESCSR(spmat* dA, spmat* dM, const double* dB, double* dX, const spmvGmresOpts* opts, spmvKrylovInfo* info) {
+    const char* who = "hipSpGMRESCSR";
+    if (opts && (opts->restart == 0 || opts->restart > 64)) {
+        if (ready(who)) ERR("%s: restart %u is not in 1 .. 64", who, opts->restart);
+        return EXIT_FAILURE;
+    }
+    DevMat* a = nullptr;
+    DevMat* m = nullptr;
+    const int rc = krylovArgs(who, dA, dM, dB, dX, opts, opts ? opts->tol : 0.0, opts ? opts->maxIter : 0, opts ? opts->history : nullptr, info, &a, &m);
+    if (rc) return rc == 2 ? EXIT_SUCCESS : EXIT_FAILURE;
+    if (gmresSolve(dA, a, m, dB, dX, opts, info, S.gmresFused, S.stream)) { ERR("%s: the solve failed", who); return EXIT_FAILURE; }
+    return EXIT_SUCCESS;
+}
+
+}  // extern "C"

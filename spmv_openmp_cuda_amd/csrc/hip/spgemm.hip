@@ -30,9 +30,8 @@
 
 namespace spmvhip {
 
-// what a product handle keeps (DevMat::prod): the ids of its sources, and the rows by class -- wave, group, sorted
+// what a product handle keeps (DevMat::prod): the rows by class -- wave, group, sorted
 struct SpgemmPlan {
-    uint64_t idA = 0, idB = 0;
     uint32_t* list = nullptr;                                  // nWave + nGroup + nSorted rows (4 B per row at most)
     uint32_t nWave = 0, nGroup = 0, nSorted = 0;
     uint64_t batchProducts = 0;                                // products of one batch of the sorted path
@@ -502,12 +501,6 @@ void freeSpgemmPlan(SpgemmPlan* p) {
     delete p;
 }
 
-bool spgemmSources(const DevMat* c, uint64_t* idA, uint64_t* idB) {
-    if (!c->prod) return false;
-    *idA = c->prod->idA; *idB = c->prod->idB;
-    return true;
-}
-
 // c: kind, M and N set by the caller, nothing allocated.  On success c owns IRP (4 B), JA, AS and the plan, and c->NZ is
 // set; on failure the caller frees c with whatever it holds.  nnz(C) >= IRP32_LIMIT and a column of A >= B.M are found
 // before JA / AS exist.
@@ -515,7 +508,6 @@ int spgemmBuild(const DevMat* a, const DevMat* b, const spmvSpgemmOpts* opts, De
     const auto t0 = std::chrono::steady_clock::now();
     const uint64_t M = a->M, BN = b->N;
     SpgemmPlan* pl = c->prod = new SpgemmPlan;
-    pl->idA = a->id; pl->idB = b->id;
     const uint64_t waveMax = clampOpt(opts ? opts->waveMaxProducts : 0, SG_WAVE_MAX, SG_WAVE_MAX);
     const uint64_t groupMax = clampOpt(opts ? opts->groupMaxProducts : 0, SG_GROUP_MAX, SG_GROUP_MAX);
     pl->batchProducts = std::max<uint64_t>(clampOpt(opts ? opts->sortBudgetBytes : 0, SG_BUDGET, SG_BUDGET_MAX) / SG_PRODUCT_BYTES, 1);

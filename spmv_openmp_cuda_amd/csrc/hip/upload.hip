@@ -1,5 +1,6 @@
-// upload.hip -- device handles: upload, adoption of device arrays, CSR -> ELL, transpose handles, free, and what looks at
-// the values of a handle (unit-value detection, the value refresh).
+// upload.hip -- device handles: upload, adoption of device arrays, and the handles made from other handles (CSR -> ELL,
+// transpose, permutation, product) with their refreshes; free; and what looks at the values of a handle (unit-value
+// detection, the value refresh).
 #include <hip/hip_runtime.h>
 #include <chrono>
 #include <cstring>
@@ -228,7 +229,7 @@ int updateValues(spmat* h, const double* AS, bool onDevice, bool reread, hipStre
     DevMat* d = descOf(h, who);
     if (!d) return EXIT_FAILURE;
     if (!reread && !AS) { ERR("%s: AS is NULL", who); return EXIT_FAILURE; }
-    if (d->derived) {
+    if (d->origin == Origin::ELL_OF_CSR) {
         ERR("%s: this ELL handle was made on the device from a CSR handle (spmvHipCsrToEll) and keeps no link to it: "
             "update the CSR handle and convert again", who);
         return EXIT_FAILURE;
@@ -281,21 +282,49 @@ int updateValues(spmat* h, const double* AS, bool onDevice, bool reread, hipStre
     return EXIT_SUCCESS;
 }
 
+// The tail of every CSR handle whose arrays (4-byte row pointers) were made on the device: the row pointers come back to
+// the host for the row blocks, then the unit detection; the descriptor is published into dst, or -- when that fails, or
+// what came before it did (built = false) -- freed with all it holds.
+static int finishCsr(spmat* dst, DevMat* d, bool built = true) {
+    std::vector<uint32_t> hIRP(d->M + 1);
+    const bool ok = built && hipOk(hipMemcpy(hIRP.data(), d->IRP, hIRP.size() * 4, hipMemcpyDeviceToHost), "hipMemcpy IRP") &&
+                    !buildRowBlocks2(d, hIRP.data(), d->M) && !detectUnit(d, S.stream);
+    if (!ok) { freeDesc(d); return EXIT_FAILURE; }
+    publish(dst, d, d->M, d->N, d->NZ, 0);
+    return EXIT_SUCCESS;
+}
+
 // a CSR handle over three device arrays the library itself has made (4-byte row pointers): the handle owns them from the
 // call on -- on failure they are freed with the descriptor
 int ownCsr(spmat* dst, uint64_t M, uint64_t N, uint64_t NZ, uint32_t* dIRP, uint32_t* dJA, double* dAS) {
     DevMat* d = new DevMat;
-    d->kind = Kind::CSR;
-    d->M = M; d->N = N; d->NZ = NZ; d->irpBytes = 4;
+    d->M = M; d->N = N; d->NZ = NZ;
     d->IRP = dIRP; d->JA = dJA; d->AS = dAS;
-    std::vector<uint32_t> hIRP(M + 1);
-    const bool ok = hipOk(hipMemcpy(hIRP.data(), dIRP, hIRP.size() * 4, hipMemcpyDeviceToHost), "hipMemcpy IRP") &&
-                    !buildRowBlocks2(d, hIRP.data(), M) && !detectUnit(d, S.stream);
-    if (!ok) { freeDesc(d); return EXIT_FAILURE; }
-    publish(dst, d, M, N, NZ, 0);
-    return EXIT_SUCCESS;
+    return finishCsr(dst, d);
 }
 }  // namespace spmvhip
+
+// a CSR descriptor with a map, made as `o` from a, for M rows and a's entries: what transposeCsr / permuteCsr fill
+static DevMat* newMappedCsr(Origin o, const DevMat* a, uint64_t M, uint64_t N, bool* ok) {
+    DevMat* t = new DevMat;
+    t->M = M; t->N = N; t->NZ = a->NZ;
+    setOrigin(t, o, a);
+    const size_t nz1 = std::max<size_t>(a->NZ, 1);
+    *ok = hipOk(hipMalloc(&t->IRP, (M + 1) * 4), "hipMalloc IRP") && hipOk(hipMalloc(&t->JA, nz1 * 4), "hipMalloc JA") &&
+          hipOk(hipMalloc(&t->AS, nz1 * 8), "hipMalloc AS") && hipOk(hipMalloc(&t->tmap, nz1 * 4), "hipMalloc map");
+    return t;
+}
+
+// dX (made as `o` from dA) takes dA's current values through its map, then refreshes its formats: the two refreshes
+static int mappedRefresh(const char* who, Origin o, spmat* dX, const char* xName, spmat* dA) {
+    if (!ready(who)) return EXIT_FAILURE;
+    DevMat* t = descOf(dX, who);
+    if (!t) return EXIT_FAILURE;
+    DevMat* a = descOf(dA, who);
+    if (!a || !madeBy(t, o, a, nullptr, who, xName, "dA")) return EXIT_FAILURE;
+    if (enqueueGatherValues(t->AS, t->tmap, t->NZ, a->AS, S.stream)) return EXIT_FAILURE;
+    return updateValues(dX, nullptr, true, true, S.stream, who);
+}
 
 extern "C" {
 
@@ -356,7 +385,7 @@ int spmvHipCsrToEll(spmat* dCsr, int transposed, spmat* dEll) {
     const uint64_t K = c->maxRowNnz, rows = c->M;
     DevMat* d = new DevMat;
     d->kind = transposed ? Kind::ELL_COLMAJOR : Kind::ELL_ROWMAJOR;
-    d->derived = true;
+    setOrigin(d, Origin::ELL_OF_CSR);
     d->M = rows; d->N = c->N; d->NZ = c->NZ; d->K = K;
     d->pitch = transposed ? (rows + 63) / 64 * 64 : (K + 1) / 2 * 2;
     const size_t cells = std::max<size_t>((transposed ? K : rows) * d->pitch, 1);
@@ -414,34 +443,13 @@ int spmvHipCsrTranspose(spmat* dA, spmat* dAT) {
     }
     if (a->N >= (1ull << 32) - 1) { ERR("%s: N=%lu columns do not fit the row ids of the transpose", who, (unsigned long)a->N); return EXIT_FAILURE; }
     if (a->NZ && (!a->JA || !a->AS)) { ERR("%s: the source has no column or value array", who); return EXIT_FAILURE; }
-    DevMat* t = new DevMat;
-    t->kind = Kind::CSR;
-    t->M = a->N; t->N = a->M; t->NZ = a->NZ; t->irpBytes = 4;
-    t->srcId = a->id;
-    const size_t nz1 = std::max<size_t>(a->NZ, 1);
-    std::vector<uint32_t> hIRP(t->M + 1);
-    const bool ok = hipOk(hipMalloc(&t->IRP, (t->M + 1) * 4), "hipMalloc IRP") && hipOk(hipMalloc(&t->JA, nz1 * 4), "hipMalloc JA") &&
-                    hipOk(hipMalloc(&t->AS, nz1 * 8), "hipMalloc AS") && hipOk(hipMalloc(&t->tmap, nz1 * 4), "hipMalloc map") &&
-                    !transposeCsr(a, t, S.stream) &&
-                    hipOk(hipMemcpy(hIRP.data(), t->IRP, hIRP.size() * 4, hipMemcpyDeviceToHost), "hipMemcpy IRP") &&
-                    !buildRowBlocks2(t, hIRP.data(), t->M) && !detectUnit(t, S.stream);
-    if (!ok) { ERR("%s: building the transpose failed", who); freeDesc(t); return EXIT_FAILURE; }
-    publish(dAT, t, t->M, t->N, t->NZ, 0);
+    bool ok = false;
+    DevMat* t = newMappedCsr(Origin::TRANSPOSE, a, a->N, a->M, &ok);
+    if (finishCsr(dAT, t, ok && !transposeCsr(a, t, S.stream))) { ERR("%s: building the transpose failed", who); return EXIT_FAILURE; }
     return EXIT_SUCCESS;
 }
 
-int spmvHipTransposeRefresh(spmat* dAT, spmat* dA) {
-    const char* who = "spmvHipTransposeRefresh";
-    if (!ready(who)) return EXIT_FAILURE;
-    DevMat* t = descOf(dAT, who);
-    if (!t) return EXIT_FAILURE;
-    DevMat* a = descOf(dA, who);
-    if (!a) return EXIT_FAILURE;
-    if (!t->srcId || t->permuted) { ERR("%s: dAT was not made by spmvHipCsrTranspose", who); return EXIT_FAILURE; }
-    if (a->id != t->srcId) { ERR("%s: dA is not the handle dAT was transposed from", who); return EXIT_FAILURE; }
-    if (enqueueGatherValues(t->AS, t->tmap, t->NZ, a->AS, S.stream)) return EXIT_FAILURE;
-    return updateValues(dAT, nullptr, true, true, S.stream, who);
-}
+int spmvHipTransposeRefresh(spmat* dAT, spmat* dA) { return mappedRefresh("spmvHipTransposeRefresh", Origin::TRANSPOSE, dAT, "dAT", dA); }
 
 // B = P A P^T as a handle of its own (colour.hip builds the arrays; the contract is in spmvHip.h, the design in DESIGN.md
 // section 21).  As the transpose: refusals come before anything is allocated for dB, and dB is written only on success.
@@ -449,17 +457,10 @@ int spmvHipCsrPermute(spmat* dA, const uint32_t* dPerm, spmat* dB) {
     const char* who = "spmvHipCsrPermute";
     if (!ready(who)) return EXIT_FAILURE;
     if (!dB || !dPerm) { ERR("%s: %s is NULL", who, !dB ? "dB" : "dPerm"); return EXIT_FAILURE; }
-    DevMat* a = descOf(dA, who);
-    if (!a) return EXIT_FAILURE;
     if (dB == dA) { ERR("%s: dB is the source handle itself", who); return EXIT_FAILURE; }
-    if (!csrOnly(a, who, "the source is an ELL handle (only CSR handles can be permuted)")) return EXIT_FAILURE;
-    if (a->M != a->N) { ERR("%s: M=%lu != N=%lu: the matrix is not square", who, (unsigned long)a->M, (unsigned long)a->N); return EXIT_FAILURE; }
-    if (a->NZ >= IRP32_LIMIT || a->M >= (1ull << 31)) {
-        ERR("%s: NZ=%lu, M=%lu: the map, the positions and the sort keys are 32-bit (limits %lu, 2^31)", who, (unsigned long)a->NZ,
-            (unsigned long)a->M, (unsigned long)IRP32_LIMIT);
-        return EXIT_FAILURE;
-    }
-    if (a->NZ && (!a->JA || !a->AS)) { ERR("%s: the source has no column or value array", who); return EXIT_FAILURE; }
+    DevMat* a = squareCsrOf(dA, who, "the source is an ELL handle (only CSR handles can be permuted)");
+    if (!a) return EXIT_FAILURE;
+    if (a->NZ && !a->AS) { ERR("%s: the source has no column or value array", who); return EXIT_FAILURE; }
     uint32_t* inv = nullptr;
     uint32_t bad = 0;
     HIP_TRY(hipMalloc(&inv, std::max<size_t>(a->M, 1) * 4));
@@ -469,36 +470,15 @@ int spmvHipCsrPermute(spmat* dA, const uint32_t* dPerm, spmat* dB) {
         ERR("%s: dPerm is not a permutation of 0..M-1 (%s)", who, bad & 1 ? "a value >= M" : "a repeated value");
         return EXIT_FAILURE;
     }
-    DevMat* t = new DevMat;
-    t->kind = Kind::CSR;
-    t->M = t->N = a->M; t->NZ = a->NZ; t->irpBytes = 4;
-    t->srcId = a->id;
-    t->permuted = true;
-    const size_t nz1 = std::max<size_t>(a->NZ, 1);
-    std::vector<uint32_t> hIRP(t->M + 1);
-    const bool ok = hipOk(hipMalloc(&t->IRP, (t->M + 1) * 4), "hipMalloc IRP") && hipOk(hipMalloc(&t->JA, nz1 * 4), "hipMalloc JA") &&
-                    hipOk(hipMalloc(&t->AS, nz1 * 8), "hipMalloc AS") && hipOk(hipMalloc(&t->tmap, nz1 * 4), "hipMalloc map") &&
-                    !permuteCsr(a, inv, t, S.stream) &&
-                    hipOk(hipMemcpy(hIRP.data(), t->IRP, hIRP.size() * 4, hipMemcpyDeviceToHost), "hipMemcpy IRP") &&
-                    !buildRowBlocks2(t, hIRP.data(), t->M) && !detectUnit(t, S.stream);
+    bool ok = false;
+    DevMat* t = newMappedCsr(Origin::PERMUTATION, a, a->M, a->M, &ok);
+    const int rc = finishCsr(dB, t, ok && !permuteCsr(a, inv, t, S.stream));
     (void)hipFree(inv);
-    if (!ok) { ERR("%s: building the permuted matrix failed", who); freeDesc(t); return EXIT_FAILURE; }
-    publish(dB, t, t->M, t->N, t->NZ, 0);
-    return EXIT_SUCCESS;
+    if (rc) ERR("%s: building the permuted matrix failed", who);
+    return rc;
 }
 
-int spmvHipPermuteRefresh(spmat* dB, spmat* dA) {
-    const char* who = "spmvHipPermuteRefresh";
-    if (!ready(who)) return EXIT_FAILURE;
-    DevMat* t = descOf(dB, who);
-    if (!t) return EXIT_FAILURE;
-    DevMat* a = descOf(dA, who);
-    if (!a) return EXIT_FAILURE;
-    if (!t->srcId || !t->permuted) { ERR("%s: dB was not made by spmvHipCsrPermute", who); return EXIT_FAILURE; }
-    if (a->id != t->srcId) { ERR("%s: dA is not the handle dB was permuted from", who); return EXIT_FAILURE; }
-    if (enqueueGatherValues(t->AS, t->tmap, t->NZ, a->AS, S.stream)) return EXIT_FAILURE;
-    return updateValues(dB, nullptr, true, true, S.stream, who);
-}
+int spmvHipPermuteRefresh(spmat* dB, spmat* dA) { return mappedRefresh("spmvHipPermuteRefresh", Origin::PERMUTATION, dB, "dB", dA); }
 
 // C = A B as a handle of its own (spgemm.hip builds the arrays; the contract is in spmvHip.h, the design in DESIGN.md
 // section 22).  Refusals come first; dC and info are written only on success.
@@ -520,15 +500,10 @@ int spmvHipSpGEMM(spmat* dA, spmat* dB, const spmvSpgemmOpts* opts, spmat* dC, s
     }
     if ((a->NZ && (!a->JA || !a->AS)) || (b->NZ && (!b->JA || !b->AS))) { ERR("%s: a source has no column or value array", who); return EXIT_FAILURE; }
     DevMat* c = new DevMat;
-    c->kind = Kind::CSR;
     c->M = a->M; c->N = b->N;
+    setOrigin(c, Origin::PRODUCT, a, b);
     spmvSpgemmInfo out{};
-    std::vector<uint32_t> hIRP(c->M + 1);
-    const bool ok = !spgemmBuild(a, b, opts, c, &out, S.stream) &&
-                    hipOk(hipMemcpy(hIRP.data(), c->IRP, hIRP.size() * 4, hipMemcpyDeviceToHost), "hipMemcpy IRP") &&
-                    !buildRowBlocks2(c, hIRP.data(), c->M) && !detectUnit(c, S.stream);
-    if (!ok) { ERR("%s: building the product failed", who); freeDesc(c); return EXIT_FAILURE; }
-    publish(dC, c, c->M, c->N, c->NZ, 0);
+    if (finishCsr(dC, c, !spgemmBuild(a, b, opts, c, &out, S.stream))) { ERR("%s: building the product failed", who); return EXIT_FAILURE; }
     if (info) *info = out;
     return EXIT_SUCCESS;
 }
@@ -540,10 +515,7 @@ int spmvHipSpGEMMRefresh(spmat* dC, spmat* dA, spmat* dB, spmvSpgemmInfo* info) 
     DevMat* c = descOf(dC, who);
     DevMat* a = c ? descOf(dA, who) : nullptr;
     DevMat* b = a ? descOf(dB, who) : nullptr;
-    if (!c || !a || !b) return EXIT_FAILURE;
-    uint64_t idA = 0, idB = 0;
-    if (!spgemmSources(c, &idA, &idB)) { ERR("%s: dC was not made by spmvHipSpGEMM", who); return EXIT_FAILURE; }
-    if (a->id != idA || b->id != idB) { ERR("%s: (dA, dB) is not the pair, in its order, that dC is the product of", who); return EXIT_FAILURE; }
+    if (!c || !a || !b || !madeBy(c, Origin::PRODUCT, a, b, who, "dC", "dA", "dB")) return EXIT_FAILURE;
     spmvSpgemmInfo out{};
     if (spgemmRefresh(c, a, b, &out, S.stream)) { ERR("%s: recomputing the values failed", who); return EXIT_FAILURE; }
     if (updateValues(dC, nullptr, true, true, S.stream, who)) return EXIT_FAILURE;
