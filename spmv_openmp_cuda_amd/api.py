@@ -7,6 +7,7 @@ Everything numeric happens in libspmvhip.so; numpy is only used to marshal host
 arrays.  The library is REQUIRED: there is no fallback implementation.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -298,7 +299,178 @@ def _check(rc, what):
 
 
 def _ptr(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None else None
+    """the address of a numpy array for a C call (None stays NULL); the caller keeps the array alive across the call"""
+    return C.c_void_p(a.ctypes.data) if a is not None else None
+
+
+_torch_module = None                                 # torch, once _torch() has found it
+
+
+def _torch():
+    """torch, imported at its first use (numpy arrays and raw pointers need none); None where it is not installed"""
+    global _torch_module
+    if _torch_module is None:
+        try:
+            import torch
+            _torch_module = torch
+        except ImportError:
+            pass
+    return _torch_module
+
+
+def _device_vector(who, name, t, n=None, int32=False):
+    """The one rule for a 1-D operand of a device call: a float64 (a permutation: int32) torch tensor on the device with
+    dim() == 1 and unit stride -- any element offset, so a `[1:]` view passes and a `[::2]` view does not -- and of
+    length n where n is given.  (With dim() == 1, is_contiguous() is that stride rule: it does not look at the offset,
+    and a stride only counts where there is more than one element.)  Returns the length."""
+    torch = _torch()
+    if torch is None or not isinstance(t, torch.Tensor) or t.dtype != (torch.int32 if int32 else torch.float64) or not t.is_cuda \
+            or t.dim() != 1 or not t.is_contiguous():
+        kind = "a DeviceBuffer of uint32 or a 1-D int32" if int32 else "a 1-D float64"
+        raise SpmvHipError(f"{who}: {name} must be {kind} torch tensor on the device with unit stride")
+    length = t.numel()
+    if n is not None and length != n:
+        raise SpmvHipError(f"{who}: {name} must have length {n}, not {length}")
+    return length
+
+
+class _Operands:
+    """The operands of one call into the library, for every entry point that takes numpy arrays or device tensors.
+
+    The first operand decides the kind of the call: a numpy array makes it a host call (inputs are uploaded into one
+    temporary DeviceBuffer that also holds the result, which is downloaded as numpy), anything else a device call (torch tensors are read and written
+    where they live, the result is a tensor).  Every other operand must be of the same kind.  Use:
+
+        with _Operands("who", first) as ops:
+            ops.vector(...)                  # the inputs in the order of the C arguments: each is CHECKED, nothing more
+            ops.result(...)                  # the result ends the declarations: checked, then a host call makes its buffer
+            _check(lib.X(..., *ops.args), "X")       # ops.args: the device addresses, in the order of declaration
+            return ops.value()               # `out` or the new tensor; a host call downloads its numpy result
+
+    so a refused call has made no device call at all, and the temporaries are freed on success and on every failure.
+    With no operand (colour, permute, aggregate) it is only the scope that frees what temp() made."""
+    __slots__ = ("who", "host", "first", "args", "tmp", "res")       # res: the result tensor, or a host call's result shape
+
+    def __init__(self, who, first=None, host_calls=True):
+        self.who, self.first, self.host, self.args, self.tmp, self.res = who, first, isinstance(first, np.ndarray), [], [], None
+        if self.host and not host_calls:
+            raise SpmvHipError(f"{who}: the operands must be torch tensors on the device")
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, kind, error, trace):
+        for b in self.tmp:
+            b.free()
+
+    def temp(self, nbytes, host=None):
+        """a DeviceBuffer that lives until the call is over, filled from the host array when one is given"""
+        buf = DeviceBuffer(nbytes)
+        self.tmp.append(buf)
+        return buf if host is None else buf.up(host)
+
+    def keep(self):
+        """the buffers made so far are the call's result: they outlive it"""
+        self.tmp = []
+
+    def _host(self, name, a, shape):
+        if not isinstance(a, np.ndarray) or a.shape != shape:
+            raise SpmvHipError(f"{self.who}: {name} must be a numpy array of shape {shape}, as this is a host call")
+        return np.ascontiguousarray(a, dtype=np.float64)
+
+    def vector(self, name, v, n=None, least=0):
+        """an input vector of length n (any length: None); returns the length"""
+        if not self.host:
+            n = _device_vector(self.who, name, v, n)
+            self.args.append(v.data_ptr())
+            return n
+        h = self._host(name, v, (n,))
+        self.args.append((h, least))
+        return h.size
+
+    def dense(self, name, X, rows):
+        """matmul's X, (rows, k) with k >= 1: (k, layout, leading dimension)"""
+        if self.host:
+            ok = X.ndim == 2
+        else:
+            torch = _torch()
+            if torch is None or not isinstance(X, torch.Tensor):
+                raise SpmvHipError(f"{self.who}: {name} must be a numpy array or a torch tensor")
+            ok = X.dim() == 2
+        if not ok or X.shape[0] != rows or X.shape[1] < 1:
+            raise SpmvHipError(f"{self.who}: {name} must be ({rows}, k) with k >= 1, not {tuple(X.shape)}")
+        k = X.shape[1]
+        if self.host:
+            h = np.ascontiguousarray(X, dtype=np.float64)
+            self.args.append((h, 0))
+            return k, SPMV_DENSE_ROW_MAJOR, k
+        layout, ld = _dense_layout(X, name)
+        self.args.append(X.data_ptr())
+        return k, layout, ld
+
+    def columns(self, name, V):
+        """multi_dot's V, (n, k) with contiguous columns: (n, k, leading dimension)"""
+        if self.host:
+            if V.ndim != 2 or V.shape[1] < 1:
+                raise SpmvHipError(f"{self.who}: {name} must be (n, k) with k >= 1, not {V.shape}")
+            self.args.append((np.asfortranarray(V, dtype=np.float64).ravel(order="F"), 8))
+            return V.shape[0], V.shape[1], V.shape[0]
+        torch = _torch()
+        if torch is None or not isinstance(V, torch.Tensor) or V.dtype != torch.float64 or not V.is_cuda or V.dim() != 2:
+            raise SpmvHipError(f"{self.who}: {name} must be a 2-D float64 torch tensor on the device")
+        n, k = V.shape
+        if (n > 1 and V.stride(0) != 1) or (k > 1 and V.stride(1) < n):
+            raise SpmvHipError(f"{self.who}: {name} needs contiguous columns (strides {V.stride()})")
+        self.args.append(V.data_ptr())
+        return n, k, V.stride(1) if k > 1 else max(n, 1)
+
+    def result(self, name, out, shape, init=None, least=0):
+        """The result; it ends the declarations.  Host call: `out` is refused; every operand is checked by now, so the
+        call's buffer is made here and the inputs are uploaded.  Device call: `out` under the rule of its rank, else a new tensor.
+        init=(name, x0): the result starts as a copy of that operand, zeros when x0 is None, and x0 itself is never
+        written; init=None: it starts uninitialised.  Returns (layout, leading dimension) of a 2-D result."""
+        if self.host:
+            if out is not None:
+                raise SpmvHipError(f"{self.who}: `{name}` is for device calls; a host call returns a new numpy array")
+            start = None
+            if init is not None:
+                start = np.zeros(shape) if init[1] is None else self._host(init[0], init[1], shape)
+            arrays, offsets, total = [h for h, _ in self.args] + [start], [], 0
+            for n in [max(h.nbytes, atleast) for h, atleast in self.args] + [max(8 * math.prod(shape), least)]:
+                offsets.append(total)                    # one allocation for the call, every operand on a 256-byte boundary
+                total += (max(n, 1) + 255) // 256 * 256
+            base = self.temp(total).ptr.value
+            self.args = [base + o for o in offsets]
+            for h, address in zip(arrays, self.args):
+                if h is not None and h.nbytes:
+                    _check(lib.spmvHipMemcpyUp(address, _ptr(h), h.nbytes), "spmvHipMemcpyUp")
+            self.res = shape
+            return (SPMV_DENSE_ROW_MAJOR, shape[1]) if len(shape) == 2 else None
+        if out is not None:
+            if len(shape) == 1:
+                _device_vector(self.who, name, out, shape[0])
+            elif not isinstance(out, _torch().Tensor) or out.dim() != 2 or tuple(out.shape) != shape:
+                raise SpmvHipError(f"{self.who}: {name} must be a torch tensor of shape {shape}")
+        elif init is None:                               # (the first operand is a float64 tensor on the device by now)
+            out = self.first.new_empty(shape)
+        elif init[1] is None:
+            out = self.first.new_zeros(shape)
+        else:
+            _device_vector(self.who, init[0], init[1], shape[0])
+            out = init[1].clone()
+        self.res = out
+        self.args.append(out.data_ptr())
+        return _dense_layout(out, name) if len(shape) == 2 else None
+
+    def value(self):
+        """after the C call: the result tensor, or the host call's result downloaded (nothing is copied for an empty one)"""
+        assert self.res is not None, "result() was not declared"
+        if not self.host:
+            return self.res
+        out = np.empty(self.res)
+        if out.size:
+            _check(lib.spmvHipMemcpyDown(_ptr(out), self.args[-1], out.nbytes), "spmvHipMemcpyDown")
+        return out
 
 
 # ----------------------------------------------------------------- lifecycle
@@ -390,7 +562,25 @@ class HostELL:
 
 
 # ----------------------------------------------------------------- device objects
-class DeviceVector:
+class _DeviceMemory:
+    """what DeviceVector and DeviceBuffer share: `ptr` goes back to the allocator once, by free() or with the object"""
+    _release = None
+
+    def free(self):
+        if self.ptr:
+            self._release(self.ptr)
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class DeviceVector(_DeviceMemory):
+    _release = staticmethod(lib.spmvHipVecFree)
+
     def __init__(self, n):
         self.n = int(n)
         p = C.c_void_p()
@@ -411,20 +601,10 @@ class DeviceVector:
     def poison(self):
         _check(lib.spmvHipVecFill(self.ptr, self.n, POISON_NAN), "spmvHipVecFill")
 
-    def free(self):
-        if self.ptr:
-            lib.spmvHipVecFree(self.ptr)
-            self.ptr = None
 
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-class DeviceBuffer:
+class DeviceBuffer(_DeviceMemory):
     """Raw device bytes (for device-format matrices built on the GPU)."""
+    _release = staticmethod(lib.spmvHipFree)
 
     def __init__(self, nbytes):
         self.nbytes = int(nbytes)
@@ -443,17 +623,6 @@ class DeviceBuffer:
         _check(lib.spmvHipMemcpyDown(_ptr(out), self.ptr, self.nbytes), "spmvHipMemcpyDown")
         return out
 
-    def free(self):
-        if self.ptr:
-            lib.spmvHipFree(self.ptr)
-            self.ptr = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
 
 class DeviceMatrix:
     """A device handle (`spmat` whose `dev` is set) plus what keeps it alive."""
@@ -467,10 +636,7 @@ class DeviceMatrix:
         """spmvHipUpdateValues: new values for the same pattern, in the handle's value layout (CSR: NZ values in CSR order;
         uploaded ELL: the host ELL value array of the upload).  AS: a numpy array (host), a float64 torch tensor (read
         where it lives) or a raw device pointer (int / c_void_p, with on_device=True)."""
-        try:
-            import torch
-        except ImportError:                              # (numpy arrays and raw pointers need no torch)
-            torch = None
+        torch = _torch()                                 # (None without torch: numpy arrays and raw pointers need none)
         keep = None
         if torch is not None and isinstance(AS, torch.Tensor):
             if AS.dtype != torch.float64 or not AS.is_contiguous():
@@ -516,21 +682,17 @@ class DeviceMatrix:
             raise SpmvHipError(f"colour: order must be one of {sorted(COLOUR_ORDERS)}, not {order!r}")
         M = int(self.handle.M)
         opts, info = spmvColourOpts(COLOUR_ORDERS[order], int(seed) & 0xFFFFFFFF), spmvColourInfo()
-        if as_torch:
-            import torch
-            perm = torch.empty(M, dtype=torch.int32, device="cuda")
-            colours = torch.empty(M, dtype=torch.int32, device="cuda") if want_colours else None
-        else:
-            perm = DeviceBuffer(4 * M)
-            colours = DeviceBuffer(4 * M) if want_colours else None
-        try:
+        with _Operands("colour") as ops:                 # no operand: the scope that frees the buffers if the call fails
+            if as_torch:
+                torch = _torch()
+                perm = torch.empty(M, dtype=torch.int32, device="cuda")
+                colours = torch.empty(M, dtype=torch.int32, device="cuda") if want_colours else None
+            else:
+                perm = ops.temp(4 * M)
+                colours = ops.temp(4 * M) if want_colours else None
             _check(lib.spmvHipColourCSR(C.byref(self.handle), C.byref(opts), _dev_ptr(colours), _dev_ptr(perm), C.byref(info)),
                    "spmvHipColourCSR")
-        except SpmvHipError:
-            for b in (perm, colours):
-                if isinstance(b, DeviceBuffer):
-                    b.free()
-            raise
+            ops.keep()                                   # the Colouring owns the buffers from here
         return Colouring(perm, colours, info)
 
     def permute(self, perm) -> "DeviceMatrix":
@@ -539,19 +701,15 @@ class DeviceMatrix:
         M uint32, an int32 device torch tensor, or a numpy array (uploaded for the call)."""
         M = int(self.handle.M)
         perm = perm.perm if isinstance(perm, Colouring) else perm
-        tmp = None
-        if isinstance(perm, np.ndarray):
-            if perm.shape != (M,):
-                raise SpmvHipError(f"permute: perm must have shape ({M},), not {perm.shape}")
-            perm = tmp = DeviceBuffer(4 * M).up(np.ascontiguousarray(perm, dtype=np.uint32))
-        elif _perm_len(perm, "permute") != M:
-            raise SpmvHipError(f"permute: perm must hold {M} entries")
         b = DeviceMatrix()
-        try:
+        with _Operands("permute") as ops:                # no operand: the scope that frees an uploaded perm
+            if isinstance(perm, np.ndarray):
+                if perm.shape != (M,):
+                    raise SpmvHipError(f"permute: perm must have shape ({M},), not {perm.shape}")
+                perm = ops.temp(4 * M, np.ascontiguousarray(perm, dtype=np.uint32))
+            elif _perm_len(perm, "permute") != M:
+                raise SpmvHipError(f"permute: perm must hold {M} entries")
             _check(lib.spmvHipCsrPermute(C.byref(self.handle), _dev_ptr(perm), C.byref(b.handle)), "spmvHipCsrPermute")
-        finally:
-            if tmp is not None:
-                tmp.free()
         b.rows = int(b.handle.M)
         return b
 
@@ -592,13 +750,10 @@ class DeviceMatrix:
         seed alone (include/spmvHip.h states the loop).  Returns (ids, info): a numpy uint32 array and a spmvAggInfo."""
         M = int(self.handle.M)
         opts, info = spmvAggOpts(int(seed) & 0xFFFFFFFF), spmvAggInfo()
-        buf = DeviceBuffer(4 * M)
-        try:
+        with _Operands("aggregate") as ops:              # no operand: the scope that frees the id buffer
+            buf = ops.temp(4 * M)
             _check(lib.spmvHipAggregateCSR(C.byref(self.handle), C.byref(opts), buf.ptr, C.byref(info)), "spmvHipAggregateCSR")
-            ids = buf.down(np.uint32) if M else np.zeros(0, np.uint32)
-        finally:
-            buf.free()
-        return ids, info
+            return (buf.down(np.uint32) if M else np.zeros(0, np.uint32)), info
 
     def amg(self, seed=0, coarseRows=None, maxLevels=None, omega=None, nu1=None, nu2=None, nuCoarse=None) -> "AmgHierarchy":
         """spmvHipAmgSetup: an aggregation multigrid hierarchy of this square matrix (include/spmvHip.h states the loops).
@@ -619,35 +774,12 @@ class DeviceMatrix:
         contiguous (k, N) tensor column-major; the leading dimension is the other stride) -> a torch tensor, `out` if
         given (same rules); or a numpy array -> uploaded, multiplied, returned as numpy.  Runs on the library stream."""
         M, N = int(self.handle.M), int(self.handle.N)
-        if isinstance(X, np.ndarray):
-            if out is not None:
-                raise SpmvHipError("matmul: `out` is for torch tensors")
-            if X.ndim != 2 or X.shape[0] != N or X.shape[1] < 1:
-                raise SpmvHipError(f"matmul: X must be ({N}, k) with k >= 1, not {X.shape}")
-            k = X.shape[1]
-            hx = np.ascontiguousarray(X, dtype=np.float64)
-            dx, dy = DeviceBuffer(hx.nbytes).up(hx), DeviceBuffer(M * k * 8)
-            try:
-                _check(lib.hipSpMMRowsCSR(C.byref(self.handle), k, dx.ptr, k, SPMV_DENSE_ROW_MAJOR, dy.ptr, k,
-                                          SPMV_DENSE_ROW_MAJOR), "hipSpMMRowsCSR")
-                return dy.down(np.float64).reshape(M, k)
-            finally:
-                dx.free()
-                dy.free()
-        import torch
-        if not isinstance(X, torch.Tensor):
-            raise SpmvHipError("matmul: X must be a numpy array or a torch tensor")
-        if X.dim() != 2 or X.shape[0] != N or X.shape[1] < 1:
-            raise SpmvHipError(f"matmul: X must be ({N}, k) with k >= 1, not {tuple(X.shape)}")
-        k = X.shape[1]
-        if out is None:
-            out = torch.empty((M, k), dtype=torch.float64, device=X.device)
-        elif out.dim() != 2 or tuple(out.shape) != (M, k):
-            raise SpmvHipError(f"matmul: out must be ({M}, {k}), not {tuple(out.shape)}")
-        xl, ldx = _dense_layout(X, "X")
-        yl, ldy = _dense_layout(out, "out")
-        _check(lib.hipSpMMRowsCSR(C.byref(self.handle), k, X.data_ptr(), ldx, xl, out.data_ptr(), ldy, yl), "hipSpMMRowsCSR")
-        return out
+        with _Operands("matmul", X) as ops:
+            k, xl, ldx = ops.dense("X", X, N)
+            yl, ldy = ops.result("out", out, (M, k))
+            dx, dy = ops.args
+            _check(lib.hipSpMMRowsCSR(C.byref(self.handle), k, dx, ldx, xl, dy, ldy, yl), "hipSpMMRowsCSR")
+            return ops.value()
 
     def triangular_analyse(self, lower=True):
         """spmvHipTriAnalyse: build the level-set schedule of the lower (or upper) triangle now (the first solve does it
@@ -669,31 +801,11 @@ class DeviceMatrix:
         N = int(self.handle.N)
         uplo = SPMV_TRI_LOWER if lower else SPMV_TRI_UPPER
         diag = SPMV_DIAG_UNIT if unit_diagonal else SPMV_DIAG_STORED
-        if isinstance(b, np.ndarray):
-            if out is not None:
-                raise SpmvHipError("solve_triangular: `out` is for torch tensors")
-            if b.ndim != 1 or b.shape[0] != N:
-                raise SpmvHipError(f"solve_triangular: b must have shape ({N},), not {b.shape}")
-            hb = np.ascontiguousarray(b, dtype=np.float64)
-            db, dx = DeviceBuffer(hb.nbytes).up(hb), DeviceBuffer(hb.nbytes)
-            try:
-                _check(lib.hipSpTRSVCSR(C.byref(self.handle), uplo, diag, db.ptr, dx.ptr), "hipSpTRSVCSR")
-                return dx.down(np.float64)
-            finally:
-                db.free()
-                dx.free()
-        import torch
-        for t, what in ((b, "b"), (out, "out")):
-            if t is None:
-                continue
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous():
-                raise SpmvHipError(f"solve_triangular: {what} must be a contiguous float64 torch tensor on the device")
-            if t.dim() != 1 or t.shape[0] != N:
-                raise SpmvHipError(f"solve_triangular: {what} must have shape ({N},), not {tuple(t.shape)}")
-        if out is None:
-            out = torch.empty_like(b)
-        _check(lib.hipSpTRSVCSR(C.byref(self.handle), uplo, diag, b.data_ptr(), out.data_ptr()), "hipSpTRSVCSR")
-        return out
+        with _Operands("solve_triangular", b) as ops:
+            ops.vector("b", b, N)
+            ops.result("out", out, (N,))
+            _check(lib.hipSpTRSVCSR(C.byref(self.handle), uplo, diag, *ops.args), "hipSpTRSVCSR")
+            return ops.value()
 
     def ilu0(self) -> "spmvIluInfo":
         """hipSpILU0CSR: overwrite this square matrix's values with its ILU(0) factors in place (L strictly lower with a unit
@@ -735,30 +847,11 @@ class DeviceMatrix:
             opts = spmvGmresOpts(float(tol), int(maxiter), int(restart), hp)
         info = spmvKrylovInfo()
         mh = C.byref(precond.handle) if precond is not None else None
-        if isinstance(b, np.ndarray):
-            for t, what in ((b, "b"), (x0, "x0")):
-                if t is not None and (not isinstance(t, np.ndarray) or t.shape != (N,)):
-                    raise SpmvHipError(f"{name}: {what} must be a numpy array of shape ({N},)")
-            hb = np.ascontiguousarray(b, dtype=np.float64)
-            hx = np.zeros(N) if x0 is None else np.ascontiguousarray(x0, dtype=np.float64)
-            db, dx = DeviceBuffer(hb.nbytes).up(hb), DeviceBuffer(hx.nbytes).up(hx)
-            try:
-                _check(fn(C.byref(self.handle), mh, db.ptr, dx.ptr, C.byref(opts), C.byref(info)), name)
-                x = dx.down(np.float64)
-            finally:
-                db.free()
-                dx.free()
-        else:
-            import torch
-            for t, what in ((b, "b"), (x0, "x0")):
-                if t is None:
-                    continue
-                if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous():
-                    raise SpmvHipError(f"{name}: {what} must be a contiguous float64 torch tensor on the device")
-                if t.dim() != 1 or t.shape[0] != N:
-                    raise SpmvHipError(f"{name}: {what} must have shape ({N},), not {tuple(t.shape)}")
-            x = torch.zeros_like(b) if x0 is None else x0.clone()
-            _check(fn(C.byref(self.handle), mh, b.data_ptr(), x.data_ptr(), C.byref(opts), C.byref(info)), name)
+        with _Operands(name, b) as ops:
+            ops.vector("b", b, N)
+            ops.result("x", None, (N,), init=("x0", x0))
+            _check(fn(C.byref(self.handle), mh, *ops.args, C.byref(opts), C.byref(info)), name)
+            x = ops.value()
         if history:
             info.history = hist[:info.iterations + 1].copy()
         return x, info
@@ -791,29 +884,11 @@ class AmgHierarchy(DeviceMatrix):
         """spmvHipAmgApply: z = V(0, r), one cycle.  r: a numpy array -> z as numpy; or a float64 device torch tensor
         (any 8-byte alignment) -> z as a torch tensor (`out` when given)."""
         N = int(self.handle.M)
-        if isinstance(r, np.ndarray):
-            if out is not None:
-                raise SpmvHipError("spmvHipAmgApply: `out` is for torch tensors")
-            if r.shape != (N,):
-                raise SpmvHipError(f"spmvHipAmgApply: r must have shape ({N},), not {r.shape}")
-            hr = np.ascontiguousarray(r, dtype=np.float64)
-            dr, dz = DeviceBuffer(hr.nbytes).up(hr), DeviceBuffer(hr.nbytes)
-            try:
-                _check(lib.spmvHipAmgApply(C.byref(self.handle), C.byref(self.source.handle), dr.ptr, dz.ptr), "spmvHipAmgApply")
-                return dz.down(np.float64) if N else np.zeros(0)
-            finally:
-                dr.free()
-                dz.free()
-        import torch
-        for t, what in ((r, "r"), (out, "out")):
-            if t is None and what == "out":
-                continue
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous() or t.shape != (N,):
-                raise SpmvHipError(f"spmvHipAmgApply: {what} must be a contiguous float64 device tensor of shape ({N},)")
-        if out is None:
-            out = torch.empty(N, dtype=torch.float64, device=r.device)
-        _check(lib.spmvHipAmgApply(C.byref(self.handle), C.byref(self.source.handle), r.data_ptr(), out.data_ptr()), "spmvHipAmgApply")
-        return out
+        with _Operands("spmvHipAmgApply", r) as ops:
+            ops.vector("r", r, N)
+            ops.result("out", out, (N,))
+            _check(lib.spmvHipAmgApply(C.byref(self.handle), C.byref(self.source.handle), *ops.args), "spmvHipAmgApply")
+            return ops.value()
 
     def refresh_from(self, source: "DeviceMatrix"):
         """spmvHipAmgRefresh: `source` (the matrix of the setup) has new values on the same pattern."""
@@ -853,17 +928,8 @@ def _dev_ptr(b):
 
 
 def _perm_len(perm, who):
-    """entries of a device permutation: a DeviceBuffer of uint32 or a contiguous int32 torch tensor on the device"""
-    if isinstance(perm, DeviceBuffer):
-        return perm.nbytes // 4
-    try:
-        import torch
-    except ImportError:
-        torch = None
-    if torch is None or not isinstance(perm, torch.Tensor) or perm.dtype != torch.int32 or not perm.is_cuda or perm.dim() != 1 \
-            or not perm.is_contiguous():
-        raise SpmvHipError(f"{who}: perm must be a DeviceBuffer of uint32 or a contiguous 1-D int32 torch tensor on the device")
-    return perm.numel()
+    """entries of a device permutation: a DeviceBuffer of uint32, or an int32 tensor under the 1-D rule of a device call"""
+    return perm.nbytes // 4 if isinstance(perm, DeviceBuffer) else _device_vector(who, "perm", perm, int32=True)
 
 
 def permute_vector(perm, v, inverse=False, out=None):
@@ -873,37 +939,16 @@ def permute_vector(perm, v, inverse=False, out=None):
     uploaded, permuted, returned as numpy.  Runs on the library stream."""
     perm = perm.perm if isinstance(perm, Colouring) else perm
     n = _perm_len(perm, "permute_vector")
-    if isinstance(v, np.ndarray):
-        if out is not None:
-            raise SpmvHipError("permute_vector: `out` is for torch tensors")
-        if v.shape != (n,):
-            raise SpmvHipError(f"permute_vector: v must have shape ({n},), not {v.shape}")
-        hv = np.ascontiguousarray(v, dtype=np.float64)
-        dv, do = DeviceBuffer(hv.nbytes).up(hv), DeviceBuffer(hv.nbytes)
-        try:
-            _check(lib.spmvHipVecPermute(n, _dev_ptr(perm), dv.ptr, do.ptr, 1 if inverse else 0), "spmvHipVecPermute")
-            return do.down(np.float64)
-        finally:
-            dv.free()
-            do.free()
-    import torch
-    for t, what in ((v, "v"), (out, "out")):
-        if t is None:
-            continue
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or not t.is_cuda or t.dim() != 1 or \
-                (t.numel() > 1 and t.stride(0) != 1):
-            raise SpmvHipError(f"permute_vector: {what} must be a 1-D float64 torch tensor on the device with unit stride")
-        if t.numel() != n:
-            raise SpmvHipError(f"permute_vector: {what} must have length {n}, not {t.numel()}")
-    if out is None:
-        out = torch.empty(n, dtype=torch.float64, device=v.device)
-    _check(lib.spmvHipVecPermute(n, _dev_ptr(perm), v.data_ptr(), out.data_ptr(), 1 if inverse else 0), "spmvHipVecPermute")
-    return out
+    with _Operands("permute_vector", v) as ops:
+        ops.vector("v", v, n)
+        ops.result("out", out, (n,))
+        _check(lib.spmvHipVecPermute(n, _dev_ptr(perm), *ops.args, 1 if inverse else 0), "spmvHipVecPermute")
+        return ops.value()
 
 
 def _dense_layout(t, what):
     """(layout, leading dimension) of a 2-D float64 device tensor of shape (rows, k) with unit stride in one dimension"""
-    import torch
+    torch = _torch()
     if t.dtype != torch.float64 or not t.is_cuda:
         raise SpmvHipError(f"matmul: {what} must be a float64 tensor on the device")
     (rows, k), (s0, s1) = t.shape, t.stride()
@@ -968,50 +1013,25 @@ def stripes_info(dmat: DeviceMatrix) -> spmvStripesInfo:
 def dot(u, v):
     """spmvHipDot: u . v of two float64 device torch tensors of one length (1-D, unit stride; any element offset) in the
     fixed order of include/spmvHip.h, as a 0-d float64 tensor on the same device.  Runs on the library stream."""
-    import torch
-    for t, what in ((u, "u"), (v, "v")):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or not t.is_cuda or t.dim() != 1 or \
-                (t.numel() > 1 and t.stride(0) != 1):
-            raise SpmvHipError(f"dot: {what} must be a 1-D float64 torch tensor on the device with unit stride")
-    if u.numel() != v.numel():
-        raise SpmvHipError(f"dot: lengths {u.numel()} and {v.numel()} differ")
-    out = torch.empty((), dtype=torch.float64, device=u.device)
-    _check(lib.spmvHipDot(u.numel(), u.data_ptr(), v.data_ptr(), out.data_ptr()), "spmvHipDot")
-    return out
+    with _Operands("dot", u, host_calls=False) as ops:
+        n = ops.vector("u", u)
+        ops.vector("v", v, n)
+        ops.result("out", None, ())
+        _check(lib.spmvHipDot(n, *ops.args), "spmvHipDot")
+        return ops.value()
 
 
 def multi_dot(V, w):
     """spmvHipMultiDot: h = V^T w, every h[i] the bits of dot(V[:, i], w).  V: a 2-D float64 device torch tensor (n, k) whose
     columns are contiguous (V.stride(0) == 1, ldv = V.stride(1) >= n) and w a 1-D one of length n with unit stride -> a
     length-k device tensor; or numpy arrays (V in Fortran order, else copied to it) -> a numpy array."""
-    if isinstance(V, np.ndarray):
-        if V.ndim != 2 or not isinstance(w, np.ndarray) or w.shape != (V.shape[0],):
-            raise SpmvHipError("multi_dot: V must be (n, k) and w (n,)")
-        n, k = V.shape
-        hV, hw = np.asfortranarray(V, dtype=np.float64), np.ascontiguousarray(w, dtype=np.float64)
-        dV, dw, dh = DeviceBuffer(max(hV.nbytes, 8)), DeviceBuffer(max(hw.nbytes, 8)), DeviceBuffer(8 * max(k, 1))
-        try:
-            if n:
-                dV.up(hV.ravel(order="F"))
-                dw.up(hw)
-            _check(lib.spmvHipMultiDot(n, k, dV.ptr, n, dw.ptr, dh.ptr), "spmvHipMultiDot")
-            return dh.down(np.float64)[:k]
-        finally:
-            for d in (dV, dw, dh):
-                d.free()
-    import torch
-    for t, dim, what in ((V, 2, "V"), (w, 1, "w")):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or not t.is_cuda or t.dim() != dim:
-            raise SpmvHipError(f"multi_dot: {what} must be a {dim}-D float64 torch tensor on the device")
-    n, k = V.shape
-    if w.numel() != n or (n > 1 and w.stride(0) != 1):
-        raise SpmvHipError(f"multi_dot: w must have length {n} and unit stride")
-    if (n > 1 and V.stride(0) != 1) or (k > 1 and V.stride(1) < n):
-        raise SpmvHipError(f"multi_dot: V needs contiguous columns (strides {V.stride()})")
-    out = torch.empty(k, dtype=torch.float64, device=V.device)
-    _check(lib.spmvHipMultiDot(n, k, V.data_ptr(), V.stride(1) if k > 1 else max(n, 1), w.data_ptr(), out.data_ptr()),
-           "spmvHipMultiDot")
-    return out
+    with _Operands("multi_dot", V) as ops:
+        n, k, ldv = ops.columns("V", V)
+        ops.vector("w", w, n, least=8)
+        ops.result("h", None, (k,), least=8)
+        dV, dw, dh = ops.args
+        _check(lib.spmvHipMultiDot(n, k, dV, ldv, dw, dh), "spmvHipMultiDot")
+        return ops.value()
 
 
 def set_variant(launcher: str, variant: int):

@@ -3,7 +3,6 @@ Python with the C layout of spmvColourOpts / spmvColourInfo, and the test side's
 loop of include/spmvHip.h: the numpy rounds equal the plain-Python loop on every small case, every result is a proper
 colouring of A + A^T, the level sets of the permuted matrix number at most the colours, the fmix32 constants are pinned,
 and a planted fault (ignoring the incoming edges) is caught.  No GPU needed."""
-import ctypes as C
 import os
 import re
 import subprocess
@@ -12,11 +11,10 @@ import numpy as np
 import pytest
 
 import colour_ref as cr
+from c_header import HEADER, code as _code
 from conftest import ROOT
-from test_krylov_abi import _code
 from trsv_ref import levels
 
-HEADER = os.path.join(ROOT, "include", "spmvHip.h")
 LIB = os.path.join(ROOT, "spmv_openmp_cuda_amd", "lib", "libspmvhip.so")
 U32 = r"uint32_t\s*\*\s*\w+"
 DECLS = {
@@ -58,19 +56,6 @@ def test_python_binds_the_four():
     assert [f[0] for f in api.spmvColourOpts._fields_] == list(OPTS)
     assert [f[0] for f in api.spmvColourInfo._fields_] == list(INFO)
     assert (api.SPMV_COLOUR_NATURAL, api.SPMV_COLOUR_HASH) == (cr.NATURAL, cr.HASH)
-
-
-@pytest.mark.parametrize("struct,fields", [("spmvColourOpts", OPTS), ("spmvColourInfo", INFO)])
-def test_struct_layout_matches_c(tmp_path, struct, fields):
-    from spmv_openmp_cuda_amd import api
-    src = tmp_path / "layout.c"
-    body = f'    printf(" %zu", sizeof({struct}));\n' + "".join(f'    printf(" %zu", offsetof({struct}, {f}));\n' for f in fields)
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "spmvHip.h"\nint main(void) {\n' + body + "    return 0;\n}\n")
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I" + os.path.join(ROOT, "include"), "-o", str(exe), str(src)], check=True)
-    got = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    py = getattr(api, struct)
-    assert got == [C.sizeof(py)] + [getattr(py, f).offset for f in fields]
 
 
 def test_fmix32_constants():

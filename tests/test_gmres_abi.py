@@ -3,7 +3,6 @@ the test side's reference (tests/gmres_ref.py) is the loop of include/spmvHip.h:
 plain Python (math.sqrt, float) on every small case of tests/gmres_exit_inputs.py, every case of that table takes the
 exit and the cycle end the table claims for it, the table is complete, and two planted faults each change a case.
 No GPU needed."""
-import ctypes as C
 import math
 import os
 import re
@@ -15,13 +14,13 @@ import pytest
 import gmres_exit_inputs as exits
 import serial_order_inputs as si
 from bits import assert_same_bits
+from c_header import HEADER, code as _code
 from conftest import ROOT
 from gmres_ref import CYCLE_ENDS, GMRES_EXITS, gmres_ref, multi_dot_ref
 from ilu0_ref import ilu0_levels, ilu0_loop
 from krylov_ref import BREAKDOWN, CONVERGED, MAXITER, NONFINITE, Csr, dot_ref
-from test_krylov_abi import _code, _div, _ops, _same, convdiff7, dot_loop
+from test_krylov_abi import _div, _ops, _same, convdiff7, dot_loop
 
-HEADER = os.path.join(ROOT, "include", "spmvHip.h")
 LIB = os.path.join(ROOT, "spmv_openmp_cuda_amd", "lib", "libspmvhip.so")
 DECLS = {
     "spmvHipMultiDot": r"size_t\s+\w+\s*,\s*unsigned\s+\w+\s*,\s*const\s+double\s*\*\s*\w+\s*,\s*size_t\s+\w+\s*,\s*"
@@ -53,17 +52,6 @@ def test_python_binds_the_two():
         assert name in api._sigs and len(getattr(api.lib, name).argtypes) == 6, name
     assert callable(api.DeviceMatrix.gmres) and callable(api.multi_dot)
     assert [f[0] for f in api.spmvGmresOpts._fields_] == list(OPTS)
-
-
-def test_struct_layout_matches_c(tmp_path):
-    from spmv_openmp_cuda_amd import api
-    src = tmp_path / "layout.c"
-    body = '    printf(" %zu", sizeof(spmvGmresOpts));\n' + "".join(f'    printf(" %zu", offsetof(spmvGmresOpts, {f}));\n' for f in OPTS)
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "spmvHip.h"\nint main(void) {\n' + body + "    return 0;\n}\n")
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I" + os.path.join(ROOT, "include"), "-o", str(exe), str(src)], check=True)
-    got = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert got == [C.sizeof(api.spmvGmresOpts)] + [getattr(api.spmvGmresOpts, f).offset for f in OPTS]
 
 
 def test_multi_dot_ref_is_k_dots():

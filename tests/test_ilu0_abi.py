@@ -1,7 +1,6 @@
 """The ILU(0) entry points (hipSpILU0CSR, spmvHipIlu0Info) are declared, exported and bound in Python with the C layout of
 spmvIluInfo, and the test side's two references (tests/ilu0_ref.py) agree bit for bit -- on inputs where another update
 order gives other bits.  No GPU needed."""
-import ctypes as C
 import os
 import re
 import subprocess
@@ -11,21 +10,17 @@ import pytest
 
 import serial_order_inputs as si
 from bits import assert_same_bits, differing_rows
+from c_header import HEADER, code as _code
 from conftest import ROOT
 from ilu0_ref import check_pattern, ilu0_crout, ilu0_kij, ilu0_levels, ilu0_loop
 from test_trsv_abi import laplacian7, random_square
 
-HEADER = os.path.join(ROOT, "include", "spmvHip.h")
 LIB = os.path.join(ROOT, "spmv_openmp_cuda_amd", "lib", "libspmvhip.so")
 DECLS = {
     "hipSpILU0CSR": r"spmat\s*\*\s*\w+",
     "spmvHipIlu0Info": r"spmat\s*\*\s*\w+\s*,\s*spmvIluInfo\s*\*\s*\w+",
 }
 FIELDS = ("zeroPivot", "firstBadRow", "levels", "launches", "longRows", "factorisations", "ms")
-
-
-def _code(path):
-    return re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
 
 
 def test_header_declares_the_two_and_the_struct():
@@ -52,19 +47,6 @@ def test_python_binds_the_two():
     for m in ("ilu0", "ilu0_info"):
         assert callable(getattr(api.DeviceMatrix, m)), m
     assert [f[0] for f in api.spmvIluInfo._fields_] == list(FIELDS)
-
-
-def test_info_layout_matches_the_c_struct(tmp_path):
-    from spmv_openmp_cuda_amd import api
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "spmvHip.h"\nint main(void) {\n'
-                   '    printf("%zu", sizeof(spmvIluInfo));\n' +
-                   "".join(f'    printf(" %zu", offsetof(spmvIluInfo, {f}));\n' for f in FIELDS) + "    return 0;\n}\n")
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I" + os.path.join(ROOT, "include"), "-o", str(exe), str(src)], check=True)
-    got = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    want = [C.sizeof(api.spmvIluInfo)] + [getattr(api.spmvIluInfo, f).offset for f in FIELDS]
-    assert got == want
 
 
 # ------------------------------------------------------------------------------------------------- the references

@@ -3,7 +3,6 @@ C layouts of spmvKrylovOpts and spmvKrylovInfo, and the test side's references (
 include/spmvHip.h: dot_ref is the documented order (which np.dot and math.fsum are not), cg_ref and bicgstab_ref equal
 the loops written in plain Python on tiny systems, and every case of tests/krylov_exit_inputs.py takes the exit of the
 loop that the table claims for it (so the table reaches every `return` of both loops).  No GPU needed."""
-import ctypes as C
 import math
 import os
 import re
@@ -14,6 +13,7 @@ import pytest
 
 import serial_order_inputs as si
 from bits import assert_same_bits
+from c_header import HEADER, code as _code
 from conftest import ROOT
 from ilu0_ref import ilu0_levels, ilu0_loop
 import krylov_exit_inputs as exits
@@ -21,7 +21,6 @@ from krylov_ref import BICGSTAB_EXITS, BREAKDOWN, CG_EXITS, CONVERGED, MAXITER, 
 from test_trsv_abi import laplacian7
 from trsv_ref import trsv_loop
 
-HEADER = os.path.join(ROOT, "include", "spmvHip.h")
 LIB = os.path.join(ROOT, "spmv_openmp_cuda_amd", "lib", "libspmvhip.so")
 _SOLVER = r"spmat\s*\*\s*\w+\s*,\s*spmat\s*\*\s*\w+\s*,\s*const\s+double\s*\*\s*\w+\s*,\s*double\s*\*\s*\w+\s*,\s*" \
           r"const\s+spmvKrylovOpts\s*\*\s*\w+\s*,\s*spmvKrylovInfo\s*\*\s*\w+"
@@ -32,10 +31,6 @@ DECLS = {
 }
 OPTS = ("tol", "maxIter", "history")
 INFO = ("status", "iterations", "rr", "bb", "launches", "hostChecks", "ms")
-
-
-def _code(path):
-    return re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
 
 
 def test_header_declares_the_three_and_the_structs():
@@ -69,23 +64,6 @@ def test_python_binds_the_three():
     assert [f[0] for f in api.spmvKrylovInfo._fields_] == list(INFO)
     assert (api.SPMV_KRYLOV_CONVERGED, api.SPMV_KRYLOV_MAXITER, api.SPMV_KRYLOV_BREAKDOWN, api.SPMV_KRYLOV_NONFINITE) == \
         (CONVERGED, MAXITER, BREAKDOWN, NONFINITE)
-
-
-def test_struct_layouts_match_c(tmp_path):
-    from spmv_openmp_cuda_amd import api
-    src = tmp_path / "layout.c"
-    body = ""
-    for struct, fields in (("spmvKrylovOpts", OPTS), ("spmvKrylovInfo", INFO)):
-        body += f'    printf(" %zu", sizeof({struct}));\n'
-        body += "".join(f'    printf(" %zu", offsetof({struct}, {f}));\n' for f in fields)
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "spmvHip.h"\nint main(void) {\n' + body + "    return 0;\n}\n")
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I" + os.path.join(ROOT, "include"), "-o", str(exe), str(src)], check=True)
-    got = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    want = []
-    for s, fields in ((api.spmvKrylovOpts, OPTS), (api.spmvKrylovInfo, INFO)):
-        want += [C.sizeof(s)] + [getattr(s, f).offset for f in fields]
-    assert got == want
 
 
 # ------------------------------------------------------------------------------------------------- the dot product

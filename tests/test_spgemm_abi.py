@@ -3,7 +3,6 @@ spmvSpgemmInfo, and the test side's reference (tests/spgemm_ref.py) is the loop 
 equals the plain loop as bits on every small case, integer-valued inputs give the dense product exactly with the
 structural pattern, rows ascend strictly, and reversing A's stored order changes a bit -- so the inputs can see a wrong
 order.  No GPU needed."""
-import ctypes as C
 import os
 import re
 import subprocess
@@ -13,10 +12,9 @@ import pytest
 
 import serial_order_inputs as si
 import spgemm_ref as sr
+from c_header import HEADER, code as _code
 from conftest import ROOT
-from test_krylov_abi import _code
 
-HEADER = os.path.join(ROOT, "include", "spmvHip.h")
 LIB = os.path.join(ROOT, "spmv_openmp_cuda_amd", "lib", "libspmvhip.so")
 H = r"spmat\s*\*\s*\w+"
 DECLS = {
@@ -56,19 +54,6 @@ def test_python_binds_both():
         assert callable(getattr(api.DeviceMatrix, m)), m
     assert [f[0] for f in api.spmvSpgemmOpts._fields_] == list(OPTS)
     assert [f[0] for f in api.spmvSpgemmInfo._fields_] == list(INFO)
-
-
-@pytest.mark.parametrize("struct,fields", [("spmvSpgemmOpts", OPTS), ("spmvSpgemmInfo", INFO)])
-def test_struct_layout_matches_c(tmp_path, struct, fields):
-    from spmv_openmp_cuda_amd import api
-    src = tmp_path / "layout.c"
-    body = f'    printf(" %zu", sizeof({struct}));\n' + "".join(f'    printf(" %zu", offsetof({struct}, {f}));\n' for f in fields)
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "spmvHip.h"\nint main(void) {\n' + body + "    return 0;\n}\n")
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I" + os.path.join(ROOT, "include"), "-o", str(exe), str(src)], check=True)
-    got = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    py = getattr(api, struct)
-    assert got == [C.sizeof(py)] + [getattr(py, f).offset for f in fields]
 
 
 @pytest.mark.parametrize("name", list(CASES))

@@ -4,14 +4,10 @@ import os
 import re
 import subprocess
 
+from c_header import HEADER, code as _code
 from conftest import ROOT
 
-HEADER = os.path.join(ROOT, "include", "spmvHip.h")
 LIB = os.path.join(ROOT, "spmv_openmp_cuda_amd", "lib", "libspmvhip.so")
-
-
-def _code(path):
-    return re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
 
 
 def test_header_declares_spmm_and_layouts():

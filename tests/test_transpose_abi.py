@@ -10,16 +10,12 @@ import pytest
 
 import serial_order_inputs as si
 from bits import assert_same_bits, differing_rows
+from c_header import HEADER, code as _code
 from conftest import ROOT
 from transpose_ref import scatter_serial, stable_transpose
 
-HEADER = os.path.join(ROOT, "include", "spmvHip.h")
 LIB = os.path.join(ROOT, "spmv_openmp_cuda_amd", "lib", "libspmvhip.so")
 NAMES = ("spmvHipCsrTranspose", "spmvHipTransposeRefresh")
-
-
-def _code(path):
-    return re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
 
 
 def test_header_declares_both():

@@ -1,7 +1,6 @@
 """The triangular-solve entry points (spmvHipTriAnalyse, hipSpTRSVCSR, spmvHipTriInfo) are declared, exported and bound
 in Python with the C layout of spmvTriInfo, and the test side's references (tests/trsv_ref.py) agree bit for bit on
 inputs where another summation order gives other bits.  No GPU needed."""
-import ctypes as C
 import os
 import re
 import subprocess
@@ -11,10 +10,10 @@ import pytest
 
 import serial_order_inputs as si
 from bits import assert_same_bits, differing_rows
+from c_header import HEADER, code as _code
 from conftest import ROOT
 from trsv_ref import diag_pos, levels, trsv_levels, trsv_loop
 
-HEADER = os.path.join(ROOT, "include", "spmvHip.h")
 LIB = os.path.join(ROOT, "spmv_openmp_cuda_amd", "lib", "libspmvhip.so")
 DECLS = {
     "spmvHipTriAnalyse": r"spmat\s*\*\s*\w+\s*,\s*int\s+\w+",
@@ -22,10 +21,6 @@ DECLS = {
     "spmvHipTriInfo": r"spmat\s*\*\s*\w+\s*,\s*int\s+\w+\s*,\s*spmvTriInfo\s*\*\s*\w+",
 }
 FIELDS = ("levels", "maxLevelRows", "launches", "fusedLevels", "longRows", "firstBadDiag", "analyses", "analysisMs", "bytes")
-
-
-def _code(path):
-    return re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
 
 
 def test_header_declares_the_three():
@@ -51,19 +46,6 @@ def test_python_binds_the_three():
     for m in ("solve_triangular", "triangular_analyse", "triangular_info"):
         assert callable(getattr(api.DeviceMatrix, m)), m
     assert [f[0] for f in api.spmvTriInfo._fields_] == list(FIELDS)
-
-
-def test_info_layout_matches_the_c_struct(tmp_path):
-    from spmv_openmp_cuda_amd import api
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "spmvHip.h"\nint main(void) {\n'
-                   '    printf("%zu", sizeof(spmvTriInfo));\n' +
-                   "".join(f'    printf(" %zu", offsetof(spmvTriInfo, {f}));\n' for f in FIELDS) + "    return 0;\n}\n")
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I" + os.path.join(ROOT, "include"), "-o", str(exe), str(src)], check=True)
-    got = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    want = [C.sizeof(api.spmvTriInfo)] + [getattr(api.spmvTriInfo, f).offset for f in FIELDS]
-    assert got == want
 
 
 # ------------------------------------------------------------------------------------------------- the references
