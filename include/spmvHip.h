@@ -507,6 +507,65 @@ typedef struct {
 } spmvSpgemmInfo;
 int spmvHipSpGEMM(spmat* dA, spmat* dB, const spmvSpgemmOpts* opts, spmat* dC, spmvSpgemmInfo* info);
 int spmvHipSpGEMMRefresh(spmat* dC, spmat* dA, spmat* dB, spmvSpgemmInfo* info);
+/* ------------------------------------------------------------- sparse matrix sum C = alpha A + beta B */
+/* spmvHipCsrAdd writes into dC a new, independent CSR handle of C = alpha A + beta B (A - sigma I, A + A^T, the smoothed
+ * prolongator T - omega D^-1 A T, a product followed by a sum).  The contract is the bits of this serial loop on the two
+ * handles' arrays (IRP, JA, AS as stored):
+ *       for i in 0 .. M-1:
+ *           for p in A.IRP[i] .. A.IRP[i+1]-1:                 (A's stored order)
+ *               j = A.JA[p];  if (i, j) is new: acc[i,j] = +0.0
+ *               acc[i,j] = acc[i,j] + (alpha * A.AS[p])        (product rounded, then the add: contraction is off)
+ *           for q in B.IRP[i] .. B.IRP[i+1]-1:                 (B's stored order, after all of A's row)
+ *               j = B.JA[q];  if (i, j) is new: acc[i,j] = +0.0
+ *               acc[i,j] = acc[i,j] + (beta * B.AS[q])
+ *           row i of C = the (j, acc[i,j]) in ascending j
+ *   Structural: every (i, j) that A or B stores is stored, even when the sum is 0.0 or the term is 0 * a: alpha = 0 keeps
+ *   A's pattern, and 0 * Inf is a NaN at its place.  A and B may have unsorted rows and repeated (row, col) pairs: each
+ *   repeat is one more term, in stored order.  Rows of C ascend strictly and have no repeats, so hipSpILU0CSR, hipSpTRSVCSR
+ *   and the serial-order SpMV selection accept C as it is.  The result is a function of the two handles' arrays, alpha and
+ *   beta alone -- not of the run, the grid, the class a row fell into or the options.  Where a term is NaN, C has a NaN at
+ *   that place; its payload is not pinned.  Every other value is pinned as bits: a -0.0 alone in its column gives +0.0
+ *   (0.0 + -0.0), and a cancelling pair a stored +0.0.
+ *   dC is like a product handle: u32 columns, 4-byte row pointers, its own unit detection, row blocks; every CSR entry
+ *   point works on it; freed with hipFreeSpmat.  dA == dB is allowed.  Sources: spMatCpyCSR / spmvHipAdoptCSR (row
+ *   pointers of 4 or 8 bytes) / transpose / permuted / product / sum handles, unit-value handles included.
+ *   A row's class comes from t = its terms (entries of A's row + entries of B's row), from whether it is PLAIN (both stored
+ *   rows ascend strictly) and from opts alone (NULL, or a field 0: the built-in default; a value above the built-in limit is
+ *   clamped to it): plain and t <= laneMaxTerms (32, limit 64) one lane merges the two rows; plain and t <= waveMaxTerms
+ *   (2 048, the limit) one wavefront places every entry by rank; everything else, and every row under allSorted, the
+ *   sorted path of spmvHipSpGEMM (one stable radix sort per batch of rows whose terms fit sortBudgetBytes: 32 B per term,
+ *   default 256 MiB, limit 4 GiB; a row above the budget is a batch of its own).
+ *   Memory: C itself 12 B per entry + 4 B per row, its row blocks, and 4 B per row for the refresh (the rows by class).
+ *   Temporaries, freed before the call returns: 20 B per row for the first pass and the lists (24 B with a row of more
+ *   than 64 terms), then 12 B per row for the counts and their scan, 16 B per sorted row, and 32 B per term of the largest
+ *   sorted batch + the sort's workspace.
+ *   info: terms (entries of A + entries of B), nnzC, maxRowTerms, maxRowNnz, rowsLane / rowsWave / rowsSorted (they sum to
+ *   the rows with a term), sortBatches, tempBytes (peak of the temporaries), symbolicMs / numericMs / ms (wall times).
+ *   Synchronous on the library stream; allocates, so not capturable.  opts and info may be NULL.
+ *   M = 0, N = 0, two empty sources and one empty source succeed with a valid C (NZ = 0 and SpMV +0.0 when both are empty).
+ * spmvHipCsrAddRefresh recomputes C's values from the sources' CURRENT value arrays with the alpha and beta of THIS call
+ *   (a shift sweep A - sigma I is one build and many refreshes), C's pattern and addresses kept: the numeric phase only, on
+ *   the classes of the build, then what spmvHipValuesChanged(dC) does.  dC records both sources' ids in order (alpha goes
+ *   with A) and refuses any other pair, and the same pair swapped.  The sources' patterns must be unchanged.
+ * Refused with a message and EXIT_FAILURE, dC and info untouched: NULL dA, dB or dC; a handle that is not live; an ELL
+ *   handle or a multigrid hierarchy; A.M != B.M or A.N != B.N; dC == dA or dC == dB; M or N >= 2^32 - 1; nnz(C) >=
+ *   IRP32_LIMIT (2^32 - 65536; found after the symbolic phase, before C's column and value arrays exist); a column id >= N
+ *   in a source (an adopted array; checked on the device in the first pass); a source with entries but no column or value
+ *   array; a refresh of a handle that is not a sum, or from other sources. */
+typedef struct {            /* 0 = the built-in default; a value above the built-in limit is clamped to it */
+    ulong laneMaxTerms;     /* plain rows with at most this many terms: one lane each          */
+    ulong waveMaxTerms;     /* ... at most this many: one wavefront each; above: the sorted path */
+    ulong sortBudgetBytes;  /* temporaries of one batch of the sorted path                     */
+    int   allSorted;        /* 1: every row on the sorted path (the general path, for checking) */
+} spmvAddOpts;
+typedef struct {
+    ulong terms, nnzC, maxRowTerms, maxRowNnz;
+    ulong rowsLane, rowsWave, rowsSorted, sortBatches;   /* the three sum to the rows with a term */
+    ulong tempBytes;        /* peak of the build's temporaries */
+    double symbolicMs, numericMs, ms;
+} spmvAddInfo;
+int spmvHipCsrAdd(double alpha, spmat* dA, double beta, spmat* dB, const spmvAddOpts* opts, spmat* dC, spmvAddInfo* info);
+int spmvHipCsrAddRefresh(spmat* dC, double alpha, spmat* dA, double beta, spmat* dB, spmvAddInfo* info);
 /* ------------------------------------------------------------- aggregation multigrid preconditioner */
 /* Plain (unsmoothed) aggregation AMG built from the pieces above: an aggregation of the pattern, the Galerkin products by
  * spmvHipCsrTranspose / spmvHipSpGEMM, a damped-Jacobi V-cycle on serial-order SpMVs.  DESIGN.md section 24.  As everywhere

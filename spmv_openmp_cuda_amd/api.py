@@ -117,6 +117,8 @@ _sigs = {
     "spmvHipVecPermute": ([_sz, _vp, _vp, _vp, _i], _i),
     "spmvHipSpGEMM": ([C.POINTER(spmat), C.POINTER(spmat), _vp, C.POINTER(spmat), _vp], _i),
     "spmvHipSpGEMMRefresh": ([C.POINTER(spmat), C.POINTER(spmat), C.POINTER(spmat), _vp], _i),
+    "spmvHipCsrAdd": ([C.c_double, C.POINTER(spmat), C.c_double, C.POINTER(spmat), _vp, C.POINTER(spmat), _vp], _i),
+    "spmvHipCsrAddRefresh": ([C.POINTER(spmat), C.c_double, C.POINTER(spmat), C.c_double, C.POINTER(spmat), _vp], _i),
     "spmvHipAggregateCSR": ([C.POINTER(spmat), _vp, _vp, _vp], _i),
     "spmvHipAmgSetup": ([C.POINTER(spmat), _vp, C.POINTER(spmat), _vp], _i),
     "spmvHipAmgRefresh": ([C.POINTER(spmat), C.POINTER(spmat)], _i),
@@ -212,6 +214,18 @@ class spmvSpgemmInfo(C.Structure):
     """include/spmvHip.h `spmvSpgemmInfo`: what a spmvHipSpGEMM / spmvHipSpGEMMRefresh call did."""
     _fields_ = [("products", C.c_ulong), ("nnzC", C.c_ulong), ("maxRowProducts", C.c_ulong), ("maxRowNnz", C.c_ulong),
                 ("rowsWave", C.c_ulong), ("rowsGroup", C.c_ulong), ("rowsSorted", C.c_ulong), ("sortBatches", C.c_ulong),
+                ("tempBytes", C.c_ulong), ("symbolicMs", C.c_double), ("numericMs", C.c_double), ("ms", C.c_double)]
+
+
+class spmvAddOpts(C.Structure):
+    """include/spmvHip.h `spmvAddOpts`: the class limits of spmvHipCsrAdd (0 = the built-in default; they only lower)."""
+    _fields_ = [("laneMaxTerms", C.c_ulong), ("waveMaxTerms", C.c_ulong), ("sortBudgetBytes", C.c_ulong), ("allSorted", _i)]
+
+
+class spmvAddInfo(C.Structure):
+    """include/spmvHip.h `spmvAddInfo`: what a spmvHipCsrAdd / spmvHipCsrAddRefresh call did."""
+    _fields_ = [("terms", C.c_ulong), ("nnzC", C.c_ulong), ("maxRowTerms", C.c_ulong), ("maxRowNnz", C.c_ulong),
+                ("rowsLane", C.c_ulong), ("rowsWave", C.c_ulong), ("rowsSorted", C.c_ulong), ("sortBatches", C.c_ulong),
                 ("tempBytes", C.c_ulong), ("symbolicMs", C.c_double), ("numericMs", C.c_double), ("ms", C.c_double)]
 
 
@@ -743,6 +757,37 @@ class DeviceMatrix:
         info = getattr(self, "_spgemm", None)
         if info is None:
             raise SpmvHipError("spgemm_info: this matrix was not made by multiply()")
+        return info
+
+    def add(self, other: "DeviceMatrix", alpha=1.0, beta=1.0, laneMaxTerms=0, waveMaxTerms=0, sortBudgetBytes=0,
+            allSorted=False) -> "DeviceMatrix":
+        """spmvHipCsrAdd: C = alpha * self + beta * other as a new DeviceMatrix that owns its handle, bit for bit the serial
+        loop of include/spmvHip.h (self's terms of a row in stored order, then other's; rows of C ascending; structural zeros
+        kept).  The options only lower the class limits (0: the defaults); allSorted sends every row down the general path.
+        `other` may be this matrix.  add_info() tells what the call did."""
+        c = DeviceMatrix()
+        opts = spmvAddOpts(int(laneMaxTerms), int(waveMaxTerms), int(sortBudgetBytes), int(bool(allSorted)))
+        info = spmvAddInfo()
+        _check(lib.spmvHipCsrAdd(float(alpha), C.byref(self.handle), float(beta), C.byref(other.handle), C.byref(opts),
+                                 C.byref(c.handle), C.byref(info)), "spmvHipCsrAdd")
+        c.rows = int(c.handle.M)
+        c._add = info
+        return c
+
+    def add_refresh(self, a: "DeviceMatrix", b: "DeviceMatrix", alpha=1.0, beta=1.0):
+        """spmvHipCsrAddRefresh: this sum takes its values again as alpha * a + beta * b from the current values of `a` and
+        `b` (the pair it was built from, in that order; alpha and beta may be new), pattern and addresses kept, then
+        refreshes its formats as values_changed() does."""
+        info = spmvAddInfo()
+        _check(lib.spmvHipCsrAddRefresh(C.byref(self.handle), float(alpha), C.byref(a.handle), float(beta), C.byref(b.handle),
+                                        C.byref(info)), "spmvHipCsrAddRefresh")
+        self._add = info
+
+    def add_info(self) -> "spmvAddInfo":
+        """the spmvAddInfo of the add() that made this matrix, or of its last add_refresh()"""
+        info = getattr(self, "_add", None)
+        if info is None:
+            raise SpmvHipError("add_info: this matrix was not made by add()")
         return info
 
     def aggregate(self, seed=0):

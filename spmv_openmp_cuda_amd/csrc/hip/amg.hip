@@ -285,10 +285,6 @@ struct AmgCorrectOp : StopMode {                // z = z + e[agg]
     }
 };
 
-double msSince(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 DevMat* matOf(spmat* h) { return static_cast<DevMat*>(h->dev); }
 
 // dinv of one level; *badRow < 0 when every row has exactly one stored diagonal entry

@@ -28,16 +28,17 @@ constexpr int      STREAM_NNZ      = 2048;              // nnz staged in LDS per
 constexpr uint64_t IRP32_LIMIT     = (1ull << 32) - 65536;
 
 enum class Kind : int { CSR = 0, ELL_ROWMAJOR = 1, ELL_COLMAJOR = 2 };
-// How a handle came to be (DevMat::origin; UPLOADED is also what ownCsr makes).  The last four are made from other handles,
+// How a handle came to be (DevMat::origin; UPLOADED is also what ownCsr makes).  TRANSPOSE and later come from other handles,
 // whose ids -- never pointers: a source may be freed first -- DevMat::src records: TRANSPOSE, PERMUTATION, HIERARCHY the
-// source (the level-0 matrix) in src[0], PRODUCT A and B in that order.  What made a handle refreshes it, from those handles
-// only (madeBy in lib.hpp).  ELL_OF_CSR (spmvHipCsrToEll) keeps no link to its source, and its values cannot be updated.
-enum class Origin : int { UPLOADED, ADOPTED, ELL_OF_CSR, TRANSPOSE, PERMUTATION, PRODUCT, HIERARCHY };
+// source (the level-0 matrix) in src[0], PRODUCT and SUM A and B in that order.  What made a handle refreshes it, from those
+// handles only (madeBy in lib.hpp).  ELL_OF_CSR (spmvHipCsrToEll) keeps no link to its source, and its values cannot be updated.
+enum class Origin : int { UPLOADED, ADOPTED, ELL_OF_CSR, TRANSPOSE, PERMUTATION, PRODUCT, HIERARCHY, SUM };
 
 struct TileFormat;          // column-sliced two-phase format, tiles.hip
 struct SellFormat;          // SELL-C-sigma, sell.hip
 struct StripeFormat;        // bin-wise CSC (y bins in LDS, x from the XCD's L2), stripes.hip
 struct SpgemmPlan;          // what a product C = A B keeps for its refresh, spgemm.hip
+struct AddPlan;             // what a sum C = alpha A + beta B keeps for its refresh, add.hip
 struct AmgHierarchy;        // the levels of an aggregation multigrid preconditioner, amg.hip
 struct TempBuf;             // a scoped device buffer, device_prims.hpp
 
@@ -105,6 +106,8 @@ struct DevMat {
     uint32_t* tmap = nullptr;
     // a product (spmvHipSpGEMM, spgemm.hip): its rows by class (4 B per row)
     SpgemmPlan* prod = nullptr;
+    // a sum (spmvHipCsrAdd, add.hip): its rows by class (4 B per row)
+    AddPlan* sum = nullptr;
     // a multigrid hierarchy (spmvHipAmgSetup, amg.hip): the handle is then no matrix (no arrays, NZ = 0) and only the
     // spmvHipAmg* calls, a Krylov solve's dM and hipFreeSpmat take it
     AmgHierarchy* amg = nullptr;
@@ -126,6 +129,10 @@ auto withIrp(const void* IRP, int irpBytes, F&& f) {
     return irpBytes == 4 ? f(static_cast<const uint32_t*>(IRP)) : f(static_cast<const uint64_t*>(IRP));
 }
 template <typename F> auto withIrp(const DevMat* d, F&& f) { return withIrp(d->IRP, d->irpBytes, f); }
+// ... of two handles (the sparse product and the sparse sum): f(irpA, irpB)
+template <typename F> auto withBoth(const DevMat* a, const DevMat* b, F&& f) {
+    return withIrp(a, [&](auto ia) { return withIrp(b, [&](auto ib) { return f(ia, ib); }); });
+}
 
 int  buildSell(DevMat* d);                                      // sell.hip
 void freeSell(SellFormat* f);
@@ -198,6 +205,13 @@ int  enqueueVecPermute(uint64_t n, const uint32_t* perm, const double* in, doubl
 int  spgemmBuild(const DevMat* a, const DevMat* b, const spmvSpgemmOpts* opts, DevMat* c, spmvSpgemmInfo* info, hipStream_t stream);
 int  spgemmRefresh(DevMat* c, const DevMat* a, const DevMat* b, spmvSpgemmInfo* info, hipStream_t stream);
 void freeSpgemmPlan(SpgemmPlan* p);
+// C = alpha A + beta B (add.hip; contract in spmvHip.h, design in DESIGN.md section 25), as the product: addBuild fills c (kind,
+// M and N set, nothing owned) with IRP (4 B), JA, AS and the plan, NZ set -- on failure the caller frees c with whatever it
+// holds --, addRefresh runs the numeric phase again into c's arrays.  Both synchronous, temporaries freed before they return.
+int  addBuild(double alpha, const DevMat* a, double beta, const DevMat* b, const spmvAddOpts* opts, DevMat* c, spmvAddInfo* info,
+              hipStream_t stream);
+int  addRefresh(DevMat* c, double alpha, const DevMat* a, double beta, const DevMat* b, spmvAddInfo* info, hipStream_t stream);
+void freeAddPlan(AddPlan* p);
 // Aggregation multigrid (amg.hip; contracts in spmvHip.h, design in DESIGN.md section 24).  aggregateCsr: the aggregate ids
 // of the checked square handle into dAgg (M words), K rounds per host check; synchronous, allocates, temporaries freed
 // before it returns.  amgBuild: the hierarchy of the checked handle hA into m->amg, K aggregation rounds per host check (on

@@ -1,5 +1,5 @@
 // device_prims.hpp -- what a build step on the device gets its temporaries, sorts and scans from (library-private; the
-// format files tiles / stripes / sell and transpose, trsv, ilu0, colour, spgemm include it after kernels.hpp).
+// format files tiles / stripes / sell and transpose, trsv, ilu0, colour, spgemm, add include it after kernels.hpp).
 //
 //   TempBuf                     one scoped device buffer; with a TempTally it keeps the bytes held and their peak
 //   sortPairs / sortKeys /      rocPRIM's "two-call" algorithms in one call: the size query, the workspace (grown only
@@ -7,14 +7,22 @@
 //   enqueueIota / enqueueFill32 the two trivial kernels, defined ONCE in transpose.hip (a definition here would put a
 //                               copy of each into every translation unit that includes this header)
 //   bitsFor / gridFor           key bits of a radix sort, the grid of a one-item-per-lane launch
+//   team_sync / clampOpt /      what the sparse product and the sparse sum share besides: the synchronisation of the lanes
+//   msSince                     of a row, an option with a default and a limit, wall milliseconds
 //   buildFail                   how a synchronous build step reports a failure and leaves
+//   SortedPath / sortedBatches  the general path of the sparse product and the sparse sum: batches of rows, one stable
+//   / sortedPass                sort per batch, a run kernel; enqueueNarrowIrp: their row pointers from a 64-bit scan.
+//                               Defined ONCE, in spgemm.hip, with the kernels they launch
 // rocPRIM is included here and nowhere else; its kernels are still instantiated by, and compiled into, each caller.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include <algorithm>
+#include <chrono>
 #include <cstdio>
+#include <functional>
+#include <vector>
 
 #include "kernels.hpp"
 
@@ -111,6 +119,49 @@ struct IncomingPattern {
 };
 struct DevMat;
 int buildIncoming(const DevMat* a, IncomingPattern& in, hipStream_t stream, const char* module);
+
+// The sorted path that the sparse product (spgemm.hip) and the sparse sum (add.hip) share; DESIGN.md sections 22 and 25.
+// A caller lists rows, counts the terms of each (terms[n] = 0) and calls sortedBatches: off[k] = the terms before row k
+// of the list, and the batches [batch[i], batch[i + 1]) of consecutive rows whose terms fit batchTerms (a row above the
+// budget is a batch of its own).  sortedPass then runs every batch: expand(k0, nRows, off + k0, key, val) is the caller's
+// own -- it enqueues what writes term f of row list[k0 + b] to off[k0 + b] - off[k0] + f as (b << 32 | column, rounded
+// term; no val when !numeric) in the order of its contract --, ONE stable radix sort, and a wavefront per row that
+// counts the run heads into counts[row] (!numeric) or lets the lane of each head add its run serially from +0.0 into c's
+// row at its rank (numeric; c's IRP is 4-byte).  Both synchronous; every temporary counts into `tally`.
+struct SortedPath {
+    const char* module;                             // for the error lines ("spgemm") ...
+    const char* items;                              // ... and what a term is there ("products")
+    TempTally* tally;
+    TempBuf off;
+    std::vector<uint64_t> hOff;
+    std::vector<uint32_t> batch;
+    SortedPath(const char* m, const char* i, TempTally* t) : module(m), items(i), tally(t), off(t) {}
+    size_t batches() const { return batch.empty() ? 0 : batch.size() - 1; }
+};
+using SortedExpand = std::function<void(uint32_t k0, uint32_t nRows, const uint64_t* off, uint64_t* key, double* val)>;
+int sortedBatches(SortedPath& s, const uint64_t* terms, uint32_t n, uint64_t batchTerms, hipStream_t stream);
+int sortedPass(SortedPath& s, bool numeric, const uint32_t* list, const SortedExpand& expand, uint32_t* counts, const DevMat* c,
+               hipStream_t stream);
+// irp[r] = (uint32_t)irp64[r] for r in [0, M], and *maxLen = max(*maxLen, the longest row)
+void enqueueNarrowIrp(uint64_t M, const uint64_t* irp64, uint32_t* irp, uint32_t* maxLen, hipStream_t stream);
+
+// The T lanes that share a row in the sparse product and the sparse sum synchronise here: a wavefront (T = 64; its LDS
+// operations execute in issue order, so a compiler fence is the whole synchronisation) or the workgroup.
+template <int T> __device__ __forceinline__ void team_sync() {
+    if constexpr (T == 64) {
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    } else {
+        __syncthreads();
+    }
+}
+
+// an option of a build: 0 asks for the default, a value above the limit is clamped to it
+inline uint64_t clampOpt(uint64_t v, uint64_t dflt, uint64_t limit) { return v == 0 ? dflt : std::min(v, limit); }
+inline double msSince(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
 
 // the bits that hold every key below n (at least 1, at most 32); every key in [0, maxKey] needs bitsFor(maxKey + 1)
 inline unsigned bitsFor(uint64_t n) {

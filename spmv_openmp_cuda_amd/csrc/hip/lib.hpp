@@ -104,19 +104,21 @@ inline DevMat* squareCsrOf(spmat* h, const char* who, const char* ell) {
 }
 
 // Provenance.  The makers record it with setOrigin; everything that takes a derived handle asks madeBy: was x (argument
-// xName) made as `want`, TRANSPOSE or later, from a (and, a product, from b, in that order)?  The refusal names the maker,
-// or the argument that is not the source.  a == null asks for the origin alone.
+// xName) made as `want`, TRANSPOSE or later, from a (and, a product or a sum, from b, in that order)?  The refusal names the
+// maker, or the argument that is not the source.  a == null asks for the origin alone.
 inline void setOrigin(DevMat* d, Origin o, const DevMat* a = nullptr, const DevMat* b = nullptr) {
     d->origin = o; d->src[0] = a ? a->id : 0; d->src[1] = b ? b->id : 0;
 }
 inline bool madeBy(const DevMat* x, Origin want, const DevMat* a, const DevMat* b, const char* who, const char* xName,
                    const char* aName = nullptr, const char* bName = nullptr) {
-    static const struct { const char* maker; const char* made; } texts[] = {     // TRANSPOSE .. HIERARCHY
-        {"spmvHipCsrTranspose", "transposed"}, {"spmvHipCsrPermute", "permuted"}, {"spmvHipSpGEMM", ""}, {"spmvHipAmgSetup", "set up"}};
+    static const struct { const char* maker; const char* made; } texts[] = {     // TRANSPOSE .. SUM
+        {"spmvHipCsrTranspose", "transposed"}, {"spmvHipCsrPermute", "permuted"}, {"spmvHipSpGEMM", ""}, {"spmvHipAmgSetup", "set up"},
+        {"spmvHipCsrAdd", ""}};
     const auto& text = texts[(int)want - (int)Origin::TRANSPOSE];
     if (x->origin != want) { ERR("%s: %s was not made by %s", who, xName, text.maker); return false; }
     if (!a || (a->id == x->src[0] && (!b || b->id == x->src[1]))) return true;
-    if (b) ERR("%s: (%s, %s) is not the pair, in its order, that %s is the product of", who, aName, bName, xName);
+    if (b && want == Origin::SUM) ERR("%s: (%s, %s) is not the pair, alpha with the first, that %s is the sum of", who, aName, bName, xName);
+    else if (b) ERR("%s: (%s, %s) is not the pair, in its order, that %s is the product of", who, aName, bName, xName);
     else ERR("%s: %s is not the handle %s was %s from", who, aName, xName, text.made);
     return false;
 }

@@ -19,6 +19,8 @@
 //      radix sort; a wavefront per row counts the run heads (symbolic) or lets one lane per head add its run
 //      serially from +0.0 (numeric).  The symbolic phase keeps nothing but the counts; the numeric phase expands again.
 // Every kernel of a row-list launch covers the count the host read; no kernel spins or waits on a flag.
+// The batching, the sort and the run kernel of the sorted path, and the narrowing of the row pointers, are what the sparse
+// sum (add.hip) needs too: they are declared in device_prims.hpp and defined here, once; the expansion is each caller's own.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <chrono>
@@ -131,17 +133,7 @@ __global__ __launch_bounds__(SG_THREADS) void sg_narrow_kernel(uint64_t M, const
 }
 
 // ------------------------------------------------------------------------------------------ the products of a row, in order
-// A team is the T lanes that share a row: a wavefront (T = 64; its LDS operations execute in issue order, so a compiler
-// fence is the whole synchronisation) or the workgroup.
-template <int T> __device__ __forceinline__ void team_sync() {
-    if constexpr (T == 64) {
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    } else {
-        __syncthreads();
-    }
-}
+// A team is the T lanes that share a row: a wavefront or the workgroup (team_sync of device_prims.hpp).
 template <int T> __device__ __forceinline__ bool team_any(bool v) {
     if constexpr (T == 64) {
         const bool r = __ballot(v) != 0;
@@ -379,17 +371,10 @@ struct Run {
     SpgemmPlan* plan;
     hipStream_t st;
     TempTally tm;                                              // every temporary of the call counts into it: tempBytes = its peak
-    // the sorted path: products before each of its rows, and the batches [batch[i], batch[i + 1]) of its list
-    TempBuf off{&tm};
-    std::vector<uint64_t> hOff;
-    std::vector<uint32_t> batch;
+    SortedPath sp{"spgemm", "products", &tm};                  // the products before each sorted row, and the batches of the list
 };
 
 int fail(hipStream_t st, const char* what) { return buildFail(st, "spgemm", what); }
-
-template <typename F> auto withBoth(const DevMat* a, const DevMat* b, F&& f) {
-    return withIrp(a, [&](auto ia) { return withIrp(b, [&](auto ib) { return f(ia, ib); }); });
-}
 
 // the two hash classes over their lists
 template <bool NUMERIC>
@@ -420,80 +405,104 @@ int sortedPrepare(Run& r) {
     const uint32_t n = pl->nSorted;
     if (!n) return EXIT_SUCCESS;
     const uint32_t* list = pl->list + pl->nWave + pl->nGroup;
-    TempBuf ubS(&r.tm), scanTmp(&r.tm), flag(&r.tm);
-    if (ubS.alloc(((size_t)n + 1) * 8) || r.off.alloc(((size_t)n + 1) * 8) || flag.alloc(4)) return fail(r.st, "temporary allocation (sorted rows)");
+    TempBuf ubS(&r.tm), flag(&r.tm);
+    if (ubS.alloc(((size_t)n + 1) * 8) || flag.alloc(4)) return fail(r.st, "temporary allocation (sorted rows)");
     if (hipMemsetAsync(ubS.p, 0, ((size_t)n + 1) * 8, r.st) != hipSuccess || hipMemsetAsync(flag.p, 0, 4, r.st) != hipSuccess) return fail(r.st, "memset");
     withBoth(r.a, r.b, [&](auto ia, auto ib) {
         hipLaunchKernelGGL((sg_ub_list_kernel<IrpT<decltype(ia)>, IrpT<decltype(ib)>>), gridFor(n, SG_THREADS / 64), dim3(SG_THREADS), 0, r.st, n,
                            list, ia, r.a->JA, ib, r.b->M, ubS.as<uint64_t>(), false, flag.as<uint32_t>());
         return 0;
     });
-    if (exclusiveScan(scanTmp, ubS.as<uint64_t>(), r.off.as<uint64_t>(), (uint64_t)0, (size_t)n + 1, r.st) != hipSuccess) return fail(r.st, "scan");
-    r.hOff.resize((size_t)n + 1);
-    if (hipMemcpyAsync(r.hOff.data(), r.off.p, r.hOff.size() * 8, hipMemcpyDeviceToHost, r.st) != hipSuccess ||
-        hipStreamSynchronize(r.st) != hipSuccess)
-        return fail(r.st, "sorted rows");
-    r.batch.assign(1, 0u);
-    for (uint32_t k = 0; k < n;) {                             // rows while their products fit; a row above the budget alone
+    return sortedBatches(r.sp, ubS.as<uint64_t>(), n, pl->batchProducts, r.st);
+}
+
+// the caller's half of the sorted path: the products of the rows list[k0 + b], b < nRows, in (p, q) order
+template <bool NUMERIC>
+int sortedClass(Run& r, uint32_t* counts, DevMat* c) {
+    const SpgemmPlan* pl = r.plan;
+    if (!pl->nSorted) return EXIT_SUCCESS;
+    const uint32_t* list = pl->list + pl->nWave + pl->nGroup;
+    return sortedPass(r.sp, NUMERIC, list, [&](uint32_t k0, uint32_t nRows, const uint64_t* off, uint64_t* key, double* val) {
+        withBoth(r.a, r.b, [&](auto ia, auto ib) {
+            hipLaunchKernelGGL((sg_expand_kernel<IrpT<decltype(ia)>, IrpT<decltype(ib)>, NUMERIC>), gridFor(nRows, 1), dim3(SG_THREADS), 0, r.st,
+                               nRows, list + k0, off, ia, r.a->JA, r.a->AS, ib, r.b->JA, r.b->AS, r.b->M, key, val);
+            return 0;
+        });
+    }, counts, c, r.st);
+}
+
+int numericPhase(Run& r, DevMat* c) {
+    if (hashPass<true>(r, nullptr, c) || sortedClass<true>(r, nullptr, c)) return EXIT_FAILURE;
+    if (hipStreamSynchronize(r.st) != hipSuccess) return fail(r.st, "numeric phase");
+    return EXIT_SUCCESS;
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------------- shared with add.hip (device_prims.hpp)
+// s.off[k] = the terms before row k of a sorted list of n rows (terms[n] is 0), read back; the batches: rows while their
+// terms fit batchTerms, a row above the budget alone
+int sortedBatches(SortedPath& s, const uint64_t* terms, uint32_t n, uint64_t batchTerms, hipStream_t st) {
+    TempBuf scanTmp(s.tally);
+    if (s.off.alloc(((size_t)n + 1) * 8)) return buildFail(st, s.module, "temporary allocation (sorted rows)");
+    if (exclusiveScan(scanTmp, terms, s.off.as<uint64_t>(), (uint64_t)0, (size_t)n + 1, st) != hipSuccess) return buildFail(st, s.module, "scan");
+    s.hOff.resize((size_t)n + 1);
+    if (hipMemcpyAsync(s.hOff.data(), s.off.p, s.hOff.size() * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+        return buildFail(st, s.module, "sorted rows");
+    s.batch.assign(1, 0u);
+    for (uint32_t k = 0; k < n;) {
         uint32_t e = k + 1;
-        while (e < n && r.hOff[e + 1] - r.hOff[k] <= pl->batchProducts) ++e;
-        r.batch.push_back(e);
+        while (e < n && s.hOff[e + 1] - s.hOff[k] <= batchTerms) ++e;
+        s.batch.push_back(e);
         k = e;
     }
     return EXIT_SUCCESS;
 }
 
-template <bool NUMERIC>
-int sortedPass(Run& r, uint32_t* counts, DevMat* c) {
-    const SpgemmPlan* pl = r.plan;
-    if (!pl->nSorted) return EXIT_SUCCESS;
-    const uint32_t* list = pl->list + pl->nWave + pl->nGroup;
+// every batch: the caller's expansion into (key, val), ONE stable sort, the run kernel (counts, or c's rows)
+int sortedPass(SortedPath& s, bool numeric, const uint32_t* list, const SortedExpand& expand, uint32_t* counts, const DevMat* c,
+               hipStream_t st) {
     uint64_t most = 0;
     uint32_t mostRows = 1;
-    for (size_t i = 0; i + 1 < r.batch.size(); ++i) {
-        most = std::max(most, r.hOff[r.batch[i + 1]] - r.hOff[r.batch[i]]);
-        mostRows = std::max(mostRows, r.batch[i + 1] - r.batch[i]);
+    for (size_t i = 0; i + 1 < s.batch.size(); ++i) {
+        most = std::max(most, s.hOff[s.batch[i + 1]] - s.hOff[s.batch[i]]);
+        mostRows = std::max(mostRows, s.batch[i + 1] - s.batch[i]);
     }
-    if (most >= (1ull << 40)) { fprintf(stderr, "libspmvhip: spgemm: a batch of %lu products is not supported\n", (unsigned long)most); return EXIT_FAILURE; }
-    TempBuf keyIn(&r.tm), keyOut(&r.tm), valIn(&r.tm), valOut(&r.tm), sortTmp(&r.tm);
-    if (keyIn.alloc(most * 8) || keyOut.alloc(most * 8) || (NUMERIC && (valIn.alloc(most * 8) || valOut.alloc(most * 8))))
-        return fail(r.st, "temporary allocation (products of a batch)");
+    if (most >= (1ull << 40)) {
+        fprintf(stderr, "libspmvhip: %s: a batch of %lu %s is not supported\n", s.module, (unsigned long)most, s.items);
+        return EXIT_FAILURE;
+    }
+    TempBuf keyIn(s.tally), keyOut(s.tally), valIn(s.tally), valOut(s.tally), sortTmp(s.tally);
+    if (keyIn.alloc(most * 8) || keyOut.alloc(most * 8) || (numeric && (valIn.alloc(most * 8) || valOut.alloc(most * 8))))
+        return buildFail(st, s.module, "temporary allocation (a sorted batch)");
     const unsigned endBit = 32 + bitsFor(mostRows);
-    for (size_t i = 0; i + 1 < r.batch.size(); ++i) {
-        const uint32_t k0 = r.batch[i], nRows = r.batch[i + 1] - k0;
-        const uint64_t nProd = r.hOff[k0 + nRows] - r.hOff[k0];
-        const uint64_t* off = r.off.as<uint64_t>() + k0;
-        withBoth(r.a, r.b, [&](auto ia, auto ib) {
-            hipLaunchKernelGGL((sg_expand_kernel<IrpT<decltype(ia)>, IrpT<decltype(ib)>, NUMERIC>), gridFor(nRows, 1), dim3(SG_THREADS), 0, r.st,
-                               nRows, list + k0, off, ia, r.a->JA, r.a->AS, ib, r.b->JA, r.b->AS, r.b->M, keyIn.as<uint64_t>(), valIn.as<double>());
-            return 0;
-        });
+    const uint32_t* irpC = c ? static_cast<const uint32_t*>(c->IRP) : nullptr;
+    for (size_t i = 0; i + 1 < s.batch.size(); ++i) {
+        const uint32_t k0 = s.batch[i], nRows = s.batch[i + 1] - k0;
+        const uint64_t nTerms = s.hOff[k0 + nRows] - s.hOff[k0];
+        const uint64_t* off = s.off.as<uint64_t>() + k0;
+        expand(k0, nRows, off, keyIn.as<uint64_t>(), valIn.as<double>());
         // (sortTmp is shared by the batches: it grows, after a wait for the batch before, only when one needs more)
-        const hipError_t e = NUMERIC ? sortPairs(sortTmp, keyIn.as<uint64_t>(), keyOut.as<uint64_t>(), valIn.as<double>(), valOut.as<double>(),
-                                                 (size_t)nProd, 0u, endBit, r.st)
-                                     : sortKeys(sortTmp, keyIn.as<uint64_t>(), keyOut.as<uint64_t>(), (size_t)nProd, 0u, endBit, r.st);
-        if (e != hipSuccess) return fail(r.st, "sort");
-        hipLaunchKernelGGL((sg_runs_kernel<NUMERIC>), gridFor(nRows, SG_THREADS / 64), dim3(SG_THREADS), 0, r.st, nRows, list + k0, off,
-                           keyOut.as<uint64_t>(), valOut.as<double>(), counts, c ? static_cast<const uint32_t*>(c->IRP) : nullptr,
-                           c ? c->JA : nullptr, c ? c->AS : nullptr);
+        const hipError_t e = numeric ? sortPairs(sortTmp, keyIn.as<uint64_t>(), keyOut.as<uint64_t>(), valIn.as<double>(), valOut.as<double>(),
+                                                 (size_t)nTerms, 0u, endBit, st)
+                                     : sortKeys(sortTmp, keyIn.as<uint64_t>(), keyOut.as<uint64_t>(), (size_t)nTerms, 0u, endBit, st);
+        if (e != hipSuccess) return buildFail(st, s.module, "sort");
+        if (numeric)
+            hipLaunchKernelGGL((sg_runs_kernel<true>), gridFor(nRows, SG_THREADS / 64), dim3(SG_THREADS), 0, st, nRows, list + k0, off,
+                               keyOut.as<uint64_t>(), valOut.as<double>(), counts, irpC, c ? c->JA : nullptr, c ? c->AS : nullptr);
+        else
+            hipLaunchKernelGGL((sg_runs_kernel<false>), gridFor(nRows, SG_THREADS / 64), dim3(SG_THREADS), 0, st, nRows, list + k0, off,
+                               keyOut.as<uint64_t>(), valOut.as<double>(), counts, irpC, c ? c->JA : nullptr, c ? c->AS : nullptr);
     }
-    if (hipGetLastError() != hipSuccess) return fail(r.st, "sorted path kernels");
-    if (hipStreamSynchronize(r.st) != hipSuccess) return fail(r.st, "sorted path");
+    if (hipGetLastError() != hipSuccess) return buildFail(st, s.module, "sorted path kernels");
+    if (hipStreamSynchronize(st) != hipSuccess) return buildFail(st, s.module, "sorted path");
     return EXIT_SUCCESS;
 }
 
-int numericPhase(Run& r, DevMat* c) {
-    if (hashPass<true>(r, nullptr, c) || sortedPass<true>(r, nullptr, c)) return EXIT_FAILURE;
-    if (hipStreamSynchronize(r.st) != hipSuccess) return fail(r.st, "numeric phase");
-    return EXIT_SUCCESS;
+void enqueueNarrowIrp(uint64_t M, const uint64_t* irp64, uint32_t* irp, uint32_t* maxLen, hipStream_t st) {
+    hipLaunchKernelGGL(sg_narrow_kernel, gridFor(M + 1), dim3(SG_THREADS), 0, st, M, irp64, irp, maxLen);
 }
-
-uint64_t clampOpt(uint64_t v, uint64_t dflt, uint64_t limit) { return v == 0 ? dflt : std::min(v, limit); }
-double msSince(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
-}  // namespace
 
 void freeSpgemmPlan(SpgemmPlan* p) {
     if (!p) return;
@@ -561,7 +570,7 @@ int spgemmBuild(const DevMat* a, const DevMat* b, const spmvSpgemmOpts* opts, De
         TempBuf counts(&r.tm), irp64(&r.tm), scanTmp(&r.tm);
         if (counts.alloc((M + 1) * 4) || irp64.alloc((M + 1) * 8)) return fail(st, "temporary allocation (12 B per row)");
         if (hipMemsetAsync(counts.p, 0, (M + 1) * 4, st) != hipSuccess || hipMemsetAsync(dCnt, 0, 4, st) != hipSuccess) return fail(st, "memset");
-        if (sortedPrepare(r) || hashPass<false>(r, counts.as<uint32_t>(), nullptr) || sortedPass<false>(r, counts.as<uint32_t>(), nullptr))
+        if (sortedPrepare(r) || hashPass<false>(r, counts.as<uint32_t>(), nullptr) || sortedClass<false>(r, counts.as<uint32_t>(), nullptr))
             return EXIT_FAILURE;
         if (exclusiveScan(scanTmp, counts.as<uint32_t>(), irp64.as<uint64_t>(), (uint64_t)0, (size_t)M + 1, st) != hipSuccess) return fail(st, "scan");
         if (hipMemcpyAsync(&nnzC, irp64.as<uint64_t>() + M, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
@@ -572,7 +581,7 @@ int spgemmBuild(const DevMat* a, const DevMat* b, const spmvSpgemmOpts* opts, De
             return EXIT_FAILURE;
         }
         uint32_t maxLen = 0;
-        hipLaunchKernelGGL(sg_narrow_kernel, gridFor(M + 1), dim3(SG_THREADS), 0, st, M, irp64.as<uint64_t>(), static_cast<uint32_t*>(c->IRP), dCnt);
+        enqueueNarrowIrp(M, irp64.as<uint64_t>(), static_cast<uint32_t*>(c->IRP), dCnt, st);
         if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&maxLen, dCnt, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
             hipStreamSynchronize(st) != hipSuccess)
             return fail(st, "row pointers");
@@ -590,7 +599,7 @@ int spgemmBuild(const DevMat* a, const DevMat* b, const spmvSpgemmOpts* opts, De
     out.numericMs = msSince(t1);
     out.nnzC = nnzC;
     out.rowsWave = pl->nWave; out.rowsGroup = pl->nGroup; out.rowsSorted = pl->nSorted;
-    out.sortBatches = r.batch.empty() ? 0 : r.batch.size() - 1;
+    out.sortBatches = r.sp.batches();
     out.tempBytes = r.tm.peak;
     out.ms = msSince(t0);
     pl->info = out;
@@ -607,7 +616,7 @@ int spgemmRefresh(DevMat* c, const DevMat* a, const DevMat* b, spmvSpgemmInfo* i
     spmvSpgemmInfo out = pl->info;
     out.symbolicMs = 0;
     out.numericMs = out.ms = msSince(t0);
-    out.sortBatches = r.batch.empty() ? 0 : r.batch.size() - 1;
+    out.sortBatches = r.sp.batches();
     out.tempBytes = r.tm.peak;
     pl->info = out;
     if (info) *info = out;

@@ -68,6 +68,7 @@ void freeDesc(DevMat* d) {
     (void)hipFree(d->blkInfo); (void)hipFree(d->blkBase); (void)hipFree(d->tmap);
     freeTri(d->tri[0]); freeTri(d->tri[1]);
     freeSpgemmPlan(d->prod);
+    freeAddPlan(d->sum);
     freeAmg(d->amg);
     freeTiles(d->tiles[0]); freeTiles(d->tiles[1]);
     freeSell(d->sell);
@@ -518,6 +519,52 @@ int spmvHipSpGEMMRefresh(spmat* dC, spmat* dA, spmat* dB, spmvSpgemmInfo* info) 
     if (!c || !a || !b || !madeBy(c, Origin::PRODUCT, a, b, who, "dC", "dA", "dB")) return EXIT_FAILURE;
     spmvSpgemmInfo out{};
     if (spgemmRefresh(c, a, b, &out, S.stream)) { ERR("%s: recomputing the values failed", who); return EXIT_FAILURE; }
+    if (updateValues(dC, nullptr, true, true, S.stream, who)) return EXIT_FAILURE;
+    if (info) *info = out;
+    return EXIT_SUCCESS;
+}
+
+// C = alpha A + beta B as a handle of its own (add.hip builds the arrays; the contract is in spmvHip.h, the design in DESIGN.md
+// section 25).  Refusals come first; dC and info are written only on success.
+int spmvHipCsrAdd(double alpha, spmat* dA, double beta, spmat* dB, const spmvAddOpts* opts, spmat* dC, spmvAddInfo* info) {
+    const char* who = "spmvHipCsrAdd";
+    if (!ready(who)) return EXIT_FAILURE;
+    if (!dA || !dB || !dC) { ERR("%s: %s is NULL", who, !dA ? "dA" : !dB ? "dB" : "dC"); return EXIT_FAILURE; }
+    if (dC == dA || dC == dB) { ERR("%s: dC is a source handle itself", who); return EXIT_FAILURE; }
+    DevMat* a = descOf(dA, who);
+    DevMat* b = a ? descOf(dB, who) : nullptr;
+    if (!a || !b) return EXIT_FAILURE;
+    if (!csrOnly(a, who, "dA is an ELL handle (only CSR handles can be added)") ||
+        !csrOnly(b, who, "dB is an ELL handle (only CSR handles can be added)"))
+        return EXIT_FAILURE;
+    if (a->M != b->M || a->N != b->N) {
+        ERR("%s: A is %lu x %lu, B is %lu x %lu", who, (unsigned long)a->M, (unsigned long)a->N, (unsigned long)b->M, (unsigned long)b->N);
+        return EXIT_FAILURE;
+    }
+    if (a->M >= (1ull << 32) - 1 || a->N >= (1ull << 32) - 1) {
+        ERR("%s: M=%lu, N=%lu: the sum has 32-bit row and column ids", who, (unsigned long)a->M, (unsigned long)a->N);
+        return EXIT_FAILURE;
+    }
+    if ((a->NZ && (!a->JA || !a->AS)) || (b->NZ && (!b->JA || !b->AS))) { ERR("%s: a source has no column or value array", who); return EXIT_FAILURE; }
+    DevMat* c = new DevMat;
+    c->M = a->M; c->N = a->N;
+    setOrigin(c, Origin::SUM, a, b);
+    spmvAddInfo out{};
+    if (finishCsr(dC, c, !addBuild(alpha, a, beta, b, opts, c, &out, S.stream))) { ERR("%s: building the sum failed", who); return EXIT_FAILURE; }
+    if (info) *info = out;
+    return EXIT_SUCCESS;
+}
+
+int spmvHipCsrAddRefresh(spmat* dC, double alpha, spmat* dA, double beta, spmat* dB, spmvAddInfo* info) {
+    const char* who = "spmvHipCsrAddRefresh";
+    if (!ready(who)) return EXIT_FAILURE;
+    if (!dA || !dB || !dC) { ERR("%s: %s is NULL", who, !dC ? "dC" : !dA ? "dA" : "dB"); return EXIT_FAILURE; }
+    DevMat* c = descOf(dC, who);
+    DevMat* a = c ? descOf(dA, who) : nullptr;
+    DevMat* b = a ? descOf(dB, who) : nullptr;
+    if (!c || !a || !b || !madeBy(c, Origin::SUM, a, b, who, "dC", "dA", "dB")) return EXIT_FAILURE;
+    spmvAddInfo out{};
+    if (addRefresh(c, alpha, a, beta, b, &out, S.stream)) { ERR("%s: recomputing the values failed", who); return EXIT_FAILURE; }
     if (updateValues(dC, nullptr, true, true, S.stream, who)) return EXIT_FAILURE;
     if (info) *info = out;
     return EXIT_SUCCESS;
