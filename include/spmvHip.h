@@ -182,6 +182,35 @@ typedef struct {
 int spmvHipTriAnalyse(spmat* dA, int uplo);
 int hipSpTRSVCSR(spmat* dA, int uplo, int diag, const double* dB, double* dX);
 int spmvHipTriInfo(spmat* dA, int uplo, spmvTriInfo* info);
+/* hipSpTRSMCSR: X = T^-1 B for a block of k right-hand sides, all columns in one pass over the triangle.  DESIGN.md section
+ * 26.  B and X are M x k on the device, each in its own layout with its own leading dimension, exactly those of
+ * hipSpMMRowsCSR below: SPMV_DENSE_ROW_MAJOR (0, element (i, c) at P[i*ld + c], ld >= k) or SPMV_DENSE_COL_MAJOR (1,
+ * element (i, c) at P[c*ld + i], ld >= M).
+ *   Bits: column c of X has the bits of hipSpTRSVCSR(dA, uplo, diag, B[:, c], .), i.e. of the loop above applied per
+ *   column: rows in order, strict-triangle products rounded and added in stored order from +0.0, entries outside the
+ *   triangle skipped (never added as 0.0), then (b - acc), divided by the stored diagonal unless diag is UNIT.  Unsorted rows
+ *   and repeated pairs behave as in the single solve; a zero stored diagonal gives +-Inf or NaN and propagates as in the
+ *   loop; unit-value handles take the value from a register.  Columns are independent: an Inf or NaN in one column never
+ *   reaches another.
+ *   Width: any k >= 1.  Columns are taken in panels of at most 16, and all panels of a level go in ONE launch: a k-column
+ *   solve enqueues exactly spmvTriInfo.launches launches, whatever k is.  (k = 1 with unit strides runs the single solve.)
+ *   In place: dB == dX with equal layout and equal leading dimension is allowed (a row reads B only at its own (i, c) and
+ *   writes X only there).  Any other overlap of the two address spans is refused, the same pointer with another layout or
+ *   leading dimension included; the check is made on the host.
+ *   Padding: elements of X outside the M x k block are never written (nor read), those of B never read.
+ *   Schedule: the TriSchedule of the handle, shared with hipSpTRSVCSR: the first call on an unanalysed triangle analyses
+ *   it, a later hipSpTRSVCSR reuses that analysis and the other way round (spmvTriInfo.analyses stays 1);
+ *   spmvHipUpdateValues, spmvHipValuesChanged and spmvHipTransposeRefresh keep it, values are read live.
+ *   Launch: kernels only, on the library stream; no allocation and no host sync once the triangle is analysed, so the
+ *   solve can be captured into a graph after spmvHipTriAnalyse.  With spmvHipSetSync(1) it waits and sets
+ *   spmvHipLastKernelSeconds (the whole solve) and spmvHipLastLaunch (the last launch); with spmvHipSetSync(0) it only
+ *   enqueues.  M = 0 succeeds and writes nothing.
+ * Refused with a message and EXIT_FAILURE, X untouched: NULL pointers, or a handle that is not live; ELL handles; M != N;
+ *   an unknown uplo, diag or layout; k = 0; a leading dimension too small for its layout; NZ >= IRP32_LIMIT or M >= 2^31;
+ *   STORED when firstBadDiag >= 0 (the message names the row); a handle with entries and no value array that is not
+ *   unit-value; the overlaps above; a multigrid hierarchy handle. */
+int hipSpTRSMCSR(spmat* dA, int uplo, int diag, unsigned k, const double* dB, size_t ldb, int bLayout,
+                 double* dX, size_t ldx, int xLayout);
 /* ------------------------------------------------------------- incomplete factorisation */
 /* hipSpILU0CSR overwrites the values of a square device CSR handle with its ILU(0) factors, in place: the strictly lower
  * part becomes L (unit diagonal, not stored), the diagonal and the upper part U, so that hipSpTRSVCSR(LOWER, UNIT) then

@@ -104,6 +104,7 @@ _sigs = {
     "spmvHipTriAnalyse": ([C.POINTER(spmat), _i], _i),
     "hipSpTRSVCSR": ([C.POINTER(spmat), _i, _i, _vp, _vp], _i),
     "spmvHipTriInfo": ([C.POINTER(spmat), _i, _vp], _i),
+    "hipSpTRSMCSR": ([C.POINTER(spmat), _i, _i, C.c_uint, _vp, _sz, _i, _vp, _sz, _i], _i),
     "hipSpILU0CSR": ([C.POINTER(spmat)], _i),
     "spmvHipIlu0Info": ([C.POINTER(spmat), _vp], _i),
     "spmvHipDot": ([_sz, _vp, _vp, _vp], _i),
@@ -418,7 +419,7 @@ class _Operands:
             h = np.ascontiguousarray(X, dtype=np.float64)
             self.args.append((h, 0))
             return k, SPMV_DENSE_ROW_MAJOR, k
-        layout, ld = _dense_layout(X, name)
+        layout, ld = _dense_layout(X, name, self.who)
         self.args.append(X.data_ptr())
         return k, layout, ld
 
@@ -474,7 +475,7 @@ class _Operands:
             out = init[1].clone()
         self.res = out
         self.args.append(out.data_ptr())
-        return _dense_layout(out, name) if len(shape) == 2 else None
+        return _dense_layout(out, name, self.who) if len(shape) == 2 else None
 
     def value(self):
         """after the C call: the result tensor, or the host call's result downloaded (nothing is copied for an empty one)"""
@@ -852,6 +853,21 @@ class DeviceMatrix:
             _check(lib.hipSpTRSVCSR(C.byref(self.handle), uplo, diag, *ops.args), "hipSpTRSVCSR")
             return ops.value()
 
+    def solve_triangular_block(self, B, lower=True, unit_diagonal=False, out=None):
+        """hipSpTRSMCSR: X = T^-1 B for a block of right-hand sides in one pass over the triangle, column c of X with the bits
+        of solve_triangular on column c of B.  B is (N, k) float64: a device torch tensor with unit stride in one dimension
+        (the rules of matmul's X) -> a torch tensor, `out` if given (same rules, its own layout; `out` may be `B`: an
+        in-place solve); or a numpy array -> uploaded, solved, returned as numpy.  Runs on the library stream."""
+        N = int(self.handle.N)
+        uplo = SPMV_TRI_LOWER if lower else SPMV_TRI_UPPER
+        diag = SPMV_DIAG_UNIT if unit_diagonal else SPMV_DIAG_STORED
+        with _Operands("solve_triangular_block", B) as ops:
+            k, bl, ldb = ops.dense("B", B, N)
+            xl, ldx = ops.result("out", out, (N, k))
+            db, dx = ops.args
+            _check(lib.hipSpTRSMCSR(C.byref(self.handle), uplo, diag, k, db, ldb, bl, dx, ldx, xl), "hipSpTRSMCSR")
+            return ops.value()
+
     def ilu0(self) -> "spmvIluInfo":
         """hipSpILU0CSR: overwrite this square matrix's values with its ILU(0) factors in place (L strictly lower with a unit
         diagonal, U the diagonal and above), with the bits of the serial loop (include/spmvHip.h); returns ilu0_info()."""
@@ -991,17 +1007,17 @@ def permute_vector(perm, v, inverse=False, out=None):
         return ops.value()
 
 
-def _dense_layout(t, what):
+def _dense_layout(t, what, who="matmul"):
     """(layout, leading dimension) of a 2-D float64 device tensor of shape (rows, k) with unit stride in one dimension"""
     torch = _torch()
     if t.dtype != torch.float64 or not t.is_cuda:
-        raise SpmvHipError(f"matmul: {what} must be a float64 tensor on the device")
+        raise SpmvHipError(f"{who}: {what} must be a float64 tensor on the device")
     (rows, k), (s0, s1) = t.shape, t.stride()
     if (s1 == 1 or k == 1) and s0 >= k:
         return SPMV_DENSE_ROW_MAJOR, s0
     if (s0 == 1 or rows == 1) and s1 >= rows:
         return SPMV_DENSE_COL_MAJOR, s1
-    raise SpmvHipError(f"matmul: {what} needs unit stride in one dimension (strides {t.stride()})")
+    raise SpmvHipError(f"{who}: {what} needs unit stride in one dimension (strides {t.stride()})")
 
 
 def spMatCpyCSR(host: HostCSR) -> DeviceMatrix:

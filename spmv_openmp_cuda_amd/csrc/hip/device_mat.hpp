@@ -238,6 +238,11 @@ int  enqueueTrsv(const DevMat* d, int uplo, int diag, const double* b, double* x
                  const uint32_t* stop = nullptr);
 void triInfo(const DevMat* d, int uplo, spmvTriInfo* out);
 void freeTri(TriSchedule* s);
+// X = T^-1 B for k columns on the analysed triangle's schedule (trsm.hip; contract in spmvHip.h, design in DESIGN.md section
+// 26): B(i, c) at B[i*sbr + c*sbc], X(i, c) at X[i*ldx + c] (xRowMajor) or X[c*ldx + i]; as many launches as enqueueTrsv
+// makes, whatever k is, on `stream`, no allocation, no sync; reports the last launch.  The caller has checked the arguments.
+int  enqueueTrsm(const DevMat* d, int uplo, int diag, uint32_t k, const double* B, uint64_t sbr, uint64_t sbc, double* X,
+                 uint64_t ldx, bool xRowMajor, hipStream_t stream, dim3* grid, dim3* block);
 // ILU(0) in place on the lower schedule d->tri[SPMV_TRI_LOWER] (ilu0.hip; contract in spmvHip.h, design in DESIGN.md section
 // 18).  iluUnsortedRow: the first row that is not strictly ascending, or -1 (synchronous).  iluFactor: the factorisation's
 // launches on `stream` for the checked handle, then the zero-pivot read-back (synchronous); groupWidth 8, 16 or 64 lanes

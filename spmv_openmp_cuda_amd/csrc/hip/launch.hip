@@ -214,14 +214,6 @@ int spmvHipEnqueueCSR(spmat* dMat, int warpPerRow, double* dX, double* dY, void*
 }
 
 // ---- blocks of vectors: Y = A X (contract in spmvHip.h, design in DESIGN.md section 15)
-// bytes spanned by a dense rows x k block in `layout` with leading dimension ld (0 for an empty block)
-static unsigned __int128 denseSpan(uint64_t rows, unsigned k, size_t ld, int layout) {
-    if (rows == 0) return 0;
-    const unsigned __int128 last = layout == SPMV_DENSE_ROW_MAJOR ? (unsigned __int128)(rows - 1) * ld + (k - 1)
-                                                                   : (unsigned __int128)(k - 1) * ld + (rows - 1);
-    return (last + 1) * sizeof(double);
-}
-
 int hipSpMMRowsCSR(spmat* dMat, unsigned k, const double* dX, size_t ldx, int xLayout, double* dY, size_t ldy, int yLayout) {
     const char* who = "hipSpMMRowsCSR";
     const Ctx cx = libraryCtx();

@@ -129,6 +129,14 @@ inline bool overlaps(const void* p, const void* q, uint64_t bytes) {
     return bytes && p0 < q0 + bytes && q0 < p0 + bytes;
 }
 
+// bytes spanned by a dense rows x k block in `layout` with leading dimension ld (0 for an empty block)
+inline unsigned __int128 denseSpan(uint64_t rows, unsigned k, size_t ld, int layout) {
+    if (rows == 0) return 0;
+    const unsigned __int128 last = layout == SPMV_DENSE_ROW_MAJOR ? (unsigned __int128)(rows - 1) * ld + (k - 1)
+                                                                   : (unsigned __int128)(k - 1) * ld + (rows - 1);
+    return (last + 1) * sizeof(double);
+}
+
 // timing bracket used by every launcher
 struct Launch {
     const Ctx cx;

@@ -66,6 +66,57 @@ int hipSpTRSVCSR(spmat* dA, int uplo, int diag, const double* dB, double* dX) {
     return L.finish(who);
 }
 
+// a block of right-hand sides (contract in spmvHip.h, design in DESIGN.md section 26)
+int hipSpTRSMCSR(spmat* dA, int uplo, int diag, unsigned k, const double* dB, size_t ldb, int bLayout, double* dX, size_t ldx,
+                 int xLayout) {
+    const char* who = "hipSpTRSMCSR";
+    const Ctx cx = libraryCtx();
+    DevMat* d = triHandle(dA, uplo, who);
+    if (!d) return EXIT_FAILURE;
+    if (!dB || !dX) { ERR("%s: %s is NULL", who, !dB ? "dB" : "dX"); return EXIT_FAILURE; }
+    if (diag != SPMV_DIAG_STORED && diag != SPMV_DIAG_UNIT) { ERR("%s: unknown diag %d", who, diag); return EXIT_FAILURE; }
+    if (k == 0) { ERR("%s: k = 0 columns", who); return EXIT_FAILURE; }
+    for (int layout : {bLayout, xLayout})
+        if (layout != SPMV_DENSE_ROW_MAJOR && layout != SPMV_DENSE_COL_MAJOR) { ERR("%s: unknown layout %d", who, layout); return EXIT_FAILURE; }
+    // ld >= k (row-major) or >= M (column-major)
+    const uint64_t needB = bLayout == SPMV_DENSE_ROW_MAJOR ? k : d->M, needX = xLayout == SPMV_DENSE_ROW_MAJOR ? k : d->M;
+    if (ldb < needB || ldx < needX) {
+        ERR("%s: leading dimension %s = %zu is below %lu", who, ldb < needB ? "ldb" : "ldx", ldb < needB ? ldb : ldx,
+            (unsigned long)(ldb < needB ? needB : needX));
+        return EXIT_FAILURE;
+    }
+    // in place is the same block: a row reads B only at its own (i, c) and writes X only there; anything else that shares
+    // memory is refused
+    if (!(dB == dX && bLayout == xLayout && ldb == ldx)) {
+        const unsigned __int128 spanB = denseSpan(d->M, k, ldb, bLayout), spanX = denseSpan(d->M, k, ldx, xLayout);
+        const unsigned __int128 b0 = (uintptr_t)dB, x0 = (uintptr_t)dX;
+        if (spanB && spanX && b0 < x0 + spanX && x0 < b0 + spanB) {
+            ERR("%s: dB and dX overlap without being the same block (same pointer, layout and leading dimension)", who);
+            return EXIT_FAILURE;
+        }
+    }
+    if (d->M == 0) return nothingToLaunch(cx, d, nullptr);
+    if (d->NZ && !d->AS && !d->unit) { ERR("%s: the handle has no value array", who); return EXIT_FAILURE; }
+    if (!d->tri[uplo] && triAnalyse(d, uplo, S.triRunRows, cx.stream)) { ERR("%s: the analysis failed", who); return EXIT_FAILURE; }
+    spmvTriInfo info;
+    triInfo(d, uplo, &info);
+    if (diag == SPMV_DIAG_STORED && info.firstBadDiag >= 0) {
+        ERR("%s: row %ld does not hold exactly one stored diagonal entry (SPMV_DIAG_STORED needs one in every row)", who,
+            info.firstBadDiag);
+        return EXIT_FAILURE;
+    }
+    const bool bRow = bLayout == SPMV_DENSE_ROW_MAJOR, xRow = xLayout == SPMV_DENSE_ROW_MAJOR;
+    const uint64_t sbr = bRow ? ldb : 1, sbc = bRow ? 1 : ldb;
+    Launch L(cx, dim3(1), dim3(1));
+    dim3 grid(1), block(1);
+    const int rc = k == 1 && sbr == 1 && (xRow ? ldx : 1) == 1      // one plain vector: the single solve
+                       ? enqueueTrsv(d, uplo, diag, dB, dX, cx.stream, &grid, &block)
+                       : enqueueTrsm(d, uplo, diag, k, dB, sbr, sbc, dX, ldx, xRow, cx.stream, &grid, &block);
+    if (rc) { ERR("%s: launch failed", who); return EXIT_FAILURE; }
+    L.shape(grid, block);
+    return L.finish(who);
+}
+
 int spmvHipTriInfo(spmat* dA, int uplo, spmvTriInfo* info) {
     const char* who = "spmvHipTriInfo";
     DevMat* d = descOf(dA, who);
