@@ -338,6 +338,61 @@ typedef struct {
 int spmvHipDot(size_t n, const double* dU, const double* dV, double* dResult);
 int hipSpCGCSR(spmat* dA, spmat* dM, const double* dB, double* dX, const spmvKrylovOpts* opts, spmvKrylovInfo* info);
 int hipSpBiCGStabCSR(spmat* dA, spmat* dM, const double* dB, double* dX, const spmvKrylovOpts* opts, spmvKrylovInfo* info);
+/* Blocks of right-hand sides.  DESIGN.md section 27.
+ *
+ * spmvHipBlockDot: dH[c] (k doubles on the device) = U(:, c) . V(:, c) for c = 0 .. k-1 in one pass.  U and V are n x k on
+ * the device, each in its own layout with its own leading dimension, exactly those of hipSpMMRowsCSR:
+ * SPMV_DENSE_ROW_MAJOR (element (i, c) at P[i*ld + c], ld >= k) or SPMV_DENSE_COL_MAJOR (P[c*ld + i], ld >= n).  Every
+ * dH[c] is bit for bit spmvHipDot(n, U(:, c), V(:, c)): the same blocks of 4096 indices, the same lane order (indices
+ * 512 s + 2 t and 512 s + 2 t + 1, s ascending), the same 256-lane tree and the same second level -- whatever k, the
+ * layouts, the leading dimensions and the alignment of the pointers are (16-byte accesses are used where a block allows
+ * them: row-major, even leading dimension, even k, 16-byte aligned; the bits do not depend on it).  U == V is allowed;
+ * n = 0 gives k times +0.0.  Kernels only, on the library stream; the block partials go to the library's dot workspace
+ * (here (k rounded up to even) * ceil(n / 4096) doubles), so a call can be captured once the workspace is large enough, as
+ * spmvHipDot.  spmvHipSetSync as for spmvHipDot.  Refused (EXIT_FAILURE): a NULL dH, a NULL dU or dV when n > 0, k = 0, an
+ * unknown layout, a leading dimension too small for its layout.
+ *
+ * hipSpCGBlockCSR / hipSpBiCGStabBlockCSR: k independent solves A x_c = b_c advanced in lock step -- not a block Krylov
+ * method: no Krylov space is shared.  B and X are M x k on the device, each in its own layout and leading dimension (the
+ * rules of hipSpTRSMCSR); X holds X0 on entry.  One opts.tol and one opts.maxIter apply to every column; the threshold is
+ * the column's own, tol2 * dot(b_c, b_c).  cols is NULL or k host records; opts.history is NULL or k * (maxIter + 1) host
+ * doubles, column c's history at history + c * (maxIter + 1), of which only hist[0 .. iterations_c] is written.
+ *   Bits: for every column c, X(:, c), cols[c].status, .iterations, .rr, .bb and the column's history are the bits of
+ *   hipSpCGCSR / hipSpBiCGStabCSR on (dA, dM, B(:, c), X0(:, c)) -- the loops written out above.  A column that has
+ *   stopped is frozen: its x is the loop's x however many more iterations its neighbours run and however far a batch of K
+ *   iterations overshoots; BiCGStab's half-step write x = x + alpha*phat is made per column.  Columns are independent: a
+ *   NaN, an Inf or a breakdown in one never reaches another.  Elements of X outside the M x k block are never written; B
+ *   is only read.
+ *   info: status is the largest column status, iterations the largest column count, rr and bb those of the
+ *   lowest-numbered column that has info.status; launches, hostChecks and ms as in the single solves.  info.launches does
+ *   not depend on k: an iteration is one hipSpMMRowsCSR pass (counted as one, also for k > 16), the two hipSpTRSMCSR
+ *   passes of dM, and one launch per fused pass and per scalar step, each covering all columns.
+ *   dM: NULL, or an ILU(0) handle, applied as hipSpTRSMCSR(LOWER, UNIT) then (UPPER, STORED); dM == dA is allowed.  A
+ *   multigrid hierarchy is refused: its cycle is single-vector.
+ *   Execution: one state block per column on the device; one finish launch runs every column's scalar step; every kernel
+ *   that writes x, r, p, s or a column's state leaves a stopped column alone.  A word that is set when the last column
+ *   stops is what the host reads once per K iterations (spmvHipSetVariant("hipSpCGBlockCSR" / "hipSpBiCGStabBlockCSR", K),
+ *   1 <= K <= 4096, default 16) and what the triangular passes take as their stop pointer; it is also read once after the
+ *   init, so a block whose columns all stop there enqueues no further kernel.  Workspace (the vectors of the single solve
+ *   times k rounded up to even, the partials, the states, the history) is allocated by the call and freed before it
+ *   returns.  Synchronous, on the library stream; not capturable.  M = 0 succeeds: every column CONVERGED, 0, no kernel;
+ *   history + c * (maxIter + 1) receives +0.0.  (k = 1 with unit strides runs the single solve, at the block's K.)
+ * Returns EXIT_SUCCESS whatever the statuses (cols and info may be NULL).  Refused with a message and EXIT_FAILURE, X
+ *   untouched: what the single solves refuse; k = 0, an unknown layout, a leading dimension too small for its layout, any
+ *   overlap of the address spans of B and X (the checks of hipSpTRSMCSR); a history of k * (maxIter + 1) doubles
+ *   overflowing; a multigrid hierarchy as dM. */
+typedef struct {
+    int    status;          /* SPMV_KRYLOV_* of this column                                  */
+    ulong  iterations;
+    double rr;              /* the last squared residual the column's loop computed          */
+    double bb;              /* dot(b_c, b_c)                                                 */
+} spmvKrylovColumn;
+int spmvHipBlockDot(size_t n, unsigned k, const double* dU, size_t ldu, int uLayout, const double* dV, size_t ldv, int vLayout,
+                    double* dH);
+int hipSpCGBlockCSR(spmat* dA, spmat* dM, unsigned k, const double* dB, size_t ldb, int bLayout, double* dX, size_t ldx,
+                    int xLayout, const spmvKrylovOpts* opts, spmvKrylovColumn* cols, spmvKrylovInfo* info);
+int hipSpBiCGStabBlockCSR(spmat* dA, spmat* dM, unsigned k, const double* dB, size_t ldb, int bLayout, double* dX, size_t ldx,
+                          int xLayout, const spmvKrylovOpts* opts, spmvKrylovColumn* cols, spmvKrylovInfo* info);
 /* spmvHipMultiDot: dH[i] (k doubles on the device) = V(:, i) . w for i = 0 .. k-1 in one pass over w, column i of V at
  * dV + i*ldv (ldv >= n).  Every dH[i] is bit for bit spmvHipDot(n, dV + i*ldv, dW): the same blocks of 4096 indices, the
  * same lane order, the same tree and the same second level -- whatever k, ldv and the alignment of the pointers are
@@ -953,6 +1008,8 @@ int spmvHipProbeLdsAtomicOrder(void);
  *   hipSpILU0CSR              8, 16 or 64: the lanes that factor one row (default 16).  AS does not change by a bit.
  *   hipSpCGCSR, hipSpBiCGStabCSR  K, 1..4096: iterations enqueued per read-back of the solver's device state
  *                             (default 16).  x does not change by a bit.
+ *   hipSpCGBlockCSR, hipSpBiCGStabBlockCSR  K, 1..4096: iterations enqueued per read-back of the block's all-stopped
+ *                             word (default 16).  No column changes by a bit.
  *   hipSpGMRESCSR             0 or 1: 1 folds the first CGS2 update into the partials of the second projection
  *                             (default 0).  x does not change by a bit.
  *   spmvHipColourCSR          K, 1..4096: rounds enqueued per read-back of the colouring's device state (default 16,

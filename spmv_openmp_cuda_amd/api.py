@@ -111,6 +111,9 @@ _sigs = {
     "hipSpCGCSR": ([C.POINTER(spmat), C.POINTER(spmat), _vp, _vp, _vp, _vp], _i),
     "hipSpBiCGStabCSR": ([C.POINTER(spmat), C.POINTER(spmat), _vp, _vp, _vp, _vp], _i),
     "spmvHipMultiDot": ([_sz, C.c_uint, _vp, _sz, _vp, _vp], _i),
+    "spmvHipBlockDot": ([_sz, C.c_uint, _vp, _sz, _i, _vp, _sz, _i, _vp], _i),
+    "hipSpCGBlockCSR": ([C.POINTER(spmat), C.POINTER(spmat), C.c_uint, _vp, _sz, _i, _vp, _sz, _i, _vp, _vp, _vp], _i),
+    "hipSpBiCGStabBlockCSR": ([C.POINTER(spmat), C.POINTER(spmat), C.c_uint, _vp, _sz, _i, _vp, _sz, _i, _vp, _vp, _vp], _i),
     "hipSpGMRESCSR": ([C.POINTER(spmat), C.POINTER(spmat), _vp, _vp, _vp, _vp], _i),
     "spmvHipColourCSR": ([C.POINTER(spmat), _vp, _vp, _vp, _vp], _i),
     "spmvHipCsrPermute": ([C.POINTER(spmat), _vp, C.POINTER(spmat)], _i),
@@ -193,6 +196,11 @@ class spmvKrylovInfo(C.Structure):
     """include/spmvHip.h `spmvKrylovInfo`: what a hipSpCGCSR / hipSpBiCGStabCSR call did."""
     _fields_ = [("status", _i), ("iterations", C.c_ulong), ("rr", C.c_double), ("bb", C.c_double), ("launches", C.c_ulong),
                 ("hostChecks", C.c_ulong), ("ms", C.c_double)]
+
+
+class spmvKrylovColumn(C.Structure):
+    """include/spmvHip.h `spmvKrylovColumn`: what one column of a hipSpCGBlockCSR / hipSpBiCGStabBlockCSR call did."""
+    _fields_ = [("status", _i), ("iterations", C.c_ulong), ("rr", C.c_double), ("bb", C.c_double)]
 
 
 class spmvColourOpts(C.Structure):
@@ -471,7 +479,12 @@ class _Operands:
         elif init[1] is None:
             out = self.first.new_zeros(shape)
         else:
-            _device_vector(self.who, init[0], init[1], shape[0])
+            if len(shape) == 1:
+                _device_vector(self.who, init[0], init[1], shape[0])
+            elif not isinstance(init[1], _torch().Tensor) or tuple(init[1].shape) != shape:
+                raise SpmvHipError(f"{self.who}: {init[0]} must be a torch tensor of shape {shape}")
+            else:
+                _dense_layout(init[1], init[0], self.who)
             out = init[1].clone()
         self.res = out
         self.args.append(out.data_ptr())
@@ -898,6 +911,37 @@ class DeviceMatrix:
         info.history holds the estimates inside a cycle and the true squared residual at every cycle's last index."""
         return self._krylov(lib.hipSpGMRESCSR, "hipSpGMRESCSR", b, x0, precond, tol, maxiter, history, restart=restart)
 
+    def cg_block(self, B, X0=None, precond=None, tol=1e-8, maxiter=1000, history=False):
+        """hipSpCGBlockCSR: k solves A x_c = b_c in lock step, column c of X with the bits of cg() on column c of B (and of
+        X0), the matrix and the preconditioner's schedule streamed once per iteration for all columns.  B (and X0) are
+        (N, k) float64: numpy arrays -> X as numpy; or device torch tensors with unit stride in one dimension (the rules
+        of matmul's X) -> X as a new torch tensor.  precond: None or a DeviceMatrix holding ILU(0) factors (a multigrid
+        hierarchy is refused).  Returns (X, info): info.columns the k spmvKrylovColumn records; info.history, when
+        history=True, a list of k arrays hist[0 .. iterations_c]."""
+        return self._krylov_block(lib.hipSpCGBlockCSR, "hipSpCGBlockCSR", B, X0, precond, tol, maxiter, history)
+
+    def bicgstab_block(self, B, X0=None, precond=None, tol=1e-8, maxiter=1000, history=False):
+        """hipSpBiCGStabBlockCSR: as cg_block(), every column with the bits of bicgstab()."""
+        return self._krylov_block(lib.hipSpBiCGStabBlockCSR, "hipSpBiCGStabBlockCSR", B, X0, precond, tol, maxiter, history)
+
+    def _krylov_block(self, fn, name, B, X0, precond, tol, maxiter, history):
+        N = int(self.handle.N)
+        info = spmvKrylovInfo()
+        mh = C.byref(precond.handle) if precond is not None else None
+        with _Operands(name, B) as ops:
+            k, bl, ldb = ops.dense("B", B, N)
+            xl, ldx = ops.result("X", None, (N, k), init=("X0", X0))
+            hist = np.zeros((k, int(maxiter) + 1), np.float64) if history else None
+            opts = spmvKrylovOpts(float(tol), int(maxiter), hist.ctypes.data_as(C.POINTER(C.c_double)) if history else None)
+            cols = (spmvKrylovColumn * k)()
+            db, dx = ops.args
+            _check(fn(C.byref(self.handle), mh, k, db, ldb, bl, dx, ldx, xl, C.byref(opts), cols, C.byref(info)), name)
+            X = ops.value()
+        info.columns = list(cols)
+        if history:
+            info.history = [hist[c, :cols[c].iterations + 1].copy() for c in range(k)]
+        return X, info
+
     def _krylov(self, fn, name, b, x0, precond, tol, maxiter, history, restart=None):
         N = int(self.handle.N)
         hist = np.zeros(int(maxiter) + 1, np.float64) if history else None
@@ -1092,6 +1136,21 @@ def multi_dot(V, w):
         ops.result("h", None, (k,), least=8)
         dV, dw, dh = ops.args
         _check(lib.spmvHipMultiDot(n, k, dV, ldv, dw, dh), "spmvHipMultiDot")
+        return ops.value()
+
+
+def block_dot(U, V):
+    """spmvHipBlockDot: h[c] = U[:, c] . V[:, c], every h[c] the bits of dot(U[:, c], V[:, c]).  U and V are (n, k) float64
+    with k >= 1: device torch tensors with unit stride in one dimension, each in its own layout (the rules of matmul's
+    X; V may be U) -> a length-k device tensor; or numpy arrays -> a numpy array."""
+    with _Operands("block_dot", U) as ops:
+        k, ul, ldu = ops.dense("U", U, U.shape[0] if U.ndim == 2 else -1)
+        kv, vl, ldv = ops.dense("V", V, U.shape[0])
+        if kv != k:
+            raise SpmvHipError(f"block_dot: V must have {k} columns, not {kv}")
+        ops.result("h", None, (k,), least=8)
+        dU, dV, dh = ops.args
+        _check(lib.spmvHipBlockDot(U.shape[0], k, dU, ldu, ul, dV, ldv, vl, dh), "spmvHipBlockDot")
         return ops.value()
 
 

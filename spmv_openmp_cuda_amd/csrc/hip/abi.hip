@@ -148,6 +148,8 @@ int spmvHipSetVariant(const char* launcher, int variant) {
     if (!strcmp(launcher, "hipSpILU0CSR") && (variant == 8 || variant == 16 || variant == 64)) { S.iluGroup = (uint32_t)variant; return EXIT_SUCCESS; }
     if (!strcmp(launcher, "hipSpCGCSR") && variant >= 1 && variant <= 4096) { S.krylovK[0] = (uint32_t)variant; return EXIT_SUCCESS; }
     if (!strcmp(launcher, "hipSpBiCGStabCSR") && variant >= 1 && variant <= 4096) { S.krylovK[1] = (uint32_t)variant; return EXIT_SUCCESS; }
+    if (!strcmp(launcher, "hipSpCGBlockCSR") && variant >= 1 && variant <= 4096) { S.krylovBlockK[0] = (uint32_t)variant; return EXIT_SUCCESS; }
+    if (!strcmp(launcher, "hipSpBiCGStabBlockCSR") && variant >= 1 && variant <= 4096) { S.krylovBlockK[1] = (uint32_t)variant; return EXIT_SUCCESS; }
     if (!strcmp(launcher, "hipSpGMRESCSR") && (variant == 0 || variant == 1)) { S.gmresFused = variant; return EXIT_SUCCESS; }
     if (!strcmp(launcher, "spmvHipColourCSR") && variant >= 1 && variant <= 4096) { S.colourK = (uint32_t)variant; return EXIT_SUCCESS; }
     if (!strcmp(launcher, "spmvHipAggregateCSR") && variant >= 1 && variant <= 4096) { S.aggK = (uint32_t)variant; return EXIT_SUCCESS; }

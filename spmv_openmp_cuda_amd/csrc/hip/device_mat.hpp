@@ -240,9 +240,10 @@ void triInfo(const DevMat* d, int uplo, spmvTriInfo* out);
 void freeTri(TriSchedule* s);
 // X = T^-1 B for k columns on the analysed triangle's schedule (trsm.hip; contract in spmvHip.h, design in DESIGN.md section
 // 26): B(i, c) at B[i*sbr + c*sbc], X(i, c) at X[i*ldx + c] (xRowMajor) or X[c*ldx + i]; as many launches as enqueueTrsv
-// makes, whatever k is, on `stream`, no allocation, no sync; reports the last launch.  The caller has checked the arguments.
+// makes, whatever k is, on `stream`, no allocation, no sync; reports the last launch; `stop` as enqueueTrsv's (the block
+// Krylov loops, krylov_block.hip).  The caller has checked the arguments.
 int  enqueueTrsm(const DevMat* d, int uplo, int diag, uint32_t k, const double* B, uint64_t sbr, uint64_t sbc, double* X,
-                 uint64_t ldx, bool xRowMajor, hipStream_t stream, dim3* grid, dim3* block);
+                 uint64_t ldx, bool xRowMajor, hipStream_t stream, dim3* grid, dim3* block, const uint32_t* stop = nullptr);
 // ILU(0) in place on the lower schedule d->tri[SPMV_TRI_LOWER] (ilu0.hip; contract in spmvHip.h, design in DESIGN.md section
 // 18).  iluUnsortedRow: the first row that is not strictly ascending, or -1 (synchronous).  iluFactor: the factorisation's
 // launches on `stream` for the checked handle, then the zero-pivot read-back (synchronous); groupWidth 8, 16 or 64 lanes
@@ -257,6 +258,15 @@ int  enqueueDot(uint64_t n, const double* u, const double* v, double* result, hi
 void freeDotWorkspace();
 int  krylovSolve(int bicg, spmat* hA, const DevMat* a, const DevMat* m, const double* b, double* x, const spmvKrylovOpts* opts,
                  spmvKrylovInfo* info, uint32_t K, hipStream_t stream);
+// Blocks of right-hand sides (krylov_block.hip; contract in spmvHip.h, design in DESIGN.md section 27), elements at
+// [i*row stride + c*column stride].  enqueueBlockDot: k fixed-order dots U(:, c) . V(:, c) into k device doubles, partials
+// in the dot workspace.  krylovBlockSolve: k solves in lock step on the checked handles, m the analysed ILU(0) handle or
+// null, K iterations per read-back of the all-stopped word; allocates its workspace, synchronous.
+int  enqueueBlockDot(uint64_t n, uint32_t k, const double* U, uint64_t sur, uint64_t suc, const double* V, uint64_t svr,
+                     uint64_t svc, double* out, hipStream_t stream);
+int  krylovBlockSolve(int bicg, const DevMat* a, const DevMat* m, uint32_t k, const double* B, uint64_t sbr, uint64_t sbc,
+                      double* X, uint64_t sxr, uint64_t sxc, const spmvKrylovOpts* opts, spmvKrylovColumn* cols,
+                      spmvKrylovInfo* info, uint32_t K, hipStream_t stream);
 // h = V^T w and restarted GMRES (gmres.hip; contract in spmvHip.h, design in DESIGN.md section 20).  enqueueMultiDot: k
 // fixed-order dots in one pass into k device doubles, partials in the dot workspace (grown to k blocks-of-n).  gmresSolve:
 // GMRES(restart) with CGS2 on the checked handles; fused != 0 folds the first update into the second projection's

@@ -1,6 +1,6 @@
-// krylov.hpp -- what the Krylov files (krylov.hip, gmres.hip) share: the blocks and lanes of the fixed-order dot, the
-// element-pair loads and stores, the fixed tree, the fused-pass kernel and its launcher, the workspace holder, and the
-// preconditioner of a solve.
+// krylov.hpp -- what the Krylov files (krylov.hip, krylov_block.hip, gmres.hip) share: the blocks and lanes of the
+// fixed-order dot, the element-pair loads and stores, the state block of CG / BiCGStab and its scalar steps, the fixed tree,
+// the fused-pass kernel and its launcher, the workspace holder, and the preconditioner of a solve.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -11,8 +11,6 @@
 
 namespace spmvhip {
 namespace {
-
-struct KState;                                  // krylov.hip: the state block of CG / BiCGStab (gmres.hip passes none)
 
 constexpr uint32_t KT = 256;                    // lanes of a block (partials) and of the finish workgroup
 constexpr uint32_t KB = 4096;                   // indices of a block
@@ -34,6 +32,93 @@ __device__ __forceinline__ void st2(double* p, uint64_t i, bool two, double2 v) 
 __device__ __forceinline__ void madd(double& acc, double2 a, double2 b, bool two) {
     acc += a.x * b.x;
     if (two) acc += a.y * b.y;
+}
+
+// the loop's scalars and its status (written only by the finish kernels, by one lane)
+struct KState {
+    uint32_t stop;          // 0 while the loop runs
+    int32_t  status;        // SPMV_KRYLOV_* once stopped
+    uint64_t iterations;
+    uint64_t halfK;         // BiCGStab: the iteration whose x = x + alpha*phat is still to be written (0: none)
+    uint64_t maxIter;
+    double   tol2, rr, bb, thresh, rz, alpha, beta, omega, rho, rhoOld;
+};
+
+enum Phase : int { F_DOT, F_CG_INIT, F_CG_RZ, F_CG_ALPHA, F_CG_RR, F_BI_INIT, F_BI_ALPHA, F_BI_SS, F_BI_OMEGA, F_BI_RR };
+
+// the loop's scalar step `ph` of iteration k on one state block, d the dot (or the two dots) that the step consumes; run
+// by one lane.  The single solves (krylov.hip) and the block solves (krylov_block.hip, a state block per column) share it,
+// so a column of a block takes the exits of the single loop by construction.
+__device__ inline void krylovScalarStep(int ph, uint64_t k, double2 d, KState* st, double* hist, int precond) {
+    auto stopAt = [&](int status, uint64_t it) { st->status = status; st->iterations = it; st->stop = 1; };
+    switch (ph) {
+    case F_CG_INIT:
+    case F_BI_INIT: {
+        const double rr = d.x, bb = d.y, thresh = st->tol2 * bb;
+        st->rr = rr; st->bb = bb; st->thresh = thresh;
+        st->iterations = 0; st->halfK = 0; st->stop = 0; st->status = SPMV_KRYLOV_MAXITER;
+        if (hist) hist[0] = rr;
+        if (rr <= thresh) { stopAt(SPMV_KRYLOV_CONVERGED, 0); break; }
+        if (!isfinite(rr)) { stopAt(SPMV_KRYLOV_NONFINITE, 0); break; }
+        if (st->maxIter == 0) { stopAt(SPMV_KRYLOV_MAXITER, 0); break; }
+        if (ph == F_CG_INIT) {
+            if (!precond) st->rz = rr;
+        } else {
+            st->rho = rr; st->rhoOld = 1.0; st->alpha = 1.0; st->omega = 1.0;
+            if (rr == 0.0) stopAt(SPMV_KRYLOV_BREAKDOWN, 0);
+        }
+        break;
+    }
+    case F_CG_RZ:                                                        // rz = dot(r, z) (k = 0), else beta = rzn / rz
+        if (k == 0) st->rz = d.x;
+        else { st->beta = d.x / st->rz; st->rz = d.x; }
+        break;
+    case F_CG_ALPHA:
+        if (d.x == 0.0) stopAt(SPMV_KRYLOV_BREAKDOWN, k - 1);
+        else st->alpha = st->rz / d.x;
+        break;
+    case F_CG_RR: {
+        const double rr = d.x;
+        st->rr = rr;
+        if (hist) hist[k] = rr;
+        if (rr <= st->thresh) stopAt(SPMV_KRYLOV_CONVERGED, k);
+        else if (!isfinite(rr)) stopAt(SPMV_KRYLOV_NONFINITE, k);
+        else if (k == st->maxIter) stopAt(SPMV_KRYLOV_MAXITER, k);
+        else if (!precond) { st->beta = rr / st->rz; st->rz = rr; }
+        break;
+    }
+    case F_BI_ALPHA:
+        if (d.x == 0.0) stopAt(SPMV_KRYLOV_BREAKDOWN, k - 1);
+        else st->alpha = st->rho / d.x;
+        break;
+    case F_BI_SS:
+        st->rr = d.x;
+        if (hist) hist[k] = d.x;
+        if (d.x <= st->thresh) { st->halfK = k; stopAt(SPMV_KRYLOV_CONVERGED, k); }
+        break;
+    case F_BI_OMEGA:
+        if (d.x == 0.0) { st->halfK = k; stopAt(SPMV_KRYLOV_BREAKDOWN, k); }
+        else st->omega = d.y / d.x;
+        break;
+    case F_BI_RR: {
+        const double rr = d.x;
+        st->rr = rr;
+        if (hist) hist[k] = rr;
+        if (rr <= st->thresh) stopAt(SPMV_KRYLOV_CONVERGED, k);
+        else if (!isfinite(rr)) stopAt(SPMV_KRYLOV_NONFINITE, k);
+        else if (st->omega == 0.0) stopAt(SPMV_KRYLOV_BREAKDOWN, k);
+        else if (k == st->maxIter) stopAt(SPMV_KRYLOV_MAXITER, k);
+        else {
+            st->rhoOld = st->rho;
+            st->rho = d.y;
+            if (d.y == 0.0) stopAt(SPMV_KRYLOV_BREAKDOWN, k);
+            else st->beta = (st->rho / st->rhoOld) * (st->alpha / st->omega);
+        }
+        break;
+    }
+    default:
+        break;
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ the fused passes

@@ -1,0 +1,506 @@
+// krylov_block.hip -- k dots in one pass (spmvHipBlockDot) and CG / BiCGStab for a block of k right-hand sides
+// (hipSpCGBlockCSR, hipSpBiCGStabBlockCSR; contract in spmvHip.h, design in DESIGN.md section 27).  These are k independent
+// solves advanced in lock step: column c of X, its status, its iteration count and its residual norms are the bits of
+// hipSpCGCSR / hipSpBiCGStabCSR on column c alone, while the matrix (one hipSpMMRowsCSR pass), the level schedule of the
+// preconditioner (two hipSpTRSMCSR passes) and every launch are shared by the columns.
+//
+// One state block (KState of krylov.hpp) per column, and the scalar steps of the single loops (krylovScalarStep) run on it
+// unchanged, one workgroup per column in one finish launch.  Every fused pass reads the state of its two columns and leaves
+// a stopped column alone -- its x, r, p and state are frozen however long its neighbours run on -- and a head word that the
+// finish kernel sets when the last column stops is what the host reads once per K iterations and what the triangular
+// passes take as their stop pointer.
+//
+// The fused passes.  The working vectors are row-major n x kp blocks, kp = k rounded up to even, so a row's column pair
+// (c, c + 1), c even, is one 16-byte access; B and X are read and written where the caller keeps them, in 16-byte accesses
+// when their layout allows and in 8-byte ones otherwise (the same bits).  A workgroup of 256 lanes takes one block of 4096
+// rows and one panel of at most 16 columns.  P adjacent lanes hold the panel's P column pairs (P = 1, 2, 4 or 8, from the
+// widest panel), so the 256 / P lane groups read 256 / P row pairs per load instruction, each row a contiguous run of 16 P
+// bytes.  What the dot's contract calls "lane t" (the products of rows 512 s + 2 t and 512 s + 2 t + 1, s ascending) is
+// computed by group g = t mod (256 / P) as its j-th partial, j = t / (256 / P); the partials of one group are exactly those
+// that the tree a[t] += a[t + h] joins at h = 128 ... 256 / P, which therefore happens in registers, in the tree's order
+// and depth first (log2 P + 1 live partials, not P); the levels below go through LDS as in the single dot.
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <vector>
+
+#include "spmvHip.h"
+#include "kernels.hpp"
+#include "krylov.hpp"
+
+namespace spmvhip {
+namespace {
+
+constexpr uint32_t BK_PANEL = 16;               // columns of a panel (the convention of spmm.hip and trsm.hip)
+
+// what the host reads once per batch and the triangular passes take as their stop pointer
+struct BlockHead {
+    uint32_t allStop;       // 0 while a column runs
+    uint32_t stopped;       // columns that have stopped (one ordinary atomicAdd by the lane that stops a column)
+};
+
+// a dense block: element (i, c) at p[i*sr + c*sc]; pair: columns (c, c + 1), c even, of a row are one aligned 16-byte access
+struct BMat {
+    double* p; uint64_t sr, sc; int pair;
+};
+BMat bmat(const double* p, uint64_t sr, uint64_t sc, uint32_t k, bool padded) {
+    // a caller's block has no element behind column k - 1: with k odd its last pair is not there to be loaded
+    const bool pair = sc == 1 && sr % 2 == 0 && aligned16(p) && (padded || k % 2 == 0);
+    return BMat{const_cast<double*>(p), sr, sc, pair};
+}
+
+__device__ __forceinline__ double2 ldp(const BMat& m, uint64_t i, uint32_t c, bool two) {
+    const double* q = m.p + i * m.sr + c * m.sc;
+    if (m.pair) return *reinterpret_cast<const double2*>(q);
+    return make_double2(q[0], two ? q[m.sc] : 0.0);
+}
+// columns c (w0) and c + 1 (w1) of row i
+__device__ __forceinline__ void stp(const BMat& m, uint64_t i, uint32_t c, int w0, int w1, double2 v) {
+    double* q = m.p + i * m.sr + c * m.sc;
+    if (m.pair && w0 && w1) { *reinterpret_cast<double2*>(q) = v; return; }
+    if (w0) q[0] = v.x;
+    if (w1) q[m.sc] = v.y;
+}
+
+// the partials of a column pair: d0 / d1 the op's first / second dot, .x column c, .y column c + 1
+struct Acc { double2 d0, d1; };
+__device__ __forceinline__ Acc accAdd(const Acc& m, const Acc& o) {
+    return Acc{make_double2(m.d0.x + o.d0.x, m.d0.y + o.d0.y), make_double2(m.d1.x + o.d1.x, m.d1.y + o.d1.y)};
+}
+__device__ __forceinline__ void madd2(double2& acc, double2 a, double2 b) { acc.x += a.x * b.x; acc.y += a.y * b.y; }
+__device__ __forceinline__ double2 axpy2(double2 a, double2 s, double2 v) { return make_double2(a.x + s.x * v.x, a.y + s.y * v.y); }
+__device__ __forceinline__ double2 axmy2(double2 a, double2 s, double2 v) { return make_double2(a.x - s.x * v.x, a.y - s.y * v.y); }
+__device__ __forceinline__ void put(double2& v, int x, double s) { if (x) v.y = s; else v.x = s; }
+
+// ------------------------------------------------------------------------------------- the block forms of the fused passes
+// Each op: NDOT; mode(x, st, sc) for column x (0 / 1) of the lane's pair with that column's state: 0 leaves the column
+// alone, otherwise the column's scalars go to the lane's sc; load() one row's inputs for the pair (two: column c + 1 exists); step() the update
+// of the columns w0 / w1 and the products, a row at a time in ascending order.  A column that is left alone is still
+// computed (its lanes share the pair's loads) but never stored, and its partials are never written.
+struct BDotOp {                                 // U(:, c) . V(:, c)
+    static constexpr int NDOT = 1;
+    static constexpr uint32_t CHUNK = 4;
+    BMat u, v;
+    struct R { double2 u, v; };
+    struct Sc {};
+    __device__ __forceinline__ int mode(int, const KState*, Sc&) const { return 1; }
+    __device__ __forceinline__ void load(uint64_t i, uint32_t c, bool two, const Sc&, R& r) const { r.u = ldp(u, i, c, two); r.v = ldp(v, i, c, two); }
+    __device__ __forceinline__ void step(uint64_t, uint32_t, int, int, const Sc&, const R& r, Acc& a) const { madd2(a.d0, r.u, r.v); }
+};
+struct BGuardedDot : BDotOp {
+    __device__ __forceinline__ int mode(int, const KState* st, Sc&) const { return !st->stop; }
+};
+
+struct BInitOp {                                // r = b - q (rhat = r too when given); r . r and b . b
+    static constexpr int NDOT = 2;
+    static constexpr uint32_t CHUNK = 4;
+    BMat b, q, r, rhat;
+    struct R { double2 b, q; };
+    struct Sc {};
+    __device__ __forceinline__ int mode(int, const KState*, Sc&) const { return 1; }
+    __device__ __forceinline__ void load(uint64_t i, uint32_t c, bool two, const Sc&, R& x) const { x.b = ldp(b, i, c, two); x.q = ldp(q, i, c, two); }
+    __device__ __forceinline__ void step(uint64_t i, uint32_t c, int w0, int w1, const Sc&, const R& x, Acc& a) const {
+        const double2 rv = make_double2(x.b.x - x.q.x, x.b.y - x.q.y);
+        stp(r, i, c, w0, w1, rv);
+        if (rhat.p) stp(rhat, i, c, w0, w1, rv);
+        madd2(a.d0, rv, rv);
+        madd2(a.d1, x.b, x.b);
+    }
+};
+
+struct BTtTsOp {                                // t . t and t . s
+    static constexpr int NDOT = 2;
+    static constexpr uint32_t CHUNK = 4;
+    BMat t, s;
+    struct R { double2 t, s; };
+    struct Sc {};
+    __device__ __forceinline__ int mode(int, const KState* st, Sc&) const { return !st->stop; }
+    __device__ __forceinline__ void load(uint64_t i, uint32_t c, bool two, const Sc&, R& r) const { r.t = ldp(t, i, c, two); r.s = ldp(s, i, c, two); }
+    __device__ __forceinline__ void step(uint64_t, uint32_t, int, int, const Sc&, const R& r, Acc& a) const { madd2(a.d0, r.t, r.t); madd2(a.d1, r.t, r.s); }
+};
+
+struct BCgUpdateOp {                            // x = x + alpha*p; r = r - alpha*q; r . r
+    static constexpr int NDOT = 1;
+    static constexpr uint32_t CHUNK = 2;
+    BMat x, p, r, q;
+    struct R { double2 x, p, r, q; };
+    struct Sc { double2 alpha; };
+    __device__ __forceinline__ int mode(int c, const KState* st, Sc& sc) const { if (st->stop) return 0; put(sc.alpha, c, st->alpha); return 1; }
+    __device__ __forceinline__ void load(uint64_t i, uint32_t c, bool two, const Sc&, R& v) const {
+        v.x = ldp(x, i, c, two); v.p = ldp(p, i, c, two); v.r = ldp(r, i, c, two); v.q = ldp(q, i, c, two);
+    }
+    __device__ __forceinline__ void step(uint64_t i, uint32_t c, int w0, int w1, const Sc& sc, const R& v, Acc& a) const {
+        const double2 rn = axmy2(v.r, sc.alpha, v.q);
+        stp(x, i, c, w0, w1, axpy2(v.x, sc.alpha, v.p));
+        stp(r, i, c, w0, w1, rn);
+        madd2(a.d0, rn, rn);
+    }
+};
+
+struct BCgPOp {                                 // p = z (first) or p = z + beta*p
+    static constexpr int NDOT = 0;
+    static constexpr uint32_t CHUNK = 4;
+    BMat z, p; int first;
+    struct R { double2 z, p; };
+    struct Sc { double2 beta; };
+    __device__ __forceinline__ int mode(int c, const KState* st, Sc& sc) const { if (st->stop) return 0; put(sc.beta, c, st->beta); return 1; }
+    __device__ __forceinline__ void load(uint64_t i, uint32_t c, bool two, const Sc&, R& v) const {
+        v.z = ldp(z, i, c, two);
+        if (!first) v.p = ldp(p, i, c, two);
+    }
+    __device__ __forceinline__ void step(uint64_t i, uint32_t c, int w0, int w1, const Sc& sc, const R& v, Acc&) const {
+        stp(p, i, c, w0, w1, first ? v.z : axpy2(v.z, sc.beta, v.p));
+    }
+};
+
+struct BBiPOp {                                 // p = r (first) or p = r + beta*(p - omega*v)
+    static constexpr int NDOT = 0;
+    static constexpr uint32_t CHUNK = 4;
+    BMat r, p, v; int first;
+    struct R { double2 r, p, v; };
+    struct Sc { double2 beta, omega; };
+    __device__ __forceinline__ int mode(int c, const KState* st, Sc& sc) const {
+        if (st->stop) return 0;
+        put(sc.beta, c, st->beta); put(sc.omega, c, st->omega);
+        return 1;
+    }
+    __device__ __forceinline__ void load(uint64_t i, uint32_t c, bool two, const Sc&, R& x) const {
+        x.r = ldp(r, i, c, two);
+        if (!first) { x.p = ldp(p, i, c, two); x.v = ldp(v, i, c, two); }
+    }
+    __device__ __forceinline__ void step(uint64_t i, uint32_t c, int w0, int w1, const Sc& sc, const R& x, Acc&) const {
+        if (first) { stp(p, i, c, w0, w1, x.r); return; }
+        stp(p, i, c, w0, w1, axpy2(x.r, sc.beta, axmy2(x.p, sc.omega, x.v)));
+    }
+};
+
+struct BSOp {                                   // s = r - alpha*v; s . s
+    static constexpr int NDOT = 1;
+    static constexpr uint32_t CHUNK = 4;
+    BMat r, v, s;
+    struct R { double2 r, v; };
+    struct Sc { double2 alpha; };
+    __device__ __forceinline__ int mode(int c, const KState* st, Sc& sc) const { if (st->stop) return 0; put(sc.alpha, c, st->alpha); return 1; }
+    __device__ __forceinline__ void load(uint64_t i, uint32_t c, bool two, const Sc&, R& x) const { x.r = ldp(r, i, c, two); x.v = ldp(v, i, c, two); }
+    __device__ __forceinline__ void step(uint64_t i, uint32_t c, int w0, int w1, const Sc& sc, const R& x, Acc& a) const {
+        const double2 sn = axmy2(x.r, sc.alpha, x.v);
+        stp(s, i, c, w0, w1, sn);
+        madd2(a.d0, sn, sn);
+    }
+};
+
+// a running column: x = (x + alpha*phat) + omega*shat; r = s - omega*t; r . r and rhat . r.  A column stopped at a half
+// step of THIS iteration (halfK == k): x = x + alpha*phat only.  Both per column: the two of a pair may differ.
+struct BBiUpdateOp {
+    static constexpr int NDOT = 2;
+    static constexpr uint32_t CHUNK = 2;
+    BMat x, phat, shat, r, s, t, rhat;
+    uint64_t k;
+    struct R { double2 x, ph, sh, s, t, rh; };
+    struct Sc { double2 alpha, omega; int full0 = 0, full1 = 0; };
+    __device__ __forceinline__ int mode(int c, const KState* st, Sc& sc) const {
+        const int full = !st->stop;
+        if (c) sc.full1 = full; else sc.full0 = full;
+        if (!full && st->halfK != k) return 0;
+        put(sc.alpha, c, st->alpha); put(sc.omega, c, st->omega);
+        return 1;
+    }
+    __device__ __forceinline__ void load(uint64_t i, uint32_t c, bool two, const Sc& sc, R& v) const {
+        v.x = ldp(x, i, c, two); v.ph = ldp(phat, i, c, two);
+        if (sc.full0 | sc.full1) { v.sh = ldp(shat, i, c, two); v.s = ldp(s, i, c, two); v.t = ldp(t, i, c, two); v.rh = ldp(rhat, i, c, two); }
+    }
+    __device__ __forceinline__ void step(uint64_t i, uint32_t c, int w0, int w1, const Sc& sc, const R& v, Acc& a) const {
+        const double2 h = axpy2(v.x, sc.alpha, v.ph);
+        if (!(sc.full0 | sc.full1)) { stp(x, i, c, w0, w1, h); return; }
+        const double2 xf = axpy2(h, sc.omega, v.sh);
+        stp(x, i, c, w0, w1, make_double2(sc.full0 ? xf.x : h.x, sc.full1 ? xf.y : h.y));
+        const double2 rn = axmy2(v.s, sc.omega, v.t);
+        stp(r, i, c, w0 && sc.full0, w1 && sc.full1, rn);
+        madd2(a.d0, rn, rn);
+        madd2(a.d1, v.rh, rn);
+    }
+};
+
+// "lane t" of the dot's contract for one column pair: rows base + 512 s + 2 t and + 1 for s = 0 .. 7, in that order from +0.0
+template <class Op>
+__device__ __forceinline__ Acc lane_partial(const Op& op, const typename Op::Sc sc, uint64_t n, uint64_t base, uint32_t t, uint32_t c, bool two, int w0, int w1) {
+    Acc a{make_double2(0.0, 0.0), make_double2(0.0, 0.0)};
+    if (!(w0 | w1)) return a;
+    const uint64_t first = base + 2 * t;
+#pragma unroll
+    for (uint32_t s = 0; s < KSLICES; s += Op::CHUNK) {
+        typename Op::R r[Op::CHUNK][2];
+#pragma unroll
+        for (uint32_t u = 0; u < Op::CHUNK; ++u) {
+            const uint64_t i = first + (uint64_t)(s + u) * (2 * KT);
+            if (i < n) op.load(i, c, two, sc, r[u][0]);
+            if (i + 1 < n) op.load(i + 1, c, two, sc, r[u][1]);
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < Op::CHUNK; ++u) {
+            const uint64_t i = first + (uint64_t)(s + u) * (2 * KT);
+            if (i < n) op.step(i, c, w0, w1, sc, r[u][0], a);
+            if (i + 1 < n) op.step(i + 1, c, w0, w1, sc, r[u][1], a);
+        }
+    }
+    return a;
+}
+
+// the tree's levels h = 128 ... 256 / P on the partials t = g + (256 / P) j of one lane group: a[j] += a[j + S'] for
+// S' = P / 2 ... 1, written depth first so that only one partial per level is alive
+template <class Op, int P, int S>
+__device__ __forceinline__ Acc group_partial(const Op& op, const typename Op::Sc sc, uint64_t n, uint64_t base, uint32_t g, uint32_t j, uint32_t c, bool two,
+                                             int w0, int w1) {
+    if constexpr (S >= P) {
+        return lane_partial(op, sc, n, base, g + (KT / P) * j, c, two, w0, w1);
+    } else {
+        const Acc m = group_partial<Op, P, 2 * S>(op, sc, n, base, g, j, c, two, w0, w1);
+        const Acc o = group_partial<Op, P, 2 * S>(op, sc, n, base, g, j + S, c, two, w0, w1);
+        return accAdd(m, o);
+    }
+}
+
+// one block of KB rows and one panel of columns: the op's update on them, and its dots' block partials into
+// part0 / part1[blk * kp + column]
+template <class Op, int P>
+__global__ __launch_bounds__(KT) void block_vec_kernel(uint64_t n, uint32_t k, uint32_t kp, uint32_t panels,
+                                                       const KState* __restrict__ st, const Op op, double* __restrict__ part0,
+                                                       double* __restrict__ part1) {
+    static_assert(P == 1 || P == 2 || P == 4 || P == 8, "column pairs of a panel");
+    __shared__ Acc sh[KT];
+    const uint64_t lin = linear_block();
+    const uint64_t blk = lin / panels;
+    if (blk * KB >= n) return;                                           // (a folded grid's tail)
+    const uint32_t tid = threadIdx.x;
+    const uint32_t c = (uint32_t)(lin % panels) * BK_PANEL + 2 * (tid % P);
+    typename Op::Sc sc{};                                                // the scalars of this lane's two columns
+    const int w0 = c < k ? op.mode(0, st + c, sc) : 0;
+    const int w1 = c + 1 < k ? op.mode(1, st + c + 1, sc) : 0;
+    if (!__syncthreads_or(w0 | w1)) return;                              // every column of this panel has stopped
+    Acc a = group_partial<Op, P, 1>(op, sc, n, blk * KB, tid / P, 0, c, c + 1 < k, w0, w1);
+    if (Op::NDOT == 0) return;
+    sh[tid] = a;
+    __syncthreads();
+#pragma unroll
+    for (uint32_t h = KT / 2; h >= P; h >>= 1) {
+        if (tid < h) sh[tid] = accAdd(sh[tid], sh[tid + h]);
+        __syncthreads();
+    }
+    if (tid >= P) return;
+    a = sh[tid];
+    double* q0 = part0 + blk * kp + c;
+    if (w0) q0[0] = a.d0.x;
+    if (w1) q0[1] = a.d0.y;
+    if (Op::NDOT > 1) {
+        double* q1 = part1 + blk * kp + c;
+        if (w0) q1[0] = a.d1.x;
+        if (w1) q1[1] = a.d1.y;
+    }
+}
+
+// column c = the workgroup: its block partials by the dot's second level (lane t adds partials t, t + 256, ... in order,
+// then the tree), then lane 0 runs the column's scalar step `ph` of iteration it -- or stores the dot (F_DOT)
+__global__ __launch_bounds__(KT) void block_finish_kernel(uint64_t nb, uint32_t k, uint32_t kp, const double* __restrict__ part0,
+                                                          const double* __restrict__ part1, int ph, uint64_t it, KState* st,
+                                                          BlockHead* head, double* hist, uint64_t histLd, double* out, int precond) {
+    __shared__ double2 sh[KT];
+    const uint32_t c = blockIdx.x;
+    if (c >= k) return;
+    KState* s = st ? st + c : nullptr;
+    if (ph != F_DOT && ph != F_CG_INIT && ph != F_BI_INIT && s->stop) return;
+    double a0 = 0.0, a1 = 0.0;
+    for (uint64_t j = threadIdx.x; j < nb; j += KT) {
+        a0 += part0[j * kp + c];
+        if (part1) a1 += part1[j * kp + c];
+    }
+    const double2 d = tree256(make_double2(a0, a1), sh);
+    if (threadIdx.x != 0) return;
+    if (ph == F_DOT) { out[c] = d.x; return; }
+    krylovScalarStep(ph, it, d, s, hist ? hist + c * histLd : nullptr, precond);
+    // the column ran (or starts) and has now stopped: it is counted once, and the last one sets the head word, which
+    // later launches read -- ordering comes from the kernel boundary
+    if (s->stop && atomicAdd(&head->stopped, 1u) + 1 == k) head->allStop = 1;
+}
+
+template <class Op>
+void launchBlockVec(uint64_t n, uint32_t k, const KState* st, const Op& op, double* p0, double* p1, hipStream_t s) {
+    const uint64_t nb = blocksOf(n);
+    if (!nb) return;
+    const uint32_t kp = k + (k & 1), panels = (k + BK_PANEL - 1) / BK_PANEL;
+    const uint32_t w = k < BK_PANEL ? k : BK_PANEL;                      // the widest panel
+    const dim3 grid = grid2d(nb * panels, KT);
+    if (w <= 2)      hipLaunchKernelGGL((block_vec_kernel<Op, 1>), grid, dim3(KT), 0, s, n, k, kp, panels, st, op, p0, p1);
+    else if (w <= 4) hipLaunchKernelGGL((block_vec_kernel<Op, 2>), grid, dim3(KT), 0, s, n, k, kp, panels, st, op, p0, p1);
+    else if (w <= 8) hipLaunchKernelGGL((block_vec_kernel<Op, 4>), grid, dim3(KT), 0, s, n, k, kp, panels, st, op, p0, p1);
+    else             hipLaunchKernelGGL((block_vec_kernel<Op, 8>), grid, dim3(KT), 0, s, n, k, kp, panels, st, op, p0, p1);
+}
+
+void launchBlockFinish(uint64_t n, uint32_t k, const double* p0, const double* p1, int ph, uint64_t it, KState* st, BlockHead* head,
+                       double* hist, uint64_t histLd, double* out, int precond, hipStream_t s) {
+    hipLaunchKernelGGL(block_finish_kernel, dim3(k), dim3(KT), 0, s, blocksOf(n), k, k + (k & 1), p0, p1, ph, it, st, head, hist,
+                       histLd, out, precond);
+}
+
+}  // namespace
+
+int enqueueBlockDot(uint64_t n, uint32_t k, const double* U, uint64_t sur, uint64_t suc, const double* V, uint64_t svr,
+                    uint64_t svc, double* out, hipStream_t st) {
+    const uint32_t kp = k + (k & 1);
+    double* part = nullptr;
+    if (dotWorkspace(blocksOf(n) * kp, &part)) return EXIT_FAILURE;
+    BDotOp op;
+    op.u = bmat(U, sur, suc, k, false);
+    op.v = bmat(V, svr, svc, k, false);
+    launchBlockVec(n, k, nullptr, op, part, nullptr, st);
+    launchBlockFinish(n, k, part, nullptr, F_DOT, 0, nullptr, nullptr, nullptr, 0, out, 0, st);
+    return hipGetLastError() == hipSuccess ? EXIT_SUCCESS : EXIT_FAILURE;
+}
+
+int krylovBlockSolve(int bicg, const DevMat* a, const DevMat* m, uint32_t k, const double* B, uint64_t sbr, uint64_t sbc, double* X,
+                     uint64_t sxr, uint64_t sxc, const spmvKrylovOpts* o, spmvKrylovColumn* cols, spmvKrylovInfo* info, uint32_t K,
+                     hipStream_t s) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint64_t n = a->M, nb = std::max<uint64_t>(blocksOf(n), 1), histLd = o->maxIter + 1;
+    const uint32_t kp = k + (k & 1);
+    const int pre = m != nullptr;
+    const auto fail = [] { fprintf(stderr, "libspmvhip: block Krylov solve: workspace allocation failed\n"); return EXIT_FAILURE; };
+    spmvKrylovInfo out{};
+    DevBufs w;
+    const int nvec = bicg ? (pre ? 8 : 6) : (pre ? 4 : 3);
+    BMat v[8] = {};
+    for (int i = 0; i < nvec; ++i) {
+        double* p = w.alloc<double>(n * kp);
+        if (!p) return fail();
+        v[i] = bmat(p, kp, 1, k, true);
+    }
+    double* part = w.alloc<double>(2 * nb * kp);
+    BlockHead* head = w.alloc<BlockHead>(1);
+    KState* st = w.alloc<KState>(k);
+    double* hist = o->history ? w.alloc<double>(k * histLd) : nullptr;
+    if (!part || !head || !st || (o->history && !hist)) return fail();
+    double* p0 = part;
+    double* p1 = part + nb * kp;
+    KState h0{};
+    h0.maxIter = o->maxIter;
+    h0.tol2 = o->tol * o->tol;
+    std::vector<KState> h(k, h0);
+    BlockHead hh{};
+    HIP_TRY(hipMemcpyAsync(st, h.data(), k * sizeof(KState), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(head, &hh, sizeof hh, hipMemcpyHostToDevice, s));
+    const BMat b = bmat(B, sbr, sbc, k, false), x = bmat(X, sxr, sxc, k, false);
+    unsigned long triLaunches = 0;
+    if (pre) {
+        spmvTriInfo t{};
+        for (int uplo : {SPMV_TRI_LOWER, SPMV_TRI_UPPER}) { triInfo(m, uplo, &t); triLaunches += t.launches; }
+    }
+    auto precond = [&](const BMat& in, const BMat& outv) {                // z = U^-1 (L^-1 in), every launch behind the head word
+        dim3 g, bl;
+        if (enqueueTrsm(m, SPMV_TRI_LOWER, SPMV_DIAG_UNIT, k, in.p, kp, 1, outv.p, kp, true, s, &g, &bl, &head->allStop)) return EXIT_FAILURE;
+        if (enqueueTrsm(m, SPMV_TRI_UPPER, SPMV_DIAG_STORED, k, outv.p, kp, 1, outv.p, kp, true, s, &g, &bl, &head->allStop)) return EXIT_FAILURE;
+        out.launches += triLaunches;
+        return EXIT_SUCCESS;
+    };
+    auto spmm = [&](const BMat& in, const BMat& outv) {
+        ++out.launches;
+        return enqueueSpmm(a, k, in.p, in.sr, in.sc, outv.p, kp, 1, s);
+    };
+    auto vec = [&](const auto& op) {
+        launchBlockVec(n, k, st, op, p0, p1, s);
+        ++out.launches;
+    };
+    auto finish = [&](int ph, uint64_t it, int ndot) {
+        launchBlockFinish(n, k, p0, ndot > 1 ? p1 : nullptr, ph, it, st, head, hist, histLd, nullptr, pre, s);
+        ++out.launches;
+    };
+    auto allStopped = [&](bool* stopped) {                                // one read-back of the head word
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&hh, head, sizeof hh, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        ++out.hostChecks;
+        *stopped = hh.allStop != 0;
+        return EXIT_SUCCESS;
+    };
+    bool done = false;
+    // r, p, q (, z) / r, rhat, p, v, s, t (, phat, shat)
+    const BMat r = v[0], q = v[2], none{};
+    if (spmm(x, q)) return EXIT_FAILURE;
+    if (!bicg) {
+        const BMat p = v[1], z = pre ? v[3] : r;
+        { BInitOp op; op.b = b; op.q = q; op.r = r; op.rhat = none; vec(op); }
+        finish(F_CG_INIT, 0, 2);
+        if (allStopped(&done)) return EXIT_FAILURE;                      // every column stopped at the init: no further kernel
+        auto rz = [&](uint64_t it) {
+            if (precond(r, z)) return EXIT_FAILURE;
+            BGuardedDot op; op.u = r; op.v = z; vec(op);
+            finish(F_CG_RZ, it, 1);
+            return EXIT_SUCCESS;
+        };
+        if (!done) {
+            if (pre && rz(0)) return EXIT_FAILURE;
+            BCgPOp op; op.z = z; op.p = p; op.first = 1; vec(op);
+        }
+        for (uint64_t it = 1; !done && it <= o->maxIter;) {
+            const uint64_t end = std::min<uint64_t>(o->maxIter, it + K - 1);
+            for (; it <= end; ++it) {
+                if (spmm(p, q)) return EXIT_FAILURE;
+                { BGuardedDot op; op.u = p; op.v = q; vec(op); }
+                finish(F_CG_ALPHA, it, 1);
+                { BCgUpdateOp op; op.x = x; op.p = p; op.r = r; op.q = q; vec(op); }
+                finish(F_CG_RR, it, 1);
+                if (pre && rz(it)) return EXIT_FAILURE;
+                { BCgPOp op; op.z = z; op.p = p; op.first = 0; vec(op); }
+            }
+            if (allStopped(&done)) return EXIT_FAILURE;
+        }
+    } else {
+        const BMat rhat = v[1], p = v[3], vv = v[4], sv = v[5], t = q, phat = pre ? v[6] : p, shat = pre ? v[7] : sv;
+        { BInitOp op; op.b = b; op.q = q; op.r = r; op.rhat = rhat; vec(op); }
+        finish(F_BI_INIT, 0, 2);
+        if (allStopped(&done)) return EXIT_FAILURE;
+        for (uint64_t it = 1; !done && it <= o->maxIter;) {
+            const uint64_t end = std::min<uint64_t>(o->maxIter, it + K - 1);
+            for (; it <= end; ++it) {
+                { BBiPOp op; op.r = r; op.p = p; op.v = vv; op.first = it == 1; vec(op); }
+                if (pre && precond(p, phat)) return EXIT_FAILURE;
+                if (spmm(phat, vv)) return EXIT_FAILURE;
+                { BGuardedDot op; op.u = rhat; op.v = vv; vec(op); }
+                finish(F_BI_ALPHA, it, 1);
+                { BSOp op; op.r = r; op.v = vv; op.s = sv; vec(op); }
+                finish(F_BI_SS, it, 1);
+                if (pre && precond(sv, shat)) return EXIT_FAILURE;
+                if (spmm(shat, t)) return EXIT_FAILURE;
+                { BTtTsOp op; op.t = t; op.s = sv; vec(op); }
+                finish(F_BI_OMEGA, it, 2);
+                {
+                    BBiUpdateOp op;
+                    op.x = x; op.phat = phat; op.shat = shat; op.r = r; op.s = sv; op.t = t; op.rhat = rhat; op.k = it;
+                    vec(op);
+                }
+                finish(F_BI_RR, it, 2);
+            }
+            if (allStopped(&done)) return EXIT_FAILURE;
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h.data(), st, k * sizeof(KState), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (uint32_t c = 0; c < k; ++c)
+        if (!h[c].stop) { fprintf(stderr, "libspmvhip: block Krylov solve: column %u did not stop\n", c); return EXIT_FAILURE; }
+    uint32_t lead = 0;                                                   // the lowest-numbered column of the largest status
+    for (uint32_t c = 0; c < k; ++c) {
+        if (o->history)
+            HIP_TRY(hipMemcpy(o->history + c * histLd, hist + c * histLd, (h[c].iterations + 1) * sizeof(double), hipMemcpyDeviceToHost));
+        if (cols) cols[c] = spmvKrylovColumn{h[c].status, h[c].iterations, h[c].rr, h[c].bb};
+        if (h[c].status > h[lead].status) lead = c;
+        out.iterations = std::max<unsigned long>(out.iterations, h[c].iterations);
+    }
+    out.status = h[lead].status;
+    out.rr = h[lead].rr;
+    out.bb = h[lead].bb;
+    out.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (info) *info = out;
+    return EXIT_SUCCESS;
+}
+
+}  // namespace spmvhip

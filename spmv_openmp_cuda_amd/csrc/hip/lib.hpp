@@ -27,6 +27,7 @@ struct State {
     uint32_t    colourK = 16;           // spmvHipColourCSR: rounds per host check
     uint32_t    aggK = 16;              // spmvHipAggregateCSR: rounds per host check
     uint32_t    krylovK[2] = {16, 16};  // hipSpCGCSR, hipSpBiCGStabCSR: iterations per host check
+    uint32_t    krylovBlockK[2] = {16, 16};   // hipSpCGBlockCSR, hipSpBiCGStabBlockCSR: the same
     int         ldsOrder = -1;          // lds_order_probe_kernel: -1 not run yet, 1 lane-ascending + in issue order, 0 anything else
     bool        ellRowLens = true;
     bool        unitValues = true;      // look for "every stored value is the same double" at upload (spmvHipSetUnitValues)

@@ -327,13 +327,13 @@ static int krylovArgs(const char* who, spmat* dA, spmat* dM, const double* dB, d
             return EXIT_FAILURE;
         }
     }
+    *pa = a;
+    *pm = m;
     if (a->M == 0) {
         if (history) history[0] = 0.0;
         if (info) *info = spmvKrylovInfo{SPMV_KRYLOV_CONVERGED, 0, 0.0, 0.0, 0, 0, 0.0};
         return 2;
     }
-    *pa = a;
-    *pm = m;
     return 0;
 }
 
@@ -348,6 +348,90 @@ static int krylov(int bicg, spmat* dA, spmat* dM, const double* dB, double* dX, 
 }
 int hipSpCGCSR(spmat* dA, spmat* dM, const double* dB, double* dX, const spmvKrylovOpts* opts, spmvKrylovInfo* info) { return krylov(0, dA, dM, dB, dX, opts, info); }
 int hipSpBiCGStabCSR(spmat* dA, spmat* dM, const double* dB, double* dX, const spmvKrylovOpts* opts, spmvKrylovInfo* info) { return krylov(1, dA, dM, dB, dX, opts, info); }
+
+// ---- blocks of right-hand sides (contract in spmvHip.h, design in DESIGN.md section 27)
+// a dense rows x k operand: its layout and leading dimension
+static bool denseOk(const char* who, const char* name, uint64_t rows, unsigned k, size_t ld, int layout) {
+    if (layout != SPMV_DENSE_ROW_MAJOR && layout != SPMV_DENSE_COL_MAJOR) { ERR("%s: unknown layout %d", who, layout); return false; }
+    const uint64_t need = layout == SPMV_DENSE_ROW_MAJOR ? k : rows;     // ld >= k (row-major) or >= the rows (column-major)
+    if (ld < need) { ERR("%s: leading dimension %s = %zu is below %lu", who, name, ld, (unsigned long)need); return false; }
+    return true;
+}
+
+int spmvHipBlockDot(size_t n, unsigned k, const double* dU, size_t ldu, int uLayout, const double* dV, size_t ldv, int vLayout,
+                    double* dH) {
+    const char* who = "spmvHipBlockDot";
+    const Ctx cx = libraryCtx();
+    if (!ready(who)) return EXIT_FAILURE;
+    if (!dH || (n && (!dU || !dV))) { ERR("%s: %s is NULL", who, !dH ? "dH" : !dU ? "dU" : "dV"); return EXIT_FAILURE; }
+    if (k == 0) { ERR("%s: k = 0 columns", who); return EXIT_FAILURE; }
+    if (!denseOk(who, "ldu", n, k, ldu, uLayout) || !denseOk(who, "ldv", n, k, ldv, vLayout)) return EXIT_FAILURE;
+    const bool uRow = uLayout == SPMV_DENSE_ROW_MAJOR, vRow = vLayout == SPMV_DENSE_ROW_MAJOR;
+    Launch L(cx, dim3(k), dim3(KT));
+    if (enqueueBlockDot(n, k, dU, uRow ? ldu : 1, uRow ? 1 : ldu, dV, vRow ? ldv : 1, vRow ? 1 : ldv, dH, cx.stream)) {
+        ERR("%s: launch failed", who);
+        return EXIT_FAILURE;
+    }
+    return L.finish(who);
+}
+
+static int krylovBlock(int bicg, spmat* dA, spmat* dM, unsigned k, const double* dB, size_t ldb, int bLayout, double* dX, size_t ldx,
+                       int xLayout, const spmvKrylovOpts* opts, spmvKrylovColumn* cols, spmvKrylovInfo* info) {
+    const char* who = bicg ? "hipSpBiCGStabBlockCSR" : "hipSpCGBlockCSR";
+    if (!ready(who)) return EXIT_FAILURE;
+    if (k == 0) { ERR("%s: k = 0 columns", who); return EXIT_FAILURE; }
+    if (dM && dM->dev && dM->dev != SPMAT_TAG_ELL_TRANSPOSED) {
+        const DevMat* h = anyDescOf(dM, who);
+        if (h && h->origin == Origin::HIERARCHY) {
+            ERR("%s: dM is a multigrid hierarchy: its cycle takes one vector at a time (hipSpCGCSR / hipSpBiCGStabCSR take it)", who);
+            return EXIT_FAILURE;
+        }
+    }
+    DevMat* a = nullptr;
+    DevMat* m = nullptr;
+    // (history and info stay with this function: they are per column)
+    const int rc = krylovArgs(who, dA, dM, dB, dX, opts, opts ? opts->tol : 0.0, opts ? opts->maxIter : 0, nullptr, nullptr, &a, &m);
+    if (rc == EXIT_FAILURE) return EXIT_FAILURE;
+    if (!denseOk(who, "ldb", a->M, k, ldb, bLayout) || !denseOk(who, "ldx", a->M, k, ldx, xLayout)) return EXIT_FAILURE;
+    const unsigned __int128 spanB = denseSpan(a->M, k, ldb, bLayout), spanX = denseSpan(a->M, k, ldx, xLayout);
+    const unsigned __int128 b0 = (uintptr_t)dB, x0 = (uintptr_t)dX;
+    if (spanB && spanX && b0 < x0 + spanX && x0 < b0 + spanB) { ERR("%s: dB and dX overlap", who); return EXIT_FAILURE; }
+    if (opts->history && opts->maxIter >= (SIZE_MAX / sizeof(double)) / k - 1) {
+        ERR("%s: a history of k * (maxIter + 1) = %u * (%lu + 1) doubles does not fit", who, k, (unsigned long)opts->maxIter);
+        return EXIT_FAILURE;
+    }
+    if (rc == 2) {                                                       // M = 0: every column CONVERGED, 0; no kernel
+        for (unsigned c = 0; c < k; ++c) {
+            if (opts->history) opts->history[(size_t)c * (opts->maxIter + 1)] = 0.0;
+            if (cols) cols[c] = spmvKrylovColumn{SPMV_KRYLOV_CONVERGED, 0, 0.0, 0.0};
+        }
+        if (info) *info = spmvKrylovInfo{SPMV_KRYLOV_CONVERGED, 0, 0.0, 0.0, 0, 0, 0.0};
+        return EXIT_SUCCESS;
+    }
+    const bool bRow = bLayout == SPMV_DENSE_ROW_MAJOR, xRow = xLayout == SPMV_DENSE_ROW_MAJOR;
+    if (k == 1 && (bRow ? ldb : 1) == 1 && (xRow ? ldx : 1) == 1) {      // one plain vector: the single solve
+        spmvKrylovInfo one{};
+        if (krylovSolve(bicg, dA, a, m, dB, dX, opts, &one, S.krylovBlockK[bicg], S.stream)) { ERR("%s: the solve failed", who); return EXIT_FAILURE; }
+        if (cols) cols[0] = spmvKrylovColumn{one.status, one.iterations, one.rr, one.bb};
+        if (info) *info = one;
+        return EXIT_SUCCESS;
+    }
+    if (krylovBlockSolve(bicg, a, m, k, dB, bRow ? ldb : 1, bRow ? 1 : ldb, dX, xRow ? ldx : 1, xRow ? 1 : ldx, opts, cols, info,
+                         S.krylovBlockK[bicg], S.stream)) {
+        ERR("%s: the solve failed", who);
+        return EXIT_FAILURE;
+    }
+    return EXIT_SUCCESS;
+}
+int hipSpCGBlockCSR(spmat* dA, spmat* dM, unsigned k, const double* dB, size_t ldb, int bLayout, double* dX, size_t ldx, int xLayout,
+                    const spmvKrylovOpts* opts, spmvKrylovColumn* cols, spmvKrylovInfo* info) {
+    return krylovBlock(0, dA, dM, k, dB, ldb, bLayout, dX, ldx, xLayout, opts, cols, info);
+}
+int hipSpBiCGStabBlockCSR(spmat* dA, spmat* dM, unsigned k, const double* dB, size_t ldb, int bLayout, double* dX, size_t ldx,
+                          int xLayout, const spmvKrylovOpts* opts, spmvKrylovColumn* cols, spmvKrylovInfo* info) {
+    return krylovBlock(1, dA, dM, k, dB, ldb, bLayout, dX, ldx, xLayout, opts, cols, info);
+}
+
 int hipSpGMRESCSR(spmat* dA, spmat* dM, const double* dB, double* dX, const spmvGmresOpts* opts, spmvKrylovInfo* info) {
     const char* who = "hipSpGMRESCSR";
     if (opts && (opts->restart == 0 || opts->restart > 64)) {

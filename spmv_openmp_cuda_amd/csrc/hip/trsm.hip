@@ -16,7 +16,8 @@
 //     shuffles from the slots that hold a strict-triangle entry (the same sum on every slot; slot 0 stores).
 //   * runs of thin levels: one workgroup of 1 024 lanes per panel walks the run's levels, 1 024 / P rows at a time, with
 //     the drain-and-barrier hand-off of trsv_run_kernel.  Panels never read each other's columns, so they need no order.
-// Lanes whose column is past the panel's width load and store nothing.  No flags, tickets, spins or atomics: ordering
+// Lanes whose column is past the panel's width load and store nothing.  A caller may hand a stop word (the block Krylov
+// loops do): every launch that finds it set when it starts returns at once; hipSpTRSMCSR hands none.  No flags, tickets, spins or atomics: ordering
 // across workgroups comes only from kernel boundaries on one stream, inside a run from the workgroup barrier.
 #include <hip/hip_runtime.h>
 
@@ -44,6 +45,7 @@ struct TrsmArgs {
     const uint32_t* JA;
     const double*   AS;
     const uint32_t* diagPos;
+    const uint32_t* stop;                           // null, or a word that ends every launch at once when it is not 0
     const double*   B;
     double*         X;
     double   unitValue;
@@ -91,6 +93,7 @@ __global__ __launch_bounds__(TRSM_THREADS) void trsm_level_kernel(uint32_t begin
                                                                   uint32_t shortBlocks, uint64_t nBlocks,
                                                                   const I* __restrict__ IRP, const TrsmArgs a) {
     static_assert(P >= 1 && P <= (int)TRSM_PANEL && (P & (P - 1)) == 0, "panel width");
+    if (a.stop && *a.stop) return;                                       // a stopped block Krylov loop (krylov_block.hip)
     const uint64_t lin = linear_block();
     if (lin >= nBlocks * a.panels) return;                               // the fold of grid2d
     const uint64_t blk = lin / a.panels;
@@ -154,8 +157,9 @@ __global__ __launch_bounds__(TRSM_RUN_THREADS) void trsm_run_kernel(uint32_t l0,
                                                                     const uint32_t* __restrict__ levelPtr,
                                                                     const I* __restrict__ IRP, const TrsmArgs a) {
     static_assert(P >= 1 && P <= (int)TRSM_PANEL && (P & (P - 1)) == 0, "panel width");
+    if (a.stop && *a.stop) return;                                       // workgroup-uniform, as the next line: in front of every barrier
     const uint64_t panel = linear_block();
-    if (panel >= a.panels) return;                                       // workgroup-uniform, in front of every barrier
+    if (panel >= a.panels) return;
     const uint32_t c0 = (uint32_t)panel * TRSM_PANEL;
     const uint32_t w = a.k - c0 < TRSM_PANEL ? a.k - c0 : TRSM_PANEL;
     const uint32_t cl = threadIdx.x % P, g = threadIdx.x / P;
@@ -213,10 +217,10 @@ void launchWidth(const DevMat* d, const TriSchedule* s, const TrsmArgs& a, bool 
 }  // namespace
 
 int enqueueTrsm(const DevMat* d, int uplo, int diag, uint32_t k, const double* B, uint64_t sbr, uint64_t sbc, double* X,
-                uint64_t ldx, bool xRowMajor, hipStream_t st, dim3* grid, dim3* block) {
+                uint64_t ldx, bool xRowMajor, hipStream_t st, dim3* grid, dim3* block, const uint32_t* stop) {
     const TriSchedule* s = d->tri[uplo];
     TrsmArgs a;
-    a.perm = s->perm; a.JA = d->JA; a.AS = d->AS; a.diagPos = s->diagPos; a.B = B; a.X = X;
+    a.perm = s->perm; a.JA = d->JA; a.AS = d->AS; a.diagPos = s->diagPos; a.stop = stop; a.B = B; a.X = X;
     a.unitValue = d->unitValue;
     a.N = d->N; a.sbr = sbr; a.sbc = sbc; a.ldx = ldx;
     a.k = k; a.panels = k / TRSM_PANEL + (k % TRSM_PANEL != 0);
