@@ -719,7 +719,41 @@ int spmvHipCsrAddRefresh(spmat* dC, double alpha, spmat* dA, double beta, spmat*
  * Refused with a message and EXIT_FAILURE, outputs untouched: NULL dA, dM, dR or dZ; handles that are not live; for the
  *   setup the refusals of spmvHipAggregateCSR, dM == dA, a source without column or value array, a row without exactly one
  *   stored diagonal entry, omega negative or not finite, maxLevels > SPMV_AMG_MAX_LEVELS; a dM that is not a hierarchy; a
- *   dA that is not the source; dR and dZ overlapping; a level beyond the last. */
+ *   dA that is not the source; dR and dZ overlapping; a level beyond the last.
+ *
+ * Smoothed aggregation.  spmvHipAmgSetupSmoothed writes a hierarchy of the same kind -- freed by
+ *   hipFreeSpmat, refused by every matrix entry point, taken by spmvHipAmgApply / Refresh / Info / Level and as dM of
+ *   hipSpCGCSR / hipSpBiCGStabCSR / hipSpGMRESCSR; the block solvers refuse it like any hierarchy -- whose prolongator is
+ *   damped-Jacobi smoothed.  opts, dinv_l, the stop rules and agg_l are those of spmvHipAmgSetup; per level that is not the last:
+ *       T_l  = the unit-value M_l x nAgg_l handle with the one entry (i, agg_l[i]) = 1.0 per row   (spmvHipAmgSetup's P_l)
+ *       s_i  = +0.0; for p in A_l.IRP[i] .. A_l.IRP[i+1]-1 (stored order): s_i = s_i + fabs(A_l.AS[p])
+ *       g_i  = fabs(dinv_l[i]) * s_i;   rho_l = max_i g_i
+ *       w_l  = smooth->omegaP != 0 ? smooth->omegaP : (4.0 / 3.0) / rho_l             (two rounded divisions, as written)
+ *       D_l  = the M_l x M_l CSR handle with the one entry (i, i) = dinv_l[i] per row
+ *       P_l  = spmvHipCsrAdd(1.0, T_l, -w_l, spmvHipSpGEMM(D_l, spmvHipSpGEMM(A_l, T_l)))
+ *       R_l  = spmvHipCsrTranspose(P_l);   A_{l+1} = spmvHipSpGEMM(R_l, spmvHipSpGEMM(A_l, P_l))
+ *   Every array of P_l, R_l and A_{l+1} is what those calls give; only s_i, g_i and w_l are arithmetic of this entry point
+ *   (the max of non-negative doubles does not depend on its order).  smooth == NULL: omegaP = 0.  On the 7-point Laplacian
+ *   the default gives w_0 = 2/3 exactly.  T_l, D_l, A_l T_l, D_l (A_l T_l) and A_l P_l are kept (the refresh reads them) and
+ *   counted in info.bytes; info.tempBytes also covers the sums' temporaries; the other fields mean what they mean above.
+ *   Refused besides what spmvHipAmgSetup refuses, outputs untouched: an omegaP that is negative or not finite; a level with
+ *   a g_i that is not finite, or with rho_l = 0 (the line names the first such row and its level).
+ *   The cycle is V(l, r) above with its correction line replaced by
+ *       for each i:  s = +0.0;  for p in P_l.IRP[i] .. P_l.IRP[i+1]-1 (stored order):  s = s + P_l.AS[p] * e[P_l.JA[p]]
+ *                    z_i = z_i + s
+ *   the serial-order SpMV with P_l followed by an add, no FMA.  A level whose P_l has no row longer than n entries does it in
+ *   ONE kernel (a lane walks two rows of P_l); a level with a longer row in two, spmvHipEnqueueAutoRows(P_l, e, d) and
+ *   z = z + d (the same bits).  n = 0 (never fused: the two-kernel form measured faster) unless
+ *   spmvHipSetVariant("spmvHipAmgApply", n), 0 <= n <= 4096 (64 is the long-row convention of the other kernels), read at the
+ *   SETUP, so Apply still only enqueues: kernels only, capturable, no allocation.  One cycle enqueues
+ *       (L - 1) * (s(nu1) + 3 + 1 + 2 * nu2) + s(nuCoarse) + (the levels whose correction is not fused)
+ *   kernels.  A hierarchy of spmvHipAmgSetup keeps its gather, its bits and its count.
+ *   spmvHipAmgRefresh on a smoothed hierarchy: per level dinv_l, rho_l and w_l, D_l's values, then the refreshes of
+ *   A_l T_l, D_l (A_l T_l), P_l (spmvHipCsrAddRefresh with the new w_l), R_l, A_l P_l and A_{l+1}; aggregates and every
+ *   pattern stay (all patterns are structural), device addresses are kept.  Bit-identical to a fresh setup.
+ * spmvHipAmgProlongator: a view like spmvHipAmgLevel's of a level that is not the last: *dPl, *dRl = copies of P_l's and
+ *   R_l's spmat with dev = NULL (the arrays stay dM's), *omegaP = w_l.  Any of the three may be NULL.  On a hierarchy of
+ *   spmvHipAmgSetup: the unit P_l, its R_l and 0.0.  Refused: a dM that is not a hierarchy, the last level and beyond. */
 #define SPMV_AMG_MAX_LEVELS 16
 #define SPMV_AMG_NO_SWEEPS  0xFFFFFFFFu
 typedef struct {
@@ -760,6 +794,11 @@ int spmvHipAmgRefresh(spmat* dM, spmat* dA);
 int spmvHipAmgApply(spmat* dM, spmat* dA, const double* dR, double* dZ);
 int spmvHipAmgInfo(spmat* dM, spmvAmgInfo* info);
 int spmvHipAmgLevel(spmat* dM, unsigned level, spmat* dAl, const uint32_t** dAgg, const double** dDinv);
+typedef struct {            /* 0 = the built-in default */
+    double omegaP;          /* prolongator damping; 0: per level (4/3) / rho_l; else used on every level */
+} spmvAmgSmoothOpts;
+int spmvHipAmgSetupSmoothed(spmat* dA, const spmvAmgOpts* opts, const spmvAmgSmoothOpts* smooth, spmat* dM, spmvAmgInfo* info);
+int spmvHipAmgProlongator(spmat* dM, unsigned level, spmat* dPl, spmat* dRl, double* omegaP);
 /* Release the device arrays behind a handle (cudaUtils.h:70-78). */
 int hipFreeSpmat(spmat* dMat);
 
@@ -1014,6 +1053,10 @@ int spmvHipProbeLdsAtomicOrder(void);
  *                             (default 0).  x does not change by a bit.
  *   spmvHipColourCSR          K, 1..4096: rounds enqueued per read-back of the colouring's device state (default 16,
  *                             unmeasured).  No colour changes.
+ *   spmvHipAmgApply           n, 0..4096: hierarchies set up by spmvHipAmgSetupSmoothed AFTER the call correct in one fused
+ *                             kernel on every level whose prolongator has no row longer than n entries (default 0 = never
+ *                             fused, an SpMV and an add: the faster form on the 5 M-row Laplacian, DESIGN.md section 28;
+ *                             64 is the long-row convention).  z does not change by a bit.
  * Returns EXIT_FAILURE for an unknown (launcher, variant). */
 int spmvHipSetVariant(const char* launcher, int variant);
 /* Use the RL array for ELL early exit (1, default when RL was uploaded) or walk

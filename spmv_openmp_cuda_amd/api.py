@@ -129,6 +129,8 @@ _sigs = {
     "spmvHipAmgApply": ([C.POINTER(spmat), C.POINTER(spmat), _vp, _vp], _i),
     "spmvHipAmgInfo": ([C.POINTER(spmat), _vp], _i),
     "spmvHipAmgLevel": ([C.POINTER(spmat), C.c_uint, C.POINTER(spmat), C.POINTER(_vp), C.POINTER(_vp)], _i),
+    "spmvHipAmgSetupSmoothed": ([C.POINTER(spmat), _vp, _vp, C.POINTER(spmat), _vp], _i),
+    "spmvHipAmgProlongator": ([C.POINTER(spmat), C.c_uint, C.POINTER(spmat), C.POINTER(spmat), C.POINTER(C.c_double)], _i),
 }
 SPMV_DENSE_ROW_MAJOR, SPMV_DENSE_COL_MAJOR = 0, 1          # include/spmvHip.h: layouts of hipSpMMRowsCSR's X and Y
 SPMV_TRI_LOWER, SPMV_TRI_UPPER = 0, 1                      # include/spmvHip.h: hipSpTRSVCSR's uplo ...
@@ -263,6 +265,11 @@ class spmvAmgInfo(C.Structure):
     _fields_ = [("levels", C.c_uint), ("rows", C.c_ulong * SPMV_AMG_MAX_LEVELS), ("nnz", C.c_ulong * SPMV_AMG_MAX_LEVELS),
                 ("aggregates", C.c_ulong * SPMV_AMG_MAX_LEVELS), ("opComplexity", C.c_double), ("bytes", C.c_ulong),
                 ("tempBytes", C.c_ulong), ("ms", C.c_double)]
+
+
+class spmvAmgSmoothOpts(C.Structure):
+    """include/spmvHip.h `spmvAmgSmoothOpts`: the damping of the smoothed prolongator (0: (4/3) / rho_l per level)."""
+    _fields_ = [("omegaP", C.c_double)]
 
 
 SPMV_COLOUR_NATURAL, SPMV_COLOUR_HASH = 0, 1
@@ -814,16 +821,25 @@ class DeviceMatrix:
             _check(lib.spmvHipAggregateCSR(C.byref(self.handle), C.byref(opts), buf.ptr, C.byref(info)), "spmvHipAggregateCSR")
             return (buf.down(np.uint32) if M else np.zeros(0, np.uint32)), info
 
-    def amg(self, seed=0, coarseRows=None, maxLevels=None, omega=None, nu1=None, nu2=None, nuCoarse=None) -> "AmgHierarchy":
+    def amg(self, seed=0, coarseRows=None, maxLevels=None, omega=None, nu1=None, nu2=None, nuCoarse=None, smoothed=False,
+            omegaP=None) -> "AmgHierarchy":
         """spmvHipAmgSetup: an aggregation multigrid hierarchy of this square matrix (include/spmvHip.h states the loops).
         None: the built-in default (512, 16, 2/3, 1, 1, 8); nu1 / nu2 / nuCoarse = 0 asks for no sweeps.  The result is
-        accepted as `precond=` by cg / bicgstab / gmres of this matrix."""
+        accepted as `precond=` by cg / bicgstab / gmres of this matrix.  smoothed: spmvHipAmgSetupSmoothed, the
+        prolongator T - omegaP D^-1 A T (omegaP None: (4/3) / rho_l per level)."""
         def sweeps(v):
             return 0 if v is None else SPMV_AMG_NO_SWEEPS if int(v) == 0 else int(v)
         opts = spmvAmgOpts(int(seed) & 0xFFFFFFFF, int(coarseRows or 0), int(maxLevels or 0), float(omega or 0.0), sweeps(nu1),
                            sweeps(nu2), sweeps(nuCoarse))
         h = AmgHierarchy(self)
-        _check(lib.spmvHipAmgSetup(C.byref(self.handle), C.byref(opts), C.byref(h.handle), C.byref(h.info)), "spmvHipAmgSetup")
+        if smoothed:
+            smooth = spmvAmgSmoothOpts(float(omegaP or 0.0))
+            _check(lib.spmvHipAmgSetupSmoothed(C.byref(self.handle), C.byref(opts), C.byref(smooth), C.byref(h.handle), C.byref(h.info)),
+                   "spmvHipAmgSetupSmoothed")
+        else:
+            if omegaP is not None:
+                raise SpmvHipError("amg: omegaP is the damping of the smoothed prolongator (smoothed=True)")
+            _check(lib.spmvHipAmgSetup(C.byref(self.handle), C.byref(opts), C.byref(h.handle), C.byref(h.info)), "spmvHipAmgSetup")
         h.rows = int(h.handle.M)
         return h
 
@@ -978,7 +994,7 @@ class DeviceMatrix:
 
 class AmgHierarchy(DeviceMatrix):
     """What DeviceMatrix.amg() returns: a hierarchy handle (no matrix: SpMV, formats and solves refuse it) with `info`
-    (spmvAmgInfo), apply(), refresh_from(), level() and free().  It keeps a reference to its source matrix."""
+    (spmvAmgInfo), apply(), refresh_from(), level(), prolongator() and free().  It keeps a reference to its source matrix."""
 
     def __init__(self, source):
         super().__init__()
@@ -1006,6 +1022,21 @@ class AmgHierarchy(DeviceMatrix):
         view, agg, dinv = spmat(), C.c_void_p(), C.c_void_p()
         _check(lib.spmvHipAmgLevel(C.byref(self.handle), int(l), C.byref(view), C.byref(agg), C.byref(dinv)), "spmvHipAmgLevel")
         return view, agg.value, dinv.value
+
+    def prolongator(self, l):
+        """spmvHipAmgProlongator: (P, R, omegaP) of level l (not the last): P_l and R_l as host CSR arrays (M, N, IRP, JA,
+        AS), downloaded, and the damping w_l (0.0 on a hierarchy that is not smoothed)"""
+        P, R, w = spmat(), spmat(), C.c_double()
+        _check(lib.spmvHipAmgProlongator(C.byref(self.handle), int(l), C.byref(P), C.byref(R), C.byref(w)), "spmvHipAmgProlongator")
+
+        def down(v):
+            M, NZ = int(v.M), int(v.NZ)
+            out = [np.empty(M + 1, np.uint32), np.empty(NZ, np.uint32), np.empty(NZ, np.float64)]
+            for a, ptr in zip(out, (v.IRP, v.JA, v.AS)):
+                if a.size:
+                    _check(lib.spmvHipMemcpyDown(a.ctypes.data_as(C.c_void_p), C.cast(ptr, C.c_void_p), a.nbytes), "spmvHipMemcpyDown")
+            return M, int(v.N), out[0], out[1], out[2]
+        return down(P), down(R), w.value
 
     def free(self):
         super().free()

@@ -153,6 +153,7 @@ int spmvHipSetVariant(const char* launcher, int variant) {
     if (!strcmp(launcher, "hipSpGMRESCSR") && (variant == 0 || variant == 1)) { S.gmresFused = variant; return EXIT_SUCCESS; }
     if (!strcmp(launcher, "spmvHipColourCSR") && variant >= 1 && variant <= 4096) { S.colourK = (uint32_t)variant; return EXIT_SUCCESS; }
     if (!strcmp(launcher, "spmvHipAggregateCSR") && variant >= 1 && variant <= 4096) { S.aggK = (uint32_t)variant; return EXIT_SUCCESS; }
+    if (!strcmp(launcher, "spmvHipAmgApply") && variant >= 0 && variant <= 4096) { S.amgFuseMax = (uint32_t)variant; return EXIT_SUCCESS; }
     ERR("spmvHipSetVariant: unknown (%s, %d)", launcher, variant);
     return EXIT_FAILURE;
 }

@@ -18,6 +18,12 @@
 // (spmvHipCsrTranspose, spmvHipSpGEMM), so their bits are pinned there.  The cycle's vector kernels are ops of the Krylov
 // files' fused-pass kernel (krylov.hpp: 16-byte accesses when every pointer allows, the same bits otherwise), each with the
 // stop pointer of a Krylov loop.
+//
+// Smoothed aggregation (spmvHipAmgSetupSmoothed).  The same build with P_l = T_l - w_l D_l^-1 A_l T_l
+// chained from the public sum and products: T_l is the unit prolongator above, D_l the diagonal handle of dinv_l, and
+// A_l T_l, D_l (A_l T_l) are kept for the refresh.  w_l comes from amg_rho_kernel (row sums of |a_ij|, an integer max on the
+// bit pattern).  The cycle's correction is then z = z + P_l e: one fused launch (amg_prolong_kernel, a lane walks two rows of
+// P_l) on a level whose P_l has no row above the threshold read at setup, else P_l's serial-order SpMV into d_l and AmgAddOp.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <chrono>
@@ -31,8 +37,11 @@ namespace spmvhip {
 
 struct AmgLevel {
     spmat A{}, P{}, R{}, AP{};          // A: levels below 0 only (level 0 is the caller's); P, R, AP: all but the last level
+    spmat T{}, D{}, AT{}, DAT{};        // smoothed, all but the last level: the unit prolongator, diag(dinv), A T, D (A T)
     uint64_t M = 0, nnz = 0, nAgg = 0;
-    const uint32_t* agg = nullptr;      // P's column array
+    const uint32_t* agg = nullptr;      // the column array of the unit prolongator (P, or T when smoothed)
+    double w = 0.0;                     // smoothed: the damping of P
+    bool fused = false;                 // smoothed: no row of P is above the threshold, the correction is one pass
     double* dinv = nullptr;
     double *r = nullptr, *z = nullptr;  // below level 0: the restricted residual and the correction
     double *t = nullptr, *d = nullptr;
@@ -41,6 +50,9 @@ struct AmgLevel {
 struct AmgHierarchy {
     uint32_t seed = 0, nu1 = 1, nu2 = 1, nuCoarse = 8;
     double omega = 2.0 / 3.0;
+    bool smoothed = false;
+    double omegaP = 0.0;                // smoothed: the caller's damping of P, 0: (4/3) / rho_l per level
+    uint32_t fuseMax = 0;               // smoothed: the longest row of P that the fused correction takes (0: never fused)
     std::vector<AmgLevel> lv;
     spmvAmgInfo info{};
 };
@@ -228,6 +240,25 @@ __global__ __launch_bounds__(AG_THREADS) void amg_dinv_kernel(uint64_t M, const 
     dinv[r] = 1.0 / dv;
 }
 
+// g_i = |dinv_i| * (the sum of |a_ip| in stored order); *rhoBits = the largest g_i as bits (non-negative doubles order as
+// their bit patterns), *bad = the first row whose g_i is not finite
+template <typename I>
+__global__ __launch_bounds__(AG_THREADS) void amg_rho_kernel(uint64_t M, const I* __restrict__ IRP, const double* __restrict__ AS,
+                                                             const double* __restrict__ dinv, unsigned long long* __restrict__ rhoBits,
+                                                             uint32_t* __restrict__ bad) {
+    const uint64_t r = linear_block() * AG_THREADS + threadIdx.x;
+    unsigned long long bits = 0;
+    if (r < M) {
+        double s = 0.0;
+        for (uint64_t p = IRP[r], e = IRP[r + 1]; p < e; ++p) s = s + fabs(AS[p]);
+        const double g = fabs(dinv[r]) * s;
+        if (isfinite(g)) bits = (unsigned long long)__double_as_longlong(g);
+        else atomicMin(bad, (uint32_t)r);
+    }
+    for (int off = 32; off; off >>= 1) bits = max(bits, (unsigned long long)__shfl_xor(bits, off));
+    if (threadIdx.x % 64 == 0 && bits) atomicMax(rhoBits, bits);
+}
+
 // ------------------------------------------------------------------------------------------------ the cycle's passes
 struct StopMode {
     const uint32_t* stop;
@@ -284,6 +315,36 @@ struct AmgCorrectOp : StopMode {                // z = z + e[agg]
         st2<VEC>(z, i, two, make_double2(v.z.x + v.e.x, v.z.y + v.e.y));
     }
 };
+// z = z + P e in one launch (the prolong-and-correct pass of a smoothed level whose P has short rows): a lane takes two
+// consecutive rows of P and walks both in stored order, each sum from +0.0 -- two independent chains per lane, every lane
+// of the grid its own pair, so the gathers of e overlap across the rows instead of queueing behind one lane's walk.  The
+// row bounds come as one 8-byte load (i is even, irp a whole allocation), z as one 16-byte access when VEC.
+template <bool VEC>
+__global__ __launch_bounds__(AG_THREADS) void amg_prolong_kernel(uint64_t M, const uint32_t* __restrict__ irp, const uint32_t* __restrict__ ja,
+                                                                 const double* __restrict__ as, const double* __restrict__ e, double* __restrict__ z,
+                                                                 const uint32_t* __restrict__ stop) {
+    const uint64_t i = (linear_block() * AG_THREADS + threadIdx.x) * 2;
+    if (i >= M || (stop && *stop)) return;
+    const bool two = i + 1 < M;
+    const uint2 b = *reinterpret_cast<const uint2*>(irp + i);
+    const uint32_t n0 = b.y - b.x, n1 = two ? irp[i + 2] - b.y : 0u, n = max(n0, n1);
+    double s0 = 0.0, s1 = 0.0;
+    for (uint32_t k = 0; k < n; ++k) {
+        if (k < n0) s0 = s0 + as[b.x + k] * e[ja[b.x + k]];
+        if (k < n1) s1 = s1 + as[b.y + k] * e[ja[b.y + k]];
+    }
+    const double2 zv = ld2<VEC>(z, i, two);
+    st2<VEC>(z, i, two, make_double2(zv.x + s0, zv.y + s1));
+}
+struct AmgAddOp : StopMode {                    // z = z + d
+    static constexpr int NDOT = 0;
+    const double* d; double* z;
+    struct R { double2 d, z; };
+    template <bool VEC> __device__ void load(uint64_t i, bool two, R& v) const { v.d = ld2<VEC>(d, i, two); v.z = ld2<VEC>(z, i, two); }
+    template <bool VEC> __device__ void step(uint64_t i, bool two, const R& v, double&, double&) const {
+        st2<VEC>(z, i, two, make_double2(v.z.x + v.d.x, v.z.y + v.d.y));
+    }
+};
 
 DevMat* matOf(spmat* h) { return static_cast<DevMat*>(h->dev); }
 
@@ -299,6 +360,39 @@ int levelDinv(const DevMat* a, double* dinv, long* badRow, hipStream_t st) {
         }))
         return EXIT_FAILURE;
     if (bad != UNDECIDED) *badRow = (long)bad;
+    return EXIT_SUCCESS;
+}
+
+// rho of one level (the largest |dinv_i| * sum_p |a_ip|); *badRow >= 0: the first row where that is not finite
+int levelRho(const DevMat* a, const double* dinv, double* rho, long* badRow, hipStream_t st) {
+    struct { unsigned long long bits; uint32_t bad, pad; } h{0, UNDECIDED, 0};
+    TempBuf buf;
+    *badRow = -1;
+    if (buf.alloc(sizeof h) != hipSuccess || hipMemcpyAsync(buf.p, &h, sizeof h, hipMemcpyHostToDevice, st) != hipSuccess) return EXIT_FAILURE;
+    withIrp(a, [&](auto irp) {
+        hipLaunchKernelGGL((amg_rho_kernel<IrpT<decltype(irp)>>), gridFor(a->M), dim3(AG_THREADS), 0, st, a->M, irp, a->AS, dinv,
+                           buf.as<unsigned long long>(), buf.as<uint32_t>() + 2);
+    });
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&h, buf.p, sizeof h, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+        return EXIT_FAILURE;
+    if (h.bad != UNDECIDED) *badRow = (long)h.bad;
+    memcpy(rho, &h.bits, 8);
+    return EXIT_SUCCESS;
+}
+
+// w of a smoothed level: the caller's damping, or (4/3) / rho; refuses (with its line) a row sum that is not finite and rho = 0
+int levelDamping(const AmgHierarchy* H, const DevMat* a, const double* dinv, size_t l, const char* module, double* w, hipStream_t st) {
+    double rho = 0.0;
+    long bad = -1;
+    if (levelRho(a, dinv, &rho, &bad, st)) return buildFail(st, module, "the row sums");
+    const bool zero = bad < 0 && !(rho > 0.0);                 // every row sum is 0: row 0 is the first without a rho
+    if (bad >= 0 || zero) {
+        fprintf(stderr, "libspmvhip: %s: row %ld of level %zu: |dinv| * (the sum of |a_ij|) is %s, the damping of the prolongator needs 0 < rho < Inf\n",
+                module, zero ? 0l : bad, l, zero ? "0, as in every row" : "not finite");
+        return EXIT_FAILURE;
+    }
+    *w = H->omegaP != 0.0 ? H->omegaP : (4.0 / 3.0) / rho;
     return EXIT_SUCCESS;
 }
 
@@ -321,7 +415,7 @@ size_t handleBytes(const spmat* h) {
 void freeAmg(AmgHierarchy* h) {
     if (!h) return;
     for (AmgLevel& l : h->lv) {
-        for (spmat* m : {&l.A, &l.P, &l.R, &l.AP})
+        for (spmat* m : {&l.A, &l.P, &l.R, &l.AP, &l.T, &l.D, &l.AT, &l.DAT})
             if (m->dev) (void)hipFreeSpmat(m);
         for (double* p : {l.dinv, l.r, l.z, l.t, l.d}) (void)hipFree(p);
     }
@@ -406,9 +500,12 @@ int aggregateCsr(const DevMat* a, uint32_t seed, uint32_t K, uint32_t* dAgg, spm
     return EXIT_SUCCESS;
 }
 
-int amgBuild(spmat* hA, const spmvAmgOpts* o, uint32_t K, DevMat* m, hipStream_t st) {
+int amgBuild(spmat* hA, const spmvAmgOpts* o, const double* omegaP, uint32_t fuseMax, uint32_t K, DevMat* m, hipStream_t st) {
     const auto t0 = std::chrono::steady_clock::now();
     AmgHierarchy* H = m->amg = new AmgHierarchy;
+    H->smoothed = omegaP != nullptr;
+    H->omegaP = omegaP ? *omegaP : 0.0;
+    H->fuseMax = fuseMax;
     const uint64_t coarseRows = o && o->coarseRows ? o->coarseRows : 512;
     const uint32_t maxLevels = o && o->maxLevels ? o->maxLevels : SPMV_AMG_MAX_LEVELS;
     auto sweeps = [](unsigned v, uint32_t dflt) { return v == 0 ? dflt : v == SPMV_AMG_NO_SWEEPS ? 0u : v; };
@@ -456,9 +553,31 @@ int amgBuild(spmat* hA, const spmvAmgOpts* o, uint32_t K, DevMat* m, hipStream_t
         }
         L.nAgg = ai.aggregates;
         info.aggregates[l] = L.nAgg;
-        if (ownCsr(&L.P, L.M, L.nAgg, L.M, irp, agg, ones)) return fail("the prolongator");
-        L.agg = matOf(&L.P)->JA;
+        spmat* unitP = H->smoothed ? &L.T : &L.P;
+        if (ownCsr(unitP, L.M, L.nAgg, L.M, irp, agg, ones)) return fail("the prolongator");
+        L.agg = matOf(unitP)->JA;
         spmvSpgemmInfo s1{}, s2{};
+        if (H->smoothed) {                                     // P = T - w D (A T), by the public sum and products
+            if (levelDamping(H, a, L.dinv, l, "multigrid setup", &L.w, st)) return EXIT_FAILURE;
+            uint32_t *dIrp = nullptr, *dJa = nullptr;
+            double* dAs = nullptr;
+            ok = hipMalloc(&dIrp, (L.M + 1) * 4) == hipSuccess && hipMalloc(&dJa, L.M * 4) == hipSuccess && hipMalloc(&dAs, L.M * 8) == hipSuccess;
+            if (ok) {
+                enqueueIota(L.M + 1, dIrp, st);
+                enqueueIota(L.M, dJa, st);
+                ok = hipMemcpyAsync(dAs, L.dinv, L.M * 8, hipMemcpyDeviceToDevice, st) == hipSuccess && hipGetLastError() == hipSuccess &&
+                     hipStreamSynchronize(st) == hipSuccess;
+            }
+            if (!ok) { (void)hipFree(dIrp); (void)hipFree(dJa); (void)hipFree(dAs); return fail("the diagonal handle"); }
+            if (ownCsr(&L.D, L.M, L.M, L.M, dIrp, dJa, dAs)) return fail("the diagonal handle");
+            spmvAddInfo sa{};
+            if (spmvHipSpGEMM(cur, &L.T, nullptr, &L.AT, &s1) || spmvHipSpGEMM(&L.D, &L.AT, nullptr, &L.DAT, &s2) ||
+                spmvHipCsrAdd(1.0, &L.T, -L.w, &L.DAT, nullptr, &L.P, &sa))
+                return fail("a level's smoothed prolongator");
+            L.fused = sa.maxRowNnz <= H->fuseMax && matOf(&L.P)->irpBytes == 4;     // (a sum's row pointers are 4-byte)
+            info.tempBytes = std::max<ulong>(info.tempBytes, std::max({s1.tempBytes, s2.tempBytes, sa.tempBytes}));
+            info.bytes += handleBytes(&L.T) + handleBytes(&L.D) + handleBytes(&L.AT) + handleBytes(&L.DAT);
+        }
         if (spmvHipCsrTranspose(&L.P, &L.R) || spmvHipSpGEMM(cur, &L.P, nullptr, &L.AP, &s1)) return fail("a level's products");
         H->lv.emplace_back();
         if (spmvHipSpGEMM(&L.R, &L.AP, nullptr, &H->lv[l + 1].A, &s2)) { H->lv.pop_back(); return fail("a level's products"); }
@@ -466,6 +585,7 @@ int amgBuild(spmat* hA, const spmvAmgOpts* o, uint32_t K, DevMat* m, hipStream_t
         info.bytes += handleBytes(&L.P) + handleBytes(&L.R) + handleBytes(&L.AP);
         if (vec(&H->lv[l + 1].r, L.nAgg)) return fail("allocation of a level's vectors");
         if (warmSpmv(&L.R, L.d, H->lv[l + 1].r, st)) return fail("the SpMV selection of a restriction");
+        if (H->smoothed && !L.fused && warmSpmv(&L.P, H->lv[l + 1].r, L.d, st)) return fail("the SpMV selection of a prolongator");
     }
     double sum = 0;
     for (uint32_t l = 0; l < info.levels; ++l) sum += (double)info.nnz[l];
@@ -486,6 +606,15 @@ int amgRefresh(DevMat* m, spmat* hA, hipStream_t st) {
         if (bad >= 0) { fprintf(stderr, "libspmvhip: multigrid refresh: row %ld of level %zu lost its one diagonal entry\n", bad, l); return EXIT_FAILURE; }
         if (warmSpmv(cur, L.d, L.t, st)) return fail("the SpMV selection of a level");
         if (l + 1 == H->lv.size()) break;
+        if (H->smoothed) {
+            if (levelDamping(H, matOf(cur), L.dinv, l, "multigrid refresh", &L.w, st)) return EXIT_FAILURE;
+            if (hipMemcpyAsync(matOf(&L.D)->AS, L.dinv, L.M * 8, hipMemcpyDeviceToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess ||
+                spmvHipValuesChanged(&L.D))
+                return fail("the diagonal handle");
+            if (spmvHipSpGEMMRefresh(&L.AT, cur, &L.T, nullptr) || spmvHipSpGEMMRefresh(&L.DAT, &L.D, &L.AT, nullptr) ||
+                spmvHipCsrAddRefresh(&L.P, 1.0, &L.T, -L.w, &L.DAT, nullptr) || spmvHipTransposeRefresh(&L.R, &L.P))
+                return fail("a level's smoothed prolongator");
+        }
         if (spmvHipSpGEMMRefresh(&L.AP, cur, &L.P, nullptr) || spmvHipSpGEMMRefresh(&H->lv[l + 1].A, &L.R, &L.AP, nullptr)) return fail("a level's products");
     }
     H->info.ms = msSince(t0);
@@ -530,7 +659,19 @@ int enqueueAmgCycle(const DevMat* m, spmat* hA, const double* r0, double* z0, hi
         AmgLevel& L = H->lv[l];
         const double* r = l ? L.r : r0;
         double* z = l ? L.z : z0;
-        pass(L.M, AmgCorrectOp{{stop}, H->lv[l + 1].z, L.agg, z}, {z});
+        const double* e = H->lv[l + 1].z;
+        if (!H->smoothed) pass(L.M, AmgCorrectOp{{stop}, e, L.agg, z}, {z});
+        else if (L.fused) {
+            const DevMat* p = matOf(&L.P);
+            const dim3 grid = gridFor((L.M + 1) / 2);
+            const uint32_t* irp = static_cast<const uint32_t*>(p->IRP);
+            if (aligned16(z)) hipLaunchKernelGGL(amg_prolong_kernel<true>, grid, dim3(AG_THREADS), 0, st, L.M, irp, p->JA, p->AS, e, z, stop);
+            else              hipLaunchKernelGGL(amg_prolong_kernel<false>, grid, dim3(AG_THREADS), 0, st, L.M, irp, p->JA, p->AS, e, z, stop);
+            ++n;
+        } else {                                               // (d is free: the restriction consumed it)
+            if (spmv(&L.P, e, L.d)) return EXIT_FAILURE;
+            pass(L.M, AmgAddOp{{stop}, L.d, z}, {L.d, z});
+        }
         for (uint32_t s = 0; s < H->nu2; ++s)
             if (sweep(l, r, z)) return EXIT_FAILURE;
     }
@@ -549,6 +690,13 @@ void amgLevel(const DevMat* m, unsigned level, spmat* dAl, const uint32_t** dAgg
     }
     if (dAgg) *dAgg = L.agg;
     if (dDinv) *dDinv = L.dinv;
+}
+
+void amgProlongator(const DevMat* m, unsigned level, spmat* dPl, spmat* dRl, double* omegaP) {
+    const AmgLevel& L = m->amg->lv[level];
+    if (dPl) { *dPl = L.P; dPl->dev = nullptr; }
+    if (dRl) { *dRl = L.R; dRl->dev = nullptr; }
+    if (omegaP) *omegaP = m->amg->smoothed ? L.w : 0.0;
 }
 
 }  // namespace spmvhip

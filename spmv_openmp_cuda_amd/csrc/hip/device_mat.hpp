@@ -215,18 +215,22 @@ void freeAddPlan(AddPlan* p);
 // Aggregation multigrid (amg.hip; contracts in spmvHip.h, design in DESIGN.md section 24).  aggregateCsr: the aggregate ids
 // of the checked square handle into dAgg (M words), K rounds per host check; synchronous, allocates, temporaries freed
 // before it returns.  amgBuild: the hierarchy of the checked handle hA into m->amg, K aggregation rounds per host check (on
-// failure the caller frees m with whatever it holds); amgRefresh: the products and the inverse diagonals again.
+// failure the caller frees m with whatever it holds); omegaP non-null: the smoothed hierarchy of spmvHipAmgSetupSmoothed
+// (*omegaP 0: per level), fuseMax the longest row of a prolongator that its fused correction takes.  amgRefresh: the products,
+// the inverse diagonals and, smoothed, the prolongators again.  amgProlongator: spmvHipAmgProlongator's outputs for a level
+// below the last.
 // enqueueAmgCycle: z = V(0, r), kernels only on `stream`; every kernel of the cycle but its SpMVs returns at once when `stop`
 // is set and *stop != 0; *launches grows by the kernels enqueued (an SpMV counted as one).  amgInfo: what the setup or the
 // last refresh did.  amgLevel: spmvHipAmgLevel's outputs for a level below amgInfo()->levels.  ownCsr (upload.hip): a CSR
 // handle that takes ownership of three device arrays.
 int  aggregateCsr(const DevMat* a, uint32_t seed, uint32_t K, uint32_t* dAgg, spmvAggInfo* info, hipStream_t stream);
-int  amgBuild(spmat* hA, const spmvAmgOpts* opts, uint32_t K, DevMat* m, hipStream_t stream);
+int  amgBuild(spmat* hA, const spmvAmgOpts* opts, const double* omegaP, uint32_t fuseMax, uint32_t K, DevMat* m, hipStream_t stream);
 int  amgRefresh(DevMat* m, spmat* hA, hipStream_t stream);
 int  enqueueAmgCycle(const DevMat* m, spmat* hA, const double* r, double* z, hipStream_t stream, const uint32_t* stop,
                      unsigned long* launches);
 const spmvAmgInfo* amgInfo(const DevMat* m);
 void amgLevel(const DevMat* m, unsigned level, spmat* dAl, const uint32_t** dAgg, const double** dDinv);
+void amgProlongator(const DevMat* m, unsigned level, spmat* dPl, spmat* dRl, double* omegaP);
 void freeAmg(AmgHierarchy* h);
 int  ownCsr(spmat* dst, uint64_t M, uint64_t N, uint64_t NZ, uint32_t* dIRP, uint32_t* dJA, double* dAS);
 // Triangular solves (trsv.hip; contract in spmvHip.h, design in DESIGN.md section 17).  triAnalyse builds d->tri[uplo]

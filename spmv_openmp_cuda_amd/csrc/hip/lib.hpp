@@ -26,6 +26,8 @@ struct State {
     int         gmresFused = 0;         // hipSpGMRESCSR: fold the first CGS2 update into the second projection
     uint32_t    colourK = 16;           // spmvHipColourCSR: rounds per host check
     uint32_t    aggK = 16;              // spmvHipAggregateCSR: rounds per host check
+    uint32_t    amgFuseMax = 0;         // spmvHipAmgSetupSmoothed: the longest row of P_l that the fused correction takes; 0: never
+                                        // fused, the form that measured faster
     uint32_t    krylovK[2] = {16, 16};  // hipSpCGCSR, hipSpBiCGStabCSR: iterations per host check
     uint32_t    krylovBlockK[2] = {16, 16};   // hipSpCGBlockCSR, hipSpBiCGStabBlockCSR: the same
     int         ldsOrder = -1;          // lds_order_probe_kernel: -1 not run yet, 1 lane-ascending + in issue order, 0 anything else

@@ -232,8 +232,8 @@ int spmvHipAggregateCSR(spmat* dA, const spmvAggOpts* opts, uint32_t* dAgg, spmv
     return EXIT_SUCCESS;
 }
 
-int spmvHipAmgSetup(spmat* dA, const spmvAmgOpts* opts, spmat* dM, spmvAmgInfo* info) {
-    const char* who = "spmvHipAmgSetup";
+// the two setups: omegaP null for the plain hierarchy, else the damping of the smoothed prolongator (0: per level)
+static int amgSetup(const char* who, spmat* dA, const spmvAmgOpts* opts, const double* omegaP, spmat* dM, spmvAmgInfo* info) {
     if (!ready(who)) return EXIT_FAILURE;
     if (!dA || !dM) { ERR("%s: %s is NULL", who, !dA ? "dA" : "dM"); return EXIT_FAILURE; }
     if (dM == dA) { ERR("%s: dM is the source handle itself", who); return EXIT_FAILURE; }
@@ -242,13 +242,22 @@ int spmvHipAmgSetup(spmat* dA, const spmvAmgOpts* opts, spmat* dM, spmvAmgInfo* 
     if (a->NZ && (!a->JA || !a->AS)) { ERR("%s: the source has no column or value array", who); return EXIT_FAILURE; }
     if (opts && opts->maxLevels > SPMV_AMG_MAX_LEVELS) { ERR("%s: maxLevels %u is above %d", who, opts->maxLevels, SPMV_AMG_MAX_LEVELS); return EXIT_FAILURE; }
     if (opts && !(opts->omega >= 0.0 && std::isfinite(opts->omega))) { ERR("%s: omega %g is negative or not finite", who, opts->omega); return EXIT_FAILURE; }
+    if (omegaP && !(*omegaP >= 0.0 && std::isfinite(*omegaP))) { ERR("%s: omegaP %g is negative or not finite", who, *omegaP); return EXIT_FAILURE; }
     DevMat* m = new DevMat;
     m->M = m->N = a->M;
     setOrigin(m, Origin::HIERARCHY, a);
-    if (amgBuild(dA, opts, S.aggK, m, S.stream)) { ERR("%s: building the hierarchy failed", who); freeDesc(m); return EXIT_FAILURE; }
+    if (amgBuild(dA, opts, omegaP, S.amgFuseMax, S.aggK, m, S.stream)) { ERR("%s: building the hierarchy failed", who); freeDesc(m); return EXIT_FAILURE; }
     publish(dM, m, m->M, m->N, 0, 0);
     if (info) *info = *amgInfo(m);
     return EXIT_SUCCESS;
+}
+
+int spmvHipAmgSetup(spmat* dA, const spmvAmgOpts* opts, spmat* dM, spmvAmgInfo* info) {
+    return amgSetup("spmvHipAmgSetup", dA, opts, nullptr, dM, info);
+}
+int spmvHipAmgSetupSmoothed(spmat* dA, const spmvAmgOpts* opts, const spmvAmgSmoothOpts* smooth, spmat* dM, spmvAmgInfo* info) {
+    const double omegaP = smooth ? smooth->omegaP : 0.0;
+    return amgSetup("spmvHipAmgSetupSmoothed", dA, opts, &omegaP, dM, info);
 }
 
 int spmvHipAmgRefresh(spmat* dM, spmat* dA) {
@@ -292,6 +301,19 @@ int spmvHipAmgLevel(spmat* dM, unsigned level, spmat* dAl, const uint32_t** dAgg
     if (!madeBy(m, Origin::HIERARCHY, nullptr, nullptr, who, "dM")) return EXIT_FAILURE;
     if (level >= amgInfo(m)->levels) { ERR("%s: level %u of %zu", who, level, (size_t)amgInfo(m)->levels); return EXIT_FAILURE; }
     amgLevel(m, level, dAl, dAgg, dDinv);
+    return EXIT_SUCCESS;
+}
+
+int spmvHipAmgProlongator(spmat* dM, unsigned level, spmat* dPl, spmat* dRl, double* omegaP) {
+    const char* who = "spmvHipAmgProlongator";
+    DevMat* m = anyDescOf(dM, who);
+    if (!m) return EXIT_FAILURE;
+    if (!madeBy(m, Origin::HIERARCHY, nullptr, nullptr, who, "dM")) return EXIT_FAILURE;
+    if (level >= amgInfo(m)->levels - 1) {                 // (a hierarchy has at least one level)
+        ERR("%s: level %u of %zu: the last level has no prolongator", who, level, (size_t)amgInfo(m)->levels);
+        return EXIT_FAILURE;
+    }
+    amgProlongator(m, level, dPl, dRl, omegaP);
     return EXIT_SUCCESS;
 }
 
