@@ -650,6 +650,67 @@ typedef struct {
 } spmvAddInfo;
 int spmvHipCsrAdd(double alpha, spmat* dA, double beta, spmat* dB, const spmvAddOpts* opts, spmat* dC, spmvAddInfo* info);
 int spmvHipCsrAddRefresh(spmat* dC, double alpha, spmat* dA, double beta, spmat* dB, spmvAddInfo* info);
+/* ------------------------------------------------------------- entry filter C = the kept entries of A */
+/* spmvHipCsrFilter writes into dC a new, independent CSR handle that holds the entries of A a predicate keeps (tril / triu /
+ * the diagonal for an L + D + U splitting, a drop tolerance, the strength-of-connection filter of smoothed aggregation).  The
+ * contract is the bits of this serial loop on the handle's arrays (IRP, JA, AS as stored), DESIGN.md section 29:
+ *       if STRENGTH or lump:  for i in 0 .. M-1:  d[i] = A.AS[p] of the ONE stored entry p of row i with A.JA[p] == i
+ *       for i in 0 .. M-1:
+ *           v = d[i]                                           (lump only)
+ *           for p in A.IRP[i] .. A.IRP[i+1]-1:                 (A's stored order)
+ *               j = A.JA[p];  a = A.AS[p]
+ *               if keep(i, j, a):  append (j, a) to row i of C (a copied as bits), kept[next place of C] = p
+ *               else if lump:      v = v + a                   (a plain add, in stored order)
+ *           if lump:  the value of C's entry (i, i) = v        (its place does not move)
+ *       keep(i, j, a), every product rounded, no FMA, a comparison with a NaN false:
+ *           STRENGTH or lump, and j == i:  true                 (the diagonal entry is always kept)
+ *           SPMV_FILTER_BAND:      opts->lo <= (int64_t)j - (int64_t)i && (int64_t)j - (int64_t)i <= opts->hi
+ *           SPMV_FILTER_ABS:       fabs(a) > opts->theta
+ *           SPMV_FILTER_STRENGTH:  a * a > (opts->theta * opts->theta) * fabs(d[i] * d[j])
+ *   Order and values: row i of C is the kept entries of A's row i in A's stored order: unsorted rows stay unsorted, and each
+ *   repeat of an (i, j) pair is judged on its own.  Values are copied as bits: -0.0 stays -0.0, a NaN keeps its payload; a
+ *   NaN fails ABS and STRENGTH and is dropped (a NaN on the kept diagonal stays).  BAND is a function of the pattern alone:
+ *   no value is read for the decision; lo > hi gives a valid empty C; INT64_MIN and INT64_MAX are the open ends, so
+ *   tril is (INT64_MIN, 0), triu (0, INT64_MAX), the diagonal (0, 0).
+ *   The diagonal d: STRENGTH, and lump in any mode, need a square A and the STORED rule of spmvHipAmgSetup: a row without
+ *   exactly one stored entry (i, i) is refused, and the line names the first such row.
+ *   lump = 1 (Vanek's filtered matrix; with ABS and STRENGTH): the loop above -- the sum v is the only arithmetic of the call.
+ *   A dropped NaN or a dropped Inf lumps into its diagonal; where v is a NaN its payload is not pinned.  info.lumpedRows =
+ *   the rows with at least one dropped entry.
+ *   dC is like a sum handle: u32 columns, 4-byte row pointers, its own unit detection, row blocks; every CSR entry point
+ *   works on it; freed with hipFreeSpmat.  Sources: spMatCpyCSR / spmvHipAdoptCSR (row pointers of 4 or 8 bytes) /
+ *   transpose / permuted / product / sum / filtered handles, unit-value handles included.  The result is a function of A's
+ *   arrays and opts alone -- not of the run or the grid.
+ *   Memory: C itself 12 B per kept entry + 4 B per row, its row blocks, 4 B per kept entry for the refresh (kept[]), and
+ *   with lump 1 bit per entry of A (the keep mask), 4 B per row (the diagonal's place in C) and 4 B per row of A above 64
+ *   entries.  Temporaries, freed before the call returns: 1 bit per entry of A + 8 B per 1 024 entries, and 16 B per row
+ *   where d is needed.  info: nnzA, nnzC, maxRowNnz (of C), lumpedRows, tempBytes (peak of the temporaries), ms (wall).
+ *   Synchronous on the library stream; allocates, so not capturable.  info may be NULL.
+ *   M = 0, N = 0, an empty A and a filter that keeps nothing succeed with a valid C (NZ = 0, SpMV +0.0).
+ * spmvHipCsrFilterRefresh: the kept set is the BUILD's; nothing is judged again.  C.AS[q] = A.AS[kept[q]] from A's CURRENT
+ *   values; with lump the diagonal is then the loop's v over A's current values at the build's dropped places.  C's pattern
+ *   and device addresses stay; then what spmvHipValuesChanged(dC) does.  dC records A's id and refuses any other source.
+ * Refused with a message and EXIT_FAILURE, dC and info untouched: NULL dA, opts or dC; a handle that is not live; an ELL
+ *   handle or a multigrid hierarchy; dC == dA; an unknown mode; theta negative or not finite (in any mode); lump with
+ *   BAND; STRENGTH or lump on a matrix that is not square, or that breaks the STORED rule; M or N >= 2^32 - 1; NZ >=
+ *   IRP32_LIMIT (2^32 - 65536); a column id >= N in the source (an adopted array; checked on the device); a source with
+ *   entries but no column or value array; a refresh of a handle that is not a filter, or from another source. */
+#define SPMV_FILTER_BAND     0   /* keep (i, j) iff lo <= (int64)j - (int64)i <= hi                        */
+#define SPMV_FILTER_ABS      1   /* keep iff fabs(a) > theta                                                */
+#define SPMV_FILTER_STRENGTH 2   /* keep iff j == i, or a*a > (theta*theta) * fabs(d_i * d_j)               */
+typedef struct {
+    int     mode;           /* SPMV_FILTER_*                                                   */
+    int64_t lo, hi;         /* BAND: the kept diagonals, INT64_MIN / INT64_MAX the open ends   */
+    double  theta;          /* ABS, STRENGTH: the threshold                                    */
+    int     lump;           /* 1: the dropped entries of a row are added to its diagonal entry */
+} spmvFilterOpts;
+typedef struct {
+    ulong nnzA, nnzC, maxRowNnz, lumpedRows;
+    ulong tempBytes;        /* peak of the build's temporaries */
+    double ms;
+} spmvFilterInfo;
+int spmvHipCsrFilter(spmat* dA, const spmvFilterOpts* opts, spmat* dC, spmvFilterInfo* info);
+int spmvHipCsrFilterRefresh(spmat* dC, spmat* dA, spmvFilterInfo* info);
 /* ------------------------------------------------------------- aggregation multigrid preconditioner */
 /* Plain (unsmoothed) aggregation AMG built from the pieces above: an aggregation of the pattern, the Galerkin products by
  * spmvHipCsrTranspose / spmvHipSpGEMM, a damped-Jacobi V-cycle on serial-order SpMVs.  DESIGN.md section 24.  As everywhere
@@ -753,7 +814,32 @@ int spmvHipCsrAddRefresh(spmat* dC, double alpha, spmat* dA, double beta, spmat*
  *   pattern stay (all patterns are structural), device addresses are kept.  Bit-identical to a fresh setup.
  * spmvHipAmgProlongator: a view like spmvHipAmgLevel's of a level that is not the last: *dPl, *dRl = copies of P_l's and
  *   R_l's spmat with dev = NULL (the arrays stay dM's), *omegaP = w_l.  Any of the three may be NULL.  On a hierarchy of
- *   spmvHipAmgSetup: the unit P_l, its R_l and 0.0.  Refused: a dM that is not a hierarchy, the last level and beyond. */
+ *   spmvHipAmgSetup: the unit P_l, its R_l and 0.0.  Refused: a dM that is not a hierarchy, the last level and beyond.
+ *
+ * Strength-filtered smoothed aggregation.  spmvHipAmgSetupStrength writes a smoothed hierarchy -- every
+ *   sentence above about spmvHipAmgSetupSmoothed's handle, cycle, launch counts and views holds -- that aggregates on, and
+ *   smooths its prolongator with, the strength-filtered matrix, so that on an anisotropic operator the aggregates follow the
+ *   strong direction.  opts and smooth are those of spmvHipAmgSetupSmoothed.  strength (NULL, or a field 0: the default):
+ *   theta 0.08, thetaScale 0.5; theta_0 = theta, theta_{l+1} = theta_l * thetaScale (one rounded product per level: a fixed
+ *   theta stalls on the coarse levels, whose entries are more alike).  Per level that is not the last:
+ *       F_l   = spmvHipCsrFilter(A_l, {SPMV_FILTER_STRENGTH, theta = theta_l, lump = 1})
+ *       agg_l = spmvHipAggregateCSR(F_l, seed);   stop when nAgg_l == M_l          (F_l is then dropped)
+ *       dF_l[i] = 1.0 / (the stored entry (i, i) of F_l);   s_i, g_i, rho_l, w_l as above, from F_l's rows and dF_l
+ *       D_l   = the M_l x M_l CSR handle with the one entry (i, i) = dF_l[i] per row
+ *       P_l   = spmvHipCsrAdd(1.0, T_l, -w_l, spmvHipSpGEMM(D_l, spmvHipSpGEMM(F_l, T_l)))
+ *       R_l   = spmvHipCsrTranspose(P_l);   A_{l+1} = spmvHipSpGEMM(R_l, spmvHipSpGEMM(A_l, P_l))     (Galerkin on the FULL A_l)
+ *   dinv_l, and with it the Jacobi sweeps of the cycle, stay those of A_l.  F_l and dF_l are kept and counted in info.bytes.
+ *   theta = 1e-200 (theta * theta is 0.0) keeps every nonzero entry: on a matrix without a stored zero the arrays are
+ *   spmvHipAmgSetupSmoothed's.
+ *   spmvHipAmgRefresh on such a hierarchy runs spmvHipCsrFilterRefresh(F_l, A_l) first, then dF_l and the smoothed chain
+ *   above with F_l in A_l's place.  The kept sets and the aggregates are the BUILD's: the refreshed hierarchy equals a fresh
+ *   setup bit for bit WHEN A FRESH SETUP WOULD KEEP THE SAME ENTRIES (all values scaled by a power of two, say); otherwise it
+ *   is the hierarchy of the build's pattern with the new values -- a valid preconditioner, not the fresh one.
+ *   Refused besides what spmvHipAmgSetupSmoothed refuses, outputs untouched: theta or thetaScale negative or not finite;
+ *   thetaScale > 1.
+ * spmvHipAmgStrength: a view like spmvHipAmgProlongator's of a level that is not the last: *dFl = a copy of F_l's spmat with
+ *   dev = NULL (the arrays stay dM's), *theta = theta_l.  Either may be NULL.  Refused: a dM that is not a hierarchy of
+ *   spmvHipAmgSetupStrength, the last level and beyond. */
 #define SPMV_AMG_MAX_LEVELS 16
 #define SPMV_AMG_NO_SWEEPS  0xFFFFFFFFu
 typedef struct {
@@ -799,6 +885,13 @@ typedef struct {            /* 0 = the built-in default */
 } spmvAmgSmoothOpts;
 int spmvHipAmgSetupSmoothed(spmat* dA, const spmvAmgOpts* opts, const spmvAmgSmoothOpts* smooth, spmat* dM, spmvAmgInfo* info);
 int spmvHipAmgProlongator(spmat* dM, unsigned level, spmat* dPl, spmat* dRl, double* omegaP);
+typedef struct {            /* 0 = the built-in default */
+    double theta;           /* the strength threshold of level 0 (0.08)                      */
+    double thetaScale;      /* theta_{l+1} = theta_l * thetaScale (0.5); at most 1           */
+} spmvAmgStrengthOpts;
+int spmvHipAmgSetupStrength(spmat* dA, const spmvAmgOpts* opts, const spmvAmgSmoothOpts* smooth,
+                            const spmvAmgStrengthOpts* strength, spmat* dM, spmvAmgInfo* info);
+int spmvHipAmgStrength(spmat* dM, unsigned level, spmat* dFl, double* theta);
 /* Release the device arrays behind a handle (cudaUtils.h:70-78). */
 int hipFreeSpmat(spmat* dMat);
 

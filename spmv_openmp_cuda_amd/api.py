@@ -123,6 +123,8 @@ _sigs = {
     "spmvHipSpGEMMRefresh": ([C.POINTER(spmat), C.POINTER(spmat), C.POINTER(spmat), _vp], _i),
     "spmvHipCsrAdd": ([C.c_double, C.POINTER(spmat), C.c_double, C.POINTER(spmat), _vp, C.POINTER(spmat), _vp], _i),
     "spmvHipCsrAddRefresh": ([C.POINTER(spmat), C.c_double, C.POINTER(spmat), C.c_double, C.POINTER(spmat), _vp], _i),
+    "spmvHipCsrFilter": ([C.POINTER(spmat), _vp, C.POINTER(spmat), _vp], _i),
+    "spmvHipCsrFilterRefresh": ([C.POINTER(spmat), C.POINTER(spmat), _vp], _i),
     "spmvHipAggregateCSR": ([C.POINTER(spmat), _vp, _vp, _vp], _i),
     "spmvHipAmgSetup": ([C.POINTER(spmat), _vp, C.POINTER(spmat), _vp], _i),
     "spmvHipAmgRefresh": ([C.POINTER(spmat), C.POINTER(spmat)], _i),
@@ -131,6 +133,8 @@ _sigs = {
     "spmvHipAmgLevel": ([C.POINTER(spmat), C.c_uint, C.POINTER(spmat), C.POINTER(_vp), C.POINTER(_vp)], _i),
     "spmvHipAmgSetupSmoothed": ([C.POINTER(spmat), _vp, _vp, C.POINTER(spmat), _vp], _i),
     "spmvHipAmgProlongator": ([C.POINTER(spmat), C.c_uint, C.POINTER(spmat), C.POINTER(spmat), C.POINTER(C.c_double)], _i),
+    "spmvHipAmgSetupStrength": ([C.POINTER(spmat), _vp, _vp, _vp, C.POINTER(spmat), _vp], _i),
+    "spmvHipAmgStrength": ([C.POINTER(spmat), C.c_uint, C.POINTER(spmat), C.POINTER(C.c_double)], _i),
 }
 SPMV_DENSE_ROW_MAJOR, SPMV_DENSE_COL_MAJOR = 0, 1          # include/spmvHip.h: layouts of hipSpMMRowsCSR's X and Y
 SPMV_TRI_LOWER, SPMV_TRI_UPPER = 0, 1                      # include/spmvHip.h: hipSpTRSVCSR's uplo ...
@@ -240,6 +244,22 @@ class spmvAddInfo(C.Structure):
                 ("tempBytes", C.c_ulong), ("symbolicMs", C.c_double), ("numericMs", C.c_double), ("ms", C.c_double)]
 
 
+SPMV_FILTER_BAND, SPMV_FILTER_ABS, SPMV_FILTER_STRENGTH = 0, 1, 2
+FILTER_MODES = {"band": SPMV_FILTER_BAND, "abs": SPMV_FILTER_ABS, "strength": SPMV_FILTER_STRENGTH}
+INT64_MIN, INT64_MAX = -(1 << 63), (1 << 63) - 1
+
+
+class spmvFilterOpts(C.Structure):
+    """include/spmvHip.h `spmvFilterOpts`: the predicate of spmvHipCsrFilter (lo / hi: INT64_MIN / INT64_MAX are the open ends)."""
+    _fields_ = [("mode", _i), ("lo", C.c_int64), ("hi", C.c_int64), ("theta", C.c_double), ("lump", _i)]
+
+
+class spmvFilterInfo(C.Structure):
+    """include/spmvHip.h `spmvFilterInfo`: what a spmvHipCsrFilter / spmvHipCsrFilterRefresh call did."""
+    _fields_ = [("nnzA", C.c_ulong), ("nnzC", C.c_ulong), ("maxRowNnz", C.c_ulong), ("lumpedRows", C.c_ulong),
+                ("tempBytes", C.c_ulong), ("ms", C.c_double)]
+
+
 SPMV_AMG_MAX_LEVELS, SPMV_AMG_NO_SWEEPS = 16, 0xFFFFFFFF
 
 
@@ -270,6 +290,11 @@ class spmvAmgInfo(C.Structure):
 class spmvAmgSmoothOpts(C.Structure):
     """include/spmvHip.h `spmvAmgSmoothOpts`: the damping of the smoothed prolongator (0: (4/3) / rho_l per level)."""
     _fields_ = [("omegaP", C.c_double)]
+
+
+class spmvAmgStrengthOpts(C.Structure):
+    """include/spmvHip.h `spmvAmgStrengthOpts`: the strength threshold per level (0: 0.08, scaled by 0.5 per level)."""
+    _fields_ = [("theta", C.c_double), ("thetaScale", C.c_double)]
 
 
 SPMV_COLOUR_NATURAL, SPMV_COLOUR_HASH = 0, 1
@@ -811,6 +836,49 @@ class DeviceMatrix:
             raise SpmvHipError("add_info: this matrix was not made by add()")
         return info
 
+    def filter(self, mode, lo=None, hi=None, theta=0.0, lump=False) -> "DeviceMatrix":
+        """spmvHipCsrFilter: the entries of this matrix that a predicate keeps, in stored order, values copied as bits, as a
+        new DeviceMatrix that owns its handle (include/spmvHip.h states the loop).  mode: "band" (lo <= j - i <= hi; None:
+        the open end), "abs" (|a| > theta) or "strength" (j == i, or a * a > theta^2 |d_i d_j|), or a SPMV_FILTER_* value.
+        lump: the dropped entries of a row are added, in stored order, to its diagonal entry.  filter_info() tells what the
+        call did."""
+        if isinstance(mode, str) and mode not in FILTER_MODES:
+            raise SpmvHipError(f"filter: mode must be one of {sorted(FILTER_MODES)}, not {mode!r}")
+        opts = spmvFilterOpts(FILTER_MODES[mode] if isinstance(mode, str) else int(mode), INT64_MIN if lo is None else int(lo),
+                              INT64_MAX if hi is None else int(hi), float(theta), int(bool(lump)))
+        c, info = DeviceMatrix(), spmvFilterInfo()
+        _check(lib.spmvHipCsrFilter(C.byref(self.handle), C.byref(opts), C.byref(c.handle), C.byref(info)), "spmvHipCsrFilter")
+        c.rows = int(c.handle.M)
+        c._filter = info
+        return c
+
+    def filter_refresh(self, source: "DeviceMatrix"):
+        """spmvHipCsrFilterRefresh: this filtered matrix takes `source`'s current values at the places kept at the build
+        (nothing is judged again; with lump the diagonal is summed again over the build's dropped places), pattern and
+        addresses kept, then refreshes its formats as values_changed() does."""
+        info = spmvFilterInfo()
+        _check(lib.spmvHipCsrFilterRefresh(C.byref(self.handle), C.byref(source.handle), C.byref(info)), "spmvHipCsrFilterRefresh")
+        self._filter = info
+
+    def filter_info(self) -> "spmvFilterInfo":
+        """the spmvFilterInfo of the filter() that made this matrix, or of its last filter_refresh()"""
+        info = getattr(self, "_filter", None)
+        if info is None:
+            raise SpmvHipError("filter_info: this matrix was not made by filter()")
+        return info
+
+    def tril(self, k=0) -> "DeviceMatrix":
+        """the entries on and below the k-th diagonal (j - i <= k), as filter("band")"""
+        return self.filter("band", hi=k)
+
+    def triu(self, k=0) -> "DeviceMatrix":
+        """the entries on and above the k-th diagonal (j - i >= k), as filter("band")"""
+        return self.filter("band", lo=k)
+
+    def diagonal_matrix(self) -> "DeviceMatrix":
+        """the stored diagonal entries as a matrix of their own, as filter("band", 0, 0)"""
+        return self.filter("band", lo=0, hi=0)
+
     def aggregate(self, seed=0):
         """spmvHipAggregateCSR: the aggregate id of every vertex of this square matrix, a function of its pattern and the
         seed alone (include/spmvHip.h states the loop).  Returns (ids, info): a numpy uint32 array and a spmvAggInfo."""
@@ -822,17 +890,26 @@ class DeviceMatrix:
             return (buf.down(np.uint32) if M else np.zeros(0, np.uint32)), info
 
     def amg(self, seed=0, coarseRows=None, maxLevels=None, omega=None, nu1=None, nu2=None, nuCoarse=None, smoothed=False,
-            omegaP=None) -> "AmgHierarchy":
+            omegaP=None, theta=None, thetaScale=None) -> "AmgHierarchy":
         """spmvHipAmgSetup: an aggregation multigrid hierarchy of this square matrix (include/spmvHip.h states the loops).
         None: the built-in default (512, 16, 2/3, 1, 1, 8); nu1 / nu2 / nuCoarse = 0 asks for no sweeps.  The result is
         accepted as `precond=` by cg / bicgstab / gmres of this matrix.  smoothed: spmvHipAmgSetupSmoothed, the
-        prolongator T - omegaP D^-1 A T (omegaP None: (4/3) / rho_l per level)."""
+        prolongator T - omegaP D^-1 A T (omegaP None: (4/3) / rho_l per level).  theta or thetaScale given (with
+        smoothed=True): spmvHipAmgSetupStrength, which aggregates and smooths on the strength-filtered matrix with the
+        threshold theta * thetaScale^l on level l (None: 0.08, 0.5)."""
         def sweeps(v):
             return 0 if v is None else SPMV_AMG_NO_SWEEPS if int(v) == 0 else int(v)
         opts = spmvAmgOpts(int(seed) & 0xFFFFFFFF, int(coarseRows or 0), int(maxLevels or 0), float(omega or 0.0), sweeps(nu1),
                            sweeps(nu2), sweeps(nuCoarse))
         h = AmgHierarchy(self)
-        if smoothed:
+        strength = theta is not None or thetaScale is not None
+        if strength and not smoothed:
+            raise SpmvHipError("amg: theta and thetaScale are the strength filter of the smoothed hierarchy (smoothed=True)")
+        if strength:
+            smooth, so = spmvAmgSmoothOpts(float(omegaP or 0.0)), spmvAmgStrengthOpts(float(theta or 0.0), float(thetaScale or 0.0))
+            _check(lib.spmvHipAmgSetupStrength(C.byref(self.handle), C.byref(opts), C.byref(smooth), C.byref(so), C.byref(h.handle),
+                                               C.byref(h.info)), "spmvHipAmgSetupStrength")
+        elif smoothed:
             smooth = spmvAmgSmoothOpts(float(omegaP or 0.0))
             _check(lib.spmvHipAmgSetupSmoothed(C.byref(self.handle), C.byref(opts), C.byref(smooth), C.byref(h.handle), C.byref(h.info)),
                    "spmvHipAmgSetupSmoothed")
@@ -994,7 +1071,7 @@ class DeviceMatrix:
 
 class AmgHierarchy(DeviceMatrix):
     """What DeviceMatrix.amg() returns: a hierarchy handle (no matrix: SpMV, formats and solves refuse it) with `info`
-    (spmvAmgInfo), apply(), refresh_from(), level(), prolongator() and free().  It keeps a reference to its source matrix."""
+    (spmvAmgInfo), apply(), refresh_from(), level(), prolongator(), strength() and free().  It keeps a reference to its source matrix."""
 
     def __init__(self, source):
         super().__init__()
@@ -1028,15 +1105,24 @@ class AmgHierarchy(DeviceMatrix):
         AS), downloaded, and the damping w_l (0.0 on a hierarchy that is not smoothed)"""
         P, R, w = spmat(), spmat(), C.c_double()
         _check(lib.spmvHipAmgProlongator(C.byref(self.handle), int(l), C.byref(P), C.byref(R), C.byref(w)), "spmvHipAmgProlongator")
+        return self._down(P), self._down(R), w.value
 
-        def down(v):
-            M, NZ = int(v.M), int(v.NZ)
-            out = [np.empty(M + 1, np.uint32), np.empty(NZ, np.uint32), np.empty(NZ, np.float64)]
-            for a, ptr in zip(out, (v.IRP, v.JA, v.AS)):
-                if a.size:
-                    _check(lib.spmvHipMemcpyDown(a.ctypes.data_as(C.c_void_p), C.cast(ptr, C.c_void_p), a.nbytes), "spmvHipMemcpyDown")
-            return M, int(v.N), out[0], out[1], out[2]
-        return down(P), down(R), w.value
+    @staticmethod
+    def _down(v):
+        """the host CSR arrays (M, N, IRP, JA, AS) of a view"""
+        M, NZ = int(v.M), int(v.NZ)
+        out = [np.empty(M + 1, np.uint32), np.empty(NZ, np.uint32), np.empty(NZ, np.float64)]
+        for a, ptr in zip(out, (v.IRP, v.JA, v.AS)):
+            if a.size:
+                _check(lib.spmvHipMemcpyDown(a.ctypes.data_as(C.c_void_p), C.cast(ptr, C.c_void_p), a.nbytes), "spmvHipMemcpyDown")
+        return M, int(v.N), out[0], out[1], out[2]
+
+    def strength(self, l):
+        """spmvHipAmgStrength: (F, theta) of level l (not the last) of a hierarchy made with theta / thetaScale: the
+        strength-filtered F_l as host CSR arrays (M, N, IRP, JA, AS), downloaded, and its threshold theta_l"""
+        F, theta = spmat(), C.c_double()
+        _check(lib.spmvHipAmgStrength(C.byref(self.handle), int(l), C.byref(F), C.byref(theta)), "spmvHipAmgStrength")
+        return self._down(F), theta.value
 
     def free(self):
         super().free()

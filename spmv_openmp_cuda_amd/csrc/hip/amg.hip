@@ -24,6 +24,12 @@
 // A_l T_l, D_l (A_l T_l) are kept for the refresh.  w_l comes from amg_rho_kernel (row sums of |a_ij|, an integer max on the
 // bit pattern).  The cycle's correction is then z = z + P_l e: one fused launch (amg_prolong_kernel, a lane walks two rows of
 // P_l) on a level whose P_l has no row above the threshold read at setup, else P_l's serial-order SpMV into d_l and AmgAddOp.
+//
+// Strength filtering (spmvHipAmgSetupStrength).  The smoothed build with F_l = spmvHipCsrFilter(A_l,
+// STRENGTH, theta_l, lump) in two places: the aggregation runs on F_l's pattern, and the prolongator smoother
+// (dF_l = 1 / diag F_l, rho_l, w_l, D_l, F_l T_l) on F_l's values.  The Galerkin product stays R_l (A_l P_l) on the full A_l,
+// and the cycle is the smoothed one, its Jacobi sweeps on dinv_l of A_l.  The refresh runs spmvHipCsrFilterRefresh first:
+// the kept sets are the build's.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <chrono>
@@ -38,6 +44,9 @@ namespace spmvhip {
 struct AmgLevel {
     spmat A{}, P{}, R{}, AP{};          // A: levels below 0 only (level 0 is the caller's); P, R, AP: all but the last level
     spmat T{}, D{}, AT{}, DAT{};        // smoothed, all but the last level: the unit prolongator, diag(dinv), A T, D (A T)
+    spmat F{};                          // strength, all but the last level: the filtered A, which then stands for A in D, AT
+    double theta = 0.0;                 // ... and its threshold
+    double* dF = nullptr;               // ... and 1 / its diagonal
     uint64_t M = 0, nnz = 0, nAgg = 0;
     const uint32_t* agg = nullptr;      // the column array of the unit prolongator (P, or T when smoothed)
     double w = 0.0;                     // smoothed: the damping of P
@@ -53,6 +62,8 @@ struct AmgHierarchy {
     bool smoothed = false;
     double omegaP = 0.0;                // smoothed: the caller's damping of P, 0: (4/3) / rho_l per level
     uint32_t fuseMax = 0;               // smoothed: the longest row of P that the fused correction takes (0: never fused)
+    bool strength = false;              // smoothed on the strength-filtered F_l
+    double theta = 0.0, thetaScale = 0.0;   // strength: theta_0, and theta_{l+1} = theta_l * thetaScale
     std::vector<AmgLevel> lv;
     spmvAmgInfo info{};
 };
@@ -415,9 +426,9 @@ size_t handleBytes(const spmat* h) {
 void freeAmg(AmgHierarchy* h) {
     if (!h) return;
     for (AmgLevel& l : h->lv) {
-        for (spmat* m : {&l.A, &l.P, &l.R, &l.AP, &l.T, &l.D, &l.AT, &l.DAT})
+        for (spmat* m : {&l.A, &l.P, &l.R, &l.AP, &l.T, &l.D, &l.AT, &l.DAT, &l.F})
             if (m->dev) (void)hipFreeSpmat(m);
-        for (double* p : {l.dinv, l.r, l.z, l.t, l.d}) (void)hipFree(p);
+        for (double* p : {l.dinv, l.r, l.z, l.t, l.d, l.dF}) (void)hipFree(p);
     }
     delete h;
 }
@@ -500,12 +511,27 @@ int aggregateCsr(const DevMat* a, uint32_t seed, uint32_t K, uint32_t* dAgg, spm
     return EXIT_SUCCESS;
 }
 
-int amgBuild(spmat* hA, const spmvAmgOpts* o, const double* omegaP, uint32_t fuseMax, uint32_t K, DevMat* m, hipStream_t st) {
+// the strength-filtered stand-in of a level's matrix and 1 / its diagonal: the build (L.theta set first) or the refresh
+static int levelFilter(AmgLevel& L, spmat* cur, bool build, const char* module, spmvFilterInfo* fi, hipStream_t st) {
+    const spmvFilterOpts fo{SPMV_FILTER_STRENGTH, 0, 0, L.theta, 1};
+    if (build ? spmvHipCsrFilter(cur, &fo, &L.F, fi) : spmvHipCsrFilterRefresh(&L.F, cur, fi)) return buildFail(st, module, "a level's strength filter");
+    if (build && hipMalloc(&L.dF, std::max<uint64_t>(L.M, 2) * sizeof(double)) != hipSuccess) return buildFail(st, module, "allocation of a level's vectors");
+    long bad = -1;
+    if (levelDinv(matOf(&L.F), L.dF, &bad, st) || bad >= 0) return buildFail(st, module, "the diagonal of a level's filtered matrix");
+    return EXIT_SUCCESS;
+}
+
+int amgBuild(spmat* hA, const spmvAmgOpts* o, const double* omegaP, const spmvAmgStrengthOpts* strength, uint32_t fuseMax, uint32_t K, DevMat* m,
+             hipStream_t st) {
     const auto t0 = std::chrono::steady_clock::now();
     AmgHierarchy* H = m->amg = new AmgHierarchy;
     H->smoothed = omegaP != nullptr;
     H->omegaP = omegaP ? *omegaP : 0.0;
     H->fuseMax = fuseMax;
+    H->strength = strength != nullptr;
+    H->theta = strength && strength->theta != 0.0 ? strength->theta : 0.08;
+    H->thetaScale = strength && strength->thetaScale != 0.0 ? strength->thetaScale : 0.5;
+    double theta = H->theta;
     const uint64_t coarseRows = o && o->coarseRows ? o->coarseRows : 512;
     const uint32_t maxLevels = o && o->maxLevels ? o->maxLevels : SPMV_AMG_MAX_LEVELS;
     auto sweeps = [](unsigned v, uint32_t dflt) { return v == 0 ? dflt : v == SPMV_AMG_NO_SWEEPS ? 0u : v; };
@@ -534,12 +560,23 @@ int amgBuild(spmat* hA, const spmvAmgOpts* o, const double* omegaP, uint32_t fus
         }
         if (warmSpmv(cur, L.d, L.t, st)) return fail("the SpMV selection of a level");
         if (L.M <= coarseRows || l + 1 == maxLevels) break;
+        // strength: F stands for A in the aggregation and in the smoother of P
+        spmat* soc = cur;
+        const double* sdinv = L.dinv;
+        if (H->strength) {
+            spmvFilterInfo fi{};
+            L.theta = theta;
+            if (levelFilter(L, cur, true, "multigrid setup", &fi, st)) return EXIT_FAILURE;
+            info.tempBytes = std::max<ulong>(info.tempBytes, fi.tempBytes);
+            soc = &L.F;
+            sdinv = L.dF;
+        }
         // aggregates -> P (its column array IS agg), R, A P, R (A P)
         uint32_t *irp = nullptr, *agg = nullptr;
         double* ones = nullptr;
         spmvAggInfo ai{};
         bool ok = hipMalloc(&irp, (L.M + 1) * 4) == hipSuccess && hipMalloc(&agg, L.M * 4) == hipSuccess && hipMalloc(&ones, L.M * 8) == hipSuccess &&
-                  !aggregateCsr(a, H->seed, K, agg, &ai, st);
+                  !aggregateCsr(matOf(soc), H->seed, K, agg, &ai, st);
         const bool alone = ok && ai.aggregates == L.M;         // every vertex its own aggregate: nothing to coarsen
         if (ok && !alone) {
             enqueueIota(L.M + 1, irp, st);
@@ -548,6 +585,11 @@ int amgBuild(spmat* hA, const spmvAmgOpts* o, const double* omegaP, uint32_t fus
         }
         if (!ok || alone) {
             (void)hipFree(irp); (void)hipFree(agg); (void)hipFree(ones);
+            if (alone && H->strength) {                        // the last level keeps no filtered matrix
+                (void)hipFreeSpmat(&L.F);
+                (void)hipFree(L.dF);
+                L.dF = nullptr;
+            }
             if (alone) break;
             return fail("the aggregation");
         }
@@ -558,25 +600,27 @@ int amgBuild(spmat* hA, const spmvAmgOpts* o, const double* omegaP, uint32_t fus
         L.agg = matOf(unitP)->JA;
         spmvSpgemmInfo s1{}, s2{};
         if (H->smoothed) {                                     // P = T - w D (A T), by the public sum and products
-            if (levelDamping(H, a, L.dinv, l, "multigrid setup", &L.w, st)) return EXIT_FAILURE;
+            if (levelDamping(H, matOf(soc), sdinv, l, "multigrid setup", &L.w, st)) return EXIT_FAILURE;
             uint32_t *dIrp = nullptr, *dJa = nullptr;
             double* dAs = nullptr;
             ok = hipMalloc(&dIrp, (L.M + 1) * 4) == hipSuccess && hipMalloc(&dJa, L.M * 4) == hipSuccess && hipMalloc(&dAs, L.M * 8) == hipSuccess;
             if (ok) {
                 enqueueIota(L.M + 1, dIrp, st);
                 enqueueIota(L.M, dJa, st);
-                ok = hipMemcpyAsync(dAs, L.dinv, L.M * 8, hipMemcpyDeviceToDevice, st) == hipSuccess && hipGetLastError() == hipSuccess &&
+                ok = hipMemcpyAsync(dAs, sdinv, L.M * 8, hipMemcpyDeviceToDevice, st) == hipSuccess && hipGetLastError() == hipSuccess &&
                      hipStreamSynchronize(st) == hipSuccess;
             }
             if (!ok) { (void)hipFree(dIrp); (void)hipFree(dJa); (void)hipFree(dAs); return fail("the diagonal handle"); }
             if (ownCsr(&L.D, L.M, L.M, L.M, dIrp, dJa, dAs)) return fail("the diagonal handle");
             spmvAddInfo sa{};
-            if (spmvHipSpGEMM(cur, &L.T, nullptr, &L.AT, &s1) || spmvHipSpGEMM(&L.D, &L.AT, nullptr, &L.DAT, &s2) ||
+            if (spmvHipSpGEMM(soc, &L.T, nullptr, &L.AT, &s1) || spmvHipSpGEMM(&L.D, &L.AT, nullptr, &L.DAT, &s2) ||
                 spmvHipCsrAdd(1.0, &L.T, -L.w, &L.DAT, nullptr, &L.P, &sa))
                 return fail("a level's smoothed prolongator");
             L.fused = sa.maxRowNnz <= H->fuseMax && matOf(&L.P)->irpBytes == 4;     // (a sum's row pointers are 4-byte)
             info.tempBytes = std::max<ulong>(info.tempBytes, std::max({s1.tempBytes, s2.tempBytes, sa.tempBytes}));
             info.bytes += handleBytes(&L.T) + handleBytes(&L.D) + handleBytes(&L.AT) + handleBytes(&L.DAT);
+            if (H->strength) info.bytes += handleBytes(&L.F) + L.M * 8;
+            theta = theta * H->thetaScale;
         }
         if (spmvHipCsrTranspose(&L.P, &L.R) || spmvHipSpGEMM(cur, &L.P, nullptr, &L.AP, &s1)) return fail("a level's products");
         H->lv.emplace_back();
@@ -607,11 +651,18 @@ int amgRefresh(DevMat* m, spmat* hA, hipStream_t st) {
         if (warmSpmv(cur, L.d, L.t, st)) return fail("the SpMV selection of a level");
         if (l + 1 == H->lv.size()) break;
         if (H->smoothed) {
-            if (levelDamping(H, matOf(cur), L.dinv, l, "multigrid refresh", &L.w, st)) return EXIT_FAILURE;
-            if (hipMemcpyAsync(matOf(&L.D)->AS, L.dinv, L.M * 8, hipMemcpyDeviceToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess ||
+            spmat* soc = cur;
+            const double* sdinv = L.dinv;
+            if (H->strength) {
+                if (levelFilter(L, cur, false, "multigrid refresh", nullptr, st)) return EXIT_FAILURE;
+                soc = &L.F;
+                sdinv = L.dF;
+            }
+            if (levelDamping(H, matOf(soc), sdinv, l, "multigrid refresh", &L.w, st)) return EXIT_FAILURE;
+            if (hipMemcpyAsync(matOf(&L.D)->AS, sdinv, L.M * 8, hipMemcpyDeviceToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess ||
                 spmvHipValuesChanged(&L.D))
                 return fail("the diagonal handle");
-            if (spmvHipSpGEMMRefresh(&L.AT, cur, &L.T, nullptr) || spmvHipSpGEMMRefresh(&L.DAT, &L.D, &L.AT, nullptr) ||
+            if (spmvHipSpGEMMRefresh(&L.AT, soc, &L.T, nullptr) || spmvHipSpGEMMRefresh(&L.DAT, &L.D, &L.AT, nullptr) ||
                 spmvHipCsrAddRefresh(&L.P, 1.0, &L.T, -L.w, &L.DAT, nullptr) || spmvHipTransposeRefresh(&L.R, &L.P))
                 return fail("a level's smoothed prolongator");
         }
@@ -697,6 +748,14 @@ void amgProlongator(const DevMat* m, unsigned level, spmat* dPl, spmat* dRl, dou
     if (dPl) { *dPl = L.P; dPl->dev = nullptr; }
     if (dRl) { *dRl = L.R; dRl->dev = nullptr; }
     if (omegaP) *omegaP = m->amg->smoothed ? L.w : 0.0;
+}
+
+bool amgIsStrength(const DevMat* m) { return m->amg->strength; }
+
+void amgStrength(const DevMat* m, unsigned level, spmat* dFl, double* theta) {
+    const AmgLevel& L = m->amg->lv[level];
+    if (dFl) { *dFl = L.F; dFl->dev = nullptr; }
+    if (theta) *theta = L.theta;
 }
 
 }  // namespace spmvhip

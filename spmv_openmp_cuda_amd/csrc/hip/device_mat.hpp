@@ -30,15 +30,16 @@ constexpr uint64_t IRP32_LIMIT     = (1ull << 32) - 65536;
 enum class Kind : int { CSR = 0, ELL_ROWMAJOR = 1, ELL_COLMAJOR = 2 };
 // How a handle came to be (DevMat::origin; UPLOADED is also what ownCsr makes).  TRANSPOSE and later come from other handles,
 // whose ids -- never pointers: a source may be freed first -- DevMat::src records: TRANSPOSE, PERMUTATION, HIERARCHY the
-// source (the level-0 matrix) in src[0], PRODUCT and SUM A and B in that order.  What made a handle refreshes it, from those
-// handles only (madeBy in lib.hpp).  ELL_OF_CSR (spmvHipCsrToEll) keeps no link to its source, and its values cannot be updated.
-enum class Origin : int { UPLOADED, ADOPTED, ELL_OF_CSR, TRANSPOSE, PERMUTATION, PRODUCT, HIERARCHY, SUM };
+// source (the level-0 matrix) in src[0], PRODUCT and SUM A and B in that order, FILTER the source in src[0].  What made a
+// handle refreshes it, from those handles only (madeBy in lib.hpp).  ELL_OF_CSR (spmvHipCsrToEll) keeps no link to its source, and its values cannot be updated.
+enum class Origin : int { UPLOADED, ADOPTED, ELL_OF_CSR, TRANSPOSE, PERMUTATION, PRODUCT, HIERARCHY, SUM, FILTER };
 
 struct TileFormat;          // column-sliced two-phase format, tiles.hip
 struct SellFormat;          // SELL-C-sigma, sell.hip
 struct StripeFormat;        // bin-wise CSC (y bins in LDS, x from the XCD's L2), stripes.hip
 struct SpgemmPlan;          // what a product C = A B keeps for its refresh, spgemm.hip
 struct AddPlan;             // what a sum C = alpha A + beta B keeps for its refresh, add.hip
+struct FilterPlan;          // what a filtered handle keeps for its refresh besides the map, filter.hip
 struct AmgHierarchy;        // the levels of an aggregation multigrid preconditioner, amg.hip
 struct TempBuf;             // a scoped device buffer, device_prims.hpp
 
@@ -101,13 +102,16 @@ struct DevMat {
     int       autoPick[2] = {-1, -1};
     float     autoMs[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};    // ... and what each candidate took (0 = not tried)
     spmvUpdateInfo lastUpdate{};    // what the last spmvHipUpdateValues / spmvHipValuesChanged did
-    // a transpose (spmvHipCsrTranspose, transpose.hip) or a permutation (spmvHipCsrPermute, colour.hip): for every entry p
-    // of this handle, the CSR position of the same entry in the source (ASt[p] = AS[tmap[p]])
+    // a transpose (spmvHipCsrTranspose, transpose.hip), a permutation (spmvHipCsrPermute, colour.hip) or a filtered handle
+    // (spmvHipCsrFilter, filter.hip): for every entry p of this handle, the CSR position of the same entry in the source
+    // (ASt[p] = AS[tmap[p]])
     uint32_t* tmap = nullptr;
     // a product (spmvHipSpGEMM, spgemm.hip): its rows by class (4 B per row)
     SpgemmPlan* prod = nullptr;
     // a sum (spmvHipCsrAdd, add.hip): its rows by class (4 B per row)
     AddPlan* sum = nullptr;
+    // a filtered handle (spmvHipCsrFilter, filter.hip): its options and, with `lump`, the keep mask and the diagonal places
+    FilterPlan* filt = nullptr;
     // a multigrid hierarchy (spmvHipAmgSetup, amg.hip): the handle is then no matrix (no arrays, NZ = 0) and only the
     // spmvHipAmg* calls, a Krylov solve's dM and hipFreeSpmat take it
     AmgHierarchy* amg = nullptr;
@@ -212,25 +216,40 @@ int  addBuild(double alpha, const DevMat* a, double beta, const DevMat* b, const
               hipStream_t stream);
 int  addRefresh(DevMat* c, double alpha, const DevMat* a, double beta, const DevMat* b, spmvAddInfo* info, hipStream_t stream);
 void freeAddPlan(AddPlan* p);
+// C = the entries of A that a predicate keeps (filter.hip; contract in spmvHip.h, design in DESIGN.md section 29).  filterBuild
+// fills c (kind, M and N set, nothing owned) with IRP (4 B), JA, AS, the map to A's positions and the plan, NZ set, for
+// checked options -- on failure the caller frees c with whatever it holds.  filterRefresh: after A's current values were
+// gathered through the map, the ordered sums of `lump` again over the build's dropped places.  Both synchronous, temporaries
+// freed before they return.  filterInfo: what the build or the last refresh did; filterSetMaxRow takes the longest row
+// from the finished handle.
+int  filterBuild(const DevMat* a, const spmvFilterOpts* opts, DevMat* c, hipStream_t stream);
+int  filterRefresh(DevMat* c, const DevMat* a, hipStream_t stream);
+const spmvFilterInfo* filterInfo(const DevMat* c);
+void filterSetMaxRow(DevMat* c);
+void freeFilterPlan(FilterPlan* p);
 // Aggregation multigrid (amg.hip; contracts in spmvHip.h, design in DESIGN.md section 24).  aggregateCsr: the aggregate ids
 // of the checked square handle into dAgg (M words), K rounds per host check; synchronous, allocates, temporaries freed
 // before it returns.  amgBuild: the hierarchy of the checked handle hA into m->amg, K aggregation rounds per host check (on
 // failure the caller frees m with whatever it holds); omegaP non-null: the smoothed hierarchy of spmvHipAmgSetupSmoothed
 // (*omegaP 0: per level), fuseMax the longest row of a prolongator that its fused correction takes.  amgRefresh: the products,
 // the inverse diagonals and, smoothed, the prolongators again.  amgProlongator: spmvHipAmgProlongator's outputs for a level
-// below the last.
+// below the last.  strength non-null (with omegaP): the hierarchy of spmvHipAmgSetupStrength (a field 0: its default);
+// amgIsStrength / amgStrength: whether a hierarchy is one, and spmvHipAmgStrength's outputs for a level below the last.
 // enqueueAmgCycle: z = V(0, r), kernels only on `stream`; every kernel of the cycle but its SpMVs returns at once when `stop`
 // is set and *stop != 0; *launches grows by the kernels enqueued (an SpMV counted as one).  amgInfo: what the setup or the
 // last refresh did.  amgLevel: spmvHipAmgLevel's outputs for a level below amgInfo()->levels.  ownCsr (upload.hip): a CSR
 // handle that takes ownership of three device arrays.
 int  aggregateCsr(const DevMat* a, uint32_t seed, uint32_t K, uint32_t* dAgg, spmvAggInfo* info, hipStream_t stream);
-int  amgBuild(spmat* hA, const spmvAmgOpts* opts, const double* omegaP, uint32_t fuseMax, uint32_t K, DevMat* m, hipStream_t stream);
+int  amgBuild(spmat* hA, const spmvAmgOpts* opts, const double* omegaP, const spmvAmgStrengthOpts* strength, uint32_t fuseMax, uint32_t K,
+              DevMat* m, hipStream_t stream);
 int  amgRefresh(DevMat* m, spmat* hA, hipStream_t stream);
 int  enqueueAmgCycle(const DevMat* m, spmat* hA, const double* r, double* z, hipStream_t stream, const uint32_t* stop,
                      unsigned long* launches);
 const spmvAmgInfo* amgInfo(const DevMat* m);
 void amgLevel(const DevMat* m, unsigned level, spmat* dAl, const uint32_t** dAgg, const double** dDinv);
 void amgProlongator(const DevMat* m, unsigned level, spmat* dPl, spmat* dRl, double* omegaP);
+bool amgIsStrength(const DevMat* m);
+void amgStrength(const DevMat* m, unsigned level, spmat* dFl, double* theta);
 void freeAmg(AmgHierarchy* h);
 int  ownCsr(spmat* dst, uint64_t M, uint64_t N, uint64_t NZ, uint32_t* dIRP, uint32_t* dJA, double* dAS);
 // Triangular solves (trsv.hip; contract in spmvHip.h, design in DESIGN.md section 17).  triAnalyse builds d->tri[uplo]

@@ -232,8 +232,10 @@ int spmvHipAggregateCSR(spmat* dA, const spmvAggOpts* opts, uint32_t* dAgg, spmv
     return EXIT_SUCCESS;
 }
 
-// the two setups: omegaP null for the plain hierarchy, else the damping of the smoothed prolongator (0: per level)
-static int amgSetup(const char* who, spmat* dA, const spmvAmgOpts* opts, const double* omegaP, spmat* dM, spmvAmgInfo* info) {
+// the three setups: omegaP null for the plain hierarchy, else the damping of the smoothed prolongator (0: per level);
+// strength non-null for the strength-filtered one (a field 0: its default)
+static int amgSetup(const char* who, spmat* dA, const spmvAmgOpts* opts, const double* omegaP, const spmvAmgStrengthOpts* strength, spmat* dM,
+                    spmvAmgInfo* info) {
     if (!ready(who)) return EXIT_FAILURE;
     if (!dA || !dM) { ERR("%s: %s is NULL", who, !dA ? "dA" : "dM"); return EXIT_FAILURE; }
     if (dM == dA) { ERR("%s: dM is the source handle itself", who); return EXIT_FAILURE; }
@@ -243,21 +245,32 @@ static int amgSetup(const char* who, spmat* dA, const spmvAmgOpts* opts, const d
     if (opts && opts->maxLevels > SPMV_AMG_MAX_LEVELS) { ERR("%s: maxLevels %u is above %d", who, opts->maxLevels, SPMV_AMG_MAX_LEVELS); return EXIT_FAILURE; }
     if (opts && !(opts->omega >= 0.0 && std::isfinite(opts->omega))) { ERR("%s: omega %g is negative or not finite", who, opts->omega); return EXIT_FAILURE; }
     if (omegaP && !(*omegaP >= 0.0 && std::isfinite(*omegaP))) { ERR("%s: omegaP %g is negative or not finite", who, *omegaP); return EXIT_FAILURE; }
+    if (strength && !(strength->theta >= 0.0 && std::isfinite(strength->theta))) { ERR("%s: theta %g is negative or not finite", who, strength->theta); return EXIT_FAILURE; }
+    if (strength && !(strength->thetaScale >= 0.0 && strength->thetaScale <= 1.0)) {
+        ERR("%s: thetaScale %g is negative, above 1 or not finite", who, strength->thetaScale);
+        return EXIT_FAILURE;
+    }
     DevMat* m = new DevMat;
     m->M = m->N = a->M;
     setOrigin(m, Origin::HIERARCHY, a);
-    if (amgBuild(dA, opts, omegaP, S.amgFuseMax, S.aggK, m, S.stream)) { ERR("%s: building the hierarchy failed", who); freeDesc(m); return EXIT_FAILURE; }
+    if (amgBuild(dA, opts, omegaP, strength, S.amgFuseMax, S.aggK, m, S.stream)) { ERR("%s: building the hierarchy failed", who); freeDesc(m); return EXIT_FAILURE; }
     publish(dM, m, m->M, m->N, 0, 0);
     if (info) *info = *amgInfo(m);
     return EXIT_SUCCESS;
 }
 
 int spmvHipAmgSetup(spmat* dA, const spmvAmgOpts* opts, spmat* dM, spmvAmgInfo* info) {
-    return amgSetup("spmvHipAmgSetup", dA, opts, nullptr, dM, info);
+    return amgSetup("spmvHipAmgSetup", dA, opts, nullptr, nullptr, dM, info);
 }
 int spmvHipAmgSetupSmoothed(spmat* dA, const spmvAmgOpts* opts, const spmvAmgSmoothOpts* smooth, spmat* dM, spmvAmgInfo* info) {
     const double omegaP = smooth ? smooth->omegaP : 0.0;
-    return amgSetup("spmvHipAmgSetupSmoothed", dA, opts, &omegaP, dM, info);
+    return amgSetup("spmvHipAmgSetupSmoothed", dA, opts, &omegaP, nullptr, dM, info);
+}
+int spmvHipAmgSetupStrength(spmat* dA, const spmvAmgOpts* opts, const spmvAmgSmoothOpts* smooth, const spmvAmgStrengthOpts* strength, spmat* dM,
+                            spmvAmgInfo* info) {
+    const double omegaP = smooth ? smooth->omegaP : 0.0;
+    const spmvAmgStrengthOpts so = strength ? *strength : spmvAmgStrengthOpts{0.0, 0.0};
+    return amgSetup("spmvHipAmgSetupStrength", dA, opts, &omegaP, &so, dM, info);
 }
 
 int spmvHipAmgRefresh(spmat* dM, spmat* dA) {
@@ -314,6 +327,20 @@ int spmvHipAmgProlongator(spmat* dM, unsigned level, spmat* dPl, spmat* dRl, dou
         return EXIT_FAILURE;
     }
     amgProlongator(m, level, dPl, dRl, omegaP);
+    return EXIT_SUCCESS;
+}
+
+int spmvHipAmgStrength(spmat* dM, unsigned level, spmat* dFl, double* theta) {
+    const char* who = "spmvHipAmgStrength";
+    DevMat* m = anyDescOf(dM, who);
+    if (!m) return EXIT_FAILURE;
+    if (!madeBy(m, Origin::HIERARCHY, nullptr, nullptr, who, "dM")) return EXIT_FAILURE;
+    if (!amgIsStrength(m)) { ERR("%s: dM was not made by spmvHipAmgSetupStrength", who); return EXIT_FAILURE; }
+    if (level >= amgInfo(m)->levels - 1) {
+        ERR("%s: level %u of %zu: the last level has no filtered matrix", who, level, (size_t)amgInfo(m)->levels);
+        return EXIT_FAILURE;
+    }
+    amgStrength(m, level, dFl, theta);
     return EXIT_SUCCESS;
 }
 

@@ -1,5 +1,5 @@
 // upload.hip -- device handles: upload, adoption of device arrays, and the handles made from other handles (CSR -> ELL,
-// transpose, permutation, product) with their refreshes; free; and what looks at the values of a handle (unit-value
+// transpose, permutation, product, sum, filter) with their refreshes; free; and what looks at the values of a handle (unit-value
 // detection, the value refresh).
 #include <hip/hip_runtime.h>
 #include <chrono>
@@ -69,6 +69,7 @@ void freeDesc(DevMat* d) {
     freeTri(d->tri[0]); freeTri(d->tri[1]);
     freeSpgemmPlan(d->prod);
     freeAddPlan(d->sum);
+    freeFilterPlan(d->filt);
     freeAmg(d->amg);
     freeTiles(d->tiles[0]); freeTiles(d->tiles[1]);
     freeSell(d->sell);
@@ -316,14 +317,17 @@ static DevMat* newMappedCsr(Origin o, const DevMat* a, uint64_t M, uint64_t N, b
     return t;
 }
 
-// dX (made as `o` from dA) takes dA's current values through its map, then refreshes its formats: the two refreshes
-static int mappedRefresh(const char* who, Origin o, spmat* dX, const char* xName, spmat* dA) {
+// dX (made as `o` from dA) takes dA's current values through its map, then refreshes its formats: the three refreshes.
+// `after` (the filter's ordered sums) runs between the gather and the formats.
+static int mappedRefresh(const char* who, Origin o, spmat* dX, const char* xName, spmat* dA,
+                         int (*after)(DevMat* x, const DevMat* a, hipStream_t st) = nullptr) {
     if (!ready(who)) return EXIT_FAILURE;
     DevMat* t = descOf(dX, who);
     if (!t) return EXIT_FAILURE;
     DevMat* a = descOf(dA, who);
     if (!a || !madeBy(t, o, a, nullptr, who, xName, "dA")) return EXIT_FAILURE;
     if (enqueueGatherValues(t->AS, t->tmap, t->NZ, a->AS, S.stream)) return EXIT_FAILURE;
+    if (after && after(t, a, S.stream)) { ERR("%s: recomputing the values failed", who); return EXIT_FAILURE; }
     return updateValues(dX, nullptr, true, true, S.stream, who);
 }
 
@@ -567,6 +571,58 @@ int spmvHipCsrAddRefresh(spmat* dC, double alpha, spmat* dA, double beta, spmat*
     if (addRefresh(c, alpha, a, beta, b, &out, S.stream)) { ERR("%s: recomputing the values failed", who); return EXIT_FAILURE; }
     if (updateValues(dC, nullptr, true, true, S.stream, who)) return EXIT_FAILURE;
     if (info) *info = out;
+    return EXIT_SUCCESS;
+}
+
+// C = the entries of A that a predicate keeps, as a handle of its own (filter.hip builds the arrays; the contract is in
+// spmvHip.h, the design in DESIGN.md section 29).  Refusals come first; dC and info are written only on success.
+int spmvHipCsrFilter(spmat* dA, const spmvFilterOpts* opts, spmat* dC, spmvFilterInfo* info) {
+    const char* who = "spmvHipCsrFilter";
+    if (!ready(who)) return EXIT_FAILURE;
+    if (!dA || !opts || !dC) { ERR("%s: %s is NULL", who, !dA ? "dA" : !opts ? "opts" : "dC"); return EXIT_FAILURE; }
+    if (dC == dA) { ERR("%s: dC is the source handle itself", who); return EXIT_FAILURE; }
+    DevMat* a = descOf(dA, who);
+    if (!a || !csrOnly(a, who, "the source is an ELL handle (only CSR handles can be filtered)")) return EXIT_FAILURE;
+    if (opts->mode != SPMV_FILTER_BAND && opts->mode != SPMV_FILTER_ABS && opts->mode != SPMV_FILTER_STRENGTH) {
+        ERR("%s: mode %d is none of SPMV_FILTER_BAND, SPMV_FILTER_ABS, SPMV_FILTER_STRENGTH", who, opts->mode);
+        return EXIT_FAILURE;
+    }
+    if (!(opts->theta >= 0.0) || opts->theta > std::numeric_limits<double>::max()) {
+        ERR("%s: theta = %g must be finite and not negative", who, opts->theta);
+        return EXIT_FAILURE;
+    }
+    if (opts->lump && opts->mode == SPMV_FILTER_BAND) {
+        ERR("%s: lump goes with SPMV_FILTER_ABS and SPMV_FILTER_STRENGTH: a band is a function of the pattern alone", who);
+        return EXIT_FAILURE;
+    }
+    if ((opts->lump || opts->mode == SPMV_FILTER_STRENGTH) && a->M != a->N) {
+        ERR("%s: M=%lu != N=%lu: SPMV_FILTER_STRENGTH and lump need the diagonal of a square matrix", who, (unsigned long)a->M, (unsigned long)a->N);
+        return EXIT_FAILURE;
+    }
+    if (a->M >= (1ull << 32) - 1 || a->N >= (1ull << 32) - 1) {
+        ERR("%s: M=%lu, N=%lu: the filtered matrix has 32-bit row and column ids", who, (unsigned long)a->M, (unsigned long)a->N);
+        return EXIT_FAILURE;
+    }
+    if (a->NZ >= IRP32_LIMIT) {
+        ERR("%s: NZ=%lu: the map and the row pointers of the filtered matrix are 32-bit (limit %lu)", who, (unsigned long)a->NZ,
+            (unsigned long)IRP32_LIMIT);
+        return EXIT_FAILURE;
+    }
+    if (a->NZ && (!a->JA || !a->AS)) { ERR("%s: the source has no column or value array", who); return EXIT_FAILURE; }
+    DevMat* c = new DevMat;
+    c->M = a->M; c->N = a->N;
+    setOrigin(c, Origin::FILTER, a);
+    if (finishCsr(dC, c, !filterBuild(a, opts, c, S.stream))) { ERR("%s: building the filtered matrix failed", who); return EXIT_FAILURE; }
+    filterSetMaxRow(c);
+    if (info) *info = *filterInfo(c);
+    return EXIT_SUCCESS;
+}
+
+int spmvHipCsrFilterRefresh(spmat* dC, spmat* dA, spmvFilterInfo* info) {
+    const char* who = "spmvHipCsrFilterRefresh";
+    if (!dA || !dC) { ERR("%s: %s is NULL", who, !dC ? "dC" : "dA"); return EXIT_FAILURE; }
+    if (mappedRefresh(who, Origin::FILTER, dC, "dC", dA, filterRefresh)) return EXIT_FAILURE;
+    if (info) *info = *filterInfo(static_cast<DevMat*>(dC->dev));
     return EXIT_SUCCESS;
 }
 
