@@ -839,7 +839,52 @@ int spmvHipCsrFilterRefresh(spmat* dC, spmat* dA, spmvFilterInfo* info);
  *   thetaScale > 1.
  * spmvHipAmgStrength: a view like spmvHipAmgProlongator's of a level that is not the last: *dFl = a copy of F_l's spmat with
  *   dev = NULL (the arrays stay dM's), *theta = theta_l.  Either may be NULL.  Refused: a dM that is not a hierarchy of
- *   spmvHipAmgSetupStrength, the last level and beyond. */
+ *   spmvHipAmgSetupStrength, the last level and beyond.
+ *
+ * Chebyshev smoother of the cycle.  spmvHipAmgSetSmoother(dM, dA, opts) chooses what a hierarchy of
+ *   any of the three setups smooths with, and how often: it changes what spmvHipAmgApply, and every Krylov loop that takes
+ *   the hierarchy as dM, enqueues FROM THEN ON -- a cycle captured earlier must be captured again.  Synchronous on the library
+ *   stream; it allocates the coefficient tables (and nothing else), so it is not capturable.  opts (NULL, or a field 0: the
+ *   built-in default): kind JACOBI; nu1, nu2, nuCoarse 0: the hierarchy's current counts, SPMV_AMG_NO_SWEEPS: none, at most
+ *   SPMV_AMG_MAX_DEGREE otherwise; eigRatio 10 (a convention); lambdaScale 1.0.  The counts apply to both kinds: with kind
+ *   JACOBI the call changes the sweeps of a Jacobi hierarchy without a new setup, and the cycle is V(l, r) above, its bits and
+ *   its kernel count, for those counts.  A hierarchy on which the call was never made is untouched in every respect.
+ *   With kind CHEBYSHEV, per level l (the last included; on a strength hierarchy from A_l, NOT F_l: the sweeps are A_l's):
+ *       rho_l = max_i fabs(dinv_l[i]) * s_i, s_i the sum of fabs(A_l.AS[p]) over row i in stored order from +0.0  (as above)
+ *       lmax = lambdaScale * rho_l;   lmin = lmax / eigRatio
+ *       theta = (lmax + lmin) / 2.0;  delta = (lmax - lmin) / 2.0;  sigma = theta / delta
+ *       s_0 = 1.0 / sigma;            a_0 = 0.0;   b_0 = 1.0 / theta
+ *       k >= 1:  s_k = 1.0 / (2.0 * sigma - s_{k-1});   a_k = s_k * s_{k-1};   b_k = (2.0 * s_k) / delta
+ *   for k < max(nu1, nu2), on the last level k < nuCoarse -- computed on the host in IEEE double, every operation rounded in
+ *   the order written (2.0 * sigma - s is a product, then a difference); a numpy float64 transcription gives the same bits.
+ *   rho_l = ||D^-1 A||_inf bounds lambda_max(D^-1 A) for any matrix and does not depend on a summation order.  The pairs
+ *   (a_k, b_k) of a level live in device memory and the kernels read them there (one uniform 16-byte load), so a captured
+ *   cycle replayed after spmvHipAmgRefresh uses the new coefficients.  A level without rows has rho_l = 0 and zeros.
+ *   The smoother, d the level's d_l (free at both places; no new vector), no FMA:
+ *       Cheb(l, r, z, q, fromNothing):
+ *         k = 0, fromNothing:  d_i = b_0 * (dinv_i * r_i);                          z_i = d_i          (no SpMV)
+ *         k = 0, otherwise:    t = A_l z;  d_i = b_0 * (dinv_i * (r_i - t_i));      z_i = z_i + d_i
+ *         k = 1 .. q-1:        t = A_l z;  d_i = a_k * d_i + b_k * (dinv_i * (r_i - t_i));   z_i = z_i + d_i
+ *   and the cycle is V(l, r) above with its pre-smoothing lines replaced by Cheb(l, r, z, sweeps, true) (z_i = +0.0 when
+ *   sweeps == 0) and its nu2 lines by Cheb(l, r, z, nu2, false): the recurrence RESTARTS at k = 0 there.  The residual, the
+ *   restriction and the correction (gather, P e in both forms, the fuse threshold) are unchanged, and so is the kernel count:
+ *   a Chebyshev step is one SpMV and one pass, like a sweep.
+ *   spmvHipAmgRefresh on a Chebyshev hierarchy recomputes, after dinv_l, rho_l and the table of every level and writes the
+ *   table to the same device address: bit-identical to a fresh setup followed by the same spmvHipAmgSetSmoother.  A rho_l
+ *   that is 0 or not finite refuses the refresh with the line below; a later refresh with good values recovers.
+ *   spmvAmgInfo.bytes counts the tables (16 B per pair).
+ *   Refused with a message and EXIT_FAILURE, the hierarchy, its smoother and its tables exactly as they were: NULL dM or dA;
+ *   handles that are not live; a dM that is not a hierarchy; a dA that is not the source; an unknown kind; an eigRatio that is
+ *   not finite or is <= 1 (0 excepted: the default); a lambdaScale that is negative or not finite; a count above
+ *   SPMV_AMG_MAX_DEGREE other than SPMV_AMG_NO_SWEEPS; with CHEBYSHEV a level whose rho_l is 0 or not finite (the line names
+ *   the level and the first such row).
+ * spmvHipAmgSmoother: a view of level l: kind, the counts in force (0: none), rho_l, lambdaMax, lambdaMin, nCoef and dCoef =
+ *   the device address of the nCoef pairs (a_0, b_0, a_1, b_1, ...; NULL when nCoef = 0).  On a hierarchy never given a
+ *   smoother, or given JACOBI: kind JACOBI, the counts, zeros and NULL.  Refused, info untouched: a dM that is not a
+ *   hierarchy, a level beyond the last, a NULL info. */
+#define SPMV_AMG_SMOOTHER_JACOBI     0
+#define SPMV_AMG_SMOOTHER_CHEBYSHEV  1
+#define SPMV_AMG_MAX_DEGREE          64
 #define SPMV_AMG_MAX_LEVELS 16
 #define SPMV_AMG_NO_SWEEPS  0xFFFFFFFFu
 typedef struct {
@@ -892,6 +937,16 @@ typedef struct {            /* 0 = the built-in default */
 int spmvHipAmgSetupStrength(spmat* dA, const spmvAmgOpts* opts, const spmvAmgSmoothOpts* smooth,
                             const spmvAmgStrengthOpts* strength, spmat* dM, spmvAmgInfo* info);
 int spmvHipAmgStrength(spmat* dM, unsigned level, spmat* dFl, double* theta);
+typedef struct {            /* 0 = the built-in default */
+    int      kind;          /* SPMV_AMG_SMOOTHER_*  (JACOBI)                                   */
+    unsigned nu1, nu2, nuCoarse;   /* 0: keep the hierarchy's; SPMV_AMG_NO_SWEEPS: none       */
+    double   eigRatio;      /* lambda_min = lambda_max / eigRatio (10); must be > 1            */
+    double   lambdaScale;   /* lambda_max_l = lambdaScale * rho_l (1.0)                        */
+} spmvAmgSmootherOpts;
+typedef struct { int kind; unsigned nu1, nu2, nuCoarse; double rho, lambdaMax, lambdaMin;
+                 unsigned nCoef; const double* dCoef; } spmvAmgSmootherInfo;
+int spmvHipAmgSetSmoother(spmat* dM, spmat* dA, const spmvAmgSmootherOpts* opts);
+int spmvHipAmgSmoother(spmat* dM, unsigned level, spmvAmgSmootherInfo* info);
 /* Release the device arrays behind a handle (cudaUtils.h:70-78). */
 int hipFreeSpmat(spmat* dMat);
 

@@ -135,6 +135,8 @@ _sigs = {
     "spmvHipAmgProlongator": ([C.POINTER(spmat), C.c_uint, C.POINTER(spmat), C.POINTER(spmat), C.POINTER(C.c_double)], _i),
     "spmvHipAmgSetupStrength": ([C.POINTER(spmat), _vp, _vp, _vp, C.POINTER(spmat), _vp], _i),
     "spmvHipAmgStrength": ([C.POINTER(spmat), C.c_uint, C.POINTER(spmat), C.POINTER(C.c_double)], _i),
+    "spmvHipAmgSetSmoother": ([C.POINTER(spmat), C.POINTER(spmat), _vp], _i),
+    "spmvHipAmgSmoother": ([C.POINTER(spmat), C.c_uint, _vp], _i),
 }
 SPMV_DENSE_ROW_MAJOR, SPMV_DENSE_COL_MAJOR = 0, 1          # include/spmvHip.h: layouts of hipSpMMRowsCSR's X and Y
 SPMV_TRI_LOWER, SPMV_TRI_UPPER = 0, 1                      # include/spmvHip.h: hipSpTRSVCSR's uplo ...
@@ -295,6 +297,21 @@ class spmvAmgSmoothOpts(C.Structure):
 class spmvAmgStrengthOpts(C.Structure):
     """include/spmvHip.h `spmvAmgStrengthOpts`: the strength threshold per level (0: 0.08, scaled by 0.5 per level)."""
     _fields_ = [("theta", C.c_double), ("thetaScale", C.c_double)]
+
+
+SPMV_AMG_SMOOTHER_JACOBI, SPMV_AMG_SMOOTHER_CHEBYSHEV, SPMV_AMG_MAX_DEGREE = 0, 1, 64
+
+
+class spmvAmgSmootherOpts(C.Structure):
+    """include/spmvHip.h `spmvAmgSmootherOpts`: the smoother of the cycle and its sweep counts (a field 0: the default)."""
+    _fields_ = [("kind", _i), ("nu1", C.c_uint), ("nu2", C.c_uint), ("nuCoarse", C.c_uint), ("eigRatio", C.c_double),
+                ("lambdaScale", C.c_double)]
+
+
+class spmvAmgSmootherInfo(C.Structure):
+    """include/spmvHip.h `spmvAmgSmootherInfo`: the smoother of one level; dCoef is the device address of nCoef (a, b) pairs."""
+    _fields_ = [("kind", _i), ("nu1", C.c_uint), ("nu2", C.c_uint), ("nuCoarse", C.c_uint), ("rho", C.c_double),
+                ("lambdaMax", C.c_double), ("lambdaMin", C.c_double), ("nCoef", C.c_uint), ("dCoef", C.POINTER(C.c_double))]
 
 
 SPMV_COLOUR_NATURAL, SPMV_COLOUR_HASH = 0, 1
@@ -1071,7 +1088,8 @@ class DeviceMatrix:
 
 class AmgHierarchy(DeviceMatrix):
     """What DeviceMatrix.amg() returns: a hierarchy handle (no matrix: SpMV, formats and solves refuse it) with `info`
-    (spmvAmgInfo), apply(), refresh_from(), level(), prolongator(), strength() and free().  It keeps a reference to its source matrix."""
+    (spmvAmgInfo), apply(), refresh_from(), level(), prolongator(), strength(), set_smoother(), smoother() and free().  It keeps a
+    reference to its source matrix."""
 
     def __init__(self, source):
         super().__init__()
@@ -1123,6 +1141,33 @@ class AmgHierarchy(DeviceMatrix):
         F, theta = spmat(), C.c_double()
         _check(lib.spmvHipAmgStrength(C.byref(self.handle), int(l), C.byref(F), C.byref(theta)), "spmvHipAmgStrength")
         return self._down(F), theta.value
+
+    def set_smoother(self, kind="chebyshev", nu1=None, nu2=None, nuCoarse=None, eig_ratio=None, lambda_scale=None):
+        """spmvHipAmgSetSmoother: what the cycle smooths with from now on, "jacobi" or "chebyshev" (or the header's number),
+        and how often: a count None keeps the hierarchy's, 0 asks for none.  eig_ratio (10) and lambda_scale (1.0) are the
+        Chebyshev interval: lambda_max = lambda_scale * rho_l, lambda_min = lambda_max / eig_ratio.  A cycle captured
+        earlier must be captured again.  `info` is read again (its bytes count the coefficient tables)."""
+        def sweeps(v):
+            return 0 if v is None else SPMV_AMG_NO_SWEEPS if int(v) == 0 else int(v)
+        kinds = {"jacobi": SPMV_AMG_SMOOTHER_JACOBI, "chebyshev": SPMV_AMG_SMOOTHER_CHEBYSHEV}
+        if isinstance(kind, str) and kind not in kinds:
+            raise SpmvHipError(f"set_smoother: kind {kind!r} is neither 'jacobi' nor 'chebyshev'")
+        opts = spmvAmgSmootherOpts(kinds[kind] if isinstance(kind, str) else int(kind), sweeps(nu1), sweeps(nu2), sweeps(nuCoarse),
+                                   float(eig_ratio or 0.0), float(lambda_scale or 0.0))
+        _check(lib.spmvHipAmgSetSmoother(C.byref(self.handle), C.byref(self.source.handle), C.byref(opts)), "spmvHipAmgSetSmoother")
+        _check(lib.spmvHipAmgInfo(C.byref(self.handle), C.byref(self.info)), "spmvHipAmgInfo")
+
+    def smoother(self, l):
+        """spmvHipAmgSmoother: the smoother of level l as a dict: kind, nu1, nu2, nuCoarse (the counts in force), rho,
+        lambdaMax, lambdaMin, dCoef (the device address of the table, None without one) and coef, the table downloaded: an
+        (nCoef, 2) array of the pairs (a_k, b_k)"""
+        v = spmvAmgSmootherInfo()
+        _check(lib.spmvHipAmgSmoother(C.byref(self.handle), int(l), C.byref(v)), "spmvHipAmgSmoother")
+        coef = np.empty((int(v.nCoef), 2), np.float64)
+        if coef.size:
+            _check(lib.spmvHipMemcpyDown(coef.ctypes.data_as(C.c_void_p), C.cast(v.dCoef, C.c_void_p), coef.nbytes), "spmvHipMemcpyDown")
+        return dict(kind=int(v.kind), nu1=int(v.nu1), nu2=int(v.nu2), nuCoarse=int(v.nuCoarse), rho=float(v.rho), lambdaMax=float(v.lambdaMax),
+                    lambdaMin=float(v.lambdaMin), dCoef=C.cast(v.dCoef, C.c_void_p).value, coef=coef)
 
     def free(self):
         super().free()

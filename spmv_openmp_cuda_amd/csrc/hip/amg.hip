@@ -30,6 +30,13 @@
 // (dF_l = 1 / diag F_l, rho_l, w_l, D_l, F_l T_l) on F_l's values.  The Galerkin product stays R_l (A_l P_l) on the full A_l,
 // and the cycle is the smoothed one, its Jacobi sweeps on dinv_l of A_l.  The refresh runs spmvHipCsrFilterRefresh first:
 // the kept sets are the build's.
+//
+// Chebyshev smoother (spmvHipAmgSetSmoother).  A hierarchy of any of the three setups may smooth with
+// the three-term recurrence on D^-1 A instead of damped Jacobi: per level lambda_max = lambdaScale * rho_l, rho_l from
+// amg_rho_kernel on A_l and dinv_l (the last level too, and A_l -- not F_l -- on a strength hierarchy), the pairs (a_k, b_k)
+// computed on the host (chebTable) and kept in DEVICE memory, where the two passes (AmgChebFirstOp, AmgChebStepOp) read
+// them: a refresh rewrites the table in place and a captured cycle sees the new values.  The recurrence's d is the level's
+// d_l.  A step is one serial-order SpMV and one pass, as a Jacobi sweep is: the launch count is the formula of the sweeps.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <chrono>
@@ -54,6 +61,10 @@ struct AmgLevel {
     double* dinv = nullptr;
     double *r = nullptr, *z = nullptr;  // below level 0: the restricted residual and the correction
     double *t = nullptr, *d = nullptr;
+    // Chebyshev: rho of A_l and dinv_l, the interval, and the nCoef pairs (a_k, b_k) on the device (null when nCoef = 0)
+    double rhoS = 0.0, lmax = 0.0, lmin = 0.0;
+    uint32_t nCoef = 0;
+    double2* coef = nullptr;
 };
 
 struct AmgHierarchy {
@@ -64,6 +75,8 @@ struct AmgHierarchy {
     uint32_t fuseMax = 0;               // smoothed: the longest row of P that the fused correction takes (0: never fused)
     bool strength = false;              // smoothed on the strength-filtered F_l
     double theta = 0.0, thetaScale = 0.0;   // strength: theta_0, and theta_{l+1} = theta_l * thetaScale
+    int smoother = SPMV_AMG_SMOOTHER_JACOBI;    // of the cycle (spmvHipAmgSetSmoother)
+    double eigRatio = 10.0, lambdaScale = 1.0;  // Chebyshev: lambda_min = lambda_max / eigRatio, lambda_max = lambdaScale * rho_l
     std::vector<AmgLevel> lv;
     spmvAmgInfo info{};
 };
@@ -302,6 +315,46 @@ struct AmgSweepOp : StopMode {                  // z = z + omega * (dinv * (r - 
         st2<VEC>(z, i, two, make_double2(v.z.x + omega * (v.d.x * (v.r.x - v.t.x)), v.z.y + omega * (v.d.y * (v.r.y - v.t.y))));
     }
 };
+// The pair (a_k, b_k) of a Chebyshev step is one uniform 16-byte load from the level's table, made in load() with the
+// slot's other loads (in step() it would come after the stores of the slot before, and every slot would wait for it alone).
+template <bool FROM_Z>
+struct AmgChebFirstOp : StopMode {              // k = 0: d = b_0 * (dinv * r), z = d; FROM_Z: d = b_0 * (dinv * (r - t)), z = z + d
+    static constexpr int NDOT = 0;
+    const double* r; const double* t; const double* dinv; double* d; double* z; const double2* c;
+    struct R { double2 r, t, di, z, c; };
+    template <bool VEC> __device__ void load(uint64_t i, bool two, R& v) const {
+        v.c = *c;
+        v.r = ld2<VEC>(r, i, two); v.di = ld2<VEC>(dinv, i, two);
+        if (FROM_Z) { v.t = ld2<VEC>(t, i, two); v.z = ld2<VEC>(z, i, two); }
+    }
+    template <bool VEC> __device__ void step(uint64_t i, bool two, const R& v, double&, double&) const {
+        const double b = v.c.y;
+        if (FROM_Z) {
+            const double2 dn = make_double2(b * (v.di.x * (v.r.x - v.t.x)), b * (v.di.y * (v.r.y - v.t.y)));
+            st2<VEC>(d, i, two, dn);
+            st2<VEC>(z, i, two, make_double2(v.z.x + dn.x, v.z.y + dn.y));
+        } else {
+            const double2 dn = make_double2(b * (v.di.x * v.r.x), b * (v.di.y * v.r.y));
+            st2<VEC>(d, i, two, dn);
+            st2<VEC>(z, i, two, dn);
+        }
+    }
+};
+struct AmgChebStepOp : StopMode {               // k >= 1: d = a_k * d + b_k * (dinv * (r - t)), z = z + d
+    static constexpr int NDOT = 0;
+    const double* r; const double* t; const double* dinv; double* d; double* z; const double2* c;
+    struct R { double2 r, t, di, d, z, c; };
+    template <bool VEC> __device__ void load(uint64_t i, bool two, R& v) const {
+        v.c = *c;
+        v.r = ld2<VEC>(r, i, two); v.t = ld2<VEC>(t, i, two); v.di = ld2<VEC>(dinv, i, two); v.d = ld2<VEC>(d, i, two); v.z = ld2<VEC>(z, i, two);
+    }
+    template <bool VEC> __device__ void step(uint64_t i, bool two, const R& v, double&, double&) const {
+        const double2 ab = v.c;
+        const double2 dn = make_double2(ab.x * v.d.x + ab.y * (v.di.x * (v.r.x - v.t.x)), ab.x * v.d.y + ab.y * (v.di.y * (v.r.y - v.t.y)));
+        st2<VEC>(d, i, two, dn);
+        st2<VEC>(z, i, two, make_double2(v.z.x + dn.x, v.z.y + dn.y));
+    }
+};
 struct AmgResidOp : StopMode {                  // d = r - t
     static constexpr int NDOT = 0;
     const double* r; const double* t; double* d;
@@ -407,6 +460,59 @@ int levelDamping(const AmgHierarchy* H, const DevMat* a, const double* dinv, siz
     return EXIT_SUCCESS;
 }
 
+// the Chebyshev interval and the n pairs (a_k, b_k) of the header, a_0 = 0.0, in IEEE double with every operation rounded
+// in the order written: this file is compiled with -ffp-contract=off (HIPFLAGS of the Makefile, host and device alike), so
+// 2.0 * sigma - s is a product and a difference, and the pragma below says so again for this function alone
+struct ChebTable { double rho = 0.0, lmax = 0.0, lmin = 0.0; std::vector<double2> ab; };
+void chebTable(double rho, double eigRatio, double lambdaScale, uint32_t n, ChebTable* out) {
+#pragma clang fp contract(off)
+    out->rho = rho;
+    const double lmax = lambdaScale * rho, lmin = lmax / eigRatio;
+    out->lmax = lmax; out->lmin = lmin;
+    out->ab.assign(n, make_double2(0.0, 0.0));
+    if (!n) return;
+    const double theta = (lmax + lmin) / 2.0, delta = (lmax - lmin) / 2.0, sigma = theta / delta;
+    double s = 1.0 / sigma;
+    out->ab[0] = make_double2(0.0, 1.0 / theta);
+    for (uint32_t k = 1; k < n; ++k) {
+        const double twice = 2.0 * sigma;
+        const double sk = 1.0 / (twice - s);
+        const double a = sk * s;
+        const double twoS = 2.0 * sk;
+        out->ab[k] = make_double2(a, twoS / delta);
+        s = sk;
+    }
+}
+
+// rho of level l from A_l's stored rows and dinv_l, and its table of n pairs; refuses (with its line) a row sum that is not
+// finite and rho = 0.  A level without rows has rho = 0 and a table of zeros (no kernel reads it).
+int levelCheb(const DevMat* a, const AmgLevel& L, size_t l, uint32_t n, double eigRatio, double lambdaScale, const char* module, ChebTable* out,
+              hipStream_t st) {
+    double rho = 0.0;
+    long bad = -1;
+    if (!a->M) { out->rho = out->lmax = out->lmin = 0.0; out->ab.assign(n, make_double2(0.0, 0.0)); return EXIT_SUCCESS; }
+    if (levelRho(a, L.dinv, &rho, &bad, st)) return buildFail(st, module, "the row sums");
+    const bool zero = bad < 0 && !(rho > 0.0);
+    if (bad >= 0 || zero) {
+        fprintf(stderr, "libspmvhip: %s: row %ld of level %zu: |dinv| * (the sum of |a_ij|) is %s, the Chebyshev smoother needs 0 < rho < Inf\n",
+                module, zero ? 0l : bad, l, zero ? "0, as in every row" : "not finite");
+        return EXIT_FAILURE;
+    }
+    chebTable(rho, eigRatio, lambdaScale, n, out);
+    return EXIT_SUCCESS;
+}
+
+// the pairs a level's table holds: up to the larger of nu1 and nu2, up to nuCoarse on the last level
+uint32_t chebPairs(const AmgHierarchy* H, size_t l, uint32_t nu1, uint32_t nu2, uint32_t nuCoarse) {
+    return l + 1 == H->lv.size() ? nuCoarse : std::max(nu1, nu2);
+}
+// a table onto the device at `dst` (n pairs), synchronously
+int chebUpload(double2* dst, const ChebTable& tb, hipStream_t st) {
+    if (tb.ab.empty()) return EXIT_SUCCESS;
+    return hipMemcpyAsync(dst, tb.ab.data(), tb.ab.size() * sizeof(double2), hipMemcpyHostToDevice, st) == hipSuccess &&
+           hipStreamSynchronize(st) == hipSuccess ? EXIT_SUCCESS : EXIT_FAILURE;
+}
+
 // the serial-order selection of a handle, made now on workspace vectors so that the cycle only enqueues
 int warmSpmv(spmat* h, double* x, double* y, hipStream_t st) {
     const DevMat* d = matOf(h);
@@ -429,6 +535,7 @@ void freeAmg(AmgHierarchy* h) {
         for (spmat* m : {&l.A, &l.P, &l.R, &l.AP, &l.T, &l.D, &l.AT, &l.DAT, &l.F})
             if (m->dev) (void)hipFreeSpmat(m);
         for (double* p : {l.dinv, l.r, l.z, l.t, l.d, l.dF}) (void)hipFree(p);
+        (void)hipFree(l.coef);
     }
     delete h;
 }
@@ -648,6 +755,12 @@ int amgRefresh(DevMat* m, spmat* hA, hipStream_t st) {
         long bad = -1;
         if (levelDinv(matOf(cur), L.dinv, &bad, st)) return fail("the diagonal");
         if (bad >= 0) { fprintf(stderr, "libspmvhip: multigrid refresh: row %ld of level %zu lost its one diagonal entry\n", bad, l); return EXIT_FAILURE; }
+        if (H->smoother == SPMV_AMG_SMOOTHER_CHEBYSHEV) {      // rho_l and the table again, at the table's address
+            ChebTable tb;
+            if (levelCheb(matOf(cur), L, l, L.nCoef, H->eigRatio, H->lambdaScale, "multigrid refresh", &tb, st)) return EXIT_FAILURE;
+            if (chebUpload(L.coef, tb, st)) return fail("a level's Chebyshev table");
+            L.rhoS = tb.rho; L.lmax = tb.lmax; L.lmin = tb.lmin;
+        }
         if (warmSpmv(cur, L.d, L.t, st)) return fail("the SpMV selection of a level");
         if (l + 1 == H->lv.size()) break;
         if (H->smoothed) {
@@ -691,6 +804,18 @@ int enqueueAmgCycle(const DevMat* m, spmat* hA, const double* r0, double* z0, hi
         pass(L.M, AmgSweepOp{{stop}, r, L.t, L.dinv, z, om}, {r, L.t, L.dinv, z});
         return EXIT_SUCCESS;
     };
+    // q Chebyshev steps on level l, the recurrence from k = 0 (d is the level's d_l: free at both smoothing sites)
+    const bool cheb = H->smoother == SPMV_AMG_SMOOTHER_CHEBYSHEV;
+    auto chebyshev = [&](size_t l, const double* r, double* z, uint32_t q, bool fromNothing) {
+        AmgLevel& L = H->lv[l];
+        for (uint32_t k = 0; k < q; ++k) {
+            if ((k || !fromNothing) && spmv(matAt(l), z, L.t)) return EXIT_FAILURE;
+            if (k) pass(L.M, AmgChebStepOp{{stop}, r, L.t, L.dinv, L.d, z, L.coef + k}, {r, L.t, L.dinv, L.d, z});
+            else if (fromNothing) pass(L.M, AmgChebFirstOp<false>{{stop}, r, nullptr, L.dinv, L.d, z, L.coef}, {r, L.dinv, L.d, z});
+            else pass(L.M, AmgChebFirstOp<true>{{stop}, r, L.t, L.dinv, L.d, z, L.coef}, {r, L.t, L.dinv, L.d, z});
+        }
+        return EXIT_SUCCESS;
+    };
     for (size_t l = 0; l < nl; ++l) {                          // down
         AmgLevel& L = H->lv[l];
         const double* r = l ? L.r : r0;
@@ -698,9 +823,12 @@ int enqueueAmgCycle(const DevMat* m, spmat* hA, const double* r0, double* z0, hi
         const bool last = l + 1 == nl;
         const uint32_t sweeps = last ? H->nuCoarse : H->nu1;
         if (sweeps == 0) pass(L.M, AmgZeroOp{{stop}, z}, {z});
-        else pass(L.M, AmgFirstOp{{stop}, r, L.dinv, z, om}, {r, L.dinv, z});
-        for (uint32_t s = 1; s < sweeps; ++s)
-            if (sweep(l, r, z)) return EXIT_FAILURE;
+        else if (cheb) { if (chebyshev(l, r, z, sweeps, true)) return EXIT_FAILURE; }
+        else {
+            pass(L.M, AmgFirstOp{{stop}, r, L.dinv, z, om}, {r, L.dinv, z});
+            for (uint32_t s = 1; s < sweeps; ++s)
+                if (sweep(l, r, z)) return EXIT_FAILURE;
+        }
         if (last) break;
         if (spmv(matAt(l), z, L.t)) return EXIT_FAILURE;
         pass(L.M, AmgResidOp{{stop}, r, L.t, L.d}, {r, L.t, L.d});
@@ -723,11 +851,54 @@ int enqueueAmgCycle(const DevMat* m, spmat* hA, const double* r0, double* z0, hi
             if (spmv(&L.P, e, L.d)) return EXIT_FAILURE;
             pass(L.M, AmgAddOp{{stop}, L.d, z}, {L.d, z});
         }
-        for (uint32_t s = 0; s < H->nu2; ++s)
-            if (sweep(l, r, z)) return EXIT_FAILURE;
+        if (cheb) { if (chebyshev(l, r, z, H->nu2, false)) return EXIT_FAILURE; }
+        else
+            for (uint32_t s = 0; s < H->nu2; ++s)
+                if (sweep(l, r, z)) return EXIT_FAILURE;
     }
     if (launches) *launches += n;
     return hipGetLastError() == hipSuccess ? EXIT_SUCCESS : EXIT_FAILURE;
+}
+
+int amgSetSmoother(DevMat* m, spmat* hA, const spmvAmgSmootherOpts* o, hipStream_t st) {
+    AmgHierarchy* H = m->amg;
+    const size_t nl = H->lv.size();
+    auto sweeps = [](unsigned v, uint32_t kept) { return v == 0 ? kept : v == SPMV_AMG_NO_SWEEPS ? 0u : v; };
+    const int kind = o ? o->kind : SPMV_AMG_SMOOTHER_JACOBI;
+    const uint32_t nu1 = sweeps(o ? o->nu1 : 0, H->nu1), nu2 = sweeps(o ? o->nu2 : 0, H->nu2), nuCoarse = sweeps(o ? o->nuCoarse : 0, H->nuCoarse);
+    const double eigRatio = o && o->eigRatio != 0.0 ? o->eigRatio : 10.0, lambdaScale = o && o->lambdaScale != 0.0 ? o->lambdaScale : 1.0;
+    // everything new is made first: a refusal leaves the hierarchy as it was
+    std::vector<ChebTable> tb(nl);
+    std::vector<double2*> dev(nl, nullptr);
+    auto drop = [&]() { for (double2* p : dev) (void)hipFree(p); return EXIT_FAILURE; };
+    if (kind == SPMV_AMG_SMOOTHER_CHEBYSHEV)
+        for (size_t l = 0; l < nl; ++l) {
+            const uint32_t n = chebPairs(H, l, nu1, nu2, nuCoarse);
+            if (levelCheb(matOf(l ? &H->lv[l].A : hA), H->lv[l], l, n, eigRatio, lambdaScale, "multigrid smoother", &tb[l], st)) return drop();
+            if (n && (hipMalloc(&dev[l], n * sizeof(double2)) != hipSuccess || chebUpload(dev[l], tb[l], st))) {
+                buildFail(st, "multigrid smoother", "a level's Chebyshev table");
+                return drop();
+            }
+        }
+    if (hipStreamSynchronize(st) != hipSuccess) return drop();     // (no cycle in flight reads a table that goes)
+    for (size_t l = 0; l < nl; ++l) {
+        AmgLevel& L = H->lv[l];
+        H->info.bytes -= L.nCoef * sizeof(double2);
+        (void)hipFree(L.coef);
+        L.coef = dev[l];
+        L.nCoef = (uint32_t)tb[l].ab.size();
+        L.rhoS = tb[l].rho; L.lmax = tb[l].lmax; L.lmin = tb[l].lmin;
+        H->info.bytes += L.nCoef * sizeof(double2);
+    }
+    H->smoother = kind; H->eigRatio = eigRatio; H->lambdaScale = lambdaScale;
+    H->nu1 = nu1; H->nu2 = nu2; H->nuCoarse = nuCoarse;
+    return EXIT_SUCCESS;
+}
+
+void amgSmoother(const DevMat* m, unsigned level, spmvAmgSmootherInfo* info) {
+    const AmgHierarchy* H = m->amg;
+    const AmgLevel& L = H->lv[level];
+    *info = spmvAmgSmootherInfo{H->smoother, H->nu1, H->nu2, H->nuCoarse, L.rhoS, L.lmax, L.lmin, L.nCoef, reinterpret_cast<const double*>(L.coef)};
 }
 
 const spmvAmgInfo* amgInfo(const DevMat* m) { return &m->amg->info; }

@@ -238,7 +238,11 @@ void freeFilterPlan(FilterPlan* p);
 // enqueueAmgCycle: z = V(0, r), kernels only on `stream`; every kernel of the cycle but its SpMVs returns at once when `stop`
 // is set and *stop != 0; *launches grows by the kernels enqueued (an SpMV counted as one).  amgInfo: what the setup or the
 // last refresh did.  amgLevel: spmvHipAmgLevel's outputs for a level below amgInfo()->levels.  ownCsr (upload.hip): a CSR
-// handle that takes ownership of three device arrays.
+// handle that takes ownership of three device arrays.  amgSetSmoother: spmvHipAmgSetSmoother on checked handles and options
+// (the smoother of the cycle and its sweep counts; synchronous, allocates the tables; a failure leaves the hierarchy as it
+// was).  amgSmoother: spmvHipAmgSmoother's output for a level below amgInfo()->levels.
+int  amgSetSmoother(DevMat* m, spmat* hA, const spmvAmgSmootherOpts* opts, hipStream_t stream);
+void amgSmoother(const DevMat* m, unsigned level, spmvAmgSmootherInfo* info);
 int  aggregateCsr(const DevMat* a, uint32_t seed, uint32_t K, uint32_t* dAgg, spmvAggInfo* info, hipStream_t stream);
 int  amgBuild(spmat* hA, const spmvAmgOpts* opts, const double* omegaP, const spmvAmgStrengthOpts* strength, uint32_t fuseMax, uint32_t K,
               DevMat* m, hipStream_t stream);

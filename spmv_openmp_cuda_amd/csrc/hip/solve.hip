@@ -344,6 +344,36 @@ int spmvHipAmgStrength(spmat* dM, unsigned level, spmat* dFl, double* theta) {
     return EXIT_SUCCESS;
 }
 
+int spmvHipAmgSetSmoother(spmat* dM, spmat* dA, const spmvAmgSmootherOpts* opts) {
+    const char* who = "spmvHipAmgSetSmoother";
+    DevMat* a = nullptr;
+    DevMat* m = hierarchyOf(dM, dA, who, &a);
+    if (!m) return EXIT_FAILURE;
+    if (opts) {
+        if (opts->kind != SPMV_AMG_SMOOTHER_JACOBI && opts->kind != SPMV_AMG_SMOOTHER_CHEBYSHEV) { ERR("%s: kind %d is no smoother", who, opts->kind); return EXIT_FAILURE; }
+        if (opts->eigRatio != 0.0 && !(opts->eigRatio > 1.0 && std::isfinite(opts->eigRatio))) {
+            ERR("%s: eigRatio %g is not finite or not above 1", who, opts->eigRatio);
+            return EXIT_FAILURE;
+        }
+        if (!(opts->lambdaScale >= 0.0 && std::isfinite(opts->lambdaScale))) { ERR("%s: lambdaScale %g is negative or not finite", who, opts->lambdaScale); return EXIT_FAILURE; }
+        for (unsigned nu : {opts->nu1, opts->nu2, opts->nuCoarse})
+            if (nu > SPMV_AMG_MAX_DEGREE && nu != SPMV_AMG_NO_SWEEPS) { ERR("%s: %u sweeps are above %d", who, nu, SPMV_AMG_MAX_DEGREE); return EXIT_FAILURE; }
+    }
+    if (amgSetSmoother(m, dA, opts, S.stream)) { ERR("%s: the smoother was not set", who); return EXIT_FAILURE; }
+    return EXIT_SUCCESS;
+}
+
+int spmvHipAmgSmoother(spmat* dM, unsigned level, spmvAmgSmootherInfo* info) {
+    const char* who = "spmvHipAmgSmoother";
+    DevMat* m = anyDescOf(dM, who);
+    if (!m) return EXIT_FAILURE;
+    if (!info) { ERR("%s: info is NULL", who); return EXIT_FAILURE; }
+    if (!madeBy(m, Origin::HIERARCHY, nullptr, nullptr, who, "dM")) return EXIT_FAILURE;
+    if (level >= amgInfo(m)->levels) { ERR("%s: level %u of %zu", who, level, (size_t)amgInfo(m)->levels); return EXIT_FAILURE; }
+    amgSmoother(m, level, info);
+    return EXIT_SUCCESS;
+}
+
 // ---- Krylov solves
 // what the three solvers check alike: 0 go on (a, m set), 1 refused, 2 done (M = 0)
 static int krylovArgs(const char* who, spmat* dA, spmat* dM, const double* dB, double* dX, const void* optsPtr, double tol, ulong maxIter,
