@@ -370,6 +370,11 @@ def _check(rc, what):
         raise SpmvHipError(f"{what} failed (EXIT_FAILURE) -- see stderr")
 
 
+def _amg_sweeps(v):
+    """a sweep count for spmvAmgOpts / spmvAmgSmootherOpts: None is the C side's 0 (its default, or what is kept), 0 asks for none"""
+    return 0 if v is None else SPMV_AMG_NO_SWEEPS if int(v) == 0 else int(v)
+
+
 def _ptr(a):
     """the address of a numpy array for a C call (None stays NULL); the caller keeps the array alive across the call"""
     return C.c_void_p(a.ctypes.data) if a is not None else None
@@ -914,10 +919,8 @@ class DeviceMatrix:
         prolongator T - omegaP D^-1 A T (omegaP None: (4/3) / rho_l per level).  theta or thetaScale given (with
         smoothed=True): spmvHipAmgSetupStrength, which aggregates and smooths on the strength-filtered matrix with the
         threshold theta * thetaScale^l on level l (None: 0.08, 0.5)."""
-        def sweeps(v):
-            return 0 if v is None else SPMV_AMG_NO_SWEEPS if int(v) == 0 else int(v)
-        opts = spmvAmgOpts(int(seed) & 0xFFFFFFFF, int(coarseRows or 0), int(maxLevels or 0), float(omega or 0.0), sweeps(nu1),
-                           sweeps(nu2), sweeps(nuCoarse))
+        opts = spmvAmgOpts(int(seed) & 0xFFFFFFFF, int(coarseRows or 0), int(maxLevels or 0), float(omega or 0.0), _amg_sweeps(nu1),
+                           _amg_sweeps(nu2), _amg_sweeps(nuCoarse))
         h = AmgHierarchy(self)
         strength = theta is not None or thetaScale is not None
         if strength and not smoothed:
@@ -1147,12 +1150,10 @@ class AmgHierarchy(DeviceMatrix):
         and how often: a count None keeps the hierarchy's, 0 asks for none.  eig_ratio (10) and lambda_scale (1.0) are the
         Chebyshev interval: lambda_max = lambda_scale * rho_l, lambda_min = lambda_max / eig_ratio.  A cycle captured
         earlier must be captured again.  `info` is read again (its bytes count the coefficient tables)."""
-        def sweeps(v):
-            return 0 if v is None else SPMV_AMG_NO_SWEEPS if int(v) == 0 else int(v)
         kinds = {"jacobi": SPMV_AMG_SMOOTHER_JACOBI, "chebyshev": SPMV_AMG_SMOOTHER_CHEBYSHEV}
         if isinstance(kind, str) and kind not in kinds:
             raise SpmvHipError(f"set_smoother: kind {kind!r} is neither 'jacobi' nor 'chebyshev'")
-        opts = spmvAmgSmootherOpts(kinds[kind] if isinstance(kind, str) else int(kind), sweeps(nu1), sweeps(nu2), sweeps(nuCoarse),
+        opts = spmvAmgSmootherOpts(kinds[kind] if isinstance(kind, str) else int(kind), _amg_sweeps(nu1), _amg_sweeps(nu2), _amg_sweeps(nuCoarse),
                                    float(eig_ratio or 0.0), float(lambda_scale or 0.0))
         _check(lib.spmvHipAmgSetSmoother(C.byref(self.handle), C.byref(self.source.handle), C.byref(opts)), "spmvHipAmgSetSmoother")
         _check(lib.spmvHipAmgInfo(C.byref(self.handle), C.byref(self.info)), "spmvHipAmgInfo")

@@ -1,42 +1,13 @@
-// amg.hip -- aggregation multigrid on the device: the aggregation of a square CSR handle (spmvHipAggregateCSR), the
-// hierarchy of Galerkin products (spmvHipAmgSetup, spmvHipAmgRefresh) and its damped-Jacobi V-cycle (spmvHipAmgApply, and
-// the dM of the Krylov solvers).  DESIGN.md section 24; the contracts -- the bits of the loops -- are in spmvHip.h.
-//
-// Aggregation.  The roots are the lexicographically first distance-2 maximal independent set under the HASH order of the
-// colouring.  Rounds of two launches over the rows still undecided:
-//   select   an undecided row that no vertex within distance 2, retired ones excepted, beats becomes a ROOT.  A state word
-//            read inside the launch is UNDECIDED or, for a row that became a root in this very launch, ROOT: both count,
-//            and a root of this round within distance 2 beats the row anyway, so the race changes nothing.
-//   retire   an undecided row with a ROOT within distance 2 retires; the others are counted into the round's word.  Roots
-//            do not change in this launch, and a row writes its own word only.
-// The middle vertex of a distance-2 path is never looked at: undecided or retired, the path counts.  No row list is
-// compacted between rounds (a decided row returns at its first load); K rounds are enqueued, then their K counts are read.
-// Then the roots are numbered by a scan, ring 1 takes its root's id, ring 2 the id of its best ring-1 neighbour.
-// Rows with more than 64 adjacency entries take a wavefront each (the lanes share the first hop), the others a lane.
-//
+// amg.hip -- aggregation multigrid on the device: the hierarchy of Galerkin products (the three spmvHipAmgSetup* calls,
+// spmvHipAmgRefresh) and its V-cycle (spmvHipAmgApply, and the dM of the Krylov solvers).  The contracts -- the bits of the
+// loops -- are in spmvHip.h; the aggregation is aggregate.hip.
 // Hierarchy.  Every level's matrix, prolongator, restriction and A P are handles made by the library's own entry points
-// (spmvHipCsrTranspose, spmvHipSpGEMM), so their bits are pinned there.  The cycle's vector kernels are ops of the Krylov
-// files' fused-pass kernel (krylov.hpp: 16-byte accesses when every pointer allows, the same bits otherwise), each with the
-// stop pointer of a Krylov loop.
-//
-// Smoothed aggregation (spmvHipAmgSetupSmoothed).  The same build with P_l = T_l - w_l D_l^-1 A_l T_l
-// chained from the public sum and products: T_l is the unit prolongator above, D_l the diagonal handle of dinv_l, and
-// A_l T_l, D_l (A_l T_l) are kept for the refresh.  w_l comes from amg_rho_kernel (row sums of |a_ij|, an integer max on the
-// bit pattern).  The cycle's correction is then z = z + P_l e: one fused launch (amg_prolong_kernel, a lane walks two rows of
-// P_l) on a level whose P_l has no row above the threshold read at setup, else P_l's serial-order SpMV into d_l and AmgAddOp.
-//
-// Strength filtering (spmvHipAmgSetupStrength).  The smoothed build with F_l = spmvHipCsrFilter(A_l,
-// STRENGTH, theta_l, lump) in two places: the aggregation runs on F_l's pattern, and the prolongator smoother
-// (dF_l = 1 / diag F_l, rho_l, w_l, D_l, F_l T_l) on F_l's values.  The Galerkin product stays R_l (A_l P_l) on the full A_l,
-// and the cycle is the smoothed one, its Jacobi sweeps on dinv_l of A_l.  The refresh runs spmvHipCsrFilterRefresh first:
-// the kept sets are the build's.
-//
-// Chebyshev smoother (spmvHipAmgSetSmoother).  A hierarchy of any of the three setups may smooth with
-// the three-term recurrence on D^-1 A instead of damped Jacobi: per level lambda_max = lambdaScale * rho_l, rho_l from
-// amg_rho_kernel on A_l and dinv_l (the last level too, and A_l -- not F_l -- on a strength hierarchy), the pairs (a_k, b_k)
-// computed on the host (chebTable) and kept in DEVICE memory, where the two passes (AmgChebFirstOp, AmgChebStepOp) read
-// them: a refresh rewrites the table in place and a captured cycle sees the new values.  The recurrence's d is the level's
-// d_l.  A step is one serial-order SpMV and one pass, as a Jacobi sweep is: the launch count is the formula of the sweeps.
+// (transpose, product, sum, filter), so their bits are pinned there.  A level is ONE recipe run in two modes, BUILD and
+// REFRESH (levelFilter, smoothProlongator, galerkin below); what a hierarchy is made of is its AmgKind.
+// Cycle.  Its vector kernels are ops of the Krylov files' fused-pass kernel (krylov.hpp: 16-byte accesses when every pointer
+// allows, the same bits otherwise), each with the stop pointer of a Krylov loop.  A smoothing step is an SpMV into t_l and one
+// pass, damped Jacobi or Chebyshev alike: the launch count is the formula of the sweeps.
+// DESIGN.md sections 24 (the cycle), 28 (smoothed P, the fused correction), 29 (strength), 30 (Chebyshev), 31 (the recipe, the kinds).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <chrono>
@@ -70,11 +41,9 @@ struct AmgLevel {
 struct AmgHierarchy {
     uint32_t seed = 0, nu1 = 1, nu2 = 1, nuCoarse = 8;
     double omega = 2.0 / 3.0;
-    bool smoothed = false;
-    double omegaP = 0.0;                // smoothed: the caller's damping of P, 0: (4/3) / rho_l per level
-    uint32_t fuseMax = 0;               // smoothed: the longest row of P that the fused correction takes (0: never fused)
-    bool strength = false;              // smoothed on the strength-filtered F_l
-    double theta = 0.0, thetaScale = 0.0;   // strength: theta_0, and theta_{l+1} = theta_l * thetaScale
+    AmgPlan plan{};                     // the setup's, defaults filled in
+    bool smoothed() const { return plan.kind != AmgKind::PLAIN; }
+    bool strength() const { return plan.kind == AmgKind::STRENGTH; }    // smoothed on the strength-filtered F_l
     int smoother = SPMV_AMG_SMOOTHER_JACOBI;    // of the cycle (spmvHipAmgSetSmoother)
     double eigRatio = 10.0, lambdaScale = 1.0;  // Chebyshev: lambda_min = lambda_max / eigRatio, lambda_max = lambdaScale * rho_l
     std::vector<AmgLevel> lv;
@@ -84,167 +53,6 @@ struct AmgHierarchy {
 namespace {
 
 constexpr uint32_t AG_THREADS = WG_THREADS;
-constexpr uint32_t AG_WAVES = AG_THREADS / 64;
-constexpr uint32_t AG_LONG = 64;                               // adjacency entries above which a row takes a wavefront
-constexpr uint32_t UNDECIDED = 0xFFFFFFFFu, RETIRED = 0, ROOT = 1, RING1 = 2;
-
-__device__ __forceinline__ uint32_t fmix32(uint32_t h) {      // the murmur3 32-bit finaliser
-    h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-    return h;
-}
-// (key, id) as one word: j beats i iff pri(j) > pri(i)
-__device__ __forceinline__ uint64_t pri(uint32_t i, uint32_t seed) { return (uint64_t)fmix32(i ^ seed) << 32 | i; }
-__device__ __forceinline__ uint32_t stateOf(const uint32_t* state, uint32_t i) { return __atomic_load_n(state + i, __ATOMIC_RELAXED); }
-
-// the pattern of A + A^T as two CSR sides: the stored rows and the incoming ones (null when the pattern is symmetric)
-template <typename I> struct Adj {
-    uint64_t M;
-    const I* IRP; const uint32_t* JA;
-    const uint32_t* tptr; const uint32_t* tcol;
-    // f(j) for every adjacency entry j != i, j < M of row i (repeats included) taken `width` apart from `lane`, until f
-    // returns true; returns whether it did
-    template <typename F> __device__ __forceinline__ bool any(uint32_t i, uint32_t lane, uint32_t width, F&& f) const {
-        for (int side = 0; side < 2; ++side) {
-            if (side && !tptr) break;
-            const uint32_t* col = side ? tcol : JA;
-            const uint64_t b = side ? tptr[i] : (uint64_t)IRP[i], e = side ? tptr[i + 1] : (uint64_t)IRP[i + 1];
-            for (uint64_t p = b + lane; p < e; p += width) {
-                const uint32_t j = col[p];
-                if (j != i && j < M && f(j)) return true;
-            }
-        }
-        return false;
-    }
-};
-
-// every row gets UNDECIDED and joins the short or the long list (one atomic per wavefront and list: the ORDER of a list
-// depends on the run, no output does)
-template <typename I>
-__global__ __launch_bounds__(AG_THREADS) void ag_classify_kernel(Adj<I> g, uint32_t* __restrict__ state, uint32_t* __restrict__ shortList,
-                                                                 uint32_t* __restrict__ longList, uint32_t* __restrict__ cnt) {
-    const uint64_t r = linear_block() * AG_THREADS + threadIdx.x;
-    const bool live = r < g.M;
-    uint64_t deg = 0;
-    if (live) {
-        state[r] = UNDECIDED;
-        deg = (uint64_t)g.IRP[r + 1] - (uint64_t)g.IRP[r] + (g.tptr ? g.tptr[r + 1] - g.tptr[r] : 0u);
-    }
-    const bool isLong = live && deg > AG_LONG, isShort = live && !isLong;
-    const uint32_t lane = threadIdx.x % 64;
-    const uint64_t below = (1ull << lane) - 1;
-    const uint64_t bs = __ballot(isShort), bl = __ballot(isLong);
-    uint32_t baseS = 0, baseL = 0;
-    if (lane == 0) {
-        if (bs) baseS = atomicAdd(&cnt[0], (uint32_t)__popcll(bs));
-        if (bl) baseL = atomicAdd(&cnt[1], (uint32_t)__popcll(bl));
-    }
-    baseS = __shfl(baseS, 0);
-    baseL = __shfl(baseL, 0);
-    if (isShort) shortList[baseS + __popcll(bs & below)] = (uint32_t)r;
-    if (isLong) longList[baseL + __popcll(bl & below)] = (uint32_t)r;
-}
-
-// the row of list place k for this lane: a lane per row, or a wavefront per row (uniform in the wavefront)
-template <bool WAVE_ROW>
-__device__ __forceinline__ bool ag_row(uint32_t n, const uint32_t* __restrict__ list, uint32_t& i, uint32_t& lane) {
-    const uint64_t k = WAVE_ROW ? linear_block() * AG_WAVES + threadIdx.x / 64 : linear_block() * AG_THREADS + threadIdx.x;
-    lane = WAVE_ROW ? threadIdx.x % 64 : 0;
-    if (k >= n) return false;
-    i = list[k];
-    return true;
-}
-
-template <typename I, bool WAVE_ROW>
-__global__ __launch_bounds__(AG_THREADS) void ag_select_kernel(Adj<I> g, uint32_t seed, uint32_t n, const uint32_t* __restrict__ list,
-                                                               uint32_t* state) {
-    uint32_t i = 0, lane = 0;
-    const bool live = ag_row<WAVE_ROW>(n, list, i, lane) && stateOf(state, i) == UNDECIDED;
-    bool blocked = false;
-    if (live) {
-        const uint64_t pi = pri(i, seed);
-        auto beats = [&](uint32_t j) { return j != i && stateOf(state, j) != RETIRED && pri(j, seed) > pi; };
-        blocked = g.any(i, lane, WAVE_ROW ? 64 : 1, [&](uint32_t k) { return beats(k) || g.any(k, 0, 1, beats); });
-    }
-    if (WAVE_ROW) blocked = __ballot(blocked) != 0;
-    if (live && !blocked && lane == 0) __atomic_store_n(state + i, ROOT, __ATOMIC_RELAXED);
-}
-
-template <typename I, bool WAVE_ROW>
-__global__ __launch_bounds__(AG_THREADS) void ag_retire_kernel(Adj<I> g, uint32_t n, const uint32_t* __restrict__ list, uint32_t* state,
-                                                               uint32_t* __restrict__ left) {
-    uint32_t i = 0, lane = 0;
-    const bool live = ag_row<WAVE_ROW>(n, list, i, lane) && stateOf(state, i) == UNDECIDED;
-    bool near = false;
-    if (live) {
-        auto isRoot = [&](uint32_t j) { return stateOf(state, j) == ROOT; };
-        near = g.any(i, lane, WAVE_ROW ? 64 : 1, [&](uint32_t k) { return isRoot(k) || g.any(k, 0, 1, isRoot); });
-    }
-    if (WAVE_ROW) near = __ballot(near) != 0;
-    if (live && near && lane == 0) __atomic_store_n(state + i, RETIRED, __ATOMIC_RELAXED);
-    const uint64_t waits = __ballot(live && !near && lane == 0);
-    if (waits && threadIdx.x % 64 == 0) atomicAdd(left, (uint32_t)__popcll(waits));
-}
-
-__global__ __launch_bounds__(AG_THREADS) void ag_flag_kernel(uint64_t M, const uint32_t* __restrict__ state, uint32_t* __restrict__ flag) {
-    const uint64_t r = linear_block() * AG_THREADS + threadIdx.x;
-    if (r <= M) flag[r] = r < M && state[r] == ROOT;
-}
-
-// roots take their number, ring 1 the number of its root (and the state RING1: a row writes its own word only, and only
-// ROOT is looked for)
-template <typename I, bool WAVE_ROW>
-__global__ __launch_bounds__(AG_THREADS) void ag_ring1_kernel(Adj<I> g, uint32_t n, const uint32_t* __restrict__ list, uint32_t* state,
-                                                              const uint32_t* __restrict__ number, uint32_t* __restrict__ agg) {
-    uint32_t i = 0, lane = 0;
-    if (!ag_row<WAVE_ROW>(n, list, i, lane)) return;
-    if (stateOf(state, i) == ROOT) { if (lane == 0) agg[i] = number[i]; return; }
-    uint32_t root = UNDECIDED;
-    g.any(i, lane, WAVE_ROW ? 64 : 1, [&](uint32_t k) { if (stateOf(state, k) == ROOT) root = k; return root != UNDECIDED; });
-    if (WAVE_ROW)
-        for (int off = 32; off; off >>= 1) root = min(root, (uint32_t)__shfl_xor(root, off));   // (one root at most: min picks it)
-    if (root == UNDECIDED || lane) return;
-    agg[i] = number[root];
-    __atomic_store_n(state + i, RING1, __ATOMIC_RELAXED);
-}
-
-template <typename I, bool WAVE_ROW>
-__global__ __launch_bounds__(AG_THREADS) void ag_ring2_kernel(Adj<I> g, uint32_t seed, uint32_t n, const uint32_t* __restrict__ list,
-                                                              const uint32_t* __restrict__ state, uint32_t* agg) {
-    uint32_t i = 0, lane = 0;
-    if (!ag_row<WAVE_ROW>(n, list, i, lane) || state[i] != RETIRED) return;
-    uint64_t best = 0;
-    bool found = false;
-    g.any(i, lane, WAVE_ROW ? 64 : 1, [&](uint32_t k) {
-        if (state[k] == RING1) {
-            const uint64_t pk = pri(k, seed);
-            if (!found || pk > best) best = pk;
-            found = true;
-        }
-        return false;
-    });
-    if (WAVE_ROW)
-        for (int off = 32; off; off >>= 1) {
-            const uint64_t ob = __shfl_xor(best, off);
-            const bool of = __shfl_xor((int)found, off) != 0;
-            if (of && (!found || ob > best)) best = ob;
-            found = found || of;
-        }
-    if (found && lane == 0) agg[i] = __atomic_load_n(agg + (uint32_t)best, __ATOMIC_RELAXED);   // (a ring-1 word: final before this launch)
-}
-
-// (bad: an id that is no aggregate -- never, by maximality; it must not index the sizes)
-__global__ __launch_bounds__(AG_THREADS) void ag_hist_kernel(uint64_t M, uint32_t nAgg, const uint32_t* __restrict__ agg, uint32_t* __restrict__ size,
-                                                             uint32_t* __restrict__ bad) {
-    const uint64_t r = linear_block() * AG_THREADS + threadIdx.x;
-    if (r >= M) return;
-    const uint32_t a = agg[r];
-    if (a < nAgg) atomicAdd(size + a, 1u);
-    else atomicOr(bad, 1u);
-}
-__global__ __launch_bounds__(AG_THREADS) void ag_minmax_kernel(uint64_t n, const uint32_t* __restrict__ size, uint32_t* __restrict__ mm) {
-    const uint64_t r = linear_block() * AG_THREADS + threadIdx.x;
-    if (r < n) { atomicMin(mm, size[r]); atomicMax(mm + 1, size[r]); }
-}
 
 // P's row pointers and values; dinv from the one stored diagonal entry of every row (*bad = the first row without exactly one)
 __global__ __launch_bounds__(AG_THREADS) void amg_ones_kernel(uint64_t n, double* __restrict__ v) {
@@ -411,10 +219,11 @@ struct AmgAddOp : StopMode {                    // z = z + d
 };
 
 DevMat* matOf(spmat* h) { return static_cast<DevMat*>(h->dev); }
+constexpr uint32_t NO_ROW = 0xFFFFFFFFu;                       // what a kernel's "first bad row" word holds when no row was bad
 
 // dinv of one level; *badRow < 0 when every row has exactly one stored diagonal entry
 int levelDinv(const DevMat* a, double* dinv, long* badRow, hipStream_t st) {
-    uint32_t bad = UNDECIDED;
+    uint32_t bad = NO_ROW;
     *badRow = -1;
     if (!a->M) return EXIT_SUCCESS;
     if (deviceFlag(0xFF, st, "amg_dinv_kernel", &bad, [&](uint32_t* dFlag) {
@@ -423,13 +232,13 @@ int levelDinv(const DevMat* a, double* dinv, long* badRow, hipStream_t st) {
             });
         }))
         return EXIT_FAILURE;
-    if (bad != UNDECIDED) *badRow = (long)bad;
+    if (bad != NO_ROW) *badRow = (long)bad;
     return EXIT_SUCCESS;
 }
 
 // rho of one level (the largest |dinv_i| * sum_p |a_ip|); *badRow >= 0: the first row where that is not finite
 int levelRho(const DevMat* a, const double* dinv, double* rho, long* badRow, hipStream_t st) {
-    struct { unsigned long long bits; uint32_t bad, pad; } h{0, UNDECIDED, 0};
+    struct { unsigned long long bits; uint32_t bad, pad; } h{0, NO_ROW, 0};
     TempBuf buf;
     *badRow = -1;
     if (buf.alloc(sizeof h) != hipSuccess || hipMemcpyAsync(buf.p, &h, sizeof h, hipMemcpyHostToDevice, st) != hipSuccess) return EXIT_FAILURE;
@@ -440,23 +249,32 @@ int levelRho(const DevMat* a, const double* dinv, double* rho, long* badRow, hip
     if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&h, buf.p, sizeof h, hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess)
         return EXIT_FAILURE;
-    if (h.bad != UNDECIDED) *badRow = (long)h.bad;
+    if (h.bad != NO_ROW) *badRow = (long)h.bad;
     memcpy(rho, &h.bits, 8);
     return EXIT_SUCCESS;
 }
 
-// w of a smoothed level: the caller's damping, or (4/3) / rho; refuses (with its line) a row sum that is not finite and rho = 0
-int levelDamping(const AmgHierarchy* H, const DevMat* a, const double* dinv, size_t l, const char* module, double* w, hipStream_t st) {
-    double rho = 0.0;
+// levelRho for `user` ("the Chebyshev smoother"), which needs 0 < rho < Inf: refuses (with its line) a row sum that is not
+// finite and rho = 0.  A level without rows has rho = 0 and is not refused.
+int checkedRho(const DevMat* a, const double* dinv, size_t l, const char* module, const char* user, double* rho, hipStream_t st) {
     long bad = -1;
-    if (levelRho(a, dinv, &rho, &bad, st)) return buildFail(st, module, "the row sums");
-    const bool zero = bad < 0 && !(rho > 0.0);                 // every row sum is 0: row 0 is the first without a rho
+    *rho = 0.0;
+    if (!a->M) return EXIT_SUCCESS;
+    if (levelRho(a, dinv, rho, &bad, st)) return buildFail(st, module, "the row sums");
+    const bool zero = bad < 0 && !(*rho > 0.0);                // every row sum is 0: row 0 is the first without a rho
     if (bad >= 0 || zero) {
-        fprintf(stderr, "libspmvhip: %s: row %ld of level %zu: |dinv| * (the sum of |a_ij|) is %s, the damping of the prolongator needs 0 < rho < Inf\n",
-                module, zero ? 0l : bad, l, zero ? "0, as in every row" : "not finite");
+        fprintf(stderr, "libspmvhip: %s: row %ld of level %zu: |dinv| * (the sum of |a_ij|) is %s, %s needs 0 < rho < Inf\n",
+                module, zero ? 0l : bad, l, zero ? "0, as in every row" : "not finite", user);
         return EXIT_FAILURE;
     }
-    *w = H->omegaP != 0.0 ? H->omegaP : (4.0 / 3.0) / rho;
+    return EXIT_SUCCESS;
+}
+
+// w of a smoothed level (it has rows): the caller's damping, or (4/3) / rho
+int levelDamping(const AmgHierarchy* H, const DevMat* a, const double* dinv, size_t l, const char* module, double* w, hipStream_t st) {
+    double rho = 0.0;
+    if (checkedRho(a, dinv, l, module, "the damping of the prolongator", &rho, st)) return EXIT_FAILURE;
+    *w = H->plan.omegaP != 0.0 ? H->plan.omegaP : (4.0 / 3.0) / rho;
     return EXIT_SUCCESS;
 }
 
@@ -484,21 +302,14 @@ void chebTable(double rho, double eigRatio, double lambdaScale, uint32_t n, Cheb
     }
 }
 
-// rho of level l from A_l's stored rows and dinv_l, and its table of n pairs; refuses (with its line) a row sum that is not
-// finite and rho = 0.  A level without rows has rho = 0 and a table of zeros (no kernel reads it).
+// rho of level l from A_l's stored rows and dinv_l, and its table of n pairs.  A level without rows has a table of zeros
+// (no kernel reads it).
 int levelCheb(const DevMat* a, const AmgLevel& L, size_t l, uint32_t n, double eigRatio, double lambdaScale, const char* module, ChebTable* out,
               hipStream_t st) {
     double rho = 0.0;
-    long bad = -1;
-    if (!a->M) { out->rho = out->lmax = out->lmin = 0.0; out->ab.assign(n, make_double2(0.0, 0.0)); return EXIT_SUCCESS; }
-    if (levelRho(a, L.dinv, &rho, &bad, st)) return buildFail(st, module, "the row sums");
-    const bool zero = bad < 0 && !(rho > 0.0);
-    if (bad >= 0 || zero) {
-        fprintf(stderr, "libspmvhip: %s: row %ld of level %zu: |dinv| * (the sum of |a_ij|) is %s, the Chebyshev smoother needs 0 < rho < Inf\n",
-                module, zero ? 0l : bad, l, zero ? "0, as in every row" : "not finite");
-        return EXIT_FAILURE;
-    }
-    chebTable(rho, eigRatio, lambdaScale, n, out);
+    if (checkedRho(a, L.dinv, l, module, "the Chebyshev smoother", &rho, st)) return EXIT_FAILURE;
+    if (a->M) chebTable(rho, eigRatio, lambdaScale, n, out);
+    else { out->rho = out->lmax = out->lmin = 0.0; out->ab.assign(n, make_double2(0.0, 0.0)); }
     return EXIT_SUCCESS;
 }
 
@@ -527,6 +338,91 @@ size_t handleBytes(const spmat* h) {
     return d ? (size_t)(d->NZ * 12 + (d->M + 1) * 4 + (d->tmap ? d->NZ * 4 : 0)) : 0;
 }
 
+// a sweep count of the options: 0 keeps `kept` (the default, or what the hierarchy has), SPMV_AMG_NO_SWEEPS is none
+uint32_t sweepsOf(unsigned v, uint32_t kept) { return v == 0 ? kept : v == SPMV_AMG_NO_SWEEPS ? 0u : v; }
+
+// an owned CSR handle of M rows with exactly one entry per row: its column from `cols` (M words, which the handle takes
+// over) or, without, the row's own index; its value vals[row] (copied) or, without, 1.0
+int oneEntryRows(spmat* dst, uint64_t M, uint64_t N, TempBuf* cols, const double* vals, hipStream_t st) {
+    TempBuf irp, ja, as;
+    if (irp.alloc((M + 1) * 4) != hipSuccess || (!cols && ja.alloc(M * 4) != hipSuccess) || as.alloc(M * 8) != hipSuccess) return EXIT_FAILURE;
+    enqueueIota(M + 1, irp.as<uint32_t>(), st);
+    if (!cols) enqueueIota(M, ja.as<uint32_t>(), st);
+    if (!vals) hipLaunchKernelGGL(amg_ones_kernel, gridFor(M), dim3(AG_THREADS), 0, st, M, as.as<double>());
+    else if (hipMemcpyAsync(as.p, vals, M * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) return EXIT_FAILURE;
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return EXIT_FAILURE;
+    return ownCsr(dst, M, N, M, irp.detach<uint32_t>(), (cols ? cols : &ja)->detach<uint32_t>(), as.detach<double>());
+}
+
+// ------------------------------------------------------------------------------------------------ the recipe of a level
+// One description of a level, run when the hierarchy is built and when it is refreshed.  Only these
+// wrappers choose between a build and a refresh entry point; a refresh reports nothing, so `info` is the build's alone.
+enum class Mode { BUILD, REFRESH };
+const char* moduleOf(Mode mode) { return mode == Mode::BUILD ? "multigrid setup" : "multigrid refresh"; }
+int product(Mode mode, spmat* out, spmat* a, spmat* b, spmvSpgemmInfo* info) {
+    return mode == Mode::BUILD ? spmvHipSpGEMM(a, b, nullptr, out, info) : spmvHipSpGEMMRefresh(out, a, b, nullptr);
+}
+int sum(Mode mode, spmat* out, double alpha, spmat* a, double beta, spmat* b, spmvAddInfo* info) {
+    return mode == Mode::BUILD ? spmvHipCsrAdd(alpha, a, beta, b, nullptr, out, info) : spmvHipCsrAddRefresh(out, alpha, a, beta, b, nullptr);
+}
+int transposeOf(Mode mode, spmat* out, spmat* in) { return mode == Mode::BUILD ? spmvHipCsrTranspose(in, out) : spmvHipTransposeRefresh(out, in); }
+
+// strength: F_l, the filtered stand-in of the level's matrix, and dF_l = 1 / its diagonal.  A build sets theta_l first and
+// allocates dF_l; a refresh keeps the build's kept sets.
+int levelFilter(Mode mode, AmgHierarchy* H, size_t l, spmat* cur, spmvFilterInfo* info, hipStream_t st) {
+    AmgLevel& L = H->lv[l];
+    const char* module = moduleOf(mode);
+    const bool build = mode == Mode::BUILD;
+    if (build) L.theta = l ? H->lv[l - 1].theta * H->plan.thetaScale : H->plan.theta;
+    const spmvFilterOpts fo{SPMV_FILTER_STRENGTH, 0, 0, L.theta, 1};
+    if (build ? spmvHipCsrFilter(cur, &fo, &L.F, info) : spmvHipCsrFilterRefresh(&L.F, cur, nullptr)) return buildFail(st, module, "a level's strength filter");
+    if (build && hipMalloc(&L.dF, std::max<uint64_t>(L.M, 2) * sizeof(double)) != hipSuccess) return buildFail(st, module, "allocation of a level's vectors");
+    long bad = -1;
+    if (levelDinv(matOf(&L.F), L.dF, &bad, st) || bad >= 0) return buildFail(st, module, "the diagonal of a level's filtered matrix");
+    return EXIT_SUCCESS;
+}
+
+// D_l = diag(sdinv): made by a build, its values rewritten by a refresh
+int diagonalHandle(Mode mode, AmgLevel& L, const double* sdinv, hipStream_t st) {
+    if (mode == Mode::BUILD) return oneEntryRows(&L.D, L.M, L.M, nullptr, sdinv, st);
+    return hipMemcpyAsync(matOf(&L.D)->AS, sdinv, L.M * 8, hipMemcpyDeviceToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess ||
+           spmvHipValuesChanged(&L.D);
+}
+
+struct StepInfo { ulong tempBytes = 0, maxRowP = 0; };         // what a build's steps report to amgBuild
+
+// what stands for A_l in the aggregation and in the smoother of P: F_l (with dF_l for dinv_l) on a strength hierarchy
+spmat* strengthOf(AmgHierarchy* H, size_t l, spmat* cur) { return H->strength() ? &H->lv[l].F : cur; }
+// smoothed: P_l = T_l - w_l D_l (A_l T_l) from the unit prolongator T_l, by the public products and sum; A_l T_l and
+// D_l (A_l T_l) are kept for the refresh.  A build has made F_l before it aggregated; a refresh makes it first of all.
+int smoothProlongator(Mode mode, AmgHierarchy* H, size_t l, spmat* cur, StepInfo* si, hipStream_t st) {
+    AmgLevel& L = H->lv[l];
+    const char* module = moduleOf(mode);
+    if (mode == Mode::REFRESH && H->strength() && levelFilter(mode, H, l, cur, nullptr, st)) return EXIT_FAILURE;
+    spmat* soc = strengthOf(H, l, cur);
+    const double* sdinv = H->strength() ? L.dF : L.dinv;
+    if (levelDamping(H, matOf(soc), sdinv, l, module, &L.w, st)) return EXIT_FAILURE;
+    if (diagonalHandle(mode, L, sdinv, st)) return buildFail(st, module, "the diagonal handle");
+    spmvSpgemmInfo s1{}, s2{}; spmvAddInfo sa{};
+    if (product(mode, &L.AT, soc, &L.T, &s1) || product(mode, &L.DAT, &L.D, &L.AT, &s2) || sum(mode, &L.P, 1.0, &L.T, -L.w, &L.DAT, &sa))
+        return buildFail(st, module, "a level's smoothed prolongator");
+    si->tempBytes = std::max<ulong>(si->tempBytes, std::max({s1.tempBytes, s2.tempBytes, sa.tempBytes}));
+    si->maxRowP = sa.maxRowNnz;
+    return EXIT_SUCCESS;
+}
+
+// R_l = P_l^T, A_l P_l and A_{l+1} = R_l (A_l P_l) into the next level, which exists.  A refresh transposes again only for a
+// smoothed kind: the plain prolongator's values are ones, and its transpose does not change.
+int galerkin(Mode mode, AmgHierarchy* H, size_t l, spmat* cur, StepInfo* si, hipStream_t st) {
+    AmgLevel& L = H->lv[l];
+    spmvSpgemmInfo s1{}, s2{};
+    const bool newR = mode == Mode::BUILD || H->smoothed();
+    if ((newR && transposeOf(mode, &L.R, &L.P)) || product(mode, &L.AP, cur, &L.P, &s1) || product(mode, &H->lv[l + 1].A, &L.R, &L.AP, &s2))
+        return buildFail(st, moduleOf(mode), "a level's products");
+    si->tempBytes = std::max<ulong>(si->tempBytes, std::max(s1.tempBytes, s2.tempBytes));
+    return EXIT_SUCCESS;
+}
+
 }  // namespace
 
 void freeAmg(AmgHierarchy* h) {
@@ -540,111 +436,17 @@ void freeAmg(AmgHierarchy* h) {
     delete h;
 }
 
-int aggregateCsr(const DevMat* a, uint32_t seed, uint32_t K, uint32_t* dAgg, spmvAggInfo* info, hipStream_t st) {
-    const auto t0 = std::chrono::steady_clock::now();
-    const uint64_t M = a->M;
-    spmvAggInfo out{};
-    out.symmetric = 1;
-    auto fail = [&](const char* what) { return buildFail(st, "aggregate", what); };
-    if (M == 0) { if (info) *info = out; return EXIT_SUCCESS; }
-    IncomingPattern in;
-    if (buildIncoming(a, in, st, "aggregate")) return EXIT_FAILURE;
-    out.symmetric = in.symmetric;
-    TempBuf state, lists, cnt, number, scanTmp, size;
-    if (state.alloc(M * 4) || lists.alloc(M * 8) || cnt.alloc((K + 2) * 4) || number.alloc((M + 1) * 8)) return fail("temporary allocation (20 B per row)");
-    uint32_t* const dState = state.as<uint32_t>();
-    uint32_t* const list[2] = {lists.as<uint32_t>(), lists.as<uint32_t>() + M};
-    uint32_t* const dCnt = cnt.as<uint32_t>();                 // [0], [1] the list lengths; [2 .. K + 1] undecided rows after a round
-    uint32_t* const dFlag = number.as<uint32_t>();             // root flags, M + 1 words, then their scan, M + 1 words
-    uint32_t* const dNumber = dFlag + M + 1;
-    std::vector<uint32_t> h(K + 2, 0);
-    if (hipMemsetAsync(dCnt, 0, (K + 2) * 4, st) != hipSuccess) return fail("state");
-    int rc = EXIT_SUCCESS;
-    withIrp(a, [&](auto irp) {
-        using I = IrpT<decltype(irp)>;
-        const Adj<I> g{M, irp, a->JA, in.ptr, in.col};
-        hipLaunchKernelGGL((ag_classify_kernel<I>), gridFor(M), dim3(AG_THREADS), 0, st, g, dState, list[0], list[1], dCnt);
-        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(h.data(), dCnt, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess) { rc = fail("classification"); return; }
-        const uint32_t nS = h[0], nL = h[1];
-        out.longRows = nL;
-        const dim3 gS = gridFor(nS), gL = gridFor(nL, AG_WAVES), blk(AG_THREADS);
-        // the rounds
-        for (bool done = false; !done;) {
-            if (hipMemsetAsync(dCnt + 2, 0, K * 4, st) != hipSuccess) { rc = fail("state"); return; }
-            for (uint32_t t = 0; t < K; ++t) {
-                if (nS) hipLaunchKernelGGL((ag_select_kernel<I, false>), gS, blk, 0, st, g, seed, nS, list[0], dState);
-                if (nL) hipLaunchKernelGGL((ag_select_kernel<I, true>), gL, blk, 0, st, g, seed, nL, list[1], dState);
-                if (nS) hipLaunchKernelGGL((ag_retire_kernel<I, false>), gS, blk, 0, st, g, nS, list[0], dState, dCnt + 2 + t);
-                if (nL) hipLaunchKernelGGL((ag_retire_kernel<I, true>), gL, blk, 0, st, g, nL, list[1], dState, dCnt + 2 + t);
-            }
-            if (hipGetLastError() != hipSuccess || hipMemcpyAsync(h.data() + 2, dCnt + 2, K * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                hipStreamSynchronize(st) != hipSuccess) { rc = fail("rounds"); return; }
-            ++out.hostChecks;
-            uint32_t used = K;
-            for (uint32_t t = 0; t < K; ++t)
-                if (h[2 + t] == 0) { used = t + 1; done = true; break; }
-            out.rounds += used;
-        }
-        // numbering and the rings
-        hipLaunchKernelGGL(ag_flag_kernel, gridFor(M + 1), blk, 0, st, M, dState, dFlag);
-        if (exclusiveScan(scanTmp, dFlag, dNumber, 0u, (size_t)M + 1, st) != hipSuccess) { rc = fail("scan"); return; }
-        if (nS) hipLaunchKernelGGL((ag_ring1_kernel<I, false>), gS, blk, 0, st, g, nS, list[0], dState, dNumber, dAgg);
-        if (nL) hipLaunchKernelGGL((ag_ring1_kernel<I, true>), gL, blk, 0, st, g, nL, list[1], dState, dNumber, dAgg);
-        if (nS) hipLaunchKernelGGL((ag_ring2_kernel<I, false>), gS, blk, 0, st, g, seed, nS, list[0], dState, dAgg);
-        if (nL) hipLaunchKernelGGL((ag_ring2_kernel<I, true>), gL, blk, 0, st, g, seed, nL, list[1], dState, dAgg);
-        uint32_t nAgg = 0;
-        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&nAgg, dNumber + M, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess) { rc = fail("rings"); return; }
-        out.aggregates = nAgg;
-    });
-    if (rc) return rc;
-    // the largest and the smallest aggregate
-    uint32_t mm[3] = {UNDECIDED, 0, 0};                        // smallest, largest, "an id out of range"
-    if (size.alloc((out.aggregates + 3) * 4)) return fail("temporary allocation (aggregate sizes)");
-    uint32_t* const dSize = size.as<uint32_t>();
-    if (hipMemsetAsync(dSize, 0, out.aggregates * 4, st) != hipSuccess ||
-        hipMemcpyAsync(dSize + out.aggregates, mm, 12, hipMemcpyHostToDevice, st) != hipSuccess)
-        return fail("aggregate sizes");
-    hipLaunchKernelGGL(ag_hist_kernel, gridFor(M), dim3(AG_THREADS), 0, st, M, (uint32_t)out.aggregates, dAgg, dSize, dSize + out.aggregates + 2);
-    hipLaunchKernelGGL(ag_minmax_kernel, gridFor(out.aggregates), dim3(AG_THREADS), 0, st, out.aggregates, dSize, dSize + out.aggregates);
-    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(mm, dSize + out.aggregates, 12, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess)
-        return fail("aggregate sizes");
-    if (mm[2]) { fprintf(stderr, "libspmvhip: aggregate: a vertex was left without an aggregate\n"); return EXIT_FAILURE; }
-    out.minAggRows = mm[0]; out.maxAggRows = mm[1];
-    out.ms = msSince(t0);
-    if (info) *info = out;
-    return EXIT_SUCCESS;
-}
-
-// the strength-filtered stand-in of a level's matrix and 1 / its diagonal: the build (L.theta set first) or the refresh
-static int levelFilter(AmgLevel& L, spmat* cur, bool build, const char* module, spmvFilterInfo* fi, hipStream_t st) {
-    const spmvFilterOpts fo{SPMV_FILTER_STRENGTH, 0, 0, L.theta, 1};
-    if (build ? spmvHipCsrFilter(cur, &fo, &L.F, fi) : spmvHipCsrFilterRefresh(&L.F, cur, fi)) return buildFail(st, module, "a level's strength filter");
-    if (build && hipMalloc(&L.dF, std::max<uint64_t>(L.M, 2) * sizeof(double)) != hipSuccess) return buildFail(st, module, "allocation of a level's vectors");
-    long bad = -1;
-    if (levelDinv(matOf(&L.F), L.dF, &bad, st) || bad >= 0) return buildFail(st, module, "the diagonal of a level's filtered matrix");
-    return EXIT_SUCCESS;
-}
-
-int amgBuild(spmat* hA, const spmvAmgOpts* o, const double* omegaP, const spmvAmgStrengthOpts* strength, uint32_t fuseMax, uint32_t K, DevMat* m,
-             hipStream_t st) {
+int amgBuild(spmat* hA, const spmvAmgOpts* o, const AmgPlan& plan, DevMat* m, hipStream_t st) {
     const auto t0 = std::chrono::steady_clock::now();
     AmgHierarchy* H = m->amg = new AmgHierarchy;
-    H->smoothed = omegaP != nullptr;
-    H->omegaP = omegaP ? *omegaP : 0.0;
-    H->fuseMax = fuseMax;
-    H->strength = strength != nullptr;
-    H->theta = strength && strength->theta != 0.0 ? strength->theta : 0.08;
-    H->thetaScale = strength && strength->thetaScale != 0.0 ? strength->thetaScale : 0.5;
-    double theta = H->theta;
+    H->plan = plan;
+    if (H->plan.theta == 0.0) H->plan.theta = 0.08;
+    if (H->plan.thetaScale == 0.0) H->plan.thetaScale = 0.5;
     const uint64_t coarseRows = o && o->coarseRows ? o->coarseRows : 512;
     const uint32_t maxLevels = o && o->maxLevels ? o->maxLevels : SPMV_AMG_MAX_LEVELS;
-    auto sweeps = [](unsigned v, uint32_t dflt) { return v == 0 ? dflt : v == SPMV_AMG_NO_SWEEPS ? 0u : v; };
     H->seed = o ? o->seed : 0u;
     H->omega = o && o->omega != 0.0 ? o->omega : 2.0 / 3.0;
-    H->nu1 = sweeps(o ? o->nu1 : 0, 1); H->nu2 = sweeps(o ? o->nu2 : 0, 1); H->nuCoarse = sweeps(o ? o->nuCoarse : 0, 8);
+    H->nu1 = sweepsOf(o ? o->nu1 : 0, 1); H->nu2 = sweepsOf(o ? o->nu2 : 0, 1); H->nuCoarse = sweepsOf(o ? o->nuCoarse : 0, 8);
     spmvAmgInfo& info = H->info;
     auto fail = [&](const char* what) { return buildFail(st, "multigrid setup", what); };
     auto vec = [&](double** p, uint64_t n) { return hipMalloc(p, std::max<uint64_t>(n, 2) * sizeof(double)) != hipSuccess; };
@@ -667,76 +469,38 @@ int amgBuild(spmat* hA, const spmvAmgOpts* o, const double* omegaP, const spmvAm
         }
         if (warmSpmv(cur, L.d, L.t, st)) return fail("the SpMV selection of a level");
         if (L.M <= coarseRows || l + 1 == maxLevels) break;
-        // strength: F stands for A in the aggregation and in the smoother of P
-        spmat* soc = cur;
-        const double* sdinv = L.dinv;
-        if (H->strength) {
+        if (H->strength()) {                                   // F stands for A in the aggregation and in the smoother of P
             spmvFilterInfo fi{};
-            L.theta = theta;
-            if (levelFilter(L, cur, true, "multigrid setup", &fi, st)) return EXIT_FAILURE;
+            if (levelFilter(Mode::BUILD, H, l, cur, &fi, st)) return EXIT_FAILURE;
             info.tempBytes = std::max<ulong>(info.tempBytes, fi.tempBytes);
-            soc = &L.F;
-            sdinv = L.dF;
         }
-        // aggregates -> P (its column array IS agg), R, A P, R (A P)
-        uint32_t *irp = nullptr, *agg = nullptr;
-        double* ones = nullptr;
+        // aggregates -> the unit prolongator (its column array IS agg): P, or T of a smoothed P
+        TempBuf agg;
         spmvAggInfo ai{};
-        bool ok = hipMalloc(&irp, (L.M + 1) * 4) == hipSuccess && hipMalloc(&agg, L.M * 4) == hipSuccess && hipMalloc(&ones, L.M * 8) == hipSuccess &&
-                  !aggregateCsr(matOf(soc), H->seed, K, agg, &ai, st);
-        const bool alone = ok && ai.aggregates == L.M;         // every vertex its own aggregate: nothing to coarsen
-        if (ok && !alone) {
-            enqueueIota(L.M + 1, irp, st);
-            hipLaunchKernelGGL(amg_ones_kernel, gridFor(L.M), dim3(AG_THREADS), 0, st, L.M, ones);
-            ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
-        }
-        if (!ok || alone) {
-            (void)hipFree(irp); (void)hipFree(agg); (void)hipFree(ones);
-            if (alone && H->strength) {                        // the last level keeps no filtered matrix
-                (void)hipFreeSpmat(&L.F);
-                (void)hipFree(L.dF);
-                L.dF = nullptr;
-            }
-            if (alone) break;
-            return fail("the aggregation");
+        if (agg.alloc(L.M * 4) != hipSuccess || aggregateCsr(matOf(strengthOf(H, l, cur)), H->seed, plan.K, agg.as<uint32_t>(), &ai, st)) return fail("the aggregation");
+        if (ai.aggregates == L.M) {                            // every vertex its own aggregate: nothing to coarsen
+            if (H->strength()) { (void)hipFreeSpmat(&L.F); (void)hipFree(L.dF); L.dF = nullptr; }     // the last level keeps no filtered matrix
+            break;
         }
         L.nAgg = ai.aggregates;
         info.aggregates[l] = L.nAgg;
-        spmat* unitP = H->smoothed ? &L.T : &L.P;
-        if (ownCsr(unitP, L.M, L.nAgg, L.M, irp, agg, ones)) return fail("the prolongator");
+        spmat* unitP = H->smoothed() ? &L.T : &L.P;
+        if (oneEntryRows(unitP, L.M, L.nAgg, &agg, nullptr, st)) return fail("the prolongator");
         L.agg = matOf(unitP)->JA;
-        spmvSpgemmInfo s1{}, s2{};
-        if (H->smoothed) {                                     // P = T - w D (A T), by the public sum and products
-            if (levelDamping(H, matOf(soc), sdinv, l, "multigrid setup", &L.w, st)) return EXIT_FAILURE;
-            uint32_t *dIrp = nullptr, *dJa = nullptr;
-            double* dAs = nullptr;
-            ok = hipMalloc(&dIrp, (L.M + 1) * 4) == hipSuccess && hipMalloc(&dJa, L.M * 4) == hipSuccess && hipMalloc(&dAs, L.M * 8) == hipSuccess;
-            if (ok) {
-                enqueueIota(L.M + 1, dIrp, st);
-                enqueueIota(L.M, dJa, st);
-                ok = hipMemcpyAsync(dAs, sdinv, L.M * 8, hipMemcpyDeviceToDevice, st) == hipSuccess && hipGetLastError() == hipSuccess &&
-                     hipStreamSynchronize(st) == hipSuccess;
-            }
-            if (!ok) { (void)hipFree(dIrp); (void)hipFree(dJa); (void)hipFree(dAs); return fail("the diagonal handle"); }
-            if (ownCsr(&L.D, L.M, L.M, L.M, dIrp, dJa, dAs)) return fail("the diagonal handle");
-            spmvAddInfo sa{};
-            if (spmvHipSpGEMM(soc, &L.T, nullptr, &L.AT, &s1) || spmvHipSpGEMM(&L.D, &L.AT, nullptr, &L.DAT, &s2) ||
-                spmvHipCsrAdd(1.0, &L.T, -L.w, &L.DAT, nullptr, &L.P, &sa))
-                return fail("a level's smoothed prolongator");
-            L.fused = sa.maxRowNnz <= H->fuseMax && matOf(&L.P)->irpBytes == 4;     // (a sum's row pointers are 4-byte)
-            info.tempBytes = std::max<ulong>(info.tempBytes, std::max({s1.tempBytes, s2.tempBytes, sa.tempBytes}));
+        StepInfo si;
+        if (H->smoothed()) {
+            if (smoothProlongator(Mode::BUILD, H, l, cur, &si, st)) return EXIT_FAILURE;
+            L.fused = si.maxRowP <= H->plan.fuseMax && matOf(&L.P)->irpBytes == 4;     // (a sum's row pointers are 4-byte)
             info.bytes += handleBytes(&L.T) + handleBytes(&L.D) + handleBytes(&L.AT) + handleBytes(&L.DAT);
-            if (H->strength) info.bytes += handleBytes(&L.F) + L.M * 8;
-            theta = theta * H->thetaScale;
+            if (H->strength()) info.bytes += handleBytes(&L.F) + L.M * 8;
         }
-        if (spmvHipCsrTranspose(&L.P, &L.R) || spmvHipSpGEMM(cur, &L.P, nullptr, &L.AP, &s1)) return fail("a level's products");
-        H->lv.emplace_back();
-        if (spmvHipSpGEMM(&L.R, &L.AP, nullptr, &H->lv[l + 1].A, &s2)) { H->lv.pop_back(); return fail("a level's products"); }
-        info.tempBytes = std::max<ulong>(info.tempBytes, std::max(s1.tempBytes, s2.tempBytes));
+        H->lv.emplace_back();                                  // (A_{l+1} goes into the next level)
+        if (galerkin(Mode::BUILD, H, l, cur, &si, st)) { H->lv.pop_back(); return EXIT_FAILURE; }
+        info.tempBytes = std::max<ulong>(info.tempBytes, si.tempBytes);
         info.bytes += handleBytes(&L.P) + handleBytes(&L.R) + handleBytes(&L.AP);
         if (vec(&H->lv[l + 1].r, L.nAgg)) return fail("allocation of a level's vectors");
         if (warmSpmv(&L.R, L.d, H->lv[l + 1].r, st)) return fail("the SpMV selection of a restriction");
-        if (H->smoothed && !L.fused && warmSpmv(&L.P, H->lv[l + 1].r, L.d, st)) return fail("the SpMV selection of a prolongator");
+        if (H->smoothed() && !L.fused && warmSpmv(&L.P, H->lv[l + 1].r, L.d, st)) return fail("the SpMV selection of a prolongator");
     }
     double sum = 0;
     for (uint32_t l = 0; l < info.levels; ++l) sum += (double)info.nnz[l];
@@ -749,6 +513,7 @@ int amgRefresh(DevMat* m, spmat* hA, hipStream_t st) {
     const auto t0 = std::chrono::steady_clock::now();
     AmgHierarchy* H = m->amg;
     auto fail = [&](const char* what) { return buildFail(st, "multigrid refresh", what); };
+    StepInfo none;                                             // (a refresh reports nothing)
     for (size_t l = 0; l < H->lv.size(); ++l) {
         AmgLevel& L = H->lv[l];
         spmat* cur = l ? &L.A : hA;
@@ -763,23 +528,8 @@ int amgRefresh(DevMat* m, spmat* hA, hipStream_t st) {
         }
         if (warmSpmv(cur, L.d, L.t, st)) return fail("the SpMV selection of a level");
         if (l + 1 == H->lv.size()) break;
-        if (H->smoothed) {
-            spmat* soc = cur;
-            const double* sdinv = L.dinv;
-            if (H->strength) {
-                if (levelFilter(L, cur, false, "multigrid refresh", nullptr, st)) return EXIT_FAILURE;
-                soc = &L.F;
-                sdinv = L.dF;
-            }
-            if (levelDamping(H, matOf(soc), sdinv, l, "multigrid refresh", &L.w, st)) return EXIT_FAILURE;
-            if (hipMemcpyAsync(matOf(&L.D)->AS, sdinv, L.M * 8, hipMemcpyDeviceToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess ||
-                spmvHipValuesChanged(&L.D))
-                return fail("the diagonal handle");
-            if (spmvHipSpGEMMRefresh(&L.AT, soc, &L.T, nullptr) || spmvHipSpGEMMRefresh(&L.DAT, &L.D, &L.AT, nullptr) ||
-                spmvHipCsrAddRefresh(&L.P, 1.0, &L.T, -L.w, &L.DAT, nullptr) || spmvHipTransposeRefresh(&L.R, &L.P))
-                return fail("a level's smoothed prolongator");
-        }
-        if (spmvHipSpGEMMRefresh(&L.AP, cur, &L.P, nullptr) || spmvHipSpGEMMRefresh(&H->lv[l + 1].A, &L.R, &L.AP, nullptr)) return fail("a level's products");
+        if (H->smoothed() && smoothProlongator(Mode::REFRESH, H, l, cur, &none, st)) return EXIT_FAILURE;
+        if (galerkin(Mode::REFRESH, H, l, cur, &none, st)) return EXIT_FAILURE;
     }
     H->info.ms = msSince(t0);
     return EXIT_SUCCESS;
@@ -798,20 +548,19 @@ int enqueueAmgCycle(const DevMat* m, spmat* hA, const double* r0, double* z0, hi
     };
     auto spmv = [&](spmat* h, const double* x, double* y) { ++n; return spmvHipEnqueueAutoRows(h, const_cast<double*>(x), y, st); };
     auto matAt = [&](size_t l) { return l ? &H->lv[l].A : hA; };
-    auto sweep = [&](size_t l, const double* r, double* z) {
-        AmgLevel& L = H->lv[l];
-        if (spmv(matAt(l), z, L.t)) return EXIT_FAILURE;
-        pass(L.M, AmgSweepOp{{stop}, r, L.t, L.dinv, z, om}, {r, L.t, L.dinv, z});
-        return EXIT_SUCCESS;
-    };
-    // q Chebyshev steps on level l, the recurrence from k = 0 (d is the level's d_l: free at both smoothing sites)
+    // q sweeps of the hierarchy's smoother on level l, from z or from nothing (z = 0, not read): step k takes A z into t unless
+    // it is the first from nothing, then makes its one pass.  (Chebyshev's d is the level's d_l: free at both smoothing sites)
     const bool cheb = H->smoother == SPMV_AMG_SMOOTHER_CHEBYSHEV;
-    auto chebyshev = [&](size_t l, const double* r, double* z, uint32_t q, bool fromNothing) {
+    auto smooth = [&](size_t l, const double* r, double* z, uint32_t q, bool fromNothing) {
         AmgLevel& L = H->lv[l];
+        if (q == 0 && fromNothing) pass(L.M, AmgZeroOp{{stop}, z}, {z});
         for (uint32_t k = 0; k < q; ++k) {
-            if ((k || !fromNothing) && spmv(matAt(l), z, L.t)) return EXIT_FAILURE;
-            if (k) pass(L.M, AmgChebStepOp{{stop}, r, L.t, L.dinv, L.d, z, L.coef + k}, {r, L.t, L.dinv, L.d, z});
-            else if (fromNothing) pass(L.M, AmgChebFirstOp<false>{{stop}, r, nullptr, L.dinv, L.d, z, L.coef}, {r, L.dinv, L.d, z});
+            const bool first = k == 0 && fromNothing;
+            if (!first && spmv(matAt(l), z, L.t)) return EXIT_FAILURE;
+            if (!cheb && first) pass(L.M, AmgFirstOp{{stop}, r, L.dinv, z, om}, {r, L.dinv, z});
+            else if (!cheb) pass(L.M, AmgSweepOp{{stop}, r, L.t, L.dinv, z, om}, {r, L.t, L.dinv, z});
+            else if (k) pass(L.M, AmgChebStepOp{{stop}, r, L.t, L.dinv, L.d, z, L.coef + k}, {r, L.t, L.dinv, L.d, z});
+            else if (first) pass(L.M, AmgChebFirstOp<false>{{stop}, r, nullptr, L.dinv, L.d, z, L.coef}, {r, L.dinv, L.d, z});
             else pass(L.M, AmgChebFirstOp<true>{{stop}, r, L.t, L.dinv, L.d, z, L.coef}, {r, L.t, L.dinv, L.d, z});
         }
         return EXIT_SUCCESS;
@@ -821,14 +570,7 @@ int enqueueAmgCycle(const DevMat* m, spmat* hA, const double* r0, double* z0, hi
         const double* r = l ? L.r : r0;
         double* z = l ? L.z : z0;
         const bool last = l + 1 == nl;
-        const uint32_t sweeps = last ? H->nuCoarse : H->nu1;
-        if (sweeps == 0) pass(L.M, AmgZeroOp{{stop}, z}, {z});
-        else if (cheb) { if (chebyshev(l, r, z, sweeps, true)) return EXIT_FAILURE; }
-        else {
-            pass(L.M, AmgFirstOp{{stop}, r, L.dinv, z, om}, {r, L.dinv, z});
-            for (uint32_t s = 1; s < sweeps; ++s)
-                if (sweep(l, r, z)) return EXIT_FAILURE;
-        }
+        if (smooth(l, r, z, last ? H->nuCoarse : H->nu1, true)) return EXIT_FAILURE;
         if (last) break;
         if (spmv(matAt(l), z, L.t)) return EXIT_FAILURE;
         pass(L.M, AmgResidOp{{stop}, r, L.t, L.d}, {r, L.t, L.d});
@@ -839,7 +581,7 @@ int enqueueAmgCycle(const DevMat* m, spmat* hA, const double* r0, double* z0, hi
         const double* r = l ? L.r : r0;
         double* z = l ? L.z : z0;
         const double* e = H->lv[l + 1].z;
-        if (!H->smoothed) pass(L.M, AmgCorrectOp{{stop}, e, L.agg, z}, {z});
+        if (!H->smoothed()) pass(L.M, AmgCorrectOp{{stop}, e, L.agg, z}, {z});
         else if (L.fused) {
             const DevMat* p = matOf(&L.P);
             const dim3 grid = gridFor((L.M + 1) / 2);
@@ -851,10 +593,7 @@ int enqueueAmgCycle(const DevMat* m, spmat* hA, const double* r0, double* z0, hi
             if (spmv(&L.P, e, L.d)) return EXIT_FAILURE;
             pass(L.M, AmgAddOp{{stop}, L.d, z}, {L.d, z});
         }
-        if (cheb) { if (chebyshev(l, r, z, H->nu2, false)) return EXIT_FAILURE; }
-        else
-            for (uint32_t s = 0; s < H->nu2; ++s)
-                if (sweep(l, r, z)) return EXIT_FAILURE;
+        if (smooth(l, r, z, H->nu2, false)) return EXIT_FAILURE;
     }
     if (launches) *launches += n;
     return hipGetLastError() == hipSuccess ? EXIT_SUCCESS : EXIT_FAILURE;
@@ -863,9 +602,8 @@ int enqueueAmgCycle(const DevMat* m, spmat* hA, const double* r0, double* z0, hi
 int amgSetSmoother(DevMat* m, spmat* hA, const spmvAmgSmootherOpts* o, hipStream_t st) {
     AmgHierarchy* H = m->amg;
     const size_t nl = H->lv.size();
-    auto sweeps = [](unsigned v, uint32_t kept) { return v == 0 ? kept : v == SPMV_AMG_NO_SWEEPS ? 0u : v; };
     const int kind = o ? o->kind : SPMV_AMG_SMOOTHER_JACOBI;
-    const uint32_t nu1 = sweeps(o ? o->nu1 : 0, H->nu1), nu2 = sweeps(o ? o->nu2 : 0, H->nu2), nuCoarse = sweeps(o ? o->nuCoarse : 0, H->nuCoarse);
+    const uint32_t nu1 = sweepsOf(o ? o->nu1 : 0, H->nu1), nu2 = sweepsOf(o ? o->nu2 : 0, H->nu2), nuCoarse = sweepsOf(o ? o->nuCoarse : 0, H->nuCoarse);
     const double eigRatio = o && o->eigRatio != 0.0 ? o->eigRatio : 10.0, lambdaScale = o && o->lambdaScale != 0.0 ? o->lambdaScale : 1.0;
     // everything new is made first: a refusal leaves the hierarchy as it was
     std::vector<ChebTable> tb(nl);
@@ -918,10 +656,10 @@ void amgProlongator(const DevMat* m, unsigned level, spmat* dPl, spmat* dRl, dou
     const AmgLevel& L = m->amg->lv[level];
     if (dPl) { *dPl = L.P; dPl->dev = nullptr; }
     if (dRl) { *dRl = L.R; dRl->dev = nullptr; }
-    if (omegaP) *omegaP = m->amg->smoothed ? L.w : 0.0;
+    if (omegaP) *omegaP = m->amg->smoothed() ? L.w : 0.0;
 }
 
-bool amgIsStrength(const DevMat* m) { return m->amg->strength; }
+bool amgIsStrength(const DevMat* m) { return m->amg->strength(); }
 
 void amgStrength(const DevMat* m, unsigned level, spmat* dFl, double* theta) {
     const AmgLevel& L = m->amg->lv[level];

@@ -227,25 +227,26 @@ int  filterRefresh(DevMat* c, const DevMat* a, hipStream_t stream);
 const spmvFilterInfo* filterInfo(const DevMat* c);
 void filterSetMaxRow(DevMat* c);
 void freeFilterPlan(FilterPlan* p);
-// Aggregation multigrid (amg.hip; contracts in spmvHip.h, design in DESIGN.md section 24).  aggregateCsr: the aggregate ids
-// of the checked square handle into dAgg (M words), K rounds per host check; synchronous, allocates, temporaries freed
-// before it returns.  amgBuild: the hierarchy of the checked handle hA into m->amg, K aggregation rounds per host check (on
-// failure the caller frees m with whatever it holds); omegaP non-null: the smoothed hierarchy of spmvHipAmgSetupSmoothed
-// (*omegaP 0: per level), fuseMax the longest row of a prolongator that its fused correction takes.  amgRefresh: the products,
-// the inverse diagonals and, smoothed, the prolongators again.  amgProlongator: spmvHipAmgProlongator's outputs for a level
-// below the last.  strength non-null (with omegaP): the hierarchy of spmvHipAmgSetupStrength (a field 0: its default);
-// amgIsStrength / amgStrength: whether a hierarchy is one, and spmvHipAmgStrength's outputs for a level below the last.
+// Aggregation multigrid (aggregate.hip, amg.hip; contracts in spmvHip.h, design in DESIGN.md sections 24 and 31).
+// aggregateCsr: the aggregate ids of the checked square handle into dAgg (M words), K rounds per host check; synchronous,
+// allocates, temporaries freed before it returns.  AmgPlan: which of the three setups a hierarchy is, with that setup's
+// checked numbers (0: the default, and what a kind does not use).  amgBuild: the hierarchy of the checked handle hA into
+// m->amg (on failure the caller frees m with whatever it holds).  amgRefresh: every level's recipe again, in place.
 // enqueueAmgCycle: z = V(0, r), kernels only on `stream`; every kernel of the cycle but its SpMVs returns at once when `stop`
-// is set and *stop != 0; *launches grows by the kernels enqueued (an SpMV counted as one).  amgInfo: what the setup or the
-// last refresh did.  amgLevel: spmvHipAmgLevel's outputs for a level below amgInfo()->levels.  ownCsr (upload.hip): a CSR
-// handle that takes ownership of three device arrays.  amgSetSmoother: spmvHipAmgSetSmoother on checked handles and options
-// (the smoother of the cycle and its sweep counts; synchronous, allocates the tables; a failure leaves the hierarchy as it
-// was).  amgSmoother: spmvHipAmgSmoother's output for a level below amgInfo()->levels.
+// is set and *stop != 0; *launches grows by the kernels enqueued (an SpMV counted as one).  amgSetSmoother: the cycle's
+// smoother and sweep counts from checked options (synchronous, allocates the tables; a failure leaves the hierarchy as it
+// was).  amgInfo: what the setup or the last refresh did.  The views: amgLevel / amgSmoother of a level below amgInfo()->levels,
+// amgProlongator / amgStrength of one below the last.  ownCsr (upload.hip): a CSR handle that owns three device arrays.
+enum class AmgKind { PLAIN, SMOOTHED, STRENGTH };              // unit prolongator; P = T - w D^-1 A T; that on the filtered A
+struct AmgPlan {
+    AmgKind kind = AmgKind::PLAIN;
+    double omegaP = 0.0, theta = 0.0, thetaScale = 0.0;     // the damping of P (0: (4/3) / rho_l); theta_0 and theta_{l+1} / theta_l
+    uint32_t fuseMax = 0, K = 16;       // the longest row of P that the fused correction takes (0: never); aggregation rounds per host check
+};
 int  amgSetSmoother(DevMat* m, spmat* hA, const spmvAmgSmootherOpts* opts, hipStream_t stream);
 void amgSmoother(const DevMat* m, unsigned level, spmvAmgSmootherInfo* info);
 int  aggregateCsr(const DevMat* a, uint32_t seed, uint32_t K, uint32_t* dAgg, spmvAggInfo* info, hipStream_t stream);
-int  amgBuild(spmat* hA, const spmvAmgOpts* opts, const double* omegaP, const spmvAmgStrengthOpts* strength, uint32_t fuseMax, uint32_t K,
-              DevMat* m, hipStream_t stream);
+int  amgBuild(spmat* hA, const spmvAmgOpts* opts, const AmgPlan& plan, DevMat* m, hipStream_t stream);
 int  amgRefresh(DevMat* m, spmat* hA, hipStream_t stream);
 int  enqueueAmgCycle(const DevMat* m, spmat* hA, const double* r, double* z, hipStream_t stream, const uint32_t* stop,
                      unsigned long* launches);

@@ -54,6 +54,8 @@ struct TempBuf {
         return e;
     }
     template <typename T> T* as() const { return static_cast<T*>(p); }
+    // the memory is the caller's from here on (a handle takes it)
+    template <typename T> T* detach() { T* q = as<T>(); if (tally) tally->cur -= n; p = nullptr; n = 0; return q; }
 };
 
 // call(nullptr, bytes) asks a rocPRIM algorithm for its workspace size, call(ws.p, bytes) runs it on `stream`.  ws grows

@@ -1,6 +1,6 @@
 // solve.hip -- the solver side of the extern "C" boundary: triangular solves, ILU(0), the multi-colour ordering and the
 // vector permutation, the dots, aggregation multigrid, and the three Krylov solvers.  The algorithm files (trsv.hip,
-// ilu0.hip, colour.hip, krylov.hip, gmres.hip, amg.hip) build and launch; here are the checks, the library's settings
+// ilu0.hip, colour.hip, krylov.hip, gmres.hip, aggregate.hip, amg.hip) build and launch; here are the checks, the library's settings
 // handed down as arguments, and the timing bracket.  Contracts in spmvHip.h, designs in DESIGN.md sections 17 to 21 and 24.
 #include <hip/hip_runtime.h>
 #include <chrono>
@@ -26,6 +26,19 @@ static DevMat* hierarchyOf(spmat* dM, spmat* dA, const char* who, DevMat** pa) {
     DevMat* a = m ? csrOf(dA, who, "dA is an ELL handle") : nullptr;
     if (!a || !madeBy(m, Origin::HIERARCHY, a, nullptr, who, "dM", "dA")) return nullptr;
     *pa = a;
+    return m;
+}
+
+// dM as a hierarchy, for a view of its level `level`: one below the last when lastLacks says what the last level has not.
+// noInfo: the entry's info, which it cannot do without, is NULL (refused after the handle, before the hierarchy, as ever).
+static DevMat* hierarchyLevel(spmat* dM, const char* who, unsigned level, const char* lastLacks, bool noInfo = false) {
+    DevMat* m = anyDescOf(dM, who);
+    if (!m) return nullptr;
+    if (noInfo) { ERR("%s: info is NULL", who); return nullptr; }
+    if (!madeBy(m, Origin::HIERARCHY, nullptr, nullptr, who, "dM")) return nullptr;
+    const size_t levels = amgInfo(m)->levels;              // (a hierarchy has at least one level)
+    if (lastLacks && level >= levels - 1) { ERR("%s: level %u of %zu: the last level has no %s", who, level, levels, lastLacks); return nullptr; }
+    if (level >= levels) { ERR("%s: level %u of %zu", who, level, levels); return nullptr; }
     return m;
 }
 
@@ -232,10 +245,9 @@ int spmvHipAggregateCSR(spmat* dA, const spmvAggOpts* opts, uint32_t* dAgg, spmv
     return EXIT_SUCCESS;
 }
 
-// the three setups: omegaP null for the plain hierarchy, else the damping of the smoothed prolongator (0: per level);
-// strength non-null for the strength-filtered one (a field 0: its default)
-static int amgSetup(const char* who, spmat* dA, const spmvAmgOpts* opts, const double* omegaP, const spmvAmgStrengthOpts* strength, spmat* dM,
-                    spmvAmgInfo* info) {
+// the three setups: the plan holds the kind and the caller's numbers of that kind (what a kind does not use is 0, which
+// passes every check here); the library's settings are filled in here
+static int amgSetup(const char* who, spmat* dA, const spmvAmgOpts* opts, AmgPlan plan, spmat* dM, spmvAmgInfo* info) {
     if (!ready(who)) return EXIT_FAILURE;
     if (!dA || !dM) { ERR("%s: %s is NULL", who, !dA ? "dA" : "dM"); return EXIT_FAILURE; }
     if (dM == dA) { ERR("%s: dM is the source handle itself", who); return EXIT_FAILURE; }
@@ -244,33 +256,34 @@ static int amgSetup(const char* who, spmat* dA, const spmvAmgOpts* opts, const d
     if (a->NZ && (!a->JA || !a->AS)) { ERR("%s: the source has no column or value array", who); return EXIT_FAILURE; }
     if (opts && opts->maxLevels > SPMV_AMG_MAX_LEVELS) { ERR("%s: maxLevels %u is above %d", who, opts->maxLevels, SPMV_AMG_MAX_LEVELS); return EXIT_FAILURE; }
     if (opts && !(opts->omega >= 0.0 && std::isfinite(opts->omega))) { ERR("%s: omega %g is negative or not finite", who, opts->omega); return EXIT_FAILURE; }
-    if (omegaP && !(*omegaP >= 0.0 && std::isfinite(*omegaP))) { ERR("%s: omegaP %g is negative or not finite", who, *omegaP); return EXIT_FAILURE; }
-    if (strength && !(strength->theta >= 0.0 && std::isfinite(strength->theta))) { ERR("%s: theta %g is negative or not finite", who, strength->theta); return EXIT_FAILURE; }
-    if (strength && !(strength->thetaScale >= 0.0 && strength->thetaScale <= 1.0)) {
-        ERR("%s: thetaScale %g is negative, above 1 or not finite", who, strength->thetaScale);
+    if (!(plan.omegaP >= 0.0 && std::isfinite(plan.omegaP))) { ERR("%s: omegaP %g is negative or not finite", who, plan.omegaP); return EXIT_FAILURE; }
+    if (!(plan.theta >= 0.0 && std::isfinite(plan.theta))) { ERR("%s: theta %g is negative or not finite", who, plan.theta); return EXIT_FAILURE; }
+    if (!(plan.thetaScale >= 0.0 && plan.thetaScale <= 1.0)) {
+        ERR("%s: thetaScale %g is negative, above 1 or not finite", who, plan.thetaScale);
         return EXIT_FAILURE;
     }
+    plan.fuseMax = S.amgFuseMax;
+    plan.K = S.aggK;
     DevMat* m = new DevMat;
     m->M = m->N = a->M;
     setOrigin(m, Origin::HIERARCHY, a);
-    if (amgBuild(dA, opts, omegaP, strength, S.amgFuseMax, S.aggK, m, S.stream)) { ERR("%s: building the hierarchy failed", who); freeDesc(m); return EXIT_FAILURE; }
+    if (amgBuild(dA, opts, plan, m, S.stream)) { ERR("%s: building the hierarchy failed", who); freeDesc(m); return EXIT_FAILURE; }
     publish(dM, m, m->M, m->N, 0, 0);
     if (info) *info = *amgInfo(m);
     return EXIT_SUCCESS;
 }
 
 int spmvHipAmgSetup(spmat* dA, const spmvAmgOpts* opts, spmat* dM, spmvAmgInfo* info) {
-    return amgSetup("spmvHipAmgSetup", dA, opts, nullptr, nullptr, dM, info);
+    return amgSetup("spmvHipAmgSetup", dA, opts, AmgPlan{}, dM, info);
 }
 int spmvHipAmgSetupSmoothed(spmat* dA, const spmvAmgOpts* opts, const spmvAmgSmoothOpts* smooth, spmat* dM, spmvAmgInfo* info) {
-    const double omegaP = smooth ? smooth->omegaP : 0.0;
-    return amgSetup("spmvHipAmgSetupSmoothed", dA, opts, &omegaP, nullptr, dM, info);
+    return amgSetup("spmvHipAmgSetupSmoothed", dA, opts, AmgPlan{AmgKind::SMOOTHED, smooth ? smooth->omegaP : 0.0}, dM, info);
 }
 int spmvHipAmgSetupStrength(spmat* dA, const spmvAmgOpts* opts, const spmvAmgSmoothOpts* smooth, const spmvAmgStrengthOpts* strength, spmat* dM,
                             spmvAmgInfo* info) {
-    const double omegaP = smooth ? smooth->omegaP : 0.0;
-    const spmvAmgStrengthOpts so = strength ? *strength : spmvAmgStrengthOpts{0.0, 0.0};
-    return amgSetup("spmvHipAmgSetupStrength", dA, opts, &omegaP, &so, dM, info);
+    AmgPlan plan{AmgKind::STRENGTH, smooth ? smooth->omegaP : 0.0};
+    if (strength) { plan.theta = strength->theta; plan.thetaScale = strength->thetaScale; }
+    return amgSetup("spmvHipAmgSetupStrength", dA, opts, plan, dM, info);
 }
 
 int spmvHipAmgRefresh(spmat* dM, spmat* dA) {
@@ -298,48 +311,31 @@ int spmvHipAmgApply(spmat* dM, spmat* dA, const double* dR, double* dZ) {
 }
 
 int spmvHipAmgInfo(spmat* dM, spmvAmgInfo* info) {
-    const char* who = "spmvHipAmgInfo";
-    DevMat* m = anyDescOf(dM, who);
+    DevMat* m = hierarchyLevel(dM, "spmvHipAmgInfo", 0, nullptr, !info);
     if (!m) return EXIT_FAILURE;
-    if (!info) { ERR("%s: info is NULL", who); return EXIT_FAILURE; }
-    if (!madeBy(m, Origin::HIERARCHY, nullptr, nullptr, who, "dM")) return EXIT_FAILURE;
     *info = *amgInfo(m);
     return EXIT_SUCCESS;
 }
 
 int spmvHipAmgLevel(spmat* dM, unsigned level, spmat* dAl, const uint32_t** dAgg, const double** dDinv) {
-    const char* who = "spmvHipAmgLevel";
-    DevMat* m = anyDescOf(dM, who);
+    DevMat* m = hierarchyLevel(dM, "spmvHipAmgLevel", level, nullptr);
     if (!m) return EXIT_FAILURE;
-    if (!madeBy(m, Origin::HIERARCHY, nullptr, nullptr, who, "dM")) return EXIT_FAILURE;
-    if (level >= amgInfo(m)->levels) { ERR("%s: level %u of %zu", who, level, (size_t)amgInfo(m)->levels); return EXIT_FAILURE; }
     amgLevel(m, level, dAl, dAgg, dDinv);
     return EXIT_SUCCESS;
 }
 
 int spmvHipAmgProlongator(spmat* dM, unsigned level, spmat* dPl, spmat* dRl, double* omegaP) {
-    const char* who = "spmvHipAmgProlongator";
-    DevMat* m = anyDescOf(dM, who);
+    DevMat* m = hierarchyLevel(dM, "spmvHipAmgProlongator", level, "prolongator");
     if (!m) return EXIT_FAILURE;
-    if (!madeBy(m, Origin::HIERARCHY, nullptr, nullptr, who, "dM")) return EXIT_FAILURE;
-    if (level >= amgInfo(m)->levels - 1) {                 // (a hierarchy has at least one level)
-        ERR("%s: level %u of %zu: the last level has no prolongator", who, level, (size_t)amgInfo(m)->levels);
-        return EXIT_FAILURE;
-    }
     amgProlongator(m, level, dPl, dRl, omegaP);
     return EXIT_SUCCESS;
 }
 
 int spmvHipAmgStrength(spmat* dM, unsigned level, spmat* dFl, double* theta) {
     const char* who = "spmvHipAmgStrength";
-    DevMat* m = anyDescOf(dM, who);
+    DevMat* m = hierarchyLevel(dM, who, level, "filtered matrix");
     if (!m) return EXIT_FAILURE;
-    if (!madeBy(m, Origin::HIERARCHY, nullptr, nullptr, who, "dM")) return EXIT_FAILURE;
     if (!amgIsStrength(m)) { ERR("%s: dM was not made by spmvHipAmgSetupStrength", who); return EXIT_FAILURE; }
-    if (level >= amgInfo(m)->levels - 1) {
-        ERR("%s: level %u of %zu: the last level has no filtered matrix", who, level, (size_t)amgInfo(m)->levels);
-        return EXIT_FAILURE;
-    }
     amgStrength(m, level, dFl, theta);
     return EXIT_SUCCESS;
 }
@@ -364,12 +360,8 @@ int spmvHipAmgSetSmoother(spmat* dM, spmat* dA, const spmvAmgSmootherOpts* opts)
 }
 
 int spmvHipAmgSmoother(spmat* dM, unsigned level, spmvAmgSmootherInfo* info) {
-    const char* who = "spmvHipAmgSmoother";
-    DevMat* m = anyDescOf(dM, who);
+    DevMat* m = hierarchyLevel(dM, "spmvHipAmgSmoother", level, nullptr, !info);
     if (!m) return EXIT_FAILURE;
-    if (!info) { ERR("%s: info is NULL", who); return EXIT_FAILURE; }
-    if (!madeBy(m, Origin::HIERARCHY, nullptr, nullptr, who, "dM")) return EXIT_FAILURE;
-    if (level >= amgInfo(m)->levels) { ERR("%s: level %u of %zu", who, level, (size_t)amgInfo(m)->levels); return EXIT_FAILURE; }
     amgSmoother(m, level, info);
     return EXIT_SUCCESS;
 }

@@ -9,6 +9,7 @@ import pytest
 
 import amg_ref as ar
 import spgemm_ref as sr
+from amg_gpu import _down, _same, _solve_and_compare, _special_r, _up, cycle_launches
 from bits import assert_same_bits
 from gmres_ref import gmres_ref
 from ilu0_ref import ilu0_levels
@@ -50,25 +51,8 @@ def krylov(api):
     da.free()
 
 
-def _down(api, ptr, n, dtype):
-    out = np.empty(n, dtype=dtype)
-    if n:
-        assert api.lib.spmvHipMemcpyDown(out.ctypes.data_as(C.c_void_p), C.cast(ptr, C.c_void_p), out.nbytes) == 0
-    return out
-
-
-def _up(api, A):
-    return api.spMatCpyCSR(api.HostCSR(*A))
-
-
 def _with_values(M, IRP, JA):
     return M, M, IRP, JA, np.ones(JA.size)
-
-
-def _same(got, want, what):
-    nan = np.isnan(want)
-    assert np.array_equal(np.isnan(got), nan), f"{what}: NaN places"
-    assert_same_bits(np.where(nan, 0.0, got), np.where(nan, 0.0, want), what)
 
 
 def test_device_memory_comes_back(api):
@@ -217,14 +201,6 @@ SWEEPS = [(0, 0, 1), (1, 1, 1), (2, 1, 3), (0, 2, 1)]
 DEPTHS = {1: dict(maxLevels=1), 2: dict(coarseRows=8, maxLevels=2), 3: dict(coarseRows=8, maxLevels=3)}
 
 
-def _special_r(M):
-    r = np.random.default_rng(7).standard_normal(M)
-    r[[3, 100, 511]] = 0.0
-    r[[4, 101]] = -0.0
-    r[200], r[201], r[300] = np.inf, -np.inf, np.nan
-    return r
-
-
 @pytest.mark.parametrize("depth", list(DEPTHS))
 @pytest.mark.parametrize("nu", SWEEPS)
 def test_cycle_bits(api, nu, depth):
@@ -296,29 +272,10 @@ def test_misaligned_vectors_and_a_captured_replay(api):
 
 
 # -------------------------------------------------------------------------------------------------------------- Krylov
-def _solve_and_compare(api, krylov, method, want, **kw):
-    A, b, ref, da, h = krylov
-    x, info = getattr(da, method)(b, precond=h, tol=KRYLOV_TOL, maxiter=200, history=True, **kw)
-    wx, wstatus, wit, whist, _ = want
-    assert (info.status, info.iterations) == (wstatus, wit), method
-    assert_same_bits(x, wx, f"{method}: x")
-    assert_same_bits(info.history, whist, f"{method}: history")
-    return info
-
-
-def cycle_launches(nu1, nu2, nuCoarse, levels):
-    """the kernels one cycle enqueues, an SpMV counted as one (include/spmvHip.h): n sweeps from nothing are one pass and
-    two kernels per further sweep; above the last level come the residual's SpMV and pass, the restriction, the gather
-    and two kernels per post-sweep"""
-    def start(n):
-        return 1 + 2 * (max(n, 1) - 1)
-    return (levels - 1) * (start(nu1) + 3 + 1 + 2 * nu2) + start(nuCoarse)
-
-
 def test_cg_with_the_hierarchy(api, krylov):
     A, b, ref, da, h = krylov
     want = cg_ref(ref, b, np.zeros(A[0]), KRYLOV_TOL, 200)
-    info = _solve_and_compare(api, krylov, "cg", want)
+    info = _solve_and_compare(da, b, h, "cg", want, KRYLOV_TOL)
     plain = cg_ref(Csr(A[0], A[2], A[3], A[4]), b, np.zeros(A[0]), KRYLOV_TOL, 200)
     assert info.iterations == want[2] < plain[2]
     # CG's own kernels: 4 before the loop and 6 per enqueued iteration (whole batches of K = 16), as a solve without dM
@@ -333,12 +290,12 @@ def test_cg_with_the_hierarchy(api, krylov):
 
 def test_bicgstab_with_the_hierarchy(api, krylov):
     A, b, ref, da, h = krylov
-    _solve_and_compare(api, krylov, "bicgstab", bicgstab_ref(ref, b, np.zeros(A[0]), KRYLOV_TOL, 200))
+    _solve_and_compare(da, b, h, "bicgstab", bicgstab_ref(ref, b, np.zeros(A[0]), KRYLOV_TOL, 200), KRYLOV_TOL)
 
 
 def test_gmres_with_the_hierarchy(api, krylov):
     A, b, ref, da, h = krylov
-    _solve_and_compare(api, krylov, "gmres", gmres_ref(ref, b, np.zeros(A[0]), KRYLOV_TOL, 200, 5), restart=5)
+    _solve_and_compare(da, b, h, "gmres", gmres_ref(ref, b, np.zeros(A[0]), KRYLOV_TOL, 200, 5), KRYLOV_TOL, restart=5)
 
 
 def test_cycles_queued_past_the_stop_change_nothing(api, krylov):

@@ -15,6 +15,7 @@ import amg_ref as ar
 import amg_sa_ref as sa
 import filter_ref as fr
 import spgemm_ref as sr
+from amg_gpu import _same, _solve_and_compare, _up, cycle_launches
 from bits import assert_same_bits
 from gmres_ref import gmres_ref
 from krylov_ref import bicgstab_ref, cg_ref
@@ -46,16 +47,6 @@ def _defaults(api):
     api.lib.spmvHipSetSync(1)
     api.set_variant("spmvHipAmgApply", NEVER)
     api.set_variant("hipSpCGCSR", 16)
-
-
-def _up(api, A):
-    return api.spMatCpyCSR(api.HostCSR(*A))
-
-
-def _same(got, want, what):
-    nan = np.isnan(want)
-    assert np.array_equal(np.isnan(got), nan), f"{what}: NaN places"
-    assert_same_bits(np.where(nan, 0.0, got), np.where(nan, 0.0, want), what)
 
 
 def _bits(x):
@@ -265,30 +256,13 @@ def krylov(api):
     da.free()
 
 
-def _solve_and_compare(krylov, method, want, precond, **kw):
-    A, b, da = krylov[:3]
-    x, info = getattr(da, method)(b, precond=precond, tol=KRYLOV_TOL, maxiter=200, history=True, **kw)
-    wx, wstatus, wit, whist, _ = want
-    assert (info.status, info.iterations) == (wstatus, wit), method
-    assert_same_bits(x, wx, f"{method}: x")
-    assert_same_bits(info.history, whist, f"{method}: history")
-    return info
-
-
-def cycle_launches(nu1, nu2, nuCoarse, levels, unfused):
-    """the kernels one cycle enqueues (include/spmvHip.h), whatever the smoother"""
-    def start(n):
-        return 1 + 2 * (max(n, 1) - 1)
-    return (levels - 1) * (start(nu1) + 3 + 1 + 2 * nu2) + start(nuCoarse) + unfused
-
-
 @pytest.mark.parametrize("hierarchy", ["plain", "smoothed"])
 def test_cg_takes_the_reference_count_and_a_cycle_the_launches_of_jacobi(api, krylov, hierarchy):
     A, b, da, hs = krylov
     ref, h = hs[hierarchy]
     want = cg_ref(ref, b, np.zeros(A[0]), KRYLOV_TOL, 200)
     assert want[2] == COUNTS[((12, 10, 8), hierarchy, NU)][2]
-    info = _solve_and_compare(krylov, "cg", want, h)
+    info = _solve_and_compare(da, b, h, "cg", want, KRYLOV_TOL)
     assert info.iterations == want[2]
     # CG's own kernels: 4 before the loop and 6 per enqueued iteration (whole batches of K = 16); every M^-1 (one before the
     # loop, one per iteration) adds the cycle, a dot pass and its finish
@@ -300,7 +274,7 @@ def test_cg_takes_the_reference_count_and_a_cycle_the_launches_of_jacobi(api, kr
     try:
         jac = cg_ref(cr.ChebCsr(A, levels=ref.levels, o=ref.o, sm=dict(kind=cr.JACOBI, nu1=NU, nu2=NU)), b, np.zeros(A[0]), KRYLOV_TOL, 200)
         assert jac[2] == COUNTS[((12, 10, 8), hierarchy, NU)][0]
-        info = _solve_and_compare(krylov, "cg", jac, h)
+        info = _solve_and_compare(da, b, h, "cg", jac, KRYLOV_TOL)
         assert info.launches == 4 + 6 * enq(jac[2]) + (enq(jac[2]) + 1) * (cycle + 2), "Jacobi's cycle is as many kernels"
     finally:
         h.set_smoother(nu1=NU, nu2=NU)
@@ -310,8 +284,8 @@ def test_cg_takes_the_reference_count_and_a_cycle_the_launches_of_jacobi(api, kr
 def test_bicgstab_and_gmres(api, krylov, hierarchy):
     A, b, da, hs = krylov
     ref, h = hs[hierarchy]
-    _solve_and_compare(krylov, "bicgstab", bicgstab_ref(ref, b, np.zeros(A[0]), KRYLOV_TOL, 200), h)
-    _solve_and_compare(krylov, "gmres", gmres_ref(ref, b, np.zeros(A[0]), KRYLOV_TOL, 200, 5), h, restart=5)
+    _solve_and_compare(da, b, h, "bicgstab", bicgstab_ref(ref, b, np.zeros(A[0]), KRYLOV_TOL, 200), KRYLOV_TOL)
+    _solve_and_compare(da, b, h, "gmres", gmres_ref(ref, b, np.zeros(A[0]), KRYLOV_TOL, 200, 5), KRYLOV_TOL, restart=5)
 
 
 def test_cycles_queued_past_the_stop_write_nothing(api, krylov):

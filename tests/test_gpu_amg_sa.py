@@ -12,6 +12,7 @@ import pytest
 import amg_ref as ar
 import amg_sa_ref as sa
 import spgemm_ref as sr
+from amg_gpu import _bits, _blob, _down, _same, _solve_and_compare, _special_r, _up, cycle_launches
 from bits import assert_same_bits
 from gmres_ref import gmres_ref
 from krylov_ref import Csr, bicgstab_ref, cg_ref
@@ -43,34 +44,6 @@ def _defaults(api):
     api.lib.spmvHipSetSync(1)
     api.set_variant("spmvHipAmgApply", DEFAULT)
     api.set_variant("hipSpCGCSR", 16)
-
-
-def _up(api, A):
-    return api.spMatCpyCSR(api.HostCSR(*A))
-
-
-def _down(api, ptr, n, dtype):
-    out = np.empty(n, dtype=dtype)
-    if n:
-        assert api.lib.spmvHipMemcpyDown(out.ctypes.data_as(C.c_void_p), C.cast(ptr, C.c_void_p), out.nbytes) == 0
-    return out
-
-
-def _same(got, want, what):
-    nan = np.isnan(want)
-    assert np.array_equal(np.isnan(got), nan), f"{what}: NaN places"
-    assert_same_bits(np.where(nan, 0.0, got), np.where(nan, 0.0, want), what)
-
-
-def _bits(x):
-    return np.float64(x).view(np.uint64)
-
-
-def _blob(v):
-    """the bytes of a downloaded piece: an array, a number, None, or a tuple of them"""
-    if isinstance(v, tuple):
-        return b"|".join(_blob(t) for t in v)
-    return b"" if v is None else np.asarray(v).tobytes()
 
 
 def _unfused(levels, threshold):
@@ -207,14 +180,6 @@ def _lap_levels(depth):
     return levels
 
 
-def _special_r(M):
-    r = np.random.default_rng(7).standard_normal(M)
-    r[[3, 100, 511]] = 0.0
-    r[[4, 101]] = -0.0
-    r[200], r[201], r[300] = np.inf, -np.inf, np.nan
-    return r
-
-
 def test_the_thresholds_split_the_levels_as_named():
     levels = _lap_levels(3)
     assert [_unfused(levels, t) for t in THRESHOLDS] == [0, 1, 2, 2]
@@ -316,24 +281,6 @@ def krylov(api):
     da.free()
 
 
-def _solve_and_compare(krylov, method, want, precond, **kw):
-    A, b, ref, da = krylov[:4]
-    x, info = getattr(da, method)(b, precond=precond, tol=KRYLOV_TOL, maxiter=200, history=True, **kw)
-    wx, wstatus, wit, whist, _ = want
-    assert (info.status, info.iterations) == (wstatus, wit), method
-    assert_same_bits(x, wx, f"{method}: x")
-    assert_same_bits(info.history, whist, f"{method}: history")
-    return info
-
-
-def cycle_launches(nu1, nu2, nuCoarse, levels, unfused):
-    """the kernels one smoothed cycle enqueues (include/spmvHip.h): the plain cycle's, and one more on every level whose
-    correction is an SpMV and an add"""
-    def start(n):
-        return 1 + 2 * (max(n, 1) - 1)
-    return (levels - 1) * (start(nu1) + 3 + 1 + 2 * nu2) + start(nuCoarse) + unfused
-
-
 def test_cg_with_the_smoothed_hierarchy_and_the_launches_of_a_cycle(api, krylov):
     A, b, ref, da, h, h0 = krylov
     want = cg_ref(ref, b, np.zeros(A[0]), KRYLOV_TOL, 200)
@@ -341,7 +288,7 @@ def test_cg_with_the_smoothed_hierarchy_and_the_launches_of_a_cycle(api, krylov)
     assert h.info.levels == h0.info.levels == len(ref.levels) >= 3 and set(KRYLOV_OPTS) == {"coarseRows"}
     enq = lambda it: min(200, -(-it // 16) * 16)
     for hier, unfused in ((h, 0), (h0, len(ref.levels) - 1)):
-        info = _solve_and_compare(krylov, "cg", want, hier)
+        info = _solve_and_compare(da, b, hier, "cg", want, KRYLOV_TOL)
         assert info.iterations == want[2]
         # CG's own kernels: 4 before the loop and 6 per enqueued iteration (whole batches of K = 16); every M^-1 (one before
         # the loop, one per iteration) adds the cycle, a dot pass and its finish
@@ -351,13 +298,13 @@ def test_cg_with_the_smoothed_hierarchy_and_the_launches_of_a_cycle(api, krylov)
 
 def test_bicgstab_with_the_smoothed_hierarchy(api, krylov):
     A, b, ref, da, h, h0 = krylov
-    _solve_and_compare(krylov, "bicgstab", bicgstab_ref(ref, b, np.zeros(A[0]), KRYLOV_TOL, 200), h)
+    _solve_and_compare(da, b, h, "bicgstab", bicgstab_ref(ref, b, np.zeros(A[0]), KRYLOV_TOL, 200), KRYLOV_TOL)
 
 
 def test_gmres_with_the_smoothed_hierarchy(api, krylov):
     A, b, ref, da, h, h0 = krylov
-    _solve_and_compare(krylov, "gmres", gmres_ref(ref, b, np.zeros(A[0]), KRYLOV_TOL, 200, 5), h0, restart=5)
-    _solve_and_compare(krylov, "gmres", gmres_ref(ref, b, np.zeros(A[0]), KRYLOV_TOL, 200, 5), h, restart=5)
+    _solve_and_compare(da, b, h0, "gmres", gmres_ref(ref, b, np.zeros(A[0]), KRYLOV_TOL, 200, 5), KRYLOV_TOL, restart=5)
+    _solve_and_compare(da, b, h, "gmres", gmres_ref(ref, b, np.zeros(A[0]), KRYLOV_TOL, 200, 5), KRYLOV_TOL, restart=5)
 
 
 def test_cycles_queued_past_the_stop_write_nothing(api, krylov):

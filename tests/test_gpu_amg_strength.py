@@ -12,6 +12,7 @@ import amg_ref as ar
 import amg_sa_ref as sa
 import filter_ref as fr
 import spgemm_ref as sr
+from amg_gpu import _bits, _blob, _down, _same, _solve_and_compare, _special_r, _up
 from bits import assert_same_bits
 from gmres_ref import gmres_ref
 from krylov_ref import bicgstab_ref, cg_ref
@@ -33,36 +34,8 @@ def api():
     a.spmvHipFinalize()
 
 
-def _up(api, A):
-    return api.spMatCpyCSR(api.HostCSR(*A))
-
-
-def _down(api, ptr, n, dtype):
-    out = np.empty(n, dtype=dtype)
-    if n:
-        assert api.lib.spmvHipMemcpyDown(out.ctypes.data_as(C.c_void_p), C.cast(ptr, C.c_void_p), out.nbytes) == 0
-    return out
-
-
-def _same(got, want, what):
-    nan = np.isnan(want)
-    assert np.array_equal(np.isnan(got), nan), f"{what}: NaN places"
-    assert_same_bits(np.where(nan, 0.0, got), np.where(nan, 0.0, want), what)
-
-
-def _bits(x):
-    return np.float64(x).view(np.uint64)
-
-
 def _raw(obj):
     return bytes(C.string_at(C.addressof(obj), C.sizeof(obj)))
-
-
-def _blob(v):
-    """the bytes of a downloaded piece: an array, a number, None, or a tuple of them"""
-    if isinstance(v, tuple):
-        return b"|".join(_blob(t) for t in v)
-    return b"" if v is None else np.asarray(v).tobytes()
 
 
 def _level_arrays(api, h, l, strength=True):
@@ -160,14 +133,6 @@ def test_a_tiny_theta_gives_the_smoothed_setup(api):
 
 
 # --------------------------------------------------------------------------------------------------------------- cycle
-def _special_r(M):
-    r = np.random.default_rng(7).standard_normal(M)
-    r[[3, 100, 511]] = 0.0
-    r[[4, 101]] = -0.0
-    r[200], r[201], r[300] = np.inf, -np.inf, np.nan
-    return r
-
-
 @pytest.mark.parametrize("nu", [(0, 0, 1), (1, 1, 8), (2, 1, 3)])
 def test_cycle_bits(api, nu):
     kw = dict(coarseRows=8, nu1=nu[0], nu2=nu[1], nuCoarse=nu[2])
@@ -194,22 +159,12 @@ def krylov(api):
     da.free()
 
 
-def _solve_and_compare(krylov, method, want, **kw):
-    A, b, ref, da, h = krylov
-    x, info = getattr(da, method)(b, precond=h, tol=KRYLOV_TOL, maxiter=200, history=True, **kw)
-    wx, wstatus, wit, whist, _ = want
-    assert (info.status, info.iterations) == (wstatus, wit), method
-    assert_same_bits(x, wx, f"{method}: x")
-    assert_same_bits(info.history, whist, f"{method}: history")
-    return info
-
-
 def test_cg_takes_exactly_the_reference_count(api, krylov):
     A, b, ref, da, h = krylov
     want = cg_ref(ref, b, np.zeros(A[0]), KRYLOV_TOL, 200)
     assert want[2] == COUNTS[ANISO][2] < COUNTS[ANISO][1]
     assert h.info.levels == len(ref.levels) == 5
-    assert _solve_and_compare(krylov, "cg", want).iterations == COUNTS[ANISO][2]
+    assert _solve_and_compare(da, b, h, "cg", want, KRYLOV_TOL).iterations == COUNTS[ANISO][2]
     smooth = da.amg(smoothed=True, **KRYLOV_OPTS)
     try:
         x, info = da.cg(b, precond=smooth, tol=KRYLOV_TOL, maxiter=200)
@@ -220,8 +175,8 @@ def test_cg_takes_exactly_the_reference_count(api, krylov):
 
 def test_bicgstab_and_gmres(api, krylov):
     A, b, ref, da, h = krylov
-    _solve_and_compare(krylov, "bicgstab", bicgstab_ref(ref, b, np.zeros(A[0]), KRYLOV_TOL, 200))
-    _solve_and_compare(krylov, "gmres", gmres_ref(ref, b, np.zeros(A[0]), KRYLOV_TOL, 200, 5), restart=5)
+    _solve_and_compare(da, b, h, "bicgstab", bicgstab_ref(ref, b, np.zeros(A[0]), KRYLOV_TOL, 200), KRYLOV_TOL)
+    _solve_and_compare(da, b, h, "gmres", gmres_ref(ref, b, np.zeros(A[0]), KRYLOV_TOL, 200, 5), KRYLOV_TOL, restart=5)
 
 
 def test_the_block_solvers_refuse_it(api, krylov, capfd):
