@@ -881,9 +881,63 @@ int spmvHipCsrFilterRefresh(spmat* dC, spmat* dA, spmvFilterInfo* info);
  * spmvHipAmgSmoother: a view of level l: kind, the counts in force (0: none), rho_l, lambdaMax, lambdaMin, nCoef and dCoef =
  *   the device address of the nCoef pairs (a_0, b_0, a_1, b_1, ...; NULL when nCoef = 0).  On a hierarchy never given a
  *   smoother, or given JACOBI: kind JACOBI, the counts, zeros and NULL.  Refused, info untouched: a dM that is not a
- *   hierarchy, a level beyond the last, a NULL info. */
+ *   hierarchy, a level beyond the last, a NULL info.
+ *
+ * Multicolour Gauss-Seidel smoother of the cycle.  spmvHipAmgSetGaussSeidel(dM, dA, opts) makes a
+ *   hierarchy of any of the three setups smooth with Gauss-Seidel sweeps ordered by a colouring, FROM THEN ON, as
+ *   spmvHipAmgSetSmoother does for its two kinds (a cycle captured earlier must be captured again; synchronous on the
+ *   library stream; it allocates the colour lists and nothing else, so it is not capturable).  It is an entry point of its
+ *   own: spmvHipAmgSetSmoother keeps refusing kind 2.  opts (NULL, or a field 0: the built-in default): order NATURAL, seed,
+ *   omega 1.0, oneWay 0 (symmetric), levels 0 (all), nu1 / nu2 / nuCoarse as in spmvAmgSmootherOpts.  The defaults are
+ *   conventions.  Per Gauss-Seidel level l, l < levels (on a strength hierarchy from A_l, NOT F_l: the sweeps are A_l's):
+ *       colour_l, perm_l = what spmvHipColourCSR(A_l, {order, seed}) gives;   C_l = its colour count
+ *       dColourPtr = the C_l + 1 offsets of the colour classes in perm_l     (class c is perm_l[dColourPtr[c] .. dColourPtr[c+1]-1])
+ *   Rows of one colour store no column of that colour but their own diagonal (a colouring of A + A^T), so the rows of a colour
+ *   may run in any order and on any lane.  The smoother, no FMA, every operation rounded in the order written:
+ *       GS(l, r, z, q, fromNothing, backward_k):
+ *         if fromNothing:  z_i = +0.0 for every i
+ *         for k = 0 .. q-1:
+ *           for c = 0 .. C_l-1  (backward_k: C_l-1 .. 0):
+ *             for every row i of colour c:
+ *               t = +0.0;  for p in A_l.IRP[i] .. A_l.IRP[i+1]-1 (stored order):  t = t + A_l.AS[p] * z[A_l.JA[p]]
+ *               z_i = z_i + omega * (dinv_i * (r_i - t))
+ *   the Jacobi sweep's line with the serial-order row sum taken from the CURRENT z, one colour at a time.  The cycle is V(l, r)
+ *   above with, on a Gauss-Seidel level, the pre-smoothing lines replaced by GS(l, r, z, sweeps, true, forward) (sweeps == 0
+ *   still gives z = +0.0) and the nu2 lines by GS(l, r, z, nu2, false, oneWay ? forward : backward); on the last level sweep k
+ *   runs forward when oneWay or k is even, backward otherwise.  The residual, the restriction, the correction (gather, fused
+ *   or two-kernel P e) and the stop pointer are unchanged.  Levels l >= levels run the Jacobi lines of V with the hierarchy's
+ *   omega, bit for bit.  With oneWay = 0 and nu1 = nu2 the cycle is a symmetric operator for a symmetric A (what CG needs).
+ *   Kernels.  A sweep of a level is one launch per colour, whatever the row lengths.  A row takes g lanes, which form g
+ *   products at a time from consecutive entries while the additions stay in stored order (the bits fix the order of the
+ *   additions, not the lane that performs them): g = the largest power of two from 4 to 64 that the level's mean row fills
+ *   (1 on a level whose mean is at most 2), unless spmvHipSetVariant("spmvHipAmgGaussSeidel", g), g = 1, 4, 8, 16, 32 or 64
+ *   (0: by the mean again), read at the SET call; with g = 1 a row of at most 64 stored entries takes a lane and a longer
+ *   one a wavefront (the convention of the colouring and the aggregation).  The same bits for every g.  A SMALL
+ *   level, 0 < M_l <= n, runs a whole sweep -- all colours in order, a workgroup barrier between them -- in ONE launch of one
+ *   workgroup: the same bits.  n = 1024 (a convention) unless spmvHipSetVariant("spmvHipAmgSetGaussSeidel", n), 0 <= n <=
+ *   65536, 0: never; read at the SET call, so Apply still only enqueues: kernels only, capturable, no allocation.  With
+ *   K_l = 1 for a small level, C_l otherwise, 0 when M_l = 0, the Gauss-Seidel levels of one cycle enqueue
+ *       sum over l < L-1 of (1 + nu1 * K_l + 3 + 1 [+ 1 when the correction is not fused] + nu2 * K_l)  +  1 + nuCoarse * K_{L-1}
+ *   kernels (the zero pass, the sweeps, the residual's SpMV and pass and the restriction, the correction); a Jacobi level
+ *   keeps its term of the formulas above.  Ordering comes from kernel boundaries and that barrier alone.
+ *   Kept per Gauss-Seidel level and counted in spmvAmgInfo.bytes: perm_l (4 B per row) and dColourPtr (4 (C_l + 1) B); no new
+ *   vector.  spmvHipAmgRefresh recomputes nothing for this smoother beyond dinv_l -- the colours are the pattern's -- and
+ *   keeps the addresses: a refreshed hierarchy is bit-identical to a fresh setup followed by the same call, and a captured
+ *   cycle replayed after a refresh is valid.
+ *   Switching: spmvHipAmgSetSmoother(JACOBI | CHEBYSHEV) on a Gauss-Seidel hierarchy drops the colour lists (the bytes of a
+ *   hierarchy that never had them); spmvHipAmgSetGaussSeidel on a Chebyshev hierarchy drops the tables, on a Gauss-Seidel
+ *   hierarchy the old lists.  Everything new is made before anything old is dropped.  spmvHipAmgSmoother on a Gauss-Seidel
+ *   hierarchy reports kind SPMV_AMG_SMOOTHER_GAUSS_SEIDEL, the counts, zeros and NULL.
+ *   Refused with a message and EXIT_FAILURE, the hierarchy, its smoother and its views exactly as they were: NULL dM or dA;
+ *   handles that are not live; a dM that is not a hierarchy; a dA that is not the source; an unknown order; an omega that is
+ *   not finite or is < 0 (0: the default); a count above SPMV_AMG_MAX_DEGREE other than SPMV_AMG_NO_SWEEPS.
+ * spmvHipAmgGaussSeidel: a view of level l: active (1 on a Gauss-Seidel level), colours = C_l, maxColourRows, longRows (the
+ *   rows of A_l above 64 stored entries), small (1: the one-workgroup sweep), omega, order, seed, oneWay, dPerm and dColourPtr
+ *   (device addresses, the hierarchy's).  On a Jacobi level of a Gauss-Seidel hierarchy, and on a hierarchy that smooths
+ *   otherwise: zeros and NULL.  Refused, info untouched: a dM that is not a hierarchy, a level beyond the last, a NULL info. */
 #define SPMV_AMG_SMOOTHER_JACOBI     0
 #define SPMV_AMG_SMOOTHER_CHEBYSHEV  1
+#define SPMV_AMG_SMOOTHER_GAUSS_SEIDEL 2      /* reported by the views; set only by spmvHipAmgSetGaussSeidel */
 #define SPMV_AMG_MAX_DEGREE          64
 #define SPMV_AMG_MAX_LEVELS 16
 #define SPMV_AMG_NO_SWEEPS  0xFFFFFFFFu
@@ -947,6 +1001,19 @@ typedef struct { int kind; unsigned nu1, nu2, nuCoarse; double rho, lambdaMax, l
                  unsigned nCoef; const double* dCoef; } spmvAmgSmootherInfo;
 int spmvHipAmgSetSmoother(spmat* dM, spmat* dA, const spmvAmgSmootherOpts* opts);
 int spmvHipAmgSmoother(spmat* dM, unsigned level, spmvAmgSmootherInfo* info);
+typedef struct {            /* 0 = the built-in default */
+    int      order;         /* SPMV_COLOUR_NATURAL (default) or SPMV_COLOUR_HASH                     */
+    uint32_t seed;          /* of the HASH keys                                                      */
+    double   omega;         /* relaxation (1.0); must be finite and > 0                              */
+    int      oneWay;        /* 0: forward before the correction, backward after it (symmetric);      */
+                            /* 1: forward everywhere                                                 */
+    unsigned levels;        /* Gauss-Seidel on levels l < levels, damped Jacobi (V above) below; 0: all */
+    unsigned nu1, nu2, nuCoarse;   /* as in spmvAmgSmootherOpts: 0 keeps, SPMV_AMG_NO_SWEEPS none, <= SPMV_AMG_MAX_DEGREE */
+} spmvAmgGsOpts;
+typedef struct { int active; unsigned colours; ulong maxColourRows, longRows; int small; double omega; int order; uint32_t seed;
+                 int oneWay; const uint32_t* dPerm; const uint32_t* dColourPtr; } spmvAmgGsInfo;
+int spmvHipAmgSetGaussSeidel(spmat* dM, spmat* dA, const spmvAmgGsOpts* opts);
+int spmvHipAmgGaussSeidel(spmat* dM, unsigned level, spmvAmgGsInfo* info);
 /* Release the device arrays behind a handle (cudaUtils.h:70-78). */
 int hipFreeSpmat(spmat* dMat);
 
@@ -1205,6 +1272,13 @@ int spmvHipProbeLdsAtomicOrder(void);
  *                             kernel on every level whose prolongator has no row longer than n entries (default 0 = never
  *                             fused, an SpMV and an add: the faster form on the 5 M-row Laplacian, DESIGN.md section 28;
  *                             64 is the long-row convention).  z does not change by a bit.
+ *   spmvHipAmgSetGaussSeidel  n, 0..65536: spmvHipAmgSetGaussSeidel calls made AFTER the call sweep a level of at most n rows
+ *                             in one launch of one workgroup (default 1024, unmeasured; 0 = never: a launch per colour).
+ *                             z does not change by a bit.
+ *   spmvHipAmgGaussSeidel     g, one of 0, 1, 4, 8, 16, 32, 64: the lanes that take one row in the sweeps of
+ *                             spmvHipAmgSetGaussSeidel calls made AFTER the call (default 0 = per level, the largest power of
+ *                             two from 4 to 64 that the mean row fills; 1 = a lane per row, a wavefront above 64 entries;
+ *                             DESIGN.md section 32 has both measured).  z does not change by a bit.
  * Returns EXIT_FAILURE for an unknown (launcher, variant). */
 int spmvHipSetVariant(const char* launcher, int variant);
 /* Use the RL array for ELL early exit (1, default when RL was uploaded) or walk

@@ -137,6 +137,8 @@ _sigs = {
     "spmvHipAmgStrength": ([C.POINTER(spmat), C.c_uint, C.POINTER(spmat), C.POINTER(C.c_double)], _i),
     "spmvHipAmgSetSmoother": ([C.POINTER(spmat), C.POINTER(spmat), _vp], _i),
     "spmvHipAmgSmoother": ([C.POINTER(spmat), C.c_uint, _vp], _i),
+    "spmvHipAmgSetGaussSeidel": ([C.POINTER(spmat), C.POINTER(spmat), _vp], _i),
+    "spmvHipAmgGaussSeidel": ([C.POINTER(spmat), C.c_uint, _vp], _i),
 }
 SPMV_DENSE_ROW_MAJOR, SPMV_DENSE_COL_MAJOR = 0, 1          # include/spmvHip.h: layouts of hipSpMMRowsCSR's X and Y
 SPMV_TRI_LOWER, SPMV_TRI_UPPER = 0, 1                      # include/spmvHip.h: hipSpTRSVCSR's uplo ...
@@ -312,6 +314,23 @@ class spmvAmgSmootherInfo(C.Structure):
     """include/spmvHip.h `spmvAmgSmootherInfo`: the smoother of one level; dCoef is the device address of nCoef (a, b) pairs."""
     _fields_ = [("kind", _i), ("nu1", C.c_uint), ("nu2", C.c_uint), ("nuCoarse", C.c_uint), ("rho", C.c_double),
                 ("lambdaMax", C.c_double), ("lambdaMin", C.c_double), ("nCoef", C.c_uint), ("dCoef", C.POINTER(C.c_double))]
+
+
+SPMV_AMG_SMOOTHER_GAUSS_SEIDEL = 2
+
+
+class spmvAmgGsOpts(C.Structure):
+    """include/spmvHip.h `spmvAmgGsOpts`: the multicolour Gauss-Seidel smoother of the cycle (a field 0: the default)."""
+    _fields_ = [("order", _i), ("seed", C.c_uint32), ("omega", C.c_double), ("oneWay", _i), ("levels", C.c_uint),
+                ("nu1", C.c_uint), ("nu2", C.c_uint), ("nuCoarse", C.c_uint)]
+
+
+class spmvAmgGsInfo(C.Structure):
+    """include/spmvHip.h `spmvAmgGsInfo`: the Gauss-Seidel state of one level; dPerm (M words) and dColourPtr (colours + 1
+    words) are device addresses."""
+    _fields_ = [("active", _i), ("colours", C.c_uint), ("maxColourRows", C.c_ulong), ("longRows", C.c_ulong), ("small", _i),
+                ("omega", C.c_double), ("order", _i), ("seed", C.c_uint32), ("oneWay", _i), ("dPerm", C.POINTER(C.c_uint32)),
+                ("dColourPtr", C.POINTER(C.c_uint32))]
 
 
 SPMV_COLOUR_NATURAL, SPMV_COLOUR_HASH = 0, 1
@@ -1091,8 +1110,8 @@ class DeviceMatrix:
 
 class AmgHierarchy(DeviceMatrix):
     """What DeviceMatrix.amg() returns: a hierarchy handle (no matrix: SpMV, formats and solves refuse it) with `info`
-    (spmvAmgInfo), apply(), refresh_from(), level(), prolongator(), strength(), set_smoother(), smoother() and free().  It keeps a
-    reference to its source matrix."""
+    (spmvAmgInfo), apply(), refresh_from(), level(), prolongator(), strength(), set_smoother(), smoother(), set_gauss_seidel(),
+    gauss_seidel() and free().  It keeps a reference to its source matrix."""
 
     def __init__(self, source):
         super().__init__()
@@ -1169,6 +1188,37 @@ class AmgHierarchy(DeviceMatrix):
             _check(lib.spmvHipMemcpyDown(coef.ctypes.data_as(C.c_void_p), C.cast(v.dCoef, C.c_void_p), coef.nbytes), "spmvHipMemcpyDown")
         return dict(kind=int(v.kind), nu1=int(v.nu1), nu2=int(v.nu2), nuCoarse=int(v.nuCoarse), rho=float(v.rho), lambdaMax=float(v.lambdaMax),
                     lambdaMin=float(v.lambdaMin), dCoef=C.cast(v.dCoef, C.c_void_p).value, coef=coef)
+
+    def set_gauss_seidel(self, omega=None, order="natural", seed=0, one_way=False, levels=None, nu1=None, nu2=None, nuCoarse=None):
+        """spmvHipAmgSetGaussSeidel: the cycle smooths with multicolour Gauss-Seidel sweeps from now on.  omega: the
+        relaxation (1.0); order / seed: those of the colouring ("natural" or "hash", or the header's number); one_way:
+        forward everywhere instead of forward before and backward after the correction; levels: Gauss-Seidel on the levels
+        below it, damped Jacobi from it on (None: all); a count None keeps the hierarchy's, 0 asks for none.  A cycle captured
+        earlier must be captured again.  `info` is read again (its bytes count the colour lists)."""
+        if isinstance(order, str) and order not in COLOUR_ORDERS:
+            raise SpmvHipError(f"set_gauss_seidel: order {order!r} is neither 'natural' nor 'hash'")
+        opts = spmvAmgGsOpts(COLOUR_ORDERS[order] if isinstance(order, str) else int(order), int(seed) & 0xFFFFFFFF, float(omega or 0.0),
+                             int(bool(one_way)), int(levels or 0), _amg_sweeps(nu1), _amg_sweeps(nu2), _amg_sweeps(nuCoarse))
+        _check(lib.spmvHipAmgSetGaussSeidel(C.byref(self.handle), C.byref(self.source.handle), C.byref(opts)), "spmvHipAmgSetGaussSeidel")
+        _check(lib.spmvHipAmgInfo(C.byref(self.handle), C.byref(self.info)), "spmvHipAmgInfo")
+
+    def gauss_seidel(self, l):
+        """spmvHipAmgGaussSeidel: the Gauss-Seidel state of level l as a dict: active, colours, maxColourRows, longRows,
+        small, omega, order, seed, oneWay, dPerm / dColourPtr (device addresses, None on a level that does not sweep by
+        colours) and perm / colourPtr, the two lists downloaded (None likewise)"""
+        v = spmvAmgGsInfo()
+        _check(lib.spmvHipAmgGaussSeidel(C.byref(self.handle), int(l), C.byref(v)), "spmvHipAmgGaussSeidel")
+        out = dict(active=int(v.active), colours=int(v.colours), maxColourRows=int(v.maxColourRows), longRows=int(v.longRows), small=int(v.small),
+                   omega=float(v.omega), order=int(v.order), seed=int(v.seed), oneWay=int(v.oneWay), dPerm=C.cast(v.dPerm, C.c_void_p).value,
+                   dColourPtr=C.cast(v.dColourPtr, C.c_void_p).value, perm=None, colourPtr=None)
+        if v.active:
+            view = spmat()
+            _check(lib.spmvHipAmgLevel(C.byref(self.handle), int(l), C.byref(view), None, None), "spmvHipAmgLevel")
+            out["perm"], out["colourPtr"] = np.empty(int(view.M), np.uint32), np.empty(int(v.colours) + 1, np.uint32)
+            for a, ptr in ((out["perm"], v.dPerm), (out["colourPtr"], v.dColourPtr)):
+                if a.size:
+                    _check(lib.spmvHipMemcpyDown(a.ctypes.data_as(C.c_void_p), C.cast(ptr, C.c_void_p), a.nbytes), "spmvHipMemcpyDown")
+        return out
 
     def free(self):
         super().free()

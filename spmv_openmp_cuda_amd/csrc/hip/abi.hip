@@ -154,6 +154,11 @@ int spmvHipSetVariant(const char* launcher, int variant) {
     if (!strcmp(launcher, "spmvHipColourCSR") && variant >= 1 && variant <= 4096) { S.colourK = (uint32_t)variant; return EXIT_SUCCESS; }
     if (!strcmp(launcher, "spmvHipAggregateCSR") && variant >= 1 && variant <= 4096) { S.aggK = (uint32_t)variant; return EXIT_SUCCESS; }
     if (!strcmp(launcher, "spmvHipAmgApply") && variant >= 0 && variant <= 4096) { S.amgFuseMax = (uint32_t)variant; return EXIT_SUCCESS; }
+    if (!strcmp(launcher, "spmvHipAmgSetGaussSeidel") && variant >= 0 && variant <= 65536) { S.amgGsSmallRows = (uint32_t)variant; return EXIT_SUCCESS; }
+    if (!strcmp(launcher, "spmvHipAmgGaussSeidel") && (variant == 0 || variant == 1 || variant == 4 || variant == 8 || variant == 16 || variant == 32 || variant == 64)) {
+        S.amgGsLanes = (uint32_t)variant;
+        return EXIT_SUCCESS;
+    }
     ERR("spmvHipSetVariant: unknown (%s, %d)", launcher, variant);
     return EXIT_FAILURE;
 }

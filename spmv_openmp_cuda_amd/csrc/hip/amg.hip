@@ -6,12 +6,15 @@
 // REFRESH (levelFilter, smoothProlongator, galerkin below); what a hierarchy is made of is its AmgKind.
 // Cycle.  Its vector kernels are ops of the Krylov files' fused-pass kernel (krylov.hpp: 16-byte accesses when every pointer
 // allows, the same bits otherwise), each with the stop pointer of a Krylov loop.  A smoothing step is an SpMV into t_l and one
-// pass, damped Jacobi or Chebyshev alike: the launch count is the formula of the sweeps.
-// DESIGN.md sections 24 (the cycle), 28 (smoothed P, the fused correction), 29 (strength), 30 (Chebyshev), 31 (the recipe, the kinds).
+// pass, damped Jacobi or Chebyshev alike: the launch count is the formula of the sweeps.  A Gauss-Seidel sweep is kernels of
+// this file: one launch per colour of the level, or one workgroup for a whole sweep of a small level.
+// DESIGN.md sections 24 (the cycle), 28 (smoothed P, the fused correction), 29 (strength), 30 (Chebyshev), 31 (the recipe, the kinds),
+// 32 (Gauss-Seidel).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <chrono>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "device_prims.hpp"
@@ -36,6 +39,14 @@ struct AmgLevel {
     double rhoS = 0.0, lmax = 0.0, lmin = 0.0;
     uint32_t nCoef = 0;
     double2* coef = nullptr;
+    // Gauss-Seidel (null and 0 on a level that does not sweep by colours): the rows by (colour, id), the C + 1 offsets of the
+    // colour classes on the device and on the host (the grids of the colour launches), and what the view reports
+    uint32_t* perm = nullptr;
+    uint32_t* colourPtr = nullptr;
+    std::vector<uint32_t> hColourPtr;
+    uint64_t maxColourRows = 0, longRows = 0;
+    bool gsSmall = false;               // the whole sweep in one launch of one workgroup
+    uint32_t gsLanes = 1;               // lanes per row of the sweep kernels: 1 (and a wavefront above 64 entries), or 4 .. 64
 };
 
 struct AmgHierarchy {
@@ -46,6 +57,10 @@ struct AmgHierarchy {
     bool strength() const { return plan.kind == AmgKind::STRENGTH; }    // smoothed on the strength-filtered F_l
     int smoother = SPMV_AMG_SMOOTHER_JACOBI;    // of the cycle (spmvHipAmgSetSmoother)
     double eigRatio = 10.0, lambdaScale = 1.0;  // Chebyshev: lambda_min = lambda_max / eigRatio, lambda_max = lambdaScale * rho_l
+    double gsOmega = 1.0;                       // Gauss-Seidel: the relaxation, the colouring's order and seed, forward everywhere
+    int gsOrder = SPMV_COLOUR_NATURAL;
+    uint32_t gsSeed = 0;
+    bool gsOneWay = false;
     std::vector<AmgLevel> lv;
     spmvAmgInfo info{};
 };
@@ -217,6 +232,125 @@ struct AmgAddOp : StopMode {                    // z = z + d
         st2<VEC>(z, i, two, make_double2(v.z.x + v.d.x, v.z.y + v.d.y));
     }
 };
+
+// ------------------------------------------------------------------------------------------------ Gauss-Seidel sweeps
+// z_i = z_i + omega * (dinv_i * (r_i - t)), t the row sum of A z in stored order from the CURRENT z, for the rows of one
+// colour: perm[slot] for the slots of the colour's class.  No row of a colour stores a column of that colour but its own
+// diagonal, so the rows of a class neither read nor write what another row of the class writes.  A wavefront takes 64
+// slots: a row of at most GS_LONG entries is walked by its lane; the longer rows of the wavefront are then taken one by
+// one by all 64 lanes, which form 64 products at a time and add them in stored order (every lane the same sum).  The
+// caller passes whole wavefronts (valid = false for a slot past the class), since the long rows are found by a ballot.
+constexpr uint32_t GS_LONG = 64;
+template <typename I>
+__device__ __forceinline__ void gs_slot(bool valid, uint32_t slot, const uint32_t* __restrict__ perm, const I* __restrict__ IRP,
+                                        const uint32_t* __restrict__ JA, const double* __restrict__ AS, const double* __restrict__ r,
+                                        const double* __restrict__ dinv, double* z, double omega) {
+    uint32_t i = 0;
+    uint64_t b = 0, e = 0;
+    if (valid) { i = perm[slot]; b = IRP[i]; e = IRP[i + 1]; }
+    const bool isLong = e - b > GS_LONG;
+    if (valid && !isLong) {
+        double t = 0.0;
+        for (uint64_t p = b; p < e; ++p) t = t + AS[p] * z[JA[p]];
+        z[i] = z[i] + omega * (dinv[i] * (r[i] - t));
+    }
+    unsigned long long todo = __ballot(isLong);
+    const uint32_t lane = threadIdx.x % 64;
+    while (todo) {
+        const int src = __ffsll(todo) - 1;
+        todo &= todo - 1;
+        const uint64_t lb = __shfl(b, src), le = __shfl(e, src);
+        double t = 0.0;
+        for (uint64_t p0 = lb; p0 < le; p0 += 64) {
+            const uint64_t p = p0 + lane;
+            const double prod = p < le ? AS[p] * z[JA[p]] : 0.0;
+            const uint32_t n = (uint32_t)min((uint64_t)64, le - p0);
+            for (uint32_t k = 0; k < n; ++k) t = t + __shfl(prod, (int)k);
+        }
+        if (lane == (uint32_t)src) z[i] = z[i] + omega * (dinv[i] * (r[i] - t));
+    }
+}
+// G > 1 lanes per row: the lanes of a group form G products at a time from G consecutive entries of their row -- one
+// contiguous piece of JA and of AS per group, where a lane per row touches a line per lane -- and every lane of the group adds
+// them in stored order, so the sum is the lane-per-row form's bit for bit.  A row longer than G takes more pieces.  The
+// lanes of a group hold the same slot: they run the same trips and read each other only.
+template <typename I, int G>
+__device__ __forceinline__ void gs_group(bool valid, uint32_t slot, const uint32_t* __restrict__ perm, const I* __restrict__ IRP,
+                                         const uint32_t* __restrict__ JA, const double* __restrict__ AS, const double* __restrict__ r,
+                                         const double* __restrict__ dinv, double* z, double omega) {
+    if (!valid) return;
+    const uint32_t sub = threadIdx.x % G, i = perm[slot];
+    const uint64_t b = IRP[i], e = IRP[i + 1];
+    double t = 0.0;
+    for (uint64_t p0 = b; p0 < e; p0 += G) {
+        const uint64_t p = p0 + sub;
+        const double prod = p < e ? AS[p] * z[JA[p]] : 0.0;
+        const uint32_t n = (uint32_t)min((uint64_t)G, e - p0);
+        for (uint32_t k = 0; k < n; ++k) t = t + __shfl(prod, (int)k, G);
+    }
+    if (sub == 0) z[i] = z[i] + omega * (dinv[i] * (r[i] - t));
+}
+template <typename I, int G>
+__device__ __forceinline__ void gs_rows(bool valid, uint32_t slot, const uint32_t* __restrict__ perm, const I* __restrict__ IRP,
+                                        const uint32_t* __restrict__ JA, const double* __restrict__ AS, const double* __restrict__ r,
+                                        const double* __restrict__ dinv, double* z, double omega) {
+    if constexpr (G == 1) gs_slot<I>(valid, slot, perm, IRP, JA, AS, r, dinv, z, omega);
+    else gs_group<I, G>(valid, slot, perm, IRP, JA, AS, r, dinv, z, omega);
+}
+// one colour of a sweep: the slots [cb, ce) of perm, one launch; G lanes per slot
+template <typename I, int G>
+__global__ __launch_bounds__(AG_THREADS) void amg_gs_colour_kernel(uint32_t cb, uint32_t ce, const uint32_t* __restrict__ perm, const I* __restrict__ IRP,
+                                                                   const uint32_t* __restrict__ JA, const double* __restrict__ AS,
+                                                                   const double* __restrict__ r, const double* __restrict__ dinv, double* z,
+                                                                   double omega, const uint32_t* __restrict__ stop) {
+    if (stop && *stop) return;
+    const uint64_t slot = cb + linear_block() * (AG_THREADS / G) + threadIdx.x / G;
+    gs_rows<I, G>(slot < ce, (uint32_t)slot, perm, IRP, JA, AS, r, dinv, z, omega);
+}
+// a whole sweep of a small level in one workgroup: the nC colours in order (backward: last first), a workgroup barrier
+// between two colours -- the writes of a colour are visible to the workgroup's other wavefronts after it
+template <typename I, int G>
+__global__ __launch_bounds__(AG_THREADS) void amg_gs_small_kernel(uint32_t nC, int backward, const uint32_t* __restrict__ colourPtr,
+                                                                  const uint32_t* __restrict__ perm, const I* __restrict__ IRP,
+                                                                  const uint32_t* __restrict__ JA, const double* __restrict__ AS,
+                                                                  const double* __restrict__ r, const double* __restrict__ dinv, double* z,
+                                                                  double omega, const uint32_t* __restrict__ stop) {
+    if (stop && *stop) return;
+    const uint32_t mine = threadIdx.x / G, waveFirst = (threadIdx.x - threadIdx.x % 64) / G;     // the slot of the lane and of its wavefront
+    for (uint32_t k = 0; k < nC; ++k) {
+        const uint32_t c = backward ? nC - 1 - k : k;
+        const uint32_t cb = colourPtr[c], ce = colourPtr[c + 1];
+        for (uint64_t base = cb; base + waveFirst < ce; base += AG_THREADS / G)             // (whole wavefronts make the trips)
+            gs_rows<I, G>(base + mine < ce, (uint32_t)(base + mine), perm, IRP, JA, AS, r, dinv, z, omega);
+        __syncthreads();
+    }
+}
+// the lanes per row as a compile-time constant: f(std::integral_constant<int, G>)
+template <typename F>
+void withLanes(uint32_t g, F&& f) {
+    switch (g) {
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 8: return f(std::integral_constant<int, 8>{});
+        case 16: return f(std::integral_constant<int, 16>{});
+        case 32: return f(std::integral_constant<int, 32>{});
+        case 64: return f(std::integral_constant<int, 64>{});
+        default: return f(std::integral_constant<int, 1>{});
+    }
+}
+// the view's count of long rows, and keys[s] = colour[perm[s]] (ascending: the class offsets are its bounds)
+template <typename I>
+__global__ __launch_bounds__(AG_THREADS) void amg_gs_classes_kernel(uint64_t M, const I* __restrict__ IRP, const uint32_t* __restrict__ colour,
+                                                                    const uint32_t* __restrict__ perm, uint32_t* __restrict__ keys,
+                                                                    uint32_t* __restrict__ nLong) {
+    const uint64_t s = linear_block() * AG_THREADS + threadIdx.x;
+    bool isLong = false;
+    if (s < M) {
+        keys[s] = colour[perm[s]];
+        isLong = IRP[s + 1] - IRP[s] > GS_LONG;
+    }
+    const unsigned long long m = __ballot(isLong);
+    if (threadIdx.x % 64 == 0 && m) atomicAdd(nLong, (uint32_t)__popcll(m));
+}
 
 DevMat* matOf(spmat* h) { return static_cast<DevMat*>(h->dev); }
 constexpr uint32_t NO_ROW = 0xFFFFFFFFu;                       // what a kernel's "first bad row" word holds when no row was bad
@@ -432,6 +566,8 @@ void freeAmg(AmgHierarchy* h) {
             if (m->dev) (void)hipFreeSpmat(m);
         for (double* p : {l.dinv, l.r, l.z, l.t, l.d, l.dF}) (void)hipFree(p);
         (void)hipFree(l.coef);
+        (void)hipFree(l.perm);
+        (void)hipFree(l.colourPtr);
     }
     delete h;
 }
@@ -551,8 +687,36 @@ int enqueueAmgCycle(const DevMat* m, spmat* hA, const double* r0, double* z0, hi
     // q sweeps of the hierarchy's smoother on level l, from z or from nothing (z = 0, not read): step k takes A z into t unless
     // it is the first from nothing, then makes its one pass.  (Chebyshev's d is the level's d_l: free at both smoothing sites)
     const bool cheb = H->smoother == SPMV_AMG_SMOOTHER_CHEBYSHEV;
+    // one Gauss-Seidel sweep of level l (it has rows), the colours forward or backward: one launch on a small level, else one per colour
+    auto gsSweep = [&](size_t l, const double* r, double* z, bool backward) {
+        const AmgLevel& L = H->lv[l];
+        const DevMat* a = matOf(matAt(l));
+        const uint32_t nC = (uint32_t)L.hColourPtr.size() - 1;
+        withIrp(a, [&](auto irp) {
+            withLanes(L.gsLanes, [&](auto lanes) {
+                using I = IrpT<decltype(irp)>;
+                constexpr int G = decltype(lanes)::value;
+                if (L.gsSmall) {
+                    hipLaunchKernelGGL((amg_gs_small_kernel<I, G>), dim3(1), dim3(AG_THREADS), 0, st, nC, (int)backward, L.colourPtr, L.perm, irp, a->JA,
+                                       a->AS, r, L.dinv, z, H->gsOmega, stop);
+                    ++n;
+                    return;
+                }
+                for (uint32_t k = 0; k < nC; ++k, ++n) {
+                    const uint32_t c = backward ? nC - 1 - k : k, cb = L.hColourPtr[c], ce = L.hColourPtr[c + 1];
+                    hipLaunchKernelGGL((amg_gs_colour_kernel<I, G>), gridFor(ce - cb, AG_THREADS / G), dim3(AG_THREADS), 0, st, cb, ce, L.perm, irp, a->JA,
+                                       a->AS, r, L.dinv, z, H->gsOmega, stop);
+                }
+            });
+        });
+    };
     auto smooth = [&](size_t l, const double* r, double* z, uint32_t q, bool fromNothing) {
         AmgLevel& L = H->lv[l];
+        if (L.perm) {                                          // a Gauss-Seidel level: forward before the correction, backward after
+            if (fromNothing) pass(L.M, AmgZeroOp{{stop}, z}, {z});     // it unless one-way; the last level's sweeps alternate
+            for (uint32_t k = 0; k < q && L.M; ++k) gsSweep(l, r, z, !H->gsOneWay && (l + 1 == nl ? (k & 1) != 0 : !fromNothing));
+            return EXIT_SUCCESS;
+        }
         if (q == 0 && fromNothing) pass(L.M, AmgZeroOp{{stop}, z}, {z});
         for (uint32_t k = 0; k < q; ++k) {
             const bool first = k == 0 && fromNothing;
@@ -599,6 +763,19 @@ int enqueueAmgCycle(const DevMat* m, spmat* hA, const double* r0, double* z0, hi
     return hipGetLastError() == hipSuccess ? EXIT_SUCCESS : EXIT_FAILURE;
 }
 
+// a level's Gauss-Seidel lists go, with their bytes (the stream is synchronised: no cycle in flight reads them)
+static void dropGsLists(AmgHierarchy* H, AmgLevel& L) {
+    if (!L.perm) return;
+    H->info.bytes -= L.M * 4 + L.hColourPtr.size() * 4;
+    (void)hipFree(L.perm);
+    (void)hipFree(L.colourPtr);
+    L.perm = L.colourPtr = nullptr;
+    L.hColourPtr.clear();
+    L.maxColourRows = L.longRows = 0;
+    L.gsSmall = false;
+    L.gsLanes = 1;
+}
+
 int amgSetSmoother(DevMat* m, spmat* hA, const spmvAmgSmootherOpts* o, hipStream_t st) {
     AmgHierarchy* H = m->amg;
     const size_t nl = H->lv.size();
@@ -621,6 +798,7 @@ int amgSetSmoother(DevMat* m, spmat* hA, const spmvAmgSmootherOpts* o, hipStream
     if (hipStreamSynchronize(st) != hipSuccess) return drop();     // (no cycle in flight reads a table that goes)
     for (size_t l = 0; l < nl; ++l) {
         AmgLevel& L = H->lv[l];
+        dropGsLists(H, L);
         H->info.bytes -= L.nCoef * sizeof(double2);
         (void)hipFree(L.coef);
         L.coef = dev[l];
@@ -631,6 +809,85 @@ int amgSetSmoother(DevMat* m, spmat* hA, const spmvAmgSmootherOpts* o, hipStream
     H->smoother = kind; H->eigRatio = eigRatio; H->lambdaScale = lambdaScale;
     H->nu1 = nu1; H->nu2 = nu2; H->nuCoarse = nuCoarse;
     return EXIT_SUCCESS;
+}
+
+// the lanes per row of a level's sweeps: what was asked for, or (0) the largest power of two from 4 to 64 that the mean row
+// fills (a level of rows of one or two entries keeps a lane per row): on the 7-point Laplacian 4 lanes measured faster than
+// 8, DESIGN.md section 32
+static uint32_t gsLanesFor(uint32_t asked, uint64_t M, uint64_t nnz) {
+    if (asked) return asked;
+    const uint64_t mean = M ? (nnz + M - 1) / M : 0;
+    if (mean <= 2) return 1;
+    uint32_t g = 4;
+    while (g * 2 <= mean && g < 64) g *= 2;
+    return g;
+}
+
+int amgSetGaussSeidel(DevMat* m, spmat* hA, const spmvAmgGsOpts* o, uint32_t smallRows, uint32_t lanes, uint32_t colourK, hipStream_t st) {
+    AmgHierarchy* H = m->amg;
+    const size_t nl = H->lv.size();
+    const int order = o ? o->order : SPMV_COLOUR_NATURAL;
+    const uint32_t seed = o ? o->seed : 0u;
+    const size_t gsLevels = o && o->levels ? std::min<size_t>(o->levels, nl) : nl;
+    auto fail = [&](const char* what) { return buildFail(st, "multigrid smoother", what); };
+    // everything new is made first: a refusal leaves the hierarchy as it was
+    struct Lists { TempBuf perm, ptr; std::vector<uint32_t> h; uint64_t maxRows = 0, longRows = 0; };
+    std::vector<Lists> nw(gsLevels);
+    for (size_t l = 0; l < gsLevels; ++l) {
+        const DevMat* a = matOf(l ? &H->lv[l].A : hA);
+        const uint64_t M = a->M;
+        spmvColourInfo ci{};
+        TempBuf colour, keys, nLong;
+        if (nw[l].perm.alloc(M * 4) != hipSuccess || colour.alloc(M * 4) != hipSuccess || keys.alloc(M * 4) != hipSuccess || nLong.alloc(4) != hipSuccess ||
+            hipMemsetAsync(nLong.p, 0, 4, st) != hipSuccess)
+            return fail("allocation of a level's colour lists");
+        if (colourCsr(a, order, seed, colourK, colour.as<uint32_t>(), nw[l].perm.as<uint32_t>(), &ci, st)) return fail("a level's colouring");
+        nw[l].h.assign(ci.colours + 1, 0u);
+        if (nw[l].ptr.alloc(nw[l].h.size() * 4) != hipSuccess) return fail("allocation of a level's colour lists");
+        if (M)
+            withIrp(a, [&](auto irp) {
+                hipLaunchKernelGGL((amg_gs_classes_kernel<IrpT<decltype(irp)>>), gridFor(M), dim3(AG_THREADS), 0, st, M, irp, colour.as<uint32_t>(),
+                                   nw[l].perm.as<uint32_t>(), keys.as<uint32_t>(), nLong.as<uint32_t>());
+            });
+        enqueueSortedBounds(M, ci.colours, keys.as<uint32_t>(), nw[l].ptr.as<uint32_t>(), st);
+        uint32_t hLong = 0;
+        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(nw[l].h.data(), nw[l].ptr.p, nw[l].h.size() * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipMemcpyAsync(&hLong, nLong.p, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+            return fail("a level's colour classes");
+        nw[l].maxRows = ci.maxColourRows;
+        nw[l].longRows = hLong;
+    }
+    if (hipStreamSynchronize(st) != hipSuccess) return fail("the stream");     // (no cycle in flight reads a list or a table that goes)
+    for (size_t l = 0; l < nl; ++l) {
+        AmgLevel& L = H->lv[l];
+        dropGsLists(H, L);
+        H->info.bytes -= L.nCoef * sizeof(double2);
+        (void)hipFree(L.coef);
+        L.coef = nullptr; L.nCoef = 0;
+        L.rhoS = L.lmax = L.lmin = 0.0;
+        if (l >= gsLevels) continue;
+        L.perm = nw[l].perm.detach<uint32_t>();
+        L.colourPtr = nw[l].ptr.detach<uint32_t>();
+        L.hColourPtr = std::move(nw[l].h);
+        L.maxColourRows = nw[l].maxRows; L.longRows = nw[l].longRows;
+        L.gsSmall = L.M && L.M <= smallRows;
+        L.gsLanes = gsLanesFor(lanes, L.M, L.nnz);
+        H->info.bytes += L.M * 4 + L.hColourPtr.size() * 4;
+    }
+    H->smoother = SPMV_AMG_SMOOTHER_GAUSS_SEIDEL;
+    H->gsOmega = o && o->omega != 0.0 ? o->omega : 1.0;
+    H->gsOrder = order; H->gsSeed = seed; H->gsOneWay = o && o->oneWay != 0;
+    H->nu1 = sweepsOf(o ? o->nu1 : 0, H->nu1); H->nu2 = sweepsOf(o ? o->nu2 : 0, H->nu2); H->nuCoarse = sweepsOf(o ? o->nuCoarse : 0, H->nuCoarse);
+    return EXIT_SUCCESS;
+}
+
+void amgGaussSeidel(const DevMat* m, unsigned level, spmvAmgGsInfo* info) {
+    const AmgHierarchy* H = m->amg;
+    const AmgLevel& L = H->lv[level];
+    *info = spmvAmgGsInfo{};
+    if (!L.perm) return;
+    *info = spmvAmgGsInfo{1, (unsigned)(L.hColourPtr.size() - 1), L.maxColourRows, L.longRows, L.gsSmall, H->gsOmega, H->gsOrder, H->gsSeed, H->gsOneWay,
+                          L.perm, L.colourPtr};
 }
 
 void amgSmoother(const DevMat* m, unsigned level, spmvAmgSmootherInfo* info) {

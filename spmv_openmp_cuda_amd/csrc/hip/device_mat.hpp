@@ -245,6 +245,11 @@ struct AmgPlan {
 };
 int  amgSetSmoother(DevMat* m, spmat* hA, const spmvAmgSmootherOpts* opts, hipStream_t stream);
 void amgSmoother(const DevMat* m, unsigned level, spmvAmgSmootherInfo* info);
+// amgSetGaussSeidel: the multicolour Gauss-Seidel smoother from checked options, as amgSetSmoother (a failure leaves the
+// hierarchy as it was): a level of at most smallRows rows sweeps in one workgroup, a row takes `lanes` lanes (1, 4 .. 64; 0:
+// by the level's mean row), the colourings take colourK rounds per host check.  amgGaussSeidel: the view of a level below amgInfo()->levels.
+int  amgSetGaussSeidel(DevMat* m, spmat* hA, const spmvAmgGsOpts* opts, uint32_t smallRows, uint32_t lanes, uint32_t colourK, hipStream_t stream);
+void amgGaussSeidel(const DevMat* m, unsigned level, spmvAmgGsInfo* info);
 int  aggregateCsr(const DevMat* a, uint32_t seed, uint32_t K, uint32_t* dAgg, spmvAggInfo* info, hipStream_t stream);
 int  amgBuild(spmat* hA, const spmvAmgOpts* opts, const AmgPlan& plan, DevMat* m, hipStream_t stream);
 int  amgRefresh(DevMat* m, spmat* hA, hipStream_t stream);

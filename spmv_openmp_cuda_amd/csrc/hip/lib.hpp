@@ -28,6 +28,9 @@ struct State {
     uint32_t    aggK = 16;              // spmvHipAggregateCSR: rounds per host check
     uint32_t    amgFuseMax = 0;         // spmvHipAmgSetupSmoothed: the longest row of P_l that the fused correction takes; 0: never
                                         // fused, the form that measured faster
+    uint32_t    amgGsSmallRows = 1024;  // spmvHipAmgSetGaussSeidel: a level of at most this many rows sweeps in one workgroup; 0: never
+                                        // (a convention)
+    uint32_t    amgGsLanes = 0;         // spmvHipAmgSetGaussSeidel: lanes per row of the sweeps: 1, 4, 8, 16, 32, 64; 0: by the level's mean row
     uint32_t    krylovK[2] = {16, 16};  // hipSpCGCSR, hipSpBiCGStabCSR: iterations per host check
     uint32_t    krylovBlockK[2] = {16, 16};   // hipSpCGBlockCSR, hipSpBiCGStabBlockCSR: the same
     int         ldsOrder = -1;          // lds_order_probe_kernel: -1 not run yet, 1 lane-ascending + in issue order, 0 anything else

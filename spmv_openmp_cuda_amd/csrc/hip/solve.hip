@@ -366,6 +366,28 @@ int spmvHipAmgSmoother(spmat* dM, unsigned level, spmvAmgSmootherInfo* info) {
     return EXIT_SUCCESS;
 }
 
+int spmvHipAmgSetGaussSeidel(spmat* dM, spmat* dA, const spmvAmgGsOpts* opts) {
+    const char* who = "spmvHipAmgSetGaussSeidel";
+    DevMat* a = nullptr;
+    DevMat* m = hierarchyOf(dM, dA, who, &a);
+    if (!m) return EXIT_FAILURE;
+    if (opts) {
+        if (opts->order != SPMV_COLOUR_NATURAL && opts->order != SPMV_COLOUR_HASH) { ERR("%s: unknown order %d", who, opts->order); return EXIT_FAILURE; }
+        if (!(opts->omega >= 0.0 && std::isfinite(opts->omega))) { ERR("%s: omega %g is negative or not finite", who, opts->omega); return EXIT_FAILURE; }
+        for (unsigned nu : {opts->nu1, opts->nu2, opts->nuCoarse})
+            if (nu > SPMV_AMG_MAX_DEGREE && nu != SPMV_AMG_NO_SWEEPS) { ERR("%s: %u sweeps are above %d", who, nu, SPMV_AMG_MAX_DEGREE); return EXIT_FAILURE; }
+    }
+    if (amgSetGaussSeidel(m, dA, opts, S.amgGsSmallRows, S.amgGsLanes, S.colourK, S.stream)) { ERR("%s: the smoother was not set", who); return EXIT_FAILURE; }
+    return EXIT_SUCCESS;
+}
+
+int spmvHipAmgGaussSeidel(spmat* dM, unsigned level, spmvAmgGsInfo* info) {
+    DevMat* m = hierarchyLevel(dM, "spmvHipAmgGaussSeidel", level, nullptr, !info);
+    if (!m) return EXIT_FAILURE;
+    amgGaussSeidel(m, level, info);
+    return EXIT_SUCCESS;
+}
+
 // ---- Krylov solves
 // what the three solvers check alike: 0 go on (a, m set), 1 refused, 2 done (M = 0)
 static int krylovArgs(const char* who, spmat* dA, spmat* dM, const double* dB, double* dX, const void* optsPtr, double tol, ulong maxIter,
