@@ -367,8 +367,12 @@ int hipSpBiCGStabCSR(spmat* dA, spmat* dM, const double* dB, double* dX, const s
  *   lowest-numbered column that has info.status; launches, hostChecks and ms as in the single solves.  info.launches does
  *   not depend on k: an iteration is one hipSpMMRowsCSR pass (counted as one, also for k > 16), the two hipSpTRSMCSR
  *   passes of dM, and one launch per fused pass and per scalar step, each covering all columns.
- *   dM: NULL, or an ILU(0) handle, applied as hipSpTRSMCSR(LOWER, UNIT) then (UPPER, STORED); dM == dA is allowed.  A
- *   multigrid hierarchy is refused: its cycle is single-vector.
+ *   dM: NULL, or an ILU(0) handle, applied as hipSpTRSMCSR(LOWER, UNIT) then (UPPER, STORED); dM == dA is allowed.  Or a
+ *   multigrid hierarchy of dA that was given a block workspace of width >= k (spmvHipAmgSetBlockWidth below): M^-1 is one
+ *   block cycle (spmvHipAmgApplyBlock) for all columns, every launch of it behind the same stop word, and it adds that
+ *   cycle's launch count, which does not depend on k either, to info.launches; the cycle's Z is scratch and a stopped
+ *   column's Z is never read.  Column c then has the bits of the single solve with (dA, dM).  A hierarchy without a
+ *   workspace, with width < k, or with a Gauss-Seidel level is refused (the line contains "multigrid hierarchy").
  *   Execution: one state block per column on the device; one finish launch runs every column's scalar step; every kernel
  *   that writes x, r, p, s or a column's state leaves a stopped column alone.  A word that is set when the last column
  *   stops is what the host reads once per K iterations (spmvHipSetVariant("hipSpCGBlockCSR" / "hipSpBiCGStabBlockCSR", K),
@@ -380,7 +384,7 @@ int hipSpBiCGStabCSR(spmat* dA, spmat* dM, const double* dB, double* dX, const s
  * Returns EXIT_SUCCESS whatever the statuses (cols and info may be NULL).  Refused with a message and EXIT_FAILURE, X
  *   untouched: what the single solves refuse; k = 0, an unknown layout, a leading dimension too small for its layout, any
  *   overlap of the address spans of B and X (the checks of hipSpTRSMCSR); a history of k * (maxIter + 1) doubles
- *   overflowing; a multigrid hierarchy as dM. */
+ *   overflowing; a multigrid hierarchy as dM that cannot run a block cycle of k columns (checked first of all, after k = 0). */
 typedef struct {
     int    status;          /* SPMV_KRYLOV_* of this column                                  */
     ulong  iterations;
@@ -934,7 +938,49 @@ int spmvHipCsrFilterRefresh(spmat* dC, spmat* dA, spmvFilterInfo* info);
  * spmvHipAmgGaussSeidel: a view of level l: active (1 on a Gauss-Seidel level), colours = C_l, maxColourRows, longRows (the
  *   rows of A_l above 64 stored entries), small (1: the one-workgroup sweep), omega, order, seed, oneWay, dPerm and dColourPtr
  *   (device addresses, the hierarchy's).  On a Jacobi level of a Gauss-Seidel hierarchy, and on a hierarchy that smooths
- *   otherwise: zeros and NULL.  Refused, info untouched: a dM that is not a hierarchy, a level beyond the last, a NULL info. */
+ *   otherwise: zeros and NULL.  Refused, info untouched: a dM that is not a hierarchy, a level beyond the last, a NULL info.
+ *
+ * The cycle for a block of vectors.  Opt-in per hierarchy: a block cycle needs a workspace of its
+ *   own, because Apply must not allocate, and a hierarchy that was never given one is refused by the block entry points
+ *   as before.
+ * spmvHipAmgSetBlockWidth(dM, dA, width) gives a hierarchy of any of the three setups the workspace of a block cycle for up
+ *   to `width` columns: per level t_l and d_l, below level 0 also r_l and z_l, each an M_l x kp row-major block, kp = width
+ *   rounded up to even, 16-byte aligned: 8 kp (2 M_0 + 4 (M_1 + ... + M_{L-1})) bytes in all.
+ *   width = 0 drops it: the hierarchy is then, in every respect and in spmvAmgInfo.bytes, one that never had it.  A second
+ *   call replaces the width; everything new is made before anything old is dropped.  Synchronous on the library stream; it
+ *   allocates, so it is not capturable.  The workspace holds no values: spmvHipAmgRefresh, spmvHipAmgSetSmoother and
+ *   spmvHipAmgSetGaussSeidel keep it and its addresses.  spmvAmgInfo.bytes counts it; spmvHipAmgBlock reports the width
+ *   and its bytes alone (zeros on a hierarchy without; refused, info untouched: a dM that is not a hierarchy, a NULL info).
+ *   The single-vector workspace, spmvHipAmgApply and the single solves are untouched: same bits, same launch counts.  The
+ *   block workspace is ONE, like the single one: two block cycles at once race; keep them in stream order.
+ *   Refused with a message and EXIT_FAILURE, the hierarchy exactly as it was: a NULL or not-live handle; a dM that is not a
+ *   hierarchy; a dA that is not the source; a size M_0 * kp * 8 that overflows, or an allocation that fails.
+ * spmvHipAmgApplyBlock: Z(:, c) = V(0, R(:, c)) for c = 0 .. k-1.  R and Z are M x k on the device, each with its own
+ *   layout and leading dimension by the rules of hipSpMMRowsCSR / hipSpTRSMCSR; only 8-byte alignment is needed.
+ *   Bits: every column of Z is bit for bit spmvHipAmgApply(dM, dA, R(:, c)) -- the loops V and Cheb and the P e correction
+ *   above -- for Jacobi and Chebyshev hierarchies of all three setups, whatever k, the layouts, the leading dimensions and
+ *   the alignment are.  Columns are independent: a NaN, an Inf or a -0.0 in one never reaches another.  Elements outside
+ *   the M x k block of Z are never written; R is only read.
+ *   Execution: the loop of the single cycle with every A_l z, R_l d and P_l e one hipSpMMRowsCSR pass on the level's handle
+ *   (a pass over more than 16 columns is several launches counted as one) and every fused vector pass one block launch
+ *   covering all columns (a workgroup per 4096 rows and 16-column panel).  The plain correction is the gather
+ *   Z(i, c) = Z(i, c) + E(agg_l[i], c), not a product with P_l (the two differ at -0.0, as in the single cycle); a smoothed
+ *   or strength hierarchy always corrects in two kernels, the product with P_l into d_l and Z = Z + d_l: the fuse threshold
+ *   of spmvHipSetVariant("spmvHipAmgApply", n) does not apply to the block cycle.  Chebyshev reads the same per-level table
+ *   in device memory: a captured block cycle replayed after a refresh uses the new coefficients.  With s(q) = 2 q - 1 for
+ *   q >= 1 and s(0) = 1, one block cycle enqueues
+ *       (L - 1) * (s(nu1) + 3 + 1 + 2 * nu2) + s(nuCoarse) + (L - 1 on a smoothed or strength hierarchy)
+ *   launches whatever k is: the formula above with no level fused.  Kernels only, on the library stream, no allocation:
+ *   capturable; it honours spmvHipSetSync.  k = 1 takes the same path (no shortcut to the single cycle).  M = 0 succeeds
+ *   with no kernel.  The padding column of the workspace (k odd) carries unspecified values; it is never stored into a
+ *   caller's block and never influences a real column.
+ *   Refused with a message and EXIT_FAILURE, Z untouched: NULL pointers; handles that are not live; a dM that is not a
+ *   hierarchy; a dA that is not the source; k = 0; an unknown layout; a leading dimension too small for its layout; any
+ *   overlap of the address spans of R and Z (the checks of hipSpTRSMCSR; there is no in-place form); a hierarchy without a
+ *   block workspace or with width < k (the line contains "multigrid hierarchy", names spmvHipAmgSetBlockWidth and gives
+ *   the width and k); a hierarchy with a Gauss-Seidel level (the line contains "multigrid hierarchy" and "Gauss-Seidel":
+ *   the block form of the colour sweeps does not exist; the width is kept, and after spmvHipAmgSetSmoother(JACOBI |
+ *   CHEBYSHEV) the block cycle works again). */
 #define SPMV_AMG_SMOOTHER_JACOBI     0
 #define SPMV_AMG_SMOOTHER_CHEBYSHEV  1
 #define SPMV_AMG_SMOOTHER_GAUSS_SEIDEL 2      /* reported by the views; set only by spmvHipAmgSetGaussSeidel */
@@ -1014,6 +1060,11 @@ typedef struct { int active; unsigned colours; ulong maxColourRows, longRows; in
                  int oneWay; const uint32_t* dPerm; const uint32_t* dColourPtr; } spmvAmgGsInfo;
 int spmvHipAmgSetGaussSeidel(spmat* dM, spmat* dA, const spmvAmgGsOpts* opts);
 int spmvHipAmgGaussSeidel(spmat* dM, unsigned level, spmvAmgGsInfo* info);
+typedef struct { unsigned width; ulong bytes; } spmvAmgBlockInfo;
+int spmvHipAmgSetBlockWidth(spmat* dM, spmat* dA, unsigned width);
+int spmvHipAmgBlock(spmat* dM, spmvAmgBlockInfo* info);
+int spmvHipAmgApplyBlock(spmat* dM, spmat* dA, unsigned k, const double* dR, size_t ldr, int rLayout,
+                         double* dZ, size_t ldz, int zLayout);
 /* Release the device arrays behind a handle (cudaUtils.h:70-78). */
 int hipFreeSpmat(spmat* dMat);
 

@@ -139,6 +139,9 @@ _sigs = {
     "spmvHipAmgSmoother": ([C.POINTER(spmat), C.c_uint, _vp], _i),
     "spmvHipAmgSetGaussSeidel": ([C.POINTER(spmat), C.POINTER(spmat), _vp], _i),
     "spmvHipAmgGaussSeidel": ([C.POINTER(spmat), C.c_uint, _vp], _i),
+    "spmvHipAmgSetBlockWidth": ([C.POINTER(spmat), C.POINTER(spmat), C.c_uint], _i),
+    "spmvHipAmgBlock": ([C.POINTER(spmat), _vp], _i),
+    "spmvHipAmgApplyBlock": ([C.POINTER(spmat), C.POINTER(spmat), C.c_uint, _vp, _sz, _i, _vp, _sz, _i], _i),
 }
 SPMV_DENSE_ROW_MAJOR, SPMV_DENSE_COL_MAJOR = 0, 1          # include/spmvHip.h: layouts of hipSpMMRowsCSR's X and Y
 SPMV_TRI_LOWER, SPMV_TRI_UPPER = 0, 1                      # include/spmvHip.h: hipSpTRSVCSR's uplo ...
@@ -331,6 +334,11 @@ class spmvAmgGsInfo(C.Structure):
     _fields_ = [("active", _i), ("colours", C.c_uint), ("maxColourRows", C.c_ulong), ("longRows", C.c_ulong), ("small", _i),
                 ("omega", C.c_double), ("order", _i), ("seed", C.c_uint32), ("oneWay", _i), ("dPerm", C.POINTER(C.c_uint32)),
                 ("dColourPtr", C.POINTER(C.c_uint32))]
+
+
+class spmvAmgBlockInfo(C.Structure):
+    """include/spmvHip.h `spmvAmgBlockInfo`: the width of a hierarchy's block workspace and its bytes (zeros: none)."""
+    _fields_ = [("width", C.c_uint), ("bytes", C.c_ulong)]
 
 
 SPMV_COLOUR_NATURAL, SPMV_COLOUR_HASH = 0, 1
@@ -1047,8 +1055,8 @@ class DeviceMatrix:
         """hipSpCGBlockCSR: k solves A x_c = b_c in lock step, column c of X with the bits of cg() on column c of B (and of
         X0), the matrix and the preconditioner's schedule streamed once per iteration for all columns.  B (and X0) are
         (N, k) float64: numpy arrays -> X as numpy; or device torch tensors with unit stride in one dimension (the rules
-        of matmul's X) -> X as a new torch tensor.  precond: None or a DeviceMatrix holding ILU(0) factors (a multigrid
-        hierarchy is refused).  Returns (X, info): info.columns the k spmvKrylovColumn records; info.history, when
+        of matmul's X) -> X as a new torch tensor.  precond: None, a DeviceMatrix holding ILU(0) factors, or this matrix's
+        multigrid hierarchy after set_block_width(width >= k) (without one it is refused).  Returns (X, info): info.columns the k spmvKrylovColumn records; info.history, when
         history=True, a list of k arrays hist[0 .. iterations_c]."""
         return self._krylov_block(lib.hipSpCGBlockCSR, "hipSpCGBlockCSR", B, X0, precond, tol, maxiter, history)
 
@@ -1110,7 +1118,7 @@ class DeviceMatrix:
 
 class AmgHierarchy(DeviceMatrix):
     """What DeviceMatrix.amg() returns: a hierarchy handle (no matrix: SpMV, formats and solves refuse it) with `info`
-    (spmvAmgInfo), apply(), refresh_from(), level(), prolongator(), strength(), set_smoother(), smoother(), set_gauss_seidel(),
+    (spmvAmgInfo), apply(), set_block_width(), block_info(), apply_block(), refresh_from(), level(), prolongator(), strength(), set_smoother(), smoother(), set_gauss_seidel(),
     gauss_seidel() and free().  It keeps a reference to its source matrix."""
 
     def __init__(self, source):
@@ -1126,6 +1134,31 @@ class AmgHierarchy(DeviceMatrix):
             ops.vector("r", r, N)
             ops.result("out", out, (N,))
             _check(lib.spmvHipAmgApply(C.byref(self.handle), C.byref(self.source.handle), *ops.args), "spmvHipAmgApply")
+            return ops.value()
+
+    def set_block_width(self, width):
+        """spmvHipAmgSetBlockWidth: the workspace of a block cycle for up to `width` columns (0 drops it); apply_block() and
+        cg_block / bicgstab_block(precond=this hierarchy) then take up to that many.  Updates `info` (its bytes count it)."""
+        _check(lib.spmvHipAmgSetBlockWidth(C.byref(self.handle), C.byref(self.source.handle), int(width)), "spmvHipAmgSetBlockWidth")
+        _check(lib.spmvHipAmgInfo(C.byref(self.handle), C.byref(self.info)), "spmvHipAmgInfo")
+
+    def block_info(self):
+        """spmvHipAmgBlock: the block workspace as a dict: width, bytes (zeros on a hierarchy without one)."""
+        v = spmvAmgBlockInfo()
+        _check(lib.spmvHipAmgBlock(C.byref(self.handle), C.byref(v)), "spmvHipAmgBlock")
+        return {"width": int(v.width), "bytes": int(v.bytes)}
+
+    def apply_block(self, R, out=None):
+        """spmvHipAmgApplyBlock: Z(:, c) = V(0, R(:, c)), one cycle for all columns, column c with the bits of apply() on
+        column c of R.  R is (M, k) float64 with k at most the width of set_block_width(): the operand rules of matmul (a
+        device torch tensor with unit stride in one dimension -> a torch tensor, `out` if given; or a numpy array -> numpy)."""
+        N = int(self.handle.M)
+        with _Operands("spmvHipAmgApplyBlock", R) as ops:
+            k, rl, ldr = ops.dense("R", R, N)
+            zl, ldz = ops.result("out", out, (N, k))
+            dr, dz = ops.args
+            _check(lib.spmvHipAmgApplyBlock(C.byref(self.handle), C.byref(self.source.handle), k, dr, ldr, rl, dz, ldz, zl),
+                   "spmvHipAmgApplyBlock")
             return ops.value()
 
     def refresh_from(self, source: "DeviceMatrix"):

@@ -8,8 +8,10 @@
 // allows, the same bits otherwise), each with the stop pointer of a Krylov loop.  A smoothing step is an SpMV into t_l and one
 // pass, damped Jacobi or Chebyshev alike: the launch count is the formula of the sweeps.  A Gauss-Seidel sweep is kernels of
 // this file: one launch per colour of the level, or one workgroup for a whole sweep of a small level.
+// The cycle for a block of vectors (spmvHipAmgApplyBlock, and the dM of the block solvers) is the same loop over row-major
+// blocks: SpMM passes and ops of the block pass (krylov_block.hpp), on a workspace that spmvHipAmgSetBlockWidth makes.
 // DESIGN.md sections 24 (the cycle), 28 (smoothed P, the fused correction), 29 (strength), 30 (Chebyshev), 31 (the recipe, the kinds),
-// 32 (Gauss-Seidel).
+// 32 (Gauss-Seidel), 33 (the block cycle).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <chrono>
@@ -19,6 +21,7 @@
 
 #include "device_prims.hpp"
 #include "krylov.hpp"
+#include "krylov_block.hpp"
 
 namespace spmvhip {
 
@@ -35,6 +38,8 @@ struct AmgLevel {
     double* dinv = nullptr;
     double *r = nullptr, *z = nullptr;  // below level 0: the restricted residual and the correction
     double *t = nullptr, *d = nullptr;
+    // the block cycle's workspace (null on a hierarchy without a block width): M x kp row-major blocks, br and bz below level 0
+    double *bt = nullptr, *bd = nullptr, *br = nullptr, *bz = nullptr;
     // Chebyshev: rho of A_l and dinv_l, the interval, and the nCoef pairs (a_k, b_k) on the device (null when nCoef = 0)
     double rhoS = 0.0, lmax = 0.0, lmin = 0.0;
     uint32_t nCoef = 0;
@@ -61,6 +66,8 @@ struct AmgHierarchy {
     int gsOrder = SPMV_COLOUR_NATURAL;
     uint32_t gsSeed = 0;
     bool gsOneWay = false;
+    uint32_t blockWidth = 0;                    // the columns a block cycle may take (spmvHipAmgSetBlockWidth; 0: none) ...
+    uint64_t blockBytes = 0;                    // ... and the bytes of its workspace, which info.bytes counts
     std::vector<AmgLevel> lv;
     spmvAmgInfo info{};
 };
@@ -230,6 +237,120 @@ struct AmgAddOp : StopMode {                    // z = z + d
     template <bool VEC> __device__ void load(uint64_t i, bool two, R& v) const { v.d = ld2<VEC>(d, i, two); v.z = ld2<VEC>(z, i, two); }
     template <bool VEC> __device__ void step(uint64_t i, bool two, const R& v, double&, double&) const {
         st2<VEC>(z, i, two, make_double2(v.z.x + v.d.x, v.z.y + v.d.y));
+    }
+};
+
+// ------------------------------------------------------------------------------------------------ the block cycle's passes
+// The passes above for a block of columns, as ops of the block pass (krylov_block.hpp): a lane holds the column pair
+// (c, c + 1) of a row, .x and .y of every double2, and computes each with exactly the arithmetic of the single form, so a
+// column never sees its neighbour.  dinv_l[i] and agg_l[i] belong to the row: one 8-byte (4-byte) load at an address that the
+// P lanes of the row share.  No per-column state: mode() reads the stop pointer alone.
+struct BStopMode {
+    const uint32_t* stop;
+    struct Sc {};
+    __device__ __forceinline__ int mode(int, const KState*, Sc&) const { return !(stop && *stop); }
+};
+struct BAmgZeroOp : BStopMode {                 // Z = +0.0
+    static constexpr int NDOT = 0;
+    static constexpr uint32_t CHUNK = 4;
+    BMat z;
+    struct R {};
+    __device__ __forceinline__ void load(uint64_t, uint32_t, bool, const Sc&, R&) const {}
+    __device__ __forceinline__ void step(uint64_t i, uint32_t c, int w0, int w1, const Sc&, const R&, Acc&) const {
+        stp(z, i, c, w0, w1, make_double2(0.0, 0.0));
+    }
+};
+struct BAmgFirstOp : BStopMode {                // Z = omega * (dinv * R)
+    static constexpr int NDOT = 0;
+    static constexpr uint32_t CHUNK = 4;
+    BMat r; const double* dinv; BMat z; double omega;
+    struct R { double2 r; double di; };
+    __device__ __forceinline__ void load(uint64_t i, uint32_t c, bool two, const Sc&, R& v) const { v.r = ldp(r, i, c, two); v.di = dinv[i]; }
+    __device__ __forceinline__ void step(uint64_t i, uint32_t c, int w0, int w1, const Sc&, const R& v, Acc&) const {
+        stp(z, i, c, w0, w1, make_double2(omega * (v.di * v.r.x), omega * (v.di * v.r.y)));
+    }
+};
+struct BAmgSweepOp : BStopMode {                // Z = Z + omega * (dinv * (R - T))
+    static constexpr int NDOT = 0;
+    static constexpr uint32_t CHUNK = 2;
+    BMat r, t; const double* dinv; BMat z; double omega;
+    struct R { double2 r, t, z; double di; };
+    __device__ __forceinline__ void load(uint64_t i, uint32_t c, bool two, const Sc&, R& v) const {
+        v.r = ldp(r, i, c, two); v.t = ldp(t, i, c, two); v.di = dinv[i]; v.z = ldp(z, i, c, two);
+    }
+    __device__ __forceinline__ void step(uint64_t i, uint32_t c, int w0, int w1, const Sc&, const R& v, Acc&) const {
+        stp(z, i, c, w0, w1, make_double2(v.z.x + omega * (v.di * (v.r.x - v.t.x)), v.z.y + omega * (v.di * (v.r.y - v.t.y))));
+    }
+};
+// (the pair (a_k, b_k) is loaded in load() with the slot's blocks, as in the single forms)
+template <bool FROM_Z>
+struct BAmgChebFirstOp : BStopMode {            // k = 0: D = b_0 * (dinv * R), Z = D; FROM_Z: D = b_0 * (dinv * (R - T)), Z = Z + D
+    static constexpr int NDOT = 0;
+    static constexpr uint32_t CHUNK = FROM_Z ? 2 : 4;
+    BMat r, t; const double* dinv; BMat d, z; const double2* cf;
+    struct R { double2 r, t, z, cf; double di; };
+    __device__ __forceinline__ void load(uint64_t i, uint32_t c, bool two, const Sc&, R& v) const {
+        v.cf = *cf;
+        v.r = ldp(r, i, c, two); v.di = dinv[i];
+        if (FROM_Z) { v.t = ldp(t, i, c, two); v.z = ldp(z, i, c, two); }
+    }
+    __device__ __forceinline__ void step(uint64_t i, uint32_t c, int w0, int w1, const Sc&, const R& v, Acc&) const {
+        const double b = v.cf.y;
+        if (FROM_Z) {
+            const double2 dn = make_double2(b * (v.di * (v.r.x - v.t.x)), b * (v.di * (v.r.y - v.t.y)));
+            stp(d, i, c, w0, w1, dn);
+            stp(z, i, c, w0, w1, make_double2(v.z.x + dn.x, v.z.y + dn.y));
+        } else {
+            const double2 dn = make_double2(b * (v.di * v.r.x), b * (v.di * v.r.y));
+            stp(d, i, c, w0, w1, dn);
+            stp(z, i, c, w0, w1, dn);
+        }
+    }
+};
+struct BAmgChebStepOp : BStopMode {             // k >= 1: D = a_k * D + b_k * (dinv * (R - T)), Z = Z + D
+    static constexpr int NDOT = 0;
+    static constexpr uint32_t CHUNK = 2;
+    BMat r, t; const double* dinv; BMat d, z; const double2* cf;
+    struct R { double2 r, t, d, z, cf; double di; };
+    __device__ __forceinline__ void load(uint64_t i, uint32_t c, bool two, const Sc&, R& v) const {
+        v.cf = *cf;
+        v.r = ldp(r, i, c, two); v.t = ldp(t, i, c, two); v.di = dinv[i]; v.d = ldp(d, i, c, two); v.z = ldp(z, i, c, two);
+    }
+    __device__ __forceinline__ void step(uint64_t i, uint32_t c, int w0, int w1, const Sc&, const R& v, Acc&) const {
+        const double2 ab = v.cf;
+        const double2 dn = make_double2(ab.x * v.d.x + ab.y * (v.di * (v.r.x - v.t.x)), ab.x * v.d.y + ab.y * (v.di * (v.r.y - v.t.y)));
+        stp(d, i, c, w0, w1, dn);
+        stp(z, i, c, w0, w1, make_double2(v.z.x + dn.x, v.z.y + dn.y));
+    }
+};
+struct BAmgResidOp : BStopMode {                // D = R - T
+    static constexpr int NDOT = 0;
+    static constexpr uint32_t CHUNK = 4;
+    BMat r, t, d;
+    struct R { double2 r, t; };
+    __device__ __forceinline__ void load(uint64_t i, uint32_t c, bool two, const Sc&, R& v) const { v.r = ldp(r, i, c, two); v.t = ldp(t, i, c, two); }
+    __device__ __forceinline__ void step(uint64_t i, uint32_t c, int w0, int w1, const Sc&, const R& v, Acc&) const {
+        stp(d, i, c, w0, w1, make_double2(v.r.x - v.t.x, v.r.y - v.t.y));
+    }
+};
+struct BAmgCorrectOp : BStopMode {              // Z(i, :) = Z(i, :) + E(agg[i], :): row agg[i] of E, a contiguous run per lane group
+    static constexpr int NDOT = 0;
+    static constexpr uint32_t CHUNK = 4;
+    BMat e; const uint32_t* agg; BMat z;
+    struct R { double2 z, e; };
+    __device__ __forceinline__ void load(uint64_t i, uint32_t c, bool two, const Sc&, R& v) const { v.z = ldp(z, i, c, two); v.e = ldp(e, agg[i], c, two); }
+    __device__ __forceinline__ void step(uint64_t i, uint32_t c, int w0, int w1, const Sc&, const R& v, Acc&) const {
+        stp(z, i, c, w0, w1, make_double2(v.z.x + v.e.x, v.z.y + v.e.y));
+    }
+};
+struct BAmgAddOp : BStopMode {                  // Z = Z + D
+    static constexpr int NDOT = 0;
+    static constexpr uint32_t CHUNK = 4;
+    BMat d, z;
+    struct R { double2 d, z; };
+    __device__ __forceinline__ void load(uint64_t i, uint32_t c, bool two, const Sc&, R& v) const { v.d = ldp(d, i, c, two); v.z = ldp(z, i, c, two); }
+    __device__ __forceinline__ void step(uint64_t i, uint32_t c, int w0, int w1, const Sc&, const R& v, Acc&) const {
+        stp(z, i, c, w0, w1, make_double2(v.z.x + v.d.x, v.z.y + v.d.y));
     }
 };
 
@@ -564,7 +685,7 @@ void freeAmg(AmgHierarchy* h) {
     for (AmgLevel& l : h->lv) {
         for (spmat* m : {&l.A, &l.P, &l.R, &l.AP, &l.T, &l.D, &l.AT, &l.DAT, &l.F})
             if (m->dev) (void)hipFreeSpmat(m);
-        for (double* p : {l.dinv, l.r, l.z, l.t, l.d, l.dF}) (void)hipFree(p);
+        for (double* p : {l.dinv, l.r, l.z, l.t, l.d, l.dF, l.bt, l.bd, l.br, l.bz}) (void)hipFree(p);
         (void)hipFree(l.coef);
         (void)hipFree(l.perm);
         (void)hipFree(l.colourPtr);
@@ -761,6 +882,116 @@ int enqueueAmgCycle(const DevMat* m, spmat* hA, const double* r0, double* z0, hi
     }
     if (launches) *launches += n;
     return hipGetLastError() == hipSuccess ? EXIT_SUCCESS : EXIT_FAILURE;
+}
+
+// The loop of enqueueAmgCycle for k columns at once: every A_l z, R_l d and P_l e one SpMM pass on the
+// level's handle, every vector pass one block launch.  R0 and Z0 are the caller's blocks with their strides; everything
+// below is the hierarchy's block workspace with the row stride kp of THIS k (k <= the width, so it fits).  A smoothed
+// correction is always the product into d_l and an add: the launch count is the header's formula with no level fused.
+int enqueueAmgCycleBlock(const DevMat* m, const DevMat* a0, uint32_t k, const double* R0, uint64_t srr, uint64_t src, double* Z0, uint64_t szr,
+                         uint64_t szc, hipStream_t st, const uint32_t* stop, unsigned long* launches) {
+    AmgHierarchy* H = m->amg;
+    const size_t nl = H->lv.size();
+    const double om = H->omega;
+    const uint32_t kp = k + (k & 1);
+    unsigned long n = 0;
+    auto ws = [&](double* p) { return bmat(p, kp, 1, k, true); };
+    auto pass = [&](uint64_t rows, const auto& op) {
+        launchBlockVec(rows, k, nullptr, op, nullptr, nullptr, st);
+        ++n;
+    };
+    auto spmm = [&](const DevMat* h, const BMat& x, const BMat& y) {
+        ++n;
+        return h->M ? enqueueSpmm(h, k, x.p, x.sr, x.sc, y.p, y.sr, y.sc, st) : EXIT_SUCCESS;
+    };
+    auto matAt = [&](size_t l) { return l ? matOf(&H->lv[l].A) : a0; };
+    const bool cheb = H->smoother == SPMV_AMG_SMOOTHER_CHEBYSHEV;
+    const BMat none{};
+    auto smooth = [&](size_t l, const BMat& r, const BMat& z, uint32_t q, bool fromNothing) {
+        AmgLevel& L = H->lv[l];
+        const BMat t = ws(L.bt), d = ws(L.bd);
+        if (q == 0 && fromNothing) pass(L.M, BAmgZeroOp{{stop}, z});
+        for (uint32_t j = 0; j < q; ++j) {
+            const bool first = j == 0 && fromNothing;
+            if (!first && spmm(matAt(l), z, t)) return EXIT_FAILURE;
+            if (!cheb && first) pass(L.M, BAmgFirstOp{{stop}, r, L.dinv, z, om});
+            else if (!cheb) pass(L.M, BAmgSweepOp{{stop}, r, t, L.dinv, z, om});
+            else if (j) pass(L.M, BAmgChebStepOp{{stop}, r, t, L.dinv, d, z, L.coef + j});
+            else if (first) pass(L.M, BAmgChebFirstOp<false>{{stop}, r, none, L.dinv, d, z, L.coef});
+            else pass(L.M, BAmgChebFirstOp<true>{{stop}, r, t, L.dinv, d, z, L.coef});
+        }
+        return EXIT_SUCCESS;
+    };
+    const BMat r0 = bmat(R0, srr, src, k, false), z0 = bmat(Z0, szr, szc, k, false);
+    for (size_t l = 0; l < nl; ++l) {                          // down
+        AmgLevel& L = H->lv[l];
+        const BMat r = l ? ws(L.br) : r0, z = l ? ws(L.bz) : z0, t = ws(L.bt), d = ws(L.bd);
+        const bool last = l + 1 == nl;
+        if (smooth(l, r, z, last ? H->nuCoarse : H->nu1, true)) return EXIT_FAILURE;
+        if (last) break;
+        if (spmm(matAt(l), z, t)) return EXIT_FAILURE;
+        pass(L.M, BAmgResidOp{{stop}, r, t, d});
+        if (spmm(matOf(&L.R), d, ws(H->lv[l + 1].br))) return EXIT_FAILURE;
+    }
+    for (size_t l = nl - 1; l-- > 0;) {                        // up
+        AmgLevel& L = H->lv[l];
+        const BMat r = l ? ws(L.br) : r0, z = l ? ws(L.bz) : z0, d = ws(L.bd), e = ws(H->lv[l + 1].bz);
+        if (!H->smoothed()) pass(L.M, BAmgCorrectOp{{stop}, e, L.agg, z});
+        else {                                                 // (d is free: the restriction consumed it)
+            if (spmm(matOf(&L.P), e, d)) return EXIT_FAILURE;
+            pass(L.M, BAmgAddOp{{stop}, d, z});
+        }
+        if (smooth(l, r, z, H->nu2, false)) return EXIT_FAILURE;
+    }
+    if (launches) *launches += n;
+    return hipGetLastError() == hipSuccess ? EXIT_SUCCESS : EXIT_FAILURE;
+}
+
+// the workspace of a block cycle for up to `width` columns (0: none).  Everything new is made before anything old is
+// dropped; the stream is synchronised in between, so no cycle in flight uses a block that goes.
+int amgSetBlockWidth(DevMat* m, uint32_t width, hipStream_t st) {
+    AmgHierarchy* H = m->amg;
+    const size_t nl = H->lv.size();
+    const uint64_t kp = (uint64_t)width + (width & 1);
+    std::vector<double*> nw(4 * nl, nullptr);                  // t, d, r, z of every level
+    auto drop = [&]() { for (double* p : nw) (void)hipFree(p); return EXIT_FAILURE; };
+    uint64_t bytes = 0;
+    if (width) {
+        if (H->lv[0].M && kp > UINT64_MAX / 8 / H->lv[0].M) {
+            fprintf(stderr, "libspmvhip: multigrid block width: %lu rows x %lu columns x 8 bytes do not fit 64 bits\n", (unsigned long)H->lv[0].M,
+                    (unsigned long)kp);
+            return EXIT_FAILURE;
+        }
+        for (size_t l = 0; l < nl; ++l) {
+            const uint64_t one = H->lv[l].M * kp * 8;
+            for (size_t v = 0; v < (l ? 4u : 2u); ++v) {
+                if (hipMalloc(&nw[4 * l + v], std::max<uint64_t>(one, 16)) != hipSuccess) {
+                    (void)hipGetLastError();
+                    fprintf(stderr, "libspmvhip: multigrid block width: allocation of level %zu's %lu-byte block failed\n", l, (unsigned long)one);
+                    return drop();
+                }
+                bytes += one;
+            }
+        }
+    }
+    if (hipStreamSynchronize(st) != hipSuccess) return drop();
+    for (size_t l = 0; l < nl; ++l) {
+        AmgLevel& L = H->lv[l];
+        for (double* p : {L.bt, L.bd, L.br, L.bz}) (void)hipFree(p);
+        L.bt = nw[4 * l]; L.bd = nw[4 * l + 1]; L.br = nw[4 * l + 2]; L.bz = nw[4 * l + 3];
+    }
+    H->info.bytes = H->info.bytes - H->blockBytes + bytes;
+    H->blockBytes = bytes;
+    H->blockWidth = width;
+    return EXIT_SUCCESS;
+}
+
+void amgBlockState(const DevMat* m, uint32_t* width, uint64_t* bytes, bool* gaussSeidel) {
+    const AmgHierarchy* H = m->amg;
+    *width = H->blockWidth;
+    *bytes = H->blockBytes;
+    *gaussSeidel = false;
+    for (const AmgLevel& L : H->lv) *gaussSeidel = *gaussSeidel || L.perm != nullptr;
 }
 
 // a level's Gauss-Seidel lists go, with their bytes (the stream is synchronised: no cycle in flight reads them)

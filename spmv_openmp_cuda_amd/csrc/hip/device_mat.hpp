@@ -255,6 +255,15 @@ int  amgBuild(spmat* hA, const spmvAmgOpts* opts, const AmgPlan& plan, DevMat* m
 int  amgRefresh(DevMat* m, spmat* hA, hipStream_t stream);
 int  enqueueAmgCycle(const DevMat* m, spmat* hA, const double* r, double* z, hipStream_t stream, const uint32_t* stop,
                      unsigned long* launches);
+// The block cycle.  amgSetBlockWidth: the workspace of a cycle for up to `width` columns, 0 drops it
+// (synchronous, allocates; a failure leaves the hierarchy as it was).  amgBlockState: the width, the workspace's bytes, and
+// whether a level sweeps by colours (which the block cycle does not).  enqueueAmgCycleBlock: Z(:, c) = V(0, R(:, c)) for
+// c < k <= the width on a hierarchy without a Gauss-Seidel level, a0 its source; R and Z with element strides; kernels
+// only, `stop` and `launches` as in enqueueAmgCycle (an SpMM pass of any width counted as one).
+int  amgSetBlockWidth(DevMat* m, uint32_t width, hipStream_t stream);
+void amgBlockState(const DevMat* m, uint32_t* width, uint64_t* bytes, bool* gaussSeidel);
+int  enqueueAmgCycleBlock(const DevMat* m, const DevMat* a0, uint32_t k, const double* R, uint64_t srr, uint64_t src, double* Z, uint64_t szr,
+                          uint64_t szc, hipStream_t stream, const uint32_t* stop, unsigned long* launches);
 const spmvAmgInfo* amgInfo(const DevMat* m);
 void amgLevel(const DevMat* m, unsigned level, spmat* dAl, const uint32_t** dAgg, const double** dDinv);
 void amgProlongator(const DevMat* m, unsigned level, spmat* dPl, spmat* dRl, double* omegaP);

@@ -10,7 +10,7 @@
 // finish kernel sets when the last column stops is what the host reads once per K iterations and what the triangular
 // passes take as their stop pointer.
 //
-// The fused passes.  The working vectors are row-major n x kp blocks, kp = k rounded up to even, so a row's column pair
+// The fused passes (the kernel and its launcher are krylov_block.hpp, which amg.hip shares; the ops are here).  The working vectors are row-major n x kp blocks, kp = k rounded up to even, so a row's column pair
 // (c, c + 1), c even, is one 16-byte access; B and X are read and written where the caller keeps them, in 16-byte accesses
 // when their layout allows and in 8-byte ones otherwise (the same bits).  A workgroup of 256 lanes takes one block of 4096
 // rows and one panel of at most 16 columns.  P adjacent lanes hold the panel's P column pairs (P = 1, 2, 4 or 8, from the
@@ -28,11 +28,10 @@
 #include "spmvHip.h"
 #include "kernels.hpp"
 #include "krylov.hpp"
+#include "krylov_block.hpp"
 
 namespace spmvhip {
 namespace {
-
-constexpr uint32_t BK_PANEL = 16;               // columns of a panel (the convention of spmm.hip and trsm.hip)
 
 // what the host reads once per batch and the triangular passes take as their stop pointer
 struct BlockHead {
@@ -40,34 +39,6 @@ struct BlockHead {
     uint32_t stopped;       // columns that have stopped (one ordinary atomicAdd by the lane that stops a column)
 };
 
-// a dense block: element (i, c) at p[i*sr + c*sc]; pair: columns (c, c + 1), c even, of a row are one aligned 16-byte access
-struct BMat {
-    double* p; uint64_t sr, sc; int pair;
-};
-BMat bmat(const double* p, uint64_t sr, uint64_t sc, uint32_t k, bool padded) {
-    // a caller's block has no element behind column k - 1: with k odd its last pair is not there to be loaded
-    const bool pair = sc == 1 && sr % 2 == 0 && aligned16(p) && (padded || k % 2 == 0);
-    return BMat{const_cast<double*>(p), sr, sc, pair};
-}
-
-__device__ __forceinline__ double2 ldp(const BMat& m, uint64_t i, uint32_t c, bool two) {
-    const double* q = m.p + i * m.sr + c * m.sc;
-    if (m.pair) return *reinterpret_cast<const double2*>(q);
-    return make_double2(q[0], two ? q[m.sc] : 0.0);
-}
-// columns c (w0) and c + 1 (w1) of row i
-__device__ __forceinline__ void stp(const BMat& m, uint64_t i, uint32_t c, int w0, int w1, double2 v) {
-    double* q = m.p + i * m.sr + c * m.sc;
-    if (m.pair && w0 && w1) { *reinterpret_cast<double2*>(q) = v; return; }
-    if (w0) q[0] = v.x;
-    if (w1) q[m.sc] = v.y;
-}
-
-// the partials of a column pair: d0 / d1 the op's first / second dot, .x column c, .y column c + 1
-struct Acc { double2 d0, d1; };
-__device__ __forceinline__ Acc accAdd(const Acc& m, const Acc& o) {
-    return Acc{make_double2(m.d0.x + o.d0.x, m.d0.y + o.d0.y), make_double2(m.d1.x + o.d1.x, m.d1.y + o.d1.y)};
-}
 __device__ __forceinline__ void madd2(double2& acc, double2 a, double2 b) { acc.x += a.x * b.x; acc.y += a.y * b.y; }
 __device__ __forceinline__ double2 axpy2(double2 a, double2 s, double2 v) { return make_double2(a.x + s.x * v.x, a.y + s.y * v.y); }
 __device__ __forceinline__ double2 axmy2(double2 a, double2 s, double2 v) { return make_double2(a.x - s.x * v.x, a.y - s.y * v.y); }
@@ -222,83 +193,6 @@ struct BBiUpdateOp {
     }
 };
 
-// "lane t" of the dot's contract for one column pair: rows base + 512 s + 2 t and + 1 for s = 0 .. 7, in that order from +0.0
-template <class Op>
-__device__ __forceinline__ Acc lane_partial(const Op& op, const typename Op::Sc sc, uint64_t n, uint64_t base, uint32_t t, uint32_t c, bool two, int w0, int w1) {
-    Acc a{make_double2(0.0, 0.0), make_double2(0.0, 0.0)};
-    if (!(w0 | w1)) return a;
-    const uint64_t first = base + 2 * t;
-#pragma unroll
-    for (uint32_t s = 0; s < KSLICES; s += Op::CHUNK) {
-        typename Op::R r[Op::CHUNK][2];
-#pragma unroll
-        for (uint32_t u = 0; u < Op::CHUNK; ++u) {
-            const uint64_t i = first + (uint64_t)(s + u) * (2 * KT);
-            if (i < n) op.load(i, c, two, sc, r[u][0]);
-            if (i + 1 < n) op.load(i + 1, c, two, sc, r[u][1]);
-        }
-#pragma unroll
-        for (uint32_t u = 0; u < Op::CHUNK; ++u) {
-            const uint64_t i = first + (uint64_t)(s + u) * (2 * KT);
-            if (i < n) op.step(i, c, w0, w1, sc, r[u][0], a);
-            if (i + 1 < n) op.step(i + 1, c, w0, w1, sc, r[u][1], a);
-        }
-    }
-    return a;
-}
-
-// the tree's levels h = 128 ... 256 / P on the partials t = g + (256 / P) j of one lane group: a[j] += a[j + S'] for
-// S' = P / 2 ... 1, written depth first so that only one partial per level is alive
-template <class Op, int P, int S>
-__device__ __forceinline__ Acc group_partial(const Op& op, const typename Op::Sc sc, uint64_t n, uint64_t base, uint32_t g, uint32_t j, uint32_t c, bool two,
-                                             int w0, int w1) {
-    if constexpr (S >= P) {
-        return lane_partial(op, sc, n, base, g + (KT / P) * j, c, two, w0, w1);
-    } else {
-        const Acc m = group_partial<Op, P, 2 * S>(op, sc, n, base, g, j, c, two, w0, w1);
-        const Acc o = group_partial<Op, P, 2 * S>(op, sc, n, base, g, j + S, c, two, w0, w1);
-        return accAdd(m, o);
-    }
-}
-
-// one block of KB rows and one panel of columns: the op's update on them, and its dots' block partials into
-// part0 / part1[blk * kp + column]
-template <class Op, int P>
-__global__ __launch_bounds__(KT) void block_vec_kernel(uint64_t n, uint32_t k, uint32_t kp, uint32_t panels,
-                                                       const KState* __restrict__ st, const Op op, double* __restrict__ part0,
-                                                       double* __restrict__ part1) {
-    static_assert(P == 1 || P == 2 || P == 4 || P == 8, "column pairs of a panel");
-    __shared__ Acc sh[KT];
-    const uint64_t lin = linear_block();
-    const uint64_t blk = lin / panels;
-    if (blk * KB >= n) return;                                           // (a folded grid's tail)
-    const uint32_t tid = threadIdx.x;
-    const uint32_t c = (uint32_t)(lin % panels) * BK_PANEL + 2 * (tid % P);
-    typename Op::Sc sc{};                                                // the scalars of this lane's two columns
-    const int w0 = c < k ? op.mode(0, st + c, sc) : 0;
-    const int w1 = c + 1 < k ? op.mode(1, st + c + 1, sc) : 0;
-    if (!__syncthreads_or(w0 | w1)) return;                              // every column of this panel has stopped
-    Acc a = group_partial<Op, P, 1>(op, sc, n, blk * KB, tid / P, 0, c, c + 1 < k, w0, w1);
-    if (Op::NDOT == 0) return;
-    sh[tid] = a;
-    __syncthreads();
-#pragma unroll
-    for (uint32_t h = KT / 2; h >= P; h >>= 1) {
-        if (tid < h) sh[tid] = accAdd(sh[tid], sh[tid + h]);
-        __syncthreads();
-    }
-    if (tid >= P) return;
-    a = sh[tid];
-    double* q0 = part0 + blk * kp + c;
-    if (w0) q0[0] = a.d0.x;
-    if (w1) q0[1] = a.d0.y;
-    if (Op::NDOT > 1) {
-        double* q1 = part1 + blk * kp + c;
-        if (w0) q1[0] = a.d1.x;
-        if (w1) q1[1] = a.d1.y;
-    }
-}
-
 // column c = the workgroup: its block partials by the dot's second level (lane t adds partials t, t + 256, ... in order,
 // then the tree), then lane 0 runs the column's scalar step `ph` of iteration it -- or stores the dot (F_DOT)
 __global__ __launch_bounds__(KT) void block_finish_kernel(uint64_t nb, uint32_t k, uint32_t kp, const double* __restrict__ part0,
@@ -321,19 +215,6 @@ __global__ __launch_bounds__(KT) void block_finish_kernel(uint64_t nb, uint32_t 
     // the column ran (or starts) and has now stopped: it is counted once, and the last one sets the head word, which
     // later launches read -- ordering comes from the kernel boundary
     if (s->stop && atomicAdd(&head->stopped, 1u) + 1 == k) head->allStop = 1;
-}
-
-template <class Op>
-void launchBlockVec(uint64_t n, uint32_t k, const KState* st, const Op& op, double* p0, double* p1, hipStream_t s) {
-    const uint64_t nb = blocksOf(n);
-    if (!nb) return;
-    const uint32_t kp = k + (k & 1), panels = (k + BK_PANEL - 1) / BK_PANEL;
-    const uint32_t w = k < BK_PANEL ? k : BK_PANEL;                      // the widest panel
-    const dim3 grid = grid2d(nb * panels, KT);
-    if (w <= 2)      hipLaunchKernelGGL((block_vec_kernel<Op, 1>), grid, dim3(KT), 0, s, n, k, kp, panels, st, op, p0, p1);
-    else if (w <= 4) hipLaunchKernelGGL((block_vec_kernel<Op, 2>), grid, dim3(KT), 0, s, n, k, kp, panels, st, op, p0, p1);
-    else if (w <= 8) hipLaunchKernelGGL((block_vec_kernel<Op, 4>), grid, dim3(KT), 0, s, n, k, kp, panels, st, op, p0, p1);
-    else             hipLaunchKernelGGL((block_vec_kernel<Op, 8>), grid, dim3(KT), 0, s, n, k, kp, panels, st, op, p0, p1);
 }
 
 void launchBlockFinish(uint64_t n, uint32_t k, const double* p0, const double* p1, int ph, uint64_t it, KState* st, BlockHead* head,
@@ -390,11 +271,13 @@ int krylovBlockSolve(int bicg, const DevMat* a, const DevMat* m, uint32_t k, con
     HIP_TRY(hipMemcpyAsync(head, &hh, sizeof hh, hipMemcpyHostToDevice, s));
     const BMat b = bmat(B, sbr, sbc, k, false), x = bmat(X, sxr, sxc, k, false);
     unsigned long triLaunches = 0;
-    if (pre) {
+    const bool cycle = pre && m->origin == Origin::HIERARCHY;            // M^-1 is a block cycle of the hierarchy (its width is >= k)
+    if (pre && !cycle) {
         spmvTriInfo t{};
         for (int uplo : {SPMV_TRI_LOWER, SPMV_TRI_UPPER}) { triInfo(m, uplo, &t); triLaunches += t.launches; }
     }
-    auto precond = [&](const BMat& in, const BMat& outv) {                // z = U^-1 (L^-1 in), every launch behind the head word
+    auto precond = [&](const BMat& in, const BMat& outv) {                // z = U^-1 (L^-1 in), or one cycle: every launch behind the head word
+        if (cycle) return enqueueAmgCycleBlock(m, a, k, in.p, kp, 1, outv.p, kp, 1, s, &head->allStop, &out.launches);
         dim3 g, bl;
         if (enqueueTrsm(m, SPMV_TRI_LOWER, SPMV_DIAG_UNIT, k, in.p, kp, 1, outv.p, kp, true, s, &g, &bl, &head->allStop)) return EXIT_FAILURE;
         if (enqueueTrsm(m, SPMV_TRI_UPPER, SPMV_DIAG_STORED, k, outv.p, kp, 1, outv.p, kp, true, s, &g, &bl, &head->allStop)) return EXIT_FAILURE;

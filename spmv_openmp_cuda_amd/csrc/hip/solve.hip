@@ -310,6 +310,78 @@ int spmvHipAmgApply(spmat* dM, spmat* dA, const double* dR, double* dZ) {
     return L.finish(who);
 }
 
+// ---- the block cycle (contract in spmvHip.h, design in DESIGN.md section 33)
+// a dense rows x k operand: its layout and leading dimension
+static bool denseOk(const char* who, const char* name, uint64_t rows, unsigned k, size_t ld, int layout) {
+    if (layout != SPMV_DENSE_ROW_MAJOR && layout != SPMV_DENSE_COL_MAJOR) { ERR("%s: unknown layout %d", who, layout); return false; }
+    const uint64_t need = layout == SPMV_DENSE_ROW_MAJOR ? k : rows;     // ld >= k (row-major) or >= the rows (column-major)
+    if (ld < need) { ERR("%s: leading dimension %s = %zu is below %lu", who, name, ld, (unsigned long)need); return false; }
+    return true;
+}
+
+// the hierarchy m cannot run a block cycle of k columns: the line says why
+static bool blockCycleRefused(const DevMat* m, unsigned k, const char* who) {
+    uint32_t width = 0;
+    uint64_t bytes = 0;
+    bool gs = false;
+    amgBlockState(m, &width, &bytes, &gs);
+    if (width < k) {
+        ERR("%s: dM is a multigrid hierarchy with a block workspace of width %u, k = %u columns: spmvHipAmgSetBlockWidth(dM, dA, width >= k) gives "
+            "it one (without, its cycle takes one vector at a time)", who, width, k);
+        return true;
+    }
+    if (gs) {
+        ERR("%s: dM is a multigrid hierarchy with a Gauss-Seidel level: the block cycle has no colour sweeps (spmvHipAmgSetSmoother with JACOBI "
+            "or CHEBYSHEV first; the width is kept)", who);
+        return true;
+    }
+    return false;
+}
+
+int spmvHipAmgSetBlockWidth(spmat* dM, spmat* dA, unsigned width) {
+    const char* who = "spmvHipAmgSetBlockWidth";
+    DevMat* a = nullptr;
+    DevMat* m = hierarchyOf(dM, dA, who, &a);
+    if (!m) return EXIT_FAILURE;
+    if (amgSetBlockWidth(m, width, S.stream)) { ERR("%s: the block workspace was not set", who); return EXIT_FAILURE; }
+    return EXIT_SUCCESS;
+}
+
+int spmvHipAmgBlock(spmat* dM, spmvAmgBlockInfo* info) {
+    DevMat* m = hierarchyLevel(dM, "spmvHipAmgBlock", 0, nullptr, !info);
+    if (!m) return EXIT_FAILURE;
+    uint32_t width = 0;
+    uint64_t bytes = 0;
+    bool gs = false;
+    amgBlockState(m, &width, &bytes, &gs);
+    *info = spmvAmgBlockInfo{width, (ulong)bytes};
+    return EXIT_SUCCESS;
+}
+
+int spmvHipAmgApplyBlock(spmat* dM, spmat* dA, unsigned k, const double* dR, size_t ldr, int rLayout, double* dZ, size_t ldz, int zLayout) {
+    const char* who = "spmvHipAmgApplyBlock";
+    const Ctx cx = libraryCtx();
+    DevMat* a = nullptr;
+    DevMat* m = hierarchyOf(dM, dA, who, &a);
+    if (!m) return EXIT_FAILURE;
+    if (!dR || !dZ) { ERR("%s: %s is NULL", who, !dR ? "dR" : "dZ"); return EXIT_FAILURE; }
+    if (a->M != m->M) { ERR("%s: dA has %lu rows, dM %lu", who, (unsigned long)a->M, (unsigned long)m->M); return EXIT_FAILURE; }
+    if (k == 0) { ERR("%s: k = 0 columns", who); return EXIT_FAILURE; }
+    if (!denseOk(who, "ldr", m->M, k, ldr, rLayout) || !denseOk(who, "ldz", m->M, k, ldz, zLayout)) return EXIT_FAILURE;
+    const unsigned __int128 spanR = denseSpan(m->M, k, ldr, rLayout), spanZ = denseSpan(m->M, k, ldz, zLayout);
+    const unsigned __int128 r0 = (uintptr_t)dR, z0 = (uintptr_t)dZ;
+    if (spanR && spanZ && r0 < z0 + spanZ && z0 < r0 + spanR) { ERR("%s: dR and dZ overlap", who); return EXIT_FAILURE; }
+    if (blockCycleRefused(m, k, who)) return EXIT_FAILURE;
+    if (m->M == 0) return nothingToLaunch(cx, m, nullptr);
+    const bool rRow = rLayout == SPMV_DENSE_ROW_MAJOR, zRow = zLayout == SPMV_DENSE_ROW_MAJOR;
+    Launch L(cx, grid2d((m->M + KB - 1) / KB * ((k + 15) / 16), KT), dim3(KT));
+    if (enqueueAmgCycleBlock(m, a, k, dR, rRow ? ldr : 1, rRow ? 1 : ldr, dZ, zRow ? ldz : 1, zRow ? 1 : ldz, cx.stream, nullptr, nullptr)) {
+        ERR("%s: launch failed", who);
+        return EXIT_FAILURE;
+    }
+    return L.finish(who);
+}
+
 int spmvHipAmgInfo(spmat* dM, spmvAmgInfo* info) {
     DevMat* m = hierarchyLevel(dM, "spmvHipAmgInfo", 0, nullptr, !info);
     if (!m) return EXIT_FAILURE;
@@ -443,14 +515,6 @@ int hipSpCGCSR(spmat* dA, spmat* dM, const double* dB, double* dX, const spmvKry
 int hipSpBiCGStabCSR(spmat* dA, spmat* dM, const double* dB, double* dX, const spmvKrylovOpts* opts, spmvKrylovInfo* info) { return krylov(1, dA, dM, dB, dX, opts, info); }
 
 // ---- blocks of right-hand sides (contract in spmvHip.h, design in DESIGN.md section 27)
-// a dense rows x k operand: its layout and leading dimension
-static bool denseOk(const char* who, const char* name, uint64_t rows, unsigned k, size_t ld, int layout) {
-    if (layout != SPMV_DENSE_ROW_MAJOR && layout != SPMV_DENSE_COL_MAJOR) { ERR("%s: unknown layout %d", who, layout); return false; }
-    const uint64_t need = layout == SPMV_DENSE_ROW_MAJOR ? k : rows;     // ld >= k (row-major) or >= the rows (column-major)
-    if (ld < need) { ERR("%s: leading dimension %s = %zu is below %lu", who, name, ld, (unsigned long)need); return false; }
-    return true;
-}
-
 int spmvHipBlockDot(size_t n, unsigned k, const double* dU, size_t ldu, int uLayout, const double* dV, size_t ldv, int vLayout,
                     double* dH) {
     const char* who = "spmvHipBlockDot";
@@ -475,10 +539,8 @@ static int krylovBlock(int bicg, spmat* dA, spmat* dM, unsigned k, const double*
     if (k == 0) { ERR("%s: k = 0 columns", who); return EXIT_FAILURE; }
     if (dM && dM->dev && dM->dev != SPMAT_TAG_ELL_TRANSPOSED) {
         const DevMat* h = anyDescOf(dM, who);
-        if (h && h->origin == Origin::HIERARCHY) {
-            ERR("%s: dM is a multigrid hierarchy: its cycle takes one vector at a time (hipSpCGCSR / hipSpBiCGStabCSR take it)", who);
-            return EXIT_FAILURE;
-        }
+        // a hierarchy is taken when it has the workspace of a block cycle of k columns (spmvHipAmgSetBlockWidth)
+        if (h && h->origin == Origin::HIERARCHY && blockCycleRefused(h, k, who)) return EXIT_FAILURE;
     }
     DevMat* a = nullptr;
     DevMat* m = nullptr;
