@@ -885,24 +885,24 @@ int enqueueAmgCycle(const DevMat* m, spmat* hA, const double* r0, double* z0, hi
 }
 
 // The loop of enqueueAmgCycle for k columns at once: every A_l z, R_l d and P_l e one SpMM pass on the
-// level's handle, every vector pass one block launch.  R0 and Z0 are the caller's blocks with their strides; everything
+// level's handle, every vector pass one block launch.  R0 and Z0 are the caller's blocks; everything
 // below is the hierarchy's block workspace with the row stride kp of THIS k (k <= the width, so it fits).  A smoothed
 // correction is always the product into d_l and an add: the launch count is the header's formula with no level fused.
-int enqueueAmgCycleBlock(const DevMat* m, const DevMat* a0, uint32_t k, const double* R0, uint64_t srr, uint64_t src, double* Z0, uint64_t szr,
-                         uint64_t szc, hipStream_t st, const uint32_t* stop, unsigned long* launches) {
+int enqueueAmgCycleBlock(const DevMat* m, const DevMat* a0, uint32_t k, const Dense& R0, const Dense& Z0, hipStream_t st, const uint32_t* stop,
+                         unsigned long* launches) {
     AmgHierarchy* H = m->amg;
     const size_t nl = H->lv.size();
     const double om = H->omega;
     const uint32_t kp = k + (k & 1);
     unsigned long n = 0;
-    auto ws = [&](double* p) { return bmat(p, kp, 1, k, true); };
+    auto ws = [&](double* p) { return bmat(Dense{p, kp, true}, k, true); };
     auto pass = [&](uint64_t rows, const auto& op) {
         launchBlockVec(rows, k, nullptr, op, nullptr, nullptr, st);
         ++n;
     };
     auto spmm = [&](const DevMat* h, const BMat& x, const BMat& y) {
         ++n;
-        return h->M ? enqueueSpmm(h, k, x.p, x.sr, x.sc, y.p, y.sr, y.sc, st) : EXIT_SUCCESS;
+        return h->M ? enqueueSpmm(h, k, dense(x), dense(y), st) : EXIT_SUCCESS;
     };
     auto matAt = [&](size_t l) { return l ? matOf(&H->lv[l].A) : a0; };
     const bool cheb = H->smoother == SPMV_AMG_SMOOTHER_CHEBYSHEV;
@@ -922,7 +922,7 @@ int enqueueAmgCycleBlock(const DevMat* m, const DevMat* a0, uint32_t k, const do
         }
         return EXIT_SUCCESS;
     };
-    const BMat r0 = bmat(R0, srr, src, k, false), z0 = bmat(Z0, szr, szc, k, false);
+    const BMat r0 = bmat(R0, k, false), z0 = bmat(Z0, k, false);
     for (size_t l = 0; l < nl; ++l) {                          // down
         AmgLevel& L = H->lv[l];
         const BMat r = l ? ws(L.br) : r0, z = l ? ws(L.bz) : z0, t = ws(L.bt), d = ws(L.bd);

@@ -227,6 +227,14 @@ int  filterRefresh(DevMat* c, const DevMat* a, hipStream_t stream);
 const spmvFilterInfo* filterInfo(const DevMat* c);
 void filterSetMaxRow(DevMat* c);
 void freeFilterPlan(FilterPlan* p);
+// A dense rows x k block of doubles in the form the C boundary is given, checked there (lib.hpp: denseOperand, denseShare):
+// element (i, c) at p[i*ld + c] (rowMajor) or p[c*ld + i].  Every block launcher below takes its operands as this; one that
+// only reads takes the same type.  A solver's own n x kp workspace block is Dense{p, kp, true}.
+struct Dense {
+    double* p; uint64_t ld; bool rowMajor;
+    uint64_t sr() const { return rowMajor ? ld : 1; }             // elements from a row to the next, and
+    uint64_t sc() const { return rowMajor ? 1 : ld; }             // from a column to the next
+};
 // Aggregation multigrid (aggregate.hip, amg.hip; contracts in spmvHip.h, design in DESIGN.md sections 24 and 31).
 // aggregateCsr: the aggregate ids of the checked square handle into dAgg (M words), K rounds per host check; synchronous,
 // allocates, temporaries freed before it returns.  AmgPlan: which of the three setups a hierarchy is, with that setup's
@@ -258,12 +266,12 @@ int  enqueueAmgCycle(const DevMat* m, spmat* hA, const double* r, double* z, hip
 // The block cycle.  amgSetBlockWidth: the workspace of a cycle for up to `width` columns, 0 drops it
 // (synchronous, allocates; a failure leaves the hierarchy as it was).  amgBlockState: the width, the workspace's bytes, and
 // whether a level sweeps by colours (which the block cycle does not).  enqueueAmgCycleBlock: Z(:, c) = V(0, R(:, c)) for
-// c < k <= the width on a hierarchy without a Gauss-Seidel level, a0 its source; R and Z with element strides; kernels
+// c < k <= the width on a hierarchy without a Gauss-Seidel level, a0 its source; R and Z the caller's blocks; kernels
 // only, `stop` and `launches` as in enqueueAmgCycle (an SpMM pass of any width counted as one).
 int  amgSetBlockWidth(DevMat* m, uint32_t width, hipStream_t stream);
 void amgBlockState(const DevMat* m, uint32_t* width, uint64_t* bytes, bool* gaussSeidel);
-int  enqueueAmgCycleBlock(const DevMat* m, const DevMat* a0, uint32_t k, const double* R, uint64_t srr, uint64_t src, double* Z, uint64_t szr,
-                          uint64_t szc, hipStream_t stream, const uint32_t* stop, unsigned long* launches);
+int  enqueueAmgCycleBlock(const DevMat* m, const DevMat* a0, uint32_t k, const Dense& R, const Dense& Z, hipStream_t stream,
+                          const uint32_t* stop, unsigned long* launches);
 const spmvAmgInfo* amgInfo(const DevMat* m);
 void amgLevel(const DevMat* m, unsigned level, spmat* dAl, const uint32_t** dAgg, const double** dDinv);
 void amgProlongator(const DevMat* m, unsigned level, spmat* dPl, spmat* dRl, double* omegaP);
@@ -281,11 +289,11 @@ int  enqueueTrsv(const DevMat* d, int uplo, int diag, const double* b, double* x
 void triInfo(const DevMat* d, int uplo, spmvTriInfo* out);
 void freeTri(TriSchedule* s);
 // X = T^-1 B for k columns on the analysed triangle's schedule (trsm.hip; contract in spmvHip.h, design in DESIGN.md section
-// 26): B(i, c) at B[i*sbr + c*sbc], X(i, c) at X[i*ldx + c] (xRowMajor) or X[c*ldx + i]; as many launches as enqueueTrsv
+// 26): B is read by its strides, X's layout picks the kernel instance; as many launches as enqueueTrsv
 // makes, whatever k is, on `stream`, no allocation, no sync; reports the last launch; `stop` as enqueueTrsv's (the block
 // Krylov loops, krylov_block.hip).  The caller has checked the arguments.
-int  enqueueTrsm(const DevMat* d, int uplo, int diag, uint32_t k, const double* B, uint64_t sbr, uint64_t sbc, double* X,
-                 uint64_t ldx, bool xRowMajor, hipStream_t stream, dim3* grid, dim3* block, const uint32_t* stop = nullptr);
+int  enqueueTrsm(const DevMat* d, int uplo, int diag, uint32_t k, const Dense& B, const Dense& X, hipStream_t stream, dim3* grid,
+                 dim3* block, const uint32_t* stop = nullptr);
 // ILU(0) in place on the lower schedule d->tri[SPMV_TRI_LOWER] (ilu0.hip; contract in spmvHip.h, design in DESIGN.md section
 // 18).  iluUnsortedRow: the first row that is not strictly ascending, or -1 (synchronous).  iluFactor: the factorisation's
 // launches on `stream` for the checked handle, then the zero-pivot read-back (synchronous); groupWidth 8, 16 or 64 lanes
@@ -300,15 +308,13 @@ int  enqueueDot(uint64_t n, const double* u, const double* v, double* result, hi
 void freeDotWorkspace();
 int  krylovSolve(int bicg, spmat* hA, const DevMat* a, const DevMat* m, const double* b, double* x, const spmvKrylovOpts* opts,
                  spmvKrylovInfo* info, uint32_t K, hipStream_t stream);
-// Blocks of right-hand sides (krylov_block.hip; contract in spmvHip.h, design in DESIGN.md section 27), elements at
-// [i*row stride + c*column stride].  enqueueBlockDot: k fixed-order dots U(:, c) . V(:, c) into k device doubles, partials
+// Blocks of right-hand sides (krylov_block.hip; contract in spmvHip.h, design in DESIGN.md sections 27 and 34).
+// enqueueBlockDot: k fixed-order dots U(:, c) . V(:, c) into k device doubles, partials
 // in the dot workspace.  krylovBlockSolve: k solves in lock step on the checked handles, m the analysed ILU(0) handle or
 // null, K iterations per read-back of the all-stopped word; allocates its workspace, synchronous.
-int  enqueueBlockDot(uint64_t n, uint32_t k, const double* U, uint64_t sur, uint64_t suc, const double* V, uint64_t svr,
-                     uint64_t svc, double* out, hipStream_t stream);
-int  krylovBlockSolve(int bicg, const DevMat* a, const DevMat* m, uint32_t k, const double* B, uint64_t sbr, uint64_t sbc,
-                      double* X, uint64_t sxr, uint64_t sxc, const spmvKrylovOpts* opts, spmvKrylovColumn* cols,
-                      spmvKrylovInfo* info, uint32_t K, hipStream_t stream);
+int  enqueueBlockDot(uint64_t n, uint32_t k, const Dense& U, const Dense& V, double* out, hipStream_t stream);
+int  krylovBlockSolve(int bicg, const DevMat* a, const DevMat* m, uint32_t k, const Dense& B, const Dense& X,
+                      const spmvKrylovOpts* opts, spmvKrylovColumn* cols, spmvKrylovInfo* info, uint32_t K, hipStream_t stream);
 // h = V^T w and restarted GMRES (gmres.hip; contract in spmvHip.h, design in DESIGN.md section 20).  enqueueMultiDot: k
 // fixed-order dots in one pass into k device doubles, partials in the dot workspace (grown to k blocks-of-n).  gmresSolve:
 // GMRES(restart) with CGS2 on the checked handles; fused != 0 folds the first update into the second projection's
@@ -322,10 +328,9 @@ int  enqueueScatterValues(double* val, const uint32_t* map, uint64_t n, const do
 int  enqueueSellValues(uint32_t nSlices, const uint64_t* sliceOff, const uint32_t* perm, const uint32_t* slen, const void* IRP,
                        int irpBytes, const double* AS, double* val, hipStream_t stream);
 int  updateValues(spmat* h, const double* AS, bool onDevice, bool reread, hipStream_t stream, const char* who);   // upload.hip
-// Y = A X for k columns, X(j, c) at X[j*sxr + c*sxc], Y(i, c) at Y[i*syr + c*syc] (spmm.hip): one launch per panel of at
+// Y = A X for k columns, X of N rows and Y of M (spmm.hip): one launch per panel of at
 // most 16 columns on `stream`, no allocation; the caller has checked handle, pointers and extents
-int  enqueueSpmm(const DevMat* d, uint32_t k, const double* X, uint64_t sxr, uint64_t sxc, double* Y, uint64_t syr,
-                 uint64_t syc, hipStream_t stream);
+int  enqueueSpmm(const DevMat* d, uint32_t k, const Dense& X, const Dense& Y, hipStream_t stream);
 constexpr uint32_t VMAP_NONE = 0xFFFFFFFFu;                    // map entry of a padding cell (value 0.0); nnz < 2^32 - 65536
 
 // Fold `blocks` workgroups into an (x, y) grid whose x extent keeps

@@ -13,7 +13,9 @@
 // status into a small device state block.  Every kernel that writes x, r, p or the state reads that block first and
 // returns once the loop has stopped; so does every triangular solve of the preconditioner (a stop pointer).  The host
 // enqueues K iterations at a time and reads the block back once per batch: iterations enqueued past the stop write
-// nothing, and x is the loop's x however far the host overshoots.
+// nothing, and x is the loop's x however far the host overshoots.  What is enqueued in which order is krylovLoop of
+// krylov.hpp, which the block solves share; here is the single width of it: the ops on plain vectors, the finish kernel, the
+// launchers, and the read-back of the one state block.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <chrono>
@@ -47,7 +49,7 @@ struct TtTsOp {                                 // t . t and t . s
 struct CgUpdateOp {                             // x = x + alpha*p; r = r - alpha*q; r . r
     static constexpr int NDOT = 1;
     double* x; const double* p; double* r; const double* q;
-    mutable double alpha;
+    mutable double alpha = 0.0;
     struct R { double2 x, p, r, q; };
     __device__ int mode(const KState* st) const { if (st->stop) return 0; alpha = st->alpha; return 1; }
     template <bool VEC> __device__ void load(uint64_t i, bool two, R& v) const {
@@ -65,7 +67,7 @@ struct CgUpdateOp {                             // x = x + alpha*p; r = r - alph
 struct CgPOp {                                  // p = z (first) or p = z + beta*p
     static constexpr int NDOT = 0;
     const double* z; double* p; int first;
-    mutable double beta;
+    mutable double beta = 0.0;
     struct R { double2 z, p; };
     __device__ int mode(const KState* st) const { if (st->stop) return 0; beta = st->beta; return 1; }
     template <bool VEC> __device__ void load(uint64_t i, bool two, R& v) const {
@@ -80,7 +82,7 @@ struct CgPOp {                                  // p = z (first) or p = z + beta
 struct BiPOp {                                  // p = r (first) or p = r + beta*(p - omega*v)
     static constexpr int NDOT = 0;
     const double* r; double* p; const double* v; int first;
-    mutable double beta, omega;
+    mutable double beta = 0.0, omega = 0.0;
     struct R { double2 r, p, v; };
     __device__ int mode(const KState* st) const { if (st->stop) return 0; beta = st->beta; omega = st->omega; return 1; }
     template <bool VEC> __device__ void load(uint64_t i, bool two, R& x) const {
@@ -97,7 +99,7 @@ struct BiPOp {                                  // p = r (first) or p = r + beta
 struct SOp {                                    // s = r - alpha*v; s . s
     static constexpr int NDOT = 1;
     const double* r; const double* v; double* s;
-    mutable double alpha;
+    mutable double alpha = 0.0;
     struct R { double2 r, v; };
     __device__ int mode(const KState* st) const { if (st->stop) return 0; alpha = st->alpha; return 1; }
     template <bool VEC> __device__ void load(uint64_t i, bool two, R& x) const { x.r = ld2<VEC>(r, i, two); x.v = ld2<VEC>(v, i, two); }
@@ -114,8 +116,8 @@ struct BiUpdateOp {
     static constexpr int NDOT = 2;
     double* x; const double* phat; const double* shat; double* r; const double* s; const double* t; const double* rhat;
     uint64_t k;
-    mutable double alpha, omega;
-    mutable int full;
+    mutable double alpha = 0.0, omega = 0.0;
+    mutable int full = 0;
     struct R { double2 x, ph, sh, s, t, rh; };
     __device__ int mode(const KState* st) const {
         full = !st->stop;
@@ -161,6 +163,40 @@ void launchFinish(uint64_t n, const double* p0, const double* p1, int ph, uint64
     hipLaunchKernelGGL(krylov_finish_kernel, dim3(1), dim3(KT), 0, s, blocksOf(n), p0, p1, ph, k, st, hist, out, precond);
 }
 
+// the single width of krylovLoop (krylov.hpp): one vector a role, one state block, which the host reads once per batch
+struct SingleWidth {
+    using Vec = double*;
+    using Init = InitOp; using Dot = GuardedDot; using TtTs = TtTsOp; using CgUpdate = CgUpdateOp; using CgP = CgPOp;
+    using BiP = BiPOp; using S = SOp; using BiUpdate = BiUpdateOp;
+    const uint64_t n; spmat* const hA; const Precond& pc; const int pre; const hipStream_t s;
+    spmvKrylovInfo& out;                        // launches and hostChecks are counted here
+    Vec b = nullptr, x = nullptr, v[8] = {};
+    double* p0 = nullptr; double* p1 = nullptr; // the block partials of a pass's first and second dot
+    KState* st = nullptr; double* hist = nullptr;
+    KState h{};                                 // the state as the host last read it
+    int product(Vec in, Vec outv) { ++out.launches; return spmvHipEnqueueAutoRows(hA, in, outv, s); }
+    int precond(Vec in, Vec outv) { return pc.apply(in, outv, &st->stop, &out.launches); }
+    template <class Op> void vec(const Op& op, std::initializer_list<const void*> ptrs) {
+        bool al = true;
+        for (const void* p : ptrs) al = al && aligned16(p);
+        launchVec(n, st, op, al, p0, p1, s);
+        ++out.launches;
+    }
+    void finish(int ph, uint64_t k, int ndot) {
+        launchFinish(n, p0, ndot > 1 ? p1 : nullptr, ph, k, st, hist, nullptr, pre, s);
+        ++out.launches;
+    }
+    int afterInit(bool* done) { *done = false; return EXIT_SUCCESS; }    // not read: the first batch is enqueued whatever the init found
+    int afterBatch(bool* done) {
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&h, st, sizeof h, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        ++out.hostChecks;
+        *done = h.stop != 0;
+        return EXIT_SUCCESS;
+    }
+};
+
 // the public dot's block partials: a library workspace, grown (synchronously) by the first call that needs more
 struct DotWorkspace { double* p = nullptr; uint64_t blocks = 0; int dev = -1; } g_dot;   // blocks: doubles held
 
@@ -200,107 +236,24 @@ int krylovSolve(int bicg, spmat* hA, const DevMat* a, const DevMat* m, const dou
     const uint64_t n = a->M, nb = std::max<uint64_t>(blocksOf(n), 1);
     const int pre = m != nullptr;
     spmvKrylovInfo out{};
-    DevBufs w;
+    DevBufs bufs;
+    const Precond pc(m, hA, s);
+    SingleWidth w{n, hA, pc, pre, s, out};
     const int nvec = bicg ? (pre ? 8 : 6) : (pre ? 4 : 3);
-    double* v[8] = {};
     for (int i = 0; i < nvec; ++i)
-        if (!(v[i] = w.alloc<double>(n))) { fprintf(stderr, "libspmvhip: Krylov solve: workspace allocation failed\n"); return EXIT_FAILURE; }
-    double* part = w.alloc<double>(2 * nb);
-    KState* st = w.alloc<KState>(1);
-    double* hist = o->history ? w.alloc<double>(o->maxIter + 1) : nullptr;
-    if (!part || !st || (o->history && !hist)) { fprintf(stderr, "libspmvhip: Krylov solve: workspace allocation failed\n"); return EXIT_FAILURE; }
-    double* p0 = part;
-    double* p1 = part + nb;
-    KState h{};
+        if (!(w.v[i] = bufs.alloc<double>(n))) { fprintf(stderr, "libspmvhip: Krylov solve: workspace allocation failed\n"); return EXIT_FAILURE; }
+    w.p0 = bufs.alloc<double>(2 * nb);
+    KState* st = w.st = bufs.alloc<KState>(1);
+    double* hist = w.hist = o->history ? bufs.alloc<double>(o->maxIter + 1) : nullptr;
+    if (!w.p0 || !st || (o->history && !hist)) { fprintf(stderr, "libspmvhip: Krylov solve: workspace allocation failed\n"); return EXIT_FAILURE; }
+    w.p1 = w.p0 + nb;
+    w.b = const_cast<double*>(b);
+    w.x = x;
+    KState& h = w.h;
     h.maxIter = o->maxIter;
     h.tol2 = o->tol * o->tol;
     HIP_TRY(hipMemcpyAsync(st, &h, sizeof h, hipMemcpyHostToDevice, s));
-    const Precond pc(m, hA, s);
-    auto precond = [&](const double* in, double* outv) { return pc.apply(in, outv, &st->stop, &out.launches); };
-    auto spmv = [&](double* in, double* outv) {
-        ++out.launches;
-        return spmvHipEnqueueAutoRows(hA, in, outv, s);
-    };
-    auto vec = [&](const auto& op, std::initializer_list<const void*> ptrs) {
-        bool al = true;
-        for (const void* p : ptrs) al = al && aligned16(p);
-        launchVec(n, st, op, al, p0, p1, s);
-        ++out.launches;
-    };
-    auto finish = [&](int ph, uint64_t k, int ndot) {
-        launchFinish(n, p0, ndot > 1 ? p1 : nullptr, ph, k, st, hist, nullptr, pre, s);
-        ++out.launches;
-    };
-    // r, p, q (, z) / r, rhat, p, v, s, t (, phat, shat)
-    double* r = v[0];
-    double* q = v[2];
-    if (spmv(x, q)) return EXIT_FAILURE;                                 // the first call for a handle chooses the kernel
-    if (!bicg) {
-        double* p = v[1];
-        double* z = pre ? v[3] : r;
-        vec(InitOp{b, q, r, nullptr}, {b, q, r});
-        finish(F_CG_INIT, 0, 2);
-        if (pre) {
-            if (precond(r, z)) return EXIT_FAILURE;
-            vec(GuardedDot{{r, z}}, {r, z});
-            finish(F_CG_RZ, 0, 1);
-        }
-        vec(CgPOp{z, p, 1, 0.0}, {z, p});
-        for (uint64_t k = 1; k <= o->maxIter;) {
-            const uint64_t end = std::min<uint64_t>(o->maxIter, k + K - 1);
-            for (; k <= end; ++k) {
-                if (spmv(p, q)) return EXIT_FAILURE;
-                vec(GuardedDot{{p, q}}, {p, q});
-                finish(F_CG_ALPHA, k, 1);
-                vec(CgUpdateOp{x, p, r, q, 0.0}, {x, p, r, q});
-                finish(F_CG_RR, k, 1);
-                if (pre) {
-                    if (precond(r, z)) return EXIT_FAILURE;
-                    vec(GuardedDot{{r, z}}, {r, z});
-                    finish(F_CG_RZ, k, 1);
-                }
-                vec(CgPOp{z, p, 0, 0.0}, {z, p});
-            }
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(&h, st, sizeof h, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            ++out.hostChecks;
-            if (h.stop) break;
-        }
-    } else {
-        double* rhat = v[1];
-        double* p = v[3];
-        double* vv = v[4];
-        double* sv = v[5];
-        double* t = q;
-        double* phat = pre ? v[6] : p;
-        double* shat = pre ? v[7] : sv;
-        vec(InitOp{b, q, r, rhat}, {b, q, r, rhat});
-        finish(F_BI_INIT, 0, 2);
-        for (uint64_t k = 1; k <= o->maxIter;) {
-            const uint64_t end = std::min<uint64_t>(o->maxIter, k + K - 1);
-            for (; k <= end; ++k) {
-                vec(BiPOp{r, p, vv, k == 1, 0.0, 0.0}, {r, p, vv});
-                if (pre && precond(p, phat)) return EXIT_FAILURE;
-                if (spmv(phat, vv)) return EXIT_FAILURE;
-                vec(GuardedDot{{rhat, vv}}, {rhat, vv});
-                finish(F_BI_ALPHA, k, 1);
-                vec(SOp{r, vv, sv, 0.0}, {r, vv, sv});
-                finish(F_BI_SS, k, 1);
-                if (pre && precond(sv, shat)) return EXIT_FAILURE;
-                if (spmv(shat, t)) return EXIT_FAILURE;
-                vec(TtTsOp{t, sv}, {t, sv});
-                finish(F_BI_OMEGA, k, 2);
-                vec(BiUpdateOp{x, phat, shat, r, sv, t, rhat, k, 0.0, 0.0, 0}, {x, phat, shat, r, sv, t, rhat});
-                finish(F_BI_RR, k, 2);
-            }
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(&h, st, sizeof h, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            ++out.hostChecks;
-            if (h.stop) break;
-        }
-    }
+    if (krylovLoop(w, bicg, pre, o->maxIter, K)) return EXIT_FAILURE;
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(&h, st, sizeof h, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));

@@ -1,6 +1,7 @@
 // krylov.hpp -- what the Krylov files (krylov.hip, krylov_block.hip, gmres.hip) share: the blocks and lanes of the
 // fixed-order dot, the element-pair loads and stores, the state block of CG / BiCGStab and its scalar steps, the fixed tree,
-// the fused-pass kernel and its launcher, the workspace holder, and the preconditioner of a solve.
+// the fused-pass kernel and its launcher, the workspace holder, the preconditioner of a solve, and the enqueue order of CG and
+// BiCGStab written once for the single and the block width (krylovLoop).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -238,6 +239,76 @@ struct Precond {
         return EXIT_SUCCESS;
     }
 };
+
+// ------------------------------------------------------------------------------------------------ the two loops
+// What CG (bicg = 0) and BiCGStab enqueue, in order, K iterations per host check.  The width W is
+// the single solve (krylov.hip) or the block of columns (krylov_block.hip) and answers for everything that differs:
+//   Vec; Init, Dot, TtTs, CgUpdate, CgP, BiP, S, BiUpdate   a vector, and the fused passes on it (fields in one order)
+//   b, x, v[8]                          the caller's vectors and the workspace: r, p, q (, z) / r, rhat, p, v, s, t (, phat, shat)
+//   product(in, out), precond(in, out)  out = A in, out = M^-1 in (asked only with a dM); not 0: the solve fails
+//   vec(op, {the op's vectors}), finish(phase, iteration, dots)   one fused pass, and the finish of its dots
+//   afterInit(&done), afterBatch(&done) whether the host knows the loop to have stopped; not 0: the solve fails
+template <class W>
+int krylovLoop(W& w, int bicg, int pre, uint64_t maxIter, uint32_t K) {
+    using V = typename W::Vec;
+    const V b = w.b, x = w.x, r = w.v[0], q = w.v[2];
+    bool done = false;
+    if (w.product(x, q)) return EXIT_FAILURE;                            // the first call for a handle chooses the kernel
+    if (!bicg) {
+        const V p = w.v[1], z = pre ? w.v[3] : r;
+        auto rz = [&](uint64_t k) {
+            if (w.precond(r, z)) return EXIT_FAILURE;
+            w.vec(typename W::Dot{{r, z}}, {r, z});
+            w.finish(F_CG_RZ, k, 1);
+            return EXIT_SUCCESS;
+        };
+        w.vec(typename W::Init{b, q, r, V{}}, {b, q, r});
+        w.finish(F_CG_INIT, 0, 2);
+        if (w.afterInit(&done)) return EXIT_FAILURE;
+        if (!done) {
+            if (pre && rz(0)) return EXIT_FAILURE;
+            w.vec(typename W::CgP{z, p, 1}, {z, p});
+        }
+        for (uint64_t k = 1; !done && k <= maxIter;) {
+            const uint64_t end = std::min<uint64_t>(maxIter, k + K - 1);
+            for (; k <= end; ++k) {
+                if (w.product(p, q)) return EXIT_FAILURE;
+                w.vec(typename W::Dot{{p, q}}, {p, q});
+                w.finish(F_CG_ALPHA, k, 1);
+                w.vec(typename W::CgUpdate{x, p, r, q}, {x, p, r, q});
+                w.finish(F_CG_RR, k, 1);
+                if (pre && rz(k)) return EXIT_FAILURE;
+                w.vec(typename W::CgP{z, p, 0}, {z, p});
+            }
+            if (w.afterBatch(&done)) return EXIT_FAILURE;
+        }
+        return EXIT_SUCCESS;
+    }
+    const V rhat = w.v[1], p = w.v[3], vv = w.v[4], sv = w.v[5], t = q, phat = pre ? w.v[6] : p, shat = pre ? w.v[7] : sv;
+    w.vec(typename W::Init{b, q, r, rhat}, {b, q, r, rhat});
+    w.finish(F_BI_INIT, 0, 2);
+    if (w.afterInit(&done)) return EXIT_FAILURE;
+    for (uint64_t k = 1; !done && k <= maxIter;) {
+        const uint64_t end = std::min<uint64_t>(maxIter, k + K - 1);
+        for (; k <= end; ++k) {
+            w.vec(typename W::BiP{r, p, vv, k == 1}, {r, p, vv});
+            if (pre && w.precond(p, phat)) return EXIT_FAILURE;
+            if (w.product(phat, vv)) return EXIT_FAILURE;
+            w.vec(typename W::Dot{{rhat, vv}}, {rhat, vv});
+            w.finish(F_BI_ALPHA, k, 1);
+            w.vec(typename W::S{r, vv, sv}, {r, vv, sv});
+            w.finish(F_BI_SS, k, 1);
+            if (pre && w.precond(sv, shat)) return EXIT_FAILURE;
+            if (w.product(shat, t)) return EXIT_FAILURE;
+            w.vec(typename W::TtTs{t, sv}, {t, sv});
+            w.finish(F_BI_OMEGA, k, 2);
+            w.vec(typename W::BiUpdate{x, phat, shat, r, sv, t, rhat, k}, {x, phat, shat, r, sv, t, rhat});
+            w.finish(F_BI_RR, k, 2);
+        }
+        if (w.afterBatch(&done)) return EXIT_FAILURE;
+    }
+    return EXIT_SUCCESS;
+}
 
 }  // namespace
 // the library's dot workspace (krylov.hip): at least `doubles` doubles on the current device, grown (device

@@ -8,7 +8,8 @@
 // unchanged, one workgroup per column in one finish launch.  Every fused pass reads the state of its two columns and leaves
 // a stopped column alone -- its x, r, p and state are frozen however long its neighbours run on -- and a head word that the
 // finish kernel sets when the last column stops is what the host reads once per K iterations and what the triangular
-// passes take as their stop pointer.
+// passes take as their stop pointer.  The order of the launches is krylovLoop of krylov.hpp, the single solves' own; here is
+// the block width of it (BlockWidth), and B and X arrive as the checked Dense operands of device_mat.hpp.
 //
 // The fused passes (the kernel and its launcher are krylov_block.hpp, which amg.hip shares; the ops are here).  The working vectors are row-major n x kp blocks, kp = k rounded up to even, so a row's column pair
 // (c, c + 1), c even, is one 16-byte access; B and X are read and written where the caller keeps them, in 16-byte accesses
@@ -223,148 +224,95 @@ void launchBlockFinish(uint64_t n, uint32_t k, const double* p0, const double* p
                        histLd, out, precond);
 }
 
+// the block width of krylovLoop (krylov.hpp): an n x kp block a role, a state block a column, and the head word, which the
+// host reads after the init (every column may have stopped there: no further kernel) and once per batch
+struct BlockWidth {
+    using Vec = BMat;
+    using Init = BInitOp; using Dot = BGuardedDot; using TtTs = BTtTsOp; using CgUpdate = BCgUpdateOp; using CgP = BCgPOp;
+    using BiP = BBiPOp; using S = BSOp; using BiUpdate = BBiUpdateOp;
+    const uint64_t n; const uint32_t k; const DevMat* const a; const DevMat* const m; const int pre; const uint64_t histLd;
+    const hipStream_t s;
+    spmvKrylovInfo& out;                        // launches and hostChecks are counted here
+    const bool cycle = pre && m->origin == Origin::HIERARCHY;            // M^-1 is a block cycle of the hierarchy (its width is >= k)
+    unsigned long triLaunches = 0;              // of the two triangular passes otherwise
+    Vec b{}, x{}, v[8] = {};
+    double* p0 = nullptr; double* p1 = nullptr; // the block partials of a pass's first and second dot
+    KState* st = nullptr; BlockHead* head = nullptr; double* hist = nullptr;
+    BlockHead hh{};                             // the head word as the host last read it
+    int product(const Vec& in, const Vec& outv) { ++out.launches; return enqueueSpmm(a, k, dense(in), dense(outv), s); }
+    int precond(const Vec& in, const Vec& outv) {                        // z = U^-1 (L^-1 in), or one cycle: every launch behind the head word
+        if (cycle) return enqueueAmgCycleBlock(m, a, k, dense(in), dense(outv), s, &head->allStop, &out.launches);
+        dim3 g, bl;
+        if (enqueueTrsm(m, SPMV_TRI_LOWER, SPMV_DIAG_UNIT, k, dense(in), dense(outv), s, &g, &bl, &head->allStop)) return EXIT_FAILURE;
+        if (enqueueTrsm(m, SPMV_TRI_UPPER, SPMV_DIAG_STORED, k, dense(outv), dense(outv), s, &g, &bl, &head->allStop)) return EXIT_FAILURE;
+        out.launches += triLaunches;
+        return EXIT_SUCCESS;
+    }
+    template <class Op> void vec(const Op& op, std::initializer_list<Vec>) {       // (a block's own `pair` is its alignment test)
+        launchBlockVec(n, k, st, op, p0, p1, s);
+        ++out.launches;
+    }
+    void finish(int ph, uint64_t it, int ndot) {
+        launchBlockFinish(n, k, p0, ndot > 1 ? p1 : nullptr, ph, it, st, head, hist, histLd, nullptr, pre, s);
+        ++out.launches;
+    }
+    int afterInit(bool* done) { return afterBatch(done); }
+    int afterBatch(bool* done) {                                         // one read-back of the head word
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&hh, head, sizeof hh, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        ++out.hostChecks;
+        *done = hh.allStop != 0;
+        return EXIT_SUCCESS;
+    }
+};
+
 }  // namespace
 
-int enqueueBlockDot(uint64_t n, uint32_t k, const double* U, uint64_t sur, uint64_t suc, const double* V, uint64_t svr,
-                    uint64_t svc, double* out, hipStream_t st) {
+int enqueueBlockDot(uint64_t n, uint32_t k, const Dense& U, const Dense& V, double* out, hipStream_t st) {
     const uint32_t kp = k + (k & 1);
     double* part = nullptr;
     if (dotWorkspace(blocksOf(n) * kp, &part)) return EXIT_FAILURE;
-    BDotOp op;
-    op.u = bmat(U, sur, suc, k, false);
-    op.v = bmat(V, svr, svc, k, false);
-    launchBlockVec(n, k, nullptr, op, part, nullptr, st);
+    launchBlockVec(n, k, nullptr, BDotOp{bmat(U, k, false), bmat(V, k, false)}, part, nullptr, st);
     launchBlockFinish(n, k, part, nullptr, F_DOT, 0, nullptr, nullptr, nullptr, 0, out, 0, st);
     return hipGetLastError() == hipSuccess ? EXIT_SUCCESS : EXIT_FAILURE;
 }
 
-int krylovBlockSolve(int bicg, const DevMat* a, const DevMat* m, uint32_t k, const double* B, uint64_t sbr, uint64_t sbc, double* X,
-                     uint64_t sxr, uint64_t sxc, const spmvKrylovOpts* o, spmvKrylovColumn* cols, spmvKrylovInfo* info, uint32_t K,
-                     hipStream_t s) {
+int krylovBlockSolve(int bicg, const DevMat* a, const DevMat* m, uint32_t k, const Dense& B, const Dense& X, const spmvKrylovOpts* o,
+                     spmvKrylovColumn* cols, spmvKrylovInfo* info, uint32_t K, hipStream_t s) {
     const auto t0 = std::chrono::steady_clock::now();
     const uint64_t n = a->M, nb = std::max<uint64_t>(blocksOf(n), 1), histLd = o->maxIter + 1;
     const uint32_t kp = k + (k & 1);
     const int pre = m != nullptr;
     const auto fail = [] { fprintf(stderr, "libspmvhip: block Krylov solve: workspace allocation failed\n"); return EXIT_FAILURE; };
     spmvKrylovInfo out{};
-    DevBufs w;
+    DevBufs bufs;
+    BlockWidth w{n, k, a, m, pre, histLd, s, out};
     const int nvec = bicg ? (pre ? 8 : 6) : (pre ? 4 : 3);
-    BMat v[8] = {};
     for (int i = 0; i < nvec; ++i) {
-        double* p = w.alloc<double>(n * kp);
+        double* p = bufs.alloc<double>(n * kp);
         if (!p) return fail();
-        v[i] = bmat(p, kp, 1, k, true);
+        w.v[i] = bmat(Dense{p, kp, true}, k, true);
     }
-    double* part = w.alloc<double>(2 * nb * kp);
-    BlockHead* head = w.alloc<BlockHead>(1);
-    KState* st = w.alloc<KState>(k);
-    double* hist = o->history ? w.alloc<double>(k * histLd) : nullptr;
-    if (!part || !head || !st || (o->history && !hist)) return fail();
-    double* p0 = part;
-    double* p1 = part + nb * kp;
+    w.p0 = bufs.alloc<double>(2 * nb * kp);
+    BlockHead* head = w.head = bufs.alloc<BlockHead>(1);
+    KState* st = w.st = bufs.alloc<KState>(k);
+    double* hist = w.hist = o->history ? bufs.alloc<double>(k * histLd) : nullptr;
+    if (!w.p0 || !head || !st || (o->history && !hist)) return fail();
+    w.p1 = w.p0 + nb * kp;
     KState h0{};
     h0.maxIter = o->maxIter;
     h0.tol2 = o->tol * o->tol;
     std::vector<KState> h(k, h0);
-    BlockHead hh{};
     HIP_TRY(hipMemcpyAsync(st, h.data(), k * sizeof(KState), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(head, &hh, sizeof hh, hipMemcpyHostToDevice, s));
-    const BMat b = bmat(B, sbr, sbc, k, false), x = bmat(X, sxr, sxc, k, false);
-    unsigned long triLaunches = 0;
-    const bool cycle = pre && m->origin == Origin::HIERARCHY;            // M^-1 is a block cycle of the hierarchy (its width is >= k)
-    if (pre && !cycle) {
+    HIP_TRY(hipMemcpyAsync(head, &w.hh, sizeof w.hh, hipMemcpyHostToDevice, s));
+    w.b = bmat(B, k, false);
+    w.x = bmat(X, k, false);
+    if (pre && !w.cycle) {
         spmvTriInfo t{};
-        for (int uplo : {SPMV_TRI_LOWER, SPMV_TRI_UPPER}) { triInfo(m, uplo, &t); triLaunches += t.launches; }
+        for (int uplo : {SPMV_TRI_LOWER, SPMV_TRI_UPPER}) { triInfo(m, uplo, &t); w.triLaunches += t.launches; }
     }
-    auto precond = [&](const BMat& in, const BMat& outv) {                // z = U^-1 (L^-1 in), or one cycle: every launch behind the head word
-        if (cycle) return enqueueAmgCycleBlock(m, a, k, in.p, kp, 1, outv.p, kp, 1, s, &head->allStop, &out.launches);
-        dim3 g, bl;
-        if (enqueueTrsm(m, SPMV_TRI_LOWER, SPMV_DIAG_UNIT, k, in.p, kp, 1, outv.p, kp, true, s, &g, &bl, &head->allStop)) return EXIT_FAILURE;
-        if (enqueueTrsm(m, SPMV_TRI_UPPER, SPMV_DIAG_STORED, k, outv.p, kp, 1, outv.p, kp, true, s, &g, &bl, &head->allStop)) return EXIT_FAILURE;
-        out.launches += triLaunches;
-        return EXIT_SUCCESS;
-    };
-    auto spmm = [&](const BMat& in, const BMat& outv) {
-        ++out.launches;
-        return enqueueSpmm(a, k, in.p, in.sr, in.sc, outv.p, kp, 1, s);
-    };
-    auto vec = [&](const auto& op) {
-        launchBlockVec(n, k, st, op, p0, p1, s);
-        ++out.launches;
-    };
-    auto finish = [&](int ph, uint64_t it, int ndot) {
-        launchBlockFinish(n, k, p0, ndot > 1 ? p1 : nullptr, ph, it, st, head, hist, histLd, nullptr, pre, s);
-        ++out.launches;
-    };
-    auto allStopped = [&](bool* stopped) {                                // one read-back of the head word
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(&hh, head, sizeof hh, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        ++out.hostChecks;
-        *stopped = hh.allStop != 0;
-        return EXIT_SUCCESS;
-    };
-    bool done = false;
-    // r, p, q (, z) / r, rhat, p, v, s, t (, phat, shat)
-    const BMat r = v[0], q = v[2], none{};
-    if (spmm(x, q)) return EXIT_FAILURE;
-    if (!bicg) {
-        const BMat p = v[1], z = pre ? v[3] : r;
-        { BInitOp op; op.b = b; op.q = q; op.r = r; op.rhat = none; vec(op); }
-        finish(F_CG_INIT, 0, 2);
-        if (allStopped(&done)) return EXIT_FAILURE;                      // every column stopped at the init: no further kernel
-        auto rz = [&](uint64_t it) {
-            if (precond(r, z)) return EXIT_FAILURE;
-            BGuardedDot op; op.u = r; op.v = z; vec(op);
-            finish(F_CG_RZ, it, 1);
-            return EXIT_SUCCESS;
-        };
-        if (!done) {
-            if (pre && rz(0)) return EXIT_FAILURE;
-            BCgPOp op; op.z = z; op.p = p; op.first = 1; vec(op);
-        }
-        for (uint64_t it = 1; !done && it <= o->maxIter;) {
-            const uint64_t end = std::min<uint64_t>(o->maxIter, it + K - 1);
-            for (; it <= end; ++it) {
-                if (spmm(p, q)) return EXIT_FAILURE;
-                { BGuardedDot op; op.u = p; op.v = q; vec(op); }
-                finish(F_CG_ALPHA, it, 1);
-                { BCgUpdateOp op; op.x = x; op.p = p; op.r = r; op.q = q; vec(op); }
-                finish(F_CG_RR, it, 1);
-                if (pre && rz(it)) return EXIT_FAILURE;
-                { BCgPOp op; op.z = z; op.p = p; op.first = 0; vec(op); }
-            }
-            if (allStopped(&done)) return EXIT_FAILURE;
-        }
-    } else {
-        const BMat rhat = v[1], p = v[3], vv = v[4], sv = v[5], t = q, phat = pre ? v[6] : p, shat = pre ? v[7] : sv;
-        { BInitOp op; op.b = b; op.q = q; op.r = r; op.rhat = rhat; vec(op); }
-        finish(F_BI_INIT, 0, 2);
-        if (allStopped(&done)) return EXIT_FAILURE;
-        for (uint64_t it = 1; !done && it <= o->maxIter;) {
-            const uint64_t end = std::min<uint64_t>(o->maxIter, it + K - 1);
-            for (; it <= end; ++it) {
-                { BBiPOp op; op.r = r; op.p = p; op.v = vv; op.first = it == 1; vec(op); }
-                if (pre && precond(p, phat)) return EXIT_FAILURE;
-                if (spmm(phat, vv)) return EXIT_FAILURE;
-                { BGuardedDot op; op.u = rhat; op.v = vv; vec(op); }
-                finish(F_BI_ALPHA, it, 1);
-                { BSOp op; op.r = r; op.v = vv; op.s = sv; vec(op); }
-                finish(F_BI_SS, it, 1);
-                if (pre && precond(sv, shat)) return EXIT_FAILURE;
-                if (spmm(shat, t)) return EXIT_FAILURE;
-                { BTtTsOp op; op.t = t; op.s = sv; vec(op); }
-                finish(F_BI_OMEGA, it, 2);
-                {
-                    BBiUpdateOp op;
-                    op.x = x; op.phat = phat; op.shat = shat; op.r = r; op.s = sv; op.t = t; op.rhat = rhat; op.k = it;
-                    vec(op);
-                }
-                finish(F_BI_RR, it, 2);
-            }
-            if (allStopped(&done)) return EXIT_FAILURE;
-        }
-    }
+    if (krylovLoop(w, bicg, pre, o->maxIter, K)) return EXIT_FAILURE;
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(h.data(), st, k * sizeof(KState), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));

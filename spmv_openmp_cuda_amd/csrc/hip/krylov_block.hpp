@@ -1,6 +1,7 @@
 // krylov_block.hpp -- the fused pass over a block of columns, shared by the block solvers (krylov_block.hip) and the block
-// form of the multigrid cycle (amg.hip): the dense block and its pair accesses, the partials of a column pair, the kernel
-// of one block of rows and one panel of columns, and its launcher.  DESIGN.md sections 27 (the pass) and 33 (why a header).
+// form of the multigrid cycle (amg.hip): the dense block as the kernels take it (made from a Dense of device_mat.hpp, and
+// back) and its pair accesses, the partials of a column pair, the kernel of one block of rows and one panel of columns, and
+// its launcher.  DESIGN.md sections 27 (the pass), 33 (why a header) and 34 (the operand).
 //
 // The working vectors are row-major n x kp blocks, kp = k rounded up to even, so a row's column pair (c, c + 1), c even, is
 // one 16-byte access; a caller's block is read and written where the caller keeps it, in 16-byte accesses when its layout
@@ -22,11 +23,14 @@ constexpr uint32_t BK_PANEL = 16;               // columns of a panel (the conve
 struct BMat {
     double* p; uint64_t sr, sc; int pair;
 };
-BMat bmat(const double* p, uint64_t sr, uint64_t sc, uint32_t k, bool padded) {
+BMat bmat(const Dense& d, uint32_t k, bool padded) {
     // a caller's block has no element behind column k - 1: with k odd its last pair is not there to be loaded
-    const bool pair = sc == 1 && sr % 2 == 0 && aligned16(p) && (padded || k % 2 == 0);
-    return BMat{const_cast<double*>(p), sr, sc, pair};
+    const bool pair = d.sc() == 1 && d.sr() % 2 == 0 && aligned16(d.p) && (padded || k % 2 == 0);
+    return BMat{d.p, d.sr(), d.sc(), pair};
 }
+// ... and as the launchers of device_mat.hpp take it (an SpMM, a TRSM, the block cycle on a block of a pass): the same
+// strides (one of the two is 1), and a workspace block comes back as the row-major one it was made from
+Dense dense(const BMat& m) { return m.sc == 1 ? Dense{m.p, m.sr, true} : Dense{m.p, m.sc, false}; }
 
 __device__ __forceinline__ double2 ldp(const BMat& m, uint64_t i, uint32_t c, bool two) {
     const double* q = m.p + i * m.sr + c * m.sc;

@@ -220,24 +220,13 @@ int hipSpMMRowsCSR(spmat* dMat, unsigned k, const double* dX, size_t ldx, int xL
     DevMat* d = csrOf(dMat, dX, dY, who, "handle is not CSR (ELL handles are not supported)");
     if (!d) return EXIT_FAILURE;
     if (k == 0) { ERR("%s: k = 0 columns", who); return EXIT_FAILURE; }
-    for (int layout : {xLayout, yLayout})
-        if (layout != SPMV_DENSE_ROW_MAJOR && layout != SPMV_DENSE_COL_MAJOR) { ERR("%s: unknown layout %d", who, layout); return EXIT_FAILURE; }
-    // ld >= k (row-major) or >= the block's rows (column-major)
-    const uint64_t needX = xLayout == SPMV_DENSE_ROW_MAJOR ? k : d->N, needY = yLayout == SPMV_DENSE_ROW_MAJOR ? k : d->M;
-    if (ldx < needX || ldy < needY) {
-        ERR("%s: leading dimension %s = %zu is below %lu", who, ldx < needX ? "ldx" : "ldy", ldx < needX ? ldx : ldy,
-            (unsigned long)(ldx < needX ? needX : needY));
-        return EXIT_FAILURE;
-    }
-    const unsigned __int128 spanX = denseSpan(d->N, k, ldx, xLayout), spanY = denseSpan(d->M, k, ldy, yLayout);
-    const unsigned __int128 x0 = (uintptr_t)dX, y0 = (uintptr_t)dY;
-    if (spanX && spanY && x0 < y0 + spanY && y0 < x0 + spanX) { ERR("%s: X and Y overlap", who); return EXIT_FAILURE; }
+    Dense X, Y;                                                          // X has N rows, Y has M
+    if (!denseOperand(who, "ldx", d->N, k, dX, ldx, xLayout, &X) || !denseOperand(who, "ldy", d->M, k, dY, ldy, yLayout, &Y)) return EXIT_FAILURE;
+    if (denseShare(k, d->N, X, d->M, Y)) { ERR("%s: X and Y overlap", who); return EXIT_FAILURE; }
     if (d->M == 0) return nothingToLaunch(cx, d, nullptr);
-    const uint64_t sxr = xLayout == SPMV_DENSE_ROW_MAJOR ? ldx : 1, sxc = xLayout == SPMV_DENSE_ROW_MAJOR ? 1 : ldx;
-    const uint64_t syr = yLayout == SPMV_DENSE_ROW_MAJOR ? ldy : 1, syc = yLayout == SPMV_DENSE_ROW_MAJOR ? 1 : ldy;
     Launch L(cx, grid2d(d->nBlk2, WG_THREADS), dim3(WG_THREADS));
-    if (k == 1 && sxr == 1 && syr == 1) launchStream2<true>(cx.stream, d, const_cast<double*>(dX), dY);     // one plain vector: the SpMV kernel
-    else if (enqueueSpmm(d, k, dX, sxr, sxc, dY, syr, syc, cx.stream)) { ERR("%s: launch failed", who); return EXIT_FAILURE; }
+    if (k == 1 && X.sr() == 1 && Y.sr() == 1) launchStream2<true>(cx.stream, d, X.p, dY);     // one plain vector: the SpMV kernel
+    else if (enqueueSpmm(d, k, X, Y, cx.stream)) { ERR("%s: launch failed", who); return EXIT_FAILURE; }
     return L.finish(who);
 }
 

@@ -135,12 +135,29 @@ inline bool overlaps(const void* p, const void* q, uint64_t bytes) {
     return bytes && p0 < q0 + bytes && q0 < p0 + bytes;
 }
 
-// bytes spanned by a dense rows x k block in `layout` with leading dimension ld (0 for an empty block)
-inline unsigned __int128 denseSpan(uint64_t rows, unsigned k, size_t ld, int layout) {
+// Dense blocks at the boundary: the one place that knows the layout constants of spmvHip.h.
+// The rows x k operand (p, ld, layout) whose leading dimension is the argument `name`, checked: ld >= k (row-major) or >=
+// the rows (column-major).  A refusal leaves *out alone.
+inline bool denseOperand(const char* who, const char* name, uint64_t rows, unsigned k, const double* p, size_t ld, int layout, Dense* out) {
+    if (layout != SPMV_DENSE_ROW_MAJOR && layout != SPMV_DENSE_COL_MAJOR) { ERR("%s: unknown layout %d", who, layout); return false; }
+    const uint64_t need = layout == SPMV_DENSE_ROW_MAJOR ? k : rows;
+    if (ld < need) { ERR("%s: leading dimension %s = %zu is below %lu", who, name, ld, (unsigned long)need); return false; }
+    *out = Dense{const_cast<double*>(p), ld, layout == SPMV_DENSE_ROW_MAJOR};
+    return true;
+}
+// bytes spanned by a dense rows x k block (0 for an empty block)
+inline unsigned __int128 denseSpan(uint64_t rows, unsigned k, const Dense& d) {
     if (rows == 0) return 0;
-    const unsigned __int128 last = layout == SPMV_DENSE_ROW_MAJOR ? (unsigned __int128)(rows - 1) * ld + (k - 1)
-                                                                   : (unsigned __int128)(k - 1) * ld + (rows - 1);
+    const unsigned __int128 last = d.rowMajor ? (unsigned __int128)(rows - 1) * d.ld + (k - 1)
+                                              : (unsigned __int128)(k - 1) * d.ld + (rows - 1);
     return (last + 1) * sizeof(double);
+}
+// two blocks of k columns share memory.  inPlace: the same block (pointer, layout and leading dimension) does not count
+inline bool denseShare(unsigned k, uint64_t rowsA, const Dense& a, uint64_t rowsB, const Dense& b, bool inPlace = false) {
+    if (inPlace && a.p == b.p && a.rowMajor == b.rowMajor && a.ld == b.ld) return false;
+    const unsigned __int128 spanA = denseSpan(rowsA, k, a), spanB = denseSpan(rowsB, k, b);
+    const unsigned __int128 a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
+    return spanA && spanB && a0 < b0 + spanB && b0 < a0 + spanA;
 }
 
 // timing bracket used by every launcher

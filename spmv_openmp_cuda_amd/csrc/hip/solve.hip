@@ -89,24 +89,13 @@ int hipSpTRSMCSR(spmat* dA, int uplo, int diag, unsigned k, const double* dB, si
     if (!dB || !dX) { ERR("%s: %s is NULL", who, !dB ? "dB" : "dX"); return EXIT_FAILURE; }
     if (diag != SPMV_DIAG_STORED && diag != SPMV_DIAG_UNIT) { ERR("%s: unknown diag %d", who, diag); return EXIT_FAILURE; }
     if (k == 0) { ERR("%s: k = 0 columns", who); return EXIT_FAILURE; }
-    for (int layout : {bLayout, xLayout})
-        if (layout != SPMV_DENSE_ROW_MAJOR && layout != SPMV_DENSE_COL_MAJOR) { ERR("%s: unknown layout %d", who, layout); return EXIT_FAILURE; }
-    // ld >= k (row-major) or >= M (column-major)
-    const uint64_t needB = bLayout == SPMV_DENSE_ROW_MAJOR ? k : d->M, needX = xLayout == SPMV_DENSE_ROW_MAJOR ? k : d->M;
-    if (ldb < needB || ldx < needX) {
-        ERR("%s: leading dimension %s = %zu is below %lu", who, ldb < needB ? "ldb" : "ldx", ldb < needB ? ldb : ldx,
-            (unsigned long)(ldb < needB ? needB : needX));
-        return EXIT_FAILURE;
-    }
+    Dense B, X;
+    if (!denseOperand(who, "ldb", d->M, k, dB, ldb, bLayout, &B) || !denseOperand(who, "ldx", d->M, k, dX, ldx, xLayout, &X)) return EXIT_FAILURE;
     // in place is the same block: a row reads B only at its own (i, c) and writes X only there; anything else that shares
     // memory is refused
-    if (!(dB == dX && bLayout == xLayout && ldb == ldx)) {
-        const unsigned __int128 spanB = denseSpan(d->M, k, ldb, bLayout), spanX = denseSpan(d->M, k, ldx, xLayout);
-        const unsigned __int128 b0 = (uintptr_t)dB, x0 = (uintptr_t)dX;
-        if (spanB && spanX && b0 < x0 + spanX && x0 < b0 + spanB) {
-            ERR("%s: dB and dX overlap without being the same block (same pointer, layout and leading dimension)", who);
-            return EXIT_FAILURE;
-        }
+    if (denseShare(k, d->M, B, d->M, X, true)) {
+        ERR("%s: dB and dX overlap without being the same block (same pointer, layout and leading dimension)", who);
+        return EXIT_FAILURE;
     }
     if (d->M == 0) return nothingToLaunch(cx, d, nullptr);
     if (d->NZ && !d->AS && !d->unit) { ERR("%s: the handle has no value array", who); return EXIT_FAILURE; }
@@ -118,13 +107,11 @@ int hipSpTRSMCSR(spmat* dA, int uplo, int diag, unsigned k, const double* dB, si
             info.firstBadDiag);
         return EXIT_FAILURE;
     }
-    const bool bRow = bLayout == SPMV_DENSE_ROW_MAJOR, xRow = xLayout == SPMV_DENSE_ROW_MAJOR;
-    const uint64_t sbr = bRow ? ldb : 1, sbc = bRow ? 1 : ldb;
     Launch L(cx, dim3(1), dim3(1));
     dim3 grid(1), block(1);
-    const int rc = k == 1 && sbr == 1 && (xRow ? ldx : 1) == 1      // one plain vector: the single solve
+    const int rc = k == 1 && B.sr() == 1 && X.sr() == 1              // one plain vector: the single solve
                        ? enqueueTrsv(d, uplo, diag, dB, dX, cx.stream, &grid, &block)
-                       : enqueueTrsm(d, uplo, diag, k, dB, sbr, sbc, dX, ldx, xRow, cx.stream, &grid, &block);
+                       : enqueueTrsm(d, uplo, diag, k, B, X, cx.stream, &grid, &block);
     if (rc) { ERR("%s: launch failed", who); return EXIT_FAILURE; }
     L.shape(grid, block);
     return L.finish(who);
@@ -311,14 +298,6 @@ int spmvHipAmgApply(spmat* dM, spmat* dA, const double* dR, double* dZ) {
 }
 
 // ---- the block cycle (contract in spmvHip.h, design in DESIGN.md section 33)
-// a dense rows x k operand: its layout and leading dimension
-static bool denseOk(const char* who, const char* name, uint64_t rows, unsigned k, size_t ld, int layout) {
-    if (layout != SPMV_DENSE_ROW_MAJOR && layout != SPMV_DENSE_COL_MAJOR) { ERR("%s: unknown layout %d", who, layout); return false; }
-    const uint64_t need = layout == SPMV_DENSE_ROW_MAJOR ? k : rows;     // ld >= k (row-major) or >= the rows (column-major)
-    if (ld < need) { ERR("%s: leading dimension %s = %zu is below %lu", who, name, ld, (unsigned long)need); return false; }
-    return true;
-}
-
 // the hierarchy m cannot run a block cycle of k columns: the line says why
 static bool blockCycleRefused(const DevMat* m, unsigned k, const char* who) {
     uint32_t width = 0;
@@ -367,18 +346,13 @@ int spmvHipAmgApplyBlock(spmat* dM, spmat* dA, unsigned k, const double* dR, siz
     if (!dR || !dZ) { ERR("%s: %s is NULL", who, !dR ? "dR" : "dZ"); return EXIT_FAILURE; }
     if (a->M != m->M) { ERR("%s: dA has %lu rows, dM %lu", who, (unsigned long)a->M, (unsigned long)m->M); return EXIT_FAILURE; }
     if (k == 0) { ERR("%s: k = 0 columns", who); return EXIT_FAILURE; }
-    if (!denseOk(who, "ldr", m->M, k, ldr, rLayout) || !denseOk(who, "ldz", m->M, k, ldz, zLayout)) return EXIT_FAILURE;
-    const unsigned __int128 spanR = denseSpan(m->M, k, ldr, rLayout), spanZ = denseSpan(m->M, k, ldz, zLayout);
-    const unsigned __int128 r0 = (uintptr_t)dR, z0 = (uintptr_t)dZ;
-    if (spanR && spanZ && r0 < z0 + spanZ && z0 < r0 + spanR) { ERR("%s: dR and dZ overlap", who); return EXIT_FAILURE; }
+    Dense R, Z;
+    if (!denseOperand(who, "ldr", m->M, k, dR, ldr, rLayout, &R) || !denseOperand(who, "ldz", m->M, k, dZ, ldz, zLayout, &Z)) return EXIT_FAILURE;
+    if (denseShare(k, m->M, R, m->M, Z)) { ERR("%s: dR and dZ overlap", who); return EXIT_FAILURE; }
     if (blockCycleRefused(m, k, who)) return EXIT_FAILURE;
     if (m->M == 0) return nothingToLaunch(cx, m, nullptr);
-    const bool rRow = rLayout == SPMV_DENSE_ROW_MAJOR, zRow = zLayout == SPMV_DENSE_ROW_MAJOR;
     Launch L(cx, grid2d((m->M + KB - 1) / KB * ((k + 15) / 16), KT), dim3(KT));
-    if (enqueueAmgCycleBlock(m, a, k, dR, rRow ? ldr : 1, rRow ? 1 : ldr, dZ, zRow ? ldz : 1, zRow ? 1 : ldz, cx.stream, nullptr, nullptr)) {
-        ERR("%s: launch failed", who);
-        return EXIT_FAILURE;
-    }
+    if (enqueueAmgCycleBlock(m, a, k, R, Z, cx.stream, nullptr, nullptr)) { ERR("%s: launch failed", who); return EXIT_FAILURE; }
     return L.finish(who);
 }
 
@@ -522,13 +496,10 @@ int spmvHipBlockDot(size_t n, unsigned k, const double* dU, size_t ldu, int uLay
     if (!ready(who)) return EXIT_FAILURE;
     if (!dH || (n && (!dU || !dV))) { ERR("%s: %s is NULL", who, !dH ? "dH" : !dU ? "dU" : "dV"); return EXIT_FAILURE; }
     if (k == 0) { ERR("%s: k = 0 columns", who); return EXIT_FAILURE; }
-    if (!denseOk(who, "ldu", n, k, ldu, uLayout) || !denseOk(who, "ldv", n, k, ldv, vLayout)) return EXIT_FAILURE;
-    const bool uRow = uLayout == SPMV_DENSE_ROW_MAJOR, vRow = vLayout == SPMV_DENSE_ROW_MAJOR;
+    Dense U, V;
+    if (!denseOperand(who, "ldu", n, k, dU, ldu, uLayout, &U) || !denseOperand(who, "ldv", n, k, dV, ldv, vLayout, &V)) return EXIT_FAILURE;
     Launch L(cx, dim3(k), dim3(KT));
-    if (enqueueBlockDot(n, k, dU, uRow ? ldu : 1, uRow ? 1 : ldu, dV, vRow ? ldv : 1, vRow ? 1 : ldv, dH, cx.stream)) {
-        ERR("%s: launch failed", who);
-        return EXIT_FAILURE;
-    }
+    if (enqueueBlockDot(n, k, U, V, dH, cx.stream)) { ERR("%s: launch failed", who); return EXIT_FAILURE; }
     return L.finish(who);
 }
 
@@ -547,10 +518,9 @@ static int krylovBlock(int bicg, spmat* dA, spmat* dM, unsigned k, const double*
     // (history and info stay with this function: they are per column)
     const int rc = krylovArgs(who, dA, dM, dB, dX, opts, opts ? opts->tol : 0.0, opts ? opts->maxIter : 0, nullptr, nullptr, &a, &m);
     if (rc == EXIT_FAILURE) return EXIT_FAILURE;
-    if (!denseOk(who, "ldb", a->M, k, ldb, bLayout) || !denseOk(who, "ldx", a->M, k, ldx, xLayout)) return EXIT_FAILURE;
-    const unsigned __int128 spanB = denseSpan(a->M, k, ldb, bLayout), spanX = denseSpan(a->M, k, ldx, xLayout);
-    const unsigned __int128 b0 = (uintptr_t)dB, x0 = (uintptr_t)dX;
-    if (spanB && spanX && b0 < x0 + spanX && x0 < b0 + spanB) { ERR("%s: dB and dX overlap", who); return EXIT_FAILURE; }
+    Dense B, X;
+    if (!denseOperand(who, "ldb", a->M, k, dB, ldb, bLayout, &B) || !denseOperand(who, "ldx", a->M, k, dX, ldx, xLayout, &X)) return EXIT_FAILURE;
+    if (denseShare(k, a->M, B, a->M, X)) { ERR("%s: dB and dX overlap", who); return EXIT_FAILURE; }
     if (opts->history && opts->maxIter >= (SIZE_MAX / sizeof(double)) / k - 1) {
         ERR("%s: a history of k * (maxIter + 1) = %u * (%lu + 1) doubles does not fit", who, k, (unsigned long)opts->maxIter);
         return EXIT_FAILURE;
@@ -563,19 +533,14 @@ static int krylovBlock(int bicg, spmat* dA, spmat* dM, unsigned k, const double*
         if (info) *info = spmvKrylovInfo{SPMV_KRYLOV_CONVERGED, 0, 0.0, 0.0, 0, 0, 0.0};
         return EXIT_SUCCESS;
     }
-    const bool bRow = bLayout == SPMV_DENSE_ROW_MAJOR, xRow = xLayout == SPMV_DENSE_ROW_MAJOR;
-    if (k == 1 && (bRow ? ldb : 1) == 1 && (xRow ? ldx : 1) == 1) {      // one plain vector: the single solve
+    if (k == 1 && B.sr() == 1 && X.sr() == 1) {                          // one plain vector: the single solve
         spmvKrylovInfo one{};
         if (krylovSolve(bicg, dA, a, m, dB, dX, opts, &one, S.krylovBlockK[bicg], S.stream)) { ERR("%s: the solve failed", who); return EXIT_FAILURE; }
         if (cols) cols[0] = spmvKrylovColumn{one.status, one.iterations, one.rr, one.bb};
         if (info) *info = one;
         return EXIT_SUCCESS;
     }
-    if (krylovBlockSolve(bicg, a, m, k, dB, bRow ? ldb : 1, bRow ? 1 : ldb, dX, xRow ? ldx : 1, xRow ? 1 : ldx, opts, cols, info,
-                         S.krylovBlockK[bicg], S.stream)) {
-        ERR("%s: the solve failed", who);
-        return EXIT_FAILURE;
-    }
+    if (krylovBlockSolve(bicg, a, m, k, B, X, opts, cols, info, S.krylovBlockK[bicg], S.stream)) { ERR("%s: the solve failed", who); return EXIT_FAILURE; }
     return EXIT_SUCCESS;
 }
 int hipSpCGBlockCSR(spmat* dA, spmat* dM, unsigned k, const double* dB, size_t ldb, int bLayout, double* dX, size_t ldx, int xLayout,

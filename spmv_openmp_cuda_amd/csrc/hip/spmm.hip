@@ -153,12 +153,12 @@ void launchPanelP(const DevMat* d, uint32_t w, const double* X, uint64_t sxr, ui
 }  // namespace
 
 // one launch per panel of at most 16 columns, in column order, on `stream`; the caller has checked the arguments
-int enqueueSpmm(const DevMat* d, uint32_t k, const double* X, uint64_t sxr, uint64_t sxc, double* Y, uint64_t syr,
-                uint64_t syc, hipStream_t stream) {
+int enqueueSpmm(const DevMat* d, uint32_t k, const Dense& X, const Dense& Y, hipStream_t stream) {
+    const uint64_t sxr = X.sr(), sxc = X.sc(), syr = Y.sr(), syc = Y.sc();
     for (uint32_t c0 = 0; c0 < k; c0 += SPMM_PANEL) {
         const uint32_t w = k - c0 < SPMM_PANEL ? k - c0 : SPMM_PANEL;
-        const double* Xp = X + (uint64_t)c0 * sxc;
-        double* Yp = Y + (uint64_t)c0 * syc;
+        const double* Xp = X.p + (uint64_t)c0 * sxc;
+        double* Yp = Y.p + (uint64_t)c0 * syc;
         if (d->unit) launchPanelP<true>(d, w, Xp, sxr, sxc, Yp, syr, syc, stream);
         else         launchPanelP<false>(d, w, Xp, sxr, sxc, Yp, syr, syc, stream);
     }

@@ -216,18 +216,18 @@ void launchWidth(const DevMat* d, const TriSchedule* s, const TrsmArgs& a, bool 
 
 }  // namespace
 
-int enqueueTrsm(const DevMat* d, int uplo, int diag, uint32_t k, const double* B, uint64_t sbr, uint64_t sbc, double* X,
-                uint64_t ldx, bool xRowMajor, hipStream_t st, dim3* grid, dim3* block, const uint32_t* stop) {
+int enqueueTrsm(const DevMat* d, int uplo, int diag, uint32_t k, const Dense& B, const Dense& X, hipStream_t st, dim3* grid,
+                dim3* block, const uint32_t* stop) {
     const TriSchedule* s = d->tri[uplo];
     TrsmArgs a;
-    a.perm = s->perm; a.JA = d->JA; a.AS = d->AS; a.diagPos = s->diagPos; a.stop = stop; a.B = B; a.X = X;
+    a.perm = s->perm; a.JA = d->JA; a.AS = d->AS; a.diagPos = s->diagPos; a.stop = stop; a.B = B.p; a.X = X.p;
     a.unitValue = d->unitValue;
-    a.N = d->N; a.sbr = sbr; a.sbc = sbc; a.ldx = ldx;
+    a.N = d->N; a.sbr = B.sr(); a.sbc = B.sc(); a.ldx = X.ld;
     a.k = k; a.panels = k / TRSM_PANEL + (k % TRSM_PANEL != 0);
     a.upper = uplo == SPMV_TRI_UPPER; a.dunit = diag == SPMV_DIAG_UNIT;
     withIrp(d, [&](auto irp) {
-        if (d->unit) launchWidth<IrpT<decltype(irp)>, true>(d, s, a, xRowMajor, st, grid, block);
-        else         launchWidth<IrpT<decltype(irp)>, false>(d, s, a, xRowMajor, st, grid, block);
+        if (d->unit) launchWidth<IrpT<decltype(irp)>, true>(d, s, a, X.rowMajor, st, grid, block);
+        else         launchWidth<IrpT<decltype(irp)>, false>(d, s, a, X.rowMajor, st, grid, block);
     });
     return hipGetLastError() == hipSuccess ? EXIT_SUCCESS : EXIT_FAILURE;
 }
