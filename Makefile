@@ -4,12 +4,13 @@
 #   oracle   oracle/liboracle.so (+ oracle/_ref when /root/reference exists) -- checker only
 #   harness  tests/harness/test_SpMV_HIP.elf (links product + oracle; test program)
 #   fuzz     tests/harness/fuzz_loader.elf (host loader + decompressors under ASan/UBSan; test program, not in `all`)
+#   ledger   tests/harness/alloc_ledger_check.elf (the allocation ledger over malloc/free under ASan/UBSan; the same)
 HIPCC    ?= hipcc
 CC        = gcc
 ARCH     ?= gfx950
 PKG       = spmv_openmp_cuda_amd
 HIPSRC    = $(PKG)/csrc/hip/abi.hip $(PKG)/csrc/hip/upload.hip $(PKG)/csrc/hip/launch.hip $(PKG)/csrc/hip/solve.hip $(PKG)/csrc/hip/select.hip $(PKG)/csrc/hip/hostcall.hip $(PKG)/csrc/hip/synth.hip $(PKG)/csrc/hip/shard.hip $(PKG)/csrc/hip/tiles.hip $(PKG)/csrc/hip/stripes.hip $(PKG)/csrc/hip/sell.hip $(PKG)/csrc/hip/peer.hip $(PKG)/csrc/hip/values.hip $(PKG)/csrc/hip/spmm.hip $(PKG)/csrc/hip/transpose.hip $(PKG)/csrc/hip/trsv.hip $(PKG)/csrc/hip/trsm.hip $(PKG)/csrc/hip/ilu0.hip $(PKG)/csrc/hip/krylov.hip $(PKG)/csrc/hip/krylov_block.hip $(PKG)/csrc/hip/gmres.hip $(PKG)/csrc/hip/colour.hip $(PKG)/csrc/hip/spgemm.hip $(PKG)/csrc/hip/add.hip $(PKG)/csrc/hip/filter.hip $(PKG)/csrc/hip/aggregate.hip $(PKG)/csrc/hip/amg.hip
-HIPHDR    = $(PKG)/csrc/hip/kernels.hpp $(PKG)/csrc/hip/device_mat.hpp $(PKG)/csrc/hip/lib.hpp $(PKG)/csrc/hip/krylov.hpp $(PKG)/csrc/hip/krylov_block.hpp $(PKG)/csrc/hip/device_prims.hpp include/spmvHip.h include/spmv_types.h
+HIPHDR    = $(PKG)/csrc/hip/kernels.hpp $(PKG)/csrc/hip/device_mat.hpp $(PKG)/csrc/hip/lib.hpp $(PKG)/csrc/hip/krylov.hpp $(PKG)/csrc/hip/krylov_block.hpp $(PKG)/csrc/hip/device_prims.hpp $(PKG)/csrc/hip/alloc_ledger.hpp include/spmvHip.h include/spmv_types.h
 HIPFLAGS  = --offload-arch=$(ARCH) -O3 -fPIC -shared -std=c++17 -ffp-contract=off -Wall -Wno-unused-function -Iinclude -ldl
 HOSTSRC   = $(wildcard $(PKG)/csrc/host/*.c)
 HOSTLIBSRC= $(filter-out %/main.c,$(HOSTSRC))
@@ -58,7 +59,13 @@ tests/harness/fuzz_loader.elf: tests/harness/fuzz_loader.c $(HOSTLIBSRC) $(wildc
 	$(CC) -O1 -g -fopenmp -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -Wall -Wextra \
 	    -Wno-unused-parameter -Iinclude -o $@ tests/harness/fuzz_loader.c $(HOSTLIBSRC) -lm -lz -ldl
 
+# the allocation ledger behind devMalloc / devFree, compiled for the CPU under the same sanitizers (tests/test_alloc_abi.py runs it)
+ledger: tests/harness/alloc_ledger_check.elf
+tests/harness/alloc_ledger_check.elf: tests/harness/alloc_ledger_check.cpp $(PKG)/csrc/hip/alloc_ledger.hpp
+	g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -Wall -Wextra \
+	    -I$(PKG)/csrc/hip -o $@ tests/harness/alloc_ledger_check.cpp
+
 clean:
 	rm -f $(PKG)/lib/*.so $(PKG)/bin/*.elf tests/harness/*.elf
 	$(MAKE) -C oracle clean
-.PHONY: all lib host oracle harness fuzz asan clean
+.PHONY: all lib host oracle harness fuzz ledger asan clean

@@ -73,6 +73,59 @@ int spmvHipFree(void* dPtr);
 int spmvHipMemcpyUp(void* dDst, const void* hSrc, size_t bytes);
 int spmvHipMemcpyDown(void* hDst, const void* dSrc, size_t bytes);
 
+/* ------------------------------------------------------------- refused allocations (for tests)
+ * These two exist for tests.  Every device allocation and release of the library -- handles, formats, schedules,
+ * workspaces, temporaries, and the vectors and bytes handed out above -- goes through one place that keeps a ledger:
+ *   live, liveBytes   what the library holds on the device now (allocations and their bytes as asked for)
+ *   peakBytes         the most it held at once since the process started
+ *   calls             allocations asked for since the last spmvHipAllocRefuse
+ *   refused           how many of those were refused on purpose
+ *   badFrees          releases of a pointer the ledger does not hold: a second release, or memory that came from
+ *                     elsewhere (such a pointer is still passed on to the runtime, whose answer decides the call)
+ * spmvHipAllocRefuse(n, fromThenOn) sets calls and refused to 0 and, with n >= 0, makes allocation number n from now
+ * (0-based) fail: that one alone, or with fromThenOn != 0 that one and every later one, until spmvHipAllocRefuse(-1, 0).
+ * A refused allocation is a real refusal of the runtime -- it is asked for 2^62 bytes -- so the caller sees the
+ * runtime's own error code and the runtime's own sticky last error.  No environment variable arms it.  Both work
+ * before spmvHipInit.
+ *
+ * What a failed device allocation leaves (tests/test_gpu_alloc_refusals.py refuses every allocation of every call below
+ * in turn).  For every call: EXIT_FAILURE, at least one "libspmvhip" line on stderr, no sticky runtime error -- the
+ * next, unrelated call is judged on its own --, the source handles untouched (values, built formats, selections), and
+ * the same call made again succeeds with the result it would have given at first.  And by family:
+ *   a call that makes a handle (spMatCpyCSR / ELL, spmvHipAdoptCSR, spmvHipCsrToEll, spmvHipCsrTranspose, ...Permute,
+ *     spmvHipSpGEMM, spmvHipCsrAdd, spmvHipCsrFilter, the three spmvHipAmgSetup*): the destination handle and info are not
+ *     written, and nothing the call allocated is still held;
+ *   a format build (spmvHipBuildTiles / Stripes / Sell and their *Opt forms, the first call of a format's launcher): the
+ *     handle stays a live CSR handle without that format, nothing of the format is held.  The device's product workspace of
+ *     the two-phase kernel (8 B per entry of the largest matrix built), once grown, stays the library's until
+ *     spmvHipFinalize;
+ *   the selections of hipSpMVRowsCSR / hipSpMVWarpPerRowCSR / hipSpMVAutoCSR: the one exception to EXIT_FAILURE.  A
+ *     candidate whose format cannot be built is skipped; with nothing to allocate the call still answers, with the kernel
+ *     that needs no memory of its own;
+ *   spmvHipUpdateValues, spmvHipValuesChanged and the refreshes (spmvHipTransposeRefresh, ...PermuteRefresh,
+ *     ...SpGEMMRefresh, ...CsrAddRefresh, ...CsrFilterRefresh, spmvHipAmgRefresh): the handle stays live with its pattern,
+ *     its addresses and every built format; info is not written; the CSR values may be the new ones while a built format
+ *     or a coarser level still holds the old ones.  CALL AGAIN before the handle is used: the repeated call completes it;
+ *   the first hipSpTRSVCSR / hipSpTRSMCSR of a triangle, spmvHipTriAnalyse: x is not written, no schedule is left;
+ *   hipSpILU0CSR: AS untouched bit for bit, and the lower triangle's schedule, if it was made, stays on the handle.  One
+ *     allocation comes after the factorisation (the unit flag of the new values): when that fails the line says "the
+ *     factors are in place", AS holds the complete factors, and the same call made again finishes the handle without
+ *     factorising a second time (a value update or a refresh in between makes it an ordinary factorisation again; see
+ *     hipSpILU0CSR's own comment for a caller who rewrites an adopted dAS);
+ *   spmvHipDot / MultiDot / BlockDot: the result is not written, the dot workspace keeps the size it had;
+ *   hipSpCGCSR, hipSpBiCGStabCSR, hipSpGMRESCSR (every allocation comes before the loop): x and info are not written; a
+ *     schedule that was made on dM stays there;
+ *   spmvHipColourCSR, spmvHipAggregateCSR: info is not written, nothing is held; dColour / dPerm / dAgg may have been
+ *     written in part and hold nothing to rely on;
+ *   spmvHipAmgSetSmoother, spmvHipAmgSetGaussSeidel, spmvHipAmgSetBlockWidth: everything new is made before anything old
+ *     is dropped -- the hierarchy keeps its smoother, its sweep counts and its block width, the cycle gives the bits it
+ *     gave before, and nothing the call allocated is still held. */
+typedef struct {
+    ulong live, liveBytes, peakBytes, calls, refused, badFrees;
+} spmvAllocStats;
+int spmvHipAllocRefuse(long n, int fromThenOn);
+int spmvHipAllocStats(spmvAllocStats* stats);
+
 /* ------------------------------------------------------------- matrix upload */
 /* Host CSR -> device (cudaUtils.cu:20-55).  `dMat` is caller-owned host memory
  * that becomes the device handle.  Column ids are narrowed to 32 bit, row
@@ -240,6 +293,12 @@ int hipSpTRSMCSR(spmat* dA, int uplo, int diag, unsigned k, const double* dB, si
  *   value array; ELL handles, spmvHipCsrToEll's included (sharded matrices are no spmat handles); M != N; NZ >= IRP32_LIMIT
  *   or M >= 2^31 (the solve's limits); a row whose columns are not strictly ascending, or a row without exactly one
  *   diagonal entry (the message names the row; spmvIluInfo.firstBadRow is the smaller of the two).
+ *   A failed device allocation is another matter ("refused allocations" above, hipSpILU0CSR's line): AS is untouched, or
+ *   -- the message then says "the factors are in place" -- holds the complete factors, and the same call made again
+ *   finishes the handle without factorising twice.  The library forgets that state whenever IT rewrites AS
+ *   (spmvHipUpdateValues, spmvHipValuesChanged, a refresh of a derived handle, failed or not).  A caller who rewrites an
+ *   adopted dAS after such a failure must call spmvHipValuesChanged before the next hipSpILU0CSR: without it the call
+ *   would take the new values for the factors it is about to finish.
  * spmvHipIlu0Info: what the last factorisation of the handle did (all zeros, zeroPivot and firstBadRow -1, before one). */
 typedef struct {
     long   zeroPivot;       /* -1, or the smallest row whose factored diagonal is +-0.0      */
@@ -522,7 +581,10 @@ int hipSpGMRESCSR(spmat* dA, spmat* dM, const double* dB, double* dX, const spmv
  * Refused with a message and EXIT_FAILURE, outputs untouched: NULL pointers (dColour, dPerm of spmvHipColourCSR, opts and
  *   info excepted); a handle that is not live; ELL handles; M != N; M >= 2^31 or NZ >= IRP32_LIMIT; dB == dA; a dPerm
  *   with a value >= M or a repeated value; a source column id >= M; an unknown order; a refresh of a handle that is not a
- *   permutation, or from a handle that is not its source; dIn == dOut or overlapping. */
+ *   permutation, or from a handle that is not its source; dIn == dOut or overlapping.
+ *   ("Outputs untouched" is the promise for these refusals.  After a failed device allocation -- "refused allocations"
+ *   above -- spmvHipColourCSR leaves info unwritten, but dColour and dPerm may have been written in part and hold nothing
+ *   to rely on; spmvHipCsrPermute leaves dB unwritten.) */
 #define SPMV_COLOUR_NATURAL 0
 #define SPMV_COLOUR_HASH    1
 typedef struct {
@@ -739,7 +801,8 @@ int spmvHipCsrFilterRefresh(spmat* dC, spmat* dA, spmvFilterInfo* info);
  *   minAggRows (the largest and smallest aggregate; 0 when M = 0), ms.  opts == NULL: seed 0.  Synchronous on the library
  *   stream; allocates, so not capturable; temporaries freed before it returns.  M = 0 succeeds, nothing written.
  *   Refusals: those of spmvHipColourCSR (a handle that is not live, ELL, M != N, M >= 2^31 or NZ >= IRP32_LIMIT), and a NULL
- *   dAgg when M > 0.
+ *   dAgg when M > 0.  After a failed device allocation ("refused allocations" above) info is unwritten, but dAgg may have
+ *   been written in part and holds nothing to rely on.
  *
  * spmvHipAmgSetup writes into dM a handle of its own kind: a hierarchy.  It is no matrix -- every SpMV, format, build and
  *   solve entry point refuses it with a message -- and is freed by hipFreeSpmat.  It records dA's id and keeps no pointer to

@@ -6,6 +6,7 @@ the reference (src/include/SpMV.h:119-142, src/include/cudaUtils.h:60-78).
 Everything numeric happens in libspmvhip.so; numpy is only used to marshal host
 arrays.  The library is REQUIRED: there is no fallback implementation.
 """
+import contextlib
 import ctypes as C
 import math
 import os
@@ -47,6 +48,7 @@ _sigs = {
     "spmvHipVecFill": ([_vp, _sz, _u64], _i),
     "spmvHipMalloc": ([C.POINTER(_vp), _sz], _i), "spmvHipFree": ([_vp], _i),
     "spmvHipMemcpyUp": ([_vp, _vp, _sz], _i), "spmvHipMemcpyDown": ([_vp, _vp, _sz], _i),
+    "spmvHipAllocRefuse": ([C.c_long, _i], _i), "spmvHipAllocStats": ([_vp], _i),
     "spMatCpyCSR": ([C.POINTER(spmat), C.POINTER(spmat)], _i),
     "spMatCpyELL": ([C.POINTER(spmat), C.POINTER(spmat)], _i),
     "spMatCpyELLTransposed": ([C.POINTER(spmat), C.POINTER(spmat)], _i),
@@ -341,6 +343,12 @@ class spmvAmgBlockInfo(C.Structure):
     _fields_ = [("width", C.c_uint), ("bytes", C.c_ulong)]
 
 
+class spmvAllocStats(C.Structure):
+    """include/spmvHip.h `spmvAllocStats`: the ledger of the library's device allocations (for tests)."""
+    _fields_ = [("live", C.c_ulong), ("liveBytes", C.c_ulong), ("peakBytes", C.c_ulong), ("calls", C.c_ulong),
+                ("refused", C.c_ulong), ("badFrees", C.c_ulong)]
+
+
 SPMV_COLOUR_NATURAL, SPMV_COLOUR_HASH = 0, 1
 COLOUR_ORDERS = {"natural": SPMV_COLOUR_NATURAL, "hash": SPMV_COLOUR_HASH}
 SPMV_KRYLOV_CONVERGED, SPMV_KRYLOV_MAXITER, SPMV_KRYLOV_BREAKDOWN, SPMV_KRYLOV_NONFINITE = 0, 1, 2, 3
@@ -395,6 +403,29 @@ SPMV_LAUNCHERS = {
 def _check(rc, what):
     if rc != 0:
         raise SpmvHipError(f"{what} failed (EXIT_FAILURE) -- see stderr")
+
+
+def alloc_refuse(n=-1, from_then_on=False):
+    """spmvHipAllocRefuse (for tests): the n-th device allocation from now (0-based) fails, with from_then_on every later
+    one too; n = -1 disarms.  The ledger's calls and refused start again at 0 either way."""
+    _check(lib.spmvHipAllocRefuse(int(n), 1 if from_then_on else 0), "spmvHipAllocRefuse")
+
+
+def alloc_stats():
+    """spmvHipAllocStats (for tests): the ledger of the library's device allocations as a spmvAllocStats"""
+    st = spmvAllocStats()
+    _check(lib.spmvHipAllocStats(C.byref(st)), "spmvHipAllocStats")
+    return st
+
+
+@contextlib.contextmanager
+def alloc_refused(n, from_then_on=False):
+    """`with alloc_refused(n): call` -- the call's n-th device allocation fails; disarmed on the way out, whatever happens"""
+    alloc_refuse(n, from_then_on)
+    try:
+        yield
+    finally:
+        alloc_refuse(-1)
 
 
 def _amg_sweeps(v):

@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "lib.hpp"
+#include "alloc_ledger.hpp"
 
 using namespace spmvhip;
 
@@ -44,6 +45,15 @@ namespace spmvhip {
 State S;
 hipStream_t libraryStream() { return S.stream; }
 
+// The allocation chokepoint: the only two calls of the runtime's allocator in the library, behind the ledger.
+static AllocLedger& ledger() {
+    static AllocLedger l([](void** p, size_t bytes) { return (int)hipMalloc(p, bytes); }, [](void* p) { return (int)hipFree(p); },
+                         (int)hipErrorOutOfMemory);
+    return l;
+}
+hipError_t devMalloc(void** p, size_t bytes) { return (hipError_t)ledger().allocate(p, bytes); }
+hipError_t devFree(void* p) { return (hipError_t)ledger().release(p); }
+
 int probeLdsOrder(hipStream_t stream) {
     if (!ready("spmvHipProbeLdsAtomicOrder")) return -1;
     if (S.ldsOrder >= 0) return S.ldsOrder;
@@ -60,7 +70,7 @@ int probeLdsOrder(hipStream_t stream) {
     double *dV = nullptr, *dOut = nullptr;
     uint32_t* dSlot = nullptr;
     int ok = 0;
-    if (hipMalloc(&dV, sizeof h) == hipSuccess && hipMalloc(&dOut, sizeof got) == hipSuccess && hipMalloc(&dSlot, sizeof slot) == hipSuccess &&
+    if (devMalloc(&dV, sizeof h) == hipSuccess && devMalloc(&dOut, sizeof got) == hipSuccess && devMalloc(&dSlot, sizeof slot) == hipSuccess &&
         hipMemcpy(dV, h, sizeof h, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(dSlot, slot, sizeof slot, hipMemcpyHostToDevice) == hipSuccess) {
         ok = 1;
         for (int rep = 0; rep < 4 && ok; ++rep) {    // a few launches: the answer must not depend on timing
@@ -69,7 +79,7 @@ int probeLdsOrder(hipStream_t stream) {
             ok = memcmp(got, expect, sizeof got) == 0;
         }
     }
-    (void)hipFree(dV); (void)hipFree(dOut); (void)hipFree(dSlot);
+    (void)devFree(dV); (void)devFree(dOut); (void)devFree(dSlot);
     (void)hipGetLastError();
     S.ldsOrder = ok;
     return ok;
@@ -174,10 +184,10 @@ int spmvHipUnitValue(spmat* dMat, double* value) {
 // ------------------------------------------------------------------------ vectors
 int spmvHipVecAlloc(double** dVec, size_t n) {
     if (!ready("spmvHipVecAlloc") || !dVec) return EXIT_FAILURE;
-    HIP_TRY(hipMalloc(dVec, std::max<size_t>(n, 1) * sizeof(double)));
+    HIP_TRY(devMalloc(dVec, std::max<size_t>(n, 1) * sizeof(double)));
     return EXIT_SUCCESS;
 }
-int spmvHipVecFree(double* dVec) { HIP_TRY(hipFree(dVec)); return EXIT_SUCCESS; }
+int spmvHipVecFree(double* dVec) { HIP_TRY(devFree(dVec)); return EXIT_SUCCESS; }
 int spmvHipVecUp(double* dVec, const double* hVec, size_t n) {
     HIP_TRY(hipMemcpyAsync(dVec, hVec, n * sizeof(double), hipMemcpyHostToDevice, S.stream));
     HIP_TRY(hipStreamSynchronize(S.stream));
@@ -192,10 +202,10 @@ int spmvHipVecFill(double* dVec, size_t n, uint64_t pattern) { return vecFill(li
 
 int spmvHipMalloc(void** dPtr, size_t bytes) {
     if (!ready("spmvHipMalloc") || !dPtr) return EXIT_FAILURE;
-    HIP_TRY(hipMalloc(dPtr, std::max<size_t>(bytes, 1)));
+    HIP_TRY(devMalloc(dPtr, std::max<size_t>(bytes, 1)));
     return EXIT_SUCCESS;
 }
-int spmvHipFree(void* dPtr) { HIP_TRY(hipFree(dPtr)); return EXIT_SUCCESS; }
+int spmvHipFree(void* dPtr) { HIP_TRY(devFree(dPtr)); return EXIT_SUCCESS; }
 int spmvHipMemcpyUp(void* dDst, const void* hSrc, size_t bytes) {
     HIP_TRY(hipMemcpyAsync(dDst, hSrc, bytes, hipMemcpyHostToDevice, S.stream));
     HIP_TRY(hipStreamSynchronize(S.stream));
@@ -204,6 +214,14 @@ int spmvHipMemcpyUp(void* dDst, const void* hSrc, size_t bytes) {
 int spmvHipMemcpyDown(void* hDst, const void* dSrc, size_t bytes) {
     HIP_TRY(hipMemcpyAsync(hDst, dSrc, bytes, hipMemcpyDeviceToHost, S.stream));
     HIP_TRY(hipStreamSynchronize(S.stream));
+    return EXIT_SUCCESS;
+}
+
+int spmvHipAllocRefuse(long n, int fromThenOn) { ledger().arm(n, fromThenOn != 0); return EXIT_SUCCESS; }
+int spmvHipAllocStats(spmvAllocStats* stats) {
+    if (!stats) return EXIT_FAILURE;
+    const AllocCounts c = ledger().counts();
+    *stats = spmvAllocStats{c.live, c.liveBytes, c.peakBytes, c.calls, c.refused, c.badFrees};
     return EXIT_SUCCESS;
 }
 

@@ -354,7 +354,7 @@ int numericPhase(Run& r, DevMat* c) {
 
 void freeAddPlan(AddPlan* p) {
     if (!p) return;
-    (void)hipFree(p->list);
+    (void)devFree(p->list);
     delete p;
 }
 
@@ -372,7 +372,7 @@ int addBuild(double alpha, const DevMat* a, double beta, const DevMat* b, const 
     pl->nzA = a->NZ; pl->nzB = b->NZ;
     spmvAddInfo out{};
     Run r{a, b, alpha, beta, pl, st};
-    if (hipMalloc(&c->IRP, (M + 1) * 4) != hipSuccess) return fail(st, "allocation of the row pointers");
+    if (devMalloc(&c->IRP, (M + 1) * 4) != hipSuccess) return fail(st, "allocation of the row pointers");
     c->irpBytes = 4;
     uint64_t nnzC = 0;
     if (M && (a->NZ || b->NZ)) {
@@ -410,7 +410,7 @@ int addBuild(double alpha, const DevMat* a, double beta, const DevMat* b, const 
         pl->nLane = h[0]; pl->nWave = h[1]; pl->nSorted = h[2];
         out.terms = hTot[0]; out.maxRowTerms = hTot[1];
         const size_t nList = (size_t)h[0] + h[1] + h[2];
-        if (hipMalloc(&pl->list, std::max<size_t>(nList, 1) * 4) != hipSuccess) return fail(st, "allocation of the class lists");
+        if (devMalloc(&pl->list, std::max<size_t>(nList, 1) * 4) != hipSuccess) return fail(st, "allocation of the class lists");
         for (int cl = 0, at = 0; cl < 3; at += h[cl], ++cl)
             if (h[cl] && hipMemcpyAsync(pl->list + at, lists.as<uint32_t>() + (size_t)cl * M, (size_t)h[cl] * 4, hipMemcpyDeviceToDevice, st) != hipSuccess)
                 return fail(st, "class lists");
@@ -443,7 +443,7 @@ int addBuild(double alpha, const DevMat* a, double beta, const DevMat* b, const 
     // 3. numeric
     const auto t1 = std::chrono::steady_clock::now();
     c->NZ = nnzC;
-    if (hipMalloc(&c->JA, std::max<uint64_t>(nnzC, 1) * 4) != hipSuccess || hipMalloc(&c->AS, std::max<uint64_t>(nnzC, 1) * 8) != hipSuccess)
+    if (devMalloc(&c->JA, std::max<uint64_t>(nnzC, 1) * 4) != hipSuccess || devMalloc(&c->AS, std::max<uint64_t>(nnzC, 1) * 8) != hipSuccess)
         return fail(st, "allocation of the sum's arrays");
     if (numericPhase(r, c)) return EXIT_FAILURE;
     out.numericMs = msSince(t1);

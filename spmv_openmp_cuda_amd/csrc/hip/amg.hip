@@ -631,7 +631,7 @@ int levelFilter(Mode mode, AmgHierarchy* H, size_t l, spmat* cur, spmvFilterInfo
     if (build) L.theta = l ? H->lv[l - 1].theta * H->plan.thetaScale : H->plan.theta;
     const spmvFilterOpts fo{SPMV_FILTER_STRENGTH, 0, 0, L.theta, 1};
     if (build ? spmvHipCsrFilter(cur, &fo, &L.F, info) : spmvHipCsrFilterRefresh(&L.F, cur, nullptr)) return buildFail(st, module, "a level's strength filter");
-    if (build && hipMalloc(&L.dF, std::max<uint64_t>(L.M, 2) * sizeof(double)) != hipSuccess) return buildFail(st, module, "allocation of a level's vectors");
+    if (build && devMalloc(&L.dF, std::max<uint64_t>(L.M, 2) * sizeof(double)) != hipSuccess) return buildFail(st, module, "allocation of a level's vectors");
     long bad = -1;
     if (levelDinv(matOf(&L.F), L.dF, &bad, st) || bad >= 0) return buildFail(st, module, "the diagonal of a level's filtered matrix");
     return EXIT_SUCCESS;
@@ -685,10 +685,10 @@ void freeAmg(AmgHierarchy* h) {
     for (AmgLevel& l : h->lv) {
         for (spmat* m : {&l.A, &l.P, &l.R, &l.AP, &l.T, &l.D, &l.AT, &l.DAT, &l.F})
             if (m->dev) (void)hipFreeSpmat(m);
-        for (double* p : {l.dinv, l.r, l.z, l.t, l.d, l.dF, l.bt, l.bd, l.br, l.bz}) (void)hipFree(p);
-        (void)hipFree(l.coef);
-        (void)hipFree(l.perm);
-        (void)hipFree(l.colourPtr);
+        for (double* p : {l.dinv, l.r, l.z, l.t, l.d, l.dF, l.bt, l.bd, l.br, l.bz}) (void)devFree(p);
+        (void)devFree(l.coef);
+        (void)devFree(l.perm);
+        (void)devFree(l.colourPtr);
     }
     delete h;
 }
@@ -706,7 +706,7 @@ int amgBuild(spmat* hA, const spmvAmgOpts* o, const AmgPlan& plan, DevMat* m, hi
     H->nu1 = sweepsOf(o ? o->nu1 : 0, 1); H->nu2 = sweepsOf(o ? o->nu2 : 0, 1); H->nuCoarse = sweepsOf(o ? o->nuCoarse : 0, 8);
     spmvAmgInfo& info = H->info;
     auto fail = [&](const char* what) { return buildFail(st, "multigrid setup", what); };
-    auto vec = [&](double** p, uint64_t n) { return hipMalloc(p, std::max<uint64_t>(n, 2) * sizeof(double)) != hipSuccess; };
+    auto vec = [&](double** p, uint64_t n) { return devMalloc(p, std::max<uint64_t>(n, 2) * sizeof(double)) != hipSuccess; };
     H->lv.reserve(SPMV_AMG_MAX_LEVELS);                        // (a level is referred to while the next one is appended)
     H->lv.emplace_back();
     for (uint32_t l = 0;; ++l) {
@@ -736,7 +736,7 @@ int amgBuild(spmat* hA, const spmvAmgOpts* o, const AmgPlan& plan, DevMat* m, hi
         spmvAggInfo ai{};
         if (agg.alloc(L.M * 4) != hipSuccess || aggregateCsr(matOf(strengthOf(H, l, cur)), H->seed, plan.K, agg.as<uint32_t>(), &ai, st)) return fail("the aggregation");
         if (ai.aggregates == L.M) {                            // every vertex its own aggregate: nothing to coarsen
-            if (H->strength()) { (void)hipFreeSpmat(&L.F); (void)hipFree(L.dF); L.dF = nullptr; }     // the last level keeps no filtered matrix
+            if (H->strength()) { (void)hipFreeSpmat(&L.F); (void)devFree(L.dF); L.dF = nullptr; }     // the last level keeps no filtered matrix
             break;
         }
         L.nAgg = ai.aggregates;
@@ -954,7 +954,7 @@ int amgSetBlockWidth(DevMat* m, uint32_t width, hipStream_t st) {
     const size_t nl = H->lv.size();
     const uint64_t kp = (uint64_t)width + (width & 1);
     std::vector<double*> nw(4 * nl, nullptr);                  // t, d, r, z of every level
-    auto drop = [&]() { for (double* p : nw) (void)hipFree(p); return EXIT_FAILURE; };
+    auto drop = [&]() { for (double* p : nw) (void)devFree(p); return EXIT_FAILURE; };
     uint64_t bytes = 0;
     if (width) {
         if (H->lv[0].M && kp > UINT64_MAX / 8 / H->lv[0].M) {
@@ -965,7 +965,7 @@ int amgSetBlockWidth(DevMat* m, uint32_t width, hipStream_t st) {
         for (size_t l = 0; l < nl; ++l) {
             const uint64_t one = H->lv[l].M * kp * 8;
             for (size_t v = 0; v < (l ? 4u : 2u); ++v) {
-                if (hipMalloc(&nw[4 * l + v], std::max<uint64_t>(one, 16)) != hipSuccess) {
+                if (devMalloc(&nw[4 * l + v], std::max<uint64_t>(one, 16)) != hipSuccess) {
                     (void)hipGetLastError();
                     fprintf(stderr, "libspmvhip: multigrid block width: allocation of level %zu's %lu-byte block failed\n", l, (unsigned long)one);
                     return drop();
@@ -977,7 +977,7 @@ int amgSetBlockWidth(DevMat* m, uint32_t width, hipStream_t st) {
     if (hipStreamSynchronize(st) != hipSuccess) return drop();
     for (size_t l = 0; l < nl; ++l) {
         AmgLevel& L = H->lv[l];
-        for (double* p : {L.bt, L.bd, L.br, L.bz}) (void)hipFree(p);
+        for (double* p : {L.bt, L.bd, L.br, L.bz}) (void)devFree(p);
         L.bt = nw[4 * l]; L.bd = nw[4 * l + 1]; L.br = nw[4 * l + 2]; L.bz = nw[4 * l + 3];
     }
     H->info.bytes = H->info.bytes - H->blockBytes + bytes;
@@ -998,8 +998,8 @@ void amgBlockState(const DevMat* m, uint32_t* width, uint64_t* bytes, bool* gaus
 static void dropGsLists(AmgHierarchy* H, AmgLevel& L) {
     if (!L.perm) return;
     H->info.bytes -= L.M * 4 + L.hColourPtr.size() * 4;
-    (void)hipFree(L.perm);
-    (void)hipFree(L.colourPtr);
+    (void)devFree(L.perm);
+    (void)devFree(L.colourPtr);
     L.perm = L.colourPtr = nullptr;
     L.hColourPtr.clear();
     L.maxColourRows = L.longRows = 0;
@@ -1016,12 +1016,12 @@ int amgSetSmoother(DevMat* m, spmat* hA, const spmvAmgSmootherOpts* o, hipStream
     // everything new is made first: a refusal leaves the hierarchy as it was
     std::vector<ChebTable> tb(nl);
     std::vector<double2*> dev(nl, nullptr);
-    auto drop = [&]() { for (double2* p : dev) (void)hipFree(p); return EXIT_FAILURE; };
+    auto drop = [&]() { for (double2* p : dev) (void)devFree(p); return EXIT_FAILURE; };
     if (kind == SPMV_AMG_SMOOTHER_CHEBYSHEV)
         for (size_t l = 0; l < nl; ++l) {
             const uint32_t n = chebPairs(H, l, nu1, nu2, nuCoarse);
             if (levelCheb(matOf(l ? &H->lv[l].A : hA), H->lv[l], l, n, eigRatio, lambdaScale, "multigrid smoother", &tb[l], st)) return drop();
-            if (n && (hipMalloc(&dev[l], n * sizeof(double2)) != hipSuccess || chebUpload(dev[l], tb[l], st))) {
+            if (n && (devMalloc(&dev[l], n * sizeof(double2)) != hipSuccess || chebUpload(dev[l], tb[l], st))) {
                 buildFail(st, "multigrid smoother", "a level's Chebyshev table");
                 return drop();
             }
@@ -1031,7 +1031,7 @@ int amgSetSmoother(DevMat* m, spmat* hA, const spmvAmgSmootherOpts* o, hipStream
         AmgLevel& L = H->lv[l];
         dropGsLists(H, L);
         H->info.bytes -= L.nCoef * sizeof(double2);
-        (void)hipFree(L.coef);
+        (void)devFree(L.coef);
         L.coef = dev[l];
         L.nCoef = (uint32_t)tb[l].ab.size();
         L.rhoS = tb[l].rho; L.lmax = tb[l].lmax; L.lmin = tb[l].lmin;
@@ -1093,7 +1093,7 @@ int amgSetGaussSeidel(DevMat* m, spmat* hA, const spmvAmgGsOpts* o, uint32_t sma
         AmgLevel& L = H->lv[l];
         dropGsLists(H, L);
         H->info.bytes -= L.nCoef * sizeof(double2);
-        (void)hipFree(L.coef);
+        (void)devFree(L.coef);
         L.coef = nullptr; L.nCoef = 0;
         L.rhoS = L.lmax = L.lmin = 0.0;
         if (l >= gsLevels) continue;

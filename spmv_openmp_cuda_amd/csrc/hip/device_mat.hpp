@@ -122,6 +122,10 @@ struct DevMat {
     // what the last call did
     bool      iluChecked = false;
     long      iluUnsortedRow = -1;  // the first row whose columns are not strictly ascending
+    // AS holds the complete factors of a hipSpILU0CSR whose last step (the unit flag, the built formats) failed: the same
+    // call made again finishes the handle and must not factorise the factors.  Whatever writes AS clears it before it
+    // writes: spmvHipUpdateValues / ValuesChanged (updateValues) and the refreshes of a derived handle (upload.hip).
+    bool      iluPending = false;
     spmvIluInfo ilu{-1, -1, 0, 0, 0, 0, 0.0};
 };
 
@@ -343,6 +347,14 @@ inline dim3 grid2d(uint64_t blocks, unsigned threads) {
     return dim3((unsigned)gx, (unsigned)((blocks + gx - 1) / gx), 1);
 }
 
+// Every device allocation and release of the library goes through these two (abi.hip, over alloc_ledger.hpp): the ledger
+// knows what is held, and spmvHipAllocRefuse can make the n-th allocation fail.  devMalloc returns what the runtime
+// returned (a refusal leaves *p null and the runtime's sticky error set, as a failed hipMalloc does); devFree(null) is
+// nothing.
+hipError_t devMalloc(void** p, size_t bytes);
+hipError_t devFree(void* p);
+template <typename T> hipError_t devMalloc(T** p, size_t bytes) { return devMalloc(reinterpret_cast<void**>(p), bytes); }
+
 // a failed call is reported HERE, once: the runtime's sticky last-error is cleared so that the next, unrelated call's
 // hipGetLastError() does not see it (a failed hipMalloc of a format build used to make the next spmvHipVecFill "fail")
 inline bool hipOk(hipError_t e, const char* what) {
@@ -359,12 +371,12 @@ inline bool hipOk(hipError_t e, const char* what) {
 template <typename L>
 int deviceFlag(int init, hipStream_t stream, const char* kernel, uint32_t* out, L&& launch) {
     uint32_t* dFlag = nullptr;
-    HIP_TRY(hipMalloc(&dFlag, 4));
+    HIP_TRY(devMalloc(&dFlag, 4));
     bool ok = hipOk(hipMemsetAsync(dFlag, init, 4, stream), "hipMemset");
     if (ok) launch(dFlag);
     ok = ok && hipOk(hipGetLastError(), kernel) && hipOk(hipMemcpyAsync(out, dFlag, 4, hipMemcpyDeviceToHost, stream), "hipMemcpy") &&
          hipOk(hipStreamSynchronize(stream), "hipStreamSynchronize");
-    (void)hipFree(dFlag);
+    (void)devFree(dFlag);
     return ok ? EXIT_SUCCESS : EXIT_FAILURE;
 }
 

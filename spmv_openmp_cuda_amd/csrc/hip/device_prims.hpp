@@ -41,13 +41,13 @@ struct TempBuf {
     ~TempBuf() { release(); }
     void release() {
         if (!p) return;
-        (void)hipFree(p);
+        (void)devFree(p);
         if (tally) tally->cur -= n;
         p = nullptr; n = 0;
     }
     hipError_t alloc(size_t bytes) {                // a buffer that holds memory gives it back first
         release();
-        const hipError_t e = hipMalloc(&p, std::max<size_t>(bytes, 1));
+        const hipError_t e = devMalloc(&p, std::max<size_t>(bytes, 1));
         if (e != hipSuccess) { p = nullptr; return e; }
         n = bytes;
         if (tally) { tally->cur += n; tally->peak = std::max(tally->peak, tally->cur); }

@@ -320,7 +320,7 @@ int lumpPass(const DevMat* a, DevMat* c, bool build, uint32_t* dCnt, TempTally* 
             return fail(st, "lump pass");
         pl->nLong = h[0];
         if (pl->nLong) {
-            if (hipMalloc(&pl->longList, (size_t)pl->nLong * 4) != hipSuccess ||
+            if (devMalloc(&pl->longList, (size_t)pl->nLong * 4) != hipSuccess ||
                 hipMemcpyAsync(pl->longList, list.p, (size_t)pl->nLong * 4, hipMemcpyDeviceToDevice, st) != hipSuccess)
                 return fail(st, "allocation of the long rows");
         }
@@ -338,7 +338,7 @@ int lumpPass(const DevMat* a, DevMat* c, bool build, uint32_t* dCnt, TempTally* 
 
 void freeFilterPlan(FilterPlan* p) {
     if (!p) return;
-    (void)hipFree(p->mask); (void)hipFree(p->diagC); (void)hipFree(p->longList);
+    (void)devFree(p->mask); (void)devFree(p->diagC); (void)devFree(p->longList);
     delete p;
 }
 
@@ -360,7 +360,7 @@ int filterBuild(const DevMat* a, const spmvFilterOpts* o, DevMat* c, hipStream_t
     TempTally tm;
     const uint64_t nTiles = (NZ + FL_TILE - 1) / FL_TILE;
     const dim3 tiles = gridFor(nTiles, 1, FL_THREADS);
-    if (hipMalloc(&c->IRP, (M + 1) * 4) != hipSuccess) return fail(st, "allocation of the row pointers");
+    if (devMalloc(&c->IRP, (M + 1) * 4) != hipSuccess) return fail(st, "allocation of the row pointers");
     c->irpBytes = 4;
     TempBuf cnt(&tm), dpos(&tm), dval(&tm), dcount(&tm), mask(&tm), counts(&tm), base(&tm), scanTmp(&tm);
     if (cnt.alloc(4 * 4)) return fail(st, "temporary allocation");
@@ -411,7 +411,7 @@ int filterBuild(const DevMat* a, const spmvFilterOpts* o, DevMat* c, hipStream_t
     // 3. write
     c->NZ = nnzC;
     const size_t nz1 = std::max<uint64_t>(nnzC, 1);
-    if (hipMalloc(&c->JA, nz1 * 4) != hipSuccess || hipMalloc(&c->AS, nz1 * 8) != hipSuccess || hipMalloc(&c->tmap, nz1 * 4) != hipSuccess)
+    if (devMalloc(&c->JA, nz1 * 4) != hipSuccess || devMalloc(&c->AS, nz1 * 8) != hipSuccess || devMalloc(&c->tmap, nz1 * 4) != hipSuccess)
         return fail(st, "allocation of the filtered arrays");
     if (NZ) {
         hipLaunchKernelGGL(fl_write_kernel, tiles, dim3(FL_THREADS), 0, st, NZ, a->JA, reinterpret_cast<const uint64_t*>(a->AS), mask.as<uint64_t>(),
@@ -426,7 +426,7 @@ int filterBuild(const DevMat* a, const spmvFilterOpts* o, DevMat* c, hipStream_t
     }
     // 4. lump: the mask stays with the handle
     if (lump && M && NZ) {
-        if (hipMalloc(&pl->diagC, M * 4) != hipSuccess) return fail(st, "allocation of the diagonal positions");
+        if (devMalloc(&pl->diagC, M * 4) != hipSuccess) return fail(st, "allocation of the diagonal positions");
         hipLaunchKernelGGL(fl_diagc_kernel, gridFor(M), dim3(FL_THREADS), 0, st, M, dpos.as<uint32_t>(), mask.as<uint64_t>(), base.as<uint32_t>(), pl->diagC);
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return fail(st, "lump pass");
         out.tempBytes = tm.peak;

@@ -18,7 +18,7 @@ struct Cached {
     bool sameSource(const spmat* m, int k) const {
         return kind == k && M == m->M && N == m->N && NZ == m->NZ && K == m->MAX_ROW_NZ && irp == m->IRP && ja == m->JA && as == m->AS && rl == m->RL;
     }
-    void release() { hipFreeSpmat(&handle); (void)hipFree(dx); (void)hipFree(dy); dx = dy = nullptr; }
+    void release() { hipFreeSpmat(&handle); (void)devFree(dx); (void)devFree(dy); dx = dy = nullptr; }
 };
 std::map<const spmat*, Cached> g_cache;
 

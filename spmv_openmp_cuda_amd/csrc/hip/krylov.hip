@@ -203,7 +203,7 @@ struct DotWorkspace { double* p = nullptr; uint64_t blocks = 0; int dev = -1; } 
 }  // namespace
 
 void freeDotWorkspace() {
-    if (g_dot.p) (void)hipFree(g_dot.p);
+    if (g_dot.p) (void)devFree(g_dot.p);
     g_dot = DotWorkspace{};
 }
 
@@ -214,7 +214,7 @@ int dotWorkspace(uint64_t doubles, double** p) {
     if (doubles > g_dot.blocks || dev != g_dot.dev) {
         HIP_TRY(hipDeviceSynchronize());                                 // the old workspace may still be read
         freeDotWorkspace();
-        HIP_TRY(hipMalloc(&g_dot.p, doubles * sizeof(double)));
+        HIP_TRY(devMalloc(&g_dot.p, doubles * sizeof(double)));
         g_dot.blocks = doubles;
         g_dot.dev = dev;
     }

@@ -210,10 +210,10 @@ void launchVec(uint64_t n, const KState* st, const Op& op, bool vec, double* p0,
 
 struct DevBufs {
     std::vector<void*> ptrs;
-    ~DevBufs() { for (void* p : ptrs) (void)hipFree(p); }
+    ~DevBufs() { for (void* p : ptrs) (void)devFree(p); }
     template <typename T> T* alloc(size_t count) {
         void* p = nullptr;
-        if (hipMalloc(&p, std::max<size_t>(count * sizeof(T), 16)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+        if (devMalloc(&p, std::max<size_t>(count * sizeof(T), 16)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
         ptrs.push_back(p);
         return static_cast<T*>(p);
     }

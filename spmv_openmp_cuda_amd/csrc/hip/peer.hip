@@ -56,16 +56,16 @@ extern "C" {
 int spmvHipWindowCreate(size_t bytes, void** dBase, unsigned char handle[SPMV_IPC_HANDLE_BYTES]) {
     if (!dBase || !handle) return EXIT_FAILURE;
     void* p = nullptr;
-    HIP_TRY(hipMalloc(&p, bytes ? bytes : 1));
+    HIP_TRY(devMalloc(&p, bytes ? bytes : 1));
     hipIpcMemHandle_t h;
-    if (!hipOk(hipIpcGetMemHandle(&h, p), "hipIpcGetMemHandle")) { (void)hipFree(p); return EXIT_FAILURE; }
+    if (!hipOk(hipIpcGetMemHandle(&h, p), "hipIpcGetMemHandle")) { (void)devFree(p); return EXIT_FAILURE; }
     memcpy(handle, &h, SPMV_IPC_HANDLE_BYTES);
     *dBase = p;
     return EXIT_SUCCESS;
 }
 
 int spmvHipWindowFree(void* dBase) {
-    if (dBase) HIP_TRY(hipFree(dBase));
+    if (dBase) HIP_TRY(devFree(dBase));
     return EXIT_SUCCESS;
 }
 

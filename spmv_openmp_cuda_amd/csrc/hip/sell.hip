@@ -197,9 +197,9 @@ int buildSellT(DevMat* d, SellFormat* f) {
     f->nSlices = (uint32_t)(padded / SELL_C);
     TempBuf keys, keysOut, rows, sortTmp, cells, scanTmp;
     if (keys.alloc(padded * 8) || keysOut.alloc(padded * 8) || rows.alloc(padded * 4) || cells.alloc(((size_t)f->nSlices + 1) * 8)) return EXIT_FAILURE;
-    HIP_TRY(hipMalloc(&f->perm, std::max<size_t>(padded, 1) * 4));
-    HIP_TRY(hipMalloc(&f->slen, std::max<size_t>(padded, 1) * 4));
-    HIP_TRY(hipMalloc(&f->sliceOff, ((size_t)f->nSlices + 1) * 8));
+    HIP_TRY(devMalloc(&f->perm, std::max<size_t>(padded, 1) * 4));
+    HIP_TRY(devMalloc(&f->slen, std::max<size_t>(padded, 1) * 4));
+    HIP_TRY(devMalloc(&f->sliceOff, ((size_t)f->nSlices + 1) * 8));
     const dim3 gRows = grid2d((padded + 255) / 256, 256);
     const uint32_t sigma = SELL_SIGMA;              // whole slices: a window that ends inside a slice would break "first row of a slice is its longest"
     hipLaunchKernelGGL((sell_keys_kernel<I>), gRows, dim3(256), 0, nullptr, M, padded, sigma, IRP, keys.as<uint64_t>(), rows.as<uint32_t>());
@@ -209,8 +209,8 @@ int buildSellT(DevMat* d, SellFormat* f) {
     HIP_TRY(exclusiveScan(scanTmp, cells.as<uint64_t>(), f->sliceOff, (uint64_t)0, (size_t)f->nSlices + 1, nullptr));
     uint64_t total = 0;
     HIP_TRY(hipMemcpy(&total, f->sliceOff + f->nSlices, 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMalloc(&f->val, std::max<uint64_t>(total, 1) * 8));
-    HIP_TRY(hipMalloc(&f->col, std::max<uint64_t>(total, 1) * 4));
+    HIP_TRY(devMalloc(&f->val, std::max<uint64_t>(total, 1) * 8));
+    HIP_TRY(devMalloc(&f->col, std::max<uint64_t>(total, 1) * 4));
     if (f->nSlices)
         hipLaunchKernelGGL((sell_fill_kernel<I>), grid2d(((uint64_t)f->nSlices + 3) / 4, 256), dim3(256), 0, nullptr, f->nSlices,
                            f->sliceOff, f->perm, f->slen, IRP, d->JA, d->AS, f->val, f->col);
@@ -218,7 +218,7 @@ int buildSellT(DevMat* d, SellFormat* f) {
     TempBuf counter;
     if (counter.alloc(4)) return EXIT_FAILURE;
     HIP_TRY(hipMemsetAsync(counter.p, 0, 4, nullptr));
-    HIP_TRY(hipMalloc(&f->longRows, std::max<uint64_t>(std::min<uint64_t>(M, d->NZ / SELL_MAX_ROW + 1), 1) * 4));
+    HIP_TRY(devMalloc(&f->longRows, std::max<uint64_t>(std::min<uint64_t>(M, d->NZ / SELL_MAX_ROW + 1), 1) * 4));
     if (M) {
         hipLaunchKernelGGL((sell_longlist_kernel<I>), grid2d((M + 255) / 256, 256), dim3(256), 0, nullptr, M, IRP, f->longRows, counter.as<uint32_t>());
         hipLaunchKernelGGL((sell_flag_long_kernel<I>), gRows, dim3(256), 0, nullptr, padded, IRP, f->perm);
@@ -234,8 +234,8 @@ int buildSellT(DevMat* d, SellFormat* f) {
 
 void freeSell(SellFormat* f) {
     if (!f) return;
-    (void)hipFree(f->sliceOff); (void)hipFree(f->perm); (void)hipFree(f->slen); (void)hipFree(f->val); (void)hipFree(f->col);
-    (void)hipFree(f->longRows);
+    (void)devFree(f->sliceOff); (void)devFree(f->perm); (void)devFree(f->slen); (void)devFree(f->val); (void)devFree(f->col);
+    (void)devFree(f->longRows);
     delete f;
 }
 

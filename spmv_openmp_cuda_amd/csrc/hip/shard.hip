@@ -26,6 +26,9 @@
 #include "spmvHip.h"
 #include "lib.hpp"
 
+using spmvhip::devFree;
+using spmvhip::devMalloc;
+
 namespace {
 
 // the handful of RCCL entry points used, with the signatures of <rccl/rccl.h>
@@ -138,11 +141,11 @@ int spmvHipShardFree(void* handle) {
         for (int g = 0; g < sh->G; ++g) {
             const size_t k = (size_t)d * sh->G + g;
             if (k < sh->mats.size()) hipFreeSpmat(&sh->mats[k]);
-            if (k < sh->dYpad.size()) (void)hipFree(sh->dYpad[k]);
+            if (k < sh->dYpad.size()) (void)devFree(sh->dYpad[k]);
             if (k < sh->evK0.size() && sh->evK0[k]) (void)hipEventDestroy(sh->evK0[k]);
             if (k < sh->evK1.size() && sh->evK1[k]) (void)hipEventDestroy(sh->evK1[k]);
         }
-        if (d < (int)sh->dX.size()) (void)hipFree(sh->dX[d]);
+        if (d < (int)sh->dX.size()) (void)devFree(sh->dX[d]);
         if (d < (int)sh->evStart.size() && sh->evStart[d]) (void)hipEventDestroy(sh->evStart[d]);
         if (d < (int)sh->evEnd.size() && sh->evEnd[d]) (void)hipEventDestroy(sh->evEnd[d]);
         if (d < (int)sh->compute.size() && sh->compute[d]) (void)hipStreamDestroy(sh->compute[d]);
@@ -176,7 +179,7 @@ int spmvHipShardCSRGroups(spmat* host, int nDev, int groups, void** shardHandle)
     int rc = EXIT_SUCCESS;
     for (int d = 0; d < nDev && !rc; ++d) {
         if (hipSetDevice(d) != hipSuccess) { rc = EXIT_FAILURE; break; }
-        if (hipMalloc(&sh->dX[d], std::max<size_t>(sh->N, 1) * sizeof(double)) != hipSuccess ||
+        if (devMalloc(&sh->dX[d], std::max<size_t>(sh->N, 1) * sizeof(double)) != hipSuccess ||
             hipStreamCreateWithFlags(&sh->compute[d], hipStreamNonBlocking) != hipSuccess ||
             hipStreamCreateWithFlags(&sh->gather[d], hipStreamNonBlocking) != hipSuccess ||
             hipEventCreate(&sh->evStart[d]) != hipSuccess || hipEventCreate(&sh->evEnd[d]) != hipSuccess) { rc = EXIT_FAILURE; break; }
@@ -187,7 +190,7 @@ int spmvHipShardCSRGroups(spmat* host, int nDev, int groups, void** shardHandle)
             rc = spMatCpyCSR(blk, &sh->mats[k]);
             free(blk->IRP); free(blk->JA); free(blk->AS); free(blk->RL); free(blk);
             if (rc) break;
-            if (hipMalloc(&sh->dYpad[k], (size_t)nDev * std::max<ulong>(sh->maxRows[g], 1) * sizeof(double)) != hipSuccess ||
+            if (devMalloc(&sh->dYpad[k], (size_t)nDev * std::max<ulong>(sh->maxRows[g], 1) * sizeof(double)) != hipSuccess ||
                 hipEventCreate(&sh->evK0[k]) != hipSuccess || hipEventCreate(&sh->evK1[k]) != hipSuccess)
                 rc = EXIT_FAILURE;
         }

@@ -154,8 +154,12 @@ int hipSpILU0CSR(spmat* dA) {
             return EXIT_FAILURE;
         }
         d->ilu.firstBadRow = -1;
-        if (iluFactor(d, S.iluGroup, S.stream)) { ERR("%s: the factorisation failed", who); return EXIT_FAILURE; }
-        if (updateValues(dA, nullptr, true, true, S.stream, who)) return EXIT_FAILURE;
+        if (!d->iluPending && iluFactor(d, S.iluGroup, S.stream)) { ERR("%s: the factorisation failed", who); return EXIT_FAILURE; }
+        if (updateValues(dA, nullptr, true, true, S.stream, who)) {
+            d->iluPending = true;                        // (after updateValues, which clears it as every value update does)
+            ERR("%s: the factors are in place, but bringing the handle's unit flag and formats up to them failed: call again", who);
+            return EXIT_FAILURE;
+        }
     } else {
         d->ilu.zeroPivot = d->ilu.firstBadRow = -1;
         d->ilu.levels = d->ilu.launches = d->ilu.longRows = 0;

@@ -506,7 +506,7 @@ void enqueueNarrowIrp(uint64_t M, const uint64_t* irp64, uint32_t* irp, uint32_t
 
 void freeSpgemmPlan(SpgemmPlan* p) {
     if (!p) return;
-    (void)hipFree(p->list);
+    (void)devFree(p->list);
     delete p;
 }
 
@@ -522,7 +522,7 @@ int spgemmBuild(const DevMat* a, const DevMat* b, const spmvSpgemmOpts* opts, De
     pl->batchProducts = std::max<uint64_t>(clampOpt(opts ? opts->sortBudgetBytes : 0, SG_BUDGET, SG_BUDGET_MAX) / SG_PRODUCT_BYTES, 1);
     spmvSpgemmInfo out{};
     Run r{a, b, pl, st};
-    if (hipMalloc(&c->IRP, (M + 1) * 4) != hipSuccess) return fail(st, "allocation of the row pointers");
+    if (devMalloc(&c->IRP, (M + 1) * 4) != hipSuccess) return fail(st, "allocation of the row pointers");
     c->irpBytes = 4;
     uint64_t nnzC = 0;
     if (M && a->NZ && b->NZ && BN) {
@@ -560,7 +560,7 @@ int spgemmBuild(const DevMat* a, const DevMat* b, const spmvSpgemmOpts* opts, De
         pl->nWave = h[0]; pl->nGroup = h[1]; pl->nSorted = h[2];
         out.products = hTot[0]; out.maxRowProducts = hTot[1];
         const size_t nList = (size_t)h[0] + h[1] + h[2];
-        if (hipMalloc(&pl->list, std::max<size_t>(nList, 1) * 4) != hipSuccess) return fail(st, "allocation of the class lists");
+        if (devMalloc(&pl->list, std::max<size_t>(nList, 1) * 4) != hipSuccess) return fail(st, "allocation of the class lists");
         for (int cl = 0, at = 0; cl < 3; at += h[cl], ++cl)
             if (h[cl] && hipMemcpyAsync(pl->list + at, lists.as<uint32_t>() + (size_t)cl * M, (size_t)h[cl] * 4, hipMemcpyDeviceToDevice, st) != hipSuccess)
                 return fail(st, "class lists");
@@ -593,7 +593,7 @@ int spgemmBuild(const DevMat* a, const DevMat* b, const spmvSpgemmOpts* opts, De
     // 3. numeric
     const auto t1 = std::chrono::steady_clock::now();
     c->NZ = nnzC;
-    if (hipMalloc(&c->JA, std::max<uint64_t>(nnzC, 1) * 4) != hipSuccess || hipMalloc(&c->AS, std::max<uint64_t>(nnzC, 1) * 8) != hipSuccess)
+    if (devMalloc(&c->JA, std::max<uint64_t>(nnzC, 1) * 4) != hipSuccess || devMalloc(&c->AS, std::max<uint64_t>(nnzC, 1) * 8) != hipSuccess)
         return fail(st, "allocation of the product's arrays");
     if (numericPhase(r, c)) return EXIT_FAILURE;
     out.numericMs = msSince(t1);

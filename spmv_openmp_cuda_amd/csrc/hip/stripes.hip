@@ -385,12 +385,12 @@ int fillFormat(StripeFormat* f, bool wide, uint64_t nnz, unsigned colBits, const
                const uint32_t* rowOf, const double* AS, const uint64_t* dStart, uint32_t* dOverflow) {
     const uint64_t cells = f->nSteps * SB_STEP;
     f->wide = wide;
-    (void)hipFree(f->cr); (void)hipFree(f->lrowW); (void)hipFree(f->stepBase);
+    (void)devFree(f->cr); (void)devFree(f->lrowW); (void)devFree(f->stepBase);
     f->cr = nullptr; f->lrowW = nullptr; f->stepBase = nullptr;
-    if (!f->val && !f->unit) HIP_TRY(hipMalloc(&f->val, std::max<uint64_t>(cells, 1) * 8));
-    HIP_TRY(hipMalloc(&f->cr, std::max<uint64_t>(cells, 1) * 4));
-    if (wide) HIP_TRY(hipMalloc(&f->lrowW, std::max<uint64_t>(cells, 1) * 2));
-    else      HIP_TRY(hipMalloc(&f->stepBase, std::max<uint64_t>(f->nSteps, 1) * 4));
+    if (!f->val && !f->unit) HIP_TRY(devMalloc(&f->val, std::max<uint64_t>(cells, 1) * 8));
+    HIP_TRY(devMalloc(&f->cr, std::max<uint64_t>(cells, 1) * 4));
+    if (wide) HIP_TRY(devMalloc(&f->lrowW, std::max<uint64_t>(cells, 1) * 2));
+    else      HIP_TRY(devMalloc(&f->stepBase, std::max<uint64_t>(f->nSteps, 1) * 4));
     // padding entries: value 0, local row SB_NONE (skipped by the kernel: 0 * x must not turn an Inf/NaN of x into a NaN of y)
     if (f->val) HIP_TRY(hipMemsetAsync(f->val, 0, cells * 8, nullptr));
     if (cells) {
@@ -457,8 +457,8 @@ const char* sortStripeKeys(const DevMat* d, const StripeFormat* f, StripeSort& s
 
 void freeStripes(StripeFormat* f) {
     if (!f) return;
-    (void)hipFree(f->val); (void)hipFree(f->cr); (void)hipFree(f->lrowW); (void)hipFree(f->stepBase);
-    (void)hipFree(f->binRow); (void)hipFree(f->subStep); (void)hipFree(f->vmap);
+    (void)devFree(f->val); (void)devFree(f->cr); (void)devFree(f->lrowW); (void)devFree(f->stepBase);
+    (void)devFree(f->binRow); (void)devFree(f->subStep); (void)devFree(f->vmap);
     delete f;
 }
 
@@ -529,7 +529,7 @@ int buildStripes(DevMat* d, const spmvStripesOpts* opts) {
     auto fail = [&](const char* what) { (void)hipGetLastError(); fprintf(stderr, "libspmvhip: stripes: %s failed\n", what); freeStripes(f); return EXIT_FAILURE; };
     StripeSort srt;
     TempBuf dStart, dOverflow;
-    if (hipMalloc(&f->binRow, ((size_t)B + 1) * 4) || hipMalloc(&f->subStep, ((size_t)nGroups + 1) * 4) || dStart.alloc(((size_t)nGroups + 1) * 8) ||
+    if (devMalloc(&f->binRow, ((size_t)B + 1) * 4) || devMalloc(&f->subStep, ((size_t)nGroups + 1) * 4) || dStart.alloc(((size_t)nGroups + 1) * 8) ||
         dOverflow.alloc(4))
         return fail("table allocation");
     if (hipMemcpy(f->binRow, binRow.data(), ((size_t)B + 1) * 4, hipMemcpyHostToDevice)) return fail("table upload");
@@ -596,11 +596,11 @@ int stripesRefreshValues(DevMat* d, StripeFormat* f, hipStream_t stream, double*
             (void)hipGetLastError();
             fprintf(stderr, "libspmvhip: stripes: value map: %s failed\n", what);
             (void)hipStreamSynchronize(stream);
-            (void)hipFree(f->vmap);
+            (void)devFree(f->vmap);
             f->vmap = nullptr;
             return EXIT_FAILURE;
         };
-        if (hipMalloc(&f->vmap, std::max<uint64_t>(cells, 1) * 4) != hipSuccess) { f->vmap = nullptr; return fail("allocation"); }
+        if (devMalloc(&f->vmap, std::max<uint64_t>(cells, 1) * 4) != hipSuccess) { f->vmap = nullptr; return fail("allocation"); }
         const uint64_t nGroups = (uint64_t)f->B * f->subs;
         StripeSort srt;
         TempBuf dStart;

@@ -786,9 +786,9 @@ static double* prodWorkspace(size_t n, bool grow) {
     if (n <= w->cap || !grow) return n <= w->cap ? w->p : nullptr;
     (void)hipDeviceSynchronize();                   // nothing may still read the old buffer
     w->used = w->marked = false;
-    if (w->raw) (void)hipFree(w->raw);
+    if (w->raw) (void)devFree(w->raw);
     w->p = nullptr; w->raw = nullptr; w->cap = 0;
-    if (hipMalloc(&w->raw, n * sizeof(double)) != hipSuccess) { w->raw = nullptr; return nullptr; }
+    if (devMalloc(&w->raw, n * sizeof(double)) != hipSuccess) { w->raw = nullptr; return nullptr; }
     w->p = static_cast<double*>(w->raw);            // (placement relative to the other arrays, 0 ... 1 MiB offsets: no effect)
     w->cap = n;
     return w->p;
@@ -839,7 +839,7 @@ void freeTilesWorkspace() {
     for (int d = 0; d < 16; ++d)
         if (g_prod[d].p || g_prod[d].lastUse) {
             (void)hipSetDevice(d);
-            if (g_prod[d].raw) (void)hipFree(g_prod[d].raw);
+            if (g_prod[d].raw) (void)devFree(g_prod[d].raw);
             if (g_prod[d].lastUse) (void)hipEventDestroy(g_prod[d].lastUse);
             g_prod[d] = ProdWorkspace{};
         }
@@ -853,8 +853,8 @@ uint64_t tilesBinRow(const DevMat* d, const TileFormat* t, uint32_t bin) {
 
 void freeTiles(TileFormat* t) {
     if (!t) return;
-    (void)hipFree(t->slab); (void)hipFree(t->tl); (void)hipFree(t->pidx); (void)hipFree(t->vmap);
-    (void)hipFree(t->binPos); (void)hipFree(t->waveTile); (void)hipFree(t->work); (void)hipFree(t->runs); (void)hipFree(t->ready);
+    (void)devFree(t->slab); (void)devFree(t->tl); (void)devFree(t->pidx); (void)devFree(t->vmap);
+    (void)devFree(t->binPos); (void)devFree(t->waveTile); (void)devFree(t->work); (void)devFree(t->runs); (void)devFree(t->ready);
     delete t;
 }
 
@@ -946,11 +946,11 @@ static int sortIntoSlices(const DevMat* d, TileFormat* t, TileBuildTemps& tmp) {
     const auto allocT0 = std::chrono::steady_clock::now();
     const size_t offLcol = (nnz * 8 + 255) / 256 * 256, offLrow = offLcol + (nnz * 2 + 255) / 256 * 256;
     const size_t slabBytes = std::max<size_t>(offLrow + nnz * 2, nnz * sizeof(PbPay));
-    if (hipMalloc(&t->slab, slabBytes) || payB.alloc(nnz * sizeof(PbPay)) || tileStart.alloc((nTiles + 2) * 4))
+    if (devMalloc(&t->slab, slabBytes) || payB.alloc(nnz * sizeof(PbPay)) || tileStart.alloc((nTiles + 2) * 4))
         return buildFailed("format / temporary allocation (12 B per entry of temporaries while the format is built)");
     double* const prodBuf = prodWorkspace(nnz, true);
-    if (!prodBuf || hipMalloc(&t->binPos, ((size_t)t->B + 1) * 4) || hipMalloc(&t->waveTile, (size_t)t->B * (t->det ? 1 : P2_WAVES) * 4) ||
-        (t->det && hipMalloc(&t->pidx, nnz * 4)))
+    if (!prodBuf || devMalloc(&t->binPos, ((size_t)t->B + 1) * 4) || devMalloc(&t->waveTile, (size_t)t->B * (t->det ? 1 : P2_WAVES) * 4) ||
+        (t->det && devMalloc(&t->pidx, nnz * 4)))
         return buildFailed("format allocation");
     t->allocMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - allocT0).count();
     t->val  = static_cast<double*>(t->slab);
@@ -998,7 +998,7 @@ static int placeTiles(TileFormat* t, TileBuildTemps& tmp) {
     HIP_TRY(hipMemcpy(&lastFlag, flags.as<uint32_t>() + nTiles - 1, 4, hipMemcpyDeviceToHost));
     t->nList = lastIdx + lastFlag;
     if (t->nList >= P2_RUNS_FLAG) return buildFailed("tile list (more than 2^31 non-empty tiles)");
-    if (hipMalloc(&t->tl, ((size_t)t->nList + TL_PAD) * sizeof(uint2))) return buildFailed("tile-list allocation");
+    if (devMalloc(&t->tl, ((size_t)t->nList + TL_PAD) * sizeof(uint2))) return buildFailed("tile-list allocation");
     t->bytes += ((size_t)t->nList + TL_PAD) * 8;
     hipLaunchKernelGGL(pb_fill_kernel, dim3(1), dim3(256), 0, nullptr, reinterpret_cast<uint32_t*>(t->tl + t->nList), 2 * TL_PAD, 0xFFFFFFFFu);
     hipLaunchKernelGGL(pb_list_kernel, grid2d((nTiles + 255) / 256, 256), dim3(256), 0, nullptr, t->S, t->B, nnz,
@@ -1147,9 +1147,9 @@ int buildTiles(DevMat* d, const spmvTilesOpts* opts) {
     const Phase1Plan plan = planPhase1Work(sliceStart, t->chunk, t->cus);
     t->nWork = (uint32_t)plan.work.size();
     t->grid1 = plan.runs.empty() ? 0 : (uint32_t)plan.runs.size() - 1;
-    HIP_TRY(hipMalloc(&t->work, std::max<size_t>(plan.work.size(), 1) * sizeof(uint3)));
+    HIP_TRY(devMalloc(&t->work, std::max<size_t>(plan.work.size(), 1) * sizeof(uint3)));
     HIP_TRY(hipMemcpy(t->work, plan.work.data(), plan.work.size() * sizeof(uint3), hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc(&t->runs, std::max<size_t>(plan.runs.size(), 1) * sizeof(uint32_t)));
+    HIP_TRY(devMalloc(&t->runs, std::max<size_t>(plan.runs.size(), 1) * sizeof(uint32_t)));
     HIP_TRY(hipMemcpy(t->runs, plan.runs.data(), plan.runs.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     HIP_TRY(hipDeviceSynchronize());
 
@@ -1178,11 +1178,11 @@ int tilesRefreshValues(DevMat* d, TileFormat* t, hipStream_t stream, double* map
             (void)hipGetLastError();
             fprintf(stderr, "libspmvhip: tiles: value map: %s failed\n", what);
             (void)hipStreamSynchronize(stream);
-            (void)hipFree(t->vmap);
+            (void)devFree(t->vmap);
             t->vmap = nullptr;
             return EXIT_FAILURE;
         };
-        if (hipMalloc(&t->vmap, std::max<uint64_t>(nnz, 1) * 4) != hipSuccess) { t->vmap = nullptr; return fail("allocation"); }
+        if (devMalloc(&t->vmap, std::max<uint64_t>(nnz, 1) * 4) != hipSuccess) { t->vmap = nullptr; return fail("allocation"); }
         const TileFormat* other = d->tiles[!t->det];
         if (other && other->vmap) {                  // both forms share the slice-major order (the same sort): the same map
             if (hipMemcpyAsync(t->vmap, other->vmap, nnz * 4, hipMemcpyDeviceToDevice, stream) != hipSuccess) return fail("copy");
@@ -1282,7 +1282,7 @@ int enqueueTilesReducePush(const DevMat* d, TileFormat* t, double* y, int nExtra
     if (!prod || prodHandover(stream)) return EXIT_FAILURE;
     const uint32_t nb = t->apiBins();
     if (!t->ready) {
-        if (hipMalloc(&t->ready, ((size_t)nb + 1) * 4) != hipSuccess) return EXIT_FAILURE;
+        if (!hipOk(devMalloc(&t->ready, ((size_t)nb + 1) * 4), "hipMalloc of the bins' ready flags")) return EXIT_FAILURE;
         if (hipMemset(t->ready, 0, ((size_t)nb + 1) * 4) != hipSuccess) return EXIT_FAILURE;   // [nb] doubles as the failure word
         t->pushFail = t->ready + nb;
     }

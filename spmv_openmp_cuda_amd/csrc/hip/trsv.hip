@@ -31,7 +31,7 @@ namespace spmvhip {
 
 void freeTri(TriSchedule* s) {
     if (!s) return;
-    (void)hipFree(s->perm); (void)hipFree(s->diagPos); (void)hipFree(s->levelPtr);
+    (void)devFree(s->perm); (void)devFree(s->diagPos); (void)devFree(s->levelPtr);
     delete s;
 }
 
@@ -291,7 +291,7 @@ int triAnalyse(DevMat* d, int uplo, uint32_t T, hipStream_t st) {
         return rc;
     };
     const size_t m1 = std::max<uint64_t>(M, 1);
-    if (hipMalloc(&s->perm, m1 * 4) || hipMalloc(&s->diagPos, m1 * 4) || cnt.alloc(m1 * 4) || lvl.alloc(m1 * 4) ||
+    if (devMalloc(&s->perm, m1 * 4) || devMalloc(&s->diagPos, m1 * 4) || cnt.alloc(m1 * 4) || lvl.alloc(m1 * 4) ||
         order.alloc(m1 * 4) || tab.alloc((M + 2) * sizeof(uint2)) || state.alloc(16) || bad.alloc(4) ||
         key.alloc(nnz * 4) || rowOf.alloc(nnz * 4) || keysOut.alloc(nnz * 4) || depRow.alloc(nnz * 4) || depPtr.alloc((N + 1) * 4))
         return fail("allocation");
@@ -350,7 +350,7 @@ int triAnalyse(DevMat* d, int uplo, uint32_t T, hipStream_t st) {
         if (hipMemcpyAsync(s->split_h.data(), split.p, L * 4ull, hipMemcpyDeviceToHost, st) || hipStreamSynchronize(st))
             return fail("split read-back");
     }
-    if (hipMalloc(&s->levelPtr, (L + 1) * 4ull) ||
+    if (devMalloc(&s->levelPtr, (L + 1) * 4ull) ||
         hipMemcpyAsync(s->levelPtr, s->levelPtr_h.data(), (L + 1) * 4ull, hipMemcpyHostToDevice, st))
         return fail("level table upload");
     // the launch plan: runs of consecutive levels of at most T rows without a long row, a launch per other level

@@ -50,8 +50,8 @@ int buildRowBlocks2(DevMat* d, const I* IRP, uint64_t M) {
     allBase.insert(allBase.end(), base.begin(), base.end());
     d->nBlk2 = (uint32_t)allInfo.size();
     d->nLong2 = (uint32_t)longs.size();
-    HIP_TRY(hipMalloc(&d->blkInfo, std::max<size_t>(allInfo.size(), 1) * sizeof(uint4)));
-    HIP_TRY(hipMalloc(&d->blkBase, std::max<size_t>(allBase.size(), 1) * sizeof(uint64_t)));
+    HIP_TRY(devMalloc(&d->blkInfo, std::max<size_t>(allInfo.size(), 1) * sizeof(uint4)));
+    HIP_TRY(devMalloc(&d->blkBase, std::max<size_t>(allBase.size(), 1) * sizeof(uint64_t)));
     HIP_TRY(hipMemcpy(d->blkInfo, allInfo.data(), allInfo.size() * sizeof(uint4), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d->blkBase, allBase.data(), allBase.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
     return EXIT_SUCCESS;
@@ -63,9 +63,9 @@ namespace spmvhip {
 void freeDesc(DevMat* d) {
     if (!d) return;
     if (d->owns) {
-        (void)hipFree(d->IRP); (void)hipFree(d->JA); (void)hipFree(d->AS); (void)hipFree(d->RL);
+        (void)devFree(d->IRP); (void)devFree(d->JA); (void)devFree(d->AS); (void)devFree(d->RL);
     }
-    (void)hipFree(d->blkInfo); (void)hipFree(d->blkBase); (void)hipFree(d->tmap);
+    (void)devFree(d->blkInfo); (void)devFree(d->blkBase); (void)devFree(d->tmap);
     freeTri(d->tri[0]); freeTri(d->tri[1]);
     freeSpgemmPlan(d->prod);
     freeAddPlan(d->sum);
@@ -99,7 +99,7 @@ int narrowUpload(T** dDst, const ulong* hSrc, size_t n, ulong limit, const char*
         if (hSrc[i] > limit) { ERR("%s[%zu] = %lu does not fit the device index width", what, i, hSrc[i]); return EXIT_FAILURE; }
         tmp[i] = (T)hSrc[i];
     }
-    HIP_TRY(hipMalloc(dDst, std::max<size_t>(n, 1) * sizeof(T)));
+    HIP_TRY(devMalloc(dDst, std::max<size_t>(n, 1) * sizeof(T)));
     HIP_TRY(hipMemcpy(*dDst, tmp.data(), n * sizeof(T), hipMemcpyHostToDevice));
     return EXIT_SUCCESS;
 }
@@ -184,8 +184,8 @@ int uploadPitched(DevMat* d, const ulong* hJA, const double* hAS, size_t nRows, 
             ja[r * pitch + c] = (uint32_t)col;
             as[r * pitch + c] = hAS[r * nCols + c];
         }
-    HIP_TRY(hipMalloc(&d->JA, total * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&d->AS, total * sizeof(double)));
+    HIP_TRY(devMalloc(&d->JA, total * sizeof(uint32_t)));
+    HIP_TRY(devMalloc(&d->AS, total * sizeof(double)));
     HIP_TRY(hipMemcpy(d->JA, ja.data(), total * sizeof(uint32_t), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d->AS, as.data(), total * sizeof(double), hipMemcpyHostToDevice));
     d->pitch = pitch;
@@ -237,6 +237,7 @@ int updateValues(spmat* h, const double* AS, bool onDevice, bool reread, hipStre
         return EXIT_FAILURE;
     }
     const auto t0 = std::chrono::steady_clock::now();
+    d->iluPending = false;                              // whatever the values were, they are being replaced or reread
     spmvUpdateInfo info{};
     info.unitBefore = d->unit;
     const double valueBefore = d->unitValue;
@@ -312,8 +313,8 @@ static DevMat* newMappedCsr(Origin o, const DevMat* a, uint64_t M, uint64_t N, b
     t->M = M; t->N = N; t->NZ = a->NZ;
     setOrigin(t, o, a);
     const size_t nz1 = std::max<size_t>(a->NZ, 1);
-    *ok = hipOk(hipMalloc(&t->IRP, (M + 1) * 4), "hipMalloc IRP") && hipOk(hipMalloc(&t->JA, nz1 * 4), "hipMalloc JA") &&
-          hipOk(hipMalloc(&t->AS, nz1 * 8), "hipMalloc AS") && hipOk(hipMalloc(&t->tmap, nz1 * 4), "hipMalloc map");
+    *ok = hipOk(devMalloc(&t->IRP, (M + 1) * 4), "hipMalloc IRP") && hipOk(devMalloc(&t->JA, nz1 * 4), "hipMalloc JA") &&
+          hipOk(devMalloc(&t->AS, nz1 * 8), "hipMalloc AS") && hipOk(devMalloc(&t->tmap, nz1 * 4), "hipMalloc map");
     return t;
 }
 
@@ -326,6 +327,7 @@ static int mappedRefresh(const char* who, Origin o, spmat* dX, const char* xName
     if (!t) return EXIT_FAILURE;
     DevMat* a = descOf(dA, who);
     if (!a || !madeBy(t, o, a, nullptr, who, xName, "dA")) return EXIT_FAILURE;
+    t->iluPending = false;                              // AS is rewritten from here on, whatever becomes of the call
     if (enqueueGatherValues(t->AS, t->tmap, t->NZ, a->AS, S.stream)) return EXIT_FAILURE;
     if (after && after(t, a, S.stream)) { ERR("%s: recomputing the values failed", who); return EXIT_FAILURE; }
     return updateValues(dX, nullptr, true, true, S.stream, who);
@@ -348,7 +350,7 @@ int spMatCpyCSR(spmat* m, spmat* dst) {
     });
     if (!rc) rc = narrowUpload<uint32_t>(&d->JA, m->JA, m->NZ, m->N ? m->N - 1 : 0, "JA");
     if (!rc) {
-        if (!hipOk(hipMalloc(&d->AS, std::max<size_t>(m->NZ, 1) * sizeof(double)), "hipMalloc AS") ||
+        if (!hipOk(devMalloc(&d->AS, std::max<size_t>(m->NZ, 1) * sizeof(double)), "hipMalloc AS") ||
             !hipOk(hipMemcpy(d->AS, m->AS, m->NZ * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy AS")) rc = EXIT_FAILURE;
     }
     if (!rc && m->RL) rc = narrowUpload<uint32_t>(&d->RL, m->RL, m->M, 0xFFFFFFFFul, "RL");
@@ -413,9 +415,9 @@ int spmvHipCsrToEll(spmat* dCsr, int transposed, spmat* dEll) {
             return EXIT_FAILURE;
         }
     }
-    if (!hipOk(hipMalloc(&d->JA, cells * sizeof(uint32_t)), "hipMalloc ELL JA") ||
-        !hipOk(hipMalloc(&d->AS, cells * sizeof(double)), "hipMalloc ELL AS") ||
-        !hipOk(hipMalloc(&d->RL, std::max<size_t>(rows, 1) * sizeof(uint32_t)), "hipMalloc ELL RL") ||
+    if (!hipOk(devMalloc(&d->JA, cells * sizeof(uint32_t)), "hipMalloc ELL JA") ||
+        !hipOk(devMalloc(&d->AS, cells * sizeof(double)), "hipMalloc ELL AS") ||
+        !hipOk(devMalloc(&d->RL, std::max<size_t>(rows, 1) * sizeof(uint32_t)), "hipMalloc ELL RL") ||
         !hipOk(hipMemsetAsync(d->JA, 0, cells * sizeof(uint32_t), S.stream), "memset") ||
         !hipOk(hipMemsetAsync(d->AS, 0, cells * sizeof(double), S.stream), "memset")) { freeDesc(d); return EXIT_FAILURE; }
     if (rows) {
@@ -468,17 +470,17 @@ int spmvHipCsrPermute(spmat* dA, const uint32_t* dPerm, spmat* dB) {
     if (a->NZ && !a->AS) { ERR("%s: the source has no column or value array", who); return EXIT_FAILURE; }
     uint32_t* inv = nullptr;
     uint32_t bad = 0;
-    HIP_TRY(hipMalloc(&inv, std::max<size_t>(a->M, 1) * 4));
-    if (invertPerm(a->M, dPerm, inv, &bad, S.stream)) { (void)hipFree(inv); ERR("%s: checking dPerm failed", who); return EXIT_FAILURE; }
+    HIP_TRY(devMalloc(&inv, std::max<size_t>(a->M, 1) * 4));
+    if (invertPerm(a->M, dPerm, inv, &bad, S.stream)) { (void)devFree(inv); ERR("%s: checking dPerm failed", who); return EXIT_FAILURE; }
     if (bad) {
-        (void)hipFree(inv);
+        (void)devFree(inv);
         ERR("%s: dPerm is not a permutation of 0..M-1 (%s)", who, bad & 1 ? "a value >= M" : "a repeated value");
         return EXIT_FAILURE;
     }
     bool ok = false;
     DevMat* t = newMappedCsr(Origin::PERMUTATION, a, a->M, a->M, &ok);
     const int rc = finishCsr(dB, t, ok && !permuteCsr(a, inv, t, S.stream));
-    (void)hipFree(inv);
+    (void)devFree(inv);
     if (rc) ERR("%s: building the permuted matrix failed", who);
     return rc;
 }
@@ -522,6 +524,7 @@ int spmvHipSpGEMMRefresh(spmat* dC, spmat* dA, spmat* dB, spmvSpgemmInfo* info) 
     DevMat* b = a ? descOf(dB, who) : nullptr;
     if (!c || !a || !b || !madeBy(c, Origin::PRODUCT, a, b, who, "dC", "dA", "dB")) return EXIT_FAILURE;
     spmvSpgemmInfo out{};
+    c->iluPending = false;                              // AS is rewritten from here on, whatever becomes of the call
     if (spgemmRefresh(c, a, b, &out, S.stream)) { ERR("%s: recomputing the values failed", who); return EXIT_FAILURE; }
     if (updateValues(dC, nullptr, true, true, S.stream, who)) return EXIT_FAILURE;
     if (info) *info = out;
@@ -568,6 +571,7 @@ int spmvHipCsrAddRefresh(spmat* dC, double alpha, spmat* dA, double beta, spmat*
     DevMat* b = a ? descOf(dB, who) : nullptr;
     if (!c || !a || !b || !madeBy(c, Origin::SUM, a, b, who, "dC", "dA", "dB")) return EXIT_FAILURE;
     spmvAddInfo out{};
+    c->iluPending = false;                              // AS is rewritten from here on, whatever becomes of the call
     if (addRefresh(c, alpha, a, beta, b, &out, S.stream)) { ERR("%s: recomputing the values failed", who); return EXIT_FAILURE; }
     if (updateValues(dC, nullptr, true, true, S.stream, who)) return EXIT_FAILURE;
     if (info) *info = out;
