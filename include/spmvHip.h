@@ -93,8 +93,8 @@ int spmvHipMemcpyDown(void* hDst, const void* dSrc, size_t bytes);
  * next, unrelated call is judged on its own --, the source handles untouched (values, built formats, selections), and
  * the same call made again succeeds with the result it would have given at first.  And by family:
  *   a call that makes a handle (spMatCpyCSR / ELL, spmvHipAdoptCSR, spmvHipCsrToEll, spmvHipCsrTranspose, ...Permute,
- *     spmvHipSpGEMM, spmvHipCsrAdd, spmvHipCsrFilter, the three spmvHipAmgSetup*): the destination handle and info are not
- *     written, and nothing the call allocated is still held;
+ *     spmvHipSpGEMM, spmvHipCsrAdd, spmvHipCsrFilter, spmvHipCooAssemble, the three spmvHipAmgSetup*): the destination handle
+ *     and info are not written, and nothing the call allocated is still held;
  *   a format build (spmvHipBuildTiles / Stripes / Sell and their *Opt forms, the first call of a format's launcher): the
  *     handle stays a live CSR handle without that format, nothing of the format is held.  The device's product workspace of
  *     the two-phase kernel (8 B per entry of the largest matrix built), once grown, stays the library's until
@@ -103,7 +103,7 @@ int spmvHipMemcpyDown(void* hDst, const void* dSrc, size_t bytes);
  *     candidate whose format cannot be built is skipped; with nothing to allocate the call still answers, with the kernel
  *     that needs no memory of its own;
  *   spmvHipUpdateValues, spmvHipValuesChanged and the refreshes (spmvHipTransposeRefresh, ...PermuteRefresh,
- *     ...SpGEMMRefresh, ...CsrAddRefresh, ...CsrFilterRefresh, spmvHipAmgRefresh): the handle stays live with its pattern,
+ *     ...SpGEMMRefresh, ...CsrAddRefresh, ...CsrFilterRefresh, spmvHipCooAssembleRefresh, spmvHipAmgRefresh): the handle stays live with its pattern,
  *     its addresses and every built format; info is not written; the CSR values may be the new ones while a built format
  *     or a coarser level still holds the old ones.  CALL AGAIN before the handle is used: the repeated call completes it;
  *   the first hipSpTRSVCSR / hipSpTRSMCSR of a triangle, spmvHipTriAnalyse: x is not written, no schedule is left;
@@ -777,6 +777,70 @@ typedef struct {
 } spmvFilterInfo;
 int spmvHipCsrFilter(spmat* dA, const spmvFilterOpts* opts, spmat* dC, spmvFilterInfo* info);
 int spmvHipCsrFilterRefresh(spmat* dC, spmat* dA, spmvFilterInfo* info);
+/* ------------------------------------------------------------- assembly C = the sum of COO triplets */
+/* spmvHipCooAssemble writes into dC a new, independent CSR handle assembled on the device from nEntries triplets
+ * (dRow[e], dCol[e], dVal[e]) -- the element-matrix entries of a finite-element or finite-volume code: unsorted, a duplicate
+ * per shared node, constrained rows and columns masked out with SPMV_COO_SKIP.  All three arrays are device memory.  The
+ * contract is the bits of this serial loop, DESIGN.md section 36:
+ *       kept = the entries e in 0 .. nEntries-1 with dRow[e] != SPMV_COO_SKIP and dCol[e] != SPMV_COO_SKIP   (ascending e)
+ *       for i in 0 .. M-1:
+ *           the distinct columns j of the kept entries with dRow[e] == i, ASCENDING  ->  row i of C
+ *           for each such j, with e0 < e1 < ... < e_{r-1} the kept entries (i, j):
+ *               SPMV_COO_SUM:   v = dVal[e0] (copied as bits);  for t in 1 .. r-1:  v = v + dVal[e_t]   (plain adds, no FMA)
+ *               SPMV_COO_LAST:  v = dVal[e_{r-1}] (copied as bits)
+ *               C.JA[q] = j, C.AS[q] = v
+ *   Values: a sum of duplicates depends on its order in floating point, and "in input order" is the one order a caller can
+ *   reproduce.  A single entry is copied as bits: -0.0 stays -0.0, a NaN keeps its payload; where a sum is a NaN its payload
+ *   is not pinned.  Explicit zeros stay entries.  The pattern is a function of the indices alone: no value is read to decide
+ *   it, and a value at a skipped place is never read at all.  C is a function of the arrays and opts alone -- not of the run
+ *   or the grid.
+ *   Cost: the duplicates of one (i, j) -- a run -- are added by ONE lane, because their order is the contract: a call costs
+ *   at least its longest run, which info.maxRun reports.  There is no second, reordered path for long runs.
+ *   dC is like a filtered handle: u32 columns, 4-byte row pointers, its own unit detection, row blocks; its rows ascend
+ *   strictly, so ILU(0), the triangular schedules and the sum's merge path take them as they are; every CSR entry point works
+ *   on it; freed with hipFreeSpmat.  The library keeps no pointer into dRow, dCol or dVal: the caller may free them when the
+ *   call returns.  opts == NULL is {SPMV_COO_SUM, 1}.
+ *   Memory: C itself 12 B per entry of C + 4 B per row and its row blocks; with keepMap = 1 the sorted order of the kept
+ *   entries (4 B per kept entry) and the run starts (4 B per entry of C, + 4 B) for the refresh, nothing else; with keepMap
+ *   = 0 nothing is kept.  Temporaries, freed before the call returns: 24 B per entry (two 64-bit keys and two entry indices
+ *   for the sort's ping-pong) + the radix sort's workspace + 8 B per 1 024 kept entries, and without keepMap 4 B per entry of
+ *   C.  info: nEntries, skipped, nnzC, duplicates (= nEntries - skipped - nnzC), maxRun (the most entries on one (i, j)),
+ *   maxRowNnz (of C), tempBytes (peak of the temporaries), ms (wall).
+ *   Synchronous on the library stream; allocates, so not capturable.  info may be NULL.
+ *   M = 0, N = 0, nEntries = 0 and a list whose every entry is skipped succeed with a valid C (NZ = 0, SpMV +0.0); the
+ *   arrays may be NULL when nEntries == 0.
+ * spmvHipCooAssembleRefresh: new values for the SAME triplet list -- the same nEntries in the same order; the indices are
+ *   not passed again.  C.AS[q] is the loop above over the build's runs, from the new dVal, in the build's mode; a value at a
+ *   skipped place is never read.  C's pattern and device addresses stay; nothing is allocated for the assembly; then what
+ *   spmvHipValuesChanged(dC) does (formats, unit detection, a pending ILU(0) dropped).  info: the build's counts, ms of this
+ *   call, tempBytes 0.  spmvHipUpdateValues / spmvHipValuesChanged on an assembled handle behave as on a sum or a filtered one.
+ * spmvHipCsrToCoo: dRow[p] = i, dCol[p] = JA[p], dVal[p] = AS[p] for the NZ entries p of any live CSR handle in stored order
+ *   (row pointers of 4 or 8 bytes, unit-value handles included; dVal may be NULL: the pattern alone).  The arrays are the
+ *   caller's device memory, NZ elements each; the library keeps no pointer to them.  Assembling its output reproduces a
+ *   handle whose rows ascend strictly bit for bit.  Allocates nothing; synchronous on the library stream.
+ * Refused with a "libspmvhip" line and EXIT_FAILURE, dC and info untouched, nothing held -- each of these before any launch
+ *   or allocation: NULL dC; a NULL array with nEntries > 0; an unknown opts->duplicates; M or N >= 2^32 - 1; nEntries >=
+ *   IRP32_LIMIT (2^32 - 65536).  A kept entry with dRow[e] >= M or dCol[e] >= N is found on the device, before C's column
+ *   and value arrays exist: the line names the SMALLEST such e, its row and its column.  A refresh: a handle that was not made
+ *   by spmvHipCooAssemble, or was built with keepMap = 0 (the line says so); another nEntries; a NULL dVal (with nEntries
+ *   > 0).  spmvHipCsrToCoo: an ELL handle or a multigrid hierarchy; NULL dRow or dCol with NZ > 0; M >= 2^32 - 1.  No kernel
+ *   is handed a pointer these checks have not passed. */
+#define SPMV_COO_SKIP  0xFFFFFFFFu   /* an entry whose row OR column is this is left out */
+#define SPMV_COO_SUM   0             /* duplicates of (i, j) are added in input order    */
+#define SPMV_COO_LAST  1             /* the last duplicate in input order is the value   */
+typedef struct {
+    int duplicates;         /* SPMV_COO_SUM or SPMV_COO_LAST                                   */
+    int keepMap;            /* 1: keep the sorted order and the run starts for a refresh       */
+} spmvCooOpts;
+typedef struct {
+    ulong nEntries, skipped, nnzC, duplicates, maxRun, maxRowNnz;   /* duplicates = nEntries - skipped - nnzC */
+    ulong tempBytes;        /* peak of the build's temporaries */
+    double ms;
+} spmvCooInfo;
+int spmvHipCooAssemble(ulong M, ulong N, ulong nEntries, const uint32_t* dRow, const uint32_t* dCol, const double* dVal,
+                       const spmvCooOpts* opts, spmat* dC, spmvCooInfo* info);
+int spmvHipCooAssembleRefresh(spmat* dC, ulong nEntries, const double* dVal, spmvCooInfo* info);
+int spmvHipCsrToCoo(spmat* dA, uint32_t* dRow, uint32_t* dCol, double* dVal);
 /* ------------------------------------------------------------- aggregation multigrid preconditioner */
 /* Plain (unsmoothed) aggregation AMG built from the pieces above: an aggregation of the pattern, the Galerkin products by
  * spmvHipCsrTranspose / spmvHipSpGEMM, a damped-Jacobi V-cycle on serial-order SpMVs.  DESIGN.md section 24.  As everywhere

@@ -127,6 +127,9 @@ _sigs = {
     "spmvHipCsrAddRefresh": ([C.POINTER(spmat), C.c_double, C.POINTER(spmat), C.c_double, C.POINTER(spmat), _vp], _i),
     "spmvHipCsrFilter": ([C.POINTER(spmat), _vp, C.POINTER(spmat), _vp], _i),
     "spmvHipCsrFilterRefresh": ([C.POINTER(spmat), C.POINTER(spmat), _vp], _i),
+    "spmvHipCooAssemble": ([C.c_ulong, C.c_ulong, C.c_ulong, _vp, _vp, _vp, _vp, C.POINTER(spmat), _vp], _i),
+    "spmvHipCooAssembleRefresh": ([C.POINTER(spmat), C.c_ulong, _vp, _vp], _i),
+    "spmvHipCsrToCoo": ([C.POINTER(spmat), _vp, _vp, _vp], _i),
     "spmvHipAggregateCSR": ([C.POINTER(spmat), _vp, _vp, _vp], _i),
     "spmvHipAmgSetup": ([C.POINTER(spmat), _vp, C.POINTER(spmat), _vp], _i),
     "spmvHipAmgRefresh": ([C.POINTER(spmat), C.POINTER(spmat)], _i),
@@ -267,6 +270,21 @@ class spmvFilterInfo(C.Structure):
     """include/spmvHip.h `spmvFilterInfo`: what a spmvHipCsrFilter / spmvHipCsrFilterRefresh call did."""
     _fields_ = [("nnzA", C.c_ulong), ("nnzC", C.c_ulong), ("maxRowNnz", C.c_ulong), ("lumpedRows", C.c_ulong),
                 ("tempBytes", C.c_ulong), ("ms", C.c_double)]
+
+
+SPMV_COO_SKIP, SPMV_COO_SUM, SPMV_COO_LAST = 0xFFFFFFFF, 0, 1
+COO_DUPLICATES = {"sum": SPMV_COO_SUM, "last": SPMV_COO_LAST}
+
+
+class spmvCooOpts(C.Structure):
+    """include/spmvHip.h `spmvCooOpts`: what spmvHipCooAssemble does with duplicates, and whether it keeps the map of a refresh."""
+    _fields_ = [("duplicates", _i), ("keepMap", _i)]
+
+
+class spmvCooInfo(C.Structure):
+    """include/spmvHip.h `spmvCooInfo`: what a spmvHipCooAssemble / spmvHipCooAssembleRefresh call did."""
+    _fields_ = [("nEntries", C.c_ulong), ("skipped", C.c_ulong), ("nnzC", C.c_ulong), ("duplicates", C.c_ulong),
+                ("maxRun", C.c_ulong), ("maxRowNnz", C.c_ulong), ("tempBytes", C.c_ulong), ("ms", C.c_double)]
 
 
 SPMV_AMG_MAX_LEVELS, SPMV_AMG_NO_SWEEPS = 16, 0xFFFFFFFF
@@ -521,6 +539,31 @@ class _Operands:
             return n
         h = self._host(name, v, (n,))
         self.args.append((h, least))
+        return h.size
+
+    def triplets(self, name, a, n=None, index=False):
+        """an operand of the triplet calls, which have no result vector to share a buffer with: the values (float64), or with
+        index=True a row / column array.  Host call: a 1-D numpy array, an index array of any integer dtype with every
+        element -1 (the skip marker) or in [0, 2^32 - 1]; it is checked, then uploaded as float64 / uint32 into a temp() of
+        its own.  Device call: a float64 / int32 tensor under the 1-D rule, used where it lives (-1 is the skip marker's
+        bits).  Appends the device address; returns the length."""
+        if not self.host:
+            n = _device_vector(self.who, name, a, n, int32=index)
+            self.args.append(a.data_ptr())
+            return n
+        if not isinstance(a, np.ndarray) or a.ndim != 1 or (n is not None and a.size != n):
+            raise SpmvHipError(f"{self.who}: {name} must be a 1-D numpy array" + (f" of length {n}" if n is not None else "")
+                               + ", as this is a host call")
+        if index:
+            if not np.issubdtype(a.dtype, np.integer):
+                raise SpmvHipError(f"{self.who}: {name} must hold integers, not {a.dtype}")
+            skip = a == -1 if np.issubdtype(a.dtype, np.signedinteger) else np.zeros(a.shape, bool)
+            if a.size and not np.all(skip | ((a >= 0) & (a <= SPMV_COO_SKIP))):
+                raise SpmvHipError(f"{self.who}: {name} holds a value that is neither -1 nor in [0, 2^32 - 1]")
+            h = np.where(skip, SPMV_COO_SKIP, a).astype(np.uint32)
+        else:
+            h = np.ascontiguousarray(a, dtype=np.float64)
+        self.args.append(self.temp(h.nbytes, h if h.size else None).ptr.value)
         return h.size
 
     def dense(self, name, X, rows):
@@ -947,6 +990,39 @@ class DeviceMatrix:
             raise SpmvHipError("filter_info: this matrix was not made by filter()")
         return info
 
+    def assemble_refresh(self, vals):
+        """spmvHipCooAssembleRefresh: this matrix, made by assemble_coo() with keep_map=True, takes new values for the SAME
+        triplet list (same length, same order): the duplicates are added again in input order over the build's runs,
+        pattern and addresses kept, then the formats are refreshed as values_changed() does.  vals: a numpy array
+        (uploaded for the call) or a float64 device torch tensor (read where it lives)."""
+        info = spmvCooInfo()
+        with _Operands("assemble_refresh", vals) as ops:
+            n = ops.triplets("vals", vals)
+            _check(lib.spmvHipCooAssembleRefresh(C.byref(self.handle), n, *ops.args, C.byref(info)), "spmvHipCooAssembleRefresh")
+        self._coo = info
+
+    def assemble_info(self) -> "spmvCooInfo":
+        """the spmvCooInfo of the assemble_coo() that made this matrix, or of its last assemble_refresh()"""
+        info = getattr(self, "_coo", None)
+        if info is None:
+            raise SpmvHipError("assemble_info: this matrix was not made by assemble_coo()")
+        return info
+
+    def to_coo(self, as_torch=False):
+        """spmvHipCsrToCoo: (rows, cols, vals) of the NZ stored entries of this CSR matrix in stored order: numpy arrays
+        (uint32, uint32, float64), or with as_torch=True device torch tensors (int32, int32, float64) written in place."""
+        NZ = int(self.handle.NZ)
+        with _Operands("to_coo") as ops:                 # no operand: the scope that frees the download buffers
+            if as_torch:
+                torch = _torch()
+                out = [torch.empty(NZ, dtype=t, device="cuda") for t in (torch.int32, torch.int32, torch.float64)]
+            else:
+                out = [ops.temp(4 * NZ), ops.temp(4 * NZ), ops.temp(8 * NZ)]
+            _check(lib.spmvHipCsrToCoo(C.byref(self.handle), *[_dev_ptr(b) for b in out]), "spmvHipCsrToCoo")
+            if as_torch:
+                return tuple(out)
+            return tuple(b.down(t) if NZ else np.zeros(0, t) for b, t in zip(out, (np.uint32, np.uint32, np.float64)))
+
     def tril(self, k=0) -> "DeviceMatrix":
         """the entries on and below the k-th diagonal (j - i <= k), as filter("band")"""
         return self.filter("band", hi=k)
@@ -1346,6 +1422,27 @@ def spMatCpyCSR(host: HostCSR) -> DeviceMatrix:
     _check(lib.spMatCpyCSR(C.byref(host.struct), C.byref(d.handle)), "spMatCpyCSR")
     d.rows = host.M
     return d
+
+
+def assemble_coo(M, N, rows, cols, vals, duplicates="sum", keep_map=True) -> DeviceMatrix:
+    """spmvHipCooAssemble: the M x N CSR matrix assembled on the device from the triplets (rows[e], cols[e], vals[e]), as a new
+    DeviceMatrix that owns its handle, bit for bit the serial loop of include/spmvHip.h: rows ascending, the duplicates of an
+    (i, j) added in input order ("sum") or the last one taken ("last"), an entry whose row or column is the skip marker
+    left out.  The three operands are numpy arrays -- index arrays of any integer dtype, -1 or 2^32 - 1 the skip marker,
+    range-checked and uploaded as uint32 for the call -- or device torch tensors (int32, int32, float64: -1 the skip marker),
+    used in place without a copy.  keep_map: keep what assemble_refresh() needs.  assemble_info() tells what the call did."""
+    if isinstance(duplicates, str) and duplicates not in COO_DUPLICATES:
+        raise SpmvHipError(f"assemble_coo: duplicates must be one of {sorted(COO_DUPLICATES)}, not {duplicates!r}")
+    opts = spmvCooOpts(COO_DUPLICATES[duplicates] if isinstance(duplicates, str) else int(duplicates), int(bool(keep_map)))
+    c, info = DeviceMatrix(), spmvCooInfo()
+    with _Operands("assemble_coo", rows) as ops:
+        n = ops.triplets("rows", rows, index=True)
+        ops.triplets("cols", cols, n, index=True)
+        ops.triplets("vals", vals, n)
+        _check(lib.spmvHipCooAssemble(int(M), int(N), n, *ops.args, C.byref(opts), C.byref(c.handle), C.byref(info)), "spmvHipCooAssemble")
+    c.rows = int(c.handle.M)
+    c._coo = info
+    return c
 
 
 def spMatCpyELL(host: HostELL) -> DeviceMatrix:

@@ -32,7 +32,8 @@ enum class Kind : int { CSR = 0, ELL_ROWMAJOR = 1, ELL_COLMAJOR = 2 };
 // whose ids -- never pointers: a source may be freed first -- DevMat::src records: TRANSPOSE, PERMUTATION, HIERARCHY the
 // source (the level-0 matrix) in src[0], PRODUCT and SUM A and B in that order, FILTER the source in src[0].  What made a
 // handle refreshes it, from those handles only (madeBy in lib.hpp).  ELL_OF_CSR (spmvHipCsrToEll) keeps no link to its source, and its values cannot be updated.
-enum class Origin : int { UPLOADED, ADOPTED, ELL_OF_CSR, TRANSPOSE, PERMUTATION, PRODUCT, HIERARCHY, SUM, FILTER };
+// ASSEMBLED (spmvHipCooAssemble) comes from the caller's triplet arrays, not from a handle: it has no source ids.
+enum class Origin : int { UPLOADED, ADOPTED, ELL_OF_CSR, TRANSPOSE, PERMUTATION, PRODUCT, HIERARCHY, SUM, FILTER, ASSEMBLED };
 
 struct TileFormat;          // column-sliced two-phase format, tiles.hip
 struct SellFormat;          // SELL-C-sigma, sell.hip
@@ -40,6 +41,7 @@ struct StripeFormat;        // bin-wise CSC (y bins in LDS, x from the XCD's L2)
 struct SpgemmPlan;          // what a product C = A B keeps for its refresh, spgemm.hip
 struct AddPlan;             // what a sum C = alpha A + beta B keeps for its refresh, add.hip
 struct FilterPlan;          // what a filtered handle keeps for its refresh besides the map, filter.hip
+struct CooPlan;             // what a handle assembled from triplets keeps for its refresh, coo.hip
 struct AmgHierarchy;        // the levels of an aggregation multigrid preconditioner, amg.hip
 struct TempBuf;             // a scoped device buffer, device_prims.hpp
 
@@ -112,6 +114,9 @@ struct DevMat {
     AddPlan* sum = nullptr;
     // a filtered handle (spmvHipCsrFilter, filter.hip): its options and, with `lump`, the keep mask and the diagonal places
     FilterPlan* filt = nullptr;
+    // a handle assembled from triplets (spmvHipCooAssemble, coo.hip): its mode and, with keepMap, the sorted order of the
+    // kept entries and the run starts
+    CooPlan* coo = nullptr;
     // a multigrid hierarchy (spmvHipAmgSetup, amg.hip): the handle is then no matrix (no arrays, NZ = 0) and only the
     // spmvHipAmg* calls, a Krylov solve's dM and hipFreeSpmat take it
     AmgHierarchy* amg = nullptr;
@@ -231,6 +236,21 @@ int  filterRefresh(DevMat* c, const DevMat* a, hipStream_t stream);
 const spmvFilterInfo* filterInfo(const DevMat* c);
 void filterSetMaxRow(DevMat* c);
 void freeFilterPlan(FilterPlan* p);
+// C from COO triplets (coo.hip; contract in spmvHip.h, design in DESIGN.md section 36).  cooBuild fills c (kind, M and N set,
+// nothing owned) with IRP (4 B), JA, AS and the plan, NZ set, from checked arguments -- on failure it has written its line and
+// the caller frees c with whatever it holds.  cooRefresh: the values again from a new value list over the build's runs, kernels
+// only.  csrToCoo: a CSR handle's entries as triplets into the caller's arrays, kernels and copies only.  All synchronous.
+// cooInfo: what the build or the last refresh did; cooSetMaxRow takes the longest row from the finished handle; cooHasMap /
+// cooEntries: what a refresh checks.
+int  cooBuild(uint64_t nEntries, const uint32_t* dRow, const uint32_t* dCol, const double* dVal, const spmvCooOpts* opts, DevMat* c,
+              hipStream_t stream);
+int  cooRefresh(DevMat* c, const double* dVal, hipStream_t stream);
+int  csrToCoo(const DevMat* a, uint32_t* dRow, uint32_t* dCol, double* dVal, hipStream_t stream);
+const spmvCooInfo* cooInfo(const DevMat* c);
+void cooSetMaxRow(DevMat* c);
+bool cooHasMap(const DevMat* c);
+uint64_t cooEntries(const DevMat* c);
+void freeCooPlan(CooPlan* p);
 // A dense rows x k block of doubles in the form the C boundary is given, checked there (lib.hpp: denseOperand, denseShare):
 // element (i, c) at p[i*ld + c] (rowMajor) or p[c*ld + i].  Every block launcher below takes its operands as this; one that
 // only reads takes the same type.  A solver's own n x kp workspace block is Dense{p, kp, true}.

@@ -1,6 +1,6 @@
 // upload.hip -- device handles: upload, adoption of device arrays, and the handles made from other handles (CSR -> ELL,
-// transpose, permutation, product, sum, filter) with their refreshes; free; and what looks at the values of a handle (unit-value
-// detection, the value refresh).
+// transpose, permutation, product, sum, filter) with their refreshes, the handle assembled from COO triplets with its own;
+// free; and what looks at the values of a handle (unit-value detection, the value refresh).
 #include <hip/hip_runtime.h>
 #include <chrono>
 #include <cstring>
@@ -70,6 +70,7 @@ void freeDesc(DevMat* d) {
     freeSpgemmPlan(d->prod);
     freeAddPlan(d->sum);
     freeFilterPlan(d->filt);
+    freeCooPlan(d->coo);
     freeAmg(d->amg);
     freeTiles(d->tiles[0]); freeTiles(d->tiles[1]);
     freeSell(d->sell);
@@ -628,6 +629,67 @@ int spmvHipCsrFilterRefresh(spmat* dC, spmat* dA, spmvFilterInfo* info) {
     if (mappedRefresh(who, Origin::FILTER, dC, "dC", dA, filterRefresh)) return EXIT_FAILURE;
     if (info) *info = *filterInfo(static_cast<DevMat*>(dC->dev));
     return EXIT_SUCCESS;
+}
+
+// C assembled from COO triplets as a handle of its own (coo.hip builds the arrays; the contract is in spmvHip.h, the design in
+// DESIGN.md section 36).  What the host can decide is refused before any launch or allocation -- no kernel is handed a pointer
+// that has not passed here --; an entry out of range is found by the build's first pass.  dC and info are written only on success.
+int spmvHipCooAssemble(ulong M, ulong N, ulong nEntries, const uint32_t* dRow, const uint32_t* dCol, const double* dVal,
+                       const spmvCooOpts* opts, spmat* dC, spmvCooInfo* info) {
+    const char* who = "spmvHipCooAssemble";
+    if (!ready(who)) return EXIT_FAILURE;
+    if (!dC) { ERR("%s: dC is NULL", who); return EXIT_FAILURE; }
+    if (nEntries && (!dRow || !dCol || !dVal)) { ERR("%s: %s is NULL with nEntries = %lu", who, !dRow ? "dRow" : !dCol ? "dCol" : "dVal", nEntries); return EXIT_FAILURE; }
+    const spmvCooOpts o = opts ? *opts : spmvCooOpts{SPMV_COO_SUM, 1};
+    if (o.duplicates != SPMV_COO_SUM && o.duplicates != SPMV_COO_LAST) {
+        ERR("%s: duplicates = %d is neither SPMV_COO_SUM nor SPMV_COO_LAST", who, o.duplicates);
+        return EXIT_FAILURE;
+    }
+    if (M >= (1ull << 32) - 1 || N >= (1ull << 32) - 1) {
+        ERR("%s: M=%lu, N=%lu: the assembled matrix has 32-bit row and column ids", who, M, N);
+        return EXIT_FAILURE;
+    }
+    if (nEntries >= IRP32_LIMIT) {
+        ERR("%s: nEntries=%lu: the entry order and the row pointers of the assembled matrix are 32-bit (limit %lu)", who, nEntries, (unsigned long)IRP32_LIMIT);
+        return EXIT_FAILURE;
+    }
+    DevMat* c = new DevMat;
+    c->M = M; c->N = N;
+    setOrigin(c, Origin::ASSEMBLED);
+    if (finishCsr(dC, c, !cooBuild(nEntries, dRow, dCol, dVal, &o, c, S.stream))) return EXIT_FAILURE;     // (the build has written its line)
+    cooSetMaxRow(c);
+    if (info) *info = *cooInfo(c);
+    return EXIT_SUCCESS;
+}
+
+int spmvHipCooAssembleRefresh(spmat* dC, ulong nEntries, const double* dVal, spmvCooInfo* info) {
+    const char* who = "spmvHipCooAssembleRefresh";
+    if (!ready(who)) return EXIT_FAILURE;
+    if (!dC) { ERR("%s: dC is NULL", who); return EXIT_FAILURE; }
+    DevMat* c = descOf(dC, who);
+    if (!c || !madeBy(c, Origin::ASSEMBLED, nullptr, nullptr, who, "dC")) return EXIT_FAILURE;
+    if (!cooHasMap(c)) { ERR("%s: dC was assembled with keepMap = 0 and keeps no map to refresh through: assemble again", who); return EXIT_FAILURE; }
+    if (nEntries != cooEntries(c)) {
+        ERR("%s: nEntries = %lu, but dC was assembled from %lu entries: a refresh takes the same list", who, nEntries, (unsigned long)cooEntries(c));
+        return EXIT_FAILURE;
+    }
+    if (nEntries && !dVal) { ERR("%s: dVal is NULL", who); return EXIT_FAILURE; }
+    c->iluPending = false;                              // AS is rewritten from here on, whatever becomes of the call
+    if (cooRefresh(c, dVal, S.stream)) { ERR("%s: recomputing the values failed", who); return EXIT_FAILURE; }
+    if (updateValues(dC, nullptr, true, true, S.stream, who)) return EXIT_FAILURE;
+    if (info) *info = *cooInfo(c);
+    return EXIT_SUCCESS;
+}
+
+int spmvHipCsrToCoo(spmat* dA, uint32_t* dRow, uint32_t* dCol, double* dVal) {
+    const char* who = "spmvHipCsrToCoo";
+    if (!ready(who)) return EXIT_FAILURE;
+    DevMat* a = descOf(dA, who);
+    if (!a || !csrOnly(a, who, "the source is an ELL handle (only CSR handles are written as triplets)")) return EXIT_FAILURE;
+    if (a->NZ && (!dRow || !dCol)) { ERR("%s: %s is NULL with NZ = %lu", who, !dRow ? "dRow" : "dCol", (unsigned long)a->NZ); return EXIT_FAILURE; }
+    if (a->M >= (1ull << 32) - 1) { ERR("%s: M=%lu rows do not fit the 32-bit row ids of the triplets", who, (unsigned long)a->M); return EXIT_FAILURE; }
+    if (a->NZ && (!a->JA || !a->AS)) { ERR("%s: the source has no column or value array", who); return EXIT_FAILURE; }
+    return csrToCoo(a, dRow, dCol, dVal, S.stream);
 }
 
 int spmvHipUpdateValues(spmat* dMat, const double* AS, int asOnDevice) {
