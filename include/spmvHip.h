@@ -604,6 +604,75 @@ int spmvHipColourCSR(spmat* dA, const spmvColourOpts* opts, uint32_t* dColour, u
 int spmvHipCsrPermute(spmat* dA, const uint32_t* dPerm, spmat* dB);
 int spmvHipPermuteRefresh(spmat* dB, spmat* dA);
 int spmvHipVecPermute(size_t n, const uint32_t* dPerm, const double* dIn, double* dOut, int inverse);
+/* ------------------------------------------------------------- bandwidth-reducing ordering (reverse Cuthill-McKee) */
+/* spmvHipRcmCSR computes, on the device, the reverse Cuthill-McKee permutation of a square CSR handle: the ordering that
+ * brings the entries of B = P A P^T near the diagonal, which is what the SpMV kernels' x reads and the level sets of ILU(0)
+ * live on.  It feeds spmvHipCsrPermute / spmvHipVecPermute unchanged.  DESIGN.md section 37.
+ *   The result is a function of the PATTERN and the options alone, and is, word for word, the output of this loop.
+ *   Adjacency, degree and column rules are the colouring's: adj(i) = { j != i : row i stores column j, or row j stores
+ *   column i }; repeats count once, the diagonal is ignored, rows need not be sorted, column ids >= M of an adopted array
+ *   are no vertices and are skipped; deg(i) = |adj(i)|.
+ *       unvisited = all vertices; order = empty list
+ *       while unvisited is not empty:
+ *           r = the unvisited vertex of smallest (deg, id)
+ *           if start == SPMV_RCM_START_PERIPHERAL:
+ *               L = BFS level structure of r inside unvisited;  n = 1
+ *               while n <= maxPasses:
+ *                   v = the vertex of L's last level of smallest (deg, id)
+ *                   if v == r: break
+ *                   Lv = BFS level structure of v inside unvisited;  n = n + 1
+ *                   if depth(Lv) > depth(L): r = v; L = Lv
+ *                   else: break
+ *           queue = [r]; mark r visited
+ *           while queue is not empty:
+ *               u = pop front; append u to order
+ *               append to the queue, and mark visited, the unvisited j in adj(u) in ascending (deg(j), j)
+ *       perm = order reversed as a whole          (forward != 0: order itself, plain Cuthill-McKee)
+ *   opts == NULL: PERIPHERAL, reversed; maxPasses = 0 means 8.
+ *   dPerm[new] = old, M words: the argument of spmvHipCsrPermute / spmvHipVecPermute.  It may be NULL (only info is wanted).
+ *   info: components; levels (of the ordering BFS, summed over the components); startBfs (BFS runs spent finding starts: the
+ *   n of the loop, summed); maxFrontier (the largest level of the ordering BFS); longRows (vertices with more than 64
+ *   adjacency entries: a wavefront expands each); symmetric (1: every row ascends strictly and the stored pattern is
+ *   structurally symmetric, so A's own arrays served as the adjacency; 0: the deduplicated pattern of A + A^T was built,
+ *   68 B/nnz while it is built, 8 B/nnz + 8 B/row kept until the call returns); bandwidthBefore / bandwidthAfter (max |i - j|
+ *   over the stored entries with both ids < M, in A's numbering and in the new one); launches and hostChecks (kernel
+ *   launches and read-backs of the device state: the only two figures that may depend on the variant); ms (wall time).
+ *   Levels of at most T vertices whose degrees sum to at most 2048 are expanded, one after the other, inside one launch of
+ *   one workgroup, which also holds the loop's state; any other ("wide") level takes a launch over its frontier and a
+ *   launch of that workgroup to take the result in.  Read-backs (hostChecks): one per launch of the workgroup -- so one per
+ *   run of thin levels and one per wide level, of the start search or of the ordering --, one more per wide level of the
+ *   ordering (the size of the next level, which its radix sort needs on the host), and one for the figures of info: two
+ *   per wide ordering level where one would do if the host kept consecutive wide levels to itself.
+ *   T = 1024 unless spmvHipSetVariant("spmvHipRcmCSR", T); no word of dPerm depends on it.  The components are taken one
+ *   after the other by that one workgroup, tens of microseconds each: vertices without a neighbour are placed all at once,
+ *   but a graph of many small components is slow here (DESIGN.md section 37 has 20 000 disjoint edges measured).
+ *   Synchronous on the library stream; allocates, so not capturable; every temporary (32 B/row, 16 B/row more once a wide
+ *   level is sorted, 4 B/nnz, the adjacency above, the sorts' workspaces) is freed before it returns.  M = 0 succeeds with
+ *   nothing written to dPerm.
+ * Refused with a message and EXIT_FAILURE, outputs untouched: a NULL handle; a handle that is not live; ELL handles; M != N;
+ *   M >= 2^31 or NZ >= IRP32_LIMIT; an unknown start.  (After a failed device allocation -- "refused allocations" above --
+ *   info is left unwritten and dPerm holds nothing to rely on, as for spmvHipColourCSR.) */
+#define SPMV_RCM_START_MIN_DEGREE 0
+#define SPMV_RCM_START_PERIPHERAL 1
+typedef struct {
+    int      start;         /* SPMV_RCM_START_MIN_DEGREE or SPMV_RCM_START_PERIPHERAL         */
+    unsigned maxPasses;     /* BFS runs of the start search per component; 0: 8              */
+    int      forward;       /* != 0: the order itself (Cuthill-McKee), not reversed          */
+} spmvRcmOpts;
+typedef struct {
+    ulong  components;      /* connected components of the adjacency                         */
+    ulong  levels;          /* levels of the ordering BFS, summed over the components        */
+    ulong  startBfs;        /* BFS runs spent finding starts                                 */
+    ulong  maxFrontier;     /* the largest level of the ordering BFS                         */
+    ulong  longRows;        /* vertices expanded by a wavefront each                         */
+    int    symmetric;       /* 1: A's own arrays served as the adjacency                     */
+    ulong  bandwidthBefore; /* max |i - j| over the stored entries, A's numbering            */
+    ulong  bandwidthAfter;  /* ... in the new numbering                                      */
+    ulong  launches;        /* kernel launches of the call                                   */
+    ulong  hostChecks;      /* read-backs of the device state                                */
+    double ms;              /* wall time of the call                                         */
+} spmvRcmInfo;
+int spmvHipRcmCSR(spmat* dA, const spmvRcmOpts* opts, uint32_t* dPerm, spmvRcmInfo* info);
 /* ------------------------------------------------------------- sparse matrix product C = A B */
 /* spmvHipSpGEMM writes into dC a new, independent CSR handle of C = A B.  A name is a contract, and the contract is the
  * bits of this serial loop on the two handles' arrays (IRP, JA, AS as stored):
@@ -1446,6 +1515,9 @@ int spmvHipProbeLdsAtomicOrder(void);
  *                             (default 0).  x does not change by a bit.
  *   spmvHipColourCSR          K, 1..4096: rounds enqueued per read-back of the colouring's device state (default 16,
  *                             unmeasured).  No colour changes.
+ *   spmvHipRcmCSR             T, 0 and up, clamped to 1024: levels of at most T vertices are expanded one after the other
+ *                             inside one launch of one workgroup (default 1024; 0 = never: every level with an edge takes
+ *                             a launch over its frontier and a read-back).  No word of dPerm changes.
  *   spmvHipAmgApply           n, 0..4096: hierarchies set up by spmvHipAmgSetupSmoothed AFTER the call correct in one fused
  *                             kernel on every level whose prolongator has no row longer than n entries (default 0 = never
  *                             fused, an SpMV and an add: the faster form on the 5 M-row Laplacian, DESIGN.md section 28;

@@ -121,6 +121,7 @@ _sigs = {
     "spmvHipCsrPermute": ([C.POINTER(spmat), _vp, C.POINTER(spmat)], _i),
     "spmvHipPermuteRefresh": ([C.POINTER(spmat), C.POINTER(spmat)], _i),
     "spmvHipVecPermute": ([_sz, _vp, _vp, _vp, _i], _i),
+    "spmvHipRcmCSR": ([C.POINTER(spmat), _vp, _vp, _vp], _i),
     "spmvHipSpGEMM": ([C.POINTER(spmat), C.POINTER(spmat), _vp, C.POINTER(spmat), _vp], _i),
     "spmvHipSpGEMMRefresh": ([C.POINTER(spmat), C.POINTER(spmat), C.POINTER(spmat), _vp], _i),
     "spmvHipCsrAdd": ([C.c_double, C.POINTER(spmat), C.c_double, C.POINTER(spmat), _vp, C.POINTER(spmat), _vp], _i),
@@ -230,6 +231,18 @@ class spmvColourInfo(C.Structure):
     """include/spmvHip.h `spmvColourInfo`: what a spmvHipColourCSR call did."""
     _fields_ = [("colours", C.c_ulong), ("rounds", C.c_ulong), ("hostChecks", C.c_ulong), ("maxColourRows", C.c_ulong),
                 ("longRows", C.c_ulong), ("symmetric", _i), ("ms", C.c_double)]
+
+
+class spmvRcmOpts(C.Structure):
+    """include/spmvHip.h `spmvRcmOpts`: the start rule, the passes of the start search (0: 8), forward != 0 for the unreversed order."""
+    _fields_ = [("start", _i), ("maxPasses", C.c_uint), ("forward", _i)]
+
+
+class spmvRcmInfo(C.Structure):
+    """include/spmvHip.h `spmvRcmInfo`: what a spmvHipRcmCSR call did."""
+    _fields_ = [("components", C.c_ulong), ("levels", C.c_ulong), ("startBfs", C.c_ulong), ("maxFrontier", C.c_ulong),
+                ("longRows", C.c_ulong), ("symmetric", _i), ("bandwidthBefore", C.c_ulong), ("bandwidthAfter", C.c_ulong),
+                ("launches", C.c_ulong), ("hostChecks", C.c_ulong), ("ms", C.c_double)]
 
 
 class spmvSpgemmOpts(C.Structure):
@@ -369,6 +382,8 @@ class spmvAllocStats(C.Structure):
 
 SPMV_COLOUR_NATURAL, SPMV_COLOUR_HASH = 0, 1
 COLOUR_ORDERS = {"natural": SPMV_COLOUR_NATURAL, "hash": SPMV_COLOUR_HASH}
+SPMV_RCM_START_MIN_DEGREE, SPMV_RCM_START_PERIPHERAL = 0, 1
+RCM_STARTS = {"min_degree": SPMV_RCM_START_MIN_DEGREE, "peripheral": SPMV_RCM_START_PERIPHERAL}
 SPMV_KRYLOV_CONVERGED, SPMV_KRYLOV_MAXITER, SPMV_KRYLOV_BREAKDOWN, SPMV_KRYLOV_NONFINITE = 0, 1, 2, 3
 KRYLOV_STATUS = {0: "converged", 1: "maxiter", 2: "breakdown", 3: "nonfinite"}
 
@@ -878,12 +893,28 @@ class DeviceMatrix:
             ops.keep()                                   # the Colouring owns the buffers from here
         return Colouring(perm, colours, info)
 
+    def rcm(self, start="peripheral", max_passes=0, forward=False, as_torch=False) -> "Ordering":
+        """spmvHipRcmCSR: the reverse Cuthill-McKee ordering of this square matrix, a function of its pattern and the options
+        alone (include/spmvHip.h states the loop).  start: "peripheral" or "min_degree"; max_passes: BFS runs of the start
+        search per component (0: 8); forward: the unreversed order.  Returns an Ordering: `perm` (perm[new] = old: the
+        argument of permute() and permute_vector()), `info` (spmvRcmInfo) and free().  perm is a DeviceBuffer of uint32, or
+        an int32 device torch tensor with as_torch=True."""
+        if start not in RCM_STARTS:
+            raise SpmvHipError(f"rcm: start must be one of {sorted(RCM_STARTS)}, not {start!r}")
+        M = int(self.handle.M)
+        opts, info = spmvRcmOpts(RCM_STARTS[start], int(max_passes), 1 if forward else 0), spmvRcmInfo()
+        with _Operands("rcm") as ops:                    # no operand: the scope that frees the buffer if the call fails
+            perm = _torch().empty(M, dtype=_torch().int32, device="cuda") if as_torch else ops.temp(4 * M)
+            _check(lib.spmvHipRcmCSR(C.byref(self.handle), C.byref(opts), _dev_ptr(perm), C.byref(info)), "spmvHipRcmCSR")
+            ops.keep()                                   # the Ordering owns the buffer from here
+        return Ordering(perm, info)
+
     def permute(self, perm) -> "DeviceMatrix":
         """spmvHipCsrPermute: B = P A P^T as a new DeviceMatrix that owns its handle; row r of B is row perm[r] of this
-        matrix, columns renumbered alike and sorted ascending (stable for repeats).  perm: a Colouring, a DeviceBuffer of
-        M uint32, an int32 device torch tensor, or a numpy array (uploaded for the call)."""
+        matrix, columns renumbered alike and sorted ascending (stable for repeats).  perm: a Colouring, an Ordering, a
+        DeviceBuffer of M uint32, an int32 device torch tensor, or a numpy array (uploaded for the call)."""
         M = int(self.handle.M)
-        perm = perm.perm if isinstance(perm, Colouring) else perm
+        perm = perm.perm if isinstance(perm, (Colouring, Ordering)) else perm
         b = DeviceMatrix()
         with _Operands("permute") as ops:                # no operand: the scope that frees an uploaded perm
             if isinstance(perm, np.ndarray):
@@ -1378,6 +1409,18 @@ class Colouring:
         self.perm = self.colours = None
 
 
+class Ordering:
+    """What DeviceMatrix.rcm() returns: the device array `perm` and `info`."""
+
+    def __init__(self, perm, info):
+        self.perm, self.info = perm, info
+
+    def free(self):
+        if isinstance(self.perm, DeviceBuffer):
+            self.perm.free()
+        self.perm = None
+
+
 def _dev_ptr(b):
     """the device address of a DeviceBuffer or a torch tensor (None stays None)"""
     if b is None:
@@ -1392,10 +1435,10 @@ def _perm_len(perm, who):
 
 def permute_vector(perm, v, inverse=False, out=None):
     """spmvHipVecPermute: forward out[r] = v[perm[r]] (b' = P b), inverse out[perm[r]] = v[r] (x = P^T x'); bits are copied.
-    perm: a Colouring, a DeviceBuffer of uint32 or an int32 device torch tensor.  v: a 1-D float64 device torch tensor with
-    unit stride (any element offset) -> a torch tensor, `out` if given (same rules, not v itself); or a numpy array ->
-    uploaded, permuted, returned as numpy.  Runs on the library stream."""
-    perm = perm.perm if isinstance(perm, Colouring) else perm
+    perm: a Colouring, an Ordering, a DeviceBuffer of uint32 or an int32 device torch tensor.  v: a 1-D float64 device torch
+    tensor with unit stride (any element offset) -> a torch tensor, `out` if given (same rules, not v itself); or a numpy
+    array -> uploaded, permuted, returned as numpy.  Runs on the library stream."""
+    perm = perm.perm if isinstance(perm, (Colouring, Ordering)) else perm
     n = _perm_len(perm, "permute_vector")
     with _Operands("permute_vector", v) as ops:
         ops.vector("v", v, n)

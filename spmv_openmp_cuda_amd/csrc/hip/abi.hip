@@ -163,6 +163,7 @@ int spmvHipSetVariant(const char* launcher, int variant) {
     if (!strcmp(launcher, "hipSpGMRESCSR") && (variant == 0 || variant == 1)) { S.gmresFused = variant; return EXIT_SUCCESS; }
     if (!strcmp(launcher, "spmvHipColourCSR") && variant >= 1 && variant <= 4096) { S.colourK = (uint32_t)variant; return EXIT_SUCCESS; }
     if (!strcmp(launcher, "spmvHipAggregateCSR") && variant >= 1 && variant <= 4096) { S.aggK = (uint32_t)variant; return EXIT_SUCCESS; }
+    if (!strcmp(launcher, "spmvHipRcmCSR") && variant >= 0) { S.rcmT = (uint32_t)std::min(variant, 1024); return EXIT_SUCCESS; }
     if (!strcmp(launcher, "spmvHipAmgApply") && variant >= 0 && variant <= 4096) { S.amgFuseMax = (uint32_t)variant; return EXIT_SUCCESS; }
     if (!strcmp(launcher, "spmvHipAmgSetGaussSeidel") && variant >= 0 && variant <= 65536) { S.amgGsSmallRows = (uint32_t)variant; return EXIT_SUCCESS; }
     if (!strcmp(launcher, "spmvHipAmgGaussSeidel") && (variant == 0 || variant == 1 || variant == 4 || variant == 8 || variant == 16 || variant == 32 || variant == 64)) {

@@ -212,6 +212,12 @@ int  colourCsr(const DevMat* a, int order, uint32_t seed, uint32_t K, uint32_t* 
 int  invertPerm(uint64_t M, const uint32_t* perm, uint32_t* inv, uint32_t* bad, hipStream_t stream);
 int  permuteCsr(const DevMat* a, const uint32_t* inv, DevMat* t, hipStream_t stream);
 int  enqueueVecPermute(uint64_t n, const uint32_t* perm, const double* in, double* out, int inverse, hipStream_t stream);
+// Reverse Cuthill-McKee ordering (rcm.hip; contract in spmvHip.h, design in DESIGN.md section 37) of the checked square handle:
+// peripheral != 0 searches a pseudo-peripheral start in at most maxPasses (>= 1) passes, forward != 0 leaves the order
+// unreversed, T (at most 1024; 0: never) is the frontier up to which the single-workgroup run expands a level itself.  dPerm
+// may be null, info not; synchronous, allocates, temporaries freed before it returns; info is written on success only.
+int  rcmCsr(const DevMat* a, int peripheral, uint32_t maxPasses, int forward, uint32_t T, uint32_t* dPerm, spmvRcmInfo* info,
+            hipStream_t stream);
 // C = A B (spgemm.hip; contract in spmvHip.h, design in DESIGN.md section 22).  spgemmBuild: c has kind, M and N set and owns
 // nothing; on success it owns IRP (4 B), JA, AS and the plan, with NZ set; on failure the caller frees c with whatever it
 // holds.  spgemmRefresh: the numeric phase again into c's arrays.  Both synchronous, temporaries freed before they return.

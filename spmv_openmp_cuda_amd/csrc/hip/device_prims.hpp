@@ -1,5 +1,5 @@
 // device_prims.hpp -- what a build step on the device gets its temporaries, sorts and scans from (library-private; the
-// format files tiles / stripes / sell and transpose, trsv, ilu0, colour, spgemm, add include it after kernels.hpp).
+// format files tiles / stripes / sell and transpose, trsv, ilu0, colour, rcm, spgemm, add include it after kernels.hpp).
 //
 //   TempBuf                     one scoped device buffer; with a TempTally it keeps the bytes held and their peak
 //   sortPairs / sortKeys /      rocPRIM's "two-call" algorithms in one call: the size query, the workspace (grown only

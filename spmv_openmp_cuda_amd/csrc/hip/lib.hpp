@@ -26,6 +26,7 @@ struct State {
     int         gmresFused = 0;         // hipSpGMRESCSR: fold the first CGS2 update into the second projection
     uint32_t    colourK = 16;           // spmvHipColourCSR: rounds per host check
     uint32_t    aggK = 16;              // spmvHipAggregateCSR: rounds per host check
+    uint32_t    rcmT = 1024;            // spmvHipRcmCSR: T, the frontier up to which one workgroup carries on
     uint32_t    amgFuseMax = 0;         // spmvHipAmgSetupSmoothed: the longest row of P_l that the fused correction takes; 0: never
                                         // fused, the form that measured faster
     uint32_t    amgGsSmallRows = 1024;  // spmvHipAmgSetGaussSeidel: a level of at most this many rows sweeps in one workgroup; 0: never

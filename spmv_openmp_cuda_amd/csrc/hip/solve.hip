@@ -1,6 +1,6 @@
-// solve.hip -- the solver side of the extern "C" boundary: triangular solves, ILU(0), the multi-colour ordering and the
-// vector permutation, the dots, aggregation multigrid, and the three Krylov solvers.  The algorithm files (trsv.hip,
-// ilu0.hip, colour.hip, krylov.hip, gmres.hip, aggregate.hip, amg.hip) build and launch; here are the checks, the library's settings
+// solve.hip -- the solver side of the extern "C" boundary: triangular solves, ILU(0), the multi-colour ordering, the reverse
+// Cuthill-McKee ordering and the vector permutation, the dots, aggregation multigrid, and the three Krylov solvers.  The algorithm
+// files (trsv.hip, ilu0.hip, colour.hip, rcm.hip, krylov.hip, gmres.hip, aggregate.hip, amg.hip) build and launch; here are the checks, the library's settings
 // handed down as arguments, and the timing bracket.  Contracts in spmvHip.h, designs in DESIGN.md sections 17 to 21 and 24.
 #include <hip/hip_runtime.h>
 #include <chrono>
@@ -186,6 +186,23 @@ int spmvHipColourCSR(spmat* dA, const spmvColourOpts* opts, uint32_t* dColour, u
     const int order = opts ? opts->order : SPMV_COLOUR_NATURAL;
     if (order != SPMV_COLOUR_NATURAL && order != SPMV_COLOUR_HASH) { ERR("%s: unknown order %d", who, order); return EXIT_FAILURE; }
     if (colourCsr(d, order, opts ? opts->seed : 0u, S.colourK, dColour, dPerm, info, S.stream)) { ERR("%s: the colouring failed", who); return EXIT_FAILURE; }
+    return EXIT_SUCCESS;
+}
+
+// ---- reverse Cuthill-McKee ordering
+int spmvHipRcmCSR(spmat* dA, const spmvRcmOpts* opts, uint32_t* dPerm, spmvRcmInfo* info) {
+    const char* who = "spmvHipRcmCSR";
+    DevMat* d = squareCsrOf(dA, who, "the handle is an ELL handle (only CSR handles are ordered)");
+    if (!d) return EXIT_FAILURE;
+    const int start = opts ? opts->start : SPMV_RCM_START_PERIPHERAL;
+    if (start != SPMV_RCM_START_MIN_DEGREE && start != SPMV_RCM_START_PERIPHERAL) { ERR("%s: unknown start %d", who, start); return EXIT_FAILURE; }
+    const unsigned maxPasses = opts && opts->maxPasses ? opts->maxPasses : 8u;
+    spmvRcmInfo out{};
+    if (rcmCsr(d, start == SPMV_RCM_START_PERIPHERAL, maxPasses, opts && opts->forward, S.rcmT, dPerm, &out, S.stream)) {
+        ERR("%s: the ordering failed", who);
+        return EXIT_FAILURE;
+    }
+    if (info) *info = out;
     return EXIT_SUCCESS;
 }
 
