@@ -93,7 +93,7 @@ int spmvHipMemcpyDown(void* hDst, const void* dSrc, size_t bytes);
  * next, unrelated call is judged on its own --, the source handles untouched (values, built formats, selections), and
  * the same call made again succeeds with the result it would have given at first.  And by family:
  *   a call that makes a handle (spMatCpyCSR / ELL, spmvHipAdoptCSR, spmvHipCsrToEll, spmvHipCsrTranspose, ...Permute,
- *     spmvHipSpGEMM, spmvHipCsrAdd, spmvHipCsrFilter, spmvHipCooAssemble, the three spmvHipAmgSetup*): the destination handle
+ *     spmvHipSpGEMM, spmvHipCsrAdd, spmvHipCsrFilter, spmvHipCooAssemble, spmvHipFsaiSetup, the three spmvHipAmgSetup*): the destination handle
  *     and info are not written, and nothing the call allocated is still held;
  *   a format build (spmvHipBuildTiles / Stripes / Sell and their *Opt forms, the first call of a format's launcher): the
  *     handle stays a live CSR handle without that format, nothing of the format is held.  The device's product workspace of
@@ -103,7 +103,7 @@ int spmvHipMemcpyDown(void* hDst, const void* dSrc, size_t bytes);
  *     candidate whose format cannot be built is skipped; with nothing to allocate the call still answers, with the kernel
  *     that needs no memory of its own;
  *   spmvHipUpdateValues, spmvHipValuesChanged and the refreshes (spmvHipTransposeRefresh, ...PermuteRefresh,
- *     ...SpGEMMRefresh, ...CsrAddRefresh, ...CsrFilterRefresh, spmvHipCooAssembleRefresh, spmvHipAmgRefresh): the handle stays live with its pattern,
+ *     ...SpGEMMRefresh, ...CsrAddRefresh, ...CsrFilterRefresh, spmvHipCooAssembleRefresh, spmvHipFsaiRefresh, spmvHipAmgRefresh): the handle stays live with its pattern,
  *     its addresses and every built format; info is not written; the CSR values may be the new ones while a built format
  *     or a coarser level still holds the old ones.  CALL AGAIN before the handle is used: the repeated call completes it;
  *   the first hipSpTRSVCSR / hipSpTRSMCSR of a triangle, spmvHipTriAnalyse: x is not written, no schedule is left;
@@ -311,6 +311,73 @@ typedef struct {
 } spmvIluInfo;
 int hipSpILU0CSR(spmat* dA);
 int spmvHipIlu0Info(spmat* dA, spmvIluInfo* info);
+/* ------------------------------------------------------------- approximate-inverse preconditioner (FSAI) */
+/* spmvHipFsaiSetup makes the factorised sparse approximate inverse of a square device CSR handle (Kolotilina-Yeremin): a
+ * sparse lower-triangular G with G^T G ~ A^-1, as a live CSR handle dG of its own.  M^-1 v = G^T (G v) is two serial-order
+ * SpMVs: no level sets, no analysis, no dependence between rows.  G A G^T has a unit diagonal, so G contains the Jacobi
+ * scaling, and M^-1 is symmetric positive definite by construction: CG may use it.  DESIGN.md section 38.
+ *   dA: only its LOWER triangle including the diagonal is ever read; symmetry is the caller's promise, as it is for CG.
+ *   dS: a pattern handle of the same size (its values are not read), or NULL for dA itself.  The caller sets the quality by
+ *   the pattern: tril(A), tril(A A) by spmvHipSpGEMM, a thresholded one by spmvHipCsrFilter.  dS need not outlive the call.
+ *   Both must have strictly ascending rows (sorted, no repeated column): hipSpILU0CSR's check, made once per handle.
+ * For row i, P = (p_0 < p_1 < ... < p_{n-1} = i) is the columns j < i that row i of dS stores, then i itself, whether or not
+ * dS stores the diagonal.  Row i of G stores exactly the columns P, ascending, the diagonal last.  Its values are
+ * g[0 .. n-1] of this loop, in IEEE double with no FMA contraction and with sqrt and / correctly rounded:
+ *     B[s][t] = the value of the stored entry (p_s, p_t) of dA, +0.0 if row p_s stores no column p_t      (0 <= t <= s < n)
+ *     for k = 0 .. n-1:
+ *         if !(B[k][k] > 0) or B[k][k] == +inf:  the row is BAD, stop
+ *         B[k][k] = sqrt(B[k][k])
+ *         for s = k+1 .. n-1:  B[s][k] = B[s][k] / B[k][k]
+ *         for t = k+1 .. n-1, s = t .. n-1:  B[s][t] = B[s][t] - B[s][k]*B[t][k]     -- the product rounded, then the difference
+ *     y[n-1] = (1.0 / B[n-1][n-1]) / B[n-1][n-1]
+ *     for t = n-2 down to 0:
+ *         acc = +0.0;  for s = n-1 down to t+1:  acc = acc + B[s][t]*y[s]
+ *         y[t] = (0.0 - acc) / B[t][t]
+ *     d = sqrt(y[n-1]);  if !(d > 0) or d == +inf: the row is BAD
+ *     g[t] = y[t] / d                                                                    (t = 0 .. n-1)
+ *     BAD row: g[0 .. n-2] = +0.0, g[n-1] = 1.0
+ *   Both halves are the right-looking forms: every entry of B receives its updates one at a time in ascending k, and every
+ *   acc receives its terms in descending s, whichever lane does the work.  (The Crout form sums first and subtracts once:
+ *   other bits.)  The group of lanes that computes a row (4, 16 or 64; spmvFsaiOpts.lanesPerRow forces one, 0 is the
+ *   built-in choice by the mean row of G) does not change a bit.
+ *   A pattern row with n > SPMV_FSAI_MAX_ROW is refused, the message naming the first such row: filter the pattern.
+ *   A BAD row is NOT a refusal: the handle is made, and info.badRows / info.firstBadRow (-1: none) report it.
+ *   M = 0 succeeds with no kernel.
+ * dG is an ordinary live CSR handle (SpMV, transpose, product, filter, spmvHipCsrToCoo take it: G A G^T can be formed with
+ *   the public product) that privately owns G^T -- the handle spmvHipCsrTranspose would make of G -- and one M-vector of
+ *   workspace; hipFreeSpmat(dG) frees all three.  Synchronous, allocates: not capturable.
+ * spmvHipFsaiRefresh(dG, dA): dA -- the handle of the setup -- has new values on the same pattern at the same addresses.  The
+ *   values of G are computed again in place over the setup's columns, G^T takes them through its map, and both are refreshed
+ *   as by spmvHipValuesChanged.  IRP, JA and AS keep their addresses.
+ * spmvHipFsaiApply(dG, dR, dZ): z = G^T (G r), both products serial-order SpMV (sgemvSerial's bits), through the handle's
+ *   workspace; dR == dZ is allowed, any other overlap is refused.  Kernels only after the first call (which chooses the
+ *   kernels of G and G^T); spmvHipSetSync as for the launchers.
+ * spmvHipFsaiTranspose(dG, dGT): *dGT becomes a borrowed view of the G^T the handle owns (dev = NULL: its arrays stay dG's).
+ * spmvHipFsaiInfo: what the setup or the last refresh did.
+ * As dM of hipSpCGCSR / hipSpBiCGStabCSR / hipSpGMRESCSR and the block solvers: see there.
+ * Refused with a message and EXIT_FAILURE, every check before the first write -- a setup does not write dG or info, a
+ *   refresh leaves dG as it was: NULL dA or dG (dR, dZ); dG == dA or dG == dS; handles that are not live; ELL handles;
+ *   M != N; NZ >= IRP32_LIMIT or M >= 2^31; dS of another size than dA; a dA without a value array; lanesPerRow that is none
+ *   of 0, 4, 16, 64; a row of dA or dS that is not strictly ascending; a pattern row above SPMV_FSAI_MAX_ROW; a dG that
+ *   spmvHipFsaiSetup did not make, or (refresh) not from this dA.  A failed device allocation: "refused allocations" above. */
+#define SPMV_FSAI_MAX_ROW 64
+typedef struct {
+    unsigned lanesPerRow;   /* 0 = the built-in choice; 4, 16 or 64 forces the group that computes a row */
+} spmvFsaiOpts;
+typedef struct {
+    ulong  nnz;             /* entries of G                                                   */
+    ulong  maxRow;          /* its longest row                                                */
+    ulong  badRows;         /* rows that got the identity row                                 */
+    long   firstBadRow;     /* -1, or the smallest of them                                    */
+    ulong  launches;        /* kernel launches of the setup's passes, or of the last refresh  */
+    ulong  setups;          /* the setup and every refresh since                              */
+    double ms;              /* host wall time of the last call                                */
+} spmvFsaiInfo;
+int spmvHipFsaiSetup(spmat* dA, spmat* dS, const spmvFsaiOpts* opts, spmat* dG, spmvFsaiInfo* info);
+int spmvHipFsaiRefresh(spmat* dG, spmat* dA, spmvFsaiInfo* info);
+int spmvHipFsaiApply(spmat* dG, const double* dR, double* dZ);
+int spmvHipFsaiTranspose(spmat* dG, spmat* dGT);
+int spmvHipFsaiInfo(spmat* dG, spmvFsaiInfo* info);
 /* ------------------------------------------------------------- Krylov solves */
 /* spmvHipDot: *dResult (one double on the device) = u . v over n elements, in an order that is a function of n alone --
  * not of the grid, the device, the stream, the alignment of the pointers or the run.  DESIGN.md section 19.  Every
@@ -334,7 +401,10 @@ int spmvHipIlu0Info(spmat* dA, spmvIluInfo* info);
  * hipSpTRSVCSR(dM, UPPER, STORED, hipSpTRSVCSR(dM, LOWER, UNIT, v)) -- the ILU(0) pair of hipSpILU0CSR; dM == dA is
  * allowed.  A dM made by spmvHipAmgSetup(dA) (hipSpGMRESCSR too) makes M^-1 v = V(0, v), the cycle of spmvHipAmgApply: its
  * kernels stop with the loop as the triangular solves do, its SpMVs run regardless, info.launches counts them all; a
- * hierarchy of another source is refused.  x, info.status, info.iterations, info.rr and history are the bits of these loops, in IEEE double with no FMA:
+ * hierarchy of another source is refused.  A dM made by spmvHipFsaiSetup (all three, and the block solvers) makes
+ * M^-1 v = G^T (G v), the two serial-order SpMVs of spmvHipFsaiApply through the handle's workspace (a block solve: two SpMM
+ * passes through one more block of its own workspace): they run regardless of the stop flag and count as two launches; the
+ * factor need not come from this dA -- a lagged preconditioner is legitimate -- but must have dA's size.  x, info.status, info.iterations, info.rr and history are the bits of these loops, in IEEE double with no FMA:
  * dot() is spmvHipDot, A v is serial-order SpMV (sgemvSerial's bits, spmvHipEnqueueAutoRows: its first call for a handle
  * chooses the kernel), every a + s*v is two roundings in the order written, tol2 = tol*tol is computed on the host.
  *     q = A x; r = b - q; rr = dot(r,r); bb = dot(b,b); thresh = tol2 * bb; hist[0] = rr

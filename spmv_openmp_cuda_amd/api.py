@@ -109,6 +109,11 @@ _sigs = {
     "hipSpTRSMCSR": ([C.POINTER(spmat), _i, _i, C.c_uint, _vp, _sz, _i, _vp, _sz, _i], _i),
     "hipSpILU0CSR": ([C.POINTER(spmat)], _i),
     "spmvHipIlu0Info": ([C.POINTER(spmat), _vp], _i),
+    "spmvHipFsaiSetup": ([C.POINTER(spmat), C.POINTER(spmat), _vp, C.POINTER(spmat), _vp], _i),
+    "spmvHipFsaiRefresh": ([C.POINTER(spmat), C.POINTER(spmat), _vp], _i),
+    "spmvHipFsaiApply": ([C.POINTER(spmat), _vp, _vp], _i),
+    "spmvHipFsaiTranspose": ([C.POINTER(spmat), C.POINTER(spmat)], _i),
+    "spmvHipFsaiInfo": ([C.POINTER(spmat), _vp], _i),
     "spmvHipDot": ([_sz, _vp, _vp, _vp], _i),
     "hipSpCGCSR": ([C.POINTER(spmat), C.POINTER(spmat), _vp, _vp, _vp, _vp], _i),
     "hipSpBiCGStabCSR": ([C.POINTER(spmat), C.POINTER(spmat), _vp, _vp, _vp, _vp], _i),
@@ -198,6 +203,20 @@ class spmvIluInfo(C.Structure):
     """include/spmvHip.h `spmvIluInfo`: what the last ILU(0) factorisation of a handle did."""
     _fields_ = [("zeroPivot", C.c_long), ("firstBadRow", C.c_long), ("levels", C.c_ulong), ("launches", C.c_ulong),
                 ("longRows", C.c_ulong), ("factorisations", _i), ("ms", C.c_double)]
+
+
+SPMV_FSAI_MAX_ROW = 64                                     # include/spmvHip.h: the longest row of an approximate-inverse factor
+
+
+class spmvFsaiOpts(C.Structure):
+    """include/spmvHip.h `spmvFsaiOpts`: the lanes that compute one row of G (0: the built-in choice; 4, 16 or 64)."""
+    _fields_ = [("lanesPerRow", C.c_uint)]
+
+
+class spmvFsaiInfo(C.Structure):
+    """include/spmvHip.h `spmvFsaiInfo`: what the setup or the last refresh of an approximate-inverse factor did."""
+    _fields_ = [("nnz", C.c_ulong), ("maxRow", C.c_ulong), ("badRows", C.c_ulong), ("firstBadRow", C.c_long),
+                ("launches", C.c_ulong), ("setups", C.c_ulong), ("ms", C.c_double)]
 
 
 class spmvKrylovOpts(C.Structure):
@@ -1171,10 +1190,24 @@ class DeviceMatrix:
         _check(lib.spmvHipIlu0Info(C.byref(self.handle), C.byref(info)), "spmvHipIlu0Info")
         return info
 
+    def fsai(self, pattern=None, lanes_per_row=0) -> "Fsai":
+        """spmvHipFsaiSetup: the factorised sparse approximate inverse G of this square matrix, G^T G ~ A^-1, with the bits
+        of the loop in include/spmvHip.h.  Only the lower triangle of this matrix is read.  pattern: a DeviceMatrix of the
+        same size whose columns j < i give row i of G (its values are not read; it may be freed afterwards), None for this
+        matrix's own; a row of G holds at most SPMV_FSAI_MAX_ROW entries.  lanes_per_row: 0 (the built-in choice), 4, 16
+        or 64 -- no bit depends on it.  The result is accepted as `precond=` by cg / bicgstab / gmres / cg_block /
+        bicgstab_block of any matrix of this size."""
+        g = Fsai(self)
+        opts = spmvFsaiOpts(int(lanes_per_row))
+        _check(lib.spmvHipFsaiSetup(C.byref(self.handle), C.byref(pattern.handle) if pattern is not None else None, C.byref(opts),
+                                    C.byref(g.handle), C.byref(g._info)), "spmvHipFsaiSetup")
+        g.rows = int(g.handle.M)
+        return g
+
     def cg(self, b, x0=None, precond=None, tol=1e-8, maxiter=1000, history=False):
         """hipSpCGCSR: solve A x = b (A symmetric positive definite) on the device with the bits of the loop in
-        include/spmvHip.h; precond: None, a DeviceMatrix holding ILU(0) factors (`ilu0()`) or this
-        matrix's multigrid hierarchy (`amg()`).  b (and x0): numpy arrays ->
+        include/spmvHip.h; precond: None, a DeviceMatrix holding ILU(0) factors (`ilu0()`), this
+        matrix's multigrid hierarchy (`amg()`) or an approximate-inverse factor (`fsai()`).  b (and x0): numpy arrays ->
         x as numpy; or contiguous float64 device torch tensors -> x as a new torch tensor.  Returns (x, info) with
         info.history a numpy array of the squared residuals hist[0 .. iterations] when history=True."""
         return self._krylov(lib.hipSpCGCSR, "hipSpCGCSR", b, x0, precond, tol, maxiter, history)
@@ -1193,8 +1226,8 @@ class DeviceMatrix:
         """hipSpCGBlockCSR: k solves A x_c = b_c in lock step, column c of X with the bits of cg() on column c of B (and of
         X0), the matrix and the preconditioner's schedule streamed once per iteration for all columns.  B (and X0) are
         (N, k) float64: numpy arrays -> X as numpy; or device torch tensors with unit stride in one dimension (the rules
-        of matmul's X) -> X as a new torch tensor.  precond: None, a DeviceMatrix holding ILU(0) factors, or this matrix's
-        multigrid hierarchy after set_block_width(width >= k) (without one it is refused).  Returns (X, info): info.columns the k spmvKrylovColumn records; info.history, when
+        of matmul's X) -> X as a new torch tensor.  precond: None, a DeviceMatrix holding ILU(0) factors, an approximate-inverse
+        factor (`fsai()`), or this matrix's multigrid hierarchy after set_block_width(width >= k) (without one it is refused).  Returns (X, info): info.columns the k spmvKrylovColumn records; info.history, when
         history=True, a list of k arrays hist[0 .. iterations_c]."""
         return self._krylov_block(lib.hipSpCGBlockCSR, "hipSpCGBlockCSR", B, X0, precond, tol, maxiter, history)
 
@@ -1390,6 +1423,48 @@ class AmgHierarchy(DeviceMatrix):
                 if a.size:
                     _check(lib.spmvHipMemcpyDown(a.ctypes.data_as(C.c_void_p), C.cast(ptr, C.c_void_p), a.nbytes), "spmvHipMemcpyDown")
         return out
+
+    def free(self):
+        super().free()
+        self.source = None
+
+
+class Fsai(DeviceMatrix):
+    """What DeviceMatrix.fsai() returns: the factor G as an ordinary CSR DeviceMatrix (SpMV, transpose, multiply, filter and
+    to_coo take it) that privately owns G^T and the workspace of apply(); free() gives all of it back.  It keeps a reference
+    to its source matrix."""
+
+    def __init__(self, source):
+        super().__init__()
+        self.source = source
+        self._info = spmvFsaiInfo()
+
+    def apply(self, r, out=None):
+        """spmvHipFsaiApply: z = G^T (G r), two serial-order SpMVs.  r: a numpy array -> z as numpy; or a float64 device
+        torch tensor -> z as a torch tensor (`out` when given; `out` may be `r`: in place)."""
+        N = int(self.handle.M)
+        with _Operands("spmvHipFsaiApply", r) as ops:
+            ops.vector("r", r, N)
+            ops.result("out", out, (N,))
+            _check(lib.spmvHipFsaiApply(C.byref(self.handle), *ops.args), "spmvHipFsaiApply")
+            return ops.value()
+
+    def refresh_from(self, source: "DeviceMatrix"):
+        """spmvHipFsaiRefresh: `source` (the matrix of the setup) has new values on the same pattern: G and G^T take the
+        values of a fresh setup in place, addresses kept.  Returns info()."""
+        _check(lib.spmvHipFsaiRefresh(C.byref(self.handle), C.byref(source.handle), C.byref(self._info)), "spmvHipFsaiRefresh")
+        return self._info
+
+    def transposed(self):
+        """spmvHipFsaiTranspose: the G^T this factor owns as host CSR arrays (M, N, IRP, JA, AS), downloaded"""
+        view = spmat()
+        _check(lib.spmvHipFsaiTranspose(C.byref(self.handle), C.byref(view)), "spmvHipFsaiTranspose")
+        return AmgHierarchy._down(view)
+
+    def info(self) -> "spmvFsaiInfo":
+        """spmvHipFsaiInfo: what the setup or the last refresh did (nnz, maxRow, badRows, firstBadRow, ...)."""
+        _check(lib.spmvHipFsaiInfo(C.byref(self.handle), C.byref(self._info)), "spmvHipFsaiInfo")
+        return self._info
 
     def free(self):
         super().free()

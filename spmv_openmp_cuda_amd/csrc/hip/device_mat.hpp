@@ -33,7 +33,8 @@ enum class Kind : int { CSR = 0, ELL_ROWMAJOR = 1, ELL_COLMAJOR = 2 };
 // source (the level-0 matrix) in src[0], PRODUCT and SUM A and B in that order, FILTER the source in src[0].  What made a
 // handle refreshes it, from those handles only (madeBy in lib.hpp).  ELL_OF_CSR (spmvHipCsrToEll) keeps no link to its source, and its values cannot be updated.
 // ASSEMBLED (spmvHipCooAssemble) comes from the caller's triplet arrays, not from a handle: it has no source ids.
-enum class Origin : int { UPLOADED, ADOPTED, ELL_OF_CSR, TRANSPOSE, PERMUTATION, PRODUCT, HIERARCHY, SUM, FILTER, ASSEMBLED };
+// FSAI (spmvHipFsaiSetup) records the matrix in src[0]; the pattern handle need not outlive the setup and is not recorded.
+enum class Origin : int { UPLOADED, ADOPTED, ELL_OF_CSR, TRANSPOSE, PERMUTATION, PRODUCT, HIERARCHY, SUM, FILTER, ASSEMBLED, FSAI };
 
 struct TileFormat;          // column-sliced two-phase format, tiles.hip
 struct SellFormat;          // SELL-C-sigma, sell.hip
@@ -43,6 +44,7 @@ struct AddPlan;             // what a sum C = alpha A + beta B keeps for its ref
 struct FilterPlan;          // what a filtered handle keeps for its refresh besides the map, filter.hip
 struct CooPlan;             // what a handle assembled from triplets keeps for its refresh, coo.hip
 struct AmgHierarchy;        // the levels of an aggregation multigrid preconditioner, amg.hip
+struct FsaiPlan;            // what an approximate-inverse factor G owns besides its arrays (below; fsai.hip builds the arrays)
 struct TempBuf;             // a scoped device buffer, device_prims.hpp
 
 // the level sets of one triangle (built by triAnalyse in trsv.hip; the ILU(0) factorisation of ilu0.hip runs on the lower one)
@@ -120,6 +122,8 @@ struct DevMat {
     // a multigrid hierarchy (spmvHipAmgSetup, amg.hip): the handle is then no matrix (no arrays, NZ = 0) and only the
     // spmvHipAmg* calls, a Krylov solve's dM and hipFreeSpmat take it
     AmgHierarchy* amg = nullptr;
+    // an approximate-inverse factor (spmvHipFsaiSetup, fsai.hip): its transpose, the workspace of an apply, what the setup did
+    FsaiPlan* fsai = nullptr;
     // the level-set schedules of the triangular solve (trsv.hip), [SPMV_TRI_LOWER] and [SPMV_TRI_UPPER]: built from the
     // pattern at the first solve or by spmvHipTriAnalyse, kept across value updates (the solve reads AS live)
     TriSchedule* tri[2] = {nullptr, nullptr};
@@ -132,6 +136,16 @@ struct DevMat {
     // writes: spmvHipUpdateValues / ValuesChanged (updateValues) and the refreshes of a derived handle (upload.hip).
     bool      iluPending = false;
     spmvIluInfo ilu{-1, -1, 0, 0, 0, 0, 0.0};
+};
+
+// What a factor G of spmvHipFsaiSetup owns privately: G^T (made and refreshed by the transpose path, with a handle of its own
+// for the launchers), a handle over G itself for them, one M-vector for G r, the forced group width and the last report.
+struct FsaiPlan {
+    DevMat*  gt = nullptr;
+    spmat    hG{}, hGT{};
+    double*  work = nullptr;
+    uint32_t lanes = 0;             // spmvFsaiOpts.lanesPerRow (0: the built-in choice)
+    spmvFsaiInfo info{0, 0, 0, -1, 0, 0, 0.0};
 };
 
 // The one place that looks at the width of the row pointers: f (a generic lambda) is called with them as const uint32_t*
@@ -257,6 +271,15 @@ void cooSetMaxRow(DevMat* c);
 bool cooHasMap(const DevMat* c);
 uint64_t cooEntries(const DevMat* c);
 void freeCooPlan(CooPlan* p);
+// The approximate-inverse factor (fsai.hip; contract in spmvHip.h, design in DESIGN.md section 38).  fsaiBuild fills g (kind,
+// M and N set, nothing owned) with IRP (4 B), JA and AS for the checked handles a and s (the pattern; s may be a), NZ set --
+// on failure the caller frees g with whatever it holds; *longRow >= 0 names a pattern row above SPMV_FSAI_MAX_ROW, for which
+// nothing was printed.  fsaiValues: the values of g again from a's current values (lanes: a forced group width or 0, maxRow:
+// the longest row of g); its one allocation comes before its first write.  Both synchronous, temporaries freed before they
+// return; info's nnz, maxRow, badRows, firstBadRow are set and launches grows.  fsaiLanes: the group width a call takes.
+int  fsaiBuild(const DevMat* a, const DevMat* s, DevMat* g, uint32_t lanes, spmvFsaiInfo* info, long* longRow, hipStream_t stream);
+int  fsaiValues(const DevMat* a, DevMat* g, uint32_t lanes, uint32_t maxRow, spmvFsaiInfo* info, hipStream_t stream);
+uint32_t fsaiLanes(uint32_t forced, uint64_t M, uint64_t nnz);
 // A dense rows x k block of doubles in the form the C boundary is given, checked there (lib.hpp: denseOperand, denseShare):
 // element (i, c) at p[i*ld + c] (rowMajor) or p[c*ld + i].  Every block launcher below takes its operands as this; one that
 // only reads takes the same type.  A solver's own n x kp workspace block is Dense{p, kp, true}.

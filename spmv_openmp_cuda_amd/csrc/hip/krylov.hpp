@@ -220,18 +220,26 @@ struct DevBufs {
 };
 
 // M^-1 of one solve, from its checked dM (null: none, and apply is not called): the ILU(0) pair U^-1 (L^-1 in) of an
-// analysed matrix handle, or the cycle of a hierarchy of hA.  apply enqueues kernels only on the solve's stream; every one
-// returns at once when *flag != 0; *launches grows by the kernels enqueued.
+// analysed matrix handle, the cycle of a hierarchy of hA, or G^T (G in) of an approximate-inverse factor through its
+// workspace vector.  apply enqueues kernels only on the solve's stream; every one but an SpMV returns at once when
+// *flag != 0; *launches grows by the kernels enqueued.
 struct Precond {
     const DevMat* m; spmat* hA; hipStream_t s;
     unsigned long triLaunches = 0;              // of the two triangular solves
     Precond(const DevMat* m_, spmat* hA_, hipStream_t s_) : m(m_), hA(hA_), s(s_) {
         spmvTriInfo t{};
-        if (m && m->origin != Origin::HIERARCHY)
+        if (m && m->origin != Origin::HIERARCHY && m->origin != Origin::FSAI)
             for (int uplo : {SPMV_TRI_LOWER, SPMV_TRI_UPPER}) { triInfo(m, uplo, &t); triLaunches += t.launches; }
     }
     int apply(const double* in, double* out, const uint32_t* flag, unsigned long* launches) const {
         if (m->origin == Origin::HIERARCHY) return enqueueAmgCycle(m, hA, in, out, s, flag, launches);
+        if (m->origin == Origin::FSAI) {                                 // (each handle's first call chooses its kernel, as hA's does)
+            FsaiPlan* const p = m->fsai;
+            if (spmvHipEnqueueAutoRows(&p->hG, const_cast<double*>(in), p->work, s)) return EXIT_FAILURE;
+            if (spmvHipEnqueueAutoRows(&p->hGT, p->work, out, s)) return EXIT_FAILURE;
+            *launches += 2;
+            return EXIT_SUCCESS;
+        }
         dim3 g, bl;
         enqueueTrsv(m, SPMV_TRI_LOWER, SPMV_DIAG_UNIT, in, out, s, &g, &bl, flag);
         enqueueTrsv(m, SPMV_TRI_UPPER, SPMV_DIAG_STORED, out, out, s, &g, &bl, flag);

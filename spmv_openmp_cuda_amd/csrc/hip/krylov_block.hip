@@ -2,7 +2,8 @@
 // (hipSpCGBlockCSR, hipSpBiCGStabBlockCSR; contract in spmvHip.h, design in DESIGN.md section 27).  These are k independent
 // solves advanced in lock step: column c of X, its status, its iteration count and its residual norms are the bits of
 // hipSpCGCSR / hipSpBiCGStabCSR on column c alone, while the matrix (one hipSpMMRowsCSR pass), the level schedule of the
-// preconditioner (two hipSpTRSMCSR passes) and every launch are shared by the columns.
+// preconditioner (two hipSpTRSMCSR passes; two SpMM passes with an approximate-inverse factor) and every launch are shared
+// by the columns.
 //
 // One state block (KState of krylov.hpp) per column, and the scalar steps of the single loops (krylovScalarStep) run on it
 // unchanged, one workgroup per column in one finish launch.  Every fused pass reads the state of its two columns and leaves
@@ -234,14 +235,20 @@ struct BlockWidth {
     const hipStream_t s;
     spmvKrylovInfo& out;                        // launches and hostChecks are counted here
     const bool cycle = pre && m->origin == Origin::HIERARCHY;            // M^-1 is a block cycle of the hierarchy (its width is >= k)
+    const bool fsai = pre && m->origin == Origin::FSAI;                  // ... or G^T (G in) of an approximate-inverse factor, through gw
     unsigned long triLaunches = 0;              // of the two triangular passes otherwise
-    Vec b{}, x{}, v[8] = {};
+    Vec b{}, x{}, v[8] = {}, gw{};
     double* p0 = nullptr; double* p1 = nullptr; // the block partials of a pass's first and second dot
     KState* st = nullptr; BlockHead* head = nullptr; double* hist = nullptr;
     BlockHead hh{};                             // the head word as the host last read it
     int product(const Vec& in, const Vec& outv) { ++out.launches; return enqueueSpmm(a, k, dense(in), dense(outv), s); }
     int precond(const Vec& in, const Vec& outv) {                        // z = U^-1 (L^-1 in), or one cycle: every launch behind the head word
         if (cycle) return enqueueAmgCycleBlock(m, a, k, dense(in), dense(outv), s, &head->allStop, &out.launches);
+        if (fsai) {                                                      // two SpMM passes, which run whatever the head word says
+            if (enqueueSpmm(m, k, dense(in), dense(gw), s) || enqueueSpmm(m->fsai->gt, k, dense(gw), dense(outv), s)) return EXIT_FAILURE;
+            out.launches += 2;
+            return EXIT_SUCCESS;
+        }
         dim3 g, bl;
         if (enqueueTrsm(m, SPMV_TRI_LOWER, SPMV_DIAG_UNIT, k, dense(in), dense(outv), s, &g, &bl, &head->allStop)) return EXIT_FAILURE;
         if (enqueueTrsm(m, SPMV_TRI_UPPER, SPMV_DIAG_STORED, k, dense(outv), dense(outv), s, &g, &bl, &head->allStop)) return EXIT_FAILURE;
@@ -294,6 +301,11 @@ int krylovBlockSolve(int bicg, const DevMat* a, const DevMat* m, uint32_t k, con
         if (!p) return fail();
         w.v[i] = bmat(Dense{p, kp, true}, k, true);
     }
+    if (w.fsai) {                                                        // one more block: G in, between the two passes
+        double* p = bufs.alloc<double>(n * kp);
+        if (!p) return fail();
+        w.gw = bmat(Dense{p, kp, true}, k, true);
+    }
     w.p0 = bufs.alloc<double>(2 * nb * kp);
     BlockHead* head = w.head = bufs.alloc<BlockHead>(1);
     KState* st = w.st = bufs.alloc<KState>(k);
@@ -308,7 +320,7 @@ int krylovBlockSolve(int bicg, const DevMat* a, const DevMat* m, uint32_t k, con
     HIP_TRY(hipMemcpyAsync(head, &w.hh, sizeof w.hh, hipMemcpyHostToDevice, s));
     w.b = bmat(B, k, false);
     w.x = bmat(X, k, false);
-    if (pre && !w.cycle) {
+    if (pre && !w.cycle && !w.fsai) {
         spmvTriInfo t{};
         for (int uplo : {SPMV_TRI_LOWER, SPMV_TRI_UPPER}) { triInfo(m, uplo, &t); w.triLaunches += t.launches; }
     }

@@ -118,9 +118,9 @@ inline void setOrigin(DevMat* d, Origin o, const DevMat* a = nullptr, const DevM
 }
 inline bool madeBy(const DevMat* x, Origin want, const DevMat* a, const DevMat* b, const char* who, const char* xName,
                    const char* aName = nullptr, const char* bName = nullptr) {
-    static const struct { const char* maker; const char* made; } texts[] = {     // TRANSPOSE .. ASSEMBLED
+    static const struct { const char* maker; const char* made; } texts[] = {     // TRANSPOSE .. FSAI
         {"spmvHipCsrTranspose", "transposed"}, {"spmvHipCsrPermute", "permuted"}, {"spmvHipSpGEMM", ""}, {"spmvHipAmgSetup", "set up"},
-        {"spmvHipCsrAdd", ""}, {"spmvHipCsrFilter", "filtered"}, {"spmvHipCooAssemble", "assembled"}};
+        {"spmvHipCsrAdd", ""}, {"spmvHipCsrFilter", "filtered"}, {"spmvHipCooAssemble", "assembled"}, {"spmvHipFsaiSetup", "set up"}};
     const auto& text = texts[(int)want - (int)Origin::TRANSPOSE];
     if (x->origin != want) { ERR("%s: %s was not made by %s", who, xName, text.maker); return false; }
     if (!a || (a->id == x->src[0] && (!b || b->id == x->src[1]))) return true;

@@ -475,6 +475,8 @@ static int krylovArgs(const char* who, spmat* dA, spmat* dM, const double* dB, d
     if (dM && !m) return EXIT_FAILURE;
     if (m && m->origin == Origin::HIERARCHY) {               // a multigrid hierarchy: M^-1 v is its cycle
         if (!madeBy(m, Origin::HIERARCHY, a, nullptr, who, "dM", "dA")) return EXIT_FAILURE;
+    } else if (m && m->origin == Origin::FSAI) {             // an approximate-inverse factor: M^-1 v = G^T (G v), of any source of dA's size
+        if (m->M != a->M) { ERR("%s: dM has %lu rows, dA %lu", who, (unsigned long)m->M, (unsigned long)a->M); return EXIT_FAILURE; }
     } else if (dM) {
         if (!(m = triHandle(dM, SPMV_TRI_LOWER, who))) return EXIT_FAILURE;
         if (m->M != a->M) { ERR("%s: dM has %lu rows, dA %lu", who, (unsigned long)m->M, (unsigned long)a->M); return EXIT_FAILURE; }

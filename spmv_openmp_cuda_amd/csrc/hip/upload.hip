@@ -72,6 +72,11 @@ void freeDesc(DevMat* d) {
     freeFilterPlan(d->filt);
     freeCooPlan(d->coo);
     freeAmg(d->amg);
+    if (d->fsai) {                                      // an approximate-inverse factor: its transpose and its workspace
+        freeDesc(d->fsai->gt);
+        (void)devFree(d->fsai->work);
+        delete d->fsai;
+    }
     freeTiles(d->tiles[0]); freeTiles(d->tiles[1]);
     freeSell(d->sell);
     freeStripes(d->stripes[0]); freeStripes(d->stripes[1]);
@@ -690,6 +695,144 @@ int spmvHipCsrToCoo(spmat* dA, uint32_t* dRow, uint32_t* dCol, double* dVal) {
     if (a->M >= (1ull << 32) - 1) { ERR("%s: M=%lu rows do not fit the 32-bit row ids of the triplets", who, (unsigned long)a->M); return EXIT_FAILURE; }
     if (a->NZ && (!a->JA || !a->AS)) { ERR("%s: the source has no column or value array", who); return EXIT_FAILURE; }
     return csrToCoo(a, dRow, dCol, dVal, S.stream);
+}
+
+// ---- the approximate-inverse factor G of a square handle, G^T G ~ A^-1 (fsai.hip builds the arrays; the contract is in
+// spmvHip.h, the design in DESIGN.md section 38).  dG owns G^T -- made and refreshed by the transpose path above -- and the
+// workspace of an apply.  Refusals come first; dG and info are written only on success.
+
+// hipSpILU0CSR's pattern check, made once per handle: every row strictly ascending
+static bool strictRows(DevMat* d, const char* who, const char* name) {
+    if (d->M && !d->iluChecked) {
+        long row = -1;
+        if (iluUnsortedRow(d, S.stream, &row)) { ERR("%s: the pattern check of %s failed", who, name); return false; }
+        d->iluUnsortedRow = row;
+        d->iluChecked = true;
+    }
+    if (d->M && d->iluUnsortedRow >= 0) {
+        ERR("%s: row %ld of %s: its columns are not strictly ascending (unsorted, or a repeated column)", who, d->iluUnsortedRow, name);
+        return false;
+    }
+    return true;
+}
+
+// dG as a factor of spmvHipFsaiSetup
+static DevMat* fsaiOf(spmat* dG, const char* who) {
+    if (!ready(who)) return nullptr;
+    if (!dG) { ERR("%s: dG is NULL", who); return nullptr; }
+    DevMat* g = descOf(dG, who);
+    if (!g || !madeBy(g, Origin::FSAI, nullptr, nullptr, who, "dG")) return nullptr;
+    return g;
+}
+
+int spmvHipFsaiSetup(spmat* dA, spmat* dS, const spmvFsaiOpts* opts, spmat* dG, spmvFsaiInfo* info) {
+    const char* who = "spmvHipFsaiSetup";
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!ready(who)) return EXIT_FAILURE;
+    if (!dA || !dG) { ERR("%s: %s is NULL", who, !dA ? "dA" : "dG"); return EXIT_FAILURE; }
+    if (dG == dA || dG == dS) { ERR("%s: dG is a source handle itself", who); return EXIT_FAILURE; }
+    DevMat* a = squareCsrOf(dA, who, "dA is an ELL handle (only CSR handles have an approximate inverse)");
+    if (!a) return EXIT_FAILURE;
+    DevMat* s = dS ? squareCsrOf(dS, who, "dS is an ELL handle (the pattern is a CSR handle)") : a;
+    if (!s) return EXIT_FAILURE;
+    if (s->M != a->M) { ERR("%s: dS has %lu rows, dA %lu", who, (unsigned long)s->M, (unsigned long)a->M); return EXIT_FAILURE; }
+    if (a->NZ && !a->AS) { ERR("%s: dA has no value array", who); return EXIT_FAILURE; }
+    const unsigned lanes = opts ? opts->lanesPerRow : 0;
+    if (lanes != 0 && lanes != 4 && lanes != 16 && lanes != 64) { ERR("%s: lanesPerRow %u is none of 0, 4, 16, 64", who, lanes); return EXIT_FAILURE; }
+    if (!strictRows(a, who, "dA") || (s != a && !strictRows(s, who, "dS"))) return EXIT_FAILURE;
+    DevMat* g = new DevMat;
+    g->M = g->N = a->M;
+    setOrigin(g, Origin::FSAI, a);
+    FsaiPlan* p = g->fsai = new FsaiPlan;
+    p->lanes = lanes;
+    long longRow = -1;
+    if (fsaiBuild(a, s, g, lanes, &p->info, &longRow, S.stream)) {
+        if (longRow >= 0)
+            ERR("%s: row %ld of the pattern gives a row of G of more than SPMV_FSAI_MAX_ROW = %d entries: filter the pattern", who, longRow,
+                SPMV_FSAI_MAX_ROW);
+        else ERR("%s: building the factor failed", who);
+        freeDesc(g);
+        return EXIT_FAILURE;
+    }
+    g->maxRowNnz = p->info.maxRow;
+    // G^T by the transpose path; an empty factor has an empty transpose and asks for no kernel
+    bool ok = false;
+    DevMat* t = newMappedCsr(Origin::TRANSPOSE, g, g->M, g->M, &ok);
+    if (ok && g->M == 0) ok = hipOk(hipMemset(t->IRP, 0, 4), "hipMemset");
+    else if (ok) ok = !transposeCsr(g, t, S.stream);
+    if (finishCsr(&p->hGT, t, ok)) { ERR("%s: building the factor's transpose failed", who); freeDesc(g); return EXIT_FAILURE; }
+    p->gt = t;
+    if (!hipOk(devMalloc(&p->work, std::max<size_t>(g->M, 1) * sizeof(double)), "hipMalloc the workspace")) { freeDesc(g); return EXIT_FAILURE; }
+    if (finishCsr(&p->hG, g)) { ERR("%s: finishing the factor failed", who); return EXIT_FAILURE; }
+    p->info.setups = 1;
+    p->info.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    *dG = p->hG;
+    if (info) *info = p->info;
+    return EXIT_SUCCESS;
+}
+
+int spmvHipFsaiRefresh(spmat* dG, spmat* dA, spmvFsaiInfo* info) {
+    const char* who = "spmvHipFsaiRefresh";
+    const auto t0 = std::chrono::steady_clock::now();
+    DevMat* g = fsaiOf(dG, who);
+    if (!g) return EXIT_FAILURE;
+    if (!dA) { ERR("%s: dA is NULL", who); return EXIT_FAILURE; }
+    DevMat* a = csrOf(dA, who, "dA is an ELL handle");
+    if (!a || !madeBy(g, Origin::FSAI, a, nullptr, who, "dG", "dA")) return EXIT_FAILURE;
+    if (a->NZ && !a->AS) { ERR("%s: dA has no value array", who); return EXIT_FAILURE; }
+    FsaiPlan* p = g->fsai;
+    spmvFsaiInfo out = p->info;
+    out.launches = 0;
+    g->iluPending = false;                              // AS is rewritten from here on, whatever becomes of the call
+    if (fsaiValues(a, g, p->lanes, (uint32_t)p->info.maxRow, &out, S.stream)) { ERR("%s: recomputing the values failed", who); return EXIT_FAILURE; }
+    if (updateValues(dG, nullptr, true, true, S.stream, who)) return EXIT_FAILURE;
+    p->gt->iluPending = false;
+    if (enqueueGatherValues(p->gt->AS, p->gt->tmap, p->gt->NZ, g->AS, S.stream)) return EXIT_FAILURE;
+    if (updateValues(&p->hGT, nullptr, true, true, S.stream, who)) return EXIT_FAILURE;
+    ++out.launches;
+    ++out.setups;
+    out.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    p->info = out;
+    if (info) *info = out;
+    return EXIT_SUCCESS;
+}
+
+int spmvHipFsaiApply(spmat* dG, const double* dR, double* dZ) {
+    const char* who = "spmvHipFsaiApply";
+    const Ctx cx = libraryCtx();
+    DevMat* g = fsaiOf(dG, who);
+    if (!g) return EXIT_FAILURE;
+    if (!dR || !dZ) { ERR("%s: %s is NULL", who, !dR ? "dR" : "dZ"); return EXIT_FAILURE; }
+    if (dR != dZ && overlaps(dR, dZ, g->M * sizeof(double))) { ERR("%s: dR and dZ overlap without being equal", who); return EXIT_FAILURE; }
+    if (g->M == 0) return nothingToLaunch(cx, g, nullptr);
+    FsaiPlan* p = g->fsai;
+    Launch L(cx, grid2d(g->nBlk2, WG_THREADS), dim3(WG_THREADS));
+    const Ctx enqueue{cx.stream, false};                // w = G r, z = G^T w: the serial-order selection of each handle
+    if (autoRun(enqueue, &p->hG, const_cast<double*>(dR), p->work, 1, who) || autoRun(enqueue, &p->hGT, p->work, dZ, 1, who)) {
+        ERR("%s: launch failed", who);
+        return EXIT_FAILURE;
+    }
+    return L.finish(who);
+}
+
+int spmvHipFsaiTranspose(spmat* dG, spmat* dGT) {
+    const char* who = "spmvHipFsaiTranspose";
+    DevMat* g = fsaiOf(dG, who);
+    if (!g) return EXIT_FAILURE;
+    if (!dGT) { ERR("%s: dGT is NULL", who); return EXIT_FAILURE; }
+    if (dGT == dG) { ERR("%s: dGT is the factor's handle itself", who); return EXIT_FAILURE; }
+    *dGT = g->fsai->hGT;
+    dGT->dev = nullptr;                                 // a view: the arrays stay the factor's
+    return EXIT_SUCCESS;
+}
+
+int spmvHipFsaiInfo(spmat* dG, spmvFsaiInfo* info) {
+    const char* who = "spmvHipFsaiInfo";
+    DevMat* g = fsaiOf(dG, who);
+    if (!g) return EXIT_FAILURE;
+    if (!info) { ERR("%s: info is NULL", who); return EXIT_FAILURE; }
+    *info = g->fsai->info;
+    return EXIT_SUCCESS;
 }
 
 int spmvHipUpdateValues(spmat* dMat, const double* AS, int asOnDevice) {
