@@ -115,6 +115,7 @@ int spmvHipMemcpyDown(void* hDst, const void* dSrc, size_t bytes);
  *   spmvHipDot / MultiDot / BlockDot: the result is not written, the dot workspace keeps the size it had;
  *   hipSpCGCSR, hipSpBiCGStabCSR, hipSpGMRESCSR (every allocation comes before the loop): x and info are not written; a
  *     schedule that was made on dM stays there;
+ *   hipSpLanczosCSR (every allocation comes before the loop): dX, theta, res and info are not written;
  *   spmvHipColourCSR, spmvHipAggregateCSR: info is not written, nothing is held; dColour / dPerm / dAgg may have been
  *     written in part and hold nothing to rely on;
  *   spmvHipAmgSetSmoother, spmvHipAmgSetGaussSeidel, spmvHipAmgSetBlockWidth: everything new is made before anything old
@@ -607,6 +608,109 @@ typedef struct {
 } spmvGmresOpts;
 int spmvHipMultiDot(size_t n, unsigned k, const double* dV, size_t ldv, const double* dW, double* dH);
 int hipSpGMRESCSR(spmat* dA, spmat* dM, const double* dB, double* dX, const spmvGmresOpts* opts, spmvKrylovInfo* info);
+/* ------------------------------------------------------------- basis rotation, extreme eigenpairs */
+/* spmvHipBlockCombine: Y = V S on the device, next to spmvHipMultiDot: V is n x m, S is m x k, Y is n x k, all
+ * column-major (V(i, j) at dV[j*ldv + i], ldv >= n; S[j][c] at dS[c*lds + j], lds >= m; Y(i, c) at dY[c*ldy + i], ldy >= n),
+ * 1 <= m <= 64, 1 <= k <= 64.
+ *     Y(i, c) = +0.0;  for j = 0 .. m-1 ascending:  Y(i, c) = Y(i, c) + V(i, j) * S[j][c]
+ * in IEEE double, every product and every add rounded on its own (no FMA, no matrix instruction) -- whatever n, the
+ * leading dimensions and the alignment of the pointers are (one form is chosen per call on the host: a lane owns two
+ * adjacent rows with 16-byte accesses when m <= 32, dV and dY are 16-byte aligned, ldv is even or m == 1, and ldy is even
+ * or k == 1; one row with 8-byte accesses otherwise).  A row's m values are all read before any of its k sums is stored,
+ * and a row touches no other row: dY == dV with ldy == ldv is allowed (in place, k <= m); a NaN or an Inf in one row of V
+ * stays in that row.  Rows >= n and columns >= k of Y, and everything of V outside Y, are not written.  n = 0 launches nothing.
+ *   One kernel on the library stream, no workspace: capturable.  spmvHipSetSync, spmvHipLastKernelSeconds and
+ *   spmvHipLastLaunch as for spmvHipDot.  It streams 8*n*(m + k) bytes.
+ *   Refused (EXIT_FAILURE, dY untouched): a NULL dV, dS or dY when n > 0; m or k outside 1 .. 64; ldv < n, ldy < n,
+ *   lds < m; dY == dV with k > m or ldy != ldv; any other overlap of the spans of dV and dY, or of dS and dY.
+ *
+ * hipSpLanczosCSR: the nev algebraically largest (SPMV_EIG_LARGEST) or smallest (SPMV_EIG_SMALLEST) eigenpairs of a
+ * symmetric square CSR handle by thick-restart Lanczos with full reorthogonalisation (classical Gram-Schmidt applied
+ * twice).  Symmetry of A is the caller's promise, as it is for hipSpCGCSR: nothing checks it.  theta, res, X, info.status,
+ * .found, .iterations, .cycles, .hostChecks, .scale and .sweepsMax are the bits of this loop, in IEEE double with no FMA:
+ * dot() is spmvHipDot, A v is serial-order SpMV, sqrt and / are correctly rounded, every a +- s*v is two roundings in the
+ * order written.  m = opts.ncv; v[0 .. m], w are vectors; T is m x m, symmetric, on the host.
+ *     nn = dot(v0,v0)
+ *     if nn is not finite: NONFINITE, 0 found;  if nn == 0: BREAKDOWN, 0 found;  if maxIter == 0: MAXITER, 0 found
+ *     v[0] = v0 / sqrt(nn) (element by element);  k = 0;  T = 0;  it = 0;  cycles = 0
+ *     kk = opts.keep, or for keep == 0: min(m-1, nev + (m - nev)/2) (integer division)
+ *     cycle:  cycles = cycles + 1
+ *       for j = k .. m-1:
+ *         w = A v[j];  it = it + 1
+ *         for i = 0..j: h[i] = dot(v[i], w)                            -- spmvHipMultiDot
+ *         for i = 0..j ascending: w = w - h[i]*v[i]
+ *         for i = 0..j: c[i] = dot(v[i], w)                            -- the second pass
+ *         for i = 0..j ascending: w = w - c[i]*v[i]
+ *         alpha = h[j] + c[j];  T[j][j] = alpha;  beta = sqrt(dot(w,w))
+ *         if alpha or beta is not finite: NONFINITE, 0 found
+ *         if beta == 0: cols = j+1; exact = true; go to ritz           -- an invariant subspace
+ *         v[j+1] = w / beta;  if j+1 < m: T[j][j+1] = T[j+1][j] = beta
+ *         if it == maxIter: cols = j+1; go to ritz
+ *       cols = m
+ *     ritz:
+ *       (d, S) = JACOBI(T[0..cols-1][0..cols-1]);  if it did not end, or a d[i] is not finite: NONFINITE, 0 found
+ *       order the columns: d ascending (SMALLEST) or descending (LARGEST), equal values by ascending index: theta, S
+ *       res[i] = exact ? +0.0 : |beta * S[cols-1][i]|;  scale = max over all cols of |theta[i]|
+ *       found = min(nev, cols);  done = cols >= nev and res[i] <= tol*scale for every i < nev
+ *       if done or exact or it == maxIter:
+ *         X(:, i) = sum over j = 0..cols-1 of v[j] * S[j][i] for i < found              -- spmvHipBlockCombine
+ *         CONVERGED if done;  else BREAKDOWN if exact (res is +0.0 then, so `done` fails only on cols < nev: BREAKDOWN
+ *         means that the Krylov space of v0 holds fewer than nev pairs, and found = cols of them are returned);  else MAXITER
+ *       V(:, i) = sum over j = 0..m-1 of v[j] * S[j][i] for i < kk (in place);  v[kk] = v[m]
+ *       T = 0;  T[i][i] = theta[i], T[kk][i] = T[i][kk] = beta * S[m-1][i] for i < kk;  k = kk;  next cycle
+ *   JACOBI(T), n = cols: A = T, S = I; sweeps of the pairs p < q by rows (p = 0..n-2, q = p+1..n-1); for a pair with
+ *   a = A[p][q]: if a == 0 nothing; if |A[p][p]| + |a| == |A[p][p]| and |A[q][q]| + |a| == |A[q][q]| then A[p][q] = A[q][p] = 0
+ *   and no rotation; else th = (A[q][q] - A[p][p]) / (2*a); t = 1 / (|th| + sqrt(th*th + 1)), negated when th < 0;
+ *   c = 1 / sqrt(t*t + 1); s = t*c; tau = s / (1 + c); for r other than p, q, with x = A[r][p], y = A[r][q]:
+ *   A[r][p] = A[p][r] = x - s*(y + tau*x), A[r][q] = A[q][r] = y + s*(x - tau*y); A[p][p] -= t*a, A[q][q] += t*a,
+ *   A[p][q] = A[q][p] = 0; for every r, with x = S[r][p], y = S[r][q]: S[r][p] = x - s*(y + tau*x), S[r][q] = y + s*(x - tau*y).
+ *   It ends after the first sweep without a rotation (d = the diagonal of A); 30 sweeps that all rotated do not end.
+ *   info.sweepsMax is the most sweeps any cycle took (the last, rotation-free one included).
+ * Outputs: dX is n x nev on the device, column-major with ldx >= n; theta and res are nev host doubles each.  Only the
+ *   first info.found columns and entries are written.  dV0 (n doubles) is only read and must not overlap dX; the library
+ *   supplies no start vector.  info.iterations counts the products A v, opts.maxIter caps them over all cycles.
+ * Execution: one device state block with `stop` and `skip`, as in hipSpGMRESCSR: a step with beta == 0, the step that
+ *   reaches maxIter and a step with a value that is not finite set skip, and the cycle's remaining enqueued kernels
+ *   return at once.  The host enqueues the m - k steps of a cycle (fewer when maxIter is nearer), reads alpha[], beta[]
+ *   and the flags back once (info.hostChecks: the number of cycles; the read after v[0] is not counted), runs JACOBI on
+ *   the host inside that wait, uploads the cols x kk (or cols x found) block of S and enqueues the rotation.  Per step:
+ *   the SpMV and 8 launches whatever j is (two for each projection, the two updates -- the second carries the partials
+ *   of dot(w,w) --, the scalar step, v[j+1] = w / beta); per cycle one rotation more; 3 launches before the first cycle.
+ *   info.launches counts them (the uploads of S and the copy v[kk] = v[m] are copies, not launches); info.ms is the
+ *   host wall time of the call and info.jacobiMs the part of it spent in JACOBI.
+ *   Workspace, allocated by the call and freed before it returns, with ldv = n rounded up to even and nb = ceil(n/4096):
+ *   8*ldv*(ncv + 2) bytes (v[0 .. ncv], w), 8*nb*(ncv + 1) of partials, 32 KiB for S, about 2 KiB of state.
+ *   Synchronous, on the library stream; not capturable.
+ * Returns EXIT_SUCCESS whatever the status (info may be NULL).  Refused with a message and EXIT_FAILURE, every output
+ *   untouched: NULL dA, dV0, opts, dX, theta or res, or a handle that is not live; ELL handles; M != N; nev == 0,
+ *   nev >= ncv, ncv > 64 or ncv > M; an unknown which; tol negative or NaN; keep not 0 and outside nev .. ncv-1;
+ *   ldx < M; dV0 overlapping the span of dX. */
+#define SPMV_EIG_LARGEST  0
+#define SPMV_EIG_SMALLEST 1
+typedef struct {
+    unsigned nev;           /* eigenpairs wanted, 1 .. ncv-1                                 */
+    unsigned ncv;           /* m: Lanczos vectors of a cycle, nev+1 .. min(64, M)            */
+    int      which;         /* SPMV_EIG_LARGEST or SPMV_EIG_SMALLEST (algebraically)         */
+    double   tol;           /* converged when res[i] <= tol * scale for every i < nev        */
+    ulong    maxIter;       /* products A v at most, over all cycles                         */
+    unsigned keep;          /* columns a restart keeps, nev .. ncv-1; 0: the default         */
+} spmvLanczosOpts;
+typedef struct {
+    int      status;        /* SPMV_KRYLOV_*                                                 */
+    unsigned found;         /* eigenpairs written                                            */
+    ulong    iterations;    /* products A v                                                  */
+    ulong    cycles;
+    ulong    launches;      /* kernels enqueued (an SpMV counted as one)                     */
+    ulong    hostChecks;    /* read-backs of the device state: the cycles                    */
+    double   scale;         /* max |theta[i]| over the last cycle's Ritz values              */
+    unsigned sweepsMax;     /* the most Jacobi sweeps a cycle took                           */
+    double   ms;            /* host wall time of the call                                    */
+    double   jacobiMs;      /* of which inside JACOBI, over all cycles                       */
+} spmvLanczosInfo;
+int spmvHipBlockCombine(size_t n, unsigned m, unsigned k, const double* dV, size_t ldv, const double* dS, size_t lds, double* dY,
+                        size_t ldy);
+int hipSpLanczosCSR(spmat* dA, const double* dV0, const spmvLanczosOpts* opts, double* dX, size_t ldx, double* theta, double* res,
+                    spmvLanczosInfo* info);
 /* ------------------------------------------------------------- multi-colour ordering, symmetric permutation */
 /* Reordering for fewer level sets: if rows of one colour share no entry and the matrix is permuted so that colours are
  * contiguous, both triangles of B = P A P^T have at most as many level sets as there are colours, and hipSpTRSVCSR /

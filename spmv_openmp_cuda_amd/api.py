@@ -122,6 +122,8 @@ _sigs = {
     "hipSpCGBlockCSR": ([C.POINTER(spmat), C.POINTER(spmat), C.c_uint, _vp, _sz, _i, _vp, _sz, _i, _vp, _vp, _vp], _i),
     "hipSpBiCGStabBlockCSR": ([C.POINTER(spmat), C.POINTER(spmat), C.c_uint, _vp, _sz, _i, _vp, _sz, _i, _vp, _vp, _vp], _i),
     "hipSpGMRESCSR": ([C.POINTER(spmat), C.POINTER(spmat), _vp, _vp, _vp, _vp], _i),
+    "spmvHipBlockCombine": ([_sz, C.c_uint, C.c_uint, _vp, _sz, _vp, _sz, _vp, _sz], _i),
+    "hipSpLanczosCSR": ([C.POINTER(spmat), _vp, _vp, _vp, _sz, _vp, _vp, _vp], _i),
     "spmvHipColourCSR": ([C.POINTER(spmat), _vp, _vp, _vp, _vp], _i),
     "spmvHipCsrPermute": ([C.POINTER(spmat), _vp, C.POINTER(spmat)], _i),
     "spmvHipPermuteRefresh": ([C.POINTER(spmat), C.POINTER(spmat)], _i),
@@ -157,6 +159,8 @@ _sigs = {
 SPMV_DENSE_ROW_MAJOR, SPMV_DENSE_COL_MAJOR = 0, 1          # include/spmvHip.h: layouts of hipSpMMRowsCSR's X and Y
 SPMV_TRI_LOWER, SPMV_TRI_UPPER = 0, 1                      # include/spmvHip.h: hipSpTRSVCSR's uplo ...
 SPMV_DIAG_STORED, SPMV_DIAG_UNIT = 0, 1                    # ... and diag
+SPMV_EIG_LARGEST, SPMV_EIG_SMALLEST = 0, 1                 # include/spmvHip.h: spmvLanczosOpts.which
+EIG_WHICH = {"LA": SPMV_EIG_LARGEST, "SA": SPMV_EIG_SMALLEST}      # DeviceMatrix.eigsh's `which`
 
 
 class spmvTilesOpts(C.Structure):
@@ -228,6 +232,19 @@ class spmvGmresOpts(C.Structure):
     """include/spmvHip.h `spmvGmresOpts`: tolerance, cap on the inner iterations, restart length (1 .. 64), optional host
     history (maxIter + 1 doubles)."""
     _fields_ = [("tol", C.c_double), ("maxIter", C.c_ulong), ("restart", C.c_uint), ("history", C.POINTER(C.c_double))]
+
+
+class spmvLanczosOpts(C.Structure):
+    """include/spmvHip.h `spmvLanczosOpts`: eigenpairs wanted, Lanczos vectors of a cycle, the end of the spectrum,
+    tolerance, cap on the products A v, columns a restart keeps (0: the default)."""
+    _fields_ = [("nev", C.c_uint), ("ncv", C.c_uint), ("which", _i), ("tol", C.c_double), ("maxIter", C.c_ulong),
+                ("keep", C.c_uint)]
+
+
+class spmvLanczosInfo(C.Structure):
+    """include/spmvHip.h `spmvLanczosInfo`: what a hipSpLanczosCSR call did."""
+    _fields_ = [("status", _i), ("found", C.c_uint), ("iterations", C.c_ulong), ("cycles", C.c_ulong), ("launches", C.c_ulong),
+                ("hostChecks", C.c_ulong), ("scale", C.c_double), ("sweepsMax", C.c_uint), ("ms", C.c_double), ("jacobiMs", C.c_double)]
 
 
 class spmvKrylovInfo(C.Structure):
@@ -1222,6 +1239,33 @@ class DeviceMatrix:
         info.history holds the estimates inside a cycle and the true squared residual at every cycle's last index."""
         return self._krylov(lib.hipSpGMRESCSR, "hipSpGMRESCSR", b, x0, precond, tol, maxiter, history, restart=restart)
 
+    def eigsh(self, k=6, which="LA", ncv=None, v0=None, tol=1e-8, maxiter=None, keep=0):
+        """hipSpLanczosCSR: the k algebraically largest (which="LA") or smallest ("SA") eigenpairs of this symmetric
+        matrix by thick-restart Lanczos, with the bits of the loop in include/spmvHip.h.  Returns (theta, X, info): theta
+        a numpy array of the info.found values in the order of the wanted end, X the (N, found) eigenvectors (numpy for
+        a numpy v0, else a torch tensor with contiguous columns), info a spmvLanczosInfo with info.res the residual
+        estimates.  Conventions of this layer, not of the library: ncv=None means min(N, 64, max(2k + 1, 20)); v0=None
+        means numpy.random.default_rng(0).standard_normal(N); maxiter=None means 10 N products A v."""
+        N = int(self.handle.N)
+        if which not in EIG_WHICH:
+            raise SpmvHipError(f"eigsh: which must be one of {sorted(EIG_WHICH)}, not {which!r}")
+        k = int(k)
+        ncv = min(N, 64, max(2 * k + 1, 20)) if ncv is None else int(ncv)
+        if v0 is None:
+            v0 = np.random.default_rng(0).standard_normal(N)
+        opts = spmvLanczosOpts(k, ncv, EIG_WHICH[which], float(tol), 10 * N if maxiter is None else int(maxiter), int(keep))
+        info = spmvLanczosInfo()
+        theta, res = np.zeros(max(k, 0)), np.zeros(max(k, 0))
+        with _Operands("eigsh", v0) as ops:
+            ops.vector("v0", v0, N)
+            ops.result("X", None, (max(k, 0), N))                    # (row c of this block is column c of X: ldx = N)
+            dv0, dx = ops.args
+            _check(lib.hipSpLanczosCSR(C.byref(self.handle), dv0, C.byref(opts), dx, N, _ptr(theta), _ptr(res), C.byref(info)),
+                   "hipSpLanczosCSR")
+            X = ops.value()
+        info.res = res[:info.found].copy()
+        return theta[:info.found].copy(), X[:info.found].T, info
+
     def cg_block(self, B, X0=None, precond=None, tol=1e-8, maxiter=1000, history=False):
         """hipSpCGBlockCSR: k solves A x_c = b_c in lock step, column c of X with the bits of cg() on column c of B (and of
         X0), the matrix and the preconditioner's schedule streamed once per iteration for all columns.  B (and X0) are
@@ -1629,6 +1673,22 @@ def multi_dot(V, w):
         dV, dw, dh = ops.args
         _check(lib.spmvHipMultiDot(n, k, dV, ldv, dw, dh), "spmvHipMultiDot")
         return ops.value()
+
+
+def block_combine(V, S):
+    """spmvHipBlockCombine: Y = V S with Y[i, c] the sum of V[i, j] * S[j, c] over ascending j from +0.0, every product and
+    every add rounded on its own.  V (n, m) and S (m, k), m and k in 1 .. 64: 2-D float64 device torch tensors with
+    contiguous columns (the rule of multi_dot's V) -> an (n, k) device tensor with contiguous columns; or numpy arrays ->
+    a numpy array."""
+    with _Operands("block_combine", V) as ops:
+        n, m, ldv = ops.columns("V", V)
+        ms, k, lds = ops.columns("S", S)
+        if ms != m:
+            raise SpmvHipError(f"block_combine: S must have {m} rows, not {ms}")
+        ops.result("Y", None, (k, n), least=8)                       # (row c of this block is column c of Y: ldy = n)
+        dV, dS, dY = ops.args
+        _check(lib.spmvHipBlockCombine(n, m, k, dV, ldv, dS, max(lds, m), dY, max(n, 1)), "spmvHipBlockCombine")
+        return ops.value().T
 
 
 def block_dot(U, V):

@@ -373,6 +373,16 @@ int  krylovBlockSolve(int bicg, const DevMat* a, const DevMat* m, uint32_t k, co
 // GMRES(restart) with CGS2 on the checked handles; fused != 0 folds the first update into the second projection's
 // partials; allocates gmresWorkspaceBytes, synchronous.
 int  enqueueMultiDot(uint64_t n, uint32_t k, const double* V, uint64_t ldv, const double* w, double* out, hipStream_t stream);
+// Y = V S and thick-restart Lanczos (lanczos.hip; contract in spmvHip.h, design in DESIGN.md section 39).
+// enqueueBlockCombine: one kernel (none for n = 0) on checked operands, *grid its shape.  lanczosSolve: the loop on the
+// checked handle and options; allocates lanczosWorkspaceBytes, synchronous; theta, res, X and info are written only on
+// EXIT_SUCCESS.  lanczosDefaultKeep: the columns a restart keeps when opts.keep == 0.
+int  enqueueBlockCombine(uint64_t n, uint32_t m, uint32_t k, const double* V, uint64_t ldv, const double* S, uint64_t lds, double* Y,
+                         uint64_t ldy, hipStream_t stream, dim3* grid);
+unsigned lanczosDefaultKeep(unsigned nev, unsigned ncv);
+size_t lanczosWorkspaceBytes(uint64_t n, uint32_t ncv);
+int  lanczosSolve(spmat* hA, const DevMat* a, const double* v0, const spmvLanczosOpts* opts, double* X, uint64_t ldx, double* theta,
+                  double* res, spmvLanczosInfo* info, hipStream_t stream);
 size_t gmresWorkspaceBytes(uint64_t n, uint32_t restart, uint64_t maxIter, int precond, int history);
 int  gmresSolve(spmat* hA, const DevMat* a, const DevMat* m, const double* b, double* x, const spmvGmresOpts* opts,
                 spmvKrylovInfo* info, int fused, hipStream_t stream);

@@ -1,4 +1,4 @@
-// krylov.hpp -- what the Krylov files (krylov.hip, krylov_block.hip, gmres.hip) share: the blocks and lanes of the
+// krylov.hpp -- what the Krylov files (krylov.hip, krylov_block.hip, gmres.hip, lanczos.hip) share: the blocks and lanes of the
 // fixed-order dot, the element-pair loads and stores, the state block of CG / BiCGStab and its scalar steps, the fixed tree,
 // the fused-pass kernel and its launcher, the workspace holder, the preconditioner of a solve, and the enqueue order of CG and
 // BiCGStab written once for the single and the block width (krylovLoop).

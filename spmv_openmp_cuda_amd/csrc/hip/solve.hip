@@ -1,6 +1,7 @@
 // solve.hip -- the solver side of the extern "C" boundary: triangular solves, ILU(0), the multi-colour ordering, the reverse
-// Cuthill-McKee ordering and the vector permutation, the dots, aggregation multigrid, and the three Krylov solvers.  The algorithm
-// files (trsv.hip, ilu0.hip, colour.hip, rcm.hip, krylov.hip, gmres.hip, aggregate.hip, amg.hip) build and launch; here are the checks, the library's settings
+// Cuthill-McKee ordering and the vector permutation, the dots, aggregation multigrid, the three Krylov solvers, the basis rotation
+// and the Lanczos eigensolver.  The algorithm
+// files (trsv.hip, ilu0.hip, colour.hip, rcm.hip, krylov.hip, gmres.hip, lanczos.hip, aggregate.hip, amg.hip) build and launch; here are the checks, the library's settings
 // handed down as arguments, and the timing bracket.  Contracts in spmvHip.h, designs in DESIGN.md sections 17 to 21 and 24.
 #include <hip/hip_runtime.h>
 #include <chrono>
@@ -586,6 +587,65 @@ int hipSpGMRESCSR(spmat* dA, spmat* dM, const double* dB, double* dX, const spmv
     const int rc = krylovArgs(who, dA, dM, dB, dX, opts, opts ? opts->tol : 0.0, opts ? opts->maxIter : 0, opts ? opts->history : nullptr, info, &a, &m);
     if (rc) return rc == 2 ? EXIT_SUCCESS : EXIT_FAILURE;
     if (gmresSolve(dA, a, m, dB, dX, opts, info, S.gmresFused, S.stream)) { ERR("%s: the solve failed", who); return EXIT_FAILURE; }
+    return EXIT_SUCCESS;
+}
+
+// ---- the basis rotation and the extreme eigenpairs (contract in spmvHip.h, design in DESIGN.md section 39)
+// bytes spanned by a column-major rows x cols block of leading dimension ld (0 for an empty block)
+static uint64_t colMajorSpan(uint64_t rows, unsigned cols, uint64_t ld) { return rows && cols ? ((cols - 1) * ld + rows) * sizeof(double) : 0; }
+static bool spansShare(const void* p, uint64_t pBytes, const void* q, uint64_t qBytes) {
+    const uintptr_t p0 = (uintptr_t)p, q0 = (uintptr_t)q;
+    return pBytes && qBytes && p0 < q0 + qBytes && q0 < p0 + pBytes;
+}
+
+int spmvHipBlockCombine(size_t n, unsigned m, unsigned k, const double* dV, size_t ldv, const double* dS, size_t lds, double* dY,
+                        size_t ldy) {
+    const char* who = "spmvHipBlockCombine";
+    const Ctx cx = libraryCtx();
+    if (!ready(who)) return EXIT_FAILURE;
+    if (n && (!dV || !dS || !dY)) { ERR("%s: %s is NULL", who, !dV ? "dV" : !dS ? "dS" : "dY"); return EXIT_FAILURE; }
+    if (m == 0 || m > 64 || k == 0 || k > 64) { ERR("%s: m=%u, k=%u: both must be in 1 .. 64", who, m, k); return EXIT_FAILURE; }
+    if (ldv < n || ldy < n || lds < m) { ERR("%s: ldv=%zu, ldy=%zu (n=%zu) or lds=%zu (m=%u) is too small", who, ldv, ldy, n, lds, m); return EXIT_FAILURE; }
+    const uint64_t vBytes = colMajorSpan(n, m, ldv), yBytes = colMajorSpan(n, k, ldy);
+    if (n && dY == dV) {
+        if (k > m || ldy != ldv) { ERR("%s: in place (dY == dV) needs k <= m and ldy == ldv", who); return EXIT_FAILURE; }
+    } else if (spansShare(dV, vBytes, dY, yBytes)) {
+        ERR("%s: dV and dY overlap without being the same block", who);
+        return EXIT_FAILURE;
+    }
+    if (spansShare(dS, colMajorSpan(m, k, lds), dY, yBytes)) { ERR("%s: dS and dY overlap", who); return EXIT_FAILURE; }
+    Launch L(cx, dim3(1), dim3(256));
+    dim3 grid(1);
+    if (enqueueBlockCombine(n, m, k, dV, ldv, dS, lds, dY, ldy, cx.stream, &grid)) { ERR("%s: launch failed", who); return EXIT_FAILURE; }
+    L.shape(grid, dim3(256));
+    return L.finish(who);
+}
+
+int hipSpLanczosCSR(spmat* dA, const double* dV0, const spmvLanczosOpts* opts, double* dX, size_t ldx, double* theta, double* res,
+                    spmvLanczosInfo* info) {
+    const char* who = "hipSpLanczosCSR";
+    if (!ready(who)) return EXIT_FAILURE;
+    if (!dV0 || !opts || !dX || !theta || !res) {
+        ERR("%s: %s is NULL", who, !dV0 ? "dV0" : !opts ? "opts" : !dX ? "dX" : !theta ? "theta" : "res");
+        return EXIT_FAILURE;
+    }
+    DevMat* a = csrOf(dA, who, "dA is an ELL handle (only CSR handles are solved)");
+    if (!a) return EXIT_FAILURE;
+    if (a->M != a->N) { ERR("%s: M=%lu != N=%lu: dA is not square", who, (unsigned long)a->M, (unsigned long)a->N); return EXIT_FAILURE; }
+    if (a->NZ && !a->AS && !a->unit) { ERR("%s: dA has no value array", who); return EXIT_FAILURE; }
+    if (opts->nev == 0 || opts->nev >= opts->ncv || opts->ncv > 64 || opts->ncv > a->M) {
+        ERR("%s: nev=%u, ncv=%u, M=%lu: 1 <= nev < ncv <= min(64, M) is required", who, opts->nev, opts->ncv, (unsigned long)a->M);
+        return EXIT_FAILURE;
+    }
+    if (opts->which != SPMV_EIG_LARGEST && opts->which != SPMV_EIG_SMALLEST) { ERR("%s: unknown which %d", who, opts->which); return EXIT_FAILURE; }
+    if (!(opts->tol >= 0.0)) { ERR("%s: tol %g is negative or NaN", who, opts->tol); return EXIT_FAILURE; }
+    if (opts->keep && (opts->keep < opts->nev || opts->keep > opts->ncv - 1)) {
+        ERR("%s: keep=%u is not 0 and not in nev .. ncv-1 = %u .. %u", who, opts->keep, opts->nev, opts->ncv - 1);
+        return EXIT_FAILURE;
+    }
+    if (ldx < a->M) { ERR("%s: ldx=%zu < M=%lu", who, ldx, (unsigned long)a->M); return EXIT_FAILURE; }
+    if (spansShare(dV0, a->M * sizeof(double), dX, colMajorSpan(a->M, opts->nev, ldx))) { ERR("%s: dV0 and dX overlap", who); return EXIT_FAILURE; }
+    if (lanczosSolve(dA, a, dV0, opts, dX, ldx, theta, res, info, S.stream)) { ERR("%s: the solve failed", who); return EXIT_FAILURE; }
     return EXIT_SUCCESS;
 }
 
