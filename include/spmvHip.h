@@ -265,6 +265,76 @@ int spmvHipTriInfo(spmat* dA, int uplo, spmvTriInfo* info);
  *   unit-value; the overlaps above; a multigrid hierarchy handle. */
 int hipSpTRSMCSR(spmat* dA, int uplo, int diag, unsigned k, const double* dB, size_t ldb, int bLayout,
                  double* dX, size_t ldx, int xLayout);
+/* Triangular solves by Jacobi sweeps: a fixed number S of sweeps on the triangle in place of the exact solve, for use as a
+ * preconditioner (iterative sparse triangular solves, Anzt, Chow and Dongarra).  DESIGN.md section 40.  A sweep has no
+ * dependence between rows: it is one launch, and no level sets are built.  The solve writes the bits of this loop, in IEEE
+ * double with no FMA contraction:
+ *     hipSpTRSVSweepsCSR(dA, uplo, diag, S, b, x):      T = the strict lower / upper triangle of dA, d_i = AS[diagPos[i]]
+ *         x0[i] = STORED ? b[i] / d_i : b[i]                                  for every i
+ *         for s = 1 .. S:                                                    (rows in any order: they read only x(s-1))
+ *             for every i:
+ *                 acc = +0.0
+ *                 for p in IRP[i] .. IRP[i+1]-1   (stored order)
+ *                     j = JA[p];  if (lower ? j < i : j > i):  acc += AS[p] * x(s-1)[j]     -- one rounding each, no FMA
+ *                 x(s)[i] = STORED ? (b[i] - acc) / d_i : (b[i] - acc)
+ *         x = x(S)
+ *   1. Entries outside the strict triangle are skipped, never added as 0.0 (-0.0 + 0.0 is +0.0).  Unsorted rows and repeated
+ *      (i, j) pairs are allowed; every stored strict-triangle entry is added, in stored order.
+ *   2. STORED needs exactly one diagonal entry per row, else the call is refused and the message names the row.  A zero
+ *      stored diagonal gives +-Inf or NaN exactly as the loop does.
+ *   3. Unit-value handles take the value from a register, as in hipSpTRSVCSR.
+ *   4. Consequence: x(S)[i] is the exact solution's x[i], bit for bit, on every row i whose level is at most S (induction on
+ *      the level: such a row reads only rows of lower levels, which are final from sweep level(j) <= S - 1 on, in the same
+ *      stored order as the exact loop).  So for S >= levels - 1 of that triangle (spmvTriInfo.levels) x has the bits of
+ *      hipSpTRSVCSR.  A row of level 0 has acc = +0.0, and b - (+0.0) is b bit for bit.  S = 0 is the diagonal scaling.
+ *   5. dB == dX (in place) is allowed: every intermediate iterate lives in the plan's workspace and only the last sweep
+ *      writes x, reading b at its own index.  Any other overlap is refused.
+ *   6. S above SPMV_TRI_SWEEPS_MAX (4096) is refused.
+ *   7. hipSpTRSMSweepsCSR: the argument list of hipSpTRSMCSR plus S; column c of X has the bits of the single sweep solve on
+ *      column c of B; both layouts and leading dimensions; padding is never written (nor read); columns go in panels of at
+ *      most 16 inside ONE launch per sweep, so the launch count does not depend on k.  In place as hipSpTRSMCSR.
+ *   8. As a preconditioner (spmvHipTriSetApply(dM, SPMV_TRI_APPLY_SWEEPS, S_L, S_U, width)): z = U~^-1 (L~^-1 r) with S_L
+ *      lower sweeps (UNIT) and S_U upper sweeps (STORED) wherever a Krylov solve takes this handle as dM -- hipSpCGCSR,
+ *      hipSpBiCGStabCSR, hipSpGMRESCSR and, with width >= k, the block solves -- whose launch counters count the sweep launches;
+ *      no level sets are analysed for such a dM.  For the ILU(0) factors of a symmetric A with S_L == S_U = S the operator is
+ *      M^-1 = P^T D^-1 P, P = sum_{j <= S} (-strict L)^j: symmetric, and positive definite whenever the factored diagonal is
+ *      positive, so it is a CG preconditioner.  Unequal counts are for BiCGStab and GMRES only; this is not checked, as the
+ *      symmetry of A is not.  Strong couplings need more sweeps (DESIGN.md section 40 has the counts).  SPMV_TRI_APPLY_EXACT
+ *      (the default) gives the exact solves and their bits again; the plan stays.
+ * Plan: spmvHipTriSweepsPrepare(dA, blockWidth) builds it (blockWidth 0: one column; a larger width than the plan's widens
+ *   the workspace, a smaller one is a no-op): the diagonal's places and two M x width iterates, 4 B + 16 B x width per row.
+ *   Synchronous, allocates (not capturable).  The first sweep solve of an unprepared handle prepares it for its own width.
+ *   spmvHipUpdateValues, spmvHipValuesChanged, hipSpILU0CSR and spmvHipTransposeRefresh keep it at the same addresses (the
+ *   sweeps read AS live); hipFreeSpmat frees it.
+ * Solve: kernels only, on the library stream: S launches (UNIT; S + 1 for S == 1 in place; S == 0: one copy, none in place),
+ *   S + 1 (STORED); no allocation and no host sync once prepared, so it can be captured into a graph.  spmvHipSetSync,
+ *   spmvHipLastKernelSeconds and spmvHipLastLaunch as for hipSpTRSVCSR.  M = 0 succeeds and writes nothing.
+ * Refused with a message and EXIT_FAILURE, outputs and handle untouched: what hipSpTRSVCSR / hipSpTRSMCSR refuse; S above
+ *   the cap; an unknown mode; k above the prepared width.
+ * spmvHipTriSweepsInfo: all zeros while the handle has no plan. */
+#define SPMV_TRI_APPLY_EXACT  0
+#define SPMV_TRI_APPLY_SWEEPS 1
+#define SPMV_TRI_SWEEPS_MAX   4096
+typedef struct {
+    int      mode;          /* SPMV_TRI_APPLY_EXACT | SPMV_TRI_APPLY_SWEEPS: how a Krylov solve applies this handle as dM */
+    unsigned lowerSweeps;   /* S_L and                                                                               */
+    unsigned upperSweeps;   /* S_U of one application in SWEEPS mode                                                 */
+    unsigned width;         /* columns the workspace holds; 0: no plan                                               */
+    ulong    solveLaunches; /* kernel launches the last sweep solve enqueued                                         */
+    ulong    applyLaunches; /* launches of one application in SWEEPS mode: S_L + S_U, + 1 when one of them is 0; EXACT: 0 */
+    long     firstBadDiag;  /* -1, or the first row without exactly one stored diagonal entry                        */
+    int      sorted;        /* every row ascends strictly and holds one diagonal entry (the ILU(0) precondition)     */
+    int      prepares;      /* builds and widenings of the plan (stays 1 across value updates)                       */
+    size_t   bytes;         /* device memory the plan keeps                                                          */
+    const uint32_t* diagPos;    /* the plan's device arrays (for address checks; NULL without a plan): the diagonal's places */
+    const double*   workspace;  /* ... and the two M x width iterates                                                 */
+} spmvTriSweepsInfo;
+int spmvHipTriSweepsPrepare(spmat* dA, unsigned blockWidth);
+int hipSpTRSVSweepsCSR(spmat* dA, int uplo, int diag, unsigned sweeps, const double* dB, double* dX);
+int hipSpTRSMSweepsCSR(spmat* dA, int uplo, int diag, unsigned sweeps, unsigned k, const double* dB, size_t ldb, int bLayout,
+                       double* dX, size_t ldx, int xLayout);
+int spmvHipTriSetApply(spmat* dA, int mode, unsigned lowerSweeps, unsigned upperSweeps, unsigned blockWidth);
+int spmvHipTriSweepsInfo(spmat* dA, spmvTriSweepsInfo* info);
 /* ------------------------------------------------------------- incomplete factorisation */
 /* hipSpILU0CSR overwrites the values of a square device CSR handle with its ILU(0) factors, in place: the strictly lower
  * part becomes L (unit diagonal, not stored), the diagonal and the upper part U, so that hipSpTRSVCSR(LOWER, UNIT) then

@@ -107,6 +107,11 @@ _sigs = {
     "hipSpTRSVCSR": ([C.POINTER(spmat), _i, _i, _vp, _vp], _i),
     "spmvHipTriInfo": ([C.POINTER(spmat), _i, _vp], _i),
     "hipSpTRSMCSR": ([C.POINTER(spmat), _i, _i, C.c_uint, _vp, _sz, _i, _vp, _sz, _i], _i),
+    "spmvHipTriSweepsPrepare": ([C.POINTER(spmat), C.c_uint], _i),
+    "hipSpTRSVSweepsCSR": ([C.POINTER(spmat), _i, _i, C.c_uint, _vp, _vp], _i),
+    "hipSpTRSMSweepsCSR": ([C.POINTER(spmat), _i, _i, C.c_uint, C.c_uint, _vp, _sz, _i, _vp, _sz, _i], _i),
+    "spmvHipTriSetApply": ([C.POINTER(spmat), _i, C.c_uint, C.c_uint, C.c_uint], _i),
+    "spmvHipTriSweepsInfo": ([C.POINTER(spmat), _vp], _i),
     "hipSpILU0CSR": ([C.POINTER(spmat)], _i),
     "spmvHipIlu0Info": ([C.POINTER(spmat), _vp], _i),
     "spmvHipFsaiSetup": ([C.POINTER(spmat), C.POINTER(spmat), _vp, C.POINTER(spmat), _vp], _i),
@@ -159,6 +164,8 @@ _sigs = {
 SPMV_DENSE_ROW_MAJOR, SPMV_DENSE_COL_MAJOR = 0, 1          # include/spmvHip.h: layouts of hipSpMMRowsCSR's X and Y
 SPMV_TRI_LOWER, SPMV_TRI_UPPER = 0, 1                      # include/spmvHip.h: hipSpTRSVCSR's uplo ...
 SPMV_DIAG_STORED, SPMV_DIAG_UNIT = 0, 1                    # ... and diag
+SPMV_TRI_APPLY_EXACT, SPMV_TRI_APPLY_SWEEPS = 0, 1         # include/spmvHip.h: spmvHipTriSetApply's mode
+SPMV_TRI_SWEEPS_MAX = 4096                                 # ... and the most sweeps of one solve
 SPMV_EIG_LARGEST, SPMV_EIG_SMALLEST = 0, 1                 # include/spmvHip.h: spmvLanczosOpts.which
 EIG_WHICH = {"LA": SPMV_EIG_LARGEST, "SA": SPMV_EIG_SMALLEST}      # DeviceMatrix.eigsh's `which`
 
@@ -201,6 +208,13 @@ class spmvTriInfo(C.Structure):
     _fields_ = [("levels", C.c_ulong), ("maxLevelRows", C.c_ulong), ("launches", C.c_ulong), ("fusedLevels", C.c_ulong),
                 ("longRows", C.c_ulong), ("firstBadDiag", C.c_long), ("analyses", _i), ("analysisMs", C.c_double),
                 ("bytes", _sz)]
+
+
+class spmvTriSweepsInfo(C.Structure):
+    """include/spmvHip.h `spmvTriSweepsInfo`: the plan of the triangular solves by Jacobi sweeps (all zeros: no plan)."""
+    _fields_ = [("mode", _i), ("lowerSweeps", C.c_uint), ("upperSweeps", C.c_uint), ("width", C.c_uint),
+                ("solveLaunches", C.c_ulong), ("applyLaunches", C.c_ulong), ("firstBadDiag", C.c_long), ("sorted", _i),
+                ("prepares", _i), ("bytes", _sz), ("diagPos", _vp), ("workspace", _vp)]
 
 
 class spmvIluInfo(C.Structure):
@@ -472,6 +486,14 @@ SPMV_LAUNCHERS = {
 def _check(rc, what):
     if rc != 0:
         raise SpmvHipError(f"{what} failed (EXIT_FAILURE) -- see stderr")
+
+
+def _sweep_count(s):
+    """a sweep count for the C boundary: a negative one cannot pass as a large unsigned"""
+    s = int(s)
+    if s < 0:
+        raise ValueError(f"sweeps = {s} is negative")
+    return s
 
 
 def alloc_refuse(n=-1, from_then_on=False):
@@ -1166,25 +1188,30 @@ class DeviceMatrix:
                "spmvHipTriInfo")
         return info
 
-    def solve_triangular(self, b, lower=True, unit_diagonal=False, out=None):
+    def solve_triangular(self, b, lower=True, unit_diagonal=False, out=None, sweeps=None):
         """hipSpTRSVCSR: x = T^-1 b for the lower (upper) triangle T of this square matrix, the other triangle ignored, with
         the bits of the serial loop (include/spmvHip.h).  b: a contiguous float64 device torch tensor of length N -> a torch
         tensor, `out` if given (same rules; `out` may be `b`: an in-place solve); or a numpy array -> uploaded, solved,
-        returned as numpy.  Runs on the library stream."""
+        returned as numpy.  Runs on the library stream.  sweeps=S: hipSpTRSVSweepsCSR, the iterate after S Jacobi sweeps on
+        the triangle in place of the exact solution (its own loop in include/spmvHip.h; no level sets)."""
         N = int(self.handle.N)
         uplo = SPMV_TRI_LOWER if lower else SPMV_TRI_UPPER
         diag = SPMV_DIAG_UNIT if unit_diagonal else SPMV_DIAG_STORED
         with _Operands("solve_triangular", b) as ops:
             ops.vector("b", b, N)
             ops.result("out", out, (N,))
-            _check(lib.hipSpTRSVCSR(C.byref(self.handle), uplo, diag, *ops.args), "hipSpTRSVCSR")
+            if sweeps is None:
+                _check(lib.hipSpTRSVCSR(C.byref(self.handle), uplo, diag, *ops.args), "hipSpTRSVCSR")
+            else:
+                _check(lib.hipSpTRSVSweepsCSR(C.byref(self.handle), uplo, diag, _sweep_count(sweeps), *ops.args), "hipSpTRSVSweepsCSR")
             return ops.value()
 
-    def solve_triangular_block(self, B, lower=True, unit_diagonal=False, out=None):
+    def solve_triangular_block(self, B, lower=True, unit_diagonal=False, out=None, sweeps=None):
         """hipSpTRSMCSR: X = T^-1 B for a block of right-hand sides in one pass over the triangle, column c of X with the bits
         of solve_triangular on column c of B.  B is (N, k) float64: a device torch tensor with unit stride in one dimension
         (the rules of matmul's X) -> a torch tensor, `out` if given (same rules, its own layout; `out` may be `B`: an
-        in-place solve); or a numpy array -> uploaded, solved, returned as numpy.  Runs on the library stream."""
+        in-place solve); or a numpy array -> uploaded, solved, returned as numpy.  Runs on the library stream.  sweeps=S:
+        hipSpTRSMSweepsCSR, column c with the bits of solve_triangular(..., sweeps=S) on column c."""
         N = int(self.handle.N)
         uplo = SPMV_TRI_LOWER if lower else SPMV_TRI_UPPER
         diag = SPMV_DIAG_UNIT if unit_diagonal else SPMV_DIAG_STORED
@@ -1192,8 +1219,35 @@ class DeviceMatrix:
             k, bl, ldb = ops.dense("B", B, N)
             xl, ldx = ops.result("out", out, (N, k))
             db, dx = ops.args
-            _check(lib.hipSpTRSMCSR(C.byref(self.handle), uplo, diag, k, db, ldb, bl, dx, ldx, xl), "hipSpTRSMCSR")
+            if sweeps is None:
+                _check(lib.hipSpTRSMCSR(C.byref(self.handle), uplo, diag, k, db, ldb, bl, dx, ldx, xl), "hipSpTRSMCSR")
+            else:
+                _check(lib.hipSpTRSMSweepsCSR(C.byref(self.handle), uplo, diag, _sweep_count(sweeps), k, db, ldb, bl, dx, ldx, xl),
+                       "hipSpTRSMSweepsCSR")
             return ops.value()
+
+    def prepare_triangular_sweeps(self, block_width=0):
+        """spmvHipTriSweepsPrepare: build the plan of the sweep solves now, or widen its workspace to block_width columns
+        (the first sweep solve does it otherwise)."""
+        _check(lib.spmvHipTriSweepsPrepare(C.byref(self.handle), int(block_width)), "spmvHipTriSweepsPrepare")
+
+    def set_triangular_apply(self, sweeps=None, block_width=0):
+        """spmvHipTriSetApply: how cg, bicgstab, gmres, cg_block and bicgstab_block apply this handle as their preconditioner M.
+        sweeps=None: the two exact triangular solves (the default).  sweeps=S or (S_lower, S_upper): that many Jacobi sweeps
+        on each triangle, one launch per sweep and no level sets; block_width >= k is needed by the block solves.  Equal
+        counts keep M^-1 symmetric (cg); unequal counts are for bicgstab and gmres."""
+        if sweeps is None:
+            _check(lib.spmvHipTriSetApply(C.byref(self.handle), SPMV_TRI_APPLY_EXACT, 0, 0, 0), "spmvHipTriSetApply")
+            return
+        lo, up = sweeps if isinstance(sweeps, (tuple, list)) else (sweeps, sweeps)
+        _check(lib.spmvHipTriSetApply(C.byref(self.handle), SPMV_TRI_APPLY_SWEEPS, _sweep_count(lo), _sweep_count(up), int(block_width)),
+               "spmvHipTriSetApply")
+
+    def triangular_sweeps_info(self) -> "spmvTriSweepsInfo":
+        """spmvHipTriSweepsInfo: the sweep plan of this handle (all zeros when it has none)."""
+        info = spmvTriSweepsInfo()
+        _check(lib.spmvHipTriSweepsInfo(C.byref(self.handle), C.byref(info)), "spmvHipTriSweepsInfo")
+        return info
 
     def ilu0(self) -> "spmvIluInfo":
         """hipSpILU0CSR: overwrite this square matrix's values with its ILU(0) factors in place (L strictly lower with a unit

@@ -46,6 +46,7 @@ struct CooPlan;             // what a handle assembled from triplets keeps for i
 struct AmgHierarchy;        // the levels of an aggregation multigrid preconditioner, amg.hip
 struct FsaiPlan;            // what an approximate-inverse factor G owns besides its arrays (below; fsai.hip builds the arrays)
 struct TempBuf;             // a scoped device buffer, device_prims.hpp
+struct TriSweepPlan;        // what the triangular solves by Jacobi sweeps keep on a handle (below; trisweep.hip builds it)
 
 // the level sets of one triangle (built by triAnalyse in trsv.hip; the ILU(0) factorisation of ilu0.hip runs on the lower one)
 struct TriSchedule {
@@ -127,6 +128,9 @@ struct DevMat {
     // the level-set schedules of the triangular solve (trsv.hip), [SPMV_TRI_LOWER] and [SPMV_TRI_UPPER]: built from the
     // pattern at the first solve or by spmvHipTriAnalyse, kept across value updates (the solve reads AS live)
     TriSchedule* tri[2] = {nullptr, nullptr};
+    // the plan of the triangular solves by Jacobi sweeps (trisweep.hip): built by spmvHipTriSweepsPrepare, spmvHipTriSetApply
+    // or the first sweep solve, kept across value updates (the sweeps read AS live), never with level sets
+    TriSweepPlan* sweep = nullptr;
     // the ILU(0) factorisation (ilu0.hip): what its pattern check found (checked once, kept across value updates) and
     // what the last call did
     bool      iluChecked = false;
@@ -136,6 +140,20 @@ struct DevMat {
     // writes: spmvHipUpdateValues / ValuesChanged (updateValues) and the refreshes of a derived handle (upload.hip).
     bool      iluPending = false;
     spmvIluInfo ilu{-1, -1, 0, 0, 0, 0, 0.0};
+};
+
+// What the sweep solves keep: the diagonal's places, what the pattern pass found, two M x width iterates
+// (ws, then ws + M * width), and how a Krylov solve applies this handle as dM.  The row blocks are the handle's blkInfo / blkBase.
+struct TriSweepPlan {
+    uint32_t* diagPos = nullptr;    // CSR position of row i's diagonal (meaningful where the row has exactly one)
+    double*   ws = nullptr;
+    uint32_t  width = 0;            // columns the iterates hold
+    long      firstBadDiag = -1;    // -1, or the first row without exactly one stored diagonal entry
+    bool      sorted = false;       // every row ascends strictly and holds one diagonal entry (the ILU(0) precondition)
+    int       mode = 0;             // SPMV_TRI_APPLY_EXACT | SPMV_TRI_APPLY_SWEEPS
+    uint32_t  sweeps[2] = {0, 0};   // lower, upper sweeps of one application in SWEEPS mode
+    int       prepares = 0;
+    unsigned long solveLaunches = 0;   // kernels the last sweep solve enqueued
 };
 
 // What a factor G of spmvHipFsaiSetup owns privately: G^T (made and refreshed by the transpose path, with a handle of its own
@@ -347,6 +365,21 @@ void freeTri(TriSchedule* s);
 // Krylov loops, krylov_block.hip).  The caller has checked the arguments.
 int  enqueueTrsm(const DevMat* d, int uplo, int diag, uint32_t k, const Dense& B, const Dense& X, hipStream_t stream, dim3* grid,
                  dim3* block, const uint32_t* stop = nullptr);
+// Triangular solves by Jacobi sweeps (trisweep.hip; contract in spmvHip.h, design in DESIGN.md section 40).  triSweepsPrepare
+// builds d->sweep for `width` columns (0: one) or widens its iterates: synchronous, allocates, never level sets; a failure
+// leaves the handle as it was.  enqueueTriSweeps: X = x(S) for k <= the width columns of a prepared handle; enqueueTriSweepsApply:
+// out = U~^-1 (L~^-1 in) with the plan's counts, in and out distinct blocks.  Both: kernels only on `stream`, every one
+// returns at once when `stop` is set and *stop != 0, *launches grows by the kernels enqueued.  triSweepsMode: d is applied
+// by sweeps as a dM.  The two counts: what a solve and an application enqueue.
+int  triSweepsPrepare(DevMat* d, uint32_t width, hipStream_t stream);
+int  enqueueTriSweeps(const DevMat* d, int uplo, int diag, uint32_t sweeps, uint32_t k, const Dense& B, const Dense& X, hipStream_t stream,
+                      dim3* grid, dim3* block, const uint32_t* stop, unsigned long* launches);
+int  enqueueTriSweepsApply(const DevMat* d, uint32_t k, const Dense& in, const Dense& out, hipStream_t stream, const uint32_t* stop,
+                           unsigned long* launches);
+bool triSweepsMode(const DevMat* d);
+unsigned long triSweepsSolveLaunches(uint32_t sweeps, bool dunit, bool inPlace);
+unsigned long triSweepsApplyLaunches(uint32_t lower, uint32_t upper);
+void freeTriSweeps(TriSweepPlan* p);
 // ILU(0) in place on the lower schedule d->tri[SPMV_TRI_LOWER] (ilu0.hip; contract in spmvHip.h, design in DESIGN.md section
 // 18).  iluUnsortedRow: the first row that is not strictly ascending, or -1 (synchronous).  iluFactor: the factorisation's
 // launches on `stream` for the checked handle, then the zero-pivot read-back (synchronous); groupWidth 8, 16 or 64 lanes

@@ -220,7 +220,7 @@ struct DevBufs {
 };
 
 // M^-1 of one solve, from its checked dM (null: none, and apply is not called): the ILU(0) pair U^-1 (L^-1 in) of an
-// analysed matrix handle, the cycle of a hierarchy of hA, or G^T (G in) of an approximate-inverse factor through its
+// analysed matrix handle (or, in SWEEPS mode, its Jacobi sweeps on the two triangles), the cycle of a hierarchy of hA, or G^T (G in) of an approximate-inverse factor through its
 // workspace vector.  apply enqueues kernels only on the solve's stream; every one but an SpMV returns at once when
 // *flag != 0; *launches grows by the kernels enqueued.
 struct Precond {
@@ -240,6 +240,8 @@ struct Precond {
             *launches += 2;
             return EXIT_SUCCESS;
         }
+        if (triSweepsMode(m))                                            // Jacobi sweeps on the two triangles (trisweep.hip)
+            return enqueueTriSweepsApply(m, 1, Dense{const_cast<double*>(in), m->M, false}, Dense{out, m->M, false}, s, flag, launches);
         dim3 g, bl;
         enqueueTrsv(m, SPMV_TRI_LOWER, SPMV_DIAG_UNIT, in, out, s, &g, &bl, flag);
         enqueueTrsv(m, SPMV_TRI_UPPER, SPMV_DIAG_STORED, out, out, s, &g, &bl, flag);

@@ -249,6 +249,7 @@ struct BlockWidth {
             out.launches += 2;
             return EXIT_SUCCESS;
         }
+        if (triSweepsMode(m)) return enqueueTriSweepsApply(m, k, dense(in), dense(outv), s, &head->allStop, &out.launches);
         dim3 g, bl;
         if (enqueueTrsm(m, SPMV_TRI_LOWER, SPMV_DIAG_UNIT, k, dense(in), dense(outv), s, &g, &bl, &head->allStop)) return EXIT_FAILURE;
         if (enqueueTrsm(m, SPMV_TRI_UPPER, SPMV_DIAG_STORED, k, dense(outv), dense(outv), s, &g, &bl, &head->allStop)) return EXIT_FAILURE;

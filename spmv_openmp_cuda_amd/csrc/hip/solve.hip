@@ -482,11 +482,12 @@ static int krylovArgs(const char* who, spmat* dA, spmat* dM, const double* dB, d
         if (!(m = triHandle(dM, SPMV_TRI_LOWER, who))) return EXIT_FAILURE;
         if (m->M != a->M) { ERR("%s: dM has %lu rows, dA %lu", who, (unsigned long)m->M, (unsigned long)a->M); return EXIT_FAILURE; }
         if (m->NZ && !m->AS && !m->unit) { ERR("%s: dM has no value array", who); return EXIT_FAILURE; }
+        const bool sweeps = triSweepsMode(m);                // applied by Jacobi sweeps (spmvHipTriSetApply): no level sets
         for (int uplo : {SPMV_TRI_LOWER, SPMV_TRI_UPPER})
-            if (m->M && !m->tri[uplo] && triAnalyse(m, uplo, S.triRunRows, S.stream)) { ERR("%s: the analysis of dM failed", who); return EXIT_FAILURE; }
-        if (m->M && m->tri[SPMV_TRI_UPPER]->info.firstBadDiag >= 0) {
-            ERR("%s: row %ld of dM does not hold exactly one stored diagonal entry (M^-1 divides by it)", who,
-                m->tri[SPMV_TRI_UPPER]->info.firstBadDiag);
+            if (!sweeps && m->M && !m->tri[uplo] && triAnalyse(m, uplo, S.triRunRows, S.stream)) { ERR("%s: the analysis of dM failed", who); return EXIT_FAILURE; }
+        const long badDiag = !m->M ? -1 : sweeps ? m->sweep->firstBadDiag : m->tri[SPMV_TRI_UPPER]->info.firstBadDiag;
+        if (badDiag >= 0) {
+            ERR("%s: row %ld of dM does not hold exactly one stored diagonal entry (M^-1 divides by it)", who, badDiag);
             return EXIT_FAILURE;
         }
     }
@@ -536,6 +537,12 @@ static int krylovBlock(int bicg, spmat* dA, spmat* dM, unsigned k, const double*
         const DevMat* h = anyDescOf(dM, who);
         // a hierarchy is taken when it has the workspace of a block cycle of k columns (spmvHipAmgSetBlockWidth)
         if (h && h->origin == Origin::HIERARCHY && blockCycleRefused(h, k, who)) return EXIT_FAILURE;
+        // a handle applied by sweeps is taken when its workspace holds k columns (spmvHipTriSetApply, spmvHipTriSweepsPrepare)
+        if (h && triSweepsMode(h) && h->sweep->width < k) {
+            ERR("%s: dM is applied by sweeps with a workspace of width %u, k = %u columns: spmvHipTriSweepsPrepare(dM, width >= k) widens it", who,
+                h->sweep->width, k);
+            return EXIT_FAILURE;
+        }
     }
     DevMat* a = nullptr;
     DevMat* m = nullptr;

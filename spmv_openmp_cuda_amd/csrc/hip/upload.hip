@@ -67,6 +67,7 @@ void freeDesc(DevMat* d) {
     }
     (void)devFree(d->blkInfo); (void)devFree(d->blkBase); (void)devFree(d->tmap);
     freeTri(d->tri[0]); freeTri(d->tri[1]);
+    freeTriSweeps(d->sweep);
     freeSpgemmPlan(d->prod);
     freeAddPlan(d->sum);
     freeFilterPlan(d->filt);
