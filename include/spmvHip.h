@@ -449,6 +449,21 @@ int spmvHipFsaiRefresh(spmat* dG, spmat* dA, spmvFsaiInfo* info);
 int spmvHipFsaiApply(spmat* dG, const double* dR, double* dZ);
 int spmvHipFsaiTranspose(spmat* dG, spmat* dGT);
 int spmvHipFsaiInfo(spmat* dG, spmvFsaiInfo* info);
+/* The factor stored in single precision.  spmvHipFsaiSetStorage(dG, SPMV_STORAGE_F32) builds the
+ * single-precision value form (spmvHipValuesF32, below) on G and on the G^T the factor owns; SPMV_STORAGE_F64, the state
+ * after a setup, releases both.  With F32 every application -- spmvHipFsaiApply, the dM of hipSpCGCSR / hipSpBiCGStabCSR /
+ * hipSpGMRESCSR, and the two SpMM passes of the block solvers -- is G~^T (G~ r) with G~_p = (double)(float)G_p: two f32
+ * products in serial order (hipSpMVRowsCSRf32 / hipSpMMRowsCSRf32), arithmetic in double.  Rounding is elementwise, so
+ * G~^T is the transpose of G~ and M^-1 stays symmetric positive semi-definite; the solution's accuracy is the outer
+ * loop's.  spmvHipFsaiRefresh keeps the setting: the forms follow the new values.  Back to F64 gives the f64 bits again.
+ * G itself keeps its double values: the f64 launchers on dG are unchanged by the setting.  Synchronous, allocates 4 B per
+ * entry of G and of G^T; idempotent.  Refused with a message, the setting left as it was: what spmvHipFsaiInfo refuses, a
+ * storage that is neither constant; a failed allocation leaves the factor in F64 with no form.
+ * spmvHipFsaiStorage reads the setting back. */
+#define SPMV_STORAGE_F64 0
+#define SPMV_STORAGE_F32 1
+int spmvHipFsaiSetStorage(spmat* dG, int storage);
+int spmvHipFsaiStorage(spmat* dG, int* storage);
 /* ------------------------------------------------------------- Krylov solves */
 /* spmvHipDot: *dResult (one double on the device) = u . v over n elements, in an order that is a function of n alone --
  * not of the grid, the device, the stream, the alignment of the pointers or the run.  DESIGN.md section 19.  Every
@@ -1503,6 +1518,24 @@ int spmvHipAmgGaussSeidel(spmat* dM, unsigned level, spmvAmgGsInfo* info);
 typedef struct { unsigned width; ulong bytes; } spmvAmgBlockInfo;
 int spmvHipAmgSetBlockWidth(spmat* dM, spmat* dA, unsigned width);
 int spmvHipAmgBlock(spmat* dM, spmvAmgBlockInfo* info);
+/* The hierarchy stored in single precision (SPMV_STORAGE_* and spmvHipValuesF32 are declared above and
+ * below).  spmvHipAmgSetStorage(dM, dA, SPMV_STORAGE_F32) builds the single-precision value form on every matrix a product of
+ * the cycle streams: dA itself (level 0 is the caller's handle: it gets the form as by spmvHipValuesF32(dA, 1)), every A_l
+ * below it, every R_l and every P_l; all of them or none.  Every A_l z, R_l d and P_l e of spmvHipAmgApply, of
+ * spmvHipAmgApplyBlock and of a hierarchy as dM is then the f32 product (hipSpMVRowsCSRf32 / hipSpMMRowsCSRf32: serial order on
+ * the values rounded through float, arithmetic in double), the fused z + P e its f32 instance with the bits of the unfused
+ * pair; the plain hierarchy's gather correction has no values.  dinv_l, rho_l and the Chebyshev tables stay what the double
+ * values give.  For the plain, smoothed and strength hierarchies, the Jacobi and the Chebyshev smoother.  The cycle is still
+ * one fixed linear operator, symmetric if it was.  spmvHipAmgRefresh keeps the setting: the forms follow the levels' new
+ * values.  SPMV_STORAGE_F64, the state after a setup, releases the forms (dA's only if this call built it).  Synchronous,
+ * allocates 4 B per entry of those matrices; idempotent.
+ * Refused with a message, the hierarchy left as it was: what spmvHipAmgRefresh refuses; a storage that is neither constant;
+ * F32 on a hierarchy with a Gauss-Seidel level (its sweeps read the double values in kernels of their own) -- and
+ * spmvHipAmgSetGaussSeidel on an F32 hierarchy; a failed allocation (what the call built is released).
+ * spmvHipAmgStorage: the setting, the number of levels, and the bytes of the f32 forms over all levels (0 in F64). */
+typedef struct { int storage; unsigned levels; ulong f32Bytes; } spmvAmgStorageInfo;
+int spmvHipAmgSetStorage(spmat* dM, spmat* dA, int storage);
+int spmvHipAmgStorage(spmat* dM, spmvAmgStorageInfo* info);
 int spmvHipAmgApplyBlock(spmat* dM, spmat* dA, unsigned k, const double* dR, size_t ldr, int rLayout,
                          double* dZ, size_t ldz, int zLayout);
 /* Release the device arrays behind a handle (cudaUtils.h:70-78). */
@@ -1607,6 +1640,60 @@ SPMV_HIP hipSpMVWarpsPerRowELLNTrasposed; /* <- cudaSpMVWarpsPerRowELLNTrasposed
  *   k = 0, an unknown layout, ld too small for its layout, X and Y address ranges that overlap (checked on the host). */
 int hipSpMMRowsCSR(spmat* dMat, unsigned k, const double* dX, size_t ldx, int xLayout,
                    double* dY, size_t ldy, int yLayout);
+
+/* ------------------------------------------- single-precision value storage */
+/* A CSR handle can keep a second copy of its values in single precision, 4 B per entry beside the 8 B of AS, for the
+ * products whose values need not be exact (a preconditioner's factors): a product then streams 8 instead of 12 bytes per
+ * entry.  Only the STORAGE is single precision.  x, y, every product, every sum and their order stay what they are; the
+ * value is widened -- exactly -- when it is loaded.  DESIGN.md section 41.  The form is this loop over the NZ entries,
+ *     for p = 0 .. NZ-1:  AS32[p] = (float)AS[p]                          -- IEEE round to nearest, ties to even
+ * with single-precision subnormals kept (nothing is flushed that is representable); a magnitude at or above
+ * (2 - 2^-24) * 2^127 becomes +-Inf and Inf stays Inf; a NaN stays a NaN (payload unspecified); the sign of a zero, and of
+ * a value that rounds to zero, is kept.  With A~_p = (double)AS32[p], an f32 product is sgemvSerial on A~ bit for bit
+ * (the serial-order names) or its sums in another order (the reduction-order name), as the f64 names are on A.
+ * A unit handle (every stored value the same double, spmvHipUnitValue) gets no array: its register value is rounded the
+ * same way on the host and the unit kernels serve it.
+ * spmvHipValuesF32(dMat, on): on != 0 builds the form and keeps it (one elementwise pass; one device allocation of
+ *   4 NZ bytes rounded up to 16, plus 32 for the pass's counters; a unit handle: none), on == 0 releases it.  Idempotent,
+ *   synchronous on the library stream.  The form belongs to the handle like the two-phase, stripes and SELL formats, is
+ *   freed with it, and FOLLOWS the values: after spmvHipUpdateValues / spmvHipValuesChanged, every refresh of a derived
+ *   handle and hipSpILU0CSR it holds the roundings of the new values at the same address.  A unit -> non-unit update
+ *   allocates the array, the reverse frees it; if that allocation is refused the update fails with a message, the handle
+ *   keeps its new double values and stays usable, and the form is not built (build it again).
+ *   No f64 call changes what it returns, which kernel it picks or what it allocates, built or not.
+ *   Accepted: CSR matrix handles of any origin (uploaded, adopted with 4- or 8-byte row pointers, derived).  Refused with
+ *   a message: NULL, a handle that is not live, an ELL handle, a multigrid hierarchy, a handle with entries but no value
+ *   array, and a live sharded matrix (the void* of spmvHipShardCSR handed in as the handle: recognised and refused before it is
+ *   read; its per-device handles are private to the shard and have no such form).
+ * spmvHipValuesF32Info: built, unit (built without an array), bytes (the allocation), refreshes (value updates followed
+ *   since the build), and for the build or the last refresh: inexact = entries p, not NaN, with (double)AS32[p] != AS[p]
+ *   (overflowed and flushed entries are among them); overflowed = finite AS[p] with infinite AS32[p]; flushed = nonzero
+ *   AS[p] with zero AS32[p]; firstOverflow = the smallest such CSR position, -1 for none.  The counts are integer atomics
+ *   after a wavefront count, so they do not depend on the order of anything.  Not built: zeros and -1.
+ * The products.  hipSpMVRowsCSRf32 (serial order) and hipSpMVWarpPerRowCSRf32 (any reduction order) have the signatures,
+ *   the synchronisation and the timing of their f64 twins; CONFIG is not looked at.  spmvHipEnqueueRowsF32 is the
+ *   enqueue-only serial-order form on an explicit stream.  hipSpMMRowsCSRf32 has the signature, layouts, panel rule and
+ *   refusals of hipSpMMRowsCSR, and every column of Y has the bits of hipSpMVRowsCSRf32.  All four are served by the
+ *   LDS-stream kernel (hipSpMVRowsCSR's variant 1) and its block form: there is no timed selection and no f32 form of the
+ *   other formats.  They never allocate -- capturable, enqueue-only under spmvHipSetSync(0) -- and refuse, with a message
+ *   that names spmvHipValuesF32, a handle whose form is not built. */
+typedef struct {
+    int   built;            /* the form exists                                                          */
+    int   unit;             /* ... without an array: the handle is a unit handle                        */
+    ulong bytes;            /* of its device allocation                                                 */
+    ulong refreshes;        /* value updates it has followed since it was built                         */
+    ulong inexact;          /* of the build or the last refresh: entries that changed under rounding    */
+    ulong overflowed;       /* ... finite entries that became +-Inf                                     */
+    ulong flushed;          /* ... nonzero entries that became +-0                                      */
+    long  firstOverflow;    /* ... the first overflowed CSR position, -1: none                          */
+} spmvF32Info;
+int spmvHipValuesF32(spmat* dMat, int on);
+int spmvHipValuesF32Info(spmat* dMat, spmvF32Info* info);
+SPMV_HIP hipSpMVRowsCSRf32;
+SPMV_HIP hipSpMVWarpPerRowCSRf32;
+int spmvHipEnqueueRowsF32(spmat* dMat, double* dX, double* dY, void* stream);
+int hipSpMMRowsCSRf32(spmat* dMat, unsigned k, const double* dX, size_t ldx, int xLayout,
+                      double* dY, size_t ldy, int yLayout);
 
 /* Column-sliced two-phase SpMV for matrices whose x gather misses the caches
  * (DESIGN.md section 7): the GPU counterpart of the reference's 2-D decomposed

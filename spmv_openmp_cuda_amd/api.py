@@ -119,6 +119,11 @@ _sigs = {
     "spmvHipFsaiApply": ([C.POINTER(spmat), _vp, _vp], _i),
     "spmvHipFsaiTranspose": ([C.POINTER(spmat), C.POINTER(spmat)], _i),
     "spmvHipFsaiInfo": ([C.POINTER(spmat), _vp], _i),
+    "spmvHipFsaiSetStorage": ([C.POINTER(spmat), _i], _i), "spmvHipFsaiStorage": ([C.POINTER(spmat), C.POINTER(_i)], _i),
+    "spmvHipValuesF32": ([C.POINTER(spmat), _i], _i), "spmvHipValuesF32Info": ([C.POINTER(spmat), _vp], _i),
+    "hipSpMVRowsCSRf32": (_SPMV_ARGS, _i), "hipSpMVWarpPerRowCSRf32": (_SPMV_ARGS, _i),
+    "spmvHipEnqueueRowsF32": ([C.POINTER(spmat), _vp, _vp, _vp], _i),
+    "hipSpMMRowsCSRf32": ([C.POINTER(spmat), C.c_uint, _vp, _sz, _i, _vp, _sz, _i], _i),
     "spmvHipDot": ([_sz, _vp, _vp, _vp], _i),
     "hipSpCGCSR": ([C.POINTER(spmat), C.POINTER(spmat), _vp, _vp, _vp, _vp], _i),
     "hipSpBiCGStabCSR": ([C.POINTER(spmat), C.POINTER(spmat), _vp, _vp, _vp, _vp], _i),
@@ -159,6 +164,7 @@ _sigs = {
     "spmvHipAmgGaussSeidel": ([C.POINTER(spmat), C.c_uint, _vp], _i),
     "spmvHipAmgSetBlockWidth": ([C.POINTER(spmat), C.POINTER(spmat), C.c_uint], _i),
     "spmvHipAmgBlock": ([C.POINTER(spmat), _vp], _i),
+    "spmvHipAmgSetStorage": ([C.POINTER(spmat), C.POINTER(spmat), _i], _i), "spmvHipAmgStorage": ([C.POINTER(spmat), _vp], _i),
     "spmvHipAmgApplyBlock": ([C.POINTER(spmat), C.POINTER(spmat), C.c_uint, _vp, _sz, _i, _vp, _sz, _i], _i),
 }
 SPMV_DENSE_ROW_MAJOR, SPMV_DENSE_COL_MAJOR = 0, 1          # include/spmvHip.h: layouts of hipSpMMRowsCSR's X and Y
@@ -168,6 +174,14 @@ SPMV_TRI_APPLY_EXACT, SPMV_TRI_APPLY_SWEEPS = 0, 1         # include/spmvHip.h: 
 SPMV_TRI_SWEEPS_MAX = 4096                                 # ... and the most sweeps of one solve
 SPMV_EIG_LARGEST, SPMV_EIG_SMALLEST = 0, 1                 # include/spmvHip.h: spmvLanczosOpts.which
 EIG_WHICH = {"LA": SPMV_EIG_LARGEST, "SA": SPMV_EIG_SMALLEST}      # DeviceMatrix.eigsh's `which`
+SPMV_STORAGE_F64, SPMV_STORAGE_F32 = 0, 1                  # include/spmvHip.h: spmvHipFsaiSetStorage's storage
+STORAGES = {"f64": SPMV_STORAGE_F64, "f32": SPMV_STORAGE_F32}
+
+
+def _storage(s, who):
+    if s not in STORAGES:
+        raise SpmvHipError(f"{who}: storage {s!r} is neither 'f64' nor 'f32'")
+    return STORAGES[s]
 
 
 class spmvTilesOpts(C.Structure):
@@ -224,6 +238,12 @@ class spmvIluInfo(C.Structure):
 
 
 SPMV_FSAI_MAX_ROW = 64                                     # include/spmvHip.h: the longest row of an approximate-inverse factor
+
+
+class spmvF32Info(C.Structure):
+    """include/spmvHip.h `spmvF32Info`: the single-precision value form of a handle and what its last rounding pass did."""
+    _fields_ = [("built", _i), ("unit", _i), ("bytes", C.c_ulong), ("refreshes", C.c_ulong), ("inexact", C.c_ulong),
+                ("overflowed", C.c_ulong), ("flushed", C.c_ulong), ("firstOverflow", C.c_long)]
 
 
 class spmvFsaiOpts(C.Structure):
@@ -424,6 +444,11 @@ class spmvAmgBlockInfo(C.Structure):
     _fields_ = [("width", C.c_uint), ("bytes", C.c_ulong)]
 
 
+class spmvAmgStorageInfo(C.Structure):
+    """include/spmvHip.h `spmvAmgStorageInfo`: a hierarchy's storage, its levels and the bytes of its f32 forms (0 in F64)."""
+    _fields_ = [("storage", _i), ("levels", C.c_uint), ("f32Bytes", C.c_ulong)]
+
+
 class spmvAllocStats(C.Structure):
     """include/spmvHip.h `spmvAllocStats`: the ledger of the library's device allocations (for tests)."""
     _fields_ = [("live", C.c_ulong), ("liveBytes", C.c_ulong), ("peakBytes", C.c_ulong), ("calls", C.c_ulong),
@@ -473,6 +498,11 @@ for _name, (_args, _res) in _hsigs.items():
 SPMV_LAUNCHERS = {
     "hipSpMVRowsCSR": lib.hipSpMVRowsCSR,
     "hipSpMVWarpPerRowCSR": lib.hipSpMVWarpPerRowCSR,
+    "hipSpMVRowsCSRf32": getattr(lib, "hipSpMVRowsCSRf32", None),           # (the products of the single-precision value form:
+    "hipSpMVWarpPerRowCSRf32": getattr(lib, "hipSpMVWarpPerRowCSRf32", None),   # values_f32() first; None only in an older
+                                                                            # tuning build loaded through SPMV_LIB).  The third f32 SpMV
+    # entry point, spmvHipEnqueueRowsF32, takes (handle, x, y, stream) -- no CONFIG -- and so cannot stand in this table of
+    # (handle, x, CONFIG, y) callables: it is bound in _sigs and called as lib.spmvHipEnqueueRowsF32.
     "hipSpMVTilesCSR": lib.hipSpMVTilesCSR,
     "hipSpMVStripesCSR": lib.hipSpMVStripesCSR,
     "hipSpMVAutoCSR": lib.hipSpMVAutoCSR,
@@ -909,6 +939,20 @@ class DeviceMatrix:
         """spmvHipValuesChanged: the handle's own value array (an adopted dAS) was rewritten on the device."""
         _check(lib.spmvHipValuesChanged(C.byref(self.handle)), "spmvHipValuesChanged")
 
+    def values_f32(self, on=True):
+        """spmvHipValuesF32: build (or, on=False, release) the single-precision form of this CSR matrix's values, 4 B per
+        entry beside the doubles: AS32[p] = (float)AS[p], round to nearest even.  The f32 launchers (`spmv` with
+        "hipSpMVRowsCSRf32" / "hipSpMVWarpPerRowCSRf32", `matmul(values="f32")`) stream it and compute in double; it follows
+        every later change of the values.  Idempotent."""
+        _check(lib.spmvHipValuesF32(C.byref(self.handle), 1 if on else 0), "spmvHipValuesF32")
+
+    def values_f32_info(self) -> "spmvF32Info":
+        """spmvHipValuesF32Info: built, unit, bytes, refreshes, and what the build or the last refresh rounded: inexact,
+        overflowed, flushed, firstOverflow."""
+        info = spmvF32Info()
+        _check(lib.spmvHipValuesF32Info(C.byref(self.handle), C.byref(info)), "spmvHipValuesF32Info")
+        return info
+
     def update_info(self) -> "spmvUpdateInfo":
         """spmvHipLastUpdateInfo: what the last update_values / values_changed did."""
         info = spmvUpdateInfo()
@@ -1141,7 +1185,7 @@ class DeviceMatrix:
         accepted as `precond=` by cg / bicgstab / gmres of this matrix.  smoothed: spmvHipAmgSetupSmoothed, the
         prolongator T - omegaP D^-1 A T (omegaP None: (4/3) / rho_l per level).  theta or thetaScale given (with
         smoothed=True): spmvHipAmgSetupStrength, which aggregates and smooths on the strength-filtered matrix with the
-        threshold theta * thetaScale^l on level l (None: 0.08, 0.5)."""
+        threshold theta * thetaScale^l on level l (None: 0.08, 0.5).  Stored in single precision: `A.amg(...).set_storage("f32")`."""
         opts = spmvAmgOpts(int(seed) & 0xFFFFFFFF, int(coarseRows or 0), int(maxLevels or 0), float(omega or 0.0), _amg_sweeps(nu1),
                            _amg_sweeps(nu2), _amg_sweeps(nuCoarse))
         h = AmgHierarchy(self)
@@ -1163,8 +1207,9 @@ class DeviceMatrix:
         h.rows = int(h.handle.M)
         return h
 
-    def matmul(self, X, out=None):
-        """hipSpMMRowsCSR: Y = A X, column c of Y bit-identical to sgemvSerial on column c of X.  X is (N, k) float64:
+    def matmul(self, X, out=None, values="f64"):
+        """hipSpMMRowsCSR: Y = A X, column c of Y bit-identical to sgemvSerial on column c of X; values="f32": hipSpMMRowsCSRf32,
+        the same from the single-precision form of the values (`values_f32()` first), arithmetic in double.  X is (N, k) float64:
         a device torch tensor with unit stride in one dimension (a contiguous tensor is row-major, a `.t()` view of a
         contiguous (k, N) tensor column-major; the leading dimension is the other stride) -> a torch tensor, `out` if
         given (same rules); or a numpy array -> uploaded, multiplied, returned as numpy.  Runs on the library stream."""
@@ -1173,7 +1218,8 @@ class DeviceMatrix:
             k, xl, ldx = ops.dense("X", X, N)
             yl, ldy = ops.result("out", out, (M, k))
             dx, dy = ops.args
-            _check(lib.hipSpMMRowsCSR(C.byref(self.handle), k, dx, ldx, xl, dy, ldy, yl), "hipSpMMRowsCSR")
+            name = "hipSpMMRowsCSRf32" if _storage(values, "matmul") else "hipSpMMRowsCSR"
+            _check(getattr(lib, name)(C.byref(self.handle), k, dx, ldx, xl, dy, ldy, yl), name)
             return ops.value()
 
     def triangular_analyse(self, lower=True):
@@ -1261,18 +1307,21 @@ class DeviceMatrix:
         _check(lib.spmvHipIlu0Info(C.byref(self.handle), C.byref(info)), "spmvHipIlu0Info")
         return info
 
-    def fsai(self, pattern=None, lanes_per_row=0) -> "Fsai":
+    def fsai(self, pattern=None, lanes_per_row=0, storage="f64") -> "Fsai":
         """spmvHipFsaiSetup: the factorised sparse approximate inverse G of this square matrix, G^T G ~ A^-1, with the bits
         of the loop in include/spmvHip.h.  Only the lower triangle of this matrix is read.  pattern: a DeviceMatrix of the
         same size whose columns j < i give row i of G (its values are not read; it may be freed afterwards), None for this
         matrix's own; a row of G holds at most SPMV_FSAI_MAX_ROW entries.  lanes_per_row: 0 (the built-in choice), 4, 16
-        or 64 -- no bit depends on it.  The result is accepted as `precond=` by cg / bicgstab / gmres / cg_block /
-        bicgstab_block of any matrix of this size."""
+        or 64 -- no bit depends on it.  storage: "f32" applies the factor from single-precision storage (Fsai.set_storage).
+        The result is accepted as `precond=` by cg / bicgstab / gmres / cg_block / bicgstab_block of any matrix of this size."""
+        _storage(storage, "fsai")
         g = Fsai(self)
         opts = spmvFsaiOpts(int(lanes_per_row))
         _check(lib.spmvHipFsaiSetup(C.byref(self.handle), C.byref(pattern.handle) if pattern is not None else None, C.byref(opts),
                                     C.byref(g.handle), C.byref(g._info)), "spmvHipFsaiSetup")
         g.rows = int(g.handle.M)
+        if storage != "f64":
+            g.set_storage(storage)
         return g
 
     def cg(self, b, x0=None, precond=None, tol=1e-8, maxiter=1000, history=False):
@@ -1410,6 +1459,21 @@ class AmgHierarchy(DeviceMatrix):
         cg_block / bicgstab_block(precond=this hierarchy) then take up to that many.  Updates `info` (its bytes count it)."""
         _check(lib.spmvHipAmgSetBlockWidth(C.byref(self.handle), C.byref(self.source.handle), int(width)), "spmvHipAmgSetBlockWidth")
         _check(lib.spmvHipAmgInfo(C.byref(self.handle), C.byref(self.info)), "spmvHipAmgInfo")
+
+    def set_storage(self, storage):
+        """spmvHipAmgSetStorage: "f32" builds the single-precision value form on the source matrix, on every level's matrix and
+        on every restriction and prolongator, and every product of the cycle (apply, apply_block, precond= of the solvers)
+        streams 8 instead of 12 bytes per entry, arithmetic in double; "f64" (the state after a setup) releases them.
+        refresh_from keeps the setting.  Refused on a hierarchy with a Gauss-Seidel level.  Returns the hierarchy, so that a
+        setup chains: `A.amg(smoothed=True).set_storage("f32")`."""
+        _check(lib.spmvHipAmgSetStorage(C.byref(self.handle), C.byref(self.source.handle), _storage(storage, "set_storage")), "spmvHipAmgSetStorage")
+        return self
+
+    def storage_info(self):
+        """spmvHipAmgStorage as a dict: storage ('f64' or 'f32'), levels, f32_bytes (of the forms over all levels)."""
+        v = spmvAmgStorageInfo()
+        _check(lib.spmvHipAmgStorage(C.byref(self.handle), C.byref(v)), "spmvHipAmgStorage")
+        return {"storage": "f32" if v.storage == SPMV_STORAGE_F32 else "f64", "levels": int(v.levels), "f32_bytes": int(v.f32Bytes)}
 
     def block_info(self):
         """spmvHipAmgBlock: the block workspace as a dict: width, bytes (zeros on a hierarchy without one)."""
@@ -1552,6 +1616,19 @@ class Fsai(DeviceMatrix):
         values of a fresh setup in place, addresses kept.  Returns info()."""
         _check(lib.spmvHipFsaiRefresh(C.byref(self.handle), C.byref(source.handle), C.byref(self._info)), "spmvHipFsaiRefresh")
         return self._info
+
+    def set_storage(self, storage):
+        """spmvHipFsaiSetStorage: "f32" builds the single-precision value form on G and on the factor's G^T, and every
+        application (apply, precond= of the solvers) becomes two f32 products -- 8 instead of 12 bytes per entry streamed,
+        arithmetic in double; "f64" (the state after a setup) releases them.  refresh_from keeps the setting."""
+        _check(lib.spmvHipFsaiSetStorage(C.byref(self.handle), _storage(storage, "set_storage")), "spmvHipFsaiSetStorage")
+
+    @property
+    def storage(self):
+        """spmvHipFsaiStorage: the setting, 'f64' or 'f32'"""
+        s = _i(0)
+        _check(lib.spmvHipFsaiStorage(C.byref(self.handle), C.byref(s)), "spmvHipFsaiStorage")
+        return "f32" if s.value == SPMV_STORAGE_F32 else "f64"
 
     def transposed(self):
         """spmvHipFsaiTranspose: the G^T this factor owns as host CSR arrays (M, N, IRP, JA, AS), downloaded"""

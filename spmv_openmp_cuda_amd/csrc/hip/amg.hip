@@ -68,6 +68,12 @@ struct AmgHierarchy {
     bool gsOneWay = false;
     uint32_t blockWidth = 0;                    // the columns a block cycle may take (spmvHipAmgSetBlockWidth; 0: none) ...
     uint64_t blockBytes = 0;                    // ... and the bytes of its workspace, which info.bytes counts
+    // SPMV_STORAGE_F64 | SPMV_STORAGE_F32 (spmvHipAmgSetStorage): with F32 every A_l z, R_l d and P_l e of
+    // the two cycles is the f32 product of the level's handle, whose single-precision form this hierarchy built: a0Form says
+    // that of the caller's level-0 handle too (it was not there before), a0Bytes what that form held when the storage was set
+    int storage = SPMV_STORAGE_F64;
+    bool a0Form = false;
+    uint64_t a0Bytes = 0;
     std::vector<AmgLevel> lv;
     spmvAmgInfo info{};
 };
@@ -212,10 +218,11 @@ struct AmgCorrectOp : StopMode {                // z = z + e[agg]
 // z = z + P e in one launch (the prolong-and-correct pass of a smoothed level whose P has short rows): a lane takes two
 // consecutive rows of P and walks both in stored order, each sum from +0.0 -- two independent chains per lane, every lane
 // of the grid its own pair, so the gathers of e overlap across the rows instead of queueing behind one lane's walk.  The
-// row bounds come as one 8-byte load (i is even, irp a whole allocation), z as one 16-byte access when VEC.
-template <bool VEC>
+// row bounds come as one 8-byte load (i is even, irp a whole allocation), z as one 16-byte access when VEC.  V: the type P's
+// values are stored in (float: P's single-precision form, widened -- exactly -- before the product; section 41).
+template <bool VEC, typename V = double>
 __global__ __launch_bounds__(AG_THREADS) void amg_prolong_kernel(uint64_t M, const uint32_t* __restrict__ irp, const uint32_t* __restrict__ ja,
-                                                                 const double* __restrict__ as, const double* __restrict__ e, double* __restrict__ z,
+                                                                 const V* __restrict__ as, const double* __restrict__ e, double* __restrict__ z,
                                                                  const uint32_t* __restrict__ stop) {
     const uint64_t i = (linear_block() * AG_THREADS + threadIdx.x) * 2;
     if (i >= M || (stop && *stop)) return;
@@ -224,8 +231,8 @@ __global__ __launch_bounds__(AG_THREADS) void amg_prolong_kernel(uint64_t M, con
     const uint32_t n0 = b.y - b.x, n1 = two ? irp[i + 2] - b.y : 0u, n = max(n0, n1);
     double s0 = 0.0, s1 = 0.0;
     for (uint32_t k = 0; k < n; ++k) {
-        if (k < n0) s0 = s0 + as[b.x + k] * e[ja[b.x + k]];
-        if (k < n1) s1 = s1 + as[b.y + k] * e[ja[b.y + k]];
+        if (k < n0) s0 = s0 + (double)as[b.x + k] * e[ja[b.x + k]];
+        if (k < n1) s1 = s1 + (double)as[b.y + k] * e[ja[b.y + k]];
     }
     const double2 zv = ld2<VEC>(z, i, two);
     st2<VEC>(z, i, two, make_double2(zv.x + s0, zv.y + s1));
@@ -803,7 +810,11 @@ int enqueueAmgCycle(const DevMat* m, spmat* hA, const double* r0, double* z0, hi
         launchVec(rows, nullptr, op, al, nullptr, nullptr, st);
         ++n;
     };
-    auto spmv = [&](spmat* h, const double* x, double* y) { ++n; return spmvHipEnqueueAutoRows(h, const_cast<double*>(x), y, st); };
+    const bool f32 = H->storage == SPMV_STORAGE_F32;          // (the f32 products refuse, with a line, a handle whose form is gone)
+    auto spmv = [&](spmat* h, const double* x, double* y) {
+        ++n;
+        return f32 ? spmvHipEnqueueRowsF32(h, const_cast<double*>(x), y, st) : spmvHipEnqueueAutoRows(h, const_cast<double*>(x), y, st);
+    };
     auto matAt = [&](size_t l) { return l ? &H->lv[l].A : hA; };
     // q sweeps of the hierarchy's smoother on level l, from z or from nothing (z = 0, not read): step k takes A z into t unless
     // it is the first from nothing, then makes its one pass.  (Chebyshev's d is the level's d_l: free at both smoothing sites)
@@ -867,12 +878,14 @@ int enqueueAmgCycle(const DevMat* m, spmat* hA, const double* r0, double* z0, hi
         double* z = l ? L.z : z0;
         const double* e = H->lv[l + 1].z;
         if (!H->smoothed()) pass(L.M, AmgCorrectOp{{stop}, e, L.agg, z}, {z});
-        else if (L.fused) {
+        else if (L.fused && !(f32 && !matOf(&L.P)->AS32)) {   // (F32 and a P without an array -- a unit P, or the form gone: the product below)
             const DevMat* p = matOf(&L.P);
             const dim3 grid = gridFor((L.M + 1) / 2);
             const uint32_t* irp = static_cast<const uint32_t*>(p->IRP);
-            if (aligned16(z)) hipLaunchKernelGGL(amg_prolong_kernel<true>, grid, dim3(AG_THREADS), 0, st, L.M, irp, p->JA, p->AS, e, z, stop);
-            else              hipLaunchKernelGGL(amg_prolong_kernel<false>, grid, dim3(AG_THREADS), 0, st, L.M, irp, p->JA, p->AS, e, z, stop);
+            if (f32 && aligned16(z)) hipLaunchKernelGGL((amg_prolong_kernel<true, float>), grid, dim3(AG_THREADS), 0, st, L.M, irp, p->JA, p->AS32, e, z, stop);
+            else if (f32)            hipLaunchKernelGGL((amg_prolong_kernel<false, float>), grid, dim3(AG_THREADS), 0, st, L.M, irp, p->JA, p->AS32, e, z, stop);
+            else if (aligned16(z))   hipLaunchKernelGGL(amg_prolong_kernel<true>, grid, dim3(AG_THREADS), 0, st, L.M, irp, p->JA, p->AS, e, z, stop);
+            else                     hipLaunchKernelGGL(amg_prolong_kernel<false>, grid, dim3(AG_THREADS), 0, st, L.M, irp, p->JA, p->AS, e, z, stop);
             ++n;
         } else {                                               // (d is free: the restriction consumed it)
             if (spmv(&L.P, e, L.d)) return EXIT_FAILURE;
@@ -900,9 +913,15 @@ int enqueueAmgCycleBlock(const DevMat* m, const DevMat* a0, uint32_t k, const De
         launchBlockVec(rows, k, nullptr, op, nullptr, nullptr, st);
         ++n;
     };
+    const bool f32 = H->storage == SPMV_STORAGE_F32;
     auto spmm = [&](const DevMat* h, const BMat& x, const BMat& y) {
         ++n;
-        return h->M ? enqueueSpmm(h, k, dense(x), dense(y), st) : EXIT_SUCCESS;
+        if (f32 && !h->f32) {
+            fprintf(stderr, "libspmvhip: multigrid block cycle: the hierarchy is stored in single precision, but a level's handle has lost its "
+                            "single-precision value form: spmvHipValuesF32 on dA, or spmvHipAmgSetStorage again\n");
+            return EXIT_FAILURE;
+        }
+        return h->M ? enqueueSpmm(h, k, dense(x), dense(y), st, f32) : EXIT_SUCCESS;
     };
     auto matAt = [&](size_t l) { return l ? matOf(&H->lv[l].A) : a0; };
     const bool cheb = H->smoother == SPMV_AMG_SMOOTHER_CHEBYSHEV;
@@ -986,6 +1005,67 @@ int amgSetBlockWidth(DevMat* m, uint32_t width, hipStream_t st) {
     return EXIT_SUCCESS;
 }
 
+// The hierarchy's products from single-precision storage (contract in spmvHip.h, design in DESIGN.md section 41).  F32: the form
+// on the caller's level-0 handle, on every A_l below it and on every R_l and P_l, all or none -- a refused allocation releases
+// what this call built.  F64: those forms released (the level-0 form only if this hierarchy built it).  Refused on a hierarchy
+// with a Gauss-Seidel level: its sweeps read AS in kernels of their own.  Synchronous.
+int amgSetStorage(DevMat* m, spmat* hA, int storage, hipStream_t st) {
+    AmgHierarchy* H = m->amg;
+    const size_t nl = H->lv.size();
+    const char* who = "spmvHipAmgSetStorage";
+    DevMat* a0 = matOf(hA);
+    std::vector<DevMat*> own;                                  // the hierarchy's own handles that a product of the cycle streams
+    for (size_t l = 0; l < nl; ++l) {
+        if (l) own.push_back(matOf(&H->lv[l].A));
+        if (l + 1 < nl) { own.push_back(matOf(&H->lv[l].R)); own.push_back(matOf(&H->lv[l].P)); }
+    }
+    if (storage == SPMV_STORAGE_F64) {
+        for (DevMat* d : own) valuesF32Drop(d);
+        if (H->a0Form) valuesF32Drop(a0);
+        H->a0Form = false; H->a0Bytes = 0;
+        H->storage = SPMV_STORAGE_F64;
+        return EXIT_SUCCESS;
+    }
+    for (const AmgLevel& L : H->lv)
+        if (L.perm) {
+            fprintf(stderr, "libspmvhip: %s: the hierarchy has a Gauss-Seidel level, whose sweeps read the double values in kernels of their own: "
+                            "spmvHipAmgSetSmoother with JACOBI or CHEBYSHEV first\n", who);
+            return EXIT_FAILURE;
+        }
+    const bool hadA0 = a0->f32;
+    std::vector<DevMat*> built;
+    bool ok = valuesF32Set(a0, 1, st, who) == EXIT_SUCCESS;
+    if (ok && !hadA0) built.push_back(a0);
+    for (size_t i = 0; ok && i < own.size(); ++i) {
+        const bool had = own[i]->f32;
+        ok = valuesF32Set(own[i], 1, st, who) == EXIT_SUCCESS;
+        if (ok && !had) built.push_back(own[i]);
+    }
+    if (!ok) {
+        for (DevMat* d : built) valuesF32Drop(d);
+        fprintf(stderr, "libspmvhip: %s: building the single-precision forms failed: the hierarchy keeps its storage\n", who);
+        return EXIT_FAILURE;
+    }
+    H->a0Form = H->a0Form || !hadA0;
+    H->a0Bytes = a0->f32Info.bytes;
+    H->storage = SPMV_STORAGE_F32;
+    return EXIT_SUCCESS;
+}
+
+void amgStorage(const DevMat* m, spmvAmgStorageInfo* info) {
+    const AmgHierarchy* H = m->amg;
+    const size_t nl = H->lv.size();
+    uint64_t bytes = 0;
+    if (H->storage == SPMV_STORAGE_F32) {
+        bytes = H->a0Bytes;
+        for (size_t l = 0; l < nl; ++l) {
+            if (l) bytes += static_cast<const DevMat*>(H->lv[l].A.dev)->f32Info.bytes;
+            if (l + 1 < nl) bytes += static_cast<const DevMat*>(H->lv[l].R.dev)->f32Info.bytes + static_cast<const DevMat*>(H->lv[l].P.dev)->f32Info.bytes;
+        }
+    }
+    *info = spmvAmgStorageInfo{H->storage, (unsigned)nl, (ulong)bytes};
+}
+
 void amgBlockState(const DevMat* m, uint32_t* width, uint64_t* bytes, bool* gaussSeidel) {
     const AmgHierarchy* H = m->amg;
     *width = H->blockWidth;
@@ -1061,6 +1141,11 @@ int amgSetGaussSeidel(DevMat* m, spmat* hA, const spmvAmgGsOpts* o, uint32_t sma
     const uint32_t seed = o ? o->seed : 0u;
     const size_t gsLevels = o && o->levels ? std::min<size_t>(o->levels, nl) : nl;
     auto fail = [&](const char* what) { return buildFail(st, "multigrid smoother", what); };
+    if (H->storage == SPMV_STORAGE_F32) {                      // the colour sweeps read AS in kernels of their own (section 41)
+        fprintf(stderr, "libspmvhip: spmvHipAmgSetGaussSeidel: the hierarchy is stored in single precision, which the Gauss-Seidel sweeps "
+                        "do not read: spmvHipAmgSetStorage(dM, dA, SPMV_STORAGE_F64) first\n");
+        return EXIT_FAILURE;
+    }
     // everything new is made first: a refusal leaves the hierarchy as it was
     struct Lists { TempBuf perm, ptr; std::vector<uint32_t> h; uint64_t maxRows = 0, longRows = 0; };
     std::vector<Lists> nw(gsLevels);

@@ -140,6 +140,13 @@ struct DevMat {
     // writes: spmvHipUpdateValues / ValuesChanged (updateValues) and the refreshes of a derived handle (upload.hip).
     bool      iluPending = false;
     spmvIluInfo ilu{-1, -1, 0, 0, 0, 0, 0.0};
+    // the single-precision form of the values (spmvHipValuesF32, values_f32.hip): AS32[p] = (float)AS[p] for the NZ entries,
+    // with the 32 bytes of the demotion's counters behind them in the same allocation; a unit handle has no array, only
+    // its register value rounded the same way.  It follows AS through updateValues like the formats above.
+    bool      f32 = false;          // the form is built (a unit handle: without an array)
+    float*    AS32 = nullptr;
+    double    unitValue32 = 0.0;    // (double)(float)unitValue
+    spmvF32Info f32Info{0, 0, 0, 0, 0, 0, 0, -1};
 };
 
 // What the sweep solves keep: the diagonal's places, what the pattern pass found, two M x width iterates
@@ -159,6 +166,7 @@ struct TriSweepPlan {
 // What a factor G of spmvHipFsaiSetup owns privately: G^T (made and refreshed by the transpose path, with a handle of its own
 // for the launchers), a handle over G itself for them, one M-vector for G r, the forced group width and the last report.
 struct FsaiPlan {
+    int      storage = 0;           // SPMV_STORAGE_F64 | SPMV_STORAGE_F32 (spmvHipFsaiSetStorage): which products an apply takes
     DevMat*  gt = nullptr;
     spmat    hG{}, hGT{};
     double*  work = nullptr;
@@ -343,6 +351,8 @@ int  amgSetBlockWidth(DevMat* m, uint32_t width, hipStream_t stream);
 void amgBlockState(const DevMat* m, uint32_t* width, uint64_t* bytes, bool* gaussSeidel);
 int  enqueueAmgCycleBlock(const DevMat* m, const DevMat* a0, uint32_t k, const Dense& R, const Dense& Z, hipStream_t stream,
                           const uint32_t* stop, unsigned long* launches);
+int  amgSetStorage(DevMat* m, spmat* hA, int storage, hipStream_t stream);      // section 41: the cycle's products from f32 forms
+void amgStorage(const DevMat* m, spmvAmgStorageInfo* info);
 const spmvAmgInfo* amgInfo(const DevMat* m);
 void amgLevel(const DevMat* m, unsigned level, spmat* dAl, const uint32_t** dAgg, const double** dDinv);
 void amgProlongator(const DevMat* m, unsigned level, spmat* dPl, spmat* dRl, double* omegaP);
@@ -426,7 +436,16 @@ int  enqueueSellValues(uint32_t nSlices, const uint64_t* sliceOff, const uint32_
 int  updateValues(spmat* h, const double* AS, bool onDevice, bool reread, hipStream_t stream, const char* who);   // upload.hip
 // Y = A X for k columns, X of N rows and Y of M (spmm.hip): one launch per panel of at
 // most 16 columns on `stream`, no allocation; the caller has checked handle, pointers and extents
-int  enqueueSpmm(const DevMat* d, uint32_t k, const Dense& X, const Dense& Y, hipStream_t stream);
+int  enqueueSpmm(const DevMat* d, uint32_t k, const Dense& X, const Dense& Y, hipStream_t stream, bool f32 = false);
+// The single-precision value form of a CSR handle (values_f32.hip; contract in spmvHip.h, design in DESIGN.md section 41).
+// valuesF32Set: build (on) or release the form of the checked CSR handle; synchronous on `stream`; a failed build leaves no
+// form.  valuesF32Follow: what updateValues calls after the unit detection when the form is built -- the new roundings at the
+// same address, the array made or freed on a unit transition; a failure has written its line and left the form not built.
+// valuesF32Drop: the form given back (the values it followed are gone).
+int  valuesF32Set(DevMat* d, int on, hipStream_t stream, const char* who);
+int  valuesF32Follow(DevMat* d, hipStream_t stream, const char* who);
+void valuesF32Drop(DevMat* d);
+bool liveShard(const void* p);                                  // shard.hip: p is a live handle of spmvHipShardCSR
 constexpr uint32_t VMAP_NONE = 0xFFFFFFFFu;                    // map entry of a padding cell (value 0.0); nnz < 2^32 - 65536
 
 // Fold `blocks` workgroups into an (x, y) grid whose x extent keeps

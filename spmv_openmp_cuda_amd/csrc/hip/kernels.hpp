@@ -33,10 +33,12 @@ __device__ __forceinline__ T stream_load(const T* p) {
     return __builtin_nontemporal_load(p);          // (plain loads: equal or slower everywhere, c2 one-pass 0.345 vs 0.320 ms)
 }
 
-// value j of a matrix: from the stream, or -- UNIT: every stored value is the same double -- from a register
-template <bool UNIT>
-__device__ __forceinline__ double value_at(const double* __restrict__ AS, uint64_t j, double unitValue) {
-    return UNIT ? unitValue : stream_load(AS + j);
+// value j of a matrix: from the stream, or -- UNIT: every stored value is the same double -- from a register.  V is the type
+// the stream is stored in: double, or float for the single-precision form of a handle (AS32), whose
+// entries are widened -- exactly -- before the product; everything after the load is the same code for both.
+template <bool UNIT, typename V>
+__device__ __forceinline__ double value_at(const V* __restrict__ AS, uint64_t j, double unitValue) {
+    return UNIT ? unitValue : (double)stream_load(AS + j);
 }
 
 // sum over the 64 lanes of a wavefront; result valid in lane 0
@@ -129,11 +131,11 @@ __device__ __forceinline__ uint64_t stream2_block(uint64_t blk, uint32_t nBlk, u
     return nLong + xcd * a + (xcd < rem ? xcd : rem) + q / 8;
 }
 
-template <typename I, bool SEQ, bool UNIT>
+template <typename I, bool SEQ, bool UNIT, typename V = double>
 __global__ __launch_bounds__(WG_THREADS) void csr_stream2_kernel(
     uint32_t nBlk, uint32_t nLong, const uint4* __restrict__ blkInfo, const uint64_t* __restrict__ blkBase,
     const I* __restrict__ IRP, const uint32_t* __restrict__ JA,
-    const double* __restrict__ AS, double unitValue, const double* __restrict__ x, double* __restrict__ y) {
+    const V* __restrict__ AS, double unitValue, const double* __restrict__ x, double* __restrict__ y) {
     __shared__ double   prod[STREAM_NNZ];
     __shared__ uint16_t rowOff[STREAM2_MAX_ROWS + 1];
     __shared__ double   wpart[WG_THREADS / WAVE];

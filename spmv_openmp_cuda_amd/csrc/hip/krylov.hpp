@@ -235,8 +235,9 @@ struct Precond {
         if (m->origin == Origin::HIERARCHY) return enqueueAmgCycle(m, hA, in, out, s, flag, launches);
         if (m->origin == Origin::FSAI) {                                 // (each handle's first call chooses its kernel, as hA's does)
             FsaiPlan* const p = m->fsai;
-            if (spmvHipEnqueueAutoRows(&p->hG, const_cast<double*>(in), p->work, s)) return EXIT_FAILURE;
-            if (spmvHipEnqueueAutoRows(&p->hGT, p->work, out, s)) return EXIT_FAILURE;
+            const auto product = p->storage == SPMV_STORAGE_F32 ? spmvHipEnqueueRowsF32 : spmvHipEnqueueAutoRows;    // (stored in single precision: the f32 products)
+            if (product(&p->hG, const_cast<double*>(in), p->work, s)) return EXIT_FAILURE;
+            if (product(&p->hGT, p->work, out, s)) return EXIT_FAILURE;
             *launches += 2;
             return EXIT_SUCCESS;
         }

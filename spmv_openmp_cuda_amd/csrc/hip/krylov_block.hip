@@ -245,7 +245,13 @@ struct BlockWidth {
     int precond(const Vec& in, const Vec& outv) {                        // z = U^-1 (L^-1 in), or one cycle: every launch behind the head word
         if (cycle) return enqueueAmgCycleBlock(m, a, k, dense(in), dense(outv), s, &head->allStop, &out.launches);
         if (fsai) {                                                      // two SpMM passes, which run whatever the head word says
-            if (enqueueSpmm(m, k, dense(in), dense(gw), s) || enqueueSpmm(m->fsai->gt, k, dense(gw), dense(outv), s)) return EXIT_FAILURE;
+            const bool f32 = m->fsai->storage == SPMV_STORAGE_F32;        // (stored in single precision: the f32 passes)
+            if (f32 && !(m->f32 && m->fsai->gt->f32)) {
+                fprintf(stderr, "libspmvhip: block Krylov solve: dM is an approximate-inverse factor stored in single precision, but its "
+                                "single-precision value forms are not built: spmvHipFsaiSetStorage(dM, SPMV_STORAGE_F32) again\n");
+                return EXIT_FAILURE;
+            }
+            if (enqueueSpmm(m, k, dense(in), dense(gw), s, f32) || enqueueSpmm(m->fsai->gt, k, dense(gw), dense(outv), s, f32)) return EXIT_FAILURE;
             out.launches += 2;
             return EXIT_SUCCESS;
         }

@@ -30,6 +30,42 @@ void launchStream2(hipStream_t stream, DevMat* d, double* x, double* y) {
     });
 }
 
+// ... from the handle's single-precision form (built: the caller has checked): the V = float instance on AS32, or -- a unit
+// handle -- the UNIT instance with the register value rounded to single precision
+template <bool SEQ>
+void launchStream2F32(hipStream_t stream, DevMat* d, double* x, double* y) {
+    withIrp(d, [&](auto irp) {
+        using I = IrpT<decltype(irp)>;
+        const dim3 grid = grid2d(d->nBlk2, WG_THREADS), block(WG_THREADS);
+        if (d->unit)
+            hipLaunchKernelGGL((csr_stream2_kernel<I, SEQ, true>), grid, block, 0, stream, d->nBlk2, d->nLong2, d->blkInfo, d->blkBase, irp, d->JA,
+                               d->AS, d->unitValue32, x, y);
+        else
+            hipLaunchKernelGGL((csr_stream2_kernel<I, SEQ, false, float>), grid, block, 0, stream, d->nBlk2, d->nLong2, d->blkInfo, d->blkBase, irp,
+                               d->JA, d->AS32, 0.0, x, y);
+    });
+}
+
+// the checked CSR handle of an f32 launcher: its single-precision form must be built (a launcher never allocates)
+DevMat* f32Of(spmat* dMat, const double* dX, const double* dY, const char* who) {
+    DevMat* d = csrOf(dMat, dX, dY, who, "handle is not CSR (only CSR handles have a single-precision value form)");
+    if (d && !d->f32) {
+        ERR("%s: the handle's single-precision value form is not built: call spmvHipValuesF32(dMat, 1) first", who);
+        return nullptr;
+    }
+    return d;
+}
+
+int streamCSRf32(Ctx cx, spmat* dMat, double* dX, double* dY, bool seq) {
+    const char* who = seq ? "hipSpMVRowsCSRf32" : "hipSpMVWarpPerRowCSRf32";
+    DevMat* d = f32Of(dMat, dX, dY, who);
+    if (!d) return EXIT_FAILURE;
+    if (d->M == 0) return nothingToLaunch(cx, d, nullptr);
+    Launch L(cx, grid2d(d->nBlk2, WG_THREADS), dim3(WG_THREADS));
+    (seq ? launchStream2F32<true> : launchStream2F32<false>)(cx.stream, d, dX, dY);
+    return L.finish(who);
+}
+
 // row-major ELL through the LDS-stream kernel (a row must fit a block): seq = one thread sums a row in ascending slots
 int launchEllStream(Ctx cx, DevMat* d, bool rl, bool seq, double* x, double* y, const char* who) {
     const uint32_t rowsPerBlk = std::min<uint32_t>((uint32_t)(STREAM_NNZ / d->pitch), WG_THREADS);
@@ -213,11 +249,22 @@ int spmvHipEnqueueCSR(spmat* dMat, int warpPerRow, double* dX, double* dY, void*
     return EXIT_SUCCESS;
 }
 
-// ---- blocks of vectors: Y = A X (contract in spmvHip.h, design in DESIGN.md section 15)
-int hipSpMMRowsCSR(spmat* dMat, unsigned k, const double* dX, size_t ldx, int xLayout, double* dY, size_t ldy, int yLayout) {
-    const char* who = "hipSpMMRowsCSR";
+// ---- the products from single-precision storage (contract in spmvHip.h, design in DESIGN.md section 41): the LDS-stream kernel only
+int hipSpMVRowsCSRf32(spmat* dMat, double* dX, CONFIG, double* dY) { return streamCSRf32(libraryCtx(), dMat, dX, dY, true); }
+int hipSpMVWarpPerRowCSRf32(spmat* dMat, double* dX, CONFIG, double* dY) { return streamCSRf32(libraryCtx(), dMat, dX, dY, false); }
+int spmvHipEnqueueRowsF32(spmat* dMat, double* dX, double* dY, void* stream) {
+    DevMat* d = f32Of(dMat, dX, dY, "spmvHipEnqueueRowsF32");
+    if (!d) return EXIT_FAILURE;
+    if (d->M == 0) return EXIT_SUCCESS;
+    launchStream2F32<true>(static_cast<hipStream_t>(stream), d, dX, dY);
+    HIP_TRY(hipGetLastError());
+    return EXIT_SUCCESS;
+}
+
+// ---- blocks of vectors: Y = A X (contract in spmvHip.h, design in DESIGN.md section 15); f32: from the single-precision form
+static int spmmRows(const char* who, bool f32, spmat* dMat, unsigned k, const double* dX, size_t ldx, int xLayout, double* dY, size_t ldy, int yLayout) {
     const Ctx cx = libraryCtx();
-    DevMat* d = csrOf(dMat, dX, dY, who, "handle is not CSR (ELL handles are not supported)");
+    DevMat* d = f32 ? f32Of(dMat, dX, dY, who) : csrOf(dMat, dX, dY, who, "handle is not CSR (ELL handles are not supported)");
     if (!d) return EXIT_FAILURE;
     if (k == 0) { ERR("%s: k = 0 columns", who); return EXIT_FAILURE; }
     Dense X, Y;                                                          // X has N rows, Y has M
@@ -225,9 +272,15 @@ int hipSpMMRowsCSR(spmat* dMat, unsigned k, const double* dX, size_t ldx, int xL
     if (denseShare(k, d->N, X, d->M, Y)) { ERR("%s: X and Y overlap", who); return EXIT_FAILURE; }
     if (d->M == 0) return nothingToLaunch(cx, d, nullptr);
     Launch L(cx, grid2d(d->nBlk2, WG_THREADS), dim3(WG_THREADS));
-    if (k == 1 && X.sr() == 1 && Y.sr() == 1) launchStream2<true>(cx.stream, d, X.p, dY);     // one plain vector: the SpMV kernel
-    else if (enqueueSpmm(d, k, X, Y, cx.stream)) { ERR("%s: launch failed", who); return EXIT_FAILURE; }
+    if (k == 1 && X.sr() == 1 && Y.sr() == 1) (f32 ? launchStream2F32<true> : launchStream2<true>)(cx.stream, d, X.p, dY);     // one plain vector: the SpMV kernel
+    else if (enqueueSpmm(d, k, X, Y, cx.stream, f32)) { ERR("%s: launch failed", who); return EXIT_FAILURE; }
     return L.finish(who);
+}
+int hipSpMMRowsCSR(spmat* dMat, unsigned k, const double* dX, size_t ldx, int xLayout, double* dY, size_t ldy, int yLayout) {
+    return spmmRows("hipSpMMRowsCSR", false, dMat, k, dX, ldx, xLayout, dY, ldy, yLayout);
+}
+int hipSpMMRowsCSRf32(spmat* dMat, unsigned k, const double* dX, size_t ldx, int xLayout, double* dY, size_t ldy, int yLayout) {
+    return spmmRows("hipSpMMRowsCSRf32", true, dMat, k, dX, ldx, xLayout, dY, ldy, yLayout);
 }
 
 // explicit launchers and queries work on the form last asked for with spmvHipBuild*Opt (default: arrival order)

@@ -129,6 +129,11 @@ int shardStep(Shard* sh, const double* hX, int mode, bool timed) {
 
 }  // namespace
 
+namespace spmvhip {
+// p is a live shard handle (spmvHipShardCSR): what an entry point that takes an spmat* asks before it reads one (values_f32.hip)
+bool liveShard(const void* p) { return g_liveShards.count(static_cast<const Shard*>(p)) != 0; }
+}  // namespace spmvhip
+
 extern "C" {
 
 int spmvHipShardFree(void* handle) {

@@ -378,6 +378,27 @@ int spmvHipAmgApplyBlock(spmat* dM, spmat* dA, unsigned k, const double* dR, siz
     return L.finish(who);
 }
 
+// ---- the hierarchy stored in single precision (contract in spmvHip.h, design in DESIGN.md section 41)
+int spmvHipAmgSetStorage(spmat* dM, spmat* dA, int storage) {
+    const char* who = "spmvHipAmgSetStorage";
+    DevMat* a = nullptr;
+    DevMat* m = hierarchyOf(dM, dA, who, &a);
+    if (!m) return EXIT_FAILURE;
+    if (storage != SPMV_STORAGE_F64 && storage != SPMV_STORAGE_F32) {
+        ERR("%s: storage %d is neither SPMV_STORAGE_F64 nor SPMV_STORAGE_F32", who, storage);
+        return EXIT_FAILURE;
+    }
+    if (amgSetStorage(m, dA, storage, S.stream)) { ERR("%s: the storage was not set", who); return EXIT_FAILURE; }
+    return EXIT_SUCCESS;
+}
+
+int spmvHipAmgStorage(spmat* dM, spmvAmgStorageInfo* info) {
+    DevMat* m = hierarchyLevel(dM, "spmvHipAmgStorage", 0, nullptr, !info);
+    if (!m) return EXIT_FAILURE;
+    amgStorage(m, info);
+    return EXIT_SUCCESS;
+}
+
 int spmvHipAmgInfo(spmat* dM, spmvAmgInfo* info) {
     DevMat* m = hierarchyLevel(dM, "spmvHipAmgInfo", 0, nullptr, !info);
     if (!m) return EXIT_FAILURE;

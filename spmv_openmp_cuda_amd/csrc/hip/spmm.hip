@@ -27,10 +27,12 @@ constexpr uint32_t SPMM_PANEL = 16;               // columns per panel: the matr
 constexpr uint32_t SPMM_AHEAD = 8;                // gathers in flight per lane on a short row
 constexpr int      SPMM_LONG_PER = STREAM_NNZ / WG_THREADS;   // products per lane and long-row chunk (8: 16 KiB in all)
 
-template <typename I, int P, bool UNIT>
+// V: the type the value stream is stored in (double, or float for the handle's single-precision form, widened at the load:
+// the LDS copy of the span and everything after it are the same for both)
+template <typename I, int P, bool UNIT, typename V = double>
 __global__ __launch_bounds__(WG_THREADS) void csr_spmm_kernel(
     uint32_t nBlk, uint32_t nLong, const uint4* __restrict__ blkInfo, const uint64_t* __restrict__ blkBase,
-    const I* __restrict__ IRP, const uint32_t* __restrict__ JA, const double* __restrict__ AS, double unitValue,
+    const I* __restrict__ IRP, const uint32_t* __restrict__ JA, const V* __restrict__ AS, double unitValue,
     uint32_t w, const double* __restrict__ X, uint64_t sxr, uint64_t sxc, double* __restrict__ Y, uint64_t syr, uint64_t syc) {
     static_assert(P >= 1 && P <= (int)SPMM_PANEL && (P & (P - 1)) == 0 && WG_THREADS % P == 0, "panel width");
     // short-row blocks: AS span in [0, STREAM_NNZ), the JA span as u32 behind it; long rows: the products of a chunk
@@ -90,7 +92,7 @@ __global__ __launch_bounds__(WG_THREADS) void csr_spmm_kernel(
         for (int u = 0; u < STREAM_UNROLL; ++u) {
             const uint32_t k = tid + u * WG_THREADS;
             col[u] = k < n ? stream_load(JA + base + k) : 0u;
-            if (!UNIT) val[u] = k < n ? stream_load(AS + base + k) : 0.0;
+            if (!UNIT) val[u] = k < n ? (double)stream_load(AS + base + k) : 0.0;
         }
         uint32_t rp0 = 0, rp1 = 0;
         if (tid < R) rp0 = (uint32_t)((uint64_t)IRP[r0 + tid] - base);
@@ -130,37 +132,40 @@ __global__ __launch_bounds__(WG_THREADS) void csr_spmm_kernel(
     }
 }
 
-template <int P, bool UNIT>
-void launchPanel(const DevMat* d, uint32_t w, const double* X, uint64_t sxr, uint64_t sxc, double* Y, uint64_t syr,
-                 uint64_t syc, hipStream_t stream) {
+// AS / unitValue: the handle's double stream and unit value, or those of its single-precision form
+template <int P, bool UNIT, typename V>
+void launchPanel(const DevMat* d, const V* AS, double unitValue, uint32_t w, const double* X, uint64_t sxr, uint64_t sxc, double* Y,
+                 uint64_t syr, uint64_t syc, hipStream_t stream) {
     const dim3 grid = grid2d(d->nBlk2, WG_THREADS), block(WG_THREADS);
     withIrp(d, [&](auto irp) {
-        hipLaunchKernelGGL((csr_spmm_kernel<IrpT<decltype(irp)>, P, UNIT>), grid, block, 0, stream, d->nBlk2, d->nLong2, d->blkInfo,
-                           d->blkBase, irp, d->JA, d->AS, d->unitValue, w, X, sxr, sxc, Y, syr, syc);
+        hipLaunchKernelGGL((csr_spmm_kernel<IrpT<decltype(irp)>, P, UNIT, V>), grid, block, 0, stream, d->nBlk2, d->nLong2, d->blkInfo,
+                           d->blkBase, irp, d->JA, AS, unitValue, w, X, sxr, sxc, Y, syr, syc);
     });
 }
 
-template <bool UNIT>
-void launchPanelP(const DevMat* d, uint32_t w, const double* X, uint64_t sxr, uint64_t sxc, double* Y, uint64_t syr,
-                  uint64_t syc, hipStream_t stream) {
-    if (w == 1)      launchPanel<1, UNIT>(d, w, X, sxr, sxc, Y, syr, syc, stream);
-    else if (w == 2) launchPanel<2, UNIT>(d, w, X, sxr, sxc, Y, syr, syc, stream);
-    else if (w <= 4) launchPanel<4, UNIT>(d, w, X, sxr, sxc, Y, syr, syc, stream);
-    else if (w <= 8) launchPanel<8, UNIT>(d, w, X, sxr, sxc, Y, syr, syc, stream);
-    else             launchPanel<16, UNIT>(d, w, X, sxr, sxc, Y, syr, syc, stream);
+template <bool UNIT, typename V>
+void launchPanelP(const DevMat* d, const V* AS, double unitValue, uint32_t w, const double* X, uint64_t sxr, uint64_t sxc, double* Y,
+                  uint64_t syr, uint64_t syc, hipStream_t stream) {
+    if (w == 1)      launchPanel<1, UNIT>(d, AS, unitValue, w, X, sxr, sxc, Y, syr, syc, stream);
+    else if (w == 2) launchPanel<2, UNIT>(d, AS, unitValue, w, X, sxr, sxc, Y, syr, syc, stream);
+    else if (w <= 4) launchPanel<4, UNIT>(d, AS, unitValue, w, X, sxr, sxc, Y, syr, syc, stream);
+    else if (w <= 8) launchPanel<8, UNIT>(d, AS, unitValue, w, X, sxr, sxc, Y, syr, syc, stream);
+    else             launchPanel<16, UNIT>(d, AS, unitValue, w, X, sxr, sxc, Y, syr, syc, stream);
 }
 
 }  // namespace
 
-// one launch per panel of at most 16 columns, in column order, on `stream`; the caller has checked the arguments
-int enqueueSpmm(const DevMat* d, uint32_t k, const Dense& X, const Dense& Y, hipStream_t stream) {
+// one launch per panel of at most 16 columns, in column order, on `stream`; the caller has checked the arguments (f32: and
+// that the handle's single-precision form is built, which then is what the panels stream)
+int enqueueSpmm(const DevMat* d, uint32_t k, const Dense& X, const Dense& Y, hipStream_t stream, bool f32) {
     const uint64_t sxr = X.sr(), sxc = X.sc(), syr = Y.sr(), syc = Y.sc();
     for (uint32_t c0 = 0; c0 < k; c0 += SPMM_PANEL) {
         const uint32_t w = k - c0 < SPMM_PANEL ? k - c0 : SPMM_PANEL;
         const double* Xp = X.p + (uint64_t)c0 * sxc;
         double* Yp = Y.p + (uint64_t)c0 * syc;
-        if (d->unit) launchPanelP<true>(d, w, Xp, sxr, sxc, Yp, syr, syc, stream);
-        else         launchPanelP<false>(d, w, Xp, sxr, sxc, Yp, syr, syc, stream);
+        if (d->unit)  launchPanelP<true>(d, d->AS, f32 ? d->unitValue32 : d->unitValue, w, Xp, sxr, sxc, Yp, syr, syc, stream);
+        else if (f32) launchPanelP<false>(d, d->AS32, 0.0, w, Xp, sxr, sxc, Yp, syr, syc, stream);
+        else          launchPanelP<false>(d, d->AS, d->unitValue, w, Xp, sxr, sxc, Yp, syr, syc, stream);
     }
     HIP_TRY(hipGetLastError());
     return EXIT_SUCCESS;

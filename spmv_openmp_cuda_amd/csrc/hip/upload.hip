@@ -65,7 +65,7 @@ void freeDesc(DevMat* d) {
     if (d->owns) {
         (void)devFree(d->IRP); (void)devFree(d->JA); (void)devFree(d->AS); (void)devFree(d->RL);
     }
-    (void)devFree(d->blkInfo); (void)devFree(d->blkBase); (void)devFree(d->tmap);
+    (void)devFree(d->blkInfo); (void)devFree(d->blkBase); (void)devFree(d->tmap); (void)devFree(d->AS32);
     freeTri(d->tri[0]); freeTri(d->tri[1]);
     freeTriSweeps(d->sweep);
     freeSpgemmPlan(d->prod);
@@ -246,12 +246,16 @@ int updateValues(spmat* h, const double* AS, bool onDevice, bool reread, hipStre
     const auto t0 = std::chrono::steady_clock::now();
     d->iluPending = false;                              // whatever the values were, they are being replaced or reread
     spmvUpdateInfo info{};
+    bool f32Failed = false;
     info.unitBefore = d->unit;
     const double valueBefore = d->unitValue;
     const hipMemcpyKind kind = onDevice ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     if (d->kind == Kind::CSR) {
         if (!reread && d->NZ) HIP_TRY(hipMemcpyAsync(d->AS, AS, d->NZ * sizeof(double), kind, st));
-        if (detectUnit(d, st)) return EXIT_FAILURE;
+        if (detectUnit(d, st)) { valuesF32Drop(d); return EXIT_FAILURE; }      // (a form that cannot follow the values is given back)
+        // the single-precision form first: whatever becomes of the formats below, it holds the new roundings or is gone.  Its
+        // failure (the array of a unit -> non-unit update refused) fails the call at its end, with the f64 side complete.
+        f32Failed = d->f32 && valuesF32Follow(d, st, who) != EXIT_SUCCESS;
         // every built format, both forms.  When the values were unit before and are unit now no kernel reads a value array
         // (SELL has no unit kernel): only the value in the registers changes.  A stripes format built for a unit matrix has
         // no value array: it is rebuilt, with its recorded options, when the values stop being unit.
@@ -289,7 +293,7 @@ int updateValues(spmat* h, const double* AS, bool onDevice, bool reread, hipStre
     info.inPlace = !info.rebuilt && (!info.unitBefore || sameUnit);
     info.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     d->lastUpdate = info;
-    return EXIT_SUCCESS;
+    return f32Failed ? EXIT_FAILURE : EXIT_SUCCESS;
 }
 
 // The tail of every CSR handle whose arrays (4-byte row pointers) were made on the device: the row pointers come back to
@@ -786,14 +790,27 @@ int spmvHipFsaiRefresh(spmat* dG, spmat* dA, spmvFsaiInfo* info) {
     out.launches = 0;
     g->iluPending = false;                              // AS is rewritten from here on, whatever becomes of the call
     if (fsaiValues(a, g, p->lanes, (uint32_t)p->info.maxRow, &out, S.stream)) { ERR("%s: recomputing the values failed", who); return EXIT_FAILURE; }
-    if (updateValues(dG, nullptr, true, true, S.stream, who)) return EXIT_FAILURE;
+    // A factor stored in single precision: an update that fails only because a form could not follow (the array of a unit ->
+    // non-unit transition refused) has left the doubles complete.  The refresh then goes on, so that G and G^T both hold the
+    // new values, and the factor falls back to double storage as a whole; the call still fails, and says so.
+    const bool wasF32 = p->storage == SPMV_STORAGE_F32;
+    if (updateValues(dG, nullptr, true, true, S.stream, who) && !(wasF32 && !g->f32)) return EXIT_FAILURE;
     p->gt->iluPending = false;
     if (enqueueGatherValues(p->gt->AS, p->gt->tmap, p->gt->NZ, g->AS, S.stream)) return EXIT_FAILURE;
-    if (updateValues(&p->hGT, nullptr, true, true, S.stream, who)) return EXIT_FAILURE;
+    if (updateValues(&p->hGT, nullptr, true, true, S.stream, who) && !(wasF32 && !p->gt->f32)) return EXIT_FAILURE;
+    const bool lostF32 = wasF32 && !(g->f32 && p->gt->f32);
+    if (lostF32) {
+        valuesF32Drop(g);
+        valuesF32Drop(p->gt);
+        p->storage = SPMV_STORAGE_F64;
+        ERR("%s: G and G^T hold the new values, but a single-precision form could not follow them: the factor is applied from its double "
+            "values now (spmvHipFsaiSetStorage sets F32 again)", who);
+    }
     ++out.launches;
     ++out.setups;
     out.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     p->info = out;
+    if (lostF32) return EXIT_FAILURE;
     if (info) *info = out;
     return EXIT_SUCCESS;
 }
@@ -809,7 +826,12 @@ int spmvHipFsaiApply(spmat* dG, const double* dR, double* dZ) {
     FsaiPlan* p = g->fsai;
     Launch L(cx, grid2d(g->nBlk2, WG_THREADS), dim3(WG_THREADS));
     const Ctx enqueue{cx.stream, false};                // w = G r, z = G^T w: the serial-order selection of each handle
-    if (autoRun(enqueue, &p->hG, const_cast<double*>(dR), p->work, 1, who) || autoRun(enqueue, &p->hGT, p->work, dZ, 1, who)) {
+    if (p->storage == SPMV_STORAGE_F32) {               // ... or, stored in single precision, the f32 product of each
+        if (spmvHipEnqueueRowsF32(&p->hG, const_cast<double*>(dR), p->work, cx.stream) || spmvHipEnqueueRowsF32(&p->hGT, p->work, dZ, cx.stream)) {
+            ERR("%s: launch failed", who);
+            return EXIT_FAILURE;
+        }
+    } else if (autoRun(enqueue, &p->hG, const_cast<double*>(dR), p->work, 1, who) || autoRun(enqueue, &p->hGT, p->work, dZ, 1, who)) {
         ERR("%s: launch failed", who);
         return EXIT_FAILURE;
     }
@@ -833,6 +855,37 @@ int spmvHipFsaiInfo(spmat* dG, spmvFsaiInfo* info) {
     if (!g) return EXIT_FAILURE;
     if (!info) { ERR("%s: info is NULL", who); return EXIT_FAILURE; }
     *info = g->fsai->info;
+    return EXIT_SUCCESS;
+}
+
+// the factor's products from single-precision storage (contract in spmvHip.h, design in DESIGN.md section 41): the form on G and
+// on G^T, both or neither
+int spmvHipFsaiSetStorage(spmat* dG, int storage) {
+    const char* who = "spmvHipFsaiSetStorage";
+    DevMat* g = fsaiOf(dG, who);
+    if (!g) return EXIT_FAILURE;
+    if (storage != SPMV_STORAGE_F64 && storage != SPMV_STORAGE_F32) {
+        ERR("%s: storage %d is neither SPMV_STORAGE_F64 nor SPMV_STORAGE_F32", who, storage);
+        return EXIT_FAILURE;
+    }
+    FsaiPlan* p = g->fsai;
+    const int on = storage == SPMV_STORAGE_F32;
+    if (valuesF32Set(g, on, S.stream, who) || valuesF32Set(p->gt, on, S.stream, who)) {
+        valuesF32Drop(g);                               // (only a build fails)
+        p->storage = SPMV_STORAGE_F64;
+        ERR("%s: building the single-precision forms failed: the factor is applied from its double values", who);
+        return EXIT_FAILURE;
+    }
+    p->storage = storage;
+    return EXIT_SUCCESS;
+}
+
+int spmvHipFsaiStorage(spmat* dG, int* storage) {
+    const char* who = "spmvHipFsaiStorage";
+    DevMat* g = fsaiOf(dG, who);
+    if (!g) return EXIT_FAILURE;
+    if (!storage) { ERR("%s: storage is NULL", who); return EXIT_FAILURE; }
+    *storage = g->fsai->storage;
     return EXIT_SUCCESS;
 }
 
