@@ -9,8 +9,8 @@ HIPCC    ?= hipcc
 CC        = gcc
 ARCH     ?= gfx950
 PKG       = spmv_openmp_cuda_amd
-HIPSRC    = $(PKG)/csrc/hip/abi.hip $(PKG)/csrc/hip/upload.hip $(PKG)/csrc/hip/launch.hip $(PKG)/csrc/hip/solve.hip $(PKG)/csrc/hip/select.hip $(PKG)/csrc/hip/hostcall.hip $(PKG)/csrc/hip/synth.hip $(PKG)/csrc/hip/shard.hip $(PKG)/csrc/hip/tiles.hip $(PKG)/csrc/hip/stripes.hip $(PKG)/csrc/hip/sell.hip $(PKG)/csrc/hip/peer.hip $(PKG)/csrc/hip/values.hip $(PKG)/csrc/hip/values_f32.hip $(PKG)/csrc/hip/spmm.hip $(PKG)/csrc/hip/transpose.hip $(PKG)/csrc/hip/trsv.hip $(PKG)/csrc/hip/trsm.hip $(PKG)/csrc/hip/trisweep.hip $(PKG)/csrc/hip/ilu0.hip $(PKG)/csrc/hip/fsai.hip $(PKG)/csrc/hip/krylov.hip $(PKG)/csrc/hip/krylov_block.hip $(PKG)/csrc/hip/gmres.hip $(PKG)/csrc/hip/lanczos.hip $(PKG)/csrc/hip/colour.hip $(PKG)/csrc/hip/rcm.hip $(PKG)/csrc/hip/spgemm.hip $(PKG)/csrc/hip/add.hip $(PKG)/csrc/hip/filter.hip $(PKG)/csrc/hip/coo.hip $(PKG)/csrc/hip/aggregate.hip $(PKG)/csrc/hip/amg.hip
-HIPHDR    = $(PKG)/csrc/hip/kernels.hpp $(PKG)/csrc/hip/device_mat.hpp $(PKG)/csrc/hip/lib.hpp $(PKG)/csrc/hip/krylov.hpp $(PKG)/csrc/hip/krylov_block.hpp $(PKG)/csrc/hip/orth.hpp $(PKG)/csrc/hip/device_prims.hpp $(PKG)/csrc/hip/alloc_ledger.hpp include/spmvHip.h include/spmv_types.h
+HIPSRC    = $(PKG)/csrc/hip/abi.hip $(PKG)/csrc/hip/upload.hip $(PKG)/csrc/hip/launch.hip $(PKG)/csrc/hip/solve.hip $(PKG)/csrc/hip/select.hip $(PKG)/csrc/hip/hostcall.hip $(PKG)/csrc/hip/synth.hip $(PKG)/csrc/hip/shard.hip $(PKG)/csrc/hip/tiles.hip $(PKG)/csrc/hip/stripes.hip $(PKG)/csrc/hip/sell.hip $(PKG)/csrc/hip/peer.hip $(PKG)/csrc/hip/values.hip $(PKG)/csrc/hip/values_f32.hip $(PKG)/csrc/hip/spmm.hip $(PKG)/csrc/hip/transpose.hip $(PKG)/csrc/hip/trsv.hip $(PKG)/csrc/hip/trsm.hip $(PKG)/csrc/hip/trisweep.hip $(PKG)/csrc/hip/ilu0.hip $(PKG)/csrc/hip/fsai.hip $(PKG)/csrc/hip/krylov.hip $(PKG)/csrc/hip/krylov_block.hip $(PKG)/csrc/hip/gmres.hip $(PKG)/csrc/hip/lanczos.hip $(PKG)/csrc/hip/davidson.hip $(PKG)/csrc/hip/colour.hip $(PKG)/csrc/hip/rcm.hip $(PKG)/csrc/hip/spgemm.hip $(PKG)/csrc/hip/add.hip $(PKG)/csrc/hip/filter.hip $(PKG)/csrc/hip/coo.hip $(PKG)/csrc/hip/aggregate.hip $(PKG)/csrc/hip/amg.hip
+HIPHDR    = $(PKG)/csrc/hip/kernels.hpp $(PKG)/csrc/hip/device_mat.hpp $(PKG)/csrc/hip/lib.hpp $(PKG)/csrc/hip/krylov.hpp $(PKG)/csrc/hip/krylov_block.hpp $(PKG)/csrc/hip/orth.hpp $(PKG)/csrc/hip/jacobi.hpp $(PKG)/csrc/hip/device_prims.hpp $(PKG)/csrc/hip/alloc_ledger.hpp include/spmvHip.h include/spmv_types.h
 HIPFLAGS  = --offload-arch=$(ARCH) -O3 -fPIC -shared -std=c++17 -ffp-contract=off -Wall -Wno-unused-function -Iinclude -ldl
 HOSTSRC   = $(wildcard $(PKG)/csrc/host/*.c)
 HOSTLIBSRC= $(filter-out %/main.c,$(HOSTSRC))

@@ -115,7 +115,8 @@ int spmvHipMemcpyDown(void* hDst, const void* dSrc, size_t bytes);
  *   spmvHipDot / MultiDot / BlockDot: the result is not written, the dot workspace keeps the size it had;
  *   hipSpCGCSR, hipSpBiCGStabCSR, hipSpGMRESCSR (every allocation comes before the loop): x and info are not written; a
  *     schedule that was made on dM stays there;
- *   hipSpLanczosCSR (every allocation comes before the loop): dX, theta, res and info are not written;
+ *   hipSpLanczosCSR, hipSpDavidsonCSR (every allocation comes before the loop): dX, theta, res and info are not written;
+ *   spmvHipBlockResidual: dR and dNorm2 are not written, the dot workspace keeps the size it had;
  *   spmvHipColourCSR, spmvHipAggregateCSR: info is not written, nothing is held; dColour / dPerm / dAgg may have been
  *     written in part and hold nothing to rely on;
  *   spmvHipAmgSetSmoother, spmvHipAmgSetGaussSeidel, spmvHipAmgSetBlockWidth: everything new is made before anything old
@@ -796,6 +797,120 @@ int spmvHipBlockCombine(size_t n, unsigned m, unsigned k, const double* dV, size
                         size_t ldy);
 int hipSpLanczosCSR(spmat* dA, const double* dV0, const spmvLanczosOpts* opts, double* dX, size_t ldx, double* theta, double* res,
                     spmvLanczosInfo* info);
+/* ------------------------------------------------------------- residual block, preconditioned eigensolver */
+/* spmvHipBlockResidual: R = W S - (V S) diag(theta) and the squared norms of R's columns in one pass, next to
+ * spmvHipBlockCombine and with its conventions: V and W are n x m, S is m x k, R is n x k, all column-major (V(i, j) at
+ * dV[j*ldv + i], W(i, j) at dW[j*ldw + i], S[j][c] at dS[c*lds + j], R(i, c) at dR[c*ldr + i]), theta and norm2 are k device
+ * doubles; 1 <= m <= 64, 1 <= k <= 16.  For row i and column c:
+ *     u = +0.0;  for j = 0 .. m-1 ascending:  u = u + V(i, j) * S[j][c]          (the bits of spmvHipBlockCombine(V, S))
+ *     q = +0.0;  for j = 0 .. m-1 ascending:  q = q + W(i, j) * S[j][c]          (the bits of spmvHipBlockCombine(W, S))
+ *     R(i, c) = q - theta[c] * u                                (the product rounded, then the subtraction)
+ *     dNorm2[c] = spmvHipDot(R(:, c), R(:, c))                  (its bits: the dot's blocks, lanes, tree and finish)
+ * in IEEE double, every product and every add rounded on its own (no FMA, no matrix instruction) -- whatever n, the leading
+ * dimensions and the alignment of the pointers are (one form is chosen per call on the host: 16-byte accesses of two adjacent
+ * rows when dV, dW and dR are 16-byte aligned, ldv and ldw are even or m == 1, and ldr is even or k == 1; 8-byte accesses
+ * otherwise).  With V a basis, W = A V and (theta, S) Ritz pairs of V^T W, column c of R is the residual A x - theta x of
+ * the Ritz vector x = V S(:, c).  A row touches no other row: a NaN or an Inf in one row of V or W stays in that row of R
+ * (it reaches dNorm2).  Rows >= n and columns >= k of R and entries >= k of dNorm2 are not written.  n = 0 launches nothing
+ * and writes nothing, dNorm2 included.
+ *   Two kernels on the library stream (the pass, which leaves k block partials per block of 4096 rows in the dot workspace,
+ *   and the finish of spmvHipMultiDot); the workspace is grown as spmvHipMultiDot grows it, so the call is capturable once a
+ *   call of this size has been made.  spmvHipSetSync, spmvHipLastKernelSeconds and spmvHipLastLaunch as for spmvHipDot.
+ *   It streams 8*n*(2*m + k) bytes.
+ *   Refused (EXIT_FAILURE, dR and dNorm2 untouched): a NULL pointer when n > 0; m outside 1 .. 64, k outside 1 .. 16;
+ *   ldv < n, ldw < n, ldr < n, lds < m; any overlap of the span of dR or of dNorm2 with dV, dW, dS or dTheta, or of dR
+ *   with dNorm2.  (dV and dW may be the same block.)
+ *
+ * hipSpDavidsonCSR: the nev algebraically smallest (or, without a dM, largest) eigenpairs of a symmetric square CSR handle
+ * by generalised Davidson with single-vector expansion: the basis grows by the preconditioned residual of the first wanted
+ * Ritz pair that has not converged, orthogonalised by classical Gram-Schmidt applied twice; the projected matrix H = V^T A V
+ * is kept whole on the host and diagonalised by JACOBI (hipSpLanczosCSR's, above); a full basis is restarted with its kk
+ * wanted Ritz vectors.  dM is NULL (t = r: the Krylov space of v0, restarted as Lanczos restarts it) or anything the Krylov
+ * solvers take as dM -- an ILU(0) handle applied by level sets or by sweeps, an approximate-inverse factor in either
+ * storage, a multigrid hierarchy of dA with any smoother and storage --, and goes through their checks.  Symmetry of A and
+ * of M^-1 is the caller's promise.  theta, res, X, info.status, .found, .iterations, .restarts, .precondApplies,
+ * .hostChecks, .launches, .scale and .sweepsMax are the bits and counts of this loop, in IEEE double with no FMA: dot() is
+ * spmvHipDot, A v is serial-order SpMV, M^-1 r is what hipSpCGCSR applies, sqrt and / are correctly rounded, every
+ * a +- s*v is two roundings in the order written.  m = opts.ncv; v[0 .. m-1], w[0 .. m-1] and R (n x nev) are on the
+ * device; H is m x m, symmetric, on the host.
+ *     nn = dot(v0,v0)
+ *     if nn is not finite: NONFINITE, 0 found;  if nn == 0: BREAKDOWN, 0 found;  if maxIter == 0: MAXITER, 0 found
+ *     v[0] = v0 / sqrt(nn) (element by element);  cols = 0;  it = 0;  restarts = 0;  H = 0
+ *     kk = opts.keep, or for keep == 0: min(m-1, nev + (m - nev)/2) (integer division)
+ *     step:
+ *       j = cols;  w[j] = A v[j];  it = it + 1
+ *       for i = 0..j: H[i][j] = H[j][i] = dot(v[i], w[j])              -- spmvHipMultiDot
+ *       cols = j+1;  if one of these is not finite: NONFINITE, 0 found
+ *       (d, S) = JACOBI(H[0..cols-1][0..cols-1]);  if it did not end, or a d[i] is not finite: NONFINITE, 0 found
+ *       order the columns: d ascending (SMALLEST) or descending (LARGEST), equal values by ascending index: theta, S
+ *       scale = max over all cols of |theta[i]|;  c = min(nev, cols)
+ *       (R, n2) = spmvHipBlockResidual(v[0..cols-1], w[0..cols-1], S[.][0..c-1], theta[0..c-1]);  res[i] = sqrt(n2[i]) for i < c
+ *       if a res[i] is not finite: NONFINITE, 0 found
+ *       done = cols >= nev and res[i] <= tol*scale for every i < nev
+ *       if done or it == maxIter:
+ *         X(:, i) = sum over j = 0..cols-1 of v[j] * S[j][i] for i < c               -- spmvHipBlockCombine
+ *         found = c;  CONVERGED if done, else MAXITER
+ *       l = the first i < c with res[i] > tol*scale;  if there is none (then cols < nev): l = c-1
+ *       if cols == m:                                                   -- the restart
+ *         V(:, i) = sum over j of v[j] * S[j][i],  W(:, i) = sum over j of w[j] * S[j][i]  for i < kk (both in place, j = 0..m-1)
+ *         H = 0;  H[i][i] = theta[i] for i < kk;  cols = kk;  restarts = restarts + 1
+ *       t = M^-1 R(:, l) with a dM (precondApplies = precondApplies + 1), else t = R(:, l)
+ *       for i = 0..cols-1: h[i] = dot(v[i], t);  for i = 0..cols-1 ascending: t = t - h[i]*v[i]
+ *       for i = 0..cols-1: g[i] = dot(v[i], t);  for i = 0..cols-1 ascending: t = t - g[i]*v[i]        -- the second pass
+ *       beta = sqrt(dot(t,t));  if beta is not finite: NONFINITE, 0 found
+ *       if beta == 0: BREAKDOWN with found = c and the X, theta, res of this step  -- t lies in the basis: nothing to add
+ *       v[cols] = t / beta;  next step
+ *   res[i] is the computed norm of the residual A x_i - theta_i x_i formed from the kept products, not an estimate.  The
+ *   vectors w[j] are products A v[j] only until the first restart: afterwards they are rotated with the basis and never
+ *   recomputed, so W drifts from A V by the rounding of the rotations.  On the reference over the converged cases of the
+ *   test table and the 12 x 10 x 8 Laplacian the largest |res[i] - ||A x_i - theta_i x_i||| recomputed from X was 3.8e-15,
+ *   the largest |X^T X - I| entry 2.3e-15 and the largest |theta[i] - eigenvalue| 2.7e-14.
+ *   BREAKDOWN after a restart step returns the first c columns of the rotated basis, which are the X of that step.
+ * Outputs: as hipSpLanczosCSR's (dX n x nev column-major with ldx >= n, theta and res nev host doubles, only the first
+ *   info.found written; dV0 only read, not overlapping dX).  info.iterations counts the products A v, opts.maxIter caps them.
+ * Execution: one device state block with `stop` and `skip`, as in hipSpLanczosCSR.  A step's expansion (M^-1, the two
+ *   projections and updates, beta's scalar step -- it sets skip on beta == 0 and stop on a beta that is not finite --,
+ *   v[cols] = t / beta), its product and the new column of H are enqueued together and read back once; JACOBI runs on the
+ *   host; theta and S[.][0..c-1] are uploaded, the residual block enqueued and its c norms read back: two read-backs a
+ *   step (info.hostChecks; the read after v[0] is not counted; a step that ends on beta has one).  info.launches counts:
+ *   3 before the first step; 3 per product enqueued (the SpMV, the two kernels of the new column of H; the product after a
+ *   beta that is 0 or not finite is enqueued and counted); 2 per residual block; 8 per expansion (two for each projection, the two updates -- the
+ *   second carries the partials of dot(t,t) --, beta's step, the division) and what the dM's application enqueues (hipSpCGCSR
+ *   counts the same); 2 per restart; 1 for X.  Uploads are copies, not launches.  info.ms is the host wall time of the call and
+ *   info.jacobiMs the part of it spent in JACOBI.
+ *   Workspace, allocated by the call and freed before it returns, with ldv = n rounded up to even and nb = ceil(n/4096), in
+ *   this order: 8*ldv*ncv bytes (v), 8*ldv*ncv (w), 8*ldv*nev (R), with a dM 8*ldv (t: no application runs in place; without
+ *   one t is R's column itself), 8*nb*(ncv + 1) of partials, 32 896 bytes for theta and S, about 1 KiB of state.
+ *   Synchronous, on the library stream; not capturable.
+ * Returns EXIT_SUCCESS whatever the status (info may be NULL).  Refused with a message and EXIT_FAILURE, every output
+ *   untouched: everything hipSpLanczosCSR refuses; nev > 16; a dM with SPMV_EIG_LARGEST (a positive definite M^-1 damps the
+ *   wanted directions: on the 21 x 19 x 17 Laplacian the search then took six times the products it takes without a dM, or
+ *   did not end); a dM that hipSpCGCSR refuses for dA. */
+typedef struct {
+    unsigned nev;           /* eigenpairs wanted, 1 .. min(16, ncv-1)                        */
+    unsigned ncv;           /* m: columns of the basis at most, nev+1 .. min(64, M)          */
+    int      which;         /* SPMV_EIG_SMALLEST; SPMV_EIG_LARGEST only without a dM         */
+    double   tol;           /* converged when res[i] <= tol * scale for every i < nev        */
+    ulong    maxIter;       /* products A v at most                                          */
+    unsigned keep;          /* columns a restart keeps, nev .. ncv-1; 0: the default         */
+} spmvDavidsonOpts;
+typedef struct {
+    int      status;        /* SPMV_KRYLOV_*                                                 */
+    unsigned found;         /* eigenpairs written                                            */
+    ulong    iterations;    /* products A v                                                  */
+    ulong    restarts;
+    ulong    precondApplies;/* applications of M^-1                                          */
+    ulong    launches;      /* kernels enqueued (an SpMV counted as one)                     */
+    ulong    hostChecks;    /* read-backs of the device state                                */
+    double   scale;         /* max |theta[i]| over the last step's Ritz values               */
+    unsigned sweepsMax;     /* the most Jacobi sweeps a step took                            */
+    double   ms;            /* host wall time of the call                                    */
+    double   jacobiMs;      /* of which inside JACOBI, over all steps                        */
+} spmvDavidsonInfo;
+int spmvHipBlockResidual(size_t n, unsigned m, unsigned k, const double* dV, size_t ldv, const double* dW, size_t ldw, const double* dS,
+                         size_t lds, const double* dTheta, double* dR, size_t ldr, double* dNorm2);
+int hipSpDavidsonCSR(spmat* dA, spmat* dM, const double* dV0, const spmvDavidsonOpts* opts, double* dX, size_t ldx, double* theta,
+                     double* res, spmvDavidsonInfo* info);
 /* ------------------------------------------------------------- multi-colour ordering, symmetric permutation */
 /* Reordering for fewer level sets: if rows of one colour share no entry and the matrix is permuted so that colours are
  * contiguous, both triangles of B = P A P^T have at most as many level sets as there are colours, and hipSpTRSVCSR /

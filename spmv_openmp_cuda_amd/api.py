@@ -134,6 +134,8 @@ _sigs = {
     "hipSpGMRESCSR": ([C.POINTER(spmat), C.POINTER(spmat), _vp, _vp, _vp, _vp], _i),
     "spmvHipBlockCombine": ([_sz, C.c_uint, C.c_uint, _vp, _sz, _vp, _sz, _vp, _sz], _i),
     "hipSpLanczosCSR": ([C.POINTER(spmat), _vp, _vp, _vp, _sz, _vp, _vp, _vp], _i),
+    "spmvHipBlockResidual": ([_sz, C.c_uint, C.c_uint, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _vp], _i),
+    "hipSpDavidsonCSR": ([C.POINTER(spmat), C.POINTER(spmat), _vp, _vp, _vp, _sz, _vp, _vp, _vp], _i),
     "spmvHipColourCSR": ([C.POINTER(spmat), _vp, _vp, _vp, _vp], _i),
     "spmvHipCsrPermute": ([C.POINTER(spmat), _vp, C.POINTER(spmat)], _i),
     "spmvHipPermuteRefresh": ([C.POINTER(spmat), C.POINTER(spmat)], _i),
@@ -279,6 +281,20 @@ class spmvLanczosInfo(C.Structure):
     """include/spmvHip.h `spmvLanczosInfo`: what a hipSpLanczosCSR call did."""
     _fields_ = [("status", _i), ("found", C.c_uint), ("iterations", C.c_ulong), ("cycles", C.c_ulong), ("launches", C.c_ulong),
                 ("hostChecks", C.c_ulong), ("scale", C.c_double), ("sweepsMax", C.c_uint), ("ms", C.c_double), ("jacobiMs", C.c_double)]
+
+
+class spmvDavidsonOpts(C.Structure):
+    """include/spmvHip.h `spmvDavidsonOpts`: eigenpairs wanted (at most 16), columns of the basis at most, the end of the
+    spectrum, tolerance, cap on the products A v, columns a restart keeps (0: the default)."""
+    _fields_ = [("nev", C.c_uint), ("ncv", C.c_uint), ("which", _i), ("tol", C.c_double), ("maxIter", C.c_ulong),
+                ("keep", C.c_uint)]
+
+
+class spmvDavidsonInfo(C.Structure):
+    """include/spmvHip.h `spmvDavidsonInfo`: what a hipSpDavidsonCSR call did."""
+    _fields_ = [("status", _i), ("found", C.c_uint), ("iterations", C.c_ulong), ("restarts", C.c_ulong), ("precondApplies", C.c_ulong),
+                ("launches", C.c_ulong), ("hostChecks", C.c_ulong), ("scale", C.c_double), ("sweepsMax", C.c_uint), ("ms", C.c_double),
+                ("jacobiMs", C.c_double)]
 
 
 class spmvKrylovInfo(C.Structure):
@@ -1342,29 +1358,45 @@ class DeviceMatrix:
         info.history holds the estimates inside a cycle and the true squared residual at every cycle's last index."""
         return self._krylov(lib.hipSpGMRESCSR, "hipSpGMRESCSR", b, x0, precond, tol, maxiter, history, restart=restart)
 
-    def eigsh(self, k=6, which="LA", ncv=None, v0=None, tol=1e-8, maxiter=None, keep=0):
-        """hipSpLanczosCSR: the k algebraically largest (which="LA") or smallest ("SA") eigenpairs of this symmetric
-        matrix by thick-restart Lanczos, with the bits of the loop in include/spmvHip.h.  Returns (theta, X, info): theta
-        a numpy array of the info.found values in the order of the wanted end, X the (N, found) eigenvectors (numpy for
-        a numpy v0, else a torch tensor with contiguous columns), info a spmvLanczosInfo with info.res the residual
-        estimates.  Conventions of this layer, not of the library: ncv=None means min(N, 64, max(2k + 1, 20)); v0=None
+    def eigsh(self, k=6, which="LA", ncv=None, v0=None, tol=1e-8, maxiter=None, keep=0, method="lanczos", precond=None):
+        """The k algebraically largest (which="LA") or smallest ("SA") eigenpairs of this symmetric matrix, with the bits of
+        the loops in include/spmvHip.h: method="lanczos" is hipSpLanczosCSR (thick-restart Lanczos), method="davidson"
+        hipSpDavidsonCSR (generalised Davidson, k <= 16), which takes precond: None, or what cg() takes -- a DeviceMatrix
+        holding ILU(0) factors, this matrix's multigrid hierarchy (`amg()`) or an approximate-inverse factor (`fsai()`) --,
+        and then only which="SA".  Returns (theta, X, info): theta a numpy array of the info.found values in the order of
+        the wanted end, X the (N, found) eigenvectors (numpy for a numpy v0, else a torch tensor with contiguous columns),
+        info a spmvLanczosInfo or spmvDavidsonInfo with info.res the residual norms (Lanczos: estimates; Davidson:
+        computed).  Conventions of this layer, not of the library: ncv=None means min(N, 64, max(2k + 1, 20)); v0=None
         means numpy.random.default_rng(0).standard_normal(N); maxiter=None means 10 N products A v."""
         N = int(self.handle.N)
         if which not in EIG_WHICH:
             raise SpmvHipError(f"eigsh: which must be one of {sorted(EIG_WHICH)}, not {which!r}")
+        if method not in ("lanczos", "davidson"):
+            raise SpmvHipError(f"eigsh: method must be 'lanczos' or 'davidson', not {method!r}")
+        if precond is not None and method != "davidson":
+            raise SpmvHipError("eigsh: precond is taken only by method='davidson'")
+        if precond is not None and which != "SA":
+            raise SpmvHipError("eigsh: precond is taken only with which='SA' (hipSpDavidsonCSR refuses it for the largest pairs)")
         k = int(k)
         ncv = min(N, 64, max(2 * k + 1, 20)) if ncv is None else int(ncv)
         if v0 is None:
             v0 = np.random.default_rng(0).standard_normal(N)
-        opts = spmvLanczosOpts(k, ncv, EIG_WHICH[which], float(tol), 10 * N if maxiter is None else int(maxiter), int(keep))
-        info = spmvLanczosInfo()
+        davidson = method == "davidson"
+        opts = (spmvDavidsonOpts if davidson else spmvLanczosOpts)(k, ncv, EIG_WHICH[which], float(tol),
+                                                                 10 * N if maxiter is None else int(maxiter), int(keep))
+        info = spmvDavidsonInfo() if davidson else spmvLanczosInfo()
         theta, res = np.zeros(max(k, 0)), np.zeros(max(k, 0))
         with _Operands("eigsh", v0) as ops:
             ops.vector("v0", v0, N)
             ops.result("X", None, (max(k, 0), N))                    # (row c of this block is column c of X: ldx = N)
             dv0, dx = ops.args
-            _check(lib.hipSpLanczosCSR(C.byref(self.handle), dv0, C.byref(opts), dx, N, _ptr(theta), _ptr(res), C.byref(info)),
-                   "hipSpLanczosCSR")
+            if davidson:
+                mh = C.byref(precond.handle) if precond is not None else None
+                _check(lib.hipSpDavidsonCSR(C.byref(self.handle), mh, dv0, C.byref(opts), dx, N, _ptr(theta), _ptr(res), C.byref(info)),
+                       "hipSpDavidsonCSR")
+            else:
+                _check(lib.hipSpLanczosCSR(C.byref(self.handle), dv0, C.byref(opts), dx, N, _ptr(theta), _ptr(res), C.byref(info)),
+                       "hipSpLanczosCSR")
             X = ops.value()
         info.res = res[:info.found].copy()
         return theta[:info.found].copy(), X[:info.found].T, info
@@ -1820,6 +1852,27 @@ def block_combine(V, S):
         dV, dS, dY = ops.args
         _check(lib.spmvHipBlockCombine(n, m, k, dV, ldv, dS, max(lds, m), dY, max(n, 1)), "spmvHipBlockCombine")
         return ops.value().T
+
+
+def block_residual(V, W, S, theta):
+    """spmvHipBlockResidual: (R, norm2) with R[i, c] = (sum_j W[i, j] S[j, c]) - theta[c] * (sum_j V[i, j] S[j, c]), both sums over
+    ascending j from +0.0 with every product and add rounded on its own, and norm2[c] the bits of dot(R[:, c], R[:, c]).  V and
+    W (n, m), S (m, k), theta (k,), m in 1 .. 64, k in 1 .. 16: float64 device torch tensors, the 2-D ones with contiguous
+    columns (the rule of multi_dot's V) -> R an (n, k) device tensor with contiguous columns and norm2 a length-k one (two
+    views of one new tensor); or numpy arrays -> numpy arrays."""
+    with _Operands("block_residual", V) as ops:
+        n, m, ldv = ops.columns("V", V)
+        nw, mw, ldw = ops.columns("W", W)
+        ms, k, lds = ops.columns("S", S)
+        if (nw, mw) != (n, m) or ms != m:
+            raise SpmvHipError(f"block_residual: W must be ({n}, {m}) and S must have {m} rows, not {(nw, mw)} and {ms}")
+        ops.vector("theta", theta, k, least=8)
+        ops.result("R", None, (k * n + k,), least=8)                 # (column c of R at [c*n ..]: ldr = n; then norm2)
+        dV, dW, dS, dTheta, dR = ops.args
+        _check(lib.spmvHipBlockResidual(n, m, k, dV, ldv, dW, max(ldw, n, 1), dS, max(lds, m), dTheta, dR, max(n, 1), dR + 8 * k * n),
+               "spmvHipBlockResidual")
+        out = ops.value()
+        return out[:k * n].reshape(k, n).T, out[k * n:]
 
 
 def block_dot(U, V):

@@ -426,6 +426,20 @@ unsigned lanczosDefaultKeep(unsigned nev, unsigned ncv);
 size_t lanczosWorkspaceBytes(uint64_t n, uint32_t ncv);
 int  lanczosSolve(spmat* hA, const DevMat* a, const double* v0, const spmvLanczosOpts* opts, double* X, uint64_t ldx, double* theta,
                   double* res, spmvLanczosInfo* info, hipStream_t stream);
+// R = W S - (V S) diag(theta) with its column norms, and generalised Davidson (davidson.hip; contract in spmvHip.h, design in
+// DESIGN.md section 42).  enqueueBlockResidual: the pass and the finish of its k norms (nothing for n = 0) on checked
+// operands, the block partials in `part` (k blocks-of-n doubles), flags null or {stop, skip} of a solve, *grid the pass's
+// shape.  blockResidual: the same with the partials in the dot workspace.  davidsonSolve: the loop on the checked handles and
+// options (m: the checked dM or null); allocates davidsonWorkspaceBytes, synchronous; theta, res, X and info are written only
+// on EXIT_SUCCESS.
+int  enqueueBlockResidual(uint64_t n, uint32_t m, uint32_t k, const double* V, uint64_t ldv, const double* W, uint64_t ldw, const double* S,
+                          uint64_t lds, const double* theta, double* R, uint64_t ldr, double* part, double* norm2, const uint32_t* flags,
+                          hipStream_t stream, dim3* grid);
+int  blockResidual(uint64_t n, uint32_t m, uint32_t k, const double* V, uint64_t ldv, const double* W, uint64_t ldw, const double* S,
+                   uint64_t lds, const double* theta, double* R, uint64_t ldr, double* norm2, hipStream_t stream, dim3* grid);
+size_t davidsonWorkspaceBytes(uint64_t n, uint32_t ncv, uint32_t nev, int precond);
+int  davidsonSolve(spmat* hA, const DevMat* a, const DevMat* m, const double* v0, const spmvDavidsonOpts* opts, double* X, uint64_t ldx,
+                   double* theta, double* res, spmvDavidsonInfo* info, hipStream_t stream);
 size_t gmresWorkspaceBytes(uint64_t n, uint32_t restart, uint64_t maxIter, int precond, int history);
 int  gmresSolve(spmat* hA, const DevMat* a, const DevMat* m, const double* b, double* x, const spmvGmresOpts* opts,
                 spmvKrylovInfo* info, int fused, hipStream_t stream);

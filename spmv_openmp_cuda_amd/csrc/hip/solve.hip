@@ -1,7 +1,7 @@
 // solve.hip -- the solver side of the extern "C" boundary: triangular solves, ILU(0), the multi-colour ordering, the reverse
 // Cuthill-McKee ordering and the vector permutation, the dots, aggregation multigrid, the three Krylov solvers, the basis rotation
-// and the Lanczos eigensolver.  The algorithm
-// files (trsv.hip, ilu0.hip, colour.hip, rcm.hip, krylov.hip, gmres.hip, lanczos.hip, aggregate.hip, amg.hip) build and launch; here are the checks, the library's settings
+// and the two eigensolvers (Lanczos, Davidson) with the residual block.  The algorithm
+// files (trsv.hip, ilu0.hip, colour.hip, rcm.hip, krylov.hip, gmres.hip, lanczos.hip, davidson.hip, aggregate.hip, amg.hip) build and launch; here are the checks, the library's settings
 // handed down as arguments, and the timing bracket.  Contracts in spmvHip.h, designs in DESIGN.md sections 17 to 21 and 24.
 #include <hip/hip_runtime.h>
 #include <chrono>
@@ -478,6 +478,33 @@ int spmvHipAmgGaussSeidel(spmat* dM, unsigned level, spmvAmgGsInfo* info) {
 }
 
 // ---- Krylov solves
+// dM as the preconditioner of a solve on the checked dA (a): NULL (none), a multigrid hierarchy of dA, an approximate-inverse
+// factor of dA's size, or a square CSR handle whose two triangles are applied (analysed here unless it runs by sweeps).
+// What hipSpCGCSR, hipSpBiCGStabCSR, hipSpGMRESCSR, their block forms and hipSpDavidsonCSR check alike; false: refused.
+static bool precondOf(const char* who, spmat* dM, DevMat* a, DevMat** pm) {
+    DevMat* m = dM ? anyDescOf(dM, who) : nullptr;
+    if (dM && !m) return false;
+    if (m && m->origin == Origin::HIERARCHY) {               // a multigrid hierarchy: M^-1 v is its cycle
+        if (!madeBy(m, Origin::HIERARCHY, a, nullptr, who, "dM", "dA")) return false;
+    } else if (m && m->origin == Origin::FSAI) {             // an approximate-inverse factor: M^-1 v = G^T (G v), of any source of dA's size
+        if (m->M != a->M) { ERR("%s: dM has %lu rows, dA %lu", who, (unsigned long)m->M, (unsigned long)a->M); return false; }
+    } else if (dM) {
+        if (!(m = triHandle(dM, SPMV_TRI_LOWER, who))) return false;
+        if (m->M != a->M) { ERR("%s: dM has %lu rows, dA %lu", who, (unsigned long)m->M, (unsigned long)a->M); return false; }
+        if (m->NZ && !m->AS && !m->unit) { ERR("%s: dM has no value array", who); return false; }
+        const bool sweeps = triSweepsMode(m);                // applied by Jacobi sweeps (spmvHipTriSetApply): no level sets
+        for (int uplo : {SPMV_TRI_LOWER, SPMV_TRI_UPPER})
+            if (!sweeps && m->M && !m->tri[uplo] && triAnalyse(m, uplo, S.triRunRows, S.stream)) { ERR("%s: the analysis of dM failed", who); return false; }
+        const long badDiag = !m->M ? -1 : sweeps ? m->sweep->firstBadDiag : m->tri[SPMV_TRI_UPPER]->info.firstBadDiag;
+        if (badDiag >= 0) {
+            ERR("%s: row %ld of dM does not hold exactly one stored diagonal entry (M^-1 divides by it)", who, badDiag);
+            return false;
+        }
+    }
+    *pm = m;
+    return true;
+}
+
 // what the three solvers check alike: 0 go on (a, m set), 1 refused, 2 done (M = 0)
 static int krylovArgs(const char* who, spmat* dA, spmat* dM, const double* dB, double* dX, const void* optsPtr, double tol, ulong maxIter,
                       double* history, spmvKrylovInfo* info, DevMat** pa, DevMat** pm) {
@@ -493,25 +520,8 @@ static int krylovArgs(const char* who, spmat* dA, spmat* dM, const double* dB, d
         ERR("%s: a history of maxIter + 1 = %lu + 1 doubles does not fit", who, (unsigned long)maxIter);
         return EXIT_FAILURE;
     }
-    DevMat* m = dM ? anyDescOf(dM, who) : nullptr;
-    if (dM && !m) return EXIT_FAILURE;
-    if (m && m->origin == Origin::HIERARCHY) {               // a multigrid hierarchy: M^-1 v is its cycle
-        if (!madeBy(m, Origin::HIERARCHY, a, nullptr, who, "dM", "dA")) return EXIT_FAILURE;
-    } else if (m && m->origin == Origin::FSAI) {             // an approximate-inverse factor: M^-1 v = G^T (G v), of any source of dA's size
-        if (m->M != a->M) { ERR("%s: dM has %lu rows, dA %lu", who, (unsigned long)m->M, (unsigned long)a->M); return EXIT_FAILURE; }
-    } else if (dM) {
-        if (!(m = triHandle(dM, SPMV_TRI_LOWER, who))) return EXIT_FAILURE;
-        if (m->M != a->M) { ERR("%s: dM has %lu rows, dA %lu", who, (unsigned long)m->M, (unsigned long)a->M); return EXIT_FAILURE; }
-        if (m->NZ && !m->AS && !m->unit) { ERR("%s: dM has no value array", who); return EXIT_FAILURE; }
-        const bool sweeps = triSweepsMode(m);                // applied by Jacobi sweeps (spmvHipTriSetApply): no level sets
-        for (int uplo : {SPMV_TRI_LOWER, SPMV_TRI_UPPER})
-            if (!sweeps && m->M && !m->tri[uplo] && triAnalyse(m, uplo, S.triRunRows, S.stream)) { ERR("%s: the analysis of dM failed", who); return EXIT_FAILURE; }
-        const long badDiag = !m->M ? -1 : sweeps ? m->sweep->firstBadDiag : m->tri[SPMV_TRI_UPPER]->info.firstBadDiag;
-        if (badDiag >= 0) {
-            ERR("%s: row %ld of dM does not hold exactly one stored diagonal entry (M^-1 divides by it)", who, badDiag);
-            return EXIT_FAILURE;
-        }
-    }
+    DevMat* m = nullptr;
+    if (!precondOf(who, dM, a, &m)) return EXIT_FAILURE;
     *pa = a;
     *pm = m;
     if (a->M == 0) {
@@ -674,6 +684,73 @@ int hipSpLanczosCSR(spmat* dA, const double* dV0, const spmvLanczosOpts* opts, d
     if (ldx < a->M) { ERR("%s: ldx=%zu < M=%lu", who, ldx, (unsigned long)a->M); return EXIT_FAILURE; }
     if (spansShare(dV0, a->M * sizeof(double), dX, colMajorSpan(a->M, opts->nev, ldx))) { ERR("%s: dV0 and dX overlap", who); return EXIT_FAILURE; }
     if (lanczosSolve(dA, a, dV0, opts, dX, ldx, theta, res, info, S.stream)) { ERR("%s: the solve failed", who); return EXIT_FAILURE; }
+    return EXIT_SUCCESS;
+}
+
+// ---- the residual block and the preconditioned eigensolver (contract in spmvHip.h, design in DESIGN.md section 42)
+int spmvHipBlockResidual(size_t n, unsigned m, unsigned k, const double* dV, size_t ldv, const double* dW, size_t ldw, const double* dS,
+                         size_t lds, const double* dTheta, double* dR, size_t ldr, double* dNorm2) {
+    const char* who = "spmvHipBlockResidual";
+    const Ctx cx = libraryCtx();
+    if (!ready(who)) return EXIT_FAILURE;
+    if (n && (!dV || !dW || !dS || !dTheta || !dR || !dNorm2)) {
+        ERR("%s: %s is NULL", who, !dV ? "dV" : !dW ? "dW" : !dS ? "dS" : !dTheta ? "dTheta" : !dR ? "dR" : "dNorm2");
+        return EXIT_FAILURE;
+    }
+    if (m == 0 || m > 64 || k == 0 || k > 16) { ERR("%s: m=%u, k=%u: m must be in 1 .. 64 and k in 1 .. 16", who, m, k); return EXIT_FAILURE; }
+    if (ldv < n || ldw < n || ldr < n || lds < m) {
+        ERR("%s: ldv=%zu, ldw=%zu, ldr=%zu (n=%zu) or lds=%zu (m=%u) is too small", who, ldv, ldw, ldr, n, lds, m);
+        return EXIT_FAILURE;
+    }
+    const uint64_t rBytes = colMajorSpan(n, k, ldr), nBytes = (uint64_t)k * sizeof(double);
+    const struct { const void* p; uint64_t bytes; const char* name; } in[] = {
+        {dV, colMajorSpan(n, m, ldv), "dV"}, {dW, colMajorSpan(n, m, ldw), "dW"}, {dS, colMajorSpan(m, k, lds), "dS"}, {dTheta, nBytes, "dTheta"}};
+    for (const auto& x : in)
+        if (spansShare(x.p, x.bytes, dR, rBytes) || (n && spansShare(x.p, x.bytes, dNorm2, nBytes))) {
+            ERR("%s: %s overlaps dR or dNorm2", who, x.name);
+            return EXIT_FAILURE;
+        }
+    if (spansShare(dR, rBytes, dNorm2, nBytes)) { ERR("%s: dR and dNorm2 overlap", who); return EXIT_FAILURE; }
+    Launch L(cx, dim3(1), dim3(256));
+    dim3 grid(1);
+    if (blockResidual(n, m, k, dV, ldv, dW, ldw, dS, lds, dTheta, dR, ldr, dNorm2, cx.stream, &grid)) { ERR("%s: launch failed", who); return EXIT_FAILURE; }
+    L.shape(grid, dim3(256));
+    return L.finish(who);
+}
+
+int hipSpDavidsonCSR(spmat* dA, spmat* dM, const double* dV0, const spmvDavidsonOpts* opts, double* dX, size_t ldx, double* theta,
+                     double* res, spmvDavidsonInfo* info) {
+    const char* who = "hipSpDavidsonCSR";
+    if (!ready(who)) return EXIT_FAILURE;
+    if (!dV0 || !opts || !dX || !theta || !res) {
+        ERR("%s: %s is NULL", who, !dV0 ? "dV0" : !opts ? "opts" : !dX ? "dX" : !theta ? "theta" : "res");
+        return EXIT_FAILURE;
+    }
+    DevMat* a = csrOf(dA, who, "dA is an ELL handle (only CSR handles are solved)");
+    if (!a) return EXIT_FAILURE;
+    if (a->M != a->N) { ERR("%s: M=%lu != N=%lu: dA is not square", who, (unsigned long)a->M, (unsigned long)a->N); return EXIT_FAILURE; }
+    if (a->NZ && !a->AS && !a->unit) { ERR("%s: dA has no value array", who); return EXIT_FAILURE; }
+    if (opts->nev == 0 || opts->nev > 16 || opts->nev >= opts->ncv || opts->ncv > 64 || opts->ncv > a->M) {
+        ERR("%s: nev=%u, ncv=%u, M=%lu: 1 <= nev <= 16 and nev < ncv <= min(64, M) are required", who, opts->nev, opts->ncv, (unsigned long)a->M);
+        return EXIT_FAILURE;
+    }
+    if (opts->which != SPMV_EIG_LARGEST && opts->which != SPMV_EIG_SMALLEST) { ERR("%s: unknown which %d", who, opts->which); return EXIT_FAILURE; }
+    if (!(opts->tol >= 0.0)) { ERR("%s: tol %g is negative or NaN", who, opts->tol); return EXIT_FAILURE; }
+    if (opts->keep && (opts->keep < opts->nev || opts->keep > opts->ncv - 1)) {
+        ERR("%s: keep=%u is not 0 and not in nev .. ncv-1 = %u .. %u", who, opts->keep, opts->nev, opts->ncv - 1);
+        return EXIT_FAILURE;
+    }
+    if (ldx < a->M) { ERR("%s: ldx=%zu < M=%lu", who, ldx, (unsigned long)a->M); return EXIT_FAILURE; }
+    if (spansShare(dV0, a->M * sizeof(double), dX, colMajorSpan(a->M, opts->nev, ldx))) { ERR("%s: dV0 and dX overlap", who); return EXIT_FAILURE; }
+    if (dM && opts->which == SPMV_EIG_LARGEST) {
+        ERR("%s: a dM with SPMV_EIG_LARGEST: a positive definite M^-1 damps the directions of the large eigenvalues, and the search for "
+            "the upper end then takes many times the products it takes without a dM (DESIGN.md section 42); drop dM or ask for "
+            "SPMV_EIG_SMALLEST", who);
+        return EXIT_FAILURE;
+    }
+    DevMat* m = nullptr;
+    if (!precondOf(who, dM, a, &m)) return EXIT_FAILURE;
+    if (davidsonSolve(dA, a, m, dV0, opts, dX, ldx, theta, res, info, S.stream)) { ERR("%s: the solve failed", who); return EXIT_FAILURE; }
     return EXIT_SUCCESS;
 }
 
