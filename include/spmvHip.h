@@ -305,8 +305,10 @@ int hipSpTRSMCSR(spmat* dA, int uplo, int diag, unsigned k, const double* dB, si
  * Plan: spmvHipTriSweepsPrepare(dA, blockWidth) builds it (blockWidth 0: one column; a larger width than the plan's widens
  *   the workspace, a smaller one is a no-op): the diagonal's places and two M x width iterates, 4 B + 16 B x width per row.
  *   Synchronous, allocates (not capturable).  The first sweep solve of an unprepared handle prepares it for its own width.
- *   spmvHipUpdateValues, spmvHipValuesChanged, hipSpILU0CSR and spmvHipTransposeRefresh keep it at the same addresses (the
- *   sweeps read AS live); hipFreeSpmat frees it.
+ *   spmvHipUpdateValues, spmvHipValuesChanged, hipSpILU0CSR and every refresh that keeps the handle's pattern --
+ *   spmvHipTransposeRefresh, spmvHipPermuteRefresh, spmvHipSpGEMMRefresh, spmvHipCsrAddRefresh, spmvHipCsrFilterRefresh and
+ *   spmvHipCooAssembleRefresh -- keep it at the same addresses with `prepares` unchanged, and keep the apply mode and its
+ *   sweep counts (the sweeps read AS live); only a widening moves the workspace, never diagPos; hipFreeSpmat frees it.
  * Solve: kernels only, on the library stream: S launches (UNIT; S + 1 for S == 1 in place; S == 0: one copy, none in place),
  *   S + 1 (STORED); no allocation and no host sync once prepared, so it can be captured into a graph.  spmvHipSetSync,
  *   spmvHipLastKernelSeconds and spmvHipLastLaunch as for hipSpTRSVCSR.  M = 0 succeeds and writes nothing.
@@ -417,7 +419,10 @@ int spmvHipIlu0Info(spmat* dA, spmvIluInfo* info);
  *   M = 0 succeeds with no kernel.
  * dG is an ordinary live CSR handle (SpMV, transpose, product, filter, spmvHipCsrToCoo take it: G A G^T can be formed with
  *   the public product) that privately owns G^T -- the handle spmvHipCsrTranspose would make of G -- and one M-vector of
- *   workspace; hipFreeSpmat(dG) frees all three.  Synchronous, allocates: not capturable.
+ *   workspace; hipFreeSpmat(dG) frees all three.  Synchronous, allocates: not capturable.  dG is to be read, not written:
+ *   after a direct write into it (spmvHipUpdateValues, spmvHipValuesChanged, hipSpILU0CSR) or a spmvHipValuesF32 call on it the
+ *   owned G^T and the storage setting no longer match G, and what spmvHipFsaiApply and a solver compute with it is undefined
+ *   until the next spmvHipFsaiRefresh; its values change through spmvHipFsaiRefresh, its f32 forms through spmvHipFsaiSetStorage.
  * spmvHipFsaiRefresh(dG, dA): dA -- the handle of the setup -- has new values on the same pattern at the same addresses.  The
  *   values of G are computed again in place over the setup's columns, G^T takes them through its map, and both are refreshed
  *   as by spmvHipValuesChanged.  IRP, JA and AS keep their addresses.
@@ -1643,7 +1648,9 @@ int spmvHipAmgBlock(spmat* dM, spmvAmgBlockInfo* info);
  * values give.  For the plain, smoothed and strength hierarchies, the Jacobi and the Chebyshev smoother.  The cycle is still
  * one fixed linear operator, symmetric if it was.  spmvHipAmgRefresh keeps the setting: the forms follow the levels' new
  * values.  SPMV_STORAGE_F64, the state after a setup, releases the forms (dA's only if this call built it).  Synchronous,
- * allocates 4 B per entry of those matrices; idempotent.
+ * allocates 4 B per entry of those matrices; idempotent.  hipFreeSpmat(dM) of an F32 hierarchy frees the forms of its own
+ * levels with them; the form on dA is dA's and stays until spmvHipValuesF32(dA, 0) or hipFreeSpmat(dA).  While a hierarchy of
+ * dA is stored in F32, releasing dA's form makes its cycles refuse until the form is built again.
  * Refused with a message, the hierarchy left as it was: what spmvHipAmgRefresh refuses; a storage that is neither constant;
  * F32 on a hierarchy with a Gauss-Seidel level (its sweeps read the double values in kernels of their own) -- and
  * spmvHipAmgSetGaussSeidel on an F32 hierarchy; a failed allocation (what the call built is released).
@@ -1769,10 +1776,12 @@ int hipSpMMRowsCSR(spmat* dMat, unsigned k, const double* dX, size_t ldx, int xL
  * A unit handle (every stored value the same double, spmvHipUnitValue) gets no array: its register value is rounded the
  * same way on the host and the unit kernels serve it.
  * spmvHipValuesF32(dMat, on): on != 0 builds the form and keeps it (one elementwise pass; one device allocation of
- *   4 NZ bytes rounded up to 16, plus 32 for the pass's counters; a unit handle: none), on == 0 releases it.  Idempotent,
+ *   4 NZ bytes rounded up to 16, plus 32 for the pass's counters; a unit handle: none), on == 0 releases it at once: the
+ *   array is freed, spmvHipValuesF32Info reports zeros and -1 again, the f32 products refuse the handle until it is built
+ *   again, and that build starts at refreshes = 0.  Idempotent,
  *   synchronous on the library stream.  The form belongs to the handle like the two-phase, stripes and SELL formats, is
  *   freed with it, and FOLLOWS the values: after spmvHipUpdateValues / spmvHipValuesChanged, every refresh of a derived
- *   handle and hipSpILU0CSR it holds the roundings of the new values at the same address.  A unit -> non-unit update
+ *   handle, spmvHipCooAssembleRefresh and hipSpILU0CSR it holds the roundings of the new values at the same address.  A unit -> non-unit update
  *   allocates the array, the reverse frees it; if that allocation is refused the update fails with a message, the handle
  *   keeps its new double values and stays usable, and the form is not built (build it again).
  *   No f64 call changes what it returns, which kernel it picks or what it allocates, built or not.

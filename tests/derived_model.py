@@ -129,6 +129,10 @@ def build_node(kind, params, S):
     if kind == "filter":
         C, kept = fr.filter_ref(S[0], params)
         return C, kept
+    if kind == "fsai":                                   # (tests/state_model.py: the factor G of S[0] on the pattern S[1], or its own)
+        import fsai_ref
+        G, info = fsai_ref.fsai_loop(S[0], S[1] if len(S) > 1 else None)
+        return G, (S[1][:4] + (None,) if len(S) > 1 else None)
     raise KeyError(kind)
 
 
@@ -142,11 +146,19 @@ def refresh_values(kind, params, aux, S):
         return ad.add_ref(params["alpha"], S[0], params["beta"], S[1])[4]
     if kind == "filter":
         return fr.filter_refresh_ref(aux, S[0], params)[4]
+    if kind == "fsai":
+        import fsai_ref
+        return fsai_ref.fsai_loop(S[0], aux)[0][4]
     raise KeyError(kind)
 
 
 def permutation(A, params):
-    """perm[new] = old of X.colour(order, seed)"""
+    """perm[new] = old of X.colour(order, seed), or of X.rcm(start, max_passes, forward) for the order "rcm" (a hook of
+    tests/state_model.py: this module's own generator never draws it)"""
+    if params["order"] == "rcm":
+        import rcm_ref
+        start = {"peripheral": rcm_ref.PERIPHERAL, "min_degree": rcm_ref.MIN_DEGREE}[params["start"]]
+        return np.asarray(rcm_ref.rcm_loop(A[0], A[2], A[3], start, params["max_passes"], params["forward"])[0], dtype=np.int64)
     colour, _ = cr.colour_ref(A[0], A[2], A[3], {"natural": cr.NATURAL, "hash": cr.HASH}[params["order"]], params["seed"])
     return cr.perm_of(colour)
 
@@ -191,13 +203,26 @@ class Hier:
         self.kind, self.kw, self.levels, self.o = kind, kw, levels, o
         self.sm, self.set_call = acr.smoother(o, kind=acr.JACOBI), None      # set_call: the last set_* call, for a twin
         self.width, self.alive, self.refreshed = 0, True, False
+        self.storage, self.a0form = "f64", False             # (tests/state_model.py switches the storage; here it stays f64)
+
+    def active(self):
+        """the levels a cycle streams: in F32 storage their roundings (values_f32_ref.rounded_levels)"""
+        if self.storage == "f64":
+            return self.levels
+        import values_f32_ref
+        return values_f32_ref.rounded_levels(self.levels)
 
     def cycle(self, r):
         ref = ags if self.sm["kind"] == ags.GAUSS_SEIDEL else acr
-        return ref.cycle_ref(self.levels, self.o, np.asarray(r, dtype=np.float64), self.sm)
+        return ref.cycle_ref(self.active(), self.o, np.asarray(r, dtype=np.float64), self.sm)
 
 
 class Generator:
+    HIER_ACTIONS = ("set_smoother", "set_gauss_seidel", "set_block_width", "refresh", "apply", "apply_block", "apply_block", "set_block_width",
+                    "set_smoother", "apply", "free")
+    OPS = OPS                           # hooks of a subclass (tests/state_model.py): its own table of operations ...
+    sources = staticmethod(sources)     # ... and its own source matrices
+
     def __init__(self, seed, steps=STEPS):
         self.hiers = []
         self.seed, self.steps = seed, steps
@@ -281,12 +306,12 @@ class Generator:
 
     # --------------------------------------------------------------------------------------------------- operations
     def run(self):
-        for name, mat in sources().items():
+        for name, mat in self.sources().items():
             n = self._add("source", (), {"adopted": name == "N"}, mat, None, name)
             yield self._log("upload", f"upload {name}" + (" (adopted, 8-byte row pointers)" if name == "N" else ""), node=n.id)
-        w = np.array([x for _, x in OPS], dtype=np.float64)
+        w = np.array([x for _, x in self.OPS], dtype=np.float64)
         for _ in range(self.steps):
-            op = OPS[int(self.rng.choice(len(OPS), p=w / w.sum()))][0]
+            op = self.OPS[int(self.rng.choice(len(self.OPS), p=w / w.sum()))][0]
             rec = getattr(self, "op_" + op)()
             if rec is None:                              # nothing to do it on yet: the pool grows instead
                 rec = self.op_derive()
@@ -346,12 +371,14 @@ class Generator:
             H.alive = False
             return self._log("hierarchy", f"free {H.label}: its source {n.label} is gone", node=n.id, hier=H.id, action="free")
         stale = n.version != H.version
-        action = ("set_smoother", "set_gauss_seidel", "set_block_width", "refresh", "apply", "apply_block", "apply_block", "set_block_width", "set_smoother", "apply", "free")[int(rng.integers(11))]
+        action = self.HIER_ACTIONS[int(rng.integers(len(self.HIER_ACTIONS)))]
         if action == "apply_block" and H.width == 0 and rng.random() < 0.6:
             action = "set_block_width"                   # a workspace first: mostly a block cycle is one that is taken
         if stale:                                        # the cycle of a stale hierarchy is not specified: refresh it, or let it go
             action = "refresh"
         nu = dict(nu1=int(rng.integers(1, 4)), nu2=int(rng.integers(1, 4)), nuCoarse=int(rng.integers(1, 5)))
+        if action == "set_storage":                          # (a subclass's action)
+            return self._hier_storage(H, n)
         if action == "free":
             H.alive = False
             return self._log("hierarchy", f"free {H.label}", node=n.id, hier=H.id, action="free")
@@ -374,6 +401,9 @@ class Generator:
         if action == "set_gauss_seidel":
             args = dict(omega=float(rng.choice([1.0, 0.9])), order=("natural", "hash")[int(rng.integers(2))], seed=int(rng.integers(1 << 16)),
                         one_way=bool(rng.integers(2)), levels=(None, 1)[int(rng.integers(2))], **nu)
+            if H.storage == "f32":                           # refused: the sweeps read the double values; the smoother stays
+                self.stats["hierarchy gauss_seidel refused in F32"] += 1
+                return self._cycle(H, n, f"{H.label}.set_gauss_seidel({args}) refused: the hierarchy is stored in F32", action, args=args, refused=True)
             H.sm = ags.smoother(H.o, omega=args["omega"], order=ags.HASH if args["order"] == "hash" else ags.NATURAL, seed=args["seed"],
                                 oneWay=args["one_way"], levels=args["levels"], **nu)
             H.set_call = ("set_gauss_seidel", args)
@@ -385,7 +415,7 @@ class Generator:
             return self._cycle(H, n, f"{H.label}.set_block_width({H.width})", action, args=dict(width=H.width))
         if action == "apply":
             self.stats["hierarchy apply"] += 1
-            return self._cycle(H, n, f"{H.label}.apply, and a twin set up with the same settings", action, twin=not (H.kind == "strength" and H.refreshed))
+            return self._cycle(H, n, f"{H.label}.apply, and a twin set up with the same settings", action, twin=not (H.kind == "strength" and H.refreshed) and H.storage == "f64")
         k = int(rng.choice([1, 3, 16]))
         if k > H.width > 0 and rng.random() < 0.7:       # mostly a block the workspace takes
             k = H.width
@@ -395,7 +425,7 @@ class Generator:
             self.stats["hierarchy apply_block refused"] += 1
             return self._cycle(H, n, f"{H.label}.apply_block(k={k}) refused: {why}", "apply_block", R=R, Z=None)
         with np.errstate(all="ignore"):
-            Z = abr.block_cycle_ref(H.levels, H.o, R, H.sm)
+            Z = abr.block_cycle_ref(H.active(), H.o, R, H.sm)
         self.stats["hierarchy apply_block"] += 1
         return self._cycle(H, n, f"{H.label}.apply_block(k={k})", "apply_block", R=R, Z=Z)
 
@@ -414,7 +444,7 @@ class Generator:
             k = min(H.width, int(self.rng.choice([1, 3, 16])))
             rec["R"] = self.rng.standard_normal((n.M, k))
             with np.errstate(all="ignore"):
-                rec["Z"] = abr.block_cycle_ref(H.levels, H.o, rec["R"], H.sm)
+                rec["Z"] = abr.block_cycle_ref(H.active(), H.o, rec["R"], H.sm)
             self.stats["hierarchy apply_block"] += 1
             text += f"; apply_block(k={k})"
         return self._log("hierarchy", text, node=n.id, hier=H.id, action=action, r=r, z=z, **rec)
@@ -474,7 +504,7 @@ class Generator:
         srcs = params = None
         if kind == "permute":
             x = self.pick(self.live(square=True), deep)
-            srcs, params = (x.id,), dict(order=("natural", "hash")[int(rng.integers(2))], seed=int(rng.integers(1 << 16)))
+            srcs, params = (x.id,), self._permute_params(x)
         elif kind == "multiply":
             x = self.pick(live, deep)
             own = [t for t in live if t.kind == "transpose" and t.srcs == (x.id,)]
@@ -515,6 +545,13 @@ class Generator:
         text = f"{label} = {kind}({names}{self._show(kind, params)}): {n.M} x {n.N}, {n.JA.size} entries, depth {n.depth}"
         return self._log("derive", text, node=n.id, kind=kind, srcs=srcs, params=params)
 
+    def _permute_params(self, x):
+        return dict(order=("natural", "hash")[int(self.rng.integers(2))], seed=int(self.rng.integers(1 << 16)))
+
+    def _situations(self, c):
+        """further (name, holds) pairs of a node about to be refreshed, for the weights and the counts (a subclass's hook)"""
+        return []
+
     @staticmethod
     def _show(kind, p):
         if kind == "filter":
@@ -551,7 +588,7 @@ class Generator:
         # most of all in a situation this seed has not had yet for the node's kind
         def weight(c):
             here = [("source stale", any(self.stale(self.nodes[s]) for s in c.srcs)), ("two-phase built before", c.tiles is not None),
-                    ("stripes built before", bool(c.stripes)), ("SELL built before", c.sell)]
+                    ("stripes built before", bool(c.stripes)), ("SELL built before", c.sell)] + self._situations(c)
             return 0.2 + 0.5 / (1.0 + self.stats[f"refresh {c.kind}"]) + sum((1.0 + 2.0 * (what == "source stale")) / (1.0 + self.stats[f"refresh {c.kind}: {what}"]) for what, on in here if on)
         w = np.array([weight(c) for c in cand])
         n = cand[int(self.rng.choice(len(cand), p=w / w.sum()))]
@@ -576,6 +613,9 @@ class Generator:
             self.stats[f"refresh {k}: SELL built before"] += 1
         if n.factored:
             self.stats["ilu0, later a refresh of the node"] += 1
+        for what, on in self._situations(n):
+            if on:
+                self.stats[f"refresh {k}: {what}"] += 1
         n.params = params
         with np.errstate(all="ignore"):
             self._set(n, refresh_values(k, params, n.aux, [s.mat for s in S]))
